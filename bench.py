@@ -13,6 +13,10 @@ rbt_transcode_gof); --in-flight GOFs (default 16) are submitted ahead of the one
   python bench.py [--gpus N] [--steps K] [--warmup W] [--pc-frames F]          (N > 1 without a launcher: starts the N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
+A plain run sets up, warms up, times the K steps and prints the result line (headline, the K steps' kernel timings and roofline). --full also runs the
+informative legs after them (CPU baselines, sequence walk, rate fan-out, multi-GOF calls, in-flight sweep, steady state, quality, external tools).
+--dump-outputs DIR writes the last timed step's output sub-bitstreams as DIR/{occupancy,geometry,attribute}.npy (see dump_outputs).
+
 N > 1: weak scaling — every rank walks its own sequence of K GOFs (one process per GPU), the re-encoded NAL units of every GOF are
 gathered on rank 0 with RCCL inside the timed region. Extra legs: sequence_walk (configs[3]: 300 frames GOF-sharded, strong scaling,
 stitched output checked against the unsharded walk) and rate_fanout (configs[4]: R1..R5, one target rate per rank).
@@ -35,6 +39,21 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak (MI355X_MICROARCH.md)
 def make_gof_maps(w, h, n_pc, seed):
     import synth
     return synth.make_gof_maps(w, h, n_pc, seed)
+
+
+DUMP_BYTES = 60 * 10**6     # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(out_dir, outs):
+    """--dump-outputs: the sub-bitstreams one GOF's rbt_wait_gof returns (occupancy, geometry, attribute), one float32 array of byte values per stream.
+    Streams longer than DUMP_BYTES in all keep a fixed, seeded sample of their bytes (same positions in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {n: np.frombuffer(s_, np.uint8) for n, s_ in zip(("occupancy", "geometry", "attribute"), outs)}
+    total = sum(a.size for a in arrs.values())
+    for n, a in arrs.items():
+        if 4 * total > DUMP_BYTES:
+            a = a[np.sort(np.random.default_rng(1051).choice(a.size, a.size * DUMP_BYTES // (4 * total), replace=False))]
+        np.save(os.path.join(out_dir, n + ".npy"), a.astype(np.float32))
 
 
 def launch_ranks(n):
@@ -112,7 +131,12 @@ def main():
     ap.add_argument("--geometry-qp", type=int, default=24)
     ap.add_argument("--attribute-qp", type=int, default=32)
     ap.add_argument("--occupancy-precision", type=int, default=4)
+    ap.add_argument("--full", action="store_true", help="also run the informative legs after the timed steps (--cpu-sample, --multi-gof, --sweep, --steady-steps, --quality, "
+                    "--walk-frames, --fanout-gofs: off without --full) and probe for external HEVC tools")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step returned (one GOF's output sub-bitstreams) as DIR/<stream>.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.cpu_sample = args.multi_gof = args.sweep = args.steady_steps = args.quality = args.walk_frames = args.fanout_gofs = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -226,7 +250,7 @@ def main():
             host_t["submit"] += time.perf_counter() - c0
             if not arena_probe: arena_probe.append(ctx.job_memory(q[-1]) / sz)      # device memory one GOF of this workload holds while it is in flight (decoder + encoder arenas; rbt_job_memory), asked once
         while q: outs = collect(q.pop(0), acc)
-        return outs[:3] if outs else outs
+        return outs[-3:] if outs else outs          # the last step's GOF (the last one of the last job)
 
     def sync():
         if world > 1:
@@ -251,6 +275,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
     steps = args.steps
     fps = world * n_pc * steps / elapsed
     n_jobs = (steps + G - 1) // G                              # kernel timings are per job = per launch group (a job's launches cover its GOFs)
@@ -323,8 +349,8 @@ def main():
     # per GPU, re-encoded NAL units gathered on rank 0 (strong scaling: the sequence is fixed). Rank 0 then walks the whole sequence alone
     # and checks that the stitched output is identical.
     walk = None
-    ctx.trim()        # the legs below run other job shapes than the headline loop: its arenas (32 GOFs' worth) go back to the driver first
     if args.walk_frames > 0 and n_pc > 1:
+        ctx.trim()        # the legs below run other job shapes than the headline loop: its arenas (32 GOFs' worth) go back to the driver first
         seq = gs.make_sequence(streams, args.walk_frames, n_pc)
         WD = min(16, args.in_flight)
         gs.transcode_sequence(ctx, seq, params, rank=rank, world=world, depth=WD, device=tdev, gofs_per_job=0)          # untimed pass: arenas of this shape exist
@@ -406,8 +432,8 @@ def main():
     # configs[4]: every rate point R1..R5 from the R5 input, target rate i on rank i mod world (decode replicated; a rank that holds several
     # rates hands each GOF over once and the library decodes it once)
     fanout = None
-    ctx.trim()
     if args.fanout_gofs > 0:
+        ctx.trim()
         fseq = [streams] * args.fanout_gofs
         gs.transcode_fanout(ctx, R, fseq, rank=rank, world=world, depth=D, device=tdev, rows_per_slice=args.rows)      # untimed: same shape, so the timed pass allocates nothing
         sync()
@@ -430,8 +456,8 @@ def main():
     # informative extra (not the headline): G GOFs handed over in one call. One GOF's critical path is a few hundred serial
     # waves, so the GPU has room for several at once; a sequence of GOFs (configs[3]) can use that inside each GPU.
     multi = None
-    ctx.trim()
     if world == 1 and args.multi_gof > 1:
+        ctx.trim()
         MG = args.multi_gof
         ms, mp = [bytes(bytearray(s_)) for _ in range(MG) for s_ in streams], params * MG     # distinct buffers: identical ones would be decoded once
         ctx.transcode_gof(ms, mp)
@@ -443,8 +469,8 @@ def main():
 
     # informative extra: the same loop with ONE GOF per job at every depth (D = 1 is the blocking call: its ms_per_gof is the latency of one GOF)
     sweep = None
-    ctx.trim()
     if world == 1 and args.sweep > 1:
+        ctx.trim()
         sweep = []
         for d in (1, 2, 4, 8, 16):
             ctx.set_depth(d)
@@ -457,8 +483,8 @@ def main():
         ctx.set_depth(D)
     # the headline of a short run (the driver's --steps 20) is all ramp-up and drain: the steady state of a long walk beside it (the same job shape rule as a 256-step run)
     steady = None
-    ctx.trim()
     if world == 1 and args.steady_steps > 0 and args.steps < args.steady_steps:
+        ctx.trim()
         g_s = gs.job_shape(args.steady_steps)[0]; d_s = max(1, min(args.in_flight, 16, (args.steady_steps + g_s - 1) // g_s))
         ctx.set_depth(d_s)
         run(d_s * g_s, d_s, None, g_s)
@@ -469,8 +495,8 @@ def main():
     # informative: what the re-encode did to the pictures (luma PSNR of the R3 output's pictures against the R5 input's,
     # both decoded by this library), and that the occupancy output is exactly the 2x2 OR-pool of the input occupancy
     quality = None
-    ctx.trim()        # every leg above ran another job shape and left its arenas cached
     if rank == 0 and world == 1 and args.quality:
+        ctx.trim()        # every leg above ran another job shape and left its arenas cached
         def psnr_y(a_stream, b_stream, ww, hh, peak):
             da, db = ctx.decode(a_stream)[0], ctx.decode(b_stream)[0]
             ya, yb = da[:, :ww * hh].astype(np.float64), db[:, :ww * hh].astype(np.float64)
@@ -656,7 +682,7 @@ def main():
 
     if rank == 0:
         import external_tools
-        ext = external_tools.describe()
+        ext = external_tools.describe() if args.full else {"external_decoder": None, "libx265": None}
         line = {"metric": "transcoded point-cloud frames/sec, R5->R3", "value": round(fps, 3), "unit": "point-cloud frames/s", "n_gpus": world,
                 "steps": steps, "warmup": args.warmup, "ms_per_step": round(1000 * elapsed / steps, 3), "higher_is_better": True, "scaling": "weak",
                 "vs_baseline": None, "dtype": "u16/i32", "data": "synthetic",

@@ -2,6 +2,8 @@
 all-intra, 16 for I,P pairs), padded by repetition, and the padding is signalled as the conformance window (7.4.3.2.1),
 which is what libx265 does behind PCCTranscoder.cpp:706. Real atlases hit this: a 1280x1296 atlas has a 640x648 occupancy
 map whose 2x2 pool is 320x324. Host emulation here (CPU), the same cases on the GPU in test_gpu_transcode.py."""
+import os
+import subprocess
 import numpy as np
 import pytest
 import oracle_lib as O
@@ -39,6 +41,7 @@ def cases(ctx, R):
 
 
 def test_conformance_window_hostemu():
+    subprocess.check_call(["make", "-s", "-C", os.path.join(os.path.dirname(__file__), "hostemu")])
     R = rbt_lib.module()
     c = R.Context(lib_path=rbt_lib.HOSTEMU_LIB)
     try: cases(c, R)

@@ -11,8 +11,12 @@ import synth
 
 
 @pytest.fixture(scope="module")
-def ctx():
+def hostemu():
     subprocess.check_call(["make", "-s", "-C", os.path.join(os.path.dirname(__file__), "hostemu")])
+
+
+@pytest.fixture(scope="module")
+def ctx(hostemu):
     R = rbt_lib.module()
     c = R.Context(lib_path=rbt_lib.HOSTEMU_LIB)
     yield c
@@ -88,7 +92,7 @@ def test_transcode_rejects_damaged_input(ctx):
     assert caught >= 4
 
 
-def test_banded_parse_is_bit_identical(monkeypatch):
+def test_banded_parse_is_bit_identical(monkeypatch, hostemu):
     """RBT_PARSE_BANDS: the resumable parser (suspend in front of a CTB row, resume in a later launch) gives the same streams"""
     import subprocess, sys, os
     code = ("import sys; sys.path.insert(0, 'tests'); import rbt_lib, synth, oracle_lib as O\n"
@@ -398,7 +402,7 @@ def test_slice_segments_must_tile_the_picture(ctx):
 
 
 @pytest.mark.parametrize("mode", ["RBT_RECON_QUEUE", "RBT_RECON_LEVEL", "RBT_RECON_DIAG"])
-def test_every_reconstruction_mode_gives_the_same_pictures(mode):
+def test_every_reconstruction_mode_gives_the_same_pictures(mode, hostemu):
     """the three ways a dependency level is launched (one launch per anti-diagonal; one per level with neighbour flags; one per level with a ready queue, round 4): the host
     build walks each one's order serially - the ready queue by the kernel's own rules (rc_ctb_successors / rc_ctb_need, first in first out) - and all must reproduce the
     oracle. The mode is read once per process, hence the child process (tests/recon_mode_worker.py); the GPU run of the same cases: tests/test_gpu_decode.py"""

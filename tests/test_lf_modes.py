@@ -18,6 +18,7 @@ def run(kind, dec, enc):
 
 @pytest.mark.parametrize("dec,enc", MODES)
 def test_loop_filter_modes_host_build(dec, enc):
+    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "hostemu")])
     run("hostemu", dec, enc)
 
 

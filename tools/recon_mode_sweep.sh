@@ -2,7 +2,7 @@
 # Reconstruction per level: per-diagonal launches / neighbour flags (the round-3 rule by depth) against the ready-queue launch at several widths.
 # Same bench command each time (driver's command + the 256-step steady state), interleaved repeats. Output: gpurun_out/recon_mode_sweep.txt
 out=gpurun_out/recon_mode_sweep.txt; : > $out
-B="python bench.py --steps 20 --warmup 5 --cpu-sample 0 --quality 0 --walk-frames 0 --fanout-gofs 0 --multi-gof 0 --sweep 0"
+B="python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --quality 0 --walk-frames 0 --fanout-gofs 0 --multi-gof 0 --sweep 0"
 run() { # label, env...
   label=$1; shift
   line=$(env "$@" timeout -k 10 500 $B 2>/dev/null | tail -1)

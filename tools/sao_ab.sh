@@ -1,7 +1,7 @@
 #!/bin/bash
 # SAO by CTB (round 4) against the per-sample kernel: the same bench command, interleaved. Output: gpurun_out/sao_ab.txt
 out=gpurun_out/sao_ab.txt; : > $out
-B="python bench.py --steps 20 --warmup 5 --cpu-sample 0 --quality 0 --walk-frames 0 --fanout-gofs 0 --multi-gof 0 --sweep 0"
+B="python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --quality 0 --walk-frames 0 --fanout-gofs 0 --multi-gof 0 --sweep 0"
 run() { label=$1; shift
   line=$(env "$@" timeout -k 10 500 $B 2>/dev/null | tail -1)
   python - "$label" "$line" >> $out <<'PY'
