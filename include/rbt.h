@@ -45,8 +45,10 @@ typedef struct {
                               * picture coded as one dependent slice segment per CTB row with entropy_coding_sync (rows predict from each other and inherit
                               * context variables: ~11 % fewer bytes than 1 at the same PSNR; what the CTC rate points use, gof_shard.DEFAULT_ROWS).
                               * All streams of one call must agree on wavefront mode or not. */
-  int md5_sei;               /* emit decoded-picture-hash SEI in the output (the reconstructed pictures come to the host and are hashed on its cores: +35 % on a blocking GOF) */
-  int verify_md5;            /* check the input stream's MD5 SEI (a device-to-host copy of every picture, hashed on the host's cores: +25 % on a blocking GOF) */
+  int md5_sei;               /* RBT_HASH_*: kind of decoded picture hash SEI written behind every output picture (0 = none; 1 = MD5, as before). Hashed on the GPU from the
+                              * encoder's reconstruction; values above RBT_HASH_CHECKSUM: RBT_ERR_PARAM */
+  int verify_md5;            /* check the input stream's decoded picture hash SEIs, whichever kind each picture carries (MD5, CRC or checksum), on the GPU after the
+                              * decoder's last filter: a mismatch fails the call with RBT_ERR_MD5 (rbt_last_error names the input) and no output */
   int occupancy_rd;          /* geometry / attribute streams handed to rbt_transcode_gof / rbt_submit_gof behind an occupancy stream that is transcoded in the same call
                               * (occupancy_precision 4): occupancy-aware coding (what dependencies/hm-modification/HM-16.20+SCM-8.8_with_RDO.patch does to
                               * HM's distortion, TComRdCost.cpp xGetSSE*). The occupancy map the output carries tells which 4x4 units the decoder makes points of; with one unit
@@ -64,10 +66,13 @@ typedef struct {
 } rbt_stream_params;
 enum { RBT_PRESET_DEFAULT = 0, RBT_PRESET_FAST = 1 };
 
+/* Kinds of decoded picture hash (H.265 D.3.19), numbered as HM's SEIDecodedPictureHash and x265's --hash: the SEI's hash_type is kind - 1 */
+enum { RBT_HASH_NONE = 0, RBT_HASH_MD5 = 1, RBT_HASH_CRC = 2, RBT_HASH_CHECKSUM = 3 };
+
 typedef struct {             /* decoded video returned by rbt_decode (host memory, rbt_free) */
   int width, height, bit_depth, n_frames;
   uint16_t* data;            /* n_frames x planar 4:2:0: Y (w*h), Cb, Cr */
-  int md5_checked, md5_failed;
+  int md5_checked, md5_failed;   /* with verify_md5: pictures whose decoded picture hash SEI was checked / did not match, of any kind (MD5, CRC, checksum) */
 } rbt_video;
 
 typedef struct {             /* timings of the last call, milliseconds */
@@ -152,10 +157,14 @@ int rbt_trim(rbt_ctx* ctx);
  * conformance window in the SPS (as libx265 does for the reference); rbt_decode returns the cropped pictures. */
 int rbt_decode(rbt_ctx* ctx, const uint8_t* annexb, size_t n, int verify_md5, rbt_video* out);
 int rbt_encode(rbt_ctx* ctx, const uint16_t* yuv, int width, int height, int bit_depth, int n_frames, int qp, int gop, int lossless,
-               int log2_ctb, int ctb_rows_per_slice, int md5_sei, uint8_t** annexb_out, size_t* n_out);
+               int log2_ctb, int ctb_rows_per_slice, int md5_sei, uint8_t** annexb_out, size_t* n_out);   /* md5_sei: RBT_HASH_* */
 
 /* resize_frame2 (PCCTranscoder.cpp:594-646) on a host plane (tests): out[v][u] = any(in block > 0) */
 int rbt_or_pool(rbt_ctx* ctx, const uint16_t* plane, int width, int height, int factor, uint16_t* out);
+/* Decoded picture hash (RBT_HASH_MD5 / _CRC / _CHECKSUM) of n_frames host pictures (planar 4:2:0, width x height luma, even sizes, bit depth 8..16), computed by the
+ * device kernels the transcoder uses: out gets 48 bytes per picture, 16 per component in SEI byte order (MD5 digest; CRC 2 bytes, checksum 4 bytes, most significant
+ * first), zero-padded. */
+int rbt_picture_hash(rbt_ctx* ctx, const uint16_t* yuv, int width, int height, int bit_depth, int n_frames, int kind, uint8_t* out);
 
 /* PCCVideoBitstream::sampleStreamToByteStream / byteStreamToSampleStream (PCCVideoBitstream.cpp:85-172), host side */
 int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t* n_out);
@@ -263,7 +272,7 @@ typedef struct {
   int occupancy_precision;   /* occupancyPrecision_: the occupancy video is transcoded (2x2 OR-pool, lossless) only when 4 (PCCTranscoder.cpp:150) */
   int geometry_qp, attribute_qp;                      /* geometryQP_, attributeQP_ */
   int forced_unit_size_precision_bytes;               /* forcedSsvhUnitSizePrecisionBytes_, 0 = none */
-  int log2_ctb, ctb_rows_per_slice, md5_sei, verify_md5;   /* as in rbt_stream_params */
+  int log2_ctb, ctb_rows_per_slice, md5_sei, verify_md5;   /* as in rbt_stream_params; md5_sei: RBT_HASH_* */
   int gofs_per_job;          /* GOFs handed to the GPU per job; 0 = by rbt_job_shape from the number of GOFs this context owns, which also lowers the announced depth for
                               * the duration of the call when the walk is short (the depth announced with rbt_set_depth is the cap and is restored) */
   int occupancy_rd;          /* occupancy-aware coding of the geometry / attribute units of every GOF (rbt_stream_params.occupancy_rd): with the occupancy map that GOF's

@@ -12,6 +12,7 @@ _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RBT_LIB_PATH") or os.path.join(_DIR, "librbt.so")   # RBT_LIB_PATH: another build of the same library (experiments)
 
 RBT_VIDEO_OCCUPANCY, RBT_VIDEO_GEOMETRY, RBT_VIDEO_ATTRIBUTE = 0, 1, 19
+RBT_HASH_NONE, RBT_HASH_MD5, RBT_HASH_CRC, RBT_HASH_CHECKSUM = 0, 1, 2, 3   # md5_sei: kind of decoded picture hash SEI (HM / x265 numbering)
 
 
 class RbtError(RuntimeError):
@@ -120,6 +121,7 @@ def load(path=None):
     L.rbt_preset_from_name.argtypes = [C.c_char_p]
     L.rbt_wait_gof.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_or_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.rbt_picture_hash.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
     L.rbt_sample_to_byte_stream.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_byte_to_sample_stream.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
@@ -349,6 +351,14 @@ class Context:
         h, w = plane.shape
         out = np.zeros((h // factor, w // factor), np.uint16)
         self._chk(self.L.rbt_or_pool(self.h, plane.ctypes.data, w, h, factor, out.ctypes.data))
+        return out
+
+    def picture_hash(self, frames, w, h, bit_depth, kind=RBT_HASH_MD5):
+        """rbt_picture_hash: decoded picture hash of planar 4:2:0 pictures ([n, w*h*3/2] uint16) -> uint8 [n, 3, 16], per component in SEI byte order
+        (MD5: 16 bytes; CRC: 2, checksum: 4, most significant first; zero-padded)"""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16).reshape(-1, w * h * 3 // 2)
+        out = np.zeros((frames.shape[0], 3, 16), np.uint8)
+        self._chk(self.L.rbt_picture_hash(self.h, frames.ctypes.data, w, h, bit_depth, frames.shape[0], kind, out.ctypes.data))
         return out
 
     def reconstruct(self, atlas, patches, occ, d0, d1, geo_bd=10, t0=None, t1=None, attr_bd=10):

@@ -20,7 +20,7 @@ static DevState g_dev[16];
 static_assert(RBT_MAX_JOBS == rbtk::RBT_JOB_SLOTS, "job slots");
 // every context entry point starts with an empty error text (rbt_last_error describes the LAST call; the pointer it returns is valid until the next call on the context)
 #define RBT_ENTER(ctx) DevState& D = g_dev[(ctx)->device]; std::lock_guard<std::mutex> lk(D.mu); (ctx)->last_err.clear(); if (rbtk::dev_select((ctx)->device)) return RBT_ERR_NO_DEVICE
-// no exception crosses the C ABI: allocation failures of the host side (std::vector, std::string, the hashing threads) come back as error codes
+// no exception crosses the C ABI: allocation failures of the host side (std::vector, std::string) come back as error codes
 #define RBT_CATCH catch (const std::bad_alloc&) { return RBT_ERR_NOMEM; } catch (...) { return RBT_ERR_NO_DEVICE; }
 
 extern "C" {
@@ -77,8 +77,11 @@ int rbt_decode(rbt_ctx* ctx, const uint8_t* annexb, size_t n, int verify_md5, rb
   memset(out, 0, sizeof(*out));
   rbt::DecodeBatch b; rbt::StreamIn in{annexb, n};
   int rc = rbt::decode_build(b, &in, 1);
+  if (!rc && verify_md5) rc = rbt::decode_hash_setup(b, std::vector<char>(1, 1));   // the pictures' hashes on the GPU, behind the decoder's last filter
   if (!rc) rc = rbt::decode_run(b);
-  if (!rc) rc = rbt::decode_fetch(b, 0, out, verify_md5 != 0);
+  if (!rc && !b.hash.empty()) { rbt::decode_launch_hash(b); if (b.hash.fetch()) { b.err = "device transfer failed"; rc = RBT_ERR_NO_DEVICE; } }
+  if (!rc) rc = rbt::decode_fetch(b, 0, out);
+  if (!rc && verify_md5) rbt::decode_hash_result(b, 0, out->md5_checked, out->md5_failed);
   if (rc) { ctx->last_err = b.err; free(out->data); memset(out, 0, sizeof(*out)); return rc; }
   ctx->stats.k_parse_ms = rbtk::timer_ms(rbt::T_PARSE); ctx->stats.k_recon_ms = rbtk::timer_ms(rbt::T_RECON);
   if (verify_md5 && out->md5_failed) return RBT_ERR_MD5;
@@ -153,6 +156,7 @@ static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const si
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
+  for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
   rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule), ctx};
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
@@ -231,6 +235,12 @@ int rbt_or_pool(rbt_ctx* ctx, const uint16_t* plane, int width, int height, int 
   if (!ctx || !plane || !out || factor < 1 || width % factor || height % factor) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   return rbt::or_pool_host(plane, width, height, factor, out);
+} RBT_CATCH
+
+int rbt_picture_hash(rbt_ctx* ctx, const uint16_t* yuv, int width, int height, int bit_depth, int n_frames, int kind, uint8_t* out) try {
+  if (!ctx || !yuv || !out || n_frames < 1) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  return rbt::picture_hash_host(ctx->last_err, yuv, width, height, bit_depth, n_frames, kind, out);
 } RBT_CATCH
 
 int rbt_selftest_transform32(rbt_ctx* ctx, const int16_t* blocks, int n_blocks, int bit_depth, uint32_t* n_mismatch) try {

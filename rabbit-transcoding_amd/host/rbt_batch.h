@@ -7,12 +7,31 @@
 #include <vector>
 #include "../../include/rbt.h"
 #include "../csrc/rbt_kernels.h"
+#include "../csrc/rbt_hash.h"
 #include "rbt_hls.h"
 
 namespace rbt {
 
 struct StreamIn { const uint8_t* p; size_t n; };
-struct FrameInfo { int stream; int nal_type; bool has_md5; uint8_t md5[3][16]; bool sao; };
+struct FrameInfo { int stream; int nal_type; int hash_kind; uint8_t hash[48]; bool sao; };   // hash_kind: RBT_HASH_* of the picture's hash SEI (0: none), hash: parse_hash_sei
+
+// Decoded picture hashes of pictures in device memory (csrc/rbt_hash.h). add() the pictures, upload() before the first kernel of the stream
+// (one copy: the picture table, the per-class lists and the zeroed state, results and counters), launch() behind the kernels that make the
+// pictures, fetch() once the stream has got there: 48 bytes per picture and one mismatch count per counter come back.
+struct HashSet {
+  std::vector<RbtHashPic> pics; int n_counters = 0;
+  std::vector<uint8_t> staging;                  // the upload, alive until it has completed
+  uint8_t* d = nullptr; size_t o_lists = 0, o_state = 0, o_out = 0, o_end = 0;
+  int n_class[6] = {}, class_off[6] = {}, class_luma[6] = {}, class_h[6] = {};   // class = (kind - 1) * 2 + (bit depth > 8)
+  std::vector<uint8_t> out; std::vector<uint32_t> counters;
+  int add(const uint16_t* const planes[3], int w, int h, int bit_depth, int kind, int counter = -1, const uint8_t* want = nullptr);   // index of the picture, < 0: refused
+  bool empty() const { return pics.empty(); }
+  int upload();
+  void launch() const;
+  int fetch();
+  ~HashSet() { rbtk::dev_free(d); }
+};
+
 
 enum { T_PARSE = 0, T_RECON = 1, T_FILTER = 2, T_ANALYSE = 3, T_ENCODE = 4, T_ENTROPY = 5, T_ALL = 6, T_POOL = 7, T_INTER = 8, T_ENTROPY_I = 9, T_COUNT = 10 };
 
@@ -43,6 +62,7 @@ struct DecodeBatch {
   bool want_save = false;              // set before decode_build to reserve d_save
   void* arena = nullptr; size_t arena_size = 0;
   RbtFrame* d_frames = nullptr; RbtSlice* d_slices = nullptr; uint8_t* d_rbsp = nullptr; int32_t* d_lists = nullptr;
+  HashSet hash; std::vector<int> hash_checked;   // verify_md5: the pictures of the checked streams (counter = stream), pictures checked per stream
   std::string err; int err_code = 0;
   ~DecodeBatch() { rbtk::dev_free(arena); }
 };
@@ -63,7 +83,12 @@ void decode_launch_level(DecodeBatch& b, size_t l);  // reconstruction + loop fi
 void decode_launch_filters(DecodeBatch& b, size_t l); // loop filters of level l only
 int decode_finish(DecodeBatch& b);   // wait for the batch's stream and check the per-picture error words
 int decode_run(DecodeBatch& b);      // launch + finish
-int decode_fetch(DecodeBatch& b, int stream, rbt_video* out, bool verify_md5);
+// verify_md5: every picture of the streams with verify[stream] that carries a hash SEI goes into b.hash (uploaded on the current stream); decode_launch_hash
+// enqueues the hashing behind the decoder's last filter, decode_hash_result reads what came back (after hash.fetch()) for one stream
+int decode_hash_setup(DecodeBatch& b, const std::vector<char>& verify);
+void decode_launch_hash(const DecodeBatch& b);
+void decode_hash_result(const DecodeBatch& b, int stream, int& checked, int& failed);
+int decode_fetch(DecodeBatch& b, int stream, rbt_video* out);   // the stream's cropped pictures to the host
 
 size_t frame_samples(const RbtStreamCfg& c);
 

@@ -27,7 +27,7 @@ int decode_build(DecodeBatch& b, const StreamIn* streams, int n_streams) {
       const uint8_t* r = b.rbsp.data() + nal.rbsp_off; int rc = 0;
       if (nal.type == NAL_SPS) rc = parse_sps(*ps, r, nal.rbsp_size, b.err);
       else if (nal.type == NAL_PPS) rc = parse_pps(*ps, r, nal.rbsp_size, b.err);
-      else if (nal.type == NAL_SEI_SUFFIX) { if (cur >= 0) { FrameInfo& fi = b.info[cur]; if (parse_md5_sei(r, nal.rbsp_size, fi.md5)) fi.has_md5 = true; } }
+      else if (nal.type == NAL_SEI_SUFFIX) { if (cur >= 0) { FrameInfo& fi = b.info[cur]; uint8_t hh[48]; if (int k = parse_hash_sei(r, nal.rbsp_size, hh)) { fi.hash_kind = k; memcpy(fi.hash, hh, 48); } } }
       else if (nal.type <= NAL_TRAIL_R || (nal.type >= 16 && nal.type <= 21)) {
         SliceHdr h; rc = parse_slice_header(*ps, r, nal.rbsp_size, nal.type, h, b.err, head_idx >= 0 ? &head_hdr : nullptr);
         if (rc) { delete ps; b.err_code = rc == -3 ? RBT_ERR_UNSUPPORTED : RBT_ERR_BITSTREAM; return b.err_code; }
@@ -352,12 +352,12 @@ int decode_finish(DecodeBatch& b) {
   return 0;
 }
 
-int decode_fetch(DecodeBatch& b, int stream, rbt_video* out, bool verify_md5) {
+int decode_fetch(DecodeBatch& b, int stream, rbt_video* out) {
   memset(out, 0, sizeof(*out));
   int first = b.stream_first[stream], n = b.stream_count[stream];
   if (n <= 0) return RBT_ERR_BITSTREAM;
   const RbtStreamCfg& c = b.frames[first].cfg; const Sps& sps = b.stream_sps[stream];
-  // output = coded picture minus the conformance window (7.4.3.2.1); the picture hash covers the whole coded picture
+  // output = coded picture minus the conformance window (7.4.3.2.1)
   const int cl = 2 * sps.conf_win[0], ct = 2 * sps.conf_win[2], dw = c.w - cl - 2 * sps.conf_win[1], dh = c.h - ct - 2 * sps.conf_win[3];
   if (dw <= 0 || dh <= 0) return RBT_ERR_BITSTREAM;
   const bool crop = dw != c.w || dh != c.h;
@@ -365,33 +365,82 @@ int decode_fetch(DecodeBatch& b, int stream, rbt_video* out, bool verify_md5) {
   out->width = dw; out->height = dh; out->bit_depth = c.bit_depth; out->n_frames = n;
   out->data = (uint16_t*)malloc(ofs * 2 * (size_t)n);
   if (!out->data) return RBT_ERR_NOMEM;
-  // with a conformance window the whole coded pictures are kept next to the cropped output while their hashes are checked (all planes side by side, md5_planes_u16)
-  const bool keep = crop && verify_md5;
-  std::vector<uint16_t> full(crop ? (keep ? fs * (size_t)n : fs) : 0);
-  std::vector<Md5PlaneJob> jobs; std::vector<uint8_t> hashes((size_t)n * 48);
+  std::vector<uint16_t> full(crop ? fs : 0);
   for (int i = 0; i < n; i++) {
     const RbtFrame& f = b.frames[first + i];
     uint16_t* dst = out->data + ofs * (size_t)i;
-    uint16_t* p = crop ? full.data() + (keep ? fs * (size_t)i : 0) : dst;
+    uint16_t* p = crop ? full.data() : dst;
     if (rbtk::d2h(p, f.out[0], fs * 2)) return RBT_ERR_NO_DEVICE;
-    if (verify_md5 && b.info[first + i].has_md5) {
-      jobs.push_back({p, c.w, c.h, c.bit_depth, &hashes[(size_t)i * 48]});
-      jobs.push_back({p + (size_t)c.w * c.h, c.cw, c.ch, c.bit_depth, &hashes[(size_t)i * 48 + 16]});
-      jobs.push_back({p + (size_t)c.w * c.h + (size_t)c.cw * c.ch, c.cw, c.ch, c.bit_depth, &hashes[(size_t)i * 48 + 32]});
-    }
     if (crop) {
-      const uint16_t* full_i = p;
-      const uint16_t* src = full_i; uint16_t* d = dst;
+      const uint16_t* src = p; uint16_t* d = dst;
       for (int k = 0; k < 3; k++) { const int sh = k ? 1 : 0, pw = c.w >> sh, ph = c.h >> sh, ow = dw >> sh, oh = dh >> sh;
         for (int y = 0; y < oh; y++) memcpy(d + (size_t)y * ow, src + (size_t)(y + (ct >> sh)) * pw + (cl >> sh), (size_t)ow * 2);
         src += (size_t)pw * ph; d += (size_t)ow * oh; }
     }
   }
-  md5_planes_u16(jobs.data(), jobs.size());
-  for (int i = 0; i < n; i++) if (verify_md5 && b.info[first + i].has_md5) {
-    out->md5_checked++;
-    if (memcmp(&hashes[(size_t)i * 48], b.info[first + i].md5[0], 16) || memcmp(&hashes[(size_t)i * 48 + 16], b.info[first + i].md5[1], 16) || memcmp(&hashes[(size_t)i * 48 + 32], b.info[first + i].md5[2], 16)) out->md5_failed++;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ decoded picture hashes (verify_md5)
+// The hash covers the whole coded picture (the decoder's out planes), whichever kind the picture's SEI names.
+int decode_hash_setup(DecodeBatch& b, const std::vector<char>& verify) {
+  const int ns = (int)b.stream_first.size();
+  b.hash_checked.assign(ns, 0); b.hash.n_counters = ns;
+  for (int si = 0; si < ns && si < (int)verify.size(); si++) if (verify[si])
+    for (int k = 0; k < b.stream_count[si]; k++) {
+      const int fi = b.stream_first[si] + k; const FrameInfo& in = b.info[fi]; const RbtFrame& f = b.frames[fi];
+      if (!in.hash_kind) continue;
+      if (b.hash.add(f.out, f.cfg.w, f.cfg.h, f.cfg.bit_depth, in.hash_kind, si, in.hash) < 0) { b.err = "picture cannot be hashed"; return b.err_code = RBT_ERR_UNSUPPORTED; }
+      b.hash_checked[si]++;
+    }
+  if (b.hash.empty()) return 0;
+  if (b.hash.upload()) { b.err = "device allocation failed"; return b.err_code = RBT_ERR_NOMEM; }
+  return 0;
+}
+void decode_launch_hash(const DecodeBatch& b) { if (!b.hash.empty()) b.hash.launch(); }
+void decode_hash_result(const DecodeBatch& b, int stream, int& checked, int& failed) {
+  checked = stream < (int)b.hash_checked.size() ? b.hash_checked[stream] : 0;
+  failed = checked && stream < (int)b.hash.counters.size() ? (int)b.hash.counters[stream] : 0;
+}
+
+static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+int HashSet::add(const uint16_t* const planes[3], int w, int h, int bit_depth, int kind, int counter, const uint8_t* want) {
+  if (kind < RBT_HASH_MD5 || kind > RBT_HASH_CHECKSUM || w <= 0 || h <= 0 || (w | h) & 1 || bit_depth < 8 || bit_depth > 16 || (int)pics.size() >= RBT_HASH_MAX_PICS) return -1;
+  RbtHashPic P; memset(&P, 0, sizeof(P));
+  for (int c = 0; c < 3; c++) { if ((uintptr_t)planes[c] & 15) return -1; P.plane[c] = planes[c]; }   // the kernels read 16 bytes at a time
+  P.w = w; P.h = h; P.bit_depth = bit_depth; P.kind = kind; P.counter = want ? counter : -1;
+  if (want) memcpy(P.want, want, 48);
+  pics.push_back(P);
+  return (int)pics.size() - 1;
+}
+int HashSet::upload() {
+  const size_t n = pics.size();
+  std::vector<int32_t> lists;
+  for (int cl = 0; cl < 6; cl++) {
+    class_off[cl] = (int)lists.size(); n_class[cl] = 0; class_luma[cl] = 0; class_h[cl] = 0;
+    for (size_t i = 0; i < n; i++) if ((pics[i].kind - 1) * 2 + (pics[i].bit_depth > 8) == cl) {
+      lists.push_back((int32_t)i); n_class[cl]++; class_luma[cl] = std::max(class_luma[cl], pics[i].w * pics[i].h); class_h[cl] = std::max(class_h[cl], pics[i].h); }
   }
+  o_lists = align16(n * sizeof(RbtHashPic)); o_state = align16(o_lists + n * 4); o_out = align16(o_state + n * RBT_HASH_STATE_WORDS * 4);
+  o_end = o_out + n * 48 + (size_t)n_counters * 4;
+  staging.assign(o_end, 0);
+  memcpy(staging.data(), pics.data(), n * sizeof(RbtHashPic)); memcpy(staging.data() + o_lists, lists.data(), n * 4);
+  rbtk::dev_free(d);
+  d = (uint8_t*)rbtk::dev_alloc(o_end);
+  if (!d) return RBT_ERR_NOMEM;
+  return rbtk::h2d(d, staging.data(), o_end) ? RBT_ERR_NO_DEVICE : 0;
+}
+void HashSet::launch() const {
+  const RbtHashPic* dp = (const RbtHashPic*)d; uint32_t* state = (uint32_t*)(d + o_state);
+  for (int cl = 0; cl < 6; cl++) rbtk::launch_hash(dp, (const int32_t*)(d + o_lists) + class_off[cl], n_class[cl], cl / 2 + 1, cl & 1, class_luma[cl], class_h[cl], state);
+  rbtk::launch_hash_finish(dp, (int)pics.size(), state, d + o_out, (uint32_t*)(d + o_out + pics.size() * 48));
+}
+int HashSet::fetch() {
+  const size_t n = pics.size();
+  std::vector<uint8_t> h(o_end - o_out);
+  if (rbtk::d2h(h.data(), d + o_out, h.size())) return RBT_ERR_NO_DEVICE;
+  out.assign(h.begin(), h.begin() + n * 48);
+  counters.assign((size_t)n_counters, 0); if (n_counters) memcpy(counters.data(), h.data() + n * 48, (size_t)n_counters * 4);
   return 0;
 }
 

@@ -1,10 +1,7 @@
-// See rbt_hls.h. H.265 7.3.1.1 (NAL), 7.3.2.x (parameter sets), 7.3.6 (slice segment header), D.2.19 (picture hash).
+// See rbt_hls.h. H.265 7.3.1.1 (NAL), 7.3.2.x (parameter sets), 7.3.6 (slice segment header), D.2.20 (decoded picture hash SEI).
 #include <cstring>
 #include "rbt_hls.h"
-#include <cmath>
 #include <algorithm>
-#include <atomic>
-#include <thread>
 
 namespace rbt {
 
@@ -242,18 +239,35 @@ int parse_slice_header(ParamSets& ps, const uint8_t* rbsp, size_t n, int nal_typ
   return 0;
 }
 
-bool parse_md5_sei(const uint8_t* rbsp, size_t n, uint8_t md5[3][16]) {
+int parse_hash_sei(const uint8_t* rbsp, size_t n, uint8_t hash[48]) {
   size_t p = 2;
   while (p + 2 <= n) {
     int type = 0, size = 0;
-    while (p < n && rbsp[p] == 0xFF) { type += 255; p++; } if (p >= n) return false; type += rbsp[p++];
-    while (p < n && rbsp[p] == 0xFF) { size += 255; p++; } if (p >= n) return false; size += rbsp[p++];
-    if (p + size > n) return false;
-    if (type == 132 && size >= 49 && rbsp[p] == 0) { for (int c = 0; c < 3; c++) memcpy(md5[c], rbsp + p + 1 + 16 * c, 16); return true; }
+    while (p < n && rbsp[p] == 0xFF) { type += 255; p++; } if (p >= n) return 0; type += rbsp[p++];
+    while (p < n && rbsp[p] == 0xFF) { size += 255; p++; } if (p >= n) return 0; size += rbsp[p++];
+    if (p + size > n) return 0;
+    // decoded_picture_hash (D.2.20): hash_type 0 / 1 / 2, then per component 16 bytes of MD5, a u(16) CRC or a u(32) checksum
+    if (type == 132 && size >= 1 && rbsp[p] <= 2) {
+      const int kind = rbsp[p] + 1, nb = hash_bytes(kind);
+      if (size >= 1 + 3 * nb) {
+        memset(hash, 0, 48);
+        for (int c = 0; c < 3; c++) memcpy(hash + 16 * c, rbsp + p + 1 + nb * c, (size_t)nb);
+        return kind;
+      }
+    }
     p += size;
     if (p < n && rbsp[p] == 0x80) break;
   }
-  return false;
+  return 0;
+}
+int hash_bytes(int kind) { return kind == RBT_HASH_MD5 ? 16 : kind == RBT_HASH_CRC ? 2 : kind == RBT_HASH_CHECKSUM ? 4 : 0; }
+void append_hash_sei(std::vector<uint8_t>& out, int kind, const uint8_t hash[48]) {
+  const int nb = hash_bytes(kind);
+  uint8_t sei[3 + 48 + 1]; size_t k = 0;
+  sei[k++] = 132; sei[k++] = (uint8_t)(1 + 3 * nb); sei[k++] = (uint8_t)(kind - 1);
+  for (int c = 0; c < 3; c++) for (int i = 0; i < nb; i++) sei[k++] = hash[16 * c + i];
+  sei[k++] = 0x80;
+  append_nal(out, NAL_SEI_SUFFIX, sei, k, false);
 }
 
 void fill_stream_cfg(const Sps& s, const Pps& p, RbtStreamCfg& c) {
@@ -367,61 +381,6 @@ void write_slice_header(BitWriter& w, const Sps& s, const Pps& p, const SliceHdr
   if (p.loop_filter_across_slices && (h.sao_luma || h.sao_chroma || !h.deblocking_disabled)) w.bit(h.lf_across);
   if (p.entropy_coding_sync) w.ue(0);   // num_entry_point_offsets
   w.bit(1); w.align_zero();
-}
-
-// ------------------------------------------------------------------------------------------------ MD5 (RFC 1321)
-namespace {
-struct Md5 {
-  uint32_t a = 0x67452301u, b = 0xefcdab89u, c = 0x98badcfeu, d = 0x10325476u; uint64_t len = 0; uint8_t buf[64]; int nbuf = 0;
-  static const uint32_t* K() { static uint32_t k[64]; static bool init = false; if (!init) { for (int i = 0; i < 64; i++) k[i] = (uint32_t)std::floor(std::fabs(std::sin((double)(i + 1))) * 4294967296.0); init = true; } return k; }
-  void block(const uint8_t* p) {
-    static const uint8_t S[64] = {7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22, 5, 9, 14, 20, 5, 9, 14, 20, 5, 9, 14, 20, 5, 9, 14, 20,
-                                  4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23, 6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21};
-    const uint32_t* Kt = K(); uint32_t M[16];
-    for (int i = 0; i < 16; i++) M[i] = p[4 * i] | (p[4 * i + 1] << 8) | (p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
-    uint32_t A = a, B = b, C = c, D = d;
-    for (int i = 0; i < 64; i++) {
-      uint32_t F; int g;
-      if (i < 16) { F = (B & C) | (~B & D); g = i; } else if (i < 32) { F = (D & B) | (~D & C); g = (5 * i + 1) & 15; }
-      else if (i < 48) { F = B ^ C ^ D; g = (3 * i + 5) & 15; } else { F = C ^ (B | ~D); g = (7 * i) & 15; }
-      F = F + A + Kt[i] + M[g]; A = D; D = C; C = B; B = B + ((F << S[i]) | (F >> (32 - S[i])));
-    }
-    a += A; b += B; c += C; d += D;
-  }
-  void update(const uint8_t* p, size_t n) {
-    len += n;
-    while (n) {
-      if (nbuf == 0 && n >= 64) { block(p); p += 64; n -= 64; continue; }
-      size_t k = 64 - nbuf; if (k > n) k = n;
-      memcpy(buf + nbuf, p, k); nbuf += (int)k; p += k; n -= k;
-      if (nbuf == 64) { block(buf); nbuf = 0; }
-    }
-  }
-  void finish(uint8_t out[16]) {
-    uint64_t bits = len * 8; uint8_t pad = 0x80; update(&pad, 1); pad = 0; while (nbuf != 56) update(&pad, 1);
-    uint8_t l[8]; for (int i = 0; i < 8; i++) l[i] = (uint8_t)(bits >> (8 * i)); update(l, 8);
-    uint32_t v[4] = {a, b, c, d}; for (int i = 0; i < 16; i++) out[i] = (uint8_t)(v[i >> 2] >> (8 * (i & 3)));
-  }
-};
-}  // namespace
-void md5_plane_u16(const uint16_t* p, int w, int h, int bit_depth, uint8_t out[16]) {
-  Md5 m;
-  if (bit_depth <= 8) { std::vector<uint8_t> row(w); for (int y = 0; y < h; y++) { for (int x = 0; x < w; x++) row[x] = (uint8_t)p[(size_t)y * w + x]; m.update(row.data(), w); } }
-  else m.update((const uint8_t*)p, (size_t)w * h * 2);   // little-endian host: samples are already 2 bytes LSB first
-  m.finish(out);
-}
-
-// The hashes of many planes at once: MD5 is a serial chain of ~5 cycles per step (~0.6 GB/s on one core, whatever the code looks like), and a 32-frame GOF of 1280x1280
-// maps is 630 MB of samples - one chain per plane on the host's cores instead (a 16-core share hashes the GOF in ~70 ms instead of 1.1 s).
-void md5_planes_u16(const Md5PlaneJob* jobs, size_t n) {
-  unsigned hw = std::thread::hardware_concurrency(); if (hw == 0) hw = 4;
-  size_t total = 0; for (size_t i = 0; i < n; i++) total += (size_t)jobs[i].w * jobs[i].h;
-  const size_t nt = total < (1u << 20) ? 1 : std::min<size_t>(std::min<size_t>(hw, 32), n);   // small pictures: not worth starting threads for
-  if (nt <= 1) { for (size_t i = 0; i < n; i++) md5_plane_u16(jobs[i].p, jobs[i].w, jobs[i].h, jobs[i].bit_depth, jobs[i].out); return; }
-  std::atomic<size_t> next{0};
-  std::vector<std::thread> th;
-  for (size_t t = 0; t < nt; t++) th.emplace_back([&]() { for (size_t i; (i = next.fetch_add(1)) < n;) md5_plane_u16(jobs[i].p, jobs[i].w, jobs[i].h, jobs[i].bit_depth, jobs[i].out); });
-  for (auto& t : th) t.join();
 }
 
 }  // namespace rbt

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "../csrc/rbt_types.h"
+#include "../../include/rbt.h"
 
 namespace rbt {
 
@@ -75,7 +76,10 @@ int parse_sps(ParamSets& ps, const uint8_t* rbsp, size_t n, std::string& err);  
 int parse_pps(ParamSets& ps, const uint8_t* rbsp, size_t n, std::string& err);
 // `head`: the header of the slice's independent segment (what a dependent slice segment repeats), nullptr when there is none yet
 int parse_slice_header(ParamSets& ps, const uint8_t* rbsp, size_t n, int nal_type, SliceHdr& h, std::string& err, const SliceHdr* head = nullptr);
-bool parse_md5_sei(const uint8_t* rbsp, size_t n, uint8_t md5[3][16]);
+// decoded picture hash SEI (D.2.20) of any kind: returns RBT_HASH_MD5 / _CRC / _CHECKSUM and the hash in SEI byte order, 16 bytes per component
+// (zero-padded), or 0 if the SEI NAL unit holds none
+int parse_hash_sei(const uint8_t* rbsp, size_t n, uint8_t hash[48]);
+int hash_bytes(int kind);   // bytes per component of an RBT_HASH_* kind: 16, 2, 4
 // PicOrderCntVal of a picture (8.3.1) from slice_pic_order_cnt_lsb; `prev_tid0_poc` is the POC anchor (prevTid0Pic), moved on unless the picture is a RASL / RADL
 // or sub-layer non-reference picture (the even NAL types up to 14: HM codes the P pictures of the CTC structure as TRAIL_N, cfg/hm/ctc-hm-geometry-ai.cfg:29)
 int slice_poc(const Sps& s, int nal_type, int poc_lsb, int& prev_tid0_poc);
@@ -88,8 +92,7 @@ void write_param_sets(std::vector<uint8_t>& out, const Sps& s, const Pps& p);
 // slice segment header up to and including byte_alignment(); is_idr pictures carry no POC/RPS syntax
 void write_slice_header(BitWriter& w, const Sps& s, const Pps& p, const SliceHdr& h, bool is_idr, int st_rps_idx);
 
-void md5_plane_u16(const uint16_t* p, int w, int h, int bit_depth, uint8_t out[16]);
-struct Md5PlaneJob { const uint16_t* p; int w, h, bit_depth; uint8_t* out; };
-void md5_planes_u16(const Md5PlaneJob* jobs, size_t n);   // the same for many planes, one chain per host thread
+// suffix SEI NAL unit with the decoded picture hash of one picture (`hash` as parse_hash_sei returns it): payload of 49, 7 or 13 bytes
+void append_hash_sei(std::vector<uint8_t>& out, int kind, const uint8_t hash[48]);
 
 }  // namespace rbt

@@ -14,7 +14,7 @@ namespace rbt {
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct EncStreamDesc {
-  int w, h, bd, n_frames, qp, i_qp_offset, gop, lossless, log2_ctb, rows, md5;   // w, h: display size (any even numbers)
+  int w, h, bd, n_frames, qp, i_qp_offset, gop, lossless, log2_ctb, rows, md5;   // w, h: display size (any even numbers); md5: RBT_HASH_* of the hash SEI behind every picture
   std::vector<const uint8_t*> hint_pm, hint_dm; int hint_w4 = 0, hint_h4 = 0;       // per frame: the decoded input picture's 4x4 maps (device), empty = no hints
   std::vector<const uint8_t*> occ4; int occ4_w = 0, occ4_h = 0;                      // per frame: occupancy of the 4x4 luma units (device, RbtFrame::occ4), empty = every sample counts
   int sao = 0;                           // SAO on (every stream that is not lossless, unless RBT_ENC_SAO=0)
@@ -41,6 +41,7 @@ struct EncodeBatch {
   std::vector<std::vector<uint16_t>> cs_keep;   // host staging of the ctb->slice maps, alive until the copies have completed
   uint8_t* d_zero = nullptr; size_t zero_bytes = 0; bool wpp = false;   // launch tickets (3 words) + row progress of the wavefront mode
   int main_stream = 0, aux_stream = -1;          // aux_stream >= 0: the intra part was enqueued there (its timers live there)
+  HashSet hash; std::vector<int> hash_idx;      // md5_sei: the reconstructions to hash (after SAO), index of each picture in `hash` (-1: none)
   std::vector<int32_t> lists_keep; size_t off_i = 0, off_ideb = 0, off_p = 0, off_sl = 0, off_sl_p = 0, off_isao = 0, off_psao = 0, off_pdeb = 0; int n_pdeb = 0, n_i = 0, n_ideb = 0, n_p = 0, n_sl_i = 0, n_sl_p = 0, n_isao = 0, n_psao = 0;   // index lists (encode_upload_lists)
   std::string err;
   ~EncodeBatch() { rbtk::dev_free(arena); }
@@ -175,6 +176,12 @@ static int encode_build(EncodeBatch& b) {
       for (int k = 0; k < f.n_slices; k++) { const RbtSlice& sl = b.slices[f.first_slice + k]; if (!sl.dependent) head = f.first_slice + k; for (int q = 0; q < sl.n_ctbs; q++) cs_host[sl.ctb_addr + q] = (uint16_t)head; } }
   }
   if (rbtk::h2d(base + o_cs_all, b.cs_keep[0].data(), cs_words * 2)) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  // decoded picture hash SEI: the whole coded reconstruction (what a decoder outputs before cropping) after SAO
+  b.hash_idx.assign(nf, -1);
+  for (size_t i = 0; i < nf; i++) if (const int kind = b.desc[b.frame_stream[i]].md5) {
+    const RbtFrame& f = b.frames[i];
+    if ((b.hash_idx[i] = b.hash.add(f.out, f.cfg.w, f.cfg.h, f.cfg.bit_depth, kind)) < 0) { b.err = "picture cannot be hashed"; return RBT_ERR_UNSUPPORTED; }
+  }
   b.d_frames = (RbtFrame*)(base + o_frames); b.d_slices = (RbtSlice*)(base + o_slices); b.d_lists = (int32_t*)(base + o_lists); b.d_dst = (uint32_t*)(base + o_dst);
   b.d_out = base + o_out; b.d_packed = base + o_packed; b.out_total = out_cap_total;
   b.d_zero = base + o_zero; b.zero_bytes = zero_bytes; b.wpp = any_wpp;
@@ -202,6 +209,7 @@ static int encode_upload_lists(EncodeBatch& b) {
   b.off_sl = lists.size(); for (size_t i = 0; i < ns; i++) if (b.frame_is_idr[b.slices[i].frame]) { lists.push_back((int)i); b.n_sl_i++; }
   b.off_sl_p = lists.size(); for (size_t i = 0; i < ns; i++) if (!b.frame_is_idr[b.slices[i].frame]) { lists.push_back((int)i); b.n_sl_p++; }
   if (rbtk::h2d(b.d_lists, lists.data(), lists.size() * sizeof(int32_t))) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  if (!b.hash.empty() && b.hash.upload()) { b.err = "device allocation failed"; return RBT_ERR_NOMEM; }
   return 0;
 }
 // intra pictures (analysis, closed-loop intra coding, deblocking): they only read their own source pictures
@@ -233,8 +241,8 @@ static void encode_launch_entropy_intra(EncodeBatch& b) {
   else rbtk::launch_entropy(b.d_frames, b.d_slices, b.d_out, b.d_lists + b.off_sl, b.n_sl_i, max_log2_ctb(b));
   rbtk::timer_end(T_ENTROPY_I);
 }
-// inter pictures (need the reconstructed intra pictures and their own sources), then the entropy coder for every slice
-static void encode_launch_rest(EncodeBatch& b) {
+// inter pictures (need the reconstructed intra pictures and their own sources); after them every reconstruction is final
+static void encode_launch_inter(EncodeBatch& b) {
   size_t nf = b.frames.size();
   int mu = 0, mc = 0, ml = 0;
   for (size_t i = 0; i < nf; i++) { const RbtStreamCfg& c = b.frames[i].cfg; mu = std::max(mu, c.w4 * c.h4); mc = std::max(mc, c.w_ctb * c.h_ctb); ml = std::max(ml, c.w * c.h); }
@@ -243,12 +251,20 @@ static void encode_launch_rest(EncodeBatch& b) {
   rbtk::launch_deblock(b.d_frames, b.d_slices, b.d_lists + b.off_pdeb, b.n_pdeb, mu);
   rbtk::launch_enc_sao(b.d_frames, b.d_slices, b.d_lists + b.off_psao, b.n_psao, mc, max_log2_ctb(b), e1_fused_lf());
   rbtk::timer_end(T_INTER);
+}
+// the entropy coder for the inter pictures' slices
+static void encode_launch_entropy_rest(EncodeBatch& b) {
   rbtk::timer_begin(T_ENTROPY);
   if (b.wpp) rbtk::launch_entropy_wave(b.d_frames, b.d_slices, b.d_out, b.d_lists + b.off_p, b.n_p, max_w_ctb(b), max_h_ctb(b), max_log2_ctb(b), (uint32_t*)b.d_zero + 2);
   else rbtk::launch_entropy(b.d_frames, b.d_slices, b.d_out, b.d_lists + b.off_sl_p, b.n_sl_p, max_log2_ctb(b));
   rbtk::timer_end(T_ENTROPY);
 }
-static int encode_launch(EncodeBatch& b) { encode_launch_intra(b); encode_launch_entropy_intra(b); encode_launch_rest(b); return 0; }
+static int encode_launch(EncodeBatch& b) {
+  encode_launch_intra(b); encode_launch_entropy_intra(b); encode_launch_inter(b);
+  if (!b.hash.empty()) b.hash.launch();
+  encode_launch_entropy_rest(b);
+  return 0;
+}
 static int encode_finish(EncodeBatch& b, std::vector<std::vector<uint8_t>>& outs, rbt_stats& st) {
   size_t nf = b.frames.size(), ns = b.slices.size();
   if (rbtk::d2h(b.slices.data(), b.d_slices, ns * sizeof(RbtSlice))) { b.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
@@ -261,24 +277,11 @@ static int encode_finish(EncodeBatch& b, std::vector<std::vector<uint8_t>>& outs
   double t0 = now_ms();
   if (total && rbtk::d2h(packed.data(), b.d_packed, total)) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
   if (rbtk::dev_sync()) { b.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (!b.hash.empty() && b.hash.fetch()) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }   // 48 bytes per picture
   st.d2h_ms += now_ms() - t0;
   // ---- NAL packing (parameter sets, slice headers, emulation prevention) ----
   double t1 = now_ms();
   outs.assign(b.desc.size(), {});
-  // decoded picture hash SEI (md5_sei): the reconstructed pictures come to the host once and their planes are hashed side by side (md5_planes_u16)
-  std::vector<uint16_t> rec; std::vector<size_t> rec_off(nf, 0); std::vector<uint8_t> hashes(nf * 48);
-  { size_t tot = 0; for (size_t i = 0; i < nf; i++) if (b.desc[b.frame_stream[i]].md5) { rec_off[i] = tot; tot += frame_samples(b.frames[i].cfg); }
-    if (tot) {
-      rec.resize(tot); std::vector<Md5PlaneJob> jobs;
-      for (size_t i = 0; i < nf; i++) if (b.desc[b.frame_stream[i]].md5) {
-        const RbtFrame& f = b.frames[i]; const RbtStreamCfg& c = f.cfg; uint16_t* r = rec.data() + rec_off[i];
-        if (rbtk::d2h(r, f.out[0], frame_samples(c) * 2)) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
-        jobs.push_back({r, c.w, c.h, c.bit_depth, &hashes[i * 48]});
-        jobs.push_back({r + (size_t)c.w * c.h, c.cw, c.ch, c.bit_depth, &hashes[i * 48 + 16]});
-        jobs.push_back({r + (size_t)c.w * c.h + (size_t)c.cw * c.ch, c.cw, c.ch, c.bit_depth, &hashes[i * 48 + 32]});
-      }
-      md5_planes_u16(jobs.data(), jobs.size());
-    } }
   for (size_t i = 0; i < nf; i++) {
     int si = b.frame_stream[i]; const Sps& s = b.sps[si]; const Pps& p = b.pps[si]; std::vector<uint8_t>& out = outs[si]; const RbtFrame& f = b.frames[i];
     bool idr = b.frame_is_idr[i] != 0;
@@ -291,12 +294,7 @@ static int encode_finish(EncodeBatch& b, std::vector<std::vector<uint8_t>>& outs
       w.b.insert(w.b.end(), packed.begin() + dst[f.first_slice + k], packed.begin() + dst[f.first_slice + k] + sl.out_size);
       append_nal(out, idr ? NAL_IDR_W_RADL : NAL_TRAIL_R, w.b.data(), w.b.size(), k == 0);
     }
-    if (b.desc[si].md5) {
-      uint8_t sei[52]; sei[0] = 132; sei[1] = 49; sei[2] = 0;
-      memcpy(sei + 3, &hashes[i * 48], 48);
-      sei[51] = 0x80;
-      append_nal(out, NAL_SEI_SUFFIX, sei, 52, false);
-    }
+    if (b.hash_idx[i] >= 0) append_hash_sei(out, b.desc[si].md5, &b.hash.out[(size_t)b.hash_idx[i] * 48]);
   }
   st.host_pack_ms += now_ms() - t1;
   { int cur = b.main_stream; if (b.aux_stream >= 0) rbtk::set_stream(b.aux_stream);
@@ -343,6 +341,7 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
   const int cl = 2 * isps.conf_win[0], ct = 2 * isps.conf_win[2], dw = c.w - cl - 2 * isps.conf_win[1], dh = c.h - ct - 2 * isps.conf_win[3];
   if (dw <= 0 || dh <= 0) { err = "empty conformance window"; return RBT_ERR_BITSTREAM; }
   if (p.preset != RBT_PRESET_DEFAULT && p.preset != RBT_PRESET_FAST) { err = "preset must be RBT_PRESET_DEFAULT or RBT_PRESET_FAST"; return RBT_ERR_PARAM; }
+  if (p.md5_sei < RBT_HASH_NONE || p.md5_sei > RBT_HASH_CHECKSUM) { err = "md5_sei must be an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
   d.bd = c.bit_depth; d.n_frames = cnt; d.qp = p.qp; d.log2_ctb = p.log2_ctb; d.rows = p.ctb_rows_per_slice; d.md5 = p.md5_sei; d.tools_off = p.preset == RBT_PRESET_FAST ? (RBT_ET_SATD | RBT_ET_REFINE | RBT_ET_RQ | RBT_ET_RDM) : 0;
   for (int k = 0; k < 3; k++) d.src[k].resize(cnt);
   auto view = [&](int k, int q) { return (const uint16_t*)db.frames[first + k].out[q]; };
@@ -471,7 +470,7 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
   std::vector<std::vector<int>> uniq(ng);          // per pipeline: the stream indices that are decoded
   for (int g = 0; g < ng; g++) for (int i : groups[g]) {
     int d = -1;
-    for (size_t q = 0; q < uniq[g].size(); q++) if (in[uniq[g][q]] == in[i] && n_in[uniq[g][q]] == n_in[i] && !p[i].verify_md5 && !p[uniq[g][q]].verify_md5) { d = (int)q; break; }
+    for (size_t q = 0; q < uniq[g].size(); q++) if (in[uniq[g][q]] == in[i] && n_in[uniq[g][q]] == n_in[i]) { d = (int)q; break; }
     if (d < 0) { d = (int)uniq[g].size(); uniq[g].push_back(i); }
     j.dec_of[g].push_back(d);
   }
@@ -486,8 +485,8 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
   // ---- phase A, longest pipeline first: build decoder and encoder batches and upload them; then enqueue decode -> pool ->
   // encode on the stream without a host round trip in between (PCCTranscoder.cpp:428-448, :466, :825-904). Every upload of
   // the job is issued before its first kernel: a copy from pageable memory blocks the host until the stream has reached it,
-  // and pipelines may share a stream. Pipelines that ask for the input MD5 check keep the decoder / encoder split, because
-  // the check needs the decoded pictures on the host first.
+  // and pipelines may share a stream. The input's picture hashes (verify_md5) are checked on the GPU behind the decoder's last
+  // filter; only the hashes and a mismatch count per decoded stream come back, when the job is collected.
   j.t_gpu = now_ms();
   int rc = 0;
   std::vector<std::vector<PoolJob>> pool_jobs(ng);
@@ -499,25 +498,25 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
     else if (gof_rule && p[i].occupancy_rd && last >= 0) { occ_of[i] = last; any_occ_rd = true; if (p[i].verify_md5 || p[last].verify_md5) { err = "occupancy_rd cannot be combined with verify_md5"; rc = RBT_ERR_PARAM; } }
   }
   std::vector<OccSource> occ_src(n); std::vector<OccJob> occ_jobs;
-  std::vector<char> verify_of(ng, 0);
   for (int k = 0; k < ng && !rc; k++) {
     const int gi = order[k], sid = job_stream(j, gi); const std::vector<int>& gs = groups[gi]; rbtk::set_stream(sid);
     std::vector<StreamIn> sins; bool verify = false;
+    std::vector<char> verify_ds(uniq[gi].size(), 0);   // per decoded stream: some entry it feeds asks for the check
     for (int i : uniq[gi]) sins.push_back(StreamIn{in[i], n_in[i]});
-    for (int i : gs) verify |= p[i].verify_md5 != 0;
-    verify_of[gi] = verify;
+    for (size_t q = 0; q < gs.size(); q++) if (p[gs[q]].verify_md5) { verify = true; verify_ds[j.dec_of[gi][q]] = 1; }
     double t0 = now_ms();
     db[gi].want_save = parse_bands() > 1 && k == 0 && j.has_aux && ng <= rbtk::RBT_AUX_STREAM && !verify;
     rc = decode_build(db[gi], sins.data(), (int)sins.size());
     st.host_parse_ms += now_ms() - t0;
     if (!rc) rc = decode_upload_lists(db[gi]);
+    if (!rc && verify) rc = decode_hash_setup(db[gi], verify_ds);
     if (rc) { err = db[gi].err; break; }
   }
   // encoder set-up: the pipelines whose occupancy streams others are coded with first (their pooled planes are what the maps are made of)
   for (int pass = 0; pass < 2 && !rc; pass++) for (int k = 0; k < ng && !rc; k++) {
     const int gi = order[k], sid = job_stream(j, gi); const std::vector<int>& gs = groups[gi]; rbtk::set_stream(sid);
     bool feeds = false; for (int i : gs) for (int c = 0; c < n; c++) feeds |= occ_of[c] == i;
-    if (feeds != (pass == 0) || verify_of[gi]) continue;
+    if (feeds != (pass == 0)) continue;
     for (size_t q = 0; q < gs.size() && !rc; q++) {
       const int i = gs[q], io = occ_of[i];
       rc = setup_encode(db[gi], j.dec_of[gi][q], (int)q, p[i], eb[gi], pooled, err, &pool_jobs[gi], io >= 0 ? &occ_src[io] : nullptr, io, &occ_jobs);
@@ -633,6 +632,11 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
       }
     }
     if (!db[gi].recon_external) rbtk::timer_end(T_RECON);
+    // the input's picture hashes behind the decoder's last filter: on the auxiliary stream where the intra coding was forked there, underneath the rest of the encoder
+    if (!db[gi].hash.empty()) {
+      if (fork) { rbtk::stream_wait(aux, sid); rbtk::set_stream(aux); decode_launch_hash(db[gi]); rbtk::set_stream(sid); }
+      else decode_launch_hash(db[gi]);
+    }
     if (!jobs.empty()) {
       // the pictures of one stream are of one size and their pooled copies evenly spaced (setup_encode): one launch per run of such jobs
       rbtk::timer_begin(T_POOL);
@@ -652,8 +656,14 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
     }
     if (consumes[gi]) for (int m : occ_marks) rbtk::stream_wait_mark(sid, m);
     if (fork) rbtk::stream_wait_mark(sid, intra_done); else { encode_launch_intra(e); encode_launch_entropy_intra(e); }
-    encode_launch_rest(e);
-    if (fork) rbtk::stream_wait(sid, e.aux_stream);      // the intra pictures' entropy coding on the auxiliary stream
+    encode_launch_inter(e);
+    // the reconstructions' hashes (md5_sei) once SAO has been applied to all of them: beside the inter pictures' entropy coding where there is an auxiliary stream
+    if (!e.hash.empty()) {
+      if (fork) { const int m = rbtk::stream_mark(sid); rbtk::stream_wait_mark(aux, m); rbtk::set_stream(aux); e.hash.launch(); rbtk::set_stream(sid); }
+      else e.hash.launch();
+    }
+    encode_launch_entropy_rest(e);
+    if (fork) rbtk::stream_wait(sid, e.aux_stream);      // the intra pictures' entropy coding and the hashes on the auxiliary stream
   }
   j.rc = rc;
   return J;
@@ -675,20 +685,17 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
     if (rc) { err = db[gi].err; continue; }
     if (j.parse_timed.empty() || j.parse_timed[gi]) st.k_parse_ms += rbtk::timer_ms(T_PARSE);
     if (j.recon_timed.empty() || j.recon_timed[gi]) st.k_recon_ms += rbtk::timer_ms(T_RECON);
-    std::vector<std::vector<uint8_t>> o1;
-    if (j.chained[gi]) rc = encode_finish(eb[gi], o1, st);
-    else {
+    // verify_md5: the hashes of the decoded pictures were compared on the GPU; a mismatch fails the job and nothing is packed
+    if (!db[gi].hash.empty()) {
+      if (db[gi].hash.fetch()) { err = "device transfer failed"; rc = RBT_ERR_NO_DEVICE; continue; }
       for (size_t q = 0; q < gs.size() && !rc; q++) if (p[gs[q]].verify_md5) {
-        rbt_video v; rc = decode_fetch(db[gi], j.dec_of[gi][q], &v, true); free(v.data);
-        if (rc) { err = "fetch failed"; break; }
-        if (v.md5_failed) { err = "input MD5 mismatch"; rc = RBT_ERR_MD5; }
+        int checked = 0, failed = 0; decode_hash_result(db[gi], j.dec_of[gi][q], checked, failed);
+        if (failed) { err = "input " + std::to_string(gs[q]) + ": decoded picture hash mismatch (" + std::to_string(failed) + " of " + std::to_string(checked) + " pictures)"; rc = RBT_ERR_MD5; }
       }
-      for (size_t q = 0; q < gs.size() && !rc; q++) rc = setup_encode(db[gi], j.dec_of[gi][q], (int)q, p[gs[q]], eb[gi], j.pooled, err);
       if (rc) continue;
-      eb[gi].main_stream = sid;
-      rc = encode_build(eb[gi]);
-      if (!rc) rc = encode_run(eb[gi], o1, st);
     }
+    std::vector<std::vector<uint8_t>> o1;
+    rc = encode_finish(eb[gi], o1, st);
     if (rc) { if (err.empty()) err = eb[gi].err; continue; }
     for (size_t q = 0; q < gs.size(); q++) outs[gs[q]].swap(o1[q]);
   }
@@ -725,6 +732,7 @@ int encode_yuv(rbt_stats& st, std::string& err, const uint16_t* yuv, int w, int 
   memset(&st, 0, sizeof(st));
   *out = nullptr; *n_out = 0;
   if (w <= 0 || h <= 0 || w % 2 || h % 2 || bd < 8 || bd > 12) { err = "bad picture format"; return RBT_ERR_PARAM; }
+  if (md5 < RBT_HASH_NONE || md5 > RBT_HASH_CHECKSUM) { err = "md5_sei must be an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
   size_t ys = (size_t)w * h, cs = (size_t)(w / 2) * (h / 2), fs = ys + 2 * cs;
   uint16_t* buf = (uint16_t*)rbtk::dev_alloc(fs * 2 * (size_t)n_frames);
   if (!buf) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
@@ -740,6 +748,36 @@ int encode_yuv(rbt_stats& st, std::string& err, const uint16_t* yuv, int w, int 
   if (!rc) rc = encode_run(eb, outs, st);
   if (rc) { err = eb.err; return rc; }
   return hand_out(outs, out, n_out);
+}
+
+// rbt_picture_hash: the pictures go to the device with every plane 16-byte aligned (the hash kernels' loads), RBT_HASH_MAX_PICS at a time
+int picture_hash_host(std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int kind, uint8_t* out) {
+  if (w <= 0 || h <= 0 || w % 2 || h % 2 || w > 16384 || h > 16384 || bd < 8 || bd > 16 || n_frames < 1) { err = "bad picture format"; return RBT_ERR_PARAM; }
+  if (kind < RBT_HASH_MD5 || kind > RBT_HASH_CHECKSUM) { err = "kind must be RBT_HASH_MD5, RBT_HASH_CRC or RBT_HASH_CHECKSUM"; return RBT_ERR_PARAM; }
+  const size_t ys = (size_t)w * h, cs = (size_t)(w / 2) * (h / 2), fs = ys + 2 * cs;
+  const size_t ay = (ys + 7) & ~(size_t)7, ac = (cs + 7) & ~(size_t)7, per = ay + 2 * ac;   // samples per picture on the device
+  for (int f0 = 0; f0 < n_frames; f0 += RBT_HASH_MAX_PICS) {
+    const int m = std::min(n_frames - f0, (int)RBT_HASH_MAX_PICS);
+    std::vector<uint16_t> staging(per * (size_t)m, 0);
+    for (int k = 0; k < m; k++) {
+      const uint16_t* src = yuv + fs * (size_t)(f0 + k); uint16_t* dst = staging.data() + per * (size_t)k;
+      memcpy(dst, src, ys * 2); memcpy(dst + ay, src + ys, cs * 2); memcpy(dst + ay + ac, src + ys + cs, cs * 2);
+    }
+    uint16_t* buf = (uint16_t*)rbtk::dev_alloc(staging.size() * 2);
+    if (!buf) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    struct G { void* p; ~G() { rbtk::dev_free(p); } } g{buf};
+    if (rbtk::h2d(buf, staging.data(), staging.size() * 2)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+    HashSet hs;
+    for (int k = 0; k < m; k++) {
+      uint16_t* y = buf + per * (size_t)k; const uint16_t* planes[3] = {y, y + ay, y + ay + ac};
+      if (hs.add(planes, w, h, bd, kind) < 0) { err = "picture cannot be hashed"; return RBT_ERR_UNSUPPORTED; }
+    }
+    int rc = hs.upload();
+    if (!rc) { hs.launch(); rc = hs.fetch(); }
+    if (rc) { err = "device transfer failed"; return rc; }
+    memcpy(out + (size_t)f0 * 48, hs.out.data(), (size_t)m * 48);
+  }
+  return 0;
 }
 
 int or_pool_host(const uint16_t* plane, int w, int h, int factor, uint16_t* out) {

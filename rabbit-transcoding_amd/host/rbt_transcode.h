@@ -12,4 +12,5 @@ void gof_abandon(GofJob* j);
 size_t gof_memory(const GofJob* j);             // device memory the job's build took (its arenas)
 int encode_yuv(rbt_stats& st, std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int qp, int gop, int lossless, int log2_ctb, int rows, int md5, uint8_t** out, size_t* n_out);
 int or_pool_host(const uint16_t* plane, int w, int h, int factor, uint16_t* out);
+int picture_hash_host(std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int kind, uint8_t* out);   // rbt_picture_hash
 }
