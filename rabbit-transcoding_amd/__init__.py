@@ -12,6 +12,7 @@ _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RBT_LIB_PATH") or os.path.join(_DIR, "librbt.so")   # RBT_LIB_PATH: another build of the same library (experiments)
 
 RBT_VIDEO_OCCUPANCY, RBT_VIDEO_GEOMETRY, RBT_VIDEO_ATTRIBUTE = 0, 1, 19
+RBT_ERR_NOMEM, RBT_ERR_OUTPUT = -5, -8   # device (or host) memory ran out / a slice's coded data is larger than the output buffer sized for it
 RBT_HASH_NONE, RBT_HASH_MD5, RBT_HASH_CRC, RBT_HASH_CHECKSUM = 0, 1, 2, 3   # md5_sei: kind of decoded picture hash SEI (HM / x265 numbering)
 
 

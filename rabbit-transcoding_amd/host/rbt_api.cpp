@@ -39,6 +39,7 @@ const char* rbt_strerror(int code) {
     case RBT_ERR_NOMEM: return "out of memory";
     case RBT_ERR_MD5: return "decoded picture hash mismatch on the input stream";
     case RBT_ERR_BUSY: return "too many transcodes in flight";
+    case RBT_ERR_OUTPUT: return "coded data exceeds the output buffer sized for it";
     default: return "unknown error";
   }
 }

@@ -34,6 +34,9 @@ int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch
       geo_bd < 8 || geo_bd > 16 || attr_bd < 8 || attr_bd > 16 || a->map_count < 1 || a->map_count > 2 || (a->map_count > 1 && !d1) || ((t0 != nullptr) != (t1 != nullptr) && a->map_count > 1) ||
       (a->geometry_smoothing && (a->grid_size < 2 || a->grid_size > 255 || a->threshold_smoothing < 0))) {
     err = "bad atlas parameters"; return RBT_ERR_PARAM; }
+  // an odd grid is refused (rbt.h: "2..255, even"): pc_sm_skip keeps a point whose coordinate is g * w - (g - 1) / 2 - 1, the remainder of that modulo g is g / 2, so its
+  // lower cell is w - 1 and pc_sm_mark / pc_sm_filter would touch cell w, outside the w^3 arrays. With an even grid the last point kept has remainder g / 2 - 1: cell w - 2.
+  if (a->geometry_smoothing && a->grid_size % 2) { err = "grid_size must be even"; return RBT_ERR_PARAM; }
   const bool smooth = a->geometry_smoothing != 0;
   RbtPccParams P; memset(&P, 0, sizeof(P));
   P.w = W; P.h = H; P.res = res; P.prec = prec; P.map_count = a->map_count; P.absolute_d1 = a->absolute_d1; P.remove_dup = a->remove_duplicate_points; P.threshold = a->threshold_lossy_om;

@@ -107,13 +107,15 @@ static int encode_build(EncodeBatch& b) {
         sl.deblocking_disabled = (uint8_t)p.pps_deblocking_disabled; sl.lf_across = (uint8_t)p.loop_filter_across_slices;
         sl.max_merge_cand = 1; sl.num_ref_idx = 1; sl.poc = f.poc; sl.sao_luma = sl.sao_chroma = (uint8_t)b.desc[si].sao;
         if (!is_i) { sl.ref_frame[0] = f.ref_frame; sl.ref_poc[0] = f.ref_poc; }
-        // slice data buffer, by the slice's QP, sized for full-range noise (the most a picture can cost: log2(2^bit_depth / Qstep) bits per sample, 1.5 samples per luma
-        // sample in 4:2:0): 3 bytes per luma sample of the slice (the raw samples at 2 bytes each) below QP 16 and for lossless streams, 2 below QP 34 (Qstep >= 4: at most
-        // 8 bits x 1.5), 1 from there on (Qstep >= 32: 5 bits x 1.5), + slack. A slice that does not fit ends the call with an error (RbtSlice::out_size = 0xFFFFFFFF), it
-        // is never cut short. Round 3 gave every slice 3: 7.6 of the 17 MB an encoded 1280x1280 picture took.
+        // slice data buffer, by the slice's QP, in quarter bytes per luma sample of the slice: 17 for lossless streams, 14 below QP 16, 8 below QP 34, 5 from there on,
+        // + slack. The figures are what the oracle (which has no caps) needs for noise pictures - the largest slices: 3.41 bytes per luma sample lossless, 2.74 at QP 0,
+        // 1.64 at QP 16, 0.92 at QP 34 (DESIGN.md 9.5 has the table) - plus a fifth, rounded up. They are measured, not derived: log2(2^bit_depth / Qstep) bits per sample, the
+        // entropy of a quantised sample, undercounts what CABAC spends - significance maps, greater-than flags and sign bits around every level, escape codes whose
+        // Golomb-Rice prefix grows with the level (lossless two-level noise costs 18 bits a sample for 10-bit samples), and per-block syntax - so noise costs more than
+        // its raw samples below QP 16. A slice that does not fit ends the call with RBT_ERR_OUTPUT (RbtSlice::out_size = 0xFFFFFFFF), it is never cut short.
         size_t rows = (size_t)(sl.n_ctbs + s.w_ctb - 1) / s.w_ctb;
-        const int bytes_per_sample = (d.lossless || sl.qp < 16) ? 3 : (sl.qp < 34 ? 2 : 1);
-        sl.out_cap = (uint32_t)(rows * ((size_t)s.width << s.log2_ctb) * bytes_per_sample + 4096);
+        const int quarter_bytes_per_sample = d.lossless ? 17 : (sl.qp < 16 ? 14 : (sl.qp < 34 ? 8 : 5));
+        sl.out_cap = (uint32_t)(rows * ((size_t)s.width << s.log2_ctb) * quarter_bytes_per_sample / 4 + 4096);
         f.n_slices++;
         b.slices.push_back(sl);
       }
@@ -148,7 +150,9 @@ static int encode_build(EncodeBatch& b) {
   size_t o_lists = a.reserve((nf + b.slices.size()) * 3 * sizeof(int32_t)), o_dst = a.reserve(b.slices.size() * sizeof(uint32_t));
   size_t out_cap_total = 0; for (auto& sl : b.slices) { sl.out_off = (uint32_t)out_cap_total; out_cap_total += sl.out_cap; }
   if (out_cap_total >= 0xFFFFFFFFull) { b.err = "output buffer too large for one call"; return RBT_ERR_UNSUPPORTED; }
-  size_t o_out = a.reserve(out_cap_total), o_packed = a.reserve(out_cap_total / 2 + 65536);
+  // the packed output holds every slice back to back: as large as the slice buffers together, so that slices which fit their buffers always fit it (half of that, which
+  // it had before, is less than noise needs in every QP band: DESIGN.md 9.5)
+  size_t o_out = a.reserve(out_cap_total), o_packed = a.reserve(out_cap_total);
   b.arena_size = a.reserve(0);
   b.arena = rbtk::dev_alloc(b.arena_size);
   if (!b.arena) { b.err = "device allocation failed"; return RBT_ERR_NOMEM; }
@@ -269,8 +273,8 @@ static int encode_finish(EncodeBatch& b, std::vector<std::vector<uint8_t>>& outs
   size_t nf = b.frames.size(), ns = b.slices.size();
   if (rbtk::d2h(b.slices.data(), b.d_slices, ns * sizeof(RbtSlice))) { b.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
   std::vector<uint32_t> dst(ns); size_t total = 0;
-  for (size_t i = 0; i < ns; i++) { if (b.slices[i].out_size > b.slices[i].out_cap) { b.err = "slice data exceeds its buffer"; return RBT_ERR_NOMEM; } dst[i] = (uint32_t)total; total += b.slices[i].out_size; }
-  if (total > b.out_total / 2 + 65536) { b.err = "packed output exceeds its buffer"; return RBT_ERR_NOMEM; }
+  // (the packed buffer is as large as the slice buffers together: total <= out_total once every slice fits)
+  for (size_t i = 0; i < ns; i++) { if (b.slices[i].out_size > b.slices[i].out_cap) { b.err = "slice data exceeds its buffer"; return RBT_ERR_OUTPUT; } dst[i] = (uint32_t)total; total += b.slices[i].out_size; }
   std::vector<uint8_t> packed(total);
   if (rbtk::h2d(b.d_dst, dst.data(), ns * sizeof(uint32_t))) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
   rbtk::launch_pack(b.d_out, b.d_slices, b.d_dst, b.d_packed, (int)ns);
@@ -371,6 +375,15 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
     for (int k = 0; k < cnt; k++) for (int q = 0; q < 3; q++) d.src[q][k] = view(k, q);
     // arena sharing: the encoder's levels and reconstruction of picture k live in the decoded picture k's dead buffers when the two pictures have one geometry (coded size
     // = the input's coded size, no window offset) and no other target rate of a fan-out took them already. RBT_ARENA_SHARE=0 switches it off.
+    // What orders the encoder's first write to such a buffer behind the decoder's last read of it (the reconstruction of picture k reads its levels, its deblocking and
+    // SAO launches - decode_launch_filters, the last thing decode_launch_level enqueues for a level - read its pre-SAO samples; nothing later does: reference pictures and
+    // the input's hash check read the SAO output) in gof_submit:
+    //  - one HIP stream: every level of the decoder is enqueued on the pipeline's stream before encode_launch_intra, the encoder's first kernel, goes onto the same stream
+    //    (the merged launches of pipelines that share a stream are enqueued earlier still, on that same stream);
+    //  - intra coding forked onto the auxiliary stream: rbtk::stream_wait(aux, sid) records an event on the pipeline's stream right behind decode_launch_level(fork_level),
+    //    fork_level being the highest dependency level of any decoded picture an output I picture is coded from - so those pictures' filters are behind the event, and I
+    //    pictures alias nothing else. The P pictures (encode_launch_inter) stay on the pipeline's stream, behind every level.
+    // tests/test_arena_share.py runs the same transcodes with the switch off and on.
     { static const int share = [] { const char* e = getenv("RBT_ARENA_SHARE"); return !e || atoi(e) != 0; }();
       if (db.alias_taken.size() < db.stream_first.size()) db.alias_taken.resize(db.stream_first.size(), 0);
       if (share && cl == 0 && ct == 0 && coded_size(dw, 2) == c.w && coded_size(dh, 2) == c.h && !db.alias_taken[si]) {

@@ -43,11 +43,11 @@ def random_atlas(R, seed, w=None, h=None):
     return atlas, patches, occ, d0, d1, 10, t0, t1, 10
 
 
-def seam_atlas(R, seed, tiles=4, prec=1, two_axes=False):
+def seam_atlas(R, seed, tiles=4, prec=1, two_axes=False, noise=1):
     """A dense surface cut into patches that MEET in 3-D, the situation geometry smoothing exists for (PCCCodec::smoothPointCloudPostprocess): tiles x tiles patches of
     2 x 2 blocks, each occupied but for a margin of 2 pixels (so its border points are boundary points, identifyBoundaryPoints), placed 28 apart in space so that the occupied
     areas of neighbours abut; depth = a smooth surface + an offset per patch (the seam a lossy geometry codec leaves) + noise; the far map a few levels behind.
-    two_axes: every other patch projects along another axis (points of different patches then share cells away from the seams too)."""
+    two_axes: every other patch projects along another axis (points of different patches then share cells away from the seams too); noise: amplitude of the depth noise."""
     r = np.random.default_rng(7000 + seed)
     res, w = 16, tiles * 32
     patches, occ_full = [], np.zeros((w, w), bool)
@@ -62,7 +62,7 @@ def seam_atlas(R, seed, tiles=4, prec=1, two_axes=False):
             patches.append(R.Patch(2 * i, 2 * j, 2, 2, 40 + 28 * i, 40 + 28 * j, 30, axes[0], axes[1], axes[2], 0, 0, 1, 1))
             sl = (slice(32 * j, 32 * j + 32), slice(32 * i, 32 * i + 32))
             occ_full[32 * j + 2:32 * j + 30, 32 * i + 2:32 * i + 30] = True
-            d0[sl] = surf[sl] + int(r.integers(-6, 7)) + r.integers(-1, 2, (32, 32))
+            d0[sl] = surf[sl] + int(r.integers(-6, 7)) + r.integers(-noise, noise + 1, (32, 32))
     holes = r.random((w, w)) < 0.01
     occ_full &= ~holes
     if prec > 1: occ_full = np.kron(occ_full[::prec, ::prec], np.ones((prec, prec), bool))
@@ -73,6 +73,75 @@ def seam_atlas(R, seed, tiles=4, prec=1, two_axes=False):
     t1 = r.integers(0, 1024, w * w * 3 // 2).astype(np.uint16)
     atlas = R.AtlasParams(w, w, res, prec, 2, 1, 1, 0, 1, [8, 8, 4, 16, 6][seed % 5], [64, 64, 16, 64, 1][seed % 5])
     return atlas, patches, occ, d0, d1, 10, t0, t1, 10
+
+
+def _copy_atlas(R, atlas, **kw):
+    a = R.AtlasParams(*[getattr(atlas, n) for n, _ in R.AtlasParams._fields_])
+    for k, v in kw.items(): setattr(a, k, v)
+    return a
+
+
+EDGE_GRIDS = (2, 4, 6, 8, 16, 254)
+
+
+def edge_residues(g):
+    return range(g) if g <= 16 else (0, 1, g // 2 - 1, g // 2, g // 2 + 1, g - 1)
+
+
+def edge_atlas(R, g, axis, residue, seed=0):
+    """seam_atlas moved so that the cloud's largest coordinate lies on `axis` (0 x, 1 y, 2 z) and is `residue` modulo the grid size g: the grid of the smoothing spans that
+    coordinate (w = ceil(max / g) cells a side), so the residue decides where in the last cell the outermost points sit and which of them pc_sm_skip lets through.
+    -> (case, largest coordinate)"""
+    import oracle_lib as O
+    case = seam_atlas(R, seed, tiles=3)
+    atlas = _copy_atlas(R, case[0], grid_size=g, threshold_smoothing=1 if g <= 4 else 64)
+    field = ("u1", "v1", "d1")[axis]                              # the patches project along z: tangent = x (u1), bitangent = y (v1), normal = z (d1)
+    low = max(0, g // 2 - 30)                                     # (the cloud starts near 40: keep it clear of the lower skip margin of a large grid)
+    for p in case[1]: p.u1 += low; p.v1 += low; p.d1 += low
+    mx = O.reconstruct(_copy_atlas(R, atlas, geometry_smoothing=0), *case[1:])[0].max(axis=0).astype(int)
+    t = max(int(mx.max()) + 1, int(mx[axis]))
+    t += (residue - t) % g
+    for p in case[1]: setattr(p, field, getattr(p, field) + t - int(mx[axis]))
+    return (atlas,) + tuple(case[1:]), t
+
+
+def check_grid_edge(ctx, g, axis):
+    """even grid sizes with the cloud's largest coordinate at every residue modulo g along one axis: points, their order, colours and the count of moved points == oracle,
+    and the smoothing moves points in at least one of the clouds (the edge is not passed over by the skip rule alone)"""
+    import oracle_lib as O
+    R = __import__("rbt_lib").module()
+    most = 0
+    for residue in edge_residues(g):
+        case, t = edge_atlas(R, g, axis, residue)
+        plain = O.reconstruct(_copy_atlas(R, case[0], geometry_smoothing=0), *case[1:])[0]
+        assert int(plain.max()) == t and int(plain[:, axis].max()) == t and t % g == residue and plain.shape[0] > 5000
+        got, want = ctx.reconstruct(*case), O.reconstruct(*case)
+        assert got[0].shape == want[0].shape
+        for a, b in zip(got, want):
+            assert np.array_equal(a, b), (g, axis, residue)
+        assert ctx.n_smoothed == O.LAST_SMOOTHED, (g, axis, residue)
+        most = max(most, ctx.n_smoothed)
+    # Grid size 2 is the one grid that cannot move a point, whatever the cloud: a point moves when cnt * |P - c|^2 + 0.5 >= 2 * max(threshold, cnt), c the trilinear blend of
+    # the eight cell centres (an empty cell counts as P). Along each axis the four cells on P's side of the blend hold coordinates P - 1 .. P (or P .. P + 1) and weigh 3/4
+    # together, the four on the other side lie 1 .. 2 away and weigh 1/4, and the two pull in opposite directions: |P - c| <= 0.75 per axis, |P - c|^2 < 1.6875. That leaves
+    # cnt = 1 (needs 1.5), i.e. fewer than five points in P's own cell (weight 27/64 each), and with so few - P itself among them - the own cell's centre cannot lie far
+    # enough towards one corner on all three axes at once (best case 1.25). 3000 random sparse clouds through smooth_reference moved none either. So 2 is held to the oracle.
+    assert most > 0 or g == 2, "no cloud of grid size %d had a point moved" % g
+
+
+def check_odd_grid_refused(ctx):
+    """rbt.h: grid_size 2..255, even. An odd grid would index one cell past the w^3 cell arrays (rbt_pcc.cpp); it is refused and the context works afterwards"""
+    import oracle_lib as O
+    R = __import__("rbt_lib").module()
+    case = seam_atlas(R, 0, tiles=3)
+    for g in (3, 5, 7, 255):
+        try:
+            ctx.reconstruct(_copy_atlas(R, case[0], grid_size=g), *case[1:])
+            raise AssertionError("grid_size %d accepted" % g)
+        except R.RbtError as e:
+            assert e.code == -4, (g, str(e))                       # RBT_ERR_PARAM
+    got, want = ctx.reconstruct(*case), O.reconstruct(*case)
+    assert got[0].shape[0] > 5000 and all(np.array_equal(a, b) for a, b in zip(got, want)) and ctx.n_smoothed == O.LAST_SMOOTHED > 0
 
 
 def smooth_reference(xyz, boundary, partition, g, threshold):

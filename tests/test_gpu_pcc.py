@@ -122,3 +122,15 @@ def test_geometry_smoothing_random_atlases_and_off_switch(ctx):
     bad = R.ctc_smoothing(case[0]); bad.grid_size = 1
     with pytest.raises(R.RbtError):
         ctx.reconstruct(bad, *case[1:])
+
+
+def test_odd_grid_size_is_refused(ctx):
+    """grid sizes 3, 5, 7 and 255 never reach a kernel (they would index one cell past the cell arrays): RBT_ERR_PARAM, and the context works afterwards"""
+    pcc_cases.check_odd_grid_refused(ctx)
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+@pytest.mark.parametrize("g", pcc_cases.EDGE_GRIDS)
+def test_geometry_smoothing_at_the_edge_of_the_grid(ctx, g, axis):
+    """even grid sizes with the cloud's largest coordinate at every residue modulo the grid size, along each axis in turn (tests/test_pcc_recon.py runs the same on the host)"""
+    pcc_cases.check_grid_edge(ctx, g, axis)

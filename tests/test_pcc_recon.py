@@ -193,3 +193,16 @@ def test_geometry_smoothing_against_a_second_writing_of_the_reference_text(ctx, 
     want = pcc_cases.smooth_reference(plain[0], boundary, part, atlas.grid_size, atlas.threshold_smoothing)
     got = ctx.reconstruct(*case)[0]
     assert np.array_equal(got, want) and (got != plain[0]).any()
+
+
+def test_odd_grid_size_is_refused(ctx):
+    """grid sizes 3, 5, 7 and 255 are refused with RBT_ERR_PARAM (rbt.h: "2..255, even"); one ordinary smoothing afterwards equals the oracle"""
+    pcc_cases.check_odd_grid_refused(ctx)
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+@pytest.mark.parametrize("g", pcc_cases.EDGE_GRIDS)
+def test_geometry_smoothing_at_the_edge_of_the_grid(ctx, g, axis):
+    """the cloud's largest coordinate at every residue modulo the grid size (254: 0, 1, 126, 127, 128, 253), along x, y and z in turn (pcc_cases.edge_atlas): the cells the
+    outermost points blend with are the last ones of the w^3 arrays. Product == oracle for every point and for the count of moved points."""
+    pcc_cases.check_grid_edge(ctx, g, axis)
