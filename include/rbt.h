@@ -205,7 +205,7 @@ typedef struct {             /* host memory, released with rbt_cloud_free */
   int n_points;
   int16_t* xyz;              /* 3 per point, in the order PCCCodec::generatePointCloud emits them */
   uint16_t* yuv;             /* 3 per point: the attribute samples at the point's pixel (chroma at the co-sited 4:2:0 sample; the reference
-                                converts to 4:4:4 first, PccLibColorConverter, out of scope) */
+                                converts to 4:4:4 first, PccLibColorConverter: rbt_reconstruct_rgb does, and returns the 16-bit 4:4:4 triples here) */
   uint8_t* occupancy_map;    /* width x height: the up-scaled, binarised occupancy map */
   uint32_t* block_to_patch;  /* (width / res) x (height / res): patch index + 1 */
   int n_smoothed;            /* points the geometry smoothing moved */
@@ -294,6 +294,39 @@ int rbt_transcode_v3c(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_p
  * writer does not know yet: forcedSsvhUnitSizePrecisionBytes_ = 4 is what fits every file). A non-zero return of the sink ends the walk (RBT_ERR_PARAM; jobs in flight are drained). */
 typedef int (*rbt_v3c_sink)(void* user, int gof, int n_units, const uint8_t* const* unit, const size_t* unit_size);
 int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt_v3c_sink sink, void* user);
+
+/* ---- colour half of the metric: 4:4:4 up-conversion, RGB, colour PSNR (csrc/rbt_color.h) ----
+ * Planar 4:2:0 pictures (samples of bit_depth 8 or 10 in uint16_t) -> n_frames x 3 planes of width x height 16-bit samples, as the decoder converts an attribute video
+ * under the CTC settings: PCCInternalColorConverter::convertYUV420ToYUV444 with g_filter420to444[0] (float round trip, four-tap up-sampling, bit for bit), or the
+ * sample replication of PCCImage::convertYUV420ToYUV444 (values unchanged). width and height even. */
+enum { RBT_UPSAMPLE_REPLICATE = -1, RBT_UPSAMPLE_F0 = 0 };
+int rbt_yuv420_to_yuv444(rbt_ctx* ctx, const uint16_t* yuv420, int width, int height, int bit_depth, int n_frames, int filter, uint16_t* yuv444);
+/* PCCPointSet3::convertYUV16ToRGB8 (PCCPointSet.h:133-166): n triples of 16-bit 4:4:4 samples -> n RGB triples */
+int rbt_yuv16_to_rgb8(rbt_ctx* ctx, const uint16_t* yuv16, int n, uint8_t* rgb);
+/* rbt_reconstruct with the colours as the decoder leaves them: the two attribute pictures are up-converted (upsample_filter: RBT_UPSAMPLE_*), every point takes the three
+ * 4:4:4 samples at its pixel (out->yuv, what colorPointCloud does on the converted video) and these are converted to RGB8 (*rgb: 3 bytes per point, released with rbt_free).
+ * attr_t0 is required (attr_t1 too with two maps); attr_bit_depth 8 or 10. Geometry smoothing moves points, not colours. */
+int rbt_reconstruct_rgb(rbt_ctx* ctx, const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const uint16_t* occ_luma, const uint16_t* geo_d0,
+                        const uint16_t* geo_d1, int geo_bit_depth, const uint16_t* attr_t0, const uint16_t* attr_t1, int attr_bit_depth, int upsample_filter,
+                        rbt_cloud* out, uint8_t** rgb);
+/* Colour metric of QualityMetrics::compute (PCCMetrics.cpp:127-179, :221-225) with the reference's defaults dropDuplicates_ = 2 and neighborsProc_ = 1, both directions:
+ *  - the points of a voxel are merged into one whose channels are sum / count in integer division (PCCPointSet.cpp:190-203);
+ *  - a merged point of P is compared with the mean colour, rounded half up, of ALL merged points of Q at exactly the nearest squared distance (the reference looks at up to
+ *    30 kd-tree results, in its order; here the set does not depend on any order, as in rbt_d2);
+ *  - per channel the error term is the BT.709 row of convertRGBtoYUVBT709 (:50-55) times 10000 applied to the RGB difference, an integer of magnitude <= 2.55e6; sse is the
+ *    sum of its squares, exact in 64 bits for up to 2^21 merged points per cloud (more are refused, RBT_ERR_PARAM);
+ *  - mse = (float)(sse / (2550000^2 n)), psnr = 10 log10f(1 / mse) (getPSNR(mse, 1.0)): identical clouds give mse 0 and psnr +inf.
+ * Coordinates 0..1023. Index 0, 1, 2 = Y, U, V. */
+typedef struct {
+  int n_a, n_b;                            /* points after merging duplicates */
+  uint64_t sse_ab[3], sse_ba[3];           /* exact integers */
+  float mse_ab[3], mse_ba[3], psnr_ab[3], psnr_ba[3], mse[3], psnr[3];   /* mse = the larger, psnr = the smaller of the two directions (PCCMetrics.cpp:321-325) */
+} rbt_color_result;
+int rbt_color_metric(rbt_ctx* ctx, const int16_t* xyz_a, const uint8_t* rgb_a, int n_a, const int16_t* xyz_b, const uint8_t* rgb_b, int n_b, rbt_color_result* out);
+/* Device time in milliseconds (events around the launches) the three stages took in this context's last call of each: [0] up-conversion, [1] RGB conversion,
+ * [2] colour metric (its kernels: insert + merge and distance, without the read-back of the merged counts between them); 0 for a stage that has not run. The stages are
+ * separate launches inside calls that also copy and allocate: this is the only way to time them without a profiling build (tools/color_quality.py). */
+int rbt_color_stage_ms(rbt_ctx* ctx, double ms[3]);
 
 #ifdef __cplusplus
 }

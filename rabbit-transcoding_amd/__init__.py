@@ -73,6 +73,15 @@ class D2Result(C.Structure):
                 ("mse_ab", C.c_float), ("mse_ba", C.c_float), ("psnr_ab", C.c_float), ("psnr_ba", C.c_float), ("psnr", C.c_float)]
 
 
+class ColorResult(C.Structure):
+    """rbt_color_result: [Y, U, V] per field"""
+    _fields_ = [("n_a", C.c_int), ("n_b", C.c_int), ("sse_ab", C.c_uint64 * 3), ("sse_ba", C.c_uint64 * 3)] + \
+               [(n, C.c_float * 3) for n in ("mse_ab", "mse_ba", "psnr_ab", "psnr_ba", "mse", "psnr")]
+
+
+RBT_UPSAMPLE_REPLICATE, RBT_UPSAMPLE_F0 = -1, 0   # rbt_yuv420_to_yuv444 / rbt_reconstruct_rgb: sample replication / g_filter420to444[0], the decoder's default
+
+
 class V3CUnit(C.Structure):
     """rbt_v3c_unit: one unit of a V3C sample stream"""
     _fields_ = [(n, C.c_int) for n in ("type", "gof", "parameter_set_id", "atlas_id", "attribute_index", "attribute_dimension_index", "map_index", "auxiliary_video", "video_type")] + \
@@ -131,6 +140,12 @@ def load(path=None):
     L.rbt_cloud_free.argtypes = [C.POINTER(Cloud)]
     L.rbt_d1.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(D1Result)]
     L.rbt_d2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(D2Result)]
+    L.rbt_yuv420_to_yuv444.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
+    L.rbt_yuv16_to_rgb8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.rbt_reconstruct_rgb.argtypes = [C.c_void_p, C.POINTER(AtlasParams), C.POINTER(Patch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.POINTER(Cloud), C.POINTER(C.c_void_p)]
+    L.rbt_color_metric.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ColorResult)]
+    L.rbt_color_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.rbt_v3c_index.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(V3CUnit)), C.POINTER(C.c_int)]
     L.rbt_v3c_write.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_v3c_stats.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(V3CStat)]
@@ -392,6 +407,53 @@ class Context:
         r = D2Result()
         self._chk(self.L.rbt_d2(self.h, a.ctypes.data, na.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], peak, C.byref(r)))
         return {n: getattr(r, n) for n, _ in D2Result._fields_}
+
+    def yuv420_to_yuv444(self, frames, w, h, bit_depth=10, upsample_filter=RBT_UPSAMPLE_F0):
+        """rbt_yuv420_to_yuv444: planar 4:2:0 pictures ([n, w*h*3/2] uint16, 8 or 10 bits) -> uint16 [n, 3, h, w], 16-bit 4:4:4 as the decoder converts an attribute video
+        (upsample_filter RBT_UPSAMPLE_F0), or the samples replicated with their values unchanged (RBT_UPSAMPLE_REPLICATE)"""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16).reshape(-1, w * h * 3 // 2)
+        out = np.zeros((frames.shape[0], 3, h, w), np.uint16)
+        self._chk(self.L.rbt_yuv420_to_yuv444(self.h, frames.ctypes.data, w, h, bit_depth, frames.shape[0], upsample_filter, out.ctypes.data))
+        return out
+
+    def yuv16_to_rgb8(self, yuv):
+        """rbt_yuv16_to_rgb8: 16-bit 4:4:4 triples (uint16 [n, 3]) -> uint8 [n, 3], PCCPointSet3::convertYUV16ToRGB8"""
+        yuv = np.ascontiguousarray(yuv, dtype=np.uint16).reshape(-1, 3)
+        out = np.zeros((yuv.shape[0], 3), np.uint8)
+        self._chk(self.L.rbt_yuv16_to_rgb8(self.h, yuv.ctypes.data, yuv.shape[0], out.ctypes.data))
+        return out
+
+    def reconstruct_rgb(self, atlas, patches, occ, d0, d1, geo_bd=10, t0=None, t1=None, attr_bd=10, upsample_filter=RBT_UPSAMPLE_F0):
+        """rbt_reconstruct_rgb: reconstruct with the colours as the decoder leaves them -> (xyz, yuv uint16 [n,3] = the 16-bit 4:4:4 samples at each point's pixel,
+        occupancy_map, block_to_patch, rgb uint8 [n,3])"""
+        ps = (Patch * max(1, len(patches)))(*patches)
+        arr = [np.ascontiguousarray(x, dtype=np.uint16) if x is not None else None for x in (occ, d0, d1, t0, t1)]
+        ptr = [x.ctypes.data if x is not None else None for x in arr]
+        c, rgb_p = Cloud(), C.c_void_p()
+        self._chk(self.L.rbt_reconstruct_rgb(self.h, C.byref(atlas), ps, len(patches), ptr[0], ptr[1], ptr[2], geo_bd, ptr[3], ptr[4], attr_bd, upsample_filter, C.byref(c), C.byref(rgb_p)))
+        n, w, h, res = c.n_points, atlas.width, atlas.height, atlas.occupancy_resolution
+        xyz = np.ctypeslib.as_array(c.xyz, shape=(max(n, 1), 3))[:n].copy(); yuv = np.ctypeslib.as_array(c.yuv, shape=(max(n, 1), 3))[:n].copy()
+        om = np.ctypeslib.as_array(c.occupancy_map, shape=(h, w)).copy(); b2p = np.ctypeslib.as_array(c.block_to_patch, shape=(h // res, w // res)).copy()
+        rgb = np.frombuffer(C.string_at(rgb_p, 3 * n), np.uint8).reshape(n, 3).copy()
+        self.n_smoothed = c.n_points and c.n_smoothed
+        self.L.rbt_free(rgb_p); self.L.rbt_cloud_free(C.byref(c))
+        return xyz, yuv, om, b2p, rgb
+
+    def color_metric(self, a, rgb_a, b, rgb_b):
+        """rbt_color_metric: colour PSNR between two clouds (xyz int16 [n,3], rgb uint8 [n,3]) -> dict; every field but n_a / n_b is a list [Y, U, V]"""
+        a = np.ascontiguousarray(a, dtype=np.int16); b = np.ascontiguousarray(b, dtype=np.int16)
+        ca = None if rgb_a is None else np.ascontiguousarray(rgb_a, dtype=np.uint8); cb = None if rgb_b is None else np.ascontiguousarray(rgb_b, dtype=np.uint8)
+        if (ca is not None and ca.shape != a.shape) or (cb is not None and cb.shape != b.shape):
+            raise ValueError("one colour per point")
+        r = ColorResult()
+        self._chk(self.L.rbt_color_metric(self.h, a.ctypes.data, None if ca is None else ca.ctypes.data, a.shape[0], b.ctypes.data, None if cb is None else cb.ctypes.data, b.shape[0], C.byref(r)))
+        return {n: (getattr(r, n) if n in ("n_a", "n_b") else list(getattr(r, n))) for n, _ in ColorResult._fields_}
+
+    def color_stage_ms(self):
+        """rbt_color_stage_ms: device milliseconds of the last up-conversion, RGB conversion and colour metric of this context"""
+        ms = (C.c_double * 3)()
+        self._chk(self.L.rbt_color_stage_ms(self.h, ms))
+        return {"upconvert": ms[0], "rgb": ms[1], "metric": ms[2]}
 
     def selftest_transform32(self, blocks, bit_depth=10):
         """rbt_selftest_transform32: matrix-core vs vector-ALU 32-point transforms on int16 blocks [n, 1024]; returns the number of differing samples"""

@@ -1,0 +1,68 @@
+// Kernels and launchers of the colour stages (rbt_color.h): 4:2:0 -> 4:4:4 up-conversion, YUV16 -> RGB8, colour metric. A translation unit of its own because it is
+// compiled with -ffp-contract=off (Makefile): the up-conversion and the RGB conversion must round every product and every sum on its own, as the reference's host code
+// does, so that their output is the same bits everywhere. No __fmul_rn / __fadd_rn is needed on top of that; the bodies also carry `#pragma clang fp contract(off)`.
+#include <hip/hip_runtime.h>
+#include "rbt_color.h"
+
+namespace rbtk {
+hipStream_t current_stream();            // rbt_kernels.hip: the stream the host code selected (set_stream)
+#define g_stream current_stream()
+
+// grid: x = tile column, y = tile row, z = picture * 3 + plane. LDS per workgroup: sizeof(RbtUpLds), 7.7 KB (the 16-byte output word is built in registers).
+__global__ void __launch_bounds__(RBT_UP_THREADS) k_up444(const uint16_t* in, uint16_t* out, int w, int h, int bd) {
+  __shared__ RbtUpLds lds;
+  const int f = (int)blockIdx.z / 3, c = (int)blockIdx.z - 3 * f;
+  cl_up_tile(in, out, w, h, bd, f, c, (int)blockIdx.x, (int)blockIdx.y, RBT_LDS_CAST(RbtUpLds, &lds));
+}
+__global__ void __launch_bounds__(256) k_replicate(const uint16_t* in, uint16_t* out, int w, int h) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x), f = (int)blockIdx.y / 3, c = (int)blockIdx.y - 3 * f;
+  if (i < w * h) cl_replicate(in, out, w, h, f, c, i);
+}
+__global__ void __launch_bounds__(256) k_yuv16_rgb8(const uint16_t* yuv, int n, uint8_t* rgb) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i < n) cl_yuv16_to_rgb8(yuv + 3 * (size_t)i, rgb + 3 * (size_t)i);
+}
+
+// sum of v over the workgroup's 256 threads, valid in thread 0: shuffles inside the wave, then the four waves through LDS
+__device__ __forceinline__ unsigned long long col_block_sum(unsigned long long v, unsigned long long* part) {
+  for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return part[0] + part[1] + part[2] + part[3];
+}
+__global__ void __launch_bounds__(256) k_col_insert(RbtColSet S, uint32_t* n_unique) {
+  __shared__ unsigned long long part[4];
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  const unsigned long long fresh = i < S.n ? (unsigned long long)cl_insert(&S, i) : 0;
+  const unsigned long long n = col_block_sum(fresh, part);
+  if (threadIdx.x == 0 && n) atomicAdd(n_unique, (uint32_t)n);
+}
+__global__ void __launch_bounds__(256) k_col_merge(RbtColSet S) {
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  if (s < (1u << S.lg)) cl_merge(&S, s);
+}
+// one lane per slot of P's map; per workgroup the three sums are reduced on chip, then one 64-bit integer atomic per workgroup and channel
+__global__ void __launch_bounds__(256) k_col_dist(RbtColSet P, RbtColSet Q, unsigned long long* sse) {
+  __shared__ unsigned long long part[3][4];
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  long long e[3] = {0, 0, 0};
+  if (s < (1u << P.lg)) cl_error(&P, &Q, s, e);
+  for (int c = 0; c < 3; c++) {
+    const unsigned long long t = col_block_sum((unsigned long long)(e[c] * e[c]), part[c]);
+    if (threadIdx.x == 0 && t) atomicAdd(&sse[c], t);
+  }
+}
+
+void launch_up444(const uint16_t* yuv420, int w, int h, int bit_depth, int n_frames, int filter, uint16_t* yuv444) {
+  if (n_frames <= 0) return;
+  if (filter == RBT_UPSAMPLE_REPLICATE) hipLaunchKernelGGL(k_replicate, dim3((unsigned)((w * h + 255) / 256), 3u * (unsigned)n_frames), dim3(256), 0, g_stream, yuv420, yuv444, w, h);
+  else hipLaunchKernelGGL(k_up444, dim3((unsigned)((w + RBT_UP_TW - 1) / RBT_UP_TW), (unsigned)((h + RBT_UP_TH - 1) / RBT_UP_TH), 3u * (unsigned)n_frames), dim3(RBT_UP_THREADS), 0, g_stream,
+                          yuv420, yuv444, w, h, bit_depth);
+}
+void launch_yuv16_rgb8(const uint16_t* yuv, int n, uint8_t* rgb) { if (n > 0) hipLaunchKernelGGL(k_yuv16_rgb8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, yuv, n, rgb); }
+void launch_col_insert(const RbtColSet* S, uint32_t* n_unique) { if (S->n > 0) hipLaunchKernelGGL(k_col_insert, dim3((unsigned)((S->n + 255) / 256)), dim3(256), 0, g_stream, *S, n_unique); }
+void launch_col_merge(const RbtColSet* S) { hipLaunchKernelGGL(k_col_merge, dim3((unsigned)(((1u << S->lg) + 255) / 256)), dim3(256), 0, g_stream, *S); }
+void launch_col_dist(const RbtColSet* P, const RbtColSet* Q, unsigned long long* sse) {
+  hipLaunchKernelGGL(k_col_dist, dim3((unsigned)(((1u << P->lg) + 255) / 256)), dim3(256), 0, g_stream, *P, *Q, sse);
+}
+}  // namespace rbtk

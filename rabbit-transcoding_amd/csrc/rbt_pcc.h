@@ -19,7 +19,7 @@
 #include "../../include/rbt.h"
 
 struct RbtPccParams {            // rbt_atlas_params + derived sizes
-  int32_t w, h, res, prec, map_count, absolute_d1, remove_dup, threshold, geo_bd, attr_bd, bw, bh, ow, n_patches, has_attr, pad;
+  int32_t w, h, res, prec, map_count, absolute_d1, remove_dup, threshold, geo_bd, attr_bd, bw, bh, ow, n_patches, has_attr, pad;   // has_attr: 0 none, 1 planar 4:2:0 pictures, 2 planar 4:4:4 pictures
 };
 enum { RBT_OR_DEFAULT = 0, RBT_OR_SWAP, RBT_OR_ROT180, RBT_OR_MIRROR, RBT_OR_MROT180, RBT_OR_ROT270, RBT_OR_MROT90, RBT_OR_ROT90 };   // PCCCommon.h:128-137
 
@@ -80,7 +80,8 @@ RBT_DEV int pc_pixel_points(const RbtPccParams* P, const rbt_patch* p, const uin
     for (int i = 0; i < n; i++) {
       const int16_t* s = i ? b : a; pts[3 * i] = s[0]; pts[3 * i + 1] = s[1]; pts[3 * i + 2] = s[2];
       const uint16_t* t = i ? t1 : t0;
-      if (P->has_attr) { col[3 * i] = t[(size_t)y * P->w + x]; col[3 * i + 1] = t[ys + co]; col[3 * i + 2] = t[ys + cs + co]; }
+      if (P->has_attr == 2) { const size_t o = (size_t)y * P->w + x; col[3 * i] = t[o]; col[3 * i + 1] = t[ys + o]; col[3 * i + 2] = t[2 * ys + o]; }   // 4:4:4 planes (rbt_reconstruct_rgb): colorPointCloud on the converted video
+      else if (P->has_attr) { col[3 * i] = t[(size_t)y * P->w + x]; col[3 * i + 1] = t[ys + co]; col[3 * i + 2] = t[ys + cs + co]; }
       else col[3 * i] = col[3 * i + 1] = col[3 * i + 2] = (uint16_t)(1 << (P->attr_bd - 1));
     }
   }

@@ -9,7 +9,7 @@
 #include "rbt_pcc.h"
 #include "rbt_internal.h"
 
-struct rbt_ctx { int device, rank, world; rbt_stats stats; std::string last_err; };
+struct rbt_ctx { int device, rank, world; rbt_stats stats; std::string last_err; double color_ms[3] = {0, 0, 0}; };
 struct rbt_job { rbt::GofJob* j; rbt_ctx* owner; };
 
 // Job slots, pipeline depth and the lock are per DEVICE (the 16 HIP streams a job's lanes map onto are the device's, rbt_kernels.hip):
@@ -267,6 +267,42 @@ int rbt_d2(rbt_ctx* ctx, const int16_t* xyz_a, const int16_t* normals_a, int n_a
   if (!ctx || !xyz_a || !normals_a || !xyz_b || !out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   return rbt::pcc_d2(ctx->last_err, xyz_a, normals_a, n_a, xyz_b, n_b, peak, out);
+} RBT_CATCH
+
+// colour half of the metric (csrc/rbt_color.h)
+int rbt_yuv420_to_yuv444(rbt_ctx* ctx, const uint16_t* yuv420, int width, int height, int bit_depth, int n_frames, int filter, uint16_t* yuv444) try {
+  if (!ctx || !yuv420 || !yuv444) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  return rbt::pcc_yuv420_to_yuv444(ctx->last_err, yuv420, width, height, bit_depth, n_frames, filter, yuv444, &ctx->color_ms[0]);
+} RBT_CATCH
+int rbt_yuv16_to_rgb8(rbt_ctx* ctx, const uint16_t* yuv16, int n, uint8_t* rgb) try {
+  if (!ctx || !yuv16 || !rgb) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  return rbt::pcc_yuv16_to_rgb8(ctx->last_err, yuv16, n, rgb, &ctx->color_ms[1]);
+} RBT_CATCH
+int rbt_reconstruct_rgb(rbt_ctx* ctx, const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const uint16_t* occ_luma, const uint16_t* geo_d0,
+                        const uint16_t* geo_d1, int geo_bit_depth, const uint16_t* attr_t0, const uint16_t* attr_t1, int attr_bit_depth, int upsample_filter,
+                        rbt_cloud* out, uint8_t** rgb) {
+  if (!ctx || !atlas || (!patches && n_patches) || !occ_luma || !geo_d0 || !out || !rgb) return RBT_ERR_PARAM;
+  *rgb = nullptr; memset(out, 0, sizeof(*out));
+  int rc;
+  try {                       // whatever the host side throws half way: nothing allocated so far is left behind
+    RBT_ENTER(ctx);
+    rc = rbt::pcc_reconstruct_rgb(ctx->last_err, atlas, patches, n_patches, occ_luma, geo_d0, geo_d1, geo_bit_depth, attr_t0, attr_t1, attr_bit_depth, upsample_filter, out, rgb, ctx->color_ms);
+  } catch (const std::bad_alloc&) { rc = RBT_ERR_NOMEM; } catch (...) { rc = RBT_ERR_NO_DEVICE; }
+  if (rc) { rbt_cloud_free(out); free(*rgb); *rgb = nullptr; }
+  return rc;
+}
+int rbt_color_metric(rbt_ctx* ctx, const int16_t* xyz_a, const uint8_t* rgb_a, int n_a, const int16_t* xyz_b, const uint8_t* rgb_b, int n_b, rbt_color_result* out) try {
+  if (!ctx || !xyz_a || !xyz_b || !out) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  return rbt::pcc_color_metric(ctx->last_err, xyz_a, rgb_a, n_a, xyz_b, rgb_b, n_b, out, &ctx->color_ms[2]);
+} RBT_CATCH
+int rbt_color_stage_ms(rbt_ctx* ctx, double ms[3]) try {
+  if (!ctx || !ms) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  for (int i = 0; i < 3; i++) ms[i] = ctx->color_ms[i];
+  return RBT_OK;
 } RBT_CATCH
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include "rbt_batch.h"
 #include "rbt_pcc.h"
 #include "../csrc/rbt_pcc.h"
+#include "../csrc/rbt_color.h"
 
 namespace rbt {
 namespace {
@@ -24,11 +25,20 @@ int block_xy(const rbt_patch& p, int ub, int vb, int* x, int* y) {       // PCCP
   }
   return 0;
 }
+// device timers of the colour stages (rbt_color_stage_ms), behind the transcoder's (rbt_batch.h)
+enum { T_COL_UP = T_COUNT, T_COL_RGB, T_COL_METRIC, T_COL_DIST };    // the metric in two parts: insert + merge, distance (a read-back of the merged counts lies between them)
+static_assert(T_COL_DIST < 16, "timer slots");
 }  // namespace
 
-int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
-                    const uint16_t* t0, const uint16_t* t1, int attr_bd, rbt_cloud* out) {
+// rgb != nullptr: rbt_reconstruct_rgb - the attribute pictures are up-converted to 4:4:4 on the device first (csrc/rbt_color.h), the colour fetch reads the three planes at the
+// point's pixel (RbtPccParams.has_attr = 2) and the triples are converted to RGB8; stage_ms[0..1]: device time of the up-conversion and of the RGB conversion
+static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
+                            const uint16_t* t0, const uint16_t* t1, int attr_bd, rbt_cloud* out, int filter, uint8_t** rgb, double* stage_ms) {
   memset(out, 0, sizeof(*out));
+  if (rgb) {
+    *rgb = nullptr;
+    if (!t0 || (a->map_count > 1 && !t1) || (attr_bd != 8 && attr_bd != 10) || (filter != RBT_UPSAMPLE_F0 && filter != RBT_UPSAMPLE_REPLICATE)) { err = "attribute pictures of 8 or 10 bits and a known up-sampling filter are needed"; return RBT_ERR_PARAM; }
+  }
   const int W = a->width, H = a->height, res = a->occupancy_resolution, prec = a->occupancy_precision;
   if (W <= 0 || H <= 0 || res < 1 || prec < 1 || W % res || H % res || W % prec || H % prec || W % 2 || H % 2 || W > 8192 || H > 8192 || n_patches < 0 || n_patches > 65535 ||
       geo_bd < 8 || geo_bd > 16 || attr_bd < 8 || attr_bd > 16 || a->map_count < 1 || a->map_count > 2 || (a->map_count > 1 && !d1) || ((t0 != nullptr) != (t1 != nullptr) && a->map_count > 1) ||
@@ -40,7 +50,7 @@ int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch
   const bool smooth = a->geometry_smoothing != 0;
   RbtPccParams P; memset(&P, 0, sizeof(P));
   P.w = W; P.h = H; P.res = res; P.prec = prec; P.map_count = a->map_count; P.absolute_d1 = a->absolute_d1; P.remove_dup = a->remove_duplicate_points; P.threshold = a->threshold_lossy_om;
-  P.geo_bd = geo_bd; P.attr_bd = attr_bd; P.bw = W / res; P.bh = H / res; P.ow = W / prec; P.n_patches = n_patches; P.has_attr = t0 != nullptr;
+  P.geo_bd = geo_bd; P.attr_bd = attr_bd; P.bw = W / res; P.bh = H / res; P.ow = W / prec; P.n_patches = n_patches; P.has_attr = rgb ? 2 : t0 != nullptr;
   // every patch block must lie on the canvas (the reference exits otherwise, PCCPatch.cpp:238-245); items in the reference's visiting order
   std::vector<uint32_t> items;
   for (int pi = 0; pi < n_patches; pi++) {
@@ -55,16 +65,22 @@ int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch
   }
   const int n_items = (int)items.size();
   const size_t ys = (size_t)W * H, os = (size_t)(W / prec) * (H / prec), fs = ys * 3 / 2;
-  DevBuf b_occ, b_d0, b_d1, b_t0, b_t1, b_patches, b_items, b_b2p, b_counts, b_off, b_om, b_xyz, b_yuv, b_meta, b_cells, b_scal;
+  DevBuf b_occ, b_d0, b_d1, b_t0, b_t1, b_patches, b_items, b_b2p, b_counts, b_off, b_om, b_xyz, b_yuv, b_meta, b_cells, b_scal, b_420, b_rgb;
   if (!b_occ.alloc(os * 2) || !b_d0.alloc(ys * 2) || !b_d1.alloc(ys * 2) || !b_patches.alloc(sizeof(rbt_patch) * (size_t)(n_patches ? n_patches : 1)) || !b_items.alloc(4 * (size_t)(n_items ? n_items : 1)) ||
       !b_b2p.alloc(4 * (size_t)P.bw * P.bh) || !b_counts.alloc(4 * (size_t)(n_items + 1)) || !b_off.alloc(4 * (size_t)(n_items + 1)) || !b_om.alloc(ys) ||
-      (t0 && (!b_t0.alloc(fs * 2) || !b_t1.alloc(fs * 2)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+      (t0 && !rgb && (!b_t0.alloc(fs * 2) || !b_t1.alloc(fs * 2))) || (rgb && (!b_420.alloc(fs * 4) || !b_t0.alloc(ys * 12)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
   int bad = rbtk::h2d(b_occ.p, occ, os * 2) | rbtk::h2d(b_d0.p, d0, ys * 2) | rbtk::h2d(b_d1.p, d1 ? d1 : d0, ys * 2);
   if (n_patches) bad |= rbtk::h2d(b_patches.p, patches, sizeof(rbt_patch) * (size_t)n_patches);
   if (n_items) bad |= rbtk::h2d(b_items.p, items.data(), 4 * (size_t)n_items);
-  if (t0) bad |= rbtk::h2d(b_t0.p, t0, fs * 2) | rbtk::h2d(b_t1.p, t1 ? t1 : t0, fs * 2);
+  if (t0 && !rgb) bad |= rbtk::h2d(b_t0.p, t0, fs * 2) | rbtk::h2d(b_t1.p, t1 ? t1 : t0, fs * 2);
+  if (rgb) bad |= rbtk::h2d(b_420.p, t0, fs * 2) | rbtk::h2d(b_420.as<uint16_t>() + fs, t1 ? t1 : t0, fs * 2);
   bad |= rbtk::dev_memset(b_b2p.p, 0, 4 * (size_t)P.bw * P.bh);
   if (bad) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  const uint16_t *p_t0 = b_t0.as<uint16_t>(), *p_t1 = b_t1.as<uint16_t>();
+  if (rgb) {        // both pictures in one launch: 2 x 3 planes of W x H in b_t0
+    rbtk::timer_begin(T_COL_UP); rbtk::launch_up444(b_420.as<uint16_t>(), W, H, attr_bd, 2, filter, b_t0.as<uint16_t>()); rbtk::timer_end(T_COL_UP);
+    p_t1 = p_t0 + 3 * ys;
+  }
   rbtk::launch_pcc_occmap(&P, b_occ.as<uint16_t>(), b_om.as<uint8_t>());
   rbtk::launch_pcc_owner(&P, b_patches.as<rbt_patch>(), b_items.as<uint32_t>(), n_items, b_occ.as<uint16_t>(), b_b2p.as<uint32_t>());
   rbtk::launch_pcc_count(&P, b_patches.as<rbt_patch>(), b_items.as<uint32_t>(), n_items, b_occ.as<uint16_t>(), b_d0.as<uint16_t>(), b_d1.as<uint16_t>(), b_b2p.as<uint32_t>(), b_counts.as<uint32_t>());
@@ -72,7 +88,7 @@ int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch
   uint32_t total = 0;
   if (rbtk::d2h(&total, b_off.as<uint32_t>() + n_items, 4)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
   if (!b_xyz.alloc(6 * (size_t)(total ? total : 1)) || !b_yuv.alloc(6 * (size_t)(total ? total : 1)) || (smooth && (!b_meta.alloc(4 * (size_t)(total ? total : 1)) || !b_scal.alloc(64)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
-  rbtk::launch_pcc_emit(&P, b_patches.as<rbt_patch>(), b_items.as<uint32_t>(), n_items, b_occ.as<uint16_t>(), b_d0.as<uint16_t>(), b_d1.as<uint16_t>(), b_t0.as<uint16_t>(), b_t1.as<uint16_t>(),
+  rbtk::launch_pcc_emit(&P, b_patches.as<rbt_patch>(), b_items.as<uint32_t>(), n_items, b_occ.as<uint16_t>(), b_d0.as<uint16_t>(), b_d1.as<uint16_t>(), p_t0, p_t1,
                         b_b2p.as<uint32_t>(), b_off.as<uint32_t>(), b_xyz.as<int16_t>(), b_yuv.as<uint16_t>(), smooth ? b_om.as<uint8_t>() : nullptr, smooth ? b_meta.as<uint32_t>() : nullptr);
   out->n_points = (int)total;
   // geometry smoothing (PCCCodec::smoothPointCloudPostprocess with gridSmoothing, PCCCodec.cpp:52-145): the grid spans the largest coordinate of the cloud (:70-83)
@@ -101,7 +117,94 @@ int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch
   if (!out->xyz || !out->yuv || !out->occupancy_map || !out->block_to_patch) { err = "out of memory"; return RBT_ERR_NOMEM; }
   bad = rbtk::d2h(out->occupancy_map, b_om.p, ys) | rbtk::d2h(out->block_to_patch, b_b2p.p, 4 * (size_t)P.bw * P.bh);
   if (total) bad |= rbtk::d2h(out->xyz, b_xyz.p, 6 * (size_t)total) | rbtk::d2h(out->yuv, b_yuv.p, 6 * (size_t)total);
+  if (rgb) {
+    *rgb = (uint8_t*)malloc(3 * (size_t)(total ? total : 1));
+    if (!*rgb) { err = "out of memory"; return RBT_ERR_NOMEM; }
+    if (!b_rgb.alloc(3 * (size_t)(total ? total : 1))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    rbtk::timer_begin(T_COL_RGB); rbtk::launch_yuv16_rgb8(b_yuv.as<uint16_t>(), (int)total, b_rgb.as<uint8_t>()); rbtk::timer_end(T_COL_RGB);
+    if (total) bad |= rbtk::d2h(*rgb, b_rgb.p, 3 * (size_t)total);
+  }
   if (bad || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (rgb && stage_ms) { stage_ms[0] = rbtk::timer_ms(T_COL_UP); stage_ms[1] = rbtk::timer_ms(T_COL_RGB); }
+  return RBT_OK;
+}
+int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
+                    const uint16_t* t0, const uint16_t* t1, int attr_bd, rbt_cloud* out) {
+  return reconstruct_impl(err, a, patches, n_patches, occ, d0, d1, geo_bd, t0, t1, attr_bd, out, 0, nullptr, nullptr);
+}
+int pcc_reconstruct_rgb(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
+                        const uint16_t* t0, const uint16_t* t1, int attr_bd, int filter, rbt_cloud* out, uint8_t** rgb, double* stage_ms) {
+  return reconstruct_impl(err, a, patches, n_patches, occ, d0, d1, geo_bd, t0, t1, attr_bd, out, filter, rgb, stage_ms);
+}
+
+int pcc_yuv420_to_yuv444(std::string& err, const uint16_t* in, int w, int h, int bd, int n_frames, int filter, uint16_t* out, double* ms) {
+  if (w <= 0 || h <= 0 || w % 2 || h % 2 || w > 16384 || h > 16384 || n_frames < 1 || n_frames > 21845 || (bd != 8 && bd != 10) || (filter != RBT_UPSAMPLE_F0 && filter != RBT_UPSAMPLE_REPLICATE)) {
+    err = "even picture size, bit depth 8 or 10 and a known up-sampling filter are needed"; return RBT_ERR_PARAM; }
+  const size_t ys = (size_t)w * h, fs = ys * 3 / 2;
+  DevBuf b_in, b_out;
+  if (!b_in.alloc(fs * 2 * n_frames) || !b_out.alloc(ys * 6 * n_frames)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::h2d(b_in.p, in, fs * 2 * n_frames)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::timer_begin(T_COL_UP); rbtk::launch_up444(b_in.as<uint16_t>(), w, h, bd, n_frames, filter, b_out.as<uint16_t>()); rbtk::timer_end(T_COL_UP);
+  if (rbtk::d2h(out, b_out.p, ys * 6 * n_frames) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (ms) *ms = rbtk::timer_ms(T_COL_UP);
+  return RBT_OK;
+}
+int pcc_yuv16_to_rgb8(std::string& err, const uint16_t* yuv, int n, uint8_t* rgb, double* ms) {
+  if (n < 1) { err = "no points"; return RBT_ERR_PARAM; }
+  DevBuf b_in, b_out;
+  if (!b_in.alloc(6 * (size_t)n) || !b_out.alloc(3 * (size_t)n)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::h2d(b_in.p, yuv, 6 * (size_t)n)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::timer_begin(T_COL_RGB); rbtk::launch_yuv16_rgb8(b_in.as<uint16_t>(), n, b_out.as<uint8_t>()); rbtk::timer_end(T_COL_RGB);
+  if (rbtk::d2h(rgb, b_out.p, 3 * (size_t)n) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (ms) *ms = rbtk::timer_ms(T_COL_RGB);
+  return RBT_OK;
+}
+
+// QualityMetrics::compute with computeColor_ (PCCMetrics.cpp:127-179, :221-225) both ways (:321-325) on merged clouds: csrc/rbt_color.h
+int pcc_color_metric(std::string& err, const int16_t* a, const uint8_t* rgb_a, int na, const int16_t* b, const uint8_t* rgb_b, int nb, rbt_color_result* out, double* ms) {
+  memset(out, 0, sizeof(*out));
+  if (na <= 0 || nb <= 0 || !rgb_a || !rgb_b) { err = "empty point cloud or no colours"; return RBT_ERR_PARAM; }
+  for (int i = 0; i < 3 * na; i++) if (a[i] < 0 || a[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
+  for (int i = 0; i < 3 * nb; i++) if (b[i] < 0 || b[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
+  const size_t vol_bytes = (size_t)1 << (3 * RBT_PCC_BITS - 3);
+  auto lg_of = [](int n) { int lg = 4; while (((size_t)1 << lg) < 2 * (size_t)n) lg++; return lg; };
+  const int lga = lg_of(na), lgb = lg_of(nb);
+  DevBuf va, vb, pa, pb, ca, cb, ka, kb, aa, ab, ma, mb, res;
+  if (!va.alloc(vol_bytes) || !vb.alloc(vol_bytes) || !pa.alloc(6 * (size_t)na) || !pb.alloc(6 * (size_t)nb) || !ca.alloc(3 * (size_t)na) || !cb.alloc(3 * (size_t)nb) ||
+      !ka.alloc((size_t)4 << lga) || !kb.alloc((size_t)4 << lgb) || !aa.alloc((size_t)16 << lga) || !ab.alloc((size_t)16 << lgb) || !ma.alloc((size_t)4 << lga) || !mb.alloc((size_t)4 << lgb) ||
+      !res.alloc(64)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  int bad = rbtk::dev_memset(va.p, 0, vol_bytes) | rbtk::dev_memset(vb.p, 0, vol_bytes) | rbtk::dev_memset(ka.p, 0, (size_t)4 << lga) | rbtk::dev_memset(kb.p, 0, (size_t)4 << lgb) |
+            rbtk::dev_memset(aa.p, 0, (size_t)16 << lga) | rbtk::dev_memset(ab.p, 0, (size_t)16 << lgb) | rbtk::dev_memset(ma.p, 0, (size_t)4 << lga) | rbtk::dev_memset(mb.p, 0, (size_t)4 << lgb) |
+            rbtk::dev_memset(res.p, 0, 64) | rbtk::h2d(pa.p, a, 6 * (size_t)na) | rbtk::h2d(pb.p, b, 6 * (size_t)nb) | rbtk::h2d(ca.p, rgb_a, 3 * (size_t)na) | rbtk::h2d(cb.p, rgb_b, 3 * (size_t)nb);
+  if (bad) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  RbtColSet A{pa.as<int16_t>(), ca.as<uint8_t>(), na, lga, va.as<uint32_t>(), ka.as<uint32_t>(), aa.as<uint32_t>(), ma.as<uint32_t>()};
+  RbtColSet B{pb.as<int16_t>(), cb.as<uint8_t>(), nb, lgb, vb.as<uint32_t>(), kb.as<uint32_t>(), ab.as<uint32_t>(), mb.as<uint32_t>()};
+  // res: u64 [0..2] sse_ab, [3..5] sse_ba; u32 [12] merged points of a, [13] of b
+  unsigned long long* r64 = res.as<unsigned long long>(); uint32_t* r32 = res.as<uint32_t>();
+  rbtk::timer_begin(T_COL_METRIC);
+  rbtk::launch_col_insert(&A, r32 + 12); rbtk::launch_col_insert(&B, r32 + 13);
+  rbtk::launch_col_merge(&A); rbtk::launch_col_merge(&B);
+  rbtk::timer_end(T_COL_METRIC);
+  if (ms) *ms = 0;
+  uint32_t cnt[2];
+  if (rbtk::d2h(cnt, r32 + 12, 8)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  // |error term| <= 2.55e6: the sum of 2^21 squares still fits 64 bits
+  if (cnt[0] > (1u << 21) || cnt[1] > (1u << 21)) { rbtk::dev_sync(); err = "more than 2^21 merged points"; return RBT_ERR_PARAM; }
+  rbtk::timer_begin(T_COL_DIST);
+  rbtk::launch_col_dist(&A, &B, r64); rbtk::launch_col_dist(&B, &A, r64 + 3);
+  rbtk::timer_end(T_COL_DIST);
+  uint64_t h[8];
+  if (rbtk::d2h(h, res.p, 64) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (ms) *ms = rbtk::timer_ms(T_COL_METRIC) + rbtk::timer_ms(T_COL_DIST);      // kernels only: the read-back between the two parts is not in it
+  out->n_a = (int)cnt[0]; out->n_b = (int)cnt[1];
+  const double unit = 2550000.0 * 2550000.0;
+  for (int c = 0; c < 3; c++) {
+    out->sse_ab[c] = h[c]; out->sse_ba[c] = h[3 + c];
+    out->mse_ab[c] = (float)((double)h[c] / (unit * (double)out->n_a)); out->mse_ba[c] = (float)((double)h[3 + c] / (unit * (double)out->n_b));
+    out->psnr_ab[c] = 10 * log10f(1.0f / out->mse_ab[c]); out->psnr_ba[c] = 10 * log10f(1.0f / out->mse_ba[c]);
+    out->mse[c] = out->mse_ab[c] > out->mse_ba[c] ? out->mse_ab[c] : out->mse_ba[c];
+    out->psnr[c] = out->psnr_ab[c] < out->psnr_ba[c] ? out->psnr_ab[c] : out->psnr_ba[c];
+  }
   return RBT_OK;
 }
 
