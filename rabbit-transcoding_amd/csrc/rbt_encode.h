@@ -460,9 +460,9 @@ RBT_DEV void en_fill_cu_maps_ctx(const EnCtbCtx* e, int x0, int y0, int N, int p
   RBT_PAR_FOR(i, n8 * n8) { const int k = ((y0 >> 3) + i / n8) * e->w8 + (x0 >> 3) + i % n8; e->cu_flags[k] = (uint8_t)flags; }
 }
 // one intra TB: (x0,y0) relative to the CTB and (gx,gy) in the picture, both in samples of component c_idx; returns cbf
-template <int TL2> RBT_DEV int en_tile_intra_tb(const RbtStreamCfg* g, RbtFrame* f, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int c_idx, int x0, int y0, int gx, int gy, int log2, int mode, int qp,
+template <int TL2> RBT_DEV int en_tile_intra_tb(const EnCtbCtx* e, RbtFrame* f, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int c_idx, int x0, int y0, int gx, int gy, int log2, int mode, int qp,
                              const RBT_LDS_AS uint16_t* src, int mark_l4, int mux, int muy, RBT_LDS_AS int16_t* lvl_buf = nullptr, long long* cost = nullptr, int lam2 = 0, int* ssd_out = nullptr, int* ts_out = nullptr, int reuse_nb = 0) {
-  const EnCtbCtx* e = static_cast<const EnCtbCtx*>(g);                 // every caller hands an EnCtbCtx in (en_intra_ctb)
+  const RbtStreamCfg* g = e;
   RBT_LDS_AS RbtEncIntraScratch* r = &L->rc; RBT_LDS_AS RbtEncTileT<TL2>* t = &L->t;
   // lvl_buf: where the levels go (default: over the luma part of `sb`, i.e. over the source once the residual is formed). cost (needs a lvl_buf that leaves
   // `src` alone): distortion * 256 + lam2 * rate of the block as the oracle's recon_tb / hm_decide_tu_split count them - squared error of the residual
@@ -597,8 +597,8 @@ template <int TL2> RBT_DEV int en_tile_intra_tb(const RbtStreamCfg* g, RbtFrame*
 // and DC - distinct ones, in that order - predicted from the RECONSTRUCTED neighbours in the tile; cost = 16 * SATD + lambda * bits (2 for the first most
 // probable mode, 3 for the other two, 6 otherwise), ties keep the earlier candidate. src: the CU's source samples, row stride N.
 // *second: the runner-up (the first of the cheapest among the other candidates; -1 if there is only one), *bits_best / *bits_second: their mode bits - for the coded trial
-template <int TL2> RBT_DEV int en_refine_mode(const RbtStreamCfg* g, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int x0, int y0, int lg, int an_mode, int ca, int cb, int lam16, const RBT_LDS_AS uint16_t* src, int* second, int* bits_best, int* bits_second) {
-  RBT_LDS_AS RbtEncIntraScratch* r = &L->rc; RBT_LDS_AS RbtEncTileT<TL2>* t = &L->t;
+template <int TL2> RBT_DEV int en_refine_mode(const EnCtbCtx* e, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int x0, int y0, int lg, int an_mode, int ca, int cb, int lam16, const RBT_LDS_AS uint16_t* src, int* second, int* bits_best, int* bits_second) {
+  const RbtStreamCfg* g = e; RBT_LDS_AS RbtEncIntraScratch* r = &L->rc; RBT_LDS_AS RbtEncTileT<TL2>* t = &L->t;
   RBT_LDS_AS int32_t* const r_nbf = (RBT_LDS_AS int32_t*)r->tmp; RBT_LDS_AS int32_t* const r_ref = r_nbf + 132;
   const int N = 1 << lg, bd = g->bit_depth, n4 = (1 << g->log2_ctb) >> 2, S = RbtEncTileT<TL2>::TS_Y;
   int m0, m1, m2;
@@ -649,14 +649,14 @@ template <int TL2> RBT_DEV int en_refine_mode(const RbtStreamCfg* g, RBT_LDS_AS 
 // cbf of quarter i in bit i. On return the tile holds the chosen reconstruction, the coefficient plane the chosen levels and every 4x4 unit of the CU
 // is marked available.
 // have_whole: the coded mode trial has just coded the CU as one block with this mode (levels in lv0, reconstruction in the tile, cost / distortion / cbf handed in)
-template <int TL2> RBT_DEV int en_intra_cu_luma(const RbtStreamCfg* g, RbtFrame* f, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int x0, int y0, int gx, int gy, int lg, int mode, int qp, int lam2, int* split, int* ts_bits,
+template <int TL2> RBT_DEV int en_intra_cu_luma(const EnCtbCtx* e, RbtFrame* f, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int x0, int y0, int gx, int gy, int lg, int mode, int qp, int lam2, int* split, int* ts_bits,
                                               int have_whole = 0, long long c_whole_in = 0, int ssd0_in = 0, int cbf0_in = 0, int reuse_nb = 0) {
-  const EnCtbCtx* e = static_cast<const EnCtbCtx*>(g);                 // every caller hands an EnCtbCtx in (en_intra_ctb)
+  const RbtStreamCfg* g = e;
   RBT_LDS_AS RbtEncTileT<TL2>* t = &L->t;
   const int N = 1 << lg, h = N >> 1, S = RbtEncTileT<TL2>::TS_Y;
   long long c_whole = c_whole_in, c_split = 3ll * lam2, cq = 0;
   int ssd0 = ssd0_in, cbf0 = cbf0_in;
-  if (!have_whole) cbf0 = en_tile_intra_tb(g, f, L, 0, x0, y0, gx, gy, lg, mode, qp, t->sb, -1, 0, 0, t->lv0, &c_whole, lam2, &ssd0, nullptr, reuse_nb);
+  if (!have_whole) cbf0 = en_tile_intra_tb(e, f, L, 0, x0, y0, gx, gy, lg, mode, qp, t->sb, -1, 0, 0, t->lv0, &c_whole, lam2, &ssd0, nullptr, reuse_nb);
   *split = 0; *ts_bits = 0;
   if ((RBT_ABLATE & 0x10000) || (!e->lossless && (long long)ssd0 * 256 < (long long)(lam2 >> 2) * N * N)) {     // coded to within lambda^2 / 4 per sample by one transform: not tried as four (lossless: the bits alone decide)
     RBT_PAR_FOR(i, 1 << (2 * (lg - 2))) t->uav[((y0 >> 2) + (i >> (lg - 2)) + 1) * RC_US + (x0 >> 2) + (i & ((1 << (lg - 2)) - 1)) + 1] = 1;
@@ -671,7 +671,7 @@ template <int TL2> RBT_DEV int en_intra_cu_luma(const RbtStreamCfg* g, RbtFrame*
     RBT_PAR_FOR(i, h * h) t->ss[i] = t->sb[(oy + (i >> (lg - 1))) * N + ox + (i & (h - 1))];
     RBT_SYNC_LDS();
     int ts = 0;
-    if (en_tile_intra_tb(g, f, L, 0, x0 + ox, y0 + oy, gx + ox, gy + oy, lg - 1, mode, qp, t->ss, lg - 3, (x0 + ox) >> 2, (y0 + oy) >> 2, t->lv1, &cq, lam2, nullptr, (lg == 3 && g->transform_skip) ? &ts : nullptr)) cbf1 |= 1 << b;
+    if (en_tile_intra_tb(e, f, L, 0, x0 + ox, y0 + oy, gx + ox, gy + oy, lg - 1, mode, qp, t->ss, lg - 3, (x0 + ox) >> 2, (y0 + oy) >> 2, t->lv1, &cq, lam2, nullptr, (lg == 3 && g->transform_skip) ? &ts : nullptr)) cbf1 |= 1 << b;
     tsm |= ts << b;
     c_split += cq;
   }
@@ -683,9 +683,9 @@ template <int TL2> RBT_DEV int en_intra_cu_luma(const RbtStreamCfg* g, RbtFrame*
   return cbf0;
 }
 // Cb and Cr TB of one CU in the same passes (see rc_tile_tb_cpair); returns cbf_cb | cbf_cr << 1. src: Cb block, then Cr at +256.
-template <int TL2> RBT_DEV int en_tile_intra_tb_cpair(const RbtStreamCfg* g, RbtFrame* f, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int x0, int y0, int gx, int gy, int log2, int mode, int qp_cb, int qp_cr,
+template <int TL2> RBT_DEV int en_tile_intra_tb_cpair(const EnCtbCtx* e, RbtFrame* f, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int x0, int y0, int gx, int gy, int log2, int mode, int qp_cb, int qp_cr,
                                    const RBT_LDS_AS uint16_t* src) {
-  const EnCtbCtx* e = static_cast<const EnCtbCtx*>(g);                 // every caller hands an EnCtbCtx in (en_intra_ctb)
+  const RbtStreamCfg* g = e;
   RBT_LDS_AS RbtEncIntraScratch* r = &L->rc; RBT_LDS_AS RbtEncTileT<TL2>* t = &L->t;
   RBT_LDS_AS int32_t* const r_ref = (RBT_LDS_AS int32_t*)r->tmp + 132; RBT_LDS_AS int32_t* const r_ref2 = r_ref + 100; RBT_LDS_AS int16_t* const lvl = (RBT_LDS_AS int16_t*)t->sb;
   const int N = 1 << log2, NN = N * N, bd = g->bit_depth, maxv = (1 << bd) - 1, n4 = (1 << g->log2_ctb) >> 2, pw = g->cw, S = RbtEncTileT<TL2>::TS_C;
@@ -848,14 +848,14 @@ template <int TL2> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices
     if (refine) {
       const int ca = x0 > 0 ? (int)t->cu_md[uy * 8 + ux - 1] : (t->left_md[8] ? (int)t->left_md[uy] : 1), cb = y0 > 0 ? (int)t->cu_md[(uy - 1) * 8 + ux] : 1;   // above: inside this CTB only (8.4.2)
       int second, b1, b2;
-      mode = en_refine_mode<TL2>(g, L, x0, y0, lg, mode, RBT_UNI(ca), RBT_UNI(cb), lam16, t->sb, &second, &b1, &b2);
+      mode = en_refine_mode<TL2>(e, L, x0, y0, lg, mode, RBT_UNI(ca), RBT_UNI(cb), lam16, t->sb, &second, &b1, &b2);
       if (rdm && second >= 0 && lg >= 4) {
         // the SATD says which two modes to look at, the coded block which of them to take (oracle/hevc_enc.c e1_mode_trial; ties: the SATD's choice; 16x16 and 32x32 CUs
         // only: on 8x8 CUs, more than half of all, the trial moved nothing). The runner-up first:
         // when the SATD's choice stands - most of the time - its block is already coded and en_intra_cu_luma goes straight on to the four-way form
         long long c2 = 0;
-        en_tile_intra_tb(g, f, L, 0, x0, y0, cx + x0, cy + y0, lg, second, qp_l, t->sb, -2, 0, 0, t->lv0, &c2, lam2, nullptr, nullptr, 1);
-        cbf_w = en_tile_intra_tb(g, f, L, 0, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, t->sb, -1, 0, 0, t->lv0, &c_w, lam2, &ssd_w, nullptr, 1);
+        en_tile_intra_tb(e, f, L, 0, x0, y0, cx + x0, cy + y0, lg, second, qp_l, t->sb, -2, 0, 0, t->lv0, &c2, lam2, nullptr, nullptr, 1);
+        cbf_w = en_tile_intra_tb(e, f, L, 0, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, t->sb, -1, 0, 0, t->lv0, &c_w, lam2, &ssd_w, nullptr, 1);
         if (c2 + (long long)lam2 * b2 < c_w + (long long)lam2 * b1) mode = second; else have_w = 1;
       }
       const int nu = N >> 3;
@@ -863,8 +863,8 @@ template <int TL2> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices
       RBT_SYNC_LDS();
     }
     int split = 0, cbf = 0, cy4 = 0, ts_bits = 0;
-    if (tu_rd) cy4 = en_intra_cu_luma(g, f, L, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, lam2, &split, &ts_bits, have_w, c_w, ssd_w, cbf_w, refine != 0);      // after the mode choice r->nb holds the CU's references
-    else cy4 = en_tile_intra_tb(g, f, L, 0, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, t->sb, lg - 2, x0 >> 2, y0 >> 2);
+    if (tu_rd) cy4 = en_intra_cu_luma(e, f, L, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, lam2, &split, &ts_bits, have_w, c_w, ssd_w, cbf_w, refine != 0);      // after the mode choice r->nb holds the CU's references
+    else cy4 = en_tile_intra_tb(e, f, L, 0, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, t->sb, lg - 2, x0 >> 2, y0 >> 2);
     if (split && lg >= 4) {
       // four transform units, each with its own Cb / Cr blocks: chroma block b is predicted when the units 0..b of the CU are reconstructed, not more
       const int hh = N >> 1, hc = Nc >> 1, n4u = hh >> 2;
@@ -875,13 +875,13 @@ template <int TL2> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices
         RBT_PAR_FOR(i, n4u * n4u) t->uav[(((y0 + oy) >> 2) + i / n4u + 1) * RC_US + ((x0 + ox) >> 2) + i % n4u + 1] = 1;
         RBT_PAR_FOR(i, 2 * hc * hc) { const int q = i >= hc * hc, j = i - q * hc * hc; t->ss[q * 256 + j] = t->sb[1024 + 256 * q + ((oy >> 1) + j / hc) * Nc + (ox >> 1) + j % hc]; }
         RBT_SYNC_LDS();
-        const int cc = en_tile_intra_tb_cpair(g, f, L, (x0 + ox) >> 1, (y0 + oy) >> 1, (cx + x0 + ox) >> 1, (cy + y0 + oy) >> 1, lg - 2, mode, qp_cb, qp_cr, t->ss);
+        const int cc = en_tile_intra_tb_cpair(e, f, L, (x0 + ox) >> 1, (y0 + oy) >> 1, (cx + x0 + ox) >> 1, (cy + y0 + oy) >> 1, lg - 2, mode, qp_cb, qp_cr, t->ss);
         const int fl = RBT_CU_TU_SPLIT | ((cy4 >> b) & 1 ? RBT_CU_CBF_Y : 0) | ((cc & 1) ? RBT_CU_CBF_CB : 0) | ((cc & 2) ? RBT_CU_CBF_CR : 0);
         en_fill_cu_maps_ctx(e, cx + x0 + ox, cy + y0 + oy, hh, RBT_MODE_INTRA | ((fl & RBT_CU_CBF_Y) ? RBT_PM_NZ : 0), qp_y, fl);
       }
       continue;
     }
-    { const int cc = en_tile_intra_tb_cpair(g, f, L, x0 >> 1, y0 >> 1, (cx + x0) >> 1, (cy + y0) >> 1, lg - 1, mode, qp_cb, qp_cr, t->sb + 1024);
+    { const int cc = en_tile_intra_tb_cpair(e, f, L, x0 >> 1, y0 >> 1, (cx + x0) >> 1, (cy + y0) >> 1, lg - 1, mode, qp_cb, qp_cr, t->sb + 1024);
       if (cc & 1) cbf |= RBT_CU_CBF_CB;
       if (cc & 2) cbf |= RBT_CU_CBF_CR; }
     if (split) cbf |= RBT_CU_TU_SPLIT | ((cy4 & 1) ? RBT_CU_CBF_Y : 0) | ((cy4 >> 1) * RBT_CU_CBF_Y1);   // 8x8 CU as four 4x4 luma blocks: their cbf bits

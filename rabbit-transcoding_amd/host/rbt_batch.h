@@ -32,13 +32,30 @@ struct HashSet {
   ~HashSet() { rbtk::dev_free(d); }
 };
 
-
 enum { T_PARSE = 0, T_RECON = 1, T_FILTER = 2, T_ANALYSE = 3, T_ENCODE = 4, T_ENTROPY = 5, T_ALL = 6, T_POOL = 7, T_INTER = 8, T_ENTROPY_I = 9, T_COUNT = 10 };
 
-struct Arena {           // bump allocator over one device allocation
-  uint8_t* base = nullptr; size_t size = 0, used = 0;
-  size_t reserve(size_t n) { size_t o = (used + 255) & ~(size_t)255; used = o + n; return o; }
+// Bump allocator over one device allocation, every buffer on a multiple of 256 bytes. A batch names each buffer of its arena once, in a layout function (decode_lay_out,
+// encode_lay_out) that runs twice: without a base it only counts (take() gives nullptr, `used` ends as the size), over the allocated block it hands out the pointers.
+struct Arena {
+  uint8_t* base = nullptr; size_t used = 0;
+  size_t mark() { return used = (used + 255) & ~(size_t)255; }          // where the next buffer will start
+  template <class T> T* take(size_t count) { const size_t o = mark(); used = o + count * sizeof(T); return base ? (T*)(base + o) : nullptr; }
+  // the three planes of a 4:2:0 picture (ys luma, cs chroma samples each) are one buffer: a new one, or one that exists elsewhere
+  template <class T> void take_planes(T* p[3], size_t ys, size_t cs) { same_planes(p, take<T>(ys + 2 * cs), ys, cs); }
+  template <class T> static void same_planes(T* p[3], T* first, size_t ys, size_t cs) { p[0] = first; p[1] = first ? first + ys : nullptr; p[2] = first ? first + ys + cs : nullptr; }
+  static uint8_t* up256(uint8_t* p) { return (uint8_t*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 };
+// One reconstruction launch of a dependency level (launch_recon). recon_level_of fills the counts; whoever owns the memory binds the pointers (decode_lay_out for a batch's
+// own levels, launch_merged in rbt_transcode.cpp for levels merged across batches).
+struct DecodeBatch;
+struct LevelPic { const DecodeBatch* b; int frame; };
+struct ReconLevel {
+  RbtFrame* frames = nullptr; const RbtSlice* slices = nullptr; const int32_t* list = nullptr;   // the pictures as a frame list of one batch (an own level), nullptr for a merged level
+  const RbtFrameRef* refs = nullptr; int n = 0, w_ctb = 0, h_ctb = 0;                           // ... as RbtFrameRef; their number; the largest picture
+  uint32_t ctbs = 0; int queue_wgs = 0; uint32_t* queue = nullptr; uint32_t* ticket = nullptr;   // ready queue: CTBs of all pictures, workgroups, recon_queue_words(ctbs) zeroed words; flag form: a zeroed word
+};
+// DecodeBatch::d_tickets, zeroed words: flag launch of the batch's own level l / of merged level l (in the lead batch), ordered hand-out of the parse tasks of level l / of a merged parse launch
+enum { TICKET_OWN_LEVEL = 0, TICKET_MERGED_LEVEL = 32, TICKET_PARSE = 64, TICKET_MERGED_PARSE = 96, TICKET_WORDS = 128, MAX_LEVELS = 32 };
 
 struct DecodeBatch {
   std::vector<uint8_t> rbsp;
@@ -54,10 +71,10 @@ struct DecodeBatch {
   std::vector<size_t> fr_off;          // offset of each level's frame list inside d_lists
   std::vector<size_t> sl_off, sl_cnt;  // slice list of each level inside d_lists
   std::vector<uint32_t> order_keep; std::vector<size_t> order_off;   // CTB dependency order per picture (host staging, offset per frame)
-  std::vector<RbtFrameRef> refs_keep; std::vector<size_t> refs_off;   // the pictures of each level as RbtFrameRef (launch_recon_level)
+  std::vector<RbtFrameRef> refs_keep;   // the pictures of every level as RbtFrameRef, level by level (host staging)
+  std::vector<ReconLevel> levels;       // the reconstruction launch of each level
   bool has_row_tasks = false;      // some segment of a wavefront stream is parsed by a wave of its own (ordered hand-out of the parse tasks, no banded parsing)
-  uint32_t* d_queue = nullptr; std::vector<size_t> queue_off; std::vector<uint32_t> queue_total; std::vector<int> queue_wgs;   // ready queues of the levels (launch_recon_queue): offset in words, CTBs, workgroups
-  uint32_t* d_order = nullptr; RbtFrameRef* d_refs = nullptr; uint32_t* d_tickets = nullptr;   // one ticket counter per level + spare ones for merged launches
+  uint32_t* d_order = nullptr; RbtFrameRef* d_refs = nullptr; uint32_t* d_tickets = nullptr;   // d_tickets: TICKET_WORDS counters (TICKET_* above)
   void* d_save = nullptr;              // RbtParseSave per slice (resumable parsing), zero-initialised; nullptr when not requested
   bool want_save = false;              // set before decode_build to reserve d_save
   void* arena = nullptr; size_t arena_size = 0;
@@ -68,9 +85,10 @@ struct DecodeBatch {
 };
 
 int decode_build(DecodeBatch& b, const StreamIn* streams, int n);
-bool recon_by_diagonals();           // per-diagonal launches instead of the flag kernel (see rbt_decode.cpp)
 int recon_mode();                    // 0 = one launch per anti-diagonal, 1 = one launch per level with neighbour flags, 2 = one launch per level with a ready queue (rbt_decode.cpp)
-int recon_queue_width(const RbtStreamCfg& c);   // CTBs of a picture that can be reconstructed side by side, on average (workgroups the ready-queue launch gets per picture)
+ReconLevel recon_level_of(const std::vector<LevelPic>& pics, std::vector<RbtFrameRef>* refs = nullptr);   // counts of the level made of `pics`; with `refs`, the pictures are appended there (their batches must be laid out)
+int recon_mode_for(const ReconLevel* lv, size_t n);   // recon_mode() for these levels: by diagonals if one of them is too large for the ready queue's 31-bit entries
+void launch_recon(const ReconLevel& lv, int mode);   // the only caller of the level-wide reconstruction launches of rbt_kernels.h
 void recon_set_depth(int depth);     // jobs the caller keeps in flight (rbt_set_depth)
 int decode_launch(DecodeBatch& b);   // enqueue every decode kernel of the batch on the current stream (no wait)
 int decode_launch_parse(DecodeBatch& b);            // index lists + entropy decoding

@@ -11,14 +11,67 @@ size_t frame_samples(const RbtStreamCfg& c) { return (size_t)c.w * c.h + 2 * (si
 
 struct DpbEntry { int poc, frame; };
 
+// index lists: slices grouped by level, frames grouped by level
+static void build_lists(DecodeBatch& b) {
+  std::vector<size_t>& sl_off = b.sl_off; std::vector<size_t>& sl_cnt = b.sl_cnt; sl_off.clear(); sl_cnt.clear();
+  std::vector<int32_t>& lists = b.lists_keep; lists.clear(); b.fr_off.clear();
+  for (auto& lf : b.level_frames) {
+    sl_off.push_back(lists.size());
+    for (int fi : lf) for (int k = 0; k < b.frames[fi].n_slices; k++) lists.push_back(b.frames[fi].first_slice + k);
+    sl_cnt.push_back(lists.size() - sl_off.back());
+  }
+  for (auto& lf : b.level_frames) { b.fr_off.push_back(lists.size()); for (int fi : lf) lists.push_back(fi); }
+}
+static RbtFrameRef frame_ref(const DecodeBatch& b, int fi) { return RbtFrameRef{b.d_frames, b.d_slices, b.d_order + b.order_off[fi], fi, 0}; }
+
+// HBM layout of a decode batch: [zero region | pm region (RBT_MODE_NONE) | ctb_slice region (0xFF) | rest, the rows' hand-over block (zeroed on its own) inside it].
+// Every buffer of the arena is named here, once (Arena in rbt_batch.h: run without a base to measure, then over the allocation to bind); returns the extents to fill.
+struct DecodeFill { size_t zero_end, pm_begin, pm_end, cs_begin, cs_end, prow_begin, prow_end; };
+static DecodeFill decode_lay_out(DecodeBatch& b, Arena& a) {
+  DecodeFill m; const size_t nf = b.frames.size(), ns = b.slices.size();
+  auto wpp = [&](size_t i) { return b.stream_pps[b.info[i].stream].entropy_coding_sync != 0; };
+  for (size_t i = 0; i < nf; i++) { RbtFrame& f = b.frames[i]; const RbtStreamCfg& c = f.cfg; const size_t ys = (size_t)c.w * c.h, cs = (size_t)c.cw * c.ch, u = (size_t)c.w4 * c.h4, nc = (size_t)c.w_ctb * c.h_ctb;
+    a.take_planes(f.coef, ys, cs); f.edges = a.take<uint8_t>(u); f.cmd_count = a.take<uint32_t>(nc); f.ctb_done = a.take<uint32_t>(nc * 2); }
+  b.d_tickets = a.take<uint32_t>(TICKET_WORDS);
+  // ready queues of the reconstruction levels (launch_recon_queue), zeroed with the rest of this region
+  size_t queue_words = 0; for (const ReconLevel& lv : b.levels) queue_words += rbtk::recon_queue_words(lv.ctbs);
+  uint32_t* d_queue = a.take<uint32_t>(queue_words);
+  // wavefront streams: progress counters of the CTB rows (zeroed with the rest of this region)
+  for (size_t i = 0; i < nf; i++) if (wpp(i)) b.frames[i].prow_done = a.take<uint32_t>((size_t)b.frames[i].cfg.h_ctb);
+  b.d_save = b.want_save ? a.take<uint8_t>(ns * rbtk::parse_save_bytes()) : nullptr;
+  m.zero_end = m.pm_begin = a.mark();
+  for (size_t i = 0; i < nf; i++) { const RbtStreamCfg& c = b.frames[i].cfg; b.frames[i].pm = a.take<uint8_t>((size_t)c.w4 * c.h4); }
+  m.pm_end = m.cs_begin = a.mark();
+  for (size_t i = 0; i < nf; i++) { const RbtStreamCfg& c = b.frames[i].cfg; b.frames[i].ctb_slice = a.take<uint16_t>((size_t)c.w_ctb * c.h_ctb); }
+  m.cs_end = a.mark();
+  for (size_t i = 0; i < nf; i++) {
+    RbtFrame& f = b.frames[i]; const RbtStreamCfg& c = f.cfg; const size_t ys = (size_t)c.w * c.h, cs = (size_t)c.cw * c.ch, u = (size_t)c.w4 * c.h4, nc = (size_t)c.w_ctb * c.h_ctb;
+    a.take_planes(f.pix, ys, cs);
+    if (b.info[i].sao) a.take_planes(f.out, ys, cs); else Arena::same_planes(f.out, f.pix[0], ys, cs);      // no SAO: the deblocked picture is the output
+    f.dm = a.take<uint8_t>(u); f.qp = a.take<int8_t>(u); f.mv = a.take<int16_t>(u * 2); f.ref = a.take<int8_t>(u); f.refpoc = a.take<int32_t>(u);
+    f.sao = a.take<RbtSao>(nc); f.cmds = a.take<RbtCmd>(nc * (size_t)f.cmd_cap);
+  }
+  m.prow_begin = a.mark();     // the rows' hand-over records (one block, zeroed per job: recycled pool memory must not pass for the state of a row nobody parsed)
+  for (size_t i = 0; i < nf; i++) if (wpp(i)) { RbtFrame& f = b.frames[i]; const size_t rows = (size_t)f.cfg.h_ctb;     // (256 spare bytes each: the records start on a 256-byte address whatever the base)
+    f.prow_ctx = Arena::up256(a.take<uint8_t>(rows * 256 + 256)); f.prow_line = Arena::up256(a.take<uint8_t>(rows * f.prow_line_bytes + 256)); }
+  m.prow_end = a.mark();
+  b.d_frames = a.take<RbtFrame>(nf); b.d_slices = a.take<RbtSlice>(ns);
+  b.d_rbsp = a.take<uint8_t>(b.rbsp.size() + 64); b.d_lists = a.take<int32_t>((nf + ns) * 2);
+  b.d_order = a.take<uint32_t>(b.order_keep.size()); b.d_refs = a.take<RbtFrameRef>(nf);
+  a.mark();
+  if (a.base) { size_t r = 0, q = 0;      // the levels' launches: their share of the lists, the refs, the queue memory and the tickets
+    for (size_t l = 0; l < b.levels.size(); l++) { ReconLevel& lv = b.levels[l];
+      lv.frames = b.d_frames; lv.slices = b.d_slices; lv.list = b.d_lists + b.fr_off[l]; lv.refs = b.d_refs + r; lv.queue = d_queue + q; lv.ticket = b.d_tickets + TICKET_OWN_LEVEL + l;
+      r += (size_t)lv.n; q += rbtk::recon_queue_words(lv.ctbs); } }
+  return m;
+}
+
 int decode_build(DecodeBatch& b, const StreamIn* streams, int n_streams) {
   b.stream_first.assign(n_streams, 0); b.stream_count.assign(n_streams, 0);
   b.stream_sps.resize(n_streams); b.stream_pps.resize(n_streams);
   // ---- host parse ----
   for (int si = 0; si < n_streams; si++) {
-    std::vector<Nal> nals; size_t rbsp_start = b.rbsp.size();
-    split_annexb(streams[si].p, streams[si].n, b.rbsp, nals);
-    (void)rbsp_start;
+    std::vector<Nal> nals; split_annexb(streams[si].p, streams[si].n, b.rbsp, nals);
     ParamSets* ps = new ParamSets();
     std::vector<DpbEntry> dpb; int prev_tid0_poc = 0, cur = -1;
     SliceHdr head_hdr; int head_idx = -1, last_seg = -1;   // the independent segment of the current slice, the last segment of its chain
@@ -133,80 +186,28 @@ int decode_build(DecodeBatch& b, const StreamIn* streams, int n_streams) {
   int n_levels = 0; for (auto& f : b.frames) n_levels = std::max(n_levels, f.level + 1);
   b.level_frames.assign(n_levels, {});
   for (size_t i = 0; i < b.frames.size(); i++) b.level_frames[b.frames[i].level].push_back((int)i);
-
-  // ---- HBM layout: [zero region | pm region (0x03) | ctb_slice region (0xFF) | rest] ----
-  Arena a;
-  size_t nf = b.frames.size();
-  std::vector<size_t> o_coef(nf), o_edges(nf), o_cnt(nf), o_done(nf), o_pm(nf), o_cs(nf), o_pix(nf), o_out(nf), o_dm(nf), o_qp(nf), o_mv(nf), o_ref(nf), o_refpoc(nf), o_sao(nf), o_cmds(nf);
-  for (size_t i = 0; i < nf; i++) { const RbtStreamCfg& c = b.frames[i].cfg; size_t u = (size_t)c.w4 * c.h4, nc = (size_t)c.w_ctb * c.h_ctb;
-    o_coef[i] = a.reserve(frame_samples(c) * 2); o_edges[i] = a.reserve(u); o_cnt[i] = a.reserve(nc * 4); o_done[i] = a.reserve(nc * 8); }
-  size_t o_tickets = a.reserve(128 * 4);
-  // ready queues of the reconstruction levels (launch_recon_queue), zeroed with the rest of this region
-  b.queue_off.clear(); b.queue_total.clear(); b.queue_wgs.clear();
-  size_t queue_words = 0;
-  for (auto& lf : b.level_frames) {
-    uint32_t tot = 0; int wg = 0;
-    for (int fi : lf) { const RbtStreamCfg& c = b.frames[fi].cfg; tot += (uint32_t)(c.w_ctb * c.h_ctb); wg += recon_queue_width(c); }
-    b.queue_off.push_back(queue_words); b.queue_total.push_back(tot); b.queue_wgs.push_back(wg); queue_words += rbtk::recon_queue_words(tot);
-  }
-  size_t o_queue = a.reserve(queue_words * 4);
-  // wavefront streams: progress counters of the CTB rows (zeroed with the rest of this region)
-  std::vector<size_t> o_prow_done(nf, 0), o_prow_ctx(nf, 0); std::vector<int> wpp_frame(nf, 0);
-  for (size_t i = 0; i < nf; i++) { wpp_frame[i] = b.stream_pps[b.info[i].stream].entropy_coding_sync; if (wpp_frame[i]) o_prow_done[i] = a.reserve((size_t)b.frames[i].cfg.h_ctb * 4); }
-  size_t o_save = b.want_save ? a.reserve(b.slices.size() * rbtk::parse_save_bytes()) : 0;
-  size_t zero_end = a.reserve(0);
-  for (size_t i = 0; i < nf; i++) { const RbtStreamCfg& c = b.frames[i].cfg; o_pm[i] = a.reserve((size_t)c.w4 * c.h4); }
-  size_t pm_begin = o_pm[0], pm_end = a.reserve(0);
-  for (size_t i = 0; i < nf; i++) { const RbtStreamCfg& c = b.frames[i].cfg; o_cs[i] = a.reserve((size_t)c.w_ctb * c.h_ctb * 2); }
-  size_t cs_begin = o_cs[0], cs_end = a.reserve(0);
-  for (size_t i = 0; i < nf; i++) {
-    const RbtStreamCfg& c = b.frames[i].cfg; size_t u = (size_t)c.w4 * c.h4, nc = (size_t)c.w_ctb * c.h_ctb;
-    o_pix[i] = a.reserve(frame_samples(c) * 2);
-    o_out[i] = b.info[i].sao ? a.reserve(frame_samples(c) * 2) : o_pix[i];
-    o_dm[i] = a.reserve(u); o_qp[i] = a.reserve(u); o_mv[i] = a.reserve(u * 4); o_ref[i] = a.reserve(u); o_refpoc[i] = a.reserve(u * 4);
-    o_sao[i] = a.reserve(nc * sizeof(RbtSao)); o_cmds[i] = a.reserve(nc * (size_t)b.frames[i].cmd_cap * sizeof(RbtCmd));
-  }
-  std::vector<size_t> o_prow_line(nf, 0);
-  const size_t prow_begin = a.reserve(0);     // the rows' hand-over records (one block, zeroed per job: recycled pool memory must not pass for the state of a row nobody parsed)
-  for (size_t i = 0; i < nf; i++) if (wpp_frame[i]) {
-    const RbtStreamCfg& c = b.frames[i].cfg;
-    b.frames[i].prow_line_bytes = (int32_t)(((size_t)c.w4 * 7 + (size_t)c.w_ctb * (2 + sizeof(RbtSao)) + 255) & ~(size_t)255);
-    o_prow_ctx[i] = a.reserve((size_t)c.h_ctb * 256 + 256); o_prow_line[i] = a.reserve((size_t)c.h_ctb * b.frames[i].prow_line_bytes + 256);
-  }
-  const size_t prow_end = a.reserve(0);
-  size_t o_frames = a.reserve(nf * sizeof(RbtFrame)), o_slices = a.reserve(b.slices.size() * sizeof(RbtSlice));
-  size_t o_rbsp = a.reserve(b.rbsp.size() + 64), o_lists = a.reserve((nf + b.slices.size()) * 2 * sizeof(int32_t));
-  // CTB dependency order (anti-diagonals x + 2y ascending, top to bottom inside one) per distinct picture geometry, and the pictures of every level as RbtFrameRef
+  if (b.level_frames.size() > MAX_LEVELS) { b.err = "too many dependency levels"; return b.err_code = RBT_ERR_UNSUPPORTED; }
+  for (size_t i = 0; i < b.frames.size(); i++) if (b.stream_pps[b.info[i].stream].entropy_coding_sync) {   // wavefront streams: the rows hand their bottom lines down (decode_lay_out)
+    const RbtStreamCfg& c = b.frames[i].cfg; b.frames[i].prow_line_bytes = (int32_t)(((size_t)c.w4 * 7 + (size_t)c.w_ctb * (2 + sizeof(RbtSao)) + 255) & ~(size_t)255); }
+  build_lists(b); b.levels.clear();
+  for (auto& lf : b.level_frames) { std::vector<LevelPic> pics; for (int fi : lf) pics.push_back(LevelPic{&b, fi}); b.levels.push_back(recon_level_of(pics)); }
+  // CTB dependency order (anti-diagonals x + 2y ascending, top to bottom inside one) per distinct picture geometry
+  const size_t nf = b.frames.size();
   b.order_keep.clear(); b.order_off.assign(nf, 0);
   { std::vector<std::pair<std::pair<int, int>, size_t>> seen;
-    for (size_t i = 0; i < nf; i++) { const int w = b.frames[i].cfg.w_ctb, h = b.frames[i].cfg.h_ctb; size_t off = (size_t)-1;
-      for (auto& s_ : seen) if (s_.first == std::make_pair(w, h)) off = s_.second;
-      if (off == (size_t)-1) { off = b.order_keep.size(); seen.push_back({{w, h}, off});
+    for (size_t i = 0; i < nf; i++) { const int w = b.frames[i].cfg.w_ctb, h = b.frames[i].cfg.h_ctb; const std::pair<std::pair<int, int>, size_t>* old = nullptr;
+      for (auto& s_ : seen) if (s_.first == std::make_pair(w, h)) old = &s_;
+      if (!old) { seen.push_back({{w, h}, b.order_keep.size()}); old = &seen.back();
         for (int d = 0; d <= w - 1 + 2 * (h - 1); d++) for (int y = 0; y < h; y++) { int x = d - 2 * y; if (x >= 0 && x < w) b.order_keep.push_back((uint32_t)x | ((uint32_t)y << 16)); } }
-      b.order_off[i] = off; } }
-  size_t o_order = a.reserve(b.order_keep.size() * 4), o_refs = a.reserve(nf * sizeof(RbtFrameRef));
-  b.arena_size = a.reserve(0);
-  b.arena = rbtk::dev_alloc(b.arena_size);
+      b.order_off[i] = old->second; } }
+  Arena a; decode_lay_out(b, a);      // measure, allocate, bind
+  b.arena_size = a.used; b.arena = rbtk::dev_alloc(b.arena_size);
   if (!b.arena) { b.err = "device allocation failed"; return b.err_code = RBT_ERR_NOMEM; }
-  uint8_t* base = (uint8_t*)b.arena;
-  for (size_t i = 0; i < nf; i++) {
-    RbtFrame& f = b.frames[i]; const RbtStreamCfg& c = f.cfg; size_t ys = (size_t)c.w * c.h, cs = (size_t)c.cw * c.ch;
-    auto planes = [&](size_t off, uint16_t** p) { p[0] = (uint16_t*)(base + off); p[1] = p[0] + ys; p[2] = p[1] + cs; };
-    planes(o_pix[i], f.pix); planes(o_out[i], f.out);
-    f.coef[0] = (int16_t*)(base + o_coef[i]); f.coef[1] = f.coef[0] + ys; f.coef[2] = f.coef[1] + cs;
-    f.pm = base + o_pm[i]; f.edges = base + o_edges[i]; f.dm = base + o_dm[i]; f.qp = (int8_t*)(base + o_qp[i]); f.mv = (int16_t*)(base + o_mv[i]);
-    f.ref = (int8_t*)(base + o_ref[i]); f.refpoc = (int32_t*)(base + o_refpoc[i]); f.sao = (RbtSao*)(base + o_sao[i]); f.ctb_slice = (uint16_t*)(base + o_cs[i]);
-    f.cmds = (RbtCmd*)(base + o_cmds[i]); f.cmd_count = (uint32_t*)(base + o_cnt[i]); f.ctb_done = (uint32_t*)(base + o_done[i]);
-    if (wpp_frame[i]) { f.prow_done = (uint32_t*)(base + o_prow_done[i]); f.prow_ctx = (uint8_t*)(((uintptr_t)(base + o_prow_ctx[i]) + 255) & ~(uintptr_t)255);
-                        f.prow_line = (uint8_t*)(((uintptr_t)(base + o_prow_line[i]) + 255) & ~(uintptr_t)255); }
-  }
-  b.d_order = (uint32_t*)(base + o_order); b.d_refs = (RbtFrameRef*)(base + o_refs); b.d_tickets = (uint32_t*)(base + o_tickets); b.d_queue = (uint32_t*)(base + o_queue);
-  b.refs_keep.clear(); b.refs_off.clear();
-  for (auto& lf : b.level_frames) { b.refs_off.push_back(b.refs_keep.size()); for (int fi : lf) b.refs_keep.push_back(RbtFrameRef{(RbtFrame*)(base + o_frames), (const RbtSlice*)(base + o_slices), b.d_order + b.order_off[fi], fi, 0}); }
-  if (b.level_frames.size() > 32) { b.err = "too many dependency levels"; return b.err_code = RBT_ERR_UNSUPPORTED; }
-  b.d_save = b.want_save ? (void*)(base + o_save) : nullptr;
-  b.d_frames = (RbtFrame*)(base + o_frames); b.d_slices = (RbtSlice*)(base + o_slices); b.d_rbsp = base + o_rbsp; b.d_lists = (int32_t*)(base + o_lists);
-  if (rbtk::dev_memset(base, 0, zero_end) || (prow_end > prow_begin && rbtk::dev_memset(base + prow_begin, 0, prow_end - prow_begin)) || rbtk::dev_memset(base + pm_begin, RBT_MODE_NONE, pm_end - pm_begin) || rbtk::dev_memset(base + cs_begin, 0xFF, cs_end - cs_begin) ||
+  uint8_t* base = (uint8_t*)b.arena; a = Arena{base};
+  const DecodeFill m = decode_lay_out(b, a);
+  // the pictures of every level as RbtFrameRef, in the order of the levels (ReconLevel::refs of level l starts where the levels before it end)
+  b.refs_keep.clear(); for (auto& lf : b.level_frames) for (int fi : lf) b.refs_keep.push_back(frame_ref(b, fi));
+  if (rbtk::dev_memset(base, 0, m.zero_end) || (m.prow_end > m.prow_begin && rbtk::dev_memset(base + m.prow_begin, 0, m.prow_end - m.prow_begin)) || rbtk::dev_memset(base + m.pm_begin, RBT_MODE_NONE, m.pm_end - m.pm_begin) || rbtk::dev_memset(base + m.cs_begin, 0xFF, m.cs_end - m.cs_begin) ||
       rbtk::h2d(b.d_frames, b.frames.data(), nf * sizeof(RbtFrame)) || rbtk::h2d(b.d_slices, b.slices.data(), b.slices.size() * sizeof(RbtSlice)) ||
       rbtk::h2d(b.d_rbsp, b.rbsp.data(), b.rbsp.size()) || rbtk::h2d(b.d_order, b.order_keep.data(), b.order_keep.size() * 4) ||
       rbtk::h2d(b.d_refs, b.refs_keep.data(), b.refs_keep.size() * sizeof(RbtFrameRef))) { b.err = "device transfer failed"; return b.err_code = RBT_ERR_NO_DEVICE; }
@@ -230,8 +231,26 @@ int recon_mode() {
   if (force == 3) return 2;
   return rbtk::jobs_in_flight() > 4 ? 0 : 1;                     // (force 4: the queue off, the round-3 rule)
 }
-bool recon_by_diagonals() { return recon_mode() == 0; }
-int recon_queue_width(const RbtStreamCfg& c) { const int w = c.w_ctb, h = c.h_ctb, d = w + 2 * h - 2; return d > 0 ? std::max(1, (w * h + d - 1) / d) : 1; }
+static int recon_queue_width(const RbtStreamCfg& c) { const int w = c.w_ctb, h = c.h_ctb, d = w + 2 * h - 2; return d > 0 ? std::max(1, (w * h + d - 1) / d) : 1; }   // CTBs of a picture that can be reconstructed side by side, on average (workgroups the ready-queue launch gets per picture)
+ReconLevel recon_level_of(const std::vector<LevelPic>& pics, std::vector<RbtFrameRef>* refs) {
+  ReconLevel lv; lv.n = (int)pics.size();
+  for (const LevelPic& p : pics) { const RbtStreamCfg& c = p.b->frames[p.frame].cfg;
+    lv.w_ctb = std::max(lv.w_ctb, (int)c.w_ctb); lv.h_ctb = std::max(lv.h_ctb, (int)c.h_ctb); lv.ctbs += (uint32_t)(c.w_ctb * c.h_ctb); lv.queue_wgs += recon_queue_width(c);
+    if (refs) refs->push_back(frame_ref(*p.b, p.frame)); }
+  return lv;
+}
+int recon_mode_for(const ReconLevel* lv, size_t n) {
+  int mode = recon_mode();
+  for (size_t l = 0; l < n && mode == 2; l++) if (lv[l].n >= 8192 || (size_t)lv[l].w_ctb * lv[l].h_ctb >= ((size_t)1 << 18)) mode = 0;
+  return mode;
+}
+// A batch's own level goes by its frame list when it goes by diagonals (the kernel bench.py's depth runs), levels merged across batches have refs only.
+void launch_recon(const ReconLevel& lv, int mode) {
+  if (mode == 0 && lv.list) rbtk::launch_recon(lv.frames, lv.slices, lv.list, lv.n, lv.w_ctb, lv.h_ctb);
+  else if (mode == 0) rbtk::launch_recon_refs(lv.refs, lv.n, lv.w_ctb, lv.h_ctb);
+  else if (mode == 1) rbtk::launch_recon_level(lv.refs, lv.n, lv.w_ctb * lv.h_ctb, lv.ticket);
+  else rbtk::launch_recon_queue(lv.refs, lv.n, lv.ctbs, lv.queue, lv.queue_wgs);
+}
 
 int decode_run(DecodeBatch& b) { int rc = decode_launch(b); return rc ? rc : decode_finish(b); }
 
@@ -243,23 +262,10 @@ int decode_launch(DecodeBatch& b) {
   rbtk::timer_end(T_RECON);
   return 0;
 }
-static void build_lists(DecodeBatch& b) {
-  std::vector<size_t>& sl_off = b.sl_off; std::vector<size_t>& sl_cnt = b.sl_cnt; sl_off.clear(); sl_cnt.clear();
-  // index lists: slices grouped by level, frames grouped by level
-  std::vector<int32_t>& lists = b.lists_keep; lists.clear(); b.fr_off.clear();
-  for (auto& lf : b.level_frames) {
-    sl_off.push_back(lists.size());
-    for (int fi : lf) for (int k = 0; k < b.frames[fi].n_slices; k++) lists.push_back(b.frames[fi].first_slice + k);
-    sl_cnt.push_back(lists.size() - sl_off.back());
-  }
-  for (auto& lf : b.level_frames) { b.fr_off.push_back(lists.size()); for (int fi : lf) lists.push_back(fi); }
-}
-static int max_w4(const DecodeBatch& b) { int m = 0; for (auto& f : b.frames) m = std::max(m, (int)f.cfg.w4); return m; }
-int decode_max_w4(const DecodeBatch& b) { return max_w4(b); }
+int decode_max_w4(const DecodeBatch& b) { int m = 0; for (auto& f : b.frames) m = std::max(m, (int)f.cfg.w4); return m; }
 int decode_upload_lists(DecodeBatch& b) {
   if (b.lists_uploaded) return 0;
   b.lists_uploaded = true;
-  build_lists(b);
   if (b.lists_keep.size() > (b.frames.size() + b.slices.size()) * 2) { b.err = "internal: list overflow"; return b.err_code = RBT_ERR_PARAM; }
   if (rbtk::h2d(b.d_lists, b.lists_keep.data(), b.lists_keep.size() * sizeof(int32_t))) { b.err = "device transfer failed"; return b.err_code = RBT_ERR_NO_DEVICE; }
   return 0;
@@ -270,9 +276,9 @@ int decode_launch_parse(DecodeBatch& b) {
   if (b.parse_external) return 0;
   const std::vector<size_t>& sl_off = b.sl_off; const std::vector<size_t>& sl_cnt = b.sl_cnt;
   rbtk::timer_begin(T_PARSE);
-  uint32_t* tk = b.has_row_tasks ? b.d_tickets + 64 : nullptr;          // row tasks wait for earlier list entries: hand the list out in start order
-  if (b.ordered_parse) { for (size_t l = 0; l < b.level_frames.size(); l++) rbtk::launch_parse(b.d_frames, b.d_slices, b.d_rbsp, b.d_lists + sl_off[l], (int)sl_cnt[l], max_w4(b), nullptr, 0, tk ? tk + l : nullptr); }
-  else rbtk::launch_parse(b.d_frames, b.d_slices, b.d_rbsp, b.d_lists, (int)b.slices.size(), max_w4(b), nullptr, 0, tk);
+  uint32_t* tk = b.has_row_tasks ? b.d_tickets + TICKET_PARSE : nullptr;          // row tasks wait for earlier list entries: hand the list out in start order
+  if (b.ordered_parse) { for (size_t l = 0; l < b.level_frames.size(); l++) rbtk::launch_parse(b.d_frames, b.d_slices, b.d_rbsp, b.d_lists + sl_off[l], (int)sl_cnt[l], decode_max_w4(b), nullptr, 0, tk ? tk + l : nullptr); }
+  else rbtk::launch_parse(b.d_frames, b.d_slices, b.d_rbsp, b.d_lists, (int)b.slices.size(), decode_max_w4(b), nullptr, 0, tk);
   rbtk::timer_end(T_PARSE);
   return 0;
 }
@@ -313,7 +319,7 @@ int decode_launch_chunked(DecodeBatch& b, int chunks, int main_stream, int aux_s
   for (int c = 0; c < chunks; c++) {
     int y_lim = c + 1 == chunks ? (1 << 30) : (max_h_all * (c + 1) + chunks - 1) / chunks;
     rbtk::set_stream(main_stream);
-    rbtk::launch_parse(b.d_frames, b.d_slices, b.d_rbsp, b.d_lists, (int)b.slices.size(), max_w4(b), b.d_save, y_lim);
+    rbtk::launch_parse(b.d_frames, b.d_slices, b.d_rbsp, b.d_lists, (int)b.slices.size(), decode_max_w4(b), b.d_save, y_lim);
     if (c + 1 == chunks) rbtk::timer_end(T_PARSE);
     rbtk::stream_wait(aux_stream, main_stream);
     rbtk::set_stream(aux_stream);
@@ -326,13 +332,7 @@ int decode_launch_chunked(DecodeBatch& b, int chunks, int main_stream, int aux_s
   return 0;
 }
 void decode_launch_level(DecodeBatch& b, size_t l) {
-  const std::vector<int>& lf = b.level_frames[l];
-  int mw = 0, mh = 0;
-  for (int fi : lf) { const RbtStreamCfg& c = b.frames[fi].cfg; mw = std::max(mw, c.w_ctb); mh = std::max(mh, c.h_ctb); }
-  const int mode = (lf.size() >= 8192 || (size_t)mw * mh >= ((size_t)1 << 18)) && recon_mode() == 2 ? 0 : recon_mode();      // the queue packs (picture, CTB) into 31 bits
-  if (mode == 0) rbtk::launch_recon(b.d_frames, b.d_slices, b.d_lists + b.fr_off[l], (int)lf.size(), mw, mh);
-  else if (mode == 1) rbtk::launch_recon_level(b.d_refs + b.refs_off[l], (int)lf.size(), mw * mh, b.d_tickets + l);
-  else rbtk::launch_recon_queue(b.d_refs + b.refs_off[l], (int)lf.size(), b.queue_total[l], b.d_queue + b.queue_off[l], b.queue_wgs[l]);
+  launch_recon(b.levels[l], recon_mode_for(&b.levels[l], 1));
   decode_launch_filters(b, l);
 }
 

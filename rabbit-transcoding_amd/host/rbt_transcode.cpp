@@ -38,7 +38,7 @@ struct EncodeBatch {
   RbtFrame* d_frames = nullptr; RbtSlice* d_slices = nullptr; int32_t* d_lists = nullptr; uint8_t* d_out = nullptr; uint8_t* d_packed = nullptr; uint32_t* d_dst = nullptr;
   size_t out_total = 0;
   std::vector<PadJob> pad_jobs;                 // source pictures that have to be copied into padded planes before the encoder reads them
-  std::vector<std::vector<uint16_t>> cs_keep;   // host staging of the ctb->slice maps, alive until the copies have completed
+  std::vector<uint16_t> cs_keep; uint16_t* d_cs = nullptr;   // the ctb->slice maps of all pictures back to back: host staging (alive until the copy has completed) and device
   uint8_t* d_zero = nullptr; size_t zero_bytes = 0; bool wpp = false;   // launch tickets (3 words) + row progress of the wavefront mode
   int main_stream = 0, aux_stream = -1;          // aux_stream >= 0: the intra part was enqueued there (its timers live there)
   HashSet hash; std::vector<int> hash_idx;      // md5_sei: the reconstructions to hash (after SAO), index of each picture in `hash` (-1: none)
@@ -74,6 +74,44 @@ static void make_param_sets(const EncStreamDesc& d, Sps& s, Pps& p) {
   p.transform_skip = !d.lossless && e1_ts_on();   // the 4x4 luma blocks are coded with or without the transform, whichever is cheaper (oracle/hevc_enc.c hm_tb_finish)
   if (d.lossless) { p.transquant_bypass = 1; p.deblocking_control_present = 1; p.pps_deblocking_disabled = 1; p.loop_filter_across_slices = 0; }
   if (d.rows < 0) { p.entropy_coding_sync = 1; p.dependent_slice_segments = 1; }   // wavefront rows, one dependent slice segment each (oracle/hevc_enc.c setup_stream)
+}
+
+// HBM layout of an encode batch. Every buffer of the arena is named here, once (Arena in rbt_batch.h: run without a base to measure, then over the allocation to bind),
+// and so is every buffer a picture has elsewhere or not at all.
+static void encode_lay_out(EncodeBatch& b, Arena& a) {
+  const size_t nf = b.frames.size(), ns = b.slices.size();
+  // the zero block (zeroed before the first kernel of every job): three launch tickets, then in wavefront mode per picture 2 * h_ctb progress words and two next-row counters
+  const size_t z0 = a.mark();
+  b.d_zero = a.take<uint8_t>(64); b.zero_bytes = a.used - z0;
+  if (b.wpp) for (size_t i = 0; i < nf; i++) { b.frames[i].row_done = a.take<uint32_t>((size_t)b.frames[i].cfg.h_ctb * 2 + 2); b.zero_bytes = a.used - z0; }
+  if (b.wpp) for (size_t i = 0; i < nf; i++) b.frames[i].row_ctx = a.take<uint8_t>((size_t)b.frames[i].cfg.h_ctb * 256);
+  for (size_t i = 0; i < nf; i++) {
+    RbtFrame& f = b.frames[i]; const RbtStreamCfg& c = f.cfg; const size_t ys = (size_t)c.w * c.h, cs = (size_t)c.cw * c.ch, u = (size_t)c.w4 * c.h4, nc = (size_t)c.w_ctb * c.h_ctb, u8 = (size_t)f.w8 * f.h8;
+    const EncStreamDesc& d = b.desc[b.frame_stream[i]]; const size_t k = i - (size_t)b.stream_first[b.frame_stream[i]];
+    // a padded copy of the source, unless the source already is a whole picture in coded geometry
+    if (c.w != d.w || c.h != d.h || d.src_x0 || d.src_y0 || (d.src_stride && d.src_stride != d.w)) {
+      uint16_t* pl[3]; a.take_planes(pl, ys, cs); const int st = d.src_stride ? d.src_stride : d.w;
+      if (a.base) for (int q = 0; q < 3; q++) { const int sh = q ? 1 : 0;
+        b.pad_jobs.push_back(PadJob{f.src[q], st >> sh, d.src_x0 >> sh, d.src_y0 >> sh, d.w >> sh, d.h >> sh, pl[q], c.w >> sh, c.h >> sh}); f.src[q] = pl[q]; }
+    }
+    // reconstruction and levels: in the decoded input picture's dead buffers where setup_encode found some (arena sharing), else here
+    if (!d.alias_pix.empty() && d.alias_pix[k]) Arena::same_planes(f.pix, d.alias_pix[k], ys, cs); else a.take_planes(f.pix, ys, cs);
+    if (!d.alias_coef.empty() && d.alias_coef[k]) Arena::same_planes(f.coef, d.alias_coef[k], ys, cs); else a.take_planes(f.coef, ys, cs);
+    if (d.sao) a.take_planes(f.out, ys, cs); else Arena::same_planes(f.out, f.pix[0], ys, cs);      // no SAO: out = pix, wherever that is
+    f.sao = a.take<RbtSao>(nc);
+    f.pm = a.take<uint8_t>(u); f.edges = a.take<uint8_t>(u); f.qp = a.take<int8_t>(u); f.mv = a.take<int16_t>(u * 2); f.ref = a.take<int8_t>(u); f.refpoc = a.take<int32_t>(u);
+    f.cu_log2 = a.take<uint8_t>(u8); f.cu_mode = a.take<uint8_t>(u8); f.cu_flags = a.take<uint8_t>(u8); f.cu_ts = a.take<uint8_t>(u8);
+  }
+  // the CTB -> slice maps of all pictures sit back to back: one upload per batch instead of one per picture (a copy is a queue entry of its own)
+  size_t cs_words = 0; for (size_t i = 0; i < nf; i++) cs_words += (size_t)b.frames[i].cfg.w_ctb * b.frames[i].cfg.h_ctb;
+  b.d_cs = a.take<uint16_t>(cs_words);
+  if (a.base) { uint16_t* at = b.d_cs; for (size_t i = 0; i < nf; i++) { b.frames[i].ctb_slice = at; at += (size_t)b.frames[i].cfg.w_ctb * b.frames[i].cfg.h_ctb; } }
+  b.d_frames = a.take<RbtFrame>(nf); b.d_slices = a.take<RbtSlice>(ns);
+  b.d_lists = a.take<int32_t>((nf + ns) * 3); b.d_dst = a.take<uint32_t>(ns);
+  // the packed output holds every slice back to back: as large as the slice buffers together, so that slices which fit their buffers always fit it (half of that, which
+  // it had before, is less than noise needs in every QP band: DESIGN.md 9.5)
+  b.d_out = a.take<uint8_t>(b.out_total); b.d_packed = a.take<uint8_t>(b.out_total);
+  a.mark();
 }
 
 static int encode_build(EncodeBatch& b) {
@@ -123,79 +161,34 @@ static int encode_build(EncodeBatch& b) {
     }
   }
   if (b.slices.size() >= 0xFFFF) { b.err = "too many slice segments in one call"; return RBT_ERR_UNSUPPORTED; }
-  // ---- HBM layout ----
-  Arena a; size_t nf = b.frames.size();
-  // wavefront bookkeeping: three launch tickets, then per picture 2 * h_ctb progress words and two next-row counters (zeroed before the first kernel of every job)
-  bool any_wpp = false; for (auto& d : b.desc) any_wpp |= d.rows < 0;
-  std::vector<size_t> o_rowdone(nf, 0), o_rowctx(nf, 0);
-  size_t o_zero = a.reserve(64), zero_bytes = 64;
-  if (any_wpp) for (size_t i = 0; i < nf; i++) { size_t n = ((size_t)b.frames[i].cfg.h_ctb * 2 + 2) * sizeof(uint32_t); o_rowdone[i] = a.reserve(n); zero_bytes = o_rowdone[i] + n - o_zero; }
-  if (any_wpp) for (size_t i = 0; i < nf; i++) o_rowctx[i] = a.reserve((size_t)b.frames[i].cfg.h_ctb * 256);
-  std::vector<size_t> o_src(nf, (size_t)-1), o_pix(nf), o_sout(nf), o_sao(nf), o_coef(nf), o_pm(nf), o_edges(nf), o_qp(nf), o_mv(nf), o_ref(nf), o_refpoc(nf), o_cs(nf), o_cul(nf), o_cum(nf), o_cuf(nf), o_cut(nf);
-  for (size_t i = 0; i < nf; i++) {
-    const RbtStreamCfg& c = b.frames[i].cfg; size_t u = (size_t)c.w4 * c.h4, nc = (size_t)c.w_ctb * c.h_ctb, u8 = (size_t)b.frames[i].w8 * b.frames[i].h8;
-    { const EncStreamDesc& d = b.desc[b.frame_stream[i]];
-      if (c.w != d.w || c.h != d.h || d.src_x0 || d.src_y0 || (d.src_stride && d.src_stride != d.w)) o_src[i] = a.reserve(frame_samples(c) * 2); }
-    { const EncStreamDesc& d = b.desc[b.frame_stream[i]]; const size_t k = i - (size_t)b.stream_first[b.frame_stream[i]];
-      o_pix[i] = (!d.alias_pix.empty() && d.alias_pix[k]) ? (size_t)-1 : a.reserve(frame_samples(c) * 2);
-      o_coef[i] = (!d.alias_coef.empty() && d.alias_coef[k]) ? (size_t)-1 : a.reserve(frame_samples(c) * 2); }
-    o_sout[i] = b.desc[b.frame_stream[i]].sao ? a.reserve(frame_samples(c) * 2) : o_pix[i]; o_sao[i] = a.reserve(nc * sizeof(RbtSao));      // (no SAO: out = pix, wherever that is)
-    o_pm[i] = a.reserve(u); o_edges[i] = a.reserve(u); o_qp[i] = a.reserve(u); o_mv[i] = a.reserve(u * 4); o_ref[i] = a.reserve(u); o_refpoc[i] = a.reserve(u * 4);
-    o_cul[i] = a.reserve(u8); o_cum[i] = a.reserve(u8); o_cuf[i] = a.reserve(u8); o_cut[i] = a.reserve(u8);
-  }
-  // the CTB -> slice maps of all pictures sit back to back: one upload per batch instead of one per picture (a copy is a queue entry of its own)
-  size_t cs_words = 0; for (size_t i = 0; i < nf; i++) { o_cs[i] = cs_words; cs_words += (size_t)b.frames[i].cfg.w_ctb * b.frames[i].cfg.h_ctb; }
-  const size_t o_cs_all = a.reserve(cs_words * 2);
-  size_t o_frames = a.reserve(nf * sizeof(RbtFrame)), o_slices = a.reserve(b.slices.size() * sizeof(RbtSlice));
-  size_t o_lists = a.reserve((nf + b.slices.size()) * 3 * sizeof(int32_t)), o_dst = a.reserve(b.slices.size() * sizeof(uint32_t));
+  b.wpp = false; for (auto& d : b.desc) b.wpp |= d.rows < 0;
   size_t out_cap_total = 0; for (auto& sl : b.slices) { sl.out_off = (uint32_t)out_cap_total; out_cap_total += sl.out_cap; }
   if (out_cap_total >= 0xFFFFFFFFull) { b.err = "output buffer too large for one call"; return RBT_ERR_UNSUPPORTED; }
-  // the packed output holds every slice back to back: as large as the slice buffers together, so that slices which fit their buffers always fit it (half of that, which
-  // it had before, is less than noise needs in every QP band: DESIGN.md 9.5)
-  size_t o_out = a.reserve(out_cap_total), o_packed = a.reserve(out_cap_total);
-  b.arena_size = a.reserve(0);
-  b.arena = rbtk::dev_alloc(b.arena_size);
+  b.out_total = out_cap_total;
+  Arena a; encode_lay_out(b, a);      // measure, allocate, bind
+  b.arena_size = a.used; b.arena = rbtk::dev_alloc(b.arena_size);
   if (!b.arena) { b.err = "device allocation failed"; return RBT_ERR_NOMEM; }
-  uint8_t* base = (uint8_t*)b.arena;
-  b.cs_keep.assign(1, std::vector<uint16_t>(cs_words, 0));
+  a = Arena{(uint8_t*)b.arena}; encode_lay_out(b, a);
+  // per CTB: the SLICE it belongs to (index of the slice's independent segment): availability, QP and loop filter flags are per slice
+  const size_t nf = b.frames.size(); b.cs_keep.clear();
   for (size_t i = 0; i < nf; i++) {
-    uint16_t* cs_host = b.cs_keep[0].data() + o_cs[i];
-    RbtFrame& f = b.frames[i]; const RbtStreamCfg& c = f.cfg; size_t ys = (size_t)c.w * c.h, cs = (size_t)c.cw * c.ch;
-    const EncStreamDesc& ds = b.desc[b.frame_stream[i]]; const size_t ks = i - (size_t)b.stream_first[b.frame_stream[i]];
-    f.pix[0] = o_pix[i] == (size_t)-1 ? ds.alias_pix[ks] : (uint16_t*)(base + o_pix[i]); f.pix[1] = f.pix[0] + ys; f.pix[2] = f.pix[1] + cs;
-    f.out[0] = o_sout[i] == (size_t)-1 ? f.pix[0] : (uint16_t*)(base + o_sout[i]); f.out[1] = f.out[0] + ys; f.out[2] = f.out[1] + cs; f.sao = (RbtSao*)(base + o_sao[i]);
-    if (o_src[i] != (size_t)-1) {
-      const EncStreamDesc& d = b.desc[b.frame_stream[i]]; const int st = d.src_stride ? d.src_stride : d.w;
-      uint16_t* pl[3] = {(uint16_t*)(base + o_src[i]), nullptr, nullptr}; pl[1] = pl[0] + ys; pl[2] = pl[1] + cs;
-      for (int k = 0; k < 3; k++) { const int sh = k ? 1 : 0;
-        b.pad_jobs.push_back(PadJob{f.src[k], st >> sh, d.src_x0 >> sh, d.src_y0 >> sh, d.w >> sh, d.h >> sh, pl[k], c.w >> sh, c.h >> sh}); f.src[k] = pl[k]; }
-    }
-    f.coef[0] = o_coef[i] == (size_t)-1 ? ds.alias_coef[ks] : (int16_t*)(base + o_coef[i]); f.coef[1] = f.coef[0] + ys; f.coef[2] = f.coef[1] + cs;
-    f.pm = base + o_pm[i]; f.edges = base + o_edges[i]; f.qp = (int8_t*)(base + o_qp[i]); f.mv = (int16_t*)(base + o_mv[i]); f.ref = (int8_t*)(base + o_ref[i]);
-    f.refpoc = (int32_t*)(base + o_refpoc[i]); f.ctb_slice = (uint16_t*)(base + o_cs_all) + o_cs[i];
-    f.cu_log2 = base + o_cul[i]; f.cu_mode = base + o_cum[i]; f.cu_flags = base + o_cuf[i]; f.cu_ts = base + o_cut[i];
-    if (any_wpp) { f.row_done = (uint32_t*)(base + o_rowdone[i]); f.row_ctx = base + o_rowctx[i]; }
-    // per CTB: the SLICE it belongs to (index of the slice's independent segment): availability, QP and loop filter flags are per slice
-    { int head = f.first_slice;
-      for (int k = 0; k < f.n_slices; k++) { const RbtSlice& sl = b.slices[f.first_slice + k]; if (!sl.dependent) head = f.first_slice + k; for (int q = 0; q < sl.n_ctbs; q++) cs_host[sl.ctb_addr + q] = (uint16_t)head; } }
+    const RbtFrame& f = b.frames[i]; const size_t at = b.cs_keep.size(); b.cs_keep.resize(at + (size_t)f.cfg.w_ctb * f.cfg.h_ctb, 0); int head = f.first_slice;
+    for (int k = 0; k < f.n_slices; k++) { const RbtSlice& sl = b.slices[f.first_slice + k]; if (!sl.dependent) head = f.first_slice + k; for (int q = 0; q < sl.n_ctbs; q++) b.cs_keep[at + sl.ctb_addr + q] = (uint16_t)head; }
   }
-  if (rbtk::h2d(base + o_cs_all, b.cs_keep[0].data(), cs_words * 2)) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  if (rbtk::h2d(b.d_cs, b.cs_keep.data(), b.cs_keep.size() * 2)) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
   // decoded picture hash SEI: the whole coded reconstruction (what a decoder outputs before cropping) after SAO
   b.hash_idx.assign(nf, -1);
   for (size_t i = 0; i < nf; i++) if (const int kind = b.desc[b.frame_stream[i]].md5) {
     const RbtFrame& f = b.frames[i];
     if ((b.hash_idx[i] = b.hash.add(f.out, f.cfg.w, f.cfg.h, f.cfg.bit_depth, kind)) < 0) { b.err = "picture cannot be hashed"; return RBT_ERR_UNSUPPORTED; }
   }
-  b.d_frames = (RbtFrame*)(base + o_frames); b.d_slices = (RbtSlice*)(base + o_slices); b.d_lists = (int32_t*)(base + o_lists); b.d_dst = (uint32_t*)(base + o_dst);
-  b.d_out = base + o_out; b.d_packed = base + o_packed; b.out_total = out_cap_total;
-  b.d_zero = base + o_zero; b.zero_bytes = zero_bytes; b.wpp = any_wpp;
   if (rbtk::h2d(b.d_frames, b.frames.data(), nf * sizeof(RbtFrame)) || rbtk::h2d(b.d_slices, b.slices.data(), b.slices.size() * sizeof(RbtSlice))) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
   return 0;
 }
 
 // runs the kernels and packs one Annex-B stream per input stream
 // The encoder of one stream is enqueued in three steps so that nothing on the host waits for the GPU in between:
-// encode_upload_lists (host -> device copies, issued while the stream is still empty), encode_launch (kernels up to the
+// encode_upload_lists (host -> device copies, issued while the stream is still empty), encode_launch_* (kernels up to the
 // entropy coder, may be enqueued behind the decoder's kernels on the same stream), encode_finish (one sync, packing, NALs).
 static int encode_upload_lists(EncodeBatch& b) {
   size_t nf = b.frames.size(), ns = b.slices.size();
@@ -263,12 +256,6 @@ static void encode_launch_entropy_rest(EncodeBatch& b) {
   else rbtk::launch_entropy(b.d_frames, b.d_slices, b.d_out, b.d_lists + b.off_sl_p, b.n_sl_p, max_log2_ctb(b));
   rbtk::timer_end(T_ENTROPY);
 }
-static int encode_launch(EncodeBatch& b) {
-  encode_launch_intra(b); encode_launch_entropy_intra(b); encode_launch_inter(b);
-  if (!b.hash.empty()) b.hash.launch();
-  encode_launch_entropy_rest(b);
-  return 0;
-}
 static int encode_finish(EncodeBatch& b, std::vector<std::vector<uint8_t>>& outs, rbt_stats& st) {
   size_t nf = b.frames.size(), ns = b.slices.size();
   if (rbtk::d2h(b.slices.data(), b.d_slices, ns * sizeof(RbtSlice))) { b.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
@@ -309,9 +296,11 @@ static int encode_finish(EncodeBatch& b, std::vector<std::vector<uint8_t>>& outs
 }
 
 static int encode_run(EncodeBatch& b, std::vector<std::vector<uint8_t>>& outs, rbt_stats& st) {
-  int rc = encode_upload_lists(b);
-  if (!rc) rc = encode_launch(b);
-  return rc ? rc : encode_finish(b, outs, st);
+  if (int rc = encode_upload_lists(b)) return rc;
+  encode_launch_intra(b); encode_launch_entropy_intra(b); encode_launch_inter(b);
+  if (!b.hash.empty()) b.hash.launch();
+  encode_launch_entropy_rest(b);
+  return encode_finish(b, outs, st);
 }
 
 static int hand_out(const std::vector<std::vector<uint8_t>>& outs, uint8_t** out, size_t* n_out) {
@@ -375,14 +364,7 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
     for (int k = 0; k < cnt; k++) for (int q = 0; q < 3; q++) d.src[q][k] = view(k, q);
     // arena sharing: the encoder's levels and reconstruction of picture k live in the decoded picture k's dead buffers when the two pictures have one geometry (coded size
     // = the input's coded size, no window offset) and no other target rate of a fan-out took them already. RBT_ARENA_SHARE=0 switches it off.
-    // What orders the encoder's first write to such a buffer behind the decoder's last read of it (the reconstruction of picture k reads its levels, its deblocking and
-    // SAO launches - decode_launch_filters, the last thing decode_launch_level enqueues for a level - read its pre-SAO samples; nothing later does: reference pictures and
-    // the input's hash check read the SAO output) in gof_submit:
-    //  - one HIP stream: every level of the decoder is enqueued on the pipeline's stream before encode_launch_intra, the encoder's first kernel, goes onto the same stream
-    //    (the merged launches of pipelines that share a stream are enqueued earlier still, on that same stream);
-    //  - intra coding forked onto the auxiliary stream: rbtk::stream_wait(aux, sid) records an event on the pipeline's stream right behind decode_launch_level(fork_level),
-    //    fork_level being the highest dependency level of any decoded picture an output I picture is coded from - so those pictures' filters are behind the event, and I
-    //    pictures alias nothing else. The P pictures (encode_launch_inter) stay on the pipeline's stream, behind every level.
+    // (what orders the encoder's first write to such a buffer behind the decoder's last read of it: enqueue_pipeline)
     // tests/test_arena_share.py runs the same transcodes with the switch off and on.
     { static const int share = [] { const char* e = getenv("RBT_ARENA_SHARE"); return !e || atoi(e) != 0; }();
       if (db.alias_taken.size() < db.stream_first.size()) db.alias_taken.resize(db.stream_first.size(), 0);
@@ -454,20 +436,26 @@ static void bind_streams(GofJob& j, int depth) {
 }
 
 size_t gof_memory(const GofJob* j) { return j ? j->dev_bytes : 0; }
-GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule) {
-  GofJob* J = new GofJob(); GofJob& j = *J;
-  struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
-  j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
-  j.params.assign(p, p + n); j.n_in.assign(n_in, n_in + n);
-  rbt_stats& st = j.st; std::string& err = j.err;
-  // Pipelines: up to three sub-bitstreams get one pipeline (= HIP stream) each. A call with more (several GOFs at once:
-  // one GOF leaves most of the GPU idle) groups them by video type, so that the slices of all attribute streams parse
-  // in one launch, all geometry streams in another, ...
+
+// What lives only while a job is submitted
+struct SubmitPlan {
+  const uint8_t* const* in; const rbt_stream_params* p; bool gof_rule;
+  std::vector<std::vector<int>> uniq;               // per pipeline: the stream indices that are decoded
+  std::vector<std::vector<PoolJob>> pool_jobs;      // per pipeline: the OR-pool launches, recorded by setup_encode and issued behind the decoder's kernels
+  // occupancy-aware coding (rbt_stream_params.occupancy_rd): entry i is coded with the occupancy map of the nearest occupancy entry in front of it, if this call pools it
+  std::vector<int> occ_of; std::vector<OccSource> occ_src; std::vector<OccJob> occ_jobs;
+  std::vector<char> feeds_any, consumes; std::vector<int> occ_marks;   // per pipeline: others are coded with its occupancy maps / it is coded with some; where on the feeders' streams the maps are complete
+};
+// Pipelines: up to three sub-bitstreams get one pipeline (= HIP stream) each. A call with more (several GOFs at once:
+// one GOF leaves most of the GPU idle) groups them by video type, so that the slices of all attribute streams parse
+// in one launch, all geometry streams in another, ... Host work only.
+static int plan_pipelines(GofJob& j, SubmitPlan& s, int depth) {
+  const int n = j.n; const rbt_stream_params* p = s.p; const uint8_t* const* in = s.in; const std::vector<size_t>& n_in = j.n_in;
   std::vector<std::vector<int>>& groups = j.groups;
   j.passthrough.resize(n); j.is_pass.assign(n, 0);
   int n_live = 0;
   for (int i = 0; i < n; i++) {
-    if (gof_rule && p[i].video_type == RBT_VIDEO_OCCUPANCY && p[i].occupancy_precision != 4) { j.is_pass[i] = 1; j.passthrough[i].assign(in[i], in[i] + n_in[i]); }
+    if (s.gof_rule && p[i].video_type == RBT_VIDEO_OCCUPANCY && p[i].occupancy_precision != 4) { j.is_pass[i] = 1; j.passthrough[i].assign(in[i], in[i] + n_in[i]); }
     else n_live++;
   }
   if (n_live <= rbtk::RBT_AUX_STREAM) { for (int i = 0; i < n; i++) if (!j.is_pass[i]) groups.push_back({i}); }
@@ -479,89 +467,91 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
   }
   const int ng = j.ng = (int)groups.size();
   // Streams of a pipeline that are the same input (same buffer: one sub-bitstream re-encoded at several rate points) are decoded once
-  j.dec_of.resize(ng);
-  std::vector<std::vector<int>> uniq(ng);          // per pipeline: the stream indices that are decoded
+  j.dec_of.resize(ng); s.uniq.resize(ng);
   for (int g = 0; g < ng; g++) for (int i : groups[g]) {
-    int d = -1;
-    for (size_t q = 0; q < uniq[g].size(); q++) if (in[uniq[g][q]] == in[i] && n_in[uniq[g][q]] == n_in[i]) { d = (int)q; break; }
-    if (d < 0) { d = (int)uniq[g].size(); uniq[g].push_back(i); }
+    std::vector<int>& u = s.uniq[g]; int d = -1;
+    for (size_t q = 0; q < u.size(); q++) if (in[u[q]] == in[i] && n_in[u[q]] == n_in[i]) { d = (int)q; break; }
+    if (d < 0) { d = (int)u.size(); u.push_back(i); }
     j.dec_of[g].push_back(d);
   }
-  auto bytes_of = [&](int g) { size_t t = 0; for (int i : uniq[g]) t += n_in[i]; return t; };
-  j.db.resize(ng); j.eb.resize(ng); j.chained.assign(ng, 0);
-  std::vector<DecodeBatch>& db = j.db; std::vector<EncodeBatch>& eb = j.eb; std::vector<char>& chained = j.chained; std::vector<void*>& pooled = j.pooled;
-  std::vector<int>& order = j.order; order.resize(ng); for (int i = 0; i < ng; i++) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bytes_of(a) > bytes_of(b); });
-  const int aux = job_stream(j, rbtk::RBT_AUX_STREAM);
+  auto bytes_of = [&](int g) { size_t t = 0; for (int i : s.uniq[g]) t += n_in[i]; return t; };
+  j.db.resize(ng); j.eb.resize(ng); j.chained.assign(ng, 0); j.parse_timed.assign(ng, 1); j.recon_timed.assign(ng, 1);
+  j.order.resize(ng); for (int i = 0; i < ng; i++) j.order[i] = i;
+  std::stable_sort(j.order.begin(), j.order.end(), [&](int a, int b) { return bytes_of(a) > bytes_of(b); });
   bind_streams(j, depth);
-  recon_set_depth(depth); rbtk::set_jobs_in_flight(depth);
-  // ---- phase A, longest pipeline first: build decoder and encoder batches and upload them; then enqueue decode -> pool ->
-  // encode on the stream without a host round trip in between (PCCTranscoder.cpp:428-448, :466, :825-904). Every upload of
-  // the job is issued before its first kernel: a copy from pageable memory blocks the host until the stream has reached it,
-  // and pipelines may share a stream. The input's picture hashes (verify_md5) are checked on the GPU behind the decoder's last
-  // filter; only the hashes and a mismatch count per decoded stream come back, when the job is collected.
-  j.t_gpu = now_ms();
+  recon_set_depth(depth);
+  s.pool_jobs.resize(ng); s.occ_of.assign(n, -1); s.occ_src.resize(n); s.feeds_any.assign(ng, 0); s.consumes.assign(ng, 0);
   int rc = 0;
-  std::vector<std::vector<PoolJob>> pool_jobs(ng);
-  // occupancy-aware coding (rbt_stream_params.occupancy_rd): entry i is coded with the occupancy map of the nearest occupancy entry in front of it, if this call pools it
-  std::vector<int> occ_of(n, -1), group_of(n, -1), pos_of(n, -1); bool any_occ_rd = false;
-  for (int g = 0; g < ng; g++) for (size_t q = 0; q < groups[g].size(); q++) { group_of[groups[g][q]] = g; pos_of[groups[g][q]] = (int)q; }
   for (int i = 0, last = -1; i < n; i++) {
-    if (p[i].video_type == RBT_VIDEO_OCCUPANCY) last = (gof_rule && !j.is_pass[i] && p[i].occupancy_precision == 4) ? i : -1;
-    else if (gof_rule && p[i].occupancy_rd && last >= 0) { occ_of[i] = last; any_occ_rd = true; if (p[i].verify_md5 || p[last].verify_md5) { err = "occupancy_rd cannot be combined with verify_md5"; rc = RBT_ERR_PARAM; } }
+    if (p[i].video_type == RBT_VIDEO_OCCUPANCY) last = (s.gof_rule && !j.is_pass[i] && p[i].occupancy_precision == 4) ? i : -1;
+    else if (s.gof_rule && p[i].occupancy_rd && last >= 0) { s.occ_of[i] = last; if (p[i].verify_md5 || p[last].verify_md5) { j.err = "occupancy_rd cannot be combined with verify_md5"; rc = RBT_ERR_PARAM; } }
   }
-  std::vector<OccSource> occ_src(n); std::vector<OccJob> occ_jobs;
-  for (int k = 0; k < ng && !rc; k++) {
-    const int gi = order[k], sid = job_stream(j, gi); const std::vector<int>& gs = groups[gi]; rbtk::set_stream(sid);
+  return rc;
+}
+
+// Decoder batches, longest pipeline first: host parse, arena, uploads (the input's picture hashes - verify_md5 - included: they are checked on the GPU behind the decoder's
+// last filter; only the hashes and a mismatch count per decoded stream come back, when the job is collected)
+static int build_decoders(GofJob& j, SubmitPlan& s) {
+  for (int k = 0; k < j.ng; k++) {
+    const int gi = j.order[k]; const std::vector<int>& gs = j.groups[gi]; DecodeBatch& db = j.db[gi]; rbtk::set_stream(job_stream(j, gi));
     std::vector<StreamIn> sins; bool verify = false;
-    std::vector<char> verify_ds(uniq[gi].size(), 0);   // per decoded stream: some entry it feeds asks for the check
-    for (int i : uniq[gi]) sins.push_back(StreamIn{in[i], n_in[i]});
-    for (size_t q = 0; q < gs.size(); q++) if (p[gs[q]].verify_md5) { verify = true; verify_ds[j.dec_of[gi][q]] = 1; }
+    std::vector<char> verify_ds(s.uniq[gi].size(), 0);   // per decoded stream: some entry it feeds asks for the check
+    for (int i : s.uniq[gi]) sins.push_back(StreamIn{s.in[i], j.n_in[i]});
+    for (size_t q = 0; q < gs.size(); q++) if (s.p[gs[q]].verify_md5) { verify = true; verify_ds[j.dec_of[gi][q]] = 1; }
     double t0 = now_ms();
-    db[gi].want_save = parse_bands() > 1 && k == 0 && j.has_aux && ng <= rbtk::RBT_AUX_STREAM && !verify;
-    rc = decode_build(db[gi], sins.data(), (int)sins.size());
-    st.host_parse_ms += now_ms() - t0;
-    if (!rc) rc = decode_upload_lists(db[gi]);
-    if (!rc && verify) rc = decode_hash_setup(db[gi], verify_ds);
-    if (rc) { err = db[gi].err; break; }
+    db.want_save = parse_bands() > 1 && k == 0 && j.has_aux && j.ng <= rbtk::RBT_AUX_STREAM && !verify;
+    int rc = decode_build(db, sins.data(), (int)sins.size());
+    j.st.host_parse_ms += now_ms() - t0;
+    if (!rc) rc = decode_upload_lists(db);
+    if (!rc && verify) rc = decode_hash_setup(db, verify_ds);
+    if (rc) { j.err = db.err; return rc; }
   }
-  // encoder set-up: the pipelines whose occupancy streams others are coded with first (their pooled planes are what the maps are made of)
-  for (int pass = 0; pass < 2 && !rc; pass++) for (int k = 0; k < ng && !rc; k++) {
-    const int gi = order[k], sid = job_stream(j, gi); const std::vector<int>& gs = groups[gi]; rbtk::set_stream(sid);
-    bool feeds = false; for (int i : gs) for (int c = 0; c < n; c++) feeds |= occ_of[c] == i;
+  return 0;
+}
+
+// Encoder batches: the pipelines whose occupancy streams others are coded with first (their pooled planes are what the maps are made of), then the rest
+static int build_encoders(GofJob& j, SubmitPlan& s) {
+  for (int pass = 0; pass < 2; pass++) for (int k = 0; k < j.ng; k++) {
+    const int gi = j.order[k]; const std::vector<int>& gs = j.groups[gi]; EncodeBatch& eb = j.eb[gi]; rbtk::set_stream(job_stream(j, gi));
+    bool feeds = false; for (int i : gs) for (int c = 0; c < j.n; c++) feeds |= s.occ_of[c] == i;
     if (feeds != (pass == 0)) continue;
-    for (size_t q = 0; q < gs.size() && !rc; q++) {
-      const int i = gs[q], io = occ_of[i];
-      rc = setup_encode(db[gi], j.dec_of[gi][q], (int)q, p[i], eb[gi], pooled, err, &pool_jobs[gi], io >= 0 ? &occ_src[io] : nullptr, io, &occ_jobs);
-      if (!rc && feeds && p[i].video_type == RBT_VIDEO_OCCUPANCY) {
-        const EncStreamDesc& d = eb[gi].desc[q];
-        if (d.n_frames > 0) { occ_src[i].occ = d.src[0][0]; occ_src[i].in_step = d.n_frames > 1 ? (size_t)(d.src[0][1] - d.src[0][0]) : 0; occ_src[i].n = d.n_frames; occ_src[i].ow = d.w; occ_src[i].oh = d.h; occ_src[i].pipeline = gi; }
-      }
+    for (size_t q = 0; q < gs.size(); q++) {
+      const int i = gs[q], io = s.occ_of[i];
+      if (int rc = setup_encode(j.db[gi], j.dec_of[gi][q], (int)q, s.p[i], eb, j.pooled, j.err, &s.pool_jobs[gi], io >= 0 ? &s.occ_src[io] : nullptr, io, &s.occ_jobs)) return rc;
+      const EncStreamDesc& d = eb.desc[q];
+      if (feeds && s.p[i].video_type == RBT_VIDEO_OCCUPANCY && d.n_frames > 0) {
+        OccSource& os = s.occ_src[i]; os.occ = d.src[0][0]; os.in_step = d.n_frames > 1 ? (size_t)(d.src[0][1] - d.src[0][0]) : 0; os.n = d.n_frames; os.ow = d.w; os.oh = d.h; os.pipeline = gi; }
     }
-    if (!rc) { rc = encode_build(eb[gi]); if (!rc) rc = encode_upload_lists(eb[gi]); if (rc) err = eb[gi].err; }
-    if (rc) break;
-    chained[gi] = 1;
+    int rc = encode_build(eb);
+    if (!rc) rc = encode_upload_lists(eb);
+    if (rc) { j.err = eb.err; return rc; }
+    j.chained[gi] = 1;
   }
-  (void)group_of; (void)pos_of;
-  // Pipelines that share a HIP stream would parse one after the other; their slices go into one merged launch instead, so
-  // that all parsers of the stream run side by side and only the (short) tails of the pipelines follow each other.
-  j.parse_timed.assign(ng, 1); j.recon_timed.assign(ng, 1);
-  for (int k = 0; k < ng && !rc; k++) {
-    const int lead = order[k];
-    if (!chained[lead] || db[lead].parse_external) continue;
+  for (const OccJob& oj : s.occ_jobs) s.feeds_any[s.occ_src[oj.source].pipeline] = 1;
+  for (int g = 0; g < j.ng; g++) for (const EncStreamDesc& d : j.eb[g].desc) s.consumes[g] |= !d.occ4.empty();
+  return 0;
+}
+
+// Pipelines that share a HIP stream would parse one after the other; their slices go into one merged launch instead, so
+// that all parsers of the stream run side by side and only the (short) tails of the pipelines follow each other.
+static int launch_merged(GofJob& j) {
+  const int ng = j.ng; std::vector<DecodeBatch>& db = j.db;
+  for (int k = 0; k < ng; k++) {
+    const int lead = j.order[k];
+    if (!j.chained[lead] || db[lead].parse_external) continue;
     std::vector<int> grp;
-    for (int q = k; q < ng; q++) { const int gi = order[q]; if (j.phys[gi] == j.phys[lead] && chained[gi] && !db[gi].ordered_parse && !db[gi].d_save) grp.push_back(gi); }
+    for (int q = k; q < ng; q++) { const int gi = j.order[q]; if (j.phys[gi] == j.phys[lead] && j.chained[gi] && !db[gi].ordered_parse && !db[gi].d_save) grp.push_back(gi); }
     if (grp.size() < 2 || grp[0] != lead) continue;
     j.tasks_keep.emplace_back(); std::vector<RbtParseTask>& tasks = j.tasks_keep.back(); int mw4 = 0;
-    std::vector<uint32_t> task_bytes; bool any_row_tasks = false;
+    std::vector<uint32_t> task_bytes; bool row_tasks = false;
     for (int gi : grp) {
       for (size_t i = 0; i < db[gi].slices.size(); i++) { tasks.push_back(RbtParseTask{db[gi].d_frames, db[gi].d_slices, db[gi].d_rbsp, db[gi].lists_keep[i], 0}); task_bytes.push_back(db[gi].slices[(size_t)db[gi].lists_keep[i]].data_size); }
-      mw4 = std::max(mw4, decode_max_w4(db[gi])); db[gi].parse_external = true; j.parse_timed[gi] = gi == lead; any_row_tasks |= db[gi].has_row_tasks;
+      mw4 = std::max(mw4, decode_max_w4(db[gi])); db[gi].parse_external = true; j.parse_timed[gi] = gi == lead; row_tasks |= db[gi].has_row_tasks;
     }
     // Longest first: a launch's waves start in list order, and when more slices are in flight than the GPU holds waves (several jobs' launches side by side) the ones that
     // wait should be the short ones - the launch lasts as long as its largest slice (an attribute IDR) however late that one starts. Not for lists with row tasks of
     // wavefront streams: there a task must come after the task of the row above it.
-    if (!any_row_tasks) {
+    if (!row_tasks) {
       std::vector<size_t> ord(tasks.size()); for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
       std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return task_bytes[a] > task_bytes[b]; });
       std::vector<RbtParseTask> sorted; sorted.reserve(tasks.size()); for (size_t i : ord) sorted.push_back(tasks[i]);
@@ -571,113 +561,125 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
     // per level and pipeline, one after the other)
     size_t n_levels = 0; for (int gi : grp) n_levels = std::max(n_levels, db[gi].level_frames.size());
     j.refs_keep.emplace_back(); std::vector<RbtFrameRef>& refs = j.refs_keep.back();
-    std::vector<size_t> lv_off(n_levels + 1, 0); std::vector<int> lv_w(n_levels, 0), lv_h(n_levels, 0);
-    std::vector<size_t> lq_off(n_levels + 1, 0); std::vector<uint32_t> lq_total(n_levels, 0); std::vector<int> lq_wgs(n_levels, 0);      // ready queues of the merged levels
+    std::vector<ReconLevel> levels; size_t queue_words = 0;
     for (size_t l = 0; l < n_levels; l++) {
-      lv_off[l] = refs.size();
-      for (int gi : grp) if (l < db[gi].level_frames.size()) for (int fi : db[gi].level_frames[l]) {
-        refs.push_back(RbtFrameRef{db[gi].d_frames, db[gi].d_slices, db[gi].d_order + db[gi].order_off[fi], fi, 0});
-        const RbtStreamCfg& c = db[gi].frames[fi].cfg;
-        lv_w[l] = std::max(lv_w[l], (int)c.w_ctb); lv_h[l] = std::max(lv_h[l], (int)c.h_ctb);
-        lq_total[l] += (uint32_t)(c.w_ctb * c.h_ctb); lq_wgs[l] += recon_queue_width(c);
-      }
-      lq_off[l + 1] = lq_off[l] + rbtk::recon_queue_words(lq_total[l]);
+      std::vector<LevelPic> pics;
+      for (int gi : grp) if (l < db[gi].level_frames.size()) for (int fi : db[gi].level_frames[l]) pics.push_back(LevelPic{&db[gi], fi});
+      levels.push_back(recon_level_of(pics, &refs)); queue_words += rbtk::recon_queue_words(levels.back().ctbs);
     }
-    lv_off[n_levels] = refs.size();
-    int rmode = recon_mode();
-    for (size_t l = 0; l < n_levels; l++) if (lv_off[l + 1] - lv_off[l] >= 8192 || (size_t)lv_w[l] * lv_h[l] >= ((size_t)1 << 18)) { if (rmode == 2) rmode = 0; }
+    const int rmode = recon_mode_for(levels.data(), levels.size());
     RbtParseTask* d_tasks = (RbtParseTask*)rbtk::dev_alloc(tasks.size() * sizeof(RbtParseTask));
     RbtFrameRef* d_refs = (RbtFrameRef*)rbtk::dev_alloc(refs.size() * sizeof(RbtFrameRef));
-    if (d_tasks) pooled.push_back(d_tasks);
-    if (d_refs) pooled.push_back(d_refs);
-    uint32_t* d_queue = rmode == 2 ? (uint32_t*)rbtk::dev_alloc(lq_off[n_levels] * 4) : nullptr;
-    if (d_queue) pooled.push_back(d_queue);
-    if (!d_tasks || !d_refs || (rmode == 2 && !d_queue)) { err = "device allocation failed"; rc = RBT_ERR_NOMEM; break; }
+    if (d_tasks) j.pooled.push_back(d_tasks);
+    if (d_refs) j.pooled.push_back(d_refs);
+    uint32_t* d_queue = rmode == 2 ? (uint32_t*)rbtk::dev_alloc(queue_words * 4) : nullptr;
+    if (d_queue) j.pooled.push_back(d_queue);
+    if (!d_tasks || !d_refs || (rmode == 2 && !d_queue)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    { size_t r = 0, q = 0;      // the merged levels' share of the refs and the queue memory; the lead batch's spare ticket words
+      for (size_t l = 0; l < n_levels; l++) { ReconLevel& lv = levels[l]; lv.refs = d_refs + r; r += (size_t)lv.n; lv.ticket = db[lead].d_tickets + TICKET_MERGED_LEVEL + l;
+        if (d_queue) { lv.queue = d_queue + q; q += rbtk::recon_queue_words(lv.ctbs); } } }
     rbtk::set_stream(job_stream(j, lead));
-    if (d_queue && rbtk::dev_memset(d_queue, 0, lq_off[n_levels] * 4)) { err = "device transfer failed"; rc = RBT_ERR_NO_DEVICE; break; }
-    if (rbtk::h2d(d_tasks, tasks.data(), tasks.size() * sizeof(RbtParseTask)) || rbtk::h2d(d_refs, refs.data(), refs.size() * sizeof(RbtFrameRef))) { err = "device transfer failed"; rc = RBT_ERR_NO_DEVICE; break; }
-    bool row_tasks = false; for (int gi : grp) row_tasks |= db[gi].has_row_tasks;
-    rbtk::timer_begin(T_PARSE); rbtk::launch_parse_tasks(d_tasks, (int)tasks.size(), mw4, row_tasks ? db[lead].d_tickets + 96 : nullptr); rbtk::timer_end(T_PARSE);
+    if (d_queue && rbtk::dev_memset(d_queue, 0, queue_words * 4)) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+    if (rbtk::h2d(d_tasks, tasks.data(), tasks.size() * sizeof(RbtParseTask)) || rbtk::h2d(d_refs, refs.data(), refs.size() * sizeof(RbtFrameRef))) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+    rbtk::timer_begin(T_PARSE); rbtk::launch_parse_tasks(d_tasks, (int)tasks.size(), mw4, row_tasks ? db[lead].d_tickets + TICKET_MERGED_PARSE : nullptr); rbtk::timer_end(T_PARSE);
     rbtk::timer_begin(T_RECON);
     for (size_t l = 0; l < n_levels; l++) {
-      // the merged launch of level l uses the lead batch's spare ticket counter 32 + l (its own levels use 0..31)
-      if (rmode == 0) rbtk::launch_recon_refs(d_refs + lv_off[l], (int)(lv_off[l + 1] - lv_off[l]), lv_w[l], lv_h[l]);
-      else if (rmode == 1) rbtk::launch_recon_level(d_refs + lv_off[l], (int)(lv_off[l + 1] - lv_off[l]), lv_w[l] * lv_h[l], db[lead].d_tickets + 32 + l);
-      else rbtk::launch_recon_queue(d_refs + lv_off[l], (int)(lv_off[l + 1] - lv_off[l]), lq_total[l], d_queue + lq_off[l], lq_wgs[l]);
+      launch_recon(levels[l], rmode);
       for (int gi : grp) if (l < db[gi].level_frames.size()) decode_launch_filters(db[gi], l);
     }
     rbtk::timer_end(T_RECON);
     for (int gi : grp) { db[gi].recon_external = true; j.recon_timed[gi] = gi == lead; }
   }
-  // enqueue order: longest pipeline first - except that a pipeline whose occupancy maps others wait for goes in front of them (an event has to be recorded before it is waited for)
-  std::vector<int> lorder; std::vector<char> feeds_any(ng, 0), consumes(ng, 0);
-  for (const OccJob& oj : occ_jobs) feeds_any[occ_src[oj.source].pipeline] = 1;
-  for (int g = 0; g < ng; g++) for (const EncStreamDesc& d : eb[g].desc) consumes[g] |= !d.occ4.empty();
-  for (int k = 0; k < ng; k++) if (feeds_any[order[k]]) lorder.push_back(order[k]);
-  for (int k = 0; k < ng; k++) if (!feeds_any[order[k]]) lorder.push_back(order[k]);
-  std::vector<int> occ_marks;
-  for (int k = 0; k < ng && !rc; k++) {
-    const int gi = lorder[k], sid = job_stream(j, gi); rbtk::set_stream(sid);
-    const std::vector<PoolJob>& jobs = pool_jobs[gi];
-    if (!chained[gi]) { rc = decode_launch(db[gi]); if (rc) { err = db[gi].err; break; } continue; }
-    // Intra pictures of the output only read the decoded pictures they are re-encoded from. When those are complete
-    // before the last dependency level of the decoder, analysis + intra coding run on an auxiliary stream underneath the
-    // remaining reconstruction levels.
-    EncodeBatch& e = eb[gi]; e.main_stream = sid;
-    size_t n_levels = db[gi].level_frames.size(), fork_level = 0;
-    for (size_t q = 0; q < e.frames.size(); q++) if (e.frame_is_idr[q]) {
-      const int si = e.frame_stream[q], local = (int)q - e.stream_first[si], ds = j.dec_of[gi][si];
-      fork_level = std::max(fork_level, (size_t)db[gi].frames[db[gi].stream_first[ds] + local].level);
-    }
-    int intra_done = 0;
-    const bool fork = gi == order[0] && j.has_aux && ng <= rbtk::RBT_AUX_STREAM && jobs.empty() && e.pad_jobs.empty() && fork_level + 1 < n_levels;   // longest pipeline only: one spare stream
-    const bool banded = db[gi].d_save != nullptr && !db[gi].ordered_parse;
-    rc = banded ? decode_launch_chunked(db[gi], parse_bands(), sid, aux) : decode_launch_parse(db[gi]);
-    if (rc) { err = db[gi].err; break; }
-    if (!db[gi].recon_external) rbtk::timer_begin(T_RECON);
-    for (size_t l = 0; l < n_levels && !db[gi].recon_external; l++) {
-      if (!(banded && l == 0)) decode_launch_level(db[gi], l);
-      if (fork && l == fork_level) {
-        e.aux_stream = aux;
-        rbtk::stream_wait(e.aux_stream, sid);
-        if (consumes[gi]) for (int m : occ_marks) rbtk::stream_wait_mark(e.aux_stream, m);      // occupancy-aware coding: the maps are made on the occupancy pipeline's stream
-        rbtk::set_stream(e.aux_stream); encode_launch_intra(e); intra_done = rbtk::stream_mark(e.aux_stream); encode_launch_entropy_intra(e); rbtk::set_stream(sid);
-      }
-    }
-    if (!db[gi].recon_external) rbtk::timer_end(T_RECON);
-    // the input's picture hashes behind the decoder's last filter: on the auxiliary stream where the intra coding was forked there, underneath the rest of the encoder
-    if (!db[gi].hash.empty()) {
-      if (fork) { rbtk::stream_wait(aux, sid); rbtk::set_stream(aux); decode_launch_hash(db[gi]); rbtk::set_stream(sid); }
-      else decode_launch_hash(db[gi]);
-    }
-    if (!jobs.empty()) {
-      // the pictures of one stream are of one size and their pooled copies evenly spaced (setup_encode): one launch per run of such jobs
-      rbtk::timer_begin(T_POOL);
-      for (size_t a0 = 0; a0 < jobs.size();) {
-        size_t a1 = a0 + 1; const PoolJob& p0 = jobs[a0];
-        const size_t step = a1 < jobs.size() ? (size_t)(jobs[a1].y - p0.y) : 0;
-        while (a1 < jobs.size() && jobs[a1].stride == p0.stride && jobs[a1].w == p0.w && jobs[a1].h == p0.h && jobs[a1].grey == p0.grey && (size_t)(jobs[a1].y - p0.y) == step * (a1 - a0)) a1++;
-        std::vector<const uint16_t*> ins; for (size_t q = a0; q < a1; q++) ins.push_back(jobs[q].in);
-        rbtk::launch_pool_many(ins.data(), (int)ins.size(), p0.stride, p0.w, p0.h, 2, p0.y, step, p0.grey);
-        a0 = a1;
-      }
-      rbtk::timer_end(T_POOL);
-    }
-    if (feeds_any[gi]) {
-      for (const OccJob& oj : occ_jobs) { const OccSource& os = occ_src[oj.source]; if (os.pipeline == gi) rbtk::launch_occ_units(os.occ, os.in_step, os.n, os.ow, os.oh, oj.W, oj.w4, oj.h4, oj.maps); }
-      occ_marks.push_back(rbtk::stream_mark(sid));
-    }
-    if (consumes[gi]) for (int m : occ_marks) rbtk::stream_wait_mark(sid, m);
-    if (fork) rbtk::stream_wait_mark(sid, intra_done); else { encode_launch_intra(e); encode_launch_entropy_intra(e); }
-    encode_launch_inter(e);
-    // the reconstructions' hashes (md5_sei) once SAO has been applied to all of them: beside the inter pictures' entropy coding where there is an auxiliary stream
-    if (!e.hash.empty()) {
-      if (fork) { const int m = rbtk::stream_mark(sid); rbtk::stream_wait_mark(aux, m); rbtk::set_stream(aux); e.hash.launch(); rbtk::set_stream(sid); }
-      else e.hash.launch();
-    }
-    encode_launch_entropy_rest(e);
-    if (fork) rbtk::stream_wait(sid, e.aux_stream);      // the intra pictures' entropy coding and the hashes on the auxiliary stream
+  return 0;
+}
+
+// One pipeline onto its stream: decode -> pool -> encode without a host round trip in between (PCCTranscoder.cpp:428-448, :466, :825-904).
+// Arena sharing (setup_encode) rests on the order made here: the encoder's first write to a buffer of a decoded picture has to come behind the decoder's last read of it.
+// The reconstruction of picture k reads its levels; its deblocking and SAO launches - decode_launch_filters, the last thing decode_launch_level enqueues for a level - read
+// its pre-SAO samples; nothing later does (reference pictures and the input's hash check read the SAO output). So:
+//  - one HIP stream: every level of the decoder is enqueued on the pipeline's stream before encode_launch_intra, the encoder's first kernel, goes onto the same stream
+//    (the merged launches of pipelines that share a stream, launch_merged, are enqueued earlier still, on that same stream);
+//  - intra coding forked onto the auxiliary stream: rbtk::stream_wait(aux, sid) below records an event on the pipeline's stream right behind decode_launch_level(fork_level),
+//    fork_level being the highest dependency level of any decoded picture an output I picture is coded from - so those pictures' filters are behind the event, and I
+//    pictures alias nothing else. The P pictures (encode_launch_inter) stay on the pipeline's stream, behind every level.
+static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
+  const int sid = job_stream(j, gi), aux = job_stream(j, rbtk::RBT_AUX_STREAM); rbtk::set_stream(sid);
+  DecodeBatch& db = j.db[gi]; const std::vector<PoolJob>& jobs = s.pool_jobs[gi];
+  if (!j.chained[gi]) { int rc = decode_launch(db); if (rc) j.err = db.err; return rc; }
+  // Intra pictures of the output only read the decoded pictures they are re-encoded from. When those are complete
+  // before the last dependency level of the decoder, analysis + intra coding run on an auxiliary stream underneath the
+  // remaining reconstruction levels.
+  EncodeBatch& e = j.eb[gi]; e.main_stream = sid;
+  size_t n_levels = db.level_frames.size(), fork_level = 0;
+  for (size_t q = 0; q < e.frames.size(); q++) if (e.frame_is_idr[q]) {
+    const int si = e.frame_stream[q], local = (int)q - e.stream_first[si], ds = j.dec_of[gi][si];
+    fork_level = std::max(fork_level, (size_t)db.frames[db.stream_first[ds] + local].level);
   }
+  int intra_done = 0;
+  const bool fork = gi == j.order[0] && j.has_aux && j.ng <= rbtk::RBT_AUX_STREAM && jobs.empty() && e.pad_jobs.empty() && fork_level + 1 < n_levels;   // longest pipeline only: one spare stream
+  const bool banded = db.d_save != nullptr && !db.ordered_parse;
+  if (int rc = banded ? decode_launch_chunked(db, parse_bands(), sid, aux) : decode_launch_parse(db)) { j.err = db.err; return rc; }
+  if (!db.recon_external) rbtk::timer_begin(T_RECON);
+  for (size_t l = 0; l < n_levels && !db.recon_external; l++) {
+    if (!(banded && l == 0)) decode_launch_level(db, l);
+    if (fork && l == fork_level) {
+      e.aux_stream = aux;
+      rbtk::stream_wait(e.aux_stream, sid);
+      if (s.consumes[gi]) for (int m : s.occ_marks) rbtk::stream_wait_mark(e.aux_stream, m);      // occupancy-aware coding: the maps are made on the occupancy pipeline's stream
+      rbtk::set_stream(e.aux_stream); encode_launch_intra(e); intra_done = rbtk::stream_mark(e.aux_stream); encode_launch_entropy_intra(e); rbtk::set_stream(sid);
+    }
+  }
+  if (!db.recon_external) rbtk::timer_end(T_RECON);
+  // the input's picture hashes behind the decoder's last filter: on the auxiliary stream where the intra coding was forked there, underneath the rest of the encoder
+  if (!db.hash.empty()) {
+    if (fork) { rbtk::stream_wait(aux, sid); rbtk::set_stream(aux); decode_launch_hash(db); rbtk::set_stream(sid); }
+    else decode_launch_hash(db);
+  }
+  if (!jobs.empty()) {
+    // the pictures of one stream are of one size and their pooled copies evenly spaced (setup_encode): one launch per run of such jobs
+    rbtk::timer_begin(T_POOL);
+    for (size_t a0 = 0; a0 < jobs.size();) {
+      size_t a1 = a0 + 1; const PoolJob& p0 = jobs[a0];
+      const size_t step = a1 < jobs.size() ? (size_t)(jobs[a1].y - p0.y) : 0;
+      while (a1 < jobs.size() && jobs[a1].stride == p0.stride && jobs[a1].w == p0.w && jobs[a1].h == p0.h && jobs[a1].grey == p0.grey && (size_t)(jobs[a1].y - p0.y) == step * (a1 - a0)) a1++;
+      std::vector<const uint16_t*> ins; for (size_t q = a0; q < a1; q++) ins.push_back(jobs[q].in);
+      rbtk::launch_pool_many(ins.data(), (int)ins.size(), p0.stride, p0.w, p0.h, 2, p0.y, step, p0.grey);
+      a0 = a1;
+    }
+    rbtk::timer_end(T_POOL);
+  }
+  if (s.feeds_any[gi]) {
+    for (const OccJob& oj : s.occ_jobs) { const OccSource& os = s.occ_src[oj.source]; if (os.pipeline == gi) rbtk::launch_occ_units(os.occ, os.in_step, os.n, os.ow, os.oh, oj.W, oj.w4, oj.h4, oj.maps); }
+    s.occ_marks.push_back(rbtk::stream_mark(sid));
+  }
+  if (s.consumes[gi]) for (int m : s.occ_marks) rbtk::stream_wait_mark(sid, m);
+  if (fork) rbtk::stream_wait_mark(sid, intra_done); else { encode_launch_intra(e); encode_launch_entropy_intra(e); }
+  encode_launch_inter(e);
+  // the reconstructions' hashes (md5_sei) once SAO has been applied to all of them: beside the inter pictures' entropy coding where there is an auxiliary stream
+  if (!e.hash.empty()) {
+    if (fork) { const int m = rbtk::stream_mark(sid); rbtk::stream_wait_mark(aux, m); rbtk::set_stream(aux); e.hash.launch(); rbtk::set_stream(sid); }
+    else e.hash.launch();
+  }
+  encode_launch_entropy_rest(e);
+  if (fork) rbtk::stream_wait(sid, e.aux_stream);      // the intra pictures' entropy coding and the hashes on the auxiliary stream
+  return 0;
+}
+
+// Phase A of a job: plan, build and upload everything, then enqueue. Every upload of the job is issued before its first kernel: a copy from pageable memory blocks the host
+// until the stream has reached it, and pipelines may share a stream. The first failure ends the submission (j.rc, j.err); gof_wait drains what was enqueued.
+GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule) {
+  GofJob* J = new GofJob(); GofJob& j = *J;
+  struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
+  j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
+  j.params.assign(p, p + n); j.n_in.assign(n_in, n_in + n);
+  SubmitPlan s; s.in = in; s.p = p; s.gof_rule = gof_rule;
+  int rc = plan_pipelines(j, s, depth);
+  j.t_gpu = now_ms();
+  if (!rc) rc = build_decoders(j, s);
+  if (!rc) rc = build_encoders(j, s);
+  if (!rc) rc = launch_merged(j);
+  // enqueue order: longest pipeline first - except that a pipeline whose occupancy maps others wait for goes in front of them (an event has to be recorded before it is waited for)
+  for (int feeding = 1; feeding >= 0; feeding--) for (int k = 0; k < j.ng && !rc; k++) if (s.feeds_any[j.order[k]] == feeding) rc = enqueue_pipeline(j, s, j.order[k]);
   j.rc = rc;
   return J;
 }
