@@ -10,7 +10,7 @@ namespace rbtk {
 hipStream_t current_stream();            // rbt_kernels.hip: the stream the host code selected (set_stream)
 #define g_stream current_stream()
 
-// one wave per slice segment: wave-uniform CABAC parse (rbt_parse.h)
+// one wave per slice segment: wave-uniform CABAC parse (rbt_parse.h; rbt_parse_slice branches once, on the slice type, into the intra-only or the general parser)
 // (CAP4: capacity of the parser's line buffers in 4-sample units; the variant fixes the LDS footprint of the workgroup)
 // ticket != nullptr: the list is handed to the waves in the order they start (a row task of a wavefront stream waits for the task of the CTB row above
 // it, which is earlier in the list: with start order = list order the wave it waits for is always running)

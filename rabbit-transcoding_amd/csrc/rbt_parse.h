@@ -62,6 +62,7 @@ struct RbtParse {
   int qp_key, qp_packed;             // qP of Y | Cb << 8 | Cr << 16 (incl. QpBdOffset) cached for QpY == qp_key (chroma mapping costs ~300 cycles)
   int il_packed, intra_chroma, max_trafo_depth, last_pu_merge;   // no arrays / index-selected fields here: they would pin the whole struct in scratch
   int error;
+  uint32_t sao_w0, sao_w1, sao_w2, sao_w3, sao_w4, sao_w5;   // intra-only instantiation, live inside pz_sao only (a local record of its own was left in scratch memory by the compiler; as part of this one it is registers)
   // Register-resident neighbour context (one value per lane). Current CTB, four horizontally adjacent 4x4 units per lane:
   // unit (ux,uy) lives in lane uy * 4 + (ux >> 2), byte ux & 3 (mv: register r_mv<ux & 3>).
   RBT_VEC(uint32_t, r_pm); RBT_VEC(uint32_t, r_dm); RBT_VEC(uint32_t, r_ed); RBT_VEC(uint32_t, r_qp); RBT_VEC(uint32_t, r_ref);
@@ -254,11 +255,14 @@ RBT_DEV PzRowRec pz_row_rec(const RbtParse* s, int row) {
   return r;
 }
 // producer: after pz_end_ctb of CTB (rx, ry) the line buffers hold this row's bottom line for the CTB's columns
-RBT_DEV void pz_export_row(RbtParse* s, int rx, int ry) {
+// (IO, here and below: the intra-only instantiation of the parser, see rbt_parse_slice. It holds no motion: the record's mv / ref columns get the values an
+// I slice always had there - mv 0, ref -1 - straight from constants, and are not read back.)
+template <bool IO> RBT_DEV void pz_export_row(RbtParse* s, int rx, int ry) {
   RBT_LDS_AS RbtParseLds* L = s->L; const int cap4 = RBT_UNI(L->cap4), l2 = pzc_log2_ctb(s), n4 = 1 << (l2 - 2), w4 = pzc_w4(s), x40 = rx << (l2 - 2), cnt = rbt_min(n4, w4 - x40);
   const PzRowRec r = pz_row_rec(s, ry);
   RBT_LDS_AS uint8_t *a_pm = pz_above_pm(L, cap4), *a_dm = pz_above_dm(L, cap4); RBT_LDS_AS int8_t* a_ref = pz_above_ref(L, cap4); RBT_LDS_AS int32_t* a_mv = pz_above_mv(L);
-  RBT_PAR_FOR(i, cnt) { r.pm[x40 + i] = a_pm[x40 + i]; r.dm[x40 + i] = a_dm[x40 + i]; r.ref[x40 + i] = a_ref[x40 + i]; r.mv[x40 + i] = a_mv[x40 + i]; }
+  if constexpr (IO) { (void)a_ref; (void)a_mv; RBT_PAR_FOR(i, cnt) { r.pm[x40 + i] = a_pm[x40 + i]; r.dm[x40 + i] = a_dm[x40 + i]; r.ref[x40 + i] = (int8_t)-1; r.mv[x40 + i] = 0; } }
+  else RBT_PAR_FOR(i, cnt) { r.pm[x40 + i] = a_pm[x40 + i]; r.dm[x40 + i] = a_dm[x40 + i]; r.ref[x40 + i] = a_ref[x40 + i]; r.mv[x40 + i] = a_mv[x40 + i]; }
   if (RBT_LANE0) {
     r.slice[rx] = pz_above_slice(L, cap4)[rx];
     uint32_t* g = (uint32_t*)&r.sao[rx]; const RBT_LDS_AS uint32_t* a = (const RBT_LDS_AS uint32_t*)&pz_sao_above(L, cap4)[rx];
@@ -266,13 +270,14 @@ RBT_DEV void pz_export_row(RbtParse* s, int rx, int ry) {
   }
 }
 // consumer (row task, first CTB row of this wave): CTB column `col` of the row above into the line buffers this wave would have filled itself
-RBT_DEV void pz_import_above(RbtParse* s, int col, int ry) {
+template <bool IO> RBT_DEV void pz_import_above(RbtParse* s, int col, int ry) {
   RBT_LDS_AS RbtParseLds* L = s->L;
   const int cap4 = RBT_UNI(L->cap4), l2 = pzc_log2_ctb(s), n4 = 1 << (l2 - 2), w4 = pzc_w4(s), wc = pzc_w_ctb(s), x40 = col << (l2 - 2);
   if (col >= wc) return;
   const int cnt = rbt_min(n4, w4 - x40); const PzRowRec r = pz_row_rec(s, ry - 1);
   RBT_LDS_AS uint8_t *a_pm = pz_above_pm(L, cap4), *a_dm = pz_above_dm(L, cap4); RBT_LDS_AS int8_t* a_ref = pz_above_ref(L, cap4); RBT_LDS_AS int32_t* a_mv = pz_above_mv(L);
-  RBT_PAR_FOR(i, cnt) { a_pm[x40 + i] = r.pm[x40 + i]; a_dm[x40 + i] = r.dm[x40 + i]; a_ref[x40 + i] = r.ref[x40 + i]; a_mv[x40 + i] = r.mv[x40 + i]; }
+  if constexpr (IO) { (void)a_ref; (void)a_mv; RBT_PAR_FOR(i, cnt) { a_pm[x40 + i] = r.pm[x40 + i]; a_dm[x40 + i] = r.dm[x40 + i]; } }
+  else RBT_PAR_FOR(i, cnt) { a_pm[x40 + i] = r.pm[x40 + i]; a_dm[x40 + i] = r.dm[x40 + i]; a_ref[x40 + i] = r.ref[x40 + i]; a_mv[x40 + i] = r.mv[x40 + i]; }
   if (RBT_LANE0) {
     pz_above_slice(L, cap4)[col] = r.slice[col];
     const uint32_t* g = (const uint32_t*)&r.sao[col]; RBT_LDS_AS uint32_t* a = (RBT_LDS_AS uint32_t*)&pz_sao_above(L, cap4)[col];
@@ -280,12 +285,27 @@ RBT_DEV void pz_import_above(RbtParse* s, int col, int ry) {
   }
   RBT_SYNC_LDS();
 }
-RBT_DEV void pz_begin_ctb(RbtParse* s, int rx, int ry) {
+template <bool IO> RBT_DEV void pz_begin_ctb(RbtParse* s, int rx, int ry) {
   RBT_LDS_AS RbtParseLds* L = s->L;
   s->ctb_x = rx << pzc_log2_ctb(s); s->ctb_y = ry << pzc_log2_ctb(s);
   const int cx4 = s->ctb_x >> 2, cap4 = RBT_UNI(L->cap4);
   RBT_LDS_AS uint8_t *a_pm = pz_above_pm(L, cap4), *a_dm = pz_above_dm(L, cap4); RBT_LDS_AS int8_t* a_ref = pz_above_ref(L, cap4); RBT_LDS_AS int32_t* a_mv = pz_above_mv(L);
   RBT_LDS_AS uint16_t* a_slice = pz_above_slice(L, cap4);
+  if constexpr (IO) {   // the same without the motion half: r_ref, r_mv*, n_ref, n_mv and the corner's ref / mv are never touched by this instantiation
+    (void)a_ref; (void)a_mv;
+    RBT_VFOR(p, 64) {
+      RBT_V(s->r_pm, p) = PZ_REP4(RBT_MODE_NONE); RBT_V(s->r_dm, p) = PZ_REP4(1); RBT_V(s->r_ed, p) = 0; RBT_V(s->r_qp, p) = 0;
+      uint32_t pm = RBT_MODE_NONE, dm = 1;
+      if (p == 0) { if (s->corner_ok) { pm = (uint32_t)s->corner_pm; dm = (uint32_t)s->corner_dm; } }
+      else if (p <= 17) {
+        const int xa4 = cx4 - 1 + p;
+        if (ry > 0 && xa4 < pzc_w4(s) && a_slice[(xa4 << 2) >> pzc_log2_ctb(s)] == s->slice_idx) { pm = a_pm[xa4]; dm = a_dm[xa4]; }
+      } else if (p >= 32 && p < 48) {
+        if (s->left_ok) { pm = L->left_pm[p - 32]; dm = L->left_dm[p - 32]; }
+      }
+      RBT_V(s->n_pm, p) = pm; RBT_V(s->n_dm, p) = dm;
+    }
+  } else
   RBT_VFOR(p, 64) {
     RBT_V(s->r_pm, p) = PZ_REP4(RBT_MODE_NONE); RBT_V(s->r_dm, p) = PZ_REP4(1); RBT_V(s->r_ed, p) = 0; RBT_V(s->r_qp, p) = 0; RBT_V(s->r_ref, p) = 0xFFFFFFFFu;
     RBT_V(s->r_mv0, p) = 0; RBT_V(s->r_mv1, p) = 0; RBT_V(s->r_mv2, p) = 0; RBT_V(s->r_mv3, p) = 0;
@@ -301,17 +321,22 @@ RBT_DEV void pz_begin_ctb(RbtParse* s, int rx, int ry) {
   }
 }
 // end of a CTB: spill its units to LDS, write them to the HBM maps, then roll the line buffers
-RBT_DEV void pz_end_ctb(RbtParse* s, int rx, int ry) {
+// (IO: the maps in HBM get what an I slice always wrote - mv 0, ref -1, no reference POC - and the mv / ref columns of the LDS buffers stay untouched)
+template <bool IO> RBT_DEV void pz_end_ctb(RbtParse* s, int rx, int ry) {
   RBT_LDS_AS RbtParseLds* L = s->L;
   int cx = s->ctb_x, cy = s->ctb_y, ctb = 1 << pzc_log2_ctb(s), n4 = ctb >> 2;
   RBT_VFOR(p, 64) {
-    const uint32_t pm = RBT_V(s->r_pm, p), dm = RBT_V(s->r_dm, p), ed = RBT_V(s->r_ed, p), qp = RBT_V(s->r_qp, p), rf = RBT_V(s->r_ref, p);
+    const uint32_t pm = RBT_V(s->r_pm, p), dm = RBT_V(s->r_dm, p), ed = RBT_V(s->r_ed, p), qp = RBT_V(s->r_qp, p);
     for (int j = 0; j < 4; j++) {
       const int k = 4 * p + j;
       L->cur_pm[k] = (uint8_t)(pm >> (8 * j)); L->cur_dm[k] = (uint8_t)(dm >> (8 * j)); L->cur_edges[k] = (uint8_t)(ed >> (8 * j));
-      L->cur_qp[k] = (int8_t)(qp >> (8 * j)); L->cur_ref[k] = (int8_t)(rf >> (8 * j));
+      L->cur_qp[k] = (int8_t)(qp >> (8 * j));
     }
+    if constexpr (!IO) {
+    const uint32_t rf = RBT_V(s->r_ref, p);
+    for (int j = 0; j < 4; j++) L->cur_ref[4 * p + j] = (int8_t)(rf >> (8 * j));
     L->cur_mv[4 * p] = (int32_t)RBT_V(s->r_mv0, p); L->cur_mv[4 * p + 1] = (int32_t)RBT_V(s->r_mv1, p); L->cur_mv[4 * p + 2] = (int32_t)RBT_V(s->r_mv2, p); L->cur_mv[4 * p + 3] = (int32_t)RBT_V(s->r_mv3, p);
+    }
   }
   RBT_SYNC_LDS();
   // map pointers are read from the picture record here, once per CTB, instead of living in registers for the whole slice
@@ -319,11 +344,16 @@ RBT_DEV void pz_end_ctb(RbtParse* s, int rx, int ry) {
   RBT_PAR_FOR(u, n4 * n4) {
     int ux = u % n4, uy = u / n4, x = cx + ux * 4, y = cy + uy * 4;
     if (x < pzc_w(s) && y < pzc_h(s)) {
-      int k = uy * 16 + ux, gk = (y >> 2) * pzc_w4(s) + (x >> 2), pm = L->cur_pm[k], ref = L->cur_ref[k], mv = L->cur_mv[k];
-      m_pm[gk] = (uint8_t)pm; m_dm[gk] = L->cur_dm[k]; m_edges[gk] = L->cur_edges[k]; m_qp[gk] = L->cur_qp[k]; m_ref[gk] = (int8_t)ref;
-      m_mv[2 * gk] = (int16_t)(mv & 0xFFFF); m_mv[2 * gk + 1] = (int16_t)(mv >> 16);
-      int mode = pm & RBT_PM_MODE_MASK;
-      m_refpoc[gk] = (mode == RBT_MODE_INTER || mode == RBT_MODE_SKIP) ? s->L->ref_poc[ref < 0 ? 0 : ref] : RBT_NO_REFPOC;
+      int k = uy * 16 + ux, gk = (y >> 2) * pzc_w4(s) + (x >> 2), pm = L->cur_pm[k];
+      m_pm[gk] = (uint8_t)pm; m_dm[gk] = L->cur_dm[k]; m_edges[gk] = L->cur_edges[k]; m_qp[gk] = L->cur_qp[k];
+      if constexpr (IO) { m_ref[gk] = (int8_t)-1; m_mv[2 * gk] = 0; m_mv[2 * gk + 1] = 0; m_refpoc[gk] = RBT_NO_REFPOC; }
+      else {
+        int ref = L->cur_ref[k], mv = L->cur_mv[k];
+        m_ref[gk] = (int8_t)ref;
+        m_mv[2 * gk] = (int16_t)(mv & 0xFFFF); m_mv[2 * gk + 1] = (int16_t)(mv >> 16);
+        int mode = pm & RBT_PM_MODE_MASK;
+        m_refpoc[gk] = (mode == RBT_MODE_INTER || mode == RBT_MODE_SKIP) ? s->L->ref_poc[ref < 0 ? 0 : ref] : RBT_NO_REFPOC;
+      }
     }
   }
   // above-left corner of the NEXT CTB = last unit of the old above row under this CTB
@@ -332,12 +362,14 @@ RBT_DEV void pz_end_ctb(RbtParse* s, int rx, int ry) {
   RBT_LDS_AS uint16_t* a_slice = pz_above_slice(L, cap4);
   int last = rbt_min(cx + ctb, pzc_w(s)) / 4 - 1;
   int c_ok = ry > 0 && a_slice[rx] == s->slice_idx;
-  int c_pm = a_pm[last], c_dm = a_dm[last], c_ref = a_ref[last], c_mv = a_mv[last];
+  int c_pm = a_pm[last], c_dm = a_dm[last], c_ref = 0, c_mv = 0;
+  if constexpr (!IO) { c_ref = a_ref[last]; c_mv = a_mv[last]; }
   RBT_SYNC_LDS();
-  s->corner_ok = c_ok; s->corner_pm = c_pm; s->corner_dm = c_dm; s->corner_ref = c_ref; s->corner_mv = c_mv;
+  s->corner_ok = c_ok; s->corner_pm = c_pm; s->corner_dm = c_dm;
+  if constexpr (!IO) { s->corner_ref = c_ref; s->corner_mv = c_mv; } else { (void)c_ref; (void)c_mv; (void)a_ref; (void)a_mv; }
   int rows = rbt_min(ctb, pzc_h(s) - cy) >> 2, cols = rbt_min(ctb, pzc_w(s) - cx) >> 2;
-  RBT_PAR_FOR(i, cols) { int k = (rows - 1) * 16 + i, a = (cx >> 2) + i; a_pm[a] = L->cur_pm[k]; a_dm[a] = L->cur_dm[k]; a_ref[a] = L->cur_ref[k]; a_mv[a] = L->cur_mv[k]; }
-  RBT_PAR_FOR(i, 16) { int k = i * 16 + cols - 1; L->left_pm[i] = i < rows ? L->cur_pm[k] : RBT_MODE_NONE; L->left_dm[i] = L->cur_dm[k]; L->left_ref[i] = L->cur_ref[k]; L->left_mv[i] = L->cur_mv[k]; }
+  RBT_PAR_FOR(i, cols) { int k = (rows - 1) * 16 + i, a = (cx >> 2) + i; a_pm[a] = L->cur_pm[k]; a_dm[a] = L->cur_dm[k]; if constexpr (!IO) { a_ref[a] = L->cur_ref[k]; a_mv[a] = L->cur_mv[k]; } }
+  RBT_PAR_FOR(i, 16) { int k = i * 16 + cols - 1; L->left_pm[i] = i < rows ? L->cur_pm[k] : RBT_MODE_NONE; L->left_dm[i] = L->cur_dm[k]; if constexpr (!IO) { L->left_ref[i] = L->cur_ref[k]; L->left_mv[i] = L->cur_mv[k]; } }
   if (RBT_LANE0) a_slice[rx] = (uint16_t)s->slice_idx;
   s->left_ok = rx + 1 < pzc_w_ctb(s);
   if (rx + 1 >= pzc_w_ctb(s)) s->corner_ok = 0;
@@ -406,8 +438,70 @@ template <int CI> RBT_DEV void pz_sao_comp(RbtParse* s, RbtCabacDec* c, PzSao* p
   const int sc = 1 << (bd - rbt_min(bd, 10));
   p->off[CI][0] = a0 * sc; p->off[CI][1] = a1 * sc; p->off[CI][2] = a2 * sc; p->off[CI][3] = a3 * sc;
 }
+// The same parameters as the six words of an RbtSao (pz_sao_word's layout, RbtParse::sao_w*), filled through compile-time byte positions: six registers, nothing for
+// the compiler to index at run time. Byte B of the record; every byte is set at most once, on zeroed words.
+template <int B> RBT_DEV void pz_saow_put(RbtParse* p, int v) {
+  const uint32_t m = ((uint32_t)v & 255u) << (8 * (B & 3));
+  if (B / 4 == 0) p->sao_w0 |= m; else if (B / 4 == 1) p->sao_w1 |= m; else if (B / 4 == 2) p->sao_w2 |= m; else if (B / 4 == 3) p->sao_w3 |= m; else if (B / 4 == 4) p->sao_w4 |= m; else p->sao_w5 |= m;
+}
+template <int B> RBT_DEV int pz_saow_get(const RbtParse* p) {
+  const uint32_t w = B / 4 == 0 ? p->sao_w0 : (B / 4 == 1 ? p->sao_w1 : (B / 4 == 2 ? p->sao_w2 : (B / 4 == 3 ? p->sao_w3 : (B / 4 == 4 ? p->sao_w4 : p->sao_w5))));
+  return (int)((w >> (8 * (B & 3))) & 255u);
+}
+// pz_sao_comp on the packed record: type at byte CI, band_position at 3 + CI, eo_class at 6 + CI, the four offsets from 9 + 4 * CI
+template <int CI> RBT_DEV void pz_saow_comp(RbtParse* s, RbtCabacDec* c, int bd, int cmax) {
+  RbtParse* p = s;
+  if ((CI == 0 && !pzs_sao_luma(s)) || (CI > 0 && !pzs_sao_chroma(s))) return;
+  int type;
+  if (CI == 2) type = pz_saow_get<1>(p);
+  else { type = 0; if (rbt_cd_bin(c, CTX_SAO_TYPE)) type = rbt_cd_bypass(c) ? 2 : 1; }
+  pz_saow_put<CI>(p, type);
+  if (!type) return;
+  int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+  while (a0 < cmax && rbt_cd_bypass(c)) a0++;
+  while (a1 < cmax && rbt_cd_bypass(c)) a1++;
+  while (a2 < cmax && rbt_cd_bypass(c)) a2++;
+  while (a3 < cmax && rbt_cd_bypass(c)) a3++;
+  if (type == 1) {
+    if (a0 && rbt_cd_bypass(c)) a0 = -a0;
+    if (a1 && rbt_cd_bypass(c)) a1 = -a1;
+    if (a2 && rbt_cd_bypass(c)) a2 = -a2;
+    if (a3 && rbt_cd_bypass(c)) a3 = -a3;
+    pz_saow_put<3 + CI>(p, (int)rbt_cd_bypass_n(c, 5));
+  } else {
+    a2 = -a2; a3 = -a3;
+    if (CI == 2) pz_saow_put<8>(p, pz_saow_get<7>(p));
+    else pz_saow_put<6 + CI>(p, (int)rbt_cd_bypass_n(c, 2));
+  }
+  const int sc = 1 << (bd - rbt_min(bd, 10));
+  pz_saow_put<9 + 4 * CI>(p, a0 * sc); pz_saow_put<10 + 4 * CI>(p, a1 * sc); pz_saow_put<11 + 4 * CI>(p, a2 * sc); pz_saow_put<12 + 4 * CI>(p, a3 * sc);
+}
 // ------------------------------------------------------------------------------------------------ SAO (7.3.8.3)
-RBT_DEV void pz_sao(RbtParse* s, int rx, int ry) {
+template <bool IO> RBT_DEV void pz_sao(RbtParse* s, int rx, int ry) {
+  if constexpr (IO) {
+    RbtCabacDec* c = &s->c;
+    rx = PZ_WU(rx); ry = PZ_WU(ry);
+    s->sao_w0 = 0u; s->sao_w1 = 0u; s->sao_w2 = 0u; s->sao_w3 = 0u; s->sao_w4 = 0u; s->sao_w5 = 0u;
+    const int wc = pzc_w_ctb(s);
+    if (pzs_sao_luma(s) || pzs_sao_chroma(s)) {
+      int merge_left = 0, merge_up = 0;
+      if (rx > 0 && s->left_ok) merge_left = rbt_cd_bin(c, CTX_SAO_MERGE);
+      if (ry > 0 && !merge_left && pz_above_slice(s->L, RBT_UNI(s->L->cap4))[rx] == s->slice_idx) merge_up = rbt_cd_bin(c, CTX_SAO_MERGE);
+      if (merge_left || merge_up) {
+        const RBT_LDS_AS uint32_t* w = merge_left ? (const RBT_LDS_AS uint32_t*)&s->L->sao_left : (const RBT_LDS_AS uint32_t*)&pz_sao_above(s->L, RBT_UNI(s->L->cap4))[rx];
+        s->sao_w0 = w[0]; s->sao_w1 = w[1]; s->sao_w2 = w[2]; s->sao_w3 = w[3]; s->sao_w4 = w[4]; s->sao_w5 = w[5] & 255u;   // (the three pad bytes stay zero, as pz_sao_word leaves them)
+      } else {
+        int bd = pzc_bit_depth(s), cmax = (1 << (rbt_min(bd, 10) - 5)) - 1;
+        pz_saow_comp<0>(s, c, bd, cmax); pz_saow_comp<1>(s, c, bd, cmax); pz_saow_comp<2>(s, c, bd, cmax);
+      }
+    }
+    if (RBT_LANE0) {
+      uint32_t* g = (uint32_t*)&s->f->sao[ry * wc + rx]; RBT_LDS_AS uint32_t* l = (RBT_LDS_AS uint32_t*)&s->L->sao_left; RBT_LDS_AS uint32_t* a = (RBT_LDS_AS uint32_t*)&pz_sao_above(s->L, s->L->cap4)[rx];
+      const uint32_t w0 = s->sao_w0, w1 = s->sao_w1, w2 = s->sao_w2, w3 = s->sao_w3, w4 = s->sao_w4, w5 = s->sao_w5;
+      g[0] = w0; l[0] = w0; a[0] = w0; g[1] = w1; l[1] = w1; a[1] = w1; g[2] = w2; l[2] = w2; a[2] = w2; g[3] = w3; l[3] = w3; a[3] = w3; g[4] = w4; l[4] = w4; a[4] = w4; g[5] = w5; l[5] = w5; a[5] = w5;
+    }
+    RBT_SYNC_LDS();
+  } else {
   RbtCabacDec* c = &s->c;
   rx = PZ_WU(rx); ry = PZ_WU(ry);
   PzSao p; pz_sao_unpack(&p, 0u, 0u, 0u, 0u, 0u, 0u);
@@ -429,6 +523,7 @@ RBT_DEV void pz_sao(RbtParse* s, int rx, int ry) {
     for (int w = 0; w < 6; w++) { const uint32_t v = pz_sao_word(&p, w); g[w] = v; l[w] = v; a[w] = v; }
   }
   RBT_SYNC_LDS();
+  }
 }
 
 // 4x4 scan positions packed 4 bits per entry (x | y << 2): diagonal, horizontal, vertical; and ctxIdxMap of 4x4 TBs
@@ -611,7 +706,7 @@ RBT_DEV int pz_scan_idx(int pred_mode, int log2, int c_idx, int intra_mode) {
 }
 
 // ------------------------------------------------------------------------------------------------ transform tree (7.3.8.8-10)
-RBT_DEV void pz_transform_unit(RbtParse* s, int x0, int y0, int xb, int yb, int log2, int blk, int cbf_luma, int cbf_cb, int cbf_cr) {
+template <bool IO> RBT_DEV void pz_transform_unit(RbtParse* s, int x0, int y0, int xb, int yb, int log2, int blk, int cbf_luma, int cbf_cb, int cbf_cr) {
   RbtCabacDec* c = &s->c;
 #ifdef RBT_PROFILE
   unsigned long long ttu_ = __builtin_readcyclecounter();
@@ -627,7 +722,8 @@ RBT_DEV void pz_transform_unit(RbtParse* s, int x0, int y0, int xb, int yb, int 
     pz_fill_qp(s, s->cu_x, s->cu_y, 1 << s->cu_log2, s->qp_y);
   }
   PZ_STAMP(s, 6);
-  int intra = s->cu_pred_mode == RBT_MODE_INTRA;
+  const int pred_mode = IO ? (int)RBT_MODE_INTRA : s->cu_pred_mode;   // IO: every CU is an intra CU, nothing to test
+  const int intra = pred_mode == RBT_MODE_INTRA;
   int part = 0;
   if (s->cu_part_mode == RBT_PART_NxN && intra) part = ((y0 - s->cu_y) >= (1 << (s->cu_log2 - 1)) ? 2 : 0) + ((x0 - s->cu_x) >= (1 << (s->cu_log2 - 1)) ? 1 : 0);
   pz_fill_tu(s, x0, y0, N, cbf_luma);
@@ -638,11 +734,11 @@ RBT_DEV void pz_transform_unit(RbtParse* s, int x0, int y0, int xb, int yb, int 
   int flags = (cbf_luma ? RBT_TU_CBF_Y : 0) | (intra ? RBT_TU_INTRA : 0) | (chroma_here ? RBT_TU_CHROMA : 0);
   if (chroma_here) flags |= (cbf_cb ? RBT_TU_CBF_CB : 0) | (cbf_cr ? RBT_TU_CBF_CR : 0);
   PZ_STAMP(s, 8);
-  if (cbf_luma && pz_residual(s, 0, x0, y0, log2, pz_scan_idx(s->cu_pred_mode, log2, 0, pz_il(s, part)))) flags |= RBT_TU_TS_Y;
+  if (cbf_luma && pz_residual(s, 0, x0, y0, log2, pz_scan_idx(pred_mode, log2, 0, pz_il(s, part)))) flags |= RBT_TU_TS_Y;
   PZ_STAMP(s, 9);
   if (chroma_here && !s->error) {
     int xc = (log2 > 2 ? x0 : xb) >> 1, yc = (log2 > 2 ? y0 : yb) >> 1, l2c = log2 > 2 ? log2 - 1 : 2;
-    int sc = pz_scan_idx(s->cu_pred_mode, l2c, 1, s->intra_chroma);
+    int sc = pz_scan_idx(pred_mode, l2c, 1, s->intra_chroma);
     if (cbf_cb && pz_residual(s, 1, xc, yc, l2c, sc)) flags |= RBT_TU_TS_CB;
     if (cbf_cr && !s->error && pz_residual(s, 2, xc, yc, l2c, sc)) flags |= RBT_TU_TS_CR;
   }
@@ -657,7 +753,7 @@ RBT_DEV void pz_transform_unit(RbtParse* s, int x0, int y0, int xb, int yb, int 
   s->t_tu += __builtin_readcyclecounter() - ttu_;
 #endif
 }
-RBT_DEV void pz_transform_tree(RbtParse* s, int x0, int y0, int xb0, int yb0, int log2, int depth0, int blk0, int pcb, int pcr) {
+template <bool IO> RBT_DEV void pz_transform_tree(RbtParse* s, int x0, int y0, int xb0, int yb0, int log2, int depth0, int blk0, int pcb, int pcr) {
   // Depth-first walk without recursion and without a stack in memory (a private array would live in scratch, and every
   // scratch access is an HBM-latency round trip for this lone wave): the per-level child counter (4 bits) and cbf_cb /
   // cbf_cr flags (2 bits) are packed into two registers, node coordinates are updated incrementally.
@@ -666,13 +762,14 @@ RBT_DEV void pz_transform_tree(RbtParse* s, int x0, int y0, int xb0, int yb0, in
   int lvl = 0, x = x0, y = y0, lg = log2;
   uint32_t states = 15u;                               // nibble lvl: 15 = not parsed yet, 0..3 = next child, 4 = done
   uint32_t flags = (uint32_t)((pcb ? 1 : 0) | (pcr ? 2 : 0));   // 2 bits per level: flags of the PARENT of the nodes at that level
-  const int intra = s->cu_pred_mode == RBT_MODE_INTRA;
+  const int intra = IO ? 1 : s->cu_pred_mode == RBT_MODE_INTRA;
   const int intra_split = intra && s->cu_part_mode == RBT_PART_NxN;
   while (!s->error) {
     lvl = PZ_WU(lvl); x = PZ_WU(x); y = PZ_WU(y); lg = PZ_WU(lg); states = (uint32_t)PZ_WU(states); flags = (uint32_t)PZ_WU(flags);
     int st = (int)((states >> (4 * lvl)) & 15u);
     if (st == 15) {
-      int inter_split = pzc_th_depth_inter(s) == 0 && !intra && s->cu_part_mode != RBT_PART_2Nx2N && lvl == 0;
+      int inter_split = 0;
+      if constexpr (!IO) inter_split = pzc_th_depth_inter(s) == 0 && !intra && s->cu_part_mode != RBT_PART_2Nx2N && lvl == 0;
       int split;
       if (lg <= pzc_log2_max_tb(s) && lg > pzc_log2_min_tb(s) && lvl < s->max_trafo_depth && !(intra_split && lvl == 0))
         split = rbt_cd_bin(c, CTX_SPLIT_TRANSFORM + 5 - lg);
@@ -690,7 +787,7 @@ RBT_DEV void pz_transform_tree(RbtParse* s, int x0, int y0, int xb0, int yb0, in
         PZ_STAMP(s, 13);
         int k = lvl ? (int)((states >> (4 * (lvl - 1))) & 15u) - 1 : 0, h = 1 << lg;
         int xb = lvl ? x - (k & 1) * h : x, yb = lvl ? y - (k >> 1) * h : y;
-        pz_transform_unit(s, x, y, xb, yb, lg, k, cbf_luma, cbf_cb, cbf_cr);
+        pz_transform_unit<IO>(s, x, y, xb, yb, lg, k, cbf_luma, cbf_cb, cbf_cr);
         PZ_STAMP(s, 14);
         st = 4;
       } else {
@@ -855,7 +952,7 @@ RBT_DEV void pz_intra_mpm(const RbtParse* s, int xp, int yp, int cand[3], int kn
     else { cand[0] = ca; cand[1] = 2 + ((ca + 29) % 32); cand[2] = 2 + ((ca - 2 + 1) % 32); }
   } else { cand[0] = ca; cand[1] = cb; cand[2] = (ca != 0 && cb != 0) ? 0 : ((ca != 1 && cb != 1) ? 1 : 26); }
 }
-RBT_DEV void pz_coding_unit(RbtParse* s, int x0, int y0, int log2, int depth) {
+template <bool IO> RBT_DEV void pz_coding_unit(RbtParse* s, int x0, int y0, int log2, int depth) {
   RbtCabacDec* c = &s->c;
 #ifdef RBT_PROFILE
   unsigned long long tcu_ = __builtin_readcyclecounter(); s->n_cu++;
@@ -869,6 +966,8 @@ RBT_DEV void pz_coding_unit(RbtParse* s, int x0, int y0, int log2, int depth) {
   s->cu_x = x0; s->cu_y = y0; s->cu_log2 = log2; s->cu_tq_bypass = 0; s->cu_part_mode = RBT_PART_2Nx2N; s->cu_pred_mode = RBT_MODE_INTRA;
   if (pzc_cu_qp_delta(s)) s->qp_y = pz_wrap_qp(s, s->qp_pred + s->cu_qp_delta_val);
   if (pzc_tq_bypass_enabled(s)) s->cu_tq_bypass = rbt_cd_bin(c, CTX_CU_TQ_BYPASS);
+  // IO: an I slice has no cu_skip_flag and no pred_mode_flag, and of part_mode only the intra bin
+  if constexpr (!IO) {
   int skip = 0;
   if (pzs_slice_type(s) != RBT_SLICE_I) {
     int nl = pz_nb(s, x0 - 1, y0), na = pz_nb(s, x0, y0 - 1);
@@ -884,10 +983,12 @@ RBT_DEV void pz_coding_unit(RbtParse* s, int x0, int y0, int log2, int depth) {
     return;
   }
   if (pzs_slice_type(s) != RBT_SLICE_I) s->cu_pred_mode = rbt_cd_bin(c, CTX_PRED_MODE) ? RBT_MODE_INTRA : RBT_MODE_INTER;
-  if (s->cu_pred_mode == RBT_MODE_INTRA) {
+  }
+  const bool intra_cu = IO || s->cu_pred_mode == RBT_MODE_INTRA;
+  if (intra_cu) {
     if (log2 == pzc_log2_min_cb(s)) s->cu_part_mode = rbt_cd_bin(c, CTX_PART_MODE) ? RBT_PART_2Nx2N : RBT_PART_NxN;
     if (s->cu_part_mode == RBT_PART_NxN && log2 == 3 && pzc_log2_min_tb(s) > 2) { s->error = 6; return; }
-  } else {
+  } else if constexpr (!IO) {
     if (rbt_cd_bin(c, CTX_PART_MODE)) s->cu_part_mode = RBT_PART_2Nx2N;
     else if (log2 == pzc_log2_min_cb(s)) {
       if (log2 == 3) s->cu_part_mode = rbt_cd_bin(c, CTX_PART_MODE + 1) ? RBT_PART_2NxN : RBT_PART_Nx2N;
@@ -901,7 +1002,7 @@ RBT_DEV void pz_coding_unit(RbtParse* s, int x0, int y0, int log2, int depth) {
     }
   }
   PZ_STAMP(s, 16);
-  if (s->cu_pred_mode == RBT_MODE_INTRA) {
+  if (intra_cu) {
     pz_fill_cu(s, x0, y0, N, RBT_MODE_INTRA | (s->cu_tq_bypass ? RBT_PM_TQ_BYPASS : 0), (depth << 6) | 1, s->qp_y);
     RBT_SYNC_LDS();
     PZ_STAMP(s, 17);
@@ -947,7 +1048,7 @@ RBT_DEV void pz_coding_unit(RbtParse* s, int x0, int y0, int log2, int depth) {
     int cmode = icp == 0 ? 0 : (icp == 1 ? 26 : (icp == 2 ? 10 : 1));
     if (icp == 4) s->intra_chroma = pz_il(s, 0);
     else s->intra_chroma = cmode == pz_il(s, 0) ? 34 : cmode;
-  } else {
+  } else if constexpr (!IO) {
     pz_fill_cu(s, x0, y0, N, RBT_MODE_NONE | (s->cu_tq_bypass ? RBT_PM_TQ_BYPASS : 0), (depth << 6) | 1, s->qp_y);
     RBT_SYNC_LDS();
     int h2 = N >> 1, q = N >> 2, pmode = s->cu_part_mode;
@@ -978,11 +1079,16 @@ RBT_DEV void pz_coding_unit(RbtParse* s, int x0, int y0, int log2, int depth) {
 #define PZ_CU_END() ((void)0)
 #endif
   PZ_STAMP(s, 20);
+  if constexpr (IO) {   // no rqt_root_cbf: an intra CU always has its transform tree
+    s->max_trafo_depth = pzc_th_depth_intra(s) + (s->cu_part_mode == RBT_PART_NxN);
+    pz_transform_tree<true>(s, x0, y0, x0, y0, log2, 0, 0, 0, 0);
+  } else {
   int rqt_root_cbf = 1;
   if (s->cu_pred_mode != RBT_MODE_INTRA && !(s->cu_part_mode == RBT_PART_2Nx2N && s->last_pu_merge)) rqt_root_cbf = rbt_cd_bin(c, CTX_RQT_ROOT_CBF);
   if (rqt_root_cbf) {
     s->max_trafo_depth = s->cu_pred_mode == RBT_MODE_INTRA ? pzc_th_depth_intra(s) + (s->cu_part_mode == RBT_PART_NxN) : pzc_th_depth_inter(s);
-    pz_transform_tree(s, x0, y0, x0, y0, log2, 0, 0, 0, 0);
+    pz_transform_tree<false>(s, x0, y0, x0, y0, log2, 0, 0, 0, 0);
+  }
   }
   RBT_SYNC_LDS();
   PZ_STAMP(s, 21);
@@ -990,7 +1096,7 @@ RBT_DEV void pz_coding_unit(RbtParse* s, int x0, int y0, int log2, int depth) {
 }
 
 // ------------------------------------------------------------------------------------------------ coding quadtree + slice data
-RBT_DEV void pz_coding_quadtree(RbtParse* s, int x0, int y0, int log2) {
+template <bool IO> RBT_DEV void pz_coding_quadtree(RbtParse* s, int x0, int y0, int log2) {
   // same stack-free walk as pz_transform_tree; children outside the picture are skipped (7.3.8.4)
   int lvl = 0, x = x0, y = y0, lg = log2;
   uint32_t states = 15u;
@@ -1008,7 +1114,7 @@ RBT_DEV void pz_coding_quadtree(RbtParse* s, int x0, int y0, int log2) {
       } else split = lg > pzc_log2_min_cb(s);
       PZ_STAMP(s, 23);
       if (pzc_cu_qp_delta(s) && lg >= pzc_log2_ctb(s) - pzc_diff_cu_qp_delta_depth(s)) pz_start_qg(s, x, y);
-      if (!split) { pz_coding_unit(s, x, y, lg, lvl); st = 4;
+      if (!split) { pz_coding_unit<IO>(s, x, y, lg, lvl); st = 4;
 #ifdef RBT_PROFILE
         s->t_last = __builtin_readcyclecounter();
 #endif
@@ -1042,7 +1148,11 @@ struct RbtParseSave {
 };
 // Entry: parses one slice segment (save == nullptr: in one go; else up to CTB row `row_limit`, resuming where it stopped).
 // `lds` holds RBT_PARSE_LDS_BYTES(cap4) bytes; the launcher picks cap4 >= the width of every picture of the launch / 4.
-RBT_DEV void rbt_parse_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx, const uint8_t* rbsp, RBT_LDS_AS RbtParseLds* lds, int cap4, RbtParseSave* save, int row_limit) {
+// IO = true is the instantiation for I slices: everything of the syntax and of the state that only a P slice has is compiled out (if constexpr) - cu_skip_flag,
+// pred_mode_flag, the inter part modes, prediction units with merge / AMVP / temporal candidates, rqt_root_cbf, the inter split of the transform tree, the motion
+// registers of RbtParse with their neighbour and corner copies, the mv / ref columns of the LDS buffers and the motion words of RbtParseSave. What reaches HBM is
+// byte for byte what the general instantiation writes for an I slice. IO = false is the general parser (P slices, which may hold intra CUs).
+template <bool IO> RBT_DEV void rbt_parse_slice_t(RbtFrame* frames, RbtSlice* slices, int slice_idx, const uint8_t* rbsp, RBT_LDS_AS RbtParseLds* lds, int cap4, RbtParseSave* save, int row_limit) {
   RbtParse s;
   RbtParseSave* sv = save ? save + slice_idx : nullptr;   // (own index: slice_idx is re-pointed at the slice's head further down)
   const int phase = sv ? RBT_UNI((int)sv->phase) : 0;
@@ -1102,9 +1212,10 @@ RBT_DEV void rbt_parse_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx, 
   } else {
     // resume: scalar state, bit reservoir (the word cursor is re-based on the same aligned pointer), context registers
     const int32_t* q = sv->sc;
-    s.left_ok = RBT_UNI(q[0]); s.corner_ok = RBT_UNI(q[1]); s.corner_pm = RBT_UNI(q[2]); s.corner_dm = RBT_UNI(q[3]); s.corner_ref = RBT_UNI(q[4]); s.corner_mv = RBT_UNI(q[5]);
+    s.left_ok = RBT_UNI(q[0]); s.corner_ok = RBT_UNI(q[1]); s.corner_pm = RBT_UNI(q[2]); s.corner_dm = RBT_UNI(q[3]);
+    if constexpr (!IO) { s.corner_ref = RBT_UNI(q[4]); s.corner_mv = RBT_UNI(q[5]); s.last_pu_merge = RBT_UNI(q[14]); }
     s.qp_y = RBT_UNI(q[6]); s.qp_pred = RBT_UNI(q[7]); s.qp_y_prev = RBT_UNI(q[8]); s.is_cu_qp_delta_coded = RBT_UNI(q[9]); s.cu_qp_delta_val = RBT_UNI(q[10]);
-    s.il_packed = RBT_UNI(q[11]); s.intra_chroma = RBT_UNI(q[12]); s.max_trafo_depth = RBT_UNI(q[13]); s.last_pu_merge = RBT_UNI(q[14]);
+    s.il_packed = RBT_UNI(q[11]); s.intra_chroma = RBT_UNI(q[12]); s.max_trafo_depth = RBT_UNI(q[13]);
     addr = RBT_UNI(q[15]); count = (uint32_t)RBT_UNI(q[16]);
     s.c.widx = (uint32_t)RBT_UNI(q[17]); s.c.nbuf = RBT_UNI(q[18]); s.c.range = (uint32_t)RBT_UNI(q[19]); s.c.value = (uint32_t)RBT_UNI(q[20]); s.c.avail = RBT_UNI(q[21]);
     s.c.buf = ((uint64_t)(uint32_t)RBT_UNI(sv->buf_hi) << 32) | (uint32_t)RBT_UNI(sv->buf_lo);
@@ -1131,9 +1242,10 @@ RBT_DEV void rbt_parse_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx, 
 #endif
       if (RBT_LANE0) {
         int32_t* q = sv->sc;
-        q[0] = s.left_ok; q[1] = s.corner_ok; q[2] = s.corner_pm; q[3] = s.corner_dm; q[4] = s.corner_ref; q[5] = s.corner_mv;
+        q[0] = s.left_ok; q[1] = s.corner_ok; q[2] = s.corner_pm; q[3] = s.corner_dm;
+        if constexpr (!IO) { q[4] = s.corner_ref; q[5] = s.corner_mv; q[14] = s.last_pu_merge; }
         q[6] = s.qp_y; q[7] = s.qp_pred; q[8] = s.qp_y_prev; q[9] = s.is_cu_qp_delta_coded; q[10] = s.cu_qp_delta_val;
-        q[11] = s.il_packed; q[12] = s.intra_chroma; q[13] = s.max_trafo_depth; q[14] = s.last_pu_merge;
+        q[11] = s.il_packed; q[12] = s.intra_chroma; q[13] = s.max_trafo_depth;
         q[15] = addr; q[16] = (int32_t)count; q[22] = seg;
         q[17] = (int32_t)s.c.widx; q[18] = s.c.nbuf; q[19] = (int32_t)s.c.range; q[20] = (int32_t)s.c.value; q[21] = s.c.avail;
         sv->buf_lo = (uint32_t)s.c.buf; sv->buf_hi = (uint32_t)(s.c.buf >> 32);
@@ -1152,8 +1264,8 @@ RBT_DEV void rbt_parse_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx, 
       seen_above = rbt_flag_wait_seen(&s.f->prow_done[ry - 1], (uint32_t)(rx + 2 < wc ? rx + 2 : wc), seen_above, &s.f->error);
       // the wait ran out, or the picture went bad meanwhile (the wave of the row above gave up and released its rows): what it would hand over is not there
       { const int32_t pe = rbt_err_peek(&s.f->error); if (pe) { s.error = pe; break; } }
-      if (rx == 0) pz_import_above(&s, 0, ry);
-      pz_import_above(&s, rx + 1, ry);
+      if (rx == 0) pz_import_above<IO>(&s, 0, ry);
+      pz_import_above<IO>(&s, rx + 1, ry);
     }
     if (wpp && rx == 0) {
       // first CTB of a row of a wavefront stream (9.3.1): the context variables of the CTB above-right after it was parsed when that CTB is
@@ -1168,24 +1280,24 @@ RBT_DEV void rbt_parse_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx, 
 #ifdef RBT_PROFILE
     unsigned long long tb_ = __builtin_readcyclecounter();
 #endif
-    pz_begin_ctb(&s, rx, ry);
+    pz_begin_ctb<IO>(&s, rx, ry);
 #ifdef RBT_PROFILE
     s.t_ctb += __builtin_readcyclecounter() - tb_;
 #endif
-    pz_sao(&s, rx, ry);
-    pz_coding_quadtree(&s, rx << pzc_log2_ctb(&s), ry << pzc_log2_ctb(&s), pzc_log2_ctb(&s));
+    pz_sao<IO>(&s, rx, ry);
+    pz_coding_quadtree<IO>(&s, rx << pzc_log2_ctb(&s), ry << pzc_log2_ctb(&s), pzc_log2_ctb(&s));
     if (RBT_LANE0) s.f->cmd_count[addr] = s.n_cmds;
     if (s.error) break;
 #ifdef RBT_PROFILE
     unsigned long long te_ = __builtin_readcyclecounter();
 #endif
-    pz_end_ctb(&s, rx, ry);
+    pz_end_ctb<IO>(&s, rx, ry);
 #ifdef RBT_PROFILE
     s.t_ctb += __builtin_readcyclecounter() - te_;
 #endif
     if (wpp && rx == 1) { rbt_ctx_store(&s.c.cs, lds->wpp_ctx); rbt_ctx_store_g(&s.c.cs, s.f->prow_ctx + (size_t)ry * 256); }   // storage process after the second CTB of a row
     if (wpp) {
-      pz_export_row(&s, rx, ry);
+      pz_export_row<IO>(&s, rx, ry);
       if (prefix_row == ry) { rbt_flag_wait(&s.f->prow_done[ry], (uint32_t)prefix_need, &s.f->error); prefix_row = -1; }
       RBT_FLAG_PUBLISH(&s.f->prow_done[ry], rx + 1);
     }   // bottom line of this CTB and (rx == 1) the context variables are out: a row task below may go on
@@ -1221,4 +1333,22 @@ RBT_DEV void rbt_parse_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx, 
   if (RBT_LANE0) { slices[own_idx].n_ctbs_decoded = count; if (s.error) s.f->error = s.error; if (sv) sv->phase = 2; }
   // a wave that gave up lets the row below go on at once (the picture is marked bad; nobody waits out the bound for rows that will not come)
   if (s.error && wpp && addr < n_ctb) { const int wc = pzc_w_ctb(&s); RBT_FLAG_PUBLISH(&s.f->prow_done[addr / wc], wc); }
+}
+// Entry of the kernels: one scalar branch per wave on the slice type, which the slice record holds before any slice data is read.
+// RBT_PARSE_INTRA_ONLY (MEASUREMENT builds only, tools/parser_resources.sh - never the product): the intra-only instantiation alone, so that the compiler's resource
+// report shows what that path needs by itself; such a build refuses P slices (error 7).
+#ifdef RBT_HOSTEMU
+extern "C" { inline uint32_t rbt_hostemu_parse_paths[2]; }   // slices parsed by the general / the intra-only instantiation (tests tell which one a stream exercised)
+#endif
+RBT_DEV void rbt_parse_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx, const uint8_t* rbsp, RBT_LDS_AS RbtParseLds* lds, int cap4, RbtParseSave* save, int row_limit) {
+  const int intra_only = RBT_UNI((int)(slices[slice_idx].slice_type & 3)) == RBT_SLICE_I;
+#ifdef RBT_HOSTEMU
+  __atomic_fetch_add(&rbt_hostemu_parse_paths[intra_only], 1u, __ATOMIC_RELAXED);
+#endif
+  if (intra_only) rbt_parse_slice_t<true>(frames, slices, slice_idx, rbsp, lds, cap4, save, row_limit);
+#ifdef RBT_PARSE_INTRA_ONLY
+  else if (RBT_LANE0) frames[slices[slice_idx].frame].error = 7;
+#else
+  else rbt_parse_slice_t<false>(frames, slices, slice_idx, rbsp, lds, cap4, save, row_limit);
+#endif
 }
