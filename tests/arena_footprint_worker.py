@@ -1,4 +1,4 @@
-"""Child process of tests/test_arena_footprint.py and tests/golden/make_arena_footprints.py (RBT_ARENA_SHARE is read once per process): a fixed list of calls on the host
+"""Child process of tests/arena_footprint_cases.py run, for tests/test_arena_footprint.py and tests/golden/make_arena_footprints.py (RBT_ARENA_SHARE is read once per process): a fixed list of calls on the host
 emulation, each submitted as a job whose device bytes (Context.job_memory: every allocation between submit and the return of submit - the decoder's and the encoder's
 arenas, pooled planes, occupancy maps, hash sets, merged launch lists) are printed as "MEM <case> <bytes>"; every output is held against the oracle. Ends with "OK <cases>"."""
 import os, sys

@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import oracle_lib as O
 import rbt_lib
-import test_gpu_transcode as T
+from parity_cases import r5_gof
 
 R = rbt_lib.module(); gs = rbt_lib.module_file("gof_shard")
 gpu = sys.argv[1] == "gpu"
@@ -31,7 +31,7 @@ def oracle(streams, params):
 
 
 # 1. an ordinary GOF: every geometry / attribute picture of the output aliases its decoded input picture
-so, sg, sa, _ = T._r5_streams(192, 128, 2, 77)
+(so, sg, sa), _ = r5_gof(192, 128, 2, 77)
 ps = [P(0, 8, 4, 5, -1, 1, 0), P(1, 24, 4, 5, -1, 1, 0), P(19, 32, 4, 5, -1, 1, 0)]
 job = ctx.submit_gof([so, sg, sa], ps); mem = ctx.job_memory(job); outs = ctx.wait_gof(job)
 assert outs == oracle([so, sg, sa], ps)
@@ -62,7 +62,7 @@ for o in outs[1:]:
     assert (w, h, chk, fail) == (192, 128, 4, 0)
 digest("md5", outs)
 # 5. sixteen jobs in flight: one HIP stream per job, the pipelines of a job behind each other in merged launches
-a = list(T._r5_streams(128, 128, 1, 303)[:3]); b = list(T._r5_streams(128, 64, 2, 404)[:3])
+a, b = r5_gof(128, 128, 1, 303)[0], r5_gof(128, 64, 2, 404)[0]
 want_a, want_b = oracle(a, ps), oracle(b, ps)
 ctx.set_depth(16)
 jobs = [ctx.submit_gof(a if i % 2 == 0 else b, ps) for i in range(16)]

@@ -8,7 +8,7 @@ Run:  python3 tests/golden/make_arena_footprints.py
 import json, os, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-import test_arena_footprint as T
+import arena_footprint_cases as T
 
 
 def main():

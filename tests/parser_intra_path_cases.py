@@ -13,7 +13,7 @@ SIZES = [(192, 128), (200, 136)]
 LOG2_CTBS = [6, 5, 4]
 ROWS = [1, 0, -1, -2]     # one CTB row per slice, one slice per picture, wavefront rows as dependent slice segments, wavefront rows behind entry points
 GRID = [(w, h, l, r) for (w, h) in SIZES for l in LOG2_CTBS for r in ROWS]
-STRESS_SEEDS = [3, 7, 12, 22]   # random syntax (tests/test_gpu_decode.py test_stress_streams): 30 % of the CUs of a P slice are intra CUs, with dQP, TS, SAO, NxN ...
+STRESS_SEEDS = [3, 7, 12, 22]   # random syntax (tests/parity_cases.py check_stress_decode): 30 % of the CUs of a P slice are intra CUs, with dQP, TS, SAO, NxN ...
 
 
 @functools.lru_cache(maxsize=None)

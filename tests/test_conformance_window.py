@@ -1,7 +1,7 @@
 """Picture sizes that are not multiples of the minimum CU size: the coded size is the display size rounded up (8 for
 all-intra, 16 for I,P pairs), padded by repetition, and the padding is signalled as the conformance window (7.4.3.2.1),
 which is what libx265 does behind PCCTranscoder.cpp:706. Real atlases hit this: a 1280x1296 atlas has a 640x648 occupancy
-map whose 2x2 pool is 320x324. Host emulation here (CPU), the same cases on the GPU in test_gpu_transcode.py."""
+map whose 2x2 pool is 320x324. The same cases on the host emulation (CPU) and on the GPU."""
 import os
 import subprocess
 import numpy as np

@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 import oracle_lib as O
-import synth
+from parity_cases import r5_gof
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "rabbit-transcoding_amd", "rbt_pipeline")
@@ -41,9 +41,7 @@ def _gofs(n):
     out = []
     for k in range(n):
         w, h = [(64, 64), (128, 64), (96, 96)][k % 3]
-        geo, attr, occ = synth.make_gof(w, h, 1 + k % 2, 700 + k)
-        out.append([O.encode(occ, w // 2, h // 2, 8, 8, gop=1, lossless=1, i_qp_offset=0, log2_ctb=6, rows_per_slice=0)[0],
-                    O.encode(geo, w, h, 10, 16, gop=2, log2_ctb=6, rows_per_slice=0)[0], O.encode(attr, w, h, 10, 22, gop=2, log2_ctb=6, rows_per_slice=0)[0]])
+        out.append(r5_gof(w, h, 1 + k % 2, 700 + k)[0])
     return out
 
 

@@ -1,9 +1,10 @@
-"""GPU parity: HIP decode path (through the C ABI) vs the CPU oracle, bit-exact."""
+"""GPU parity: HIP decode path (through the C ABI) vs the CPU oracle, bit-exact. The cases shared with the host build are in tests/parity_cases.py."""
 import numpy as np
 import pytest
 import oracle_lib as O
 import rbt_lib
 import synth
+import parity_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -18,14 +19,7 @@ def ctx():
 
 @pytest.mark.parametrize("seed", range(1, 41))
 def test_stress_streams(ctx, seed):
-    """random-syntax streams: all intra modes, NxN, TU trees, TS, bypass, AMP, AMVP/merge, TMVP, SAO, dQP, SDH, slices"""
-    w = [64, 96, 128, 80][seed % 4]; h = [64, 80, 48, 128][(seed // 4) % 4]
-    bd = 10 if seed % 3 else 8
-    fr = np.zeros((5, w * h * 3 // 2), np.uint16)
-    bs, rec = O.encode(fr, w, h, bd, qp=30, gop=2, stress_seed=seed, log2_ctb=0)
-    dec, dw, dh, dbd, chk, fail = ctx.decode(bs)
-    assert (dw, dh, dbd) == (w, h, bd) and chk == 5 and fail == 0
-    assert np.array_equal(dec, rec)
+    parity_cases.check_stress_decode(ctx, seed)
 
 
 @pytest.mark.parametrize("log2_ctb,rows", [(5, 1), (6, 0), (4, 2), (5, -1), (6, -1), (5, -2), (4, -2)])   # -1: wavefront rows as dependent slice segments, -2: behind entry points (x265's form)
@@ -58,25 +52,15 @@ def test_corrupt_stream_is_rejected(ctx):
 
 @pytest.mark.parametrize("w", [1536, 1552, 4096, 4112])
 def test_wide_pictures_use_the_larger_parser_variants(ctx, w):
-    """the slice parser's LDS line buffers come in three sizes (pictures up to 1536 / 4096 / 8192 samples wide): widths on
-    both sides of each boundary, several CTB rows so that every above-neighbour path reads the line buffers"""
-    h = 48
-    r = np.random.default_rng(w)
-    fr = r.integers(0, 1024, (2, w * h * 3 // 2)).astype(np.uint16)
-    fr[1] = np.clip(fr[0].astype(int) + r.integers(-2, 3, fr[0].shape), 0, 1023)
-    for log2_ctb, seed in ((4, 0), (6, 7)):
-        bs, rec = O.encode(fr, w, h, 10, qp=34, gop=2, stress_seed=seed, log2_ctb=log2_ctb)
-        dec, dw, dh, dbd, chk, fail = ctx.decode(bs)
-        assert (dw, dh, fail) == (w, h, 0) and np.array_equal(dec, rec)
+    parity_cases.check_wide_pictures(ctx, w)
 
 
 def test_slice_segments_must_tile_the_picture(ctx):
     """missing / repeated / swapped slice segments on the GPU: refused by the first wave that sees the hole or the overlap (RbtSlice::end_addr), row tasks below do not
-    wait out their bound, the context stays usable (tests/test_hostemu_parity.py slice_segment_damage)"""
+    wait out their bound, the context stays usable (tests/parity_cases.py slice_segment_damage)"""
     import time
-    import test_hostemu_parity as T
     t0 = time.time()
-    T.slice_segment_damage(ctx, rbt_lib.module())
+    parity_cases.slice_segment_damage(ctx, rbt_lib.module())
     assert time.time() - t0 < 60
 
 

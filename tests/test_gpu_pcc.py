@@ -73,9 +73,8 @@ def test_full_size_frame_after_transcode(ctx):
 
 
 def test_d2_matches_oracle_and_brute_force(ctx):
-    """rbt_d2 on the GPU (hash map voxel -> lowest index, ties walked in the bit volume, integer normal sums, double atomics) == oracle == brute force (tests/test_pcc_recon.py)"""
-    import test_pcc_recon as T
-    T.check_d2(ctx)
+    """rbt_d2 on the GPU (hash map voxel -> lowest index, ties walked in the bit volume, integer normal sums, double atomics) == oracle == brute force (tests/pcc_cases.py check_d2)"""
+    pcc_cases.check_d2(ctx)
 
 
 def test_d2_of_a_synthetic_frame(ctx):

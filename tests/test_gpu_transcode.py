@@ -1,10 +1,12 @@
 """GPU parity of the encode half and of the whole transcode path (through the C ABI) vs the CPU oracle: bit-exact
-bitstreams, plus size-independent properties at BASELINE.json frame size."""
+bitstreams, plus size-independent properties at BASELINE.json frame size. The cases shared with the host build are in tests/parity_cases.py."""
 import numpy as np
 import pytest
 import oracle_lib as O
 import rbt_lib
 import synth
+import parity_cases
+from parity_cases import r5_gof, r3_params
 
 pytestmark = pytest.mark.gpu
 
@@ -19,15 +21,7 @@ def ctx():
 
 @pytest.mark.parametrize("w,h,log2_ctb,n,bd,lossless", [(32, 96, 5, 2, 10, 0), (16, 64, 4, 3, 10, 0), (200, 120, 5, 4, 10, 0), (256, 192, 6, 2, 10, 0), (72, 40, 5, 2, 8, 1), (640, 352, 5, 2, 10, 0)])
 def test_wavefront_mode_edge_sizes(ctx, w, h, log2_ctb, n, bd, lossless):
-    """wavefront mode on the GPU (rows of a picture on different waves, progress counters between them) where its rules bend: pictures one CTB wide,
-    conformance windows, 64x64 CTBs, lossless, and a picture wide enough for several waves per picture; noise content. Encoder == oracle, decoder reads it back."""
-    fr = np.random.default_rng(w * 131 + h).integers(0, 1 << bd, size=(n, w * h * 3 // 2), dtype=np.uint16)
-    for qp in (22, 34):
-        a, ra = O.encode(fr, w, h, bd, qp, gop=1 if lossless else 2, i_qp_offset=0 if lossless else -3, lossless=lossless, log2_ctb=log2_ctb, rows_per_slice=-1)
-        b = ctx.encode(fr, w, h, bd, qp, gop=1 if lossless else 2, lossless=lossless, log2_ctb=log2_ctb, rows_per_slice=-1)
-        assert a == b
-        dec, dw, dh, dbd, chk, fail = ctx.decode(b)
-        assert (dw, dh, dbd, chk, fail) == (w, h, bd, n, 0) and np.array_equal(dec, ra)
+    parity_cases.check_wavefront_edge_sizes(ctx, w, h, log2_ctb, n, bd, lossless)
 
 
 @pytest.mark.parametrize("log2_ctb,rows", [(5, 1), (6, 0), (4, 2), (5, 0), (6, 1), (5, -1), (6, -1), (4, -1)])   # rows -1: wavefront mode
@@ -62,18 +56,10 @@ def test_or_pool(ctx):
     assert np.array_equal(ctx.or_pool(np.zeros((64, 64), np.uint16), 2), np.zeros((32, 32), np.uint16))
 
 
-def _r5_streams(w, h, n_pc, seed):
-    geo, attr, occ = synth.make_gof(w, h, n_pc, seed)
-    sg, _ = O.encode(geo, w, h, 10, 16, gop=2, log2_ctb=6, rows_per_slice=0)
-    sa, _ = O.encode(attr, w, h, 10, 22, gop=2, log2_ctb=6, rows_per_slice=0)
-    so, _ = O.encode(occ, w // 2, h // 2, 8, 8, gop=1, lossless=1, i_qp_offset=0, log2_ctb=6, rows_per_slice=0)
-    return so, sg, sa, occ
-
-
 @pytest.mark.parametrize("target", [(24, 32), (32, 42)])   # R3 and R1 QPs (cfg/rate/ctc-r3.cfg, ctc-r1.cfg)
 def test_transcode_substreams_identical_to_oracle(ctx, target):
     R = rbt_lib.module()
-    so, sg, sa, _ = _r5_streams(192, 128, 2, 77)
+    (so, sg, sa), _ = r5_gof(192, 128, 2, 77)
     for s, vt, qp in ((sg, R.RBT_VIDEO_GEOMETRY, target[0]), (sa, R.RBT_VIDEO_ATTRIBUTE, target[1]), (so, R.RBT_VIDEO_OCCUPANCY, 8)):
         assert ctx.transcode_substream(s, vt, qp, verify_md5=1) == O.transcode_substream(s, vt, qp)
     # occupancy precision 2: no pooling, lossless re-encode at the same size
@@ -81,10 +67,8 @@ def test_transcode_substreams_identical_to_oracle(ctx, target):
 
 
 def test_transcode_gof_equals_per_stream_calls(ctx):
-    R = rbt_lib.module()
-    so, sg, sa, _ = _r5_streams(192, 128, 3, 5)
-    P = R.StreamParams
-    outs = ctx.transcode_gof([so, sg, sa], [P(0, 8, 4, 5, 1, 1, 0), P(1, 24, 4, 5, 1, 1, 0), P(19, 32, 4, 5, 1, 1, 0)])
+    (so, sg, sa), _ = r5_gof(192, 128, 3, 5)
+    outs = ctx.transcode_gof([so, sg, sa], r3_params(rbt_lib.module()))
     assert outs[0] == ctx.transcode_substream(so, 0, 8)
     assert outs[1] == ctx.transcode_substream(sg, 1, 24)
     assert outs[2] == ctx.transcode_substream(sa, 19, 32)
@@ -94,7 +78,7 @@ def test_full_size_point_cloud_frame(ctx):
     """BASELINE.json frame size (1280x1280 maps, 640x640 occupancy), one point-cloud frame, R5 -> R3, bit-exact vs oracle;
     then the size-independent properties: output decodes with every MD5 SEI matching, occupancy == OR-pool of the input."""
     R = rbt_lib.module()
-    so, sg, sa, occ = _r5_streams(1280, 1280, 1, 1051)
+    (so, sg, sa), occ = r5_gof(1280, 1280, 1, 1051)
     P = R.StreamParams
     outs = ctx.transcode_gof([so, sg, sa], [P(0, 8, 4, 5, 1, 1, 1), P(1, 24, 4, 5, 1, 1, 1), P(19, 32, 4, 5, 1, 1, 1)])
     assert outs[1] == O.transcode_substream(sg, 1, 24)
@@ -112,7 +96,7 @@ def test_full_size_point_cloud_frame(ctx):
 def test_transcode_is_idempotent_in_structure(ctx):
     """transcoding the transcoder's own output (per-row slices, CTB 32) works and keeps sizes / frame counts"""
     R = rbt_lib.module()
-    so, sg, sa, _ = _r5_streams(128, 128, 2, 3)
+    (so, sg, sa), _ = r5_gof(128, 128, 2, 3)
     once = ctx.transcode_substream(sg, R.RBT_VIDEO_GEOMETRY, 24)
     twice = ctx.transcode_substream(once, R.RBT_VIDEO_GEOMETRY, 32, verify_md5=1)
     assert twice == O.transcode_substream(once, 1, 32)
@@ -121,102 +105,26 @@ def test_transcode_is_idempotent_in_structure(ctx):
 
 
 def test_transcode_rejects_damaged_input(ctx):
-    """a slice whose data is damaged must surface as an error from the chained decode -> re-encode pipeline (the
-    encoder is enqueued behind the decoder without a host round trip, so it runs on whatever the decoder left)"""
-    R = rbt_lib.module()
-    so, sg, sa, _ = _r5_streams(128, 128, 2, 11)
-    # CABAC data has no redundancy of its own: a damaged slice may decode to garbage without a syntax error. Eight damage patterns:
-    # none may crash or hang, most must be caught (overrun of the slice data, impossible syntax), and the context stays usable.
-    caught = 0
-    for seed in range(8):
-        bad = bytearray(sa)
-        r = np.random.default_rng(seed)
-        for k in r.integers(len(bad) // 4, len(bad) - 8, 200): bad[int(k)] = int(r.integers(1, 255))
-        try:
-            ctx.transcode_substream(bytes(bad[: len(bad) // 2 + len(bad) // 3]), R.RBT_VIDEO_ATTRIBUTE, 32)
-        except R.RbtError:
-            caught += 1
-    assert caught >= 4
-    # the context stays usable
-    assert ctx.transcode_substream(sg, R.RBT_VIDEO_GEOMETRY, 24) == O.transcode_substream(sg, 1, 24)
+    parity_cases.check_damaged_input(ctx, rbt_lib.module())
 
 
 def test_transcode_gof_more_streams_than_pipelines(ctx):
-    """more sub-bitstreams than HIP streams (4): pipelines share streams, results must not change"""
-    R = rbt_lib.module()
-    so, sg, sa, _ = _r5_streams(128, 128, 1, 33)
-    P = R.StreamParams
-    streams = [sg, sa, sg, sa, sg, so]
-    params = [P(1, 24, 4, 5, 1, 1, 0), P(19, 32, 4, 5, 1, 1, 0), P(1, 32, 4, 4, 1, 1, 0), P(19, 42, 4, 5, 0, 1, 0), P(1, 28, 4, 5, 1, 1, 1), P(0, 8, 4, 5, 1, 1, 0)]
-    outs = ctx.transcode_gof(streams, params)
-    assert outs[0] == O.transcode_substream(sg, 1, 24)
-    assert outs[1] == O.transcode_substream(sa, 19, 32)
-    assert outs[2] == O.transcode_substream(sg, 1, 32, log2_ctb=4)
-    assert outs[3] == O.transcode_substream(sa, 19, 42, rows_per_slice=0)
-    assert outs[4] == ctx.transcode_substream(sg, 1, 28, verify_md5=1)
-    assert outs[5] == O.transcode_substream(so, 0, 8)
+    parity_cases.check_more_streams_than_pipelines(ctx, rbt_lib.module(), 128, 128, log2_ctb=6)
 
 
 def test_two_gofs_in_one_call_equal_single_gof_calls(ctx):
-    """sub-bitstreams of several GOFs in one call (grouped by video type into three pipelines) give the single-GOF outputs"""
-    R = rbt_lib.module()
-    a = _r5_streams(128, 128, 2, 101); b = _r5_streams(192, 128, 1, 202)
-    P = R.StreamParams
-    ps = [P(0, 8, 4, 5, 1, 1, 0), P(1, 24, 4, 5, 1, 1, 0), P(19, 32, 4, 5, 1, 1, 0)]
-    outs = ctx.transcode_gof([a[0], a[1], a[2], b[0], b[1], b[2]], ps + ps)
-    assert outs[:3] == ctx.transcode_gof([a[0], a[1], a[2]], ps)
-    assert outs[3:] == ctx.transcode_gof([b[0], b[1], b[2]], ps)
+    parity_cases.check_two_gofs_in_one_call(ctx, rbt_lib.module(), (128, 128, 2, 101), (192, 128, 1, 202))
 
 
 def test_two_jobs_in_flight_equal_blocking_calls(ctx):
-    """rbt_submit_gof / rbt_wait_gof: up to four GOFs in flight on disjoint HIP streams give the blocking call's outputs"""
-    R = rbt_lib.module()
-    a = list(_r5_streams(192, 128, 4, 303)[:3]); b = list(_r5_streams(128, 192, 4, 404)[:3])
-    P = R.StreamParams
-    ps = [P(0, 8, 4, 5, 1, 1, 0), P(1, 24, 4, 5, 1, 1, 0), P(19, 32, 4, 5, 1, 1, 0)]
-    want_a, want_b = ctx.transcode_gof(a, ps), ctx.transcode_gof(b, ps)
-    ctx.set_depth(4)
-    for _ in range(3):
-        ja = ctx.submit_gof(a, ps); jb = ctx.submit_gof(b, ps); jc = ctx.submit_gof(b, ps); jd = ctx.submit_gof(a, ps)
-        with pytest.raises(R.RbtError) as e:
-            ctx.submit_gof(a, ps)
-        assert e.value.code == -7
-        assert ctx.wait_gof(jb) == want_b and ctx.wait_gof(jd) == want_a and ctx.wait_gof(ja) == want_a and ctx.wait_gof(jc) == want_b
-    # steady-state pipeline: submit i+1 before waiting for i
-    seq = [a, b, a, b, a]
-    outs = []; prev = ctx.submit_gof(seq[0], ps)
-    for g in seq[1:]:
-        nxt = ctx.submit_gof(g, ps); outs.append(ctx.wait_gof(prev)); prev = nxt
-    outs.append(ctx.wait_gof(prev))
-    assert outs == [want_a, want_b, want_a, want_b, want_a]
-    # deeper pipelines give each job fewer HIP streams (5: three, 6..8: two, 9..16: one, parsers of pipelines that share a
-    # stream in one merged launch): same outputs
-    for depth in (5, 8, 16, 1):
-        ctx.set_depth(depth)
-        jobs = [ctx.submit_gof(a if i % 2 == 0 else b, ps) for i in range(depth)]
-        with pytest.raises(R.RbtError):
-            ctx.set_depth(2)                 # refused while jobs are in flight
-        for i, jb in enumerate(jobs):
-            assert ctx.wait_gof(jb) == (want_a if i % 2 == 0 else want_b)
-    ctx.set_depth(4)
+    """three rounds, the steady-state pipeline, depths on both sides of every change in the HIP streams per job; no damaged job"""
+    parity_cases.check_jobs_in_flight(ctx, rbt_lib.module(), (192, 128, 4, 303), (128, 192, 4, 404), rounds=3, submit_ahead=True, depths=(5, 8, 16, 1), damaged_job=False)
 
 
 def test_destroy_with_jobs_in_flight_drains_them():
-    """rbt_destroy on a context that still owns submitted jobs waits for their streams and frees them; the library stays usable"""
+    """a new context takes the sixteen jobs afterwards"""
     R = rbt_lib.module()
-    a = list(_r5_streams(128, 128, 2, 909)[:3])
-    P = R.StreamParams
-    ps = [P(0, 8, 4, 5, 1, 1, 0), P(1, 24, 4, 5, 1, 1, 0), P(19, 32, 4, 5, 1, 1, 0)]
-    c1 = R.Context(device=0)
-    want = c1.transcode_gof(a, ps)
-    c1.set_depth(3)
-    for _ in range(3): c1.submit_gof(a, ps)
-    c1.close()                                   # three jobs never waited for
-    c2 = R.Context(device=0)
-    c2.set_depth(16)
-    jobs = [c2.submit_gof(a, ps) for _ in range(16)]     # every slot is free again
-    assert all(c2.wait_gof(j) == want for j in jobs)
-    c2.close()
+    parity_cases.check_destroy_with_jobs_in_flight(R, lambda: R.Context(device=0), (128, 128, 2, 909))
 
 
 
@@ -236,7 +144,7 @@ def test_stream_conversions_in_the_gpu_run(ctx):
     runs: a re-encoded sub-bitstream framed the way transcodeVideo leaves it (byteStreamToSampleStream, :517) and back, vs the oracle restatement"""
     import ctypes
     R = rbt_lib.module()
-    so, sg, sa, _ = _r5_streams(128, 128, 2, 19)
+    (so, sg, sa), _ = r5_gof(128, 128, 2, 19)
     out = ctx.transcode_substream(sg, R.RBT_VIDEO_GEOMETRY, 24)
     L = ctx.L
     p, n = ctypes.c_void_p(), ctypes.c_size_t()
@@ -255,9 +163,7 @@ def test_stream_conversions_in_the_gpu_run(ctx):
 def test_transform_skip_blocks(ctx, monkeypatch, w, h, log2_ctb, rows):
     """4x4 luma blocks with the DST or with transform skip, whichever is cheaper (csrc en_tile_intra_tb == oracle hm_tb_finish): step-shaped depth maps, where skipping
     wins often. GPU encoder == oracle, the stream differs from the oracle's without transform skip, and the GPU decoder reads it back to the encoder's reconstruction."""
-    r = np.random.default_rng(w + h)
-    y = (r.integers(0, 6, (h // 4, w // 4)) * 37 + 300).repeat(4, 0).repeat(4, 1)
-    y[:, w // 2:] += r.integers(0, 2, (h, w // 2)) * 9
+    y = parity_cases.step_map(np.random.default_rng(w + h), w, h)
     fr = np.concatenate([y.ravel(), np.full(w * h // 2, 512)]).astype(np.uint16)[None, :].repeat(4, 0)
     fr[2:, : w * h] = np.roll(y, 3, axis=1).ravel()
     ratios = []
@@ -282,12 +188,11 @@ def test_transform_skip_blocks(ctx, monkeypatch, w, h, log2_ctb, rows):
 
 def test_occupancy_aware_coding_matches_oracle(ctx):
     """rbt_stream_params.occupancy_rd on the GPU: geometry / attribute streams coded with the occupancy map the output carries (made on the
-    occupancy pipeline's stream, waited for by the others) == oracle_transcode_data for every case of tests/test_hostemu_parity.py occupancy_rd_cases, fewer bytes,
+    occupancy pipeline's stream, waited for by the others) == oracle_transcode_data for every case of tests/parity_cases.py occupancy_rd_cases, fewer bytes,
     the occupied samples as good as without; then with two jobs in flight (the maps of one job must not be read by another)."""
-    import test_hostemu_parity as T
     R = rbt_lib.module()
-    T.check_occupancy_rd(ctx, R)
-    cases = T.occupancy_rd_cases(R)[:3]
+    parity_cases.check_occupancy_rd(ctx, R)
+    cases = parity_cases.occupancy_rd_cases(R)[:3]
     want = [ctx.transcode_gof(s, p) for s, p in cases]
     jobs = [ctx.submit_gof(s, p) for s, p in cases[:2]]
     assert [ctx.wait_gof(j) for j in jobs] == want[:2]
@@ -295,8 +200,7 @@ def test_occupancy_aware_coding_matches_oracle(ctx):
 
 def test_preset_matches_oracle(ctx):
     """rbt_stream_params.preset on the GPU: RBT_PRESET_FAST == the oracle without the round-3 decision tools, the default == the oracle with them, both in one call"""
-    import test_hostemu_parity as T
-    T.check_preset(ctx, rbt_lib.module())
+    parity_cases.check_preset(ctx, rbt_lib.module())
 
 
 def test_preset_fast_full_size_frame(ctx):

@@ -4,7 +4,7 @@ of the product and of the oracle are both checked against it. V3C_VPS and V3C_AD
 import struct
 import numpy as np
 import oracle_lib as O
-import synth
+from parity_cases import r5_gof
 
 VPS, AD, OVD, GVD, AVD = range(5)
 
@@ -40,9 +40,7 @@ def parse(data):
 
 def gof_streams(w, h, n_pc, seed, log2_ctb=6):
     """[occupancy, geometry, attribute] Annex-B sub-bitstreams of one GOF at R5-like settings (precision 2 occupancy, lossless)"""
-    geo, attr, occ = synth.make_gof(w, h, n_pc, seed)
-    return [O.encode(occ, w // 2, h // 2, 8, 8, gop=1, lossless=1, i_qp_offset=0, log2_ctb=log2_ctb, rows_per_slice=0)[0],
-            O.encode(geo, w, h, 10, 16, gop=2, log2_ctb=log2_ctb, rows_per_slice=0)[0], O.encode(attr, w, h, 10, 22, gop=2, log2_ctb=log2_ctb, rows_per_slice=0)[0]]
+    return r5_gof(w, h, n_pc, seed, log2_ctb)[0]
 
 
 def gof_units(streams, seed, aux=False, extra_attr_partition=False):

@@ -11,6 +11,7 @@ from collections import namedtuple
 import numpy as np
 import oracle_lib as O
 import rbt_lib
+from parity_cases import r5_gof
 
 RBT_ERR_OUTPUT = -8                      # RBT_ERR_OUTPUT (include/rbt.h): coded data larger than the output buffer sized for it
 
@@ -137,10 +138,9 @@ def check_transcode_gof(ctx):
 
 def check_noise_between_ordinary_gofs(ctx):
     """submit / wait at depth 4: a GOF of noise between two ordinary ones; the ordinary ones come out as they do alone"""
-    import test_gpu_transcode as T
     R = rbt_lib.module()
     P = R.StreamParams
-    a = list(T._r5_streams(192, 128, 2, 303)[:3]); b = list(T._r5_streams(128, 192, 2, 404)[:3])
+    a, b = r5_gof(192, 128, 2, 303)[0], r5_gof(128, 192, 2, 404)[0]
     ps = [P(0, 8, 4, 5, -1, 1, 0), P(1, 24, 4, 5, -1, 1, 0), P(19, 32, 4, 5, -1, 1, 0)]
     noise = [a[0], input_stream("two_level"), input_stream("uniform")]
     want = [[O.transcode_substream(s, p.video_type, p.qp, rows_per_slice=-1) for s, p in zip(g, ps)] for g in (a, noise, b)]
