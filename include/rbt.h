@@ -305,7 +305,8 @@ int rbt_yuv420_to_yuv444(rbt_ctx* ctx, const uint16_t* yuv420, int width, int he
 int rbt_yuv16_to_rgb8(rbt_ctx* ctx, const uint16_t* yuv16, int n, uint8_t* rgb);
 /* rbt_reconstruct with the colours as the decoder leaves them: the two attribute pictures are up-converted (upsample_filter: RBT_UPSAMPLE_*), every point takes the three
  * 4:4:4 samples at its pixel (out->yuv, what colorPointCloud does on the converted video) and these are converted to RGB8 (*rgb: 3 bytes per point, released with rbt_free).
- * attr_t0 is required (attr_t1 too with two maps); attr_bit_depth 8 or 10. Geometry smoothing moves points, not colours. */
+ * attr_t0 is required (attr_t1 too with two maps); attr_bit_depth 8 or 10. Geometry smoothing moves points, not colours: the re-colouring the reference decoder does after
+ * its smoothing is rbt_reconstruct_decoded below. */
 int rbt_reconstruct_rgb(rbt_ctx* ctx, const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const uint16_t* occ_luma, const uint16_t* geo_d0,
                         const uint16_t* geo_d1, int geo_bit_depth, const uint16_t* attr_t0, const uint16_t* attr_t1, int attr_bit_depth, int upsample_filter,
                         rbt_cloud* out, uint8_t** rgb);
@@ -327,6 +328,44 @@ int rbt_color_metric(rbt_ctx* ctx, const int16_t* xyz_a, const uint8_t* rgb_a, i
  * [2] colour metric (its kernels: insert + merge and distance, without the read-back of the merged counts between them); 0 for a stage that has not run. The stages are
  * separate launches inside calls that also copy and allocate: this is the only way to time them without a profiling build (tools/color_quality.py). */
 int rbt_color_stage_ms(rbt_ctx* ctx, double ms[3]);
+
+/* ---- attribute transfer after geometry smoothing (csrc/rbt_color.h) ----
+ * Under the CTC settings the reference decoder copies the cloud, smooths the geometry and then re-colours every point the smoothing moved (PCCDecoder.cpp:434-494:
+ * tempFrameBuffer.transferColors16bitBP(reconstruct, 1, 0, isAttributes444, 8, 1, true, true, true, false, 4, 4, 1000, 1000, 1000 * 256, 1000 * 256), PCCPointSet.cpp:1126-1485;
+ * attrTransferFilterType_ 1). With these arguments the distance and colour pruning never fires and the search range is 0, and what is left is this.
+ * Source S: the cloud before smoothing (positions, 16-bit 4:4:4 triples). Target T: the cloud after it, with the same colours, and one byte per point, "moved". Distances are
+ * squared Euclidean distances of integer positions.
+ *   forward, for every moved u:  N(u) = the 8 source points nearest to T[u]. If the nearest is at distance 0, color1[u] is its colour; else per channel
+ *            color1[u] = clip16(round(sum(c_i w_i) / sum(w_i))), w_i = 1 / (dist_i + 4.0), in double, summed over N(u) in its order. The 8 neighbours of all moved points, moved
+ *            points in index order, form the list E.
+ *   backward, for every entry e of E:  v = the target point nearest to e's position (among ALL target points). If |e.colour - T.colour[v]| < 40 in all three channels (the
+ *            colours before any update), (dist(e, v), e.colour) joins the list L(v).
+ *   result, for every moved u:  L(u) empty: color1[u]; one entry: its colour; else per channel clip16(round(sum(c w) / sum(w))), w = 1 / (sqrt(dist) + 4.0), in list order.
+ * round is C's (half away from zero); sqrt and the divisions are the correctly rounded double operations. Points that did not move keep their colour.
+ * Where the reference depends on the order its kd-tree (nanoflann) returns equidistant points in, or on an unstable std::sort, this is defined instead, as rbt_d2 and
+ * rbt_color_metric define their tie sets: N(u) is ordered by (distance, source index) - ties at the 8th place and among coincident points go to the lower index; v is the
+ * lowest-index target point at the nearest distance; L(v) is ordered by (distance, position in E).
+ * Coordinates 0..1023. tgt_yuv: the colours before on entry, after on return. *n_changed: points whose triple is another one afterwards. n_src < 8 (the reference's search
+ * asserts there), a coordinate out of range or a null pointer: RBT_ERR_PARAM. n_tgt == 0 or no moved point: nothing to do, RBT_OK. `moved` may be set for a point whose
+ * position is unchanged: it takes the colour of its source twin. A moved point with fewer than 8 source points within 64 grid units (per axis) is refused,
+ * RBT_ERR_UNSUPPORTED: the search is bounded, and the smoothing does not carry a point that far from the cloud it came from. Two more limits, RBT_ERR_UNSUPPORTED as well, keep
+ * the two single-lane sorts short: at most 256 source points at one position, at most 1024 entries in one list L(v). */
+int rbt_transfer_colors(rbt_ctx* ctx, const int16_t* src_xyz, const uint16_t* src_yuv, int n_src, const int16_t* tgt_xyz, uint16_t* tgt_yuv, const uint8_t* moved, int n_tgt,
+                        int* n_changed);
+/* rbt_reconstruct_rgb followed by what the reference decoder does next: the positions before smoothing stay on the device, the smoothing runs with a flag per point, the
+ * colours are transferred from the unsmoothed to the smoothed cloud as above, and the RGB conversion runs on the transferred triples (out->yuv holds them).
+ * attr_transfer: 0 = off, 1 = the filter above; any other value (the reference's filter types 2, 3, 5, 7, 9) RBT_ERR_UNSUPPORTED. *moved (may be NULL): one byte per point, 1 for
+ * the out->n_smoothed points the smoothing moved, released with rbt_free. With attr_transfer 0 or atlas->geometry_smoothing 0 the cloud and *rgb are rbt_reconstruct_rgb's.
+ * Unlike rbt_reconstruct_rgb, the transfer needs the cloud inside the 1024^3 volume of the metrics: with attr_transfer 1 and at least one moved point, a coordinate outside
+ * 0..1023 before or after smoothing gives RBT_ERR_PARAM (as do fewer than 8 points), and the limits of rbt_transfer_colors apply. */
+int rbt_reconstruct_decoded(rbt_ctx* ctx, const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const uint16_t* occ_luma, const uint16_t* geo_d0,
+                            const uint16_t* geo_d1, int geo_bit_depth, const uint16_t* attr_t0, const uint16_t* attr_t1, int attr_bit_depth, int upsample_filter, int attr_transfer,
+                            rbt_cloud* out, uint8_t** rgb, uint8_t** moved);
+/* The fourth colour stage next to rbt_color_stage_ms (whose array of three is part of the ABI): device milliseconds of the transfer's kernels (index building, forward,
+ * backward, lists; in rbt_reconstruct_decoded also the two copies that keep the cloud from before the smoothing and the filter pass that writes the per-point flags; events
+ * around the launches; the clears of the two 128 MB volumes and of the maps, the allocations and the read-back are outside) and the number of colours changed, in this context's last
+ * rbt_transfer_colors or rbt_reconstruct_decoded; 0 when that call had nothing to transfer. Either pointer may be NULL. */
+int rbt_transfer_stage(rbt_ctx* ctx, double* ms, int* n_changed);
 
 #ifdef __cplusplus
 }

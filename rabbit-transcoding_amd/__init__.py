@@ -146,6 +146,10 @@ def load(path=None):
                                       C.POINTER(Cloud), C.POINTER(C.c_void_p)]
     L.rbt_color_metric.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ColorResult)]
     L.rbt_color_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.rbt_transfer_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.rbt_reconstruct_decoded.argtypes = [C.c_void_p, C.POINTER(AtlasParams), C.POINTER(Patch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(Cloud), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rbt_transfer_stage.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.rbt_v3c_index.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(V3CUnit)), C.POINTER(C.c_int)]
     L.rbt_v3c_write.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_v3c_stats.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(V3CStat)]
@@ -450,10 +454,42 @@ class Context:
         return {n: (getattr(r, n) if n in ("n_a", "n_b") else list(getattr(r, n))) for n, _ in ColorResult._fields_}
 
     def color_stage_ms(self):
-        """rbt_color_stage_ms: device milliseconds of the last up-conversion, RGB conversion and colour metric of this context"""
-        ms = (C.c_double * 3)()
+        """rbt_color_stage_ms + rbt_transfer_stage: device milliseconds of the last up-conversion, RGB conversion, colour metric and attribute transfer of this context"""
+        ms = (C.c_double * 3)(); t = C.c_double()
         self._chk(self.L.rbt_color_stage_ms(self.h, ms))
-        return {"upconvert": ms[0], "rgb": ms[1], "metric": ms[2]}
+        self._chk(self.L.rbt_transfer_stage(self.h, C.byref(t), None))
+        return {"upconvert": ms[0], "rgb": ms[1], "metric": ms[2], "transfer": t.value}
+
+    def transfer_colors(self, src_xyz, src_yuv, tgt_xyz, tgt_yuv, moved):
+        """rbt_transfer_colors: the attribute transfer after geometry smoothing on its own. src_* : the cloud before smoothing (int16 [n,3], uint16 [n,3]); tgt_xyz: the
+        cloud after it, tgt_yuv its colours before the transfer, moved: one flag per target point -> (yuv uint16 [n_tgt,3] after the transfer, n_changed)"""
+        sx = np.ascontiguousarray(src_xyz, dtype=np.int16).reshape(-1, 3); sc = np.ascontiguousarray(src_yuv, dtype=np.uint16).reshape(-1, 3)
+        tx = np.ascontiguousarray(tgt_xyz, dtype=np.int16).reshape(-1, 3); out = np.array(tgt_yuv, dtype=np.uint16).reshape(-1, 3)
+        mv = np.ascontiguousarray(np.asarray(moved) != 0, dtype=np.uint8).reshape(-1)
+        if sc.shape != sx.shape or out.shape != tx.shape or mv.shape[0] != tx.shape[0]:
+            raise ValueError("one colour per point and one flag per target point")
+        n = C.c_int()
+        self._chk(self.L.rbt_transfer_colors(self.h, sx.ctypes.data, sc.ctypes.data, sx.shape[0], tx.ctypes.data, out.ctypes.data, mv.ctypes.data, tx.shape[0], C.byref(n)))
+        return out, n.value
+
+    def reconstruct_decoded(self, atlas, patches, occ, d0, d1, geo_bd=10, t0=None, t1=None, attr_bd=10, upsample_filter=RBT_UPSAMPLE_F0, attr_transfer=1):
+        """rbt_reconstruct_decoded: reconstruct_rgb, then the colours of the points the geometry smoothing moved are transferred from the unsmoothed cloud as the reference
+        decoder does (attr_transfer=1; 0 = off) -> (xyz, yuv, occupancy_map, block_to_patch, rgb, moved uint8 [n]); self.n_changed = colours the transfer changed"""
+        ps = (Patch * max(1, len(patches)))(*patches)
+        arr = [np.ascontiguousarray(x, dtype=np.uint16) if x is not None else None for x in (occ, d0, d1, t0, t1)]
+        ptr = [x.ctypes.data if x is not None else None for x in arr]
+        c, rgb_p, mv_p = Cloud(), C.c_void_p(), C.c_void_p()
+        self._chk(self.L.rbt_reconstruct_decoded(self.h, C.byref(atlas), ps, len(patches), ptr[0], ptr[1], ptr[2], geo_bd, ptr[3], ptr[4], attr_bd, upsample_filter, attr_transfer,
+                                                 C.byref(c), C.byref(rgb_p), C.byref(mv_p)))
+        n, w, h, res = c.n_points, atlas.width, atlas.height, atlas.occupancy_resolution
+        xyz = np.ctypeslib.as_array(c.xyz, shape=(max(n, 1), 3))[:n].copy(); yuv = np.ctypeslib.as_array(c.yuv, shape=(max(n, 1), 3))[:n].copy()
+        om = np.ctypeslib.as_array(c.occupancy_map, shape=(h, w)).copy(); b2p = np.ctypeslib.as_array(c.block_to_patch, shape=(h // res, w // res)).copy()
+        rgb = np.frombuffer(C.string_at(rgb_p, 3 * n), np.uint8).reshape(n, 3).copy()
+        moved = np.frombuffer(C.string_at(mv_p, n), np.uint8).copy()
+        self.n_smoothed = c.n_points and c.n_smoothed
+        ch = C.c_int(); self._chk(self.L.rbt_transfer_stage(self.h, None, C.byref(ch))); self.n_changed = ch.value
+        self.L.rbt_free(rgb_p); self.L.rbt_free(mv_p); self.L.rbt_cloud_free(C.byref(c))
+        return xyz, yuv, om, b2p, rgb, moved
 
     def selftest_transform32(self, blocks, bit_depth=10):
         """rbt_selftest_transform32: matrix-core vs vector-ALU 32-point transforms on int16 blocks [n, 1024]; returns the number of differing samples"""

@@ -1,4 +1,4 @@
-// Kernels and launchers of the colour stages (rbt_color.h): 4:2:0 -> 4:4:4 up-conversion, YUV16 -> RGB8, colour metric. A translation unit of its own because it is
+// Kernels and launchers of the colour stages (rbt_color.h): 4:2:0 -> 4:4:4 up-conversion, YUV16 -> RGB8, colour metric, attribute transfer after geometry smoothing. A translation unit of its own because it is
 // compiled with -ffp-contract=off (Makefile): the up-conversion and the RGB conversion must round every product and every sum on its own, as the reference's host code
 // does, so that their output is the same bits everywhere. No __fmul_rn / __fadd_rn is needed on top of that; the bodies also carry `#pragma clang fp contract(off)`.
 #include <hip/hip_runtime.h>
@@ -53,6 +53,24 @@ __global__ void __launch_bounds__(256) k_col_dist(RbtColSet P, RbtColSet Q, unsi
   }
 }
 
+// ---- attribute transfer (rbt_color.h): one lane per source point / hash slot / target point / moved point / entry; no LDS ----
+__global__ void __launch_bounds__(256) k_tc_copy(uint16_t* dst, const uint16_t* src, size_t n) { const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i < n) dst[i] = src[i]; }
+__global__ void __launch_bounds__(256) k_tc_flag(RbtSmooth G, const int16_t* xyz_before, const uint32_t* meta, uint8_t* moved) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i < G.n_points) moved[i] = (uint8_t)tc_flag(&G, xyz_before, meta, i);
+}
+__global__ void __launch_bounds__(256) k_tc_src_count(RbtTransfer T) { const int i = (int)(blockIdx.x * 256 + threadIdx.x); if (i < T.ns) tc_src_count(&T, i); }
+__global__ void __launch_bounds__(256) k_tc_src_alloc(RbtTransfer T) { const uint32_t s = blockIdx.x * 256 + threadIdx.x; if (s < (1u << T.slg)) tc_src_alloc(&T, s); }
+__global__ void __launch_bounds__(256) k_tc_src_scatter(RbtTransfer T) { const int i = (int)(blockIdx.x * 256 + threadIdx.x); if (i < T.ns) tc_src_scatter(&T, i); }
+__global__ void __launch_bounds__(256) k_tc_src_sort(RbtTransfer T) { const uint32_t s = blockIdx.x * 256 + threadIdx.x; if (s < (1u << T.slg)) tc_src_sort(&T, s); }
+__global__ void __launch_bounds__(256) k_tc_tgt_insert(RbtTransfer T) { const int u = (int)(blockIdx.x * 256 + threadIdx.x); if (u < T.nt) tc_tgt_insert(&T, u); }
+// 64 lanes per workgroup: the walks of neighbouring moved points differ in length, and a short workgroup frees its slot sooner
+__global__ void __launch_bounds__(64) k_tc_forward(RbtTransfer T) { tc_forward(&T, blockIdx.x * 64 + threadIdx.x); }
+__global__ void __launch_bounds__(256) k_tc_backward(RbtTransfer T) { tc_backward(&T, blockIdx.x * 256 + threadIdx.x); }
+__global__ void __launch_bounds__(256) k_tc_list_alloc(RbtTransfer T) { tc_list_alloc(&T, blockIdx.x * 256 + threadIdx.x); }
+__global__ void __launch_bounds__(256) k_tc_list_scatter(RbtTransfer T) { tc_list_scatter(&T, blockIdx.x * 256 + threadIdx.x); }
+__global__ void __launch_bounds__(256) k_tc_result(RbtTransfer T) { if (tc_result(&T, blockIdx.x * 256 + threadIdx.x)) atomicAdd(&T.scal[RBT_TC_N_CHANGED], 1u); }
+
 void launch_up444(const uint16_t* yuv420, int w, int h, int bit_depth, int n_frames, int filter, uint16_t* yuv444) {
   if (n_frames <= 0) return;
   if (filter == RBT_UPSAMPLE_REPLICATE) hipLaunchKernelGGL(k_replicate, dim3((unsigned)((w * h + 255) / 256), 3u * (unsigned)n_frames), dim3(256), 0, g_stream, yuv420, yuv444, w, h);
@@ -64,5 +82,24 @@ void launch_col_insert(const RbtColSet* S, uint32_t* n_unique) { if (S->n > 0) h
 void launch_col_merge(const RbtColSet* S) { hipLaunchKernelGGL(k_col_merge, dim3((unsigned)(((1u << S->lg) + 255) / 256)), dim3(256), 0, g_stream, *S); }
 void launch_col_dist(const RbtColSet* P, const RbtColSet* Q, unsigned long long* sse) {
   hipLaunchKernelGGL(k_col_dist, dim3((unsigned)(((1u << P->lg) + 255) / 256)), dim3(256), 0, g_stream, *P, *Q, sse);
+}
+void launch_tc_copy(uint16_t* dst, const uint16_t* src, size_t n) { if (n) hipLaunchKernelGGL(k_tc_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, dst, src, n); }
+void launch_tc_flag(const RbtSmooth* G, const int16_t* xyz_before, const uint32_t* meta, uint8_t* moved) {
+  if (G->n_points > 0) hipLaunchKernelGGL(k_tc_flag, dim3((unsigned)((G->n_points + 255) / 256)), dim3(256), 0, g_stream, *G, xyz_before, meta, moved);
+}
+void launch_transfer(const RbtTransfer* T) {
+  if (T->cap <= 0 || T->ns <= 0 || T->nt <= 0) return;
+  const dim3 b(256), gs((unsigned)((T->ns + 255) / 256)), gh((unsigned)(((1u << T->slg) + 255) / 256)), gt((unsigned)((T->nt + 255) / 256)), gm((unsigned)((T->cap + 255) / 256)),
+             ge((unsigned)(((size_t)RBT_TC_K * T->cap + 255) / 256));
+  hipLaunchKernelGGL(k_tc_src_count, gs, b, 0, g_stream, *T);
+  hipLaunchKernelGGL(k_tc_src_alloc, gh, b, 0, g_stream, *T);
+  hipLaunchKernelGGL(k_tc_src_scatter, gs, b, 0, g_stream, *T);
+  hipLaunchKernelGGL(k_tc_src_sort, gh, b, 0, g_stream, *T);
+  hipLaunchKernelGGL(k_tc_tgt_insert, gt, b, 0, g_stream, *T);
+  hipLaunchKernelGGL(k_tc_forward, dim3((unsigned)((T->cap + 63) / 64)), dim3(64), 0, g_stream, *T);
+  hipLaunchKernelGGL(k_tc_backward, ge, b, 0, g_stream, *T);
+  hipLaunchKernelGGL(k_tc_list_alloc, gm, b, 0, g_stream, *T);
+  hipLaunchKernelGGL(k_tc_list_scatter, ge, b, 0, g_stream, *T);
+  hipLaunchKernelGGL(k_tc_result, gm, b, 0, g_stream, *T);
 }
 }  // namespace rbtk

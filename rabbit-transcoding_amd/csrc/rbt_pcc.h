@@ -253,13 +253,14 @@ RBT_DEV void pc_sm_accum(const RbtSmooth* G, const int16_t* xyz, const uint32_t*
   atomicAdd(&G->cnt[c], 1u); atomicMin(&G->pmin[c], pidx); atomicMax(&G->pmax[c], pidx);
 #endif
 }
-// gridFiltering + the decision of smoothPointCloudGrid for boundary point i: writes the new position and returns 1 when the point moves
-RBT_DEV int pc_sm_filter(const RbtSmooth* G, int16_t* xyz, const uint32_t* meta, int i) {
+// gridFiltering + the decision of smoothPointCloudGrid for a boundary point at `in` (meta as above): writes the new position to `out` (which may be `in`) and returns 1
+// when the point moves. It reads nothing of the cloud but the point itself, so it can be asked again about a position from before the pass (csrc/rbt_color.h tc_flag).
+RBT_DEV int pc_sm_filter_point(const RbtSmooth* G, const int16_t* in, uint32_t meta, int16_t* out) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-  if (!(meta[i] >> 31)) return 0;
-  const int P[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  if (!(meta >> 31)) return 0;
+  const int P[3] = {in[0], in[1], in[2]};
   if (pc_sm_skip(G, P[0], P[1], P[2])) return 0;
   const int g = G->g, w = G->w, half = g / 2, g2 = g * 2;
   int S[3], Wt[3]; size_t idx[8]; int other = 0;
@@ -289,7 +290,8 @@ RBT_DEV int pc_sm_filter(const RbtSmooth* G, int16_t* xyz, const uint32_t* meta,
   for (int k = 0; k < 3; k++) { centroid[k] = (c4[k] / vol) * (double)cnt; d[k] = cur[k] * (double)cnt - centroid[k]; }
   const double dist2 = (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) / (double)cnt + 0.5;
   if (!(dist2 >= (double)((G->threshold > cnt ? G->threshold : cnt) * 2))) return 0;
-  for (int k = 0; k < 3; k++) xyz[3 * i + k] = (int16_t)(double)(long long)(centroid[k] / (double)cnt + 0.5);
+  for (int k = 0; k < 3; k++) out[k] = (int16_t)(double)(long long)(centroid[k] / (double)cnt + 0.5);
   return 1;
 }
+RBT_DEV int pc_sm_filter(const RbtSmooth* G, int16_t* xyz, const uint32_t* meta, int i) { return pc_sm_filter_point(G, xyz + 3 * i, meta[i], xyz + 3 * i); }
 

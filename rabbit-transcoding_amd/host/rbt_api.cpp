@@ -9,7 +9,7 @@
 #include "rbt_pcc.h"
 #include "rbt_internal.h"
 
-struct rbt_ctx { int device, rank, world; rbt_stats stats; std::string last_err; double color_ms[3] = {0, 0, 0}; };
+struct rbt_ctx { int device, rank, world; rbt_stats stats; std::string last_err; double color_ms[4] = {0, 0, 0, 0}; int n_changed = 0; };
 struct rbt_job { rbt::GofJob* j; rbt_ctx* owner; };
 
 // Job slots, pipeline depth and the lock are per DEVICE (the 16 HIP streams a job's lanes map onto are the device's, rbt_kernels.hip):
@@ -297,6 +297,37 @@ int rbt_color_metric(rbt_ctx* ctx, const int16_t* xyz_a, const uint8_t* rgb_a, i
   if (!ctx || !xyz_a || !xyz_b || !out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   return rbt::pcc_color_metric(ctx->last_err, xyz_a, rgb_a, n_a, xyz_b, rgb_b, n_b, out, &ctx->color_ms[2]);
+} RBT_CATCH
+int rbt_reconstruct_decoded(rbt_ctx* ctx, const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const uint16_t* occ_luma, const uint16_t* geo_d0,
+                            const uint16_t* geo_d1, int geo_bit_depth, const uint16_t* attr_t0, const uint16_t* attr_t1, int attr_bit_depth, int upsample_filter, int attr_transfer,
+                            rbt_cloud* out, uint8_t** rgb, uint8_t** moved) {
+  if (!ctx || !atlas || (!patches && n_patches) || !occ_luma || !geo_d0 || !out || !rgb) return RBT_ERR_PARAM;
+  *rgb = nullptr; memset(out, 0, sizeof(*out)); if (moved) *moved = nullptr;
+  int rc;
+  try {
+    RBT_ENTER(ctx);
+    ctx->color_ms[3] = 0; ctx->n_changed = 0;
+    if (attr_transfer != 0 && attr_transfer != 1) { ctx->last_err = "attribute transfer filter types other than 1 are not built"; return RBT_ERR_UNSUPPORTED; }
+    rc = rbt::pcc_reconstruct_decoded(ctx->last_err, atlas, patches, n_patches, occ_luma, geo_d0, geo_d1, geo_bit_depth, attr_t0, attr_t1, attr_bit_depth, upsample_filter, attr_transfer, out, rgb, moved,
+                                      &ctx->n_changed, ctx->color_ms);
+  } catch (const std::bad_alloc&) { rc = RBT_ERR_NOMEM; } catch (...) { rc = RBT_ERR_NO_DEVICE; }
+  if (rc) { rbt_cloud_free(out); free(*rgb); *rgb = nullptr; if (moved) { free(*moved); *moved = nullptr; } }
+  return rc;
+}
+int rbt_transfer_colors(rbt_ctx* ctx, const int16_t* src_xyz, const uint16_t* src_yuv, int n_src, const int16_t* tgt_xyz, uint16_t* tgt_yuv, const uint8_t* moved, int n_tgt, int* n_changed) try {
+  if (!ctx || !src_xyz || !src_yuv || !n_changed || (n_tgt > 0 && (!tgt_xyz || !tgt_yuv || !moved))) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  ctx->color_ms[3] = 0; ctx->n_changed = 0;
+  const int rc = rbt::pcc_transfer_colors(ctx->last_err, src_xyz, src_yuv, n_src, tgt_xyz, tgt_yuv, moved, n_tgt, n_changed, &ctx->color_ms[3]);
+  if (!rc) ctx->n_changed = *n_changed;
+  return rc;
+} RBT_CATCH
+int rbt_transfer_stage(rbt_ctx* ctx, double* ms, int* n_changed) try {
+  if (!ctx) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  if (ms) *ms = ctx->color_ms[3];
+  if (n_changed) *n_changed = ctx->n_changed;
+  return RBT_OK;
 } RBT_CATCH
 int rbt_color_stage_ms(rbt_ctx* ctx, double ms[3]) try {
   if (!ctx || !ms) return RBT_ERR_PARAM;

@@ -26,15 +26,54 @@ int block_xy(const rbt_patch& p, int ub, int vb, int* x, int* y) {       // PCCP
   return 0;
 }
 // device timers of the colour stages (rbt_color_stage_ms), behind the transcoder's (rbt_batch.h)
-enum { T_COL_UP = T_COUNT, T_COL_RGB, T_COL_METRIC, T_COL_DIST };    // the metric in two parts: insert + merge, distance (a read-back of the merged counts lies between them)
-static_assert(T_COL_DIST < 16, "timer slots");
+enum { T_COL_UP = T_COUNT, T_COL_RGB, T_COL_METRIC, T_COL_DIST, T_COL_TRANSFER, T_COL_TRANSFER_COPY };    // the metric in two parts: insert + merge, distance (a read-back of the merged counts lies between them)
+static_assert(T_COL_TRANSFER_COPY < 16, "timer slots");
+int lg_of(int n) { int lg = 4; while (((size_t)1 << lg) < 2 * (size_t)n) lg++; return lg; }
+
+// Attribute transfer (csrc/rbt_color.h) on clouds that are on the device: source = the cloud before smoothing, target = the cloud after it, whose colours are updated in
+// place; n_moved = the number of set bytes in d_moved, > 0. flag_G / flag_meta (rbt_reconstruct_decoded): d_moved is still to be written, by the smoothing's filter asked
+// once more about the source positions - inside the timed region, it is work of this stage. The volumes and maps are cleared first; the events lie around the kernels only,
+// and the scalars are read back after the second event.
+int transfer_on_device(std::string& err, const int16_t* d_sxyz, const uint16_t* d_syuv, int ns, const int16_t* d_txyz, uint16_t* d_tyuv, uint8_t* d_moved, int nt, int n_moved,
+                       int* n_changed, const RbtSmooth* flag_G = nullptr, const uint32_t* flag_meta = nullptr) {
+  const size_t vol_bytes = (size_t)1 << (3 * RBT_PCC_BITS - 3), ne = (size_t)RBT_TC_K * n_moved;
+  const int slg = lg_of(ns), tlg = lg_of(nt);
+  const size_t sw = (size_t)4 << slg, tw = (size_t)4 << tlg;
+  DevBuf svol, tvol, shash, thash, sidx, per_t, mlist, c1, ent, lkey, lsrc, scal;
+  if (!svol.alloc(vol_bytes) || !tvol.alloc(vol_bytes) || !shash.alloc(4 * sw) || !thash.alloc(2 * tw) || !sidx.alloc(4 * (size_t)ns) || !per_t.alloc(12 * (size_t)nt) || !mlist.alloc(4 * (size_t)n_moved) ||
+      !c1.alloc(6 * (size_t)n_moved) || !ent.alloc(12 * ne) || !lkey.alloc(8 * ne) || !lsrc.alloc(4 * ne) || !scal.alloc(4 * RBT_TC_SCALARS)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  RbtTransfer T; memset(&T, 0, sizeof(T));
+  T.sxyz = d_sxyz; T.syuv = d_syuv; T.ns = ns; T.slg = slg; T.svol = svol.as<uint32_t>();
+  T.skeys = shash.as<uint32_t>(); T.scnt = T.skeys + ((size_t)1 << slg); T.sfill = T.scnt + ((size_t)1 << slg); T.sfirst = T.sfill + ((size_t)1 << slg); T.sidx = sidx.as<uint32_t>();
+  T.txyz = d_txyz; T.tyuv = d_tyuv; T.moved = d_moved; T.nt = nt; T.tlg = tlg; T.tvol = tvol.as<uint32_t>(); T.tkeys = thash.as<uint32_t>(); T.tvals = T.tkeys + ((size_t)1 << tlg);
+  T.mlist = mlist.as<uint32_t>(); T.cap = n_moved; T.color1 = c1.as<uint16_t>(); T.ent = ent.as<uint32_t>(); T.ev = T.ent + ne; T.ed = T.ev + ne;
+  T.lcnt = per_t.as<uint32_t>(); T.lfill = T.lcnt + nt; T.lfirst = T.lfill + nt; T.lkey = lkey.as<unsigned long long>(); T.lsrc = lsrc.as<uint32_t>(); T.scal = scal.as<uint32_t>();
+  if (rbtk::dev_memset(svol.p, 0, vol_bytes) | rbtk::dev_memset(tvol.p, 0, vol_bytes) | rbtk::dev_memset(shash.p, 0, 3 * sw) | rbtk::dev_memset(T.tkeys, 0, tw) | rbtk::dev_memset(T.tvals, 0xFF, tw) |
+      rbtk::dev_memset(per_t.p, 0, 8 * (size_t)nt) | rbtk::dev_memset(scal.p, 0, 4 * RBT_TC_SCALARS)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::timer_begin(T_COL_TRANSFER);
+  if (flag_G) rbtk::launch_tc_flag(flag_G, d_sxyz, flag_meta, d_moved);
+  rbtk::launch_transfer(&T);
+  rbtk::timer_end(T_COL_TRANSFER);
+  uint32_t h[RBT_TC_SCALARS];
+  if (rbtk::d2h(h, scal.p, sizeof(h)) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (h[RBT_TC_ERR] == RBT_TC_ERR_LIST) { err = "more than 1024 entries chose one moved point"; return RBT_ERR_UNSUPPORTED; }
+  if (h[RBT_TC_ERR] == RBT_TC_ERR_BUCKET) { err = "more than 256 coincident source points"; return RBT_ERR_UNSUPPORTED; }
+  if (h[RBT_TC_ERR] == RBT_TC_ERR_WALK) { err = "a moved point has fewer than 8 source points within 64 grid units"; return RBT_ERR_UNSUPPORTED; }
+  if (h[RBT_TC_ERR] == RBT_TC_ERR_RANGE) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
+  if (h[RBT_TC_ERR] || h[RBT_TC_N_MOVED] != (uint32_t)n_moved) { err = "attribute transfer: inconsistent input"; return RBT_ERR_PARAM; }
+  *n_changed = (int)h[RBT_TC_N_CHANGED];
+  return RBT_OK;
+}
 }  // namespace
 
 // rgb != nullptr: rbt_reconstruct_rgb - the attribute pictures are up-converted to 4:4:4 on the device first (csrc/rbt_color.h), the colour fetch reads the three planes at the
 // point's pixel (RbtPccParams.has_attr = 2) and the triples are converted to RGB8; stage_ms[0..1]: device time of the up-conversion and of the RGB conversion
 static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
-                            const uint16_t* t0, const uint16_t* t1, int attr_bd, rbt_cloud* out, int filter, uint8_t** rgb, double* stage_ms) {
+                            const uint16_t* t0, const uint16_t* t1, int attr_bd, rbt_cloud* out, int filter, uint8_t** rgb, double* stage_ms, int attr_transfer = 0, uint8_t** moved_out = nullptr,
+                            int* n_changed = nullptr) {
   memset(out, 0, sizeof(*out));
+  if (moved_out) *moved_out = nullptr;
+  if (n_changed) *n_changed = 0;
   if (rgb) {
     *rgb = nullptr;
     if (!t0 || (a->map_count > 1 && !t1) || (attr_bd != 8 && attr_bd != 10) || (filter != RBT_UPSAMPLE_F0 && filter != RBT_UPSAMPLE_REPLICATE)) { err = "attribute pictures of 8 or 10 bits and a known up-sampling filter are needed"; return RBT_ERR_PARAM; }
@@ -47,7 +86,7 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
   // an odd grid is refused (rbt.h: "2..255, even"): pc_sm_skip keeps a point whose coordinate is g * w - (g - 1) / 2 - 1, the remainder of that modulo g is g / 2, so its
   // lower cell is w - 1 and pc_sm_mark / pc_sm_filter would touch cell w, outside the w^3 arrays. With an even grid the last point kept has remainder g / 2 - 1: cell w - 2.
   if (a->geometry_smoothing && a->grid_size % 2) { err = "grid_size must be even"; return RBT_ERR_PARAM; }
-  const bool smooth = a->geometry_smoothing != 0;
+  const bool smooth = a->geometry_smoothing != 0, transfer = smooth && attr_transfer != 0, keep = transfer || (smooth && moved_out);   // keep: the cloud before smoothing stays
   RbtPccParams P; memset(&P, 0, sizeof(P));
   P.w = W; P.h = H; P.res = res; P.prec = prec; P.map_count = a->map_count; P.absolute_d1 = a->absolute_d1; P.remove_dup = a->remove_duplicate_points; P.threshold = a->threshold_lossy_om;
   P.geo_bd = geo_bd; P.attr_bd = attr_bd; P.bw = W / res; P.bh = H / res; P.ow = W / prec; P.n_patches = n_patches; P.has_attr = rgb ? 2 : t0 != nullptr;
@@ -65,7 +104,7 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
   }
   const int n_items = (int)items.size();
   const size_t ys = (size_t)W * H, os = (size_t)(W / prec) * (H / prec), fs = ys * 3 / 2;
-  DevBuf b_occ, b_d0, b_d1, b_t0, b_t1, b_patches, b_items, b_b2p, b_counts, b_off, b_om, b_xyz, b_yuv, b_meta, b_cells, b_scal, b_420, b_rgb;
+  DevBuf b_occ, b_d0, b_d1, b_t0, b_t1, b_patches, b_items, b_b2p, b_counts, b_off, b_om, b_xyz, b_yuv, b_meta, b_cells, b_scal, b_420, b_rgb, b_xyz0, b_yuv0, b_moved;
   if (!b_occ.alloc(os * 2) || !b_d0.alloc(ys * 2) || !b_d1.alloc(ys * 2) || !b_patches.alloc(sizeof(rbt_patch) * (size_t)(n_patches ? n_patches : 1)) || !b_items.alloc(4 * (size_t)(n_items ? n_items : 1)) ||
       !b_b2p.alloc(4 * (size_t)P.bw * P.bh) || !b_counts.alloc(4 * (size_t)(n_items + 1)) || !b_off.alloc(4 * (size_t)(n_items + 1)) || !b_om.alloc(ys) ||
       (t0 && !rgb && (!b_t0.alloc(fs * 2) || !b_t1.alloc(fs * 2))) || (rgb && (!b_420.alloc(fs * 4) || !b_t0.alloc(ys * 12)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
@@ -91,6 +130,13 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
   rbtk::launch_pcc_emit(&P, b_patches.as<rbt_patch>(), b_items.as<uint32_t>(), n_items, b_occ.as<uint16_t>(), b_d0.as<uint16_t>(), b_d1.as<uint16_t>(), p_t0, p_t1,
                         b_b2p.as<uint32_t>(), b_off.as<uint32_t>(), b_xyz.as<int16_t>(), b_yuv.as<uint16_t>(), smooth ? b_om.as<uint8_t>() : nullptr, smooth ? b_meta.as<uint32_t>() : nullptr);
   out->n_points = (int)total;
+  if (keep && total) {              // rbt_reconstruct_decoded: the cloud before smoothing stays on the device as the source of the attribute transfer
+    if (!b_xyz0.alloc(6 * (size_t)total) || !b_yuv0.alloc(6 * (size_t)total) || !b_moved.alloc(total)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    rbtk::timer_begin(T_COL_TRANSFER_COPY);
+    rbtk::launch_tc_copy(b_xyz0.as<uint16_t>(), b_xyz.as<uint16_t>(), 3 * (size_t)total); rbtk::launch_tc_copy(b_yuv0.as<uint16_t>(), b_yuv.as<uint16_t>(), 3 * (size_t)total);
+    rbtk::timer_end(T_COL_TRANSFER_COPY);
+    if (rbtk::dev_memset(b_moved.p, 0, total)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  }
   // geometry smoothing (PCCCodec::smoothPointCloudPostprocess with gridSmoothing, PCCCodec.cpp:52-145): the grid spans the largest coordinate of the cloud (:70-83)
   if (smooth && total) {
     uint32_t* scal = b_scal.as<uint32_t>();                        // [0] largest coordinate, [1] points moved
@@ -107,9 +153,18 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
       G.flag = base; G.sum = (uint32_t*)(base + o_sum); G.cnt = (uint32_t*)(base + o_cnt); G.pmin = (uint32_t*)(base + o_min); G.pmax = (uint32_t*)(base + o_max); G.moved = scal + 1;
       if (rbtk::dev_memset(base, 0, bytes) || rbtk::dev_memset(G.pmin, 0xFF, 4 * w3)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
       rbtk::launch_sm_passes(&G, b_xyz.as<int16_t>(), b_meta.as<uint32_t>());
-      uint32_t moved = 0;
-      if (rbtk::d2h(&moved, scal + 1, 4)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-      out->n_smoothed = (int)moved;
+      uint32_t moved[16];
+      if (rbtk::d2h(moved, scal, 64)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+      out->n_smoothed = (int)moved[1];
+      if (transfer && moved[1]) {   // the flags are written inside the stage (and its events); a coordinate outside the 1024^3 volumes comes back as RBT_ERR_PARAM
+        if (total < RBT_TC_K) { err = "fewer than 8 points"; return RBT_ERR_PARAM; }
+        int changed = 0;
+        const int rc = transfer_on_device(err, b_xyz0.as<int16_t>(), b_yuv0.as<uint16_t>(), (int)total, b_xyz.as<int16_t>(), b_yuv.as<uint16_t>(), b_moved.as<uint8_t>(), (int)total, (int)moved[1], &changed,
+                                          &G, b_meta.as<uint32_t>());
+        if (rc) return rc;
+        if (n_changed) *n_changed = changed;
+        if (stage_ms) stage_ms[3] = rbtk::timer_ms(T_COL_TRANSFER) + rbtk::timer_ms(T_COL_TRANSFER_COPY);
+      } else if (keep) rbtk::launch_tc_flag(&G, b_xyz0.as<int16_t>(), b_meta.as<uint32_t>(), b_moved.as<uint8_t>());
     }
   }
   out->xyz = (int16_t*)malloc(6 * (size_t)(total ? total : 1)); out->yuv = (uint16_t*)malloc(6 * (size_t)(total ? total : 1));
@@ -117,6 +172,11 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
   if (!out->xyz || !out->yuv || !out->occupancy_map || !out->block_to_patch) { err = "out of memory"; return RBT_ERR_NOMEM; }
   bad = rbtk::d2h(out->occupancy_map, b_om.p, ys) | rbtk::d2h(out->block_to_patch, b_b2p.p, 4 * (size_t)P.bw * P.bh);
   if (total) bad |= rbtk::d2h(out->xyz, b_xyz.p, 6 * (size_t)total) | rbtk::d2h(out->yuv, b_yuv.p, 6 * (size_t)total);
+  if (moved_out) {
+    *moved_out = (uint8_t*)calloc(total ? total : 1, 1);
+    if (!*moved_out) { err = "out of memory"; return RBT_ERR_NOMEM; }
+    if (b_moved.p && total) bad |= rbtk::d2h(*moved_out, b_moved.p, total);
+  }
   if (rgb) {
     *rgb = (uint8_t*)malloc(3 * (size_t)(total ? total : 1));
     if (!*rgb) { err = "out of memory"; return RBT_ERR_NOMEM; }
@@ -135,6 +195,31 @@ int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch
 int pcc_reconstruct_rgb(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
                         const uint16_t* t0, const uint16_t* t1, int attr_bd, int filter, rbt_cloud* out, uint8_t** rgb, double* stage_ms) {
   return reconstruct_impl(err, a, patches, n_patches, occ, d0, d1, geo_bd, t0, t1, attr_bd, out, filter, rgb, stage_ms);
+}
+
+int pcc_reconstruct_decoded(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
+                            const uint16_t* t0, const uint16_t* t1, int attr_bd, int filter, int attr_transfer, rbt_cloud* out, uint8_t** rgb, uint8_t** moved, int* n_changed, double* stage_ms) {
+  return reconstruct_impl(err, a, patches, n_patches, occ, d0, d1, geo_bd, t0, t1, attr_bd, out, filter, rgb, stage_ms, attr_transfer, moved, n_changed);
+}
+
+// the stage on its own (rbt_transfer_colors): host clouds in, the target's colours updated in place
+int pcc_transfer_colors(std::string& err, const int16_t* sxyz, const uint16_t* syuv, int ns, const int16_t* txyz, uint16_t* tyuv, const uint8_t* moved, int nt, int* n_changed, double* ms) {
+  *n_changed = 0;
+  if (ns < RBT_TC_K || nt < 0 || ns > (1 << 26) || nt > (1 << 26)) { err = "at least 8 source points (and at most 2^26 points a cloud) are needed"; return RBT_ERR_PARAM; }
+  for (size_t i = 0; i < 3 * (size_t)ns; i++) if (sxyz[i] < 0 || sxyz[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
+  for (size_t i = 0; i < 3 * (size_t)nt; i++) if (txyz[i] < 0 || txyz[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
+  std::vector<uint8_t> flag((size_t)nt); int n_moved = 0;
+  for (int i = 0; i < nt; i++) { flag[i] = moved[i] != 0; n_moved += flag[i]; }
+  if (!n_moved) return RBT_OK;
+  DevBuf b_sx, b_sc, b_tx, b_tc, b_m;
+  if (!b_sx.alloc(6 * (size_t)ns) || !b_sc.alloc(6 * (size_t)ns) || !b_tx.alloc(6 * (size_t)nt) || !b_tc.alloc(6 * (size_t)nt) || !b_m.alloc((size_t)nt)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::h2d(b_sx.p, sxyz, 6 * (size_t)ns) | rbtk::h2d(b_sc.p, syuv, 6 * (size_t)ns) | rbtk::h2d(b_tx.p, txyz, 6 * (size_t)nt) | rbtk::h2d(b_tc.p, tyuv, 6 * (size_t)nt) | rbtk::h2d(b_m.p, flag.data(), (size_t)nt)) {
+    err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  const int rc = transfer_on_device(err, b_sx.as<int16_t>(), b_sc.as<uint16_t>(), ns, b_tx.as<int16_t>(), b_tc.as<uint16_t>(), b_m.as<uint8_t>(), nt, n_moved, n_changed);
+  if (rc) return rc;
+  if (rbtk::d2h(tyuv, b_tc.p, 6 * (size_t)nt) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (ms) *ms = rbtk::timer_ms(T_COL_TRANSFER);
+  return RBT_OK;
 }
 
 int pcc_yuv420_to_yuv444(std::string& err, const uint16_t* in, int w, int h, int bd, int n_frames, int filter, uint16_t* out, double* ms) {

@@ -8,6 +8,10 @@ int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch
 // colour stages (csrc/rbt_color.h); ms / stage_ms: device time of the stage's launches, may be null
 int pcc_reconstruct_rgb(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
                         const uint16_t* t0, const uint16_t* t1, int attr_bd, int filter, rbt_cloud* out, uint8_t** rgb, double* stage_ms);
+// rbt_reconstruct_decoded: pcc_reconstruct_rgb + the attribute transfer after geometry smoothing; stage_ms[3]: device time of the transfer's kernels
+int pcc_reconstruct_decoded(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
+                            const uint16_t* t0, const uint16_t* t1, int attr_bd, int filter, int attr_transfer, rbt_cloud* out, uint8_t** rgb, uint8_t** moved, int* n_changed, double* stage_ms);
+int pcc_transfer_colors(std::string& err, const int16_t* sxyz, const uint16_t* syuv, int ns, const int16_t* txyz, uint16_t* tyuv, const uint8_t* moved, int nt, int* n_changed, double* ms);
 int pcc_yuv420_to_yuv444(std::string& err, const uint16_t* in, int w, int h, int bd, int n_frames, int filter, uint16_t* out, double* ms);
 int pcc_yuv16_to_rgb8(std::string& err, const uint16_t* yuv, int n, uint8_t* rgb, double* ms);
 int pcc_color_metric(std::string& err, const int16_t* a, const uint8_t* rgb_a, int na, const int16_t* b, const uint8_t* rgb_b, int nb, rbt_color_result* out, double* ms);
