@@ -367,6 +367,55 @@ int rbt_reconstruct_decoded(rbt_ctx* ctx, const rbt_atlas_params* atlas, const r
  * rbt_transfer_colors or rbt_reconstruct_decoded; 0 when that call had nothing to transfer. Either pointer may be NULL. */
 int rbt_transfer_stage(rbt_ctx* ctx, double* ms, int* n_changed);
 
+/* ---- frame scoring on clouds that stay on the device (csrc/rbt_score.h) ----
+ * rbt_d1, rbt_d2 and rbt_color_metric each upload both clouds, build their own index and search on their own. Here a cloud is uploaded (or reconstructed) once and
+ * indexed once - bit volume, a coarse level over it, one map voxel -> lowest point index + merged colour - and rbt_score runs one nearest-distance search per direction
+ * that feeds all three metrics. The definitions do not change: out->d1 is what rbt_d1(a, b, peak) returns, out->color what rbt_color_metric(a, b) returns and out->d2
+ * what rbt_d2(a, normals_a, b, peak) returns (same merged points and representatives, same tie sets - all points at exactly the nearest squared distance -, same give /
+ * take rule for the decoded cloud's normals), with one exception, the order of the two D2 sums:
+ *   rbt_d2 adds its per-point values with floating-point atomics, in order of arrival. rbt_score stores the value v[i] of every point i (0 for a point that is not the
+ *   lowest-index point of its voxel) and adds them in an order that depends on the input alone. Block b holds s[t] = v[256 b + t], t = 0..255 (0 past the last point) and
+ *   is folded by s[t] = s[t] + s[t + h] for all t < h, h = 128, 64, .. 1; its sum is s[0]. Then S[t] = the sums of blocks t, t + 256, t + 512, .. added in ascending
+ *   order starting from 0, t = 0..255, and S is folded the same way; sse = S[0]. Every operation is a double addition rounded on its own. Two calls therefore return the
+ *   same bits, and so does the serial host emulation of the kernels. sse_* may differ from rbt_d2's in the last bits (relative 1e-9 at most for these sizes); max_* and the
+ *   counts are exact.
+ * A handle belongs to the context that made it: used with another context it is refused (RBT_ERR_PARAM); rbt_destroy releases the handles still outstanding.
+ * Limits: 1 .. 2^26 points a cloud, coordinates 0..1023 (a coordinate outside is RBT_ERR_PARAM: a kernel checks them and reports through an error word before any
+ * word of the volume is touched). The colour part needs at most 2^21 merged points in each cloud (rbt_color_metric's limit: its integer sums are exact up to there); larger
+ * clouds do not allow it, as clouds without colours do not. A handle holds a 128 MB volume; the volume of a released cloud is
+ * cleaned (the cloud's own words) and kept by the context for its next cloud: rbt_device_memory counts such volumes as cached, rbt_trim hands them back. */
+typedef struct rbt_pcloud rbt_pcloud;
+/* xyz: 3 per point; rgb (3 bytes per point) and normals_q14 (3 per point, 16384 = 1.0) may be NULL: the colour part needs colours on both clouds, D2 normals on the source */
+int rbt_pcloud_upload(rbt_ctx* ctx, const int16_t* xyz, const uint8_t* rgb, const int16_t* normals_q14, int n, rbt_pcloud** out);
+/* rbt_reconstruct_decoded whose result stays on the device: positions after smoothing, the transferred 4:4:4 triples and their RGB8 triples are kept and indexed (no normals).
+ * Arguments, limits and error codes are rbt_reconstruct_decoded's; in addition an empty cloud or a coordinate outside 0..1023 is RBT_ERR_PARAM. host_copy and rgb may be
+ * NULL; given, they receive exactly what rbt_reconstruct_decoded returns (rbt_cloud_free / rbt_free). rbt_transfer_stage reports on the transfer as after
+ * rbt_reconstruct_decoded. */
+int rbt_pcloud_from_maps(rbt_ctx* ctx, const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const uint16_t* occ_luma, const uint16_t* geo_d0,
+                         const uint16_t* geo_d1, int geo_bit_depth, const uint16_t* attr_t0, const uint16_t* attr_t1, int attr_bit_depth, int upsample_filter, int attr_transfer,
+                         rbt_pcloud** out, rbt_cloud* host_copy, uint8_t** rgb);
+int rbt_pcloud_points(const rbt_pcloud* cloud, int* n_points, int* n_merged);
+void rbt_pcloud_release(rbt_ctx* ctx, rbt_pcloud* cloud);
+enum { RBT_SCORE_D1 = 1, RBT_SCORE_D2 = 2, RBT_SCORE_COLOR = 4 };
+typedef struct {
+  int parts;                             /* RBT_SCORE_* computed; the results of the other parts are zero */
+  rbt_d1_result d1; rbt_d2_result d2; rbt_color_result color;
+  double device_ms;                      /* device time between events around the score's kernels (searches, walks, sums); index building, clears and read-back are outside */
+  int n_points_a, n_points_b, n_merged_a, n_merged_b;
+} rbt_frame_score;
+/* a: the source (D2 needs its normals), b: the decoded cloud. parts: RBT_SCORE_* wanted, 0 = all the two clouds allow (out->parts says which); a part the clouds cannot
+ * give, or peak < 1, is RBT_ERR_PARAM. */
+int rbt_score(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int parts, rbt_frame_score* out);
+/* Summary over the frames of a sequence, per figure (the symmetric PSNR of D1, D2, Y, U, V): arithmetic mean and minimum, in double, over the frames that carry that part
+ * (n_d1 / n_d2 / n_color of them; 0 where there is none); a frame whose PSNR is +inf makes the mean +inf. The reference itself writes one line per frame and averages
+ * nothing (PCCMetrics::write); the mean over the frames is what the CTC reporting forms from those lines. points_* / merged_*: sums over all frames. Host only. */
+typedef struct {
+  int n_frames, n_d1, n_d2, n_color;
+  double mean_d1, min_d1, mean_d2, min_d2, mean_color[3], min_color[3];
+  int64_t points_a, points_b, merged_a, merged_b;
+} rbt_sequence_score;
+int rbt_score_summary(const rbt_frame_score* frames, int n_frames, rbt_sequence_score* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,21 @@ class ColorResult(C.Structure):
                [(n, C.c_float * 3) for n in ("mse_ab", "mse_ba", "psnr_ab", "psnr_ba", "mse", "psnr")]
 
 
+RBT_SCORE_D1, RBT_SCORE_D2, RBT_SCORE_COLOR = 1, 2, 4
+
+
+class FrameScore(C.Structure):
+    """rbt_frame_score: what rbt_score returns for one pair of clouds"""
+    _fields_ = [("parts", C.c_int), ("d1", D1Result), ("d2", D2Result), ("color", ColorResult), ("device_ms", C.c_double)] + \
+               [(n, C.c_int) for n in ("n_points_a", "n_points_b", "n_merged_a", "n_merged_b")]
+
+
+class SequenceScore(C.Structure):
+    """rbt_sequence_score: mean and minimum of the per-frame symmetric PSNRs"""
+    _fields_ = [(n, C.c_int) for n in ("n_frames", "n_d1", "n_d2", "n_color")] + [(n, C.c_double) for n in ("mean_d1", "min_d1", "mean_d2", "min_d2")] + \
+               [("mean_color", C.c_double * 3), ("min_color", C.c_double * 3)] + [(n, C.c_int64) for n in ("points_a", "points_b", "merged_a", "merged_b")]
+
+
 RBT_UPSAMPLE_REPLICATE, RBT_UPSAMPLE_F0 = -1, 0   # rbt_yuv420_to_yuv444 / rbt_reconstruct_rgb: sample replication / g_filter420to444[0], the decoder's default
 
 
@@ -150,6 +165,14 @@ def load(path=None):
     L.rbt_reconstruct_decoded.argtypes = [C.c_void_p, C.POINTER(AtlasParams), C.POINTER(Patch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(Cloud), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.rbt_transfer_stage.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    L.rbt_pcloud_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.rbt_pcloud_from_maps.argtypes = [C.c_void_p, C.POINTER(AtlasParams), C.POINTER(Patch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_void_p), C.POINTER(Cloud), C.POINTER(C.c_void_p)]
+    L.rbt_pcloud_points.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.rbt_pcloud_release.argtypes = [C.c_void_p, C.c_void_p]
+    L.rbt_pcloud_release.restype = None
+    L.rbt_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(FrameScore)]
+    L.rbt_score_summary.argtypes = [C.POINTER(FrameScore), C.c_int, C.POINTER(SequenceScore)]
     L.rbt_v3c_index.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(V3CUnit)), C.POINTER(C.c_int)]
     L.rbt_v3c_write.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_v3c_stats.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(V3CStat)]
@@ -239,6 +262,47 @@ def v3c_write(units, forced_precision_bytes=0, lib=None):
     res = C.string_at(out, n.value)
     L.rbt_free(out)
     return res
+
+
+def _result_dict(r):
+    return {n: (list(v) if isinstance(v, C.Array) else v) for n, v in ((n, getattr(r, n)) for n, _ in r._fields_)}
+
+
+def frame_score_dict(s):
+    """a FrameScore as nested dicts: parts, device_ms, the point counts, and d1 / d2 / color as Context.d1 / d2 / color_metric return them (None for a part not computed)"""
+    out = {n: getattr(s, n) for n in ("parts", "device_ms", "n_points_a", "n_points_b", "n_merged_a", "n_merged_b")}
+    for name, bit in (("d1", RBT_SCORE_D1), ("d2", RBT_SCORE_D2), ("color", RBT_SCORE_COLOR)):
+        out[name] = _result_dict(getattr(s, name)) if s.parts & bit else None
+    return out
+
+
+def score_summary(frames, lib=None):
+    """rbt_score_summary: a list of FrameScore (Context.score(..., raw=True)) -> dict of the sequence's means, minima and counts (host only)"""
+    L = lib or load()
+    arr = (FrameScore * max(1, len(frames)))(*frames)
+    out = SequenceScore()
+    rc = L.rbt_score_summary(arr, len(frames), C.byref(out))
+    if rc != 0:
+        raise RbtError(rc, L.rbt_strerror(rc).decode())
+    return _result_dict(out)
+
+
+class PCloud:
+    """rbt_pcloud: a point cloud on the device with its index; belongs to the context that made it. release() hands it back (its clean volume stays cached in the context)."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def points(self):
+        """(points, merged points)"""
+        n, m = C.c_int(), C.c_int()
+        self.ctx._chk(self.ctx.L.rbt_pcloud_points(self.h, C.byref(n), C.byref(m)))
+        return n.value, m.value
+
+    def release(self):
+        if self.h:
+            self.ctx.L.rbt_pcloud_release(self.ctx.h, self.h)
+            self.h = C.c_void_p()
 
 
 class Context:
@@ -490,6 +554,43 @@ class Context:
         ch = C.c_int(); self._chk(self.L.rbt_transfer_stage(self.h, None, C.byref(ch))); self.n_changed = ch.value
         self.L.rbt_free(rgb_p); self.L.rbt_free(mv_p); self.L.rbt_cloud_free(C.byref(c))
         return xyz, yuv, om, b2p, rgb, moved
+
+    def pcloud_upload(self, xyz, rgb=None, normals=None):
+        """rbt_pcloud_upload: xyz int16 [n,3], rgb uint8 [n,3] or None, normals int16 [n,3] in Q14 or None -> PCloud"""
+        a = np.ascontiguousarray(xyz, dtype=np.int16).reshape(-1, 3)
+        c = None if rgb is None else np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3); nr = None if normals is None else np.ascontiguousarray(normals, dtype=np.int16).reshape(-1, 3)
+        if (c is not None and c.shape != a.shape) or (nr is not None and nr.shape != a.shape):
+            raise ValueError("one colour and one normal per point")
+        h = C.c_void_p()
+        self._chk(self.L.rbt_pcloud_upload(self.h, a.ctypes.data, None if c is None else c.ctypes.data, None if nr is None else nr.ctypes.data, a.shape[0], C.byref(h)))
+        return PCloud(self, h)
+
+    def pcloud_from_maps(self, atlas, patches, occ, d0, d1, geo_bd=10, t0=None, t1=None, attr_bd=10, upsample_filter=RBT_UPSAMPLE_F0, attr_transfer=1, host_copy=False):
+        """rbt_pcloud_from_maps: reconstruct_decoded whose cloud stays on the device -> PCloud, or with host_copy (PCloud, (xyz, yuv, occupancy_map, block_to_patch, rgb));
+        self.n_smoothed / self.n_changed as after reconstruct_decoded"""
+        ps = (Patch * max(1, len(patches)))(*patches)
+        arr = [np.ascontiguousarray(x, dtype=np.uint16) if x is not None else None for x in (occ, d0, d1, t0, t1)]
+        ptr = [x.ctypes.data if x is not None else None for x in arr]
+        h, c, rgb_p = C.c_void_p(), Cloud(), C.c_void_p()
+        self._chk(self.L.rbt_pcloud_from_maps(self.h, C.byref(atlas), ps, len(patches), ptr[0], ptr[1], ptr[2], geo_bd, ptr[3], ptr[4], attr_bd, upsample_filter, attr_transfer, C.byref(h),
+                                              C.byref(c) if host_copy else None, C.byref(rgb_p) if host_copy else None))
+        ch = C.c_int(); self._chk(self.L.rbt_transfer_stage(self.h, None, C.byref(ch))); self.n_changed = ch.value
+        cloud = PCloud(self, h)
+        if not host_copy:
+            return cloud
+        n, w, hh, res = c.n_points, atlas.width, atlas.height, atlas.occupancy_resolution
+        xyz = np.ctypeslib.as_array(c.xyz, shape=(max(n, 1), 3))[:n].copy(); yuv = np.ctypeslib.as_array(c.yuv, shape=(max(n, 1), 3))[:n].copy()
+        om = np.ctypeslib.as_array(c.occupancy_map, shape=(hh, w)).copy(); b2p = np.ctypeslib.as_array(c.block_to_patch, shape=(hh // res, w // res)).copy()
+        rgb = np.frombuffer(C.string_at(rgb_p, 3 * n), np.uint8).reshape(n, 3).copy()
+        self.n_smoothed = c.n_points and c.n_smoothed
+        self.L.rbt_free(rgb_p); self.L.rbt_cloud_free(C.byref(c))
+        return cloud, (xyz, yuv, om, b2p, rgb)
+
+    def score(self, a, b, peak=1023, parts=0, raw=False):
+        """rbt_score: a = the source PCloud, b = the decoded one; parts = RBT_SCORE_* wanted, 0 = all the clouds allow -> frame_score_dict, or the FrameScore itself (raw)"""
+        s = FrameScore()
+        self._chk(self.L.rbt_score(self.h, a.h if a is not None else None, b.h if b is not None else None, peak, parts, C.byref(s)))
+        return s if raw else frame_score_dict(s)
 
     def selftest_transform32(self, blocks, bit_depth=10):
         """rbt_selftest_transform32: matrix-core vs vector-ALU 32-point transforms on int16 blocks [n, 1024]; returns the number of differing samples"""

@@ -3,6 +3,7 @@
 // does, so that their output is the same bits everywhere. No __fmul_rn / __fadd_rn is needed on top of that; the bodies also carry `#pragma clang fp contract(off)`.
 #include <hip/hip_runtime.h>
 #include "rbt_color.h"
+#include "rbt_score.h"
 
 namespace rbtk {
 hipStream_t current_stream();            // rbt_kernels.hip: the stream the host code selected (set_stream)
@@ -71,6 +72,56 @@ __global__ void __launch_bounds__(256) k_tc_list_alloc(RbtTransfer T) { tc_list_
 __global__ void __launch_bounds__(256) k_tc_list_scatter(RbtTransfer T) { tc_list_scatter(&T, blockIdx.x * 256 + threadIdx.x); }
 __global__ void __launch_bounds__(256) k_tc_result(RbtTransfer T) { if (tc_result(&T, blockIdx.x * 256 + threadIdx.x)) atomicAdd(&T.scal[RBT_TC_N_CHANGED], 1u); }
 
+// ---- frame scoring on device clouds (rbt_score.h) ----
+__device__ __forceinline__ uint32_t sc_block_max(uint32_t v, uint32_t* part) {     // as col_block_sum
+  for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o); v = w > v ? w : v; }
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const uint32_t a = part[0] > part[1] ? part[0] : part[1], b = part[2] > part[3] ? part[2] : part[3];
+  return a > b ? a : b;
+}
+__global__ void __launch_bounds__(256) k_sc_check(const int16_t* xyz, int n, uint32_t* scal) {
+  __shared__ unsigned long long part[4];
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  const unsigned long long bad = col_block_sum(i < n && !tc_in_range(xyz + 3 * (size_t)i) ? 1ull : 0ull, part);
+  if (threadIdx.x == 0 && bad) atomicOr(&scal[RBT_SC_ERR], 1u);
+}
+__global__ void __launch_bounds__(256) k_sc_insert(RbtScoreCloud S, uint32_t* scal) {
+  __shared__ unsigned long long part[4];
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  const unsigned long long n = col_block_sum(i < S.n ? (unsigned long long)sc_insert(&S, i) : 0ull, part);
+  if (threadIdx.x == 0 && n) atomicAdd(&scal[RBT_SC_N_MERGED], (uint32_t)n);
+}
+__global__ void __launch_bounds__(256) k_sc_merge(RbtScoreCloud S) { const uint32_t s = blockIdx.x * 256 + threadIdx.x; if (s < (1u << S.lg)) sc_merge(&S, s); }
+__global__ void __launch_bounds__(256) k_sc_clear(RbtScoreCloud S) { const int i = (int)(blockIdx.x * 256 + threadIdx.x); if (i < S.n) sc_clear(&S, i); }
+// 64 lanes per workgroup, as k_tc_forward: the searches of a wave's points differ in length
+__global__ void __launch_bounds__(64) k_sc_search(RbtScoreCloud P, RbtScoreCloud Q, uint32_t* dist) { const int i = (int)(blockIdx.x * 64 + threadIdx.x); if (i < P.n) sc_search(&P, &Q, dist, i); }
+// dir 0: A -> B, 1: B -> A (P is the walking cloud). Integer sums: reduced in the workgroup, then one atomic per workgroup and sum
+__global__ void __launch_bounds__(256) k_sc_walk(RbtScoreCloud A, RbtScoreCloud B, RbtScoreWork W, int parts, int dir) {
+  __shared__ unsigned long long part[4][4]; __shared__ uint32_t pmax[4];
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  uint32_t d = 0; long long e[3] = {0, 0, 0};
+  if (i < (dir ? B.n : A.n)) { if (dir) sc_walk_ba(&B, &A, &W, parts, i, &d, e); else sc_walk_ab(&A, &B, &W, parts, i, &d, e); }
+  const unsigned long long sd = col_block_sum(d, part[3]);
+  if (threadIdx.x == 0 && sd) atomicAdd(&W.res[RBT_SC_D1_AB + dir], sd);
+  const uint32_t md = sc_block_max(d, pmax);
+  if (threadIdx.x == 0 && md) atomicMax((uint32_t*)&W.res[RBT_SC_D1_MAX] + dir, md);
+  if (parts & RBT_SCORE_COLOR)
+    for (int c = 0; c < 3; c++) {
+      const unsigned long long t = col_block_sum((unsigned long long)(e[c] * e[c]), part[c]);
+      if (threadIdx.x == 0 && t) atomicAdd(&W.res[(dir ? RBT_SC_COL_BA : RBT_SC_COL_AB) + c], t);
+    }
+}
+__global__ void __launch_bounds__(256) k_sc_d2_ab(RbtScoreCloud A, RbtScoreCloud B, RbtScoreWork W) { const int i = (int)(blockIdx.x * 256 + threadIdx.x); if (i < A.n) sc_d2_ab(&A, &B, &W, i); }
+__global__ void __launch_bounds__(RBT_SC_SUM) k_sc_sum_block(const double* val, int n, double* part) {
+  __shared__ RbtScoreSumLds lds;
+  sc_sum_block(val, n, (int)blockIdx.x, part, RBT_LDS_CAST(RbtScoreSumLds, &lds));
+}
+__global__ void __launch_bounds__(RBT_SC_SUM) k_sc_sum_final(const double* part, int n_blocks, double* out) {
+  __shared__ RbtScoreSumLds lds;
+  sc_sum_final(part, n_blocks, out, RBT_LDS_CAST(RbtScoreSumLds, &lds));
+}
+
 void launch_up444(const uint16_t* yuv420, int w, int h, int bit_depth, int n_frames, int filter, uint16_t* yuv444) {
   if (n_frames <= 0) return;
   if (filter == RBT_UPSAMPLE_REPLICATE) hipLaunchKernelGGL(k_replicate, dim3((unsigned)((w * h + 255) / 256), 3u * (unsigned)n_frames), dim3(256), 0, g_stream, yuv420, yuv444, w, h);
@@ -101,5 +152,27 @@ void launch_transfer(const RbtTransfer* T) {
   hipLaunchKernelGGL(k_tc_list_alloc, gm, b, 0, g_stream, *T);
   hipLaunchKernelGGL(k_tc_list_scatter, ge, b, 0, g_stream, *T);
   hipLaunchKernelGGL(k_tc_result, gm, b, 0, g_stream, *T);
+}
+void launch_sc_check(const int16_t* xyz, int n, uint32_t* scal) { if (n > 0) hipLaunchKernelGGL(k_sc_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, xyz, n, scal); }
+void launch_sc_index(const RbtScoreCloud* S, uint32_t* scal) {
+  if (S->n <= 0) return;
+  hipLaunchKernelGGL(k_sc_insert, dim3((unsigned)((S->n + 255) / 256)), dim3(256), 0, g_stream, *S, scal);
+  if (S->rgb) hipLaunchKernelGGL(k_sc_merge, dim3((unsigned)(((1u << S->lg) + 255) / 256)), dim3(256), 0, g_stream, *S);
+}
+void launch_sc_clear(const RbtScoreCloud* S) { if (S->n > 0) hipLaunchKernelGGL(k_sc_clear, dim3((unsigned)((S->n + 255) / 256)), dim3(256), 0, g_stream, *S); }
+void launch_sc_score(const RbtScoreCloud* A, const RbtScoreCloud* B, int parts, const RbtScoreWork* W) {
+  if (A->n <= 0 || B->n <= 0) return;
+  const dim3 b(256), ga((unsigned)((A->n + 255) / 256)), gb((unsigned)((B->n + 255) / 256));
+  hipLaunchKernelGGL(k_sc_search, dim3((unsigned)((A->n + 63) / 64)), dim3(64), 0, g_stream, *A, *B, W->dist_a);
+  hipLaunchKernelGGL(k_sc_search, dim3((unsigned)((B->n + 63) / 64)), dim3(64), 0, g_stream, *B, *A, W->dist_b);
+  hipLaunchKernelGGL(k_sc_walk, ga, b, 0, g_stream, *A, *B, *W, parts, 0);
+  hipLaunchKernelGGL(k_sc_walk, gb, b, 0, g_stream, *A, *B, *W, parts, 1);
+  if (!(parts & RBT_SCORE_D2)) return;
+  hipLaunchKernelGGL(k_sc_d2_ab, ga, b, 0, g_stream, *A, *B, *W);
+  for (int dir = 0; dir < 2; dir++) {
+    const int n = dir ? B->n : A->n, nb = (n + RBT_SC_SUM - 1) / RBT_SC_SUM;
+    hipLaunchKernelGGL(k_sc_sum_block, dim3((unsigned)nb), dim3(RBT_SC_SUM), 0, g_stream, dir ? W->val_ba : W->val_ab, n, W->part);
+    hipLaunchKernelGGL(k_sc_sum_final, dim3(1), dim3(RBT_SC_SUM), 0, g_stream, W->part, nb, (double*)&W->res[dir ? RBT_SC_D2_BA : RBT_SC_D2_AB]);
+  }
 }
 }  // namespace rbtk

@@ -1,0 +1,284 @@
+// Frame scoring on clouds that stay on the device (rbt_pcloud_*, rbt_score; the definitions are in include/rbt.h): D1, D2 and the colour PSNR from ONE index per cloud
+// and ONE nearest-distance search per direction, where rbt_d1 + rbt_d2 + rbt_color_metric build six indices and search seven to eight times.
+//   index    built once per cloud: the 1024^3-bit volume (csrc/rbt_pcc.h), a coarse level over it (one bit per 8 x 8 x 8 block, 256 KB), one hash map voxel -> slot whose
+//            slot holds the lowest point index of the voxel (the representative of the merged point, as in D2) and the colour sums and count (as in the colour metric).
+//            Only the first point of a voxel touches the volume and the coarse level. Coordinates are checked by a kernel of their own first (error word), so a
+//            refused cloud has touched no volume word.
+//   search   one lane per point, in point order (neighbouring lanes are neighbouring points of a patch); lanes of representatives search, the others store
+//            RBT_SC_NONE. The volume is read by 32-bit words: first the 5 x 5 rows around the query, masked to x - 2 .. x + 2 (25 to 50 independent loads; a surface
+//            within 3 voxels ends here), then shells of coarse blocks of growing Chebyshev radius, where only occupied blocks that can still hold a nearer point have their
+//            8 x 8 rows read. The shell loop ends when the shell's nearest possible voxel is no nearer than the best found, at radius 127 at the latest.
+//   walks    everything else is pc_for_ties at the stored distance: A -> B gives normals to B (integer atomics) and accumulates the D1 term and the colour error; B -> A
+//            accumulates the same, the D2 value against A's own normals, and is the "take" step for points of B that got no normal; a third walk over A's ties computes
+//            the D2 value A -> B from B's completed normals. Integer sums: workgroup reduction, then one 64-bit atomic per workgroup.
+//   D2 sums  the per-point values are stored (0 for a point that is no representative) and summed in a fixed order (include/rbt.h): no floating-point atomics, the
+//            same bits from every call and from the serial host emulation. This file is compiled with -ffp-contract=off like the rest of rbt_color.hip.
+// No kernel waits for another; every loop is bounded by the size of the volume.
+#pragma once
+#include "rbt_color.h"
+
+enum { RBT_SC_BLOCK_BITS = 3, RBT_SC_CDIM = RBT_PCC_DIM >> RBT_SC_BLOCK_BITS, RBT_SC_CROW = RBT_SC_CDIM / 32, RBT_SC_COARSE_WORDS = RBT_SC_CDIM * RBT_SC_CDIM * RBT_SC_CROW,
+       RBT_SC_FINE_R = 2, RBT_SC_SUM = 256 };
+#define RBT_SC_NONE 0xFFFFFFFFu
+enum { RBT_SC_ERR = 0, RBT_SC_N_MERGED = 1, RBT_SC_SCALARS = 16 };        // words of a cloud's scalars (zeroed beforehand)
+// words of the result block of one rbt_score call (zeroed beforehand), 64-bit each; the two D1 maxima are the 32-bit halves of one word
+enum { RBT_SC_D1_AB = 0, RBT_SC_D1_BA, RBT_SC_COL_AB, RBT_SC_COL_BA = RBT_SC_COL_AB + 3, RBT_SC_D1_MAX = RBT_SC_COL_BA + 3, RBT_SC_D2_AB, RBT_SC_D2_BA = RBT_SC_D2_AB + 2, RBT_SC_RESULTS = 16 };
+
+// a cloud with its index. keys: voxel id + 1 (0 = empty); vals: lowest point index of the voxel (starts at 0xFFFFFFFF); acc: R, G, B sums and the count per slot (zeroed);
+// col: the merged colour per slot. rgb / nrm may be null.
+struct RbtScoreCloud { const int16_t* xyz; const uint8_t* rgb; const int16_t* nrm; int32_t n, lg; uint32_t* vol; uint32_t* coarse; uint32_t* keys; uint32_t* vals; uint32_t* acc; uint32_t* col; };
+// scratch of one rbt_score call. dist_*: nearest squared distance per point; acc_b / cnt_b: the normals given to B (zeroed beforehand; not part of B's index: B may be
+// scored against another source next); val_*: D2 value per point; part: 2 * ceil(max(n) / 256) doubles; res: RBT_SC_RESULTS words (zeroed beforehand)
+struct RbtScoreWork { uint32_t* dist_a; uint32_t* dist_b; long long* acc_b; int32_t* cnt_b; double* val_ab; double* val_ba; double* part; unsigned long long* res; };
+struct RbtScoreSumLds { double s[RBT_SC_SUM]; double m[RBT_SC_SUM]; };
+
+namespace rbtk {
+void launch_sc_check(const int16_t* xyz, int n, uint32_t* scal);        // scal[RBT_SC_ERR] = 1 when a coordinate lies outside 0..1023
+void launch_sc_index(const RbtScoreCloud* S, uint32_t* scal);           // insert + merge; scal[RBT_SC_N_MERGED] counts the voxels
+void launch_sc_clear(const RbtScoreCloud* S);                           // the volume and coarse words of the cloud's own points back to zero
+// parts: RBT_SCORE_* (D1 always runs: its sums come with the walks)
+void launch_sc_score(const RbtScoreCloud* A, const RbtScoreCloud* B, int parts, const RbtScoreWork* W);
+}  // namespace rbtk
+
+// ------------------------------------------------------------------------------------------------ bodies (device and host emulation)
+RBT_DEV size_t sc_coarse_word(int cx, int cy, int cz) { return (((size_t)cz * RBT_SC_CDIM + cy) * RBT_SC_CROW) + (cx >> 5); }
+// point i into the index; returns 1 for the first point of a voxel. A point out of range is never indexed (launch_sc_check has reported it).
+RBT_DEV int sc_insert(const RbtScoreCloud* S, int i) {
+  const int16_t* p = S->xyz + 3 * (size_t)i;
+  if (!tc_in_range(p)) return 0;
+  const int x = p[0], y = p[1], z = p[2];
+  int fresh; const uint32_t s = cl_slot_claim(S->keys, S->lg, pc_voxel_id(x, y, z), &fresh);
+  uint32_t* vw = &S->vol[pc_voxel_word(x, y, z)]; uint32_t* cw = &S->coarse[sc_coarse_word(x >> RBT_SC_BLOCK_BITS, y >> RBT_SC_BLOCK_BITS, z >> RBT_SC_BLOCK_BITS)];
+  const uint32_t vbit = 1u << (x & 31), cbit = 1u << ((x >> RBT_SC_BLOCK_BITS) & 31);
+#ifdef RBT_HOSTEMU
+  if (fresh) { *vw |= vbit; *cw |= cbit; }
+  if ((uint32_t)i < S->vals[s]) S->vals[s] = (uint32_t)i;
+  if (S->rgb) { for (int c = 0; c < 3; c++) S->acc[4 * s + c] += S->rgb[3 * (size_t)i + c]; S->acc[4 * s + 3]++; }
+#else
+  if (fresh) { atomicOr(vw, vbit); atomicOr(cw, cbit); }
+  atomicMin(&S->vals[s], (uint32_t)i);
+  if (S->rgb) { for (int c = 0; c < 3; c++) atomicAdd(&S->acc[4 * s + c], (uint32_t)S->rgb[3 * (size_t)i + c]); atomicAdd(&S->acc[4 * s + 3], 1u); }
+#endif
+  return fresh;
+}
+RBT_DEV void sc_merge(const RbtScoreCloud* S, uint32_t s) {             // removeDuplicate (PCCPointSet.cpp:190-203), as cl_merge
+  if (!S->keys[s]) return;
+  const uint32_t n = S->acc[4 * s + 3];
+  S->col[s] = (S->acc[4 * s] / n) | (S->acc[4 * s + 1] / n) << 8 | (S->acc[4 * s + 2] / n) << 16;
+}
+RBT_DEV void sc_clear(const RbtScoreCloud* S, int i) {
+  const int16_t* p = S->xyz + 3 * (size_t)i;
+  if (!tc_in_range(p)) return;
+  S->vol[pc_voxel_word(p[0], p[1], p[2])] = 0;
+  S->coarse[sc_coarse_word(p[0] >> RBT_SC_BLOCK_BITS, p[1] >> RBT_SC_BLOCK_BITS, p[2] >> RBT_SC_BLOCK_BITS)] = 0;
+}
+
+// the set bits of `bits` (bit k = voxel x0 + k of a row at squared distance `base` in y and z) against the query's x
+RBT_DEV uint32_t sc_row_best(uint32_t bits, int x0, int x, uint32_t base, uint32_t best) {
+  while (bits) { const int dx = x0 + __builtin_ctz(bits) - x; bits &= bits - 1; const uint32_t d = base + (uint32_t)(dx * dx); if (d < best) best = d; }
+  return best;
+}
+RBT_DEV uint32_t sc_mask(int lo, int hi) { return (0xFFFFFFFFu << (lo & 31)) & (0xFFFFFFFFu >> (31 - (hi & 31))); }     // bits lo .. hi of one word
+RBT_DEV int sc_gap(int q, int c) { const int lo = c << RBT_SC_BLOCK_BITS, hi = lo + (1 << RBT_SC_BLOCK_BITS) - 1; return q < lo ? lo - q : (q > hi ? q - hi : 0); }   // from coordinate q to block c along one axis
+// squared distance from (x, y, z) to the nearest point of Q (Q is not empty)
+RBT_DEV uint32_t sc_nearest(const RbtScoreCloud* Q, int x, int y, int z) {
+  const uint32_t* vol = Q->vol;
+  uint32_t best = 0xFFFFFFFFu;
+  const int lo = x - RBT_SC_FINE_R < 0 ? 0 : x - RBT_SC_FINE_R, hi = x + RBT_SC_FINE_R >= RBT_PCC_DIM ? RBT_PCC_DIM - 1 : x + RBT_SC_FINE_R;
+  const int w0 = lo >> 5, w1 = hi >> 5;
+  for (int dz = -RBT_SC_FINE_R; dz <= RBT_SC_FINE_R; dz++) {
+    const int zz = z + dz; if (zz < 0 || zz >= RBT_PCC_DIM) continue;
+    for (int dy = -RBT_SC_FINE_R; dy <= RBT_SC_FINE_R; dy++) {
+      const int yy = y + dy; if (yy < 0 || yy >= RBT_PCC_DIM) continue;
+      const uint32_t* row = vol + pc_voxel_word(0, yy, zz); const uint32_t base = (uint32_t)(dz * dz + dy * dy);
+      if (w0 == w1) best = sc_row_best(row[w0] & sc_mask(lo, hi), w0 * 32, x, base, best);
+      else { best = sc_row_best(row[w0] & sc_mask(lo, 31), w0 * 32, x, base, best); best = sc_row_best(row[w1] & sc_mask(0, hi), w1 * 32, x, base, best); }
+    }
+  }
+  // everything outside the cube is at least RBT_SC_FINE_R + 1 away
+  if (best <= (uint32_t)((RBT_SC_FINE_R + 1) * (RBT_SC_FINE_R + 1))) return best;
+  const int bx = x >> RBT_SC_BLOCK_BITS, by = y >> RBT_SC_BLOCK_BITS, bz = z >> RBT_SC_BLOCK_BITS;
+  auto block = [&](int cx, int cy, int cz) {                          // an occupied block: its 8 x 8 rows, one byte of a volume word each
+    const int gx = sc_gap(x, cx), gy = sc_gap(y, cy), gz = sc_gap(z, cz);
+    if ((uint32_t)(gx * gx + gy * gy + gz * gz) >= best) return;
+    const int x0 = cx << RBT_SC_BLOCK_BITS;
+    for (int zz = cz << RBT_SC_BLOCK_BITS; zz < (cz + 1) << RBT_SC_BLOCK_BITS; zz++)
+      for (int yy = cy << RBT_SC_BLOCK_BITS; yy < (cy + 1) << RBT_SC_BLOCK_BITS; yy++) {
+        const uint32_t base = (uint32_t)((zz - z) * (zz - z) + (yy - y) * (yy - y));
+        if (base >= best) continue;
+        best = sc_row_best((vol[pc_voxel_word(x0, yy, zz)] >> (x0 & 31)) & 0xFFu, x0, x, base, best);
+      }
+  };
+  for (int r = 0; r < RBT_SC_CDIM; r++) {
+    // a block of shell r lies at least 8 (r - 1) + 1 away along the axis on which it is r blocks off
+    if (r > 0) { const uint32_t lb = (uint32_t)(((r - 1) << RBT_SC_BLOCK_BITS) + 1); if (lb * lb >= best) break; }
+    const int clo = bx - r < 0 ? 0 : bx - r, chi = bx + r >= RBT_SC_CDIM ? RBT_SC_CDIM - 1 : bx + r;
+    for (int dz = -r; dz <= r; dz++) {
+      const int cz = bz + dz; if (cz < 0 || cz >= RBT_SC_CDIM) continue;
+      for (int dy = -r; dy <= r; dy++) {
+        const int cy = by + dy; if (cy < 0 || cy >= RBT_SC_CDIM) continue;
+        const int gy = sc_gap(y, cy), gz = sc_gap(z, cz);
+        if ((uint32_t)(gy * gy + gz * gz) >= best) continue;
+        const uint32_t* crow = Q->coarse + sc_coarse_word(0, cy, cz);
+        if (dz == -r || dz == r || dy == -r || dy == r) {              // on a face of the shell: the whole run of blocks, word by word
+          for (int w = clo >> 5; w <= chi >> 5; w++) {
+            uint32_t bits = crow[w] & sc_mask(w == clo >> 5 ? clo : 0, w == chi >> 5 ? chi : 31);
+            while (bits) { const int cx = w * 32 + __builtin_ctz(bits); bits &= bits - 1; block(cx, cy, cz); }
+          }
+        } else {                                                       // inside: the two ends of the run
+          if (bx - r >= 0 && ((crow[(bx - r) >> 5] >> ((bx - r) & 31)) & 1)) block(bx - r, cy, cz);
+          if (bx + r < RBT_SC_CDIM && ((crow[(bx + r) >> 5] >> ((bx + r) & 31)) & 1)) block(bx + r, cy, cz);
+        }
+      }
+    }
+  }
+  return best;
+}
+// one lane per point of P: representatives search Q
+RBT_DEV void sc_search(const RbtScoreCloud* P, const RbtScoreCloud* Q, uint32_t* dist, int i) {
+  const int16_t* p = P->xyz + 3 * (size_t)i;
+  const uint32_t s = cl_slot_find(P->keys, P->lg, pc_voxel_id(p[0], p[1], p[2]));
+  dist[i] = P->vals[s] == (uint32_t)i ? sc_nearest(Q, p[0], p[1], p[2]) : RBT_SC_NONE;
+}
+// the colour error terms of a merged point of colour pc against the tie sums (cl_error)
+RBT_DEV void sc_color_error(uint32_t pc, uint32_t sr, uint32_t sg, uint32_t sb, uint32_t n, long long e[3]) {
+  const int dr = (int)(pc & 255u) - (int)((2 * sr + n) / (2 * n)), dg = (int)((pc >> 8) & 255u) - (int)((2 * sg + n) / (2 * n)), db = (int)(pc >> 16) - (int)((2 * sb + n) / (2 * n));
+  e[0] = 2126 * dr + 7152 * dg + 722 * db;
+  e[1] = -1146 * dr - 3854 * dg + 5000 * db;
+  e[2] = 5000 * dr - 4542 * dg - 458 * db;
+}
+// walk A -> B for point i of A: normals to B's tie points (pc_d2_give), the D1 term *d, the colour error e. Returns 0 for a point that is no representative.
+RBT_DEV int sc_walk_ab(const RbtScoreCloud* A, const RbtScoreCloud* B, const RbtScoreWork* W, int parts, int i, uint32_t* d, long long e[3]) {
+  const uint32_t d2 = W->dist_a[i]; if (d2 == RBT_SC_NONE) return 0;
+  const int16_t* p = A->xyz + 3 * (size_t)i; const int x = p[0], y = p[1], z = p[2];
+  uint32_t sr = 0, sg = 0, sb = 0, n = 0;
+  pc_for_ties(B->vol, x, y, z, d2, [&](uint32_t id) {
+    const uint32_t s = cl_slot_find(B->keys, B->lg, id);
+    if (parts & RBT_SCORE_COLOR) { const uint32_t c = B->col[s]; sr += c & 255u; sg += (c >> 8) & 255u; sb += c >> 16; }
+    n++;
+    if (parts & RBT_SCORE_D2) {
+      const uint32_t j = B->vals[s];
+#ifdef RBT_HOSTEMU
+      for (int c = 0; c < 3; c++) W->acc_b[3 * (size_t)j + c] += A->nrm[3 * (size_t)i + c];
+      W->cnt_b[j]++;
+#else
+      for (int c = 0; c < 3; c++) atomicAdd((unsigned long long*)&W->acc_b[3 * (size_t)j + c], (unsigned long long)(long long)A->nrm[3 * (size_t)i + c]);
+      atomicAdd(&W->cnt_b[j], 1);
+#endif
+    }
+  });
+  *d = d2;
+  if (parts & RBT_SCORE_COLOR) sc_color_error(A->col[cl_slot_find(A->keys, A->lg, pc_voxel_id(x, y, z))], sr, sg, sb, n, e);
+  return 1;
+}
+// walk B -> A for point j of B: the D1 term, the colour error, the D2 value against A's own normals (pc_d2_value with a count of 1), and the "take" step of
+// scaleNormals for a point that got no normal from the walk A -> B (pc_d2_take)
+RBT_DEV int sc_walk_ba(const RbtScoreCloud* B, const RbtScoreCloud* A, const RbtScoreWork* W, int parts, int j, uint32_t* d, long long e[3]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const uint32_t d2 = W->dist_b[j];
+  if (d2 == RBT_SC_NONE) { if (parts & RBT_SCORE_D2) W->val_ba[j] = 0.0; return 0; }
+  const int16_t* p = B->xyz + 3 * (size_t)j; const int x = p[0], y = p[1], z = p[2];
+  uint32_t sr = 0, sg = 0, sb = 0, n = 0; long long s0 = 0, s1 = 0, s2 = 0; double sum = 0;
+  pc_for_ties(A->vol, x, y, z, d2, [&](uint32_t id) {
+    const uint32_t s = cl_slot_find(A->keys, A->lg, id);
+    if (parts & RBT_SCORE_COLOR) { const uint32_t c = A->col[s]; sr += c & 255u; sg += (c >> 8) & 255u; sb += c >> 16; }
+    n++;
+    if (parts & RBT_SCORE_D2) {
+      const int16_t* q = A->nrm + 3 * (size_t)A->vals[s];
+      const int ex = x - (int)(id & (RBT_PCC_DIM - 1)), ey = y - (int)((id >> RBT_PCC_BITS) & (RBT_PCC_DIM - 1)), ez = z - (int)(id >> (2 * RBT_PCC_BITS));
+      const long long dot = (long long)ex * q[0] + (long long)ey * q[1] + (long long)ez * q[2];
+      const double v = (double)dot / (double)1;
+      sum += v * v; s0 += q[0]; s1 += q[1]; s2 += q[2];
+    }
+  });
+  *d = d2;
+  if (parts & RBT_SCORE_COLOR) sc_color_error(B->col[cl_slot_find(B->keys, B->lg, pc_voxel_id(x, y, z))], sr, sg, sb, n, e);
+  if (parts & RBT_SCORE_D2) {
+    W->val_ba[j] = sum / (int)n / (16384.0 * 16384.0);
+    if (W->cnt_b[j] == 0) { W->acc_b[3 * (size_t)j] = s0; W->acc_b[3 * (size_t)j + 1] = s1; W->acc_b[3 * (size_t)j + 2] = s2; W->cnt_b[j] = (int32_t)n; }
+  }
+  return 1;
+}
+// third walk, point i of A: the D2 value against B's normals acc_b / cnt_b, complete now (pc_d2_value)
+RBT_DEV void sc_d2_ab(const RbtScoreCloud* A, const RbtScoreCloud* B, const RbtScoreWork* W, int i) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const uint32_t d2 = W->dist_a[i];
+  if (d2 == RBT_SC_NONE) { W->val_ab[i] = 0.0; return; }
+  const int16_t* p = A->xyz + 3 * (size_t)i; const int x = p[0], y = p[1], z = p[2];
+  double sum = 0; int n = 0;
+  pc_for_ties(B->vol, x, y, z, d2, [&](uint32_t id) {
+    const uint32_t j = B->vals[cl_slot_find(B->keys, B->lg, id)];
+    const int ex = x - (int)(id & (RBT_PCC_DIM - 1)), ey = y - (int)((id >> RBT_PCC_BITS) & (RBT_PCC_DIM - 1)), ez = z - (int)(id >> (2 * RBT_PCC_BITS));
+    const long long dot = ex * W->acc_b[3 * (size_t)j] + ey * W->acc_b[3 * (size_t)j + 1] + ez * W->acc_b[3 * (size_t)j + 2];
+    const double v = (double)dot / (double)W->cnt_b[j];
+    sum += v * v; n++;
+  });
+  W->val_ab[i] = sum / n / (16384.0 * 16384.0);
+}
+// The fixed summation order of the D2 values (include/rbt.h). Block b: entries b * 256 + t, t = 0..255 (0 past the end), folded by s[t] += s[t + h] for h = 128, 64, .. 1.
+RBT_DEV void sc_fold(RBT_LDS_AS RbtScoreSumLds* L, double* sum, double* max) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  RBT_SYNC();
+  for (int h = RBT_SC_SUM / 2; h > 0; h >>= 1) {
+    RBT_BLK_FOR(t, h) { L->s[t] = L->s[t] + L->s[t + h]; if (L->m[t + h] > L->m[t]) L->m[t] = L->m[t + h]; }
+    RBT_SYNC();
+  }
+  RBT_BLK_FOR(t, 1) { *sum = L->s[0]; *max = L->m[0]; }
+  RBT_SYNC();
+}
+RBT_DEV void sc_sum_block(const double* val, int n, int b, double* part, RBT_LDS_AS RbtScoreSumLds* L) {
+  RBT_BLK_FOR(t, RBT_SC_SUM) { const int i = b * RBT_SC_SUM + t; const double v = i < n ? val[i] : 0.0; L->s[t] = v; L->m[t] = v; }
+  sc_fold(L, &part[2 * b], &part[2 * b + 1]);
+}
+// the block results: lane t adds those of blocks t, t + 256, .. in ascending order, then the same fold. out[0] = sum, out[1] = maximum
+RBT_DEV void sc_sum_final(const double* part, int n_blocks, double* out, RBT_LDS_AS RbtScoreSumLds* L) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  RBT_BLK_FOR(t, RBT_SC_SUM) {
+    double s = 0.0, m = 0.0;
+    for (int b = t; b < n_blocks; b += RBT_SC_SUM) { s = s + part[2 * b]; if (part[2 * b + 1] > m) m = part[2 * b + 1]; }
+    L->s[t] = s; L->m[t] = m;
+  }
+  sc_fold(L, &out[0], &out[1]);
+}
+
+#ifdef RBT_HOSTEMU
+// serial stand-ins of the launchers (the product's are in rbt_color.hip)
+namespace rbtk {
+inline void launch_sc_check(const int16_t* xyz, int n, uint32_t* scal) { for (int i = 0; i < n; i++) if (!tc_in_range(xyz + 3 * (size_t)i)) scal[RBT_SC_ERR] = 1; }
+inline void launch_sc_index(const RbtScoreCloud* S, uint32_t* scal) {
+  for (int i = 0; i < S->n; i++) scal[RBT_SC_N_MERGED] += (uint32_t)sc_insert(S, i);
+  if (S->rgb) for (uint32_t s = 0; s < (1u << S->lg); s++) sc_merge(S, s);
+}
+inline void launch_sc_clear(const RbtScoreCloud* S) { for (int i = 0; i < S->n; i++) sc_clear(S, i); }
+inline void launch_sc_score(const RbtScoreCloud* A, const RbtScoreCloud* B, int parts, const RbtScoreWork* W) {
+  static RbtScoreSumLds lds;
+  uint32_t* mx = (uint32_t*)&W->res[RBT_SC_D1_MAX];
+  for (int i = 0; i < A->n; i++) sc_search(A, B, W->dist_a, i);
+  for (int j = 0; j < B->n; j++) sc_search(B, A, W->dist_b, j);
+  for (int dir = 0; dir < 2; dir++) {
+    const int n = dir ? B->n : A->n;
+    for (int i = 0; i < n; i++) {
+      uint32_t d = 0; long long e[3] = {0, 0, 0};
+      if (!(dir ? sc_walk_ba(B, A, W, parts, i, &d, e) : sc_walk_ab(A, B, W, parts, i, &d, e))) continue;
+      W->res[RBT_SC_D1_AB + dir] += d; if (d > mx[dir]) mx[dir] = d;
+      for (int c = 0; c < 3; c++) W->res[(dir ? RBT_SC_COL_BA : RBT_SC_COL_AB) + c] += (unsigned long long)(e[c] * e[c]);
+    }
+  }
+  if (!(parts & RBT_SCORE_D2)) return;
+  for (int i = 0; i < A->n; i++) sc_d2_ab(A, B, W, i);
+  for (int dir = 0; dir < 2; dir++) {
+    const int n = dir ? B->n : A->n, nb = (n + RBT_SC_SUM - 1) / RBT_SC_SUM;
+    for (int b = 0; b < nb; b++) sc_sum_block(dir ? W->val_ba : W->val_ab, n, b, W->part, &lds);
+    sc_sum_final(W->part, nb, (double*)&W->res[dir ? RBT_SC_D2_BA : RBT_SC_D2_AB], &lds);
+  }
+}
+}  // namespace rbtk
+#endif

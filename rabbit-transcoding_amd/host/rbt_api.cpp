@@ -4,12 +4,15 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <vector>
 #include "rbt_batch.h"
 #include "rbt_transcode.h"
 #include "rbt_pcc.h"
 #include "rbt_internal.h"
 
-struct rbt_ctx { int device, rank, world; rbt_stats stats; std::string last_err; double color_ms[4] = {0, 0, 0, 0}; int n_changed = 0; };
+struct rbt_pcloud { rbt::PCloud* cloud; rbt_ctx* owner; };
+struct rbt_ctx { int device, rank, world; rbt_stats stats; std::string last_err; double color_ms[4] = {0, 0, 0, 0}; int n_changed = 0;
+                 std::vector<rbt_pcloud*> clouds; rbt::PCloudCache cloud_cache; };      // handles outstanding; clean volumes of released clouds
 struct rbt_job { rbt::GofJob* j; rbt_ctx* owner; };
 
 // Job slots, pipeline depth and the lock are per DEVICE (the 16 HIP streams a job's lanes map onto are the device's, rbt_kernels.hip):
@@ -61,6 +64,8 @@ void rbt_destroy(rbt_ctx* ctx) {
     DevState& D = g_dev[ctx->device]; std::lock_guard<std::mutex> lk(D.mu);
     if (!rbtk::dev_select(ctx->device)) {
       for (int s = 0; s < RBT_MAX_JOBS; s++) if (D.jobs[s] && D.jobs[s]->owner == ctx) { rbt::gof_abandon(D.jobs[s]->j); delete D.jobs[s]; D.jobs[s] = nullptr; }
+      for (rbt_pcloud* h : ctx->clouds) { rbt::pcloud_release(ctx->cloud_cache, h->cloud); delete h; }
+      ctx->clouds.clear(); rbt::pcloud_cache_trim(ctx->cloud_cache);
       rbtk::dev_release_pool();
     }
   }
@@ -199,6 +204,8 @@ int rbt_device_memory(rbt_ctx* ctx, rbt_memory* out) try {
   memset(out, 0, sizeof(*out));
   if (rbtk::dev_mem_info(&out->free_bytes, &out->total_bytes, &out->cached_bytes, &out->in_use_bytes)) return RBT_ERR_NO_DEVICE;
   out->reserve_bytes = rbtk::dev_reserve_bytes();
+  const size_t kept = ctx->cloud_cache.bytes();           // clean volumes of released clouds: cached, not in use
+  out->cached_bytes += kept; out->in_use_bytes -= kept < out->in_use_bytes ? kept : out->in_use_bytes;
   return RBT_OK;
 } RBT_CATCH
 int rbt_job_memory(rbt_ctx* ctx, const rbt_job* job, size_t* bytes) try {
@@ -213,6 +220,7 @@ int rbt_trim(rbt_ctx* ctx) try {
   if (!ctx) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   for (int s = 0; s < RBT_MAX_JOBS; s++) if (D.jobs[s]) return RBT_ERR_BUSY;
+  rbt::pcloud_cache_trim(ctx->cloud_cache);
   rbtk::dev_release_pool();
   return RBT_OK;
 } RBT_CATCH
@@ -335,5 +343,82 @@ int rbt_color_stage_ms(rbt_ctx* ctx, double ms[3]) try {
   for (int i = 0; i < 3; i++) ms[i] = ctx->color_ms[i];
   return RBT_OK;
 } RBT_CATCH
+
+// ---- clouds on the device and their scoring (csrc/rbt_score.h) ----
+static bool cloud_of(const rbt_ctx* ctx, const rbt_pcloud* h) { return h && h->owner == ctx; }
+static int cloud_handle(rbt_ctx* ctx, rbt::PCloud* c, rbt_pcloud** out) {
+  rbt_pcloud* h = nullptr;
+  try { h = new rbt_pcloud{c, ctx}; ctx->clouds.push_back(h); } catch (...) { delete h; rbt::pcloud_release(ctx->cloud_cache, c); return RBT_ERR_NOMEM; }
+  *out = h;
+  return RBT_OK;
+}
+int rbt_pcloud_upload(rbt_ctx* ctx, const int16_t* xyz, const uint8_t* rgb, const int16_t* normals_q14, int n, rbt_pcloud** out) try {
+  if (!ctx || !out) return RBT_ERR_PARAM;
+  *out = nullptr;
+  if (!xyz) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  rbt::PCloud* c = nullptr;
+  const int rc = rbt::pcloud_upload(ctx->last_err, ctx->cloud_cache, xyz, rgb, normals_q14, n, &c);
+  return rc ? rc : cloud_handle(ctx, c, out);
+} RBT_CATCH
+int rbt_pcloud_from_maps(rbt_ctx* ctx, const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const uint16_t* occ_luma, const uint16_t* geo_d0,
+                         const uint16_t* geo_d1, int geo_bit_depth, const uint16_t* attr_t0, const uint16_t* attr_t1, int attr_bit_depth, int upsample_filter, int attr_transfer,
+                         rbt_pcloud** out, rbt_cloud* host_copy, uint8_t** rgb) {
+  if (!ctx || !out) return RBT_ERR_PARAM;
+  *out = nullptr; if (rgb) *rgb = nullptr; if (host_copy) memset(host_copy, 0, sizeof(*host_copy));
+  if (!atlas || (!patches && n_patches) || !occ_luma || !geo_d0) return RBT_ERR_PARAM;
+  int rc;
+  try {
+    RBT_ENTER(ctx);
+    ctx->color_ms[3] = 0; ctx->n_changed = 0;
+    if (attr_transfer != 0 && attr_transfer != 1) { ctx->last_err = "attribute transfer filter types other than 1 are not built"; return RBT_ERR_UNSUPPORTED; }
+    rbt::PCloud* c = nullptr;
+    rc = rbt::pcloud_from_maps(ctx->last_err, ctx->cloud_cache, atlas, patches, n_patches, occ_luma, geo_d0, geo_d1, geo_bit_depth, attr_t0, attr_t1, attr_bit_depth, upsample_filter, attr_transfer, &c,
+                               host_copy, rgb, &ctx->n_changed, ctx->color_ms);
+    if (!rc) rc = cloud_handle(ctx, c, out);
+  } catch (const std::bad_alloc&) { rc = RBT_ERR_NOMEM; } catch (...) { rc = RBT_ERR_NO_DEVICE; }
+  if (rc) { if (host_copy) rbt_cloud_free(host_copy); if (rgb) { free(*rgb); *rgb = nullptr; } }
+  return rc;
+}
+int rbt_pcloud_points(const rbt_pcloud* cloud, int* n_points, int* n_merged) {
+  if (!cloud) return RBT_ERR_PARAM;
+  rbt::pcloud_points(cloud->cloud, n_points, n_merged);
+  return RBT_OK;
+}
+void rbt_pcloud_release(rbt_ctx* ctx, rbt_pcloud* cloud) {
+  if (!ctx || !cloud_of(ctx, cloud)) return;
+  DevState& D = g_dev[ctx->device]; std::lock_guard<std::mutex> lk(D.mu);
+  for (size_t i = 0; i < ctx->clouds.size(); i++) if (ctx->clouds[i] == cloud) {
+    ctx->clouds.erase(ctx->clouds.begin() + (long)i);
+    if (!rbtk::dev_select(ctx->device)) rbt::pcloud_release(ctx->cloud_cache, cloud->cloud);
+    delete cloud;
+    return;
+  }
+}
+int rbt_score(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int parts, rbt_frame_score* out) try {
+  if (!ctx || !out) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  if (!cloud_of(ctx, a) || !cloud_of(ctx, b)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
+  if (parts < 0 || parts > (RBT_SCORE_D1 | RBT_SCORE_D2 | RBT_SCORE_COLOR)) { ctx->last_err = "parts is not a set of RBT_SCORE_*"; return RBT_ERR_PARAM; }
+  return rbt::pcloud_score(ctx->last_err, a->cloud, b->cloud, peak, parts, out);
+} RBT_CATCH
+int rbt_score_summary(const rbt_frame_score* frames, int n_frames, rbt_sequence_score* out) {
+  if (!out || n_frames < 0 || (!frames && n_frames)) return RBT_ERR_PARAM;
+  memset(out, 0, sizeof(*out));
+  out->n_frames = n_frames;
+  double sum[5] = {0, 0, 0, 0, 0}, least[5] = {0, 0, 0, 0, 0}; int n[5] = {0, 0, 0, 0, 0};
+  for (int f = 0; f < n_frames; f++) {
+    const rbt_frame_score& s = frames[f];
+    out->points_a += s.n_points_a; out->points_b += s.n_points_b; out->merged_a += s.n_merged_a; out->merged_b += s.n_merged_b;
+    const double fig[5] = {s.d1.psnr, s.d2.psnr, s.color.psnr[0], s.color.psnr[1], s.color.psnr[2]};
+    const int part[5] = {RBT_SCORE_D1, RBT_SCORE_D2, RBT_SCORE_COLOR, RBT_SCORE_COLOR, RBT_SCORE_COLOR};
+    for (int k = 0; k < 5; k++) if (s.parts & part[k]) { sum[k] += fig[k]; if (!n[k] || fig[k] < least[k]) least[k] = fig[k]; n[k]++; }
+  }
+  out->n_d1 = n[0]; out->n_d2 = n[1]; out->n_color = n[2];
+  double mean[5]; for (int k = 0; k < 5; k++) mean[k] = n[k] ? sum[k] / n[k] : 0.0;
+  out->mean_d1 = mean[0]; out->min_d1 = least[0]; out->mean_d2 = mean[1]; out->min_d2 = least[1];
+  for (int c = 0; c < 3; c++) { out->mean_color[c] = mean[2 + c]; out->min_color[c] = least[2 + c]; }
+  return RBT_OK;
+}
 
 }  // extern "C"

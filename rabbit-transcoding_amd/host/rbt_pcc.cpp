@@ -8,10 +8,14 @@
 #include "rbt_pcc.h"
 #include "../csrc/rbt_pcc.h"
 #include "../csrc/rbt_color.h"
+#include "../csrc/rbt_score.h"
 
 namespace rbt {
 namespace {
-struct DevBuf { void* p = nullptr; ~DevBuf() { rbtk::dev_free(p); } bool alloc(size_t n) { p = rbtk::dev_alloc(n); return p != nullptr; } template <class T> T* as() { return (T*)p; } };
+struct DevBuf { void* p = nullptr; ~DevBuf() { rbtk::dev_free(p); } bool alloc(size_t n) { p = rbtk::dev_alloc(n); return p != nullptr; } template <class T> T* as() const { return (T*)p; }
+                void take(DevBuf& o) { rbtk::dev_free(p); p = o.p; o.p = nullptr; } };
+// what reconstruct_impl leaves on the device for rbt_pcloud_from_maps: positions, 4:4:4 triples and RGB8 triples of the finished cloud
+struct DevCloud { DevBuf xyz, yuv, rgb; };
 int block_xy(const rbt_patch& p, int ub, int vb, int* x, int* y) {       // PCCPatch::patchBlock2CanvasBlock
   switch (p.orientation) {
     case RBT_OR_DEFAULT: *x = ub + p.u0; *y = vb + p.v0; return 1;
@@ -29,6 +33,22 @@ int block_xy(const rbt_patch& p, int ub, int vb, int* x, int* y) {       // PCCP
 enum { T_COL_UP = T_COUNT, T_COL_RGB, T_COL_METRIC, T_COL_DIST, T_COL_TRANSFER, T_COL_TRANSFER_COPY };    // the metric in two parts: insert + merge, distance (a read-back of the merged counts lies between them)
 static_assert(T_COL_TRANSFER_COPY < 16, "timer slots");
 int lg_of(int n) { int lg = 4; while (((size_t)1 << lg) < 2 * (size_t)n) lg++; return lg; }
+// the derived fields of the three results from the sums and counts (shared by the host-array calls and rbt_score)
+// QualityMetrics::compute :204-206: float mse, getPSNR with factor 3; symmetric = the worse direction (:299-309)
+template <class R> void finish_geometry(R* out, int peak) {
+  out->mse_ab = (float)((double)out->sse_ab / out->n_a); out->mse_ba = (float)((double)out->sse_ba / out->n_b);
+  const float p = (float)peak, m = out->mse_ab > out->mse_ba ? out->mse_ab : out->mse_ba;
+  out->psnr_ab = 10 * log10f(3 * p * p / out->mse_ab); out->psnr_ba = 10 * log10f(3 * p * p / out->mse_ba); out->psnr = 10 * log10f(3 * p * p / m);
+}
+void finish_color(rbt_color_result* out) {
+  const double unit = 2550000.0 * 2550000.0;
+  for (int c = 0; c < 3; c++) {
+    out->mse_ab[c] = (float)((double)out->sse_ab[c] / (unit * (double)out->n_a)); out->mse_ba[c] = (float)((double)out->sse_ba[c] / (unit * (double)out->n_b));
+    out->psnr_ab[c] = 10 * log10f(1.0f / out->mse_ab[c]); out->psnr_ba[c] = 10 * log10f(1.0f / out->mse_ba[c]);
+    out->mse[c] = out->mse_ab[c] > out->mse_ba[c] ? out->mse_ab[c] : out->mse_ba[c];
+    out->psnr[c] = out->psnr_ab[c] < out->psnr_ba[c] ? out->psnr_ab[c] : out->psnr_ba[c];
+  }
+}
 
 // Attribute transfer (csrc/rbt_color.h) on clouds that are on the device: source = the cloud before smoothing, target = the cloud after it, whose colours are updated in
 // place; n_moved = the number of set bytes in d_moved, > 0. flag_G / flag_meta (rbt_reconstruct_decoded): d_moved is still to be written, by the smoothing's filter asked
@@ -70,12 +90,13 @@ int transfer_on_device(std::string& err, const int16_t* d_sxyz, const uint16_t* 
 // point's pixel (RbtPccParams.has_attr = 2) and the triples are converted to RGB8; stage_ms[0..1]: device time of the up-conversion and of the RGB conversion
 static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
                             const uint16_t* t0, const uint16_t* t1, int attr_bd, rbt_cloud* out, int filter, uint8_t** rgb, double* stage_ms, int attr_transfer = 0, uint8_t** moved_out = nullptr,
-                            int* n_changed = nullptr) {
+                            int* n_changed = nullptr, DevCloud* keep_dev = nullptr, bool to_host = true) {
+  const bool want_rgb = rgb != nullptr || keep_dev != nullptr;      // the colour path of rbt_reconstruct_rgb; to_host = false (with keep_dev): only the counts of *out are filled
   memset(out, 0, sizeof(*out));
   if (moved_out) *moved_out = nullptr;
   if (n_changed) *n_changed = 0;
-  if (rgb) {
-    *rgb = nullptr;
+  if (rgb) *rgb = nullptr;
+  if (want_rgb) {
     if (!t0 || (a->map_count > 1 && !t1) || (attr_bd != 8 && attr_bd != 10) || (filter != RBT_UPSAMPLE_F0 && filter != RBT_UPSAMPLE_REPLICATE)) { err = "attribute pictures of 8 or 10 bits and a known up-sampling filter are needed"; return RBT_ERR_PARAM; }
   }
   const int W = a->width, H = a->height, res = a->occupancy_resolution, prec = a->occupancy_precision;
@@ -89,7 +110,7 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
   const bool smooth = a->geometry_smoothing != 0, transfer = smooth && attr_transfer != 0, keep = transfer || (smooth && moved_out);   // keep: the cloud before smoothing stays
   RbtPccParams P; memset(&P, 0, sizeof(P));
   P.w = W; P.h = H; P.res = res; P.prec = prec; P.map_count = a->map_count; P.absolute_d1 = a->absolute_d1; P.remove_dup = a->remove_duplicate_points; P.threshold = a->threshold_lossy_om;
-  P.geo_bd = geo_bd; P.attr_bd = attr_bd; P.bw = W / res; P.bh = H / res; P.ow = W / prec; P.n_patches = n_patches; P.has_attr = rgb ? 2 : t0 != nullptr;
+  P.geo_bd = geo_bd; P.attr_bd = attr_bd; P.bw = W / res; P.bh = H / res; P.ow = W / prec; P.n_patches = n_patches; P.has_attr = want_rgb ? 2 : t0 != nullptr;
   // every patch block must lie on the canvas (the reference exits otherwise, PCCPatch.cpp:238-245); items in the reference's visiting order
   std::vector<uint32_t> items;
   for (int pi = 0; pi < n_patches; pi++) {
@@ -107,16 +128,16 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
   DevBuf b_occ, b_d0, b_d1, b_t0, b_t1, b_patches, b_items, b_b2p, b_counts, b_off, b_om, b_xyz, b_yuv, b_meta, b_cells, b_scal, b_420, b_rgb, b_xyz0, b_yuv0, b_moved;
   if (!b_occ.alloc(os * 2) || !b_d0.alloc(ys * 2) || !b_d1.alloc(ys * 2) || !b_patches.alloc(sizeof(rbt_patch) * (size_t)(n_patches ? n_patches : 1)) || !b_items.alloc(4 * (size_t)(n_items ? n_items : 1)) ||
       !b_b2p.alloc(4 * (size_t)P.bw * P.bh) || !b_counts.alloc(4 * (size_t)(n_items + 1)) || !b_off.alloc(4 * (size_t)(n_items + 1)) || !b_om.alloc(ys) ||
-      (t0 && !rgb && (!b_t0.alloc(fs * 2) || !b_t1.alloc(fs * 2))) || (rgb && (!b_420.alloc(fs * 4) || !b_t0.alloc(ys * 12)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+      (t0 && !want_rgb && (!b_t0.alloc(fs * 2) || !b_t1.alloc(fs * 2))) || (want_rgb && (!b_420.alloc(fs * 4) || !b_t0.alloc(ys * 12)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
   int bad = rbtk::h2d(b_occ.p, occ, os * 2) | rbtk::h2d(b_d0.p, d0, ys * 2) | rbtk::h2d(b_d1.p, d1 ? d1 : d0, ys * 2);
   if (n_patches) bad |= rbtk::h2d(b_patches.p, patches, sizeof(rbt_patch) * (size_t)n_patches);
   if (n_items) bad |= rbtk::h2d(b_items.p, items.data(), 4 * (size_t)n_items);
-  if (t0 && !rgb) bad |= rbtk::h2d(b_t0.p, t0, fs * 2) | rbtk::h2d(b_t1.p, t1 ? t1 : t0, fs * 2);
-  if (rgb) bad |= rbtk::h2d(b_420.p, t0, fs * 2) | rbtk::h2d(b_420.as<uint16_t>() + fs, t1 ? t1 : t0, fs * 2);
+  if (t0 && !want_rgb) bad |= rbtk::h2d(b_t0.p, t0, fs * 2) | rbtk::h2d(b_t1.p, t1 ? t1 : t0, fs * 2);
+  if (want_rgb) bad |= rbtk::h2d(b_420.p, t0, fs * 2) | rbtk::h2d(b_420.as<uint16_t>() + fs, t1 ? t1 : t0, fs * 2);
   bad |= rbtk::dev_memset(b_b2p.p, 0, 4 * (size_t)P.bw * P.bh);
   if (bad) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
   const uint16_t *p_t0 = b_t0.as<uint16_t>(), *p_t1 = b_t1.as<uint16_t>();
-  if (rgb) {        // both pictures in one launch: 2 x 3 planes of W x H in b_t0
+  if (want_rgb) {        // both pictures in one launch: 2 x 3 planes of W x H in b_t0
     rbtk::timer_begin(T_COL_UP); rbtk::launch_up444(b_420.as<uint16_t>(), W, H, attr_bd, 2, filter, b_t0.as<uint16_t>()); rbtk::timer_end(T_COL_UP);
     p_t1 = p_t0 + 3 * ys;
   }
@@ -167,25 +188,31 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
       } else if (keep) rbtk::launch_tc_flag(&G, b_xyz0.as<int16_t>(), b_meta.as<uint32_t>(), b_moved.as<uint8_t>());
     }
   }
-  out->xyz = (int16_t*)malloc(6 * (size_t)(total ? total : 1)); out->yuv = (uint16_t*)malloc(6 * (size_t)(total ? total : 1));
-  out->occupancy_map = (uint8_t*)malloc(ys); out->block_to_patch = (uint32_t*)malloc(4 * (size_t)P.bw * P.bh);
-  if (!out->xyz || !out->yuv || !out->occupancy_map || !out->block_to_patch) { err = "out of memory"; return RBT_ERR_NOMEM; }
-  bad = rbtk::d2h(out->occupancy_map, b_om.p, ys) | rbtk::d2h(out->block_to_patch, b_b2p.p, 4 * (size_t)P.bw * P.bh);
-  if (total) bad |= rbtk::d2h(out->xyz, b_xyz.p, 6 * (size_t)total) | rbtk::d2h(out->yuv, b_yuv.p, 6 * (size_t)total);
+  bad = 0;
+  if (to_host) {
+    out->xyz = (int16_t*)malloc(6 * (size_t)(total ? total : 1)); out->yuv = (uint16_t*)malloc(6 * (size_t)(total ? total : 1));
+    out->occupancy_map = (uint8_t*)malloc(ys); out->block_to_patch = (uint32_t*)malloc(4 * (size_t)P.bw * P.bh);
+    if (!out->xyz || !out->yuv || !out->occupancy_map || !out->block_to_patch) { err = "out of memory"; return RBT_ERR_NOMEM; }
+    bad = rbtk::d2h(out->occupancy_map, b_om.p, ys) | rbtk::d2h(out->block_to_patch, b_b2p.p, 4 * (size_t)P.bw * P.bh);
+    if (total) bad |= rbtk::d2h(out->xyz, b_xyz.p, 6 * (size_t)total) | rbtk::d2h(out->yuv, b_yuv.p, 6 * (size_t)total);
+  }
   if (moved_out) {
     *moved_out = (uint8_t*)calloc(total ? total : 1, 1);
     if (!*moved_out) { err = "out of memory"; return RBT_ERR_NOMEM; }
     if (b_moved.p && total) bad |= rbtk::d2h(*moved_out, b_moved.p, total);
   }
-  if (rgb) {
-    *rgb = (uint8_t*)malloc(3 * (size_t)(total ? total : 1));
-    if (!*rgb) { err = "out of memory"; return RBT_ERR_NOMEM; }
+  if (want_rgb) {
     if (!b_rgb.alloc(3 * (size_t)(total ? total : 1))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
     rbtk::timer_begin(T_COL_RGB); rbtk::launch_yuv16_rgb8(b_yuv.as<uint16_t>(), (int)total, b_rgb.as<uint8_t>()); rbtk::timer_end(T_COL_RGB);
-    if (total) bad |= rbtk::d2h(*rgb, b_rgb.p, 3 * (size_t)total);
+    if (rgb) {
+      *rgb = (uint8_t*)malloc(3 * (size_t)(total ? total : 1));
+      if (!*rgb) { err = "out of memory"; return RBT_ERR_NOMEM; }
+      if (total) bad |= rbtk::d2h(*rgb, b_rgb.p, 3 * (size_t)total);
+    }
   }
   if (bad || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-  if (rgb && stage_ms) { stage_ms[0] = rbtk::timer_ms(T_COL_UP); stage_ms[1] = rbtk::timer_ms(T_COL_RGB); }
+  if (want_rgb && stage_ms) { stage_ms[0] = rbtk::timer_ms(T_COL_UP); stage_ms[1] = rbtk::timer_ms(T_COL_RGB); }
+  if (keep_dev) { keep_dev->xyz.take(b_xyz); keep_dev->yuv.take(b_yuv); keep_dev->rgb.take(b_rgb); }
   return RBT_OK;
 }
 int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
@@ -282,14 +309,8 @@ int pcc_color_metric(std::string& err, const int16_t* a, const uint8_t* rgb_a, i
   if (rbtk::d2h(h, res.p, 64) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
   if (ms) *ms = rbtk::timer_ms(T_COL_METRIC) + rbtk::timer_ms(T_COL_DIST);      // kernels only: the read-back between the two parts is not in it
   out->n_a = (int)cnt[0]; out->n_b = (int)cnt[1];
-  const double unit = 2550000.0 * 2550000.0;
-  for (int c = 0; c < 3; c++) {
-    out->sse_ab[c] = h[c]; out->sse_ba[c] = h[3 + c];
-    out->mse_ab[c] = (float)((double)h[c] / (unit * (double)out->n_a)); out->mse_ba[c] = (float)((double)h[3 + c] / (unit * (double)out->n_b));
-    out->psnr_ab[c] = 10 * log10f(1.0f / out->mse_ab[c]); out->psnr_ba[c] = 10 * log10f(1.0f / out->mse_ba[c]);
-    out->mse[c] = out->mse_ab[c] > out->mse_ba[c] ? out->mse_ab[c] : out->mse_ba[c];
-    out->psnr[c] = out->psnr_ab[c] < out->psnr_ba[c] ? out->psnr_ab[c] : out->psnr_ba[c];
-  }
+  for (int c = 0; c < 3; c++) { out->sse_ab[c] = h[c]; out->sse_ba[c] = h[3 + c]; }
+  finish_color(out);
   return RBT_OK;
 }
 
@@ -313,10 +334,7 @@ int pcc_d1(std::string& err, const int16_t* a, int na, const int16_t* b, int nb,
   if (rbtk::d2h(h, acc.p, 64) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
   const uint32_t* h32 = (const uint32_t*)h;
   out->sse_ab = h[0]; out->sse_ba = h[1]; out->n_a = (int)h32[4]; out->n_b = (int)h32[5]; out->max_ab = h32[6]; out->max_ba = h32[7];
-  // QualityMetrics::compute :204-206: float mse, getPSNR with factor 3; symmetric = the worse direction (:299-309)
-  out->mse_ab = (float)((double)out->sse_ab / out->n_a); out->mse_ba = (float)((double)out->sse_ba / out->n_b);
-  const float p = (float)peak, m = out->mse_ab > out->mse_ba ? out->mse_ab : out->mse_ba;
-  out->psnr_ab = 10 * log10f(3 * p * p / out->mse_ab); out->psnr_ba = 10 * log10f(3 * p * p / out->mse_ba); out->psnr = 10 * log10f(3 * p * p / m);
+  finish_geometry(out, peak);
   return RBT_OK;
 }
 
@@ -348,9 +366,124 @@ int pcc_d2(std::string& err, const int16_t* a, const int16_t* normals_a, int na,
   if (rbtk::d2h(h, res.p, 64) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
   uint64_t cnt_a, cnt_b; memcpy(&cnt_a, &h[2], 8); memcpy(&cnt_b, &h[6], 8);
   out->n_a = (int)cnt_a; out->n_b = (int)cnt_b; out->sse_ab = h[0]; out->max_ab = h[1]; out->sse_ba = h[4]; out->max_ba = h[5];
-  out->mse_ab = (float)(out->sse_ab / out->n_a); out->mse_ba = (float)(out->sse_ba / out->n_b);
-  const float p = (float)peak, m = out->mse_ab > out->mse_ba ? out->mse_ab : out->mse_ba;
-  out->psnr_ab = 10 * log10f(3 * p * p / out->mse_ab); out->psnr_ba = 10 * log10f(3 * p * p / out->mse_ba); out->psnr = 10 * log10f(3 * p * p / m);
+  finish_geometry(out, peak);
+  return RBT_OK;
+}
+
+// ---- clouds that stay on the device, and their scoring (csrc/rbt_score.h) ----
+struct PCloud {
+  int n = 0, n_merged = 0, lg = 0; bool indexed = false;
+  DevBuf xyz, rgb, yuv, nrm, maps, scal; void* vol = nullptr;             // vol: the bit volume with the coarse level behind it; taken from / returned to the context's cache
+  RbtScoreCloud view() const {
+    uint32_t* m = maps.as<uint32_t>(); const size_t slots = (size_t)1 << lg;
+    return RbtScoreCloud{xyz.as<int16_t>(), rgb.as<uint8_t>(), nrm.as<int16_t>(), n, lg, (uint32_t*)vol, (uint32_t*)vol + (PCLOUD_VOL_BYTES - 4 * (size_t)RBT_SC_COARSE_WORDS) / 4, m, m + slots, m + 2 * slots, m + 6 * slots};
+  }
+};
+static_assert(PCLOUD_VOL_BYTES == ((size_t)1 << (3 * RBT_PCC_BITS - 3)) + 4 * (size_t)RBT_SC_COARSE_WORDS, "volume + coarse level");
+void pcloud_cache_trim(PCloudCache& cache) { for (void* v : cache.vols) rbtk::dev_free(v); cache.vols.clear(); }
+void pcloud_points(const PCloud* c, int* n_points, int* n_merged) { if (n_points) *n_points = c->n; if (n_merged) *n_merged = c->n_merged; }
+// The cloud's own volume and coarse words go back to zero and the clean volume to the cache; the maps and the point arrays go back to the device pool.
+void pcloud_release(PCloudCache& cache, PCloud* c) {
+  if (!c) return;
+  if (c->vol) {
+    bool clean = true;
+    if (c->indexed) { const RbtScoreCloud S = c->view(); rbtk::launch_sc_clear(&S); clean = rbtk::dev_sync() == 0; }
+    if (clean) cache.vols.push_back(c->vol); else rbtk::dev_free(c->vol);
+  }
+  delete c;
+}
+// xyz (and whatever else the cloud has) is on the device already: check, take a volume, build the index
+static int pcloud_index(std::string& err, PCloudCache& cache, PCloud* c) {
+  if (c->n > (1 << 26)) { err = "more than 2^26 points"; return RBT_ERR_PARAM; }
+  c->lg = lg_of(c->n);
+  const size_t slots = (size_t)1 << c->lg;
+  if (!c->scal.alloc(4 * RBT_SC_SCALARS) || !c->maps.alloc(4 * 7 * slots)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  uint32_t h[RBT_SC_SCALARS];
+  if (rbtk::dev_memset(c->scal.p, 0, sizeof(h))) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::launch_sc_check(c->xyz.as<int16_t>(), c->n, c->scal.as<uint32_t>());
+  if (rbtk::d2h(h, c->scal.p, sizeof(h)) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (h[RBT_SC_ERR]) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }       // nothing of a volume has been touched
+  if (!cache.vols.empty()) { c->vol = cache.vols.back(); cache.vols.pop_back(); }
+  else {
+    c->vol = rbtk::dev_alloc(PCLOUD_VOL_BYTES);
+    if (!c->vol) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    if (rbtk::dev_memset(c->vol, 0, PCLOUD_VOL_BYTES)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  }
+  uint32_t* m = c->maps.as<uint32_t>();
+  if (rbtk::dev_memset(m, 0, 4 * slots) | rbtk::dev_memset(m + slots, 0xFF, 4 * slots) | rbtk::dev_memset(m + 2 * slots, 0, 4 * 5 * slots)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  const RbtScoreCloud S = c->view();
+  c->indexed = true;
+  rbtk::launch_sc_index(&S, c->scal.as<uint32_t>());
+  if (rbtk::d2h(h, c->scal.p, sizeof(h)) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  c->n_merged = (int)h[RBT_SC_N_MERGED];
+  return RBT_OK;
+}
+int pcloud_upload(std::string& err, PCloudCache& cache, const int16_t* xyz, const uint8_t* rgb, const int16_t* nrm, int n, PCloud** out) {
+  *out = nullptr;
+  if (n <= 0) { err = "empty point cloud"; return RBT_ERR_PARAM; }
+  PCloud* c = new PCloud(); c->n = n;
+  int rc = RBT_OK;
+  if (!c->xyz.alloc(6 * (size_t)n) || (rgb && !c->rgb.alloc(3 * (size_t)n)) || (nrm && !c->nrm.alloc(6 * (size_t)n))) { err = "device allocation failed"; rc = RBT_ERR_NOMEM; }
+  else if (rbtk::h2d(c->xyz.p, xyz, 6 * (size_t)n) | (rgb ? rbtk::h2d(c->rgb.p, rgb, 3 * (size_t)n) : 0) | (nrm ? rbtk::h2d(c->nrm.p, nrm, 6 * (size_t)n) : 0)) { err = "device transfer failed"; rc = RBT_ERR_NO_DEVICE; }
+  else rc = pcloud_index(err, cache, c);
+  if (rc) { pcloud_release(cache, c); return rc; }
+  *out = c;
+  return RBT_OK;
+}
+int pcloud_from_maps(std::string& err, PCloudCache& cache, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
+                     const uint16_t* t0, const uint16_t* t1, int attr_bd, int filter, int attr_transfer, PCloud** out, rbt_cloud* host_copy, uint8_t** rgb, int* n_changed, double* stage_ms) {
+  *out = nullptr;
+  DevCloud dev; rbt_cloud counts;
+  int rc = reconstruct_impl(err, a, patches, n_patches, occ, d0, d1, geo_bd, t0, t1, attr_bd, host_copy ? host_copy : &counts, filter, rgb, stage_ms, attr_transfer, nullptr, n_changed, &dev, host_copy != nullptr);
+  if (rc) return rc;
+  const int n = (host_copy ? host_copy : &counts)->n_points;
+  if (n <= 0) { err = "empty point cloud"; return RBT_ERR_PARAM; }
+  PCloud* c = new PCloud(); c->n = n;
+  c->xyz.take(dev.xyz); c->yuv.take(dev.yuv); c->rgb.take(dev.rgb);
+  rc = pcloud_index(err, cache, c);
+  if (rc) { pcloud_release(cache, c); return rc; }
+  *out = c;
+  return RBT_OK;
+}
+int pcloud_score(std::string& err, const PCloud* a, const PCloud* b, int peak, int parts, rbt_frame_score* out) {
+  memset(out, 0, sizeof(*out));
+  // |colour error term| <= 2.55e6: the sum of 2^21 squares still fits 64 bits - rbt_color_metric refuses larger clouds, and so does the colour part here
+  const bool colours = a->rgb.p && b->rgb.p && a->n_merged <= (1 << 21) && b->n_merged <= (1 << 21);
+  const int can = RBT_SCORE_D1 | (a->nrm.p ? RBT_SCORE_D2 : 0) | (colours ? RBT_SCORE_COLOR : 0);
+  if (parts == 0) parts = can;
+  if (peak <= 0 || (parts & ~can)) {
+    err = parts & ~can & RBT_SCORE_D2 ? "D2 needs normals on the source" : parts & ~can & RBT_SCORE_COLOR ? "the colour part needs colours on both clouds and at most 2^21 merged points in each" : "bad peak or parts";
+    return RBT_ERR_PARAM;
+  }
+  const size_t na = (size_t)a->n, nb = (size_t)b->n, blocks = (std::max(na, nb) + RBT_SC_SUM - 1) / RBT_SC_SUM;
+  const bool d2 = (parts & RBT_SCORE_D2) != 0;
+  DevBuf dist, nrm_b, val, part, res;
+  if (!dist.alloc(4 * (na + nb)) || !res.alloc(8 * RBT_SC_RESULTS) || (d2 && (!nrm_b.alloc(28 * nb) || !val.alloc(8 * (na + nb)) || !part.alloc(16 * blocks)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::dev_memset(res.p, 0, 8 * RBT_SC_RESULTS) | (d2 ? rbtk::dev_memset(nrm_b.p, 0, 28 * nb) : 0)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  RbtScoreWork W; memset(&W, 0, sizeof(W));
+  W.dist_a = dist.as<uint32_t>(); W.dist_b = W.dist_a + na; W.res = res.as<unsigned long long>();
+  if (d2) { W.acc_b = nrm_b.as<long long>(); W.cnt_b = (int32_t*)(W.acc_b + 3 * nb); W.val_ab = val.as<double>(); W.val_ba = W.val_ab + na; W.part = part.as<double>(); }
+  const RbtScoreCloud A = a->view(), B = b->view();
+  rbtk::timer_begin(T_COL_DIST);             // the colour metric's distance timer: every call reads its timers before it returns
+  rbtk::launch_sc_score(&A, &B, parts, &W);
+  rbtk::timer_end(T_COL_DIST);
+  uint64_t h[RBT_SC_RESULTS];
+  if (rbtk::d2h(h, res.p, sizeof(h)) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  out->parts = parts | RBT_SCORE_D1; out->device_ms = rbtk::timer_ms(T_COL_DIST);
+  out->n_points_a = a->n; out->n_points_b = b->n; out->n_merged_a = a->n_merged; out->n_merged_b = b->n_merged;
+  const uint32_t* mx = (const uint32_t*)&h[RBT_SC_D1_MAX];
+  out->d1.n_a = a->n_merged; out->d1.n_b = b->n_merged; out->d1.sse_ab = h[RBT_SC_D1_AB]; out->d1.sse_ba = h[RBT_SC_D1_BA]; out->d1.max_ab = mx[0]; out->d1.max_ba = mx[1];
+  finish_geometry(&out->d1, peak);
+  if (d2) {
+    double v[4]; memcpy(v, &h[RBT_SC_D2_AB], sizeof(v));
+    out->d2.n_a = a->n_merged; out->d2.n_b = b->n_merged; out->d2.sse_ab = v[0]; out->d2.max_ab = v[1]; out->d2.sse_ba = v[2]; out->d2.max_ba = v[3];
+    finish_geometry(&out->d2, peak);
+  }
+  if (parts & RBT_SCORE_COLOR) {
+    out->color.n_a = a->n_merged; out->color.n_b = b->n_merged;
+    for (int c = 0; c < 3; c++) { out->color.sse_ab[c] = h[RBT_SC_COL_AB + c]; out->color.sse_ba[c] = h[RBT_SC_COL_BA + c]; }
+    finish_color(&out->color);
+  }
   return RBT_OK;
 }
 }  // namespace rbt

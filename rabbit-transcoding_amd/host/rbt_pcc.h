@@ -1,6 +1,7 @@
 // Verification stage: reconstruction of the point cloud from decoded maps and the D1 metric. See rbt_pcc.cpp.
 #pragma once
 #include <string>
+#include <vector>
 #include "../../include/rbt.h"
 namespace rbt {
 int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
@@ -17,4 +18,15 @@ int pcc_yuv16_to_rgb8(std::string& err, const uint16_t* yuv, int n, uint8_t* rgb
 int pcc_color_metric(std::string& err, const int16_t* a, const uint8_t* rgb_a, int na, const int16_t* b, const uint8_t* rgb_b, int nb, rbt_color_result* out, double* ms);
 int pcc_d1(std::string& err, const int16_t* a, int na, const int16_t* b, int nb, int peak, rbt_d1_result* out);
 int pcc_d2(std::string& err, const int16_t* a, const int16_t* normals_a, int na, const int16_t* b, int nb, int peak, rbt_d2_result* out);
+// clouds that stay on the device with their index, and their scoring (csrc/rbt_score.h; rbt_pcloud_*, rbt_score). A context keeps the clean volumes of released clouds.
+struct PCloud;
+enum : size_t { PCLOUD_VOL_BYTES = ((size_t)1 << 27) + ((size_t)1 << 18) };          // the 1024^3-bit volume and its coarse level (one bit per 8 x 8 x 8 block)
+struct PCloudCache { std::vector<void*> vols; size_t bytes() const { return vols.size() * PCLOUD_VOL_BYTES; } };
+int pcloud_upload(std::string& err, PCloudCache& cache, const int16_t* xyz, const uint8_t* rgb, const int16_t* nrm, int n, PCloud** out);
+int pcloud_from_maps(std::string& err, PCloudCache& cache, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
+                     const uint16_t* t0, const uint16_t* t1, int attr_bd, int filter, int attr_transfer, PCloud** out, rbt_cloud* host_copy, uint8_t** rgb, int* n_changed, double* stage_ms);
+void pcloud_points(const PCloud* c, int* n_points, int* n_merged);
+void pcloud_release(PCloudCache& cache, PCloud* c);
+void pcloud_cache_trim(PCloudCache& cache);
+int pcloud_score(std::string& err, const PCloud* a, const PCloud* b, int peak, int parts, rbt_frame_score* out);
 }
