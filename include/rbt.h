@@ -124,7 +124,14 @@ int rbt_transcode_gof(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, cons
  * RBT_ERR_BUSY while jobs are in flight): the library has 16 HIP streams (more hardware queues slow every queue down on
  * MI355X), so up to 4 jobs get four streams each, 5 get three, up to 8 two, up to 16 one (pipelines that share a stream run
  * their entropy decoding and their reconstruction in merged launches). rbt_submit_gof returns RBT_ERR_BUSY when that many
- * jobs are already in flight. */
+ * jobs are already in flight.
+ * Every shape above assumes that each of the 16 streams has a hardware queue of its own (streams that share a queue serialise). The HIP
+ * runtime has 4 unless GPU_MAX_HW_QUEUES says otherwise, and reads that once, when it initialises. The first rbt_create of a process
+ * therefore sets GPU_MAX_HW_QUEUES=16 before its first HIP call, over a value that is already there (RBT_HW_QUEUES=<1..32> chooses
+ * another count and, since GPU_MAX_HW_QUEUES is overwritten, is the only way to choose it for such a process; RBT_HW_QUEUES=4 gives the
+ * runtime's default back, fewer than 4 is accepted and untested). The library cannot change the count in a process that has used
+ * HIP before - a host application with HIP code of its own, a framework that selected its device first: such a process sets
+ * GPU_MAX_HW_QUEUES=16 in its own environment, or creates the context before its first HIP call. */
 #define RBT_MAX_JOBS 16
 typedef struct rbt_job rbt_job;
 int rbt_set_depth(rbt_ctx* ctx, int max_in_flight);

@@ -19,9 +19,20 @@ int dev_select(int device);               // makes an initialised device the cal
 // sub-bitstream pipeline, and the last one is the auxiliary stream of the longest pipeline.
 // Several GOFs can be in flight (rbt_submit_gof). Host code names streams by "lane" = job slot * 4 + pipeline (timers are kept
 // per lane); map_lane binds a lane to one of the 16 HIP streams. dev_init asks the HIP runtime for 16 hardware queues
-// (GPU_MAX_HW_QUEUES) when it is the first HIP user of the process. Measured on MI355X: with 24 / 32 queues a lone GOF takes
+// (GPU_MAX_HW_QUEUES, written over a value the environment holds) when it is the first HIP user of the process. Measured on MI355X: with 24 / 32 queues a lone GOF takes
 // 342 / 441 ms instead of 276 ms (the queues are time-sliced), so 16 it is; deeper pipelines give each job fewer streams.
 enum { RBT_AUX_STREAM = 3, RBT_STREAMS_PER_JOB = 4, RBT_JOB_SLOTS = 16, RBT_N_LANES = RBT_STREAMS_PER_JOB * RBT_JOB_SLOTS, RBT_N_STREAMS = 16 };
+// Hardware queues dev_init asks for: RBT_HW_QUEUES (`text` = its value, nullptr if unset) when that is an integer from 1 to 32, else one per HIP stream.
+// RBT_HW_QUEUES=4 gives the runtime's default back (the A/B switch of DESIGN.md 11); more than 32 is never asked for.
+// Since the request overwrites GPU_MAX_HW_QUEUES, RBT_HW_QUEUES is the only way to choose the count for a process whose first HIP user is this library. Counts below 4 are
+// accepted and untested (the runtime's own default is 4; every measurement of this project is at 4, 16, 24 or 32).
+enum { RBT_HW_QUEUES_DEFAULT = RBT_N_STREAMS, RBT_HW_QUEUES_MAX = 32 };
+inline int hw_queues_wanted(const char* text) {
+  if (!text || !*text) return RBT_HW_QUEUES_DEFAULT;
+  int v = 0;
+  for (const char* p = text; *p; p++) { if (*p < '0' || *p > '9') return RBT_HW_QUEUES_DEFAULT; v = v * 10 + (*p - '0'); if (v > RBT_HW_QUEUES_MAX) return RBT_HW_QUEUES_DEFAULT; }
+  return v >= 1 ? v : RBT_HW_QUEUES_DEFAULT;
+}
 void map_lane(int lane, int stream);
 void set_stream(int i);
 void stream_wait(int waiter, int signaller);

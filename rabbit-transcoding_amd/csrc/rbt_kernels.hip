@@ -41,12 +41,19 @@ hipStream_t current_stream() { return g_stream; }   // for rbt_kernels_parse.hip
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(t_err, sizeof t_err, "%s: %s", #x, hipGetErrorString(e_)); return -1; } } while (0)
 
 int dev_init(int device) {
-  // one hardware queue per HIP stream (default: 4 queues shared by all streams); only honoured before the runtime initialises
-  setenv("GPU_MAX_HW_QUEUES", "16", 0);
+  // One hardware queue per HIP stream (the runtime's default: 4 queues shared by all streams, and streams that share a queue serialise). The request is written OVER a value
+  // the environment already holds - a launcher's GPU_MAX_HW_QUEUES=4 used to win against it - before this library's first HIP call; RBT_HW_QUEUES (hw_queues_wanted) chooses
+  // another count. The runtime reads the variable once, when it initialises: in a process that used HIP before its first rbt_create (a host application with HIP code of its
+  // own, a torch process that selected its device first) the count is what that first use found, and nothing here can change it - such a process sets GPU_MAX_HW_QUEUES
+  // itself. Written once per process, by the first call, whatever becomes of that call: the runtime has read the variable by the end of it. The write is
+  // under g_devs_mu and comes before the first device exists; every other getenv of the library (dev_reserve_bytes, the host code's read-once switches) runs on behalf of
+  // a context, i.e. after it, so none can meet it.
+  std::lock_guard<std::mutex> lk(g_devs_mu);
+  static bool queues_asked = false;
+  if (!queues_asked) { char v[16]; snprintf(v, sizeof v, "%d", hw_queues_wanted(getenv("RBT_HW_QUEUES"))); setenv("GPU_MAX_HW_QUEUES", v, 1); queues_asked = true; }
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { snprintf(t_err, sizeof t_err, "no HIP device"); return -1; }
   if (device < 0 || device >= n || device >= RBT_MAX_DEVICES) { snprintf(t_err, sizeof t_err, "device %d out of range (%d devices)", device, n); return -1; }
-  std::lock_guard<std::mutex> lk(g_devs_mu);
   HIPCHK(hipSetDevice(device));
   if (!g_devs[device]) {
     Dev* d = new Dev(); d->id = device;
