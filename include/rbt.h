@@ -423,6 +423,46 @@ typedef struct {
 } rbt_sequence_score;
 int rbt_score_summary(const rbt_frame_score* frames, int n_frames, rbt_sequence_score* out);
 
+/* ---- normal estimation (csrc/rbt_normals.h) ----
+ * D2 needs normals on the source. Where a sequence comes without them, the reference's PccAppNormalGenerator makes them (PCCNormalsGenerator.cpp: a kd-tree query of the
+ * 16 nearest neighbours, a covariance matrix and a 3 x 3 eigen-decomposition per point, on the CPU). This is that stage on the index of a device cloud.
+ * Normals are computed on the merged cloud - one point per occupied voxel, as D1, D2 and colour see the cloud - and every point of a voxel receives its voxel's normal.
+ * For a voxel p:
+ *  1. Neighbours. N(p) = the min(k, number of occupied voxels) occupied voxels nearest to p, p itself included at distance 0 (the reference's query returns the query
+ *     point too), in the order (squared integer distance, voxel id ascending), voxel id = z << 20 | y << 10 | x. The reference depends on the order in which nanoflann
+ *     returns equidistant points; this rule is defined instead, in the spirit of the tie rules of rbt_d2 and rbt_transfer_colors. It uses the voxel id, not the point index:
+ *     the result does not depend on the order of the points, and for a cloud without duplicates the neighbour set is always one the reference could have produced. The
+ *     search is exact for any cloud inside 0..1023: no bounded radius, no refusal; empty space is skipped with the coarse level of the index.
+ *  2. Scatter matrix, exact: with m = |N(p)|, S = m * sum(q q^T) - sum(q) sum(q)^T over q in N(p): a symmetric 3 x 3 integer matrix, |entry| < 2^31 for m <= 32 and
+ *     coordinates <= 1023, and a positive multiple of the reference's covariance (PCCNormalsGenerator.cpp:84-101), so the eigenvectors are the same. It becomes double
+ *     only after the integer sums.
+ *  3. Eigenvector: the Jacobi iteration of PCCDiagonalize (PCCMath.h:505) restated in double - at most 24 rotations, pivot = the largest off-diagonal magnitude with the
+ *     reference's comparison order, stop when the pivot is exactly 0 or the rotation's cosine exactly 1 - then the reference's column choice on |D_ii|
+ *     (PCCNormalsGenerator.cpp:105-145): column 0 if strictly smallest, else column 1 if D11 < D22, else column 2. Restating the iteration, where another solver would do
+ *     for regular neighbourhoods, makes degenerate ones fall where the reference's fall: an isotropic S gives (0, 0, 1). Only + - * /, fabs and sqrt, each rounded on its
+ *     own (no contraction, no trigonometric call): the GPU and the serial host emulation return the same bits. m <= 1 gives the zero vector (:77, :83).
+ *  4. Orientation. RBT_NORMALS_ORIENT_VIEW_POINT (the default; default view point (0, 0, 0)): the normal is negated when normal . (view_point - p) < 0, evaluated in
+ *     double as :147 does. RBT_NORMALS_ORIENT_NONE: the eigenvector as computed. The reference's spanning-tree and cube-map strategies and its normal smoothing are serial
+ *     priority-queue walks; they are not built (RBT_ERR_UNSUPPORTED). D2 squares the projection on the normal, so the sign does not enter it directly. The normals handed to
+ *     the decoded cloud, however, are sums of source normals: opposite signs at the silhouette seen from the view point do matter there. That is what the view-point rule
+ *     gives and what the spanning tree would improve.
+ *  5. Output: Q14 per component, round(16384 * n) half away from zero, int16_t. */
+enum { RBT_NORMALS_ORIENT_NONE = 0, RBT_NORMALS_ORIENT_SPANNING_TREE = 1, RBT_NORMALS_ORIENT_VIEW_POINT = 2, RBT_NORMALS_ORIENT_CUBEMAP = 3 };
+typedef struct {
+  uint32_t struct_size;                  /* sizeof(rbt_normals_params): checked, so that a later field is told from a caller built against this layout */
+  int k;                                 /* neighbours, the point itself included: 0 = 16 (the reference's default), else 3..32 */
+  int orientation;                       /* RBT_NORMALS_ORIENT_* */
+  int32_t view_point[3];
+} rbt_normals_params;
+/* Gives a device cloud its normals - one from rbt_pcloud_from_maps too - in place of any it was uploaded with; the cloud then allows the D2 part of rbt_score as a source.
+ * The normals stay on the device; normals_q14 (3 per point, in point order; may be NULL) receives a copy. p == NULL: all defaults. *device_ms (may be NULL): device time
+ * between events around the estimation's kernels; index building, clears and read-back are outside, as for rbt_frame_score.device_ms.
+ * k outside {0, 3..32}, an unknown orientation, a wrong struct_size or a handle of another context: RBT_ERR_PARAM; orientation 1 or 3: RBT_ERR_UNSUPPORTED. A refused call
+ * leaves the cloud, and the normals it had, untouched. */
+int rbt_pcloud_estimate_normals(rbt_ctx* ctx, rbt_pcloud* cloud, const rbt_normals_params* p, int16_t* normals_q14, double* device_ms);
+/* The same stage for host arrays: upload, index, estimate, release. Limits and error codes of rbt_pcloud_upload, and the above. */
+int rbt_estimate_normals(rbt_ctx* ctx, const int16_t* xyz, int n, const rbt_normals_params* p, int16_t* normals_q14);
+
 #ifdef __cplusplus
 }
 #endif

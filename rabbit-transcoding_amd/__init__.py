@@ -172,6 +172,8 @@ def load(path=None):
     L.rbt_pcloud_release.argtypes = [C.c_void_p, C.c_void_p]
     L.rbt_pcloud_release.restype = None
     L.rbt_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(FrameScore)]
+    L.rbt_pcloud_estimate_normals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(NormalsParams), C.c_void_p, C.POINTER(C.c_double)]
+    L.rbt_estimate_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(NormalsParams), C.c_void_p]
     L.rbt_score_summary.argtypes = [C.POINTER(FrameScore), C.c_int, C.POINTER(SequenceScore)]
     L.rbt_v3c_index.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(V3CUnit)), C.POINTER(C.c_int)]
     L.rbt_v3c_write.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -287,6 +289,17 @@ def score_summary(frames, lib=None):
     return _result_dict(out)
 
 
+RBT_NORMALS_ORIENT_NONE, RBT_NORMALS_ORIENT_SPANNING_TREE, RBT_NORMALS_ORIENT_VIEW_POINT, RBT_NORMALS_ORIENT_CUBEMAP = range(4)
+
+
+class NormalsParams(C.Structure):
+    """rbt_normals_params; struct_size is filled in"""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_int), ("orientation", C.c_int), ("view_point", C.c_int32 * 3)]
+
+    def __init__(self, k=0, orientation=RBT_NORMALS_ORIENT_VIEW_POINT, view_point=(0, 0, 0)):
+        super().__init__(C.sizeof(NormalsParams), k, orientation, (C.c_int32 * 3)(*view_point))
+
+
 class PCloud:
     """rbt_pcloud: a point cloud on the device with its index; belongs to the context that made it. release() hands it back (its clean volume stays cached in the context)."""
 
@@ -298,6 +311,14 @@ class PCloud:
         n, m = C.c_int(), C.c_int()
         self.ctx._chk(self.ctx.L.rbt_pcloud_points(self.h, C.byref(n), C.byref(m)))
         return n.value, m.value
+
+    def estimate_normals(self, params=None, copy=True):
+        """rbt_pcloud_estimate_normals: the cloud gets normals of its own (params: NormalsParams or None = defaults) -> (normals int16 [n,3] in Q14, or None without
+        copy; device_ms)"""
+        out = np.empty((self.points()[0], 3), np.int16) if copy else None
+        ms = C.c_double()
+        self.ctx._chk(self.ctx.L.rbt_pcloud_estimate_normals(self.ctx.h, self.h, None if params is None else C.byref(params), None if out is None else out.ctypes.data, C.byref(ms)))
+        return out, ms.value
 
     def release(self):
         if self.h:
@@ -585,6 +606,13 @@ class Context:
         self.n_smoothed = c.n_points and c.n_smoothed
         self.L.rbt_free(rgb_p); self.L.rbt_cloud_free(C.byref(c))
         return cloud, (xyz, yuv, om, b2p, rgb)
+
+    def estimate_normals(self, xyz, params=None):
+        """rbt_estimate_normals: xyz int16 [n,3] -> normals int16 [n,3] in Q14 (params: NormalsParams or None = defaults)"""
+        a = np.ascontiguousarray(xyz, dtype=np.int16).reshape(-1, 3)
+        out = np.empty(a.shape, np.int16)
+        self._chk(self.L.rbt_estimate_normals(self.h, a.ctypes.data, a.shape[0], None if params is None else C.byref(params), out.ctypes.data))
+        return out
 
     def score(self, a, b, peak=1023, parts=0, raw=False):
         """rbt_score: a = the source PCloud, b = the decoded one; parts = RBT_SCORE_* wanted, 0 = all the clouds allow -> frame_score_dict, or the FrameScore itself (raw)"""

@@ -395,6 +395,40 @@ void rbt_pcloud_release(rbt_ctx* ctx, rbt_pcloud* cloud) {
     return;
   }
 }
+// the checked form of rbt_normals_params (NULL = all defaults)
+static int normals_params(std::string& err, const rbt_normals_params* p, int* k, int* orient, int32_t vp[3]) {
+  *k = 16; *orient = RBT_NORMALS_ORIENT_VIEW_POINT; vp[0] = vp[1] = vp[2] = 0;
+  if (!p) return RBT_OK;
+  if (p->struct_size != sizeof(rbt_normals_params)) { err = "rbt_normals_params.struct_size is not sizeof(rbt_normals_params)"; return RBT_ERR_PARAM; }
+  if (p->k != 0 && (p->k < 3 || p->k > 32)) { err = "k is 0 (= 16) or 3..32"; return RBT_ERR_PARAM; }
+  if (p->orientation < RBT_NORMALS_ORIENT_NONE || p->orientation > RBT_NORMALS_ORIENT_CUBEMAP) { err = "orientation is not one of RBT_NORMALS_ORIENT_*"; return RBT_ERR_PARAM; }
+  if (p->orientation == RBT_NORMALS_ORIENT_SPANNING_TREE || p->orientation == RBT_NORMALS_ORIENT_CUBEMAP) { err = "spanning-tree and cube-map orientation are not built"; return RBT_ERR_UNSUPPORTED; }
+  if (p->k) *k = p->k;
+  *orient = p->orientation; for (int i = 0; i < 3; i++) vp[i] = p->view_point[i];
+  return RBT_OK;
+}
+int rbt_pcloud_estimate_normals(rbt_ctx* ctx, rbt_pcloud* cloud, const rbt_normals_params* p, int16_t* normals_q14, double* device_ms) try {
+  if (!ctx) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  if (device_ms) *device_ms = 0;
+  if (!cloud_of(ctx, cloud)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
+  int k, orient; int32_t vp[3];
+  const int rc = normals_params(ctx->last_err, p, &k, &orient, vp);
+  return rc ? rc : rbt::pcloud_estimate_normals(ctx->last_err, cloud->cloud, k, orient, vp, normals_q14, device_ms);
+} RBT_CATCH
+int rbt_estimate_normals(rbt_ctx* ctx, const int16_t* xyz, int n, const rbt_normals_params* p, int16_t* normals_q14) try {
+  if (!ctx || !xyz || !normals_q14) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  int k, orient; int32_t vp[3];
+  int rc = normals_params(ctx->last_err, p, &k, &orient, vp);
+  if (rc) return rc;
+  rbt::PCloud* c = nullptr;
+  rc = rbt::pcloud_upload(ctx->last_err, ctx->cloud_cache, xyz, nullptr, nullptr, n, &c);
+  if (rc) return rc;
+  rc = rbt::pcloud_estimate_normals(ctx->last_err, c, k, orient, vp, normals_q14, nullptr);
+  rbt::pcloud_release(ctx->cloud_cache, c);
+  return rc;
+} RBT_CATCH
 int rbt_score(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int parts, rbt_frame_score* out) try {
   if (!ctx || !out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);

@@ -9,6 +9,7 @@
 #include "../csrc/rbt_pcc.h"
 #include "../csrc/rbt_color.h"
 #include "../csrc/rbt_score.h"
+#include "../csrc/rbt_normals.h"
 
 namespace rbt {
 namespace {
@@ -443,6 +444,23 @@ int pcloud_from_maps(std::string& err, PCloudCache& cache, const rbt_atlas_param
   rc = pcloud_index(err, cache, c);
   if (rc) { pcloud_release(cache, c); return rc; }
   *out = c;
+  return RBT_OK;
+}
+// The cloud keeps the normals it had until the new ones are complete: they are written to a buffer of their own, which replaces the old one after the kernels have run.
+int pcloud_estimate_normals(std::string& err, PCloud* c, int k, int orient, const int32_t view_point[3], int16_t* out, double* device_ms) {
+  const size_t n = (size_t)c->n, slots = (size_t)1 << c->lg;
+  DevBuf nrm, slot;
+  if (!nrm.alloc(6 * n) || !slot.alloc(8 * slots)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  RbtNormals N; memset(&N, 0, sizeof(N));
+  N.k = k < c->n_merged ? k : c->n_merged; N.orient = orient; for (int i = 0; i < 3; i++) N.vp[i] = view_point[i];
+  N.out = nrm.as<int16_t>(); N.slot = slot.as<int16_t>();
+  const RbtScoreCloud S = c->view();
+  rbtk::timer_begin(T_COL_DIST);             // as pcloud_score: every call reads its timers before it returns
+  rbtk::launch_nm_estimate(&S, &N);
+  rbtk::timer_end(T_COL_DIST);
+  if ((out ? rbtk::d2h(out, nrm.p, 6 * n) : 0) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (device_ms) *device_ms = rbtk::timer_ms(T_COL_DIST);
+  c->nrm.take(nrm);
   return RBT_OK;
 }
 int pcloud_score(std::string& err, const PCloud* a, const PCloud* b, int peak, int parts, rbt_frame_score* out) {

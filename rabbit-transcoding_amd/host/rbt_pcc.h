@@ -28,5 +28,7 @@ int pcloud_from_maps(std::string& err, PCloudCache& cache, const rbt_atlas_param
 void pcloud_points(const PCloud* c, int* n_points, int* n_merged);
 void pcloud_release(PCloudCache& cache, PCloud* c);
 void pcloud_cache_trim(PCloudCache& cache);
+// normals of the merged cloud (csrc/rbt_normals.h); k, orient and view_point are checked by the caller. out (3 per point) and device_ms may be null
+int pcloud_estimate_normals(std::string& err, PCloud* c, int k, int orient, const int32_t view_point[3], int16_t* out, double* device_ms);
 int pcloud_score(std::string& err, const PCloud* a, const PCloud* b, int peak, int parts, rbt_frame_score* out);
 }

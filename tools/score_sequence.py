@@ -13,6 +13,9 @@ Timing, per frame of the R3 pair, both routes in this one process, alternating, 
 Also recorded: rbt_frame_score.device_ms of (b) and the colour stage's rbt_color_stage_ms figure of (a) for the same pair. All samples are kept. "faster" holds for a
 frame when median(a) - median(b) exceeds the spread (max - min) of (a)'s samples. Prints the per-frame lines and the summaries, then one JSON line; --out also writes it.
 
+--estimate-normals scores D2 a second time with source normals estimated by rbt_pcloud_estimate_normals (k = 16, oriented towards the origin) beside the projection-axis
+normals: per frame "d2_estimated_db" and the estimation's device time, and the sequence summary under "<pair>_estimated_normals". Without the option nothing changes.
+
     python tools/score_sequence.py --out profiles/score_sequence.json
 """
 import argparse
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--frames", type=int, default=4, help="point-cloud frames 0..n-1 (at most 4: the GOF's base atlases)")
     ap.add_argument("--time-frames", type=int, default=4, help="how many of them the two routes are timed on")
     ap.add_argument("--samples", type=int, default=5)
+    ap.add_argument("--estimate-normals", action="store_true", help="also score D2 with source normals estimated on the GPU")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import rbt_lib
@@ -60,17 +64,26 @@ def main():
         xyz, nrm = synth.source_normals(R, ctx.reconstruct, w, h, 1051 + k, m["occ_full"], m["geo"])
         assert np.array_equal(xyz, c[0])
         source.append((c[0], c[4], nrm)); handles.append(ctx.pcloud_upload(c[0], c[4], nrm))
+    estimated, estimate_ms = [], []
+    if args.estimate_normals:
+        for sx, srgb, _ in source:
+            hn = ctx.pcloud_upload(sx, srgb); estimate_ms.append(hn.estimate_normals(copy=False)[1]); estimated.append(hn)
 
     scores, summaries = {}, {}
     for name in streams:
-        raw = []
+        raw, raw_est = [], []
         for k in range(nfr):
             hb = ctx.pcloud_from_maps(*decoded[name][k], attr_transfer=1)
-            raw.append(ctx.score(handles[k], hb, raw=True)); hb.release()
+            raw.append(ctx.score(handles[k], hb, raw=True))
+            if estimated: raw_est.append(ctx.score(estimated[k], hb, raw=True))
+            hb.release()
         per = [R.frame_score_dict(s) for s in raw]
         scores[name + "_vs_source"] = [{"frame": k, "points": [s["n_points_a"], s["n_points_b"]], "merged": [s["n_merged_a"], s["n_merged_b"]], "d1_db": round(s["d1"]["psnr"], 4),
                                         "d2_db": round(s["d2"]["psnr"], 4), "yuv_db": [round(x, 4) for x in s["color"]["psnr"]], "device_ms": round(s["device_ms"], 4)} for k, s in enumerate(per)]
         summaries[name + "_vs_source"] = R.score_summary(raw)
+        for k, e in enumerate(raw_est):
+            scores[name + "_vs_source"][k].update({"d2_estimated_db": round(e.d2.psnr, 4), "estimate_normals_device_ms": round(estimate_ms[k], 4)})
+        if raw_est: summaries[name + "_vs_source_estimated_normals"] = R.score_summary(raw_est)
         for line in scores[name + "_vs_source"]: print(name, line)
         print(name, "summary", summaries[name + "_vs_source"])
 
@@ -96,7 +109,7 @@ def main():
                        "host_arrays_spread_ms": round(spread, 4), "ratio_host_arrays_over_device_clouds": round(med["host_arrays_ms"] / med["device_clouds_ms"], 3),
                        "faster_by_more_than_the_spread": bool(med["host_arrays_ms"] - med["device_clouds_ms"] > spread)})
         print("timing", timing[-1]["frame"], timing[-1]["median_ms"], "spread", timing[-1]["host_arrays_spread_ms"], "ratio", timing[-1]["ratio_host_arrays_over_device_clouds"])
-    for hd in handles: hd.release()
+    for hd in handles + estimated: hd.release()
     line = {"tool": "score_sequence", "size": [w, h], "frames": nfr, "scores": scores, "summary": summaries, "timing_r3_vs_source": timing,
             "timing_note": "host clock around calls that end in a synchronise, both routes alternating in one process, one warm-up of each, then the samples; host_arrays: "
                            "reconstruct_decoded to the host, then d1 + d2 + color_metric; device_clouds: pcloud_from_maps + score against the source handle uploaded beforehand + "
