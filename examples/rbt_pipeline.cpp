@@ -5,6 +5,9 @@
 //   rbt_pipeline --v3c <in.bin> <out.bin> [depth] [geometryQP] [attributeQP] [occupancyPrecision]
 //       the file-level form: a V3C sample stream in, a V3C sample stream out (rbt_transcode_v3c = the loop of PccAppTranscoder.cpp:277-349), then the
 //       PCCBitstreamStat-style totals of both files (rbt_v3c_stats)
+//       [--geometry-kbps K] [--attribute-kbps K] [--pictures-per-second F] anywhere behind --v3c: the geometry / attribute video is transcoded to that bit rate instead of
+//       at its QP (rbt_transcode_v3c_rate: a budget of K * 1000 / F bits per picture for every GOF's unit; F defaults to 60, two maps of 30 point-cloud frames a second),
+//       and the QP every GOF ended at is printed
 //
 // File format (little endian, test harness only): u32 n_gofs, then per GOF three sub-bitstreams in the order occupancy, geometry,
 // attribute, each as u32 size + Annex-B bytes. The output file has the same layout with the re-encoded streams.
@@ -31,6 +34,15 @@ static bool read_all(const char* path, std::vector<Gof>& gofs) {
 }
 
 static int v3c_main(int argc, char** argv) {
+  double geo_kbps = 0, attr_kbps = 0, pps = 60;
+  { int k = 2;                // the rate options out of the argument list, the positional arguments stay where they were
+    for (int i = 2; i < argc; i++) {
+      double* v = !strcmp(argv[i], "--geometry-kbps") ? &geo_kbps : !strcmp(argv[i], "--attribute-kbps") ? &attr_kbps : !strcmp(argv[i], "--pictures-per-second") ? &pps : nullptr;
+      if (v && i + 1 < argc) *v = atof(argv[++i]); else argv[k++] = argv[i];
+    }
+    argc = k; }
+  if (geo_kbps < 0 || attr_kbps < 0 || pps <= 0) { fprintf(stderr, "bit rates must not be negative and --pictures-per-second must be positive\n"); return 2; }
+  const uint32_t geo_bits = (uint32_t)(geo_kbps * 1000.0 / pps + 0.5), attr_bits = (uint32_t)(attr_kbps * 1000.0 / pps + 0.5);
   if (argc < 4) { fprintf(stderr, "usage: %s --v3c in.bin out.bin [depth] [geometryQP] [attributeQP] [occupancyPrecision]\n", argv[0]); return 2; }
   const int depth = argc > 4 ? atoi(argv[4]) : 8;
   rbt_v3c_params vp; memset(&vp, 0, sizeof(vp));
@@ -45,8 +57,19 @@ static int v3c_main(int argc, char** argv) {
   int rc = rbt_create(&ctx, 0, 0, 1);
   if (rc != RBT_OK) { fprintf(stderr, "rbt_create: %s\n", rbt_strerror(rc)); return 1; }
   uint8_t* out = nullptr; size_t n = 0;
-  if ((rc = rbt_set_depth(ctx, depth)) == RBT_OK) rc = rbt_transcode_v3c(ctx, in.data(), in.size(), &vp, &out, &n);
+  rbt_rate_result* per_gof = nullptr;
+  if ((rc = rbt_set_depth(ctx, depth)) == RBT_OK)
+    rc = geo_bits || attr_bits ? rbt_transcode_v3c_rate(ctx, in.data(), in.size(), &vp, geo_bits, attr_bits, &out, &n, &per_gof) : rbt_transcode_v3c(ctx, in.data(), in.size(), &vp, &out, &n);
   if (rc != RBT_OK) { fprintf(stderr, "rbt_transcode_v3c: %s %s\n", rbt_strerror(rc), rbt_last_error(ctx)); rbt_destroy(ctx); return 1; }
+  if (per_gof) {
+    rbt_v3c_stat st;
+    if (rbt_v3c_stats(in.data(), in.size(), &st) == RBT_OK) for (int g = 0; g < st.n_gofs; g++) for (int t = 0; t < 2; t++) {
+      const rbt_rate_result& r = per_gof[2 * g + t];
+      if ((t ? attr_bits : geo_bits) && r.n_encodes) printf("GOF %d %s: QP %d (estimate %d), %llu B, budget %s, %d encodes\n", g, t ? "attribute" : "geometry", r.qp, r.qp_estimate,
+                                                            (unsigned long long)r.bytes, r.met ? "met" : "missed", r.n_encodes);
+    }
+    rbt_free(per_gof);
+  }
   rbt_destroy(ctx);
   f = fopen(argv[3], "wb"); if (!f) return 2;
   fwrite(out, 1, n, f); fclose(f);

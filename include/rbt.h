@@ -161,6 +161,57 @@ int rbt_wait_gof(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out
  * numbers of streams per job), so that the old shapes do not crowd the 288 GB. RBT_ERR_BUSY while jobs are in flight on the device. */
 int rbt_trim(rbt_ctx* ctx);
 
+/* ---- transcoding to a byte budget (csrc/rbt_rate.h) ----
+ * rbt_submit_gof codes every entry at the QP the caller names. Here an entry may name a budget instead: the library decodes the input once, counts on the GPU what the
+ * decoder left in device memory (the level census), forms a first guess of the QP on the host and closes the loop on the true sizes of trial encodes of the still-resident
+ * decoded pictures. Nothing is decoded twice.
+ *
+ * 1. Level census. Per decoded picture uint32 hist[3][53], one histogram per plane (Y, Cb, Cr). A coefficient level l != 0 of plane c at sample (x, y) has the input QP
+ *    qin = QpY of the 4x4 luma unit that covers it (chroma: the unit that covers luma sample (2x, 2y); QpY for all three planes, on both sides - a model), clamped to 0..51.
+ *    Units coded with cu_transquant_bypass hold residual samples, not levels, and are left out. With LS = {40, 45, 51, 57, 64, 72}, G = {26214, 23302, 20560, 18396, 16384, 14564}
+ *    and m = |l| * LS[qin % 6] * 2^(qin / 6) (|-32768| = 32768), l SURVIVES output QP q when 3 * m * G[q % 6] >= 2^(21 + q / 6): the requantised level is at least 2 / 3.
+ *    64-bit integers (46 bits at most); monotone in q. The bin of l is the number of q in 0..51 it survives (0..52; a level of 1 lands in bin qin + 4), and hist[c][b]
+ *    counts the levels of plane c with bin b.
+ * 2. Estimate. Output picture k of a geometry / attribute stream is an I picture coded at max(0, q - 3) for even k and a P picture coded at q for odd k; q_k is that QP.
+ *    nz_k(q') = sum over the planes of the bins b > q'; N0_k = the sum of all bins; B_k = the bytes of the VCL NAL units of input picture k as they stand in the Annex-B
+ *    input (start codes and trailing zero bytes excluded, emulation prevention bytes included; a picture starts at first_slice_segment_in_pic_flag).
+ *    E(q) = sum over k of floor(B_k * nz_k(q_k) / max(1, N0_k)), in 64 bits: the input calibrates itself through its own bytes per non-zero level, there is no tuned constant.
+ * 3. Walk. s(q) = the size of the entry's output from rbt_transcode_gof with qp = q and everything else equal; T = target_bytes, the budget of the WHOLE output stream
+ *    (parameter sets, SEIs and start codes included); lo = qp_min, hi = qp_max (0 = 51), 0 <= lo <= hi <= 51.
+ *      qe = the lowest q in [lo, hi] with E(q) <= T, or hi if there is none.
+ *      s(qe) <= T:  q* starts at qe and goes down while q* > lo and s(q* - 1) <= T; met = 1.
+ *      otherwise:   q* starts at qe and goes up while q* < hi and s(q*) > T; met = (s(q*) <= T).
+ *    s is NOT monotone in q - the 192x128 geometry maps of the tests give 368, 369, 369 bytes at QP 31, 32, 33 - so "the lowest QP that fits" is not defined by bisection; the
+ *    walk is the definition, and it says where it starts. A budget that even hi misses is no error: the stream at hi comes back with met = 0 and RBT_OK. The returned stream is
+ *    byte for byte rbt_transcode_gof's at qp = q*. The result depends on s and E alone, not on how the library batches its trial encodes (qe - 1, qe, qe + 1 first, then two at a
+ *    time in the walk's direction): n_encodes <= |q* - qe| + 4.
+ * target_bytes 0: the entry is coded at params[i].qp exactly as rbt_submit_gof codes it. RBT_ERR_PARAM (reason in rbt_last_error; nothing is submitted and the context stays
+ * usable): a target on an occupancy entry; a target on an entry with occupancy_rd (left out on purpose: the census would have to know the occupancy map); struct_size that is
+ * not sizeof(rbt_rate_target); a bad range. verify_md5, md5_sei, preset, log2_ctb, the slice structure and any job depth work as in the constant-QP path.
+ * Submit enqueues the decoders and, behind each targeted stream's last filter, the census; the wait half reads the histograms back (3 x 53 words a picture), forms qe and runs
+ * the trial encodes in rounds on the job's streams, one entry's rounds after the other's, while the decoders of the other jobs in flight keep the GPU busy.
+ * rbt_job_memory counts the arenas of the first round (three trial encodes per targeted entry). */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(rbt_rate_target): checked */
+  uint64_t target_bytes;     /* 0 = constant QP (params[i].qp) */
+  int qp_min, qp_max;        /* the walk's range; qp_max 0 = 51 */
+} rbt_rate_target;
+typedef struct {
+  int qp, qp_estimate, met, n_encodes;   /* q*, qe, met, trial encodes run for the entry (constant-QP entries: params[i].qp twice, 1, 1) */
+  uint64_t bytes, estimate_bytes;        /* s(q*), E(qe) (constant-QP entries: the output size, 0) */
+} rbt_rate_result;
+int rbt_submit_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_rate_target* targets, rbt_job** job);
+int rbt_wait_gof_rate(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results);   /* results: n entries; a job of rbt_submit_gof may be collected here too */
+int rbt_transcode_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_rate_target* targets,
+                           uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results);   /* submit + wait */
+/* The census kernel on host arrays (tests): three planes of int16 levels (w x h, then two of w/2 x h/2; w, h multiples of 8, at most 8192), QpY and the pm byte
+ * (bit 2 = cu_transquant_bypass) per 4x4 luma unit, (w / 4) x (h / 4) each -> hist[3][53]. */
+int rbt_level_census(rbt_ctx* ctx, const int16_t* y, const int16_t* cb, const int16_t* cr, int w, int h, const int8_t* qp4, const uint8_t* pm4, uint32_t* hist);
+/* Decodes a geometry / attribute stream, runs the census and returns what the walk starts from: per picture the histogram (hist: n_pictures x 3 x 53) and B_k
+ * (picture_bytes), and E(q) for q = 0..51. The arrays are malloc'd (rbt_free). census_ms: device time between events around the census kernel. */
+typedef struct { int n_pictures; uint32_t* hist; uint64_t* picture_bytes; uint64_t estimate[52]; double census_ms; } rbt_rate_table;
+int rbt_rate_estimate(rbt_ctx* ctx, const uint8_t* annexb, size_t n, int video_type, rbt_rate_table* out);
+
 /* The two halves exposed on their own (SURVEY.md 8(b) alternative seam; used by the parity tests).
  * Picture sizes: any even width / height. Sizes that are not multiples of 8 (all-intra) / 16 (gop 2) are coded padded with a
  * conformance window in the SPS (as libx265 does for the reference); rbt_decode returns the cropped pictures. */
@@ -301,6 +352,14 @@ int rbt_transcode_v3c(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_p
  * writer does not know yet: forcedSsvhUnitSizePrecisionBytes_ = 4 is what fits every file). A non-zero return of the sink ends the walk (RBT_ERR_PARAM; jobs in flight are drained). */
 typedef int (*rbt_v3c_sink)(void* user, int gof, int n_units, const uint8_t* const* unit, const size_t* unit_size);
 int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt_v3c_sink sink, void* user);
+
+/* rbt_transcode_v3c's walk with byte budgets (rbt_submit_gof_rate / rbt_wait_gof_rate, above): the budget of a GOF's geometry / attribute unit is
+ * ceil(bits_per_picture x pictures in that unit / 8) bytes of Annex-B, walked over the QPs 0..51; a value of 0 means constant QP (geometry_qp / attribute_qp) for that type, and
+ * with both 0 the output is rbt_transcode_v3c's. rbt_v3c_params has no size field and is not changed. *per_gof (may be NULL; malloc'd, rbt_free): two results per GOF of the input
+ * (rbt_v3c_stat.n_gofs), geometry then attribute, zeros for a GOF this context does not own or a unit it does not have. Multi-GPU ownership and the memory-bounded depth are the
+ * walk's. Any rate target together with occupancy_rd: RBT_ERR_PARAM. */
+int rbt_transcode_v3c_rate(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, uint32_t geometry_bits_per_picture, uint32_t attribute_bits_per_picture,
+                           uint8_t** out, size_t* n_out, rbt_rate_result** per_gof);
 
 /* ---- colour half of the metric: 4:4:4 up-conversion, RGB, colour PSNR (csrc/rbt_color.h) ----
  * Planar 4:2:0 pictures (samples of bit_depth 8 or 10 in uint16_t) -> n_frames x 3 planes of width x height 16-bit samples, as the decoder converts an attribute video

@@ -114,6 +114,24 @@ class V3CStat(C.Structure):
                [(n, C.c_uint64) for n in ("occupancy_video", "geometry_video", "geometry_aux_video", "attribute_video", "attribute_aux_video", "total_metadata", "total_geometry", "total_attribute", "total")]
 
 
+class RateTarget(C.Structure):
+    """rbt_rate_target; struct_size is filled in. target_bytes 0 = constant QP, qp_max 0 = 51"""
+    _fields_ = [("struct_size", C.c_uint32), ("target_bytes", C.c_uint64), ("qp_min", C.c_int), ("qp_max", C.c_int)]
+
+    def __init__(self, target_bytes=0, qp_min=0, qp_max=0):
+        super().__init__(C.sizeof(RateTarget), target_bytes, qp_min, qp_max)
+
+
+class RateResult(C.Structure):
+    """rbt_rate_result: q*, the estimate it started from, met, trial encodes, s(q*), E(estimate)"""
+    _fields_ = [("qp", C.c_int), ("qp_estimate", C.c_int), ("met", C.c_int), ("n_encodes", C.c_int), ("bytes", C.c_uint64), ("estimate_bytes", C.c_uint64)]
+
+
+class RateTable(C.Structure):
+    """rbt_rate_table"""
+    _fields_ = [("n_pictures", C.c_int), ("hist", C.POINTER(C.c_uint32)), ("picture_bytes", C.POINTER(C.c_uint64)), ("estimate", C.c_uint64 * 52), ("census_ms", C.c_double)]
+
+
 V3C_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))   # rbt_v3c_sink
 RBT_V3C_VPS, RBT_V3C_AD, RBT_V3C_OVD, RBT_V3C_GVD, RBT_V3C_AVD = range(5)
 
@@ -182,6 +200,13 @@ def load(path=None):
     L.rbt_job_memory.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
     L.rbt_transcode_v3c_stream.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), V3C_SINK, C.c_void_p]
     L.rbt_transcode_v3c.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    L.rbt_submit_gof_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(RateTarget), C.POINTER(C.c_void_p)]
+    L.rbt_wait_gof_rate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(RateResult)]
+    L.rbt_transcode_gof_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(RateTarget), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                         C.POINTER(RateResult)]
+    L.rbt_level_census.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rbt_rate_estimate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(RateTable)]
+    L.rbt_transcode_v3c_rate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(RateResult))]
     return L
 
 
@@ -450,6 +475,79 @@ class Context:
             res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
             self.L.rbt_free(outs[i])
         return res
+
+    def submit_gof_rate(self, streams, params, targets):
+        """rbt_submit_gof_rate: submit_gof with one RateTarget per entry (target_bytes 0 = constant QP); returns a job for wait_gof_rate"""
+        k = len(streams)
+        ins = (C.c_char_p * k)(*streams)
+        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
+        ps = (StreamParams * k)(*params)
+        ts = (RateTarget * k)(*targets)
+        job = C.c_void_p()
+        self._chk(self.L.rbt_submit_gof_rate(self.h, k, ins, sizes, ps, ts, C.byref(job)))
+        return (job, k)
+
+    def wait_gof_rate(self, job):
+        """rbt_wait_gof_rate -> ([stream bytes, ...], [result dict, ...])"""
+        h, k = job
+        outs = (C.c_void_p * k)()
+        ns = (C.c_size_t * k)()
+        rs = (RateResult * k)()
+        self._chk(self.L.rbt_wait_gof_rate(self.h, h, outs, ns, rs))
+        res = []
+        for i in range(k):
+            res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
+            self.L.rbt_free(outs[i])
+        return res, [_result_dict(r) for r in rs]
+
+    def transcode_gof_rate(self, streams, params, targets):
+        """rbt_transcode_gof_rate: submit + wait"""
+        k = len(streams)
+        ins = (C.c_char_p * k)(*streams)
+        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
+        ps = (StreamParams * k)(*params)
+        ts = (RateTarget * k)(*targets)
+        outs = (C.c_void_p * k)()
+        ns = (C.c_size_t * k)()
+        rs = (RateResult * k)()
+        self._chk(self.L.rbt_transcode_gof_rate(self.h, k, ins, sizes, ps, ts, outs, ns, rs))
+        res = []
+        for i in range(k):
+            res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
+            self.L.rbt_free(outs[i])
+        return res, [_result_dict(r) for r in rs]
+
+    def level_census(self, y, cb, cr, qp4, pm4):
+        """rbt_level_census: int16 planes y [h, w], cb / cr [h/2, w/2], int8 qp4 and uint8 pm4 [h/4, w/4] -> uint32 [3, 53]"""
+        y = np.ascontiguousarray(y, dtype=np.int16); cb = np.ascontiguousarray(cb, dtype=np.int16); cr = np.ascontiguousarray(cr, dtype=np.int16)
+        qp4 = np.ascontiguousarray(qp4, dtype=np.int8); pm4 = np.ascontiguousarray(pm4, dtype=np.uint8)
+        h, w = y.shape
+        if cb.shape != (h // 2, w // 2) or cr.shape != cb.shape or qp4.shape != (h // 4, w // 4) or pm4.shape != qp4.shape:
+            raise ValueError("plane and map shapes do not belong to one picture")
+        out = np.zeros((3, 53), np.uint32)
+        self._chk(self.L.rbt_level_census(self.h, y.ctypes.data, cb.ctypes.data, cr.ctypes.data, w, h, qp4.ctypes.data, pm4.ctypes.data, out.ctypes.data))
+        return out
+
+    def rate_estimate(self, stream: bytes, video_type=RBT_VIDEO_GEOMETRY):
+        """rbt_rate_estimate -> {"hist": uint32 [n, 3, 53], "picture_bytes": uint64 [n], "estimate": uint64 [52], "census_ms": float}"""
+        t = RateTable()
+        self._chk(self.L.rbt_rate_estimate(self.h, stream, len(stream), video_type, C.byref(t)))
+        n = t.n_pictures
+        out = {"hist": np.ctypeslib.as_array(t.hist, shape=(n, 3, 53)).copy(), "picture_bytes": np.ctypeslib.as_array(t.picture_bytes, shape=(n,)).copy(),
+               "estimate": np.array(list(t.estimate), np.uint64), "census_ms": t.census_ms}
+        self.L.rbt_free(t.hist); self.L.rbt_free(t.picture_bytes)
+        return out
+
+    def transcode_v3c_rate(self, data: bytes, geometry_qp, attribute_qp, geometry_bits_per_picture=0, attribute_bits_per_picture=0, occupancy_precision=4, forced_precision_bytes=0, log2_ctb=5,
+                           rows_per_slice=-1, md5_sei=0, verify_md5=0, gofs_per_job=1, occupancy_rd=0, preset=0):
+        """rbt_transcode_v3c_rate -> (sample stream, [(geometry result, attribute result) per GOF of the input])"""
+        p = V3CParams(occupancy_precision, geometry_qp, attribute_qp, forced_precision_bytes, log2_ctb, rows_per_slice, md5_sei, verify_md5, gofs_per_job, occupancy_rd, preset)
+        out, n, rs = C.c_void_p(), C.c_size_t(), C.POINTER(RateResult)()
+        self._chk(self.L.rbt_transcode_v3c_rate(self.h, data, len(data), C.byref(p), geometry_bits_per_picture, attribute_bits_per_picture, C.byref(out), C.byref(n), C.byref(rs)))
+        n_gofs = v3c_stats(data, self.L)["n_gofs"]
+        per = [(_result_dict(rs[2 * g]), _result_dict(rs[2 * g + 1])) for g in range(n_gofs)]
+        self.L.rbt_free(rs)
+        return self._take(out, n), per
 
     def or_pool(self, plane, factor=2):
         plane = np.ascontiguousarray(plane, dtype=np.uint16)

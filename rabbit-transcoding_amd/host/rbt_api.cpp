@@ -138,7 +138,7 @@ int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t
   return RBT_OK;
 } RBT_CATCH
 
-static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule);
+static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets = nullptr);
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
 int rbt_transcode_substream(rbt_ctx* ctx, const uint8_t* annexb_in, size_t n_in, const rbt_stream_params* p, uint8_t** annexb_out, size_t* n_out) try {
   if (!ctx || !annexb_in || !p || !annexb_out || !n_out) return RBT_ERR_PARAM;
@@ -155,15 +155,29 @@ int rbt_transcode_gof(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, cons
   return rbt_wait_gof(ctx, job, annexb_out, n_out);
 } RBT_CATCH
 int rbt_submit_gof(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job) try { return submit(ctx, n, annexb_in, n_in, p, job, true); } RBT_CATCH
-static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule) {
+// the refusals of rbt_submit_gof_rate: nothing has been submitted when one of them fires
+static int check_targets(std::string& err, int n, const rbt_stream_params* p, const rbt_rate_target* t) {
+  for (int i = 0; i < n; i++) {
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    if (t[i].struct_size != sizeof(rbt_rate_target)) { err = who + "rbt_rate_target.struct_size is not sizeof(rbt_rate_target)"; return RBT_ERR_PARAM; }
+    if (!t[i].target_bytes) continue;
+    if (p[i].video_type == RBT_VIDEO_OCCUPANCY) { err = who + "an occupancy stream is coded losslessly and takes no rate target"; return RBT_ERR_PARAM; }
+    if (p[i].occupancy_rd) { err = who + "a rate target cannot be combined with occupancy_rd"; return RBT_ERR_PARAM; }
+    const int lo = t[i].qp_min, hi = t[i].qp_max ? t[i].qp_max : 51;
+    if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
+  }
+  return RBT_OK;
+}
+static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
   RBT_ENTER(ctx);
+  if (targets) if (int rc = check_targets(ctx->last_err, n, p, targets)) return rc;
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
-  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule), ctx};
+  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets), ctx};
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -224,15 +238,45 @@ int rbt_trim(rbt_ctx* ctx) try {
   rbtk::dev_release_pool();
   return RBT_OK;
 } RBT_CATCH
-int rbt_wait_gof(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out) try {
+static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results) {
   if (!ctx || !job || !annexb_out || !n_out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   int slot = -1;
   for (int s = 0; s < RBT_MAX_JOBS; s++) if (D.jobs[s] == job) slot = s;
   if (slot < 0 || job->owner != ctx) return RBT_ERR_PARAM;
-  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out);
+  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results);
   D.jobs[slot] = nullptr; delete job;
   return rc;
+}
+int rbt_wait_gof(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out) try { return wait(ctx, job, annexb_out, n_out, nullptr); } RBT_CATCH
+// ---- transcoding to a byte budget ----
+int rbt_submit_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_rate_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  return submit(ctx, n, annexb_in, n_in, p, job, true, targets);
+} RBT_CATCH
+int rbt_wait_gof_rate(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  return wait(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
+int rbt_transcode_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_rate_target* targets,
+                           uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results) try {
+  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_rate(ctx, n, annexb_in, n_in, p, targets, &job);
+  if (rc) return rc;
+  return rbt_wait_gof_rate(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
+int rbt_level_census(rbt_ctx* ctx, const int16_t* y, const int16_t* cb, const int16_t* cr, int w, int h, const int8_t* qp4, const uint8_t* pm4, uint32_t* hist) try {
+  if (!ctx || !y || !cb || !cr || !qp4 || !pm4 || !hist) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  return rbt::level_census_host(ctx->last_err, y, cb, cr, w, h, qp4, pm4, hist);
+} RBT_CATCH
+int rbt_rate_estimate(rbt_ctx* ctx, const uint8_t* annexb, size_t n, int video_type, rbt_rate_table* out) try {
+  if (!ctx || !annexb || !out) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  memset(out, 0, sizeof(*out));
+  if (video_type == RBT_VIDEO_OCCUPANCY) { ctx->last_err = "an occupancy stream is coded losslessly: there is no rate estimate for it"; return RBT_ERR_PARAM; }
+  return rbt::rate_estimate(ctx->last_err, annexb, n, out);
 } RBT_CATCH
 int rbt_encode(rbt_ctx* ctx, const uint16_t* yuv, int width, int height, int bit_depth, int n_frames, int qp, int gop, int lossless,
                int log2_ctb, int ctb_rows_per_slice, int md5_sei, uint8_t** annexb_out, size_t* n_out) try {

@@ -8,12 +8,14 @@
 #include "../../include/rbt.h"
 #include "../csrc/rbt_kernels.h"
 #include "../csrc/rbt_hash.h"
+#include "../csrc/rbt_rate.h"
 #include "rbt_hls.h"
 
 namespace rbt {
 
 struct StreamIn { const uint8_t* p; size_t n; };
-struct FrameInfo { int stream; int nal_type; int hash_kind; uint8_t hash[48]; bool sao; };   // hash_kind: RBT_HASH_* of the picture's hash SEI (0: none), hash: parse_hash_sei
+struct FrameInfo { int stream; int nal_type; int hash_kind; uint8_t hash[48]; bool sao; uint64_t vcl_bytes; };   // hash_kind: RBT_HASH_* of the picture's hash SEI (0: none), hash: parse_hash_sei;
+// vcl_bytes: the picture's VCL NAL units as they stand in the input (start codes excluded, emulation prevention bytes included): B_k of the rate estimate
 
 // Decoded picture hashes of pictures in device memory (csrc/rbt_hash.h). add() the pictures, upload() before the first kernel of the stream
 // (one copy: the picture table, the per-class lists and the zeroed state, results and counters), launch() behind the kernels that make the
@@ -32,7 +34,22 @@ struct HashSet {
   ~HashSet() { rbtk::dev_free(d); }
 };
 
-enum { T_PARSE = 0, T_RECON = 1, T_FILTER = 2, T_ANALYSE = 3, T_ENCODE = 4, T_ENTROPY = 5, T_ALL = 6, T_POOL = 7, T_INTER = 8, T_ENTROPY_I = 9, T_COUNT = 10 };
+// Level census of decoded pictures in device memory (csrc/rbt_rate.h), used like HashSet: add() the pictures, upload() before the first kernel of the stream (one copy: the
+// picture table and the zeroed histograms), launch() behind the kernels that leave the levels and the per-unit QPs (and before an encoder that shares the decoder's arena
+// writes there), fetch() once the stream has got there: RBT_RATE_HIST_WORDS words per picture come back.
+struct CensusSet {
+  std::vector<RbtCensusPic> pics; int max_words = 0;
+  std::vector<uint8_t> staging; uint8_t* d = nullptr; size_t o_hist = 0;
+  std::vector<uint32_t> hist;                    // after fetch(): hist[3][53] per picture, in add() order
+  int add(const RbtFrame& f);                    // index of the picture, < 0: refused (size not a multiple of 8)
+  bool empty() const { return pics.empty(); }
+  int upload();
+  void launch() const;                           // between the events of T_CENSUS on the current stream
+  int fetch();
+  ~CensusSet() { rbtk::dev_free(d); }
+};
+
+enum { T_PARSE = 0, T_RECON = 1, T_CENSUS = 2, T_ANALYSE = 3, T_ENCODE = 4, T_ENTROPY = 5, T_ALL = 6, T_POOL = 7, T_INTER = 8, T_ENTROPY_I = 9, T_COUNT = 10 };   // (the device keeps 16 events per lane, rbt_pcc.cpp has the other six; T_CENSUS took the slot of a filter timer nothing used)
 
 // Bump allocator over one device allocation, every buffer on a multiple of 256 bytes. A batch names each buffer of its arena once, in a layout function (decode_lay_out,
 // encode_lay_out) that runs twice: without a base it only counts (take() gives nullptr, `used` ends as the size), over the allocated block it hands out the pointers.
@@ -79,6 +96,7 @@ struct DecodeBatch {
   bool want_save = false;              // set before decode_build to reserve d_save
   void* arena = nullptr; size_t arena_size = 0;
   RbtFrame* d_frames = nullptr; RbtSlice* d_slices = nullptr; uint8_t* d_rbsp = nullptr; int32_t* d_lists = nullptr;
+  CensusSet census; std::vector<int> census_first;   // rate targets: the pictures of the streams that are counted (census_first[stream]: index of the stream's first picture in `census`, -1: not counted)
   HashSet hash; std::vector<int> hash_checked;   // verify_md5: the pictures of the checked streams (counter = stream), pictures checked per stream
   std::string err; int err_code = 0;
   ~DecodeBatch() { rbtk::dev_free(arena); }
@@ -106,6 +124,8 @@ int decode_run(DecodeBatch& b);      // launch + finish
 int decode_hash_setup(DecodeBatch& b, const std::vector<char>& verify);
 void decode_launch_hash(const DecodeBatch& b);
 void decode_hash_result(const DecodeBatch& b, int stream, int& checked, int& failed);
+// rate targets: every picture of the streams with want[stream] goes into b.census (uploaded on the current stream); b.census.launch() goes behind the decoder's last filter
+int decode_census_setup(DecodeBatch& b, const std::vector<char>& want);
 int decode_fetch(DecodeBatch& b, int stream, rbt_video* out);   // the stream's cropped pictures to the host
 
 size_t frame_samples(const RbtStreamCfg& c);

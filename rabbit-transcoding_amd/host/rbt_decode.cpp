@@ -107,6 +107,7 @@ int decode_build(DecodeBatch& b, const StreamIn* streams, int n_streams) {
         { const int n_ctb = sps.w_ctb * sps.h_ctb, prev = b.frames[cur].n_slices ? b.slices.back().ctb_addr : -1;
           if ((int)h.segment_addr <= prev || (int)h.segment_addr >= n_ctb || (prev < 0 && h.segment_addr != 0)) { delete ps; b.err = "slice segment address out of order"; return b.err_code = RBT_ERR_BITSTREAM; }
           if (prev >= 0) b.slices.back().end_addr = (int32_t)h.segment_addr; }
+        b.info[cur].vcl_bytes += nal.rbsp_size + nal.epb.size();
         RbtSlice s; memset(&s, 0, sizeof(s));
         s.frame = cur; s.data_off = (uint32_t)(nal.rbsp_off + h.data_byte_offset);
         if (h.data_byte_offset > nal.rbsp_size) { delete ps; b.err = "empty slice data"; return b.err_code = RBT_ERR_BITSTREAM; }
@@ -403,6 +404,50 @@ void decode_hash_result(const DecodeBatch& b, int stream, int& checked, int& fai
   failed = checked && stream < (int)b.hash.counters.size() ? (int)b.hash.counters[stream] : 0;
 }
 
+// ------------------------------------------------------------------------------------------------ level census (rate targets)
+int decode_census_setup(DecodeBatch& b, const std::vector<char>& want) {
+  const int ns = (int)b.stream_first.size();
+  b.census_first.assign(ns, -1);
+  for (int si = 0; si < ns && si < (int)want.size(); si++) if (want[si])
+    for (int k = 0; k < b.stream_count[si]; k++) {
+      const int at = b.census.add(b.frames[b.stream_first[si] + k]);
+      if (at < 0) { b.err = "picture size is not a multiple of 8"; return b.err_code = RBT_ERR_UNSUPPORTED; }
+      if (k == 0) b.census_first[si] = at;
+    }
+  if (b.census.empty()) return 0;
+  if (int rc = b.census.upload()) { b.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return b.err_code = rc; }
+  return 0;
+}
+int CensusSet::add(const RbtFrame& f) {
+  if (f.cfg.w <= 0 || f.cfg.h <= 0 || (f.cfg.w | f.cfg.h) & 7) return -1;
+  RbtCensusPic P; memset(&P, 0, sizeof(P));
+  for (int c = 0; c < 3; c++) { if ((uintptr_t)f.coef[c] & 7) return -1; P.coef[c] = f.coef[c]; }   // the kernel reads 8 bytes at a time
+  P.qp = f.qp; P.pm = f.pm; P.w = f.cfg.w; P.h = f.cfg.h;
+  max_words = std::max(max_words, RBT_RATE_PIC_WORDS(P.w, P.h));
+  pics.push_back(P);
+  return (int)pics.size() - 1;
+}
+int CensusSet::upload() {
+  const size_t n = pics.size();
+  o_hist = (n * sizeof(RbtCensusPic) + 255) & ~(size_t)255;
+  const size_t end = o_hist + n * RBT_RATE_HIST_WORDS * 4;
+  rbtk::dev_free(d);
+  d = (uint8_t*)rbtk::dev_alloc(end);
+  if (!d) return RBT_ERR_NOMEM;
+  for (size_t i = 0; i < n; i++) pics[i].hist = (uint32_t*)(d + o_hist) + i * RBT_RATE_HIST_WORDS;
+  staging.assign(end, 0);
+  memcpy(staging.data(), pics.data(), n * sizeof(RbtCensusPic));
+  return rbtk::h2d(d, staging.data(), end) ? RBT_ERR_NO_DEVICE : 0;
+}
+void CensusSet::launch() const {
+  rbtk::timer_begin(T_CENSUS);
+  rbtk::launch_level_census((const RbtCensusPic*)d, (int)pics.size(), max_words);
+  rbtk::timer_end(T_CENSUS);
+}
+int CensusSet::fetch() {
+  hist.assign(pics.size() * RBT_RATE_HIST_WORDS, 0);
+  return !hist.empty() && rbtk::d2h(hist.data(), d + o_hist, hist.size() * 4) ? RBT_ERR_NO_DEVICE : 0;
+}
 static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 int HashSet::add(const uint16_t* const planes[3], int w, int h, int bit_depth, int kind, int counter, const uint8_t* want) {
   if (kind < RBT_HASH_MD5 || kind > RBT_HASH_CHECKSUM || w <= 0 || h <= 0 || (w | h) & 1 || bit_depth < 8 || bit_depth > 16 || (int)pics.size() >= RBT_HASH_MAX_PICS) return -1;

@@ -2,12 +2,14 @@
 // Replaces initEncoder / setEncoderOptions / encodeVideo / resize_frame2 of PCCTranscoder (PCCTranscoder.cpp:683-753,
 // :825-904, :548-592, :594-646) and the decode -> pool -> encode loop of transcodeVideo (:428-510).
 #include <algorithm>
+#include <map>
 #include <memory>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include "rbt_batch.h"
 #include "rbt_transcode.h"
+#include "rbt_rate_walk.h"
 
 namespace rbt {
 
@@ -114,7 +116,8 @@ static void encode_lay_out(EncodeBatch& b, Arena& a) {
   a.mark();
 }
 
-static int encode_build(EncodeBatch& b) {
+// host half of encode_build: parameter sets, pictures, slices and the size of the arena (b.arena_size); nothing is allocated
+static int encode_plan(EncodeBatch& b) {
   size_t ns = b.desc.size();
   b.sps.resize(ns); b.pps.resize(ns); b.stream_first.resize(ns);
   for (size_t si = 0; si < ns; si++) {
@@ -165,10 +168,15 @@ static int encode_build(EncodeBatch& b) {
   size_t out_cap_total = 0; for (auto& sl : b.slices) { sl.out_off = (uint32_t)out_cap_total; out_cap_total += sl.out_cap; }
   if (out_cap_total >= 0xFFFFFFFFull) { b.err = "output buffer too large for one call"; return RBT_ERR_UNSUPPORTED; }
   b.out_total = out_cap_total;
-  Arena a; encode_lay_out(b, a);      // measure, allocate, bind
-  b.arena_size = a.used; b.arena = rbtk::dev_alloc(b.arena_size);
+  Arena a; encode_lay_out(b, a);      // measure
+  b.arena_size = a.used;
+  return 0;
+}
+static int encode_build(EncodeBatch& b) {
+  if (int rc = encode_plan(b)) return rc;
+  b.arena = rbtk::dev_alloc(b.arena_size);      // allocate, bind
   if (!b.arena) { b.err = "device allocation failed"; return RBT_ERR_NOMEM; }
-  a = Arena{(uint8_t*)b.arena}; encode_lay_out(b, a);
+  Arena a{(uint8_t*)b.arena}; encode_lay_out(b, a);
   // per CTB: the SLICE it belongs to (index of the slice's independent segment): availability, QP and loop filter flags are per slice
   const size_t nf = b.frames.size(); b.cs_keep.clear();
   for (size_t i = 0; i < nf; i++) {
@@ -404,6 +412,15 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
 // One transcode call in flight. rbt_transcode_gof = submit + wait; rbt_submit_gof / rbt_wait_gof expose the two halves so that
 // a caller can keep two GOFs in flight (job slots use disjoint HIP streams): the next GOF's entropy decoding then runs
 // underneath the previous GOF's reconstruction and re-encode.
+// Rate targets: what a pipeline with a targeted entry keeps between the rounds of its trial encodes (rate_run_pipeline, rate_launch_round, rate_finish_round)
+struct RateCand { int q, qp, walk; };          // entry q of the group at qp; walk: index of its RateWalk, -1 for a constant-QP entry of the pipeline
+struct RatePipe {
+  std::vector<RateWalk> walks; std::vector<int> n_enc;
+  std::vector<RateCand> cands;                 // the round to run (eb == nullptr) or running
+  std::unique_ptr<EncodeBatch> eb;             // the round in flight on the pipeline's stream
+  std::vector<std::vector<uint8_t>> o1;        // the pipeline's streams in group order, as they settle
+  bool done = false;
+};
 struct GofJob {
   int n = 0, slot = 0, ng = 0, rc = 0;
   std::vector<std::vector<int>> groups; std::vector<int> order;
@@ -419,6 +436,9 @@ struct GofJob {
   std::vector<std::vector<uint8_t>> passthrough;   // transcodeData (PCCTranscoder.cpp:150): occupancy is only transcoded when occupancyPrecision == 4; else the stream stays as it is
   std::vector<char> is_pass;
   std::vector<std::vector<int>> dec_of;            // per pipeline: decode stream of each of its (encode) streams - identical inputs are decoded once
+  // rate targets (rbt_submit_gof_rate): a pipeline that holds a targeted entry is decoded and counted at submit and encoded in the wait half (rate_run_pipeline)
+  std::vector<rbt_rate_target> targets; std::vector<char> rate_pipe; std::vector<rbt_rate_result> results; size_t rate_bytes = 0;   // rate_bytes: arenas of the first round of trial encodes
+  std::vector<RatePipe> rate;                                // per pipeline
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   ~GofJob() { for (void* q : pooled) rbtk::dev_free(q); }
 };
@@ -435,7 +455,8 @@ static void bind_streams(GofJob& j, int depth) {
   rbtk::map_lane(job_stream(j, rbtk::RBT_AUX_STREAM), base + spj - 1);
 }
 
-size_t gof_memory(const GofJob* j) { return j ? j->dev_bytes : 0; }
+size_t gof_memory(const GofJob* j) { return j ? j->dev_bytes + j->rate_bytes : 0; }
+static bool has_target(const GofJob& j, int i) { return !j.targets.empty() && j.targets[i].target_bytes != 0; }
 
 // What lives only while a job is submitted
 struct SubmitPlan {
@@ -480,12 +501,16 @@ static int plan_pipelines(GofJob& j, SubmitPlan& s, int depth) {
   std::stable_sort(j.order.begin(), j.order.end(), [&](int a, int b) { return bytes_of(a) > bytes_of(b); });
   bind_streams(j, depth);
   recon_set_depth(depth);
+  j.rate_pipe.assign(ng, 0);
+  for (int g = 0; g < ng; g++) for (int i : groups[g]) j.rate_pipe[g] |= (char)has_target(j, i);
   s.pool_jobs.resize(ng); s.occ_of.assign(n, -1); s.occ_src.resize(n); s.feeds_any.assign(ng, 0); s.consumes.assign(ng, 0);
   int rc = 0;
   for (int i = 0, last = -1; i < n; i++) {
     if (p[i].video_type == RBT_VIDEO_OCCUPANCY) last = (s.gof_rule && !j.is_pass[i] && p[i].occupancy_precision == 4) ? i : -1;
     else if (s.gof_rule && p[i].occupancy_rd && last >= 0) { s.occ_of[i] = last; if (p[i].verify_md5 || p[last].verify_md5) { j.err = "occupancy_rd cannot be combined with verify_md5"; rc = RBT_ERR_PARAM; } }
   }
+  // a pipeline with a target is encoded in the wait half, where the occupancy maps of the submission are gone (only calls with more than three streams share pipelines)
+  for (int g = 0; g < ng; g++) if (j.rate_pipe[g]) for (int i : groups[g]) if (s.occ_of[i] >= 0) { j.err = "entry " + std::to_string(i) + ": occupancy_rd on an entry that shares a pipeline with a rate-targeted entry"; rc = RBT_ERR_PARAM; }
   return rc;
 }
 
@@ -504,17 +529,24 @@ static int build_decoders(GofJob& j, SubmitPlan& s) {
     j.st.host_parse_ms += now_ms() - t0;
     if (!rc) rc = decode_upload_lists(db);
     if (!rc && verify) rc = decode_hash_setup(db, verify_ds);
+    if (!rc && j.rate_pipe[gi]) {
+      std::vector<char> count_ds(s.uniq[gi].size(), 0);    // per decoded stream: some entry it feeds has a target
+      for (size_t q = 0; q < gs.size(); q++) if (has_target(j, gs[q])) count_ds[j.dec_of[gi][q]] = 1;
+      rc = decode_census_setup(db, count_ds);
+    }
     if (rc) { j.err = db.err; return rc; }
   }
   return 0;
 }
 
+static int rate_measure(GofJob& j, int gi);
 // Encoder batches: the pipelines whose occupancy streams others are coded with first (their pooled planes are what the maps are made of), then the rest
 static int build_encoders(GofJob& j, SubmitPlan& s) {
   for (int pass = 0; pass < 2; pass++) for (int k = 0; k < j.ng; k++) {
     const int gi = j.order[k]; const std::vector<int>& gs = j.groups[gi]; EncodeBatch& eb = j.eb[gi]; rbtk::set_stream(job_stream(j, gi));
     bool feeds = false; for (int i : gs) for (int c = 0; c < j.n; c++) feeds |= s.occ_of[c] == i;
     if (feeds != (pass == 0)) continue;
+    if (j.rate_pipe[gi]) { if (int rc = rate_measure(j, gi)) return rc; continue; }      // stays unchained: decoder and census now, encoders in the wait half
     for (size_t q = 0; q < gs.size(); q++) {
       const int i = gs[q], io = s.occ_of[i];
       if (int rc = setup_encode(j.db[gi], j.dec_of[gi][q], (int)q, s.p[i], eb, j.pooled, j.err, &s.pool_jobs[gi], io >= 0 ? &s.occ_src[io] : nullptr, io, &s.occ_jobs)) return rc;
@@ -529,6 +561,120 @@ static int build_encoders(GofJob& j, SubmitPlan& s) {
   }
   for (const OccJob& oj : s.occ_jobs) s.feeds_any[s.occ_src[oj.source].pipeline] = 1;
   for (int g = 0; g < j.ng; g++) for (const EncStreamDesc& d : j.eb[g].desc) s.consumes[g] |= !d.occ4.empty();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ rate targets (include/rbt.h, "transcoding to a byte budget")
+static int rate_fill_batch(GofJob& j, int gi, const std::vector<RateCand>& cands, EncodeBatch& eb) {
+  for (size_t e = 0; e < cands.size(); e++) {
+    rbt_stream_params pp = j.params[j.groups[gi][cands[e].q]]; pp.qp = cands[e].qp;
+    if (int rc = setup_encode(j.db[gi], j.dec_of[gi][cands[e].q], (int)e, pp, eb, j.pooled, j.err)) return rc;
+  }
+  return 0;
+}
+static void rate_first_round(const GofJob& j, int gi, std::vector<RateCand>& cands, const std::vector<RateWalk>* walks) {
+  const std::vector<int>& gs = j.groups[gi]; std::vector<int> qps; int nw = 0;
+  for (size_t q = 0; q < gs.size(); q++) {
+    if (!has_target(j, gs[q])) { cands.push_back(RateCand{(int)q, j.params[gs[q]].qp, -1}); continue; }
+    RateWalk w0; if (!walks) { const rbt_rate_target& t = j.targets[gs[q]]; w0.lo = t.qp_min; w0.hi = t.qp_max ? t.qp_max : 51; w0.qe = std::min(w0.hi, w0.lo + 1); }   // (measuring: three QPs in the lowest band)
+    rate_round_qps(walks ? (*walks)[nw] : w0, 0, 0, qps);
+    for (int qp : qps) cands.push_back(RateCand{(int)q, qp, nw});
+    nw++;
+  }
+}
+// at submit: what the first round of trial encodes will take (rbt_job_memory), measured on the layout without allocating; the estimate is not known yet, the arenas do not
+// depend on it but for the slice buffers' QP bands
+static int rate_measure(GofJob& j, int gi) {
+  DecodeBatch& db = j.db[gi];
+  for (int i : j.groups[gi]) if (j.params[i].video_type == RBT_VIDEO_OCCUPANCY) return 0;      // (its pooled planes would be allocated: left uncounted)
+  std::vector<RateCand> cands; rate_first_round(j, gi, cands, nullptr);
+  const std::vector<char> taken = db.alias_taken;
+  EncodeBatch eb; int rc = rate_fill_batch(j, gi, cands, eb);
+  if (!rc && (rc = encode_plan(eb)) != 0) j.err = eb.err;
+  db.alias_taken = taken;
+  if (!rc) j.rate_bytes += eb.arena_size;
+  return rc;
+}
+// Rounds. A round of a pipeline is one encode batch of candidates on the pipeline's stream: rate_launch_round builds and enqueues it, rate_finish_round waits for it, packs
+// the streams, lets the walks look at the sizes and names the next round.
+static int rate_launch_round(GofJob& j, int gi) {
+  RatePipe& r = j.rate[gi];
+  if (r.cands.empty()) { r.done = true; return 0; }
+  rbtk::set_stream(job_stream(j, gi));
+  r.eb.reset(new EncodeBatch()); EncodeBatch& eb = *r.eb;
+  int rc = rate_fill_batch(j, gi, r.cands, eb);
+  if (!rc && ((rc = encode_build(eb)) != 0 || (rc = encode_upload_lists(eb)) != 0)) j.err = eb.err;
+  if (rc) return rc;
+  encode_launch_intra(eb); encode_launch_entropy_intra(eb); encode_launch_inter(eb);
+  if (!eb.hash.empty()) eb.hash.launch();
+  encode_launch_entropy_rest(eb);
+  return 0;
+}
+static int rate_finish_round(GofJob& j, int gi) {
+  RatePipe& r = j.rate[gi]; std::vector<std::vector<uint8_t>> outs;
+  rbtk::set_stream(job_stream(j, gi));
+  if (int rc = encode_finish(*r.eb, outs, j.st)) { j.err = r.eb->err; return rc; }
+  r.eb.reset();
+  for (size_t e = 0; e < r.cands.size(); e++) {
+    if (r.cands[e].walk < 0) r.o1[r.cands[e].q].swap(outs[e]);
+    else { r.walks[r.cands[e].walk].tried[r.cands[e].qp].swap(outs[e]); r.n_enc[r.cands[e].walk]++; }
+  }
+  r.cands.clear(); std::vector<int> qps;
+  for (size_t k = 0; k < r.walks.size(); k++) {
+    int need = 0, dir = 0;
+    if (r.walks[k].settled || rate_walk_step(r.walks[k], need, dir)) continue;
+    rate_round_qps(r.walks[k], need, dir, qps);
+    for (int qp : qps) r.cands.push_back(RateCand{r.walks[k].q, qp, (int)k});
+  }
+  return 0;
+}
+// a decoded pipeline's checks, shared by the constant-QP path and rate_run_pipeline: error words and coverage, timers, the input's picture hashes (verify_md5)
+static int pipeline_decoded(GofJob& j, int gi) {
+  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
+  int rc = decode_finish(db);
+  if (rc) { j.err = db.err; return rc; }
+  if (j.parse_timed.empty() || j.parse_timed[gi]) j.st.k_parse_ms += rbtk::timer_ms(T_PARSE);
+  if (j.recon_timed.empty() || j.recon_timed[gi]) j.st.k_recon_ms += rbtk::timer_ms(T_RECON);
+  // verify_md5: the hashes of the decoded pictures were compared on the GPU; a mismatch fails the job and nothing is packed
+  if (!db.hash.empty()) {
+    if (db.hash.fetch()) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+    for (size_t q = 0; q < gs.size(); q++) if (j.params[gs[q]].verify_md5) {
+      int checked = 0, failed = 0; decode_hash_result(db, j.dec_of[gi][q], checked, failed);
+      if (failed) { j.err = "input " + std::to_string(gs[q]) + ": decoded picture hash mismatch (" + std::to_string(failed) + " of " + std::to_string(checked) + " pictures)"; return RBT_ERR_MD5; }
+    }
+  }
+  return 0;
+}
+// A pipeline with a target, in the wait half: its decoder is collected, the histograms come back, the estimates are formed and the rounds run, one after the other, until
+// every walk has settled. (Measured and not adopted, DESIGN.md 12: the rounds of a job's pipelines side by side, and the first rounds of the other jobs in flight enqueued
+// ahead of their turn - both were slower than one pipeline's rounds at a time.)
+static int rate_run_pipeline(GofJob& j, int gi) {
+  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
+  j.rate.resize(j.ng); j.results.resize(j.n); RatePipe& r = j.rate[gi];
+  if (int rc = pipeline_decoded(j, gi)) return rc;
+  if (db.census.fetch()) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  for (size_t q = 0; q < gs.size(); q++) if (has_target(j, gs[q])) {
+    const rbt_rate_target& t = j.targets[gs[q]]; const int ds = j.dec_of[gi][q], first = db.stream_first[ds], cnt = db.stream_count[ds];
+    RateWalk w; w.q = (int)q; w.entry = gs[q]; w.T = t.target_bytes; w.lo = t.qp_min; w.hi = t.qp_max ? t.qp_max : 51;
+    std::vector<uint64_t> bytes(cnt); for (int i = 0; i < cnt; i++) bytes[i] = db.info[first + i].vcl_bytes;
+    uint64_t E[52]; rate_table(db.census.hist.data() + (size_t)db.census_first[ds] * RBT_RATE_HIST_WORDS, bytes.data(), cnt, E);
+    w.qe = w.hi; for (int qq = w.lo; qq <= w.hi; qq++) if (E[qq] <= w.T) { w.qe = qq; break; }
+    w.e_qe = E[w.qe];
+    r.walks.push_back(std::move(w));
+  }
+  r.o1.assign(gs.size(), {}); r.n_enc.assign(r.walks.size(), 0);
+  rate_first_round(j, gi, r.cands, &r.walks);
+  for (;;) {
+    if (int rc = rate_launch_round(j, gi)) return rc;
+    if (r.done) break;
+    if (int rc = rate_finish_round(j, gi)) return rc;
+  }
+  for (size_t k = 0; k < r.walks.size(); k++) {
+    RateWalk& w = r.walks[k];
+    if (!w.settled) { j.err = "internal: rate walk did not settle"; return RBT_ERR_PARAM; }
+    j.results[w.entry] = rbt_rate_result{w.qstar, w.qe, w.met, r.n_enc[k], (uint64_t)w.tried[w.qstar].size(), w.e_qe};
+    r.o1[w.q].swap(w.tried[w.qstar]);
+  }
   return 0;
 }
 
@@ -605,7 +751,12 @@ static int launch_merged(GofJob& j) {
 static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
   const int sid = job_stream(j, gi), aux = job_stream(j, rbtk::RBT_AUX_STREAM); rbtk::set_stream(sid);
   DecodeBatch& db = j.db[gi]; const std::vector<PoolJob>& jobs = s.pool_jobs[gi];
-  if (!j.chained[gi]) { int rc = decode_launch(db); if (rc) j.err = db.err; return rc; }
+  if (!j.chained[gi]) {      // a pipeline with rate targets: the decoder, the input's hash check and the census; rate_run_pipeline encodes when the job is collected
+    if (int rc = decode_launch(db)) { j.err = db.err; return rc; }
+    if (!db.hash.empty()) decode_launch_hash(db);
+    if (!db.census.empty()) db.census.launch();
+    return 0;
+  }
   // Intra pictures of the output only read the decoded pictures they are re-encoded from. When those are complete
   // before the last dependency level of the decoder, analysis + intra coding run on an auxiliary stream underneath the
   // remaining reconstruction levels.
@@ -667,11 +818,12 @@ static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
 
 // Phase A of a job: plan, build and upload everything, then enqueue. Every upload of the job is issued before its first kernel: a copy from pageable memory blocks the host
 // until the stream has reached it, and pipelines may share a stream. The first failure ends the submission (j.rc, j.err); gof_wait drains what was enqueued.
-GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule) {
+GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets) {
   GofJob* J = new GofJob(); GofJob& j = *J;
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
   j.params.assign(p, p + n); j.n_in.assign(n_in, n_in + n);
+  if (targets) j.targets.assign(targets, targets + n);
   SubmitPlan s; s.in = in; s.p = p; s.gof_rule = gof_rule;
   int rc = plan_pipelines(j, s, depth);
   j.t_gpu = now_ms();
@@ -685,7 +837,7 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
 }
 
 // phase B, shortest pipeline first: one sync per stream, then slice sizes -> pack -> NAL assembly. Consumes the job.
-int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out) {
+int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results) {
   std::unique_ptr<GofJob> guard(J); GofJob& j = *J;
   const int n = j.n, ng = j.ng; int rc = j.rc;
   rbt_stats& st = j.st; std::string& err = j.err;
@@ -696,22 +848,14 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
     const int gi = j.order[k], sid = job_stream(j, gi); const std::vector<int>& gs = j.groups[gi]; rbtk::set_stream(sid);
     if (rc) { rbtk::dev_sync(); continue; }              // drain the remaining streams before their arenas are released
     if (db[gi].frames.empty()) continue;
-    rc = decode_finish(db[gi]);
-    if (rc) { err = db[gi].err; continue; }
-    if (j.parse_timed.empty() || j.parse_timed[gi]) st.k_parse_ms += rbtk::timer_ms(T_PARSE);
-    if (j.recon_timed.empty() || j.recon_timed[gi]) st.k_recon_ms += rbtk::timer_ms(T_RECON);
-    // verify_md5: the hashes of the decoded pictures were compared on the GPU; a mismatch fails the job and nothing is packed
-    if (!db[gi].hash.empty()) {
-      if (db[gi].hash.fetch()) { err = "device transfer failed"; rc = RBT_ERR_NO_DEVICE; continue; }
-      for (size_t q = 0; q < gs.size() && !rc; q++) if (p[gs[q]].verify_md5) {
-        int checked = 0, failed = 0; decode_hash_result(db[gi], j.dec_of[gi][q], checked, failed);
-        if (failed) { err = "input " + std::to_string(gs[q]) + ": decoded picture hash mismatch (" + std::to_string(failed) + " of " + std::to_string(checked) + " pictures)"; rc = RBT_ERR_MD5; }
-      }
-      if (rc) continue;
-    }
     std::vector<std::vector<uint8_t>> o1;
-    rc = encode_finish(eb[gi], o1, st);
-    if (rc) { if (err.empty()) err = eb[gi].err; continue; }
+    if (j.rate_pipe[gi]) { rc = rate_run_pipeline(j, gi); rbtk::set_stream(sid); if (rc) continue; o1.swap(j.rate[gi].o1); }      // estimates, rounds of trial encodes, walks
+    else {
+      rc = pipeline_decoded(j, gi);
+      if (rc) continue;
+      rc = encode_finish(eb[gi], o1, st);
+      if (rc) { if (err.empty()) err = eb[gi].err; continue; }
+    }
     for (size_t q = 0; q < gs.size(); q++) outs[gs[q]].swap(o1[q]);
   }
   rbtk::set_stream(0);
@@ -719,6 +863,10 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
   for (int i = 0; i < n; i++) if (j.is_pass[i]) outs[i].swap(j.passthrough[i]);
   st.gpu_ms = now_ms() - j.t_gpu;
   rc = hand_out(outs, out, n_out);
+  if (results) for (int i = 0; i < n; i++) {
+    if (has_target(j, i)) { results[i] = j.results[i]; continue; }
+    results[i] = rbt_rate_result{p[i].qp, p[i].qp, 1, j.is_pass[i] ? 0 : 1, (uint64_t)n_out[i], 0};
+  }
   // SURVEY.md 8(d) algorithmic traffic: per coded picture of S samples (2 bytes each): decode writes S, P pictures read
   // their reference once; encode reads the source S, writes the reconstruction S (I) and reads the reference (P)
   uint64_t bytes = 0;
@@ -739,7 +887,7 @@ void gof_abandon(GofJob* J) {   // a job nobody will wait for: drain its streams
   delete J;
 }
 int transcode_gof(rbt_stats& st, std::string& err, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, uint8_t** out, size_t* n_out) {
-  return gof_wait(gof_submit(0, 1, n, in, n_in, p, true), st, err, out, n_out);
+  return gof_wait(gof_submit(0, 1, n, in, n_in, p, true, nullptr), st, err, out, n_out, nullptr);
 }
 
 int encode_yuv(rbt_stats& st, std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int qp, int gop, int lossless, int log2_ctb, int rows, int md5,
@@ -792,6 +940,48 @@ int picture_hash_host(std::string& err, const uint16_t* yuv, int w, int h, int b
     if (rc) { err = "device transfer failed"; return rc; }
     memcpy(out + (size_t)f0 * 48, hs.out.data(), (size_t)m * 48);
   }
+  return 0;
+}
+
+// rbt_level_census: the planes go to the device back to back (every plane 8-byte aligned: w and h are multiples of 8), the maps behind them
+int level_census_host(std::string& err, const int16_t* y, const int16_t* cb, const int16_t* cr, int w, int h, const int8_t* qp4, const uint8_t* pm4, uint32_t* hist) {
+  if (w <= 0 || h <= 0 || (w | h) & 7 || w > 8192 || h > 8192) { err = "picture size must be a multiple of 8 and at most 8192"; return RBT_ERR_PARAM; }
+  const size_t ys = (size_t)w * h, cs = ys / 4, u = ys / 16;
+  std::vector<uint8_t> staging((ys + 2 * cs) * 2 + 2 * u);
+  memcpy(staging.data(), y, ys * 2); memcpy(staging.data() + ys * 2, cb, cs * 2); memcpy(staging.data() + (ys + cs) * 2, cr, cs * 2);
+  memcpy(staging.data() + (ys + 2 * cs) * 2, qp4, u); memcpy(staging.data() + (ys + 2 * cs) * 2 + u, pm4, u);
+  uint8_t* buf = (uint8_t*)rbtk::dev_alloc(staging.size());
+  if (!buf) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  struct G { void* p; ~G() { rbtk::dev_free(p); } } g{buf};
+  if (rbtk::h2d(buf, staging.data(), staging.size())) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  RbtFrame f; memset(&f, 0, sizeof(f));
+  f.cfg.w = w; f.cfg.h = h; Arena::same_planes(f.coef, (int16_t*)buf, ys, cs); f.qp = (int8_t*)(buf + (ys + 2 * cs) * 2); f.pm = buf + (ys + 2 * cs) * 2 + u;
+  CensusSet cs1;
+  if (cs1.add(f) < 0) { err = "picture cannot be counted"; return RBT_ERR_PARAM; }
+  int rc = cs1.upload();
+  if (!rc) { cs1.launch(); rc = cs1.fetch(); }
+  if (rc) { err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
+  memcpy(hist, cs1.hist.data(), RBT_RATE_HIST_WORDS * 4);
+  return 0;
+}
+
+// rbt_rate_estimate: decode, census behind the last filter, table
+int rate_estimate(std::string& err, const uint8_t* annexb, size_t n, rbt_rate_table* out) {
+  memset(out, 0, sizeof(*out));
+  DecodeBatch b; StreamIn in{annexb, n};
+  int rc = decode_build(b, &in, 1);
+  if (!rc) rc = decode_census_setup(b, std::vector<char>(1, 1));
+  if (!rc) rc = decode_launch(b);
+  if (!rc) { b.census.launch(); rc = decode_finish(b); }
+  if (!rc && b.census.fetch()) { b.err = "device transfer failed"; rc = RBT_ERR_NO_DEVICE; }
+  if (rc) { err = b.err; return rc; }
+  const int np = b.stream_count[0];
+  out->n_pictures = np; out->census_ms = rbtk::timer_ms(T_CENSUS);
+  out->hist = (uint32_t*)malloc((size_t)np * RBT_RATE_HIST_WORDS * 4); out->picture_bytes = (uint64_t*)malloc((size_t)np * 8);
+  if (!out->hist || !out->picture_bytes) { free(out->hist); free(out->picture_bytes); memset(out, 0, sizeof(*out)); return RBT_ERR_NOMEM; }
+  memcpy(out->hist, b.census.hist.data(), (size_t)np * RBT_RATE_HIST_WORDS * 4);
+  for (int k = 0; k < np; k++) out->picture_bytes[k] = b.info[b.stream_first[0] + k].vcl_bytes;
+  rate_table(out->hist, out->picture_bytes, np, out->estimate);
   return 0;
 }
 

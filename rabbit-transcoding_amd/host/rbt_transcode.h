@@ -6,11 +6,14 @@ namespace rbt {
 int transcode_gof(rbt_stats& st, std::string& err, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, uint8_t** out, size_t* n_out);
 struct GofJob;
 // gof_rule: apply transcodeData's rule (PCCTranscoder.cpp:150): an occupancy stream is only transcoded when occupancyPrecision == 4
-GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule);
-int gof_wait(GofJob* j, rbt_stats& st, std::string& err, uint8_t** out, size_t* n_out);   // consumes the job
+// targets: nullptr, or one per entry (checked by the caller: rbt_submit_gof_rate); results: nullptr, or one per entry
+GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets = nullptr);
+int gof_wait(GofJob* j, rbt_stats& st, std::string& err, uint8_t** out, size_t* n_out, rbt_rate_result* results = nullptr);   // consumes the job
 void gof_abandon(GofJob* j);
 size_t gof_memory(const GofJob* j);             // device memory the job's build took (its arenas)
 int encode_yuv(rbt_stats& st, std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int qp, int gop, int lossless, int log2_ctb, int rows, int md5, uint8_t** out, size_t* n_out);
 int or_pool_host(const uint16_t* plane, int w, int h, int factor, uint16_t* out);
+int level_census_host(std::string& err, const int16_t* y, const int16_t* cb, const int16_t* cr, int w, int h, const int8_t* qp4, const uint8_t* pm4, uint32_t* hist);   // rbt_level_census
+int rate_estimate(std::string& err, const uint8_t* annexb, size_t n, rbt_rate_table* out);   // rbt_rate_estimate
 int picture_hash_host(std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int kind, uint8_t* out);   // rbt_picture_hash
 }

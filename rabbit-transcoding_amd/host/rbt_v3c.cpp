@@ -18,6 +18,20 @@ namespace {
 struct Buf { uint8_t* p = nullptr; size_t n = 0; };
 // floorLog2 / ceilLog2 of PCCBitstreamCommon.h:526-566
 int ceil_log2(uint32_t x) { if (x == 0) return -1; x -= 1; int r = -1; while (x) { r++; x >>= 1; } return r + 1; }
+// pictures of a video sub-bitstream in sample stream form (4-byte sizes): VCL NAL units with first_slice_segment_in_pic_flag
+uint64_t count_pictures(const uint8_t* ss, size_t n) {
+  uint64_t pics = 0;
+  for (size_t at = 0; at + 4 <= n;) {
+    size_t sz = 0; for (int i = 0; i < 4; i++) sz = (sz << 8) + ss[at + i];
+    if (sz > n - at - 4) break;
+    if (sz >= 3 && ((ss[at + 4] >> 1) & 0x3F) < 32 && (ss[at + 6] & 0x80)) pics++;
+    at += 4 + sz;
+  }
+  return pics;
+}
+// rate targets of the walk (rbt_transcode_v3c_rate): bits per picture by video type (0 = constant QP), and where the results go (two per GOF: geometry, attribute)
+struct WalkRate { uint32_t geometry_bits = 0, attribute_bits = 0; rbt_rate_result* per_gof = nullptr; bool on() const { return geometry_bits || attribute_bits; } };
+int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt_v3c_sink sink, void* user, const WalkRate& rate);
 }
 
 #include <new>
@@ -110,6 +124,12 @@ int rbt_v3c_stats(const uint8_t* in, size_t n, rbt_v3c_stat* out) try {
 
 int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt_v3c_sink sink, void* user) try {
   if (!ctx || !in || !p || !sink) return RBT_ERR_PARAM;
+  return walk(ctx, in, n, p, sink, user, WalkRate());
+} RBT_CATCH
+}  // extern "C"
+
+namespace {
+int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt_v3c_sink sink, void* user, const WalkRate& rate) {
   rbt_v3c_unit* units = nullptr; int nu = 0;
   int rc = rbt_v3c_index(in, n, &units, &nu);
   if (rc) return rc;
@@ -157,6 +177,17 @@ int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rb
     return RBT_OK;
   };
   // jobs: the picked units of `per` consecutive owned GOFs each, as many in flight as the context allows (RBT_ERR_BUSY tells) AND as the device memory holds
+  // a job of a walk with rate targets is collected with its results: entry k of the job is unit jb.unit[k]
+  auto wait_job = [&](rbt_job* j, const std::vector<int>& unit, uint8_t** o, size_t* on) -> int {
+    if (!rate.on()) return rbt_wait_gof(ctx, j, o, on);
+    std::vector<rbt_rate_result> res(unit.size());
+    const int r = rbt_wait_gof_rate(ctx, j, o, on, res.data());
+    if (!r && rate.per_gof) for (size_t k = 0; k < unit.size(); k++) {
+      const rbt_v3c_unit& u = U[unit[k]];
+      if (u.video_type == RBT_VIDEO_GEOMETRY) rate.per_gof[2 * u.gof] = res[k]; else if (u.video_type == RBT_VIDEO_ATTRIBUTE) rate.per_gof[2 * u.gof + 1] = res[k];
+    }
+    return r;
+  };
   struct Job { rbt_job* j; std::vector<int> unit; int last_gof; size_t a, a_end; size_t others; };   // [a, a_end) of `owned`; others: jobs in flight when it was submitted
   std::deque<Job> q;
   std::string first_err;                                                      // text of the call that failed (every later call on the context clears rbt_last_error)
@@ -190,7 +221,7 @@ int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rb
   auto collect = [&](bool hand_over) -> int {
     Job jb = q.front(); q.pop_front();
     std::vector<uint8_t*> o(jb.unit.size(), nullptr); std::vector<size_t> on(jb.unit.size(), 0);
-    int r = rbt_wait_gof(ctx, jb.j, o.data(), on.data());
+    int r = wait_job(jb.j, jb.unit, o.data(), on.data());
     if (r == RBT_ERR_NOMEM && (jb.a_end - jb.a > 1 || jb.others > 0)) {
       // run its GOFs again, alone; jobs behind it are collected first (they hold the memory), failed ones among them join the list, in GOF order
       std::vector<std::pair<size_t, size_t>> again{{jb.a, jb.a_end}};
@@ -199,7 +230,7 @@ int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rb
       while (!q.empty() && !rr) {
         Job k = q.front(); q.pop_front();
         std::vector<uint8_t*> ko(k.unit.size(), nullptr); std::vector<size_t> kn(k.unit.size(), 0);
-        int r2 = rbt_wait_gof(ctx, k.j, ko.data(), kn.data());
+        int r2 = wait_job(k.j, k.unit, ko.data(), kn.data());
         if (r2 == RBT_ERR_NOMEM) again.push_back({k.a, k.a_end}); else if (r2) rr = note(r2);
         for (size_t u = 0; u < k.unit.size(); u++) { if (!r2 && !rr) rr = note(rbt_byte_to_sample_stream(ko[u], kn[u], &repl[k.unit[u]].p, &repl[k.unit[u]].n)); rbt_free(ko[u]); }
       }
@@ -220,7 +251,7 @@ int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rb
     if (todo.empty()) { rc = collect(true); continue; }
     if (!q.empty() && (tight || !fits())) { rc = collect(true); continue; }   // make room first
     const size_t a = todo.front().first, a_end = todo.front().second; todo.pop_front();
-    std::vector<Buf> conv; std::vector<const uint8_t*> ip; std::vector<size_t> in_n; std::vector<rbt_stream_params> sp; Job jb{nullptr, {}, owned[a_end - 1], a, a_end, 0};
+    std::vector<Buf> conv; std::vector<const uint8_t*> ip; std::vector<size_t> in_n; std::vector<rbt_stream_params> sp; std::vector<rbt_rate_target> tg; Job jb{nullptr, {}, owned[a_end - 1], a, a_end, 0};
     struct FreeConv { std::vector<Buf>& c; ~FreeConv() { for (auto& b : c) free(b.p); } } free_conv{conv};   // the inputs may go as soon as submit returns
     for (size_t b = a; b < a_end && !rc; b++)
       for (const Pick& pk : picks[owned[b]]) {
@@ -231,11 +262,16 @@ int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rb
         s.video_type = pk.video_type; s.qp = pk.video_type == RBT_VIDEO_GEOMETRY ? p->geometry_qp : (pk.video_type == RBT_VIDEO_ATTRIBUTE ? p->attribute_qp : 8);
         s.occupancy_precision = p->occupancy_precision; s.log2_ctb = p->log2_ctb; s.ctb_rows_per_slice = p->ctb_rows_per_slice; s.md5_sei = p->md5_sei; s.verify_md5 = p->verify_md5; s.occupancy_rd = pk.video_type != RBT_VIDEO_OCCUPANCY ? p->occupancy_rd : 0; s.preset = p->preset;
         sp.push_back(s);
+        // the budget of a geometry / attribute unit: ceil(bits per picture x pictures of the unit / 8) bytes of Annex-B, over the whole QP range
+        rbt_rate_target t; memset(&t, 0, sizeof(t)); t.struct_size = (uint32_t)sizeof(t);
+        const uint32_t bits = pk.video_type == RBT_VIDEO_GEOMETRY ? rate.geometry_bits : (pk.video_type == RBT_VIDEO_ATTRIBUTE ? rate.attribute_bits : 0);
+        if (bits) { t.target_bytes = ((uint64_t)bits * count_pictures(in + U[pk.unit].offset + 4, U[pk.unit].size - 4) + 7) / 8; if (!t.target_bytes) t.target_bytes = 1; }
+        tg.push_back(t);
       }
     for (auto& c : conv) { ip.push_back(c.p); in_n.push_back(c.n); }
     if (!rc && (int)ip.size() > RBT_MAX_STREAMS) rc = RBT_ERR_PARAM;
     while (!rc) {
-      rc = rbt_submit_gof(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), &jb.j);
+      rc = rate.on() ? rbt_submit_gof_rate(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), tg.data(), &jb.j) : rbt_submit_gof(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), &jb.j);
       if (rc == RBT_ERR_BUSY && !q.empty()) { rc = collect(true); continue; }  // every slot taken: take the oldest result first (and hand its GOFs over)
       note(rc);
       break;
@@ -250,7 +286,9 @@ int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rb
   if (!rc) rc = deliver(n_gofs);                                              // GOFs behind the last job (no video units of their own)
   if (rc) rbt_internal_set_error(ctx, first_err.empty() ? rbt_strerror(rc) : first_err.c_str());
   return rc;
-} RBT_CATCH
+}
+}  // namespace
+extern "C" {
 
 // the whole file at once: the stream walk with a sink that keeps every unit, then PCCBitstreamWriter::write over all of them
 namespace { struct Keep { std::vector<std::vector<uint8_t>> unit; };
@@ -268,6 +306,26 @@ int rbt_transcode_v3c(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_p
   std::vector<const uint8_t*> up; std::vector<size_t> un;
   for (auto& u : k.unit) { up.push_back(u.data()); un.push_back(u.size()); }
   return rbt_v3c_write(up.data(), un.data(), (int)up.size(), p->forced_unit_size_precision_bytes, out, n_out);
+} RBT_CATCH
+// rbt_transcode_v3c with byte budgets for the geometry / attribute units (include/rbt.h)
+int rbt_transcode_v3c_rate(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, uint32_t geometry_bits_per_picture, uint32_t attribute_bits_per_picture,
+                           uint8_t** out, size_t* n_out, rbt_rate_result** per_gof) try {
+  if (!ctx || !in || !p || !out || !n_out) return RBT_ERR_PARAM;
+  *out = nullptr; *n_out = 0; if (per_gof) *per_gof = nullptr;
+  if (p->occupancy_rd && (geometry_bits_per_picture || attribute_bits_per_picture)) { rbt_internal_set_error(ctx, "a rate target cannot be combined with occupancy_rd"); return RBT_ERR_PARAM; }
+  rbt_v3c_stat st;
+  int rc = rbt_v3c_stats(in, n, &st);
+  if (rc) return rc;
+  WalkRate rate; rate.geometry_bits = geometry_bits_per_picture; rate.attribute_bits = attribute_bits_per_picture;
+  rate.per_gof = (rbt_rate_result*)calloc((size_t)(st.n_gofs > 0 ? st.n_gofs : 1) * 2, sizeof(rbt_rate_result));
+  if (!rate.per_gof) return RBT_ERR_NOMEM;
+  Keep k;
+  rc = walk(ctx, in, n, p, keep_units, &k, rate);
+  std::vector<const uint8_t*> up; std::vector<size_t> un;
+  for (auto& u : k.unit) { up.push_back(u.data()); un.push_back(u.size()); }
+  if (!rc) rc = rbt_v3c_write(up.data(), un.data(), (int)up.size(), p->forced_unit_size_precision_bytes, out, n_out);
+  if (rc || !per_gof) free(rate.per_gof); else *per_gof = rate.per_gof;
+  return rc;
 } RBT_CATCH
 
 }  // extern "C"
