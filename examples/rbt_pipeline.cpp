@@ -8,6 +8,10 @@
 //       [--geometry-kbps K] [--attribute-kbps K] [--pictures-per-second F] anywhere behind --v3c: the geometry / attribute video is transcoded to that bit rate instead of
 //       at its QP (rbt_transcode_v3c_rate: a budget of K * 1000 / F bits per picture for every GOF's unit; F defaults to 60, two maps of 30 point-cloud frames a second),
 //       and the QP every GOF ended at is printed
+//       [--geometry-psnr DB] [--attribute-psnr DB] [--occupied] anywhere behind --v3c: the geometry / attribute video is transcoded to the highest QP that keeps the luma
+//       PSNR of every GOF's unit against its decoded input at or above DB (rbt_transcode_v3c_quality), and one line per GOF says q*, the bytes and the PSNRs. --occupied:
+//       the floors look at the occupied samples, and the units are coded occupancy-aware (occupancy_rd), so the bytes differ from a run without it and an input without
+//       a pooled occupancy unit is refused; it needs at least one floor. Not together with a bit rate.
 //
 // File format (little endian, test harness only): u32 n_gofs, then per GOF three sub-bitstreams in the order occupancy, geometry,
 // attribute, each as u32 size + Annex-B bytes. The output file has the same layout with the re-encoded streams.
@@ -34,20 +38,27 @@ static bool read_all(const char* path, std::vector<Gof>& gofs) {
 }
 
 static int v3c_main(int argc, char** argv) {
-  double geo_kbps = 0, attr_kbps = 0, pps = 60;
+  double geo_kbps = 0, attr_kbps = 0, pps = 60, geo_db = 0, attr_db = 0; int occupied = 0;
   { int k = 2;                // the rate options out of the argument list, the positional arguments stay where they were
     for (int i = 2; i < argc; i++) {
-      double* v = !strcmp(argv[i], "--geometry-kbps") ? &geo_kbps : !strcmp(argv[i], "--attribute-kbps") ? &attr_kbps : !strcmp(argv[i], "--pictures-per-second") ? &pps : nullptr;
-      if (v && i + 1 < argc) *v = atof(argv[++i]); else argv[k++] = argv[i];
+      double* v = !strcmp(argv[i], "--geometry-kbps") ? &geo_kbps : !strcmp(argv[i], "--attribute-kbps") ? &attr_kbps : !strcmp(argv[i], "--pictures-per-second") ? &pps :
+                  !strcmp(argv[i], "--geometry-psnr") ? &geo_db : !strcmp(argv[i], "--attribute-psnr") ? &attr_db : nullptr;
+      if (!strcmp(argv[i], "--occupied")) occupied = 1;
+      else if (v && i + 1 < argc) *v = atof(argv[++i]); else argv[k++] = argv[i];
     }
     argc = k; }
   if (geo_kbps < 0 || attr_kbps < 0 || pps <= 0) { fprintf(stderr, "bit rates must not be negative and --pictures-per-second must be positive\n"); return 2; }
+  if (geo_db < 0 || attr_db < 0 || geo_db > 2000 || attr_db > 2000) { fprintf(stderr, "PSNR floors must be between 0 and 2000 dB\n"); return 2; }
+  const bool floors = geo_db > 0 || attr_db > 0;
+  if (occupied && !floors) { fprintf(stderr, "--occupied says which samples a PSNR floor looks at: give --geometry-psnr or --attribute-psnr with it\n"); return 2; }
+  if (floors && (geo_kbps > 0 || attr_kbps > 0)) { fprintf(stderr, "a PSNR floor and a bit rate cannot be combined in one call\n"); return 2; }
   const uint32_t geo_bits = (uint32_t)(geo_kbps * 1000.0 / pps + 0.5), attr_bits = (uint32_t)(attr_kbps * 1000.0 / pps + 0.5);
   if (argc < 4) { fprintf(stderr, "usage: %s --v3c in.bin out.bin [depth] [geometryQP] [attributeQP] [occupancyPrecision]\n", argv[0]); return 2; }
   const int depth = argc > 4 ? atoi(argv[4]) : 8;
   rbt_v3c_params vp; memset(&vp, 0, sizeof(vp));
   vp.geometry_qp = argc > 5 ? atoi(argv[5]) : 24; vp.attribute_qp = argc > 6 ? atoi(argv[6]) : 32; vp.occupancy_precision = argc > 7 ? atoi(argv[7]) : 4;
   vp.ctb_rows_per_slice = -1; vp.gofs_per_job = 0;   // job shape by the length of the walk (rbt_job_shape), `depth` is the cap
+  vp.occupancy_rd = occupied;
   std::vector<uint8_t> in;
   FILE* f = fopen(argv[2], "rb"); if (!f) { fprintf(stderr, "cannot read %s\n", argv[2]); return 2; }
   fseek(f, 0, SEEK_END); long sz = ftell(f); fseek(f, 0, SEEK_SET); in.resize(sz > 0 ? (size_t)sz : 0);
@@ -57,9 +68,10 @@ static int v3c_main(int argc, char** argv) {
   int rc = rbt_create(&ctx, 0, 0, 1);
   if (rc != RBT_OK) { fprintf(stderr, "rbt_create: %s\n", rbt_strerror(rc)); return 1; }
   uint8_t* out = nullptr; size_t n = 0;
-  rbt_rate_result* per_gof = nullptr;
+  rbt_rate_result* per_gof = nullptr; rbt_quality_result* q_per_gof = nullptr;
   if ((rc = rbt_set_depth(ctx, depth)) == RBT_OK)
-    rc = geo_bits || attr_bits ? rbt_transcode_v3c_rate(ctx, in.data(), in.size(), &vp, geo_bits, attr_bits, &out, &n, &per_gof) : rbt_transcode_v3c(ctx, in.data(), in.size(), &vp, &out, &n);
+    rc = floors ? rbt_transcode_v3c_quality(ctx, in.data(), in.size(), &vp, (int32_t)(geo_db * 1000.0 + 0.5), (int32_t)(attr_db * 1000.0 + 0.5), occupied ? RBT_QUALITY_OCCUPIED : RBT_QUALITY_ALL, &out, &n, &q_per_gof) :
+         geo_bits || attr_bits ? rbt_transcode_v3c_rate(ctx, in.data(), in.size(), &vp, geo_bits, attr_bits, &out, &n, &per_gof) : rbt_transcode_v3c(ctx, in.data(), in.size(), &vp, &out, &n);
   if (rc != RBT_OK) { fprintf(stderr, "rbt_transcode_v3c: %s %s\n", rbt_strerror(rc), rbt_last_error(ctx)); rbt_destroy(ctx); return 1; }
   if (per_gof) {
     rbt_v3c_stat st;
@@ -69,6 +81,15 @@ static int v3c_main(int argc, char** argv) {
                                                             (unsigned long long)r.bytes, r.met ? "met" : "missed", r.n_encodes);
     }
     rbt_free(per_gof);
+  }
+  if (q_per_gof) {
+    rbt_v3c_stat st;
+    if (rbt_v3c_stats(in.data(), in.size(), &st) == RBT_OK) for (int g = 0; g < st.n_gofs; g++) for (int t = 0; t < 2; t++) {
+      const rbt_quality_result& r = q_per_gof[2 * g + t];
+      if (r.n_encodes) printf("GOF %d %s: QP %d (probe %d, start %d), %llu B, Y %.3f dB, occupied Y %.3f dB, Cb %.3f Cr %.3f dB, floor %s, %d encodes\n", g, t ? "attribute" : "geometry", r.qp, r.qp_probe,
+                              r.qp_start, (unsigned long long)r.bytes, r.psnr[0], r.psnr_occ[0], r.psnr[1], r.psnr[2], (t ? attr_db : geo_db) > 0 ? (r.met ? "met" : "missed") : "none", r.n_encodes);
+    }
+    rbt_free(q_per_gof);
   }
   rbt_destroy(ctx);
   f = fopen(argv[3], "wb"); if (!f) return 2;

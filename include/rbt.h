@@ -212,6 +212,63 @@ int rbt_level_census(rbt_ctx* ctx, const int16_t* y, const int16_t* cb, const in
 typedef struct { int n_pictures; uint32_t* hist; uint64_t* picture_bytes; uint64_t estimate[52]; double census_ms; } rbt_rate_table;
 int rbt_rate_estimate(rbt_ctx* ctx, const uint8_t* annexb, size_t n, int video_type, rbt_rate_table* out);
 
+/* ---- transcoding to a PSNR floor (csrc/rbt_quality.h) ----
+ * "Keep the output within X dB of the input and spend as few bytes as possible." When a re-encode finishes both pictures are in device memory - the decoded input is the
+ * encoder's source, and the encoder's reconstruction after its last filter is bit for bit what a decoder makes of the output - so the distortion costs one streaming kernel
+ * (k_picture_sse) behind the trial encode's last filter and nine words of read-back per picture.
+ *
+ * 1. Sums. Per picture and plane c (Y, Cb, Cr), unsigned 64-bit integers: sse[c] = the sum of (A - B)^2 over the plane (w x h for luma, w/2 x h/2 for chroma), A the decoded
+ *    input seen through its conformance window, B the reconstruction of the displayed w x h area (the coding padding is excluded); sse_occ[c] the same sum over the occupied
+ *    samples and n_occ[c] their number. Occupied, with an occupancy luma plane O of ow x oh samples: s = w / ow must equal h / oh, both divisions whole, s >= 1; luma sample
+ *    (x, y) is occupied iff O[y / s][x / s] > 0, chroma sample (x, y) iff luma sample (2x, 2y) is. Without a map sse_occ and n_occ are 0. Integer sums: exact, and
+ *    independent of the order of arrival.
+ * 2. PSNR. psnr = 10.0 * log10((double)peak * peak * (double)samples / (double)sse) with peak = 2^bit_depth - 1; +inf for sse == 0 with samples > 0, 0 for samples == 0.
+ * 3. Occupancy source of an entry: the nearest occupancy entry in front of it that this call pools (the rule of occupancy_rd), if the entry's picture count is a multiple of
+ *    the occupancy frame count and there is one whole scale in both directions. Picture k uses occupancy frame k * n_occ / cnt; O is the pooled luma plane, the one the output
+ *    occupancy stream carries. When an entry has a source, sse_occ is reported whatever `region` says.
+ * 4. meets(q), on plane 0 of the chosen region: true when samples == 0 (nothing to protect); true when sse == 0; otherwise psnr >= min_psnr_mdb / 1000.0, in double as written.
+ * 5. Walk. lo = qp_min, hi = qp_max (0 = 51), 0 <= lo <= hi <= 51. q0 = clamp(params[i].qp, lo, hi) is encoded first. qs = q0 when its psnr is +inf, otherwise
+ *    qs = clamp(q0 + (int)(psnr(q0) - F), lo, hi) with F = min_psnr_mdb / 1000.0 and a cast that truncates toward zero: one QP step is 2^(1/6) of the quantiser's step size,
+ *    about 1 dB - no tuned constant.
+ *      meets(qs):  q* starts at qs and goes up while q* < hi and meets(q* + 1); met = 1.
+ *      otherwise:  q* starts at qs and goes down while q* > lo and !meets(q*); met = meets(q*).
+ *    The distortion is NOT monotone in q - the 64x64 geometry maps of the tests give 41.737, 41.116, 41.186, 39.719 dB at QP 34..37 - so the walk is the definition, and it
+ *    says where it starts. A floor that even lo misses is no error: the stream at lo comes back with met = 0 and RBT_OK. The returned stream is byte for byte
+ *    rbt_transcode_gof's at qp = q* with the same parameters, occupancy_rd included. Rounds: q0; then qs - 1, qs, qs + 1; then two at a time in the walk's direction; a QP
+ *    already tried is never encoded again: n_encodes <= |q* - qs| + 5.
+ * min_psnr_mdb 0: the entry is coded at params[i].qp and its distortion is reported (qp = qp_probe = qp_start = params[i].qp, met = 1, n_encodes = 1). Occupancy entries
+ * are coded as rbt_submit_gof codes them; their result carries qp, bytes and zeros.
+ * RBT_ERR_PARAM (reason in rbt_last_error; nothing is submitted and the context stays usable): struct_size that is not sizeof(rbt_quality_target); a bad range; an unknown
+ * region; a negative min_psnr_mdb; a floor on an occupancy entry; RBT_QUALITY_OCCUPIED on an entry without an occupancy source (or with a shape rule 3 refuses);
+ * occupancy_rd together with verify_md5, as in rbt_submit_gof.
+ * Submit enqueues the decoders and the occupancy pipelines; the geometry / attribute pipelines are encoded in the wait half, in rounds on the job's streams. The pooled
+ * occupancy planes and the per-unit maps of occupancy_rd stay alive until the job is collected, and the first trial encode starts only after the occupancy pipeline has made
+ * them. A job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality only, and rbt_wait_gof_quality collects no other job: any other pairing is RBT_ERR_PARAM and the
+ * job stays collectable. rbt_job_memory counts the arenas of the first round (one trial encode per geometry / attribute entry).
+ * Not built: a floor per picture (the floor is on the stream's sum), a floor on the point-to-point distortion D1 (needs the atlas), a floor and a byte budget in one call. */
+enum { RBT_QUALITY_ALL = 0, RBT_QUALITY_OCCUPIED = 1 };
+typedef struct {
+  uint32_t struct_size;    /* sizeof(rbt_quality_target): checked */
+  int32_t  min_psnr_mdb;   /* floor on the luma PSNR of the entry's output against its decoded input, 1/1000 dB; 0 = none: coded at params[i].qp, distortion reported */
+  int      region;         /* RBT_QUALITY_*: which samples the floor looks at */
+  int      qp_min, qp_max; /* the walk's range; qp_max 0 = 51 */
+} rbt_quality_target;
+typedef struct {
+  int qp, qp_probe, qp_start, met, n_encodes;   /* q*, q0, qs, met, distinct QPs encoded */
+  uint64_t bytes;                               /* size of the returned stream */
+  uint64_t sse[3], samples[3];                  /* of the returned stream, summed over its pictures; Y, Cb, Cr */
+  uint64_t sse_occ[3], samples_occ[3];          /* occupied samples; zeros when the entry has no occupancy source */
+  double psnr[3], psnr_occ[3];
+} rbt_quality_result;
+int rbt_submit_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job);
+int rbt_wait_gof_quality(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_quality_result* results);   /* results: n entries */
+int rbt_transcode_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets,
+                              uint8_t** annexb_out, size_t* n_out, rbt_quality_result* results);   /* submit + wait */
+/* The kernel on host arrays (tests): a and b are n_frames planar 4:2:0 pictures each (width x height luma, then two planes of width/2 x height/2, back to back); occ is NULL
+ * or n_frames planes of ow x oh samples, one per picture. out: n_frames x 3 x {sse, sse_occ, n_occ}. RBT_ERR_PARAM: odd sizes, sizes above 8192, a map whose scale is
+ * not whole and equal in both directions. rbt_get_stats afterwards: gpu_ms = the device time between events around the kernel's launches, everything else 0. */
+int rbt_picture_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int width, int height, int n_frames, const uint16_t* occ, int ow, int oh, uint64_t* out);
+
 /* The two halves exposed on their own (SURVEY.md 8(b) alternative seam; used by the parity tests).
  * Picture sizes: any even width / height. Sizes that are not multiples of 8 (all-intra) / 16 (gop 2) are coded padded with a
  * conformance window in the SPS (as libx265 does for the reference); rbt_decode returns the cropped pictures. */
@@ -360,6 +417,12 @@ int rbt_transcode_v3c_stream(rbt_ctx* ctx, const uint8_t* in, size_t n, const rb
  * walk's. Any rate target together with occupancy_rd: RBT_ERR_PARAM. */
 int rbt_transcode_v3c_rate(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, uint32_t geometry_bits_per_picture, uint32_t attribute_bits_per_picture,
                            uint8_t** out, size_t* n_out, rbt_rate_result** per_gof);
+
+/* rbt_transcode_v3c's walk with PSNR floors per unit type (rbt_submit_gof_quality / rbt_wait_gof_quality, above), walked over the QPs 0..51 from geometry_qp / attribute_qp;
+ * 0 for a type means constant QP, and with both 0 the output is rbt_transcode_v3c's. region: RBT_QUALITY_*. p->occupancy_rd is allowed. *per_gof as in
+ * rbt_transcode_v3c_rate: two results per GOF of the input, geometry then attribute. Multi-GPU ownership and the memory-bounded depth are the walk's. */
+int rbt_transcode_v3c_quality(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, int32_t geometry_min_psnr_mdb, int32_t attribute_min_psnr_mdb, int region,
+                              uint8_t** out, size_t* n_out, rbt_quality_result** per_gof);
 
 /* ---- colour half of the metric: 4:4:4 up-conversion, RGB, colour PSNR (csrc/rbt_color.h) ----
  * Planar 4:2:0 pictures (samples of bit_depth 8 or 10 in uint16_t) -> n_frames x 3 planes of width x height 16-bit samples, as the decoder converts an attribute video

@@ -127,6 +127,23 @@ class RateResult(C.Structure):
     _fields_ = [("qp", C.c_int), ("qp_estimate", C.c_int), ("met", C.c_int), ("n_encodes", C.c_int), ("bytes", C.c_uint64), ("estimate_bytes", C.c_uint64)]
 
 
+RBT_QUALITY_ALL, RBT_QUALITY_OCCUPIED = 0, 1
+
+
+class QualityTarget(C.Structure):
+    """rbt_quality_target; struct_size is filled in. min_psnr_mdb 0 = no floor (coded at the entry's QP, distortion reported), qp_max 0 = 51"""
+    _fields_ = [("struct_size", C.c_uint32), ("min_psnr_mdb", C.c_int32), ("region", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int)]
+
+    def __init__(self, min_psnr_mdb=0, region=RBT_QUALITY_ALL, qp_min=0, qp_max=0):
+        super().__init__(C.sizeof(QualityTarget), min_psnr_mdb, region, qp_min, qp_max)
+
+
+class QualityResult(C.Structure):
+    """rbt_quality_result: q*, the probe q0, the walk's start qs, met, distinct QPs encoded, the stream's size, its sums and PSNRs (Y, Cb, Cr; all samples and occupied)"""
+    _fields_ = [("qp", C.c_int), ("qp_probe", C.c_int), ("qp_start", C.c_int), ("met", C.c_int), ("n_encodes", C.c_int), ("bytes", C.c_uint64),
+                ("sse", C.c_uint64 * 3), ("samples", C.c_uint64 * 3), ("sse_occ", C.c_uint64 * 3), ("samples_occ", C.c_uint64 * 3), ("psnr", C.c_double * 3), ("psnr_occ", C.c_double * 3)]
+
+
 class RateTable(C.Structure):
     """rbt_rate_table"""
     _fields_ = [("n_pictures", C.c_int), ("hist", C.POINTER(C.c_uint32)), ("picture_bytes", C.POINTER(C.c_uint64)), ("estimate", C.c_uint64 * 52), ("census_ms", C.c_double)]
@@ -204,6 +221,12 @@ def load(path=None):
     L.rbt_wait_gof_rate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(RateResult)]
     L.rbt_transcode_gof_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(RateTarget), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                          C.POINTER(RateResult)]
+    L.rbt_submit_gof_quality.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QualityTarget), C.POINTER(C.c_void_p)]
+    L.rbt_wait_gof_quality.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(QualityResult)]
+    L.rbt_transcode_gof_quality.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QualityTarget), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                            C.POINTER(QualityResult)]
+    L.rbt_picture_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.rbt_transcode_v3c_quality.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(QualityResult))]
     L.rbt_level_census.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rbt_rate_estimate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(RateTable)]
     L.rbt_transcode_v3c_rate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(RateResult))]
@@ -516,6 +539,75 @@ class Context:
             res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
             self.L.rbt_free(outs[i])
         return res, [_result_dict(r) for r in rs]
+
+    def submit_gof_quality(self, streams, params, targets):
+        """rbt_submit_gof_quality: submit_gof with one QualityTarget per entry (min_psnr_mdb 0 = constant QP, distortion reported); returns a job for wait_gof_quality"""
+        k = len(streams)
+        ins = (C.c_char_p * k)(*streams)
+        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
+        ps = (StreamParams * k)(*params)
+        ts = (QualityTarget * k)(*targets)
+        job = C.c_void_p()
+        self._chk(self.L.rbt_submit_gof_quality(self.h, k, ins, sizes, ps, ts, C.byref(job)))
+        return (job, k)
+
+    def wait_gof_quality(self, job):
+        """rbt_wait_gof_quality -> ([stream bytes, ...], [result dict, ...])"""
+        h, k = job
+        outs = (C.c_void_p * k)()
+        ns = (C.c_size_t * k)()
+        rs = (QualityResult * k)()
+        self._chk(self.L.rbt_wait_gof_quality(self.h, h, outs, ns, rs))
+        res = []
+        for i in range(k):
+            res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
+            self.L.rbt_free(outs[i])
+        return res, [_result_dict(r) for r in rs]
+
+    def transcode_gof_quality(self, streams, params, targets):
+        """rbt_transcode_gof_quality: submit + wait"""
+        k = len(streams)
+        ins = (C.c_char_p * k)(*streams)
+        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
+        ps = (StreamParams * k)(*params)
+        ts = (QualityTarget * k)(*targets)
+        outs = (C.c_void_p * k)()
+        ns = (C.c_size_t * k)()
+        rs = (QualityResult * k)()
+        self._chk(self.L.rbt_transcode_gof_quality(self.h, k, ins, sizes, ps, ts, outs, ns, rs))
+        res = []
+        for i in range(k):
+            res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
+            self.L.rbt_free(outs[i])
+        return res, [_result_dict(r) for r in rs]
+
+    def picture_sse(self, a, b, w, h, occ=None):
+        """rbt_picture_sse: planar 4:2:0 pictures a, b ([n, w*h*3/2] uint16) and, or None, one occupancy plane per picture ([n, oh, ow] uint16) -> uint64 [n, 3, 3]:
+        per picture and plane (Y, Cb, Cr) the sums sse, sse_occ, n_occ; stats()["gpu_ms"] afterwards: the device time of the kernel's launches"""
+        a = np.ascontiguousarray(a, dtype=np.uint16).reshape(-1, w * h * 3 // 2)
+        b = np.ascontiguousarray(b, dtype=np.uint16).reshape(-1, w * h * 3 // 2)
+        if a.shape != b.shape:
+            raise ValueError("a and b must hold the same number of pictures")
+        ow = oh = 0
+        if occ is not None:
+            occ = np.ascontiguousarray(occ, dtype=np.uint16)
+            if occ.ndim != 3 or occ.shape[0] != a.shape[0]:
+                raise ValueError("occ must be [n, oh, ow]")
+            oh, ow = occ.shape[1:]
+        out = np.zeros((a.shape[0], 3, 3), np.uint64)
+        self._chk(self.L.rbt_picture_sse(self.h, a.ctypes.data, b.ctypes.data, w, h, a.shape[0], occ.ctypes.data if occ is not None else None, ow, oh, out.ctypes.data))
+        return out
+
+    def transcode_v3c_quality(self, data: bytes, geometry_qp, attribute_qp, geometry_min_psnr_mdb=0, attribute_min_psnr_mdb=0, region=RBT_QUALITY_ALL, occupancy_precision=4, forced_precision_bytes=0,
+                              log2_ctb=5, rows_per_slice=-1, md5_sei=0, verify_md5=0, gofs_per_job=1, occupancy_rd=0, preset=0):
+        """rbt_transcode_v3c_quality -> (sample stream, [(geometry result, attribute result) per GOF of the input])"""
+        p = V3CParams(occupancy_precision, geometry_qp, attribute_qp, forced_precision_bytes, log2_ctb, rows_per_slice, md5_sei, verify_md5, gofs_per_job, occupancy_rd, preset)
+        out, n, rs = C.c_void_p(), C.c_size_t(), C.POINTER(QualityResult)()
+        self._chk(self.L.rbt_transcode_v3c_quality(self.h, data, len(data), C.byref(p), geometry_min_psnr_mdb, attribute_min_psnr_mdb, region, C.byref(out), C.byref(n), C.byref(rs)))
+        n_gofs = v3c_stats(data, self.L)["n_gofs"]
+        per = [(_result_dict(rs[2 * g]), _result_dict(rs[2 * g + 1])) for g in range(n_gofs)]
+        self.L.rbt_free(rs)
+        return self._take(out, n), per
 
     def level_census(self, y, cb, cr, qp4, pm4):
         """rbt_level_census: int16 planes y [h, w], cb / cr [h/2, w/2], int8 qp4 and uint8 pm4 [h/4, w/4] -> uint32 [3, 53]"""

@@ -138,7 +138,7 @@ int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t
   return RBT_OK;
 } RBT_CATCH
 
-static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets = nullptr);
+static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr);
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
 int rbt_transcode_substream(rbt_ctx* ctx, const uint8_t* annexb_in, size_t n_in, const rbt_stream_params* p, uint8_t** annexb_out, size_t* n_out) try {
   if (!ctx || !annexb_in || !p || !annexb_out || !n_out) return RBT_ERR_PARAM;
@@ -168,16 +168,31 @@ static int check_targets(std::string& err, int n, const rbt_stream_params* p, co
   }
   return RBT_OK;
 }
-static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets) {
+// the refusals of rbt_submit_gof_quality that the parameters alone decide (those that need the streams' sizes: gof_refused)
+static int check_quality(std::string& err, int n, const rbt_stream_params* p, const rbt_quality_target* t) {
+  for (int i = 0; i < n; i++) {
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    if (t[i].struct_size != sizeof(rbt_quality_target)) { err = who + "rbt_quality_target.struct_size is not sizeof(rbt_quality_target)"; return RBT_ERR_PARAM; }
+    if (t[i].min_psnr_mdb < 0) { err = who + "min_psnr_mdb must not be negative"; return RBT_ERR_PARAM; }
+    if (t[i].region != RBT_QUALITY_ALL && t[i].region != RBT_QUALITY_OCCUPIED) { err = who + "region must be RBT_QUALITY_ALL or RBT_QUALITY_OCCUPIED"; return RBT_ERR_PARAM; }
+    const int lo = t[i].qp_min, hi = t[i].qp_max ? t[i].qp_max : 51;
+    if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
+    if (t[i].min_psnr_mdb && p[i].video_type == RBT_VIDEO_OCCUPANCY) { err = who + "an occupancy stream is coded losslessly and takes no PSNR floor"; return RBT_ERR_PARAM; }
+  }
+  return RBT_OK;
+}
+static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
   RBT_ENTER(ctx);
   if (targets) if (int rc = check_targets(ctx->last_err, n, p, targets)) return rc;
+  if (quality) if (int rc = check_quality(ctx->last_err, n, p, quality)) return rc;
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
-  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets), ctx};
+  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality), ctx};
+  if (quality) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -238,13 +253,15 @@ int rbt_trim(rbt_ctx* ctx) try {
   rbtk::dev_release_pool();
   return RBT_OK;
 } RBT_CATCH
-static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results) {
+static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* quality = nullptr) {
   if (!ctx || !job || !annexb_out || !n_out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   int slot = -1;
   for (int s = 0; s < RBT_MAX_JOBS; s++) if (D.jobs[s] == job) slot = s;
   if (slot < 0 || job->owner != ctx) return RBT_ERR_PARAM;
-  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results);
+  if (rbt::gof_is_quality(job->j) != (quality != nullptr)) {      // the job stays collectable
+    ctx->last_err = quality ? "rbt_wait_gof_quality collects jobs of rbt_submit_gof_quality only" : "a job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality"; return RBT_ERR_PARAM; }
+  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality);
   D.jobs[slot] = nullptr; delete job;
   return rc;
 }
@@ -265,6 +282,28 @@ int rbt_transcode_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in,
   int rc = rbt_submit_gof_rate(ctx, n, annexb_in, n_in, p, targets, &job);
   if (rc) return rc;
   return rbt_wait_gof_rate(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
+// ---- transcoding to a PSNR floor ----
+int rbt_submit_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, targets);
+} RBT_CATCH
+int rbt_wait_gof_quality(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_quality_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  return wait(ctx, job, annexb_out, n_out, nullptr, results);
+} RBT_CATCH
+int rbt_transcode_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets,
+                              uint8_t** annexb_out, size_t* n_out, rbt_quality_result* results) try {
+  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_quality(ctx, n, annexb_in, n_in, p, targets, &job);
+  if (rc) return rc;
+  return rbt_wait_gof_quality(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
+int rbt_picture_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int width, int height, int n_frames, const uint16_t* occ, int ow, int oh, uint64_t* out) try {
+  if (!ctx || !a || !b || !out) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  return rbt::picture_sse_host(ctx->last_err, a, b, width, height, n_frames, occ, ow, oh, out, ctx->stats);
 } RBT_CATCH
 int rbt_level_census(rbt_ctx* ctx, const int16_t* y, const int16_t* cb, const int16_t* cr, int w, int h, const int8_t* qp4, const uint8_t* pm4, uint32_t* hist) try {
   if (!ctx || !y || !cb || !cr || !qp4 || !pm4 || !hist) return RBT_ERR_PARAM;

@@ -9,6 +9,7 @@
 #include "../csrc/rbt_kernels.h"
 #include "../csrc/rbt_hash.h"
 #include "../csrc/rbt_rate.h"
+#include "../csrc/rbt_quality.h"
 #include "rbt_hls.h"
 
 namespace rbt {
@@ -47,6 +48,22 @@ struct CensusSet {
   void launch() const;                           // between the events of T_CENSUS on the current stream
   int fetch();
   ~CensusSet() { rbtk::dev_free(d); }
+};
+
+// Distortion sums of picture pairs in device memory (csrc/rbt_quality.h), used like CensusSet: add() the pairs, upload() before the first kernel of the stream (one copy: the
+// pair table and the zeroed sums), launch() behind the encoder's last filter, fetch() once the stream has got there: RBT_SSE_WORDS 64-bit words per pair come back.
+// With `ext` set before upload() the sums live there instead (RBT_SSE_WORDS words per pair, zeroed by the owner): an encode batch keeps them behind its slice table, and
+// they come back with the slice sizes in one copy (encode_finish).
+struct SseSet {
+  std::vector<RbtSsePic> pics; int max_chunks = 0; uint64_t* ext = nullptr;
+  std::vector<uint8_t> staging; uint8_t* d = nullptr; size_t o_out = 0;
+  std::vector<uint64_t> words;                   // after fetch(): {sse, sse_occ, n_occ} x 3 planes per pair, in add() order
+  void add(const RbtSsePic& p);
+  bool empty() const { return pics.empty(); }
+  int upload();
+  void launch() const;
+  int fetch();
+  ~SseSet() { rbtk::dev_free(d); }
 };
 
 enum { T_PARSE = 0, T_RECON = 1, T_CENSUS = 2, T_ANALYSE = 3, T_ENCODE = 4, T_ENTROPY = 5, T_ALL = 6, T_POOL = 7, T_INTER = 8, T_ENTROPY_I = 9, T_COUNT = 10 };   // (the device keeps 16 events per lane, rbt_pcc.cpp has the other six; T_CENSUS took the slot of a filter timer nothing used)

@@ -10,6 +10,7 @@
 #include "rbt_batch.h"
 #include "rbt_transcode.h"
 #include "rbt_rate_walk.h"
+#include "rbt_quality_walk.h"
 
 namespace rbt {
 
@@ -44,6 +45,7 @@ struct EncodeBatch {
   uint8_t* d_zero = nullptr; size_t zero_bytes = 0; bool wpp = false;   // launch tickets (3 words) + row progress of the wavefront mode
   int main_stream = 0, aux_stream = -1;          // aux_stream >= 0: the intra part was enqueued there (its timers live there)
   HashSet hash; std::vector<int> hash_idx;      // md5_sei: the reconstructions to hash (after SAO), index of each picture in `hash` (-1: none)
+  size_t n_sums = 0; uint64_t* d_sums = nullptr; std::vector<uint64_t> sums;   // quality floors: RBT_SSE_WORDS distortion words per picture behind the slice table (set n_sums before encode_build); after encode_finish: their values
   std::vector<int32_t> lists_keep; size_t off_i = 0, off_ideb = 0, off_p = 0, off_sl = 0, off_sl_p = 0, off_isao = 0, off_psao = 0, off_pdeb = 0; int n_pdeb = 0, n_i = 0, n_ideb = 0, n_p = 0, n_sl_i = 0, n_sl_p = 0, n_isao = 0, n_psao = 0;   // index lists (encode_upload_lists)
   std::string err;
   ~EncodeBatch() { rbtk::dev_free(arena); }
@@ -109,6 +111,7 @@ static void encode_lay_out(EncodeBatch& b, Arena& a) {
   b.d_cs = a.take<uint16_t>(cs_words);
   if (a.base) { uint16_t* at = b.d_cs; for (size_t i = 0; i < nf; i++) { b.frames[i].ctb_slice = at; at += (size_t)b.frames[i].cfg.w_ctb * b.frames[i].cfg.h_ctb; } }
   b.d_frames = a.take<RbtFrame>(nf); b.d_slices = a.take<RbtSlice>(ns);
+  if (b.n_sums) b.d_sums = a.take<uint64_t>(b.n_sums);      // right behind the slices: one copy brings both back
   b.d_lists = a.take<int32_t>((nf + ns) * 3); b.d_dst = a.take<uint32_t>(ns);
   // the packed output holds every slice back to back: as large as the slice buffers together, so that slices which fit their buffers always fit it (half of that, which
   // it had before, is less than noise needs in every QP band: DESIGN.md 9.5)
@@ -266,6 +269,11 @@ static void encode_launch_entropy_rest(EncodeBatch& b) {
 }
 static int encode_finish(EncodeBatch& b, std::vector<std::vector<uint8_t>>& outs, rbt_stats& st) {
   size_t nf = b.frames.size(), ns = b.slices.size();
+  if (b.n_sums) {      // the slice sizes and the distortion words in one copy: the span from the slice table to the end of the words
+    const size_t off = (size_t)((uint8_t*)b.d_sums - (uint8_t*)b.d_slices); std::vector<uint8_t> span(off + b.n_sums * 8);
+    if (rbtk::d2h(span.data(), b.d_slices, span.size())) { b.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+    memcpy(b.slices.data(), span.data(), ns * sizeof(RbtSlice)); b.sums.resize(b.n_sums); memcpy(b.sums.data(), span.data() + off, b.n_sums * 8);
+  } else
   if (rbtk::d2h(b.slices.data(), b.d_slices, ns * sizeof(RbtSlice))) { b.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
   std::vector<uint32_t> dst(ns); size_t total = 0;
   // (the packed buffer is as large as the slice buffers together: total <= out_total once every slice fits)
@@ -421,6 +429,16 @@ struct RatePipe {
   std::vector<std::vector<uint8_t>> o1;        // the pipeline's streams in group order, as they settle
   bool done = false;
 };
+// Quality floors: the occupancy source of an entry (include/rbt.h, "transcoding to a PSNR floor", rule 3), kept in the job because the pipelines that use it are encoded in
+// the wait half: the pooled luma planes of the occupancy stream, and for occupancy_rd the per-4x4-unit maps made of them (both live in GofJob::pooled until the job goes)
+struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
+struct QualityPipe {
+  std::vector<QualityWalk> walks; std::vector<int> n_enc;
+  std::vector<RateCand> cands;                 // the round to run or running
+  std::unique_ptr<EncodeBatch> eb; std::unique_ptr<SseSet> sse;   // the round in flight on the pipeline's stream
+  std::vector<std::vector<uint8_t>> o1; std::vector<QualitySums> sums;   // the pipeline's streams in group order, as they settle, and their sums
+  bool done = false;
+};
 struct GofJob {
   int n = 0, slot = 0, ng = 0, rc = 0;
   std::vector<std::vector<int>> groups; std::vector<int> order;
@@ -439,6 +457,9 @@ struct GofJob {
   // rate targets (rbt_submit_gof_rate): a pipeline that holds a targeted entry is decoded and counted at submit and encoded in the wait half (rate_run_pipeline)
   std::vector<rbt_rate_target> targets; std::vector<char> rate_pipe; std::vector<rbt_rate_result> results; size_t rate_bytes = 0;   // rate_bytes: arenas of the first round of trial encodes
   std::vector<RatePipe> rate;                                // per pipeline
+  // quality floors (rbt_submit_gof_quality): every pipeline with a geometry / attribute entry is decoded at submit and encoded in the wait half (quality_run_pipeline); it
+  // is marked in rate_pipe like a pipeline with a rate target, which keeps it unchained
+  std::vector<rbt_quality_target> qtargets; std::vector<QualityOcc> qocc; std::vector<QualityPipe> qual; std::vector<rbt_quality_result> qresults; bool refused = false;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   ~GofJob() { for (void* q : pooled) rbtk::dev_free(q); }
 };
@@ -456,6 +477,8 @@ static void bind_streams(GofJob& j, int depth) {
 }
 
 size_t gof_memory(const GofJob* j) { return j ? j->dev_bytes + j->rate_bytes : 0; }
+bool gof_is_quality(const GofJob* j) { return j && !j->qtargets.empty(); }
+int gof_refused(const GofJob* j, std::string& err) { if (!j || !j->refused) return 0; err = j->err; return j->rc; }
 static bool has_target(const GofJob& j, int i) { return !j.targets.empty() && j.targets[i].target_bytes != 0; }
 
 // What lives only while a job is submitted
@@ -465,6 +488,7 @@ struct SubmitPlan {
   std::vector<std::vector<PoolJob>> pool_jobs;      // per pipeline: the OR-pool launches, recorded by setup_encode and issued behind the decoder's kernels
   // occupancy-aware coding (rbt_stream_params.occupancy_rd): entry i is coded with the occupancy map of the nearest occupancy entry in front of it, if this call pools it
   std::vector<int> occ_of; std::vector<OccSource> occ_src; std::vector<OccJob> occ_jobs;
+  std::vector<int> meas_of;                         // quality floors: the occupancy entry whose pooled planes say which samples of entry i are occupied, whether or not it is coded with them
   std::vector<char> feeds_any, consumes; std::vector<int> occ_marks;   // per pipeline: others are coded with its occupancy maps / it is coded with some; where on the feeders' streams the maps are complete
 };
 // Pipelines: up to three sub-bitstreams get one pipeline (= HIP stream) each. A call with more (several GOFs at once:
@@ -502,15 +526,22 @@ static int plan_pipelines(GofJob& j, SubmitPlan& s, int depth) {
   bind_streams(j, depth);
   recon_set_depth(depth);
   j.rate_pipe.assign(ng, 0);
-  for (int g = 0; g < ng; g++) for (int i : groups[g]) j.rate_pipe[g] |= (char)has_target(j, i);
-  s.pool_jobs.resize(ng); s.occ_of.assign(n, -1); s.occ_src.resize(n); s.feeds_any.assign(ng, 0); s.consumes.assign(ng, 0);
+  const bool quality = !j.qtargets.empty();
+  for (int g = 0; g < ng; g++) for (int i : groups[g]) j.rate_pipe[g] |= (char)(has_target(j, i) || (quality && p[i].video_type != RBT_VIDEO_OCCUPANCY));
+  s.pool_jobs.resize(ng); s.meas_of.assign(n, -1); s.occ_of.assign(n, -1); s.occ_src.resize(n); s.feeds_any.assign(ng, 0); s.consumes.assign(ng, 0);
   int rc = 0;
   for (int i = 0, last = -1; i < n; i++) {
     if (p[i].video_type == RBT_VIDEO_OCCUPANCY) last = (s.gof_rule && !j.is_pass[i] && p[i].occupancy_precision == 4) ? i : -1;
-    else if (s.gof_rule && p[i].occupancy_rd && last >= 0) { s.occ_of[i] = last; if (p[i].verify_md5 || p[last].verify_md5) { j.err = "occupancy_rd cannot be combined with verify_md5"; rc = RBT_ERR_PARAM; } }
+    else if (quality && s.gof_rule) s.meas_of[i] = last;
+    if (p[i].video_type != RBT_VIDEO_OCCUPANCY && s.gof_rule && p[i].occupancy_rd && last >= 0) { s.occ_of[i] = last; if (p[i].verify_md5 || p[last].verify_md5) { j.err = "occupancy_rd cannot be combined with verify_md5"; rc = RBT_ERR_PARAM; } }
   }
   // a pipeline with a target is encoded in the wait half, where the occupancy maps of the submission are gone (only calls with more than three streams share pipelines)
-  for (int g = 0; g < ng; g++) if (j.rate_pipe[g]) for (int i : groups[g]) if (s.occ_of[i] >= 0) { j.err = "entry " + std::to_string(i) + ": occupancy_rd on an entry that shares a pipeline with a rate-targeted entry"; rc = RBT_ERR_PARAM; }
+  for (int g = 0; g < ng; g++) if (j.rate_pipe[g] && !quality) for (int i : groups[g]) if (s.occ_of[i] >= 0) { j.err = "entry " + std::to_string(i) + ": occupancy_rd on an entry that shares a pipeline with a rate-targeted entry"; rc = RBT_ERR_PARAM; }
+  // quality floors keep the maps in the job; the occupancy pipelines themselves are coded at submit, so an occupancy entry cannot share a pipeline with the others
+  if (quality) for (int g = 0; g < ng; g++) if (j.rate_pipe[g]) for (int i : groups[g]) if (p[i].video_type == RBT_VIDEO_OCCUPANCY) { j.err = "entry " + std::to_string(i) + ": an occupancy entry shares a pipeline with entries of an unknown video type"; rc = RBT_ERR_PARAM; }
+  if (quality) for (int i = 0; i < n; i++) if (j.qtargets[i].region == RBT_QUALITY_OCCUPIED && p[i].video_type != RBT_VIDEO_OCCUPANCY && s.meas_of[i] < 0) {
+    j.err = "entry " + std::to_string(i) + ": RBT_QUALITY_OCCUPIED on an entry without an occupancy source (no pooled occupancy entry in front of it)"; rc = RBT_ERR_PARAM; }
+  if (rc) j.refused = true;
   return rc;
 }
 
@@ -540,13 +571,14 @@ static int build_decoders(GofJob& j, SubmitPlan& s) {
 }
 
 static int rate_measure(GofJob& j, int gi);
+static int quality_prepare(GofJob& j, SubmitPlan& s, int gi);
 // Encoder batches: the pipelines whose occupancy streams others are coded with first (their pooled planes are what the maps are made of), then the rest
 static int build_encoders(GofJob& j, SubmitPlan& s) {
   for (int pass = 0; pass < 2; pass++) for (int k = 0; k < j.ng; k++) {
     const int gi = j.order[k]; const std::vector<int>& gs = j.groups[gi]; EncodeBatch& eb = j.eb[gi]; rbtk::set_stream(job_stream(j, gi));
-    bool feeds = false; for (int i : gs) for (int c = 0; c < j.n; c++) feeds |= s.occ_of[c] == i;
+    bool feeds = false; for (int i : gs) for (int c = 0; c < j.n; c++) feeds |= s.occ_of[c] == i || s.meas_of[c] == i;
     if (feeds != (pass == 0)) continue;
-    if (j.rate_pipe[gi]) { if (int rc = rate_measure(j, gi)) return rc; continue; }      // stays unchained: decoder and census now, encoders in the wait half
+    if (j.rate_pipe[gi]) { if (int rc = j.qtargets.empty() ? rate_measure(j, gi) : quality_prepare(j, s, gi)) return rc; continue; }      // stays unchained: decoder and census now, encoders in the wait half
     for (size_t q = 0; q < gs.size(); q++) {
       const int i = gs[q], io = s.occ_of[i];
       if (int rc = setup_encode(j.db[gi], j.dec_of[gi][q], (int)q, s.p[i], eb, j.pooled, j.err, &s.pool_jobs[gi], io >= 0 ? &s.occ_src[io] : nullptr, io, &s.occ_jobs)) return rc;
@@ -674,6 +706,165 @@ static int rate_run_pipeline(GofJob& j, int gi) {
     if (!w.settled) { j.err = "internal: rate walk did not settle"; return RBT_ERR_PARAM; }
     j.results[w.entry] = rbt_rate_result{w.qstar, w.qe, w.met, r.n_enc[k], (uint64_t)w.tried[w.qstar].size(), w.e_qe};
     r.o1[w.q].swap(w.tried[w.qstar]);
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ quality floors (include/rbt.h, "transcoding to a PSNR floor")
+void SseSet::add(const RbtSsePic& p) { max_chunks = std::max(max_chunks, RBT_SSE_PIC_CHUNKS(p.w, p.h)); pics.push_back(p); }
+int SseSet::upload() {
+  const size_t n = pics.size();
+  o_out = (n * sizeof(RbtSsePic) + 255) & ~(size_t)255;
+  const size_t end = ext ? n * sizeof(RbtSsePic) : o_out + n * RBT_SSE_WORDS * 8;
+  rbtk::dev_free(d);
+  d = (uint8_t*)rbtk::dev_alloc(end);
+  if (!d) return RBT_ERR_NOMEM;
+  for (size_t i = 0; i < n; i++) pics[i].out = (ext ? ext : (uint64_t*)(d + o_out)) + i * RBT_SSE_WORDS;
+  staging.assign(end, 0);
+  memcpy(staging.data(), pics.data(), n * sizeof(RbtSsePic));
+  return rbtk::h2d(d, staging.data(), end) ? RBT_ERR_NO_DEVICE : 0;
+}
+void SseSet::launch() const { rbtk::launch_picture_sse((const RbtSsePic*)d, (int)pics.size(), max_chunks); }
+int SseSet::fetch() {
+  words.assign(pics.size() * RBT_SSE_WORDS, 0);
+  return !words.empty() && rbtk::d2h(words.data(), d + o_out, words.size() * 8) ? RBT_ERR_NO_DEVICE : 0;
+}
+static bool has_floor(const GofJob& j, int i) { return j.qtargets[i].min_psnr_mdb != 0; }
+// the candidates of a round as an encode batch; entries coded with occupancy_rd get the maps the occupancy pipeline made at submit
+static int quality_fill_batch(GofJob& j, int gi, const std::vector<RateCand>& cands, EncodeBatch& eb) {
+  if (int rc = rate_fill_batch(j, gi, cands, eb)) return rc;
+  for (size_t e = 0; e < cands.size(); e++) {
+    const QualityOcc& o = j.qocc[j.groups[gi][cands[e].q]]; EncStreamDesc& d = eb.desc[e];
+    if (!o.maps || d.lossless) continue;
+    d.occ4.resize(d.n_frames); d.occ4_w = o.w4; d.occ4_h = o.h4;
+    for (int k = 0; k < d.n_frames; k++) d.occ4[k] = o.maps + (size_t)((size_t)k * o.n / d.n_frames) * o.w4 * o.h4;
+  }
+  return 0;
+}
+// At submit, behind the encoder batches of the occupancy pipelines: the occupancy source of every entry of the pipeline (rule 3), the maps of occupancy_rd - allocated
+// here, made by the occupancy pipeline's launch_occ_units like those of a constant-QP job -, and what the first round will take (rbt_job_memory): one encode per entry
+static int quality_prepare(GofJob& j, SubmitPlan& s, int gi) {
+  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
+  if (db.frames.empty()) return 0;
+  for (size_t q = 0; q < gs.size(); q++) {
+    const int i = gs[q], io = s.meas_of[i], ds = j.dec_of[gi][q], first = db.stream_first[ds], cnt = db.stream_count[ds];
+    bool has = false;
+    if (io >= 0 && s.occ_src[io].n > 0 && cnt > 0) {
+      const OccSource& os = s.occ_src[io]; const RbtStreamCfg& c = db.frames[first].cfg; const Sps& isps = db.stream_sps[ds];
+      const int dw = c.w - 2 * isps.conf_win[0] - 2 * isps.conf_win[1], dh = c.h - 2 * isps.conf_win[2] - 2 * isps.conf_win[3];
+      if (dw > 0 && dh > 0 && cnt % os.n == 0 && dw % os.ow == 0 && dh % os.oh == 0 && dw / os.ow == dh / os.oh) {
+        has = true; QualityOcc& o = j.qocc[i]; o.occ = os.occ; o.in_step = os.in_step; o.n = os.n; o.ow = os.ow; o.oh = os.oh;
+        if (s.occ_of[i] >= 0) {
+          o.w4 = (dw + 3) / 4; o.h4 = (dh + 3) / 4;
+          uint8_t* maps = (uint8_t*)rbtk::dev_alloc((size_t)os.n * o.w4 * o.h4);
+          if (!maps) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
+          j.pooled.push_back(maps); s.occ_jobs.push_back(OccJob{io, maps, dw, o.w4, o.h4}); o.maps = maps;
+        }
+      }
+    }
+    if (j.qtargets[i].region == RBT_QUALITY_OCCUPIED && !has) {
+      j.err = "entry " + std::to_string(i) + ": RBT_QUALITY_OCCUPIED on an entry whose occupancy source does not fit it (picture count a multiple of the occupancy frames, one whole scale in both directions)";
+      j.refused = true; return RBT_ERR_PARAM; }
+  }
+  std::vector<RateCand> cands; for (size_t q = 0; q < gs.size(); q++) cands.push_back(RateCand{(int)q, j.params[gs[q]].qp, -1});
+  const std::vector<char> taken = db.alias_taken;
+  EncodeBatch eb; int rc = quality_fill_batch(j, gi, cands, eb);
+  if (!rc && (rc = encode_plan(eb)) != 0) j.err = eb.err;
+  db.alias_taken = taken;
+  if (!rc) j.rate_bytes += eb.arena_size;
+  return rc;
+}
+// A round of a pipeline: one encode batch of candidates on the pipeline's stream, and behind its last filter the sums of every candidate picture against the decoded
+// picture it was coded from - EncStreamDesc::src, which no encoder writes to (arena sharing hands out the decoded pictures' dead buffers only)
+static int quality_launch_round(GofJob& j, int gi) {
+  QualityPipe& r = j.qual[gi];
+  if (r.cands.empty()) { r.done = true; return 0; }
+  rbtk::set_stream(job_stream(j, gi));
+  r.eb.reset(new EncodeBatch()); r.sse.reset(new SseSet()); EncodeBatch& eb = *r.eb;
+  int rc = quality_fill_batch(j, gi, r.cands, eb);
+  for (const EncStreamDesc& d : eb.desc) eb.n_sums += (size_t)d.n_frames * RBT_SSE_WORDS;
+  if (!rc && (rc = encode_build(eb)) != 0) j.err = eb.err;
+  if (rc) return rc;
+  r.sse->ext = eb.d_sums;
+  if (rbtk::dev_memset(eb.d_sums, 0, eb.n_sums * 8)) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  for (size_t e = 0; e < r.cands.size(); e++) {
+    const EncStreamDesc& d = eb.desc[e]; const QualityOcc& o = j.qocc[j.groups[gi][r.cands[e].q]]; const int st = d.src_stride ? d.src_stride : d.w;
+    for (int k = 0; k < d.n_frames; k++) {
+      const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k];
+      RbtSsePic P; memset(&P, 0, sizeof(P));
+      for (int c = 0; c < 3; c++) { const int sh = c ? 1 : 0; P.a[c] = d.src[c][k] + (size_t)(d.src_y0 >> sh) * (size_t)(st >> sh) + (d.src_x0 >> sh); P.b[c] = f.out[c]; }
+      P.w = d.w; P.h = d.h; P.a_stride = st; P.b_stride = f.cfg.w;
+      if (o.occ) { P.occ = o.occ + o.in_step * (size_t)((size_t)k * o.n / d.n_frames); P.ow = o.ow; P.scale = d.w / o.ow; }
+      r.sse->add(P);
+    }
+  }
+  if ((rc = r.sse->upload()) != 0) { j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
+  if ((rc = encode_upload_lists(eb)) != 0) { j.err = eb.err; return rc; }
+  encode_launch_intra(eb); encode_launch_entropy_intra(eb); encode_launch_inter(eb);
+  if (!eb.hash.empty()) eb.hash.launch();
+  r.sse->launch();
+  encode_launch_entropy_rest(eb);
+  return 0;
+}
+static int quality_finish_round(GofJob& j, int gi) {
+  QualityPipe& r = j.qual[gi]; std::vector<std::vector<uint8_t>> outs;
+  rbtk::set_stream(job_stream(j, gi));
+  if (int rc = encode_finish(*r.eb, outs, j.st)) { j.err = r.eb->err; return rc; }
+  size_t at = 0;                                                    // (the words came back with the slice sizes)
+  for (size_t e = 0; e < r.cands.size(); e++) {
+    const EncStreamDesc& d = r.eb->desc[e]; QualitySums sums;
+    for (int k = 0; k < d.n_frames; k++, at++) quality_add_picture(sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
+    if (r.cands[e].walk < 0) { r.o1[r.cands[e].q].swap(outs[e]); r.sums[r.cands[e].q] = sums; }
+    else { QualityTried& t = r.walks[r.cands[e].walk].tried[r.cands[e].qp]; t.stream.swap(outs[e]); t.sums = sums; r.n_enc[r.cands[e].walk]++; }
+  }
+  r.eb.reset(); r.sse.reset();
+  r.cands.clear(); std::vector<int> qps;
+  for (size_t k = 0; k < r.walks.size(); k++) {
+    int need = 0, dir = 0;
+    if (r.walks[k].settled || quality_walk_step(r.walks[k], need, dir)) continue;
+    quality_round_qps(r.walks[k], need, dir, qps);
+    for (int qp : qps) r.cands.push_back(RateCand{r.walks[k].q, qp, (int)k});
+  }
+  return 0;
+}
+static void quality_fill_result(rbt_quality_result& o, int qp, int q0, int qs, int met, int n_enc, uint64_t bytes, const QualitySums& s, int bit_depth) {
+  memset(&o, 0, sizeof(o));
+  o.qp = qp; o.qp_probe = q0; o.qp_start = qs; o.met = met; o.n_encodes = n_enc; o.bytes = bytes;
+  for (int c = 0; c < 3; c++) {
+    o.sse[c] = s.sse[c]; o.samples[c] = s.samples[c]; o.sse_occ[c] = s.sse_occ[c]; o.samples_occ[c] = s.samples_occ[c];
+    o.psnr[c] = quality_psnr(s.sse[c], s.samples[c], bit_depth); o.psnr_occ[c] = quality_psnr(s.sse_occ[c], s.samples_occ[c], bit_depth);
+  }
+}
+// A geometry / attribute pipeline of a job with floors, in the wait half: its decoder is collected and its rounds run, one after the other, until every walk has settled.
+// The occupancy pipelines of the job have been collected by then (gof_wait), so the pooled planes and the maps the rounds read are complete.
+static int quality_run_pipeline(GofJob& j, int gi) {
+  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
+  j.qual.resize(j.ng); j.qresults.resize(j.n); QualityPipe& r = j.qual[gi];
+  if (int rc = pipeline_decoded(j, gi)) return rc;
+  r.o1.assign(gs.size(), {}); r.sums.assign(gs.size(), QualitySums());
+  std::vector<int> bd(gs.size(), 8);
+  for (size_t q = 0; q < gs.size(); q++) {
+    const int ds = j.dec_of[gi][q]; bd[q] = db.frames[db.stream_first[ds]].cfg.bit_depth;
+    if (!has_floor(j, gs[q])) { r.cands.push_back(RateCand{(int)q, j.params[gs[q]].qp, -1}); continue; }
+    const rbt_quality_target& t = j.qtargets[gs[q]];
+    QualityWalk w; w.q = (int)q; w.entry = gs[q]; w.floor_mdb = t.min_psnr_mdb; w.region = t.region; w.bit_depth = bd[q]; w.lo = t.qp_min; w.hi = t.qp_max ? t.qp_max : 51;
+    w.q0 = std::min(w.hi, std::max(w.lo, j.params[gs[q]].qp));
+    r.cands.push_back(RateCand{(int)q, w.q0, (int)r.walks.size()});
+    r.walks.push_back(std::move(w));
+  }
+  r.n_enc.assign(r.walks.size(), 0);
+  for (;;) {
+    if (int rc = quality_launch_round(j, gi)) return rc;
+    if (r.done) break;
+    if (int rc = quality_finish_round(j, gi)) return rc;
+  }
+  for (size_t q = 0; q < gs.size(); q++) if (!has_floor(j, gs[q])) { const int qp = j.params[gs[q]].qp; quality_fill_result(j.qresults[gs[q]], qp, qp, qp, 1, 1, r.o1[q].size(), r.sums[q], bd[q]); }
+  for (size_t k = 0; k < r.walks.size(); k++) {
+    QualityWalk& w = r.walks[k];
+    if (!w.settled) { j.err = "internal: quality walk did not settle"; return RBT_ERR_PARAM; }
+    QualityTried& t = w.tried[w.qstar];
+    quality_fill_result(j.qresults[w.entry], w.qstar, w.q0, w.qs, w.met, r.n_enc[k], t.stream.size(), t.sums, w.bit_depth);
+    r.o1[w.q].swap(t.stream);
   }
   return 0;
 }
@@ -818,12 +1009,13 @@ static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
 
 // Phase A of a job: plan, build and upload everything, then enqueue. Every upload of the job is issued before its first kernel: a copy from pageable memory blocks the host
 // until the stream has reached it, and pipelines may share a stream. The first failure ends the submission (j.rc, j.err); gof_wait drains what was enqueued.
-GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets) {
+GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality) {
   GofJob* J = new GofJob(); GofJob& j = *J;
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
   j.params.assign(p, p + n); j.n_in.assign(n_in, n_in + n);
   if (targets) j.targets.assign(targets, targets + n);
+  if (quality) { j.qtargets.assign(quality, quality + n); j.qocc.assign(n, QualityOcc()); }
   SubmitPlan s; s.in = in; s.p = p; s.gof_rule = gof_rule;
   int rc = plan_pipelines(j, s, depth);
   j.t_gpu = now_ms();
@@ -837,19 +1029,24 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
 }
 
 // phase B, shortest pipeline first: one sync per stream, then slice sizes -> pack -> NAL assembly. Consumes the job.
-int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results) {
+int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* qresults) {
   std::unique_ptr<GofJob> guard(J); GofJob& j = *J;
   const int n = j.n, ng = j.ng; int rc = j.rc;
   rbt_stats& st = j.st; std::string& err = j.err;
   std::vector<DecodeBatch>& db = j.db; std::vector<EncodeBatch>& eb = j.eb; const rbt_stream_params* p = j.params.data();
   for (int i = 0; i < n; i++) { out[i] = nullptr; n_out[i] = 0; }
   std::vector<std::vector<uint8_t>> outs(n);
-  for (int k = ng - 1; k >= 0; k--) {
+  // a job with quality floors: the pipelines that were encoded at submit first - its occupancy pipelines, whose pooled planes and maps the others' rounds read -, then those
+  // that are encoded here; every other job has one pass
+  const bool quality = !j.qtargets.empty();
+  for (int pass = 0; pass < (quality ? 2 : 1); pass++) for (int k = ng - 1; k >= 0; k--) {
     const int gi = j.order[k], sid = job_stream(j, gi); const std::vector<int>& gs = j.groups[gi]; rbtk::set_stream(sid);
+    if (quality && (j.rate_pipe[gi] != 0) != (pass == 1)) continue;
     if (rc) { rbtk::dev_sync(); continue; }              // drain the remaining streams before their arenas are released
     if (db[gi].frames.empty()) continue;
     std::vector<std::vector<uint8_t>> o1;
-    if (j.rate_pipe[gi]) { rc = rate_run_pipeline(j, gi); rbtk::set_stream(sid); if (rc) continue; o1.swap(j.rate[gi].o1); }      // estimates, rounds of trial encodes, walks
+    if (quality && j.rate_pipe[gi]) { rc = quality_run_pipeline(j, gi); rbtk::set_stream(sid); if (rc) continue; o1.swap(j.qual[gi].o1); }      // rounds of trial encodes with their sums, walks
+    else if (j.rate_pipe[gi]) { rc = rate_run_pipeline(j, gi); rbtk::set_stream(sid); if (rc) continue; o1.swap(j.rate[gi].o1); }      // estimates, rounds of trial encodes, walks
     else {
       rc = pipeline_decoded(j, gi);
       if (rc) continue;
@@ -866,6 +1063,10 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
   if (results) for (int i = 0; i < n; i++) {
     if (has_target(j, i)) { results[i] = j.results[i]; continue; }
     results[i] = rbt_rate_result{p[i].qp, p[i].qp, 1, j.is_pass[i] ? 0 : 1, (uint64_t)n_out[i], 0};
+  }
+  if (qresults) for (int i = 0; i < n; i++) {
+    if (quality && !j.is_pass[i] && p[i].video_type != RBT_VIDEO_OCCUPANCY && i < (int)j.qresults.size()) { qresults[i] = j.qresults[i]; continue; }
+    quality_fill_result(qresults[i], p[i].qp, p[i].qp, p[i].qp, 1, j.is_pass[i] ? 0 : 1, (uint64_t)n_out[i], QualitySums(), 8);
   }
   // SURVEY.md 8(d) algorithmic traffic: per coded picture of S samples (2 bytes each): decode writes S, P pictures read
   // their reference once; encode reads the source S, writes the reconstruction S (I) and reads the reference (P)
@@ -962,6 +1163,37 @@ int level_census_host(std::string& err, const int16_t* y, const int16_t* cb, con
   if (!rc) { cs1.launch(); rc = cs1.fetch(); }
   if (rc) { err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
   memcpy(hist, cs1.hist.data(), RBT_RATE_HIST_WORDS * 4);
+  return 0;
+}
+
+// rbt_picture_sse: the pictures of a, then those of b, then the maps, each block on a multiple of 256 bytes - the rows of a and b are equally far from a 16-byte boundary
+int picture_sse_host(std::string& err, const uint16_t* a, const uint16_t* b, int w, int h, int n_frames, const uint16_t* occ, int ow, int oh, uint64_t* out, rbt_stats& st) {
+  memset(&st, 0, sizeof(st));
+  if (w <= 0 || h <= 0 || w % 2 || h % 2 || w > 8192 || h > 8192 || n_frames < 1) { err = "picture size must be even and at most 8192"; return RBT_ERR_PARAM; }
+  if (occ && (ow <= 0 || oh <= 0 || w % ow || h % oh || w / ow != h / oh)) { err = "the occupancy map's scale must be whole and the same in both directions"; return RBT_ERR_PARAM; }
+  const size_t ys = (size_t)w * h, cs = (size_t)(w / 2) * (h / 2), fs = ys + 2 * cs, os = occ ? (size_t)ow * oh : 0;
+  const size_t blk = (fs * 2 * (size_t)n_frames + 255) & ~(size_t)255;
+  std::vector<uint8_t> staging(2 * blk + os * 2 * (size_t)n_frames);
+  memcpy(staging.data(), a, fs * 2 * (size_t)n_frames); memcpy(staging.data() + blk, b, fs * 2 * (size_t)n_frames);
+  if (occ) memcpy(staging.data() + 2 * blk, occ, os * 2 * (size_t)n_frames);
+  uint8_t* buf = (uint8_t*)rbtk::dev_alloc(staging.size());
+  if (!buf) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  struct G { void* p; ~G() { rbtk::dev_free(p); } } g{buf};
+  if (rbtk::h2d(buf, staging.data(), staging.size())) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  SseSet set;
+  for (int k = 0; k < n_frames; k++) {
+    RbtSsePic P; memset(&P, 0, sizeof(P));
+    const uint16_t* pa = (const uint16_t*)buf + fs * (size_t)k; const uint16_t* pb = (const uint16_t*)(buf + blk) + fs * (size_t)k;
+    Arena::same_planes(P.a, pa, ys, cs); Arena::same_planes(P.b, pb, ys, cs);
+    P.w = w; P.h = h; P.a_stride = P.b_stride = w;
+    if (occ) { P.occ = (const uint16_t*)(buf + 2 * blk) + os * (size_t)k; P.ow = ow; P.scale = w / ow; }
+    set.add(P);
+  }
+  int rc = set.upload();
+  if (!rc) { rbtk::timer_begin(T_CENSUS); set.launch(); rbtk::timer_end(T_CENSUS); rc = set.fetch(); }      // (the census timer's events: no census runs inside this call)
+  if (rc) { err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
+  st.gpu_ms = rbtk::timer_ms(T_CENSUS);
+  memcpy(out, set.words.data(), set.words.size() * 8);
   return 0;
 }
 

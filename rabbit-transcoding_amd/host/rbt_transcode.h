@@ -7,13 +7,17 @@ int transcode_gof(rbt_stats& st, std::string& err, int n, const uint8_t* const* 
 struct GofJob;
 // gof_rule: apply transcodeData's rule (PCCTranscoder.cpp:150): an occupancy stream is only transcoded when occupancyPrecision == 4
 // targets: nullptr, or one per entry (checked by the caller: rbt_submit_gof_rate); results: nullptr, or one per entry
-GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets = nullptr);
-int gof_wait(GofJob* j, rbt_stats& st, std::string& err, uint8_t** out, size_t* n_out, rbt_rate_result* results = nullptr);   // consumes the job
+// quality: nullptr, or one floor per entry (rbt_submit_gof_quality; not together with targets); quality_results: nullptr, or one per entry of such a job
+GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr);
+int gof_wait(GofJob* j, rbt_stats& st, std::string& err, uint8_t** out, size_t* n_out, rbt_rate_result* results = nullptr, rbt_quality_result* quality_results = nullptr);   // consumes the job
+bool gof_is_quality(const GofJob* j);           // a job of rbt_submit_gof_quality
+int gof_refused(const GofJob* j, std::string& err);   // != 0: the job's plan was refused before anything was built or enqueued (the code; the reason in err)
 void gof_abandon(GofJob* j);
 size_t gof_memory(const GofJob* j);             // device memory the job's build took (its arenas)
 int encode_yuv(rbt_stats& st, std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int qp, int gop, int lossless, int log2_ctb, int rows, int md5, uint8_t** out, size_t* n_out);
 int or_pool_host(const uint16_t* plane, int w, int h, int factor, uint16_t* out);
 int level_census_host(std::string& err, const int16_t* y, const int16_t* cb, const int16_t* cr, int w, int h, const int8_t* qp4, const uint8_t* pm4, uint32_t* hist);   // rbt_level_census
+int picture_sse_host(std::string& err, const uint16_t* a, const uint16_t* b, int w, int h, int n_frames, const uint16_t* occ, int ow, int oh, uint64_t* out, rbt_stats& st);   // rbt_picture_sse; st.gpu_ms: device time between events around the launches
 int rate_estimate(std::string& err, const uint8_t* annexb, size_t n, rbt_rate_table* out);   // rbt_rate_estimate
 int picture_hash_host(std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int kind, uint8_t* out);   // rbt_picture_hash
 }

@@ -30,7 +30,9 @@ uint64_t count_pictures(const uint8_t* ss, size_t n) {
   return pics;
 }
 // rate targets of the walk (rbt_transcode_v3c_rate): bits per picture by video type (0 = constant QP), and where the results go (two per GOF: geometry, attribute)
-struct WalkRate { uint32_t geometry_bits = 0, attribute_bits = 0; rbt_rate_result* per_gof = nullptr; bool on() const { return geometry_bits || attribute_bits; } };
+struct WalkRate { uint32_t geometry_bits = 0, attribute_bits = 0; rbt_rate_result* per_gof = nullptr; bool on() const { return geometry_bits || attribute_bits; }
+  // PSNR floors instead of budgets (rbt_transcode_v3c_quality): every job of the walk is a job of rbt_submit_gof_quality, floors of 0 included - its results carry the distortion
+  bool quality = false; int32_t geometry_floor = 0, attribute_floor = 0; int region = 0; rbt_quality_result* q_per_gof = nullptr; };
 int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt_v3c_sink sink, void* user, const WalkRate& rate);
 }
 
@@ -179,6 +181,15 @@ int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt
   // jobs: the picked units of `per` consecutive owned GOFs each, as many in flight as the context allows (RBT_ERR_BUSY tells) AND as the device memory holds
   // a job of a walk with rate targets is collected with its results: entry k of the job is unit jb.unit[k]
   auto wait_job = [&](rbt_job* j, const std::vector<int>& unit, uint8_t** o, size_t* on) -> int {
+    if (rate.quality) {
+      std::vector<rbt_quality_result> res(unit.size());
+      const int r = rbt_wait_gof_quality(ctx, j, o, on, res.data());
+      if (!r && rate.q_per_gof) for (size_t k = 0; k < unit.size(); k++) {
+        const rbt_v3c_unit& u = U[unit[k]];
+        if (u.video_type == RBT_VIDEO_GEOMETRY) rate.q_per_gof[2 * u.gof] = res[k]; else if (u.video_type == RBT_VIDEO_ATTRIBUTE) rate.q_per_gof[2 * u.gof + 1] = res[k];
+      }
+      return r;
+    }
     if (!rate.on()) return rbt_wait_gof(ctx, j, o, on);
     std::vector<rbt_rate_result> res(unit.size());
     const int r = rbt_wait_gof_rate(ctx, j, o, on, res.data());
@@ -195,13 +206,14 @@ int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt
   std::vector<int> owned; for (int g = 0; g < n_gofs; g++) if (rbt_owns_gof(ctx, g) && !picks[g].empty()) owned.push_back(g);
   int per = p->gofs_per_job > 1 ? p->gofs_per_job : 1, announced = 0;
   // whatever way this function is left - error, exception - the jobs still in flight are collected, the caller's depth is put back and the buffers are freed
-  struct Guard { rbt_ctx* ctx; std::deque<Job>& q; int& announced; std::vector<Buf>& repl;
+  struct Guard { rbt_ctx* ctx; std::deque<Job>& q; int& announced; std::vector<Buf>& repl; bool quality;
     ~Guard() {
       while (!q.empty()) { Job jb = q.front(); q.pop_front(); std::vector<uint8_t*> o(jb.unit.size(), nullptr); std::vector<size_t> on(jb.unit.size(), 0);
-        rbt_wait_gof(ctx, jb.j, o.data(), on.data()); for (uint8_t* x : o) rbt_free(x); }
+        if (quality) { std::vector<rbt_quality_result> res(jb.unit.size()); rbt_wait_gof_quality(ctx, jb.j, o.data(), on.data(), res.data()); } else rbt_wait_gof(ctx, jb.j, o.data(), on.data());
+        for (uint8_t* x : o) rbt_free(x); }
       if (announced) rbt_set_depth(ctx, announced);
       for (auto& b : repl) { free(b.p); b.p = nullptr; }
-    } } guard{ctx, q, announced, repl};
+    } } guard{ctx, q, announced, repl, rate.quality};
   if (p->gofs_per_job <= 0) {                                                 // job shape by the length of the walk; a short one runs with fewer, larger jobs
     int d = 0; announced = rbt_get_depth(ctx);
     if (announced < 1 || rbt_job_shape((int)owned.size(), announced, &per, &d) != RBT_OK) { announced = 0; return RBT_ERR_PARAM; }
@@ -251,7 +263,7 @@ int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt
     if (todo.empty()) { rc = collect(true); continue; }
     if (!q.empty() && (tight || !fits())) { rc = collect(true); continue; }   // make room first
     const size_t a = todo.front().first, a_end = todo.front().second; todo.pop_front();
-    std::vector<Buf> conv; std::vector<const uint8_t*> ip; std::vector<size_t> in_n; std::vector<rbt_stream_params> sp; std::vector<rbt_rate_target> tg; Job jb{nullptr, {}, owned[a_end - 1], a, a_end, 0};
+    std::vector<Buf> conv; std::vector<const uint8_t*> ip; std::vector<size_t> in_n; std::vector<rbt_stream_params> sp; std::vector<rbt_rate_target> tg; std::vector<rbt_quality_target> qt; Job jb{nullptr, {}, owned[a_end - 1], a, a_end, 0};
     struct FreeConv { std::vector<Buf>& c; ~FreeConv() { for (auto& b : c) free(b.p); } } free_conv{conv};   // the inputs may go as soon as submit returns
     for (size_t b = a; b < a_end && !rc; b++)
       for (const Pick& pk : picks[owned[b]]) {
@@ -267,11 +279,14 @@ int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt
         const uint32_t bits = pk.video_type == RBT_VIDEO_GEOMETRY ? rate.geometry_bits : (pk.video_type == RBT_VIDEO_ATTRIBUTE ? rate.attribute_bits : 0);
         if (bits) { t.target_bytes = ((uint64_t)bits * count_pictures(in + U[pk.unit].offset + 4, U[pk.unit].size - 4) + 7) / 8; if (!t.target_bytes) t.target_bytes = 1; }
         tg.push_back(t);
+        rbt_quality_target f; memset(&f, 0, sizeof(f)); f.struct_size = (uint32_t)sizeof(f); f.region = rate.region;
+        f.min_psnr_mdb = pk.video_type == RBT_VIDEO_GEOMETRY ? rate.geometry_floor : (pk.video_type == RBT_VIDEO_ATTRIBUTE ? rate.attribute_floor : 0);
+        qt.push_back(f);
       }
     for (auto& c : conv) { ip.push_back(c.p); in_n.push_back(c.n); }
     if (!rc && (int)ip.size() > RBT_MAX_STREAMS) rc = RBT_ERR_PARAM;
     while (!rc) {
-      rc = rate.on() ? rbt_submit_gof_rate(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), tg.data(), &jb.j) : rbt_submit_gof(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), &jb.j);
+      rc = rate.quality ? rbt_submit_gof_quality(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), qt.data(), &jb.j) : rate.on() ? rbt_submit_gof_rate(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), tg.data(), &jb.j) : rbt_submit_gof(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), &jb.j);
       if (rc == RBT_ERR_BUSY && !q.empty()) { rc = collect(true); continue; }  // every slot taken: take the oldest result first (and hand its GOFs over)
       note(rc);
       break;
@@ -306,6 +321,27 @@ int rbt_transcode_v3c(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_p
   std::vector<const uint8_t*> up; std::vector<size_t> un;
   for (auto& u : k.unit) { up.push_back(u.data()); un.push_back(u.size()); }
   return rbt_v3c_write(up.data(), un.data(), (int)up.size(), p->forced_unit_size_precision_bytes, out, n_out);
+} RBT_CATCH
+// rbt_transcode_v3c with PSNR floors for the geometry / attribute units (include/rbt.h)
+int rbt_transcode_v3c_quality(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, int32_t geometry_min_psnr_mdb, int32_t attribute_min_psnr_mdb, int region,
+                              uint8_t** out, size_t* n_out, rbt_quality_result** per_gof) try {
+  if (!ctx || !in || !p || !out || !n_out) return RBT_ERR_PARAM;
+  *out = nullptr; *n_out = 0; if (per_gof) *per_gof = nullptr;
+  if (geometry_min_psnr_mdb < 0 || attribute_min_psnr_mdb < 0) { rbt_internal_set_error(ctx, "min_psnr_mdb must not be negative"); return RBT_ERR_PARAM; }
+  if (region != RBT_QUALITY_ALL && region != RBT_QUALITY_OCCUPIED) { rbt_internal_set_error(ctx, "region must be RBT_QUALITY_ALL or RBT_QUALITY_OCCUPIED"); return RBT_ERR_PARAM; }
+  rbt_v3c_stat st;
+  int rc = rbt_v3c_stats(in, n, &st);
+  if (rc) return rc;
+  WalkRate rate; rate.quality = true; rate.geometry_floor = geometry_min_psnr_mdb; rate.attribute_floor = attribute_min_psnr_mdb; rate.region = region;
+  rate.q_per_gof = (rbt_quality_result*)calloc((size_t)(st.n_gofs > 0 ? st.n_gofs : 1) * 2, sizeof(rbt_quality_result));
+  if (!rate.q_per_gof) return RBT_ERR_NOMEM;
+  Keep k;
+  rc = walk(ctx, in, n, p, keep_units, &k, rate);
+  std::vector<const uint8_t*> up; std::vector<size_t> un;
+  for (auto& u : k.unit) { up.push_back(u.data()); un.push_back(u.size()); }
+  if (!rc) rc = rbt_v3c_write(up.data(), un.data(), (int)up.size(), p->forced_unit_size_precision_bytes, out, n_out);
+  if (rc || !per_gof) free(rate.q_per_gof); else *per_gof = rate.q_per_gof;
+  return rc;
 } RBT_CATCH
 // rbt_transcode_v3c with byte budgets for the geometry / attribute units (include/rbt.h)
 int rbt_transcode_v3c_rate(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, uint32_t geometry_bits_per_picture, uint32_t attribute_bits_per_picture,
