@@ -291,6 +291,21 @@ int rbt_get_stats(rbt_ctx* ctx, rbt_stats* out);
 /* Device self-test of the 32-point transform stages on the matrix cores (v_mfma_i32_32x32x32_i8) against the vector-ALU form of the same stages:
  * n_blocks blocks of 32 x 32 int16 (coefficients for the inverse, residuals for the forward transform); *n_mismatch = differing output samples. */
 int rbt_selftest_transform32(rbt_ctx* ctx, const int16_t* blocks, int n_blocks, int bit_depth, uint32_t* n_mismatch);
+/* Test hook: single transform blocks through the decoder's own reconstruction routine (csrc/rbt_recon.h rc_tile_tb / rc_tile_tb_cpair), one wave per case, so that the
+ * block's arithmetic can be held against H.265 8.4.4.2 / 8.6 directly (tests/tb_spec.py). A case is staged into a CTB tile the way the CTB kernel stages a CTB: the 4N+1
+ * neighbour samples around the block at (x0, y0) inside the CTB (samples of the block's component), the availability of the neighbours' 4x4 luma units, the levels where
+ * the block's samples will be; what the routine leaves at the block's position comes back (samples; for an inter block the residual as int16 bit patterns).
+ * kind: RBT_TB_LUMA / _CB / _CR = one block of that component through rc_tile_tb, RBT_TB_PAIR = Cb and Cr of one transform unit through rc_tile_tb_cpair (cbf / qp [0] = Cb,
+ * [1] = Cr; no transform skip). log2: 2..5 (chroma 2..4); bit_depth 8..12; log2_ctb 4..6; x0, y0 multiples of 4 with the block inside the CTB; qp as the kernels take it
+ * (including 6 * (bit_depth - 8)), 0 .. 51 + 6 * (bit_depth - 8).
+ * nb: [n][2][RBT_TB_NB] samples in reference order (0 = p[-1][2N-1] .. 2N-1 = p[-1][0], 2N = corner, 2N+1+x = p[x][-1]); unit_av: [n][RBT_TB_UNITS] flags of the units of
+ * 4 (chroma: 2) samples in the same order (2N / unit up the left column, the corner, 2N / unit along the row above) - a unit below the CTB, or right of it in a row of
+ * the CTB itself, is never available and its flag is ignored; levels, out: [n][2][1024], row pitch N; plane slot 1 is used by RBT_TB_PAIR only. */
+enum { RBT_TB_LUMA = 0, RBT_TB_CB = 1, RBT_TB_CR = 2, RBT_TB_PAIR = 3, RBT_TB_NB = 129, RBT_TB_UNITS = 33 };
+typedef struct rbt_tb_case {
+  int32_t kind, log2, bit_depth, log2_ctb, x0, y0, strong_intra_smoothing, intra, mode, cbf[2], transform_skip, cu_transquant_bypass, qp[2], pad;
+} rbt_tb_case;
+int rbt_selftest_tb(rbt_ctx* ctx, const rbt_tb_case* cases, int n_cases, const uint16_t* nb, const uint8_t* unit_av, const int16_t* levels, uint16_t* out);
 
 /* ---- decoder-side verification stage: what turns transcoded maps into the D1 figure of the metric ----
  * Replaces PCCCodec::generateOccupancyMap (PCCCodec.cpp:1584-1606), generateBlockToPatchFromOccupancyMapVideo (:1725-1763),

@@ -73,13 +73,13 @@ void hevc_inv_transform(const int16_t* d, int16_t* res, int log2, int is_dst, in
     for (int x = 0; x < N; x++) {
       int s = 0;
       for (int k = 0; k < N; k++) s += tcoef(N, is_dst, k, x) * tmp[y * N + k];
-      res[y * N + x] = (int16_t)((s + (1 << (sh - 1))) >> sh);
+      res[y * N + x] = (int16_t)clip3(-32768, 32767, (s + (1 << (sh - 1))) >> sh);   /* the text's residual has no width; saturated, Clip1(pred + res) is the text's sample */
     }
 }
 /* 8.6.4.2 transform-skip branch (v1): r = d << 7, then bdShift = 20 - bitDepth */
 void hevc_inv_transform_skip(const int16_t* d, int16_t* res, int log2, int bit_depth) {
   int n = 1 << (2 * log2), sh = 20 - bit_depth;
-  for (int i = 0; i < n; i++) res[i] = (int16_t)((((int)d[i] << 7) + (1 << (sh - 1))) >> sh);
+  for (int i = 0; i < n; i++) res[i] = (int16_t)(((int)d[i] * 128 + (1 << (sh - 1))) >> sh);
 }
 /* encoder-side forward transform: rows then columns, HM shift convention */
 void hevc_fwd_transform(const int16_t* res, int16_t* coef, int log2, int is_dst, int bit_depth) {

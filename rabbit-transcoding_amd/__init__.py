@@ -186,6 +186,7 @@ def load(path=None):
     L.rbt_byte_to_sample_stream.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.rbt_selftest_transform32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
+    L.rbt_selftest_tb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rbt_reconstruct.argtypes = [C.c_void_p, C.POINTER(AtlasParams), C.POINTER(Patch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Cloud)]
     L.rbt_cloud_free.argtypes = [C.POINTER(Cloud)]
     L.rbt_d1.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(D1Result)]
@@ -816,6 +817,17 @@ class Context:
         bad = C.c_uint32()
         self._chk(self.L.rbt_selftest_transform32(self.h, blocks.ctypes.data, blocks.shape[0], bit_depth, C.byref(bad)))
         return bad.value
+
+    def selftest_tb(self, cases, nb, unit_av, levels):
+        """rbt_selftest_tb: transform blocks through the decoder's own routine. cases int32 [n, 16] (the fields of rbt_tb_case in order), nb uint16 [n, 2, 129],
+        unit_av uint8 [n, 33], levels int16 [n, 2, 1024] -> uint16 [n, 2, 1024]"""
+        cases = np.ascontiguousarray(cases, dtype=np.int32); n = cases.shape[0]
+        nb = np.ascontiguousarray(nb, dtype=np.uint16); unit_av = np.ascontiguousarray(unit_av, dtype=np.uint8); levels = np.ascontiguousarray(levels, dtype=np.int16)
+        if cases.shape != (n, 16) or nb.shape != (n, 2, 129) or unit_av.shape != (n, 33) or levels.shape != (n, 2, 1024):
+            raise ValueError("selftest_tb: array shapes")
+        out = np.zeros((n, 2, 1024), np.uint16)
+        self._chk(self.L.rbt_selftest_tb(self.h, cases.ctypes.data, n, nb.ctypes.data, unit_av.ctypes.data, levels.ctypes.data, out.ctypes.data))
+        return out
 
     def stats(self):
         s = Stats()

@@ -105,6 +105,14 @@ void launch_entropy_wave(RbtFrame* frames, RbtSlice* slices, uint8_t* out, const
 void launch_pack(const uint8_t* out, const RbtSlice* slices, const uint32_t* dst_off, uint8_t* packed, int n_slices);
 // matrix-core transform stages against the vector-ALU stages on n blocks of 32 x 32 int16 (0 = ok; *n_bad = differing samples)
 int selftest_transform32(const int16_t* blocks, int n, int bd, uint32_t* n_bad);
+// single transform blocks through the decoder's rc_tile_tb / rc_tile_tb_cpair (rbt_tb_hook.h; arrays as rbt_selftest_tb documents them, cases validated by the caller; 0 = ok)
+// (The serial stand-in of this interface under tests/hostemu is a file of the tests, and a stand-in written before this hook existed must still link and load: there the
+// symbol is weak, and rbt_selftest_tb reports a stand-in that lacks it instead of the library failing to load. In the product it is an ordinary symbol.)
+#ifdef RBT_HOSTEMU
+int selftest_tb(const rbt_tb_case* cases, int n, const uint16_t* nb, const uint8_t* unit_av, const int16_t* levels, uint16_t* out) __attribute__((weak));
+#else
+int selftest_tb(const rbt_tb_case* cases, int n, const uint16_t* nb, const uint8_t* unit_av, const int16_t* levels, uint16_t* out);
+#endif
 // verification stage (rbt_pcc.h). items: one (patch << 16 | block inside the patch) word per patch block, in the reference's visiting order
 void launch_pcc_occmap(const RbtPccParams* P, const uint16_t* occ, uint8_t* om);
 void launch_pcc_owner(const RbtPccParams* P, const rbt_patch* patches, const uint32_t* items, int n_items, const uint16_t* occ, uint32_t* b2p);

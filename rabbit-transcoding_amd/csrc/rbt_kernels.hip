@@ -9,6 +9,7 @@
 #include "rbt_recon.h"
 #include "rbt_filter.h"
 #include "rbt_encode.h"
+#include "rbt_tb_hook.h"
 #include "rbt_pcc.h"
 
 namespace rbtk {
@@ -610,6 +611,28 @@ int selftest_transform32(const int16_t* blocks, int n, int bd, uint32_t* n_bad) 
   int rc = h2d(d_in, blocks, (size_t)n * 2048) | dev_memset(d_bad, 0, 4);
   if (!rc) { hipLaunchKernelGGL(k_selftest_t32, dim3(n < 256 ? n : 256), dim3(64), 0, g_stream, d_in, n, bd, d_bad); rc = d2h(n_bad, d_bad, 4) | dev_sync(); }
   dev_free(d_in); dev_free(d_bad);
+  return rc;
+}
+// Single transform blocks through rc_tile_tb / rc_tile_tb_cpair (rbt_tb_hook.h), one wave per case
+__global__ void __launch_bounds__(64) k_selftest_tb(const rbt_tb_case* cases, int n, const uint16_t* nb, const uint8_t* unit_av, const int16_t* lev, uint16_t* out) {
+  __shared__ RbtCtbTile tile; __shared__ RbtReconRole role;
+  RBT_LDS_AS RbtCtbTile* t = RBT_LDS_CAST(RbtCtbTile, &tile); RBT_LDS_AS RbtReconRole* R = RBT_LDS_CAST(RbtReconRole, &role);
+  rc_stage_tables(&R->rc);
+  for (int b = blockIdx.x; b < n; b += gridDim.x)
+    rc_selftest_tb_case(&cases[b], nb + (size_t)b * 2 * RBT_TB_NB, unit_av + (size_t)b * RBT_TB_UNITS, lev + (size_t)b * 2048, out + (size_t)b * 2048, t, R);
+}
+int selftest_tb(const rbt_tb_case* cases, int n, const uint16_t* nb, const uint8_t* unit_av, const int16_t* levels, uint16_t* out) {
+  const size_t sz[5] = {(size_t)n * sizeof(rbt_tb_case), (size_t)n * 2 * RBT_TB_NB * 2, (size_t)n * RBT_TB_UNITS, (size_t)n * 4096, (size_t)n * 4096};
+  const void* src[4] = {cases, nb, unit_av, levels}; void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int rc = 0;
+  for (int i = 0; i < 5; i++) { d[i] = dev_alloc(sz[i]); if (!d[i]) rc = -1; }
+  for (int i = 0; i < 4 && !rc; i++) rc = h2d(d[i], src[i], sz[i]);
+  if (!rc) rc = dev_memset(d[4], 0, sz[4]);
+  if (!rc) {
+    hipLaunchKernelGGL(k_selftest_tb, dim3(n < 1024 ? n : 1024), dim3(64), 0, g_stream, (const rbt_tb_case*)d[0], n, (const uint16_t*)d[1], (const uint8_t*)d[2], (const int16_t*)d[3], (uint16_t*)d[4]);
+    rc = d2h(out, d[4], sz[4]) | dev_sync();
+  }
+  for (int i = 0; i < 5; i++) dev_free(d[i]);
   return rc;
 }
 

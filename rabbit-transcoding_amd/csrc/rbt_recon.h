@@ -243,23 +243,28 @@ template <int LOG2> RBT_DEV void rc_inv_transform_n(int is_dst, int sh, RBT_LDS_
     int x = i & (N - 1), y = i >> LOG2, s = 0;
 #pragma unroll
     for (int k = 0; k < N; k++) s += rc_tcoef(l, N, is_dst, k, x) * l->tmp[y * N + k];
-    l->res[i] = (int16_t)((s + (1 << (sh - 1))) >> sh);
+    l->res[i] = (int16_t)rbt_clip3(-32768, 32767, (s + (1 << (sh - 1))) >> sh);   // saturated: see rc_inv_transform
   }
   RBT_SYNC_LDS();
 }
-// 32 x 32: both stages on the matrix cores (rbt_mfma.h). tmp[y][x] = clip16((sum_k T[k][y] res[k][x] + 64) >> 7), then res[y][x] = (sum_k tmp[y][k] T[k][x] + round) >> sh
+// 32 x 32: both stages on the matrix cores (rbt_mfma.h). tmp[y][x] = clip16((sum_k T[k][y] res[k][x] + 64) >> 7), then res[y][x] = clip16((sum_k tmp[y][k] T[k][x] + round) >> sh)
 RBT_DEV void rc_inv_transform_32(int sh, RBT_LDS_AS RbtReconLdsCore* l) {
 #ifdef RBT_HOSTEMU
   rc_inv_transform_n<5>(0, sh, l);
 #else
   mf_mm32<true>(l->dct, 1, 32, l->res, l->tmp, 7, 1);
-  mf_mm32<false>(l->dct, 1, 32, l->tmp, l->res, sh, 0);
+  mf_mm32<false>(l->dct, 1, 32, l->tmp, l->res, sh, 1);
 #endif
 }
+// The residual of 8.6.2 is an integer of no particular width: 8.6.7 adds it to the prediction and clips the sum. It is kept in 16 bits here, so the second stage SATURATES:
+// for a prediction in 0 .. 2^bd - 1 a residual beyond +-32767 and the saturated one give the same sample, where a wrapped one gives the opposite end of the range. The
+// largest |r| legal levels reach is (largest column sum of |T| * 32768) >> (20 - bd): 59584 for 32x32 at 10 bit, at most 30080 for every smaller size up to 10 bit and 14896
+// for everything at 8 bit - but 16x16 passes 2^15 at 11 bit (60160) and 8x8 at 12 (61312), so the clip is on every size (one v_med3 per sample) and not on 32x32 alone.
+// Transform skip stays at or below 2^14 up to 12 bit by construction.
 RBT_DEV void rc_inv_transform(int log2, int is_dst, int ts, int bd, RBT_LDS_AS RbtReconLdsCore* l) {
   int N = 1 << log2, sh = 20 - bd;
   if (ts) {
-    RBT_PAR_FOR(i, N * N) l->res[i] = (int16_t)((((int)l->res[i] << 7) + (1 << (sh - 1))) >> sh);
+    RBT_PAR_FOR(i, N * N) l->res[i] = (int16_t)(((int)l->res[i] * 128 + (1 << (sh - 1))) >> sh);
     RBT_SYNC_LDS();
     return;
   }
@@ -288,7 +293,7 @@ template <int LOG2> RBT_DEV void rc_inv_transform_pair_n(int sh, int m0, int m1,
       int s = 0;
 #pragma unroll
       for (int k = 0; k < N; k++) s += rc_tcoef(l, N, 0, k, x) * l->tmp[b * 256 + y * N + k];
-      l->res[b * 256 + j] = (int16_t)((s + (1 << (sh - 1))) >> sh);
+      l->res[b * 256 + j] = (int16_t)rbt_clip3(-32768, 32767, (s + (1 << (sh - 1))) >> sh);
     }
   }
   RBT_SYNC_LDS();
@@ -381,7 +386,7 @@ struct RbtReconCtbLds { RbtCtbTile t; RbtReconRole role[2]; };
 // availability of unit p of the TB at (x0,y0) (plane samples relative to the CTB) from the CTB's unit flags
 RBT_DEV int rc_nb_unit_av(const RBT_LDS_AS uint8_t* uav, int p, int x0, int y0, int N, int sh, int n4) {
   int xn, yn; rc_nb_unit_xy(p, x0, y0, N, sh, &xn, &yn);
-  const int ux = (xn << sh) >> 2, uy = (yn << sh) >> 2;                  // -1 for the border column / row
+  const int ux = (xn * (1 << sh)) >> 2, uy = (yn * (1 << sh)) >> 2;      // -1 for the border column / row (a product: xn, yn may be -1, and shifting that left is undefined)
   return uy < n4 && uav[(uy + 1) * RC_US + ux + 1];
 }
 // mark_l4 >= 0: also flags the TB's (1 << mark_l4)^2 luma units at (mux,muy) as decoded in the same pass

@@ -340,6 +340,26 @@ int rbt_selftest_transform32(rbt_ctx* ctx, const int16_t* blocks, int n_blocks, 
   RBT_ENTER(ctx);
   return rbtk::selftest_transform32(blocks, n_blocks, bit_depth, n_mismatch) ? RBT_ERR_NO_DEVICE : RBT_OK;
 } RBT_CATCH
+// a case the hook can stage without leaving the CTB tile (csrc/rbt_tb_hook.h)
+static bool tb_case_ok(const rbt_tb_case& c) {
+  if (c.kind < RBT_TB_LUMA || c.kind > RBT_TB_PAIR || c.bit_depth < 8 || c.bit_depth > 12 || c.log2_ctb < 4 || c.log2_ctb > 6) return false;
+  const int sh = c.kind != RBT_TB_LUMA, nn = (1 << c.log2_ctb) >> sh;
+  if (c.log2 < 2 || c.log2 > (sh ? 4 : 5)) return false;
+  const int N = 1 << c.log2, qp_max = 51 + 6 * (c.bit_depth - 8);
+  if (c.x0 < 0 || c.y0 < 0 || (c.x0 & 3) || (c.y0 & 3) || c.x0 + N > nn || c.y0 + N > nn || c.mode < 0 || c.mode > 34) return false;
+  if (c.qp[0] < 0 || c.qp[0] > qp_max || c.qp[1] < 0 || c.qp[1] > qp_max) return false;
+  if (c.kind == RBT_TB_PAIR && c.transform_skip) return false;
+  return true;
+}
+int rbt_selftest_tb(rbt_ctx* ctx, const rbt_tb_case* cases, int n_cases, const uint16_t* nb, const uint8_t* unit_av, const int16_t* levels, uint16_t* out) try {
+  if (!ctx || !cases || n_cases < 1 || n_cases > (1 << 16) || !nb || !unit_av || !levels || !out) return RBT_ERR_PARAM;
+  for (int i = 0; i < n_cases; i++) if (!tb_case_ok(cases[i])) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+#ifdef RBT_HOSTEMU
+  if (!rbtk::selftest_tb) { ctx->last_err = "this stand-in of the launch interface has no selftest_tb"; return RBT_ERR_PARAM; }
+#endif
+  return rbtk::selftest_tb(cases, n_cases, nb, unit_av, levels, out) ? RBT_ERR_NO_DEVICE : RBT_OK;
+} RBT_CATCH
 int rbt_reconstruct(rbt_ctx* ctx, const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const uint16_t* occ_luma, const uint16_t* geo_d0,
                     const uint16_t* geo_d1, int geo_bit_depth, const uint16_t* attr_t0, const uint16_t* attr_t1, int attr_bit_depth, rbt_cloud* out) try {
   if (!ctx || !atlas || (!patches && n_patches) || !occ_luma || !geo_d0 || !out) return RBT_ERR_PARAM;

@@ -15,6 +15,7 @@
 #include "../../rabbit-transcoding_amd/csrc/rbt_recon.h"
 #include "../../rabbit-transcoding_amd/csrc/rbt_filter.h"
 #include "../../rabbit-transcoding_amd/csrc/rbt_encode.h"
+#include "../../rabbit-transcoding_amd/csrc/rbt_tb_hook.h"
 #include "../../rabbit-transcoding_amd/csrc/rbt_pcc.h"
 #include "../../rabbit-transcoding_amd/host/rbt_hls.h"
 
@@ -170,6 +171,12 @@ void launch_sao(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_l
 }
 #include "rbt_kernels_hostemu_enc.inc"
 int selftest_transform32(const int16_t*, int, int, uint32_t* n_bad) { *n_bad = 0; return 0; }   // no matrix cores here
+int selftest_tb(const rbt_tb_case* cases, int n, const uint16_t* nb, const uint8_t* unit_av, const int16_t* levels, uint16_t* out) {     // the bodies themselves, serially
+  static RbtCtbTile tile; static RbtReconRole role;
+  rc_stage_tables(&role.rc);
+  for (int b = 0; b < n; b++) rc_selftest_tb_case(&cases[b], nb + (size_t)b * 2 * RBT_TB_NB, unit_av + (size_t)b * RBT_TB_UNITS, levels + (size_t)b * 2048, out + (size_t)b * 2048, &tile, &role);
+  return 0;
+}
 // verification stage: the same per-element routines, visited serially
 void launch_pcc_occmap(const RbtPccParams* P, const uint16_t* occ, uint8_t* om) { for (int i = 0; i < P->w * P->h; i++) om[i] = occ[(size_t)(i / P->w / P->prec) * P->ow + (i % P->w) / P->prec] > P->threshold; }
 void launch_pcc_owner(const RbtPccParams* P, const rbt_patch* patches, const uint32_t* items, int n_items, const uint16_t* occ, uint32_t* b2p) {
