@@ -288,6 +288,10 @@ int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t
 int rbt_byte_to_sample_stream(const uint8_t* in, size_t n, uint8_t** out, size_t* n_out);
 
 int rbt_get_stats(rbt_ctx* ctx, rbt_stats* out);
+/* Decoded pictures of the context's last collected job (rbt_wait_gof*, the blocking transcode calls) or rbt_decode that were reconstructed with flat chroma: no coded
+ * chroma block, no chroma SAO, default weighting, flat references - both chroma planes are then 1 << (bit_depth - 1) by H.265's text and are filled, not computed
+ * (DESIGN.md 14). A failed call leaves the count of the call before it. */
+int rbt_flat_pictures(const rbt_ctx* ctx);
 /* Device self-test of the 32-point transform stages on the matrix cores (v_mfma_i32_32x32x32_i8) against the vector-ALU form of the same stages:
  * n_blocks blocks of 32 x 32 int16 (coefficients for the inverse, residuals for the forward transform); *n_mismatch = differing output samples. */
 int rbt_selftest_transform32(rbt_ctx* ctx, const int16_t* blocks, int n_blocks, int bit_depth, uint32_t* n_mismatch);

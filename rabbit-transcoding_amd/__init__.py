@@ -829,6 +829,11 @@ class Context:
         self._chk(self.L.rbt_selftest_tb(self.h, cases.ctypes.data, n, nb.ctypes.data, unit_av.ctypes.data, levels.ctypes.data, out.ctypes.data))
         return out
 
+    def flat_pictures(self):
+        """rbt_flat_pictures: decoded pictures of the last collected job or decode that were reconstructed with flat chroma"""
+        self.L.rbt_flat_pictures.argtypes = [C.c_void_p]      # (declared here: load() also serves builds from before the function, which comparisons of two libraries put side by side)
+        return int(self.L.rbt_flat_pictures(self.h))
+
     def stats(self):
         s = Stats()
         self._chk(self.L.rbt_get_stats(self.h, C.byref(s)))

@@ -438,6 +438,15 @@ template <int TL2> struct RbtEncTileLdsT { RbtEncIntraScratch rc; RbtEncTileT<TL
 RBT_DEV int en_quant_scale(int r) { const uint64_t lo = 26214ull | (23302ull << 16) | (20560ull << 32) | (18396ull << 48), hi = 16384ull | (14564ull << 16); return (int)(((r < 4 ? lo : hi) >> (16 * (r & 3))) & 0xFFFF); }
 // What the intra chain asks of the picture over and over, read once per CTB into scalar registers. Through the RbtFrame pointer every use was a load from HBM with a wait
 // behind it - nothing lets the compiler keep a value across the stores in between - in the middle of a serial chain: six per transform block.
+#define EN_CTX_FLAT_SRC 0x100      // EnCtbCtx::enc_tools only, beside the RBT_ET_* bits of the picture
+static_assert((EN_CTX_FLAT_SRC & RBT_ET_ALL) == 0 && RBT_ET_ALL == (RBT_ET_SATD | RBT_ET_REFINE | RBT_ET_RQ | RBT_ET_RDM), "EN_CTX_FLAT_SRC must stay clear of the RBT_ET_* bits it shares a word with");
+#ifdef RBT_HOSTEMU
+extern "C" { inline uint32_t rbt_hostemu_flat_ctbs[3]; }   // CTBs that took the flat-chroma path of en_intra_ctb / en_inter_ctb / en_sao_ctb (the output is the same bytes either way: tests tell by this that the path was on)
+#define EN_FLAT_COUNT(k, on) do { if (on) __atomic_fetch_add(&rbt_hostemu_flat_ctbs[k], 1u, __ATOMIC_RELAXED); } while (0)
+#else
+#define EN_FLAT_COUNT(k, on) do { } while (0)
+#endif
+#define EN_FLAT(e) (((e)->enc_tools & EN_CTX_FLAT_SRC) != 0)
 struct EnCtbCtx : RbtStreamCfg { int lossless, enc_tools, f4, w8; int16_t* coef[3]; uint8_t *pm, *edges, *cu_flags, *cu_mode, *cu_ts; int8_t* qp; const uint16_t* src[3]; };
 RBT_DEV void en_ctb_ctx(EnCtbCtx* e, const RbtFrame* f) {
   *(RbtStreamCfg*)e = rc_cfg_uni(&f->cfg);
@@ -445,6 +454,9 @@ RBT_DEV void en_ctb_ctx(EnCtbCtx* e, const RbtFrame* f) {
   for (int c = 0; c < 3; c++) e->coef[c] = rbt_uni_ptr(f->coef[c]);
   e->w8 = RBT_UNI(f->w8); e->pm = rbt_uni_ptr(f->pm); e->edges = rbt_uni_ptr(f->edges); e->cu_flags = rbt_uni_ptr(f->cu_flags); e->cu_mode = rbt_uni_ptr(f->cu_mode); e->qp = rbt_uni_ptr(f->qp);
   e->cu_ts = rbt_uni_ptr(f->cu_ts); for (int c = 0; c < 3; c++) e->src[c] = rbt_uni_ptr(f->src[c]);
+  // flat source: the chroma_flat word of the decoded picture this one is coded from, complete before any encoder launch that reads the picture
+  // (one more bit of enc_tools: the intra chain is short of scalar registers, and a word of its own spilled)
+  { const uint32_t* sf = rbt_uni_ptr(f->src_flat); if (sf && RBT_UNI(*sf)) e->enc_tools |= EN_CTX_FLAT_SRC; }
 }
 // en_fill_cu_maps for the intra chain: the maps' addresses from the CTB's context
 RBT_DEV void en_fill_cu_maps_ctx(const EnCtbCtx* e, int x0, int y0, int N, int pm_val, int qp_y, int flags) {
@@ -801,8 +813,14 @@ template <int TL2> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices
   const int qp_y = sl->qp, bd = g->bit_depth;
   const int qp_l = qp_y + 6 * (bd - 8), qp_cb = en_chroma_qp(f, sl, 1, qp_y), qp_cr = en_chroma_qp(f, sl, 2, qp_y);
   const int tu_rd = g->th_depth_intra > 0, lam16 = k_lambda16[rbt_clip3(0, 75, qp_l)], lam2 = lam16 * lam16;
+  // Flat source: Cb / Cr of the source are v = 1 << (bd - 1), so are the references of every chroma block (substituted, or reconstructed by this rule),
+  // every predictor returns v, the residual is 0, the dead-zone quantiser keeps 0 (as do the lossless and the occupancy-aware form), cbf is 0 and the reconstruction is v.
+  // No decision reads more of a chroma block than its two cbf bits, so the blocks are not coded: nothing of Cb / Cr is fetched, and the CTB's v samples and zero levels
+  // are stored once, at the end.
+  EN_FLAT_COUNT(0, EN_FLAT(e));
+  if (EN_FLAT(e) && ctb_addr == 0 && RBT_LANE0) f->chroma_flat = 1u;      // the reconstruction is flat: this picture's loop filters and the P picture coded from it (later launches)
   // ---- borders, unit availability, analysis results ----
-  for (int c = 0; c < 3; c++) {
+  for (int c = 0; c < (EN_FLAT(e) ? 1 : 3); c++) {
     const int sh = c ? 1 : 0, nn = ctb >> sh, pw = c ? g->cw : g->w, ph = c ? g->ch : g->h, ox = cx >> sh, oy = cy >> sh, S = c ? RbtEncTileT<TL2>::TS_C : RbtEncTileT<TL2>::TS_Y;
     const uint16_t* p = f->pix[c]; RBT_LDS_AS uint16_t* tile = c == 0 ? t->y : t->c[c - 1]; RBT_LDS_AS uint16_t* top = c == 0 ? t->top_y : t->top_c[c - 1];
     if (carry_left) { RBT_PAR_FOR(i, nn) tile[i * S] = tile[i * S + nn]; RBT_SYNC_LDS(); }
@@ -842,7 +860,7 @@ template <int TL2> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices
     int mode = RBT_UNI(t->cu_md[uy * 8 + ux]);
     // source samples of the CU's three TBs: one HBM round trip
     { const uint16_t* sp = e->src[0] + (size_t)(cy + y0) * g->w + cx + x0; RBT_PAR_FOR(i, N * N) t->sb[i] = sp[(size_t)(i >> lg) * g->w + (i & (N - 1))]; }
-    for (int q = 0; q < 2; q++) { const uint16_t* sp = (q ? e->src[2] : e->src[1]) + (size_t)((cy + y0) >> 1) * g->cw + ((cx + x0) >> 1); RBT_PAR_FOR(i, Nc * Nc) t->sb[1024 + 256 * q + i] = sp[(size_t)(i >> (lg - 1)) * g->cw + (i & (Nc - 1))]; }
+    if (!EN_FLAT(e)) for (int q = 0; q < 2; q++) { const uint16_t* sp = (q ? e->src[2] : e->src[1]) + (size_t)((cy + y0) >> 1) * g->cw + ((cx + x0) >> 1); RBT_PAR_FOR(i, Nc * Nc) t->sb[1024 + 256 * q + i] = sp[(size_t)(i >> (lg - 1)) * g->cw + (i & (Nc - 1))]; }
     RBT_SYNC();
     int have_w = 0, ssd_w = 0, cbf_w = 0; long long c_w = 0;
     if (refine) {
@@ -873,15 +891,15 @@ template <int TL2> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices
       for (int b = 0; b < 4; b++) {
         const int ox = (b & 1) * hh, oy = (b >> 1) * hh;
         RBT_PAR_FOR(i, n4u * n4u) t->uav[(((y0 + oy) >> 2) + i / n4u + 1) * RC_US + ((x0 + ox) >> 2) + i % n4u + 1] = 1;
-        RBT_PAR_FOR(i, 2 * hc * hc) { const int q = i >= hc * hc, j = i - q * hc * hc; t->ss[q * 256 + j] = t->sb[1024 + 256 * q + ((oy >> 1) + j / hc) * Nc + (ox >> 1) + j % hc]; }
+        if (!EN_FLAT(e)) RBT_PAR_FOR(i, 2 * hc * hc) { const int q = i >= hc * hc, j = i - q * hc * hc; t->ss[q * 256 + j] = t->sb[1024 + 256 * q + ((oy >> 1) + j / hc) * Nc + (ox >> 1) + j % hc]; }
         RBT_SYNC_LDS();
-        const int cc = en_tile_intra_tb_cpair(e, f, L, (x0 + ox) >> 1, (y0 + oy) >> 1, (cx + x0 + ox) >> 1, (cy + y0 + oy) >> 1, lg - 2, mode, qp_cb, qp_cr, t->ss);
+        const int cc = EN_FLAT(e) ? 0 : en_tile_intra_tb_cpair(e, f, L, (x0 + ox) >> 1, (y0 + oy) >> 1, (cx + x0 + ox) >> 1, (cy + y0 + oy) >> 1, lg - 2, mode, qp_cb, qp_cr, t->ss);
         const int fl = RBT_CU_TU_SPLIT | ((cy4 >> b) & 1 ? RBT_CU_CBF_Y : 0) | ((cc & 1) ? RBT_CU_CBF_CB : 0) | ((cc & 2) ? RBT_CU_CBF_CR : 0);
         en_fill_cu_maps_ctx(e, cx + x0 + ox, cy + y0 + oy, hh, RBT_MODE_INTRA | ((fl & RBT_CU_CBF_Y) ? RBT_PM_NZ : 0), qp_y, fl);
       }
       continue;
     }
-    { const int cc = en_tile_intra_tb_cpair(e, f, L, x0 >> 1, y0 >> 1, (cx + x0) >> 1, (cy + y0) >> 1, lg - 1, mode, qp_cb, qp_cr, t->sb + 1024);
+    { const int cc = EN_FLAT(e) ? 0 : en_tile_intra_tb_cpair(e, f, L, x0 >> 1, y0 >> 1, (cx + x0) >> 1, (cy + y0) >> 1, lg - 1, mode, qp_cb, qp_cr, t->sb + 1024);
       if (cc & 1) cbf |= RBT_CU_CBF_CB;
       if (cc & 2) cbf |= RBT_CU_CBF_CR; }
     if (split) cbf |= RBT_CU_TU_SPLIT | ((cy4 & 1) ? RBT_CU_CBF_Y : 0) | ((cy4 >> 1) * RBT_CU_CBF_Y1);   // 8x8 CU as four 4x4 luma blocks: their cbf bits
@@ -893,6 +911,11 @@ template <int TL2> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices
   for (int c = 0; c < 3; c++) {
     const int sh = c ? 1 : 0, nn = ctb >> sh, lnn = g->log2_ctb - sh, pw = c ? g->cw : g->w, ph = c ? g->ch : g->h, ox = cx >> sh, oy = cy >> sh, S = c ? RbtEncTileT<TL2>::TS_C : RbtEncTileT<TL2>::TS_Y;
     uint16_t* p = f->pix[c]; RBT_LDS_AS uint16_t* tile = c == 0 ? t->y : t->c[c - 1];
+    if (c && EN_FLAT(e)) {      // (coef picked by a test, not by index: a run-time index would put the whole context into scratch memory) what the chroma blocks of the CTB's CUs would have left: v in the reconstruction, 0 in the levels (the picture is whole CUs: everything inside it is covered)
+      int16_t* cp = c == 1 ? e->coef[1] : e->coef[2]; const uint16_t v = (uint16_t)(1 << (bd - 1));
+      RBT_PAR_FOR(i, nn * nn) { int x = i & (nn - 1), y = i >> lnn; if (ox + x < pw && oy + y < ph) { const size_t o = (size_t)(oy + y) * pw + ox + x; p[o] = v; cp[o] = 0; } }
+      continue;
+    }
     RBT_PAR_FOR(i, nn * nn) { int x = i & (nn - 1), y = i >> lnn; if (ox + x < pw && oy + y < ph) p[(size_t)(oy + y) * pw + ox + x] = tile[y * S + x + 1]; }
   }
 }
@@ -902,6 +925,12 @@ RBT_DEV void en_inter_ctb(RbtFrame* frames, RbtFrame* f, const RbtSlice* slices,
   const RbtStreamCfg* g = &f->cfg;
   const RbtFrame* ref = &frames[f->ref_frame];
   int ctb = 1 << g->log2_ctb, cx = (ctb_addr % g->w_ctb) << g->log2_ctb, cy = (ctb_addr / g->w_ctb) << g->log2_ctb;
+  // a P picture with a flat source coded from a flat reconstruction is flat (zero motion, prediction v, residual 0): said for its loop filters. The reference's
+  // word is read only where an earlier launch wrote it (an I picture's, by en_intra_ctb).
+  int flat;
+  { const uint32_t* sf = rbt_uni_ptr(f->src_flat); flat = sf && RBT_UNI(*sf) && RBT_UNI(ref->ref_frame) < 0 && RBT_UNI(ref->chroma_flat); }
+  if (ctb_addr == 0 && RBT_LANE0) f->chroma_flat = (uint32_t)flat;
+  EN_FLAT_COUNT(1, flat);
   const RbtSlice* sl = &slices[f->ctb_slice[ctb_addr]];
   int qp_y = sl->qp, bd = g->bit_depth;
   int qp[3] = {qp_y + 6 * (bd - 8), en_chroma_qp(f, sl, 1, qp_y), en_chroma_qp(f, sl, 2, qp_y)};
@@ -910,7 +939,11 @@ RBT_DEV void en_inter_ctb(RbtFrame* frames, RbtFrame* f, const RbtSlice* slices,
     int x0 = cx + (b % n16) * 16, y0 = cy + (b / n16) * 16;
     if (x0 >= g->w || y0 >= g->h) continue;
     int cbf = 0;
-    for (int c = 0; c < 3; c++) {
+    // flat: the Cb / Cr blocks' prediction is v, their residual 0 and their cbf 0 (en_code_tb stores no levels of such a block): the reconstruction is stored, nothing is read
+    // (not clipped, like en_code_tb's stores below: pictures with P pictures are coded at a multiple of 16 - coded_size in rbt_transcode.cpp - so a 16x16 CU whose origin
+    // passed the test above lies inside the picture whole)
+    if (flat) { const uint16_t v = (uint16_t)(1 << (bd - 1)); const size_t o0 = (size_t)(y0 >> 1) * g->cw + (x0 >> 1); RBT_PAR_FOR(i, 64) { const size_t o = o0 + (size_t)(i >> 3) * g->cw + (i & 7); f->pix[1][o] = v; f->pix[2][o] = v; } }
+    for (int c = 0; c < (flat ? 1 : 3); c++) {
       int sh = c ? 1 : 0, S = 16 >> sh, pw = c ? g->cw : g->w;
       const uint16_t* rp = ref->out[c];
       RBT_PAR_FOR(i, S * S) { int x = i & (S - 1), y = i / S; l->rc.pred[i] = rp[(size_t)((y0 >> sh) + y) * pw + (x0 >> sh) + x]; }
@@ -1311,6 +1344,9 @@ RBT_DEV void en_wave_sum16(const int (&v)[16], RBT_LDS_AS int32_t* dst) {
 template <bool REGION> RBT_DEV void en_sao_ctb(RbtFrame* f, const RbtSlice* slices, int ctb_addr, RBT_LDS_AS RbtSaoLds* L, RBT_LDS_AS uint16_t* ry, RBT_LDS_AS uint16_t* rc0, RBT_LDS_AS uint16_t* rc1) {
   const RbtStreamCfg gcopy = rc_cfg_uni(&f->cfg); const RbtStreamCfg* g = &gcopy;
   const int ctb = 1 << g->log2_ctb, cxi = ctb_addr % g->w_ctb, cyi = ctb_addr / g->w_ctb, bd = g->bit_depth, has_occ = RBT_UNI(f->occ4 != nullptr);
+  // flat reconstruction of a flat source: source minus reconstruction is 0 in Cb and Cr, every offset is 0 and the chroma type is 0 - no chroma statistics
+  const int flat = RBT_UNI(f->chroma_flat) != 0;
+  EN_FLAT_COUNT(2, flat);
   const RbtSlice* sl = &slices[f->ctb_slice[ctb_addr]];
   const long long lam16 = k_lambda16[rbt_clip3(0, 75, sl->qp + 6 * (bd - 8))], lam = lam16 * lam16;
   // a CTB made of skipped CUs only is a copy of the (already filtered) reference: no statistics, no offsets (P pictures are mostly that)
@@ -1349,7 +1385,7 @@ template <bool REGION> RBT_DEV void en_sao_ctb(RbtFrame* f, const RbtSlice* slic
   }
   // deblocked sample of plane c at picture position (x,y) (inside the CTB or one sample around it)
 #define EN_SAO_RP(c, x, y) (REGION ? ((c) == 0 ? (int)ry[((y) - oy) * RS + ((x) - ox)] : (int)((c) == 1 ? rc0 : rc1)[((y) - coy) * RSC + ((x) - cox)]) : (int)f->pix[c][(size_t)(y) * pw + (x)])
-  for (int c = 0; c < 3 && !all_skip; c++) {
+  for (int c = 0; c < (flat ? 1 : 3) && !all_skip; c++) {
     const int sh = c ? 1 : 0, pw = c ? g->cw : g->w, ph = c ? g->ch : g->h, n = ctb >> sh, lgn = g->log2_ctb - sh;
     const int x0 = (cxi * ctb) >> sh, y0 = (cyi * ctb) >> sh;
     const uint16_t* sp = f->src[c];
@@ -1434,7 +1470,7 @@ template <bool REGION> RBT_DEV void en_sao_ctb(RbtFrame* f, const RbtSlice* slic
   if (bt >= 0) { out.type[0] = bt == 0 ? 1 : 2; out.band_pos[0] = (uint8_t)(bt == 0 ? L->bpos[0] : 0); out.eo_class[0] = (uint8_t)(bt ? bt - 1 : 0);
     for (int k = 0; k < 4; k++) out.offset[0][k] = (int8_t)(bt == 0 ? L->off[0][L->bpos[0] + k] : L->off[0][32 + (bt - 1) * 4 + k]); }
   bt = -1; bgn = 0;
-  if (!all_skip) for (int t = 0; t < 5; t++) if (L->tgain[1][t] + L->tgain[2][t] > bgn) { bgn = L->tgain[1][t] + L->tgain[2][t]; bt = t; }
+  if (!all_skip && !flat) for (int t = 0; t < 5; t++) if (L->tgain[1][t] + L->tgain[2][t] > bgn) { bgn = L->tgain[1][t] + L->tgain[2][t]; bt = t; }
   if (bt >= 0) for (int c = 1; c < 3; c++) { out.type[c] = bt == 0 ? 1 : 2; out.band_pos[c] = (uint8_t)(bt == 0 ? L->bpos[c] : 0); out.eo_class[c] = (uint8_t)(bt ? bt - 1 : 0);
     for (int k = 0; k < 4; k++) out.offset[c][k] = (int8_t)(bt == 0 ? L->off[c][L->bpos[c] + k] : L->off[c][32 + (bt - 1) * 4 + k]); }
   // a type whose offsets are all zero costs bits for nothing

@@ -124,7 +124,8 @@ RBT_DEV void rbt_deblock_unit(RbtFrame* f, const RbtSlice* slices, int unit, int
   int bs = fl_bs(f, slices, x, y, dir);
   if (!bs) return;
   fl_luma_segment(f, slices, x, y, dir, bs);
-  if (bs == 2 && !(dir == 0 ? (x & 15) : (y & 15))) { fl_chroma_segment(f, slices, 1, x, y, dir); fl_chroma_segment(f, slices, 2, x, y, dir); }
+  // (a flat picture's chroma edges: the filter's delta over a constant plane is 0 and every sample it would store is the one that is there - DESIGN.md 14)
+  if (bs == 2 && !(dir == 0 ? (x & 15) : (y & 15)) && !f->chroma_flat) { fl_chroma_segment(f, slices, 1, x, y, dir); fl_chroma_segment(f, slices, 2, x, y, dir); }
 }
 
 // SAO of one sample of component c: reads f->pix (deblocked), writes f->out
@@ -178,6 +179,8 @@ RBT_DEV void rbt_sao_ctb_p(RbtFrame* f, const RbtSlice* slices, int ctb, const R
     const int sh = c ? 1 : 0, pw = c ? g->cw : g->w, ph = c ? g->ch : g->h, x0 = cx >> sh, y0 = cy >> sh;
     const int nw = rbt_min((1 << g->log2_ctb) >> sh, pw - x0), nh = rbt_min((1 << g->log2_ctb) >> sh, ph - y0);
     const uint16_t* sp = f->pix[c]; uint16_t* dp = f->out[c];
+    // a flat picture has no chroma SAO type and its deblocked chroma is the constant: the copy without its loads. The encoder sets the word on its own pictures too (en_intra_ctb / en_inter_ctb, CTB 0) where source and reconstruction are flat: en_sao_ctb has then decided chroma type 0 and the same fill applies
+    if (c && f->chroma_flat) { const uint16_t v = (uint16_t)(1 << (bd - 1)); RBT_BLK_FOR(i, nw * nh) dp[(size_t)(y0 + i / nw) * pw + x0 + i % nw] = v; continue; }
     const int type = (c ? sl->sao_chroma : sl->sao_luma) ? s->type[c] : 0;
     if (!type) { RBT_BLK_FOR(i, nw * nh) { const size_t o = (size_t)(y0 + i / nw) * pw + x0 + i % nw; dp[o] = sp[o]; } continue; }
     const int o0 = s->offset[c][0], o1 = s->offset[c][1], o2 = s->offset[c][2], o3 = s->offset[c][3];

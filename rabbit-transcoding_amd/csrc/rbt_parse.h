@@ -62,6 +62,7 @@ struct RbtParse {
   int qp_key, qp_packed;             // qP of Y | Cb << 8 | Cr << 16 (incl. QpBdOffset) cached for QpY == qp_key (chroma mapping costs ~300 cycles)
   int il_packed, intra_chroma, max_trafo_depth, last_pu_merge;   // no arrays / index-selected fields here: they would pin the whole struct in scratch
   int error;
+  int chroma_seen;                      // wave-uniform: a cbf_cb / cbf_cr of 1 or a chroma SAO type was parsed (RbtFrame::chroma_seen; off the bin-to-bin chain: an OR of values just decoded)
   uint32_t sao_w0, sao_w1, sao_w2, sao_w3, sao_w4, sao_w5;   // intra-only instantiation, live inside pz_sao only (a local record of its own was left in scratch memory by the compiler; as part of this one it is registers)
   // Register-resident neighbour context (one value per lane). Current CTB, four horizontally adjacent 4x4 units per lane:
   // unit (ux,uy) lives in lane uy * 4 + (ux >> 2), byte ux & 3 (mv: register r_mv<ux & 3>).
@@ -495,6 +496,7 @@ template <bool IO> RBT_DEV void pz_sao(RbtParse* s, int rx, int ry) {
         pz_saow_comp<0>(s, c, bd, cmax); pz_saow_comp<1>(s, c, bd, cmax); pz_saow_comp<2>(s, c, bd, cmax);
       }
     }
+    s->chroma_seen |= (s->sao_w0 & 0xFFFF00u) != 0;     // type[1] | type[2], merged or parsed
     if (RBT_LANE0) {
       uint32_t* g = (uint32_t*)&s->f->sao[ry * wc + rx]; RBT_LDS_AS uint32_t* l = (RBT_LDS_AS uint32_t*)&s->L->sao_left; RBT_LDS_AS uint32_t* a = (RBT_LDS_AS uint32_t*)&pz_sao_above(s->L, s->L->cap4)[rx];
       const uint32_t w0 = s->sao_w0, w1 = s->sao_w1, w2 = s->sao_w2, w3 = s->sao_w3, w4 = s->sao_w4, w5 = s->sao_w5;
@@ -517,6 +519,7 @@ template <bool IO> RBT_DEV void pz_sao(RbtParse* s, int rx, int ry) {
       pz_sao_comp<0>(s, c, &p, bd, cmax); pz_sao_comp<1>(s, c, &p, bd, cmax); pz_sao_comp<2>(s, c, &p, bd, cmax);
     }
   }
+  s->chroma_seen |= (p.type[1] | p.type[2]) != 0;     // type[1] | type[2], merged or parsed
   if (RBT_LANE0) {
     uint32_t* g = (uint32_t*)&s->f->sao[ry * wc + rx]; RBT_LDS_AS uint32_t* l = (RBT_LDS_AS uint32_t*)&s->L->sao_left; RBT_LDS_AS uint32_t* a = (RBT_LDS_AS uint32_t*)&pz_sao_above(s->L, s->L->cap4)[rx];
 #pragma unroll
@@ -781,6 +784,7 @@ template <bool IO> RBT_DEV void pz_transform_tree(RbtParse* s, int x0, int y0, i
         if (lvl == 0 || ppcb) cbf_cb = rbt_cd_bin(c, CTX_CBF_CHROMA + lvl);
         if (lvl == 0 || ppcr) cbf_cr = rbt_cd_bin(c, CTX_CBF_CHROMA + lvl);
       } else { cbf_cb = ppcb; cbf_cr = ppcr; }
+      s->chroma_seen |= cbf_cb | cbf_cr;
       if (!split) {
         int cbf_luma = 1;
         if (intra || lvl != 0 || cbf_cb || cbf_cr) cbf_luma = rbt_cd_bin(c, CTX_CBF_LUMA + (lvl == 0 ? 1 : 0));
@@ -1173,7 +1177,7 @@ template <bool IO> RBT_DEV void rbt_parse_slice_t(RbtFrame* frames, RbtSlice* sl
   else { RBT_LDS_AS uint32_t* lw = (RBT_LDS_AS uint32_t*)lds; RBT_PAR_FOR(i, (int)(RBT_PARSE_LDS_BYTES(cap4) / 4)) lw[i] = sv->lds[i]; }
   RBT_SYNC();
   if (RBT_LANE0) lds->cap4 = cap4;
-  s.frames = frames; s.f = &frames[RBT_UNI(gs->frame)]; s.slice_idx = slice_idx; s.error = 0;
+  s.frames = frames; s.f = &frames[RBT_UNI(gs->frame)]; s.slice_idx = slice_idx; s.error = 0; s.chroma_seen = 0;
   s.s_bits = (uint32_t)RBT_UNI((gs->slice_type & 3) | ((gs->sao_luma & 1) << 2) | ((gs->sao_chroma & 1) << 3) | ((gs->temporal_mvp & 1) << 4) | ((gs->cabac_init_flag & 1) << 5) |
                                ((gs->max_merge_cand & 7) << 6) | ((gs->num_ref_idx & 31) << 9) | ((gs->collocated_ref_idx & 15) << 14));
   s.s_qp = (uint32_t)RBT_UNI((uint32_t)(uint8_t)gs->qp | ((uint32_t)(uint8_t)gs->cb_qp_offset << 8) | ((uint32_t)(uint8_t)gs->cr_qp_offset << 16));
@@ -1240,6 +1244,7 @@ template <bool IO> RBT_DEV void rbt_parse_slice_t(RbtFrame* frames, RbtSlice* sl
 #else
       { const int ln = (int)threadIdx.x & 63; sv->ctx[0][ln] = (uint32_t)s.c.cs.st0; sv->ctx[1][ln] = (uint32_t)s.c.cs.st1; sv->ctx[2][ln] = (uint32_t)s.c.cs.st2; sv->ctx[3][ln] = (uint32_t)s.c.cs.st3; }
 #endif
+      if (RBT_LANE0 && RBT_UNI(s.chroma_seen)) s.f->chroma_seen = 1u;     // (a banded parse: the host has marked the picture chroma_unknown anyway)
       if (RBT_LANE0) {
         int32_t* q = sv->sc;
         q[0] = s.left_ok; q[1] = s.corner_ok; q[2] = s.corner_pm; q[3] = s.corner_dm;
@@ -1330,6 +1335,8 @@ template <bool IO> RBT_DEV void rbt_parse_slice_t(RbtFrame* frames, RbtSlice* sl
   if (RBT_LANE0) for (int i = 22; i < 26; i++) printf("stamp %d: %llu cycles, %u hits\n", i, lds->prof[i], lds->profn[i]);
   if (RBT_LANE0) printf("slice %d: total %llu cyc, residual %llu (%u TBs) [setup+last %llu, csbf+sig %llu, gt1/2 %llu, levels %llu], TU total (incl. residual) %llu, CU header %llu (%u CUs), ctb begin/end %llu, CU total %llu, fills %llu, mpm %llu, bins ctx %u bypass %u, bits %u\n", slice_idx, __builtin_readcyclecounter() - t_all_, s.t_res, s.n_res, s.t_a, s.t_b, s.t_c, s.t_d, s.t_tu, s.t_hdr, s.n_cu, s.t_ctb, s.t_cu, s.t_fill, s.t_mpm, s.c.n_bins, s.c.n_byp, s.c.widx * 32u - (uint32_t)s.c.nbuf);
 #endif
+  // every wave of a picture (row tasks, slices) that saw chroma stores the same 1 over the host's 0: a plain store, no atomics
+  if (RBT_LANE0 && RBT_UNI(s.chroma_seen)) s.f->chroma_seen = 1u;
   if (RBT_LANE0) { slices[own_idx].n_ctbs_decoded = count; if (s.error) s.f->error = s.error; if (sv) sv->phase = 2; }
   // a wave that gave up lets the row below go on at once (the picture is marked bad; nobody waits out the bound for rows that will not come)
   if (s.error && wpp && addr < n_ctb) { const int wc = pzc_w_ctb(&s); RBT_FLAG_PUBLISH(&s.f->prow_done[addr / wc], wc); }

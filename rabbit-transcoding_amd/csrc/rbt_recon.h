@@ -569,12 +569,40 @@ RBT_DEV RbtCmd rc_cmd_uni(const RbtCmdRaw& raw) {
   u.r.w[0] = RBT_UNI(raw.w[0]); u.r.w[1] = RBT_UNI(raw.w[1]); u.r.w[2] = RBT_UNI(raw.w[2]); u.r.w[3] = RBT_UNI(raw.w[3]);
   return u.c;
 }
+// flat(f) of DESIGN.md 14 as wave-uniform scalars: the picture's own word (the parser's, complete before any reconstruction launch of the picture unless the host says
+// chroma_unknown) and the chroma_flat words of its reference pictures, which CTB 0 of each stored in an earlier level's launch. Nothing here is written in the caller's launch.
+RBT_DEV int rc_chroma_flat(const RbtFrame* frames, const RbtFrame* f) {
+  int flat = !(RBT_UNI(f->chroma_seen) | RBT_UNI(f->chroma_unknown));
+#pragma unroll
+  for (int i = 0; i < RBT_MAX_REFS; i++) { const int r = RBT_UNI(f->flat_ref[i]); if (r >= 0) flat &= RBT_UNI(frames[r].chroma_flat) != 0; }
+  return flat;
+}
+// The Cb/Cr half of a CTB of a flat picture: both planes at 1 << (bit_depth - 1), clipped to the picture - the samples the general path computes, with no
+// command walk, no tile fetch and no marks. The stores stay: pix[1] / pix[2] are read by both deblockers, SAO, and (as `out` of a picture without SAO) by motion compensation,
+// the hash check, the read-back and the encoder.
+RBT_DEV void rc_fill_flat_ctb(RbtFrame* f, int ctb_addr) {
+  const int L = RBT_UNI(f->cfg.log2_ctb), wc = RBT_UNI(f->cfg.w_ctb), cw = RBT_UNI(f->cfg.cw), ch = RBT_UNI(f->cfg.ch), v = 1 << (RBT_UNI(f->cfg.bit_depth) - 1);
+  const int nn = 1 << (L - 1), ox = (ctb_addr % wc) << (L - 1), oy = (ctb_addr / wc) << (L - 1), nw = rbt_min(nn, cw - ox), nh = rbt_min(nn, ch - oy);
+  uint16_t* cb = f->pix[1]; uint16_t* cr = f->pix[2];
+  // two samples per lane and store: the luma size is a multiple of the minimum CU size, 8, so a chroma row is a multiple of 4 samples long, and so is what of it lies in a CTB
+  const int nw2 = nw >> 1; const uint32_t vv = (uint32_t)v * 0x10001u;
+  RBT_PAR_FOR(i, nw2 * nh) { const int y = i / nw2, x2 = i - y * nw2; const size_t o = (size_t)(oy + y) * cw + ox + 2 * x2; *(uint32_t*)(cb + o) = vv; *(uint32_t*)(cr + o) = vv; }
+}
 // ROLE: RC_ROLE_LUMA / RC_ROLE_CHROMA = the calling wave's half of the CTB (see RbtReconRole); RC_ROLE_ALL = everything on one wave.
 template <int ROLE>
 RBT_DEV void rbt_recon_ctb(RbtFrame* frames, const RbtSlice* slices, int frame_idx, int ctb_addr, RBT_LDS_AS RbtCtbTile* t, RBT_LDS_AS RbtReconRole* R) {
   constexpr bool DO_Y = ROLE != RC_ROLE_CHROMA, DO_C = ROLE != RC_ROLE_LUMA;
   frame_idx = RBT_UNI(frame_idx); ctb_addr = RBT_UNI(ctb_addr);
   RbtFrame* f = &frames[frame_idx];
+  if constexpr (DO_C) {
+    const int flat = rc_chroma_flat(frames, f);
+    if (ctb_addr == 0 && RBT_LANE0) f->chroma_flat = (uint32_t)flat;      // for the later levels, the loop filters and the encoder (all behind this launch)
+    if (flat) {
+      rc_fill_flat_ctb(f, ctb_addr);
+      if constexpr (DO_Y) rbt_recon_ctb<RC_ROLE_LUMA>(frames, slices, frame_idx, ctb_addr, t, R);
+      return;
+    }
+  }
   const RbtStreamCfg gcopy = rc_cfg_uni(&f->cfg);                        // private copy: not reloaded after every store, and in scalar registers
   const RbtStreamCfg* g = &gcopy;
   const int ctb = 1 << g->log2_ctb, n4 = ctb >> 2, cx = (ctb_addr % g->w_ctb) << g->log2_ctb, cy = (ctb_addr / g->w_ctb) << g->log2_ctb;

@@ -71,8 +71,12 @@ struct RbtFrame {
   int32_t* refpoc;               // per 4x4: POC of the reference (for TMVP / deblocking), filled after parsing
   RbtSao* sao;                   // per CTB
   uint16_t* ctb_slice;           // per CTB: index into the batch slice table
-  RbtCmd* cmds;                  // per CTB: cmd_cap records
-  int32_t cmd_cap;
+  union {                        // (one side's fields in the room of the other's: a picture is decoded or encoded, and device memory per picture is pinned to the byte - tests/test_arena_footprint.py)
+    struct { RbtCmd* cmds; int32_t cmd_cap; };      // decoder, per CTB: cmd_cap records
+    // encoder, flat chroma: the chroma_flat word (device) of the decoded picture this one is coded from, or its own src_flat_one - a source whose chroma is constant by
+    // construction (pooled occupancy maps) -, nullptr = not known to be flat
+    struct { const uint32_t* src_flat; uint32_t src_flat_one; };
+  };
   uint32_t* cmd_count;           // per CTB
   int32_t poc;
   int32_t level;                 // dependency level inside the batch (0: no references inside the batch)
@@ -84,7 +88,16 @@ struct RbtFrame {
   // reading wave writes itself: mv int32[w4] | RbtSao[w_ctb] | slice u16[w_ctb] | pm, dm, ref bytes[w4] each)
   uint32_t* prow_done; uint8_t* prow_ctx; uint8_t* prow_line; int32_t prow_line_bytes;
   // ---- encoder side (RBT-E1) ----
-  const uint16_t* src[3];        // source planes (the decoder's `out` planes or the pooled occupancy map)
+  union {
+    const uint16_t* src[3];      // source planes (the decoder's `out` planes or the pooled occupancy map)
+    // decoder, flat chroma - a picture with no coded chroma block and no chroma SAO, default weighting, no constrained intra prediction and flat references is flat:
+    struct {
+      uint32_t chroma_seen;      // 0 from the host's upload; the slice parser stores 1 when a slice of the picture holds a cbf_cb / cbf_cr of 1 or a CTB with a chroma SAO type
+      uint32_t chroma_unknown;   // from the host: what the headers rule out (constrained intra prediction, a slice with explicit weights, more distinct reference pictures than
+                                 // flat_ref holds) or a parse that is not complete when the reconstruction starts (banded parse): never flat
+      int32_t flat_ref[RBT_MAX_REFS];   // from the host: batch indices of the distinct reference pictures of the picture's slices, -1 = unused
+    };
+  };
   uint8_t* cu_log2;              // per 8x8 unit: log2 size of the coding unit covering it
   uint8_t* cu_mode;              // per 8x8 unit: luma intra prediction mode of that CU
   uint8_t* cu_flags;             // per 8x8 unit: RBT_CU_* bits of that CU
@@ -106,11 +119,14 @@ struct RbtFrame {
   // the unit or of a unit next to it (k_occ_units, from the occupancy map the output carries); occ4_w x occ4_h units, units beyond are unoccupied; nullptr = every sample counts
   const uint8_t* occ4; int32_t occ4_w, occ4_h;
   int32_t enc_tools;             // RBT_ET_* decision tools of RBT-E1 (all on unless a development switch RBT_ENC_SATD / _REFINE / _RQ = 0 says otherwise: oracle/hevc_enc.c)
-  int32_t pad_et;
+  uint32_t chroma_flat;          // flat chroma: both chroma planes of the reconstruction are 1 << (bit_depth - 1) everywhere, before and after the loop filters.
+                                 // Decoder: flat(picture), stored by the reconstruction workgroup of CTB 0 (rc_chroma_flat) for the later levels, the loop filters and the
+                                 // encoder. Encoder: stored by CTB 0 of en_intra_ctb / en_inter_ctb for the picture's loop filters and the P picture coded from it. 0 from the host.
 };
 #define RBT_ET_SATD 1      // block costs of the intra analysis by SATD (en_analyse_ctb)
 #define RBT_ET_REFINE 2    // closed-loop choice of the luma intra mode (en_refine_mode)
 #define RBT_ET_RQ 4        // rounding offset of the intra quantiser by level and position (en_rq_offset)
+#define RBT_ET_ALL (1 | 2 | 4 | 16)      // every RBT_ET_* bit (a new one is added here too: csrc/rbt_encode.h keeps a private bit of its CTB context clear of them)
 #define RBT_ET_RDM 16      // the two cheapest candidates of the closed-loop mode choice coded as one transform block each, the cheaper kept (en_intra_ctb; oracle e1_mode_trial)
 #define RBT_CU_CBF_Y 1
 #define RBT_CU_CBF_CB 2

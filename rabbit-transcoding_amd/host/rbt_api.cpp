@@ -11,7 +11,7 @@
 #include "rbt_internal.h"
 
 struct rbt_pcloud { rbt::PCloud* cloud; rbt_ctx* owner; };
-struct rbt_ctx { int device, rank, world; rbt_stats stats; std::string last_err; double color_ms[4] = {0, 0, 0, 0}; int n_changed = 0;
+struct rbt_ctx { int device, rank, world; rbt_stats stats; std::string last_err; double color_ms[4] = {0, 0, 0, 0}; int n_changed = 0; int n_flat = 0;
                  std::vector<rbt_pcloud*> clouds; rbt::PCloudCache cloud_cache; };      // handles outstanding; clean volumes of released clouds
 struct rbt_job { rbt::GofJob* j; rbt_ctx* owner; };
 
@@ -75,6 +75,7 @@ void rbt_destroy(rbt_ctx* ctx) {
 // walks the sequence GOF by GOF (PccAppTranscoder.cpp:307-341) on every rank skips the GOFs its context does not own.
 int rbt_owns_gof(const rbt_ctx* ctx, int gof_index) { return ctx && gof_index >= 0 && gof_index % ctx->world == ctx->rank; }
 int rbt_world(const rbt_ctx* ctx, int* rank, int* size) { if (!ctx) return RBT_ERR_PARAM; if (rank) *rank = ctx->rank; if (size) *size = ctx->world; return RBT_OK; }
+int rbt_flat_pictures(const rbt_ctx* ctx) { return ctx ? ctx->n_flat : 0; }
 int rbt_get_stats(rbt_ctx* ctx, rbt_stats* out) { if (!ctx || !out) return RBT_ERR_PARAM; *out = ctx->stats; return RBT_OK; }
 
 int rbt_decode(rbt_ctx* ctx, const uint8_t* annexb, size_t n, int verify_md5, rbt_video* out) try {
@@ -89,6 +90,7 @@ int rbt_decode(rbt_ctx* ctx, const uint8_t* annexb, size_t n, int verify_md5, rb
   if (!rc) rc = rbt::decode_fetch(b, 0, out);
   if (!rc && verify_md5) rbt::decode_hash_result(b, 0, out->md5_checked, out->md5_failed);
   if (rc) { ctx->last_err = b.err; free(out->data); memset(out, 0, sizeof(*out)); return rc; }
+  ctx->n_flat = b.n_flat;
   ctx->stats.k_parse_ms = rbtk::timer_ms(rbt::T_PARSE); ctx->stats.k_recon_ms = rbtk::timer_ms(rbt::T_RECON);
   if (verify_md5 && out->md5_failed) return RBT_ERR_MD5;
   return RBT_OK;
@@ -261,7 +263,9 @@ static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out,
   if (slot < 0 || job->owner != ctx) return RBT_ERR_PARAM;
   if (rbt::gof_is_quality(job->j) != (quality != nullptr)) {      // the job stays collectable
     ctx->last_err = quality ? "rbt_wait_gof_quality collects jobs of rbt_submit_gof_quality only" : "a job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality"; return RBT_ERR_PARAM; }
-  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality);
+  int n_flat = 0;
+  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality, &n_flat);
+  if (!rc) ctx->n_flat = n_flat;
   D.jobs[slot] = nullptr; delete job;
   return rc;
 }

@@ -115,6 +115,7 @@ struct DecodeBatch {
   RbtFrame* d_frames = nullptr; RbtSlice* d_slices = nullptr; uint8_t* d_rbsp = nullptr; int32_t* d_lists = nullptr;
   CensusSet census; std::vector<int> census_first;   // rate targets: the pictures of the streams that are counted (census_first[stream]: index of the stream's first picture in `census`, -1: not counted)
   HashSet hash; std::vector<int> hash_checked;   // verify_md5: the pictures of the checked streams (counter = stream), pictures checked per stream
+  int n_flat = 0;                      // after decode_finish: pictures reconstructed with flat chroma (RbtFrame::chroma_flat, read back with the error words)
   std::string err; int err_code = 0;
   ~DecodeBatch() { rbtk::dev_free(arena); }
 };

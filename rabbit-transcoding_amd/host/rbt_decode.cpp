@@ -184,6 +184,17 @@ int decode_build(DecodeBatch& b, const StreamIn* streams, int n_streams) {
   for (size_t i = 0; i < b.slices.size(); i++) if (!b.slices[i].end_addr) { const RbtStreamCfg& c = b.frames[b.slices[i].frame].cfg; b.slices[i].end_addr = c.w_ctb * c.h_ctb; }   // the last entry of a picture ends with the picture
   if (b.has_row_tasks) b.want_save = false;                              // banded (resumable) parsing re-launches the list; row tasks need one ordered launch
   if (b.slices.size() >= 0xFFFF) { b.err = "too many slice segments"; return b.err_code = RBT_ERR_UNSUPPORTED; }
+  // flat chroma: what the headers decide. The distinct reference pictures of a picture's slices, whose chroma_flat words its reconstruction reads; never
+  // flat under constrained intra prediction, with explicit weights in any slice, with more references than flat_ref holds, or where the reconstruction starts before the
+  // parse is complete (banded parse: d_save)
+  for (size_t i = 0; i < b.frames.size(); i++) { RbtFrame& f = b.frames[i];
+    f.chroma_seen = f.chroma_flat = 0; f.chroma_unknown = f.cfg.cip || b.want_save; for (int k = 0; k < RBT_MAX_REFS; k++) f.flat_ref[k] = -1;
+    for (int k = 0; k < f.n_slices; k++) { const RbtSlice& s = b.slices[(size_t)f.first_slice + k];
+      if (s.wp_on) f.chroma_unknown = 1;
+      for (int r = 0; s.slice_type != RBT_SLICE_I && r < s.num_ref_idx; r++) {
+        if (r >= RBT_MAX_REFS) { f.chroma_unknown = 1; break; }
+        int q = 0; while (q < RBT_MAX_REFS && f.flat_ref[q] >= 0 && f.flat_ref[q] != s.ref_frame[r]) q++;
+        if (q == RBT_MAX_REFS) f.chroma_unknown = 1; else f.flat_ref[q] = s.ref_frame[r]; } } }
   int n_levels = 0; for (auto& f : b.frames) n_levels = std::max(n_levels, f.level + 1);
   b.level_frames.assign(n_levels, {});
   for (size_t i = 0; i < b.frames.size(); i++) b.level_frames[b.frames[i].level].push_back((int)i);
@@ -343,6 +354,7 @@ int decode_finish(DecodeBatch& b) {
   // per-picture error words and slice coverage
   std::vector<RbtFrame> fr(nf);
   if (rbtk::d2h(fr.data(), b.d_frames, nf * sizeof(RbtFrame))) { b.err = "device transfer failed"; return b.err_code = RBT_ERR_NO_DEVICE; }
+  b.n_flat = 0; for (size_t i = 0; i < nf; i++) b.n_flat += fr[i].chroma_flat != 0;
   for (size_t i = 0; i < nf; i++) if (fr[i].error) { b.err = "slice data decoding failed (code " + std::to_string(fr[i].error) + ")"; return b.err_code = RBT_ERR_BITSTREAM; }
   // every CTB of every picture must have been decoded by exactly one slice segment (a truncated stream leaves pictures with holes)
   std::vector<RbtSlice> sl(b.slices.size());

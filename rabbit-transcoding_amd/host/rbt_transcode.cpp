@@ -23,6 +23,8 @@ struct EncStreamDesc {
   int sao = 0;                           // SAO on (every stream that is not lossless, unless RBT_ENC_SAO=0)
   int tools_off = 0;                     // RBT_ET_* decision tools left out (rbt_stream_params.preset)
   std::vector<const uint16_t*> src[3];   // device planes per frame
+  std::vector<const uint32_t*> src_flat; // per frame: the chroma_flat word (device) of the decoded picture the planes belong to, empty = none (RbtFrame::src_flat)
+  bool src_flat_always = false;          // the planes' chroma is the constant 1 << (bd - 1) by construction (pooled occupancy maps)
   // Arena sharing (round 4): per frame, buffers of the DECODED input picture that are dead by the time this picture is encoded and have the encoder's geometry - its
   // coefficient levels (read by the reconstruction of that picture only) and its pre-SAO samples (read by that picture's own loop filters only): the encoder keeps its own
   // levels and reconstruction there instead of in memory of its own (9.8 MB per 1280x1280 picture, 1.26 GB per GOF). Empty / null = the encoder allocates.
@@ -111,6 +113,7 @@ static void encode_lay_out(EncodeBatch& b, Arena& a) {
   b.d_cs = a.take<uint16_t>(cs_words);
   if (a.base) { uint16_t* at = b.d_cs; for (size_t i = 0; i < nf; i++) { b.frames[i].ctb_slice = at; at += (size_t)b.frames[i].cfg.w_ctb * b.frames[i].cfg.h_ctb; } }
   b.d_frames = a.take<RbtFrame>(nf); b.d_slices = a.take<RbtSlice>(ns);
+  if (a.base) for (size_t i = 0; i < nf; i++) if (b.desc[b.frame_stream[i]].src_flat_always) { b.frames[i].src_flat_one = 1; b.frames[i].src_flat = &b.d_frames[i].src_flat_one; }
   if (b.n_sums) b.d_sums = a.take<uint64_t>(b.n_sums);      // right behind the slices: one copy brings both back
   b.d_lists = a.take<int32_t>((nf + ns) * 3); b.d_dst = a.take<uint32_t>(ns);
   // the packed output holds every slice back to back: as large as the slice buffers together, so that slices which fit their buffers always fit it (half of that, which
@@ -139,6 +142,7 @@ static int encode_plan(EncodeBatch& b) {
       f.poc = is_i ? 0 : (i % d.gop); f.level = is_i ? 0 : 1; f.first_slice = (int)b.slices.size();
       f.w8 = s.width / 8; f.h8 = s.height / 8; f.lossless = d.lossless; f.enc_tools = e1_tools(d.lossless) & ~d.tools_off; f.ref_frame = is_i ? -1 : (int)b.frames.size() - 1; f.ref_poc = is_i ? 0 : f.poc - 1;
       for (int c = 0; c < 3; c++) f.src[c] = d.src[c][i];
+      if (!d.src_flat.empty()) f.src_flat = d.src_flat[i];
       if (!d.hint_dm.empty()) { f.hint_pm = d.hint_pm[i]; f.hint_dm = d.hint_dm[i]; f.hint_w4 = d.hint_w4; f.hint_h4 = d.hint_h4; }
       if (!d.occ4.empty() && !d.lossless) { f.occ4 = d.occ4[i]; f.occ4_w = d.occ4_w; f.occ4_h = d.occ4_h; }
       int n_ctb = s.w_ctb * s.h_ctb, step = d.rows > 0 ? d.rows * s.w_ctb : (d.rows < 0 ? s.w_ctb : n_ctb);
@@ -354,6 +358,8 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
   d.bd = c.bit_depth; d.n_frames = cnt; d.qp = p.qp; d.log2_ctb = p.log2_ctb; d.rows = p.ctb_rows_per_slice; d.md5 = p.md5_sei; d.tools_off = p.preset == RBT_PRESET_FAST ? (RBT_ET_SATD | RBT_ET_REFINE | RBT_ET_RQ | RBT_ET_RDM) : 0;
   for (int k = 0; k < 3; k++) d.src[k].resize(cnt);
   auto view = [&](int k, int q) { return (const uint16_t*)db.frames[first + k].out[q]; };
+  // flat chroma: a window of a flat decoded picture, and its padding, are flat; the pooled occupancy maps are flat by construction
+  d.src_flat.resize(cnt); for (int k = 0; k < cnt; k++) d.src_flat[k] = &db.d_frames[first + k].chroma_flat;
   if (p.video_type == RBT_VIDEO_OCCUPANCY) {
     int factor = p.occupancy_precision / 2; if (factor < 1) factor = 1;
     d.gop = 1; d.lossless = 1; d.i_qp_offset = 0; d.w = dw / factor; d.h = dh / factor;
@@ -372,6 +378,7 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
         else rbtk::launch_pool(in, c.w, dw, dh, 2, y, y + ys, y + ys + cs, 1 << (c.bit_depth - 1));
         d.src[0][k] = y; d.src[1][k] = y + ys; d.src[2][k] = y + ys + cs;
       }
+      d.src_flat.clear(); d.src_flat_always = true;
       if (!pool_jobs) rbtk::timer_end(T_POOL);
     } else { d.src_stride = c.w; d.src_x0 = cl; d.src_y0 = ct; for (int k = 0; k < cnt; k++) for (int q = 0; q < 3; q++) d.src[q][k] = view(k, q); }
   } else {
@@ -1029,7 +1036,7 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
 }
 
 // phase B, shortest pipeline first: one sync per stream, then slice sizes -> pack -> NAL assembly. Consumes the job.
-int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* qresults) {
+int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* qresults, int* n_flat) {
   std::unique_ptr<GofJob> guard(J); GofJob& j = *J;
   const int n = j.n, ng = j.ng; int rc = j.rc;
   rbt_stats& st = j.st; std::string& err = j.err;
@@ -1057,6 +1064,7 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
   }
   rbtk::set_stream(0);
   if (rc) { err_out = err; st_out = st; return rc; }
+  if (n_flat) { *n_flat = 0; for (int g = 0; g < ng; g++) *n_flat += db[g].n_flat; }      // decoded pictures reconstructed with flat chroma (came back with the error words: decode_finish)
   for (int i = 0; i < n; i++) if (j.is_pass[i]) outs[i].swap(j.passthrough[i]);
   st.gpu_ms = now_ms() - j.t_gpu;
   rc = hand_out(outs, out, n_out);
