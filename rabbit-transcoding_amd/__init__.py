@@ -425,18 +425,7 @@ class Context:
         return self._take(out, n)
 
     def transcode_gof(self, streams, params):
-        k = len(streams)
-        ins = (C.c_char_p * k)(*streams)
-        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
-        ps = (StreamParams * k)(*params)
-        outs = (C.c_void_p * k)()
-        ns = (C.c_size_t * k)()
-        self._chk(self.L.rbt_transcode_gof(self.h, k, ins, sizes, ps, outs, ns))
-        res = []
-        for i in range(k):
-            res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
-            self.L.rbt_free(outs[i])
-        return res
+        return self._transcode(self.L.rbt_transcode_gof, streams, params)
 
     def transcode_v3c(self, data: bytes, geometry_qp, attribute_qp, occupancy_precision=4, forced_precision_bytes=0, log2_ctb=5, rows_per_slice=-1, md5_sei=0,
                       verify_md5=0, gofs_per_job=1, occupancy_rd=0, preset=0):
@@ -479,108 +468,64 @@ class Context:
         """rbt_trim: hand the cached device memory of earlier jobs back to the driver (call when the workload changes shape)"""
         self._chk(self.L.rbt_trim(self.h))
 
-    def submit_gof(self, streams, params):
-        """rbt_submit_gof: enqueue one GOF; returns a job for wait_gof. Up to set_depth() jobs may be in flight."""
+    @staticmethod
+    def _gof_args(streams, params, targets=None, target_type=None):
+        """the entries of a GOF call as ctypes arguments: count, streams, sizes, params and, for a call with targets, one target_type per entry"""
         k = len(streams)
-        ins = (C.c_char_p * k)(*streams)
-        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
-        ps = (StreamParams * k)(*params)
-        job = C.c_void_p()
-        self._chk(self.L.rbt_submit_gof(self.h, k, ins, sizes, ps, C.byref(job)))
-        return (job, k)
+        args = [k, (C.c_char_p * k)(*streams), (C.c_size_t * k)(*[len(s) for s in streams]), (StreamParams * k)(*params)]
+        return args if target_type is None else args + [(target_type * k)(*targets)]
 
-    def wait_gof(self, job):
-        h, k = job
+    def _submit(self, fn, streams, params, targets=None, target_type=None):
+        job = C.c_void_p()
+        self._chk(fn(self.h, *self._gof_args(streams, params, targets, target_type), C.byref(job)))
+        return (job, len(streams))
+
+    def _collect(self, fn, k, args, result_type=None):
+        """fn(handle, *args, outs, sizes[, results]) -> [stream bytes, ...], with a result_type: ([stream bytes, ...], [result dict, ...])"""
         outs = (C.c_void_p * k)()
         ns = (C.c_size_t * k)()
-        self._chk(self.L.rbt_wait_gof(self.h, h, outs, ns))
+        rs = [(result_type * k)()] if result_type is not None else []
+        self._chk(fn(self.h, *args, outs, ns, *rs))
         res = []
         for i in range(k):
             res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
             self.L.rbt_free(outs[i])
-        return res
+        return (res, [_result_dict(r) for r in rs[0]]) if rs else res
+
+    def _transcode(self, fn, streams, params, targets=None, target_type=None, result_type=None):
+        args = self._gof_args(streams, params, targets, target_type)
+        return self._collect(fn, args[0], args, result_type)
+
+    def submit_gof(self, streams, params):
+        """rbt_submit_gof: enqueue one GOF; returns a job for wait_gof. Up to set_depth() jobs may be in flight."""
+        return self._submit(self.L.rbt_submit_gof, streams, params)
+
+    def wait_gof(self, job):
+        return self._collect(self.L.rbt_wait_gof, job[1], [job[0]])
 
     def submit_gof_rate(self, streams, params, targets):
         """rbt_submit_gof_rate: submit_gof with one RateTarget per entry (target_bytes 0 = constant QP); returns a job for wait_gof_rate"""
-        k = len(streams)
-        ins = (C.c_char_p * k)(*streams)
-        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
-        ps = (StreamParams * k)(*params)
-        ts = (RateTarget * k)(*targets)
-        job = C.c_void_p()
-        self._chk(self.L.rbt_submit_gof_rate(self.h, k, ins, sizes, ps, ts, C.byref(job)))
-        return (job, k)
+        return self._submit(self.L.rbt_submit_gof_rate, streams, params, targets, RateTarget)
 
     def wait_gof_rate(self, job):
         """rbt_wait_gof_rate -> ([stream bytes, ...], [result dict, ...])"""
-        h, k = job
-        outs = (C.c_void_p * k)()
-        ns = (C.c_size_t * k)()
-        rs = (RateResult * k)()
-        self._chk(self.L.rbt_wait_gof_rate(self.h, h, outs, ns, rs))
-        res = []
-        for i in range(k):
-            res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
-            self.L.rbt_free(outs[i])
-        return res, [_result_dict(r) for r in rs]
+        return self._collect(self.L.rbt_wait_gof_rate, job[1], [job[0]], RateResult)
 
     def transcode_gof_rate(self, streams, params, targets):
         """rbt_transcode_gof_rate: submit + wait"""
-        k = len(streams)
-        ins = (C.c_char_p * k)(*streams)
-        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
-        ps = (StreamParams * k)(*params)
-        ts = (RateTarget * k)(*targets)
-        outs = (C.c_void_p * k)()
-        ns = (C.c_size_t * k)()
-        rs = (RateResult * k)()
-        self._chk(self.L.rbt_transcode_gof_rate(self.h, k, ins, sizes, ps, ts, outs, ns, rs))
-        res = []
-        for i in range(k):
-            res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
-            self.L.rbt_free(outs[i])
-        return res, [_result_dict(r) for r in rs]
+        return self._transcode(self.L.rbt_transcode_gof_rate, streams, params, targets, RateTarget, RateResult)
 
     def submit_gof_quality(self, streams, params, targets):
         """rbt_submit_gof_quality: submit_gof with one QualityTarget per entry (min_psnr_mdb 0 = constant QP, distortion reported); returns a job for wait_gof_quality"""
-        k = len(streams)
-        ins = (C.c_char_p * k)(*streams)
-        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
-        ps = (StreamParams * k)(*params)
-        ts = (QualityTarget * k)(*targets)
-        job = C.c_void_p()
-        self._chk(self.L.rbt_submit_gof_quality(self.h, k, ins, sizes, ps, ts, C.byref(job)))
-        return (job, k)
+        return self._submit(self.L.rbt_submit_gof_quality, streams, params, targets, QualityTarget)
 
     def wait_gof_quality(self, job):
         """rbt_wait_gof_quality -> ([stream bytes, ...], [result dict, ...])"""
-        h, k = job
-        outs = (C.c_void_p * k)()
-        ns = (C.c_size_t * k)()
-        rs = (QualityResult * k)()
-        self._chk(self.L.rbt_wait_gof_quality(self.h, h, outs, ns, rs))
-        res = []
-        for i in range(k):
-            res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
-            self.L.rbt_free(outs[i])
-        return res, [_result_dict(r) for r in rs]
+        return self._collect(self.L.rbt_wait_gof_quality, job[1], [job[0]], QualityResult)
 
     def transcode_gof_quality(self, streams, params, targets):
         """rbt_transcode_gof_quality: submit + wait"""
-        k = len(streams)
-        ins = (C.c_char_p * k)(*streams)
-        sizes = (C.c_size_t * k)(*[len(s) for s in streams])
-        ps = (StreamParams * k)(*params)
-        ts = (QualityTarget * k)(*targets)
-        outs = (C.c_void_p * k)()
-        ns = (C.c_size_t * k)()
-        rs = (QualityResult * k)()
-        self._chk(self.L.rbt_transcode_gof_quality(self.h, k, ins, sizes, ps, ts, outs, ns, rs))
-        res = []
-        for i in range(k):
-            res.append(C.string_at(outs[i], ns[i]) if outs[i] else b"")
-            self.L.rbt_free(outs[i])
-        return res, [_result_dict(r) for r in rs]
+        return self._transcode(self.L.rbt_transcode_gof_quality, streams, params, targets, QualityTarget, QualityResult)
 
     def picture_sse(self, a, b, w, h, occ=None):
         """rbt_picture_sse: planar 4:2:0 pictures a, b ([n, w*h*3/2] uint16) and, or None, one occupancy plane per picture ([n, oh, ow] uint16) -> uint64 [n, 3, 3]:

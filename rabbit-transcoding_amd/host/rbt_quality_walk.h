@@ -1,13 +1,13 @@
-// Host half of a transcode to a PSNR floor (include/rbt.h, "transcoding to a PSNR floor"): PSNR and the floor's condition on the integer sums of csrc/rbt_quality.h, and the
-// walk over the distortions of trial encodes. Plain host code without a device call, so that tests/quality_check.cpp can run it under the sanitizers next to the kernel body.
+// Host half of a transcode to a PSNR floor (include/rbt.h, "transcoding to a PSNR floor"): PSNR and the floor's condition on the integer sums of csrc/rbt_quality.h, and what
+// makes the shared walk (rbt_qp_walk.h) the walk of a floor: a probe in front of it. Plain host code without a device call, so that tests/quality_check.cpp can run it under the sanitizers next to the kernel body.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <limits>
-#include <map>
 #include <vector>
 #include "../csrc/rbt_quality.h"
+#include "rbt_qp_walk.h"
 
 namespace rbt {
 // the sums of one stream: every picture's nine words added up, and the samples they were taken over
@@ -29,44 +29,18 @@ inline bool quality_meets(const QualitySums& s, int region, int32_t min_psnr_mdb
   return quality_psnr(sse, n, bit_depth) >= min_psnr_mdb / 1000.0;
 }
 
-// The walk of one entry with a floor over the trial encodes run so far. It is the definition restated: it looks at the sums of the QPs it names only, so the result does
-// not depend on what else a round happened to bring.
+// The floor of one entry. Its walk goes toward larger QPs while meets(q) holds on the sums of the trial at q. A probe at q0 - the entry's own QP, clamped to the range -
+// comes first and says where the walk starts: qs (w.start), one QP further per dB the probe is above the floor, q0 itself when the probe came back exactly.
 struct QualityTried { std::vector<uint8_t> stream; QualitySums sums; };
-struct QualityWalk {
-  int q = 0, entry = 0;                        // position in the pipeline's group, index of the entry in the call
-  int32_t floor_mdb = 0; int region = 0, bit_depth = 8, lo = 0, hi = 51, q0 = 0;
-  std::map<int, QualityTried> tried;           // QP -> what it gave
-  bool started = false, settled = false; int qs = 0, qstar = 0, met = 0;
-};
-// true: settled (qstar, met); false: the walk needs the sums of QP `need` next and is going in direction dir (0: the probe at q0, or the start at qs)
-inline bool quality_walk_step(QualityWalk& w, int& need, int& dir) {
-  auto known = [&](int q) { return w.tried.count(q) != 0; };
-  auto meets = [&](int q) { return quality_meets(w.tried[q].sums, w.region, w.floor_mdb, w.bit_depth); };
-  if (!known(w.q0)) { need = w.q0; dir = 0; return false; }
-  if (!w.started) {
-    const double p = quality_region_psnr(w.tried[w.q0].sums, w.region, w.bit_depth);
-    w.qs = std::isinf(p) ? w.q0 : std::min(w.hi, std::max(w.lo, w.q0 + (int)(p - w.floor_mdb / 1000.0)));
-    w.started = true;
-  }
-  if (!known(w.qs)) { need = w.qs; dir = 0; return false; }
-  int q = w.qs;
-  if (meets(q)) {
-    while (q < w.hi) { if (!known(q + 1)) { need = q + 1; dir = 1; return false; } if (meets(q + 1)) q++; else break; }
-    w.met = 1;
-  } else {
-    while (q > w.lo && !meets(q)) { q--; if (!known(q)) { need = q; dir = -1; return false; } }
-    w.met = meets(q);
-  }
-  w.qstar = q; w.settled = true;
-  return true;
+struct QualityGoal { int32_t floor_mdb = 0; int region = 0, bit_depth = 8, q0 = 0; bool probed = false; };
+template <class Trial> inline void quality_seed(QpWalk<Trial>& w, QualityGoal& g, int qp) { w.toward = 1; g.q0 = std::min(w.hi, std::max(w.lo, qp)); }
+// false: the probe has not been tried, a round has to bring q0 alone; true: w.start is known and qp_walk_step can look
+template <class Trial> inline bool quality_probe(QpWalk<Trial>& w, QualityGoal& g) {
+  const auto t = w.tried.find(g.q0);
+  if (g.probed || t == w.tried.end()) return g.probed;
+  const double p = quality_region_psnr(t->second.sums, g.region, g.bit_depth);
+  w.start = std::isinf(p) ? g.q0 : std::min(w.hi, std::max(w.lo, g.q0 + (int)(p - g.floor_mdb / 1000.0)));
+  return g.probed = true;
 }
-// what a round encodes for a walk: q0 alone first, then the three QPs around qs, then two at a time where the walk is going; a QP already tried is never encoded again
-// (one wasted encode at most per round: n_encodes <= |q* - qs| + 5)
-inline void quality_round_qps(const QualityWalk& w, int need, int dir, std::vector<int>& qps) {
-  qps.clear();
-  auto want = [&](int q) { if (q >= w.lo && q <= w.hi && !w.tried.count(q)) qps.push_back(q); };
-  if (dir == 0 && !w.started) want(need);
-  else if (dir == 0) { for (int q = need - 1; q <= need + 1; q++) want(q); }
-  else { want(need); want(need + dir); }
-}
+template <class Trial> inline auto quality_holds(const QpWalk<Trial>& w, const QualityGoal& g) { return [&w, &g](int q) { return quality_meets(w.tried.find(q)->second.sums, g.region, g.floor_mdb, g.bit_depth); }; }
 }  // namespace rbt

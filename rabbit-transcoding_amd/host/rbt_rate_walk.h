@@ -1,11 +1,11 @@
-// Host half of a rate-targeted transcode (include/rbt.h, "transcoding to a byte budget"): the estimate from the census and the walk over the sizes of trial encodes. Plain
-// host code without a device call, so that tests/rate_check.cpp can run it under the sanitizers next to the census body.
+// Host half of a rate-targeted transcode (include/rbt.h, "transcoding to a byte budget"): the estimate from the census, and what makes the shared walk (rbt_qp_walk.h) the
+// walk of a budget. Plain host code without a device call, so that tests/rate_check.cpp can run it under the sanitizers next to the census body.
 #pragma once
 #include <algorithm>
 #include <cstdint>
-#include <map>
 #include <vector>
 #include "../csrc/rbt_rate.h"
+#include "rbt_qp_walk.h"
 
 namespace rbt {
 // Output picture k of a geometry / attribute stream is an I picture coded at max(0, q - 3) for even k and a P picture coded at q for odd k (RBT-E1, gop 2); per picture the
@@ -23,34 +23,14 @@ inline void rate_table(const uint32_t* hist, const uint64_t* picture_bytes, int 
   }
 }
 
-// The walk of one targeted entry over the sizes of the trial encodes run so far. It is the definition restated: it looks at s(q) and E(q) only, so the result does not
-// depend on which sizes a round happened to bring beyond the one it asked for.
-struct RateWalk {
-  int q = 0, entry = 0;                        // position in the pipeline's group, index of the entry in the call
-  uint64_t T = 0, e_qe = 0; int lo = 0, hi = 51, qe = 0;
-  std::map<int, std::vector<uint8_t>> tried;   // QP -> the stream it gave
-  bool settled = false; int qstar = 0, met = 0;
-};
-// true: settled (qstar, met); false: the walk needs s(need) next and is going in direction dir (0: it has not started)
-inline bool rate_walk_step(RateWalk& w, int& need, int& dir) {
-  auto known = [&](int q) { return w.tried.count(q) != 0; };
-  auto size_at = [&](int q) { return (uint64_t)w.tried[q].size(); };
-  if (!known(w.qe)) { need = w.qe; dir = 0; return false; }
-  int q = w.qe;
-  if (size_at(q) <= w.T) {
-    while (q > w.lo) { if (!known(q - 1)) { need = q - 1; dir = -1; return false; } if (size_at(q - 1) <= w.T) q--; else break; }
-    w.met = 1;
-  } else {
-    while (q < w.hi && size_at(q) > w.T) { q++; if (!known(q)) { need = q; dir = 1; return false; } }
-    w.met = size_at(q) <= w.T;
-  }
-  w.qstar = q; w.settled = true;
-  return true;
+// The budget of one targeted entry. Its walk goes toward smaller QPs while s(q) <= T, s(q) being the size of the stream the trial at q gave (Trial::stream), and starts
+// at qe (w.start): the smallest QP of the range whose estimate fits the budget, the end of the range if none does; e_qe = E(qe)
+struct RateGoal { uint64_t T = 0, e_qe = 0; };
+struct RateTrial { std::vector<uint8_t> stream; };
+template <class Trial> inline void rate_seed(QpWalk<Trial>& w, RateGoal& g, const uint64_t estimate[52]) {
+  w.toward = -1; w.start = w.hi;
+  for (int q = w.lo; q <= w.hi; q++) if (estimate[q] <= g.T) { w.start = q; break; }
+  g.e_qe = estimate[w.start];
 }
-// what a round encodes for a walk: the three QPs around the estimate first, then two at a time where the walk is going (one wasted encode at most per round: n_encodes <= |q* - qe| + 4)
-inline void rate_round_qps(const RateWalk& w, int need, int dir, std::vector<int>& qps) {
-  qps.clear();
-  if (dir == 0) { for (int q = w.qe - 1; q <= w.qe + 1; q++) if (q >= w.lo && q <= w.hi) qps.push_back(q); }
-  else for (int q = need, k = 0; k < 2 && q >= w.lo && q <= w.hi; q += dir, k++) qps.push_back(q);
-}
+template <class Trial> inline auto rate_fits(const QpWalk<Trial>& w, const RateGoal& g) { return [&w, &g](int q) { return (uint64_t)w.tried.find(q)->second.stream.size() <= g.T; }; }
 }  // namespace rbt

@@ -427,23 +427,17 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
 // One transcode call in flight. rbt_transcode_gof = submit + wait; rbt_submit_gof / rbt_wait_gof expose the two halves so that
 // a caller can keep two GOFs in flight (job slots use disjoint HIP streams): the next GOF's entropy decoding then runs
 // underneath the previous GOF's reconstruction and re-encode.
-// Rate targets: what a pipeline with a targeted entry keeps between the rounds of its trial encodes (rate_run_pipeline, rate_launch_round, rate_finish_round)
-struct RateCand { int q, qp, walk; };          // entry q of the group at qp; walk: index of its RateWalk, -1 for a constant-QP entry of the pipeline
-struct RatePipe {
-  std::vector<RateWalk> walks; std::vector<int> n_enc;
-  std::vector<RateCand> cands;                 // the round to run (eb == nullptr) or running
-  std::unique_ptr<EncodeBatch> eb;             // the round in flight on the pipeline's stream
-  std::vector<std::vector<uint8_t>> o1;        // the pipeline's streams in group order, as they settle
-  bool done = false;
-};
+// Targets - a byte budget or a PSNR floor per entry -: what a pipeline with such an entry keeps between the rounds of its trial encodes (run_rounds, launch_round, finish_round)
+struct RoundCand { int q, qp, walk; };         // entry q of the group at qp; walk: index of its walk, -1 for a constant-QP entry of the pipeline
+struct TargetWalk : QpWalk<QualityTried> { RateGoal budget; QualityGoal floor; };   // toward < 0: a budget, toward > 0: a floor
 // Quality floors: the occupancy source of an entry (include/rbt.h, "transcoding to a PSNR floor", rule 3), kept in the job because the pipelines that use it are encoded in
 // the wait half: the pooled luma planes of the occupancy stream, and for occupancy_rd the per-4x4-unit maps made of them (both live in GofJob::pooled until the job goes)
 struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
-struct QualityPipe {
-  std::vector<QualityWalk> walks; std::vector<int> n_enc;
-  std::vector<RateCand> cands;                 // the round to run or running
-  std::unique_ptr<EncodeBatch> eb; std::unique_ptr<SseSet> sse;   // the round in flight on the pipeline's stream
-  std::vector<std::vector<uint8_t>> o1; std::vector<QualitySums> sums;   // the pipeline's streams in group order, as they settle, and their sums
+struct RoundPipe {
+  std::vector<TargetWalk> walks; std::vector<int> n_enc;
+  std::vector<RoundCand> cands;                // the round to run (eb == nullptr) or running
+  std::unique_ptr<EncodeBatch> eb; std::unique_ptr<SseSet> sse;   // the round in flight on the pipeline's stream; sse: a round of a job with floors carries distortion sums
+  std::vector<std::vector<uint8_t>> o1; std::vector<QualitySums> sums;   // the pipeline's streams in group order, as they settle, and (floors) their sums
   bool done = false;
 };
 struct GofJob {
@@ -461,12 +455,12 @@ struct GofJob {
   std::vector<std::vector<uint8_t>> passthrough;   // transcodeData (PCCTranscoder.cpp:150): occupancy is only transcoded when occupancyPrecision == 4; else the stream stays as it is
   std::vector<char> is_pass;
   std::vector<std::vector<int>> dec_of;            // per pipeline: decode stream of each of its (encode) streams - identical inputs are decoded once
-  // rate targets (rbt_submit_gof_rate): a pipeline that holds a targeted entry is decoded and counted at submit and encoded in the wait half (rate_run_pipeline)
+  // rate targets (rbt_submit_gof_rate): a pipeline that holds a targeted entry is decoded and counted at submit and encoded in the wait half (run_rounds)
   std::vector<rbt_rate_target> targets; std::vector<char> rate_pipe; std::vector<rbt_rate_result> results; size_t rate_bytes = 0;   // rate_bytes: arenas of the first round of trial encodes
-  std::vector<RatePipe> rate;                                // per pipeline
-  // quality floors (rbt_submit_gof_quality): every pipeline with a geometry / attribute entry is decoded at submit and encoded in the wait half (quality_run_pipeline); it
-  // is marked in rate_pipe like a pipeline with a rate target, which keeps it unchained
-  std::vector<rbt_quality_target> qtargets; std::vector<QualityOcc> qocc; std::vector<QualityPipe> qual; std::vector<rbt_quality_result> qresults; bool refused = false;
+  std::vector<RoundPipe> pipes;                              // per pipeline
+  // quality floors (rbt_submit_gof_quality): every pipeline with a geometry / attribute entry is decoded at submit and encoded in the wait half (run_rounds); it is marked
+  // in rate_pipe like a pipeline with a rate target, which keeps it unchained
+  std::vector<rbt_quality_target> qtargets; std::vector<QualityOcc> qocc; std::vector<rbt_quality_result> qresults; bool refused = false;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   ~GofJob() { for (void* q : pooled) rbtk::dev_free(q); }
 };
@@ -487,6 +481,7 @@ size_t gof_memory(const GofJob* j) { return j ? j->dev_bytes + j->rate_bytes : 0
 bool gof_is_quality(const GofJob* j) { return j && !j->qtargets.empty(); }
 int gof_refused(const GofJob* j, std::string& err) { if (!j || !j->refused) return 0; err = j->err; return j->rc; }
 static bool has_target(const GofJob& j, int i) { return !j.targets.empty() && j.targets[i].target_bytes != 0; }
+static bool has_floor(const GofJob& j, int i) { return !j.qtargets.empty() && j.qtargets[i].min_psnr_mdb != 0; }
 
 // What lives only while a job is submitted
 struct SubmitPlan {
@@ -532,7 +527,7 @@ static int plan_pipelines(GofJob& j, SubmitPlan& s, int depth) {
   std::stable_sort(j.order.begin(), j.order.end(), [&](int a, int b) { return bytes_of(a) > bytes_of(b); });
   bind_streams(j, depth);
   recon_set_depth(depth);
-  j.rate_pipe.assign(ng, 0);
+  j.rate_pipe.assign(ng, 0); j.pipes.resize(ng);
   const bool quality = !j.qtargets.empty();
   for (int g = 0; g < ng; g++) for (int i : groups[g]) j.rate_pipe[g] |= (char)(has_target(j, i) || (quality && p[i].video_type != RBT_VIDEO_OCCUPANCY));
   s.pool_jobs.resize(ng); s.meas_of.assign(n, -1); s.occ_of.assign(n, -1); s.occ_src.resize(n); s.feeds_any.assign(ng, 0); s.consumes.assign(ng, 0);
@@ -577,7 +572,7 @@ static int build_decoders(GofJob& j, SubmitPlan& s) {
   return 0;
 }
 
-static int rate_measure(GofJob& j, int gi);
+static int rate_prepare(GofJob& j, int gi);
 static int quality_prepare(GofJob& j, SubmitPlan& s, int gi);
 // Encoder batches: the pipelines whose occupancy streams others are coded with first (their pooled planes are what the maps are made of), then the rest
 static int build_encoders(GofJob& j, SubmitPlan& s) {
@@ -585,7 +580,7 @@ static int build_encoders(GofJob& j, SubmitPlan& s) {
     const int gi = j.order[k]; const std::vector<int>& gs = j.groups[gi]; EncodeBatch& eb = j.eb[gi]; rbtk::set_stream(job_stream(j, gi));
     bool feeds = false; for (int i : gs) for (int c = 0; c < j.n; c++) feeds |= s.occ_of[c] == i || s.meas_of[c] == i;
     if (feeds != (pass == 0)) continue;
-    if (j.rate_pipe[gi]) { if (int rc = j.qtargets.empty() ? rate_measure(j, gi) : quality_prepare(j, s, gi)) return rc; continue; }      // stays unchained: decoder and census now, encoders in the wait half
+    if (j.rate_pipe[gi]) { if (int rc = j.qtargets.empty() ? rate_prepare(j, gi) : quality_prepare(j, s, gi)) return rc; continue; }      // stays unchained: decoder and census now, encoders in the wait half
     for (size_t q = 0; q < gs.size(); q++) {
       const int i = gs[q], io = s.occ_of[i];
       if (int rc = setup_encode(j.db[gi], j.dec_of[gi][q], (int)q, s.p[i], eb, j.pooled, j.err, &s.pool_jobs[gi], io >= 0 ? &s.occ_src[io] : nullptr, io, &s.occ_jobs)) return rc;
@@ -603,71 +598,140 @@ static int build_encoders(GofJob& j, SubmitPlan& s) {
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ rate targets (include/rbt.h, "transcoding to a byte budget")
-static int rate_fill_batch(GofJob& j, int gi, const std::vector<RateCand>& cands, EncodeBatch& eb) {
+// ------------------------------------------------------------------------------------------------ targets: byte budgets (include/rbt.h, "transcoding to a byte budget")
+// and PSNR floors ("transcoding to a PSNR floor"). Both are one walk with a direction (rbt_qp_walk.h) over rounds of trial encodes; they differ in how a walk is seeded
+// (seed_budgets, seed_floors), in whether a round carries distortion sums, and in how the public result is filled (fill_results).
+// the candidates of a round as an encode batch; in a job with floors the entries coded with occupancy_rd get the maps the occupancy pipeline made at submit
+static int round_fill_batch(GofJob& j, int gi, const std::vector<RoundCand>& cands, EncodeBatch& eb) {
   for (size_t e = 0; e < cands.size(); e++) {
     rbt_stream_params pp = j.params[j.groups[gi][cands[e].q]]; pp.qp = cands[e].qp;
     if (int rc = setup_encode(j.db[gi], j.dec_of[gi][cands[e].q], (int)e, pp, eb, j.pooled, j.err)) return rc;
   }
+  for (size_t e = 0; e < cands.size() && !j.qocc.empty(); e++) {
+    const QualityOcc& o = j.qocc[j.groups[gi][cands[e].q]]; EncStreamDesc& d = eb.desc[e];
+    if (!o.maps || d.lossless) continue;
+    d.occ4.resize(d.n_frames); d.occ4_w = o.w4; d.occ4_h = o.h4;
+    for (int k = 0; k < d.n_frames; k++) d.occ4[k] = o.maps + (size_t)((size_t)k * o.n / d.n_frames) * o.w4 * o.h4;
+  }
   return 0;
 }
-static void rate_first_round(const GofJob& j, int gi, std::vector<RateCand>& cands, const std::vector<RateWalk>* walks) {
-  const std::vector<int>& gs = j.groups[gi]; std::vector<int> qps; int nw = 0;
-  for (size_t q = 0; q < gs.size(); q++) {
-    if (!has_target(j, gs[q])) { cands.push_back(RateCand{(int)q, j.params[gs[q]].qp, -1}); continue; }
-    RateWalk w0; if (!walks) { const rbt_rate_target& t = j.targets[gs[q]]; w0.lo = t.qp_min; w0.hi = t.qp_max ? t.qp_max : 51; w0.qe = std::min(w0.hi, w0.lo + 1); }   // (measuring: three QPs in the lowest band)
-    rate_round_qps(walks ? (*walks)[nw] : w0, 0, 0, qps);
-    for (int qp : qps) cands.push_back(RateCand{(int)q, qp, nw});
-    nw++;
+template <class Target> static TargetWalk new_walk(size_t q, int entry, const Target& t) { TargetWalk w; w.q = (int)q; w.entry = entry; w.lo = t.qp_min; w.hi = t.qp_max ? t.qp_max : 51; return w; }
+// A budget's walk starts at the estimate: the histograms of the census come back and rate_table turns them and the input's own bytes into E(q). At submit (census false)
+// there is no estimate yet: the measurement takes the three QPs of the lowest band, qe = min(hi, lo + 1)
+static int seed_budgets(GofJob& j, int gi, RoundPipe& r, bool census) {
+  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
+  if (census && db.census.fetch()) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  for (size_t q = 0; q < gs.size(); q++) if (has_target(j, gs[q])) {
+    const rbt_rate_target& t = j.targets[gs[q]];
+    TargetWalk w = new_walk(q, gs[q], t); w.budget.T = t.target_bytes; w.start = std::min(w.hi, w.lo + 1);
+    if (census) {
+      const int ds = j.dec_of[gi][q], first = db.stream_first[ds], cnt = db.stream_count[ds];
+      std::vector<uint64_t> bytes(cnt); for (int i = 0; i < cnt; i++) bytes[i] = db.info[first + i].vcl_bytes;
+      uint64_t E[52]; rate_table(db.census.hist.data() + (size_t)db.census_first[ds] * RBT_RATE_HIST_WORDS, bytes.data(), cnt, E);
+      rate_seed(w, w.budget, E);
+    }
+    r.walks.push_back(std::move(w));
+  }
+  return 0;
+}
+// A floor's walk starts with a probe at the entry's own QP
+static int entry_bit_depth(const GofJob& j, int gi, size_t q) { const DecodeBatch& db = j.db[gi]; return db.frames[db.stream_first[j.dec_of[gi][q]]].cfg.bit_depth; }
+static void seed_floors(GofJob& j, int gi, RoundPipe& r) {
+  const std::vector<int>& gs = j.groups[gi];
+  for (size_t q = 0; q < gs.size(); q++) if (has_floor(j, gs[q])) {
+    const rbt_quality_target& t = j.qtargets[gs[q]];
+    TargetWalk w = new_walk(q, gs[q], t); w.floor.floor_mdb = t.min_psnr_mdb; w.floor.region = t.region; w.floor.bit_depth = entry_bit_depth(j, gi, q);
+    quality_seed(w, w.floor, j.params[gs[q]].qp);
+    r.walks.push_back(std::move(w));
   }
 }
-// at submit: what the first round of trial encodes will take (rbt_job_memory), measured on the layout without allocating; the estimate is not known yet, the arenas do not
-// depend on it but for the slice buffers' QP bands
-static int rate_measure(GofJob& j, int gi) {
+// true: settled; false: the walk needs the trial at `need` next (alone: a probe, the round brings nothing else for it)
+static bool walk_step(TargetWalk& w, int& need, int& dir, bool& alone) {
+  alone = w.toward > 0 && !quality_probe(w, w.floor);
+  if (alone) { need = w.floor.q0; dir = 0; return false; }
+  return w.toward > 0 ? qp_walk_step(w, quality_holds(w, w.floor), need, dir) : qp_walk_step(w, rate_fits(w, w.budget), need, dir);
+}
+// The round to run next, in group order: what every unsettled walk asks for (qp_round) and, in the first round, the pipeline's entries without a target at their own QP
+static void name_round(const GofJob& j, int gi, RoundPipe& r, bool first) {
+  const std::vector<int>& gs = j.groups[gi]; std::vector<int> qps; size_t k = 0;
+  r.cands.clear();
+  for (size_t q = 0; q < gs.size(); q++) {
+    if (k == r.walks.size() || r.walks[k].q != (int)q) { if (first) r.cands.push_back(RoundCand{(int)q, j.params[gs[q]].qp, -1}); continue; }
+    TargetWalk& w = r.walks[k]; int need = 0, dir = 0; bool alone = false;
+    if (!w.settled && !walk_step(w, need, dir, alone)) { qp_round(w, need, dir, alone, qps); for (int qp : qps) r.cands.push_back(RoundCand{w.q, qp, (int)k}); }
+    k++;
+  }
+}
+// at submit: what the first round of trial encodes will take (rbt_job_memory), measured on the layout without allocating
+static int measure_round(GofJob& j, int gi, const std::vector<RoundCand>& cands) {
   DecodeBatch& db = j.db[gi];
-  for (int i : j.groups[gi]) if (j.params[i].video_type == RBT_VIDEO_OCCUPANCY) return 0;      // (its pooled planes would be allocated: left uncounted)
-  std::vector<RateCand> cands; rate_first_round(j, gi, cands, nullptr);
   const std::vector<char> taken = db.alias_taken;
-  EncodeBatch eb; int rc = rate_fill_batch(j, gi, cands, eb);
+  EncodeBatch eb; int rc = round_fill_batch(j, gi, cands, eb);
   if (!rc && (rc = encode_plan(eb)) != 0) j.err = eb.err;
   db.alias_taken = taken;
   if (!rc) j.rate_bytes += eb.arena_size;
   return rc;
 }
-// Rounds. A round of a pipeline is one encode batch of candidates on the pipeline's stream: rate_launch_round builds and enqueues it, rate_finish_round waits for it, packs
-// the streams, lets the walks look at the sizes and names the next round.
-static int rate_launch_round(GofJob& j, int gi) {
-  RatePipe& r = j.rate[gi];
+// a pipeline with a budget at submit: the estimate is not known yet, the arenas do not depend on it but for the slice buffers' QP bands
+static int rate_prepare(GofJob& j, int gi) {
+  for (int i : j.groups[gi]) if (j.params[i].video_type == RBT_VIDEO_OCCUPANCY) return 0;      // (its pooled planes would be allocated: left uncounted)
+  RoundPipe r; seed_budgets(j, gi, r, false); name_round(j, gi, r, true);
+  return measure_round(j, gi, r.cands);
+}
+// Rounds. A round of a pipeline is one encode batch of candidates on the pipeline's stream: launch_round builds and enqueues it, finish_round waits for it, packs the
+// streams, lets the walks look at what came back and names the next round. In a job with floors the round carries, behind its last filter, the sums of every candidate
+// picture against the decoded picture it was coded from - EncStreamDesc::src, which no encoder writes to (arena sharing hands out the decoded pictures' dead buffers only)
+static int round_sums_setup(GofJob& j, int gi) {
+  RoundPipe& r = j.pipes[gi]; EncodeBatch& eb = *r.eb;
+  r.sse.reset(new SseSet()); r.sse->ext = eb.d_sums;
+  if (rbtk::dev_memset(eb.d_sums, 0, eb.n_sums * 8)) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  for (size_t e = 0; e < r.cands.size(); e++) {
+    const EncStreamDesc& d = eb.desc[e]; const QualityOcc& o = j.qocc[j.groups[gi][r.cands[e].q]]; const int st = d.src_stride ? d.src_stride : d.w;
+    for (int k = 0; k < d.n_frames; k++) {
+      const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k];
+      RbtSsePic P; memset(&P, 0, sizeof(P));
+      for (int c = 0; c < 3; c++) { const int sh = c ? 1 : 0; P.a[c] = d.src[c][k] + (size_t)(d.src_y0 >> sh) * (size_t)(st >> sh) + (d.src_x0 >> sh); P.b[c] = f.out[c]; }
+      P.w = d.w; P.h = d.h; P.a_stride = st; P.b_stride = f.cfg.w;
+      if (o.occ) { P.occ = o.occ + o.in_step * (size_t)((size_t)k * o.n / d.n_frames); P.ow = o.ow; P.scale = d.w / o.ow; }
+      r.sse->add(P);
+    }
+  }
+  if (int rc = r.sse->upload()) { j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
+  return 0;
+}
+static int launch_round(GofJob& j, int gi) {
+  RoundPipe& r = j.pipes[gi]; const bool sums = !j.qtargets.empty();
   if (r.cands.empty()) { r.done = true; return 0; }
   rbtk::set_stream(job_stream(j, gi));
   r.eb.reset(new EncodeBatch()); EncodeBatch& eb = *r.eb;
-  int rc = rate_fill_batch(j, gi, r.cands, eb);
-  if (!rc && ((rc = encode_build(eb)) != 0 || (rc = encode_upload_lists(eb)) != 0)) j.err = eb.err;
+  int rc = round_fill_batch(j, gi, r.cands, eb);
+  if (sums) for (const EncStreamDesc& d : eb.desc) eb.n_sums += (size_t)d.n_frames * RBT_SSE_WORDS;
+  if (!rc && (rc = encode_build(eb)) != 0) j.err = eb.err;
+  if (!rc && sums) rc = round_sums_setup(j, gi);
+  if (!rc && (rc = encode_upload_lists(eb)) != 0) j.err = eb.err;
   if (rc) return rc;
   encode_launch_intra(eb); encode_launch_entropy_intra(eb); encode_launch_inter(eb);
   if (!eb.hash.empty()) eb.hash.launch();
+  if (sums) r.sse->launch();
   encode_launch_entropy_rest(eb);
   return 0;
 }
-static int rate_finish_round(GofJob& j, int gi) {
-  RatePipe& r = j.rate[gi]; std::vector<std::vector<uint8_t>> outs;
+static int finish_round(GofJob& j, int gi) {
+  RoundPipe& r = j.pipes[gi]; std::vector<std::vector<uint8_t>> outs;
   rbtk::set_stream(job_stream(j, gi));
   if (int rc = encode_finish(*r.eb, outs, j.st)) { j.err = r.eb->err; return rc; }
-  r.eb.reset();
+  size_t at = 0;                                                    // (the words came back with the slice sizes)
   for (size_t e = 0; e < r.cands.size(); e++) {
-    if (r.cands[e].walk < 0) r.o1[r.cands[e].q].swap(outs[e]);
-    else { r.walks[r.cands[e].walk].tried[r.cands[e].qp].swap(outs[e]); r.n_enc[r.cands[e].walk]++; }
+    const EncStreamDesc& d = r.eb->desc[e]; const RoundCand& c = r.cands[e]; QualitySums sums;
+    for (int k = 0; r.sse && k < d.n_frames; k++, at++) quality_add_picture(sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
+    if (c.walk < 0) { r.o1[c.q].swap(outs[e]); r.sums[c.q] = sums; }
+    else { QualityTried& t = r.walks[c.walk].tried[c.qp]; t.stream.swap(outs[e]); t.sums = sums; r.n_enc[c.walk]++; }
   }
-  r.cands.clear(); std::vector<int> qps;
-  for (size_t k = 0; k < r.walks.size(); k++) {
-    int need = 0, dir = 0;
-    if (r.walks[k].settled || rate_walk_step(r.walks[k], need, dir)) continue;
-    rate_round_qps(r.walks[k], need, dir, qps);
-    for (int qp : qps) r.cands.push_back(RateCand{r.walks[k].q, qp, (int)k});
-  }
+  r.eb.reset(); r.sse.reset();
+  name_round(j, gi, r, false);
   return 0;
 }
-// a decoded pipeline's checks, shared by the constant-QP path and rate_run_pipeline: error words and coverage, timers, the input's picture hashes (verify_md5)
+// a decoded pipeline's checks, shared by the constant-QP path and run_rounds: error words and coverage, timers, the input's picture hashes (verify_md5)
 static int pipeline_decoded(GofJob& j, int gi) {
   DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
   int rc = decode_finish(db);
@@ -684,36 +748,44 @@ static int pipeline_decoded(GofJob& j, int gi) {
   }
   return 0;
 }
-// A pipeline with a target, in the wait half: its decoder is collected, the histograms come back, the estimates are formed and the rounds run, one after the other, until
-// every walk has settled. (Measured and not adopted, DESIGN.md 12: the rounds of a job's pipelines side by side, and the first rounds of the other jobs in flight enqueued
-// ahead of their turn - both were slower than one pipeline's rounds at a time.)
-static int rate_run_pipeline(GofJob& j, int gi) {
-  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
-  j.rate.resize(j.ng); j.results.resize(j.n); RatePipe& r = j.rate[gi];
-  if (int rc = pipeline_decoded(j, gi)) return rc;
-  if (db.census.fetch()) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
-  for (size_t q = 0; q < gs.size(); q++) if (has_target(j, gs[q])) {
-    const rbt_rate_target& t = j.targets[gs[q]]; const int ds = j.dec_of[gi][q], first = db.stream_first[ds], cnt = db.stream_count[ds];
-    RateWalk w; w.q = (int)q; w.entry = gs[q]; w.T = t.target_bytes; w.lo = t.qp_min; w.hi = t.qp_max ? t.qp_max : 51;
-    std::vector<uint64_t> bytes(cnt); for (int i = 0; i < cnt; i++) bytes[i] = db.info[first + i].vcl_bytes;
-    uint64_t E[52]; rate_table(db.census.hist.data() + (size_t)db.census_first[ds] * RBT_RATE_HIST_WORDS, bytes.data(), cnt, E);
-    w.qe = w.hi; for (int qq = w.lo; qq <= w.hi; qq++) if (E[qq] <= w.T) { w.qe = qq; break; }
-    w.e_qe = E[w.qe];
-    r.walks.push_back(std::move(w));
+static void quality_fill_result(rbt_quality_result& o, int qp, int q0, int qs, int met, int n_enc, uint64_t bytes, const QualitySums& s, int bit_depth) {
+  memset(&o, 0, sizeof(o));
+  o.qp = qp; o.qp_probe = q0; o.qp_start = qs; o.met = met; o.n_encodes = n_enc; o.bytes = bytes;
+  for (int c = 0; c < 3; c++) {
+    o.sse[c] = s.sse[c]; o.samples[c] = s.samples[c]; o.sse_occ[c] = s.sse_occ[c]; o.samples_occ[c] = s.samples_occ[c];
+    o.psnr[c] = quality_psnr(s.sse[c], s.samples[c], bit_depth); o.psnr_occ[c] = quality_psnr(s.sse_occ[c], s.samples_occ[c], bit_depth);
   }
-  r.o1.assign(gs.size(), {}); r.n_enc.assign(r.walks.size(), 0);
-  rate_first_round(j, gi, r.cands, &r.walks);
-  for (;;) {
-    if (int rc = rate_launch_round(j, gi)) return rc;
-    if (r.done) break;
-    if (int rc = rate_finish_round(j, gi)) return rc;
-  }
+}
+// the public results of a pipeline whose walks have settled: a budget's (qe = the walk's start), or a floor's and the distortion of the entries without one
+static void fill_results(GofJob& j, int gi) {
+  RoundPipe& r = j.pipes[gi]; const std::vector<int>& gs = j.groups[gi];
+  if (j.qtargets.empty()) j.results.resize(j.n); else j.qresults.resize(j.n);
+  for (size_t q = 0; q < gs.size() && !j.qtargets.empty(); q++) if (!has_floor(j, gs[q])) { const int qp = j.params[gs[q]].qp; quality_fill_result(j.qresults[gs[q]], qp, qp, qp, 1, 1, r.o1[q].size(), r.sums[q], entry_bit_depth(j, gi, q)); }
   for (size_t k = 0; k < r.walks.size(); k++) {
-    RateWalk& w = r.walks[k];
-    if (!w.settled) { j.err = "internal: rate walk did not settle"; return RBT_ERR_PARAM; }
-    j.results[w.entry] = rbt_rate_result{w.qstar, w.qe, w.met, r.n_enc[k], (uint64_t)w.tried[w.qstar].size(), w.e_qe};
-    r.o1[w.q].swap(w.tried[w.qstar]);
+    const TargetWalk& w = r.walks[k]; const QualityTried& t = w.tried.find(w.qstar)->second;
+    if (w.toward < 0) j.results[w.entry] = rbt_rate_result{w.qstar, w.start, w.met, r.n_enc[k], (uint64_t)t.stream.size(), w.budget.e_qe};
+    else quality_fill_result(j.qresults[w.entry], w.qstar, w.floor.q0, w.start, w.met, r.n_enc[k], t.stream.size(), t.sums, w.floor.bit_depth);
   }
+}
+// A pipeline with targets, in the wait half: its decoder is collected, the walks are seeded and the rounds run, one after the other, until every walk has settled. In a
+// job with floors the occupancy pipelines have been collected by then (gof_wait), so the pooled planes and the maps the rounds read are complete. (Measured and not
+// adopted, DESIGN.md 12: the rounds of a job's pipelines side by side, and the first rounds of the other jobs in flight enqueued ahead of their turn - both were slower
+// than one pipeline's rounds at a time.)
+static int run_rounds(GofJob& j, int gi) {
+  RoundPipe& r = j.pipes[gi]; const size_t n = j.groups[gi].size();
+  if (int rc = pipeline_decoded(j, gi)) return rc;
+  if (!j.qtargets.empty()) seed_floors(j, gi, r);
+  else if (int rc = seed_budgets(j, gi, r, true)) return rc;
+  r.o1.assign(n, {}); r.sums.assign(n, QualitySums()); r.n_enc.assign(r.walks.size(), 0);
+  name_round(j, gi, r, true);
+  for (;;) {
+    if (int rc = launch_round(j, gi)) return rc;
+    if (r.done) break;
+    if (int rc = finish_round(j, gi)) return rc;
+  }
+  for (const TargetWalk& w : r.walks) if (!w.settled) { j.err = "internal: QP walk did not settle"; return RBT_ERR_PARAM; }
+  fill_results(j, gi);
+  for (TargetWalk& w : r.walks) r.o1[w.q].swap(w.tried[w.qstar].stream);
   return 0;
 }
 
@@ -735,18 +807,6 @@ void SseSet::launch() const { rbtk::launch_picture_sse((const RbtSsePic*)d, (int
 int SseSet::fetch() {
   words.assign(pics.size() * RBT_SSE_WORDS, 0);
   return !words.empty() && rbtk::d2h(words.data(), d + o_out, words.size() * 8) ? RBT_ERR_NO_DEVICE : 0;
-}
-static bool has_floor(const GofJob& j, int i) { return j.qtargets[i].min_psnr_mdb != 0; }
-// the candidates of a round as an encode batch; entries coded with occupancy_rd get the maps the occupancy pipeline made at submit
-static int quality_fill_batch(GofJob& j, int gi, const std::vector<RateCand>& cands, EncodeBatch& eb) {
-  if (int rc = rate_fill_batch(j, gi, cands, eb)) return rc;
-  for (size_t e = 0; e < cands.size(); e++) {
-    const QualityOcc& o = j.qocc[j.groups[gi][cands[e].q]]; EncStreamDesc& d = eb.desc[e];
-    if (!o.maps || d.lossless) continue;
-    d.occ4.resize(d.n_frames); d.occ4_w = o.w4; d.occ4_h = o.h4;
-    for (int k = 0; k < d.n_frames; k++) d.occ4[k] = o.maps + (size_t)((size_t)k * o.n / d.n_frames) * o.w4 * o.h4;
-  }
-  return 0;
 }
 // At submit, behind the encoder batches of the occupancy pipelines: the occupancy source of every entry of the pipeline (rule 3), the maps of occupancy_rd - allocated
 // here, made by the occupancy pipeline's launch_occ_units like those of a constant-QP job -, and what the first round will take (rbt_job_memory): one encode per entry
@@ -773,109 +833,9 @@ static int quality_prepare(GofJob& j, SubmitPlan& s, int gi) {
       j.err = "entry " + std::to_string(i) + ": RBT_QUALITY_OCCUPIED on an entry whose occupancy source does not fit it (picture count a multiple of the occupancy frames, one whole scale in both directions)";
       j.refused = true; return RBT_ERR_PARAM; }
   }
-  std::vector<RateCand> cands; for (size_t q = 0; q < gs.size(); q++) cands.push_back(RateCand{(int)q, j.params[gs[q]].qp, -1});
-  const std::vector<char> taken = db.alias_taken;
-  EncodeBatch eb; int rc = quality_fill_batch(j, gi, cands, eb);
-  if (!rc && (rc = encode_plan(eb)) != 0) j.err = eb.err;
-  db.alias_taken = taken;
-  if (!rc) j.rate_bytes += eb.arena_size;
-  return rc;
+  std::vector<RoundCand> cands; for (size_t q = 0; q < gs.size(); q++) cands.push_back(RoundCand{(int)q, j.params[gs[q]].qp, -1});
+  return measure_round(j, gi, cands);
 }
-// A round of a pipeline: one encode batch of candidates on the pipeline's stream, and behind its last filter the sums of every candidate picture against the decoded
-// picture it was coded from - EncStreamDesc::src, which no encoder writes to (arena sharing hands out the decoded pictures' dead buffers only)
-static int quality_launch_round(GofJob& j, int gi) {
-  QualityPipe& r = j.qual[gi];
-  if (r.cands.empty()) { r.done = true; return 0; }
-  rbtk::set_stream(job_stream(j, gi));
-  r.eb.reset(new EncodeBatch()); r.sse.reset(new SseSet()); EncodeBatch& eb = *r.eb;
-  int rc = quality_fill_batch(j, gi, r.cands, eb);
-  for (const EncStreamDesc& d : eb.desc) eb.n_sums += (size_t)d.n_frames * RBT_SSE_WORDS;
-  if (!rc && (rc = encode_build(eb)) != 0) j.err = eb.err;
-  if (rc) return rc;
-  r.sse->ext = eb.d_sums;
-  if (rbtk::dev_memset(eb.d_sums, 0, eb.n_sums * 8)) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
-  for (size_t e = 0; e < r.cands.size(); e++) {
-    const EncStreamDesc& d = eb.desc[e]; const QualityOcc& o = j.qocc[j.groups[gi][r.cands[e].q]]; const int st = d.src_stride ? d.src_stride : d.w;
-    for (int k = 0; k < d.n_frames; k++) {
-      const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k];
-      RbtSsePic P; memset(&P, 0, sizeof(P));
-      for (int c = 0; c < 3; c++) { const int sh = c ? 1 : 0; P.a[c] = d.src[c][k] + (size_t)(d.src_y0 >> sh) * (size_t)(st >> sh) + (d.src_x0 >> sh); P.b[c] = f.out[c]; }
-      P.w = d.w; P.h = d.h; P.a_stride = st; P.b_stride = f.cfg.w;
-      if (o.occ) { P.occ = o.occ + o.in_step * (size_t)((size_t)k * o.n / d.n_frames); P.ow = o.ow; P.scale = d.w / o.ow; }
-      r.sse->add(P);
-    }
-  }
-  if ((rc = r.sse->upload()) != 0) { j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
-  if ((rc = encode_upload_lists(eb)) != 0) { j.err = eb.err; return rc; }
-  encode_launch_intra(eb); encode_launch_entropy_intra(eb); encode_launch_inter(eb);
-  if (!eb.hash.empty()) eb.hash.launch();
-  r.sse->launch();
-  encode_launch_entropy_rest(eb);
-  return 0;
-}
-static int quality_finish_round(GofJob& j, int gi) {
-  QualityPipe& r = j.qual[gi]; std::vector<std::vector<uint8_t>> outs;
-  rbtk::set_stream(job_stream(j, gi));
-  if (int rc = encode_finish(*r.eb, outs, j.st)) { j.err = r.eb->err; return rc; }
-  size_t at = 0;                                                    // (the words came back with the slice sizes)
-  for (size_t e = 0; e < r.cands.size(); e++) {
-    const EncStreamDesc& d = r.eb->desc[e]; QualitySums sums;
-    for (int k = 0; k < d.n_frames; k++, at++) quality_add_picture(sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
-    if (r.cands[e].walk < 0) { r.o1[r.cands[e].q].swap(outs[e]); r.sums[r.cands[e].q] = sums; }
-    else { QualityTried& t = r.walks[r.cands[e].walk].tried[r.cands[e].qp]; t.stream.swap(outs[e]); t.sums = sums; r.n_enc[r.cands[e].walk]++; }
-  }
-  r.eb.reset(); r.sse.reset();
-  r.cands.clear(); std::vector<int> qps;
-  for (size_t k = 0; k < r.walks.size(); k++) {
-    int need = 0, dir = 0;
-    if (r.walks[k].settled || quality_walk_step(r.walks[k], need, dir)) continue;
-    quality_round_qps(r.walks[k], need, dir, qps);
-    for (int qp : qps) r.cands.push_back(RateCand{r.walks[k].q, qp, (int)k});
-  }
-  return 0;
-}
-static void quality_fill_result(rbt_quality_result& o, int qp, int q0, int qs, int met, int n_enc, uint64_t bytes, const QualitySums& s, int bit_depth) {
-  memset(&o, 0, sizeof(o));
-  o.qp = qp; o.qp_probe = q0; o.qp_start = qs; o.met = met; o.n_encodes = n_enc; o.bytes = bytes;
-  for (int c = 0; c < 3; c++) {
-    o.sse[c] = s.sse[c]; o.samples[c] = s.samples[c]; o.sse_occ[c] = s.sse_occ[c]; o.samples_occ[c] = s.samples_occ[c];
-    o.psnr[c] = quality_psnr(s.sse[c], s.samples[c], bit_depth); o.psnr_occ[c] = quality_psnr(s.sse_occ[c], s.samples_occ[c], bit_depth);
-  }
-}
-// A geometry / attribute pipeline of a job with floors, in the wait half: its decoder is collected and its rounds run, one after the other, until every walk has settled.
-// The occupancy pipelines of the job have been collected by then (gof_wait), so the pooled planes and the maps the rounds read are complete.
-static int quality_run_pipeline(GofJob& j, int gi) {
-  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
-  j.qual.resize(j.ng); j.qresults.resize(j.n); QualityPipe& r = j.qual[gi];
-  if (int rc = pipeline_decoded(j, gi)) return rc;
-  r.o1.assign(gs.size(), {}); r.sums.assign(gs.size(), QualitySums());
-  std::vector<int> bd(gs.size(), 8);
-  for (size_t q = 0; q < gs.size(); q++) {
-    const int ds = j.dec_of[gi][q]; bd[q] = db.frames[db.stream_first[ds]].cfg.bit_depth;
-    if (!has_floor(j, gs[q])) { r.cands.push_back(RateCand{(int)q, j.params[gs[q]].qp, -1}); continue; }
-    const rbt_quality_target& t = j.qtargets[gs[q]];
-    QualityWalk w; w.q = (int)q; w.entry = gs[q]; w.floor_mdb = t.min_psnr_mdb; w.region = t.region; w.bit_depth = bd[q]; w.lo = t.qp_min; w.hi = t.qp_max ? t.qp_max : 51;
-    w.q0 = std::min(w.hi, std::max(w.lo, j.params[gs[q]].qp));
-    r.cands.push_back(RateCand{(int)q, w.q0, (int)r.walks.size()});
-    r.walks.push_back(std::move(w));
-  }
-  r.n_enc.assign(r.walks.size(), 0);
-  for (;;) {
-    if (int rc = quality_launch_round(j, gi)) return rc;
-    if (r.done) break;
-    if (int rc = quality_finish_round(j, gi)) return rc;
-  }
-  for (size_t q = 0; q < gs.size(); q++) if (!has_floor(j, gs[q])) { const int qp = j.params[gs[q]].qp; quality_fill_result(j.qresults[gs[q]], qp, qp, qp, 1, 1, r.o1[q].size(), r.sums[q], bd[q]); }
-  for (size_t k = 0; k < r.walks.size(); k++) {
-    QualityWalk& w = r.walks[k];
-    if (!w.settled) { j.err = "internal: quality walk did not settle"; return RBT_ERR_PARAM; }
-    QualityTried& t = w.tried[w.qstar];
-    quality_fill_result(j.qresults[w.entry], w.qstar, w.q0, w.qs, w.met, r.n_enc[k], t.stream.size(), t.sums, w.bit_depth);
-    r.o1[w.q].swap(t.stream);
-  }
-  return 0;
-}
-
 // Pipelines that share a HIP stream would parse one after the other; their slices go into one merged launch instead, so
 // that all parsers of the stream run side by side and only the (short) tails of the pipelines follow each other.
 static int launch_merged(GofJob& j) {
@@ -949,7 +909,7 @@ static int launch_merged(GofJob& j) {
 static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
   const int sid = job_stream(j, gi), aux = job_stream(j, rbtk::RBT_AUX_STREAM); rbtk::set_stream(sid);
   DecodeBatch& db = j.db[gi]; const std::vector<PoolJob>& jobs = s.pool_jobs[gi];
-  if (!j.chained[gi]) {      // a pipeline with rate targets: the decoder, the input's hash check and the census; rate_run_pipeline encodes when the job is collected
+  if (!j.chained[gi]) {      // a pipeline with rate targets: the decoder, the input's hash check and the census; run_rounds encodes when the job is collected
     if (int rc = decode_launch(db)) { j.err = db.err; return rc; }
     if (!db.hash.empty()) decode_launch_hash(db);
     if (!db.census.empty()) db.census.launch();
@@ -1052,8 +1012,7 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
     if (rc) { rbtk::dev_sync(); continue; }              // drain the remaining streams before their arenas are released
     if (db[gi].frames.empty()) continue;
     std::vector<std::vector<uint8_t>> o1;
-    if (quality && j.rate_pipe[gi]) { rc = quality_run_pipeline(j, gi); rbtk::set_stream(sid); if (rc) continue; o1.swap(j.qual[gi].o1); }      // rounds of trial encodes with their sums, walks
-    else if (j.rate_pipe[gi]) { rc = rate_run_pipeline(j, gi); rbtk::set_stream(sid); if (rc) continue; o1.swap(j.rate[gi].o1); }      // estimates, rounds of trial encodes, walks
+    if (j.rate_pipe[gi]) { rc = run_rounds(j, gi); rbtk::set_stream(sid); if (rc) continue; o1.swap(j.pipes[gi].o1); }      // seeds, rounds of trial encodes, walks
     else {
       rc = pipeline_decoded(j, gi);
       if (rc) continue;

@@ -1,8 +1,9 @@
 // TEST-ONLY: the body of the distortion sums (csrc/rbt_quality.h) and the host half of a transcode to a PSNR floor (host/rbt_quality_walk.h: PSNR, the floor's condition,
-// walk, rounds) as a stand-alone host program, so that they can be built with -fsanitize=address,undefined and run on the CPU (tests/test_quality.py). The planes are views
+// probe; host/rbt_qp_walk.h: walk, rounds) as a stand-alone host program, so that they can be built with -fsanitize=address,undefined and run on the CPU (tests/test_quality.py). The planes are views
 // into heap blocks that end with the last sample of the last row, at every misalignment of the two pictures against a 16-byte boundary and against each other, so a read
 // past a row's end or a misaligned 16-byte load is caught; the sums are compared with a per-sample loop of the definition, the walk - driven round by round the way
-// quality_run_pipeline drives it - with the definition's loop on every floor, start and range of three PSNR tables, one of them not monotone. Prints "ok".
+// run_rounds drives it - with the definition's loop on every floor, start and range of three PSNR tables, one of them not monotone, and every round with the rule of what
+// a round encodes. Prints "ok".
 #define RBT_HOSTEMU 1
 #include <stdio.h>
 #include <stdlib.h>
@@ -51,21 +52,33 @@ static rbt::QualitySums sums_of(double db) {
   return s;
 }
 static int walk_case(const std::vector<rbt::QualitySums>& t, int qp, int32_t floor_mdb, int region, int lo, int hi) {
-  rbt::QualityWalk w; w.floor_mdb = floor_mdb; w.region = region; w.bit_depth = 10; w.lo = lo; w.hi = hi; w.q0 = qp < lo ? lo : qp > hi ? hi : qp;
-  int n_enc = 0, need = 0, dir = 0; std::vector<int> qps;
-  while (!rbt::quality_walk_step(w, need, dir)) {
-    rbt::quality_round_qps(w, need, dir, qps);
+  rbt::QpWalk<rbt::QualityTried> w; rbt::QualityGoal g; g.floor_mdb = floor_mdb; g.region = region; g.bit_depth = 10; w.lo = lo; w.hi = hi; rbt::quality_seed(w, g, qp);
+  const int q0 = qp < lo ? lo : qp > hi ? hi : qp;
+  if (g.q0 != q0 || w.toward != 1) return fail("seed", qp, g.q0, q0);
+  auto meets = [&](int q) { return rbt::quality_meets(t[q], region, floor_mdb, 10); };
+  const double p0 = rbt::quality_region_psnr(t[q0], region, 10);
+  int qs = std::isinf(p0) ? q0 : q0 + (int)(p0 - floor_mdb / 1000.0); qs = qs < lo ? lo : qs > hi ? hi : qs;
+  int n_enc = 0, need = 0, dir = 0, round = 0; std::vector<int> qps, rule;
+  for (;; round++) {
+    const bool probe = !rbt::quality_probe(w, g);
+    if (probe) { need = g.q0; dir = 0; } else if (rbt::qp_walk_step(w, rbt::quality_holds(w, g), need, dir)) break;
+    rbt::qp_round(w, need, dir, probe, qps);
+    // the rule: the first round is the probe at q0 alone; the second qs - 1, qs, qs + 1; every later one the QP asked for and the next one the same way - up while the
+    // floor was met at qs, down while it was not -; a QP out of the range or already encoded is left out
+    rule.clear();
+    if (round == 0) { if (!probe || need != q0 || dir != 0) return fail("first round", need, dir, q0); rule = {q0}; }
+    else if (dir == 0) { if (probe || round != 1 || need != qs) return fail("start round", round, need, qs); rule = {qs - 1, qs, qs + 1}; }
+    else { if (probe || dir != (meets(qs) ? 1 : -1)) return fail("direction", dir, qs, floor_mdb); rule = {need, need + dir}; }
+    for (size_t i = rule.size(); i-- > 0;) if (rule[i] < lo || rule[i] > hi || w.tried.count(rule[i])) rule.erase(rule.begin() + i);
+    if (qps != rule) return fail("round is not the rule's", round, need, dir);
     if (qps.empty()) return fail("empty round", floor_mdb, lo, hi);
     bool brought = false;
     for (int q : qps) { if (q < lo || q > hi) return fail("round out of range", q, lo, hi); if (w.tried.count(q)) return fail("encoded twice", q, lo, hi); w.tried[q].sums = t[q]; n_enc++; brought |= q == need; }
     if (!brought) return fail("round without the sums asked for", need, lo, hi);
   }
-  auto meets = [&](int q) { return rbt::quality_meets(t[q], region, floor_mdb, 10); };
-  const double p0 = rbt::quality_region_psnr(t[w.q0], region, 10);
-  int qs = std::isinf(p0) ? w.q0 : w.q0 + (int)(p0 - floor_mdb / 1000.0); qs = qs < lo ? lo : qs > hi ? hi : qs;
   int q = qs, met;
   if (meets(q)) { while (q < hi && meets(q + 1)) q++; met = 1; } else { while (q > lo && !meets(q)) q--; met = meets(q); }
-  if (w.qs != qs || w.qstar != q || w.met != met) return fail("walk", floor_mdb, w.qstar, q);
+  if (w.start != qs || w.qstar != q || w.met != met) return fail("walk", floor_mdb, w.qstar, q);
   if (n_enc > abs(q - qs) + 5) return fail("encodes", n_enc, q, qs);
   return 0;
 }

@@ -1,7 +1,8 @@
-// TEST-ONLY: the body of the level census (csrc/rbt_rate.h) and the host half of a rate-targeted transcode (host/rbt_rate_walk.h: estimate, walk, rounds) as a stand-alone
+// TEST-ONLY: the body of the level census (csrc/rbt_rate.h) and the host half of a rate-targeted transcode (host/rbt_rate_walk.h: estimate, seed, budget; host/rbt_qp_walk.h: walk, rounds) as a stand-alone
 // host program, so that they can be built with -fsanitize=address,undefined and run on the CPU (tests/test_rate.py). The planes and maps are heap blocks of exactly the
 // picture's size, so a read past a plane's last word is caught; the census is compared with a per-sample count of the definition, the walk - driven round by round the way
-// rate_run_pipeline drives it - with the definition's loop on every budget and range of three size tables, one of them not monotone. Prints "ok".
+// run_rounds drives it - with the definition's loop on every budget and range of three size tables, one of them not monotone, and every round with the rule of what a
+// round encodes. Prints "ok".
 #define RBT_HOSTEMU 1
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,20 +38,28 @@ static int census_case(int w, int h, int density_pct, int extremes) {
 
 // s(q) for q = 0..51; the rounds as the library runs them; the definition beside them
 static int walk_case(const std::vector<uint64_t>& s, const uint64_t E[52], uint64_t T, int lo, int hi) {
-  rbt::RateWalk w; w.T = T; w.lo = lo; w.hi = hi; w.qe = hi;
-  for (int q = lo; q <= hi; q++) if (E[q] <= T) { w.qe = q; break; }
-  int n_enc = 0, need = 0, dir = 0; std::vector<int> qps;
-  while (!rbt::rate_walk_step(w, need, dir)) {
-    rbt::rate_round_qps(w, need, dir, qps);
+  rbt::QpWalk<rbt::RateTrial> w; rbt::RateGoal g; g.T = T; w.lo = lo; w.hi = hi; rbt::rate_seed(w, g, E);
+  int qe = hi; for (int q = lo; q <= hi; q++) if (E[q] <= T) { qe = q; break; }
+  if (w.start != qe || w.toward != -1 || g.e_qe != E[qe]) return fail("seed", (long)T, w.start, qe);
+  int n_enc = 0, need = 0, dir = 0, round = 0; std::vector<int> qps, rule;
+  for (; !rbt::qp_walk_step(w, rbt::rate_fits(w, g), need, dir); round++) {
+    rbt::qp_round(w, need, dir, false, qps);
+    // the rule: the first round is qe - 1, qe, qe + 1; every later one the QP asked for and the next one the same way - down while the budget held at qe, up while it
+    // did not -; a QP out of the range or already encoded is left out
+    rule.clear();
+    if (round == 0) { if (need != qe || dir != 0) return fail("first round", need, dir, qe); rule = {qe - 1, qe, qe + 1}; }
+    else { if (dir != (s[qe] <= T ? -1 : 1)) return fail("direction", dir, qe, (long)T); rule = {need, need + dir}; }
+    for (size_t i = rule.size(); i-- > 0;) if (rule[i] < lo || rule[i] > hi || w.tried.count(rule[i])) rule.erase(rule.begin() + i);
+    if (qps != rule) return fail("round is not the rule's", round, need, dir);
     if (qps.empty()) return fail("empty round", (long)T, lo, hi);
     bool brought = false;
-    for (int q : qps) { if (q < lo || q > hi) return fail("round out of range", q, lo, hi); if (w.tried.count(q)) return fail("encoded twice", q, lo, hi); w.tried[q].assign((size_t)s[q], 0); n_enc++; brought |= q == need; }
+    for (int q : qps) { if (q < lo || q > hi) return fail("round out of range", q, lo, hi); if (w.tried.count(q)) return fail("encoded twice", q, lo, hi); w.tried[q].stream.assign((size_t)s[q], 0); n_enc++; brought |= q == need; }
     if (!brought) return fail("round without the size asked for", need, lo, hi);
   }
-  int q = w.qe, met;
+  int q = qe, met;
   if (s[q] <= T) { while (q > lo && s[q - 1] <= T) q--; met = 1; } else { while (q < hi && s[q] > T) q++; met = s[q] <= T; }
   if (w.qstar != q || w.met != met) return fail("walk", (long)T, w.qstar, q);
-  if (n_enc > abs(q - w.qe) + 4) return fail("encodes", n_enc, q, w.qe);
+  if (n_enc > abs(q - qe) + 4) return fail("encodes", n_enc, q, qe);
   return 0;
 }
 
