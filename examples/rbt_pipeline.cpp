@@ -12,6 +12,8 @@
 //       PSNR of every GOF's unit against its decoded input at or above DB (rbt_transcode_v3c_quality), and one line per GOF says q*, the bytes and the PSNRs. --occupied:
 //       the floors look at the occupied samples, and the units are coded occupancy-aware (occupancy_rd), so the bytes differ from a run without it and an input without
 //       a pooled occupancy unit is refused; it needs at least one floor. Not together with a bit rate.
+//       Not built: a floor on the point-to-point distortion D1 for a container. rbt_submit_gof_d1 (include/rbt.h) needs the patches of every frame, and the library does not
+//       parse the atlas sub-bitstream they are in; a host that has them calls it per GOF.
 //
 // File format (little endian, test harness only): u32 n_gofs, then per GOF three sub-bitstreams in the order occupancy, geometry,
 // attribute, each as u32 size + Annex-B bytes. The output file has the same layout with the re-encoded streams.

@@ -245,7 +245,7 @@ int rbt_rate_estimate(rbt_ctx* ctx, const uint8_t* annexb, size_t n, int video_t
  * occupancy planes and the per-unit maps of occupancy_rd stay alive until the job is collected, and the first trial encode starts only after the occupancy pipeline has made
  * them. A job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality only, and rbt_wait_gof_quality collects no other job: any other pairing is RBT_ERR_PARAM and the
  * job stays collectable. rbt_job_memory counts the arenas of the first round (one trial encode per geometry / attribute entry).
- * Not built: a floor per picture (the floor is on the stream's sum), a floor on the point-to-point distortion D1 (needs the atlas), a floor and a byte budget in one call. */
+ * Not built: a floor per picture (the floor is on the stream's sum), a floor and a byte budget in one call. (A floor on the point-to-point distortion D1: rbt_submit_gof_d1 below.) */
 enum { RBT_QUALITY_ALL = 0, RBT_QUALITY_OCCUPIED = 1 };
 typedef struct {
   uint32_t struct_size;    /* sizeof(rbt_quality_target): checked */
@@ -268,6 +268,56 @@ int rbt_transcode_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_
  * or n_frames planes of ow x oh samples, one per picture. out: n_frames x 3 x {sse, sse_occ, n_occ}. RBT_ERR_PARAM: odd sizes, sizes above 8192, a map whose scale is
  * not whole and equal in both directions. rbt_get_stats afterwards: gpu_ms = the device time between events around the kernel's launches, everything else 0. */
 int rbt_picture_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int width, int height, int n_frames, const uint16_t* occ, int ow, int oh, uint64_t* out);
+
+/* ---- transcoding geometry to a D1 floor (csrc/rbt_cloudmaps.h, host/rbt_d1_walk.h) ----
+ * "The cheapest geometry stream that keeps the point-to-point distortion D1 within X dB." The luma PSNR of a geometry map is a proxy for D1: the occupancy map of the
+ * output decides which samples become points at all, and pooling it from precision 2 to 4 adds and removes points whatever the geometry QP. Here the cloud of every trial
+ * encode is rebuilt and scored on the GPU: when a round of trial encodes ends, the decoded input and the encoder's reconstructions are in device memory; a gather kernel
+ * (k_gather_luma) makes the packed luma planes of them, the reconstruction kernels of rbt_reconstruct emit the positions, the cloud is indexed as rbt_pcloud_upload indexes
+ * one and scored as rbt_score scores it. Only counts and the D1 sums come back to the host. The types of the atlas, patches, clouds and D1 results are declared further
+ * down in this header.
+ *
+ * 1. Occupancy source of a geometry entry: the nearest occupancy entry in front of it in the call that this call pools (occupancy_precision 4; the rule of occupancy_rd and
+ *    of the PSNR floor). Its output luma is the pooled plane. Without such an entry: RBT_ERR_PARAM. (Not built: an occupancy entry that is passed through, whose decoded
+ *    input plane would be the output's - the library does not decode a stream it hands back unchanged.)
+ * 2. Shapes. The entry's displayed picture size equals atlas.width x atlas.height; its picture count is atlas.map_count x n_frames; the occupancy entry has n_frames
+ *    pictures; atlas.occupancy_precision equals width / (output occupancy width), and the input occupancy width divides width by a whole number, the same in both
+ *    directions. Anything else is RBT_ERR_PARAM with the reason in rbt_last_error.
+ * 3. Cloud of a trial. B_f(q) is the positions rbt_reconstruct returns for the atlas and the patches of frame f, the output occupancy luma of frame f and the luma of output
+ *    pictures map_count * f (and + 1) of the stream rbt_transcode_gof gives at qp = q. No attribute pictures. Geometry smoothing runs as atlas.geometry_smoothing says.
+ * 4. Reference. A_f is the handle given for frame f. Where it is NULL, A_f is the same reconstruction on the decoded input: input occupancy luma, input geometry luma, the
+ *    same atlas with occupancy_precision = width / input occupancy width.
+ * 5. Score. D_f(q) = rbt_d1(A_f, B_f(q), peak): the integer fields from the search rbt_score runs, the float fields from the routine both public calls use. D(q) is the
+ *    minimum over f of (double)psnr (RBT_D1_MIN), or the sum in frame order in double divided by n_frames (RBT_D1_MEAN). meets(q): D(q) >= min_d1_mdb / 1000.0; +inf meets
+ *    any floor.
+ * 6. Walk. The PSNR floor's walk (rule 5 there), word for word, with D in place of the PSNR: probe at q0 = clamp(params[i].qp, lo, hi); qs = q0 when D(q0) is infinite,
+ *    otherwise clamp(q0 + (int)(D(q0) - F), lo, hi); toward larger QPs while meets holds, else down; met and q* as there; n_encodes <= |q* - qs| + 5. The 1 dB-per-step
+ *    model behind qs is poor for D1 - about 0.2 dB per step on the synthetic atlases of the tests, and D is far from monotone (58.5, 59.3, 58.2, 59.1 dB at QP 24..27) -
+ *    which costs encodes, not correctness: the walk is the definition. The rule is kept so that the probe is the PSNR floor's.
+ * 7. Stream. The returned stream is byte for byte rbt_transcode_gof's at qp = q*, occupancy_rd included. A floor that even lo misses is no error (met = 0, RBT_OK).
+ * min_d1_mdb 0: the entry is coded at params[i].qp and its D1 is reported (qp = qp_probe = qp_start = params[i].qp, met = 1, n_encodes = 1).
+ * Other entries - attribute, occupancy, geometry without a target - are coded as rbt_submit_gof codes them; their target is empty (every field but struct_size zero) and
+ * their result carries qp, bytes and zeros.
+ * RBT_ERR_PARAM (reason in rbt_last_error; nothing is submitted and the context stays usable): a wrong struct_size; a target on a non-geometry entry; a bad range; an unknown
+ * stat; a negative floor; n_frames < 1; a missing patch list; a reference handle of another context; rules 1 and 2; an atlas or a patch rbt_reconstruct refuses;
+ * occupancy_rd together with verify_md5. An empty cloud or a coordinate outside 0..1023 is found when the cloud is built: the job fails in its wait call as the PCC stage
+ * reports it (RBT_ERR_PARAM, "empty point cloud" / "coordinate outside 0..1023") and the context stays usable.
+ * The patch lists are copied at submit; a reference handle must stay alive until the job is collected. A job of rbt_submit_gof_d1 is collected by rbt_wait_gof_d1 only, and
+ * rbt_wait_gof_d1 collects no other job: any other pairing is RBT_ERR_PARAM and the job stays collectable.
+ * Memory: the clouds of a round are scored one after the other. A job holds one 128 MB volume per frame without a reference handle (for the whole job), one more for the
+ * trial being scored, and three packed planes per frame; rbt_job_memory counts them with the arenas of the first round.
+ * Not built: a container-level call (the library does not parse the atlas sub-bitstream, so rbt_transcode_v3c cannot know the patches), a D2 or colour floor, a D1 floor
+ * together with a byte budget or a PSNR floor, a floor per frame other than through RBT_D1_MIN. */
+enum { RBT_D1_MIN = 0, RBT_D1_MEAN = 1 };
+typedef struct rbt_d1_target rbt_d1_target;                  /* both defined behind rbt_score_summary, where the types of their fields are known */
+typedef struct rbt_d1_floor_result rbt_d1_floor_result;
+int rbt_submit_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets, rbt_job** job);
+int rbt_wait_gof_d1(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results);   /* results: n entries */
+int rbt_transcode_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets,
+                         uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results);   /* submit + wait */
+/* The gather kernel on host arrays (tests): src holds n_pics planes of `stride` x `rows` samples; the w x h window at (x0, y0) of each comes back packed in out
+ * (n_pics x w x h). The planes go to the device with their first sample src_misalign (0..7) samples behind a 256-byte boundary, the packed planes start on one. */
+int rbt_gather_luma(rbt_ctx* ctx, const uint16_t* src, int n_pics, int stride, int rows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out);
 
 /* The two halves exposed on their own (SURVEY.md 8(b) alternative seam; used by the parity tests).
  * Picture sizes: any even width / height. Sizes that are not multiples of 8 (all-intra) / 16 (gop 2) are coded padded with a
@@ -563,6 +613,30 @@ typedef struct {
   int64_t points_a, points_b, merged_a, merged_b;
 } rbt_sequence_score;
 int rbt_score_summary(const rbt_frame_score* frames, int n_frames, rbt_sequence_score* out);
+
+/* The target and the result of a transcode to a D1 floor ("transcoding geometry to a D1 floor" above). */
+struct rbt_d1_target {
+  uint32_t struct_size;                  /* sizeof(rbt_d1_target): checked */
+  int32_t  min_d1_mdb;                   /* floor on D, 1/1000 dB; 0 = none: coded at params[i].qp, D1 reported */
+  int      stat;                         /* RBT_D1_MIN (the default): the floor is on the worst frame; RBT_D1_MEAN: on the mean over the frames */
+  int      peak;                         /* 0 = 1023 */
+  int      qp_min, qp_max;               /* the walk's range; qp_max 0 = 51 */
+  int      n_frames;                     /* point-cloud frames of the entry; 0 in an empty target */
+  rbt_atlas_params atlas;                /* the OUTPUT atlas: occupancy_precision is that of the output occupancy video */
+  const rbt_patch* const* patches;       /* n_frames lists (a NULL list only with a count of 0) ... */
+  const int* n_patches;                  /* ... and their lengths; copied at submit */
+  const rbt_pcloud* const* reference;    /* NULL, or n_frames handles: A_f; a NULL handle = the cloud of the decoded input */
+};
+struct rbt_d1_floor_result {
+  int qp, qp_probe, qp_start, met, n_encodes;   /* q*, q0, qs, met, distinct QPs encoded */
+  uint64_t bytes;                               /* size of the returned stream */
+  double mean_d1, min_d1;                       /* over the frames at q*: the sum of (double)psnr in frame order / n_frames, and the minimum */
+  int n_frames;                                 /* 0 for an entry without a target */
+  rbt_d1_result* frames;                        /* n_frames results at q* (malloc'd, rbt_free; NULL for an entry without a target) */
+  double cloud_ms;                              /* time between events on the pipeline's stream around the gather, the reconstruction, the index and the search of every cloud
+                                                 * of the job's rounds for this entry, the reference clouds included: the kernels and the gaps in which the stream waits for the
+                                                 * host's read-backs of counts and its launches (the clear of a released volume is outside) */
+};
 
 /* ---- normal estimation (csrc/rbt_normals.h) ----
  * D2 needs normals on the source. Where a sequence comes without them, the reference's PccAppNormalGenerator makes them (PCCNormalsGenerator.cpp: a kd-tree query of the

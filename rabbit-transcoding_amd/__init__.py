@@ -144,6 +144,40 @@ class QualityResult(C.Structure):
                 ("sse", C.c_uint64 * 3), ("samples", C.c_uint64 * 3), ("sse_occ", C.c_uint64 * 3), ("samples_occ", C.c_uint64 * 3), ("psnr", C.c_double * 3), ("psnr_occ", C.c_double * 3)]
 
 
+RBT_D1_MIN, RBT_D1_MEAN = 0, 1
+
+
+class D1Target(C.Structure):
+    """rbt_d1_target; struct_size is filled in. D1Target() is the empty target of an entry without one. patches: one list of Patch per point-cloud frame; reference: None,
+    or one PCloud (or None = the cloud of the decoded input) per frame. The object keeps the arrays it points to alive."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_d1_mdb", C.c_int32), ("stat", C.c_int), ("peak", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("n_frames", C.c_int),
+                ("atlas", AtlasParams), ("patches", C.POINTER(C.POINTER(Patch))), ("n_patches", C.POINTER(C.c_int)), ("reference", C.POINTER(C.c_void_p))]
+
+    def __init__(self, atlas=None, patches=None, min_d1_mdb=0, stat=RBT_D1_MIN, qp_min=0, qp_max=0, peak=0, reference=None):
+        super().__init__(C.sizeof(D1Target), min_d1_mdb, stat, peak, qp_min, qp_max)
+        self._keep = []
+        if atlas is None:
+            return
+        self.atlas = AtlasParams(*[getattr(atlas, n) for n, _ in AtlasParams._fields_])
+        self.n_frames = len(patches)
+        lists = [(Patch * max(1, len(p)))(*p) for p in patches]
+        ptrs = (C.POINTER(Patch) * max(1, len(lists)))(*[C.cast(a, C.POINTER(Patch)) for a in lists])
+        counts = (C.c_int * max(1, len(lists)))(*[len(p) for p in patches])
+        self.patches, self.n_patches = ptrs, counts
+        self._keep += [lists, ptrs, counts]
+        if reference is not None:
+            refs = (C.c_void_p * max(1, len(reference)))(*[None if r is None else (r.h.value if isinstance(r, PCloud) else r) for r in reference])
+            self.reference = refs
+            self._keep += [refs, list(reference)]
+
+
+class D1FloorResult(C.Structure):
+    """rbt_d1_floor_result: q*, the probe q0, the walk's start qs, met, distinct QPs encoded, the stream's size, mean and minimum D1 over the frames, the frames' D1Result
+    (freed by the binding), device milliseconds of the clouds"""
+    _fields_ = [("qp", C.c_int), ("qp_probe", C.c_int), ("qp_start", C.c_int), ("met", C.c_int), ("n_encodes", C.c_int), ("bytes", C.c_uint64), ("mean_d1", C.c_double), ("min_d1", C.c_double),
+                ("n_frames", C.c_int), ("frames", C.POINTER(D1Result)), ("cloud_ms", C.c_double)]
+
+
 class RateTable(C.Structure):
     """rbt_rate_table"""
     _fields_ = [("n_pictures", C.c_int), ("hist", C.POINTER(C.c_uint32)), ("picture_bytes", C.POINTER(C.c_uint64)), ("estimate", C.c_uint64 * 52), ("census_ms", C.c_double)]
@@ -226,6 +260,11 @@ def load(path=None):
     L.rbt_wait_gof_quality.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(QualityResult)]
     L.rbt_transcode_gof_quality.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QualityTarget), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                             C.POINTER(QualityResult)]
+    L.rbt_submit_gof_d1.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p)]
+    L.rbt_wait_gof_d1.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(D1FloorResult)]
+    L.rbt_transcode_gof_d1.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                       C.POINTER(D1FloorResult)]
+    L.rbt_gather_luma.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]
     L.rbt_picture_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.rbt_transcode_v3c_quality.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(QualityResult))]
     L.rbt_level_census.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -380,6 +419,7 @@ class Context:
 
     def __init__(self, device=0, rank=0, world=1, lib_path=None):
         self.L = load(lib_path)
+        self.lib_path = lib_path      # (a second context on the same build: Context(lib_path=ctx.lib_path))
         self.h = C.c_void_p()
         rc = self.L.rbt_create(C.byref(self.h), device, rank, world)
         if rc != 0:
@@ -526,6 +566,37 @@ class Context:
     def transcode_gof_quality(self, streams, params, targets):
         """rbt_transcode_gof_quality: submit + wait"""
         return self._transcode(self.L.rbt_transcode_gof_quality, streams, params, targets, QualityTarget, QualityResult)
+
+    def _d1_results(self, res):
+        """([stream bytes, ...], [D1FloorResult, ...] as dicts): frames becomes a list of D1 dicts and the library's array is released"""
+        outs, rs = res
+        for r in rs:
+            ptr = r["frames"]
+            r["frames"] = [{n: getattr(ptr[f], n) for n, _ in D1Result._fields_} for f in range(r["n_frames"])]
+            self.L.rbt_free(ptr)
+        return outs, rs
+
+    def submit_gof_d1(self, streams, params, targets):
+        """rbt_submit_gof_d1: submit_gof with one D1Target per entry (D1Target() = none; min_d1_mdb 0 = constant QP, D1 reported); returns a job for wait_gof_d1"""
+        return self._submit(self.L.rbt_submit_gof_d1, streams, params, targets, D1Target)
+
+    def wait_gof_d1(self, job):
+        """rbt_wait_gof_d1 -> ([stream bytes, ...], [result dict, ...])"""
+        return self._d1_results(self._collect(self.L.rbt_wait_gof_d1, job[1], [job[0]], D1FloorResult))
+
+    def transcode_gof_d1(self, streams, params, targets):
+        """rbt_transcode_gof_d1: submit + wait"""
+        args = self._gof_args(streams, params, targets, D1Target)
+        return self._d1_results(self._collect(self.L.rbt_transcode_gof_d1, args[0], args, D1FloorResult))
+
+    def gather_luma(self, src, x0, y0, w, h, src_misalign=0):
+        """rbt_gather_luma: planes src ([n, rows, stride] uint16) -> the w x h window at (x0, y0) of each, packed ([n, h, w]); the planes lie src_misalign samples behind
+        a 256-byte boundary on the device"""
+        src = np.ascontiguousarray(src, dtype=np.uint16)
+        n, rows, stride = src.shape
+        out = np.zeros((n, h, w), np.uint16)
+        self._chk(self.L.rbt_gather_luma(self.h, src.ctypes.data, n, stride, rows, x0, y0, w, h, src_misalign, out.ctypes.data))
+        return out
 
     def picture_sse(self, a, b, w, h, occ=None):
         """rbt_picture_sse: planar 4:2:0 pictures a, b ([n, w*h*3/2] uint16) and, or None, one occupancy plane per picture ([n, oh, ow] uint16) -> uint64 [n, 3, 3]:

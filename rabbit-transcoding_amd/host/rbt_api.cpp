@@ -140,7 +140,8 @@ int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t
   return RBT_OK;
 } RBT_CATCH
 
-static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr);
+static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr,
+                  const rbt_d1_target* d1 = nullptr);
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
 int rbt_transcode_substream(rbt_ctx* ctx, const uint8_t* annexb_in, size_t n_in, const rbt_stream_params* p, uint8_t** annexb_out, size_t* n_out) try {
   if (!ctx || !annexb_in || !p || !annexb_out || !n_out) return RBT_ERR_PARAM;
@@ -183,18 +184,51 @@ static int check_quality(std::string& err, int n, const rbt_stream_params* p, co
   }
   return RBT_OK;
 }
-static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality) {
+// the refusals of rbt_submit_gof_d1 that the parameters alone decide (those that need the streams' sizes: gof_refused); req: the reference handles as clouds
+static int check_d1(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_d1_target* t, rbt::D1Request& req) {
+  std::string& err = ctx->last_err;
+  req.targets = t; req.cache = &ctx->cloud_cache; req.refs.assign((size_t)n, {});
+  for (int i = 0; i < n; i++) {
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    if (t[i].struct_size != sizeof(rbt_d1_target)) { err = who + "rbt_d1_target.struct_size is not sizeof(rbt_d1_target)"; return RBT_ERR_PARAM; }
+    rbt_d1_target zero; memset(&zero, 0, sizeof(zero)); zero.struct_size = t[i].struct_size;
+    const bool empty = !t[i].min_d1_mdb && !t[i].stat && !t[i].peak && !t[i].qp_min && !t[i].qp_max && !t[i].n_frames && !t[i].patches && !t[i].n_patches && !t[i].reference &&
+                       !memcmp(&t[i].atlas, &zero.atlas, sizeof(zero.atlas));
+    if (empty) continue;
+    if (p[i].video_type != RBT_VIDEO_GEOMETRY) { err = who + "a D1 target on a non-geometry entry (the target of an attribute or occupancy entry must be empty)"; return RBT_ERR_PARAM; }
+    if (t[i].min_d1_mdb < 0) { err = who + "min_d1_mdb must not be negative"; return RBT_ERR_PARAM; }
+    if (t[i].stat != RBT_D1_MIN && t[i].stat != RBT_D1_MEAN) { err = who + "stat must be RBT_D1_MIN or RBT_D1_MEAN"; return RBT_ERR_PARAM; }
+    if (t[i].peak < 0) { err = who + "peak must not be negative (0 = 1023)"; return RBT_ERR_PARAM; }
+    const int lo = t[i].qp_min, hi = t[i].qp_max ? t[i].qp_max : 51;
+    if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
+    if (t[i].n_frames < 1) { err = who + "n_frames must be at least 1"; return RBT_ERR_PARAM; }
+    if (!t[i].patches || !t[i].n_patches) { err = who + "the patch lists are missing"; return RBT_ERR_PARAM; }
+    for (int f = 0; f < t[i].n_frames; f++) {
+      if (t[i].n_patches[f] < 0 || (!t[i].patches[f] && t[i].n_patches[f])) { err = who + "the patch list of frame " + std::to_string(f) + " is missing"; return RBT_ERR_PARAM; }
+      std::string why;
+      if (rbt::mapframe_check(why, &t[i].atlas, t[i].patches[f], t[i].n_patches[f])) { err = who + "frame " + std::to_string(f) + ": " + why; return RBT_ERR_PARAM; }
+      const rbt_pcloud* h = t[i].reference ? t[i].reference[f] : nullptr;
+      if (h) { bool mine = false; for (const rbt_pcloud* c : ctx->clouds) mine |= c == h; if (!mine) { err = who + "reference " + std::to_string(f) + " is not a cloud of this context"; return RBT_ERR_PARAM; } }
+      req.refs[(size_t)i].push_back(h ? h->cloud : nullptr);
+    }
+  }
+  return RBT_OK;
+}
+static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
+                  const rbt_d1_target* d1) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
   RBT_ENTER(ctx);
   if (targets) if (int rc = check_targets(ctx->last_err, n, p, targets)) return rc;
   if (quality) if (int rc = check_quality(ctx->last_err, n, p, quality)) return rc;
+  rbt::D1Request req;
+  if (d1) if (int rc = check_d1(ctx, n, p, d1, req)) return rc;
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
-  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality), ctx};
-  if (quality) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
+  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality, d1 ? &req : nullptr), ctx};
+  if (quality || d1) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -255,7 +289,7 @@ int rbt_trim(rbt_ctx* ctx) try {
   rbtk::dev_release_pool();
   return RBT_OK;
 } RBT_CATCH
-static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* quality = nullptr) {
+static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* quality = nullptr, rbt_d1_floor_result* d1 = nullptr) {
   if (!ctx || !job || !annexb_out || !n_out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   int slot = -1;
@@ -263,8 +297,10 @@ static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out,
   if (slot < 0 || job->owner != ctx) return RBT_ERR_PARAM;
   if (rbt::gof_is_quality(job->j) != (quality != nullptr)) {      // the job stays collectable
     ctx->last_err = quality ? "rbt_wait_gof_quality collects jobs of rbt_submit_gof_quality only" : "a job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality"; return RBT_ERR_PARAM; }
+  if (rbt::gof_is_d1(job->j) != (d1 != nullptr)) {                // ... and so does a job of rbt_submit_gof_d1
+    ctx->last_err = d1 ? "rbt_wait_gof_d1 collects jobs of rbt_submit_gof_d1 only" : "a job of rbt_submit_gof_d1 is collected by rbt_wait_gof_d1"; return RBT_ERR_PARAM; }
   int n_flat = 0;
-  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality, &n_flat);
+  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality, &n_flat, d1);
   if (!rc) ctx->n_flat = n_flat;
   D.jobs[slot] = nullptr; delete job;
   return rc;
@@ -303,6 +339,28 @@ int rbt_transcode_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_
   int rc = rbt_submit_gof_quality(ctx, n, annexb_in, n_in, p, targets, &job);
   if (rc) return rc;
   return rbt_wait_gof_quality(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
+// ---- transcoding geometry to a D1 floor ----
+int rbt_submit_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, targets);
+} RBT_CATCH
+int rbt_wait_gof_d1(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  return wait(ctx, job, annexb_out, n_out, nullptr, nullptr, results);
+} RBT_CATCH
+int rbt_transcode_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets,
+                         uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results) try {
+  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_d1(ctx, n, annexb_in, n_in, p, targets, &job);
+  if (rc) return rc;
+  return rbt_wait_gof_d1(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
+int rbt_gather_luma(rbt_ctx* ctx, const uint16_t* src, int n_pics, int stride, int rows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out) try {
+  if (!ctx || !src || !out) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  return rbt::gather_luma_host(ctx->last_err, src, n_pics, stride, rows, x0, y0, w, h, src_misalign, out);
 } RBT_CATCH
 int rbt_picture_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int width, int height, int n_frames, const uint16_t* occ, int ow, int oh, uint64_t* out) try {
   if (!ctx || !a || !b || !out) return RBT_ERR_PARAM;

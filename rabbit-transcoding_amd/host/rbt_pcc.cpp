@@ -3,10 +3,12 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 #include "rbt_batch.h"
 #include "rbt_pcc.h"
 #include "../csrc/rbt_pcc.h"
+#include "../csrc/rbt_cloudmaps.h"
 #include "../csrc/rbt_color.h"
 #include "../csrc/rbt_score.h"
 #include "../csrc/rbt_normals.h"
@@ -446,6 +448,120 @@ int pcloud_from_maps(std::string& err, PCloudCache& cache, const rbt_atlas_param
   *out = c;
   return RBT_OK;
 }
+// ---- positions-only reconstruction from device planes (rbt_submit_gof_d1; rbt_pcc.h) ----
+// The checks reconstruct_impl makes on the atlas and the patches, for a call without attribute pictures; items in the reference's visiting order
+int mapframe_check(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, std::vector<uint32_t>* items) {
+  const int W = a->width, H = a->height, res = a->occupancy_resolution, prec = a->occupancy_precision;
+  if (W <= 0 || H <= 0 || res < 1 || prec < 1 || W % res || H % res || W % prec || H % prec || W % 2 || H % 2 || W > 8192 || H > 8192 || n_patches < 0 || n_patches > 65535 ||
+      a->map_count < 1 || a->map_count > 2 || (a->geometry_smoothing && (a->grid_size < 2 || a->grid_size > 255 || a->threshold_smoothing < 0))) { err = "bad atlas parameters"; return RBT_ERR_PARAM; }
+  if (a->geometry_smoothing && a->grid_size % 2) { err = "grid_size must be even"; return RBT_ERR_PARAM; }
+  const int bw = W / res, bh = H / res;
+  for (int pi = 0; pi < n_patches; pi++) {
+    const rbt_patch& p = patches[pi];
+    const bool swapped = p.orientation == RBT_OR_ROT90 || p.orientation == RBT_OR_ROT270 || p.orientation == RBT_OR_MROT90 || p.orientation == RBT_OR_SWAP;
+    if (p.size_u0 < 1 || p.size_v0 < 1 || (long long)p.size_u0 * p.size_v0 > 65535 || p.orientation < 0 || p.orientation > RBT_OR_ROT90 || p.u0 < 0 || p.v0 < 0 ||
+        p.u0 + (swapped ? p.size_v0 : p.size_u0) > bw || p.v0 + (swapped ? p.size_u0 : p.size_v0) > bh ||
+        p.normal_axis < 0 || p.normal_axis > 2 || p.tangent_axis < 0 || p.tangent_axis > 2 || p.bitangent_axis < 0 || p.bitangent_axis > 2 ||
+        p.normal_axis == p.tangent_axis || p.normal_axis == p.bitangent_axis || p.tangent_axis == p.bitangent_axis) { err = "patch outside the atlas or malformed"; return RBT_ERR_PARAM; }
+    for (int vb = 0; vb < p.size_v0; vb++) for (int ub = 0; ub < p.size_u0; ub++) { int x, y; block_xy(p, ub, vb, &x, &y); if (x < 0 || y < 0 || x >= bw || y >= bh) { err = "patch block outside the atlas"; return RBT_ERR_PARAM; }
+      if (items) items->push_back((uint32_t)pi << 16 | (uint32_t)(vb * p.size_u0 + ub)); }
+  }
+  return RBT_OK;
+}
+struct MapFrame {
+  rbt_atlas_params a; RbtPccParams P; int n_items = 0; const uint16_t* d_occ = nullptr;
+  std::vector<uint32_t> items; std::vector<rbt_patch> patches;      // host staging of the two uploads, alive as long as the frame
+  DevBuf b_patches, b_items, b_b2p, b_om, b_counts, b_off;
+};
+void mapframe_delete(MapFrame* f) { delete f; }
+size_t mapframe_bytes(const rbt_atlas_params* a, int n_patches) {
+  const size_t res = (size_t)(a->occupancy_resolution > 0 ? a->occupancy_resolution : 1), blocks = (size_t)a->width / res * ((size_t)a->height / res);
+  return sizeof(rbt_patch) * (size_t)(n_patches > 0 ? n_patches : 1) + 4 * blocks + (size_t)a->width * (size_t)a->height;
+}
+int mapframe_new(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* d_occ, MapFrame** out) {
+  *out = nullptr;
+  std::unique_ptr<MapFrame> F(new MapFrame());
+  if (int rc = mapframe_check(err, a, patches, n_patches, &F->items)) return rc;
+  F->a = *a; F->d_occ = d_occ; F->n_items = (int)F->items.size(); F->patches.assign(patches, patches + n_patches);
+  RbtPccParams& P = F->P; memset(&P, 0, sizeof(P));
+  P.w = a->width; P.h = a->height; P.res = a->occupancy_resolution; P.prec = a->occupancy_precision; P.map_count = a->map_count; P.absolute_d1 = a->absolute_d1; P.remove_dup = a->remove_duplicate_points;
+  P.threshold = a->threshold_lossy_om; P.geo_bd = 8; P.attr_bd = 8; P.bw = P.w / P.res; P.bh = P.h / P.res; P.ow = P.w / P.prec; P.n_patches = n_patches; P.has_attr = 0;
+  const int n_items = F->n_items; const size_t ys = (size_t)P.w * P.h;
+  if (!F->b_patches.alloc(sizeof(rbt_patch) * (size_t)(n_patches ? n_patches : 1)) || !F->b_items.alloc(4 * (size_t)(n_items ? n_items : 1)) || !F->b_b2p.alloc(4 * (size_t)P.bw * P.bh) ||
+      !F->b_counts.alloc(4 * (size_t)(n_items + 1)) || !F->b_off.alloc(4 * (size_t)(n_items + 1)) || !F->b_om.alloc(ys)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  int bad = rbtk::dev_memset(F->b_b2p.p, 0, 4 * (size_t)P.bw * P.bh);
+  if (n_patches) bad |= rbtk::h2d(F->b_patches.p, F->patches.data(), sizeof(rbt_patch) * (size_t)n_patches);
+  if (n_items) bad |= rbtk::h2d(F->b_items.p, F->items.data(), 4 * (size_t)n_items);
+  if (bad) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::launch_pcc_occmap(&P, d_occ, F->b_om.as<uint8_t>());
+  rbtk::launch_pcc_owner(&P, F->b_patches.as<rbt_patch>(), F->b_items.as<uint32_t>(), n_items, d_occ, F->b_b2p.as<uint32_t>());
+  *out = F.release();
+  return RBT_OK;
+}
+// the cloud of one pair of geometry planes: count, scan, emit, smoothing (as reconstruct_impl runs them), index
+int mapframe_cloud(std::string& err, PCloudCache& cache, const MapFrame* F, const uint16_t* d0, const uint16_t* d1, int geo_bd, PCloud** out, int* n_smoothed) {
+  *out = nullptr; if (n_smoothed) *n_smoothed = 0;
+  if (geo_bd < 8 || geo_bd > 16) { err = "bad atlas parameters"; return RBT_ERR_PARAM; }
+  RbtPccParams P = F->P; P.geo_bd = geo_bd; P.attr_bd = geo_bd;
+  const rbt_atlas_params* a = &F->a; const int n_items = F->n_items; const bool smooth = a->geometry_smoothing != 0;
+  const rbt_patch* patches = F->b_patches.as<rbt_patch>(); const uint32_t *items = F->b_items.as<uint32_t>(), *b2p = F->b_b2p.as<uint32_t>();
+  if (!d1) d1 = d0;
+  rbtk::launch_pcc_count(&P, patches, items, n_items, F->d_occ, d0, d1, b2p, F->b_counts.as<uint32_t>());
+  rbtk::launch_scan_u32(F->b_counts.as<uint32_t>(), F->b_off.as<uint32_t>(), n_items);
+  uint32_t total = 0;
+  if (rbtk::d2h(&total, F->b_off.as<uint32_t>() + n_items, 4)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (!total) { err = "empty point cloud"; return RBT_ERR_PARAM; }
+  DevBuf b_xyz, b_yuv, b_meta, b_scal, b_cells;
+  if (!b_xyz.alloc(6 * (size_t)total) || !b_yuv.alloc(6 * (size_t)total) || (smooth && (!b_meta.alloc(4 * (size_t)total) || !b_scal.alloc(64)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  rbtk::launch_pcc_emit(&P, patches, items, n_items, F->d_occ, d0, d1, nullptr, nullptr, b2p, F->b_off.as<uint32_t>(), b_xyz.as<int16_t>(), b_yuv.as<uint16_t>(),
+                        smooth ? F->b_om.as<uint8_t>() : nullptr, smooth ? b_meta.as<uint32_t>() : nullptr);
+  if (smooth) {
+    uint32_t* scal = b_scal.as<uint32_t>(); uint32_t maxv = 0;                        // [0] largest coordinate, [1] points moved
+    if (rbtk::dev_memset(scal, 0, 64)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+    rbtk::launch_sm_max(b_xyz.as<int16_t>(), (int)total, scal);
+    if (rbtk::d2h(&maxv, scal, 4)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+    RbtSmooth G; memset(&G, 0, sizeof(G));
+    G.g = a->grid_size; G.w = ((int)maxv + G.g - 1) / G.g; G.disth = std::max(G.g / 2, 1); G.th = G.g * G.w; G.threshold = a->threshold_smoothing; G.n_points = (int)total;
+    if (G.w > 0) {
+      const size_t w3 = (size_t)G.w * G.w * G.w, o_sum = (w3 + 255) & ~(size_t)255, o_cnt = o_sum + 12 * w3, o_min = o_cnt + 4 * w3, o_max = o_min + 4 * w3, bytes = o_max + 4 * w3;
+      if (!b_cells.alloc(bytes)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+      uint8_t* base = b_cells.as<uint8_t>();
+      G.flag = base; G.sum = (uint32_t*)(base + o_sum); G.cnt = (uint32_t*)(base + o_cnt); G.pmin = (uint32_t*)(base + o_min); G.pmax = (uint32_t*)(base + o_max); G.moved = scal + 1;
+      if (rbtk::dev_memset(base, 0, bytes) || rbtk::dev_memset(G.pmin, 0xFF, 4 * w3)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+      rbtk::launch_sm_passes(&G, b_xyz.as<int16_t>(), b_meta.as<uint32_t>());
+      uint32_t moved[16];
+      if (rbtk::d2h(moved, scal, 64)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+      if (n_smoothed) *n_smoothed = (int)moved[1];
+    }
+  }
+  PCloud* c = new PCloud(); c->n = (int)total;
+  c->xyz.take(b_xyz);
+  if (int rc = pcloud_index(err, cache, c)) { pcloud_release(cache, c); return rc; }      // (waits for the stream: the buffers that go out of scope here are idle)
+  *out = c;
+  return RBT_OK;
+}
+int pcloud_d1(std::string& err, const PCloud* a, const PCloud* b, int peak, rbt_d1_result* out) {
+  rbt_frame_score s;
+  const int rc = pcloud_score(err, a, b, peak, RBT_SCORE_D1, &s);
+  *out = s.d1;
+  return rc;
+}
+int gather_luma_host(std::string& err, const uint16_t* src, int n_pics, int stride, int rows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out) {
+  if (n_pics < 1 || w < 1 || h < 1 || x0 < 0 || y0 < 0 || stride < 1 || rows < 1 || x0 + w > stride || y0 + h > rows || stride > 16384 || rows > 16384 || src_misalign < 0 || src_misalign > 7) {
+    err = "the window must lie inside planes of at most 16384 x 16384 samples, src_misalign in 0..7"; return RBT_ERR_PARAM; }
+  const size_t plane = (size_t)stride * rows, in_n = plane * (size_t)n_pics, out_n = (size_t)w * h * (size_t)n_pics, in_bytes = ((in_n + 8) * 2 + 255) & ~(size_t)255;
+  DevBuf buf, desc;
+  if (!buf.alloc(256 + in_bytes + out_n * 2) || !desc.alloc(sizeof(RbtGatherPic) * (size_t)n_pics)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  uint8_t* base = (uint8_t*)(((uintptr_t)buf.p + 255) & ~(uintptr_t)255);
+  uint16_t* d_in = (uint16_t*)base + src_misalign; uint16_t* d_out = (uint16_t*)(base + in_bytes);
+  std::vector<RbtGatherPic> pics((size_t)n_pics);
+  for (int k = 0; k < n_pics; k++) pics[k] = RbtGatherPic{d_in + plane * (size_t)k + (size_t)y0 * stride + x0, d_out + (size_t)w * h * (size_t)k, w, h, stride, 0};
+  if (rbtk::h2d(d_in, src, in_n * 2) | rbtk::h2d(desc.p, pics.data(), sizeof(RbtGatherPic) * (size_t)n_pics) | rbtk::dev_memset(d_out, 0xEE, out_n * 2)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::launch_gather_luma(desc.as<RbtGatherPic>(), n_pics, RBT_GM_PIC_CHUNKS(w, h));
+  if (rbtk::d2h(out, d_out, out_n * 2) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  return RBT_OK;
+}
+
 // The cloud keeps the normals it had until the new ones are complete: they are written to a buffer of their own, which replaces the old one after the kernels have run.
 int pcloud_estimate_normals(std::string& err, PCloud* c, int k, int orient, const int32_t view_point[3], int16_t* out, double* device_ms) {
   const size_t n = (size_t)c->n, slots = (size_t)1 << c->lg;

@@ -31,4 +31,18 @@ void pcloud_cache_trim(PCloudCache& cache);
 // normals of the merged cloud (csrc/rbt_normals.h); k, orient and view_point are checked by the caller. out (3 per point) and device_ms may be null
 int pcloud_estimate_normals(std::string& err, PCloud* c, int k, int orient, const int32_t view_point[3], int16_t* out, double* device_ms);
 int pcloud_score(std::string& err, const PCloud* a, const PCloud* b, int peak, int parts, rbt_frame_score* out);
+// Positions-only reconstruction from packed luma planes that are on the device already (rbt_submit_gof_d1), next to reconstruct_impl, which uploads host arrays. What of a
+// frame does not depend on the trial encode - patches, items, occupancy map, block-to-patch map - is made once (MapFrame, from the occupancy luma d_occ, which has to stay
+// alive as long as the frame); per trial the count, scan, emit, smoothing and index remain (mapframe_cloud: an indexed cloud without colours). Everything is enqueued on the
+// current stream (rbtk::set_stream) and waits on that stream alone.
+struct MapFrame;
+int mapframe_check(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, std::vector<uint32_t>* items = nullptr);   // host only: what rbt_reconstruct refuses
+int mapframe_new(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* d_occ, MapFrame** out);
+void mapframe_delete(MapFrame* f);
+size_t mapframe_bytes(const rbt_atlas_params* a, int n_patches);         // device memory of a MapFrame, but for its items (bounded by the atlas' blocks per patch list)
+int mapframe_cloud(std::string& err, PCloudCache& cache, const MapFrame* f, const uint16_t* d_d0, const uint16_t* d_d1, int geo_bd, PCloud** out, int* n_smoothed);
+// the D1 part of pcloud_score: out is what rbt_d1 returns for the two clouds
+int pcloud_d1(std::string& err, const PCloud* a, const PCloud* b, int peak, rbt_d1_result* out);
+// rbt_gather_luma: the gather kernel (csrc/rbt_cloudmaps.h) on host arrays
+int gather_luma_host(std::string& err, const uint16_t* src, int n_pics, int stride, int rows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out);
 }

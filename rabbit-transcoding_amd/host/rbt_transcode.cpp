@@ -11,6 +11,9 @@
 #include "rbt_transcode.h"
 #include "rbt_rate_walk.h"
 #include "rbt_quality_walk.h"
+#include "rbt_d1_walk.h"
+#include "rbt_pcc.h"
+#include "../csrc/rbt_cloudmaps.h"
 
 namespace rbt {
 
@@ -429,7 +432,8 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
 // underneath the previous GOF's reconstruction and re-encode.
 // Targets - a byte budget or a PSNR floor per entry -: what a pipeline with such an entry keeps between the rounds of its trial encodes (run_rounds, launch_round, finish_round)
 struct RoundCand { int q, qp, walk; };         // entry q of the group at qp; walk: index of its walk, -1 for a constant-QP entry of the pipeline
-struct TargetWalk : QpWalk<QualityTried> { RateGoal budget; QualityGoal floor; };   // toward < 0: a budget, toward > 0: a floor
+struct TargetTried : QualityTried { std::vector<rbt_d1_result> d1; };      // d1: a job with D1 floors, the frames of the trial
+struct TargetWalk : QpWalk<TargetTried> { RateGoal budget; QualityGoal floor; D1Goal dist; bool is_d1 = false; };   // toward < 0: a budget, toward > 0: a floor - on the PSNR, or (is_d1) on D1
 // Quality floors: the occupancy source of an entry (include/rbt.h, "transcoding to a PSNR floor", rule 3), kept in the job because the pipelines that use it are encoded in
 // the wait half: the pooled luma planes of the occupancy stream, and for occupancy_rd the per-4x4-unit maps made of them (both live in GofJob::pooled until the job goes)
 struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
@@ -438,8 +442,18 @@ struct RoundPipe {
   std::vector<RoundCand> cands;                // the round to run (eb == nullptr) or running
   std::unique_ptr<EncodeBatch> eb; std::unique_ptr<SseSet> sse;   // the round in flight on the pipeline's stream; sse: a round of a job with floors carries distortion sums
   std::vector<std::vector<uint8_t>> o1; std::vector<QualitySums> sums;   // the pipeline's streams in group order, as they settle, and (floors) their sums
+  std::vector<std::vector<rbt_d1_result>> d1;  // (D1 floors) the frames of the constant-QP entries with a target, in group order
   bool done = false;
 };
+// D1 floors: the target of one entry (n_frames 0: none) as the job keeps it, and what its clouds are rebuilt from. The decoded input of the occupancy source (in_*: the
+// pipeline and decoded stream that hold it, its displayed size) is what the reference clouds of frames without a handle are made of; the trials' clouds use the pooled
+// planes (GofJob::qocc). frames / own_ref live while run_rounds runs (D1Live).
+struct D1Entry {
+  rbt_d1_target t; std::vector<std::vector<rbt_patch>> patches; std::vector<const PCloud*> ref;
+  int in_pipe = -1, in_ds = -1, in_ow = 0, in_oh = 0;
+  std::vector<MapFrame*> frames; std::vector<PCloud*> own_ref; double cloud_ms = 0;
+};
+struct D1Out { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<rbt_d1_result> frames; double cloud_ms = 0; };
 struct GofJob {
   int n = 0, slot = 0, ng = 0, rc = 0;
   std::vector<std::vector<int>> groups; std::vector<int> order;
@@ -461,6 +475,9 @@ struct GofJob {
   // quality floors (rbt_submit_gof_quality): every pipeline with a geometry / attribute entry is decoded at submit and encoded in the wait half (run_rounds); it is marked
   // in rate_pipe like a pipeline with a rate target, which keeps it unchained
   std::vector<rbt_quality_target> qtargets; std::vector<QualityOcc> qocc; std::vector<rbt_quality_result> qresults; bool refused = false;
+  // D1 floors (rbt_submit_gof_d1): the job runs as a job with quality floors that are all 0 - every geometry / attribute pipeline is encoded in the wait half, the pooled
+  // occupancy planes and the maps of occupancy_rd stay in the job - and d1 holds the targets with their patch lists copied (d1_setup, d1_score, run_rounds)
+  std::vector<D1Entry> d1; std::vector<D1Out> d1out; PCloudCache* cloud_cache = nullptr;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   ~GofJob() { for (void* q : pooled) rbtk::dev_free(q); }
 };
@@ -478,7 +495,10 @@ static void bind_streams(GofJob& j, int depth) {
 }
 
 size_t gof_memory(const GofJob* j) { return j ? j->dev_bytes + j->rate_bytes : 0; }
-bool gof_is_quality(const GofJob* j) { return j && !j->qtargets.empty(); }
+bool gof_is_quality(const GofJob* j) { return j && !j->qtargets.empty() && j->d1.empty(); }
+bool gof_is_d1(const GofJob* j) { return j && !j->d1.empty(); }
+static bool has_d1(const GofJob& j, int i) { return !j.d1.empty() && j.d1[i].t.n_frames > 0; }
+static bool has_d1_floor(const GofJob& j, int i) { return has_d1(j, i) && j.d1[i].t.min_d1_mdb != 0; }
 int gof_refused(const GofJob* j, std::string& err) { if (!j || !j->refused) return 0; err = j->err; return j->rc; }
 static bool has_target(const GofJob& j, int i) { return !j.targets.empty() && j.targets[i].target_bytes != 0; }
 static bool has_floor(const GofJob& j, int i) { return !j.qtargets.empty() && j.qtargets[i].min_psnr_mdb != 0; }
@@ -574,13 +594,18 @@ static int build_decoders(GofJob& j, SubmitPlan& s) {
 
 static int rate_prepare(GofJob& j, int gi);
 static int quality_prepare(GofJob& j, SubmitPlan& s, int gi);
+static int d1_prepare(GofJob& j, SubmitPlan& s, int gi);
 // Encoder batches: the pipelines whose occupancy streams others are coded with first (their pooled planes are what the maps are made of), then the rest
 static int build_encoders(GofJob& j, SubmitPlan& s) {
   for (int pass = 0; pass < 2; pass++) for (int k = 0; k < j.ng; k++) {
     const int gi = j.order[k]; const std::vector<int>& gs = j.groups[gi]; EncodeBatch& eb = j.eb[gi]; rbtk::set_stream(job_stream(j, gi));
     bool feeds = false; for (int i : gs) for (int c = 0; c < j.n; c++) feeds |= s.occ_of[c] == i || s.meas_of[c] == i;
     if (feeds != (pass == 0)) continue;
-    if (j.rate_pipe[gi]) { if (int rc = j.qtargets.empty() ? rate_prepare(j, gi) : quality_prepare(j, s, gi)) return rc; continue; }      // stays unchained: decoder and census now, encoders in the wait half
+    if (j.rate_pipe[gi]) {      // stays unchained: decoder and census now, encoders in the wait half
+      if (int rc = j.qtargets.empty() ? rate_prepare(j, gi) : quality_prepare(j, s, gi)) return rc;
+      if (!j.d1.empty()) if (int rc = d1_prepare(j, s, gi)) return rc;
+      continue;
+    }
     for (size_t q = 0; q < gs.size(); q++) {
       const int i = gs[q], io = s.occ_of[i];
       if (int rc = setup_encode(j.db[gi], j.dec_of[gi][q], (int)q, s.p[i], eb, j.pooled, j.err, &s.pool_jobs[gi], io >= 0 ? &s.occ_src[io] : nullptr, io, &s.occ_jobs)) return rc;
@@ -645,8 +670,23 @@ static void seed_floors(GofJob& j, int gi, RoundPipe& r) {
     r.walks.push_back(std::move(w));
   }
 }
+// A D1 floor's walk is the PSNR floor's with D in place of the PSNR (rbt_d1_walk.h)
+static void seed_d1_floors(GofJob& j, int gi, RoundPipe& r) {
+  const std::vector<int>& gs = j.groups[gi];
+  for (size_t q = 0; q < gs.size(); q++) if (has_d1_floor(j, gs[q])) {
+    const rbt_d1_target& t = j.d1[gs[q]].t;
+    TargetWalk w = new_walk(q, gs[q], t); w.is_d1 = true; w.dist.floor_mdb = t.min_d1_mdb; w.dist.stat = t.stat;
+    d1_seed(w, w.dist, j.params[gs[q]].qp);
+    r.walks.push_back(std::move(w));
+  }
+}
 // true: settled; false: the walk needs the trial at `need` next (alone: a probe, the round brings nothing else for it)
 static bool walk_step(TargetWalk& w, int& need, int& dir, bool& alone) {
+  if (w.is_d1) {
+    alone = !d1_probe(w, w.dist);
+    if (alone) { need = w.dist.q0; dir = 0; return false; }
+    return qp_walk_step(w, d1_holds(w, w.dist), need, dir);
+  }
   alone = w.toward > 0 && !quality_probe(w, w.floor);
   if (alone) { need = w.floor.q0; dir = 0; return false; }
   return w.toward > 0 ? qp_walk_step(w, quality_holds(w, w.floor), need, dir) : qp_walk_step(w, rate_fits(w, w.budget), need, dir);
@@ -716,6 +756,133 @@ static int launch_round(GofJob& j, int gi) {
   encode_launch_entropy_rest(eb);
   return 0;
 }
+// ------------------------------------------------------------------------------------------------ D1 floors (include/rbt.h, "transcoding geometry to a D1 floor")
+// At submit, behind quality_prepare (which has found the pooled planes of every entry's occupancy source): rules 1 and 2 for every entry of the pipeline with a target,
+// where the decoded input of the occupancy source lies, and what the clouds will take (rbt_job_memory)
+static int d1_prepare(GofJob& j, SubmitPlan& s, int gi) {
+  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
+  if (db.frames.empty()) return 0;
+  auto refuse = [&](int i, const std::string& why) { j.err = "entry " + std::to_string(i) + ": " + why; j.refused = true; return RBT_ERR_PARAM; };
+  for (size_t q = 0; q < gs.size(); q++) if (has_d1(j, gs[q])) {
+    const int i = gs[q], io = s.meas_of[i], ds = j.dec_of[gi][q], first = db.stream_first[ds], cnt = db.stream_count[ds];
+    D1Entry& E = j.d1[i]; const rbt_atlas_params& a = E.t.atlas;
+    if (io < 0 || s.occ_src[io].n <= 0) return refuse(i, "a D1 target needs an occupancy source: a pooled occupancy entry (occupancy_precision 4) in front of it");
+    const OccSource& os = s.occ_src[io]; const RbtStreamCfg& c = db.frames[first].cfg; const Sps& isps = db.stream_sps[ds];
+    const int dw = c.w - 2 * isps.conf_win[0] - 2 * isps.conf_win[1], dh = c.h - 2 * isps.conf_win[2] - 2 * isps.conf_win[3];
+    if (dw != a.width || dh != a.height) return refuse(i, "the displayed picture size is not atlas.width x atlas.height");
+    if (cnt != a.map_count * E.t.n_frames) return refuse(i, "the picture count is not atlas.map_count x n_frames");
+    if (os.n != E.t.n_frames) return refuse(i, "the occupancy source does not hold n_frames pictures");
+    if (os.ow * a.occupancy_precision != dw || os.oh * a.occupancy_precision != dh) return refuse(i, "atlas.occupancy_precision is not width / (output occupancy width)");
+    // the decoded input of the occupancy source
+    for (int g = 0; g < j.ng; g++) for (size_t k = 0; k < j.groups[g].size(); k++) if (j.groups[g][k] == io) { E.in_pipe = g; E.in_ds = j.dec_of[g][k]; }
+    if (E.in_pipe < 0 || j.db[E.in_pipe].frames.empty()) return refuse(i, "the occupancy source was not decoded");
+    const DecodeBatch& ob = j.db[E.in_pipe]; const RbtStreamCfg& oc = ob.frames[ob.stream_first[E.in_ds]].cfg; const Sps& osps = ob.stream_sps[E.in_ds];
+    E.in_ow = oc.w - 2 * osps.conf_win[0] - 2 * osps.conf_win[1]; E.in_oh = oc.h - 2 * osps.conf_win[2] - 2 * osps.conf_win[3];
+    if (E.in_ow <= 0 || E.in_oh <= 0 || dw % E.in_ow || dh % E.in_oh || dw / E.in_ow != dh / E.in_oh) return refuse(i, "the input occupancy size does not divide the atlas by one whole factor");
+    // memory: per frame the frame's maps (twice while a reference cloud is made), per frame without a handle a volume, one more for the trial being scored; the packed
+    // planes of one trial and of the decoded input
+    size_t bytes = PCLOUD_VOL_BYTES + 2 * (size_t)cnt * (size_t)dw * dh * 2 + (size_t)E.t.n_frames * (size_t)E.in_ow * E.in_oh * 2;
+    for (int f = 0; f < E.t.n_frames; f++) bytes += 2 * mapframe_bytes(&a, (int)E.patches[f].size()) + (E.ref[f] ? 0 : PCLOUD_VOL_BYTES);
+    j.rate_bytes += bytes;
+  }
+  return 0;
+}
+// the luma planes of pictures as packed planes, one launch (csrc/rbt_cloudmaps.h); the descriptors' host staging stays alive in `keep`
+struct GatherSet {
+  std::vector<RbtGatherPic> pics; void* d = nullptr; int max_chunks = 0;
+  ~GatherSet() { rbtk::dev_free(d); }
+  void add(const uint16_t* src, int stride, int w, int h, uint16_t* dst) { pics.push_back(RbtGatherPic{src, dst, w, h, stride, 0}); max_chunks = std::max(max_chunks, RBT_GM_PIC_CHUNKS(w, h)); }
+  int launch() {
+    d = rbtk::dev_alloc(pics.size() * sizeof(RbtGatherPic));
+    if (!d) return RBT_ERR_NOMEM;
+    if (rbtk::h2d(d, pics.data(), pics.size() * sizeof(RbtGatherPic))) return RBT_ERR_NO_DEVICE;
+    rbtk::launch_gather_luma((const RbtGatherPic*)d, (int)pics.size(), max_chunks);
+    return 0;
+  }
+};
+struct DevPlanes { uint16_t* p = nullptr; ~DevPlanes() { rbtk::dev_free(p); } bool alloc(size_t samples) { p = (uint16_t*)rbtk::dev_alloc(samples * 2); return p != nullptr; } };
+// the device time of one cloud's work, between the events of T_CENSUS on the pipeline's stream (no census runs in a job with floors)
+static int d1_timed(GofJob& j, D1Entry& E, int rc) {
+  rbtk::timer_end(T_CENSUS);
+  if (rc) return rc;
+  if (rbtk::dev_sync()) { j.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  E.cloud_ms += rbtk::timer_ms(T_CENSUS);
+  return 0;
+}
+// In the wait half, once the pipeline's decoder has been collected (the occupancy pipelines were collected before it, gof_wait): per entry with a target and per frame
+// what does not depend on the QP - the maps of the frame from the pooled occupancy plane (MapFrame) and, for a frame without a handle, the reference cloud from the decoded
+// input. On the pipeline's stream; waits are on that stream.
+static int d1_setup(GofJob& j, int gi) {
+  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi]; PCloudCache& cache = *j.cloud_cache;
+  rbtk::set_stream(job_stream(j, gi));
+  for (size_t q = 0; q < gs.size(); q++) if (has_d1(j, gs[q])) {
+    const int i = gs[q], ds = j.dec_of[gi][q], first = db.stream_first[ds], nf = j.d1[i].t.n_frames;
+    D1Entry& E = j.d1[i]; const rbt_atlas_params& a = E.t.atlas; const QualityOcc& o = j.qocc[i]; const int W = a.width, H = a.height, mc = a.map_count;
+    if (!o.occ) { j.err = "internal: no occupancy source"; return RBT_ERR_PARAM; }
+    E.frames.assign(nf, nullptr); E.own_ref.assign(nf, nullptr);
+    for (int f = 0; f < nf; f++) if (int rc = mapframe_new(j.err, &a, E.patches[f].data(), (int)E.patches[f].size(), o.occ + o.in_step * (size_t)f, &E.frames[f])) return rc;
+    bool any = false; for (int f = 0; f < nf; f++) any |= E.ref[f] == nullptr;
+    if (!any) continue;
+    // the decoded input seen through its conformance windows, packed: occupancy luma and geometry luma of the frames without a handle
+    const DecodeBatch& ob = j.db[E.in_pipe]; const int ofirst = ob.stream_first[E.in_ds]; const RbtStreamCfg& oc = ob.frames[ofirst].cfg; const Sps& osps = ob.stream_sps[E.in_ds];
+    const RbtStreamCfg& c = db.frames[first].cfg; const Sps& isps = db.stream_sps[ds];
+    const size_t ys = (size_t)W * H, os = (size_t)E.in_ow * E.in_oh;
+    DevPlanes geo, occ; GatherSet gs_in;
+    if (!geo.alloc(ys * (size_t)mc * nf) || !occ.alloc(os * (size_t)nf)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    rbtk::timer_begin(T_CENSUS);
+    for (int f = 0; f < nf; f++) if (!E.ref[f]) {
+      gs_in.add((const uint16_t*)ob.frames[ofirst + f].out[0] + (size_t)(2 * osps.conf_win[2]) * oc.w + 2 * osps.conf_win[0], oc.w, E.in_ow, E.in_oh, occ.p + os * (size_t)f);
+      for (int m = 0; m < mc; m++) gs_in.add((const uint16_t*)db.frames[first + mc * f + m].out[0] + (size_t)(2 * isps.conf_win[2]) * c.w + 2 * isps.conf_win[0], c.w, W, H, geo.p + ys * (size_t)(mc * f + m));
+    }
+    int rc = gs_in.launch();
+    if (rc) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+    rbt_atlas_params ain = a; ain.occupancy_precision = W / E.in_ow;
+    for (int f = 0; f < nf && !rc; f++) if (!E.ref[f]) {
+      MapFrame* F = nullptr;
+      rc = mapframe_new(j.err, &ain, E.patches[f].data(), (int)E.patches[f].size(), occ.p + os * (size_t)f, &F);
+      if (!rc) rc = mapframe_cloud(j.err, cache, F, geo.p + ys * (size_t)(mc * f), mc > 1 ? geo.p + ys * (size_t)(mc * f + 1) : nullptr, c.bit_depth, &E.own_ref[f], nullptr);
+      if (rbtk::dev_sync() && !rc) { j.err = "kernel execution failed"; rc = RBT_ERR_NO_DEVICE; }      // F's buffers are idle before they go
+      mapframe_delete(F);
+    }
+    if (int bad = d1_timed(j, E, rc)) return bad;
+  }
+  return 0;
+}
+// what d1_setup made, released on every way out of run_rounds (the clouds' volumes go back to the context's cache)
+struct D1Live {
+  GofJob& j; int gi;
+  ~D1Live() {
+    if (j.d1.empty()) return;
+    rbtk::set_stream(job_stream(j, gi)); rbtk::dev_sync();
+    for (int i : j.groups[gi]) { D1Entry& E = j.d1[i];
+      for (MapFrame* F : E.frames) mapframe_delete(F);
+      for (PCloud* c : E.own_ref) pcloud_release(*j.cloud_cache, c);
+      E.frames.clear(); E.own_ref.clear(); }
+  }
+};
+// The clouds of candidate e of the round in flight - stream `q` of the pipeline's group at one QP - against the entry's references: the luma of the encoder's
+// reconstructions (the displayed window starts at the picture's origin: make_param_sets pads at the right and at the bottom) is gathered into packed planes by one launch,
+// then frame after frame: cloud, index, search, release (one recycled volume). The round's encode has been waited for (encode_finish).
+static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, std::vector<rbt_d1_result>& out) {
+  const int i = j.groups[gi][q]; D1Entry& E = j.d1[i]; const rbt_atlas_params& a = E.t.atlas; PCloudCache& cache = *j.cloud_cache;
+  const EncStreamDesc& d = eb.desc[e]; const int W = a.width, H = a.height, mc = a.map_count, nf = E.t.n_frames, peak = E.t.peak ? E.t.peak : 1023;
+  const size_t ys = (size_t)W * H;
+  if (d.w != W || d.h != H || d.n_frames != mc * nf || (int)E.frames.size() != nf) { j.err = "internal: a D1 target does not fit its stream"; return RBT_ERR_PARAM; }
+  DevPlanes geo; GatherSet gs;
+  if (!geo.alloc(ys * (size_t)d.n_frames)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  out.assign(nf, rbt_d1_result());
+  rbtk::timer_begin(T_CENSUS);
+  for (int k = 0; k < d.n_frames; k++) { const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k]; gs.add(f.out[0], f.cfg.w, W, H, geo.p + ys * (size_t)k); }
+  int rc = gs.launch();
+  if (rc) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+  for (int f = 0; f < nf && !rc; f++) {
+    PCloud* c = nullptr;
+    rc = mapframe_cloud(j.err, cache, E.frames[f], geo.p + ys * (size_t)(mc * f), mc > 1 ? geo.p + ys * (size_t)(mc * f + 1) : nullptr, d.bd, &c, nullptr);
+    if (!rc) rc = pcloud_d1(j.err, E.ref[f] ? E.ref[f] : E.own_ref[f], c, peak, &out[f]);
+    pcloud_release(cache, c);
+  }
+  return d1_timed(j, E, rc);
+}
 static int finish_round(GofJob& j, int gi) {
   RoundPipe& r = j.pipes[gi]; std::vector<std::vector<uint8_t>> outs;
   rbtk::set_stream(job_stream(j, gi));
@@ -724,8 +891,10 @@ static int finish_round(GofJob& j, int gi) {
   for (size_t e = 0; e < r.cands.size(); e++) {
     const EncStreamDesc& d = r.eb->desc[e]; const RoundCand& c = r.cands[e]; QualitySums sums;
     for (int k = 0; r.sse && k < d.n_frames; k++, at++) quality_add_picture(sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
-    if (c.walk < 0) { r.o1[c.q].swap(outs[e]); r.sums[c.q] = sums; }
-    else { QualityTried& t = r.walks[c.walk].tried[c.qp]; t.stream.swap(outs[e]); t.sums = sums; r.n_enc[c.walk]++; }
+    std::vector<rbt_d1_result> frames;                                // a D1 target: the candidate's clouds, from its reconstruction while the round's arena is alive
+    if (has_d1(j, j.groups[gi][c.q])) if (int rc = d1_score(j, gi, c.q, *r.eb, e, frames)) return rc;
+    if (c.walk < 0) { r.o1[c.q].swap(outs[e]); r.sums[c.q] = sums; r.d1[c.q].swap(frames); }
+    else { TargetTried& t = r.walks[c.walk].tried[c.qp]; t.stream.swap(outs[e]); t.sums = sums; t.d1.swap(frames); r.n_enc[c.walk]++; }
   }
   r.eb.reset(); r.sse.reset();
   name_round(j, gi, r, false);
@@ -764,8 +933,19 @@ static void fill_results(GofJob& j, int gi) {
   for (size_t k = 0; k < r.walks.size(); k++) {
     const TargetWalk& w = r.walks[k]; const QualityTried& t = w.tried.find(w.qstar)->second;
     if (w.toward < 0) j.results[w.entry] = rbt_rate_result{w.qstar, w.start, w.met, r.n_enc[k], (uint64_t)t.stream.size(), w.budget.e_qe};
-    else quality_fill_result(j.qresults[w.entry], w.qstar, w.floor.q0, w.start, w.met, r.n_enc[k], t.stream.size(), t.sums, w.floor.bit_depth);
+    else if (!w.is_d1) quality_fill_result(j.qresults[w.entry], w.qstar, w.floor.q0, w.start, w.met, r.n_enc[k], t.stream.size(), t.sums, w.floor.bit_depth);
   }
+  // D1 floors: the frames at q*, or at the entry's own QP
+  if (!j.d1.empty()) j.d1out.resize(j.n);
+  for (size_t q = 0; q < gs.size() && !j.d1.empty(); q++) if (has_d1(j, gs[q]) && !has_d1_floor(j, gs[q])) {
+    D1Out& o = j.d1out[gs[q]]; const int qp = j.params[gs[q]].qp;
+    o.qp = o.q0 = o.qs = qp; o.met = 1; o.n_enc = 1; o.bytes = r.o1[q].size(); o.frames = r.d1[q];
+  }
+  for (size_t k = 0; k < r.walks.size(); k++) if (r.walks[k].is_d1) {
+    const TargetWalk& w = r.walks[k]; const TargetTried& t = w.tried.find(w.qstar)->second; D1Out& o = j.d1out[w.entry];
+    o.qp = w.qstar; o.q0 = w.dist.q0; o.qs = w.start; o.met = w.met; o.n_enc = r.n_enc[k]; o.bytes = t.stream.size(); o.frames = t.d1;
+  }
+  for (size_t q = 0; q < gs.size() && !j.d1.empty(); q++) if (has_d1(j, gs[q])) j.d1out[gs[q]].cloud_ms = j.d1[gs[q]].cloud_ms;
 }
 // A pipeline with targets, in the wait half: its decoder is collected, the walks are seeded and the rounds run, one after the other, until every walk has settled. In a
 // job with floors the occupancy pipelines have been collected by then (gof_wait), so the pooled planes and the maps the rounds read are complete. (Measured and not
@@ -774,9 +954,11 @@ static void fill_results(GofJob& j, int gi) {
 static int run_rounds(GofJob& j, int gi) {
   RoundPipe& r = j.pipes[gi]; const size_t n = j.groups[gi].size();
   if (int rc = pipeline_decoded(j, gi)) return rc;
-  if (!j.qtargets.empty()) seed_floors(j, gi, r);
+  D1Live d1_live{j, gi};                                            // (releases the pipeline's frames and reference clouds on every way out)
+  if (!j.d1.empty()) { seed_d1_floors(j, gi, r); if (int rc = d1_setup(j, gi)) return rc; }
+  else if (!j.qtargets.empty()) seed_floors(j, gi, r);
   else if (int rc = seed_budgets(j, gi, r, true)) return rc;
-  r.o1.assign(n, {}); r.sums.assign(n, QualitySums()); r.n_enc.assign(r.walks.size(), 0);
+  r.o1.assign(n, {}); r.sums.assign(n, QualitySums()); r.d1.assign(n, {}); r.n_enc.assign(r.walks.size(), 0);
   name_round(j, gi, r, true);
   for (;;) {
     if (int rc = launch_round(j, gi)) return rc;
@@ -976,13 +1158,23 @@ static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
 
 // Phase A of a job: plan, build and upload everything, then enqueue. Every upload of the job is issued before its first kernel: a copy from pageable memory blocks the host
 // until the stream has reached it, and pipelines may share a stream. The first failure ends the submission (j.rc, j.err); gof_wait drains what was enqueued.
-GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality) {
+GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
+                   const D1Request* d1) {
   GofJob* J = new GofJob(); GofJob& j = *J;
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
   j.params.assign(p, p + n); j.n_in.assign(n_in, n_in + n);
   if (targets) j.targets.assign(targets, targets + n);
   if (quality) { j.qtargets.assign(quality, quality + n); j.qocc.assign(n, QualityOcc()); }
+  if (d1) {      // a job with quality floors of 0, and the D1 targets with their patch lists copied
+    j.qtargets.assign(n, rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, RBT_QUALITY_ALL, 0, 0}); j.qocc.assign(n, QualityOcc());
+    j.d1.resize(n); j.cloud_cache = d1->cache;
+    for (int i = 0; i < n; i++) {
+      D1Entry& E = j.d1[i]; E.t = d1->targets[i]; E.ref = d1->refs[i];
+      for (int f = 0; f < E.t.n_frames; f++) E.patches.emplace_back(E.t.patches[f], E.t.patches[f] + E.t.n_patches[f]);
+      E.t.patches = nullptr; E.t.n_patches = nullptr; E.t.reference = nullptr;      // (the caller's arrays may go when submit returns)
+    }
+  }
   SubmitPlan s; s.in = in; s.p = p; s.gof_rule = gof_rule;
   int rc = plan_pipelines(j, s, depth);
   j.t_gpu = now_ms();
@@ -996,12 +1188,12 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
 }
 
 // phase B, shortest pipeline first: one sync per stream, then slice sizes -> pack -> NAL assembly. Consumes the job.
-int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* qresults, int* n_flat) {
+int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* qresults, int* n_flat, rbt_d1_floor_result* d1results) {
   std::unique_ptr<GofJob> guard(J); GofJob& j = *J;
   const int n = j.n, ng = j.ng; int rc = j.rc;
   rbt_stats& st = j.st; std::string& err = j.err;
   std::vector<DecodeBatch>& db = j.db; std::vector<EncodeBatch>& eb = j.eb; const rbt_stream_params* p = j.params.data();
-  for (int i = 0; i < n; i++) { out[i] = nullptr; n_out[i] = 0; }
+  for (int i = 0; i < n; i++) { out[i] = nullptr; n_out[i] = 0; if (d1results) memset(&d1results[i], 0, sizeof(d1results[i])); }
   std::vector<std::vector<uint8_t>> outs(n);
   // a job with quality floors: the pipelines that were encoded at submit first - its occupancy pipelines, whose pooled planes and maps the others' rounds read -, then those
   // that are encoded here; every other job has one pass
@@ -1035,6 +1227,18 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
     if (quality && !j.is_pass[i] && p[i].video_type != RBT_VIDEO_OCCUPANCY && i < (int)j.qresults.size()) { qresults[i] = j.qresults[i]; continue; }
     quality_fill_result(qresults[i], p[i].qp, p[i].qp, p[i].qp, 1, j.is_pass[i] ? 0 : 1, (uint64_t)n_out[i], QualitySums(), 8);
   }
+  if (d1results && !rc) for (int i = 0; i < n; i++) {
+    rbt_d1_floor_result& o = d1results[i]; memset(&o, 0, sizeof(o));
+    o.qp = o.qp_probe = o.qp_start = p[i].qp; o.met = 1; o.n_encodes = j.is_pass[i] ? 0 : 1; o.bytes = (uint64_t)n_out[i];
+    if (!has_d1(j, i) || i >= (int)j.d1out.size()) continue;
+    const D1Out& r = j.d1out[i];
+    o.qp = r.qp; o.qp_probe = r.q0; o.qp_start = r.qs; o.met = r.met; o.n_encodes = r.n_enc; o.bytes = r.bytes; o.cloud_ms = r.cloud_ms; o.n_frames = (int)r.frames.size();
+    d1_stats(r.frames.data(), o.n_frames, &o.mean_d1, &o.min_d1);
+    o.frames = (rbt_d1_result*)malloc(sizeof(rbt_d1_result) * r.frames.size());
+    if (!o.frames) { rc = RBT_ERR_NOMEM; break; }
+    memcpy(o.frames, r.frames.data(), sizeof(rbt_d1_result) * r.frames.size());
+  }
+  if (d1results && rc) { for (int i = 0; i < n; i++) { free(d1results[i].frames); memset(&d1results[i], 0, sizeof(d1results[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; } }
   // SURVEY.md 8(d) algorithmic traffic: per coded picture of S samples (2 bytes each): decode writes S, P pictures read
   // their reference once; encode reads the source S, writes the reconstruction S (I) and reads the reference (P)
   uint64_t bytes = 0;

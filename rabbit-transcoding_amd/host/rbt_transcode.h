@@ -1,6 +1,7 @@
 // Encode half + the transcode pipeline (decode -> pool -> encode). See rbt_transcode.cpp.
 #pragma once
 #include <string>
+#include <vector>
 #include "../../include/rbt.h"
 namespace rbt {
 int transcode_gof(rbt_stats& st, std::string& err, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, uint8_t** out, size_t* n_out);
@@ -8,9 +9,16 @@ struct GofJob;
 // gof_rule: apply transcodeData's rule (PCCTranscoder.cpp:150): an occupancy stream is only transcoded when occupancyPrecision == 4
 // targets: nullptr, or one per entry (checked by the caller: rbt_submit_gof_rate); results: nullptr, or one per entry
 // quality: nullptr, or one floor per entry (rbt_submit_gof_quality; not together with targets); quality_results: nullptr, or one per entry of such a job
-GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr);
-int gof_wait(GofJob* j, rbt_stats& st, std::string& err, uint8_t** out, size_t* n_out, rbt_rate_result* results = nullptr, rbt_quality_result* quality_results = nullptr, int* n_flat = nullptr);   // consumes the job
+// d1: nullptr, or the D1 targets of rbt_submit_gof_d1 (checked by the caller; not together with targets or quality): one per entry, the reference handles of each entry
+// resolved to the clouds (n_frames of them, nullptr = the cloud of the decoded input), and the context's cache of cloud volumes
+struct PCloud; struct PCloudCache;
+struct D1Request { const rbt_d1_target* targets; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache; };
+GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr,
+                   const D1Request* d1 = nullptr);
+int gof_wait(GofJob* j, rbt_stats& st, std::string& err, uint8_t** out, size_t* n_out, rbt_rate_result* results = nullptr, rbt_quality_result* quality_results = nullptr, int* n_flat = nullptr,
+             rbt_d1_floor_result* d1_results = nullptr);   // consumes the job
 bool gof_is_quality(const GofJob* j);           // a job of rbt_submit_gof_quality
+bool gof_is_d1(const GofJob* j);                // a job of rbt_submit_gof_d1
 int gof_refused(const GofJob* j, std::string& err);   // != 0: the job's plan was refused before anything was built or enqueued (the code; the reason in err)
 void gof_abandon(GofJob* j);
 size_t gof_memory(const GofJob* j);             // device memory the job's build took (its arenas)
