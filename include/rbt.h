@@ -306,7 +306,7 @@ int rbt_picture_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int widt
  * rbt_wait_gof_d1 collects no other job: any other pairing is RBT_ERR_PARAM and the job stays collectable.
  * Memory: the clouds of a round are scored one after the other. A job holds one 128 MB volume per frame without a reference handle (for the whole job), one more for the
  * trial being scored, and three packed planes per frame; rbt_job_memory counts them with the arenas of the first round.
- * Not built: a container-level call (the library does not parse the atlas sub-bitstream, so rbt_transcode_v3c cannot know the patches), a D2 or colour floor, a D1 floor
+ * Not built: a container-level call (the library does not parse the atlas sub-bitstream, so rbt_transcode_v3c cannot know the patches), a D2 floor (a colour floor: rbt_submit_gof_color below), a D1 floor
  * together with a byte budget or a PSNR floor, a floor per frame other than through RBT_D1_MIN. */
 enum { RBT_D1_MIN = 0, RBT_D1_MEAN = 1 };
 typedef struct rbt_d1_target rbt_d1_target;                  /* both defined behind rbt_score_summary, where the types of their fields are known */
@@ -315,9 +315,58 @@ int rbt_submit_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, cons
 int rbt_wait_gof_d1(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results);   /* results: n entries */
 int rbt_transcode_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets,
                          uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results);   /* submit + wait */
+/* ---- transcoding attributes to a colour PSNR floor (csrc/rbt_score.h, csrc/rbt_cloudmaps.h, host/rbt_color_walk.h) ----
+ * "The cheapest attribute stream that keeps the colour PSNR of the decoded cloud within X dB." The luma PSNR of an attribute map is a proxy for what the common test
+ * conditions report: the output occupancy map and the output geometry decide which samples become points and where, the cloud's colour is taken after the 4:2:0 -> 4:4:4
+ * up-conversion and after the attribute transfer that follows geometry smoothing, and the metric merges duplicates and averages tie sets. Here the cloud of every trial
+ * encode is scored on the GPU. Its geometry does not change with the attribute QP, so it is made once per job and frame, behind the geometry pipeline's only encode
+ * (positions before and after smoothing, the moved flags, the index of the final cloud, and against the reference a score pair: rbt_score_pair_create below); per trial
+ * the three planes of every attribute picture are gathered (k_gather_luma, three descriptors a picture), up-converted, fetched per point, transferred, converted to RGB,
+ * and the cloud is recoloured (rbt_pcloud_set_colors' kernels) and scored by the colour walks alone. Only the colour sums come back to the host.
+ *
+ * 1. Sources. A target sits on an attribute entry only. Its occupancy source is the D1 rule's: the nearest pooled occupancy entry in front of it. Its geometry source is
+ *    the nearest geometry entry in front of it that has the same occupancy source; that entry is coded at its own params[i].qp, exactly as rbt_submit_gof codes it,
+ *    occupancy_rd included. A missing source is RBT_ERR_PARAM.
+ * 2. Shapes. The displayed size of the geometry and of the attribute entry equals atlas.width x atlas.height, both hold atlas.map_count x n_frames pictures, the
+ *    attribute bit depth is 8 or 10; the occupancy rules are those of D1 rule 2.
+ * 3. Cloud of a trial. B_f(q) is what rbt_pcloud_from_maps makes of the atlas and the patches of frame f, the output occupancy luma of frame f, the luma of the geometry
+ *    entry's output pictures map_count * f (and + 1), the attribute entry's output pictures map_count * f (and + 1) at qp = q, upsample_filter and attr_transfer.
+ * 4. Reference. A_f is the handle given for frame f; it must carry colours and belong to the same context. Where it is NULL, A_f is the same route on the decoded input
+ *    occupancy, geometry and attribute, with the atlas at the input occupancy's precision.
+ * 5. Score. C_f(q) is the .color part of rbt_score(A_f, B_f(q), peak, RBT_SCORE_COLOR): the integer sums from the colour walks, the float fields from the routine both
+ *    public calls use. D(q) is the minimum over f of (double)psnr[channel] (RBT_D1_MIN), or the sum in frame order in double divided by n_frames (RBT_D1_MEAN).
+ *    meets(q): D(q) >= min_psnr_mdb / 1000.0; +inf meets any floor.
+ * 6. Walk and stream. The PSNR floor's walk, word for word, with D in place of the PSNR (D1 rule 6; n_encodes <= |q* - qs| + 5). The returned stream is byte for byte
+ *    rbt_transcode_gof's at qp = q*. min_psnr_mdb 0: the entry is coded at params[i].qp and its colour results are reported (met = 1, n_encodes = 1). A floor that even
+ *    qp_min misses is no error (met = 0, RBT_OK).
+ * 7. Errors are the D1 section's, applied to this shape: RBT_ERR_PARAM (reason in rbt_last_error; nothing is submitted, the context stays usable) for a wrong struct_size,
+ *    a target on a non-attribute entry, a bad range, an unknown stat, channel or up-sampling filter, a negative floor, n_frames < 1, a missing patch list, a reference
+ *    handle of another context or without colours, rules 1 and 2, an atlas or patch rbt_reconstruct refuses. An empty cloud, a coordinate outside 0..1023 or more than 2^21
+ *    merged points in a cloud fail the job in its wait call (RBT_ERR_PARAM) and the context stays usable. A job of rbt_submit_gof_color is collected by rbt_wait_gof_color
+ *    only, and rbt_wait_gof_color collects no other job: any other pairing is RBT_ERR_PARAM and the job stays collectable.
+ * The patch lists are copied at submit; a reference handle must stay alive, and keep its colours (no rbt_pcloud_set_colors on it), until the job is collected. Entries
+ * without a target carry an empty target (every field but
+ * struct_size zero) and their result carries qp, bytes and zeros.
+ * Memory: a job holds, per frame, one 128 MB volume and one set of maps for B_f, the same for a reference of its own, 8 bytes per point of distances and the packed
+ * geometry planes; per trial the packed attribute planes, their 4:4:4 planes and the two volumes of the attribute transfer. rbt_job_memory counts them with the arenas of
+ * the first round. The volumes go back to the context's cache when the rounds end.
+ * Not built: a container-level call (the library does not parse the atlas sub-bitstream), a colour floor together with a D1 floor, a byte budget or a PSNR floor in one
+ * job, a floor per frame other than through RBT_D1_MIN, batched scoring across frames, transfer neighbour sets kept across trials, colour smoothing. */
+typedef struct rbt_color_target rbt_color_target;             /* both defined behind rbt_d1_floor_result */
+typedef struct rbt_color_floor_result rbt_color_floor_result;
+int rbt_submit_gof_color(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_color_target* targets, rbt_job** job);
+int rbt_wait_gof_color(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_color_floor_result* results);   /* results: n entries */
+int rbt_transcode_gof_color(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_color_target* targets,
+                            uint8_t** annexb_out, size_t* n_out, rbt_color_floor_result* results);   /* submit + wait */
 /* The gather kernel on host arrays (tests): src holds n_pics planes of `stride` x `rows` samples; the w x h window at (x0, y0) of each comes back packed in out
  * (n_pics x w x h). The planes go to the device with their first sample src_misalign (0..7) samples behind a 256-byte boundary, the packed planes start on one. */
 int rbt_gather_luma(rbt_ctx* ctx, const uint16_t* src, int n_pics, int stride, int rows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out);
+/* The same kernel on all three planes of coded 4:2:0 pictures (tests): a picture of src is its luma plane (`stride` x `rows` samples) followed by Cb and Cr (`chroma_stride`
+ * x `chroma_rows` each). The even w x h window at the even offset (x0, y0), and the w/2 x h/2 windows at (x0/2, y0/2) of the chroma planes, come back as packed planar
+ * 4:2:0 pictures - w*h luma samples, then w*h/4 of Cb, then of Cr - which is the layout rbt_yuv420_to_yuv444 reads. One descriptor per plane: a chroma row of 1, 7 or 36
+ * samples is cut into chunks as a luma row is. Misalignment as for rbt_gather_luma. RBT_ERR_PARAM: an odd window or offset, a window outside a plane. */
+int rbt_gather_420(rbt_ctx* ctx, const uint16_t* src, int n_pics, int stride, int rows, int chroma_stride, int chroma_rows, int x0, int y0, int w, int h, int src_misalign,
+                   uint16_t* out);
 
 /* The two halves exposed on their own (SURVEY.md 8(b) alternative seam; used by the parity tests).
  * Picture sizes: any even width / height. Sizes that are not multiples of 8 (all-intra) / 16 (gop 2) are coded padded with a
@@ -604,6 +653,25 @@ typedef struct {
 /* a: the source (D2 needs its normals), b: the decoded cloud. parts: RBT_SCORE_* wanted, 0 = all the two clouds allow (out->parts says which); a part the clouds cannot
  * give, or peak < 1, is RBT_ERR_PARAM. */
 int rbt_score(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int parts, rbt_frame_score* out);
+/* New colours for a cloud that is indexed already: rgb holds 3 bytes per point, in the cloud's point order (rbt_pcloud_points: n_points of them). Positions, volume, the
+ * map's keys and lowest point indices stay; the colour sums, counts and merged colours of the index are remade (k_sc_recolor_zero, k_sc_recolor_add, then the merge of
+ * rbt_pcloud_upload). Afterwards the cloud scores exactly as a fresh rbt_pcloud_upload of the same points with the new colours would - every integer and every float
+ * field of every part; D1 and D2 do not change. A cloud uploaded without colours has them afterwards. The 4:4:4 triples a cloud of rbt_pcloud_from_maps keeps are not
+ * touched. RBT_ERR_PARAM: a handle of another context. Score pairs of the cloud stay valid: their distances depend on positions only - and they read the clouds' colours of
+ * the moment they are asked: recolouring a cloud that is the `reference` of a job of rbt_submit_gof_color in flight changes that job's scores, so leave a reference's colours
+ * alone until the job is collected. */
+int rbt_pcloud_set_colors(rbt_ctx* ctx, rbt_pcloud* cloud, const uint8_t* rgb);
+/* A score pair keeps what of rbt_score(a, b) depends on positions only: the nearest squared distance of every merged point, both directions (8 bytes per point of the two
+ * clouds; the two searches of rbt_score run once, at create). rbt_score_pair_color runs the colour walks alone on the stored distances (k_sc_color_walk: the tie sets, the
+ * averaged tie colour and the error terms of rbt_score, integer sums, one 64-bit atomic per workgroup and sum) with the colours the two clouds have at that moment: out is
+ * the .color part of rbt_score(a, b, peak, RBT_SCORE_COLOR), bit for bit, before and after rbt_pcloud_set_colors on either cloud. Where a sequence of candidates differs in
+ * colour only - the trial encodes of an attribute stream over one geometry - this is the score without the searches, which are most of rbt_score's time.
+ * RBT_ERR_PARAM: a handle of another context; at rbt_score_pair_color a cloud without colours, more than 2^21 merged points in a cloud, or a pair one of whose clouds has
+ * been released (the pair itself is still released by rbt_score_pair_release; rbt_destroy releases the pairs still outstanding). */
+typedef struct rbt_score_pair rbt_score_pair;
+int rbt_score_pair_create(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, rbt_score_pair** out);
+int rbt_score_pair_color(rbt_ctx* ctx, const rbt_score_pair* pair, rbt_color_result* out);
+void rbt_score_pair_release(rbt_ctx* ctx, rbt_score_pair* pair);
 /* Summary over the frames of a sequence, per figure (the symmetric PSNR of D1, D2, Y, U, V): arithmetic mean and minimum, in double, over the frames that carry that part
  * (n_d1 / n_d2 / n_color of them; 0 where there is none); a frame whose PSNR is +inf makes the mean +inf. The reference itself writes one line per frame and averages
  * nothing (PCCMetrics::write); the mean over the frames is what the CTC reporting forms from those lines. points_* / merged_*: sums over all frames. Host only. */
@@ -636,6 +704,32 @@ struct rbt_d1_floor_result {
   double cloud_ms;                              /* time between events on the pipeline's stream around the gather, the reconstruction, the index and the search of every cloud
                                                  * of the job's rounds for this entry, the reference clouds included: the kernels and the gaps in which the stream waits for the
                                                  * host's read-backs of counts and its launches (the clear of a released volume is outside) */
+};
+
+/* The target and the result of a transcode to a colour PSNR floor ("transcoding attributes to a colour PSNR floor" above). */
+struct rbt_color_target {
+  uint32_t struct_size;                  /* sizeof(rbt_color_target): checked */
+  int32_t  min_psnr_mdb;                 /* floor on D, 1/1000 dB; 0 = none: coded at params[i].qp, the colour results reported */
+  int      channel;                      /* 0 Y (the default), 1 U, 2 V: the channel of the symmetric colour PSNR the floor is on */
+  int      stat;                         /* RBT_D1_MIN (the default): the floor is on the worst frame; RBT_D1_MEAN: on the mean over the frames */
+  int      qp_min, qp_max;               /* the walk's range; qp_max 0 = 51 */
+  int      n_frames;                     /* point-cloud frames of the entry; 0 in an empty target */
+  rbt_atlas_params atlas;                /* the OUTPUT atlas: occupancy_precision is that of the output occupancy video */
+  const rbt_patch* const* patches;       /* n_frames lists (a NULL list only with a count of 0) ... */
+  const int* n_patches;                  /* ... and their lengths; copied at submit */
+  int      upsample_filter;              /* RBT_UPSAMPLE_F0 or RBT_UPSAMPLE_REPLICATE, as rbt_pcloud_from_maps takes it */
+  int      attr_transfer;                /* 0 or 1, as rbt_pcloud_from_maps takes it */
+  const rbt_pcloud* const* reference;    /* NULL, or n_frames handles: A_f; a NULL handle = the cloud of the decoded input */
+};
+struct rbt_color_floor_result {
+  int qp, qp_probe, qp_start, met, n_encodes;   /* q*, q0, qs, met, distinct QPs encoded */
+  uint64_t bytes;                               /* size of the returned stream */
+  double mean_psnr[3], min_psnr[3];             /* Y, U, V over the frames at q*: the sum of (double)psnr[c] in frame order / n_frames, and the minimum */
+  int n_frames;                                 /* 0 for an entry without a target */
+  rbt_color_result* frames;                     /* n_frames results at q* (malloc'd, rbt_free; NULL for an entry without a target) */
+  double cloud_ms;                              /* time between events on the pipelines' streams around the work on the clouds: the geometry half and the references once,
+                                                 * then per trial gather, up-conversion, fetch, transfer, RGB, recolour and colour walks, with the gaps in which the stream
+                                                 * waits for the host */
 };
 
 /* ---- normal estimation (csrc/rbt_normals.h) ----

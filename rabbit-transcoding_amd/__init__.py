@@ -178,6 +178,39 @@ class D1FloorResult(C.Structure):
                 ("n_frames", C.c_int), ("frames", C.POINTER(D1Result)), ("cloud_ms", C.c_double)]
 
 
+class ColorTarget(C.Structure):
+    """rbt_color_target; struct_size is filled in. ColorTarget() is the empty target of an entry without one. patches: one list of Patch per point-cloud frame; reference:
+    None, or one PCloud with colours (or None = the cloud of the decoded input) per frame. The object keeps the arrays it points to alive."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_psnr_mdb", C.c_int32), ("channel", C.c_int), ("stat", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("n_frames", C.c_int),
+                ("atlas", AtlasParams), ("patches", C.POINTER(C.POINTER(Patch))), ("n_patches", C.POINTER(C.c_int)), ("upsample_filter", C.c_int), ("attr_transfer", C.c_int),
+                ("reference", C.POINTER(C.c_void_p))]
+
+    def __init__(self, atlas=None, patches=None, min_psnr_mdb=0, channel=0, stat=RBT_D1_MIN, qp_min=0, qp_max=0, upsample_filter=0, attr_transfer=1, reference=None):
+        super().__init__(C.sizeof(ColorTarget))
+        self._keep = []
+        if atlas is None:
+            return
+        self.min_psnr_mdb, self.channel, self.stat, self.qp_min, self.qp_max, self.upsample_filter, self.attr_transfer = min_psnr_mdb, channel, stat, qp_min, qp_max, upsample_filter, attr_transfer
+        self.atlas = AtlasParams(*[getattr(atlas, n) for n, _ in AtlasParams._fields_])
+        self.n_frames = len(patches)
+        lists = [(Patch * max(1, len(p)))(*p) for p in patches]
+        ptrs = (C.POINTER(Patch) * max(1, len(lists)))(*[C.cast(a, C.POINTER(Patch)) for a in lists])
+        counts = (C.c_int * max(1, len(lists)))(*[len(p) for p in patches])
+        self.patches, self.n_patches = ptrs, counts
+        self._keep += [lists, ptrs, counts]
+        if reference is not None:
+            refs = (C.c_void_p * max(1, len(reference)))(*[None if r is None else (r.h.value if isinstance(r, PCloud) else r) for r in reference])
+            self.reference = refs
+            self._keep += [refs, list(reference)]
+
+
+class ColorFloorResult(C.Structure):
+    """rbt_color_floor_result: q*, the probe q0, the walk's start qs, met, distinct QPs encoded, the stream's size, mean and minimum colour PSNR (Y, U, V) over the frames,
+    the frames' ColorResult (freed by the binding), device milliseconds of the clouds"""
+    _fields_ = [("qp", C.c_int), ("qp_probe", C.c_int), ("qp_start", C.c_int), ("met", C.c_int), ("n_encodes", C.c_int), ("bytes", C.c_uint64), ("mean_psnr", C.c_double * 3),
+                ("min_psnr", C.c_double * 3), ("n_frames", C.c_int), ("frames", C.POINTER(ColorResult)), ("cloud_ms", C.c_double)]
+
+
 class RateTable(C.Structure):
     """rbt_rate_table"""
     _fields_ = [("n_pictures", C.c_int), ("hist", C.POINTER(C.c_uint32)), ("picture_bytes", C.POINTER(C.c_uint64)), ("estimate", C.c_uint64 * 52), ("census_ms", C.c_double)]
@@ -265,6 +298,16 @@ def load(path=None):
     L.rbt_transcode_gof_d1.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                        C.POINTER(D1FloorResult)]
     L.rbt_gather_luma.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]
+    L.rbt_submit_gof_color.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(ColorTarget), C.POINTER(C.c_void_p)]
+    L.rbt_wait_gof_color.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(ColorFloorResult)]
+    L.rbt_transcode_gof_color.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(ColorTarget), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                          C.POINTER(ColorFloorResult)]
+    L.rbt_gather_420.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]
+    L.rbt_pcloud_set_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rbt_score_pair_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.rbt_score_pair_color.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ColorResult)]
+    L.rbt_score_pair_release.argtypes = [C.c_void_p, C.c_void_p]
+    L.rbt_score_pair_release.restype = None
     L.rbt_picture_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.rbt_transcode_v3c_quality.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(QualityResult))]
     L.rbt_level_census.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -408,9 +451,36 @@ class PCloud:
         self.ctx._chk(self.ctx.L.rbt_pcloud_estimate_normals(self.ctx.h, self.h, None if params is None else C.byref(params), None if out is None else out.ctypes.data, C.byref(ms)))
         return out, ms.value
 
+    def set_colors(self, rgb):
+        """rbt_pcloud_set_colors: new colours (uint8 [n,3], one per point in point order) for the indexed cloud; positions and the index's keys stay"""
+        c = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if c.shape != (self.points()[0], 3):
+            raise ValueError("one colour per point")
+        self.ctx._chk(self.ctx.L.rbt_pcloud_set_colors(self.ctx.h, self.h, c.ctypes.data))
+
     def release(self):
         if self.h:
             self.ctx.L.rbt_pcloud_release(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+class ScorePair:
+    """rbt_score_pair: the nearest squared distances between two PClouds, both directions, kept on the device; color() is the colour part of Context.score for the
+    colours the clouds have at that moment. The clouds must outlive the pair."""
+
+    def __init__(self, ctx, a, b):
+        self.ctx, self.h = ctx, C.c_void_p()
+        ctx._chk(ctx.L.rbt_score_pair_create(ctx.h, a.h if a is not None else None, b.h if b is not None else None, C.byref(self.h)))
+
+    def color(self):
+        """rbt_score_pair_color -> dict as Context.color_metric returns it"""
+        r = ColorResult()
+        self.ctx._chk(self.ctx.L.rbt_score_pair_color(self.ctx.h, self.h, C.byref(r)))
+        return {n: (getattr(r, n) if n in ("n_a", "n_b") else list(getattr(r, n))) for n, _ in ColorResult._fields_}
+
+    def release(self):
+        if self.h:
+            self.ctx.L.rbt_score_pair_release(self.ctx.h, self.h)
             self.h = C.c_void_p()
 
 
@@ -588,6 +658,30 @@ class Context:
         """rbt_transcode_gof_d1: submit + wait"""
         args = self._gof_args(streams, params, targets, D1Target)
         return self._d1_results(self._collect(self.L.rbt_transcode_gof_d1, args[0], args, D1FloorResult))
+
+    def _color_results(self, res):
+        """([stream bytes, ...], [ColorFloorResult, ...] as dicts): frames becomes a list of colour dicts (Context.color_metric's) and the library's array is released"""
+        outs, rs = res
+        for r in rs:
+            ptr = r["frames"]
+            r["frames"] = [{n: (getattr(ptr[f], n) if n in ("n_a", "n_b") else list(getattr(ptr[f], n))) for n, _ in ColorResult._fields_} for f in range(r["n_frames"])]
+            r["mean_psnr"], r["min_psnr"] = list(r["mean_psnr"]), list(r["min_psnr"])
+            self.L.rbt_free(ptr)
+        return outs, rs
+
+    def submit_gof_color(self, streams, params, targets):
+        """rbt_submit_gof_color: submit_gof with one ColorTarget per entry (ColorTarget() = none; min_psnr_mdb 0 = constant QP, colour results reported); returns a job for
+        wait_gof_color"""
+        return self._submit(self.L.rbt_submit_gof_color, streams, params, targets, ColorTarget)
+
+    def wait_gof_color(self, job):
+        """rbt_wait_gof_color -> ([stream bytes, ...], [result dict, ...])"""
+        return self._color_results(self._collect(self.L.rbt_wait_gof_color, job[1], [job[0]], ColorFloorResult))
+
+    def transcode_gof_color(self, streams, params, targets):
+        """rbt_transcode_gof_color: submit + wait"""
+        args = self._gof_args(streams, params, targets, ColorTarget)
+        return self._color_results(self._collect(self.L.rbt_transcode_gof_color, args[0], args, ColorFloorResult))
 
     def gather_luma(self, src, x0, y0, w, h, src_misalign=0):
         """rbt_gather_luma: planes src ([n, rows, stride] uint16) -> the w x h window at (x0, y0) of each, packed ([n, h, w]); the planes lie src_misalign samples behind
@@ -826,6 +920,21 @@ class Context:
         s = FrameScore()
         self._chk(self.L.rbt_score(self.h, a.h if a is not None else None, b.h if b is not None else None, peak, parts, C.byref(s)))
         return s if raw else frame_score_dict(s)
+
+    def score_pair(self, a, b):
+        """rbt_score_pair_create: a = the source PCloud, b = the decoded one -> ScorePair"""
+        return ScorePair(self, a, b)
+
+    def gather_420(self, src, stride, rows, chroma_stride, chroma_rows, x0, y0, w, h, src_misalign=0):
+        """rbt_gather_420: coded 4:2:0 pictures src ([n, stride*rows + 2*chroma_stride*chroma_rows] uint16: luma plane, Cb, Cr) -> the even w x h window at (x0, y0) of
+        each as packed planar 4:2:0 ([n, w*h*3/2]); the pictures lie src_misalign samples behind a 256-byte boundary on the device"""
+        src = np.ascontiguousarray(src, dtype=np.uint16)
+        n = src.shape[0]
+        if src.ndim != 2 or src.shape[1] != stride * rows + 2 * chroma_stride * chroma_rows:
+            raise ValueError("a picture is its luma plane followed by the two chroma planes")
+        out = np.zeros((n, max(0, w * h * 3 // 2)), np.uint16)
+        self._chk(self.L.rbt_gather_420(self.h, src.ctypes.data, n, stride, rows, chroma_stride, chroma_rows, x0, y0, w, h, src_misalign, out.ctypes.data))
+        return out
 
     def selftest_transform32(self, blocks, bit_depth=10):
         """rbt_selftest_transform32: matrix-core vs vector-ALU 32-point transforms on int16 blocks [n, 1024]; returns the number of differing samples"""

@@ -6,6 +6,8 @@
 //            boundary, chunk 0 is the head in front of that boundary (0..7 samples), the chunks behind it hold 8 samples each - one 16-byte load and one 16-byte store -
 //            and the last one the tail; where they are not, chunk 0 is empty and every chunk goes sample by sample, like heads and tails.
 //   lanes    one lane per chunk, consecutive lanes on consecutive chunks of a row: a wave moves 1 KB of a row with one load and one store instruction.
+//   4:2:0    a descriptor is one plane with a width, a height and a stride of its own, so the chroma planes of an attribute picture go through the same kernel: three
+//            descriptors a picture, into the packed planar layout launch_up444 reads (rbt_submit_gof_color, rbt_gather_420); a row of 1, 7 or 36 samples is cut like any other.
 // No kernel waits for another, a lane has no loop but the at most 8 samples of its chunk, and a chunk index past the picture's last row does nothing.
 #pragma once
 #include "rbt_platform.h"

@@ -112,6 +112,20 @@ __global__ void __launch_bounds__(256) k_sc_walk(RbtScoreCloud A, RbtScoreCloud 
       if (threadIdx.x == 0 && t) atomicAdd(&W.res[(dir ? RBT_SC_COL_BA : RBT_SC_COL_AB) + c], t);
     }
 }
+// recolouring (rbt_pcloud_set_colors): per slot, per point; the merge behind them is k_sc_merge
+__global__ void __launch_bounds__(256) k_sc_recolor_zero(RbtScoreCloud S) { const uint32_t s = blockIdx.x * 256 + threadIdx.x; if (s < (1u << S.lg)) sc_recolor_zero(&S, s); }
+__global__ void __launch_bounds__(256) k_sc_recolor_add(RbtScoreCloud S) { const int i = (int)(blockIdx.x * 256 + threadIdx.x); if (i < S.n) sc_recolor_add(&S, i); }
+// the colour sums of k_sc_walk from the distances a score pair keeps; dir 0: A -> B into res[0..2], 1: B -> A into res[3..5]
+__global__ void __launch_bounds__(256) k_sc_color_walk(RbtScoreCloud A, RbtScoreCloud B, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* res, int dir) {
+  __shared__ unsigned long long part[3][4];
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  long long e[3] = {0, 0, 0};
+  if (i < (dir ? B.n : A.n)) sc_color_walk(&A, &B, dist_a, dist_b, dir, i, e);
+  for (int c = 0; c < 3; c++) {
+    const unsigned long long t = col_block_sum((unsigned long long)(e[c] * e[c]), part[c]);
+    if (threadIdx.x == 0 && t) atomicAdd(&res[3 * dir + c], t);
+  }
+}
 __global__ void __launch_bounds__(256) k_sc_d2_ab(RbtScoreCloud A, RbtScoreCloud B, RbtScoreWork W) { const int i = (int)(blockIdx.x * 256 + threadIdx.x); if (i < A.n) sc_d2_ab(&A, &B, &W, i); }
 __global__ void __launch_bounds__(RBT_SC_SUM) k_sc_sum_block(const double* val, int n, double* part) {
   __shared__ RbtScoreSumLds lds;
@@ -174,5 +188,22 @@ void launch_sc_score(const RbtScoreCloud* A, const RbtScoreCloud* B, int parts, 
     hipLaunchKernelGGL(k_sc_sum_block, dim3((unsigned)nb), dim3(RBT_SC_SUM), 0, g_stream, dir ? W->val_ba : W->val_ab, n, W->part);
     hipLaunchKernelGGL(k_sc_sum_final, dim3(1), dim3(RBT_SC_SUM), 0, g_stream, W->part, nb, (double*)&W->res[dir ? RBT_SC_D2_BA : RBT_SC_D2_AB]);
   }
+}
+void launch_sc_recolor(const RbtScoreCloud* S) {
+  if (S->n <= 0 || !S->rgb) return;
+  const dim3 b(256), gs((unsigned)(((1u << S->lg) + 255) / 256));
+  hipLaunchKernelGGL(k_sc_recolor_zero, gs, b, 0, g_stream, *S);
+  hipLaunchKernelGGL(k_sc_recolor_add, dim3((unsigned)((S->n + 255) / 256)), b, 0, g_stream, *S);
+  hipLaunchKernelGGL(k_sc_merge, gs, b, 0, g_stream, *S);
+}
+void launch_sc_search(const RbtScoreCloud* A, const RbtScoreCloud* B, uint32_t* dist_a, uint32_t* dist_b) {
+  if (A->n <= 0 || B->n <= 0) return;
+  hipLaunchKernelGGL(k_sc_search, dim3((unsigned)((A->n + 63) / 64)), dim3(64), 0, g_stream, *A, *B, dist_a);
+  hipLaunchKernelGGL(k_sc_search, dim3((unsigned)((B->n + 63) / 64)), dim3(64), 0, g_stream, *B, *A, dist_b);
+}
+void launch_sc_color_walks(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* res) {
+  if (A->n <= 0 || B->n <= 0) return;
+  hipLaunchKernelGGL(k_sc_color_walk, dim3((unsigned)((A->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, dist_a, dist_b, res, 0);
+  hipLaunchKernelGGL(k_sc_color_walk, dim3((unsigned)((B->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, dist_a, dist_b, res, 1);
 }
 }  // namespace rbtk

@@ -13,6 +13,11 @@
 //            the D2 value A -> B from B's completed normals. Integer sums: workgroup reduction, then one 64-bit atomic per workgroup.
 //   D2 sums  the per-point values are stored (0 for a point that is no representative) and summed in a fixed order (include/rbt.h): no floating-point atomics, the
 //            same bits from every call and from the serial host emulation. This file is compiled with -ffp-contract=off like the rest of rbt_color.hip.
+//   recolour new colours for an indexed cloud (rbt_pcloud_set_colors): positions, volume, keys and lowest indices stay; the occupied slots' sums, counts and merged colours
+//            go back to zero, every point adds its triple through the voxel -> slot lookup, and the slots are merged again (sc_merge). Integer sums: the result is that of
+//            a fresh index of the same points with the new colours.
+//   pairs    the nearest squared distances of both directions depend on positions only. A score pair (rbt_score_pair_*) keeps them; launch_sc_color_walks runs the walks
+//            with the colour part alone on the stored distances - three sums per direction, reduced in the workgroup, one 64-bit atomic per workgroup and sum.
 // No kernel waits for another; every loop is bounded by the size of the volume.
 #pragma once
 #include "rbt_color.h"
@@ -38,7 +43,12 @@ void launch_sc_index(const RbtScoreCloud* S, uint32_t* scal);           // inser
 void launch_sc_clear(const RbtScoreCloud* S);                           // the volume and coarse words of the cloud's own points back to zero
 // parts: RBT_SCORE_* (D1 always runs: its sums come with the walks)
 void launch_sc_score(const RbtScoreCloud* A, const RbtScoreCloud* B, int parts, const RbtScoreWork* W);
+void launch_sc_recolor(const RbtScoreCloud* S);                         // S->rgb holds the new triples: sums, counts and merged colours of the index remade
+void launch_sc_search(const RbtScoreCloud* A, const RbtScoreCloud* B, uint32_t* dist_a, uint32_t* dist_b);   // the two searches of launch_sc_score on their own
+// the colour sums of launch_sc_score from stored distances: res[0..2] A -> B, res[3..5] B -> A (RBT_SC_COLOR_RESULTS words, zeroed beforehand)
+void launch_sc_color_walks(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* res);
 }  // namespace rbtk
+enum { RBT_SC_COLOR_RESULTS = 8 };
 
 // ------------------------------------------------------------------------------------------------ bodies (device and host emulation)
 RBT_DEV size_t sc_coarse_word(int cx, int cy, int cz) { return (((size_t)cz * RBT_SC_CDIM + cy) * RBT_SC_CROW) + (cx >> 5); }
@@ -65,6 +75,25 @@ RBT_DEV void sc_merge(const RbtScoreCloud* S, uint32_t s) {             // remov
   if (!S->keys[s]) return;
   const uint32_t n = S->acc[4 * s + 3];
   S->col[s] = (S->acc[4 * s] / n) | (S->acc[4 * s + 1] / n) << 8 | (S->acc[4 * s + 2] / n) << 16;
+}
+// recolouring, per slot: an occupied slot's sums, count and merged colour back to zero
+RBT_DEV void sc_recolor_zero(const RbtScoreCloud* S, uint32_t s) {
+  if (!S->keys[s]) return;
+  for (int c = 0; c < 4; c++) S->acc[4 * s + c] = 0;
+  S->col[s] = 0;
+}
+// recolouring, per point: the point's new triple into its voxel's slot (the voxel is in the map: the cloud is indexed)
+RBT_DEV void sc_recolor_add(const RbtScoreCloud* S, int i) {
+  const int16_t* p = S->xyz + 3 * (size_t)i;
+  if (!tc_in_range(p)) return;
+  const uint32_t s = cl_slot_find(S->keys, S->lg, pc_voxel_id(p[0], p[1], p[2]));
+#ifdef RBT_HOSTEMU
+  for (int c = 0; c < 3; c++) S->acc[4 * s + c] += S->rgb[3 * (size_t)i + c];
+  S->acc[4 * s + 3]++;
+#else
+  for (int c = 0; c < 3; c++) atomicAdd(&S->acc[4 * s + c], (uint32_t)S->rgb[3 * (size_t)i + c]);
+  atomicAdd(&S->acc[4 * s + 3], 1u);
+#endif
 }
 RBT_DEV void sc_clear(const RbtScoreCloud* S, int i) {
   const int16_t* p = S->xyz + 3 * (size_t)i;
@@ -201,6 +230,12 @@ RBT_DEV int sc_walk_ba(const RbtScoreCloud* B, const RbtScoreCloud* A, const Rbt
   }
   return 1;
 }
+// the colour error terms of sc_walk_ab (dir 0, point i of A) / sc_walk_ba (dir 1, point i of B) at a stored distance: the walks themselves with the colour part alone
+RBT_DEV int sc_color_walk(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* dist_a, const uint32_t* dist_b, int dir, int i, long long e[3]) {
+  RbtScoreWork W; W.dist_a = (uint32_t*)dist_a; W.dist_b = (uint32_t*)dist_b; W.acc_b = nullptr; W.cnt_b = nullptr; W.val_ab = nullptr; W.val_ba = nullptr; W.part = nullptr; W.res = nullptr;
+  uint32_t d = 0;
+  return dir ? sc_walk_ba(B, A, &W, RBT_SCORE_COLOR, i, &d, e) : sc_walk_ab(A, B, &W, RBT_SCORE_COLOR, i, &d, e);
+}
 // third walk, point i of A: the D2 value against B's normals acc_b / cnt_b, complete now (pc_d2_value)
 RBT_DEV void sc_d2_ab(const RbtScoreCloud* A, const RbtScoreCloud* B, const RbtScoreWork* W, int i) {
 #if defined(__clang__)
@@ -278,6 +313,23 @@ inline void launch_sc_score(const RbtScoreCloud* A, const RbtScoreCloud* B, int 
     const int n = dir ? B->n : A->n, nb = (n + RBT_SC_SUM - 1) / RBT_SC_SUM;
     for (int b = 0; b < nb; b++) sc_sum_block(dir ? W->val_ba : W->val_ab, n, b, W->part, &lds);
     sc_sum_final(W->part, nb, (double*)&W->res[dir ? RBT_SC_D2_BA : RBT_SC_D2_AB], &lds);
+  }
+}
+inline void launch_sc_recolor(const RbtScoreCloud* S) {
+  if (S->n <= 0 || !S->rgb) return;
+  for (uint32_t s = 0; s < (1u << S->lg); s++) sc_recolor_zero(S, s);
+  for (int i = 0; i < S->n; i++) sc_recolor_add(S, i);
+  for (uint32_t s = 0; s < (1u << S->lg); s++) sc_merge(S, s);
+}
+inline void launch_sc_search(const RbtScoreCloud* A, const RbtScoreCloud* B, uint32_t* dist_a, uint32_t* dist_b) {
+  for (int i = 0; i < A->n; i++) sc_search(A, B, dist_a, i);
+  for (int j = 0; j < B->n; j++) sc_search(B, A, dist_b, j);
+}
+inline void launch_sc_color_walks(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* res) {
+  for (int dir = 0; dir < 2; dir++) for (int i = 0; i < (dir ? B->n : A->n); i++) {
+    long long e[3] = {0, 0, 0};
+    if (!sc_color_walk(A, B, dist_a, dist_b, dir, i, e)) continue;
+    for (int c = 0; c < 3; c++) res[3 * dir + c] += (unsigned long long)(e[c] * e[c]);
   }
 }
 }  // namespace rbtk

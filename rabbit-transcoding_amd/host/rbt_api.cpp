@@ -11,8 +11,9 @@
 #include "rbt_internal.h"
 
 struct rbt_pcloud { rbt::PCloud* cloud; rbt_ctx* owner; };
+struct rbt_score_pair { rbt::ScorePair* pair; rbt_ctx* owner; bool stale; };      // stale: one of its clouds has been released
 struct rbt_ctx { int device, rank, world; rbt_stats stats; std::string last_err; double color_ms[4] = {0, 0, 0, 0}; int n_changed = 0; int n_flat = 0;
-                 std::vector<rbt_pcloud*> clouds; rbt::PCloudCache cloud_cache; };      // handles outstanding; clean volumes of released clouds
+                 std::vector<rbt_pcloud*> clouds; std::vector<rbt_score_pair*> pairs; rbt::PCloudCache cloud_cache; };      // handles outstanding; clean volumes of released clouds
 struct rbt_job { rbt::GofJob* j; rbt_ctx* owner; };
 
 // Job slots, pipeline depth and the lock are per DEVICE (the 16 HIP streams a job's lanes map onto are the device's, rbt_kernels.hip):
@@ -64,6 +65,8 @@ void rbt_destroy(rbt_ctx* ctx) {
     DevState& D = g_dev[ctx->device]; std::lock_guard<std::mutex> lk(D.mu);
     if (!rbtk::dev_select(ctx->device)) {
       for (int s = 0; s < RBT_MAX_JOBS; s++) if (D.jobs[s] && D.jobs[s]->owner == ctx) { rbt::gof_abandon(D.jobs[s]->j); delete D.jobs[s]; D.jobs[s] = nullptr; }
+      for (rbt_score_pair* h : ctx->pairs) { rbt::score_pair_release(h->pair); delete h; }
+      ctx->pairs.clear();
       for (rbt_pcloud* h : ctx->clouds) { rbt::pcloud_release(ctx->cloud_cache, h->cloud); delete h; }
       ctx->clouds.clear(); rbt::pcloud_cache_trim(ctx->cloud_cache);
       rbtk::dev_release_pool();
@@ -141,7 +144,7 @@ int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t
 } RBT_CATCH
 
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr,
-                  const rbt_d1_target* d1 = nullptr);
+                  const rbt_d1_target* d1 = nullptr, const rbt_color_target* color = nullptr);
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
 int rbt_transcode_substream(rbt_ctx* ctx, const uint8_t* annexb_in, size_t n_in, const rbt_stream_params* p, uint8_t** annexb_out, size_t* n_out) try {
   if (!ctx || !annexb_in || !p || !annexb_out || !n_out) return RBT_ERR_PARAM;
@@ -214,8 +217,44 @@ static int check_d1(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_d
   }
   return RBT_OK;
 }
+// the refusals of rbt_submit_gof_color that the parameters alone decide, as check_d1
+static int check_color(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_color_target* t, rbt::ColorRequest& req) {
+  std::string& err = ctx->last_err;
+  req.targets = t; req.cache = &ctx->cloud_cache; req.refs.assign((size_t)n, {});
+  for (int i = 0; i < n; i++) {
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    if (t[i].struct_size != sizeof(rbt_color_target)) { err = who + "rbt_color_target.struct_size is not sizeof(rbt_color_target)"; return RBT_ERR_PARAM; }
+    rbt_color_target zero; memset(&zero, 0, sizeof(zero));
+    const bool empty = !t[i].min_psnr_mdb && !t[i].channel && !t[i].stat && !t[i].qp_min && !t[i].qp_max && !t[i].n_frames && !t[i].patches && !t[i].n_patches && !t[i].upsample_filter &&
+                       !t[i].attr_transfer && !t[i].reference && !memcmp(&t[i].atlas, &zero.atlas, sizeof(zero.atlas));
+    if (empty) continue;
+    if (p[i].video_type != RBT_VIDEO_ATTRIBUTE) { err = who + "a colour target on a non-attribute entry (the target of a geometry or occupancy entry must be empty)"; return RBT_ERR_PARAM; }
+    if (t[i].min_psnr_mdb < 0) { err = who + "min_psnr_mdb must not be negative"; return RBT_ERR_PARAM; }
+    if (t[i].channel < 0 || t[i].channel > 2) { err = who + "channel must be 0 (Y), 1 (U) or 2 (V)"; return RBT_ERR_PARAM; }
+    if (t[i].stat != RBT_D1_MIN && t[i].stat != RBT_D1_MEAN) { err = who + "stat must be RBT_D1_MIN or RBT_D1_MEAN"; return RBT_ERR_PARAM; }
+    if (t[i].upsample_filter != RBT_UPSAMPLE_F0 && t[i].upsample_filter != RBT_UPSAMPLE_REPLICATE) { err = who + "upsample_filter must be RBT_UPSAMPLE_F0 or RBT_UPSAMPLE_REPLICATE"; return RBT_ERR_PARAM; }
+    if (t[i].attr_transfer != 0 && t[i].attr_transfer != 1) { err = who + "attr_transfer must be 0 or 1"; return RBT_ERR_PARAM; }
+    const int lo = t[i].qp_min, hi = t[i].qp_max ? t[i].qp_max : 51;
+    if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
+    if (t[i].n_frames < 1) { err = who + "n_frames must be at least 1"; return RBT_ERR_PARAM; }
+    if (!t[i].patches || !t[i].n_patches) { err = who + "the patch lists are missing"; return RBT_ERR_PARAM; }
+    for (int f = 0; f < t[i].n_frames; f++) {
+      if (t[i].n_patches[f] < 0 || (!t[i].patches[f] && t[i].n_patches[f])) { err = who + "the patch list of frame " + std::to_string(f) + " is missing"; return RBT_ERR_PARAM; }
+      std::string why;
+      if (rbt::mapframe_check(why, &t[i].atlas, t[i].patches[f], t[i].n_patches[f])) { err = who + "frame " + std::to_string(f) + ": " + why; return RBT_ERR_PARAM; }
+      const rbt_pcloud* h = t[i].reference ? t[i].reference[f] : nullptr;
+      if (h) {
+        bool mine = false; for (const rbt_pcloud* c : ctx->clouds) mine |= c == h;
+        if (!mine) { err = who + "reference " + std::to_string(f) + " is not a cloud of this context"; return RBT_ERR_PARAM; }
+        if (!rbt::pcloud_has_colors(h->cloud)) { err = who + "reference " + std::to_string(f) + " carries no colours"; return RBT_ERR_PARAM; }
+      }
+      req.refs[(size_t)i].push_back(h ? h->cloud : nullptr);
+    }
+  }
+  return RBT_OK;
+}
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
-                  const rbt_d1_target* d1) {
+                  const rbt_d1_target* d1, const rbt_color_target* color) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
   RBT_ENTER(ctx);
@@ -223,12 +262,14 @@ static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const si
   if (quality) if (int rc = check_quality(ctx->last_err, n, p, quality)) return rc;
   rbt::D1Request req;
   if (d1) if (int rc = check_d1(ctx, n, p, d1, req)) return rc;
+  rbt::ColorRequest creq;
+  if (color) if (int rc = check_color(ctx, n, p, color, creq)) return rc;
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
-  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality, d1 ? &req : nullptr), ctx};
-  if (quality || d1) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
+  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality, d1 ? &req : nullptr, color ? &creq : nullptr), ctx};
+  if (quality || d1 || color) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -289,7 +330,8 @@ int rbt_trim(rbt_ctx* ctx) try {
   rbtk::dev_release_pool();
   return RBT_OK;
 } RBT_CATCH
-static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* quality = nullptr, rbt_d1_floor_result* d1 = nullptr) {
+static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* quality = nullptr, rbt_d1_floor_result* d1 = nullptr,
+                rbt_color_floor_result* color = nullptr) {
   if (!ctx || !job || !annexb_out || !n_out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   int slot = -1;
@@ -299,8 +341,10 @@ static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out,
     ctx->last_err = quality ? "rbt_wait_gof_quality collects jobs of rbt_submit_gof_quality only" : "a job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality"; return RBT_ERR_PARAM; }
   if (rbt::gof_is_d1(job->j) != (d1 != nullptr)) {                // ... and so does a job of rbt_submit_gof_d1
     ctx->last_err = d1 ? "rbt_wait_gof_d1 collects jobs of rbt_submit_gof_d1 only" : "a job of rbt_submit_gof_d1 is collected by rbt_wait_gof_d1"; return RBT_ERR_PARAM; }
+  if (rbt::gof_is_color(job->j) != (color != nullptr)) {          // ... and a job of rbt_submit_gof_color
+    ctx->last_err = color ? "rbt_wait_gof_color collects jobs of rbt_submit_gof_color only" : "a job of rbt_submit_gof_color is collected by rbt_wait_gof_color"; return RBT_ERR_PARAM; }
   int n_flat = 0;
-  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality, &n_flat, d1);
+  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality, &n_flat, d1, color);
   if (!rc) ctx->n_flat = n_flat;
   D.jobs[slot] = nullptr; delete job;
   return rc;
@@ -357,10 +401,32 @@ int rbt_transcode_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, c
   if (rc) return rc;
   return rbt_wait_gof_d1(ctx, job, annexb_out, n_out, results);
 } RBT_CATCH
+// ---- transcoding attributes to a colour PSNR floor ----
+int rbt_submit_gof_color(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_color_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, nullptr, targets);
+} RBT_CATCH
+int rbt_wait_gof_color(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_color_floor_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  return wait(ctx, job, annexb_out, n_out, nullptr, nullptr, nullptr, results);
+} RBT_CATCH
+int rbt_transcode_gof_color(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_color_target* targets,
+                            uint8_t** annexb_out, size_t* n_out, rbt_color_floor_result* results) try {
+  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_color(ctx, n, annexb_in, n_in, p, targets, &job);
+  if (rc) return rc;
+  return rbt_wait_gof_color(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
 int rbt_gather_luma(rbt_ctx* ctx, const uint16_t* src, int n_pics, int stride, int rows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out) try {
   if (!ctx || !src || !out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   return rbt::gather_luma_host(ctx->last_err, src, n_pics, stride, rows, x0, y0, w, h, src_misalign, out);
+} RBT_CATCH
+int rbt_gather_420(rbt_ctx* ctx, const uint16_t* src, int n_pics, int stride, int rows, int chroma_stride, int chroma_rows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out) try {
+  if (!ctx || !src || !out) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  return rbt::gather_420_host(ctx->last_err, src, n_pics, stride, rows, chroma_stride, chroma_rows, x0, y0, w, h, src_misalign, out);
 } RBT_CATCH
 int rbt_picture_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int width, int height, int n_frames, const uint16_t* occ, int ow, int oh, uint64_t* out) try {
   if (!ctx || !a || !b || !out) return RBT_ERR_PARAM;
@@ -555,6 +621,7 @@ void rbt_pcloud_release(rbt_ctx* ctx, rbt_pcloud* cloud) {
   DevState& D = g_dev[ctx->device]; std::lock_guard<std::mutex> lk(D.mu);
   for (size_t i = 0; i < ctx->clouds.size(); i++) if (ctx->clouds[i] == cloud) {
     ctx->clouds.erase(ctx->clouds.begin() + (long)i);
+    for (rbt_score_pair* p : ctx->pairs) p->stale |= rbt::score_pair_uses(p->pair, cloud->cloud);
     if (!rbtk::dev_select(ctx->device)) rbt::pcloud_release(ctx->cloud_cache, cloud->cloud);
     delete cloud;
     return;
@@ -601,6 +668,43 @@ int rbt_score(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, 
   if (parts < 0 || parts > (RBT_SCORE_D1 | RBT_SCORE_D2 | RBT_SCORE_COLOR)) { ctx->last_err = "parts is not a set of RBT_SCORE_*"; return RBT_ERR_PARAM; }
   return rbt::pcloud_score(ctx->last_err, a->cloud, b->cloud, peak, parts, out);
 } RBT_CATCH
+int rbt_pcloud_set_colors(rbt_ctx* ctx, rbt_pcloud* cloud, const uint8_t* rgb) try {
+  if (!ctx || !rgb) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  if (!cloud_of(ctx, cloud)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
+  return rbt::pcloud_set_colors(ctx->last_err, cloud->cloud, rgb);
+} RBT_CATCH
+static bool pair_of(const rbt_ctx* ctx, const rbt_score_pair* h) { return h && h->owner == ctx; }
+int rbt_score_pair_create(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, rbt_score_pair** out) try {
+  if (!ctx || !out) return RBT_ERR_PARAM;
+  *out = nullptr;
+  RBT_ENTER(ctx);
+  if (!cloud_of(ctx, a) || !cloud_of(ctx, b)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
+  rbt::ScorePair* p = nullptr;
+  if (int rc = rbt::score_pair_create(ctx->last_err, a->cloud, b->cloud, &p)) return rc;
+  rbt_score_pair* h = nullptr;
+  try { h = new rbt_score_pair{p, ctx, false}; ctx->pairs.push_back(h); } catch (...) { delete h; rbt::score_pair_release(p); return RBT_ERR_NOMEM; }
+  *out = h;
+  return RBT_OK;
+} RBT_CATCH
+int rbt_score_pair_color(rbt_ctx* ctx, const rbt_score_pair* pair, rbt_color_result* out) try {
+  if (!ctx || !out) return RBT_ERR_PARAM;
+  memset(out, 0, sizeof(*out));
+  RBT_ENTER(ctx);
+  if (!pair_of(ctx, pair)) { ctx->last_err = "not a score pair of this context"; return RBT_ERR_PARAM; }
+  if (pair->stale) { ctx->last_err = "a cloud of the pair has been released"; return RBT_ERR_PARAM; }
+  return rbt::score_pair_color(ctx->last_err, pair->pair, out);
+} RBT_CATCH
+void rbt_score_pair_release(rbt_ctx* ctx, rbt_score_pair* pair) {
+  if (!ctx || !pair_of(ctx, pair)) return;
+  DevState& D = g_dev[ctx->device]; std::lock_guard<std::mutex> lk(D.mu);
+  for (size_t i = 0; i < ctx->pairs.size(); i++) if (ctx->pairs[i] == pair) {
+    ctx->pairs.erase(ctx->pairs.begin() + (long)i);
+    if (!rbtk::dev_select(ctx->device)) rbt::score_pair_release(pair->pair);
+    delete pair;
+    return;
+  }
+}
 int rbt_score_summary(const rbt_frame_score* frames, int n_frames, rbt_sequence_score* out) {
   if (!out || n_frames < 0 || (!frames && n_frames)) return RBT_ERR_PARAM;
   memset(out, 0, sizeof(*out));

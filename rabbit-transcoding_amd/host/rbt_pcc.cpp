@@ -384,6 +384,8 @@ struct PCloud {
 };
 static_assert(PCLOUD_VOL_BYTES == ((size_t)1 << (3 * RBT_PCC_BITS - 3)) + 4 * (size_t)RBT_SC_COARSE_WORDS, "volume + coarse level");
 void pcloud_cache_trim(PCloudCache& cache) { for (void* v : cache.vols) rbtk::dev_free(v); cache.vols.clear(); }
+bool pcloud_has_colors(const PCloud* c) { return c->rgb.p != nullptr; }
+int pcloud_merged(const PCloud* c) { return c->n_merged; }
 void pcloud_points(const PCloud* c, int* n_points, int* n_merged) { if (n_points) *n_points = c->n; if (n_merged) *n_merged = c->n_merged; }
 // The cloud's own volume and coarse words go back to zero and the clean volume to the cache; the maps and the point arrays go back to the device pool.
 void pcloud_release(PCloudCache& cache, PCloud* c) {
@@ -498,48 +500,129 @@ int mapframe_new(std::string& err, const rbt_atlas_params* a, const rbt_patch* p
   *out = F.release();
   return RBT_OK;
 }
-// the cloud of one pair of geometry planes: count, scan, emit, smoothing (as reconstruct_impl runs them), index
-int mapframe_cloud(std::string& err, PCloudCache& cache, const MapFrame* F, const uint16_t* d0, const uint16_t* d1, int geo_bd, PCloud** out, int* n_smoothed) {
-  *out = nullptr; if (n_smoothed) *n_smoothed = 0;
-  if (geo_bd < 8 || geo_bd > 16) { err = "bad atlas parameters"; return RBT_ERR_PARAM; }
-  RbtPccParams P = F->P; P.geo_bd = geo_bd; P.attr_bd = geo_bd;
+// The positions of one pair of geometry planes, as reconstruct_impl makes them: count, scan, emit, and geometry smoothing where the atlas asks for it. xyz / yuv are
+// allocated here (yuv: the triples the emit writes, grey without attribute pictures). keep_xyz0 / keep_moved (both or neither; smoothing only): the positions before
+// smoothing and, where points moved and `flags` is set, the per-point moved flags (k_tc_flag, while the grid's cells are alive). One routine for mapframe_cloud and
+// colorframe_new: the grid's sizing lives here and in reconstruct_impl.
+static int mapframe_points(std::string& err, const MapFrame* F, const RbtPccParams& P, const uint16_t* d0, const uint16_t* d1, DevBuf& xyz, DevBuf& yuv, DevBuf* keep_xyz0, DevBuf* keep_moved, bool flags,
+                           int* n_points, int* n_moved) {
+  *n_points = 0; *n_moved = 0;
   const rbt_atlas_params* a = &F->a; const int n_items = F->n_items; const bool smooth = a->geometry_smoothing != 0;
   const rbt_patch* patches = F->b_patches.as<rbt_patch>(); const uint32_t *items = F->b_items.as<uint32_t>(), *b2p = F->b_b2p.as<uint32_t>();
-  if (!d1) d1 = d0;
   rbtk::launch_pcc_count(&P, patches, items, n_items, F->d_occ, d0, d1, b2p, F->b_counts.as<uint32_t>());
   rbtk::launch_scan_u32(F->b_counts.as<uint32_t>(), F->b_off.as<uint32_t>(), n_items);
   uint32_t total = 0;
   if (rbtk::d2h(&total, F->b_off.as<uint32_t>() + n_items, 4)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
   if (!total) { err = "empty point cloud"; return RBT_ERR_PARAM; }
-  DevBuf b_xyz, b_yuv, b_meta, b_scal, b_cells;
-  if (!b_xyz.alloc(6 * (size_t)total) || !b_yuv.alloc(6 * (size_t)total) || (smooth && (!b_meta.alloc(4 * (size_t)total) || !b_scal.alloc(64)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
-  rbtk::launch_pcc_emit(&P, patches, items, n_items, F->d_occ, d0, d1, nullptr, nullptr, b2p, F->b_off.as<uint32_t>(), b_xyz.as<int16_t>(), b_yuv.as<uint16_t>(),
+  DevBuf b_meta, b_scal, b_cells;
+  if (!xyz.alloc(6 * (size_t)total) || !yuv.alloc(6 * (size_t)total) || (smooth && (!b_meta.alloc(4 * (size_t)total) || !b_scal.alloc(64))) ||
+      (smooth && keep_xyz0 && (!keep_xyz0->alloc(6 * (size_t)total) || !keep_moved->alloc(total)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  rbtk::launch_pcc_emit(&P, patches, items, n_items, F->d_occ, d0, d1, nullptr, nullptr, b2p, F->b_off.as<uint32_t>(), xyz.as<int16_t>(), yuv.as<uint16_t>(),
                         smooth ? F->b_om.as<uint8_t>() : nullptr, smooth ? b_meta.as<uint32_t>() : nullptr);
-  if (smooth) {
-    uint32_t* scal = b_scal.as<uint32_t>(); uint32_t maxv = 0;                        // [0] largest coordinate, [1] points moved
-    if (rbtk::dev_memset(scal, 0, 64)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
-    rbtk::launch_sm_max(b_xyz.as<int16_t>(), (int)total, scal);
-    if (rbtk::d2h(&maxv, scal, 4)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-    RbtSmooth G; memset(&G, 0, sizeof(G));
-    G.g = a->grid_size; G.w = ((int)maxv + G.g - 1) / G.g; G.disth = std::max(G.g / 2, 1); G.th = G.g * G.w; G.threshold = a->threshold_smoothing; G.n_points = (int)total;
-    if (G.w > 0) {
-      const size_t w3 = (size_t)G.w * G.w * G.w, o_sum = (w3 + 255) & ~(size_t)255, o_cnt = o_sum + 12 * w3, o_min = o_cnt + 4 * w3, o_max = o_min + 4 * w3, bytes = o_max + 4 * w3;
-      if (!b_cells.alloc(bytes)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
-      uint8_t* base = b_cells.as<uint8_t>();
-      G.flag = base; G.sum = (uint32_t*)(base + o_sum); G.cnt = (uint32_t*)(base + o_cnt); G.pmin = (uint32_t*)(base + o_min); G.pmax = (uint32_t*)(base + o_max); G.moved = scal + 1;
-      if (rbtk::dev_memset(base, 0, bytes) || rbtk::dev_memset(G.pmin, 0xFF, 4 * w3)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
-      rbtk::launch_sm_passes(&G, b_xyz.as<int16_t>(), b_meta.as<uint32_t>());
-      uint32_t moved[16];
-      if (rbtk::d2h(moved, scal, 64)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-      if (n_smoothed) *n_smoothed = (int)moved[1];
-    }
+  *n_points = (int)total;
+  if (!smooth) return RBT_OK;
+  if (keep_xyz0) {
+    rbtk::launch_tc_copy(keep_xyz0->as<uint16_t>(), xyz.as<uint16_t>(), 3 * (size_t)total);
+    if (rbtk::dev_memset(keep_moved->p, 0, total)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
   }
-  PCloud* c = new PCloud(); c->n = (int)total;
+  uint32_t* scal = b_scal.as<uint32_t>(); uint32_t maxv = 0;                        // [0] largest coordinate, [1] points moved
+  if (rbtk::dev_memset(scal, 0, 64)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::launch_sm_max(xyz.as<int16_t>(), (int)total, scal);
+  if (rbtk::d2h(&maxv, scal, 4)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  RbtSmooth G; memset(&G, 0, sizeof(G));
+  G.g = a->grid_size; G.w = ((int)maxv + G.g - 1) / G.g; G.disth = std::max(G.g / 2, 1); G.th = G.g * G.w; G.threshold = a->threshold_smoothing; G.n_points = (int)total;
+  if (G.w <= 0) return RBT_OK;
+  const size_t w3 = (size_t)G.w * G.w * G.w, o_sum = (w3 + 255) & ~(size_t)255, o_cnt = o_sum + 12 * w3, o_min = o_cnt + 4 * w3, o_max = o_min + 4 * w3, bytes = o_max + 4 * w3;
+  if (!b_cells.alloc(bytes)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  uint8_t* base = b_cells.as<uint8_t>();
+  G.flag = base; G.sum = (uint32_t*)(base + o_sum); G.cnt = (uint32_t*)(base + o_cnt); G.pmin = (uint32_t*)(base + o_min); G.pmax = (uint32_t*)(base + o_max); G.moved = scal + 1;
+  if (rbtk::dev_memset(base, 0, bytes) || rbtk::dev_memset(G.pmin, 0xFF, 4 * w3)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::launch_sm_passes(&G, xyz.as<int16_t>(), b_meta.as<uint32_t>());
+  uint32_t moved[16];
+  if (rbtk::d2h(moved, scal, 64)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  *n_moved = (int)moved[1];
+  if (keep_xyz0 && flags && moved[1]) {
+    if (total < RBT_TC_K) { err = "fewer than 8 points"; return RBT_ERR_PARAM; }
+    rbtk::launch_tc_flag(&G, keep_xyz0->as<int16_t>(), b_meta.as<uint32_t>(), keep_moved->as<uint8_t>());
+    if (rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }      // the cells go with this scope
+  }
+  return RBT_OK;
+}
+// the cloud of one pair of geometry planes: the positions (mapframe_points), index
+int mapframe_cloud(std::string& err, PCloudCache& cache, const MapFrame* F, const uint16_t* d0, const uint16_t* d1, int geo_bd, PCloud** out, int* n_smoothed) {
+  *out = nullptr; if (n_smoothed) *n_smoothed = 0;
+  if (geo_bd < 8 || geo_bd > 16) { err = "bad atlas parameters"; return RBT_ERR_PARAM; }
+  RbtPccParams P = F->P; P.geo_bd = geo_bd; P.attr_bd = geo_bd;
+  DevBuf b_xyz, b_yuv; int total = 0, moved = 0;
+  if (int rc = mapframe_points(err, F, P, d0, d1 ? d1 : d0, b_xyz, b_yuv, nullptr, nullptr, false, &total, &moved)) return rc;
+  if (n_smoothed) *n_smoothed = moved;
+  PCloud* c = new PCloud(); c->n = total;
   c->xyz.take(b_xyz);
   if (int rc = pcloud_index(err, cache, c)) { pcloud_release(cache, c); return rc; }      // (waits for the stream: the buffers that go out of scope here are idle)
   *out = c;
   return RBT_OK;
 }
+// ---- recolouring a frame's cloud per trial (rbt_submit_gof_color; rbt_pcc.h) ----
+// The geometry half of one frame, made once: what reconstruct_impl does with the occupancy and geometry planes - count, scan, emit, smoothing with the per-point moved
+// flags - and the index of the final cloud. Kept: the frame's maps and offsets (the colour half emits again, against the trial's 4:4:4 planes), the positions before and
+// after smoothing, the flags.
+struct ColorFrame {
+  MapFrame* maps = nullptr; RbtPccParams P; const uint16_t* d0 = nullptr; const uint16_t* d1 = nullptr;
+  int total = 0, n_moved = 0, n_changed = 0; bool transfer = false;
+  DevBuf xyz0, moved, scratch_xyz, yuv0, yuv; PCloud* cloud = nullptr; ScorePair* pair = nullptr;
+};
+void colorframe_delete(PCloudCache& cache, ColorFrame* f) {
+  if (!f) return;
+  score_pair_release(f->pair); pcloud_release(cache, f->cloud); mapframe_delete(f->maps);
+  delete f;
+}
+void colorframe_upconvert(const uint16_t* d_420, int w, int h, int bit_depth, int n_pictures, int filter, uint16_t* d_444) { rbtk::launch_up444(d_420, w, h, bit_depth, n_pictures, filter, d_444); }
+const PCloud* colorframe_cloud(const ColorFrame* f) { return f->cloud; }
+int colorframe_changed(const ColorFrame* f) { return f->n_changed; }
+size_t colorframe_bytes(const rbt_atlas_params* a, int n_patches) {      // but for its volume: maps, and per possible point positions twice, flags, triples twice, the index's maps
+  const size_t pts = (size_t)a->width * (size_t)a->height * (size_t)a->map_count;
+  return mapframe_bytes(a, n_patches) + pts * (6 + 6 + 1 + 6 + 6 + 6 + 3 + 2 * 28);
+}
+int colorframe_new(std::string& err, PCloudCache& cache, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* d_occ, const uint16_t* d_d0, const uint16_t* d_d1,
+                   int geo_bd, int attr_transfer, ColorFrame** out) {
+  *out = nullptr;
+  if (geo_bd < 8 || geo_bd > 16) { err = "bad atlas parameters"; return RBT_ERR_PARAM; }
+  struct Guard { PCloudCache& cache; ColorFrame* f; ~Guard() { colorframe_delete(cache, f); } } g{cache, new ColorFrame()};
+  ColorFrame* F = g.f;
+  if (int rc = mapframe_new(err, a, patches, n_patches, d_occ, &F->maps)) return rc;
+  F->P = F->maps->P; F->P.geo_bd = geo_bd; F->P.attr_bd = geo_bd; F->d0 = d_d0; F->d1 = d_d1 ? d_d1 : d_d0;
+  DevBuf b_xyz;
+  if (int rc = mapframe_points(err, F->maps, F->P, F->d0, F->d1, b_xyz, F->yuv0, &F->xyz0, &F->moved, attr_transfer != 0, &F->total, &F->n_moved)) return rc;
+  F->transfer = a->geometry_smoothing != 0 && attr_transfer != 0 && F->n_moved != 0;
+  const size_t total = (size_t)F->total;
+  PCloud* c = new PCloud(); c->n = F->total; c->xyz.take(b_xyz);
+  F->cloud = c;
+  if (!F->yuv.alloc(6 * total) || !F->scratch_xyz.alloc(6 * total) || !c->rgb.alloc(3 * total)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::dev_memset(c->rgb.p, 0, 3 * total)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  if (int rc = pcloud_index(err, cache, c)) return rc;                  // (waits for the stream: the buffers that went out of scope above were idle)
+  *out = F; g.f = nullptr;
+  return RBT_OK;
+}
+// The colour half for one trial: t0 / t1 = the 4:4:4 planes (3 x W x H each) of the frame's attribute pictures. Emit once more for the colours, transfer, RGB, recolour.
+int colorframe_color(std::string& err, ColorFrame* F, const uint16_t* t0, const uint16_t* t1, int attr_bd) {
+  const MapFrame* M = F->maps; const size_t n = (size_t)F->total;
+  RbtPccParams P = F->P; P.attr_bd = attr_bd; P.has_attr = 2;
+  uint16_t* colours = F->transfer ? F->yuv0.as<uint16_t>() : F->yuv.as<uint16_t>();
+  rbtk::launch_pcc_emit(&P, M->b_patches.as<rbt_patch>(), M->b_items.as<uint32_t>(), M->n_items, M->d_occ, F->d0, F->d1, t0, t1 ? t1 : t0, M->b_b2p.as<uint32_t>(), M->b_off.as<uint32_t>(),
+                        F->scratch_xyz.as<int16_t>(), colours, nullptr, nullptr);
+  F->n_changed = 0;
+  if (F->transfer) {
+    rbtk::launch_tc_copy(F->yuv.as<uint16_t>(), F->yuv0.as<uint16_t>(), 3 * n);
+    if (int rc = transfer_on_device(err, F->xyz0.as<int16_t>(), F->yuv0.as<uint16_t>(), F->total, F->cloud->xyz.as<int16_t>(), F->yuv.as<uint16_t>(), F->moved.as<uint8_t>(), F->total, F->n_moved, &F->n_changed)) return rc;
+  }
+  rbtk::launch_yuv16_rgb8(F->yuv.as<uint16_t>(), F->total, F->cloud->rgb.as<uint8_t>());
+  const RbtScoreCloud S = F->cloud->view();
+  rbtk::launch_sc_recolor(&S);
+  return RBT_OK;
+}
+int colorframe_pair(std::string& err, ColorFrame* F, const PCloud* ref) { score_pair_release(F->pair); F->pair = nullptr; return score_pair_create(err, ref, F->cloud, &F->pair); }
+int colorframe_score(std::string& err, const ColorFrame* F, rbt_color_result* out) { return score_pair_color(err, F->pair, out); }
+
 int pcloud_d1(std::string& err, const PCloud* a, const PCloud* b, int peak, rbt_d1_result* out) {
   rbt_frame_score s;
   const int rc = pcloud_score(err, a, b, peak, RBT_SCORE_D1, &s);
@@ -559,6 +642,73 @@ int gather_luma_host(std::string& err, const uint16_t* src, int n_pics, int stri
   if (rbtk::h2d(d_in, src, in_n * 2) | rbtk::h2d(desc.p, pics.data(), sizeof(RbtGatherPic) * (size_t)n_pics) | rbtk::dev_memset(d_out, 0xEE, out_n * 2)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
   rbtk::launch_gather_luma(desc.as<RbtGatherPic>(), n_pics, RBT_GM_PIC_CHUNKS(w, h));
   if (rbtk::d2h(out, d_out, out_n * 2) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  return RBT_OK;
+}
+
+// A picture of src: the luma plane (stride x rows), then Cb and Cr (cstride x crows each). Three descriptors a picture - the chroma windows are half the luma window in
+// both directions, with a stride of their own - so chroma rows of 1, 7 or 36 samples go through gm_chunk as luma rows do.
+int gather_420_host(std::string& err, const uint16_t* src, int n_pics, int stride, int rows, int cstride, int crows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out) {
+  if (n_pics < 1 || w < 2 || h < 2 || (w | h | x0 | y0) & 1 || x0 < 0 || y0 < 0 || stride < 1 || rows < 1 || cstride < 1 || crows < 1 || x0 + w > stride || y0 + h > rows ||
+      (x0 + w) / 2 > cstride || (y0 + h) / 2 > crows || stride > 16384 || rows > 16384 || cstride > 16384 || crows > 16384 || src_misalign < 0 || src_misalign > 7) {
+    err = "an even window inside planes of at most 16384 x 16384 samples, its half inside the chroma planes, src_misalign in 0..7"; return RBT_ERR_PARAM; }
+  const size_t luma = (size_t)stride * rows, chroma = (size_t)cstride * crows, pic = luma + 2 * chroma, in_n = pic * (size_t)n_pics, ys = (size_t)w * h, cs = ys / 4, fs = ys + 2 * cs,
+               out_n = fs * (size_t)n_pics, in_bytes = ((in_n + 8) * 2 + 255) & ~(size_t)255;
+  DevBuf buf, desc;
+  if (!buf.alloc(256 + in_bytes + out_n * 2) || !desc.alloc(sizeof(RbtGatherPic) * 3 * (size_t)n_pics)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  uint8_t* base = (uint8_t*)(((uintptr_t)buf.p + 255) & ~(uintptr_t)255);
+  uint16_t* d_in = (uint16_t*)base + src_misalign; uint16_t* d_out = (uint16_t*)(base + in_bytes);
+  std::vector<RbtGatherPic> pics;
+  for (int k = 0; k < n_pics; k++) {
+    const uint16_t* p = d_in + pic * (size_t)k; uint16_t* o = d_out + fs * (size_t)k;
+    pics.push_back(RbtGatherPic{p + (size_t)y0 * stride + x0, o, w, h, stride, 0});
+    for (int c = 0; c < 2; c++) pics.push_back(RbtGatherPic{p + luma + chroma * (size_t)c + (size_t)(y0 / 2) * cstride + x0 / 2, o + ys + cs * (size_t)c, w / 2, h / 2, cstride, 0});
+  }
+  if (rbtk::h2d(d_in, src, in_n * 2) | rbtk::h2d(desc.p, pics.data(), sizeof(RbtGatherPic) * pics.size()) | rbtk::dev_memset(d_out, 0xEE, out_n * 2)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::launch_gather_luma(desc.as<RbtGatherPic>(), (int)pics.size(), RBT_GM_PIC_CHUNKS(w, h));
+  if (rbtk::d2h(out, d_out, out_n * 2) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  return RBT_OK;
+}
+
+// New colours for an indexed cloud. The triples go to a buffer of their own first: the cloud keeps its colours and its index until the upload has succeeded.
+int pcloud_set_colors(std::string& err, PCloud* c, const uint8_t* rgb) {
+  DevBuf fresh;
+  if (!fresh.alloc(3 * (size_t)c->n)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::h2d(fresh.p, rgb, 3 * (size_t)c->n)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  if (rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }      // nothing in flight reads the triples that go
+  c->rgb.take(fresh);
+  const RbtScoreCloud S = c->view();
+  rbtk::launch_sc_recolor(&S);
+  if (rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  return RBT_OK;
+}
+
+struct ScorePair { const PCloud* a; const PCloud* b; int na, nb; DevBuf dist; };
+bool score_pair_uses(const ScorePair* p, const PCloud* c) { return p->a == c || p->b == c; }
+void score_pair_release(ScorePair* p) { delete p; }
+int score_pair_create(std::string& err, const PCloud* a, const PCloud* b, ScorePair** out) {
+  *out = nullptr;
+  std::unique_ptr<ScorePair> P(new ScorePair{a, b, a->n, b->n, {}});
+  if (!P->dist.alloc(4 * ((size_t)a->n + (size_t)b->n))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  const RbtScoreCloud A = a->view(), B = b->view();
+  rbtk::launch_sc_search(&A, &B, P->dist.as<uint32_t>(), P->dist.as<uint32_t>() + a->n);
+  if (rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  *out = P.release();
+  return RBT_OK;
+}
+int score_pair_color(std::string& err, const ScorePair* p, rbt_color_result* out) {
+  memset(out, 0, sizeof(*out));
+  const PCloud *a = p->a, *b = p->b;
+  if (!a->rgb.p || !b->rgb.p || a->n_merged > (1 << 21) || b->n_merged > (1 << 21)) { err = "the colour part needs colours on both clouds and at most 2^21 merged points in each"; return RBT_ERR_PARAM; }
+  DevBuf res;
+  if (!res.alloc(8 * RBT_SC_COLOR_RESULTS)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::dev_memset(res.p, 0, 8 * RBT_SC_COLOR_RESULTS)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  const RbtScoreCloud A = a->view(), B = b->view();
+  rbtk::launch_sc_color_walks(&A, &B, p->dist.as<uint32_t>(), p->dist.as<uint32_t>() + p->na, res.as<unsigned long long>());
+  uint64_t h[RBT_SC_COLOR_RESULTS];
+  if (rbtk::d2h(h, res.p, sizeof(h)) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  out->n_a = a->n_merged; out->n_b = b->n_merged;
+  for (int c = 0; c < 3; c++) { out->sse_ab[c] = h[c]; out->sse_ba[c] = h[3 + c]; }
+  finish_color(out);
   return RBT_OK;
 }
 

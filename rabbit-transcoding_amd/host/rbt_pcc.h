@@ -45,4 +45,34 @@ int mapframe_cloud(std::string& err, PCloudCache& cache, const MapFrame* f, cons
 int pcloud_d1(std::string& err, const PCloud* a, const PCloud* b, int peak, rbt_d1_result* out);
 // rbt_gather_luma: the gather kernel (csrc/rbt_cloudmaps.h) on host arrays
 int gather_luma_host(std::string& err, const uint16_t* src, int n_pics, int stride, int rows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out);
+// rbt_gather_420: the same kernel on the three planes of coded 4:2:0 pictures, three descriptors a picture; out: packed planar 4:2:0, the layout launch_up444 reads
+int gather_420_host(std::string& err, const uint16_t* src, int n_pics, int stride, int rows, int cstride, int crows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out);
+// rbt_pcloud_set_colors: new RGB triples (3 per point, host) for an indexed cloud; only the colour sums and merged colours of its index are remade (csrc/rbt_score.h)
+int pcloud_set_colors(std::string& err, PCloud* c, const uint8_t* rgb);
+// rbt_score_pair_*: the nearest squared distances of both directions between two indexed clouds, kept; pair_color runs the colour walks on them (out: what the colour
+// part of pcloud_score returns for the clouds' colours of the moment). The clouds must outlive the pair.
+struct ScorePair;
+int score_pair_create(std::string& err, const PCloud* a, const PCloud* b, ScorePair** out);
+int score_pair_color(std::string& err, const ScorePair* p, rbt_color_result* out);
+bool score_pair_uses(const ScorePair* p, const PCloud* c);
+void score_pair_release(ScorePair* p);
+// A frame whose cloud is recoloured per trial (rbt_submit_gof_color): the geometry of a trial does not change with the attribute QP. colorframe_new is the geometry half,
+// made once from packed planes on the device (d_occ, d_d0, d_d1 stay alive as long as the frame): the frame's maps, count, scan, emit, smoothing with the per-point moved
+// flags, the index of the final cloud. colorframe_color is the colour half for the 4:4:4 planes (3 x W x H each) of one trial's attribute pictures: emit again for the
+// colours, attribute transfer, RGB, recolour of the index (launch_sc_recolor); the cloud is then what rbt_pcloud_from_maps makes of the same maps. colorframe_pair keeps
+// the distances against a reference, colorframe_score runs the colour walks on them. Everything is enqueued on the current stream and waits on that stream alone.
+struct ColorFrame;
+int colorframe_new(std::string& err, PCloudCache& cache, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* d_occ, const uint16_t* d_d0, const uint16_t* d_d1,
+                   int geo_bd, int attr_transfer, ColorFrame** out);
+int colorframe_color(std::string& err, ColorFrame* f, const uint16_t* d_t0, const uint16_t* d_t1, int attr_bd);
+int colorframe_pair(std::string& err, ColorFrame* f, const PCloud* reference);
+int colorframe_score(std::string& err, const ColorFrame* f, rbt_color_result* out);
+// packed planar 4:2:0 pictures on the device -> their 4:4:4 planes (3 x w x h each): launch_up444 on the current stream
+void colorframe_upconvert(const uint16_t* d_420, int w, int h, int bit_depth, int n_pictures, int filter, uint16_t* d_444);
+const PCloud* colorframe_cloud(const ColorFrame* f);
+int colorframe_changed(const ColorFrame* f);                              // colours the last colorframe_color's transfer changed
+size_t colorframe_bytes(const rbt_atlas_params* a, int n_patches);        // device memory of a frame at most, but for its volume
+void colorframe_delete(PCloudCache& cache, ColorFrame* f);
+bool pcloud_has_colors(const PCloud* c);
+int pcloud_merged(const PCloud* c);
 }

@@ -12,6 +12,7 @@
 #include "rbt_rate_walk.h"
 #include "rbt_quality_walk.h"
 #include "rbt_d1_walk.h"
+#include "rbt_color_walk.h"
 #include "rbt_pcc.h"
 #include "../csrc/rbt_cloudmaps.h"
 
@@ -432,8 +433,9 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
 // underneath the previous GOF's reconstruction and re-encode.
 // Targets - a byte budget or a PSNR floor per entry -: what a pipeline with such an entry keeps between the rounds of its trial encodes (run_rounds, launch_round, finish_round)
 struct RoundCand { int q, qp, walk; };         // entry q of the group at qp; walk: index of its walk, -1 for a constant-QP entry of the pipeline
-struct TargetTried : QualityTried { std::vector<rbt_d1_result> d1; };      // d1: a job with D1 floors, the frames of the trial
-struct TargetWalk : QpWalk<TargetTried> { RateGoal budget; QualityGoal floor; D1Goal dist; bool is_d1 = false; };   // toward < 0: a budget, toward > 0: a floor - on the PSNR, or (is_d1) on D1
+struct TargetTried : QualityTried { std::vector<rbt_d1_result> d1; std::vector<rbt_color_result> color; };      // d1 / color: a job with D1 / colour floors, the frames of the trial
+// toward < 0: a budget, toward > 0: a floor - on the PSNR, (is_d1) on D1 or (is_color) on the colour PSNR of the cloud
+struct TargetWalk : QpWalk<TargetTried> { RateGoal budget; QualityGoal floor; D1Goal dist; ColorGoal col; bool is_d1 = false, is_color = false; };
 // Quality floors: the occupancy source of an entry (include/rbt.h, "transcoding to a PSNR floor", rule 3), kept in the job because the pipelines that use it are encoded in
 // the wait half: the pooled luma planes of the occupancy stream, and for occupancy_rd the per-4x4-unit maps made of them (both live in GofJob::pooled until the job goes)
 struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
@@ -443,6 +445,7 @@ struct RoundPipe {
   std::unique_ptr<EncodeBatch> eb; std::unique_ptr<SseSet> sse;   // the round in flight on the pipeline's stream; sse: a round of a job with floors carries distortion sums
   std::vector<std::vector<uint8_t>> o1; std::vector<QualitySums> sums;   // the pipeline's streams in group order, as they settle, and (floors) their sums
   std::vector<std::vector<rbt_d1_result>> d1;  // (D1 floors) the frames of the constant-QP entries with a target, in group order
+  std::vector<std::vector<rbt_color_result>> color;   // (colour floors) the same
   bool done = false;
 };
 // D1 floors: the target of one entry (n_frames 0: none) as the job keeps it, and what its clouds are rebuilt from. The decoded input of the occupancy source (in_*: the
@@ -454,6 +457,16 @@ struct D1Entry {
   std::vector<MapFrame*> frames; std::vector<PCloud*> own_ref; double cloud_ms = 0;
 };
 struct D1Out { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<rbt_d1_result> frames; double cloud_ms = 0; };
+// Colour floors: the target of one attribute entry (n_frames 0: none) as the job keeps it. geo: the entry that is its geometry source; in_* : where the decoded input of
+// the occupancy source lies, as D1Entry has it. frames: the geometry half of every frame (ColorFrame, rbt_pcc.h), made behind the geometry pipeline's encode from its
+// reconstruction's luma (geo_planes, packed) and kept until the attribute pipeline's rounds end; own_ref: the same for the decoded input, where no handle was given.
+struct ColorEntry {
+  rbt_color_target t; std::vector<std::vector<rbt_patch>> patches; std::vector<const PCloud*> ref;
+  int geo = -1, in_pipe = -1, in_ds = -1, in_ow = 0, in_oh = 0;
+  uint16_t* geo_planes = nullptr; uint16_t* in_planes = nullptr;
+  std::vector<ColorFrame*> frames, own_ref; double cloud_ms = 0;
+};
+struct ColorOut { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<rbt_color_result> frames; double cloud_ms = 0; };
 struct GofJob {
   int n = 0, slot = 0, ng = 0, rc = 0;
   std::vector<std::vector<int>> groups; std::vector<int> order;
@@ -478,8 +491,18 @@ struct GofJob {
   // D1 floors (rbt_submit_gof_d1): the job runs as a job with quality floors that are all 0 - every geometry / attribute pipeline is encoded in the wait half, the pooled
   // occupancy planes and the maps of occupancy_rd stay in the job - and d1 holds the targets with their patch lists copied (d1_setup, d1_score, run_rounds)
   std::vector<D1Entry> d1; std::vector<D1Out> d1out; PCloudCache* cloud_cache = nullptr;
+  // colour floors (rbt_submit_gof_color): the same kind of job; the geometry pipelines' rounds run before the attribute pipelines' (gof_wait), because the clouds' geometry
+  // half is made behind the geometry encode (color_geometry) and recoloured per attribute trial (color_setup, color_score)
+  std::vector<ColorEntry> color; std::vector<ColorOut> colorout;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
-  ~GofJob() { for (void* q : pooled) rbtk::dev_free(q); }
+  void color_release(int entry) {        // the frames' volumes go back to the context's cache; their streams have been waited for
+    ColorEntry& E = color[entry];
+    for (ColorFrame* F : E.frames) colorframe_delete(*cloud_cache, F);
+    for (ColorFrame* F : E.own_ref) colorframe_delete(*cloud_cache, F);
+    E.frames.clear(); E.own_ref.clear();
+    rbtk::dev_free(E.geo_planes); rbtk::dev_free(E.in_planes); E.geo_planes = nullptr; E.in_planes = nullptr;
+  }
+  ~GofJob() { for (size_t i = 0; i < color.size(); i++) color_release((int)i); for (void* q : pooled) rbtk::dev_free(q); }
 };
 static int job_stream(const GofJob& j, int pipeline) { return j.slot * rbtk::RBT_STREAMS_PER_JOB + pipeline; }
 
@@ -495,8 +518,12 @@ static void bind_streams(GofJob& j, int depth) {
 }
 
 size_t gof_memory(const GofJob* j) { return j ? j->dev_bytes + j->rate_bytes : 0; }
-bool gof_is_quality(const GofJob* j) { return j && !j->qtargets.empty() && j->d1.empty(); }
+bool gof_is_quality(const GofJob* j) { return j && !j->qtargets.empty() && j->d1.empty() && j->color.empty(); }
 bool gof_is_d1(const GofJob* j) { return j && !j->d1.empty(); }
+bool gof_is_color(const GofJob* j) { return j && !j->color.empty(); }
+static bool has_color(const GofJob& j, int i) { return !j.color.empty() && j.color[i].t.n_frames > 0; }
+static bool has_color_floor(const GofJob& j, int i) { return has_color(j, i) && j.color[i].t.min_psnr_mdb != 0; }
+static bool color_pipe(const GofJob& j, int gi) { for (int i : j.groups[gi]) if (has_color(j, i)) return true; return false; }
 static bool has_d1(const GofJob& j, int i) { return !j.d1.empty() && j.d1[i].t.n_frames > 0; }
 static bool has_d1_floor(const GofJob& j, int i) { return has_d1(j, i) && j.d1[i].t.min_d1_mdb != 0; }
 int gof_refused(const GofJob* j, std::string& err) { if (!j || !j->refused) return 0; err = j->err; return j->rc; }
@@ -595,6 +622,7 @@ static int build_decoders(GofJob& j, SubmitPlan& s) {
 static int rate_prepare(GofJob& j, int gi);
 static int quality_prepare(GofJob& j, SubmitPlan& s, int gi);
 static int d1_prepare(GofJob& j, SubmitPlan& s, int gi);
+static int color_prepare(GofJob& j, SubmitPlan& s, int gi);
 // Encoder batches: the pipelines whose occupancy streams others are coded with first (their pooled planes are what the maps are made of), then the rest
 static int build_encoders(GofJob& j, SubmitPlan& s) {
   for (int pass = 0; pass < 2; pass++) for (int k = 0; k < j.ng; k++) {
@@ -604,6 +632,7 @@ static int build_encoders(GofJob& j, SubmitPlan& s) {
     if (j.rate_pipe[gi]) {      // stays unchained: decoder and census now, encoders in the wait half
       if (int rc = j.qtargets.empty() ? rate_prepare(j, gi) : quality_prepare(j, s, gi)) return rc;
       if (!j.d1.empty()) if (int rc = d1_prepare(j, s, gi)) return rc;
+      if (!j.color.empty()) if (int rc = color_prepare(j, s, gi)) return rc;
       continue;
     }
     for (size_t q = 0; q < gs.size(); q++) {
@@ -680,8 +709,23 @@ static void seed_d1_floors(GofJob& j, int gi, RoundPipe& r) {
     r.walks.push_back(std::move(w));
   }
 }
+// ... and so is a colour floor's (rbt_color_walk.h)
+static void seed_color_floors(GofJob& j, int gi, RoundPipe& r) {
+  const std::vector<int>& gs = j.groups[gi];
+  for (size_t q = 0; q < gs.size(); q++) if (has_color_floor(j, gs[q])) {
+    const rbt_color_target& t = j.color[gs[q]].t;
+    TargetWalk w = new_walk(q, gs[q], t); w.is_color = true; w.col.floor_mdb = t.min_psnr_mdb; w.col.stat = t.stat; w.col.channel = t.channel;
+    color_seed(w, w.col, j.params[gs[q]].qp);
+    r.walks.push_back(std::move(w));
+  }
+}
 // true: settled; false: the walk needs the trial at `need` next (alone: a probe, the round brings nothing else for it)
 static bool walk_step(TargetWalk& w, int& need, int& dir, bool& alone) {
+  if (w.is_color) {
+    alone = !color_probe(w, w.col);
+    if (alone) { need = w.col.q0; dir = 0; return false; }
+    return qp_walk_step(w, color_holds(w, w.col), need, dir);
+  }
   if (w.is_d1) {
     alone = !d1_probe(w, w.dist);
     if (alone) { need = w.dist.q0; dir = 0; return false; }
@@ -883,6 +927,175 @@ static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, s
   }
   return d1_timed(j, E, rc);
 }
+// ------------------------------------------------------------------------------------------------ colour floors (include/rbt.h, "transcoding attributes to a colour PSNR floor")
+static int displayed(const DecodeBatch& db, int ds, int* w, int* h) {
+  const RbtStreamCfg& c = db.frames[db.stream_first[ds]].cfg; const Sps& sps = db.stream_sps[ds];
+  *w = c.w - 2 * sps.conf_win[0] - 2 * sps.conf_win[1]; *h = c.h - 2 * sps.conf_win[2] - 2 * sps.conf_win[3];
+  return db.stream_count[ds];
+}
+static bool find_entry(const GofJob& j, int entry, int* pipe, size_t* q) {
+  for (int g = 0; g < j.ng; g++) for (size_t k = 0; k < j.groups[g].size(); k++) if (j.groups[g][k] == entry) { *pipe = g; *q = k; return true; }
+  return false;
+}
+// At submit, behind quality_prepare: rules 1 and 2 for every entry of the pipeline with a target - its occupancy source, its geometry source, their shapes -, where the
+// decoded input of the occupancy source lies, and what the clouds will take (rbt_job_memory)
+static int color_prepare(GofJob& j, SubmitPlan& s, int gi) {
+  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
+  if (db.frames.empty()) return 0;
+  auto refuse = [&](int i, const std::string& why) { j.err = "entry " + std::to_string(i) + ": " + why; j.refused = true; return RBT_ERR_PARAM; };
+  for (size_t q = 0; q < gs.size(); q++) if (has_color(j, gs[q])) {
+    const int i = gs[q], io = s.meas_of[i], ds = j.dec_of[gi][q];
+    ColorEntry& E = j.color[i]; const rbt_atlas_params& a = E.t.atlas;
+    if (io < 0 || s.occ_src[io].n <= 0) return refuse(i, "a colour target needs an occupancy source: a pooled occupancy entry (occupancy_precision 4) in front of it");
+    for (int g = i - 1; g > io && E.geo < 0; g--) if (s.p[g].video_type == RBT_VIDEO_GEOMETRY && s.meas_of[g] == io) E.geo = g;
+    if (E.geo < 0) return refuse(i, "a colour target needs a geometry source: a geometry entry in front of it with the same occupancy source");
+    const OccSource& os = s.occ_src[io];
+    int dw, dh; const int cnt = displayed(db, ds, &dw, &dh), bd = db.frames[db.stream_first[ds]].cfg.bit_depth;
+    if (dw != a.width || dh != a.height) return refuse(i, "the displayed picture size is not atlas.width x atlas.height");
+    if (cnt != a.map_count * E.t.n_frames) return refuse(i, "the picture count is not atlas.map_count x n_frames");
+    if (bd != 8 && bd != 10) return refuse(i, "the attribute bit depth is neither 8 nor 10");
+    int gp = -1; size_t gq = 0;
+    if (!find_entry(j, E.geo, &gp, &gq) || gp == gi || j.db[gp].frames.empty()) return refuse(i, "the geometry source was not decoded in a pipeline of its own");
+    int gw, gh; const int gcnt = displayed(j.db[gp], j.dec_of[gp][gq], &gw, &gh);
+    if (gw != dw || gh != dh || gcnt != cnt) return refuse(i, "the geometry source's displayed size or picture count is not the attribute entry's");
+    if (os.n != E.t.n_frames) return refuse(i, "the occupancy source does not hold n_frames pictures");
+    if (os.ow * a.occupancy_precision != dw || os.oh * a.occupancy_precision != dh) return refuse(i, "atlas.occupancy_precision is not width / (output occupancy width)");
+    size_t oq = 0;
+    if (!find_entry(j, io, &E.in_pipe, &oq) || j.db[E.in_pipe].frames.empty()) return refuse(i, "the occupancy source was not decoded");
+    E.in_ds = j.dec_of[E.in_pipe][oq];
+    displayed(j.db[E.in_pipe], E.in_ds, &E.in_ow, &E.in_oh);
+    if (E.in_ow <= 0 || E.in_oh <= 0 || dw % E.in_ow || dh % E.in_oh || dw / E.in_ow != dh / E.in_oh) return refuse(i, "the input occupancy size does not divide the atlas by one whole factor");
+    // memory: per frame a volume, the frame's buffers and 8 bytes per point of distances - twice where the reference is the job's own, with the packed
+    // planes of the decoded input -, the packed geometry planes; per trial the packed attribute planes, their 4:4:4 planes and the two volumes of the transfer
+    const size_t ys = (size_t)dw * dh, vol = (size_t)1 << 27;
+    size_t bytes = (size_t)cnt * ys * 2 + (size_t)cnt * ys * 3 + (size_t)cnt * ys * 6 + (a.geometry_smoothing && E.t.attr_transfer ? 2 * vol : 0);
+    for (int f = 0; f < E.t.n_frames; f++) {
+      const size_t one = PCLOUD_VOL_BYTES + colorframe_bytes(&a, (int)E.patches[f].size()) + 8 * ys * (size_t)a.map_count;
+      bytes += one + (E.ref[f] ? 0 : one + (size_t)a.map_count * ys * 2 + (size_t)E.in_ow * E.in_oh * 2);
+    }
+    j.rate_bytes += bytes;
+  }
+  return 0;
+}
+static int color_timed(GofJob& j, ColorEntry& E, int rc) {
+  rbtk::timer_end(T_CENSUS);
+  if (rc) return rc;
+  if (rbtk::dev_sync()) { j.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  E.cloud_ms += rbtk::timer_ms(T_CENSUS);
+  return 0;
+}
+// The geometry half, behind the only encode of a geometry entry that is some colour target's geometry source (finish_round; candidate e of the round in flight): the luma
+// of its reconstruction gathered into packed planes, which stay until the attribute rounds end, and per frame the ColorFrame - maps from the pooled occupancy plane, count,
+// scan, emit, smoothing with the moved flags, index. On the geometry pipeline's stream, waited for before the round's arena goes.
+static int color_geometry(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e) {
+  const int g = j.groups[gi][q]; const EncStreamDesc& d = eb.desc[e];
+  for (int i = 0; i < j.n; i++) if (has_color(j, i) && j.color[i].geo == g) {
+    ColorEntry& E = j.color[i]; const rbt_atlas_params& a = E.t.atlas; const QualityOcc& o = j.qocc[i];
+    const int W = a.width, H = a.height, mc = a.map_count, nf = E.t.n_frames; const size_t ys = (size_t)W * H;
+    if (d.w != W || d.h != H || d.n_frames != mc * nf || !o.occ || !E.frames.empty()) { j.err = "internal: a colour target does not fit its geometry source"; return RBT_ERR_PARAM; }
+    E.geo_planes = (uint16_t*)rbtk::dev_alloc(ys * (size_t)d.n_frames * 2);
+    if (!E.geo_planes) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    GatherSet gs;
+    rbtk::timer_begin(T_CENSUS);
+    for (int k = 0; k < d.n_frames; k++) { const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k]; gs.add(f.out[0], f.cfg.w, W, H, E.geo_planes + ys * (size_t)k); }
+    int rc = gs.launch();
+    if (rc) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+    E.frames.assign(nf, nullptr);
+    for (int f = 0; f < nf && !rc; f++)
+      rc = colorframe_new(j.err, *j.cloud_cache, &a, E.patches[f].data(), (int)E.patches[f].size(), o.occ + o.in_step * (size_t)f, E.geo_planes + ys * (size_t)(mc * f),
+                          mc > 1 ? E.geo_planes + ys * (size_t)(mc * f + 1) : nullptr, d.bd, E.t.attr_transfer, &E.frames[f]);
+    if (int bad = color_timed(j, E, rc)) return bad;
+  }
+  return 0;
+}
+// the three planes of coded 4:2:0 pictures as packed planar pictures (the layout launch_up444 reads): x0, y0 = the displayed window's offset in luma samples
+static void gather_420(GatherSet& gs, uint16_t* const planes[3], int stride, int x0, int y0, int w, int h, uint16_t* dst) {
+  const size_t ys = (size_t)w * h, cs = ys / 4;
+  gs.add(planes[0] + (size_t)y0 * stride + x0, stride, w, h, dst);
+  for (int c = 1; c < 3; c++) gs.add(planes[c] + (size_t)(y0 / 2) * (stride / 2) + x0 / 2, stride / 2, w / 2, h / 2, dst + ys + cs * (size_t)(c - 1));
+}
+static const char* merged_limit = "more than 2^21 merged points in a cloud";
+// In the wait half of an attribute pipeline with colour targets, once its decoder has been collected (the geometry pipelines ran before it, gof_wait): for a frame
+// without a handle the reference - the same route on the decoded input occupancy, geometry and attribute -, then per frame the score pair against the reference.
+static int color_setup(GofJob& j, int gi) {
+  DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi]; PCloudCache& cache = *j.cloud_cache;
+  rbtk::set_stream(job_stream(j, gi));
+  for (size_t q = 0; q < gs.size(); q++) if (has_color(j, gs[q])) {
+    const int i = gs[q], ds = j.dec_of[gi][q], first = db.stream_first[ds], nf = j.color[i].t.n_frames;
+    ColorEntry& E = j.color[i]; const rbt_atlas_params& a = E.t.atlas; const int W = a.width, H = a.height, mc = a.map_count;
+    if ((int)E.frames.size() != nf) { j.err = "internal: the geometry half of a colour target was not made"; return RBT_ERR_PARAM; }
+    bool any = false; for (int f = 0; f < nf; f++) any |= E.ref[f] == nullptr;
+    E.own_ref.assign(nf, nullptr);
+    rbtk::timer_begin(T_CENSUS);
+    int rc = 0;
+    if (any) {
+      int gp = -1; size_t gq = 0; find_entry(j, E.geo, &gp, &gq);
+      const DecodeBatch& ob = j.db[E.in_pipe]; const int ofirst = ob.stream_first[E.in_ds]; const RbtStreamCfg& oc = ob.frames[ofirst].cfg; const Sps& osps = ob.stream_sps[E.in_ds];
+      const DecodeBatch& gb = j.db[gp]; const int gds = j.dec_of[gp][gq], gfirst = gb.stream_first[gds]; const RbtStreamCfg& gc = gb.frames[gfirst].cfg; const Sps& gsps = gb.stream_sps[gds];
+      const RbtStreamCfg& c = db.frames[first].cfg; const Sps& isps = db.stream_sps[ds];
+      const size_t ys = (size_t)W * H, os = (size_t)E.in_ow * E.in_oh, fs = ys * 3 / 2, n_pic = (size_t)mc * nf;
+      // packed: input occupancy luma, input geometry luma (both stay with the frames), input attribute 4:2:0 and its 4:4:4 planes (this block only)
+      E.in_planes = (uint16_t*)rbtk::dev_alloc((os * (size_t)nf + ys * n_pic) * 2);
+      DevPlanes attr, up; GatherSet gin;
+      if (!E.in_planes || !attr.alloc(fs * n_pic) || !up.alloc(3 * ys * n_pic)) { j.err = "device allocation failed"; rc = RBT_ERR_NOMEM; }
+      uint16_t* occ = E.in_planes; uint16_t* geo = E.in_planes + os * (size_t)nf;
+      for (int f = 0; f < nf && !rc; f++) if (!E.ref[f]) {
+        gin.add((const uint16_t*)ob.frames[ofirst + f].out[0] + (size_t)(2 * osps.conf_win[2]) * oc.w + 2 * osps.conf_win[0], oc.w, E.in_ow, E.in_oh, occ + os * (size_t)f);
+        for (int m = 0; m < mc; m++) {
+          gin.add((const uint16_t*)gb.frames[gfirst + mc * f + m].out[0] + (size_t)(2 * gsps.conf_win[2]) * gc.w + 2 * gsps.conf_win[0], gc.w, W, H, geo + ys * (size_t)(mc * f + m));
+          gather_420(gin, db.frames[first + mc * f + m].out, c.w, 2 * isps.conf_win[0], 2 * isps.conf_win[2], W, H, attr.p + fs * (size_t)(mc * f + m));
+        }
+      }
+      if (!rc && (rc = gin.launch()) != 0) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+      if (!rc) colorframe_upconvert(attr.p, W, H, c.bit_depth, (int)n_pic, E.t.upsample_filter, up.p);      // (pictures of frames with a handle: never gathered, never read)
+      rbt_atlas_params ain = a; ain.occupancy_precision = W / E.in_ow;
+      for (int f = 0; f < nf && !rc; f++) if (!E.ref[f]) {
+        rc = colorframe_new(j.err, cache, &ain, E.patches[f].data(), (int)E.patches[f].size(), occ + os * (size_t)f, geo + ys * (size_t)(mc * f), mc > 1 ? geo + ys * (size_t)(mc * f + 1) : nullptr,
+                            gc.bit_depth, E.t.attr_transfer, &E.own_ref[f]);
+        if (!rc) rc = colorframe_color(j.err, E.own_ref[f], up.p + 3 * ys * (size_t)(mc * f), mc > 1 ? up.p + 3 * ys * (size_t)(mc * f + 1) : nullptr, c.bit_depth);
+      }
+      if (rbtk::dev_sync() && !rc) { j.err = "kernel execution failed"; rc = RBT_ERR_NO_DEVICE; }      // attr and up are idle before they go
+    }
+    for (int f = 0; f < nf && !rc; f++) {
+      const PCloud* A = E.ref[f] ? E.ref[f] : colorframe_cloud(E.own_ref[f]);
+      if (pcloud_merged(A) > (1 << 21) || pcloud_merged(colorframe_cloud(E.frames[f])) > (1 << 21)) { j.err = merged_limit; rc = RBT_ERR_PARAM; }
+      else rc = colorframe_pair(j.err, E.frames[f], A);
+    }
+    if (int bad = color_timed(j, E, rc)) return bad;
+  }
+  return 0;
+}
+// what color_geometry and color_setup made for the pipeline's entries, released on every way out of run_rounds (the clouds' volumes go back to the context's cache)
+struct ColorLive {
+  GofJob& j; int gi;
+  ~ColorLive() {
+    if (j.color.empty() || !color_pipe(j, gi)) return;
+    rbtk::set_stream(job_stream(j, gi)); rbtk::dev_sync();
+    for (int i : j.groups[gi]) if (has_color(j, i)) j.color_release(i);
+  }
+};
+// The clouds of candidate e of the round in flight - stream `q` of the pipeline's group at one QP - against the entry's references, while the round's arena is alive: the
+// three planes of every reconstructed attribute picture gathered into packed 4:2:0 (the displayed window starts at the picture's origin), one up-conversion for all of
+// them, then frame after frame the colour half (colorframe_color) and the colour walks on the pair's distances. Only the colour sums come back.
+static int color_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, std::vector<rbt_color_result>& out) {
+  const int i = j.groups[gi][q]; ColorEntry& E = j.color[i]; const rbt_atlas_params& a = E.t.atlas;
+  const EncStreamDesc& d = eb.desc[e]; const int W = a.width, H = a.height, mc = a.map_count, nf = E.t.n_frames;
+  const size_t ys = (size_t)W * H, fs = ys * 3 / 2;
+  if (d.w != W || d.h != H || d.n_frames != mc * nf || (int)E.frames.size() != nf) { j.err = "internal: a colour target does not fit its stream"; return RBT_ERR_PARAM; }
+  DevPlanes attr, up; GatherSet gs;
+  if (!attr.alloc(fs * (size_t)d.n_frames) || !up.alloc(3 * ys * (size_t)d.n_frames)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  out.assign(nf, rbt_color_result());
+  rbtk::timer_begin(T_CENSUS);
+  for (int k = 0; k < d.n_frames; k++) { const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k]; gather_420(gs, f.out, f.cfg.w, 0, 0, W, H, attr.p + fs * (size_t)k); }
+  int rc = gs.launch();
+  if (rc) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+  if (!rc) colorframe_upconvert(attr.p, W, H, d.bd, d.n_frames, E.t.upsample_filter, up.p);
+  for (int f = 0; f < nf && !rc; f++) {
+    rc = colorframe_color(j.err, E.frames[f], up.p + 3 * ys * (size_t)(mc * f), mc > 1 ? up.p + 3 * ys * (size_t)(mc * f + 1) : nullptr, d.bd);
+    if (!rc) rc = colorframe_score(j.err, E.frames[f], &out[f]);
+  }
+  return color_timed(j, E, rc);
+}
 static int finish_round(GofJob& j, int gi) {
   RoundPipe& r = j.pipes[gi]; std::vector<std::vector<uint8_t>> outs;
   rbtk::set_stream(job_stream(j, gi));
@@ -893,8 +1106,13 @@ static int finish_round(GofJob& j, int gi) {
     for (int k = 0; r.sse && k < d.n_frames; k++, at++) quality_add_picture(sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
     std::vector<rbt_d1_result> frames;                                // a D1 target: the candidate's clouds, from its reconstruction while the round's arena is alive
     if (has_d1(j, j.groups[gi][c.q])) if (int rc = d1_score(j, gi, c.q, *r.eb, e, frames)) return rc;
-    if (c.walk < 0) { r.o1[c.q].swap(outs[e]); r.sums[c.q] = sums; r.d1[c.q].swap(frames); }
-    else { TargetTried& t = r.walks[c.walk].tried[c.qp]; t.stream.swap(outs[e]); t.sums = sums; t.d1.swap(frames); r.n_enc[c.walk]++; }
+    std::vector<rbt_color_result> cframes;                            // a colour target: the candidate's clouds, recoloured from its reconstruction
+    if (!j.color.empty()) {
+      if (has_color(j, j.groups[gi][c.q])) { if (int rc = color_score(j, gi, c.q, *r.eb, e, cframes)) return rc; }
+      else if (c.walk < 0) if (int rc = color_geometry(j, gi, c.q, *r.eb, e)) return rc;      // a geometry source: the geometry half of its clouds, behind its only encode
+    }
+    if (c.walk < 0) { r.o1[c.q].swap(outs[e]); r.sums[c.q] = sums; r.d1[c.q].swap(frames); r.color[c.q].swap(cframes); }
+    else { TargetTried& t = r.walks[c.walk].tried[c.qp]; t.stream.swap(outs[e]); t.sums = sums; t.d1.swap(frames); t.color.swap(cframes); r.n_enc[c.walk]++; }
   }
   r.eb.reset(); r.sse.reset();
   name_round(j, gi, r, false);
@@ -933,7 +1151,7 @@ static void fill_results(GofJob& j, int gi) {
   for (size_t k = 0; k < r.walks.size(); k++) {
     const TargetWalk& w = r.walks[k]; const QualityTried& t = w.tried.find(w.qstar)->second;
     if (w.toward < 0) j.results[w.entry] = rbt_rate_result{w.qstar, w.start, w.met, r.n_enc[k], (uint64_t)t.stream.size(), w.budget.e_qe};
-    else if (!w.is_d1) quality_fill_result(j.qresults[w.entry], w.qstar, w.floor.q0, w.start, w.met, r.n_enc[k], t.stream.size(), t.sums, w.floor.bit_depth);
+    else if (!w.is_d1 && !w.is_color) quality_fill_result(j.qresults[w.entry], w.qstar, w.floor.q0, w.start, w.met, r.n_enc[k], t.stream.size(), t.sums, w.floor.bit_depth);
   }
   // D1 floors: the frames at q*, or at the entry's own QP
   if (!j.d1.empty()) j.d1out.resize(j.n);
@@ -946,6 +1164,17 @@ static void fill_results(GofJob& j, int gi) {
     o.qp = w.qstar; o.q0 = w.dist.q0; o.qs = w.start; o.met = w.met; o.n_enc = r.n_enc[k]; o.bytes = t.stream.size(); o.frames = t.d1;
   }
   for (size_t q = 0; q < gs.size() && !j.d1.empty(); q++) if (has_d1(j, gs[q])) j.d1out[gs[q]].cloud_ms = j.d1[gs[q]].cloud_ms;
+  // colour floors: the same
+  if (!j.color.empty()) j.colorout.resize(j.n);
+  for (size_t q = 0; q < gs.size() && !j.color.empty(); q++) if (has_color(j, gs[q]) && !has_color_floor(j, gs[q])) {
+    ColorOut& o = j.colorout[gs[q]]; const int qp = j.params[gs[q]].qp;
+    o.qp = o.q0 = o.qs = qp; o.met = 1; o.n_enc = 1; o.bytes = r.o1[q].size(); o.frames = r.color[q];
+  }
+  for (size_t k = 0; k < r.walks.size(); k++) if (r.walks[k].is_color) {
+    const TargetWalk& w = r.walks[k]; const TargetTried& t = w.tried.find(w.qstar)->second; ColorOut& o = j.colorout[w.entry];
+    o.qp = w.qstar; o.q0 = w.col.q0; o.qs = w.start; o.met = w.met; o.n_enc = r.n_enc[k]; o.bytes = t.stream.size(); o.frames = t.color;
+  }
+  for (size_t q = 0; q < gs.size() && !j.color.empty(); q++) if (has_color(j, gs[q])) j.colorout[gs[q]].cloud_ms = j.color[gs[q]].cloud_ms;
 }
 // A pipeline with targets, in the wait half: its decoder is collected, the walks are seeded and the rounds run, one after the other, until every walk has settled. In a
 // job with floors the occupancy pipelines have been collected by then (gof_wait), so the pooled planes and the maps the rounds read are complete. (Measured and not
@@ -955,10 +1184,12 @@ static int run_rounds(GofJob& j, int gi) {
   RoundPipe& r = j.pipes[gi]; const size_t n = j.groups[gi].size();
   if (int rc = pipeline_decoded(j, gi)) return rc;
   D1Live d1_live{j, gi};                                            // (releases the pipeline's frames and reference clouds on every way out)
+  ColorLive color_live{j, gi};                                      // (releases the frames of the pipeline's colour entries on every way out)
   if (!j.d1.empty()) { seed_d1_floors(j, gi, r); if (int rc = d1_setup(j, gi)) return rc; }
+  else if (!j.color.empty()) { seed_color_floors(j, gi, r); if (int rc = color_setup(j, gi)) return rc; }
   else if (!j.qtargets.empty()) seed_floors(j, gi, r);
   else if (int rc = seed_budgets(j, gi, r, true)) return rc;
-  r.o1.assign(n, {}); r.sums.assign(n, QualitySums()); r.d1.assign(n, {}); r.n_enc.assign(r.walks.size(), 0);
+  r.o1.assign(n, {}); r.sums.assign(n, QualitySums()); r.d1.assign(n, {}); r.color.assign(n, {}); r.n_enc.assign(r.walks.size(), 0);
   name_round(j, gi, r, true);
   for (;;) {
     if (int rc = launch_round(j, gi)) return rc;
@@ -1159,7 +1390,7 @@ static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
 // Phase A of a job: plan, build and upload everything, then enqueue. Every upload of the job is issued before its first kernel: a copy from pageable memory blocks the host
 // until the stream has reached it, and pipelines may share a stream. The first failure ends the submission (j.rc, j.err); gof_wait drains what was enqueued.
 GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
-                   const D1Request* d1) {
+                   const D1Request* d1, const ColorRequest* color) {
   GofJob* J = new GofJob(); GofJob& j = *J;
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
@@ -1175,6 +1406,15 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
       E.t.patches = nullptr; E.t.n_patches = nullptr; E.t.reference = nullptr;      // (the caller's arrays may go when submit returns)
     }
   }
+  if (color) {   // the same kind of job with the colour targets
+    j.qtargets.assign(n, rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, RBT_QUALITY_ALL, 0, 0}); j.qocc.assign(n, QualityOcc());
+    j.color.resize(n); j.cloud_cache = color->cache;
+    for (int i = 0; i < n; i++) {
+      ColorEntry& E = j.color[i]; E.t = color->targets[i]; E.ref = color->refs[i];
+      for (int f = 0; f < E.t.n_frames; f++) E.patches.emplace_back(E.t.patches[f], E.t.patches[f] + E.t.n_patches[f]);
+      E.t.patches = nullptr; E.t.n_patches = nullptr; E.t.reference = nullptr;
+    }
+  }
   SubmitPlan s; s.in = in; s.p = p; s.gof_rule = gof_rule;
   int rc = plan_pipelines(j, s, depth);
   j.t_gpu = now_ms();
@@ -1188,19 +1428,21 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
 }
 
 // phase B, shortest pipeline first: one sync per stream, then slice sizes -> pack -> NAL assembly. Consumes the job.
-int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* qresults, int* n_flat, rbt_d1_floor_result* d1results) {
+int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* qresults, int* n_flat, rbt_d1_floor_result* d1results,
+             rbt_color_floor_result* cresults) {
   std::unique_ptr<GofJob> guard(J); GofJob& j = *J;
   const int n = j.n, ng = j.ng; int rc = j.rc;
   rbt_stats& st = j.st; std::string& err = j.err;
   std::vector<DecodeBatch>& db = j.db; std::vector<EncodeBatch>& eb = j.eb; const rbt_stream_params* p = j.params.data();
-  for (int i = 0; i < n; i++) { out[i] = nullptr; n_out[i] = 0; if (d1results) memset(&d1results[i], 0, sizeof(d1results[i])); }
+  for (int i = 0; i < n; i++) { out[i] = nullptr; n_out[i] = 0; if (d1results) memset(&d1results[i], 0, sizeof(d1results[i])); if (cresults) memset(&cresults[i], 0, sizeof(cresults[i])); }
   std::vector<std::vector<uint8_t>> outs(n);
   // a job with quality floors: the pipelines that were encoded at submit first - its occupancy pipelines, whose pooled planes and maps the others' rounds read -, then those
   // that are encoded here; every other job has one pass
   const bool quality = !j.qtargets.empty();
-  for (int pass = 0; pass < (quality ? 2 : 1); pass++) for (int k = ng - 1; k >= 0; k--) {
+  // (a job with colour floors has a third pass: the pipelines with a colour target behind the geometry pipelines, whose reconstructions their clouds are made of)
+  for (int pass = 0; pass < (quality ? 3 : 1); pass++) for (int k = ng - 1; k >= 0; k--) {
     const int gi = j.order[k], sid = job_stream(j, gi); const std::vector<int>& gs = j.groups[gi]; rbtk::set_stream(sid);
-    if (quality && (j.rate_pipe[gi] != 0) != (pass == 1)) continue;
+    if (quality && (j.rate_pipe[gi] ? (color_pipe(j, gi) ? 2 : 1) : 0) != pass) continue;
     if (rc) { rbtk::dev_sync(); continue; }              // drain the remaining streams before their arenas are released
     if (db[gi].frames.empty()) continue;
     std::vector<std::vector<uint8_t>> o1;
@@ -1238,6 +1480,18 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
     if (!o.frames) { rc = RBT_ERR_NOMEM; break; }
     memcpy(o.frames, r.frames.data(), sizeof(rbt_d1_result) * r.frames.size());
   }
+  if (cresults && !rc) for (int i = 0; i < n; i++) {
+    rbt_color_floor_result& o = cresults[i]; memset(&o, 0, sizeof(o));
+    o.qp = o.qp_probe = o.qp_start = p[i].qp; o.met = 1; o.n_encodes = j.is_pass[i] ? 0 : 1; o.bytes = (uint64_t)n_out[i];
+    if (!has_color(j, i) || i >= (int)j.colorout.size()) continue;
+    const ColorOut& r = j.colorout[i];
+    o.qp = r.qp; o.qp_probe = r.q0; o.qp_start = r.qs; o.met = r.met; o.n_encodes = r.n_enc; o.bytes = r.bytes; o.cloud_ms = r.cloud_ms; o.n_frames = (int)r.frames.size();
+    color_stats(r.frames.data(), o.n_frames, o.mean_psnr, o.min_psnr);
+    o.frames = (rbt_color_result*)malloc(sizeof(rbt_color_result) * r.frames.size());
+    if (!o.frames) { rc = RBT_ERR_NOMEM; break; }
+    memcpy(o.frames, r.frames.data(), sizeof(rbt_color_result) * r.frames.size());
+  }
+  if (cresults && rc) { for (int i = 0; i < n; i++) { free(cresults[i].frames); memset(&cresults[i], 0, sizeof(cresults[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; } }
   if (d1results && rc) { for (int i = 0; i < n; i++) { free(d1results[i].frames); memset(&d1results[i], 0, sizeof(d1results[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; } }
   // SURVEY.md 8(d) algorithmic traffic: per coded picture of S samples (2 bytes each): decode writes S, P pictures read
   // their reference once; encode reads the source S, writes the reconstruction S (I) and reads the reference (P)
