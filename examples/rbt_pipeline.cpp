@@ -12,6 +12,8 @@
 //       PSNR of every GOF's unit against its decoded input at or above DB (rbt_transcode_v3c_quality), and one line per GOF says q*, the bytes and the PSNRs. --occupied:
 //       the floors look at the occupied samples, and the units are coded occupancy-aware (occupancy_rd), so the bytes differ from a run without it and an input without
 //       a pooled occupancy unit is refused; it needs at least one floor. Not together with a bit rate.
+//       [--per-frame] with a PSNR floor: every point-cloud frame holds the floor on its own and gets its own QP (rbt_transcode_v3c_quality_frames); one line per GOF
+//       and unit lists the QP of every frame, the passes and the pictures encoded.
 //       Not built: a floor on the point-to-point distortion D1 for a container. rbt_submit_gof_d1 (include/rbt.h) needs the patches of every frame, and the library does not
 //       parse the atlas sub-bitstream they are in; a host that has them calls it per GOF.
 //
@@ -40,12 +42,13 @@ static bool read_all(const char* path, std::vector<Gof>& gofs) {
 }
 
 static int v3c_main(int argc, char** argv) {
-  double geo_kbps = 0, attr_kbps = 0, pps = 60, geo_db = 0, attr_db = 0; int occupied = 0;
+  double geo_kbps = 0, attr_kbps = 0, pps = 60, geo_db = 0, attr_db = 0; int occupied = 0, per_frame = 0;
   { int k = 2;                // the rate options out of the argument list, the positional arguments stay where they were
     for (int i = 2; i < argc; i++) {
       double* v = !strcmp(argv[i], "--geometry-kbps") ? &geo_kbps : !strcmp(argv[i], "--attribute-kbps") ? &attr_kbps : !strcmp(argv[i], "--pictures-per-second") ? &pps :
                   !strcmp(argv[i], "--geometry-psnr") ? &geo_db : !strcmp(argv[i], "--attribute-psnr") ? &attr_db : nullptr;
       if (!strcmp(argv[i], "--occupied")) occupied = 1;
+      else if (!strcmp(argv[i], "--per-frame")) per_frame = 1;
       else if (v && i + 1 < argc) *v = atof(argv[++i]); else argv[k++] = argv[i];
     }
     argc = k; }
@@ -53,6 +56,7 @@ static int v3c_main(int argc, char** argv) {
   if (geo_db < 0 || attr_db < 0 || geo_db > 2000 || attr_db > 2000) { fprintf(stderr, "PSNR floors must be between 0 and 2000 dB\n"); return 2; }
   const bool floors = geo_db > 0 || attr_db > 0;
   if (occupied && !floors) { fprintf(stderr, "--occupied says which samples a PSNR floor looks at: give --geometry-psnr or --attribute-psnr with it\n"); return 2; }
+  if (per_frame && !floors) { fprintf(stderr, "--per-frame says how a PSNR floor is held: give --geometry-psnr or --attribute-psnr with it\n"); return 2; }
   if (floors && (geo_kbps > 0 || attr_kbps > 0)) { fprintf(stderr, "a PSNR floor and a bit rate cannot be combined in one call\n"); return 2; }
   const uint32_t geo_bits = (uint32_t)(geo_kbps * 1000.0 / pps + 0.5), attr_bits = (uint32_t)(attr_kbps * 1000.0 / pps + 0.5);
   if (argc < 4) { fprintf(stderr, "usage: %s --v3c in.bin out.bin [depth] [geometryQP] [attributeQP] [occupancyPrecision]\n", argv[0]); return 2; }
@@ -70,9 +74,10 @@ static int v3c_main(int argc, char** argv) {
   int rc = rbt_create(&ctx, 0, 0, 1);
   if (rc != RBT_OK) { fprintf(stderr, "rbt_create: %s\n", rbt_strerror(rc)); return 1; }
   uint8_t* out = nullptr; size_t n = 0;
-  rbt_rate_result* per_gof = nullptr; rbt_quality_result* q_per_gof = nullptr;
+  rbt_rate_result* per_gof = nullptr; rbt_quality_result* q_per_gof = nullptr; rbt_frame_floor_result* f_per_gof = nullptr;
   if ((rc = rbt_set_depth(ctx, depth)) == RBT_OK)
-    rc = floors ? rbt_transcode_v3c_quality(ctx, in.data(), in.size(), &vp, (int32_t)(geo_db * 1000.0 + 0.5), (int32_t)(attr_db * 1000.0 + 0.5), occupied ? RBT_QUALITY_OCCUPIED : RBT_QUALITY_ALL, &out, &n, &q_per_gof) :
+    rc = per_frame ? rbt_transcode_v3c_quality_frames(ctx, in.data(), in.size(), &vp, (int32_t)(geo_db * 1000.0 + 0.5), (int32_t)(attr_db * 1000.0 + 0.5), occupied ? RBT_QUALITY_OCCUPIED : RBT_QUALITY_ALL, &out, &n, &f_per_gof) :
+         floors ? rbt_transcode_v3c_quality(ctx, in.data(), in.size(), &vp, (int32_t)(geo_db * 1000.0 + 0.5), (int32_t)(attr_db * 1000.0 + 0.5), occupied ? RBT_QUALITY_OCCUPIED : RBT_QUALITY_ALL, &out, &n, &q_per_gof) :
          geo_bits || attr_bits ? rbt_transcode_v3c_rate(ctx, in.data(), in.size(), &vp, geo_bits, attr_bits, &out, &n, &per_gof) : rbt_transcode_v3c(ctx, in.data(), in.size(), &vp, &out, &n);
   if (rc != RBT_OK) { fprintf(stderr, "rbt_transcode_v3c: %s %s\n", rbt_strerror(rc), rbt_last_error(ctx)); rbt_destroy(ctx); return 1; }
   if (per_gof) {
@@ -92,6 +97,20 @@ static int v3c_main(int argc, char** argv) {
                               r.qp_start, (unsigned long long)r.bytes, r.psnr[0], r.psnr_occ[0], r.psnr[1], r.psnr[2], (t ? attr_db : geo_db) > 0 ? (r.met ? "met" : "missed") : "none", r.n_encodes);
     }
     rbt_free(q_per_gof);
+  }
+  if (f_per_gof) {
+    rbt_v3c_stat st;
+    if (rbt_v3c_stats(in.data(), in.size(), &st) == RBT_OK) for (int g = 0; g < st.n_gofs; g++) for (int t = 0; t < 2; t++) {
+      const rbt_frame_floor_result& r = f_per_gof[2 * g + t];
+      if (r.n_frames) {
+        printf("GOF %d %s: QP per frame", g, t ? "attribute" : "geometry");
+        for (int k = 0; k < r.n_frames; k++) printf(" %d%s", r.frames[k].qp, r.frames[k].met ? "" : "!");
+        printf(" (probe %d), %llu B, Y %.3f dB, floor %s, %d passes, %llu pictures encoded\n", r.qp_probe, (unsigned long long)r.bytes, r.sums.psnr[0],
+               (t ? attr_db : geo_db) > 0 ? (r.met_all ? "met by every frame" : "missed by the frames marked !") : "none", r.n_passes, (unsigned long long)r.pictures_encoded);
+      }
+      rbt_free(r.frames);
+    }
+    rbt_free(f_per_gof);
   }
   rbt_destroy(ctx);
   f = fopen(argv[3], "wb"); if (!f) return 2;

@@ -161,6 +161,36 @@ int rbt_wait_gof(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out
  * numbers of streams per job), so that the old shapes do not crowd the 288 GB. RBT_ERR_BUSY while jobs are in flight on the device. */
 int rbt_trim(rbt_ctx* ctx);
 
+/* ---- a QP per point-cloud frame (host/rbt_transcode.cpp encode_plan) ----
+ * rbt_submit_gof codes every picture of an entry from one QP. Here an entry may carry a list with one QP per point-cloud frame: the constant-quality building block beside
+ * constant QP (the frames of a GOF scatter by several dB of D1 at one QP). The encoder kernels read the QP from the slice descriptor, so nothing on the device
+ * changes: the list reaches the slices of each picture, and the slice headers carry the difference to the picture parameter set.
+ *
+ * 1. Frames. A geometry / attribute entry has 2 output pictures per point-cloud frame: frame f is output pictures 2f and 2f + 1, an I picture and a zero-motion P picture
+ *    that refers to it; nothing crosses a frame. n_frames must equal pictures / 2.
+ * 2. QPs. With Q = the list, picture 2f is coded at max(0, Q[f] - 3) and picture 2f + 1 at Q[f], exactly as the constant-QP path derives them from qp. 0 <= Q[f] <= 51.
+ * 3. Parameter sets. They are those of rbt_transcode_gof at params[i].qp - init_qp_minus26 comes from params[i].qp -; only slice_qp_delta differs from picture to picture.
+ * 4. Identity. If every Q[f] == params[i].qp the output is byte for byte rbt_transcode_gof's.
+ * 5. Composition. With C(q) = rbt_transcode_gof's stream at qp = q and everything else equal: decoded pictures 2f and 2f + 1 of the output equal those of C(Q[f]) sample
+ *    for sample; the picture hash SEI NAL units behind them (md5_sei) are byte for byte those of C(Q[f]); each slice NAL differs in length from its counterpart in C(Q[f])
+ *    by at most 2 bytes - the width of slice_qp_delta (se(v) of a difference of up to 51: 1 to 13 bits against 1 to 13 bits) and one emulation prevention byte at the
+ *    seam. The encoder holds no state that crosses a frame: every decision of a picture reads its own source, its own slice QP and, for the P picture, the I picture of
+ *    the same frame.
+ * 6. occupancy_rd, the input-mode hints, the flat-chroma fill, verify_md5, preset, log2_ctb, every slice structure (wavefront included) and every job depth behave as in
+ *    the constant-QP path. The slice buffers are sized per slice from the slice's own QP.
+ * 7. RBT_ERR_PARAM (reason in rbt_last_error; nothing is submitted and the context stays usable): struct_size that is not sizeof(rbt_frame_qp); a list on an occupancy
+ *    entry (coded losslessly); n_frames that is not pictures / 2 (n_frames without a list, a list without n_frames); a QP outside 0..51.
+ * An entry with n_frames 0 and qp NULL is coded at params[i].qp. The lists are copied at submit. The job is collected by rbt_wait_gof like a job of rbt_submit_gof.
+ * Floors that choose the list: "floors held frame by frame" (rbt_submit_gof_quality_frames), further down. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(rbt_frame_qp): checked */
+  int n_frames;              /* pictures / 2; 0 with qp NULL = no list */
+  const int8_t* qp;          /* Q[0 .. n_frames - 1] */
+} rbt_frame_qp;
+int rbt_submit_gof_frame_qp(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_frame_qp* lists, rbt_job** job);   /* collected by rbt_wait_gof */
+int rbt_transcode_gof_frame_qp(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_frame_qp* lists,
+                               uint8_t** annexb_out, size_t* n_out);   /* submit + wait */
+
 /* ---- transcoding to a byte budget (csrc/rbt_rate.h) ----
  * rbt_submit_gof codes every entry at the QP the caller names. Here an entry may name a budget instead: the library decodes the input once, counts on the GPU what the
  * decoder left in device memory (the level census), forms a first guess of the QP on the host and closes the loop on the true sizes of trial encodes of the still-resident
@@ -245,7 +275,7 @@ int rbt_rate_estimate(rbt_ctx* ctx, const uint8_t* annexb, size_t n, int video_t
  * occupancy planes and the per-unit maps of occupancy_rd stay alive until the job is collected, and the first trial encode starts only after the occupancy pipeline has made
  * them. A job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality only, and rbt_wait_gof_quality collects no other job: any other pairing is RBT_ERR_PARAM and the
  * job stays collectable. rbt_job_memory counts the arenas of the first round (one trial encode per geometry / attribute entry).
- * Not built: a floor per picture (the floor is on the stream's sum), a floor and a byte budget in one call. (A floor on the point-to-point distortion D1: rbt_submit_gof_d1 below.) */
+ * Not built: a floor and a byte budget in one call. (A floor per point-cloud frame: rbt_submit_gof_quality_frames below.) (A floor on the point-to-point distortion D1: rbt_submit_gof_d1 below.) */
 enum { RBT_QUALITY_ALL = 0, RBT_QUALITY_OCCUPIED = 1 };
 typedef struct {
   uint32_t struct_size;    /* sizeof(rbt_quality_target): checked */
@@ -731,6 +761,57 @@ struct rbt_color_floor_result {
                                                  * then per trial gather, up-conversion, fetch, transfer, RGB, recolour and colour walks, with the gaps in which the stream
                                                  * waits for the host */
 };
+
+/* ---- floors held frame by frame (host/rbt_frame_walk.h) ----
+ * rbt_submit_gof_quality holds the floor on the sums of the whole stream; a D1 floor on the worst frame makes that frame dictate the QP of all. Here every point-cloud
+ * frame of an entry walks to its own QP, and the returned stream carries a QP per frame ("a QP per point-cloud frame" above): every frame is coded just as well as
+ * required. The entry points take rbt_quality_target unchanged.
+ *
+ * 1. Figure of frame f at QP q: rule 2 of the PSNR floor applied to the sums of pictures 2f and 2f + 1 together, plane 0 of the chosen region; meets is rule 4 there. By
+ *    the composition rule of the QP list it is what a constant-QP trial at q gives for these two pictures.
+ * 2. Probe. One pass at q0 = clamp(params[i].qp, lo, hi) for all frames.
+ * 3. Start. Per frame qs_f by the PSNR floor's rule: q0 if the figure is infinite, else clamp(q0 + (int)(figure_f(q0) - F), lo, hi).
+ * 4. Walk. One walk per frame, the PSNR floor's rule 5 word for word, on frame f's figures alone: q*_f, met_f; n_encodes_f <= |q*_f - qs_f| + 5.
+ * 5. Rounds. A pass is one encode launch sequence over (frame, QP) pairs of one entry; frames that are not listed are not encoded. In a round every unsettled frame names
+ *    its QPs as the PSNR floor's rounds name them; pass j of the round carries, for each frame that named at least j + 1 QPs, the j-th of them. Settled frames are in no
+ *    pass. pictures_encoded = 2 * the sum of n_encodes_f; n_passes counts the passes. The result depends on the figures alone, not on how the passes are formed.
+ * 6. Stream. Byte for byte rbt_transcode_gof_frame_qp's for Q = (q*_0, .., q*_{F-1}). It is assembled on the host from the NAL units the passes returned - every pass
+ *    writes the parameter sets of params[i].qp -; no further encode runs. frames[f].bytes is the size of frame f's NAL units in it, start codes included.
+ * 7. min_psnr_mdb 0: the constant-QP stream at params[i].qp, the figures reported per frame (qp = qp_start = params[i].qp, met = 1, n_encodes = 1). A floor that lo misses
+ *    for some frame is no error: that frame comes back at lo with met = 0, and the call returns RBT_OK.
+ * 8. Errors, the occupancy source, occupancy_rd and the lifetime of the occupancy planes are the PSNR floor's; a geometry / attribute entry with an odd number of pictures
+ *    is refused as well (RBT_ERR_PARAM, nothing submitted). A job of rbt_submit_gof_quality_frames is collected by
+ *    rbt_wait_gof_quality_frames only, and rbt_wait_gof_quality_frames collects no other job: any other pairing is RBT_ERR_PARAM and the job stays collectable.
+ *    rbt_job_memory counts the first round (the probe passes). Occupancy entries are coded as rbt_submit_gof codes them: n_frames 0, frames NULL, qp_probe = params[i].qp.
+ * D1 kind (rbt_submit_gof_d1_frames, with rbt_d1_target unchanged): the figure of frame f at q is (double)psnr of D_f(q), D1 rule 5, with the same references, smoothing and
+ * occupancy source; the walk per frame is D1 rule 6 on that figure. stat must be 0 (RBT_D1_MIN) and atlas.map_count 2 (a frame is the pair of pictures), else
+ * RBT_ERR_PARAM. The clouds of a pass are made of the frames it carries: the gather descriptors go by the coded picture, the maps, patch lists and references by the frame.
+ * results[i].d1 holds the rbt_d1_result of every frame at q*_f, cloud_ms the time of rbt_d1_floor_result.cloud_ms; sums is reported as for the PSNR kind. Entries without
+ * a target carry an empty target and are coded at params[i].qp (their frames are reported with the PSNR figure). Errors, pairing and memory are the D1 section's; the job
+ * is collected by rbt_wait_gof_d1_frames only. There is no container-level call, as for rbt_submit_gof_d1.
+ * Not built: byte caps and colour floors per frame, two kinds of floor in one job. */
+typedef struct { int qp, qp_start, met, n_encodes; uint64_t bytes; double figure; } rbt_frame_pick;   /* q*_f, qs_f, met_f, distinct QPs encoded, frame f's bytes, its figure at q*_f */
+typedef struct {
+  int n_frames, qp_probe, met_all, n_passes;      /* q0; met_all = AND of frames[f].met */
+  uint64_t bytes, pictures_encoded;               /* size of the returned stream; 2 * sum of frames[f].n_encodes */
+  rbt_frame_pick* frames;                         /* n_frames picks (malloc'd, rbt_free; NULL for an occupancy entry) */
+  rbt_quality_result sums;                        /* over the returned stream, as rbt_wait_gof_quality reports them; its qp fields are -1 */
+  rbt_d1_result* d1;                              /* D1 kind: n_frames results, frame f at q*_f (malloc'd, rbt_free); else NULL */
+  double cloud_ms;                                /* D1 kind: as rbt_d1_floor_result.cloud_ms; else 0 */
+} rbt_frame_floor_result;
+int rbt_submit_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job);
+int rbt_wait_gof_quality_frames(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results);   /* results: n entries */
+int rbt_transcode_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets,
+                                     uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results);   /* submit + wait */
+int rbt_submit_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets, rbt_job** job);
+int rbt_wait_gof_d1_frames(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results);   /* results: n entries */
+int rbt_transcode_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets,
+                                uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results);   /* submit + wait */
+/* rbt_transcode_v3c_quality with the floors held frame by frame: the same walk over jobs of rbt_submit_gof_quality_frames, the same arguments. *per_gof (may be NULL): two
+ * results per GOF of the input, geometry then attribute, zeros for a GOF this context does not own; the caller releases every frames array, then the array itself
+ * (rbt_free). With both floors 0 the output is rbt_transcode_v3c's. */
+int rbt_transcode_v3c_quality_frames(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, int32_t geometry_min_psnr_mdb, int32_t attribute_min_psnr_mdb, int region,
+                                     uint8_t** out, size_t* n_out, rbt_frame_floor_result** per_gof);
 
 /* ---- normal estimation (csrc/rbt_normals.h) ----
  * D2 needs normals on the source. Where a sequence comes without them, the reference's PccAppNormalGenerator makes them (PCCNormalsGenerator.cpp: a kd-tree query of the

@@ -127,6 +127,16 @@ class RateResult(C.Structure):
     _fields_ = [("qp", C.c_int), ("qp_estimate", C.c_int), ("met", C.c_int), ("n_encodes", C.c_int), ("bytes", C.c_uint64), ("estimate_bytes", C.c_uint64)]
 
 
+class FrameQp(C.Structure):
+    """rbt_frame_qp: one QP per point-cloud frame of an entry; struct_size is filled in. No argument (or an empty list) = no list: the entry is coded at its own QP"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_frames", C.c_int), ("qp", C.POINTER(C.c_int8))]
+
+    def __init__(self, qps=None):
+        qps = list(qps or [])
+        self._keep = (C.c_int8 * max(1, len(qps)))(*qps)
+        super().__init__(C.sizeof(FrameQp), len(qps), self._keep if qps else None)
+
+
 RBT_QUALITY_ALL, RBT_QUALITY_OCCUPIED = 0, 1
 
 
@@ -142,6 +152,17 @@ class QualityResult(C.Structure):
     """rbt_quality_result: q*, the probe q0, the walk's start qs, met, distinct QPs encoded, the stream's size, its sums and PSNRs (Y, Cb, Cr; all samples and occupied)"""
     _fields_ = [("qp", C.c_int), ("qp_probe", C.c_int), ("qp_start", C.c_int), ("met", C.c_int), ("n_encodes", C.c_int), ("bytes", C.c_uint64),
                 ("sse", C.c_uint64 * 3), ("samples", C.c_uint64 * 3), ("sse_occ", C.c_uint64 * 3), ("samples_occ", C.c_uint64 * 3), ("psnr", C.c_double * 3), ("psnr_occ", C.c_double * 3)]
+
+
+class FramePick(C.Structure):
+    """rbt_frame_pick: q*_f, qs_f, met_f, distinct QPs encoded for the frame, the frame's bytes in the returned stream, its figure at q*_f"""
+    _fields_ = [("qp", C.c_int), ("qp_start", C.c_int), ("met", C.c_int), ("n_encodes", C.c_int), ("bytes", C.c_uint64), ("figure", C.c_double)]
+
+
+class FrameFloorResult(C.Structure):
+    """rbt_frame_floor_result: the picks per frame, the probe q0, met_all, the passes, the stream's size, the pictures encoded, the stream's sums"""
+    _fields_ = [("n_frames", C.c_int), ("qp_probe", C.c_int), ("met_all", C.c_int), ("n_passes", C.c_int), ("bytes", C.c_uint64), ("pictures_encoded", C.c_uint64),
+                ("frames", C.POINTER(FramePick)), ("sums", QualityResult), ("d1", C.POINTER(D1Result)), ("cloud_ms", C.c_double)]
 
 
 RBT_D1_MIN, RBT_D1_MEAN = 0, 1
@@ -285,6 +306,8 @@ def load(path=None):
     L.rbt_job_memory.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
     L.rbt_transcode_v3c_stream.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), V3C_SINK, C.c_void_p]
     L.rbt_transcode_v3c.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    L.rbt_submit_gof_frame_qp.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(FrameQp), C.POINTER(C.c_void_p)]
+    L.rbt_transcode_gof_frame_qp.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(FrameQp), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_submit_gof_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(RateTarget), C.POINTER(C.c_void_p)]
     L.rbt_wait_gof_rate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(RateResult)]
     L.rbt_transcode_gof_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(RateTarget), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
@@ -293,6 +316,14 @@ def load(path=None):
     L.rbt_wait_gof_quality.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(QualityResult)]
     L.rbt_transcode_gof_quality.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QualityTarget), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                             C.POINTER(QualityResult)]
+    L.rbt_submit_gof_quality_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QualityTarget), C.POINTER(C.c_void_p)]
+    L.rbt_wait_gof_quality_frames.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(FrameFloorResult)]
+    L.rbt_transcode_gof_quality_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QualityTarget), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                   C.POINTER(FrameFloorResult)]
+    L.rbt_submit_gof_d1_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p)]
+    L.rbt_wait_gof_d1_frames.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(FrameFloorResult)]
+    L.rbt_transcode_gof_d1_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                              C.POINTER(FrameFloorResult)]
     L.rbt_submit_gof_d1.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p)]
     L.rbt_wait_gof_d1.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(D1FloorResult)]
     L.rbt_transcode_gof_d1.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
@@ -310,6 +341,8 @@ def load(path=None):
     L.rbt_score_pair_release.restype = None
     L.rbt_picture_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.rbt_transcode_v3c_quality.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(QualityResult))]
+    L.rbt_transcode_v3c_quality_frames.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                   C.POINTER(C.POINTER(FrameFloorResult))]
     L.rbt_level_census.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rbt_rate_estimate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(RateTable)]
     L.rbt_transcode_v3c_rate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(RateResult))]
@@ -613,6 +646,20 @@ class Context:
     def wait_gof(self, job):
         return self._collect(self.L.rbt_wait_gof, job[1], [job[0]])
 
+    @staticmethod
+    def _frame_qp(lists):
+        return [l if isinstance(l, FrameQp) else FrameQp(l) for l in lists]
+
+    def submit_gof_frame_qp(self, streams, params, lists):
+        """rbt_submit_gof_frame_qp: submit_gof with, per entry, a list of one QP per point-cloud frame (None / empty = the entry's own QP) or a FrameQp; returns a job for wait_gof"""
+        lists = self._frame_qp(lists)      # (alive until the call returns: the library copies the lists)
+        return self._submit(self.L.rbt_submit_gof_frame_qp, streams, params, lists, FrameQp)
+
+    def transcode_gof_frame_qp(self, streams, params, lists):
+        """rbt_transcode_gof_frame_qp: submit + wait"""
+        lists = self._frame_qp(lists)
+        return self._transcode(self.L.rbt_transcode_gof_frame_qp, streams, params, lists, FrameQp)
+
     def submit_gof_rate(self, streams, params, targets):
         """rbt_submit_gof_rate: submit_gof with one RateTarget per entry (target_bytes 0 = constant QP); returns a job for wait_gof_rate"""
         return self._submit(self.L.rbt_submit_gof_rate, streams, params, targets, RateTarget)
@@ -636,6 +683,45 @@ class Context:
     def transcode_gof_quality(self, streams, params, targets):
         """rbt_transcode_gof_quality: submit + wait"""
         return self._transcode(self.L.rbt_transcode_gof_quality, streams, params, targets, QualityTarget, QualityResult)
+
+    def _frame_results(self, res):
+        """([stream bytes, ...], [FrameFloorResult, ...] as dicts): frames becomes a list of pick dicts, sums a dict, and the library's array is released"""
+        outs, rs = res
+        for r in rs:
+            ptr = r["frames"]
+            r["frames"] = [_result_dict(ptr[f]) for f in range(r["n_frames"])] if ptr else []
+            self.L.rbt_free(ptr)
+            r["sums"] = _result_dict(r["sums"])
+            d1 = r["d1"]
+            r["d1"] = [{n: getattr(d1[f], n) for n, _ in D1Result._fields_} for f in range(r["n_frames"])] if d1 else None
+            self.L.rbt_free(d1)
+        return outs, rs
+
+    def submit_gof_d1_frames(self, streams, params, targets):
+        """rbt_submit_gof_d1_frames: submit_gof_d1 with the floor held by every point-cloud frame on its own (stat must be RBT_D1_MIN); returns a job for wait_gof_d1_frames"""
+        return self._submit(self.L.rbt_submit_gof_d1_frames, streams, params, targets, D1Target)
+
+    def wait_gof_d1_frames(self, job):
+        """rbt_wait_gof_d1_frames -> ([stream bytes, ...], [result dict, ...]); d1: the D1 dict of every frame at its pick"""
+        return self._frame_results(self._collect(self.L.rbt_wait_gof_d1_frames, job[1], [job[0]], FrameFloorResult))
+
+    def transcode_gof_d1_frames(self, streams, params, targets):
+        """rbt_transcode_gof_d1_frames: submit + wait"""
+        args = self._gof_args(streams, params, targets, D1Target)
+        return self._frame_results(self._collect(self.L.rbt_transcode_gof_d1_frames, args[0], args, FrameFloorResult))
+
+    def submit_gof_quality_frames(self, streams, params, targets):
+        """rbt_submit_gof_quality_frames: submit_gof_quality with the floor held by every point-cloud frame on its own; returns a job for wait_gof_quality_frames"""
+        return self._submit(self.L.rbt_submit_gof_quality_frames, streams, params, targets, QualityTarget)
+
+    def wait_gof_quality_frames(self, job):
+        """rbt_wait_gof_quality_frames -> ([stream bytes, ...], [result dict, ...])"""
+        return self._frame_results(self._collect(self.L.rbt_wait_gof_quality_frames, job[1], [job[0]], FrameFloorResult))
+
+    def transcode_gof_quality_frames(self, streams, params, targets):
+        """rbt_transcode_gof_quality_frames: submit + wait"""
+        args = self._gof_args(streams, params, targets, QualityTarget)
+        return self._frame_results(self._collect(self.L.rbt_transcode_gof_quality_frames, args[0], args, FrameFloorResult))
 
     def _d1_results(self, res):
         """([stream bytes, ...], [D1FloorResult, ...] as dicts): frames becomes a list of D1 dicts and the library's array is released"""
@@ -719,6 +805,17 @@ class Context:
         per = [(_result_dict(rs[2 * g]), _result_dict(rs[2 * g + 1])) for g in range(n_gofs)]
         self.L.rbt_free(rs)
         return self._take(out, n), per
+
+    def transcode_v3c_quality_frames(self, data: bytes, geometry_qp, attribute_qp, geometry_min_psnr_mdb=0, attribute_min_psnr_mdb=0, region=RBT_QUALITY_ALL, occupancy_precision=4,
+                                     forced_precision_bytes=0, log2_ctb=5, rows_per_slice=-1, md5_sei=0, verify_md5=0, gofs_per_job=1, occupancy_rd=0, preset=0):
+        """rbt_transcode_v3c_quality_frames -> (sample stream, [(geometry result, attribute result) per GOF of the input]), the results as wait_gof_quality_frames gives them"""
+        p = V3CParams(occupancy_precision, geometry_qp, attribute_qp, forced_precision_bytes, log2_ctb, rows_per_slice, md5_sei, verify_md5, gofs_per_job, occupancy_rd, preset)
+        out, n, rs = C.c_void_p(), C.c_size_t(), C.POINTER(FrameFloorResult)()
+        self._chk(self.L.rbt_transcode_v3c_quality_frames(self.h, data, len(data), C.byref(p), geometry_min_psnr_mdb, attribute_min_psnr_mdb, region, C.byref(out), C.byref(n), C.byref(rs)))
+        n_gofs = v3c_stats(data, self.L)["n_gofs"]
+        flat = self._frame_results(([], [_result_dict(rs[i]) for i in range(2 * n_gofs)]))[1]
+        self.L.rbt_free(rs)
+        return self._take(out, n), [(flat[2 * g], flat[2 * g + 1]) for g in range(n_gofs)]
 
     def level_census(self, y, cb, cr, qp4, pm4):
         """rbt_level_census: int16 planes y [h, w], cb / cr [h/2, w/2], int8 qp4 and uint8 pm4 [h/4, w/4] -> uint32 [3, 53]"""

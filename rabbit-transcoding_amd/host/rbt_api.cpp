@@ -144,7 +144,7 @@ int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t
 } RBT_CATCH
 
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr,
-                  const rbt_d1_target* d1 = nullptr, const rbt_color_target* color = nullptr);
+                  const rbt_d1_target* d1 = nullptr, const rbt_color_target* color = nullptr, const rbt_frame_qp* lists = nullptr, bool per_frame = false);
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
 int rbt_transcode_substream(rbt_ctx* ctx, const uint8_t* annexb_in, size_t n_in, const rbt_stream_params* p, uint8_t** annexb_out, size_t* n_out) try {
   if (!ctx || !annexb_in || !p || !annexb_out || !n_out) return RBT_ERR_PARAM;
@@ -253,8 +253,22 @@ static int check_color(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rb
   }
   return RBT_OK;
 }
+// the refusals of rbt_submit_gof_frame_qp that the parameters alone decide (the count against the stream's pictures: gof_refused); out: the lists, copied
+static int check_frame_qp(std::string& err, int n, const rbt_stream_params* p, const rbt_frame_qp* l, std::vector<std::vector<int8_t>>& out) {
+  out.assign((size_t)n, {});
+  for (int i = 0; i < n; i++) {
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    if (l[i].struct_size != sizeof(rbt_frame_qp)) { err = who + "rbt_frame_qp.struct_size is not sizeof(rbt_frame_qp)"; return RBT_ERR_PARAM; }
+    if (!l[i].n_frames && !l[i].qp) continue;
+    if (l[i].n_frames < 1 || !l[i].qp) { err = who + "rbt_frame_qp.n_frames must be pictures / 2 with a list of that many QPs (n_frames 0 and qp NULL: no list)"; return RBT_ERR_PARAM; }
+    if (p[i].video_type == RBT_VIDEO_OCCUPANCY) { err = who + "an occupancy stream is coded losslessly and takes no QP list"; return RBT_ERR_PARAM; }
+    for (int f = 0; f < l[i].n_frames; f++) if (l[i].qp[f] < 0 || l[i].qp[f] > 51) { err = who + "the QP of frame " + std::to_string(f) + " is outside 0..51"; return RBT_ERR_PARAM; }
+    out[(size_t)i].assign(l[i].qp, l[i].qp + l[i].n_frames);
+  }
+  return RBT_OK;
+}
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
-                  const rbt_d1_target* d1, const rbt_color_target* color) {
+                  const rbt_d1_target* d1, const rbt_color_target* color, const rbt_frame_qp* lists, bool per_frame) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
   RBT_ENTER(ctx);
@@ -262,14 +276,17 @@ static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const si
   if (quality) if (int rc = check_quality(ctx->last_err, n, p, quality)) return rc;
   rbt::D1Request req;
   if (d1) if (int rc = check_d1(ctx, n, p, d1, req)) return rc;
+  if (d1 && per_frame) for (int i = 0; i < n; i++) if (d1[i].stat != RBT_D1_MIN) { ctx->last_err = "entry " + std::to_string(i) + ": stat must be 0 (RBT_D1_MIN): every frame holds the floor on its own"; return RBT_ERR_PARAM; }
   rbt::ColorRequest creq;
   if (color) if (int rc = check_color(ctx, n, p, color, creq)) return rc;
+  std::vector<std::vector<int8_t>> frame_qp;
+  if (lists) if (int rc = check_frame_qp(ctx->last_err, n, p, lists, frame_qp)) return rc;
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
-  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality, d1 ? &req : nullptr, color ? &creq : nullptr), ctx};
-  if (quality || d1 || color) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
+  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality, d1 ? &req : nullptr, color ? &creq : nullptr, lists ? &frame_qp : nullptr, per_frame), ctx};
+  if (quality || d1 || color || lists) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -331,7 +348,7 @@ int rbt_trim(rbt_ctx* ctx) try {
   return RBT_OK;
 } RBT_CATCH
 static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* quality = nullptr, rbt_d1_floor_result* d1 = nullptr,
-                rbt_color_floor_result* color = nullptr) {
+                rbt_color_floor_result* color = nullptr, rbt_frame_floor_result* frames = nullptr, bool d1_frames = false) {
   if (!ctx || !job || !annexb_out || !n_out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   int slot = -1;
@@ -343,13 +360,30 @@ static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out,
     ctx->last_err = d1 ? "rbt_wait_gof_d1 collects jobs of rbt_submit_gof_d1 only" : "a job of rbt_submit_gof_d1 is collected by rbt_wait_gof_d1"; return RBT_ERR_PARAM; }
   if (rbt::gof_is_color(job->j) != (color != nullptr)) {          // ... and a job of rbt_submit_gof_color
     ctx->last_err = color ? "rbt_wait_gof_color collects jobs of rbt_submit_gof_color only" : "a job of rbt_submit_gof_color is collected by rbt_wait_gof_color"; return RBT_ERR_PARAM; }
+  if (rbt::gof_is_d1_frames(job->j) != (frames != nullptr && d1_frames)) { // ... and a job of rbt_submit_gof_d1_frames
+    ctx->last_err = d1_frames ? "rbt_wait_gof_d1_frames collects jobs of rbt_submit_gof_d1_frames only" : "a job of rbt_submit_gof_d1_frames is collected by rbt_wait_gof_d1_frames"; return RBT_ERR_PARAM; }
+  if (rbt::gof_is_quality_frames(job->j) != (frames != nullptr && !d1_frames)) { // ... and a job of rbt_submit_gof_quality_frames
+    ctx->last_err = frames ? "rbt_wait_gof_quality_frames collects jobs of rbt_submit_gof_quality_frames only" : "a job of rbt_submit_gof_quality_frames is collected by rbt_wait_gof_quality_frames"; return RBT_ERR_PARAM; }
   int n_flat = 0;
-  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality, &n_flat, d1, color);
+  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality, &n_flat, d1, color, frames);
   if (!rc) ctx->n_flat = n_flat;
   D.jobs[slot] = nullptr; delete job;
   return rc;
 }
 int rbt_wait_gof(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out) try { return wait(ctx, job, annexb_out, n_out, nullptr); } RBT_CATCH
+// ---- a QP per point-cloud frame ----
+int rbt_submit_gof_frame_qp(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_frame_qp* lists, rbt_job** job) try {
+  if (!lists) return RBT_ERR_PARAM;
+  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, nullptr, nullptr, lists);
+} RBT_CATCH
+int rbt_transcode_gof_frame_qp(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_frame_qp* lists,
+                               uint8_t** annexb_out, size_t* n_out) try {
+  if (!annexb_out || !n_out) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_frame_qp(ctx, n, annexb_in, n_in, p, lists, &job);
+  if (rc) return rc;
+  return rbt_wait_gof(ctx, job, annexb_out, n_out);
+} RBT_CATCH
 // ---- transcoding to a byte budget ----
 int rbt_submit_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_rate_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
@@ -383,6 +417,39 @@ int rbt_transcode_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_
   int rc = rbt_submit_gof_quality(ctx, n, annexb_in, n_in, p, targets, &job);
   if (rc) return rc;
   return rbt_wait_gof_quality(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
+// ---- floors held frame by frame ----
+int rbt_submit_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, targets, nullptr, nullptr, nullptr, true);
+} RBT_CATCH
+int rbt_wait_gof_quality_frames(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  return wait(ctx, job, annexb_out, n_out, nullptr, nullptr, nullptr, nullptr, results);
+} RBT_CATCH
+int rbt_transcode_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets,
+                                     uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
+  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_quality_frames(ctx, n, annexb_in, n_in, p, targets, &job);
+  if (rc) return rc;
+  return rbt_wait_gof_quality_frames(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
+int rbt_submit_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, targets, nullptr, nullptr, true);
+} RBT_CATCH
+int rbt_wait_gof_d1_frames(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  return wait(ctx, job, annexb_out, n_out, nullptr, nullptr, nullptr, nullptr, results, true);
+} RBT_CATCH
+int rbt_transcode_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets,
+                                uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
+  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_d1_frames(ctx, n, annexb_in, n_in, p, targets, &job);
+  if (rc) return rc;
+  return rbt_wait_gof_d1_frames(ctx, job, annexb_out, n_out, results);
 } RBT_CATCH
 // ---- transcoding geometry to a D1 floor ----
 int rbt_submit_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets, rbt_job** job) try {

@@ -13,6 +13,7 @@
 #include "rbt_quality_walk.h"
 #include "rbt_d1_walk.h"
 #include "rbt_color_walk.h"
+#include "rbt_frame_walk.h"
 #include "rbt_pcc.h"
 #include "../csrc/rbt_cloudmaps.h"
 
@@ -34,6 +35,8 @@ struct EncStreamDesc {
   // levels and reconstruction there instead of in memory of its own (9.8 MB per 1280x1280 picture, 1.26 GB per GOF). Empty / null = the encoder allocates.
   std::vector<uint16_t*> alias_pix; std::vector<int16_t*> alias_coef;
   int src_stride = 0, src_x0 = 0, src_y0 = 0;   // the planes are views: luma row stride (0 = w) and origin of the w x h region (luma samples)
+  std::vector<int> pic; int n_total = 0; // a pass over a subset of the frames (desc_subset): the stream's picture behind each coded picture, and how many the stream has; empty = all of them
+  std::vector<int8_t> frame_qp;          // a QP per point-cloud frame (rbt_frame_qp): pictures f * gop .. f * gop + gop - 1 are coded from frame_qp[f] where qp would be used; empty = qp. The parameter sets stay those of qp
 };
 // Pictures are coded at the display size rounded up to 8 (all-intra) or 16 (I,P pairs: 16x16 inter CUs) and the padding is
 // signalled as the conformance window (7.4.3.2.1), like libx265 does for the reference (PCCTranscoder.cpp:706).
@@ -47,6 +50,7 @@ struct EncodeBatch {
   RbtFrame* d_frames = nullptr; RbtSlice* d_slices = nullptr; int32_t* d_lists = nullptr; uint8_t* d_out = nullptr; uint8_t* d_packed = nullptr; uint32_t* d_dst = nullptr;
   size_t out_total = 0;
   std::vector<PadJob> pad_jobs;                 // source pictures that have to be copied into padded planes before the encoder reads them
+  std::vector<std::vector<size_t>> pic_at;     // after encode_finish, per stream: where in its output the NAL units of each picture start (rbt_frame_walk.h frame_cut)
   std::vector<uint16_t> cs_keep; uint16_t* d_cs = nullptr;   // the ctb->slice maps of all pictures back to back: host staging (alive until the copy has completed) and device
   uint8_t* d_zero = nullptr; size_t zero_bytes = 0; bool wpp = false;   // launch tickets (3 words) + row progress of the wavefront mode
   int main_stream = 0, aux_stream = -1;          // aux_stream >= 0: the intra part was enqueued there (its timers live there)
@@ -139,8 +143,10 @@ static int encode_plan(EncodeBatch& b) {
     make_param_sets(b.desc[si], b.sps[si], b.pps[si]);
     const Sps& s = b.sps[si]; const Pps& p = b.pps[si];
     b.stream_first[si] = (int)b.frames.size();
+    if (!d.frame_qp.empty() && (d.lossless || d.gop < 1 || (int)d.frame_qp.size() * d.gop != d.n_frames)) { b.err = "internal: a QP list that does not match the stream's pictures"; return RBT_ERR_PARAM; }
     for (int i = 0; i < d.n_frames; i++) {
       bool is_i = d.gop <= 1 || (i % d.gop) == 0;
+      const int qp = d.frame_qp.empty() ? d.qp : d.frame_qp[(size_t)(i / d.gop)];      // only slice_qp_delta tells the pictures of a mixed-QP stream apart (write_slice_header: h.qp - init_qp)
       RbtFrame f; memset(&f, 0, sizeof(f));
       fill_stream_cfg(s, p, f.cfg);
       f.poc = is_i ? 0 : (i % d.gop); f.level = is_i ? 0 : 1; f.first_slice = (int)b.slices.size();
@@ -155,7 +161,7 @@ static int encode_plan(EncodeBatch& b) {
         sl.next_seg = -1; sl.wpp = (uint8_t)(d.rows < 0); sl.dependent = (uint8_t)(d.rows < 0 && addr > 0);
         sl.frame = (int)b.frames.size(); sl.ctb_addr = addr; sl.n_ctbs = std::min(step, n_ctb - addr);
         sl.slice_type = (int8_t)(is_i ? RBT_SLICE_I : RBT_SLICE_P);
-        sl.qp = (int8_t)std::min(51, std::max(0, is_i ? d.qp + d.i_qp_offset : d.qp));
+        sl.qp = (int8_t)std::min(51, std::max(0, is_i ? qp + d.i_qp_offset : qp));
         sl.deblocking_disabled = (uint8_t)p.pps_deblocking_disabled; sl.lf_across = (uint8_t)p.loop_filter_across_slices;
         sl.max_merge_cand = 1; sl.num_ref_idx = 1; sl.poc = f.poc; sl.sao_luma = sl.sao_chroma = (uint8_t)b.desc[si].sao;
         if (!is_i) { sl.ref_frame[0] = f.ref_frame; sl.ref_poc[0] = f.ref_poc; }
@@ -296,10 +302,11 @@ static int encode_finish(EncodeBatch& b, std::vector<std::vector<uint8_t>>& outs
   st.d2h_ms += now_ms() - t0;
   // ---- NAL packing (parameter sets, slice headers, emulation prevention) ----
   double t1 = now_ms();
-  outs.assign(b.desc.size(), {});
+  outs.assign(b.desc.size(), {}); b.pic_at.assign(b.desc.size(), {});
   for (size_t i = 0; i < nf; i++) {
     int si = b.frame_stream[i]; const Sps& s = b.sps[si]; const Pps& p = b.pps[si]; std::vector<uint8_t>& out = outs[si]; const RbtFrame& f = b.frames[i];
     bool idr = b.frame_is_idr[i] != 0;
+    b.pic_at[si].push_back(out.size());
     if (idr) write_param_sets(out, s, p);
     for (int k = 0; k < f.n_slices; k++) {
       const RbtSlice& sl = b.slices[f.first_slice + k];
@@ -432,7 +439,7 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
 // a caller can keep two GOFs in flight (job slots use disjoint HIP streams): the next GOF's entropy decoding then runs
 // underneath the previous GOF's reconstruction and re-encode.
 // Targets - a byte budget or a PSNR floor per entry -: what a pipeline with such an entry keeps between the rounds of its trial encodes (run_rounds, launch_round, finish_round)
-struct RoundCand { int q, qp, walk; };         // entry q of the group at qp; walk: index of its walk, -1 for a constant-QP entry of the pipeline
+struct RoundCand { int q, qp, walk; int fw = -1; FramePass pass; };   // entry q of the group at qp; walk: index of its walk, -1 for a constant-QP entry of the pipeline; fw >= 0: a pass of the entry's frame walks (qp: the entry's own, for the parameter sets)
 struct TargetTried : QualityTried { std::vector<rbt_d1_result> d1; std::vector<rbt_color_result> color; };      // d1 / color: a job with D1 / colour floors, the frames of the trial
 // toward < 0: a budget, toward > 0: a floor - on the PSNR, (is_d1) on D1 or (is_color) on the colour PSNR of the cloud
 struct TargetWalk : QpWalk<TargetTried> { RateGoal budget; QualityGoal floor; D1Goal dist; ColorGoal col; bool is_d1 = false, is_color = false; };
@@ -441,6 +448,7 @@ struct TargetWalk : QpWalk<TargetTried> { RateGoal budget; QualityGoal floor; D1
 struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
 struct RoundPipe {
   std::vector<TargetWalk> walks; std::vector<int> n_enc;
+  std::vector<FrameWalks<TargetWalk>> fwalks;  // a job with floors held frame by frame: per entry of the group one walk per point-cloud frame
   std::vector<RoundCand> cands;                // the round to run (eb == nullptr) or running
   std::unique_ptr<EncodeBatch> eb; std::unique_ptr<SseSet> sse;   // the round in flight on the pipeline's stream; sse: a round of a job with floors carries distortion sums
   std::vector<std::vector<uint8_t>> o1; std::vector<QualitySums> sums;   // the pipeline's streams in group order, as they settle, and (floors) their sums
@@ -467,6 +475,7 @@ struct ColorEntry {
   std::vector<ColorFrame*> frames, own_ref; double cloud_ms = 0;
 };
 struct ColorOut { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<rbt_color_result> frames; double cloud_ms = 0; };
+struct FrameFloorOut { int q0 = 0, n_passes = 0, bit_depth = 8; std::vector<rbt_frame_pick> frames; std::vector<rbt_d1_result> d1; double cloud_ms = 0; uint64_t bytes = 0, pictures = 0; QualitySums sums; };
 struct GofJob {
   int n = 0, slot = 0, ng = 0, rc = 0;
   std::vector<std::vector<int>> groups; std::vector<int> order;
@@ -494,6 +503,10 @@ struct GofJob {
   // colour floors (rbt_submit_gof_color): the same kind of job; the geometry pipelines' rounds run before the attribute pipelines' (gof_wait), because the clouds' geometry
   // half is made behind the geometry encode (color_geometry) and recoloured per attribute trial (color_setup, color_score)
   std::vector<ColorEntry> color; std::vector<ColorOut> colorout;
+  // a QP per point-cloud frame (rbt_submit_gof_frame_qp): per entry the list, empty = the entry's own QP; such a job is an ordinary constant-QP job in every other respect
+  std::vector<std::vector<int8_t>> frame_qp;
+  // floors held frame by frame (rbt_submit_gof_quality_frames): a job with quality floors whose pipelines walk every frame on its own (RoundPipe::fwalks)
+  bool per_frame = false; std::vector<FrameFloorOut> fout;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   void color_release(int entry) {        // the frames' volumes go back to the context's cache; their streams have been waited for
     ColorEntry& E = color[entry];
@@ -518,8 +531,10 @@ static void bind_streams(GofJob& j, int depth) {
 }
 
 size_t gof_memory(const GofJob* j) { return j ? j->dev_bytes + j->rate_bytes : 0; }
-bool gof_is_quality(const GofJob* j) { return j && !j->qtargets.empty() && j->d1.empty() && j->color.empty(); }
-bool gof_is_d1(const GofJob* j) { return j && !j->d1.empty(); }
+bool gof_is_quality(const GofJob* j) { return j && !j->qtargets.empty() && j->d1.empty() && j->color.empty() && !j->per_frame; }
+bool gof_is_quality_frames(const GofJob* j) { return j && j->per_frame && j->d1.empty(); }
+bool gof_is_d1_frames(const GofJob* j) { return j && j->per_frame && !j->d1.empty(); }
+bool gof_is_d1(const GofJob* j) { return j && !j->d1.empty() && !j->per_frame; }
 bool gof_is_color(const GofJob* j) { return j && !j->color.empty(); }
 static bool has_color(const GofJob& j, int i) { return !j.color.empty() && j.color[i].t.n_frames > 0; }
 static bool has_color_floor(const GofJob& j, int i) { return has_color(j, i) && j.color[i].t.min_psnr_mdb != 0; }
@@ -619,6 +634,21 @@ static int build_decoders(GofJob& j, SubmitPlan& s) {
   return 0;
 }
 
+// A QP per point-cloud frame (include/rbt.h, "a QP per point-cloud frame", rule 1): once the decoders know their pictures, a list must name one QP per pair of them. A
+// refusal here is a refusal of the plan: nothing has been enqueued (gof_refused)
+static int check_frame_qp(GofJob& j) {
+  if (j.frame_qp.empty()) return 0;
+  for (int g = 0; g < j.ng; g++) for (size_t q = 0; q < j.groups[g].size(); q++) {
+    const int i = j.groups[g][q]; const DecodeBatch& db = j.db[g];
+    if (j.frame_qp[i].empty()) continue;
+    const int cnt = db.stream_count[j.dec_of[g][q]];
+    if (cnt % 2 || (int)j.frame_qp[i].size() != cnt / 2) {
+      j.err = "entry " + std::to_string(i) + ": rbt_frame_qp.n_frames is " + std::to_string(j.frame_qp[i].size()) + ", the stream holds " + std::to_string(cnt) + " pictures (n_frames must be pictures / 2)";
+      j.refused = true; return RBT_ERR_PARAM;
+    }
+  }
+  return 0;
+}
 static int rate_prepare(GofJob& j, int gi);
 static int quality_prepare(GofJob& j, SubmitPlan& s, int gi);
 static int d1_prepare(GofJob& j, SubmitPlan& s, int gi);
@@ -638,6 +668,7 @@ static int build_encoders(GofJob& j, SubmitPlan& s) {
     for (size_t q = 0; q < gs.size(); q++) {
       const int i = gs[q], io = s.occ_of[i];
       if (int rc = setup_encode(j.db[gi], j.dec_of[gi][q], (int)q, s.p[i], eb, j.pooled, j.err, &s.pool_jobs[gi], io >= 0 ? &s.occ_src[io] : nullptr, io, &s.occ_jobs)) return rc;
+      if (!j.frame_qp.empty()) eb.desc[q].frame_qp = j.frame_qp[i];
       const EncStreamDesc& d = eb.desc[q];
       if (feeds && s.p[i].video_type == RBT_VIDEO_OCCUPANCY && d.n_frames > 0) {
         OccSource& os = s.occ_src[i]; os.occ = d.src[0][0]; os.in_step = d.n_frames > 1 ? (size_t)(d.src[0][1] - d.src[0][0]) : 0; os.n = d.n_frames; os.ow = d.w; os.oh = d.h; os.pipeline = gi; }
@@ -656,6 +687,17 @@ static int build_encoders(GofJob& j, SubmitPlan& s) {
 // and PSNR floors ("transcoding to a PSNR floor"). Both are one walk with a direction (rbt_qp_walk.h) over rounds of trial encodes; they differ in how a walk is seeded
 // (seed_budgets, seed_floors), in whether a round carries distortion sums, and in how the public result is filled (fill_results).
 // the candidates of a round as an encode batch; in a job with floors the entries coded with occupancy_rd get the maps the occupancy pipeline made at submit
+// A pass over a subset of an entry's frames: everything the encoder and the distortion stage index by "picture k of the stream" - the source planes, the hints, the flat
+// words, the occupancy maps, the shared buffers - is picked through the explicit picture list d.pic, which round_sums_setup reads for the occupancy frame as well
+static void desc_subset(EncStreamDesc& d, const FramePass& p) {
+  std::vector<int> pic;
+  for (int f : p.frames) for (int k = 0; k < d.gop; k++) pic.push_back(f * d.gop + k);
+  auto pick = [&](auto& v) { if (v.empty()) return; typename std::remove_reference<decltype(v)>::type o; for (int k : pic) o.push_back(v[(size_t)k]); v.swap(o); };
+  for (int c = 0; c < 3; c++) pick(d.src[c]);
+  pick(d.hint_pm); pick(d.hint_dm); pick(d.occ4); pick(d.src_flat); pick(d.alias_pix); pick(d.alias_coef);
+  d.n_total = d.n_frames; d.n_frames = (int)pic.size(); d.pic.swap(pic);
+  d.frame_qp.assign(p.qps.begin(), p.qps.end());
+}
 static int round_fill_batch(GofJob& j, int gi, const std::vector<RoundCand>& cands, EncodeBatch& eb) {
   for (size_t e = 0; e < cands.size(); e++) {
     rbt_stream_params pp = j.params[j.groups[gi][cands[e].q]]; pp.qp = cands[e].qp;
@@ -667,6 +709,7 @@ static int round_fill_batch(GofJob& j, int gi, const std::vector<RoundCand>& can
     d.occ4.resize(d.n_frames); d.occ4_w = o.w4; d.occ4_h = o.h4;
     for (int k = 0; k < d.n_frames; k++) d.occ4[k] = o.maps + (size_t)((size_t)k * o.n / d.n_frames) * o.w4 * o.h4;
   }
+  for (size_t e = 0; e < cands.size(); e++) if (cands[e].fw >= 0) desc_subset(eb.desc[e], cands[e].pass);      // last: every table above is per picture of the stream
   return 0;
 }
 template <class Target> static TargetWalk new_walk(size_t q, int entry, const Target& t) { TargetWalk w; w.q = (int)q; w.entry = entry; w.lo = t.qp_min; w.hi = t.qp_max ? t.qp_max : 51; return w; }
@@ -697,6 +740,29 @@ static void seed_floors(GofJob& j, int gi, RoundPipe& r) {
     TargetWalk w = new_walk(q, gs[q], t); w.floor.floor_mdb = t.min_psnr_mdb; w.floor.region = t.region; w.floor.bit_depth = entry_bit_depth(j, gi, q);
     quality_seed(w, w.floor, j.params[gs[q]].qp);
     r.walks.push_back(std::move(w));
+  }
+}
+// Floors held frame by frame: every entry of the pipeline gets one walk per point-cloud frame, seeded like the entry's walk. An entry without a floor is a walk whose
+// range is its own QP alone: one pass, the figures reported per frame
+static void seed_frame_floors(GofJob& j, int gi, RoundPipe& r) {
+  const std::vector<int>& gs = j.groups[gi]; const DecodeBatch& db = j.db[gi];
+  for (size_t q = 0; q < gs.size(); q++) {
+    const rbt_quality_target& t = j.qtargets[gs[q]]; const int qp = j.params[gs[q]].qp, nf = db.stream_count[j.dec_of[gi][q]] / 2;
+    FrameWalks<TargetWalk> fw; fw.q = (int)q; fw.entry = gs[q]; fw.n_enc.assign((size_t)nf, 0);
+    for (int f = 0; f < nf; f++) {
+      TargetWalk w = new_walk(q, gs[q], t);
+      if (!t.min_psnr_mdb) w.lo = w.hi = std::min(51, std::max(0, qp));
+      w.floor.floor_mdb = t.min_psnr_mdb; w.floor.region = t.region; w.floor.bit_depth = entry_bit_depth(j, gi, q);
+      quality_seed(w, w.floor, qp);
+      if (has_d1(j, gs[q])) {      // a D1 target: the frame's walk is the D1 floor's on the frame's own cloud (one result per trial, so the statistic is that result)
+        const rbt_d1_target& d = j.d1[gs[q]].t;
+        if (d.min_d1_mdb) { w.lo = d.qp_min; w.hi = d.qp_max ? d.qp_max : 51; }
+        w.is_d1 = true; w.dist.floor_mdb = d.min_d1_mdb; w.dist.stat = RBT_D1_MIN;
+        d1_seed(w, w.dist, qp);
+      }
+      fw.frames.push_back(std::move(w));
+    }
+    r.fwalks.push_back(std::move(fw));
   }
 }
 // A D1 floor's walk is the PSNR floor's with D in place of the PSNR (rbt_d1_walk.h)
@@ -739,6 +805,15 @@ static bool walk_step(TargetWalk& w, int& need, int& dir, bool& alone) {
 static void name_round(const GofJob& j, int gi, RoundPipe& r, bool first) {
   const std::vector<int>& gs = j.groups[gi]; std::vector<int> qps; size_t k = 0;
   r.cands.clear();
+  if (j.per_frame) {      // every entry of the pipeline walks frame by frame: its passes (rbt_frame_walk.h), in group order
+    std::vector<FramePass> passes;
+    for (size_t e = 0; e < r.fwalks.size(); e++) {
+      FrameWalks<TargetWalk>& fw = r.fwalks[e];
+      frame_round(fw, [](TargetWalk& w, int& need, int& dir, bool& alone) { return walk_step(w, need, dir, alone); }, passes);
+      for (FramePass& p : passes) { RoundCand c{fw.q, j.params[fw.entry].qp, -1}; c.fw = (int)e; c.pass = std::move(p); r.cands.push_back(std::move(c)); }
+    }
+    return;
+  }
   for (size_t q = 0; q < gs.size(); q++) {
     if (k == r.walks.size() || r.walks[k].q != (int)q) { if (first) r.cands.push_back(RoundCand{(int)q, j.params[gs[q]].qp, -1}); continue; }
     TargetWalk& w = r.walks[k]; int need = 0, dir = 0; bool alone = false;
@@ -776,7 +851,8 @@ static int round_sums_setup(GofJob& j, int gi) {
       RbtSsePic P; memset(&P, 0, sizeof(P));
       for (int c = 0; c < 3; c++) { const int sh = c ? 1 : 0; P.a[c] = d.src[c][k] + (size_t)(d.src_y0 >> sh) * (size_t)(st >> sh) + (d.src_x0 >> sh); P.b[c] = f.out[c]; }
       P.w = d.w; P.h = d.h; P.a_stride = st; P.b_stride = f.cfg.w;
-      if (o.occ) { P.occ = o.occ + o.in_step * (size_t)((size_t)k * o.n / d.n_frames); P.ow = o.ow; P.scale = d.w / o.ow; }
+      const size_t pk = d.pic.empty() ? (size_t)k : (size_t)d.pic[k], pn = d.pic.empty() ? (size_t)d.n_frames : (size_t)d.n_total;      // picture pk of the stream's pn
+      if (o.occ) { P.occ = o.occ + o.in_step * (pk * o.n / pn); P.ow = o.ow; P.scale = d.w / o.ow; }
       r.sse->add(P);
     }
   }
@@ -815,6 +891,7 @@ static int d1_prepare(GofJob& j, SubmitPlan& s, int gi) {
     const int dw = c.w - 2 * isps.conf_win[0] - 2 * isps.conf_win[1], dh = c.h - 2 * isps.conf_win[2] - 2 * isps.conf_win[3];
     if (dw != a.width || dh != a.height) return refuse(i, "the displayed picture size is not atlas.width x atlas.height");
     if (cnt != a.map_count * E.t.n_frames) return refuse(i, "the picture count is not atlas.map_count x n_frames");
+    if (j.per_frame && a.map_count != 2) return refuse(i, "floors held frame by frame need atlas.map_count 2: a point-cloud frame is the two pictures that are coded as a pair");
     if (os.n != E.t.n_frames) return refuse(i, "the occupancy source does not hold n_frames pictures");
     if (os.ow * a.occupancy_precision != dw || os.oh * a.occupancy_precision != dh) return refuse(i, "atlas.occupancy_precision is not width / (output occupancy width)");
     // the decoded input of the occupancy source
@@ -911,18 +988,21 @@ static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, s
   const int i = j.groups[gi][q]; D1Entry& E = j.d1[i]; const rbt_atlas_params& a = E.t.atlas; PCloudCache& cache = *j.cloud_cache;
   const EncStreamDesc& d = eb.desc[e]; const int W = a.width, H = a.height, mc = a.map_count, nf = E.t.n_frames, peak = E.t.peak ? E.t.peak : 1023;
   const size_t ys = (size_t)W * H;
-  if (d.w != W || d.h != H || d.n_frames != mc * nf || (int)E.frames.size() != nf) { j.err = "internal: a D1 target does not fit its stream"; return RBT_ERR_PARAM; }
+  // a pass over a subset of the frames (desc_subset) codes np of the nf frames: coded pictures mc * i .. of the pass are stream pictures d.pic[mc * i] .., frame d.pic[mc * i] / mc -
+  // the gather descriptors go by the coded picture, the maps, the patch lists and the references by the frame; out is in pass order
+  const int np = d.n_frames / mc;
+  if (d.w != W || d.h != H || d.n_frames != mc * np || (d.pic.empty() ? np != nf : d.n_total != mc * nf) || (int)E.frames.size() != nf) { j.err = "internal: a D1 target does not fit its stream"; return RBT_ERR_PARAM; }
   DevPlanes geo; GatherSet gs;
   if (!geo.alloc(ys * (size_t)d.n_frames)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
-  out.assign(nf, rbt_d1_result());
+  out.assign(np, rbt_d1_result());
   rbtk::timer_begin(T_CENSUS);
   for (int k = 0; k < d.n_frames; k++) { const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k]; gs.add(f.out[0], f.cfg.w, W, H, geo.p + ys * (size_t)k); }
   int rc = gs.launch();
   if (rc) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
-  for (int f = 0; f < nf && !rc; f++) {
-    PCloud* c = nullptr;
-    rc = mapframe_cloud(j.err, cache, E.frames[f], geo.p + ys * (size_t)(mc * f), mc > 1 ? geo.p + ys * (size_t)(mc * f + 1) : nullptr, d.bd, &c, nullptr);
-    if (!rc) rc = pcloud_d1(j.err, E.ref[f] ? E.ref[f] : E.own_ref[f], c, peak, &out[f]);
+  for (int i = 0; i < np && !rc; i++) {
+    const int f = d.pic.empty() ? i : d.pic[(size_t)(mc * i)] / mc; PCloud* c = nullptr;
+    rc = mapframe_cloud(j.err, cache, E.frames[f], geo.p + ys * (size_t)(mc * i), mc > 1 ? geo.p + ys * (size_t)(mc * i + 1) : nullptr, d.bd, &c, nullptr);
+    if (!rc) rc = pcloud_d1(j.err, E.ref[f] ? E.ref[f] : E.own_ref[f], c, peak, &out[i]);
     pcloud_release(cache, c);
   }
   return d1_timed(j, E, rc);
@@ -1103,6 +1183,20 @@ static int finish_round(GofJob& j, int gi) {
   size_t at = 0;                                                    // (the words came back with the slice sizes)
   for (size_t e = 0; e < r.cands.size(); e++) {
     const EncStreamDesc& d = r.eb->desc[e]; const RoundCand& c = r.cands[e]; QualitySums sums;
+    if (c.fw >= 0) {      // a pass: every frame it carried goes to its own walk - its NAL units and the sums of its pictures
+      FrameWalks<TargetWalk>& fw = r.fwalks[c.fw];
+      std::vector<rbt_d1_result> clouds;                               // a D1 target: the clouds of the frames the pass carried, in pass order
+      if (has_d1(j, j.groups[gi][c.q])) if (int rc = d1_score(j, gi, c.q, *r.eb, e, clouds)) return rc;
+      for (size_t i = 0; i < c.pass.frames.size(); i++) {
+        TargetTried& t = fw.frames[c.pass.frames[i]].tried[c.pass.qps[i]];
+        frame_cut(outs[e], r.eb->pic_at[e], i, (size_t)d.gop, t.stream);
+        for (int k = 0; k < d.gop; k++, at++) quality_add_picture(t.sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
+        if (!clouds.empty()) t.d1.assign(1, clouds[i]);
+        fw.n_enc[c.pass.frames[i]]++;
+      }
+      fw.n_passes++;
+      continue;
+    }
     for (int k = 0; r.sse && k < d.n_frames; k++, at++) quality_add_picture(sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
     std::vector<rbt_d1_result> frames;                                // a D1 target: the candidate's clouds, from its reconstruction while the round's arena is alive
     if (has_d1(j, j.groups[gi][c.q])) if (int rc = d1_score(j, gi, c.q, *r.eb, e, frames)) return rc;
@@ -1176,6 +1270,24 @@ static void fill_results(GofJob& j, int gi) {
   }
   for (size_t q = 0; q < gs.size() && !j.color.empty(); q++) if (has_color(j, gs[q])) j.colorout[gs[q]].cloud_ms = j.color[gs[q]].cloud_ms;
 }
+// ... and of a pipeline whose entries walked frame by frame: per frame q*, qs, met, its encodes, its bytes and its figure at q*; the stream assembled from the passes
+static void fill_frame_results(GofJob& j, int gi) {
+  RoundPipe& r = j.pipes[gi];
+  j.fout.resize(j.n);
+  for (const FrameWalks<TargetWalk>& fw : r.fwalks) {
+    FrameFloorOut& o = j.fout[fw.entry]; std::vector<uint64_t> bytes;
+    frame_assemble(fw, r.o1[fw.q], bytes);
+    o.n_passes = fw.n_passes; o.bytes = r.o1[fw.q].size();
+    if (has_d1(j, fw.entry)) o.cloud_ms = j.d1[fw.entry].cloud_ms;
+    for (size_t f = 0; f < fw.frames.size(); f++) {
+      const TargetWalk& w = fw.frames[f]; const TargetTried& at = w.tried.find(w.qstar)->second; const QualitySums& s = at.sums;
+      o.q0 = w.is_d1 ? w.dist.q0 : w.floor.q0; o.bit_depth = w.floor.bit_depth; o.pictures += 2 * (uint64_t)fw.n_enc[f];
+      if (w.is_d1) o.d1.push_back(at.d1[0]);
+      o.frames.push_back(rbt_frame_pick{w.qstar, w.start, w.met, fw.n_enc[f], bytes[f], w.is_d1 ? (double)at.d1[0].psnr : quality_region_psnr(s, w.floor.region, w.floor.bit_depth)});
+      for (int c = 0; c < 3; c++) { o.sums.sse[c] += s.sse[c]; o.sums.samples[c] += s.samples[c]; o.sums.sse_occ[c] += s.sse_occ[c]; o.sums.samples_occ[c] += s.samples_occ[c]; }
+    }
+  }
+}
 // A pipeline with targets, in the wait half: its decoder is collected, the walks are seeded and the rounds run, one after the other, until every walk has settled. In a
 // job with floors the occupancy pipelines have been collected by then (gof_wait), so the pooled planes and the maps the rounds read are complete. (Measured and not
 // adopted, DESIGN.md 12: the rounds of a job's pipelines side by side, and the first rounds of the other jobs in flight enqueued ahead of their turn - both were slower
@@ -1185,8 +1297,9 @@ static int run_rounds(GofJob& j, int gi) {
   if (int rc = pipeline_decoded(j, gi)) return rc;
   D1Live d1_live{j, gi};                                            // (releases the pipeline's frames and reference clouds on every way out)
   ColorLive color_live{j, gi};                                      // (releases the frames of the pipeline's colour entries on every way out)
-  if (!j.d1.empty()) { seed_d1_floors(j, gi, r); if (int rc = d1_setup(j, gi)) return rc; }
+  if (!j.d1.empty()) { if (j.per_frame) seed_frame_floors(j, gi, r); else seed_d1_floors(j, gi, r); if (int rc = d1_setup(j, gi)) return rc; }
   else if (!j.color.empty()) { seed_color_floors(j, gi, r); if (int rc = color_setup(j, gi)) return rc; }
+  else if (j.per_frame && j.d1.empty()) seed_frame_floors(j, gi, r);
   else if (!j.qtargets.empty()) seed_floors(j, gi, r);
   else if (int rc = seed_budgets(j, gi, r, true)) return rc;
   r.o1.assign(n, {}); r.sums.assign(n, QualitySums()); r.d1.assign(n, {}); r.color.assign(n, {}); r.n_enc.assign(r.walks.size(), 0);
@@ -1197,6 +1310,8 @@ static int run_rounds(GofJob& j, int gi) {
     if (int rc = finish_round(j, gi)) return rc;
   }
   for (const TargetWalk& w : r.walks) if (!w.settled) { j.err = "internal: QP walk did not settle"; return RBT_ERR_PARAM; }
+  for (const FrameWalks<TargetWalk>& fw : r.fwalks) if (!fw.settled()) { j.err = "internal: QP walk did not settle"; return RBT_ERR_PARAM; }
+  if (j.per_frame) { fill_frame_results(j, gi); return 0; }
   fill_results(j, gi);
   for (TargetWalk& w : r.walks) r.o1[w.q].swap(w.tried[w.qstar].stream);
   return 0;
@@ -1229,6 +1344,9 @@ static int quality_prepare(GofJob& j, SubmitPlan& s, int gi) {
   for (size_t q = 0; q < gs.size(); q++) {
     const int i = gs[q], io = s.meas_of[i], ds = j.dec_of[gi][q], first = db.stream_first[ds], cnt = db.stream_count[ds];
     bool has = false;
+    if (j.per_frame && cnt % 2) {      // a frame is two pictures: a stream that ends with half a frame has no walk for it
+      j.err = "entry " + std::to_string(i) + ": floors held frame by frame need two pictures per point-cloud frame, the stream holds " + std::to_string(cnt);
+      j.refused = true; return RBT_ERR_PARAM; }
     if (io >= 0 && s.occ_src[io].n > 0 && cnt > 0) {
       const OccSource& os = s.occ_src[io]; const RbtStreamCfg& c = db.frames[first].cfg; const Sps& isps = db.stream_sps[ds];
       const int dw = c.w - 2 * isps.conf_win[0] - 2 * isps.conf_win[1], dh = c.h - 2 * isps.conf_win[2] - 2 * isps.conf_win[3];
@@ -1390,12 +1508,14 @@ static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
 // Phase A of a job: plan, build and upload everything, then enqueue. Every upload of the job is issued before its first kernel: a copy from pageable memory blocks the host
 // until the stream has reached it, and pipelines may share a stream. The first failure ends the submission (j.rc, j.err); gof_wait drains what was enqueued.
 GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
-                   const D1Request* d1, const ColorRequest* color) {
+                   const D1Request* d1, const ColorRequest* color, const std::vector<std::vector<int8_t>>* frame_qp, bool per_frame) {
   GofJob* J = new GofJob(); GofJob& j = *J;
+  j.per_frame = per_frame && (quality || d1);
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
   j.params.assign(p, p + n); j.n_in.assign(n_in, n_in + n);
   if (targets) j.targets.assign(targets, targets + n);
+  if (frame_qp) j.frame_qp = *frame_qp;
   if (quality) { j.qtargets.assign(quality, quality + n); j.qocc.assign(n, QualityOcc()); }
   if (d1) {      // a job with quality floors of 0, and the D1 targets with their patch lists copied
     j.qtargets.assign(n, rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, RBT_QUALITY_ALL, 0, 0}); j.qocc.assign(n, QualityOcc());
@@ -1419,6 +1539,7 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
   int rc = plan_pipelines(j, s, depth);
   j.t_gpu = now_ms();
   if (!rc) rc = build_decoders(j, s);
+  if (!rc) rc = check_frame_qp(j);
   if (!rc) rc = build_encoders(j, s);
   if (!rc) rc = launch_merged(j);
   // enqueue order: longest pipeline first - except that a pipeline whose occupancy maps others wait for goes in front of them (an event has to be recorded before it is waited for)
@@ -1429,7 +1550,7 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
 
 // phase B, shortest pipeline first: one sync per stream, then slice sizes -> pack -> NAL assembly. Consumes the job.
 int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* qresults, int* n_flat, rbt_d1_floor_result* d1results,
-             rbt_color_floor_result* cresults) {
+             rbt_color_floor_result* cresults, rbt_frame_floor_result* fresults) {
   std::unique_ptr<GofJob> guard(J); GofJob& j = *J;
   const int n = j.n, ng = j.ng; int rc = j.rc;
   rbt_stats& st = j.st; std::string& err = j.err;
@@ -1469,6 +1590,27 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
     if (quality && !j.is_pass[i] && p[i].video_type != RBT_VIDEO_OCCUPANCY && i < (int)j.qresults.size()) { qresults[i] = j.qresults[i]; continue; }
     quality_fill_result(qresults[i], p[i].qp, p[i].qp, p[i].qp, 1, j.is_pass[i] ? 0 : 1, (uint64_t)n_out[i], QualitySums(), 8);
   }
+  if (fresults) for (int i = 0; i < n; i++) memset(&fresults[i], 0, sizeof(fresults[i]));
+  if (fresults && !rc) for (int i = 0; i < n; i++) {
+    rbt_frame_floor_result& o = fresults[i];
+    o.qp_probe = p[i].qp; o.met_all = 1; o.bytes = (uint64_t)n_out[i];
+    quality_fill_result(o.sums, -1, -1, -1, 1, 0, o.bytes, QualitySums(), 8);
+    if (i >= (int)j.fout.size() || j.fout[i].frames.empty()) continue;
+    const FrameFloorOut& r = j.fout[i];
+    o.n_frames = (int)r.frames.size(); o.qp_probe = r.q0; o.n_passes = r.n_passes; o.pictures_encoded = r.pictures;
+    for (const rbt_frame_pick& f : r.frames) o.met_all &= f.met;
+    quality_fill_result(o.sums, -1, -1, -1, o.met_all, (int)(r.pictures / 2), o.bytes, r.sums, r.bit_depth);
+    o.frames = (rbt_frame_pick*)malloc(sizeof(rbt_frame_pick) * r.frames.size());
+    if (!o.frames) { rc = RBT_ERR_NOMEM; break; }
+    memcpy(o.frames, r.frames.data(), sizeof(rbt_frame_pick) * r.frames.size());
+    o.cloud_ms = r.cloud_ms;
+    if (!r.d1.empty()) {
+      o.d1 = (rbt_d1_result*)malloc(sizeof(rbt_d1_result) * r.d1.size());
+      if (!o.d1) { rc = RBT_ERR_NOMEM; break; }
+      memcpy(o.d1, r.d1.data(), sizeof(rbt_d1_result) * r.d1.size());
+    }
+  }
+  if (fresults && rc) { for (int i = 0; i < n; i++) { free(fresults[i].frames); free(fresults[i].d1); memset(&fresults[i], 0, sizeof(fresults[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; } }
   if (d1results && !rc) for (int i = 0; i < n; i++) {
     rbt_d1_floor_result& o = d1results[i]; memset(&o, 0, sizeof(o));
     o.qp = o.qp_probe = o.qp_start = p[i].qp; o.met = 1; o.n_encodes = j.is_pass[i] ? 0 : 1; o.bytes = (uint64_t)n_out[i];

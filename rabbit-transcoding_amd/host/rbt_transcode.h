@@ -15,11 +15,15 @@ struct PCloud; struct PCloudCache;
 struct D1Request { const rbt_d1_target* targets; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache; };
 // color: nullptr, or the colour targets of rbt_submit_gof_color (checked by the caller; not together with targets, quality or d1), resolved the same way
 struct ColorRequest { const rbt_color_target* targets; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache; };
+// frame_qp: nullptr, or per entry a QP per point-cloud frame (rbt_submit_gof_frame_qp; values and video types checked by the caller, the count against the stream's pictures
+// here: gof_refused), empty = the entry's own QP; not together with targets, quality, d1 or color
 GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr,
-                   const D1Request* d1 = nullptr, const ColorRequest* color = nullptr);
+                   const D1Request* d1 = nullptr, const ColorRequest* color = nullptr, const std::vector<std::vector<int8_t>>* frame_qp = nullptr, bool per_frame = false);   // per_frame: with quality, rbt_submit_gof_quality_frames
 int gof_wait(GofJob* j, rbt_stats& st, std::string& err, uint8_t** out, size_t* n_out, rbt_rate_result* results = nullptr, rbt_quality_result* quality_results = nullptr, int* n_flat = nullptr,
-             rbt_d1_floor_result* d1_results = nullptr, rbt_color_floor_result* color_results = nullptr);   // consumes the job
+             rbt_d1_floor_result* d1_results = nullptr, rbt_color_floor_result* color_results = nullptr, rbt_frame_floor_result* frame_results = nullptr);   // consumes the job
 bool gof_is_quality(const GofJob* j);           // a job of rbt_submit_gof_quality
+bool gof_is_quality_frames(const GofJob* j);    // a job of rbt_submit_gof_quality_frames
+bool gof_is_d1_frames(const GofJob* j);         // a job of rbt_submit_gof_d1_frames
 bool gof_is_d1(const GofJob* j);                // a job of rbt_submit_gof_d1
 bool gof_is_color(const GofJob* j);             // a job of rbt_submit_gof_color
 int gof_refused(const GofJob* j, std::string& err);   // != 0: the job's plan was refused before anything was built or enqueued (the code; the reason in err)

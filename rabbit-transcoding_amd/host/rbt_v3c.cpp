@@ -32,7 +32,9 @@ uint64_t count_pictures(const uint8_t* ss, size_t n) {
 // rate targets of the walk (rbt_transcode_v3c_rate): bits per picture by video type (0 = constant QP), and where the results go (two per GOF: geometry, attribute)
 struct WalkRate { uint32_t geometry_bits = 0, attribute_bits = 0; rbt_rate_result* per_gof = nullptr; bool on() const { return geometry_bits || attribute_bits; }
   // PSNR floors instead of budgets (rbt_transcode_v3c_quality): every job of the walk is a job of rbt_submit_gof_quality, floors of 0 included - its results carry the distortion
-  bool quality = false; int32_t geometry_floor = 0, attribute_floor = 0; int region = 0; rbt_quality_result* q_per_gof = nullptr; };
+  bool quality = false; int32_t geometry_floor = 0, attribute_floor = 0; int region = 0; rbt_quality_result* q_per_gof = nullptr;
+  // ... held frame by frame (rbt_transcode_v3c_quality_frames): the same walk over jobs of rbt_submit_gof_quality_frames
+  bool frames = false; rbt_frame_floor_result* f_per_gof = nullptr; };
 int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt_v3c_sink sink, void* user, const WalkRate& rate);
 }
 
@@ -181,6 +183,15 @@ int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt
   // jobs: the picked units of `per` consecutive owned GOFs each, as many in flight as the context allows (RBT_ERR_BUSY tells) AND as the device memory holds
   // a job of a walk with rate targets is collected with its results: entry k of the job is unit jb.unit[k]
   auto wait_job = [&](rbt_job* j, const std::vector<int>& unit, uint8_t** o, size_t* on) -> int {
+    if (rate.frames) {
+      std::vector<rbt_frame_floor_result> res(unit.size());
+      const int r = rbt_wait_gof_quality_frames(ctx, j, o, on, res.data());
+      for (size_t k = 0; k < unit.size() && !r; k++) {
+        const rbt_v3c_unit& u = U[unit[k]]; const int slot = u.video_type == RBT_VIDEO_GEOMETRY ? 2 * u.gof : u.video_type == RBT_VIDEO_ATTRIBUTE ? 2 * u.gof + 1 : -1;
+        if (slot >= 0 && rate.f_per_gof) { rbt_free(rate.f_per_gof[slot].frames); rate.f_per_gof[slot] = res[k]; } else rbt_free(res[k].frames);      // (a GOF that ran again replaces its first result)
+      }
+      return r;
+    }
     if (rate.quality) {
       std::vector<rbt_quality_result> res(unit.size());
       const int r = rbt_wait_gof_quality(ctx, j, o, on, res.data());
@@ -206,14 +217,15 @@ int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt
   std::vector<int> owned; for (int g = 0; g < n_gofs; g++) if (rbt_owns_gof(ctx, g) && !picks[g].empty()) owned.push_back(g);
   int per = p->gofs_per_job > 1 ? p->gofs_per_job : 1, announced = 0;
   // whatever way this function is left - error, exception - the jobs still in flight are collected, the caller's depth is put back and the buffers are freed
-  struct Guard { rbt_ctx* ctx; std::deque<Job>& q; int& announced; std::vector<Buf>& repl; bool quality;
+  struct Guard { rbt_ctx* ctx; std::deque<Job>& q; int& announced; std::vector<Buf>& repl; bool quality, frames;
     ~Guard() {
       while (!q.empty()) { Job jb = q.front(); q.pop_front(); std::vector<uint8_t*> o(jb.unit.size(), nullptr); std::vector<size_t> on(jb.unit.size(), 0);
-        if (quality) { std::vector<rbt_quality_result> res(jb.unit.size()); rbt_wait_gof_quality(ctx, jb.j, o.data(), on.data(), res.data()); } else rbt_wait_gof(ctx, jb.j, o.data(), on.data());
+        if (frames) { std::vector<rbt_frame_floor_result> res(jb.unit.size()); if (!rbt_wait_gof_quality_frames(ctx, jb.j, o.data(), on.data(), res.data())) for (auto& x : res) rbt_free(x.frames); }
+        else if (quality) { std::vector<rbt_quality_result> res(jb.unit.size()); rbt_wait_gof_quality(ctx, jb.j, o.data(), on.data(), res.data()); } else rbt_wait_gof(ctx, jb.j, o.data(), on.data());
         for (uint8_t* x : o) rbt_free(x); }
       if (announced) rbt_set_depth(ctx, announced);
       for (auto& b : repl) { free(b.p); b.p = nullptr; }
-    } } guard{ctx, q, announced, repl, rate.quality};
+    } } guard{ctx, q, announced, repl, rate.quality, rate.frames};
   if (p->gofs_per_job <= 0) {                                                 // job shape by the length of the walk; a short one runs with fewer, larger jobs
     int d = 0; announced = rbt_get_depth(ctx);
     if (announced < 1 || rbt_job_shape((int)owned.size(), announced, &per, &d) != RBT_OK) { announced = 0; return RBT_ERR_PARAM; }
@@ -286,7 +298,7 @@ int walk(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, rbt
     for (auto& c : conv) { ip.push_back(c.p); in_n.push_back(c.n); }
     if (!rc && (int)ip.size() > RBT_MAX_STREAMS) rc = RBT_ERR_PARAM;
     while (!rc) {
-      rc = rate.quality ? rbt_submit_gof_quality(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), qt.data(), &jb.j) : rate.on() ? rbt_submit_gof_rate(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), tg.data(), &jb.j) : rbt_submit_gof(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), &jb.j);
+      rc = rate.frames ? rbt_submit_gof_quality_frames(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), qt.data(), &jb.j) : rate.quality ? rbt_submit_gof_quality(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), qt.data(), &jb.j) : rate.on() ? rbt_submit_gof_rate(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), tg.data(), &jb.j) : rbt_submit_gof(ctx, (int)ip.size(), ip.data(), in_n.data(), sp.data(), &jb.j);
       if (rc == RBT_ERR_BUSY && !q.empty()) { rc = collect(true); continue; }  // every slot taken: take the oldest result first (and hand its GOFs over)
       note(rc);
       break;
@@ -341,6 +353,28 @@ int rbt_transcode_v3c_quality(rbt_ctx* ctx, const uint8_t* in, size_t n, const r
   for (auto& u : k.unit) { up.push_back(u.data()); un.push_back(u.size()); }
   if (!rc) rc = rbt_v3c_write(up.data(), un.data(), (int)up.size(), p->forced_unit_size_precision_bytes, out, n_out);
   if (rc || !per_gof) free(rate.q_per_gof); else *per_gof = rate.q_per_gof;
+  return rc;
+} RBT_CATCH
+// rbt_transcode_v3c_quality with the floors held by every point-cloud frame on its own (include/rbt.h)
+int rbt_transcode_v3c_quality_frames(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, int32_t geometry_min_psnr_mdb, int32_t attribute_min_psnr_mdb, int region,
+                                     uint8_t** out, size_t* n_out, rbt_frame_floor_result** per_gof) try {
+  if (!ctx || !in || !p || !out || !n_out) return RBT_ERR_PARAM;
+  *out = nullptr; *n_out = 0; if (per_gof) *per_gof = nullptr;
+  if (geometry_min_psnr_mdb < 0 || attribute_min_psnr_mdb < 0) { rbt_internal_set_error(ctx, "min_psnr_mdb must not be negative"); return RBT_ERR_PARAM; }
+  if (region != RBT_QUALITY_ALL && region != RBT_QUALITY_OCCUPIED) { rbt_internal_set_error(ctx, "region must be RBT_QUALITY_ALL or RBT_QUALITY_OCCUPIED"); return RBT_ERR_PARAM; }
+  rbt_v3c_stat st;
+  int rc = rbt_v3c_stats(in, n, &st);
+  if (rc) return rc;
+  const size_t slots = (size_t)(st.n_gofs > 0 ? st.n_gofs : 1) * 2;
+  WalkRate rate; rate.quality = rate.frames = true; rate.geometry_floor = geometry_min_psnr_mdb; rate.attribute_floor = attribute_min_psnr_mdb; rate.region = region;
+  rate.f_per_gof = (rbt_frame_floor_result*)calloc(slots, sizeof(rbt_frame_floor_result));
+  if (!rate.f_per_gof) return RBT_ERR_NOMEM;
+  Keep k;
+  rc = walk(ctx, in, n, p, keep_units, &k, rate);
+  std::vector<const uint8_t*> up; std::vector<size_t> un;
+  for (auto& u : k.unit) { up.push_back(u.data()); un.push_back(u.size()); }
+  if (!rc) rc = rbt_v3c_write(up.data(), un.data(), (int)up.size(), p->forced_unit_size_precision_bytes, out, n_out);
+  if (rc || !per_gof) { for (size_t i = 0; i < slots; i++) free(rate.f_per_gof[i].frames); free(rate.f_per_gof); } else *per_gof = rate.f_per_gof;
   return rc;
 } RBT_CATCH
 // rbt_transcode_v3c with byte budgets for the geometry / attribute units (include/rbt.h)
