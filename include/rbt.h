@@ -813,6 +813,54 @@ int rbt_transcode_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annex
 int rbt_transcode_v3c_quality_frames(rbt_ctx* ctx, const uint8_t* in, size_t n, const rbt_v3c_params* p, int32_t geometry_min_psnr_mdb, int32_t attribute_min_psnr_mdb, int region,
                                      uint8_t** out, size_t* n_out, rbt_frame_floor_result** per_gof);
 
+/* ---- a QP per CTB (csrc/rbt_qpmap.h, host/rbt_transcode.cpp encode_plan) ----
+ * Every call above spends one QP on a whole picture. An atlas picture is a few dozen patches and the padding between them, and what a V-PCC user steers is the patch. Here a
+ * geometry / attribute entry may carry a map with one QP per CTB and point-cloud frame: M[f][r][c], n_frames * h_ctb * w_ctb values, row-major. It is the building block,
+ * as the QP list was for the floors held frame by frame; floors and byte caps per patch are not built on it yet.
+ *
+ * Let T be the target QP of a CTB: max(0, M[f][r][c] - 3) in picture 2f and M[f][r][c] in picture 2f + 1, the constant-QP path's own I / P rule.
+ * 1. Decisions. Everything the encoder derives from the QP takes T of the CTB it works in instead of the slice's QP: the quantiser and the dequantiser, the chroma QPs, the
+ *    lambdas of the analysis, of the closed-loop decisions and of the SAO decision, the rounding offsets. Nothing else about a decision changes.
+ * 2. Parameter sets. Those of rbt_transcode_gof at params[i].qp, except cu_qp_delta_enabled_flag = 1 and diff_cu_qp_delta_depth = 0 in the PPS of an entry that carries a
+ *    map: the quantisation group is the CTB.
+ * 3. Slice QP. SliceQpY of every independent slice segment is T of its first CTB; the dependent segments of a wavefront picture inherit it.
+ * 4. Signalling (H.265 7.3.8.14, 8.6.1). In a CTB the first transform unit in decoding order with a luma or chroma cbf carries cu_qp_delta_abs / cu_qp_delta_sign_flag, no
+ *    later unit of that CTB does. The value d is the one in -(26 + QpBdOffset / 2) .. 25 + QpBdOffset / 2 with wrap(pred + d) = T, wrap being the modular rule of 8.6.1:
+ *    it is not T - pred where that leaves the range (CTB 0 next to CTB 51 is legal).
+ * 5. Prediction. With the group as large as the CTB the left and upper neighbours of 8.6.1 are never in the same CTB, so pred = qPY_PREV: the QpY of the last coding unit
+ *    of the previous CTB in decoding order, SliceQpY at the first CTB of a slice and, in wavefront mode, of every CTB row. In closed form: pred(c) is T of the nearest
+ *    earlier CTB of the same slice (same row under wavefront) that has any cbf, SliceQpY if there is none.
+ * 6. The QpY a decoder derives, and the deblocking filter reads: pred(c), not T, for a coding unit of a CTB that comes before the first unit with a cbf, and for every unit
+ *    of a CTB without any cbf (skipped P CUs mostly); T from the coding unit with the first cbf on. The encoder's loop filters read the same values, so that the stream
+ *    decodes to the encoder's reconstruction (md5_sei says so picture by picture).
+ * 7. No map. An entry with n_frames 0 and qp NULL, or maps == NULL, is coded as rbt_submit_gof codes it, byte for byte; the PPS flag stays 0.
+ * 8. Uniform map. If every M[f][r][c] == q every cu_qp_delta coded is 0 and every QpY is the slice's: the decoded pictures equal those of C(q), rbt_transcode_gof's stream
+ *    at qp = q, sample for sample, and the hash SEI NAL units are those of C(q) byte for byte. A map that is constant per frame, M[f][..] == Q[f], decodes to what
+ *    rbt_transcode_gof_frame_qp with the list Q decodes to, hash SEIs included; the bytes differ by the PPS flag and the zero deltas.
+ * 9. occupancy_rd, the input-mode hints, the flat-chroma fill, verify_md5, md5_sei, preset, log2_ctb 4..6, every slice structure and every job depth behave as in the
+ *    constant-QP path. A slice buffer is sized from the lowest T of its CTBs; overflow stays RBT_ERR_OUTPUT.
+ * 10. RBT_ERR_PARAM (reason in rbt_last_error; nothing is submitted and the context stays usable): struct_size that is not sizeof(rbt_qp_map); a map on an occupancy entry
+ *    (coded losslessly); n_frames that is not pictures / 2, or a stream with an odd picture count; w_ctb / h_ctb that are not the CTB columns / rows of the output pictures
+ *    at the entry's log2_ctb; a value outside 0..51; a map without its counts, or counts without a map.
+ * The maps are copied at submit. The job is a job of rbt_submit_gof in every other respect: depth, rbt_job_memory, rbt_wait_gof, shared pipelines. Maps together with a rate,
+ * quality, D1 or colour target are not offered.
+ * Not built: floors and byte caps per patch, a map in the container-level calls (rbt_transcode_v3c), quantisation groups smaller than the CTB. */
+typedef struct {
+  uint32_t struct_size;   /* sizeof(rbt_qp_map): checked */
+  int n_frames;           /* pictures / 2; 0 with qp NULL = no map */
+  int w_ctb, h_ctb;       /* CTB columns / rows of the OUTPUT pictures at the entry's log2_ctb (0 = 5): ceil(w / ctb), ceil(h / ctb) */
+  const int8_t* qp;       /* M[f][r][c], n_frames * h_ctb * w_ctb values, row-major, 0..51 */
+} rbt_qp_map;
+int rbt_submit_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_qp_map* maps, rbt_job** job);   /* collected by rbt_wait_gof */
+int rbt_transcode_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_qp_map* maps,
+                             uint8_t** annexb_out, size_t* n_out);   /* submit + wait */
+/* Host helper, no device work: the map of one frame from its patches. CTB (c, r) of a picture of atlas->width x atlas->height samples cut into CTBs of 1 << log2_ctb gets the
+ * minimum of patch_qp[k] over the patches whose rectangle - u0, v0, size_u0, size_v0 in blocks of atlas->occupancy_resolution - meets the CTB, background_qp where none
+ * does. out: h_ctb * w_ctb values, row-major. RBT_ERR_PARAM: a null argument (patches and patch_qp may be NULL with n_patches 0), log2_ctb outside 4..6, w_ctb / h_ctb
+ * that are not ceil(width / ctb), ceil(height / ctb), a QP outside 0..51, occupancy_resolution < 1. A patch that reaches beyond the atlas is clipped to it. */
+int rbt_qp_map_from_patches(const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const int8_t* patch_qp, int background_qp,
+                            int log2_ctb, int8_t* out, int w_ctb, int h_ctb);
+
 /* ---- normal estimation (csrc/rbt_normals.h) ----
  * D2 needs normals on the source. Where a sequence comes without them, the reference's PccAppNormalGenerator makes them (PCCNormalsGenerator.cpp: a kd-tree query of the
  * 16 nearest neighbours, a covariance matrix and a 3 x 3 eigen-decomposition per point, on the CPU). This is that stage on the index of a device cloud.

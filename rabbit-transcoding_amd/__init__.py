@@ -137,6 +137,23 @@ class FrameQp(C.Structure):
         super().__init__(C.sizeof(FrameQp), len(qps), self._keep if qps else None)
 
 
+class QpMap(C.Structure):
+    """rbt_qp_map: one QP per CTB and point-cloud frame of an entry, from an integer array M[f][r][c] (n_frames x h_ctb x w_ctb); struct_size is filled in. No argument = no
+    map: the entry is coded at its own QP"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_frames", C.c_int), ("w_ctb", C.c_int), ("h_ctb", C.c_int), ("qp", C.POINTER(C.c_int8))]
+
+    def __init__(self, m=None):
+        if m is None:
+            self._keep = None
+            super().__init__(C.sizeof(QpMap), 0, 0, 0, None)
+            return
+        m = np.ascontiguousarray(np.asarray(m), dtype=np.int8)
+        if m.ndim != 3:
+            raise ValueError("a QP map is M[f][r][c]: three dimensions")
+        self._keep = m
+        super().__init__(C.sizeof(QpMap), m.shape[0], m.shape[2], m.shape[1], m.ctypes.data_as(C.POINTER(C.c_int8)))
+
+
 RBT_QUALITY_ALL, RBT_QUALITY_OCCUPIED = 0, 1
 
 
@@ -308,6 +325,9 @@ def load(path=None):
     L.rbt_transcode_v3c.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(V3CParams), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_submit_gof_frame_qp.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(FrameQp), C.POINTER(C.c_void_p)]
     L.rbt_transcode_gof_frame_qp.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(FrameQp), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    L.rbt_submit_gof_qp_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QpMap), C.POINTER(C.c_void_p)]
+    L.rbt_transcode_gof_qp_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QpMap), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    L.rbt_qp_map_from_patches.argtypes = [C.POINTER(AtlasParams), C.POINTER(Patch), C.c_int, C.POINTER(C.c_int8), C.c_int, C.c_int, C.POINTER(C.c_int8), C.c_int, C.c_int]
     L.rbt_submit_gof_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(RateTarget), C.POINTER(C.c_void_p)]
     L.rbt_wait_gof_rate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(RateResult)]
     L.rbt_transcode_gof_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(RateTarget), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
@@ -379,6 +399,20 @@ def job_shape(n_gofs, max_jobs=16, lib=None):
     if rc != 0:
         raise RbtError(rc, L.rbt_strerror(rc).decode())
     return g.value, d.value
+
+
+def qp_map_from_patches(atlas, patches, patch_qp, background_qp, log2_ctb=5, lib=None):
+    """rbt_qp_map_from_patches (host only): the QP map of one frame, int8 [h_ctb, w_ctb] - per CTB the lowest patch_qp of the patches that meet it, background_qp where none does"""
+    L = lib or load()
+    ctb = 1 << log2_ctb
+    wc, hc = (atlas.width + ctb - 1) // ctb, (atlas.height + ctb - 1) // ctb
+    n = len(patches)
+    out = np.zeros((max(hc, 0), max(wc, 0)), np.int8)
+    rc = L.rbt_qp_map_from_patches(C.byref(atlas), (Patch * max(1, n))(*patches), n, (C.c_int8 * max(1, n))(*patch_qp), background_qp, log2_ctb,
+                                   out.ctypes.data_as(C.POINTER(C.c_int8)), wc, hc)
+    if rc != 0:
+        raise RbtError(rc, L.rbt_strerror(rc).decode())
+    return out
 
 
 def byte_to_sample_stream(data: bytes, lib=None):
@@ -659,6 +693,24 @@ class Context:
         """rbt_transcode_gof_frame_qp: submit + wait"""
         lists = self._frame_qp(lists)
         return self._transcode(self.L.rbt_transcode_gof_frame_qp, streams, params, lists, FrameQp)
+
+    @staticmethod
+    def _qp_maps(maps):
+        return [m if isinstance(m, QpMap) else QpMap(m) for m in maps]
+
+    def submit_gof_qp_map(self, streams, params, maps):
+        """rbt_submit_gof_qp_map: submit_gof with, per entry, a map M[f][r][c] of one QP per CTB and point-cloud frame (None = the entry's own QP) or a QpMap; maps=None hands
+        the library a null pointer (rbt_submit_gof). Returns a job for wait_gof"""
+        if maps is None:
+            job = C.c_void_p()
+            self._chk(self.L.rbt_submit_gof_qp_map(self.h, *self._gof_args(streams, params), None, C.byref(job)))
+            return (job, len(streams))
+        maps = self._qp_maps(maps)      # (alive until the call returns: the library copies the maps)
+        return self._submit(self.L.rbt_submit_gof_qp_map, streams, params, maps, QpMap)
+
+    def transcode_gof_qp_map(self, streams, params, maps):
+        """rbt_transcode_gof_qp_map: submit + wait"""
+        return self.wait_gof(self.submit_gof_qp_map(streams, params, maps))
 
     def submit_gof_rate(self, streams, params, targets):
         """rbt_submit_gof_rate: submit_gof with one RateTarget per entry (target_bytes 0 = constant QP); returns a job for wait_gof_rate"""

@@ -16,6 +16,7 @@
 #include "rbt_cabac.h"
 #include "rbt_recon.h"
 #include "rbt_filter.h"
+#include "rbt_qpmap.h"
 
 RBT_CONST uint16_t k_lambda16[76] = {3,    3,    4,    4,    5,    5,    6,    7,    8,    9,    10,   11,   12,   14,   15,   17,   19,   22,   24,
                                      27,   30,   34,   38,   43,   48,   54,   61,   68,   77,   86,   97,   108,  122,  137,  153,  172,  193,  217,
@@ -92,6 +93,21 @@ RBT_DEV int en_chroma_qp(const RbtFrame* f, const RbtSlice* sl, int c_idx, int q
   int qpi = rbt_clip3(-bdo, 57, qp_y + off);
   return (qpi < 0 ? qpi : rbt_chroma_qp(qpi)) + bdo;
 }
+// QpY the encoder codes CTB ctb_addr with (include/rbt.h "a QP per CTB", rule 1): the CTB's entry of the picture's map, the slice's QP where the picture carries none.
+// Wave-uniform; every decision of the analysis, the closed-loop stages and the SAO decision takes its QP from here.
+// QPMAP: the stages that read a QP come in two instantiations. The constant-QP one never looks at the map - it is the code it was before maps existed, register for register
+// (profiles/qp_map.txt: through one instantiation the look cost the entropy coder, the analysis and the row kernel scalar registers they do not have). The other one serves
+// the batches that hold a picture with a map (rbtk::enc_qp_map_variant); a picture without one in such a batch takes the slice's QP there too. The serial host emulation
+// calls one instantiation for everything, so there the default asks.
+#ifdef RBT_HOSTEMU
+#define EN_QP_ASK true
+#else
+#define EN_QP_ASK false
+#endif
+template <bool QPMAP> RBT_DEV int en_ctb_qp(const RbtFrame* f, const RbtSlice* sl, int ctb_addr) {
+  if constexpr (QPMAP) { const int8_t* m = rbt_uni_ptr(f->qp_map); if (m != nullptr) return RBT_UNI(m[ctb_addr]); }
+  return sl->qp;
+}
 
 // ------------------------------------------------------------------------------------------------ analysis (I pictures)
 // availability (6.4.1) of luma position (xn,yn) as intra reference of the block at (xc,yc), both inside or next to CTB
@@ -115,7 +131,7 @@ struct RbtAnalyseLds {
   uint8_t hint[64];                      // transcoder: the input stream's luma intra mode of the quadrant's 4x4 units (uy * 8 + ux; 255 = not intra / outside)
 };
 RBT_DEV int en_nb_unit_av(const EnCtbNb* q, int p, int x0, int y0, int S) { int xn, yn; rc_nb_unit_xy(p, x0, y0, S, 0, &xn, &yn); return en_avail(q, x0, y0, xn, yn); }   // unit p of the block at (x0,y0) of the picture (rc_nb_unit_xy)
-RBT_DEV void en_analyse_ctb(RbtFrame* f, const RbtSlice* slices, int ctb_addr, RBT_LDS_AS RbtAnalyseLds* l) {
+template <bool QPMAP = EN_QP_ASK> RBT_DEV void en_analyse_ctb(RbtFrame* f, const RbtSlice* slices, int ctb_addr, RBT_LDS_AS RbtAnalyseLds* l) {
   const RbtStreamCfg gcopy = rc_cfg_uni(&f->cfg); const RbtStreamCfg* g = &gcopy;
   int ctb = 1 << g->log2_ctb, rx = ctb_addr % g->w_ctb, ry = ctb_addr / g->w_ctb, cx = rx << g->log2_ctb, cy = ry << g->log2_ctb;
   const int my_slice = f->ctb_slice[ctb_addr];
@@ -241,7 +257,7 @@ RBT_DEV void en_analyse_ctb(RbtFrame* f, const RbtSlice* slices, int ctb_addr, R
       }
     }
     RBT_SYNC_LDS();
-    int lam = k_lambda16[rbt_clip3(0, 75, sl->qp + 6 * (g->bit_depth - 8))], pen = (lam * RBT_SPLIT_BITS) >> 4;
+    int lam = k_lambda16[rbt_clip3(0, 75, en_ctb_qp<QPMAP>(f, sl, ctb_addr) + 6 * (g->bit_depth - 8))], pen = (lam * RBT_SPLIT_BITS) >> 4;
     for (int si = 1; si < 3; si++) {
       int S = 8 << si; if (S > qs) break;
       int nb = qs / S, nbc = nb * 2;
@@ -805,12 +821,12 @@ template <int TL2> RBT_DEV int en_tile_intra_tb_cpair(const EnCtbCtx* e, RbtFram
 }
 // carry_left: the CTB to the left was coded by this wave just before (its reconstruction is still in the tile): take the
 // left border from LDS instead of reading back stores that may still be in flight
-template <int TL2> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices, int ctb_addr, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int carry_left) {
+template <int TL2, bool QPMAP = EN_QP_ASK> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices, int ctb_addr, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int carry_left) {
   EnCtbCtx gcopy; en_ctb_ctx(&gcopy, f); const RbtStreamCfg* g = &gcopy; const EnCtbCtx* e = &gcopy;
   RBT_LDS_AS RbtEncTileT<TL2>* t = &L->t;
   const int ctb = 1 << g->log2_ctb, n4 = ctb >> 2, n8 = ctb >> 3, rx = ctb_addr % g->w_ctb, ry = ctb_addr / g->w_ctb, cx = rx << g->log2_ctb, cy = ry << g->log2_ctb;
   const RbtSlice* sl = &slices[f->ctb_slice[ctb_addr]];
-  const int qp_y = sl->qp, bd = g->bit_depth;
+  const int qp_y = en_ctb_qp<QPMAP>(f, sl, ctb_addr), bd = g->bit_depth;
   const int qp_l = qp_y + 6 * (bd - 8), qp_cb = en_chroma_qp(f, sl, 1, qp_y), qp_cr = en_chroma_qp(f, sl, 2, qp_y);
   const int tu_rd = g->th_depth_intra > 0, lam16 = k_lambda16[rbt_clip3(0, 75, qp_l)], lam2 = lam16 * lam16;
   // Flat source: Cb / Cr of the source are v = 1 << (bd - 1), so are the references of every chroma block (substituted, or reconstructed by this rule),
@@ -921,7 +937,7 @@ template <int TL2> RBT_DEV void en_intra_ctb(RbtFrame* f, const RbtSlice* slices
 }
 
 // ------------------------------------------------------------------------------------------------ P pictures: one CTB
-RBT_DEV void en_inter_ctb(RbtFrame* frames, RbtFrame* f, const RbtSlice* slices, int ctb_addr, RBT_LDS_AS RbtEncLds* l) {
+template <bool QPMAP = EN_QP_ASK> RBT_DEV void en_inter_ctb(RbtFrame* frames, RbtFrame* f, const RbtSlice* slices, int ctb_addr, RBT_LDS_AS RbtEncLds* l) {
   const RbtStreamCfg* g = &f->cfg;
   const RbtFrame* ref = &frames[f->ref_frame];
   int ctb = 1 << g->log2_ctb, cx = (ctb_addr % g->w_ctb) << g->log2_ctb, cy = (ctb_addr / g->w_ctb) << g->log2_ctb;
@@ -932,7 +948,7 @@ RBT_DEV void en_inter_ctb(RbtFrame* frames, RbtFrame* f, const RbtSlice* slices,
   if (ctb_addr == 0 && RBT_LANE0) f->chroma_flat = (uint32_t)flat;
   EN_FLAT_COUNT(1, flat);
   const RbtSlice* sl = &slices[f->ctb_slice[ctb_addr]];
-  int qp_y = sl->qp, bd = g->bit_depth;
+  int qp_y = en_ctb_qp<QPMAP>(f, sl, ctb_addr), bd = g->bit_depth;
   int qp[3] = {qp_y + 6 * (bd - 8), en_chroma_qp(f, sl, 1, qp_y), en_chroma_qp(f, sl, 2, qp_y)};
   int n16 = ctb / 16;
   for (int b = 0; b < n16 * n16; b++) {
@@ -990,6 +1006,7 @@ RBT_DEV void en_inter_ctb(RbtFrame* frames, RbtFrame* f, const RbtSlice* slices,
 // ------------------------------------------------------------------------------------------------ entropy coding
 struct RbtEnt { RbtFrame* f; const RbtSlice* sl; int slice_idx; RbtCabacEnc c; RBT_LDS_AS RbtEntropyLds* l;
                 int w, h, log2_ctb, log2_min_cb, tq_bypass_enabled, is_p, cx, cy, th_intra;
+                int dqp;      // QP per CTB: 0x100 | cu_qp_delta + 64 while the CTB's delta is still to be coded (its first transform unit with a cbf codes it), else 0
 #ifdef RBT_PROFILE
                 unsigned long long t_stage, t_res, t_cu, t_resA, t_resB; unsigned n_cu, n_tb, n_bins;
 #endif
@@ -1160,7 +1177,18 @@ RBT_DEV void en_stage_ctb(RbtEnt* s, int cx, int cy) {
   s->t_stage += __builtin_readcyclecounter() - ts_;
 #endif
 }
-RBT_DEV void en_write_cu(RbtEnt* s, int x0, int y0, int log2, int depth) {
+// cu_qp_delta_abs / cu_qp_delta_sign_flag (7.3.8.14, 9.3.3.10) as the parser reads them (pz_transform_unit): up to five prefix bins, the first on its own context, the rest
+// on the second, an EG0 bypass suffix behind five ones, the sign in bypass
+RBT_DEV void en_write_qp_delta(RbtEnt* s) {
+  RbtCabacEnc* c = &s->c;
+  const int d = (RBT_UNI(s->dqp) & 0xFF) - 64, a = rbt_abs(d);
+  s->dqp = 0;
+  for (int i = 0; i < rbt_min(a, 5); i++) rbt_ce_bin0(c, CTX_CU_QP_DELTA + (i ? 1 : 0), 1);
+  if (a < 5) rbt_ce_bin0(c, CTX_CU_QP_DELTA + (a ? 1 : 0), 0);
+  else { int r = a - 5, k = 0; while (r >= (1 << k)) { rbt_ce_bypass(c, 1); r -= 1 << k; k++; } rbt_ce_bypass(c, 0); if (k) rbt_ce_bypass_n(c, (uint32_t)r, k); }
+  if (a) rbt_ce_bypass(c, d < 0);
+}
+template <bool QPMAP> RBT_DEV void en_write_cu(RbtEnt* s, int x0, int y0, int log2, int depth) {
   RbtCabacEnc* c = &s->c; const RbtFrame* f = s->f; RBT_LDS_AS RbtEntropyLds* l = s->l;
 #ifdef RBT_PROFILE
   unsigned long long tc_ = __builtin_readcyclecounter(); s->n_cu++;
@@ -1233,6 +1261,7 @@ RBT_DEV void en_write_cu(RbtEnt* s, int x0, int y0, int log2, int depth) {
         }
         const int qy_cbf = (fl[b] & RBT_CU_CBF_Y) != 0;
         rbt_ce_bin0(c, CTX_CBF_LUMA + 0, qy_cbf);
+        if constexpr (QPMAP) if (s->dqp && (qy_cbf | (log2 > 3 ? qcb | qcr : pcb | pcr))) en_write_qp_delta(s);      // cbfChroma of a 4x4 luma block is the 8x8 unit's (7.3.8.10)
         if (qy_cbf) en_write_residual(s, 0, en_lv(l, 0, s->log2_ctb) + qy * ctb + qx, ctb, log2 - 1, en_scan_idx(1, log2 - 1, 0, mode), log2 == 3 ? (cu_ts >> b) & 1 : 0);
         if (log2 > 3) {
           if (qcb) en_write_residual(s, 1, en_lv(l, 1, s->log2_ctb) + (qy >> 1) * (ctb >> 1) + (qx >> 1), ctb >> 1, log2 - 2, en_scan_idx(1, log2 - 2, 1, mode));
@@ -1251,6 +1280,7 @@ RBT_DEV void en_write_cu(RbtEnt* s, int x0, int y0, int log2, int depth) {
   rbt_ce_bin0(c, CTX_CBF_CHROMA + 0, cbf_cb);
   rbt_ce_bin0(c, CTX_CBF_CHROMA + 0, cbf_cr);
   if (!is_p || cbf_cb || cbf_cr) rbt_ce_bin0(c, CTX_CBF_LUMA + 1, cbf_y);
+  if constexpr (QPMAP) if (s->dqp && (cbf_y | cbf_cb | cbf_cr)) en_write_qp_delta(s);
 #ifdef RBT_PROFILE
   unsigned long long tr_ = __builtin_readcyclecounter(); s->t_cu += tr_ - tc_;
 #endif
@@ -1262,7 +1292,7 @@ RBT_DEV void en_write_cu(RbtEnt* s, int x0, int y0, int log2, int depth) {
 #endif
   (void)depth;
 }
-RBT_DEV void en_write_quadtree(RbtEnt* s, int x0, int y0, int log2) {
+template <bool QPMAP> RBT_DEV void en_write_quadtree(RbtEnt* s, int x0, int y0, int log2) {
   // stack-free depth-first walk (per-level child counters packed in one register, see the parser's pz_coding_quadtree)
   RBT_LDS_AS RbtEntropyLds* l = s->l;
   int lvl = 0, x = x0, y = y0, lg = log2;
@@ -1281,7 +1311,7 @@ RBT_DEV void en_write_quadtree(RbtEnt* s, int x0, int y0, int log2) {
         const int cl = l2l != 0xFF && (s->log2_ctb - l2l) > lvl, ca = l2a != 0xFF && (s->log2_ctb - l2a) > lvl;
         rbt_ce_bin0(&s->c, CTX_SPLIT_CU + (cl ? 1 : 0) + (ca ? 1 : 0), split);
       }
-      if (!split) { en_write_cu(s, x, y, lg, lvl); st = 4; } else st = 0;
+      if (!split) { en_write_cu<QPMAP>(s, x, y, lg, lvl); st = 4; } else st = 0;
     }
     while (st < 4 && (x + (st & 1) * h >= s->w || y + (st >> 1) * h >= s->h)) st++;   // children outside the picture are skipped
     if (st < 4) {
@@ -1341,14 +1371,14 @@ RBT_DEV void en_wave_sum16(const int (&v)[16], RBT_LDS_AS int32_t* dst) {
   }
 #endif
 }
-template <bool REGION> RBT_DEV void en_sao_ctb(RbtFrame* f, const RbtSlice* slices, int ctb_addr, RBT_LDS_AS RbtSaoLds* L, RBT_LDS_AS uint16_t* ry, RBT_LDS_AS uint16_t* rc0, RBT_LDS_AS uint16_t* rc1) {
+template <bool REGION, bool QPMAP = EN_QP_ASK> RBT_DEV void en_sao_ctb(RbtFrame* f, const RbtSlice* slices, int ctb_addr, RBT_LDS_AS RbtSaoLds* L, RBT_LDS_AS uint16_t* ry, RBT_LDS_AS uint16_t* rc0, RBT_LDS_AS uint16_t* rc1) {
   const RbtStreamCfg gcopy = rc_cfg_uni(&f->cfg); const RbtStreamCfg* g = &gcopy;
   const int ctb = 1 << g->log2_ctb, cxi = ctb_addr % g->w_ctb, cyi = ctb_addr / g->w_ctb, bd = g->bit_depth, has_occ = RBT_UNI(f->occ4 != nullptr);
   // flat reconstruction of a flat source: source minus reconstruction is 0 in Cb and Cr, every offset is 0 and the chroma type is 0 - no chroma statistics
   const int flat = RBT_UNI(f->chroma_flat) != 0;
   EN_FLAT_COUNT(2, flat);
   const RbtSlice* sl = &slices[f->ctb_slice[ctb_addr]];
-  const long long lam16 = k_lambda16[rbt_clip3(0, 75, sl->qp + 6 * (bd - 8))], lam = lam16 * lam16;
+  const long long lam16 = k_lambda16[rbt_clip3(0, 75, en_ctb_qp<QPMAP>(f, sl, ctb_addr) + 6 * (bd - 8))], lam = lam16 * lam16;
   // a CTB made of skipped CUs only is a copy of the (already filtered) reference: no statistics, no offsets (P pictures are mostly that)
   int all_skip = 0;
   if (f->ref_frame >= 0) {
@@ -1530,7 +1560,7 @@ RBT_DEV void en_write_sao(RbtCabacEnc* c, const RbtFrame* f, int addr, int rx, i
     } else if (ci < 2) rbt_ce_bypass_n(c, (uint32_t)en_sao_byte(p, 6 + ci), 2);
   }
 }
-RBT_DEV void en_entropy_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx, uint8_t* out, RBT_LDS_AS RbtEntropyLds* l) {
+template <bool QPMAP = EN_QP_ASK> RBT_DEV void en_entropy_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx, uint8_t* out, RBT_LDS_AS RbtEntropyLds* l) {
   RbtEnt s; s.sl = &slices[slice_idx]; s.f = &frames[RBT_UNI(s.sl->frame)]; s.slice_idx = slice_idx; s.l = l;
   const RbtSlice* sl = s.sl; const RbtStreamCfg* g = &s.f->cfg;
   s.w = RBT_UNI(g->w); s.h = RBT_UNI(g->h); s.log2_ctb = RBT_UNI(g->log2_ctb); s.log2_min_cb = RBT_UNI(g->log2_min_cb); s.tq_bypass_enabled = RBT_UNI(g->tq_bypass_enabled);
@@ -1550,11 +1580,15 @@ RBT_DEV void en_entropy_slice(RbtFrame* frames, RbtSlice* slices, int slice_idx,
   unsigned long long tall_ = __builtin_readcyclecounter(); s.t_stage = s.t_res = s.t_cu = s.t_resA = s.t_resB = 0; s.n_cu = s.n_tb = s.n_bins = 0;
 #endif
   const int n_ctbs = RBT_UNI(sl->n_ctbs), first = RBT_UNI(sl->ctb_addr), wc = (s.w + (1 << s.log2_ctb) - 1) >> s.log2_ctb;
+  // QP per CTB: the delta from the predictor en_qp_fix_ctb left for this CTB to its target, where the CTB codes one (rbt_qpmap.h)
+  const int8_t* qp_map = nullptr; s.dqp = 0;
+  if constexpr (QPMAP) qp_map = rbt_uni_ptr(s.f->qp_map);
   for (int a = 0; a < n_ctbs; a++) {
     const int addr = first + a, rx = addr % wc, ry = addr / wc;
+    if constexpr (QPMAP) if (qp_map != nullptr) { const int pw = RBT_UNI(s.f->qp_pred[addr]); s.dqp = (pw & RBT_QP_CODED) ? 0x100 | (en_qp_delta(RBT_UNI(qp_map[addr]), pw & 63, RBT_UNI(g->bit_depth)) + 64) : 0; }
     if (RBT_UNI(sl->sao_luma | sl->sao_chroma)) en_write_sao(&s.c, s.f, addr, rx, ry, wc, RBT_UNI(g->bit_depth));
     en_stage_ctb(&s, rx << s.log2_ctb, ry << s.log2_ctb);
-    en_write_quadtree(&s, rx << s.log2_ctb, ry << s.log2_ctb, s.log2_ctb);
+    en_write_quadtree<QPMAP>(&s, rx << s.log2_ctb, ry << s.log2_ctb, s.log2_ctb);
     if (wave_mode && rx == 1) { rbt_ctx_store_g(&s.c.cs, s.f->row_ctx + (size_t)ry * 256); RBT_FLAG_PUBLISH(&s.f->row_done[hc0 + ry], 2u); }
     rbt_ce_terminate(&s.c, a == n_ctbs - 1);
   }

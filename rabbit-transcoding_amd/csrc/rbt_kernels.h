@@ -93,6 +93,14 @@ void launch_enc_analyse(RbtFrame* frames, const RbtSlice* slices, const int32_t*
 // otherwise CTBs are scheduled on anti-diagonals like the decoder's reconstruction
 void launch_enc_intra(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, int max_w_ctb, int max_h_ctb, int row_mode, int max_log2_ctb, uint32_t* ticket = nullptr);
 void launch_enc_inter(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, int max_ctbs);
+#ifndef RBT_HOSTEMU      // (host emulation: both stand-ins are in rbt_qpmap.h itself)
+// QP per CTB (csrc/rbt_qpmap.h): for the listed pictures, which all carry a map (RbtFrame::qp_map), the QpY a decoder derives into RbtFrame::qp and the predictor of every
+// CTB's cu_qp_delta into RbtFrame::qp_pred; between the closed-loop stage and the loop filters
+void launch_enc_qp_fix(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, int max_ctbs);
+// on != 0: the encoder launches this thread issues from now on (analysis, intra, inter, SAO, both entropy coders) take the instantiations that read RbtFrame::qp_map - for a batch
+// that holds a picture with a map; 0: back to the constant-QP instantiations, which never look at it (csrc/rbt_encode.h en_ctb_qp)
+void enc_qp_map_variant(int on);
+#endif
 // SAO parameters from source-vs-reconstruction statistics and their application for every CTB of the listed pictures (en_sao_ctb); deblock_inside: the pictures have not
 // been through launch_deblock, the kernel deblocks each CTB and its halo in LDS first (RBT_FUSED_ENC_LF=1)
 void launch_enc_sao(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, int max_ctbs, int max_log2_ctb, int deblock_inside);

@@ -401,21 +401,23 @@ __global__ void __launch_bounds__(256) k_pool_many(PoolIn in, int w, int factor,
   if (i < ow * oh) en_pool_sample(src, w, factor, y, ow, i % ow, i / ow);
   if (i < (ow / 2) * (oh / 2)) { cb[i] = (uint16_t)chroma_value; cr[i] = (uint16_t)chroma_value; }
 }
+// (QPMAP, here and below: the instantiation that reads RbtFrame::qp_map - rbt_encode.h en_ctb_qp; the launchers pick it for batches with a map, enc_qp_map_variant)
+template <bool QPMAP>
 __global__ void __launch_bounds__(64) k_enc_analyse(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list) {
   __shared__ RbtAnalyseLds lds;
   RbtFrame* f = &frames[frame_list[blockIdx.y]];
   if ((int)blockIdx.x >= f->cfg.w_ctb * f->cfg.h_ctb) return;
-  en_analyse_ctb(f, slices, xcd_tile(blockIdx.x, f->cfg.w_ctb * f->cfg.h_ctb), RBT_LDS_CAST(RbtAnalyseLds, &lds));
+  en_analyse_ctb<QPMAP>(f, slices, xcd_tile(blockIdx.x, f->cfg.w_ctb * f->cfg.h_ctb), RBT_LDS_CAST(RbtAnalyseLds, &lds));
 }
 // (TL2: log2 of the largest CTB of the launch; fixes the size of the reconstruction tile in LDS)
-template <int TL2>
+template <int TL2, bool QPMAP>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) k_enc_intra_rows(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list) {
   __shared__ RbtEncTileLdsT<TL2> lds;
   RbtFrame* f = &frames[frame_list[blockIdx.y]];
   int row = blockIdx.x;
   if (row >= f->cfg.h_ctb) return;
   rc_stage_tables(&RBT_LDS_CAST(RbtEncTileLdsT<TL2>, &lds)->rc);
-  for (int x = 0; x < f->cfg.w_ctb; x++) en_intra_ctb<TL2>(f, slices, row * f->cfg.w_ctb + x, RBT_LDS_CAST(RbtEncTileLdsT<TL2>, &lds), x > 0);
+  for (int x = 0; x < f->cfg.w_ctb; x++) en_intra_ctb<TL2, QPMAP>(f, slices, row * f->cfg.w_ctb + x, RBT_LDS_CAST(RbtEncTileLdsT<TL2>, &lds), x > 0);
 }
 // Wavefront mode (one slice per picture, one dependent slice segment per CTB row): rows of a picture predict from each other, so CTB x of row r is coded
 // once row r - 1 has finished CTB x + 1 (its above-right neighbour; the last CTB of the row for the last column). With that two-CTB lag at most w_ctb / 2
@@ -431,7 +433,7 @@ __device__ __forceinline__ int wave_next_row(uint32_t* counter) {
   if ((threadIdx.x & 63) == 0) r = (int)atomicAdd(counter, 1u);
   return __builtin_amdgcn_readfirstlane(r);
 }
-template <int TL2>
+template <int TL2, bool QPMAP>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) k_enc_intra_wave(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, uint32_t* ticket) {
   __shared__ RbtEncTileLdsT<TL2> lds;
   const uint32_t t = (uint32_t)wave_next_row(ticket);
@@ -443,50 +445,51 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
     uint32_t seen = 0;
     for (int x = 0; x < w; x++) {
       if (row > 0) seen = rbt_flag_wait_seen(&done[row - 1], (uint32_t)(x + 2 < w ? x + 2 : w), seen, &f->error);
-      en_intra_ctb<TL2>(f, slices, row * w + x, RBT_LDS_CAST(RbtEncTileLdsT<TL2>, &lds), x > 0);
+      en_intra_ctb<TL2, QPMAP>(f, slices, row * w + x, RBT_LDS_CAST(RbtEncTileLdsT<TL2>, &lds), x > 0);
       if (((x + 1) & (WAVE_PUBLISH_EVERY - 1)) == 0 || x + 1 == w) RBT_FLAG_PUBLISH(&done[row], x + 1);   // a release (L2 write-back) per few CTBs, not per CTB
     }
   }
 }
-template <int TL2>
+template <int TL2, bool QPMAP>
 __global__ void __launch_bounds__(64) k_enc_intra_diag(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int d) {
   __shared__ RbtEncTileLdsT<TL2> lds;
   RbtFrame* f = &frames[frame_list[blockIdx.y]];
   int y = blockIdx.x, x = d - 2 * y;
   if (y >= f->cfg.h_ctb || x < 0 || x >= f->cfg.w_ctb) return;
   rc_stage_tables(&RBT_LDS_CAST(RbtEncTileLdsT<TL2>, &lds)->rc);
-  en_intra_ctb<TL2>(f, slices, y * f->cfg.w_ctb + x, RBT_LDS_CAST(RbtEncTileLdsT<TL2>, &lds), 0);
+  en_intra_ctb<TL2, QPMAP>(f, slices, y * f->cfg.w_ctb + x, RBT_LDS_CAST(RbtEncTileLdsT<TL2>, &lds), 0);
 }
+template <bool QPMAP>
 __global__ void __launch_bounds__(64) k_enc_inter(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list) {
   __shared__ RbtEncLds lds;
   RbtFrame* f = &frames[frame_list[blockIdx.y]];
   if ((int)blockIdx.x >= f->cfg.w_ctb * f->cfg.h_ctb) return;
   rc_stage_tables(&RBT_LDS_CAST(RbtEncLds, &lds)->rc);
-  en_inter_ctb(frames, f, slices, xcd_tile(blockIdx.x, f->cfg.w_ctb * f->cfg.h_ctb), RBT_LDS_CAST(RbtEncLds, &lds));
+  en_inter_ctb<QPMAP>(frames, f, slices, xcd_tile(blockIdx.x, f->cfg.w_ctb * f->cfg.h_ctb), RBT_LDS_CAST(RbtEncLds, &lds));
 }
-template <int TL2, bool REGION>
+template <int TL2, bool REGION, bool QPMAP>
 __global__ void __launch_bounds__(64) k_enc_sao(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list) {
   __shared__ RbtSaoLds lds;
   __shared__ RbtSaoRegionT<REGION ? TL2 : 2> reg;      // REGION: the CTB + halo, deblocked here (RBT_FUSED_ENC_LF=1); otherwise a stub
   RbtFrame* f = &frames[frame_list[blockIdx.y]];
   if ((int)blockIdx.x >= f->cfg.w_ctb * f->cfg.h_ctb) return;
-  en_sao_ctb<REGION>(f, slices, xcd_tile(blockIdx.x, f->cfg.w_ctb * f->cfg.h_ctb), RBT_LDS_CAST(RbtSaoLds, &lds), RBT_LDS_CAST(uint16_t, reg.ry), RBT_LDS_CAST(uint16_t, reg.rc[0]), RBT_LDS_CAST(uint16_t, reg.rc[1]));
+  en_sao_ctb<REGION, QPMAP>(f, slices, xcd_tile(blockIdx.x, f->cfg.w_ctb * f->cfg.h_ctb), RBT_LDS_CAST(RbtSaoLds, &lds), RBT_LDS_CAST(uint16_t, reg.ry), RBT_LDS_CAST(uint16_t, reg.rc[0]), RBT_LDS_CAST(uint16_t, reg.rc[1]));
 }
-template <int TL2>
+template <int TL2, bool QPMAP>
 __global__ void __launch_bounds__(64) k_entropy(RbtFrame* frames, RbtSlice* slices, uint8_t* out, const int32_t* slice_list) {
   __shared__ alignas(16) uint32_t lds[(RBT_ENTROPY_LDS_BYTES(TL2) + 3) / 4];
-  en_entropy_slice(frames, slices, slice_list[blockIdx.x], out, RBT_LDS_CAST(RbtEntropyLds, lds));
+  en_entropy_slice<QPMAP>(frames, slices, slice_list[blockIdx.x], out, RBT_LDS_CAST(RbtEntropyLds, lds));
 }
 // Wavefront mode: the segment of CTB row r starts from the context variables row r - 1 had after its second CTB (en_entropy_slice waits for them); as in
 // k_enc_intra_wave a picture gets K = ceil(w_ctb / 2) waves, each taking the next row not handed out yet (segment of row r = the picture's first_slice + r).
-template <int TL2>
+template <int TL2, bool QPMAP>
 __global__ void __launch_bounds__(64) k_entropy_wave(RbtFrame* frames, RbtSlice* slices, uint8_t* out, const int32_t* frame_list, int n_frames, uint32_t* ticket) {
   __shared__ alignas(16) uint32_t lds[(RBT_ENTROPY_LDS_BYTES(TL2) + 3) / 4];
   const uint32_t t = (uint32_t)wave_next_row(ticket);
   const RbtFrame* f = &frames[frame_list[t % (uint32_t)n_frames]];
   const int h = f->cfg.h_ctb, first = f->first_slice;
   uint32_t* next = &f->row_done[2 * h + 1];
-  for (int row = wave_next_row(next); row < h; row = wave_next_row(next)) en_entropy_slice(frames, slices, first + row, out, RBT_LDS_CAST(RbtEntropyLds, lds));
+  for (int row = wave_next_row(next); row < h; row = wave_next_row(next)) en_entropy_slice<QPMAP>(frames, slices, first + row, out, RBT_LDS_CAST(RbtEntropyLds, lds));
 }
 
 __global__ void __launch_bounds__(256) k_pack(const uint8_t* out, const RbtSlice* slices, const uint32_t* dst_off, uint8_t* packed) {
@@ -529,9 +532,13 @@ void launch_occ_units(const uint16_t* occ, size_t in_step, int n, int ow, int oh
   if (n <= 0) return;
   hipLaunchKernelGGL(k_occ_units, dim3((w4 * h4 + 255) / 256, n), dim3(256), 0, g_stream, occ, in_step, ow, oh, W / ow, w4, h4, out);
 }
+// the instantiations the encoder launches of this thread take (enc_qp_map_variant)
+static thread_local bool t_qp_map = false;
+void enc_qp_map_variant(int on) { t_qp_map = on != 0; }
+#define RBT_QM_LAUNCH(K_MAP, K_PLAIN, ...) do { if (t_qp_map) hipLaunchKernelGGL(K_MAP, __VA_ARGS__); else hipLaunchKernelGGL(K_PLAIN, __VA_ARGS__); } while (0)
 void launch_enc_analyse(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, int max_ctbs) {
   if (n_frames <= 0) return;
-  hipLaunchKernelGGL(k_enc_analyse, dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
+  RBT_QM_LAUNCH((k_enc_analyse<true>), (k_enc_analyse<false>), dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
 }
 // Waves per picture of the wavefront kernels. w_ctb / 2 is all a picture can use (two-CTB lag between rows) and gives the shortest launch; while the first
 // rows ramp up and the last ramp down those waves wait, holding their LDS. With many jobs in flight the GPU is full anyway and idle residents only take
@@ -545,42 +552,52 @@ void launch_enc_intra(RbtFrame* frames, const RbtSlice* slices, const int32_t* f
   const bool small = max_log2_ctb <= 5;
   if (row_mode == 2) {
     const int K = wave_rows_in_flight(max_w_ctb, max_h_ctb);
-    if (small) hipLaunchKernelGGL(k_enc_intra_wave<5>, dim3(K * n_frames), dim3(64), 0, g_stream, frames, slices, frame_list, n_frames, ticket);
-    else hipLaunchKernelGGL(k_enc_intra_wave<6>, dim3(K * n_frames), dim3(64), 0, g_stream, frames, slices, frame_list, n_frames, ticket);
+    if (small) RBT_QM_LAUNCH((k_enc_intra_wave<5, true>), (k_enc_intra_wave<5, false>), dim3(K * n_frames), dim3(64), 0, g_stream, frames, slices, frame_list, n_frames, ticket);
+    else RBT_QM_LAUNCH((k_enc_intra_wave<6, true>), (k_enc_intra_wave<6, false>), dim3(K * n_frames), dim3(64), 0, g_stream, frames, slices, frame_list, n_frames, ticket);
     return;
   }
   if (row_mode) {
-    if (small) hipLaunchKernelGGL(k_enc_intra_rows<5>, dim3(max_h_ctb, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
-    else hipLaunchKernelGGL(k_enc_intra_rows<6>, dim3(max_h_ctb, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
+    if (small) RBT_QM_LAUNCH((k_enc_intra_rows<5, true>), (k_enc_intra_rows<5, false>), dim3(max_h_ctb, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
+    else RBT_QM_LAUNCH((k_enc_intra_rows<6, true>), (k_enc_intra_rows<6, false>), dim3(max_h_ctb, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
     return;
   }
   int n_diag = max_w_ctb + 2 * (max_h_ctb - 1);
   for (int d = 0; d < n_diag; d++) {
     int rows = d / 2 + 1; if (rows > max_h_ctb) rows = max_h_ctb;
-    if (small) hipLaunchKernelGGL(k_enc_intra_diag<5>, dim3(rows, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list, d);
-    else hipLaunchKernelGGL(k_enc_intra_diag<6>, dim3(rows, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list, d);
+    if (small) RBT_QM_LAUNCH((k_enc_intra_diag<5, true>), (k_enc_intra_diag<5, false>), dim3(rows, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list, d);
+    else RBT_QM_LAUNCH((k_enc_intra_diag<6, true>), (k_enc_intra_diag<6, false>), dim3(rows, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list, d);
   }
 }
 void launch_enc_inter(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, int max_ctbs) {
   if (n_frames <= 0) return;
-  hipLaunchKernelGGL(k_enc_inter, dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
+  RBT_QM_LAUNCH((k_enc_inter<true>), (k_enc_inter<false>), dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
+}
+// QP per CTB (rbt_qpmap.h): blockIdx.y = picture, blockIdx.x = CTB, one wave each; pass 1 reads what pass 0 stored for other CTBs, so the passes are two launches
+__global__ void __launch_bounds__(64) k_enc_qp_fix(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int pass) {
+  RbtFrame* f = &frames[frame_list[blockIdx.y]];
+  if ((int)blockIdx.x >= f->cfg.w_ctb * f->cfg.h_ctb || f->qp_map == nullptr) return;
+  if (pass == 0) en_qp_scan_ctb(f, (int)blockIdx.x); else en_qp_fix_ctb(f, slices, (int)blockIdx.x);
+}
+void launch_enc_qp_fix(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, int max_ctbs) {
+  if (n_frames <= 0 || max_ctbs <= 0) return;
+  for (int pass = 0; pass < 2; pass++) hipLaunchKernelGGL(k_enc_qp_fix, dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list, pass);
 }
 void launch_enc_sao(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, int max_ctbs, int max_log2_ctb, int deblock_inside) {
   if (n_frames <= 0) return;
-  if (!deblock_inside) hipLaunchKernelGGL((k_enc_sao<5, false>), dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
-  else if (max_log2_ctb <= 5) hipLaunchKernelGGL((k_enc_sao<5, true>), dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
-  else hipLaunchKernelGGL((k_enc_sao<6, true>), dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
+  if (!deblock_inside) RBT_QM_LAUNCH((k_enc_sao<5, false, true>), (k_enc_sao<5, false, false>), dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
+  else if (max_log2_ctb <= 5) RBT_QM_LAUNCH((k_enc_sao<5, true, true>), (k_enc_sao<5, true, false>), dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
+  else RBT_QM_LAUNCH((k_enc_sao<6, true, true>), (k_enc_sao<6, true, false>), dim3(max_ctbs, n_frames), dim3(64), 0, g_stream, frames, slices, frame_list);
 }
 void launch_entropy(RbtFrame* frames, RbtSlice* slices, uint8_t* out, const int32_t* slice_list, int n_slices, int max_log2_ctb) {
   if (n_slices <= 0) return;
-  if (max_log2_ctb <= 5) hipLaunchKernelGGL(k_entropy<5>, dim3(n_slices), dim3(64), 0, g_stream, frames, slices, out, slice_list);
-  else hipLaunchKernelGGL(k_entropy<6>, dim3(n_slices), dim3(64), 0, g_stream, frames, slices, out, slice_list);
+  if (max_log2_ctb <= 5) RBT_QM_LAUNCH((k_entropy<5, true>), (k_entropy<5, false>), dim3(n_slices), dim3(64), 0, g_stream, frames, slices, out, slice_list);
+  else RBT_QM_LAUNCH((k_entropy<6, true>), (k_entropy<6, false>), dim3(n_slices), dim3(64), 0, g_stream, frames, slices, out, slice_list);
 }
 void launch_entropy_wave(RbtFrame* frames, RbtSlice* slices, uint8_t* out, const int32_t* frame_list, int n_frames, int max_w_ctb, int max_h_ctb, int max_log2_ctb, uint32_t* ticket) {
   if (n_frames <= 0) return;
   const int K = wave_rows_in_flight(max_w_ctb, max_h_ctb);
-  if (max_log2_ctb <= 5) hipLaunchKernelGGL(k_entropy_wave<5>, dim3(K * n_frames), dim3(64), 0, g_stream, frames, slices, out, frame_list, n_frames, ticket);
-  else hipLaunchKernelGGL(k_entropy_wave<6>, dim3(K * n_frames), dim3(64), 0, g_stream, frames, slices, out, frame_list, n_frames, ticket);
+  if (max_log2_ctb <= 5) RBT_QM_LAUNCH((k_entropy_wave<5, true>), (k_entropy_wave<5, false>), dim3(K * n_frames), dim3(64), 0, g_stream, frames, slices, out, frame_list, n_frames, ticket);
+  else RBT_QM_LAUNCH((k_entropy_wave<6, true>), (k_entropy_wave<6, false>), dim3(K * n_frames), dim3(64), 0, g_stream, frames, slices, out, frame_list, n_frames, ticket);
 }
 // ---------------------------------------------------------------------------------------------- self-test
 // The 32-point transform stages on the matrix cores (rbt_mfma.h) against the vector-ALU form of the same stages, on the device, for every block

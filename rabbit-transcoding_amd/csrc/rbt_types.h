@@ -86,7 +86,15 @@ struct RbtFrame {
   // wavefront streams (decoder): what the wave of one CTB row hands to the wave of the row below: CTBs parsed (zeroed per job), the context variables after
   // the second CTB (256 bytes per row), and the row's bottom line (prow_line_bytes per row, a multiple of 256 so that no cache line is shared with anything the
   // reading wave writes itself: mv int32[w4] | RbtSao[w_ctb] | slice u16[w_ctb] | pm, dm, ref bytes[w4] each)
-  uint32_t* prow_done; uint8_t* prow_ctx; uint8_t* prow_line; int32_t prow_line_bytes;
+  union {
+    struct { uint32_t* prow_done; uint8_t* prow_ctx; };
+    // encoder, QP per CTB (include/rbt.h "a QP per CTB"; in the room of decoder-only members, as src_flat is): qp_map = the target QpY T of every CTB of
+    // the picture (w_ctb * h_ctb bytes, the I pictures' -3 applied by the host), nullptr = the slice's QP everywhere. qp_pred (only with qp_map; 2 * w_ctb * h_ctb bytes,
+    // written by en_qp_fix_ctb between the closed-loop stage and the loop filters): per CTB qPY_PRED (8.6.1) in bits 0..5 and RBT_QP_CODED where the CTB holds a block
+    // with a cbf, i.e. codes a cu_qp_delta; behind it per CTB the first pass's word (RBT_QP_CODED | z-order index of the first 8x8 unit of the first coding unit with a cbf)
+    struct { const int8_t* qp_map; uint8_t* qp_pred; };
+  };
+  uint8_t* prow_line; int32_t prow_line_bytes;
   // ---- encoder side (RBT-E1) ----
   union {
     const uint16_t* src[3];      // source planes (the decoder's `out` planes or the pooled occupancy map)
@@ -128,6 +136,7 @@ struct RbtFrame {
 #define RBT_ET_RQ 4        // rounding offset of the intra quantiser by level and position (en_rq_offset)
 #define RBT_ET_ALL (1 | 2 | 4 | 16)      // every RBT_ET_* bit (a new one is added here too: csrc/rbt_encode.h keeps a private bit of its CTB context clear of them)
 #define RBT_ET_RDM 16      // the two cheapest candidates of the closed-loop mode choice coded as one transform block each, the cheaper kept (en_intra_ctb; oracle e1_mode_trial)
+#define RBT_QP_CODED 0x80   // RbtFrame::qp_pred
 #define RBT_CU_CBF_Y 1
 #define RBT_CU_CBF_CB 2
 #define RBT_CU_CBF_CR 4

@@ -9,6 +9,7 @@
 #include "rbt_transcode.h"
 #include "rbt_pcc.h"
 #include "rbt_internal.h"
+#include "rbt_qp_map.h"
 
 struct rbt_pcloud { rbt::PCloud* cloud; rbt_ctx* owner; };
 struct rbt_score_pair { rbt::ScorePair* pair; rbt_ctx* owner; bool stale; };      // stale: one of its clouds has been released
@@ -144,7 +145,7 @@ int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t
 } RBT_CATCH
 
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr,
-                  const rbt_d1_target* d1 = nullptr, const rbt_color_target* color = nullptr, const rbt_frame_qp* lists = nullptr, bool per_frame = false);
+                  const rbt_d1_target* d1 = nullptr, const rbt_color_target* color = nullptr, const rbt_frame_qp* lists = nullptr, bool per_frame = false, const rbt_qp_map* maps = nullptr);
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
 int rbt_transcode_substream(rbt_ctx* ctx, const uint8_t* annexb_in, size_t n_in, const rbt_stream_params* p, uint8_t** annexb_out, size_t* n_out) try {
   if (!ctx || !annexb_in || !p || !annexb_out || !n_out) return RBT_ERR_PARAM;
@@ -267,8 +268,27 @@ static int check_frame_qp(std::string& err, int n, const rbt_stream_params* p, c
   }
   return RBT_OK;
 }
+// the refusals of rbt_submit_gof_qp_map that the parameters alone decide (the counts against the stream's pictures: gof_refused); out: the maps, copied
+static int check_qp_maps(std::string& err, int n, const rbt_stream_params* p, const rbt_qp_map* m, std::vector<rbt::QpMapIn>& out) {
+  out.assign((size_t)n, {});
+  for (int i = 0; i < n; i++) {
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    if (m[i].struct_size != sizeof(rbt_qp_map)) { err = who + "rbt_qp_map.struct_size is not sizeof(rbt_qp_map)"; return RBT_ERR_PARAM; }
+    if (!m[i].n_frames && !m[i].w_ctb && !m[i].h_ctb && !m[i].qp) continue;
+    if (!m[i].qp) { err = who + "rbt_qp_map carries counts without a map (n_frames, w_ctb and h_ctb 0 with qp NULL: no map)"; return RBT_ERR_PARAM; }
+    if (m[i].n_frames < 1 || m[i].w_ctb < 1 || m[i].h_ctb < 1) { err = who + "rbt_qp_map carries a map without its counts: n_frames must be pictures / 2, w_ctb and h_ctb the CTB columns and rows of the output pictures"; return RBT_ERR_PARAM; }
+    if (p[i].video_type == RBT_VIDEO_OCCUPANCY) { err = who + "an occupancy stream is coded losslessly and takes no QP map"; return RBT_ERR_PARAM; }
+    if (m[i].w_ctb > 8192 / 16 || m[i].h_ctb > 8192 / 16) { err = who + "rbt_qp_map.w_ctb x h_ctb is beyond any picture (8192 samples at most)"; return RBT_ERR_PARAM; }
+    const size_t cnt = (size_t)m[i].n_frames * m[i].w_ctb * m[i].h_ctb;
+    for (size_t k = 0; k < cnt; k++) if (m[i].qp[k] < 0 || m[i].qp[k] > 51) {
+      const size_t per = (size_t)m[i].w_ctb * m[i].h_ctb;
+      err = who + "the QP of frame " + std::to_string(k / per) + ", CTB row " + std::to_string(k % per / m[i].w_ctb) + ", column " + std::to_string(k % m[i].w_ctb) + " is outside 0..51"; return RBT_ERR_PARAM; }
+    out[(size_t)i].qp.assign(m[i].qp, m[i].qp + cnt); out[(size_t)i].n_frames = m[i].n_frames; out[(size_t)i].w_ctb = m[i].w_ctb; out[(size_t)i].h_ctb = m[i].h_ctb;
+  }
+  return RBT_OK;
+}
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
-                  const rbt_d1_target* d1, const rbt_color_target* color, const rbt_frame_qp* lists, bool per_frame) {
+                  const rbt_d1_target* d1, const rbt_color_target* color, const rbt_frame_qp* lists, bool per_frame, const rbt_qp_map* maps) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
   RBT_ENTER(ctx);
@@ -281,12 +301,14 @@ static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const si
   if (color) if (int rc = check_color(ctx, n, p, color, creq)) return rc;
   std::vector<std::vector<int8_t>> frame_qp;
   if (lists) if (int rc = check_frame_qp(ctx->last_err, n, p, lists, frame_qp)) return rc;
+  std::vector<rbt::QpMapIn> qp_maps;
+  if (maps) if (int rc = check_qp_maps(ctx->last_err, n, p, maps, qp_maps)) return rc;
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
-  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality, d1 ? &req : nullptr, color ? &creq : nullptr, lists ? &frame_qp : nullptr, per_frame), ctx};
-  if (quality || d1 || color || lists) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
+  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality, d1 ? &req : nullptr, color ? &creq : nullptr, lists ? &frame_qp : nullptr, per_frame, maps ? &qp_maps : nullptr), ctx};
+  if (quality || d1 || color || lists || maps) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -417,6 +439,22 @@ int rbt_transcode_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_
   int rc = rbt_submit_gof_quality(ctx, n, annexb_in, n_in, p, targets, &job);
   if (rc) return rc;
   return rbt_wait_gof_quality(ctx, job, annexb_out, n_out, results);
+} RBT_CATCH
+// ---- a QP per CTB ----
+int rbt_submit_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_qp_map* maps, rbt_job** job) try {
+  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, nullptr, nullptr, nullptr, false, maps);      // maps == NULL: rbt_submit_gof
+} RBT_CATCH
+int rbt_transcode_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_qp_map* maps,
+                             uint8_t** annexb_out, size_t* n_out) try {
+  if (!annexb_out || !n_out) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_qp_map(ctx, n, annexb_in, n_in, p, maps, &job);
+  if (rc) return rc;
+  return rbt_wait_gof(ctx, job, annexb_out, n_out);
+} RBT_CATCH
+int rbt_qp_map_from_patches(const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const int8_t* patch_qp, int background_qp, int log2_ctb, int8_t* out, int w_ctb, int h_ctb) try {
+  std::string err;      // (no context to leave the reason with: the header names every refusal)
+  return rbt::qp_map_from_patches(err, atlas, patches, n_patches, patch_qp, background_qp, log2_ctb, out, w_ctb, h_ctb);
 } RBT_CATCH
 // ---- floors held frame by frame ----
 int rbt_submit_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job) try {

@@ -16,6 +16,9 @@
 #include "rbt_frame_walk.h"
 #include "rbt_pcc.h"
 #include "../csrc/rbt_cloudmaps.h"
+#ifdef RBT_HOSTEMU
+#include "../csrc/rbt_qpmap.h"      // the serial stand-in of launch_enc_qp_fix (the product's launcher is declared in rbt_kernels.h)
+#endif
 
 namespace rbt {
 
@@ -37,6 +40,9 @@ struct EncStreamDesc {
   int src_stride = 0, src_x0 = 0, src_y0 = 0;   // the planes are views: luma row stride (0 = w) and origin of the w x h region (luma samples)
   std::vector<int> pic; int n_total = 0; // a pass over a subset of the frames (desc_subset): the stream's picture behind each coded picture, and how many the stream has; empty = all of them
   std::vector<int8_t> frame_qp;          // a QP per point-cloud frame (rbt_frame_qp): pictures f * gop .. f * gop + gop - 1 are coded from frame_qp[f] where qp would be used; empty = qp. The parameter sets stay those of qp
+  // a QP per CTB (rbt_qp_map): M[f][r][c], qm_h rows of qm_w CTBs per point-cloud frame, as the caller gave them; picture f * gop + k takes its targets from frame f as
+  // frame_qp's pictures take theirs (encode_plan). Empty = none. The PPS of such a stream says cu_qp_delta_enabled_flag = 1, everything else is that of qp
+  std::vector<int8_t> qp_map; int qm_w = 0, qm_h = 0;
 };
 // Pictures are coded at the display size rounded up to 8 (all-intra) or 16 (I,P pairs: 16x16 inter CUs) and the padding is
 // signalled as the conformance window (7.4.3.2.1), like libx265 does for the reference (PCCTranscoder.cpp:706).
@@ -52,6 +58,9 @@ struct EncodeBatch {
   std::vector<PadJob> pad_jobs;                 // source pictures that have to be copied into padded planes before the encoder reads them
   std::vector<std::vector<size_t>> pic_at;     // after encode_finish, per stream: where in its output the NAL units of each picture start (rbt_frame_walk.h frame_cut)
   std::vector<uint16_t> cs_keep; uint16_t* d_cs = nullptr;   // the ctb->slice maps of all pictures back to back: host staging (alive until the copy has completed) and device
+  std::vector<int8_t> qm_keep; int8_t* d_qm = nullptr;       // QP per CTB: the target maps (RbtFrame::qp_map) of the pictures that carry one, back to back, staged and uploaded like the maps above
+  std::vector<int> frame_qm;                                  // ... per picture where its map starts in qm_keep, -1 = the picture has none
+  size_t off_iqm = 0, off_pqm = 0; int n_iqm = 0, n_pqm = 0;  // ... index lists of the I / P pictures with a map (launch_enc_qp_fix)
   uint8_t* d_zero = nullptr; size_t zero_bytes = 0; bool wpp = false;   // launch tickets (3 words) + row progress of the wavefront mode
   int main_stream = 0, aux_stream = -1;          // aux_stream >= 0: the intra part was enqueued there (its timers live there)
   HashSet hash; std::vector<int> hash_idx;      // md5_sei: the reconstructions to hash (after SAO), index of each picture in `hash` (-1: none)
@@ -88,6 +97,7 @@ static void make_param_sets(const EncStreamDesc& d, Sps& s, Pps& p) {
   p.transform_skip = !d.lossless && e1_ts_on();   // the 4x4 luma blocks are coded with or without the transform, whichever is cheaper (oracle/hevc_enc.c hm_tb_finish)
   if (d.lossless) { p.transquant_bypass = 1; p.deblocking_control_present = 1; p.pps_deblocking_disabled = 1; p.loop_filter_across_slices = 0; }
   if (d.rows < 0) { p.entropy_coding_sync = 1; p.dependent_slice_segments = 1; }   // wavefront rows, one dependent slice segment each (oracle/hevc_enc.c setup_stream)
+  if (!d.qp_map.empty()) { p.cu_qp_delta = 1; p.diff_cu_qp_delta_depth = 0; }     // a QP per CTB: the quantisation group is the CTB
 }
 
 // HBM layout of an encode batch. Every buffer of the arena is named here, once (Arena in rbt_batch.h: run without a base to measure, then over the allocation to bind),
@@ -120,6 +130,11 @@ static void encode_lay_out(EncodeBatch& b, Arena& a) {
   size_t cs_words = 0; for (size_t i = 0; i < nf; i++) cs_words += (size_t)b.frames[i].cfg.w_ctb * b.frames[i].cfg.h_ctb;
   b.d_cs = a.take<uint16_t>(cs_words);
   if (a.base) { uint16_t* at = b.d_cs; for (size_t i = 0; i < nf; i++) { b.frames[i].ctb_slice = at; at += (size_t)b.frames[i].cfg.w_ctb * b.frames[i].cfg.h_ctb; } }
+  // QP per CTB: the target maps, and per picture with a map the two bytes per CTB en_qp_fix_ctb keeps (RbtFrame::qp_pred); a batch without a map takes nothing here
+  if (!b.qm_keep.empty()) {
+    b.d_qm = a.take<int8_t>(b.qm_keep.size());
+    for (size_t i = 0; i < nf; i++) if (b.frame_qm[i] >= 0) { uint8_t* pr = a.take<uint8_t>(2 * (size_t)b.frames[i].cfg.w_ctb * b.frames[i].cfg.h_ctb); if (a.base) { b.frames[i].qp_map = b.d_qm + b.frame_qm[i]; b.frames[i].qp_pred = pr; } }
+  }
   b.d_frames = a.take<RbtFrame>(nf); b.d_slices = a.take<RbtSlice>(ns);
   if (a.base) for (size_t i = 0; i < nf; i++) if (b.desc[b.frame_stream[i]].src_flat_always) { b.frames[i].src_flat_one = 1; b.frames[i].src_flat = &b.d_frames[i].src_flat_one; }
   if (b.n_sums) b.d_sums = a.take<uint64_t>(b.n_sums);      // right behind the slices: one copy brings both back
@@ -133,6 +148,7 @@ static void encode_lay_out(EncodeBatch& b, Arena& a) {
 // host half of encode_build: parameter sets, pictures, slices and the size of the arena (b.arena_size); nothing is allocated
 static int encode_plan(EncodeBatch& b) {
   size_t ns = b.desc.size();
+  b.qm_keep.clear(); b.frame_qm.clear();
   b.sps.resize(ns); b.pps.resize(ns); b.stream_first.resize(ns);
   for (size_t si = 0; si < ns; si++) {
     const EncStreamDesc& d = b.desc[si];
@@ -144,6 +160,8 @@ static int encode_plan(EncodeBatch& b) {
     const Sps& s = b.sps[si]; const Pps& p = b.pps[si];
     b.stream_first[si] = (int)b.frames.size();
     if (!d.frame_qp.empty() && (d.lossless || d.gop < 1 || (int)d.frame_qp.size() * d.gop != d.n_frames)) { b.err = "internal: a QP list that does not match the stream's pictures"; return RBT_ERR_PARAM; }
+    const size_t qm_n = (size_t)s.w_ctb * s.h_ctb;      // CTBs of a picture = entries of a frame's map
+    if (!d.qp_map.empty() && (d.lossless || d.gop < 1 || !d.frame_qp.empty() || d.qm_w != s.w_ctb || d.qm_h != s.h_ctb || d.qp_map.size() * d.gop != qm_n * d.n_frames)) { b.err = "internal: a QP map that does not match the stream's pictures"; return RBT_ERR_PARAM; }
     for (int i = 0; i < d.n_frames; i++) {
       bool is_i = d.gop <= 1 || (i % d.gop) == 0;
       const int qp = d.frame_qp.empty() ? d.qp : d.frame_qp[(size_t)(i / d.gop)];      // only slice_qp_delta tells the pictures of a mixed-QP stream apart (write_slice_header: h.qp - init_qp)
@@ -156,12 +174,27 @@ static int encode_plan(EncodeBatch& b) {
       if (!d.hint_dm.empty()) { f.hint_pm = d.hint_pm[i]; f.hint_dm = d.hint_dm[i]; f.hint_w4 = d.hint_w4; f.hint_h4 = d.hint_h4; }
       if (!d.occ4.empty() && !d.lossless) { f.occ4 = d.occ4[i]; f.occ4_w = d.occ4_w; f.occ4_h = d.occ4_h; }
       int n_ctb = s.w_ctb * s.h_ctb, step = d.rows > 0 ? d.rows * s.w_ctb : (d.rows < 0 ? s.w_ctb : n_ctb);
+      // a QP per CTB: the picture's targets T - the map of its frame with the constant-QP path's I / P rule applied (include/rbt.h "a QP per CTB", definition) - go to the batch's staging
+      const int8_t* tq = nullptr;
+      if (!d.qp_map.empty()) {
+        const int8_t* m = d.qp_map.data() + (size_t)(i / d.gop) * qm_n; const size_t at = b.qm_keep.size();
+        for (size_t c = 0; c < qm_n; c++) b.qm_keep.push_back((int8_t)std::min(51, std::max(0, is_i ? m[c] + d.i_qp_offset : (int)m[c])));
+        b.frame_qm.push_back((int)at);
+      } else b.frame_qm.push_back(-1);
       for (int addr = 0; addr < n_ctb; addr += step) {
         RbtSlice sl; memset(&sl, 0, sizeof(sl));
         sl.next_seg = -1; sl.wpp = (uint8_t)(d.rows < 0); sl.dependent = (uint8_t)(d.rows < 0 && addr > 0);
         sl.frame = (int)b.frames.size(); sl.ctb_addr = addr; sl.n_ctbs = std::min(step, n_ctb - addr);
         sl.slice_type = (int8_t)(is_i ? RBT_SLICE_I : RBT_SLICE_P);
         sl.qp = (int8_t)std::min(51, std::max(0, is_i ? qp + d.i_qp_offset : qp));
+        // ... SliceQpY is T of the first CTB of the slice; the dependent segments of a wavefront picture belong to the slice that starts at CTB 0. The buffer is sized from the
+        // lowest T of the segment's CTBs (through the bands below)
+        int qp_cap = sl.qp;
+        if (!d.qp_map.empty()) {
+          tq = b.qm_keep.data() + b.frame_qm.back();
+          sl.qp = tq[d.rows < 0 ? 0 : addr];
+          qp_cap = 51; for (int c = 0; c < sl.n_ctbs; c++) qp_cap = std::min(qp_cap, (int)tq[addr + c]);
+        }
         sl.deblocking_disabled = (uint8_t)p.pps_deblocking_disabled; sl.lf_across = (uint8_t)p.loop_filter_across_slices;
         sl.max_merge_cand = 1; sl.num_ref_idx = 1; sl.poc = f.poc; sl.sao_luma = sl.sao_chroma = (uint8_t)b.desc[si].sao;
         if (!is_i) { sl.ref_frame[0] = f.ref_frame; sl.ref_poc[0] = f.ref_poc; }
@@ -172,7 +205,7 @@ static int encode_plan(EncodeBatch& b) {
         // Golomb-Rice prefix grows with the level (lossless two-level noise costs 18 bits a sample for 10-bit samples), and per-block syntax - so noise costs more than
         // its raw samples below QP 16. A slice that does not fit ends the call with RBT_ERR_OUTPUT (RbtSlice::out_size = 0xFFFFFFFF), it is never cut short.
         size_t rows = (size_t)(sl.n_ctbs + s.w_ctb - 1) / s.w_ctb;
-        const int quarter_bytes_per_sample = d.lossless ? 17 : (sl.qp < 16 ? 14 : (sl.qp < 34 ? 8 : 5));
+        const int quarter_bytes_per_sample = d.lossless ? 17 : (qp_cap < 16 ? 14 : (qp_cap < 34 ? 8 : 5));
         sl.out_cap = (uint32_t)(rows * ((size_t)s.width << s.log2_ctb) * quarter_bytes_per_sample / 4 + 4096);
         f.n_slices++;
         b.slices.push_back(sl);
@@ -201,6 +234,7 @@ static int encode_build(EncodeBatch& b) {
     for (int k = 0; k < f.n_slices; k++) { const RbtSlice& sl = b.slices[f.first_slice + k]; if (!sl.dependent) head = f.first_slice + k; for (int q = 0; q < sl.n_ctbs; q++) b.cs_keep[at + sl.ctb_addr + q] = (uint16_t)head; }
   }
   if (rbtk::h2d(b.d_cs, b.cs_keep.data(), b.cs_keep.size() * 2)) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  if (!b.qm_keep.empty() && rbtk::h2d(b.d_qm, b.qm_keep.data(), b.qm_keep.size())) { b.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
   // decoded picture hash SEI: the whole coded reconstruction (what a decoder outputs before cropping) after SAO
   b.hash_idx.assign(nf, -1);
   for (size_t i = 0; i < nf; i++) if (const int kind = b.desc[b.frame_stream[i]].md5) {
@@ -226,6 +260,10 @@ static int encode_upload_lists(EncodeBatch& b) {
   b.n_isao = b.n_psao = 0;
   b.off_isao = lists.size(); for (size_t i = 0; i < nf; i++) if (b.frame_is_idr[i] && b.desc[b.frame_stream[i]].sao) { lists.push_back((int)i); b.n_isao++; }
   b.off_psao = lists.size(); for (size_t i = 0; i < nf; i++) if (!b.frame_is_idr[i] && b.desc[b.frame_stream[i]].sao) { lists.push_back((int)i); b.n_psao++; }
+  // the pictures with a QP map (at most nf more entries: the lists hold 3 * (nf + ns), and a picture has a slice)
+  b.n_iqm = b.n_pqm = 0;
+  b.off_iqm = lists.size(); for (size_t i = 0; i < nf; i++) if (b.frame_is_idr[i] && b.frames[i].qp_map) { lists.push_back((int)i); b.n_iqm++; }
+  b.off_pqm = lists.size(); for (size_t i = 0; i < nf; i++) if (!b.frame_is_idr[i] && b.frames[i].qp_map) { lists.push_back((int)i); b.n_pqm++; }
   // slice segments of the intra pictures first, then the rest: the two groups are entropy-coded by separate launches
   b.n_sl_i = b.n_sl_p = 0;
   b.off_sl = lists.size(); for (size_t i = 0; i < ns; i++) if (b.frame_is_idr[b.slices[i].frame]) { lists.push_back((int)i); b.n_sl_i++; }
@@ -234,8 +272,11 @@ static int encode_upload_lists(EncodeBatch& b) {
   if (!b.hash.empty() && b.hash.upload()) { b.err = "device allocation failed"; return RBT_ERR_NOMEM; }
   return 0;
 }
+// a batch that holds a picture with a QP map launches the encoder instantiations that read it, every other batch the constant-QP ones (rbtk::enc_qp_map_variant)
+struct QpMapVariant { explicit QpMapVariant(const EncodeBatch& b) { rbtk::enc_qp_map_variant(!b.qm_keep.empty()); } ~QpMapVariant() { rbtk::enc_qp_map_variant(0); } };
 // intra pictures (analysis, closed-loop intra coding, deblocking): they only read their own source pictures
 static void encode_launch_intra(EncodeBatch& b) {
+  QpMapVariant variant(b);
   size_t nf = b.frames.size();
   for (const PadJob& j : b.pad_jobs) rbtk::launch_pad(j.in, j.stride, j.x0, j.y0, j.w, j.h, j.out, j.dw, j.dh);
   int mw = 0, mh = 0, mu = 0, mc = 0, row_mode = 1, ml2 = 0, ml = 0;
@@ -249,6 +290,7 @@ static void encode_launch_intra(EncodeBatch& b) {
   rbtk::timer_end(T_ANALYSE);
   rbtk::timer_begin(T_ENCODE);
   rbtk::launch_enc_intra(b.d_frames, b.d_slices, b.d_lists + b.off_i, b.n_i, mw, mh, row_mode, ml2, (uint32_t*)b.d_zero);
+  if (b.n_iqm) rbtk::launch_enc_qp_fix(b.d_frames, b.d_slices, b.d_lists + b.off_iqm, b.n_iqm, mc);      // QP per CTB: the QpY the loop filters read, the predictors the entropy coder codes against
   rbtk::launch_deblock(b.d_frames, b.d_slices, b.d_lists + b.off_ideb, b.n_ideb, mu);
   rbtk::launch_enc_sao(b.d_frames, b.d_slices, b.d_lists + b.off_isao, b.n_isao, mc, ml2, e1_fused_lf());   // decides and applies
   rbtk::timer_end(T_ENCODE);
@@ -258,6 +300,7 @@ static int max_log2_ctb(const EncodeBatch& b) { int m = 0; for (auto& f : b.fram
 static int max_w_ctb(const EncodeBatch& b) { int m = 0; for (auto& f : b.frames) m = std::max(m, (int)f.cfg.w_ctb); return m; }
 static int max_h_ctb(const EncodeBatch& b) { int m = 0; for (auto& f : b.frames) m = std::max(m, (int)f.cfg.h_ctb); return m; }
 static void encode_launch_entropy_intra(EncodeBatch& b) {
+  QpMapVariant variant(b);
   rbtk::timer_begin(T_ENTROPY_I);
   if (b.wpp) rbtk::launch_entropy_wave(b.d_frames, b.d_slices, b.d_out, b.d_lists + b.off_i, b.n_i, max_w_ctb(b), max_h_ctb(b), max_log2_ctb(b), (uint32_t*)b.d_zero + 1);
   else rbtk::launch_entropy(b.d_frames, b.d_slices, b.d_out, b.d_lists + b.off_sl, b.n_sl_i, max_log2_ctb(b));
@@ -265,17 +308,20 @@ static void encode_launch_entropy_intra(EncodeBatch& b) {
 }
 // inter pictures (need the reconstructed intra pictures and their own sources); after them every reconstruction is final
 static void encode_launch_inter(EncodeBatch& b) {
+  QpMapVariant variant(b);
   size_t nf = b.frames.size();
   int mu = 0, mc = 0, ml = 0;
   for (size_t i = 0; i < nf; i++) { const RbtStreamCfg& c = b.frames[i].cfg; mu = std::max(mu, c.w4 * c.h4); mc = std::max(mc, c.w_ctb * c.h_ctb); ml = std::max(ml, c.w * c.h); }
   rbtk::timer_begin(T_INTER);
   rbtk::launch_enc_inter(b.d_frames, b.d_slices, b.d_lists + b.off_p, b.n_p, mc);
+  if (b.n_pqm) rbtk::launch_enc_qp_fix(b.d_frames, b.d_slices, b.d_lists + b.off_pqm, b.n_pqm, mc);
   rbtk::launch_deblock(b.d_frames, b.d_slices, b.d_lists + b.off_pdeb, b.n_pdeb, mu);
   rbtk::launch_enc_sao(b.d_frames, b.d_slices, b.d_lists + b.off_psao, b.n_psao, mc, max_log2_ctb(b), e1_fused_lf());
   rbtk::timer_end(T_INTER);
 }
 // the entropy coder for the inter pictures' slices
 static void encode_launch_entropy_rest(EncodeBatch& b) {
+  QpMapVariant variant(b);
   rbtk::timer_begin(T_ENTROPY);
   if (b.wpp) rbtk::launch_entropy_wave(b.d_frames, b.d_slices, b.d_out, b.d_lists + b.off_p, b.n_p, max_w_ctb(b), max_h_ctb(b), max_log2_ctb(b), (uint32_t*)b.d_zero + 2);
   else rbtk::launch_entropy(b.d_frames, b.d_slices, b.d_out, b.d_lists + b.off_sl_p, b.n_sl_p, max_log2_ctb(b));
@@ -505,6 +551,7 @@ struct GofJob {
   std::vector<ColorEntry> color; std::vector<ColorOut> colorout;
   // a QP per point-cloud frame (rbt_submit_gof_frame_qp): per entry the list, empty = the entry's own QP; such a job is an ordinary constant-QP job in every other respect
   std::vector<std::vector<int8_t>> frame_qp;
+  std::vector<QpMapIn> qp_maps;      // a QP per CTB (rbt_submit_gof_qp_map): per entry the maps, an empty qp = none; the job is a constant-QP job otherwise, as with frame_qp
   // floors held frame by frame (rbt_submit_gof_quality_frames): a job with quality floors whose pipelines walk every frame on its own (RoundPipe::fwalks)
   bool per_frame = false; std::vector<FrameFloorOut> fout;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
@@ -649,6 +696,28 @@ static int check_frame_qp(GofJob& j) {
   }
   return 0;
 }
+// A QP per CTB (include/rbt.h "a QP per CTB", rule 10): the counts a map came with against the pictures the decoders found - a point-cloud frame per pair of pictures, and the
+// CTB grid of the OUTPUT pictures (the input's displayed size, setup_encode) at the entry's log2_ctb. A refusal of the plan, like check_frame_qp's
+static int check_qp_maps(GofJob& j) {
+  if (j.qp_maps.empty()) return 0;
+  for (int g = 0; g < j.ng; g++) for (size_t q = 0; q < j.groups[g].size(); q++) {
+    const int i = j.groups[g][q]; const DecodeBatch& db = j.db[g]; const QpMapIn& m = j.qp_maps[i];
+    if (m.qp.empty()) continue;
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    const int ds = j.dec_of[g][q], cnt = db.stream_count[ds];
+    if (cnt % 2 || m.n_frames != cnt / 2) {
+      j.err = who + "rbt_qp_map.n_frames is " + std::to_string(m.n_frames) + ", the stream holds " + std::to_string(cnt) + " pictures (n_frames must be pictures / 2)";
+      j.refused = true; return RBT_ERR_PARAM; }
+    const RbtStreamCfg& c = db.frames[db.stream_first[ds]].cfg; const Sps& isps = db.stream_sps[ds];
+    const int dw = c.w - 2 * isps.conf_win[0] - 2 * isps.conf_win[1], dh = c.h - 2 * isps.conf_win[2] - 2 * isps.conf_win[3], l2 = j.params[i].log2_ctb ? j.params[i].log2_ctb : 5;
+    const int wc = (dw + (1 << l2) - 1) >> l2, hc = (dh + (1 << l2) - 1) >> l2;
+    if (dw > 0 && dh > 0 && l2 >= 4 && l2 <= 6 && (m.w_ctb != wc || m.h_ctb != hc)) {
+      j.err = who + "rbt_qp_map.w_ctb x h_ctb is " + std::to_string(m.w_ctb) + " x " + std::to_string(m.h_ctb) + ", the output pictures (" + std::to_string(dw) + " x " + std::to_string(dh) + ") hold " +
+              std::to_string(wc) + " x " + std::to_string(hc) + " CTBs at log2_ctb " + std::to_string(l2);
+      j.refused = true; return RBT_ERR_PARAM; }
+  }
+  return 0;
+}
 static int rate_prepare(GofJob& j, int gi);
 static int quality_prepare(GofJob& j, SubmitPlan& s, int gi);
 static int d1_prepare(GofJob& j, SubmitPlan& s, int gi);
@@ -669,6 +738,7 @@ static int build_encoders(GofJob& j, SubmitPlan& s) {
       const int i = gs[q], io = s.occ_of[i];
       if (int rc = setup_encode(j.db[gi], j.dec_of[gi][q], (int)q, s.p[i], eb, j.pooled, j.err, &s.pool_jobs[gi], io >= 0 ? &s.occ_src[io] : nullptr, io, &s.occ_jobs)) return rc;
       if (!j.frame_qp.empty()) eb.desc[q].frame_qp = j.frame_qp[i];
+      if (!j.qp_maps.empty() && !j.qp_maps[i].qp.empty()) { eb.desc[q].qp_map = j.qp_maps[i].qp; eb.desc[q].qm_w = j.qp_maps[i].w_ctb; eb.desc[q].qm_h = j.qp_maps[i].h_ctb; }
       const EncStreamDesc& d = eb.desc[q];
       if (feeds && s.p[i].video_type == RBT_VIDEO_OCCUPANCY && d.n_frames > 0) {
         OccSource& os = s.occ_src[i]; os.occ = d.src[0][0]; os.in_step = d.n_frames > 1 ? (size_t)(d.src[0][1] - d.src[0][0]) : 0; os.n = d.n_frames; os.ow = d.w; os.oh = d.h; os.pipeline = gi; }
@@ -1508,7 +1578,7 @@ static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
 // Phase A of a job: plan, build and upload everything, then enqueue. Every upload of the job is issued before its first kernel: a copy from pageable memory blocks the host
 // until the stream has reached it, and pipelines may share a stream. The first failure ends the submission (j.rc, j.err); gof_wait drains what was enqueued.
 GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
-                   const D1Request* d1, const ColorRequest* color, const std::vector<std::vector<int8_t>>* frame_qp, bool per_frame) {
+                   const D1Request* d1, const ColorRequest* color, const std::vector<std::vector<int8_t>>* frame_qp, bool per_frame, const std::vector<QpMapIn>* qp_maps) {
   GofJob* J = new GofJob(); GofJob& j = *J;
   j.per_frame = per_frame && (quality || d1);
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
@@ -1516,6 +1586,7 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
   j.params.assign(p, p + n); j.n_in.assign(n_in, n_in + n);
   if (targets) j.targets.assign(targets, targets + n);
   if (frame_qp) j.frame_qp = *frame_qp;
+  if (qp_maps) j.qp_maps = *qp_maps;
   if (quality) { j.qtargets.assign(quality, quality + n); j.qocc.assign(n, QualityOcc()); }
   if (d1) {      // a job with quality floors of 0, and the D1 targets with their patch lists copied
     j.qtargets.assign(n, rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, RBT_QUALITY_ALL, 0, 0}); j.qocc.assign(n, QualityOcc());
@@ -1540,6 +1611,7 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
   j.t_gpu = now_ms();
   if (!rc) rc = build_decoders(j, s);
   if (!rc) rc = check_frame_qp(j);
+  if (!rc) rc = check_qp_maps(j);
   if (!rc) rc = build_encoders(j, s);
   if (!rc) rc = launch_merged(j);
   // enqueue order: longest pipeline first - except that a pipeline whose occupancy maps others wait for goes in front of them (an event has to be recorded before it is waited for)

@@ -17,8 +17,12 @@ struct D1Request { const rbt_d1_target* targets; std::vector<std::vector<const P
 struct ColorRequest { const rbt_color_target* targets; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache; };
 // frame_qp: nullptr, or per entry a QP per point-cloud frame (rbt_submit_gof_frame_qp; values and video types checked by the caller, the count against the stream's pictures
 // here: gof_refused), empty = the entry's own QP; not together with targets, quality, d1 or color
+// qp_maps: nullptr, or per entry a QP per CTB (rbt_submit_gof_qp_map; struct sizes, values and video types checked by the caller, the counts against the stream's pictures here:
+// gof_refused), an empty qp = the entry's own QP; not together with anything but p
+struct QpMapIn { std::vector<int8_t> qp; int n_frames = 0, w_ctb = 0, h_ctb = 0; };
 GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr,
-                   const D1Request* d1 = nullptr, const ColorRequest* color = nullptr, const std::vector<std::vector<int8_t>>* frame_qp = nullptr, bool per_frame = false);   // per_frame: with quality, rbt_submit_gof_quality_frames
+                   const D1Request* d1 = nullptr, const ColorRequest* color = nullptr, const std::vector<std::vector<int8_t>>* frame_qp = nullptr, bool per_frame = false,   // per_frame: with quality, rbt_submit_gof_quality_frames
+                   const std::vector<QpMapIn>* qp_maps = nullptr);
 int gof_wait(GofJob* j, rbt_stats& st, std::string& err, uint8_t** out, size_t* n_out, rbt_rate_result* results = nullptr, rbt_quality_result* quality_results = nullptr, int* n_flat = nullptr,
              rbt_d1_floor_result* d1_results = nullptr, rbt_color_floor_result* color_results = nullptr, rbt_frame_floor_result* frame_results = nullptr);   // consumes the job
 bool gof_is_quality(const GofJob* j);           // a job of rbt_submit_gof_quality
