@@ -443,13 +443,14 @@ template <int TL2> struct RbtEncTileT {
   uint8_t occ_u[(1 << (TL2 - 2)) * (1 << (TL2 - 2))];        // occupancy-aware coding: RbtFrame::occ4 of the CTB's 4x4 luma units (uy * n4 + ux)
   uint8_t left_md[16];                                       // luma modes of the 8x8 units in the last column of the CTB to the left ([8] = that CTB is available, 6.4.1)
   // one TU or four (en_intra_cu_luma): levels and reconstruction of the CU's luma coded as ONE transform block, kept while it is coded as four;
-  // levels of the current quarter; source samples of the current quarter (luma, or Cb at 0 and Cr at 256)
-  int16_t lv0[32 * 32]; uint16_t rec0[32 * 32]; int16_t lv1[16 * 16]; uint16_t ss[512];
+  // levels of the current quarter (a quarter's source samples are read where they lie in `sb`, with the CU's row stride)
+  int16_t lv0[32 * 32]; uint16_t rec0[32 * 32]; int16_t lv1[16 * 16];
 };
-// TB scratch of the intra-coding kernel: the core + the prediction. The smoothed / angular reference arrays alias `tmp` (dead until
+// TB scratch of the intra-coding kernel: the core alone. The smoothed / angular reference arrays alias `tmp` (dead until
 // the forward transform) and the quantised levels alias the luma part of `sb` (the source samples are consumed when the residual is
-// formed): 14.7 instead of 18 KB per slice, 11 instead of 8 slices in flight per CU.
-struct RbtEncIntraScratch : RbtReconLdsCore { uint16_t pred[32 * 32]; };
+// formed). The prediction of a block lives in the block's own tile area: that area is dead from the moment the block's
+// references are gathered until its reconstruction is stored, as in the decoder's rc_tile_tb.
+struct RbtEncIntraScratch : RbtReconLdsCore { };
 template <int TL2> struct RbtEncTileLdsT { RbtEncIntraScratch rc; RbtEncTileT<TL2> t; };
 RBT_DEV int en_quant_scale(int r) { const uint64_t lo = 26214ull | (23302ull << 16) | (20560ull << 32) | (18396ull << 48), hi = 16384ull | (14564ull << 16); return (int)(((r < 4 ? lo : hi) >> (16 * (r & 3))) & 0xFFFF); }
 // What the intra chain asks of the picture over and over, read once per CTB into scalar registers. Through the RbtFrame pointer every use was a load from HBM with a wait
@@ -459,8 +460,13 @@ static_assert((EN_CTX_FLAT_SRC & RBT_ET_ALL) == 0 && RBT_ET_ALL == (RBT_ET_SATD 
 #ifdef RBT_HOSTEMU
 extern "C" { inline uint32_t rbt_hostemu_flat_ctbs[3]; }   // CTBs that took the flat-chroma path of en_intra_ctb / en_inter_ctb / en_sao_ctb (the output is the same bytes either way: tests tell by this that the path was on)
 #define EN_FLAT_COUNT(k, on) do { if (on) __atomic_fetch_add(&rbt_hostemu_flat_ctbs[k], 1u, __ATOMIC_RELAXED); } while (0)
+// what the intra chain's transform-block code reached (tests tell by these that a case ran it): CUs coded as one block after being tried as four, CUs kept as four, coded
+// mode trials that took the runner-up, 4x4 luma blocks that took transform skip, trials that left only their prediction in the tile (mark_l4 == -2, see en_tile_intra_tb)
+extern "C" { inline uint32_t rbt_hostemu_intra_tb[5]; }
+#define EN_TB_COUNT(k, on) do { if (on) __atomic_fetch_add(&rbt_hostemu_intra_tb[k], 1u, __ATOMIC_RELAXED); } while (0)
 #else
 #define EN_FLAT_COUNT(k, on) do { } while (0)
+#define EN_TB_COUNT(k, on) do { } while (0)
 #endif
 #define EN_FLAT(e) (((e)->enc_tools & EN_CTX_FLAT_SRC) != 0)
 struct EnCtbCtx : RbtStreamCfg { int lossless, enc_tools, f4, w8; int16_t* coef[3]; uint8_t *pm, *edges, *cu_flags, *cu_mode, *cu_ts; int8_t* qp; const uint16_t* src[3]; };
@@ -487,9 +493,12 @@ RBT_DEV void en_fill_cu_maps_ctx(const EnCtbCtx* e, int x0, int y0, int N, int p
   }
   RBT_PAR_FOR(i, n8 * n8) { const int k = ((y0 >> 3) + i / n8) * e->w8 + (x0 >> 3) + i % n8; e->cu_flags[k] = (uint8_t)flags; }
 }
-// one intra TB: (x0,y0) relative to the CTB and (gx,gy) in the picture, both in samples of component c_idx; returns cbf
+// one intra TB: (x0,y0) relative to the CTB and (gx,gy) in the picture, both in samples of component c_idx; returns cbf. src: the block's source samples, row stride sstr
+// (a quarter of a CU is read where it lies in the CU's block).
+// The prediction is written to the block's own tile area and read back from there when the reconstruction is stored: the references are gathered first (or were, with
+// reuse_nb), and nothing reads that area in between. With mark_l4 == -2 the tile is left holding the prediction (see below).
 template <int TL2> RBT_DEV int en_tile_intra_tb(const EnCtbCtx* e, RbtFrame* f, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int c_idx, int x0, int y0, int gx, int gy, int log2, int mode, int qp,
-                             const RBT_LDS_AS uint16_t* src, int mark_l4, int mux, int muy, RBT_LDS_AS int16_t* lvl_buf = nullptr, long long* cost = nullptr, int lam2 = 0, int* ssd_out = nullptr, int* ts_out = nullptr, int reuse_nb = 0) {
+                             const RBT_LDS_AS uint16_t* src, int sstr, int mark_l4, int mux, int muy, RBT_LDS_AS int16_t* lvl_buf = nullptr, long long* cost = nullptr, int lam2 = 0, int* ssd_out = nullptr, int* ts_out = nullptr, int reuse_nb = 0) {
   const RbtStreamCfg* g = e;
   RBT_LDS_AS RbtEncIntraScratch* r = &L->rc; RBT_LDS_AS RbtEncTileT<TL2>* t = &L->t;
   // lvl_buf: where the levels go (default: over the luma part of `sb`, i.e. over the source once the residual is formed). cost (needs a lvl_buf that leaves
@@ -515,7 +524,7 @@ template <int TL2> RBT_DEV int en_tile_intra_tb(const EnCtbCtx* e, RbtFrame* f, 
   RBT_LDS_AS int32_t* fin = rc_intra_filter(g, c_idx, log2, mode, r->nb, r_nbf);
   RcIntraCtx q; rc_intra_setup(g, c_idx, log2, mode, fin, r_ref, &q);
   // prediction and residual
-#define EN_BODY(PV) RBT_PAR_FOR(i, N * N) { const int x = i & (N - 1), y = i >> log2, pv = (PV); r->pred[i] = (uint16_t)pv; r->res[i] = (int16_t)((int)src[i] - pv); }
+#define EN_BODY(PV) RBT_PAR_FOR(i, N * N) { const int x = i & (N - 1), y = i >> log2, pv = (PV); tile[(y0 + y) * S + x0 + x + 1] = (uint16_t)pv; r->res[i] = (int16_t)((int)src[y * sstr + x] - pv); }
   RC_INTRA_KINDS(&q, fin, r_ref, EN_BODY);
 #undef EN_BODY
   RBT_SYNC_LDS();
@@ -547,28 +556,24 @@ template <int TL2> RBT_DEV int en_tile_intra_tb(const EnCtbCtx* e, RbtFrame* f, 
     en_fwd_transform(log2, c_idx == 0 && log2 == 2, bd, r);
     const int qbits = 14 + qp / 6 + (15 - bd - log2), sc = en_quant_scale(qp % 6); int part = 0;
     const int rq = e->enc_tools & RBT_ET_RQ;
+    // quantised and scaled back (8.6.3) in one go: lane i reads coefficient i and puts the de-quantised value in its place. Of a block that turns out empty it is not used.
+    const int bd_shift = bd + log2 - 5, scale = (16 * rc_level_scale(qp % 6)) << (qp / 6);
+    const long long add = 1ll << (bd_shift - 1);
     RBT_PAR_FOR(i, N * N) {
       const int cv = r->res[i], a = rbt_abs(cv);
       const long long tq = (long long)a * sc; const int lf = (int)(tq >> qbits);
       const int off = rq ? en_rq_offset(lf == 0, lf == 1, (i & (N - 1)) + (i >> log2)) : 171;      // oracle/hevc_enc.c e1_quant_intra
       long long qv = (tq + ((long long)off << (qbits - 9))) >> qbits;
       if (qv > 32767) qv = 32767;
-      lvl[i] = (int16_t)(cv < 0 ? -qv : qv);
+      const int16_t lv = (int16_t)(cv < 0 ? -qv : qv);
+      lvl[i] = lv;
       part += qv != 0;
+      const long long v = ((long long)lv * scale + add) >> bd_shift; r->res[i] = (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v));
     }
     nz = en_wave_sum(part, (RBT_LDS_AS RbtEncLds*)0);
   }
   RBT_SYNC_LDS();
-  if (nz && !e->lossless) {
-    const int bd_shift = bd + log2 - 5, scale = (16 * rc_level_scale(qp % 6)) << (qp / 6);
-    const long long add = 1ll << (bd_shift - 1);
-    RBT_PAR_FOR(i, N * N) { long long v = ((long long)lvl[i] * scale + add) >> bd_shift; r->res[i] = (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
-    RBT_SYNC_LDS();
-    rc_inv_transform(log2, c_idx == 0 && log2 == 2, 0, bd, r);
-  } else if (nz) {
-    RBT_PAR_FOR(i, N * N) r->res[i] = lvl[i];
-    RBT_SYNC_LDS();
-  }
+  if (nz && !e->lossless) rc_inv_transform(log2, c_idx == 0 && log2 == 2, 0, bd, r);      // (lossless: res already is what the levels give back)
   if (ts_out && !e->lossless && !occ_none) {
     // transform skip (7.3.8.11 transform_skip_flag, 8.6.4.2): the residual scaled by 2^(15 - bitDepth - 2) is quantised like coefficients; both ways are
     // priced as distortion * 256 + lambda^2 * rate, the flag costs one bit more, and transform skip needs a non-zero level
@@ -590,32 +595,38 @@ template <int TL2> RBT_DEV int en_tile_intra_tb(const EnCtbCtx* e, RbtFrame* f, 
     const int nz1 = en_wave_sum(p_nz, (RBT_LDS_AS RbtEncLds*)0), d0 = en_wave_sum(p_d0, (RBT_LDS_AS RbtEncLds*)0), d1 = en_wave_sum(p_d1, (RBT_LDS_AS RbtEncLds*)0);
     const int b0 = en_wave_sum(p_b0, (RBT_LDS_AS RbtEncLds*)0), b1 = en_wave_sum(p_b1, (RBT_LDS_AS RbtEncLds*)0);
     const long long c0 = (long long)d0 * 256 + (long long)lam2 * (b0 ? b0 + 3 : 1), c1 = (long long)d1 * 256 + (long long)lam2 * ((b1 ? b1 + 3 : 1) + 1);
-    RBT_SYNC_LDS();
-    if (nz1 && c1 < c0) {
+    if (nz1 && c1 < c0) {      // (lane i reads back what lane i wrote, here and in the last pass below: nothing to wait for between them)
       RBT_PAR_FOR(i, 16) { lvl[i] = lvl[16 + i]; r->res[i] = lvl[48 + i]; }
       nz = nz1; *ts_out = 1;
-      RBT_SYNC_LDS();
     }
   }
-  if (mark_l4 != -2) {                                  // -2: a trial whose block is coded again, or replaced, before anything reads it (the coded mode trial's runner-up): only its cost
-    { int16_t* cp = e->coef[c_idx] + (size_t)gy * pw + gx; RBT_PAR_FOR(i, N * N) cp[(size_t)(i >> log2) * pw + (i & (N - 1))] = lvl[i]; }
+  // one last pass over the block: lane i's level to the coefficient plane, prediction + residual to the tile, and its share of the cost's sums, from one read of each.
+  // mark_l4 == -2: a trial of which only the cost is wanted. Nothing is stored, and the block's tile area is left holding the PREDICTION, not a reconstruction: the caller
+  // codes the same block again (or replaces it) before anything reads that area. The host build poisons it with a value no sample has, so that a read in between changes bytes.
+  {
+    const int store = mark_l4 != -2; int ps = 0, pb = 0;
+    int16_t* const cp = e->coef[c_idx] + (size_t)gy * pw + gx;
     RBT_PAR_FOR(i, N * N) {
-      const int x = i & (N - 1), y = i >> log2;
-      tile[(y0 + y) * S + x0 + x + 1] = (uint16_t)(nz ? rbt_clip3(0, maxv, (int)r->pred[i] + r->res[i]) : r->pred[i]);
+      const int x = i & (N - 1), y = i >> log2, p = (y0 + y) * S + x0 + x + 1;
+      const int pv = tile[p], rv = nz ? (int)r->res[i] : 0, lv = lvl[i];
+      if (store) { cp[(size_t)y * pw + x] = (int16_t)lv; if (nz) tile[p] = (uint16_t)rbt_clip3(0, maxv, pv + rv); }
+      if (cost) {
+        const int d = (int)src[y * sstr + x] - pv - rv, a = rbt_abs(lv);
+        if (!f4 || EN_TB_OCC(i)) ps += d * d;                            // at most 16 samples per lane and 1024 per block: fits 32 bits
+        if (a) pb += 3 + 2 * (31 - __builtin_clz((unsigned)a));
+      }
     }
+    if (cost) {
+      const int ssd = en_wave_sum(ps, (RBT_LDS_AS RbtEncLds*)0), bits = en_wave_sum(pb, (RBT_LDS_AS RbtEncLds*)0);
+      *cost = (long long)ssd * 256 + (long long)lam2 * (bits ? bits + 3 : 1);
+      if (ssd_out) *ssd_out = ssd;
+    }
+    EN_TB_COUNT(4, !store);
+#ifdef RBT_HOSTEMU
+    if (!store) RBT_PAR_FOR(i, N * N) tile[(y0 + (i >> log2)) * S + x0 + (i & (N - 1)) + 1] = 0xFFFF;
+#endif
   }
   if (mark_l4 >= 0) { RBT_PAR_FOR(i, 1 << (2 * mark_l4)) t->uav[(muy + (i >> mark_l4) + 1) * RC_US + mux + (i & ((1 << mark_l4) - 1)) + 1] = 1; }
-  if (cost) {
-    int ps = 0, pb = 0;
-    RBT_PAR_FOR(i, N * N) {
-      const int d = (int)src[i] - (int)r->pred[i] - (nz ? (int)r->res[i] : 0), a = rbt_abs((int)lvl[i]);
-      if (!f4 || EN_TB_OCC(i)) ps += d * d;                              // at most 16 samples per lane and 1024 per block: fits 32 bits
-      if (a) pb += 3 + 2 * (31 - __builtin_clz((unsigned)a));
-    }
-    const int ssd = en_wave_sum(ps, (RBT_LDS_AS RbtEncLds*)0), bits = en_wave_sum(pb, (RBT_LDS_AS RbtEncLds*)0);
-    *cost = (long long)ssd * 256 + (long long)lam2 * (bits ? bits + 3 : 1);
-    if (ssd_out) *ssd_out = ssd;
-  }
 #undef EN_TB_OCC
   RBT_SYNC_LDS();
   return nz != 0;
@@ -684,7 +695,7 @@ template <int TL2> RBT_DEV int en_intra_cu_luma(const EnCtbCtx* e, RbtFrame* f, 
   const int N = 1 << lg, h = N >> 1, S = RbtEncTileT<TL2>::TS_Y;
   long long c_whole = c_whole_in, c_split = 3ll * lam2, cq = 0;
   int ssd0 = ssd0_in, cbf0 = cbf0_in;
-  if (!have_whole) cbf0 = en_tile_intra_tb(e, f, L, 0, x0, y0, gx, gy, lg, mode, qp, t->sb, -1, 0, 0, t->lv0, &c_whole, lam2, &ssd0, nullptr, reuse_nb);
+  if (!have_whole) cbf0 = en_tile_intra_tb(e, f, L, 0, x0, y0, gx, gy, lg, mode, qp, t->sb, N, -1, 0, 0, t->lv0, &c_whole, lam2, &ssd0, nullptr, reuse_nb);
   *split = 0; *ts_bits = 0;
   if ((RBT_ABLATE & 0x10000) || (!e->lossless && (long long)ssd0 * 256 < (long long)(lam2 >> 2) * N * N)) {     // coded to within lambda^2 / 4 per sample by one transform: not tried as four (lossless: the bits alone decide)
     RBT_PAR_FOR(i, 1 << (2 * (lg - 2))) t->uav[((y0 >> 2) + (i >> (lg - 2)) + 1) * RC_US + (x0 >> 2) + (i & ((1 << (lg - 2)) - 1)) + 1] = 1;
@@ -696,23 +707,24 @@ template <int TL2> RBT_DEV int en_intra_cu_luma(const EnCtbCtx* e, RbtFrame* f, 
   int cbf1 = 0, tsm = 0;
   for (int b = 0; b < 4; b++) {
     const int ox = (b & 1) * h, oy = (b >> 1) * h;
-    RBT_PAR_FOR(i, h * h) t->ss[i] = t->sb[(oy + (i >> (lg - 1))) * N + ox + (i & (h - 1))];
-    RBT_SYNC_LDS();
-    int ts = 0;
-    if (en_tile_intra_tb(e, f, L, 0, x0 + ox, y0 + oy, gx + ox, gy + oy, lg - 1, mode, qp, t->ss, lg - 3, (x0 + ox) >> 2, (y0 + oy) >> 2, t->lv1, &cq, lam2, nullptr, (lg == 3 && g->transform_skip) ? &ts : nullptr)) cbf1 |= 1 << b;
+    int ts = 0;      // the quarter's source where it lies in the CU's block (row stride N); its levels go to lv1, so `sb` stays whole for the quarters behind it
+    if (en_tile_intra_tb(e, f, L, 0, x0 + ox, y0 + oy, gx + ox, gy + oy, lg - 1, mode, qp, t->sb + oy * N + ox, N, lg - 3, (x0 + ox) >> 2, (y0 + oy) >> 2, t->lv1, &cq, lam2, nullptr, (lg == 3 && g->transform_skip) ? &ts : nullptr)) cbf1 |= 1 << b;
     tsm |= ts << b;
     c_split += cq;
   }
   *split = c_split < c_whole;
-  if (*split) { *ts_bits = tsm; return cbf1; }
+  EN_TB_COUNT(0, !*split); EN_TB_COUNT(1, *split);
+  if (*split) { for (int b = 0; b < 4; b++) EN_TB_COUNT(3, (tsm >> b) & 1); *ts_bits = tsm; return cbf1; }
   RBT_PAR_FOR(i, N * N) t->y[(y0 + (i >> lg)) * S + x0 + (i & (N - 1)) + 1] = t->rec0[i];
   { int16_t* cp = e->coef[0] + (size_t)gy * g->w + gx; RBT_PAR_FOR(i, N * N) cp[(size_t)(i >> lg) * g->w + (i & (N - 1))] = t->lv0[i]; }
   RBT_SYNC_LDS();
   return cbf0;
 }
-// Cb and Cr TB of one CU in the same passes (see rc_tile_tb_cpair); returns cbf_cb | cbf_cr << 1. src: Cb block, then Cr at +256.
+// Cb and Cr TB of one CU in the same passes (see rc_tile_tb_cpair); returns cbf_cb | cbf_cr << 1. src: the Cb block with row stride sstr, the Cr block sdist samples behind it.
+// As in en_tile_intra_tb the predictions live in the blocks' own tile areas. The levels go over the luma part of `sb`: the CU's luma is coded, quarters included, before any
+// of its chroma blocks, and the chroma sources lie behind it (sb + 1024).
 template <int TL2> RBT_DEV int en_tile_intra_tb_cpair(const EnCtbCtx* e, RbtFrame* f, RBT_LDS_AS RbtEncTileLdsT<TL2>* L, int x0, int y0, int gx, int gy, int log2, int mode, int qp_cb, int qp_cr,
-                                   const RBT_LDS_AS uint16_t* src) {
+                                   const RBT_LDS_AS uint16_t* src, int sstr, int sdist) {
   const RbtStreamCfg* g = e;
   RBT_LDS_AS RbtEncIntraScratch* r = &L->rc; RBT_LDS_AS RbtEncTileT<TL2>* t = &L->t;
   RBT_LDS_AS int32_t* const r_ref = (RBT_LDS_AS int32_t*)r->tmp + 132; RBT_LDS_AS int32_t* const r_ref2 = r_ref + 100; RBT_LDS_AS int16_t* const lvl = (RBT_LDS_AS int16_t*)t->sb;
@@ -757,7 +769,7 @@ template <int TL2> RBT_DEV int en_tile_intra_tb_cpair(const EnCtbCtx* e, RbtFram
 #define EN_BODY(PV) RBT_PAR_FOR(i, 2 * NN) { \
     const int b = i >= NN, j = i - b * NN, x = j & (N - 1), y = j >> log2; \
     const RcIntraCtx* qp = b ? &q1 : &q0; const RBT_LDS_AS int32_t* nbp = r->nb + b * 66; const RBT_LDS_AS int32_t* refp = r_ref + b * 100; \
-    const int pv = (PV); r->pred[b * 256 + j] = (uint16_t)pv; r->res[b * 256 + j] = (int16_t)((int)src[b * 256 + j] - pv); }
+    const int pv = (PV); t->c[b][(y0 + y) * S + x0 + x + 1] = (uint16_t)pv; r->res[b * 256 + j] = (int16_t)((int)src[b * sdist + y * sstr + x] - pv); }
   RC_INTRA_KINDS_PAIR(&q0, qp, nbp, refp, EN_BODY);
 #undef EN_BODY
   RBT_SYNC_LDS();
@@ -784,6 +796,9 @@ template <int TL2> RBT_DEV int en_tile_intra_tb_cpair(const EnCtbCtx* e, RbtFram
     if (log2 == 2) en_fwd_transform_pair_n<2>(bd, r); else if (log2 == 3) en_fwd_transform_pair_n<3>(bd, r); else en_fwd_transform_pair_n<4>(bd, r);
     const int qb_cb = 14 + qp_cb / 6 + (15 - bd - log2), qb_cr = 14 + qp_cr / 6 + (15 - bd - log2), sc_cb = en_quant_scale(qp_cb % 6), sc_cr = en_quant_scale(qp_cr % 6);
     const int rq = e->enc_tools & RBT_ET_RQ;
+    // quantised and scaled back in one go, as in en_tile_intra_tb (a plane that turns out empty does not use the value)
+    const int bd_shift = bd + log2 - 5, ds_cb = (16 * rc_level_scale(qp_cb % 6)) << (qp_cb / 6), ds_cr = (16 * rc_level_scale(qp_cr % 6)) << (qp_cr / 6);
+    const long long add = 1ll << (bd_shift - 1);
     RBT_PAR_FOR(i, 2 * NN) {
       const int b = i >= NN, j = i - b * NN, qbits = b ? qb_cr : qb_cb;
       const int cv = r->res[b * 256 + j], a = rbt_abs(cv);
@@ -791,30 +806,23 @@ template <int TL2> RBT_DEV int en_tile_intra_tb_cpair(const EnCtbCtx* e, RbtFram
       const int off = rq ? en_rq_offset(lf == 0, lf == 1, (j & (N - 1)) + (j >> log2)) : 171;
       long long qv = (tq + ((long long)off << (qbits - 9))) >> qbits;
       if (qv > 32767) qv = 32767;
-      lvl[b * 256 + j] = (int16_t)(cv < 0 ? -qv : qv);
+      const int16_t lv = (int16_t)(cv < 0 ? -qv : qv);
+      lvl[b * 256 + j] = lv;
       part += (qv != 0) << (16 * b);
+      const long long v = ((long long)lv * (b ? ds_cr : ds_cb) + add) >> bd_shift; r->res[b * 256 + j] = (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v));
     }
   }
   const int nzp = en_wave_sum(part, (RBT_LDS_AS RbtEncLds*)0), nz0 = nzp & 0xFFFF, nz1 = nzp >> 16;
   RBT_SYNC_LDS();
-  RBT_PAR_FOR(i, 2 * NN) { const int b = i >= NN, j = i - b * NN; (b ? e->coef[2] : e->coef[1])[(size_t)(gy + (j >> log2)) * pw + gx + (j & (N - 1))] = lvl[b * 256 + j]; }
-  if ((nz0 | nz1) && !e->lossless) {
-    const int bd_shift = bd + log2 - 5, sc_cb = (16 * rc_level_scale(qp_cb % 6)) << (qp_cb / 6), sc_cr = (16 * rc_level_scale(qp_cr % 6)) << (qp_cr / 6);
-    const long long add = 1ll << (bd_shift - 1);
-    RBT_PAR_FOR(i, 2 * NN) {
-      const int b = i >= NN, j = i - b * NN;
-      if (b ? nz1 : nz0) { long long v = ((long long)lvl[b * 256 + j] * (b ? sc_cr : sc_cb) + add) >> bd_shift; r->res[b * 256 + j] = (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
-    }
-    RBT_SYNC_LDS();
+  if ((nz0 | nz1) && !e->lossless) {      // (lossless: res already is what the levels give back)
     const int sh = 20 - bd;
     if (log2 == 2) rc_inv_transform_pair_n<2>(sh, nz0, nz1, r); else if (log2 == 3) rc_inv_transform_pair_n<3>(sh, nz0, nz1, r); else rc_inv_transform_pair_n<4>(sh, nz0, nz1, r);
-  } else if (nz0 | nz1) {
-    RBT_PAR_FOR(i, 2 * NN) { const int b = i >= NN, j = i - b * NN; r->res[b * 256 + j] = lvl[b * 256 + j]; }
-    RBT_SYNC_LDS();
   }
+  // one last pass: the level to the coefficient plane, prediction + residual to the tile
   RBT_PAR_FOR(i, 2 * NN) {
-    const int b = i >= NN, j = i - b * NN, x = j & (N - 1), y = j >> log2, nz = b ? nz1 : nz0;
-    t->c[b][(y0 + y) * S + x0 + x + 1] = (uint16_t)(nz ? rbt_clip3(0, maxv, (int)r->pred[b * 256 + j] + r->res[b * 256 + j]) : r->pred[b * 256 + j]);
+    const int b = i >= NN, j = i - b * NN, x = j & (N - 1), y = j >> log2, nz = b ? nz1 : nz0, p = (y0 + y) * S + x0 + x + 1;
+    (b ? e->coef[2] : e->coef[1])[(size_t)(gy + y) * pw + gx + x] = lvl[b * 256 + j];
+    if (nz) t->c[b][p] = (uint16_t)rbt_clip3(0, maxv, (int)t->c[b][p] + r->res[b * 256 + j]);
   }
   RBT_SYNC_LDS();
   return (nz0 != 0) | ((nz1 != 0) << 1);
@@ -888,8 +896,11 @@ template <int TL2, bool QPMAP = EN_QP_ASK> RBT_DEV void en_intra_ctb(RbtFrame* f
         // only: on 8x8 CUs, more than half of all, the trial moved nothing). The runner-up first:
         // when the SATD's choice stands - most of the time - its block is already coded and en_intra_cu_luma goes straight on to the four-way form
         long long c2 = 0;
-        en_tile_intra_tb(e, f, L, 0, x0, y0, cx + x0, cy + y0, lg, second, qp_l, t->sb, -2, 0, 0, t->lv0, &c2, lam2, nullptr, nullptr, 1);
-        cbf_w = en_tile_intra_tb(e, f, L, 0, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, t->sb, -1, 0, 0, t->lv0, &c_w, lam2, &ssd_w, nullptr, 1);
+        // The trial (mark_l4 == -2) leaves the runner-up's PREDICTION in the CU's tile area. The invariant that makes this safe: the very next call codes the same block
+        // again, with the references en_refine_mode gathered (reuse_nb: it reads nothing of the tile), and writes the whole area before anything reads it.
+        en_tile_intra_tb(e, f, L, 0, x0, y0, cx + x0, cy + y0, lg, second, qp_l, t->sb, N, -2, 0, 0, t->lv0, &c2, lam2, nullptr, nullptr, 1);
+        cbf_w = en_tile_intra_tb(e, f, L, 0, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, t->sb, N, -1, 0, 0, t->lv0, &c_w, lam2, &ssd_w, nullptr, 1);
+        EN_TB_COUNT(2, c2 + (long long)lam2 * b2 < c_w + (long long)lam2 * b1);
         if (c2 + (long long)lam2 * b2 < c_w + (long long)lam2 * b1) mode = second; else have_w = 1;
       }
       const int nu = N >> 3;
@@ -898,24 +909,24 @@ template <int TL2, bool QPMAP = EN_QP_ASK> RBT_DEV void en_intra_ctb(RbtFrame* f
     }
     int split = 0, cbf = 0, cy4 = 0, ts_bits = 0;
     if (tu_rd) cy4 = en_intra_cu_luma(e, f, L, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, lam2, &split, &ts_bits, have_w, c_w, ssd_w, cbf_w, refine != 0);      // after the mode choice r->nb holds the CU's references
-    else cy4 = en_tile_intra_tb(e, f, L, 0, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, t->sb, lg - 2, x0 >> 2, y0 >> 2);
+    else cy4 = en_tile_intra_tb(e, f, L, 0, x0, y0, cx + x0, cy + y0, lg, mode, qp_l, t->sb, N, lg - 2, x0 >> 2, y0 >> 2);
     if (split && lg >= 4) {
       // four transform units, each with its own Cb / Cr blocks: chroma block b is predicted when the units 0..b of the CU are reconstructed, not more
-      const int hh = N >> 1, hc = Nc >> 1, n4u = hh >> 2;
+      const int hh = N >> 1, n4u = hh >> 2;
       RBT_PAR_FOR(i, 4 * n4u * n4u) { const int ux = i % (2 * n4u), uy = i / (2 * n4u); t->uav[((y0 >> 2) + uy + 1) * RC_US + (x0 >> 2) + ux + 1] = 0; }
       RBT_SYNC_LDS();
       for (int b = 0; b < 4; b++) {
         const int ox = (b & 1) * hh, oy = (b >> 1) * hh;
         RBT_PAR_FOR(i, n4u * n4u) t->uav[(((y0 + oy) >> 2) + i / n4u + 1) * RC_US + ((x0 + ox) >> 2) + i % n4u + 1] = 1;
-        if (!EN_FLAT(e)) RBT_PAR_FOR(i, 2 * hc * hc) { const int q = i >= hc * hc, j = i - q * hc * hc; t->ss[q * 256 + j] = t->sb[1024 + 256 * q + ((oy >> 1) + j / hc) * Nc + (ox >> 1) + j % hc]; }
         RBT_SYNC_LDS();
-        const int cc = EN_FLAT(e) ? 0 : en_tile_intra_tb_cpair(e, f, L, (x0 + ox) >> 1, (y0 + oy) >> 1, (cx + x0 + ox) >> 1, (cy + y0 + oy) >> 1, lg - 2, mode, qp_cb, qp_cr, t->ss);
+        // the quarter's Cb / Cr sources where they lie in the CU's blocks (row stride Nc). The pair's levels go over sb[0..511], the luma source: all four luma quarters are coded by now
+        const int cc = EN_FLAT(e) ? 0 : en_tile_intra_tb_cpair(e, f, L, (x0 + ox) >> 1, (y0 + oy) >> 1, (cx + x0 + ox) >> 1, (cy + y0 + oy) >> 1, lg - 2, mode, qp_cb, qp_cr, t->sb + 1024 + (oy >> 1) * Nc + (ox >> 1), Nc, 256);
         const int fl = RBT_CU_TU_SPLIT | ((cy4 >> b) & 1 ? RBT_CU_CBF_Y : 0) | ((cc & 1) ? RBT_CU_CBF_CB : 0) | ((cc & 2) ? RBT_CU_CBF_CR : 0);
         en_fill_cu_maps_ctx(e, cx + x0 + ox, cy + y0 + oy, hh, RBT_MODE_INTRA | ((fl & RBT_CU_CBF_Y) ? RBT_PM_NZ : 0), qp_y, fl);
       }
       continue;
     }
-    { const int cc = EN_FLAT(e) ? 0 : en_tile_intra_tb_cpair(e, f, L, x0 >> 1, y0 >> 1, (cx + x0) >> 1, (cy + y0) >> 1, lg - 1, mode, qp_cb, qp_cr, t->sb + 1024);
+    { const int cc = EN_FLAT(e) ? 0 : en_tile_intra_tb_cpair(e, f, L, x0 >> 1, y0 >> 1, (cx + x0) >> 1, (cy + y0) >> 1, lg - 1, mode, qp_cb, qp_cr, t->sb + 1024, Nc, 256);
       if (cc & 1) cbf |= RBT_CU_CBF_CB;
       if (cc & 2) cbf |= RBT_CU_CBF_CR; }
     if (split) cbf |= RBT_CU_TU_SPLIT | ((cy4 & 1) ? RBT_CU_CBF_Y : 0) | ((cy4 >> 1) * RBT_CU_CBF_Y1);   // 8x8 CU as four 4x4 luma blocks: their cbf bits

@@ -410,8 +410,10 @@ __global__ void __launch_bounds__(64) k_enc_analyse(RbtFrame* frames, const RbtS
   en_analyse_ctb<QPMAP>(f, slices, xcd_tile(blockIdx.x, f->cfg.w_ctb * f->cfg.h_ctb), RBT_LDS_CAST(RbtAnalyseLds, &lds));
 }
 // (TL2: log2 of the largest CTB of the launch; fixes the size of the reconstruction tile in LDS)
+// Two waves per SIMD, here and in k_enc_intra_wave: what the chain needs in registers (about 200 VGPRs) allows no more. While the tile took 20.4 KB the LDS held the
+// compiler to two whatever was asked for; at 17.3 KB a request for three is honoured with 168 VGPRs, the rest in scratch memory.
 template <int TL2, bool QPMAP>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) k_enc_intra_rows(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_enc_intra_rows(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list) {
   __shared__ RbtEncTileLdsT<TL2> lds;
   RbtFrame* f = &frames[frame_list[blockIdx.y]];
   int row = blockIdx.x;
@@ -434,7 +436,7 @@ __device__ __forceinline__ int wave_next_row(uint32_t* counter) {
   return __builtin_amdgcn_readfirstlane(r);
 }
 template <int TL2, bool QPMAP>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) k_enc_intra_wave(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, uint32_t* ticket) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_enc_intra_wave(RbtFrame* frames, const RbtSlice* slices, const int32_t* frame_list, int n_frames, uint32_t* ticket) {
   __shared__ RbtEncTileLdsT<TL2> lds;
   const uint32_t t = (uint32_t)wave_next_row(ticket);
   RbtFrame* f = &frames[frame_list[t % (uint32_t)n_frames]];

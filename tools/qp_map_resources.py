@@ -65,12 +65,15 @@ def main():
     names = sorted(n for n in set(a) | set(b) if "k_enc_" in n or "k_entropy" in n)
     pretty = demangle(names)
     rows = {}      # kernel -> [parent figures, change figures]
+    parent_names = {pretty[n] for n in names if n in a}
     for n in names:
         for side, (res, ins) in enumerate(((a, ia), (b, ib))):
             if n in res:
                 r = dict(res[n])
                 if n in ins: r["insts"] = ins[n]
-                rows.setdefault(plain(pretty[n]) if side else pretty[n], [{}, {}])[side] = r
+                # (a parent from before the map instantiations has k<5> where the change has k<5, false>; a later parent has the same names as the change)
+                name = plain(pretty[n]) if side and pretty[n] not in parent_names and plain(pretty[n]) in parent_names else pretty[n]
+                rows.setdefault(name, [{}, {}])[side] = r
     cols = [s for _, s in KEYS] + (["insts"] if ia else [])
     print("%-28s %s" % ("kernel (parent -> change)", " ".join("%13s" % c for c in cols)))
     grew = 0
