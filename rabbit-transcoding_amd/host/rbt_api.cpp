@@ -28,6 +28,29 @@ static_assert(RBT_MAX_JOBS == rbtk::RBT_JOB_SLOTS, "job slots");
 // no exception crosses the C ABI: allocation failures of the host side (std::vector, std::string) come back as error codes
 #define RBT_CATCH catch (const std::bad_alloc&) { return RBT_ERR_NOMEM; } catch (...) { return RBT_ERR_NO_DEVICE; }
 
+// What the checks of a D1 target and of a colour target end with: the QP range, the frames, their patch lists, and the reference handles, which must be clouds of this
+// context (colours: with colours); refs: the handles as clouds, nullptr = none
+template <class Target> static int check_cloud_target(rbt_ctx* ctx, const std::string& who, const Target& t, bool colours, std::vector<const rbt::PCloud*>& refs) {
+  std::string& err = ctx->last_err;
+  const int lo = t.qp_min, hi = t.qp_max ? t.qp_max : 51;
+  if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
+  if (t.n_frames < 1) { err = who + "n_frames must be at least 1"; return RBT_ERR_PARAM; }
+  if (!t.patches || !t.n_patches) { err = who + "the patch lists are missing"; return RBT_ERR_PARAM; }
+  for (int f = 0; f < t.n_frames; f++) {
+    if (t.n_patches[f] < 0 || (!t.patches[f] && t.n_patches[f])) { err = who + "the patch list of frame " + std::to_string(f) + " is missing"; return RBT_ERR_PARAM; }
+    std::string why;
+    if (rbt::mapframe_check(why, &t.atlas, t.patches[f], t.n_patches[f])) { err = who + "frame " + std::to_string(f) + ": " + why; return RBT_ERR_PARAM; }
+    const rbt_pcloud* h = t.reference ? t.reference[f] : nullptr;
+    if (h) {
+      bool mine = false; for (const rbt_pcloud* c : ctx->clouds) mine |= c == h;
+      if (!mine) { err = who + "reference " + std::to_string(f) + " is not a cloud of this context"; return RBT_ERR_PARAM; }
+      if (colours && !rbt::pcloud_has_colors(h->cloud)) { err = who + "reference " + std::to_string(f) + " carries no colours"; return RBT_ERR_PARAM; }
+    }
+    refs.push_back(h ? h->cloud : nullptr);
+  }
+  return RBT_OK;
+}
+
 extern "C" {
 
 const char* rbt_version(void) { return "rabbit-transcoding_amd 0.1 (RBT-E1 encoder, gfx950)"; }
@@ -144,13 +167,18 @@ int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t
   return RBT_OK;
 } RBT_CATCH
 
-static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr,
-                  const rbt_d1_target* d1 = nullptr, const rbt_color_target* color = nullptr, const rbt_frame_qp* lists = nullptr, bool per_frame = false, const rbt_qp_map* maps = nullptr);
+// what a submit adds to the inputs and their parameters: at most one of the target arrays (per_frame: the floors of quality / d1 are held frame by frame), QP lists or QP maps
+struct SubmitExtras {
+  bool gof_rule = true; const rbt_rate_target* targets = nullptr; const rbt_quality_target* quality = nullptr; const rbt_d1_target* d1 = nullptr; const rbt_color_target* color = nullptr;
+  bool per_frame = false; const rbt_frame_qp* lists = nullptr; const rbt_qp_map* maps = nullptr;
+};
+static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x = SubmitExtras());
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
 int rbt_transcode_substream(rbt_ctx* ctx, const uint8_t* annexb_in, size_t n_in, const rbt_stream_params* p, uint8_t** annexb_out, size_t* n_out) try {
   if (!ctx || !annexb_in || !p || !annexb_out || !n_out) return RBT_ERR_PARAM;
   rbt_job* job = nullptr;
-  int rc = submit(ctx, 1, &annexb_in, &n_in, p, &job, false);
+  SubmitExtras x; x.gof_rule = false;
+  int rc = submit(ctx, 1, &annexb_in, &n_in, p, &job, x);
   if (rc) return rc;
   return rbt_wait_gof(ctx, job, annexb_out, n_out);
 } RBT_CATCH
@@ -161,7 +189,7 @@ int rbt_transcode_gof(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, cons
   if (rc) return rc;
   return rbt_wait_gof(ctx, job, annexb_out, n_out);
 } RBT_CATCH
-int rbt_submit_gof(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job) try { return submit(ctx, n, annexb_in, n_in, p, job, true); } RBT_CATCH
+int rbt_submit_gof(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job) try { return submit(ctx, n, annexb_in, n_in, p, job); } RBT_CATCH
 // the refusals of rbt_submit_gof_rate: nothing has been submitted when one of them fires
 static int check_targets(std::string& err, int n, const rbt_stream_params* p, const rbt_rate_target* t) {
   for (int i = 0; i < n; i++) {
@@ -189,7 +217,7 @@ static int check_quality(std::string& err, int n, const rbt_stream_params* p, co
   return RBT_OK;
 }
 // the refusals of rbt_submit_gof_d1 that the parameters alone decide (those that need the streams' sizes: gof_refused); req: the reference handles as clouds
-static int check_d1(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_d1_target* t, rbt::D1Request& req) {
+static int check_d1(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_d1_target* t, rbt::CloudRequest<rbt_d1_target>& req) {
   std::string& err = ctx->last_err;
   req.targets = t; req.cache = &ctx->cloud_cache; req.refs.assign((size_t)n, {});
   for (int i = 0; i < n; i++) {
@@ -203,23 +231,12 @@ static int check_d1(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_d
     if (t[i].min_d1_mdb < 0) { err = who + "min_d1_mdb must not be negative"; return RBT_ERR_PARAM; }
     if (t[i].stat != RBT_D1_MIN && t[i].stat != RBT_D1_MEAN) { err = who + "stat must be RBT_D1_MIN or RBT_D1_MEAN"; return RBT_ERR_PARAM; }
     if (t[i].peak < 0) { err = who + "peak must not be negative (0 = 1023)"; return RBT_ERR_PARAM; }
-    const int lo = t[i].qp_min, hi = t[i].qp_max ? t[i].qp_max : 51;
-    if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
-    if (t[i].n_frames < 1) { err = who + "n_frames must be at least 1"; return RBT_ERR_PARAM; }
-    if (!t[i].patches || !t[i].n_patches) { err = who + "the patch lists are missing"; return RBT_ERR_PARAM; }
-    for (int f = 0; f < t[i].n_frames; f++) {
-      if (t[i].n_patches[f] < 0 || (!t[i].patches[f] && t[i].n_patches[f])) { err = who + "the patch list of frame " + std::to_string(f) + " is missing"; return RBT_ERR_PARAM; }
-      std::string why;
-      if (rbt::mapframe_check(why, &t[i].atlas, t[i].patches[f], t[i].n_patches[f])) { err = who + "frame " + std::to_string(f) + ": " + why; return RBT_ERR_PARAM; }
-      const rbt_pcloud* h = t[i].reference ? t[i].reference[f] : nullptr;
-      if (h) { bool mine = false; for (const rbt_pcloud* c : ctx->clouds) mine |= c == h; if (!mine) { err = who + "reference " + std::to_string(f) + " is not a cloud of this context"; return RBT_ERR_PARAM; } }
-      req.refs[(size_t)i].push_back(h ? h->cloud : nullptr);
-    }
+    if (int rc = check_cloud_target(ctx, who, t[i], false, req.refs[(size_t)i])) return rc;
   }
   return RBT_OK;
 }
 // the refusals of rbt_submit_gof_color that the parameters alone decide, as check_d1
-static int check_color(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_color_target* t, rbt::ColorRequest& req) {
+static int check_color(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_color_target* t, rbt::CloudRequest<rbt_color_target>& req) {
   std::string& err = ctx->last_err;
   req.targets = t; req.cache = &ctx->cloud_cache; req.refs.assign((size_t)n, {});
   for (int i = 0; i < n; i++) {
@@ -235,22 +252,7 @@ static int check_color(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rb
     if (t[i].stat != RBT_D1_MIN && t[i].stat != RBT_D1_MEAN) { err = who + "stat must be RBT_D1_MIN or RBT_D1_MEAN"; return RBT_ERR_PARAM; }
     if (t[i].upsample_filter != RBT_UPSAMPLE_F0 && t[i].upsample_filter != RBT_UPSAMPLE_REPLICATE) { err = who + "upsample_filter must be RBT_UPSAMPLE_F0 or RBT_UPSAMPLE_REPLICATE"; return RBT_ERR_PARAM; }
     if (t[i].attr_transfer != 0 && t[i].attr_transfer != 1) { err = who + "attr_transfer must be 0 or 1"; return RBT_ERR_PARAM; }
-    const int lo = t[i].qp_min, hi = t[i].qp_max ? t[i].qp_max : 51;
-    if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
-    if (t[i].n_frames < 1) { err = who + "n_frames must be at least 1"; return RBT_ERR_PARAM; }
-    if (!t[i].patches || !t[i].n_patches) { err = who + "the patch lists are missing"; return RBT_ERR_PARAM; }
-    for (int f = 0; f < t[i].n_frames; f++) {
-      if (t[i].n_patches[f] < 0 || (!t[i].patches[f] && t[i].n_patches[f])) { err = who + "the patch list of frame " + std::to_string(f) + " is missing"; return RBT_ERR_PARAM; }
-      std::string why;
-      if (rbt::mapframe_check(why, &t[i].atlas, t[i].patches[f], t[i].n_patches[f])) { err = who + "frame " + std::to_string(f) + ": " + why; return RBT_ERR_PARAM; }
-      const rbt_pcloud* h = t[i].reference ? t[i].reference[f] : nullptr;
-      if (h) {
-        bool mine = false; for (const rbt_pcloud* c : ctx->clouds) mine |= c == h;
-        if (!mine) { err = who + "reference " + std::to_string(f) + " is not a cloud of this context"; return RBT_ERR_PARAM; }
-        if (!rbt::pcloud_has_colors(h->cloud)) { err = who + "reference " + std::to_string(f) + " carries no colours"; return RBT_ERR_PARAM; }
-      }
-      req.refs[(size_t)i].push_back(h ? h->cloud : nullptr);
-    }
+    if (int rc = check_cloud_target(ctx, who, t[i], true, req.refs[(size_t)i])) return rc;
   }
   return RBT_OK;
 }
@@ -287,28 +289,28 @@ static int check_qp_maps(std::string& err, int n, const rbt_stream_params* p, co
   }
   return RBT_OK;
 }
-static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
-                  const rbt_d1_target* d1, const rbt_color_target* color, const rbt_frame_qp* lists, bool per_frame, const rbt_qp_map* maps) {
+static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
   RBT_ENTER(ctx);
-  if (targets) if (int rc = check_targets(ctx->last_err, n, p, targets)) return rc;
-  if (quality) if (int rc = check_quality(ctx->last_err, n, p, quality)) return rc;
-  rbt::D1Request req;
-  if (d1) if (int rc = check_d1(ctx, n, p, d1, req)) return rc;
-  if (d1 && per_frame) for (int i = 0; i < n; i++) if (d1[i].stat != RBT_D1_MIN) { ctx->last_err = "entry " + std::to_string(i) + ": stat must be 0 (RBT_D1_MIN): every frame holds the floor on its own"; return RBT_ERR_PARAM; }
-  rbt::ColorRequest creq;
-  if (color) if (int rc = check_color(ctx, n, p, color, creq)) return rc;
+  rbt::GofRequest r; r.n = n; r.in = annexb_in; r.n_in = n_in; r.params = p; r.gof_rule = x.gof_rule; r.targets = x.targets; r.quality = x.quality; r.per_frame = x.per_frame;
+  if (x.targets) if (int rc = check_targets(ctx->last_err, n, p, x.targets)) return rc;
+  if (x.quality) if (int rc = check_quality(ctx->last_err, n, p, x.quality)) return rc;
+  rbt::CloudRequest<rbt_d1_target> d1;
+  if (x.d1) { if (int rc = check_d1(ctx, n, p, x.d1, d1)) return rc; r.d1 = &d1; }
+  if (x.d1 && x.per_frame) for (int i = 0; i < n; i++) if (x.d1[i].stat != RBT_D1_MIN) { ctx->last_err = "entry " + std::to_string(i) + ": stat must be 0 (RBT_D1_MIN): every frame holds the floor on its own"; return RBT_ERR_PARAM; }
+  rbt::CloudRequest<rbt_color_target> color;
+  if (x.color) { if (int rc = check_color(ctx, n, p, x.color, color)) return rc; r.color = &color; }
   std::vector<std::vector<int8_t>> frame_qp;
-  if (lists) if (int rc = check_frame_qp(ctx->last_err, n, p, lists, frame_qp)) return rc;
+  if (x.lists) { if (int rc = check_frame_qp(ctx->last_err, n, p, x.lists, frame_qp)) return rc; r.frame_qp = &frame_qp; }
   std::vector<rbt::QpMapIn> qp_maps;
-  if (maps) if (int rc = check_qp_maps(ctx->last_err, n, p, maps, qp_maps)) return rc;
+  if (x.maps) { if (int rc = check_qp_maps(ctx->last_err, n, p, x.maps, qp_maps)) return rc; r.qp_maps = &qp_maps; }
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
-  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, n, annexb_in, n_in, p, gof_rule, targets, quality, d1 ? &req : nullptr, color ? &creq : nullptr, lists ? &frame_qp : nullptr, per_frame, maps ? &qp_maps : nullptr), ctx};
-  if (quality || d1 || color || lists || maps) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
+  rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, r), ctx};
+  if (x.quality || x.d1 || x.color || x.lists || x.maps) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -369,34 +371,34 @@ int rbt_trim(rbt_ctx* ctx) try {
   rbtk::dev_release_pool();
   return RBT_OK;
 } RBT_CATCH
-static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* quality = nullptr, rbt_d1_floor_result* d1 = nullptr,
-                rbt_color_floor_result* color = nullptr, rbt_frame_floor_result* frames = nullptr, bool d1_frames = false) {
+// kind: the kind of job the calling wait collects, r: where its results go (the streams and n_flat are filled in here). A job of another kind stays collectable; of the two
+// kinds that differ the one that comes first in GofKind is named - by the wait that was called if it is that wait's, by the job's wait if it is the job's
+static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt::GofKind kind = rbt::GOF_PLAIN, rbt::GofResults r = rbt::GofResults()) {
   if (!ctx || !job || !annexb_out || !n_out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   int slot = -1;
   for (int s = 0; s < RBT_MAX_JOBS; s++) if (D.jobs[s] == job) slot = s;
   if (slot < 0 || job->owner != ctx) return RBT_ERR_PARAM;
-  if (rbt::gof_is_quality(job->j) != (quality != nullptr)) {      // the job stays collectable
-    ctx->last_err = quality ? "rbt_wait_gof_quality collects jobs of rbt_submit_gof_quality only" : "a job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality"; return RBT_ERR_PARAM; }
-  if (rbt::gof_is_d1(job->j) != (d1 != nullptr)) {                // ... and so does a job of rbt_submit_gof_d1
-    ctx->last_err = d1 ? "rbt_wait_gof_d1 collects jobs of rbt_submit_gof_d1 only" : "a job of rbt_submit_gof_d1 is collected by rbt_wait_gof_d1"; return RBT_ERR_PARAM; }
-  if (rbt::gof_is_color(job->j) != (color != nullptr)) {          // ... and a job of rbt_submit_gof_color
-    ctx->last_err = color ? "rbt_wait_gof_color collects jobs of rbt_submit_gof_color only" : "a job of rbt_submit_gof_color is collected by rbt_wait_gof_color"; return RBT_ERR_PARAM; }
-  if (rbt::gof_is_d1_frames(job->j) != (frames != nullptr && d1_frames)) { // ... and a job of rbt_submit_gof_d1_frames
-    ctx->last_err = d1_frames ? "rbt_wait_gof_d1_frames collects jobs of rbt_submit_gof_d1_frames only" : "a job of rbt_submit_gof_d1_frames is collected by rbt_wait_gof_d1_frames"; return RBT_ERR_PARAM; }
-  if (rbt::gof_is_quality_frames(job->j) != (frames != nullptr && !d1_frames)) { // ... and a job of rbt_submit_gof_quality_frames
-    ctx->last_err = frames ? "rbt_wait_gof_quality_frames collects jobs of rbt_submit_gof_quality_frames only" : "a job of rbt_submit_gof_quality_frames is collected by rbt_wait_gof_quality_frames"; return RBT_ERR_PARAM; }
-  int n_flat = 0;
-  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, annexb_out, n_out, results, quality, &n_flat, d1, color, frames);
+  static const char* const mismatch[][2] = {      // per GofKind: the wait was called for a job of another kind / the job was handed to another wait
+    {nullptr, nullptr},
+    {"rbt_wait_gof_quality collects jobs of rbt_submit_gof_quality only", "a job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality"},
+    {"rbt_wait_gof_d1 collects jobs of rbt_submit_gof_d1 only", "a job of rbt_submit_gof_d1 is collected by rbt_wait_gof_d1"},
+    {"rbt_wait_gof_color collects jobs of rbt_submit_gof_color only", "a job of rbt_submit_gof_color is collected by rbt_wait_gof_color"},
+    {"rbt_wait_gof_d1_frames collects jobs of rbt_submit_gof_d1_frames only", "a job of rbt_submit_gof_d1_frames is collected by rbt_wait_gof_d1_frames"},
+    {"rbt_wait_gof_quality_frames collects jobs of rbt_submit_gof_quality_frames only", "a job of rbt_submit_gof_quality_frames is collected by rbt_wait_gof_quality_frames"}};
+  const rbt::GofKind is = rbt::gof_kind(job->j);
+  if (is != kind) { const bool called = is == rbt::GOF_PLAIN || (kind != rbt::GOF_PLAIN && kind < is); ctx->last_err = mismatch[called ? kind : is][called ? 0 : 1]; return RBT_ERR_PARAM; }
+  int n_flat = 0; r.out = annexb_out; r.n_out = n_out; r.n_flat = &n_flat;
+  int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, r);
   if (!rc) ctx->n_flat = n_flat;
   D.jobs[slot] = nullptr; delete job;
   return rc;
 }
-int rbt_wait_gof(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out) try { return wait(ctx, job, annexb_out, n_out, nullptr); } RBT_CATCH
+int rbt_wait_gof(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out) try { return wait(ctx, job, annexb_out, n_out); } RBT_CATCH
 // ---- a QP per point-cloud frame ----
 int rbt_submit_gof_frame_qp(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_frame_qp* lists, rbt_job** job) try {
   if (!lists) return RBT_ERR_PARAM;
-  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, nullptr, nullptr, lists);
+  SubmitExtras x; x.lists = lists; return submit(ctx, n, annexb_in, n_in, p, job, x);
 } RBT_CATCH
 int rbt_transcode_gof_frame_qp(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_frame_qp* lists,
                                uint8_t** annexb_out, size_t* n_out) try {
@@ -409,11 +411,11 @@ int rbt_transcode_gof_frame_qp(rbt_ctx* ctx, int n, const uint8_t* const* annexb
 // ---- transcoding to a byte budget ----
 int rbt_submit_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_rate_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
-  return submit(ctx, n, annexb_in, n_in, p, job, true, targets);
+  SubmitExtras x; x.targets = targets; return submit(ctx, n, annexb_in, n_in, p, job, x);
 } RBT_CATCH
 int rbt_wait_gof_rate(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results) try {
   if (!results) return RBT_ERR_PARAM;
-  return wait(ctx, job, annexb_out, n_out, results);
+  rbt::GofResults r; r.rate = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_PLAIN, r);
 } RBT_CATCH
 int rbt_transcode_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_rate_target* targets,
                            uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results) try {
@@ -426,11 +428,11 @@ int rbt_transcode_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in,
 // ---- transcoding to a PSNR floor ----
 int rbt_submit_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
-  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, targets);
+  SubmitExtras x; x.quality = targets; return submit(ctx, n, annexb_in, n_in, p, job, x);
 } RBT_CATCH
 int rbt_wait_gof_quality(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_quality_result* results) try {
   if (!results) return RBT_ERR_PARAM;
-  return wait(ctx, job, annexb_out, n_out, nullptr, results);
+  rbt::GofResults r; r.quality = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_QUALITY, r);
 } RBT_CATCH
 int rbt_transcode_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets,
                               uint8_t** annexb_out, size_t* n_out, rbt_quality_result* results) try {
@@ -442,7 +444,7 @@ int rbt_transcode_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_
 } RBT_CATCH
 // ---- a QP per CTB ----
 int rbt_submit_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_qp_map* maps, rbt_job** job) try {
-  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, nullptr, nullptr, nullptr, false, maps);      // maps == NULL: rbt_submit_gof
+  SubmitExtras x; x.maps = maps; return submit(ctx, n, annexb_in, n_in, p, job, x);      // maps == NULL: rbt_submit_gof
 } RBT_CATCH
 int rbt_transcode_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_qp_map* maps,
                              uint8_t** annexb_out, size_t* n_out) try {
@@ -459,11 +461,11 @@ int rbt_qp_map_from_patches(const rbt_atlas_params* atlas, const rbt_patch* patc
 // ---- floors held frame by frame ----
 int rbt_submit_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
-  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, targets, nullptr, nullptr, nullptr, true);
+  SubmitExtras x; x.quality = targets; x.per_frame = true; return submit(ctx, n, annexb_in, n_in, p, job, x);
 } RBT_CATCH
 int rbt_wait_gof_quality_frames(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
   if (!results) return RBT_ERR_PARAM;
-  return wait(ctx, job, annexb_out, n_out, nullptr, nullptr, nullptr, nullptr, results);
+  rbt::GofResults r; r.frames = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_QUALITY_FRAMES, r);
 } RBT_CATCH
 int rbt_transcode_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets,
                                      uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
@@ -475,11 +477,11 @@ int rbt_transcode_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* 
 } RBT_CATCH
 int rbt_submit_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
-  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, targets, nullptr, nullptr, true);
+  SubmitExtras x; x.d1 = targets; x.per_frame = true; return submit(ctx, n, annexb_in, n_in, p, job, x);
 } RBT_CATCH
 int rbt_wait_gof_d1_frames(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
   if (!results) return RBT_ERR_PARAM;
-  return wait(ctx, job, annexb_out, n_out, nullptr, nullptr, nullptr, nullptr, results, true);
+  rbt::GofResults r; r.frames = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_D1_FRAMES, r);
 } RBT_CATCH
 int rbt_transcode_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets,
                                 uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
@@ -492,11 +494,11 @@ int rbt_transcode_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annex
 // ---- transcoding geometry to a D1 floor ----
 int rbt_submit_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
-  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, targets);
+  SubmitExtras x; x.d1 = targets; return submit(ctx, n, annexb_in, n_in, p, job, x);
 } RBT_CATCH
 int rbt_wait_gof_d1(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results) try {
   if (!results) return RBT_ERR_PARAM;
-  return wait(ctx, job, annexb_out, n_out, nullptr, nullptr, results);
+  rbt::GofResults r; r.d1 = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_D1, r);
 } RBT_CATCH
 int rbt_transcode_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets,
                          uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results) try {
@@ -509,11 +511,11 @@ int rbt_transcode_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, c
 // ---- transcoding attributes to a colour PSNR floor ----
 int rbt_submit_gof_color(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_color_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
-  return submit(ctx, n, annexb_in, n_in, p, job, true, nullptr, nullptr, nullptr, targets);
+  SubmitExtras x; x.color = targets; return submit(ctx, n, annexb_in, n_in, p, job, x);
 } RBT_CATCH
 int rbt_wait_gof_color(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_color_floor_result* results) try {
   if (!results) return RBT_ERR_PARAM;
-  return wait(ctx, job, annexb_out, n_out, nullptr, nullptr, nullptr, results);
+  rbt::GofResults r; r.color = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_COLOR, r);
 } RBT_CATCH
 int rbt_transcode_gof_color(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_color_target* targets,
                             uint8_t** annexb_out, size_t* n_out, rbt_color_floor_result* results) try {

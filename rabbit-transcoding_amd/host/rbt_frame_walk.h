@@ -2,7 +2,8 @@
 // walks is encoded in, and the assembly of the returned stream from the frames the passes brought. A frame of a geometry / attribute stream is a closed pair of pictures
 // (an I picture and a P picture that refers to it), so a pass may carry any subset of the frames at any QPs and frame f at QP q comes out the same whatever else the pass
 // holds. Plain host code without a device call, so that tests/frame_qp_check.cpp can run it under the sanitizers. The walk does not know what a figure is: the caller hands
-// in the step of its kind of floor (a PSNR floor's today; a byte cap or a colour floor per frame would hand in theirs).
+// in the step of its floor - walk_step of rbt_transcode.cpp, which binds the figure of the walk's kind: a PSNR floor's or a D1 floor's; a byte cap or a colour floor per frame
+// would be one more kind there.
 #pragma once
 #include <cstddef>
 #include <cstdint>

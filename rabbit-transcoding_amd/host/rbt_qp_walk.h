@@ -1,6 +1,6 @@
 // The walk that a byte budget and a PSNR floor share (include/rbt.h, "transcoding to a byte budget", "transcoding to a PSNR floor"): both look for the boundary of a
 // condition on the trial encodes of one entry - the smallest QP whose stream fits the budget, the largest whose distortion meets the floor. One walk with a direction, and
-// one rule for what a round of trial encodes brings it. Plain host code without a device call; rbt_rate_walk.h and rbt_quality_walk.h add the seed and the condition.
+// one rule for what a round of trial encodes brings it. Plain host code without a device call; rbt_rate_walk.h adds a budget's seed and condition, rbt_floor_walk.h a floor's.
 #pragma once
 #include <map>
 #include <vector>

@@ -10,6 +10,7 @@
 #include "rbt_batch.h"
 #include "rbt_transcode.h"
 #include "rbt_rate_walk.h"
+#include "rbt_floor_walk.h"
 #include "rbt_quality_walk.h"
 #include "rbt_d1_walk.h"
 #include "rbt_color_walk.h"
@@ -487,8 +488,9 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
 // Targets - a byte budget or a PSNR floor per entry -: what a pipeline with such an entry keeps between the rounds of its trial encodes (run_rounds, launch_round, finish_round)
 struct RoundCand { int q, qp, walk; int fw = -1; FramePass pass; };   // entry q of the group at qp; walk: index of its walk, -1 for a constant-QP entry of the pipeline; fw >= 0: a pass of the entry's frame walks (qp: the entry's own, for the parameter sets)
 struct TargetTried : QualityTried { std::vector<rbt_d1_result> d1; std::vector<rbt_color_result> color; };      // d1 / color: a job with D1 / colour floors, the frames of the trial
-// toward < 0: a budget, toward > 0: a floor - on the PSNR, (is_d1) on D1 or (is_color) on the colour PSNR of the cloud
-struct TargetWalk : QpWalk<TargetTried> { RateGoal budget; QualityGoal floor; D1Goal dist; ColorGoal col; bool is_d1 = false, is_color = false; };
+// A budget (toward < 0) or a floor (toward > 0, rbt_floor_walk.h) - on the PSNR of `region` at bit_depth, on D1 or on the colour PSNR of `channel` of the clouds, stat over the frames
+enum WalkKind { WALK_BUDGET, WALK_PSNR, WALK_D1, WALK_COLOR };
+struct TargetWalk : QpWalk<TargetTried> { WalkKind kind = WALK_BUDGET; RateGoal budget; FloorGoal floor; int region = 0, bit_depth = 8, stat = RBT_D1_MIN, channel = 0; };
 // Quality floors: the occupancy source of an entry (include/rbt.h, "transcoding to a PSNR floor", rule 3), kept in the job because the pipelines that use it are encoded in
 // the wait half: the pooled luma planes of the occupancy stream, and for occupancy_rd the per-4x4-unit maps made of them (both live in GofJob::pooled until the job goes)
 struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
@@ -502,28 +504,22 @@ struct RoundPipe {
   std::vector<std::vector<rbt_color_result>> color;   // (colour floors) the same
   bool done = false;
 };
+// Cloud targets - D1 floors and colour floors -, what the two kinds share of the target of one entry as the job keeps it: the patch lists copied, the reference clouds
+// (nullptr = the cloud of the decoded input), where the decoded input of the occupancy source lies and the device time of the clouds' work
+struct CloudEntry { std::vector<std::vector<rbt_patch>> patches; std::vector<const PCloud*> ref; int in_pipe = -1, in_ds = -1, in_ow = 0, in_oh = 0; double cloud_ms = 0; };
 // D1 floors: the target of one entry (n_frames 0: none) as the job keeps it, and what its clouds are rebuilt from. The decoded input of the occupancy source (in_*: the
 // pipeline and decoded stream that hold it, its displayed size) is what the reference clouds of frames without a handle are made of; the trials' clouds use the pooled
 // planes (GofJob::qocc). frames / own_ref live while run_rounds runs (D1Live).
-struct D1Entry {
-  rbt_d1_target t; std::vector<std::vector<rbt_patch>> patches; std::vector<const PCloud*> ref;
-  int in_pipe = -1, in_ds = -1, in_ow = 0, in_oh = 0;
-  std::vector<MapFrame*> frames; std::vector<PCloud*> own_ref; double cloud_ms = 0;
-};
-struct D1Out { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<rbt_d1_result> frames; double cloud_ms = 0; };
+struct D1Entry : CloudEntry { rbt_d1_target t; std::vector<MapFrame*> frames; std::vector<PCloud*> own_ref; };
 // Colour floors: the target of one attribute entry (n_frames 0: none) as the job keeps it. geo: the entry that is its geometry source; in_* : where the decoded input of
 // the occupancy source lies, as D1Entry has it. frames: the geometry half of every frame (ColorFrame, rbt_pcc.h), made behind the geometry pipeline's encode from its
 // reconstruction's luma (geo_planes, packed) and kept until the attribute pipeline's rounds end; own_ref: the same for the decoded input, where no handle was given.
-struct ColorEntry {
-  rbt_color_target t; std::vector<std::vector<rbt_patch>> patches; std::vector<const PCloud*> ref;
-  int geo = -1, in_pipe = -1, in_ds = -1, in_ow = 0, in_oh = 0;
-  uint16_t* geo_planes = nullptr; uint16_t* in_planes = nullptr;
-  std::vector<ColorFrame*> frames, own_ref; double cloud_ms = 0;
-};
-struct ColorOut { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<rbt_color_result> frames; double cloud_ms = 0; };
+struct ColorEntry : CloudEntry { rbt_color_target t; int geo = -1; uint16_t* geo_planes = nullptr; uint16_t* in_planes = nullptr; std::vector<ColorFrame*> frames, own_ref; };
+// what a pipeline's rounds leave of an entry with a cloud target: the walk's result - or the entry's own QP - and the frames' figures there
+template <class Result> struct FloorOut { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<Result> frames; double cloud_ms = 0; };
 struct FrameFloorOut { int q0 = 0, n_passes = 0, bit_depth = 8; std::vector<rbt_frame_pick> frames; std::vector<rbt_d1_result> d1; double cloud_ms = 0; uint64_t bytes = 0, pictures = 0; QualitySums sums; };
 struct GofJob {
-  int n = 0, slot = 0, ng = 0, rc = 0;
+  int n = 0, slot = 0, ng = 0, rc = 0; GofKind kind = GOF_PLAIN;      // kind: which submit made the job, fixed there
   std::vector<std::vector<int>> groups; std::vector<int> order;
   std::vector<DecodeBatch> db; std::vector<EncodeBatch> eb; std::vector<char> chained;
   std::vector<void*> pooled;
@@ -545,10 +541,10 @@ struct GofJob {
   std::vector<rbt_quality_target> qtargets; std::vector<QualityOcc> qocc; std::vector<rbt_quality_result> qresults; bool refused = false;
   // D1 floors (rbt_submit_gof_d1): the job runs as a job with quality floors that are all 0 - every geometry / attribute pipeline is encoded in the wait half, the pooled
   // occupancy planes and the maps of occupancy_rd stay in the job - and d1 holds the targets with their patch lists copied (d1_setup, d1_score, run_rounds)
-  std::vector<D1Entry> d1; std::vector<D1Out> d1out; PCloudCache* cloud_cache = nullptr;
+  std::vector<D1Entry> d1; std::vector<FloorOut<rbt_d1_result>> d1out; PCloudCache* cloud_cache = nullptr;
   // colour floors (rbt_submit_gof_color): the same kind of job; the geometry pipelines' rounds run before the attribute pipelines' (gof_wait), because the clouds' geometry
   // half is made behind the geometry encode (color_geometry) and recoloured per attribute trial (color_setup, color_score)
-  std::vector<ColorEntry> color; std::vector<ColorOut> colorout;
+  std::vector<ColorEntry> color; std::vector<FloorOut<rbt_color_result>> colorout;
   // a QP per point-cloud frame (rbt_submit_gof_frame_qp): per entry the list, empty = the entry's own QP; such a job is an ordinary constant-QP job in every other respect
   std::vector<std::vector<int8_t>> frame_qp;
   std::vector<QpMapIn> qp_maps;      // a QP per CTB (rbt_submit_gof_qp_map): per entry the maps, an empty qp = none; the job is a constant-QP job otherwise, as with frame_qp
@@ -578,11 +574,7 @@ static void bind_streams(GofJob& j, int depth) {
 }
 
 size_t gof_memory(const GofJob* j) { return j ? j->dev_bytes + j->rate_bytes : 0; }
-bool gof_is_quality(const GofJob* j) { return j && !j->qtargets.empty() && j->d1.empty() && j->color.empty() && !j->per_frame; }
-bool gof_is_quality_frames(const GofJob* j) { return j && j->per_frame && j->d1.empty(); }
-bool gof_is_d1_frames(const GofJob* j) { return j && j->per_frame && !j->d1.empty(); }
-bool gof_is_d1(const GofJob* j) { return j && !j->d1.empty() && !j->per_frame; }
-bool gof_is_color(const GofJob* j) { return j && !j->color.empty(); }
+GofKind gof_kind(const GofJob* j) { return j ? j->kind : GOF_PLAIN; }
 static bool has_color(const GofJob& j, int i) { return !j.color.empty() && j.color[i].t.n_frames > 0; }
 static bool has_color_floor(const GofJob& j, int i) { return has_color(j, i) && j.color[i].t.min_psnr_mdb != 0; }
 static bool color_pipe(const GofJob& j, int gi) { for (int i : j.groups[gi]) if (has_color(j, i)) return true; return false; }
@@ -591,6 +583,17 @@ static bool has_d1_floor(const GofJob& j, int i) { return has_d1(j, i) && j.d1[i
 int gof_refused(const GofJob* j, std::string& err) { if (!j || !j->refused) return 0; err = j->err; return j->rc; }
 static bool has_target(const GofJob& j, int i) { return !j.targets.empty() && j.targets[i].target_bytes != 0; }
 static bool has_floor(const GofJob& j, int i) { return !j.qtargets.empty() && j.qtargets[i].min_psnr_mdb != 0; }
+// the displayed size of decoded stream ds - its pictures seen through the conformance window - and its picture count
+static int displayed(const DecodeBatch& db, int ds, int* w, int* h) {
+  const RbtStreamCfg& c = db.frames[db.stream_first[ds]].cfg; const Sps& sps = db.stream_sps[ds];
+  *w = c.w - 2 * sps.conf_win[0] - 2 * sps.conf_win[1]; *h = c.h - 2 * sps.conf_win[2] - 2 * sps.conf_win[3];
+  return db.stream_count[ds];
+}
+// the pipeline that holds an entry of the call, and the entry's position in the pipeline's group
+static bool find_entry(const GofJob& j, int entry, int* pipe, size_t* q) {
+  for (int g = 0; g < j.ng; g++) for (size_t k = 0; k < j.groups[g].size(); k++) if (j.groups[g][k] == entry) { *pipe = g; *q = k; return true; }
+  return false;
+}
 
 // What lives only while a job is submitted
 struct SubmitPlan {
@@ -708,8 +711,8 @@ static int check_qp_maps(GofJob& j) {
     if (cnt % 2 || m.n_frames != cnt / 2) {
       j.err = who + "rbt_qp_map.n_frames is " + std::to_string(m.n_frames) + ", the stream holds " + std::to_string(cnt) + " pictures (n_frames must be pictures / 2)";
       j.refused = true; return RBT_ERR_PARAM; }
-    const RbtStreamCfg& c = db.frames[db.stream_first[ds]].cfg; const Sps& isps = db.stream_sps[ds];
-    const int dw = c.w - 2 * isps.conf_win[0] - 2 * isps.conf_win[1], dh = c.h - 2 * isps.conf_win[2] - 2 * isps.conf_win[3], l2 = j.params[i].log2_ctb ? j.params[i].log2_ctb : 5;
+    int dw, dh; displayed(db, ds, &dw, &dh);
+    const int l2 = j.params[i].log2_ctb ? j.params[i].log2_ctb : 5;
     const int wc = (dw + (1 << l2) - 1) >> l2, hc = (dh + (1 << l2) - 1) >> l2;
     if (dw > 0 && dh > 0 && l2 >= 4 && l2 <= 6 && (m.w_ctb != wc || m.h_ctb != hc)) {
       j.err = who + "rbt_qp_map.w_ctb x h_ctb is " + std::to_string(m.w_ctb) + " x " + std::to_string(m.h_ctb) + ", the output pictures (" + std::to_string(dw) + " x " + std::to_string(dh) + ") hold " +
@@ -801,75 +804,52 @@ static int seed_budgets(GofJob& j, int gi, RoundPipe& r, bool census) {
   }
   return 0;
 }
-// A floor's walk starts with a probe at the entry's own QP
+// A floor's walk starts with a probe at the entry's own QP; what the figures of its kind need comes from the target. pinned: the range is the entry's own QP alone
 static int entry_bit_depth(const GofJob& j, int gi, size_t q) { const DecodeBatch& db = j.db[gi]; return db.frames[db.stream_first[j.dec_of[gi][q]]].cfg.bit_depth; }
-static void seed_floors(GofJob& j, int gi, RoundPipe& r) {
+static void walk_goal(TargetWalk& w, const rbt_quality_target& t) { w.kind = WALK_PSNR; w.floor.floor_mdb = t.min_psnr_mdb; w.region = t.region; }
+static void walk_goal(TargetWalk& w, const rbt_d1_target& t) { w.kind = WALK_D1; w.floor.floor_mdb = t.min_d1_mdb; w.stat = t.stat; }
+static void walk_goal(TargetWalk& w, const rbt_color_target& t) { w.kind = WALK_COLOR; w.floor.floor_mdb = t.min_psnr_mdb; w.stat = t.stat; w.channel = t.channel; }
+template <class Target> static TargetWalk floor_walk(const GofJob& j, int gi, size_t q, const Target& t, bool pinned = false) {
+  const int i = j.groups[gi][q], qp = j.params[i].qp;
+  TargetWalk w = new_walk(q, i, t); walk_goal(w, t); w.bit_depth = entry_bit_depth(j, gi, q);
+  if (pinned) w.lo = w.hi = std::min(51, std::max(0, qp));
+  floor_seed(w, w.floor, qp);
+  return w;
+}
+// the walks of a pipeline's entries with a floor of the job's kind
+static void seed_floors(GofJob& j, int gi, RoundPipe& r, WalkKind kind) {
   const std::vector<int>& gs = j.groups[gi];
-  for (size_t q = 0; q < gs.size(); q++) if (has_floor(j, gs[q])) {
-    const rbt_quality_target& t = j.qtargets[gs[q]];
-    TargetWalk w = new_walk(q, gs[q], t); w.floor.floor_mdb = t.min_psnr_mdb; w.floor.region = t.region; w.floor.bit_depth = entry_bit_depth(j, gi, q);
-    quality_seed(w, w.floor, j.params[gs[q]].qp);
-    r.walks.push_back(std::move(w));
+  for (size_t q = 0; q < gs.size(); q++) {
+    const int i = gs[q];
+    if (kind == WALK_D1) { if (has_d1_floor(j, i)) r.walks.push_back(floor_walk(j, gi, q, j.d1[i].t)); }
+    else if (kind == WALK_COLOR) { if (has_color_floor(j, i)) r.walks.push_back(floor_walk(j, gi, q, j.color[i].t)); }
+    else if (has_floor(j, i)) r.walks.push_back(floor_walk(j, gi, q, j.qtargets[i]));
   }
 }
-// Floors held frame by frame: every entry of the pipeline gets one walk per point-cloud frame, seeded like the entry's walk. An entry without a floor is a walk whose
-// range is its own QP alone: one pass, the figures reported per frame
+// Floors held frame by frame: every entry of the pipeline gets one walk per point-cloud frame, seeded like the entry's walk - a D1 floor's on the frame's own cloud (one
+// result per trial, so the statistic is that result) where the entry has a D1 target, else a PSNR floor's. An entry without a floor is a walk whose range is its own QP
+// alone: one pass, the figures reported per frame
 static void seed_frame_floors(GofJob& j, int gi, RoundPipe& r) {
   const std::vector<int>& gs = j.groups[gi]; const DecodeBatch& db = j.db[gi];
   for (size_t q = 0; q < gs.size(); q++) {
-    const rbt_quality_target& t = j.qtargets[gs[q]]; const int qp = j.params[gs[q]].qp, nf = db.stream_count[j.dec_of[gi][q]] / 2;
-    FrameWalks<TargetWalk> fw; fw.q = (int)q; fw.entry = gs[q]; fw.n_enc.assign((size_t)nf, 0);
-    for (int f = 0; f < nf; f++) {
-      TargetWalk w = new_walk(q, gs[q], t);
-      if (!t.min_psnr_mdb) w.lo = w.hi = std::min(51, std::max(0, qp));
-      w.floor.floor_mdb = t.min_psnr_mdb; w.floor.region = t.region; w.floor.bit_depth = entry_bit_depth(j, gi, q);
-      quality_seed(w, w.floor, qp);
-      if (has_d1(j, gs[q])) {      // a D1 target: the frame's walk is the D1 floor's on the frame's own cloud (one result per trial, so the statistic is that result)
-        const rbt_d1_target& d = j.d1[gs[q]].t;
-        if (d.min_d1_mdb) { w.lo = d.qp_min; w.hi = d.qp_max ? d.qp_max : 51; }
-        w.is_d1 = true; w.dist.floor_mdb = d.min_d1_mdb; w.dist.stat = RBT_D1_MIN;
-        d1_seed(w, w.dist, qp);
-      }
-      fw.frames.push_back(std::move(w));
-    }
+    const int i = gs[q], nf = db.stream_count[j.dec_of[gi][q]] / 2;
+    FrameWalks<TargetWalk> fw; fw.q = (int)q; fw.entry = i; fw.n_enc.assign((size_t)nf, 0);
+    const TargetWalk w = has_d1(j, i) ? floor_walk(j, gi, q, j.d1[i].t, !j.d1[i].t.min_d1_mdb) : floor_walk(j, gi, q, j.qtargets[i], !j.qtargets[i].min_psnr_mdb);
+    fw.frames.assign((size_t)nf, w);
     r.fwalks.push_back(std::move(fw));
-  }
-}
-// A D1 floor's walk is the PSNR floor's with D in place of the PSNR (rbt_d1_walk.h)
-static void seed_d1_floors(GofJob& j, int gi, RoundPipe& r) {
-  const std::vector<int>& gs = j.groups[gi];
-  for (size_t q = 0; q < gs.size(); q++) if (has_d1_floor(j, gs[q])) {
-    const rbt_d1_target& t = j.d1[gs[q]].t;
-    TargetWalk w = new_walk(q, gs[q], t); w.is_d1 = true; w.dist.floor_mdb = t.min_d1_mdb; w.dist.stat = t.stat;
-    d1_seed(w, w.dist, j.params[gs[q]].qp);
-    r.walks.push_back(std::move(w));
-  }
-}
-// ... and so is a colour floor's (rbt_color_walk.h)
-static void seed_color_floors(GofJob& j, int gi, RoundPipe& r) {
-  const std::vector<int>& gs = j.groups[gi];
-  for (size_t q = 0; q < gs.size(); q++) if (has_color_floor(j, gs[q])) {
-    const rbt_color_target& t = j.color[gs[q]].t;
-    TargetWalk w = new_walk(q, gs[q], t); w.is_color = true; w.col.floor_mdb = t.min_psnr_mdb; w.col.stat = t.stat; w.col.channel = t.channel;
-    color_seed(w, w.col, j.params[gs[q]].qp);
-    r.walks.push_back(std::move(w));
   }
 }
 // true: settled; false: the walk needs the trial at `need` next (alone: a probe, the round brings nothing else for it)
 static bool walk_step(TargetWalk& w, int& need, int& dir, bool& alone) {
-  if (w.is_color) {
-    alone = !color_probe(w, w.col);
-    if (alone) { need = w.col.q0; dir = 0; return false; }
-    return qp_walk_step(w, color_holds(w, w.col), need, dir);
-  }
-  if (w.is_d1) {
-    alone = !d1_probe(w, w.dist);
-    if (alone) { need = w.dist.q0; dir = 0; return false; }
-    return qp_walk_step(w, d1_holds(w, w.dist), need, dir);
-  }
-  alone = w.toward > 0 && !quality_probe(w, w.floor);
+  alone = false;
+  if (w.kind == WALK_BUDGET) return qp_walk_step(w, rate_fits(w, w.budget), need, dir);
+  auto figure = [&w](const TargetTried& t) { return w.kind == WALK_D1 ? d1_figure(t.d1, w.stat) : w.kind == WALK_COLOR ? color_figure(t.color, w.stat, w.channel) : quality_region_psnr(t.sums, w.region, w.bit_depth); };
+  auto meets = [&w](const TargetTried& t) {
+    return w.kind == WALK_D1 ? d1_meets(t.d1, w.stat, w.floor.floor_mdb) : w.kind == WALK_COLOR ? color_meets(t.color, w.stat, w.channel, w.floor.floor_mdb) : quality_meets(t.sums, w.region, w.floor.floor_mdb, w.bit_depth);
+  };
+  alone = !floor_probe(w, w.floor, figure);
   if (alone) { need = w.floor.q0; dir = 0; return false; }
-  return w.toward > 0 ? qp_walk_step(w, quality_holds(w, w.floor), need, dir) : qp_walk_step(w, rate_fits(w, w.budget), need, dir);
+  return qp_walk_step(w, floor_holds(w, meets), need, dir);
 }
 // The round to run next, in group order: what every unsettled walk asks for (qp_round) and, in the first round, the pipeline's entries without a target at their own QP
 static void name_round(const GofJob& j, int gi, RoundPipe& r, bool first) {
@@ -946,6 +926,34 @@ static int launch_round(GofJob& j, int gi) {
   encode_launch_entropy_rest(eb);
   return 0;
 }
+// ------------------------------------------------------------------------------------------------ cloud targets: what D1 floors and colour floors share
+// The refusals of rules 1 and 2 that the two kinds have in common, nullptr = the target fits. They come in two parts, which each kind calls where its own checks leave
+// room for them: a target against the stream it sits on (its displayed size dw x dh, its cnt pictures) ...
+template <class Target> static const char* cloud_fits_stream(const Target& t, int dw, int dh, int cnt) {
+  if (dw != t.atlas.width || dh != t.atlas.height) return "the displayed picture size is not atlas.width x atlas.height";
+  if (cnt != t.atlas.map_count * t.n_frames) return "the picture count is not atlas.map_count x n_frames";
+  return nullptr;
+}
+// ... and against its occupancy source, entry `io` with the pooled planes `os`, whose decoded input is located on the way (E.in_*: what the reference clouds of frames
+// without a handle are made of)
+template <class Target> static const char* cloud_fits_occupancy(const GofJob& j, const OccSource& os, int io, const Target& t, int dw, int dh, CloudEntry& E) {
+  if (os.n != t.n_frames) return "the occupancy source does not hold n_frames pictures";
+  if (os.ow * t.atlas.occupancy_precision != dw || os.oh * t.atlas.occupancy_precision != dh) return "atlas.occupancy_precision is not width / (output occupancy width)";
+  size_t oq = 0;
+  if (!find_entry(j, io, &E.in_pipe, &oq) || j.db[E.in_pipe].frames.empty()) return "the occupancy source was not decoded";
+  E.in_ds = j.dec_of[E.in_pipe][oq];
+  displayed(j.db[E.in_pipe], E.in_ds, &E.in_ow, &E.in_oh);
+  if (E.in_ow <= 0 || E.in_oh <= 0 || dw % E.in_ow || dh % E.in_oh || dw / E.in_ow != dh / E.in_oh) return "the input occupancy size does not divide the atlas by one whole factor";
+  return nullptr;
+}
+// the device time of one cloud's work, between the events of T_CENSUS on the pipeline's stream (no census runs in a job with floors)
+static int cloud_timed(GofJob& j, CloudEntry& E, int rc) {
+  rbtk::timer_end(T_CENSUS);
+  if (rc) return rc;
+  if (rbtk::dev_sync()) { j.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  E.cloud_ms += rbtk::timer_ms(T_CENSUS);
+  return 0;
+}
 // ------------------------------------------------------------------------------------------------ D1 floors (include/rbt.h, "transcoding geometry to a D1 floor")
 // At submit, behind quality_prepare (which has found the pooled planes of every entry's occupancy source): rules 1 and 2 for every entry of the pipeline with a target,
 // where the decoded input of the occupancy source lies, and what the clouds will take (rbt_job_memory)
@@ -954,22 +962,13 @@ static int d1_prepare(GofJob& j, SubmitPlan& s, int gi) {
   if (db.frames.empty()) return 0;
   auto refuse = [&](int i, const std::string& why) { j.err = "entry " + std::to_string(i) + ": " + why; j.refused = true; return RBT_ERR_PARAM; };
   for (size_t q = 0; q < gs.size(); q++) if (has_d1(j, gs[q])) {
-    const int i = gs[q], io = s.meas_of[i], ds = j.dec_of[gi][q], first = db.stream_first[ds], cnt = db.stream_count[ds];
+    const int i = gs[q], io = s.meas_of[i];
     D1Entry& E = j.d1[i]; const rbt_atlas_params& a = E.t.atlas;
     if (io < 0 || s.occ_src[io].n <= 0) return refuse(i, "a D1 target needs an occupancy source: a pooled occupancy entry (occupancy_precision 4) in front of it");
-    const OccSource& os = s.occ_src[io]; const RbtStreamCfg& c = db.frames[first].cfg; const Sps& isps = db.stream_sps[ds];
-    const int dw = c.w - 2 * isps.conf_win[0] - 2 * isps.conf_win[1], dh = c.h - 2 * isps.conf_win[2] - 2 * isps.conf_win[3];
-    if (dw != a.width || dh != a.height) return refuse(i, "the displayed picture size is not atlas.width x atlas.height");
-    if (cnt != a.map_count * E.t.n_frames) return refuse(i, "the picture count is not atlas.map_count x n_frames");
+    int dw, dh; const int cnt = displayed(db, j.dec_of[gi][q], &dw, &dh);
+    if (const char* why = cloud_fits_stream(E.t, dw, dh, cnt)) return refuse(i, why);
     if (j.per_frame && a.map_count != 2) return refuse(i, "floors held frame by frame need atlas.map_count 2: a point-cloud frame is the two pictures that are coded as a pair");
-    if (os.n != E.t.n_frames) return refuse(i, "the occupancy source does not hold n_frames pictures");
-    if (os.ow * a.occupancy_precision != dw || os.oh * a.occupancy_precision != dh) return refuse(i, "atlas.occupancy_precision is not width / (output occupancy width)");
-    // the decoded input of the occupancy source
-    for (int g = 0; g < j.ng; g++) for (size_t k = 0; k < j.groups[g].size(); k++) if (j.groups[g][k] == io) { E.in_pipe = g; E.in_ds = j.dec_of[g][k]; }
-    if (E.in_pipe < 0 || j.db[E.in_pipe].frames.empty()) return refuse(i, "the occupancy source was not decoded");
-    const DecodeBatch& ob = j.db[E.in_pipe]; const RbtStreamCfg& oc = ob.frames[ob.stream_first[E.in_ds]].cfg; const Sps& osps = ob.stream_sps[E.in_ds];
-    E.in_ow = oc.w - 2 * osps.conf_win[0] - 2 * osps.conf_win[1]; E.in_oh = oc.h - 2 * osps.conf_win[2] - 2 * osps.conf_win[3];
-    if (E.in_ow <= 0 || E.in_oh <= 0 || dw % E.in_ow || dh % E.in_oh || dw / E.in_ow != dh / E.in_oh) return refuse(i, "the input occupancy size does not divide the atlas by one whole factor");
+    if (const char* why = cloud_fits_occupancy(j, s.occ_src[io], io, E.t, dw, dh, E)) return refuse(i, why);
     // memory: per frame the frame's maps (twice while a reference cloud is made), per frame without a handle a volume, one more for the trial being scored; the packed
     // planes of one trial and of the decoded input
     size_t bytes = PCLOUD_VOL_BYTES + 2 * (size_t)cnt * (size_t)dw * dh * 2 + (size_t)E.t.n_frames * (size_t)E.in_ow * E.in_oh * 2;
@@ -983,23 +982,24 @@ struct GatherSet {
   std::vector<RbtGatherPic> pics; void* d = nullptr; int max_chunks = 0;
   ~GatherSet() { rbtk::dev_free(d); }
   void add(const uint16_t* src, int stride, int w, int h, uint16_t* dst) { pics.push_back(RbtGatherPic{src, dst, w, h, stride, 0}); max_chunks = std::max(max_chunks, RBT_GM_PIC_CHUNKS(w, h)); }
-  int launch() {
+  int launch(std::string& err) {
     d = rbtk::dev_alloc(pics.size() * sizeof(RbtGatherPic));
-    if (!d) return RBT_ERR_NOMEM;
-    if (rbtk::h2d(d, pics.data(), pics.size() * sizeof(RbtGatherPic))) return RBT_ERR_NO_DEVICE;
+    if (!d) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    if (rbtk::h2d(d, pics.data(), pics.size() * sizeof(RbtGatherPic))) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
     rbtk::launch_gather_luma((const RbtGatherPic*)d, (int)pics.size(), max_chunks);
     return 0;
   }
+  // the luma of picture k of decoded stream ds, seen through its conformance window (w x h: displayed())
+  void add_decoded(const DecodeBatch& db, int ds, int k, int w, int h, uint16_t* dst) {
+    const int first = db.stream_first[ds]; const RbtStreamCfg& c = db.frames[first].cfg; const Sps& sps = db.stream_sps[ds];
+    add((const uint16_t*)db.frames[first + k].out[0] + (size_t)(2 * sps.conf_win[2]) * c.w + 2 * sps.conf_win[0], c.w, w, h, dst);
+  }
+  // the luma of the reconstructions of stream e of an encode batch - the displayed window starts at the picture's origin - back to back
+  void add_coded(const EncodeBatch& eb, size_t e, int w, int h, uint16_t* dst) {
+    for (int k = 0; k < eb.desc[e].n_frames; k++) { const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k]; add(f.out[0], f.cfg.w, w, h, dst + (size_t)w * h * (size_t)k); }
+  }
 };
 struct DevPlanes { uint16_t* p = nullptr; ~DevPlanes() { rbtk::dev_free(p); } bool alloc(size_t samples) { p = (uint16_t*)rbtk::dev_alloc(samples * 2); return p != nullptr; } };
-// the device time of one cloud's work, between the events of T_CENSUS on the pipeline's stream (no census runs in a job with floors)
-static int d1_timed(GofJob& j, D1Entry& E, int rc) {
-  rbtk::timer_end(T_CENSUS);
-  if (rc) return rc;
-  if (rbtk::dev_sync()) { j.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-  E.cloud_ms += rbtk::timer_ms(T_CENSUS);
-  return 0;
-}
 // In the wait half, once the pipeline's decoder has been collected (the occupancy pipelines were collected before it, gof_wait): per entry with a target and per frame
 // what does not depend on the QP - the maps of the frame from the pooled occupancy plane (MapFrame) and, for a frame without a handle, the reference cloud from the decoded
 // input. On the pipeline's stream; waits are on that stream.
@@ -1015,27 +1015,24 @@ static int d1_setup(GofJob& j, int gi) {
     bool any = false; for (int f = 0; f < nf; f++) any |= E.ref[f] == nullptr;
     if (!any) continue;
     // the decoded input seen through its conformance windows, packed: occupancy luma and geometry luma of the frames without a handle
-    const DecodeBatch& ob = j.db[E.in_pipe]; const int ofirst = ob.stream_first[E.in_ds]; const RbtStreamCfg& oc = ob.frames[ofirst].cfg; const Sps& osps = ob.stream_sps[E.in_ds];
-    const RbtStreamCfg& c = db.frames[first].cfg; const Sps& isps = db.stream_sps[ds];
-    const size_t ys = (size_t)W * H, os = (size_t)E.in_ow * E.in_oh;
+    const size_t ys = (size_t)W * H, os = (size_t)E.in_ow * E.in_oh; const int bd = db.frames[first].cfg.bit_depth;
     DevPlanes geo, occ; GatherSet gs_in;
     if (!geo.alloc(ys * (size_t)mc * nf) || !occ.alloc(os * (size_t)nf)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
     rbtk::timer_begin(T_CENSUS);
     for (int f = 0; f < nf; f++) if (!E.ref[f]) {
-      gs_in.add((const uint16_t*)ob.frames[ofirst + f].out[0] + (size_t)(2 * osps.conf_win[2]) * oc.w + 2 * osps.conf_win[0], oc.w, E.in_ow, E.in_oh, occ.p + os * (size_t)f);
-      for (int m = 0; m < mc; m++) gs_in.add((const uint16_t*)db.frames[first + mc * f + m].out[0] + (size_t)(2 * isps.conf_win[2]) * c.w + 2 * isps.conf_win[0], c.w, W, H, geo.p + ys * (size_t)(mc * f + m));
+      gs_in.add_decoded(j.db[E.in_pipe], E.in_ds, f, E.in_ow, E.in_oh, occ.p + os * (size_t)f);
+      for (int m = 0; m < mc; m++) gs_in.add_decoded(db, ds, mc * f + m, W, H, geo.p + ys * (size_t)(mc * f + m));
     }
-    int rc = gs_in.launch();
-    if (rc) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+    int rc = gs_in.launch(j.err);
     rbt_atlas_params ain = a; ain.occupancy_precision = W / E.in_ow;
     for (int f = 0; f < nf && !rc; f++) if (!E.ref[f]) {
       MapFrame* F = nullptr;
       rc = mapframe_new(j.err, &ain, E.patches[f].data(), (int)E.patches[f].size(), occ.p + os * (size_t)f, &F);
-      if (!rc) rc = mapframe_cloud(j.err, cache, F, geo.p + ys * (size_t)(mc * f), mc > 1 ? geo.p + ys * (size_t)(mc * f + 1) : nullptr, c.bit_depth, &E.own_ref[f], nullptr);
+      if (!rc) rc = mapframe_cloud(j.err, cache, F, geo.p + ys * (size_t)(mc * f), mc > 1 ? geo.p + ys * (size_t)(mc * f + 1) : nullptr, bd, &E.own_ref[f], nullptr);
       if (rbtk::dev_sync() && !rc) { j.err = "kernel execution failed"; rc = RBT_ERR_NO_DEVICE; }      // F's buffers are idle before they go
       mapframe_delete(F);
     }
-    if (int bad = d1_timed(j, E, rc)) return bad;
+    if (int bad = cloud_timed(j, E, rc)) return bad;
   }
   return 0;
 }
@@ -1066,27 +1063,17 @@ static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, s
   if (!geo.alloc(ys * (size_t)d.n_frames)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
   out.assign(np, rbt_d1_result());
   rbtk::timer_begin(T_CENSUS);
-  for (int k = 0; k < d.n_frames; k++) { const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k]; gs.add(f.out[0], f.cfg.w, W, H, geo.p + ys * (size_t)k); }
-  int rc = gs.launch();
-  if (rc) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+  gs.add_coded(eb, e, W, H, geo.p);
+  int rc = gs.launch(j.err);
   for (int i = 0; i < np && !rc; i++) {
     const int f = d.pic.empty() ? i : d.pic[(size_t)(mc * i)] / mc; PCloud* c = nullptr;
     rc = mapframe_cloud(j.err, cache, E.frames[f], geo.p + ys * (size_t)(mc * i), mc > 1 ? geo.p + ys * (size_t)(mc * i + 1) : nullptr, d.bd, &c, nullptr);
     if (!rc) rc = pcloud_d1(j.err, E.ref[f] ? E.ref[f] : E.own_ref[f], c, peak, &out[i]);
     pcloud_release(cache, c);
   }
-  return d1_timed(j, E, rc);
+  return cloud_timed(j, E, rc);
 }
 // ------------------------------------------------------------------------------------------------ colour floors (include/rbt.h, "transcoding attributes to a colour PSNR floor")
-static int displayed(const DecodeBatch& db, int ds, int* w, int* h) {
-  const RbtStreamCfg& c = db.frames[db.stream_first[ds]].cfg; const Sps& sps = db.stream_sps[ds];
-  *w = c.w - 2 * sps.conf_win[0] - 2 * sps.conf_win[1]; *h = c.h - 2 * sps.conf_win[2] - 2 * sps.conf_win[3];
-  return db.stream_count[ds];
-}
-static bool find_entry(const GofJob& j, int entry, int* pipe, size_t* q) {
-  for (int g = 0; g < j.ng; g++) for (size_t k = 0; k < j.groups[g].size(); k++) if (j.groups[g][k] == entry) { *pipe = g; *q = k; return true; }
-  return false;
-}
 // At submit, behind quality_prepare: rules 1 and 2 for every entry of the pipeline with a target - its occupancy source, its geometry source, their shapes -, where the
 // decoded input of the occupancy source lies, and what the clouds will take (rbt_job_memory)
 static int color_prepare(GofJob& j, SubmitPlan& s, int gi) {
@@ -1099,22 +1086,14 @@ static int color_prepare(GofJob& j, SubmitPlan& s, int gi) {
     if (io < 0 || s.occ_src[io].n <= 0) return refuse(i, "a colour target needs an occupancy source: a pooled occupancy entry (occupancy_precision 4) in front of it");
     for (int g = i - 1; g > io && E.geo < 0; g--) if (s.p[g].video_type == RBT_VIDEO_GEOMETRY && s.meas_of[g] == io) E.geo = g;
     if (E.geo < 0) return refuse(i, "a colour target needs a geometry source: a geometry entry in front of it with the same occupancy source");
-    const OccSource& os = s.occ_src[io];
     int dw, dh; const int cnt = displayed(db, ds, &dw, &dh), bd = db.frames[db.stream_first[ds]].cfg.bit_depth;
-    if (dw != a.width || dh != a.height) return refuse(i, "the displayed picture size is not atlas.width x atlas.height");
-    if (cnt != a.map_count * E.t.n_frames) return refuse(i, "the picture count is not atlas.map_count x n_frames");
+    if (const char* why = cloud_fits_stream(E.t, dw, dh, cnt)) return refuse(i, why);
     if (bd != 8 && bd != 10) return refuse(i, "the attribute bit depth is neither 8 nor 10");
     int gp = -1; size_t gq = 0;
     if (!find_entry(j, E.geo, &gp, &gq) || gp == gi || j.db[gp].frames.empty()) return refuse(i, "the geometry source was not decoded in a pipeline of its own");
     int gw, gh; const int gcnt = displayed(j.db[gp], j.dec_of[gp][gq], &gw, &gh);
     if (gw != dw || gh != dh || gcnt != cnt) return refuse(i, "the geometry source's displayed size or picture count is not the attribute entry's");
-    if (os.n != E.t.n_frames) return refuse(i, "the occupancy source does not hold n_frames pictures");
-    if (os.ow * a.occupancy_precision != dw || os.oh * a.occupancy_precision != dh) return refuse(i, "atlas.occupancy_precision is not width / (output occupancy width)");
-    size_t oq = 0;
-    if (!find_entry(j, io, &E.in_pipe, &oq) || j.db[E.in_pipe].frames.empty()) return refuse(i, "the occupancy source was not decoded");
-    E.in_ds = j.dec_of[E.in_pipe][oq];
-    displayed(j.db[E.in_pipe], E.in_ds, &E.in_ow, &E.in_oh);
-    if (E.in_ow <= 0 || E.in_oh <= 0 || dw % E.in_ow || dh % E.in_oh || dw / E.in_ow != dh / E.in_oh) return refuse(i, "the input occupancy size does not divide the atlas by one whole factor");
+    if (const char* why = cloud_fits_occupancy(j, s.occ_src[io], io, E.t, dw, dh, E)) return refuse(i, why);
     // memory: per frame a volume, the frame's buffers and 8 bytes per point of distances - twice where the reference is the job's own, with the packed
     // planes of the decoded input -, the packed geometry planes; per trial the packed attribute planes, their 4:4:4 planes and the two volumes of the transfer
     const size_t ys = (size_t)dw * dh, vol = (size_t)1 << 27;
@@ -1125,13 +1104,6 @@ static int color_prepare(GofJob& j, SubmitPlan& s, int gi) {
     }
     j.rate_bytes += bytes;
   }
-  return 0;
-}
-static int color_timed(GofJob& j, ColorEntry& E, int rc) {
-  rbtk::timer_end(T_CENSUS);
-  if (rc) return rc;
-  if (rbtk::dev_sync()) { j.err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-  E.cloud_ms += rbtk::timer_ms(T_CENSUS);
   return 0;
 }
 // The geometry half, behind the only encode of a geometry entry that is some colour target's geometry source (finish_round; candidate e of the round in flight): the luma
@@ -1147,14 +1119,13 @@ static int color_geometry(GofJob& j, int gi, int q, const EncodeBatch& eb, size_
     if (!E.geo_planes) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
     GatherSet gs;
     rbtk::timer_begin(T_CENSUS);
-    for (int k = 0; k < d.n_frames; k++) { const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k]; gs.add(f.out[0], f.cfg.w, W, H, E.geo_planes + ys * (size_t)k); }
-    int rc = gs.launch();
-    if (rc) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+    gs.add_coded(eb, e, W, H, E.geo_planes);
+    int rc = gs.launch(j.err);
     E.frames.assign(nf, nullptr);
     for (int f = 0; f < nf && !rc; f++)
       rc = colorframe_new(j.err, *j.cloud_cache, &a, E.patches[f].data(), (int)E.patches[f].size(), o.occ + o.in_step * (size_t)f, E.geo_planes + ys * (size_t)(mc * f),
                           mc > 1 ? E.geo_planes + ys * (size_t)(mc * f + 1) : nullptr, d.bd, E.t.attr_transfer, &E.frames[f]);
-    if (int bad = color_timed(j, E, rc)) return bad;
+    if (int bad = cloud_timed(j, E, rc)) return bad;
   }
   return 0;
 }
@@ -1180,8 +1151,7 @@ static int color_setup(GofJob& j, int gi) {
     int rc = 0;
     if (any) {
       int gp = -1; size_t gq = 0; find_entry(j, E.geo, &gp, &gq);
-      const DecodeBatch& ob = j.db[E.in_pipe]; const int ofirst = ob.stream_first[E.in_ds]; const RbtStreamCfg& oc = ob.frames[ofirst].cfg; const Sps& osps = ob.stream_sps[E.in_ds];
-      const DecodeBatch& gb = j.db[gp]; const int gds = j.dec_of[gp][gq], gfirst = gb.stream_first[gds]; const RbtStreamCfg& gc = gb.frames[gfirst].cfg; const Sps& gsps = gb.stream_sps[gds];
+      const DecodeBatch& gb = j.db[gp]; const int gds = j.dec_of[gp][gq]; const RbtStreamCfg& gc = gb.frames[gb.stream_first[gds]].cfg;
       const RbtStreamCfg& c = db.frames[first].cfg; const Sps& isps = db.stream_sps[ds];
       const size_t ys = (size_t)W * H, os = (size_t)E.in_ow * E.in_oh, fs = ys * 3 / 2, n_pic = (size_t)mc * nf;
       // packed: input occupancy luma, input geometry luma (both stay with the frames), input attribute 4:2:0 and its 4:4:4 planes (this block only)
@@ -1190,13 +1160,13 @@ static int color_setup(GofJob& j, int gi) {
       if (!E.in_planes || !attr.alloc(fs * n_pic) || !up.alloc(3 * ys * n_pic)) { j.err = "device allocation failed"; rc = RBT_ERR_NOMEM; }
       uint16_t* occ = E.in_planes; uint16_t* geo = E.in_planes + os * (size_t)nf;
       for (int f = 0; f < nf && !rc; f++) if (!E.ref[f]) {
-        gin.add((const uint16_t*)ob.frames[ofirst + f].out[0] + (size_t)(2 * osps.conf_win[2]) * oc.w + 2 * osps.conf_win[0], oc.w, E.in_ow, E.in_oh, occ + os * (size_t)f);
+        gin.add_decoded(j.db[E.in_pipe], E.in_ds, f, E.in_ow, E.in_oh, occ + os * (size_t)f);
         for (int m = 0; m < mc; m++) {
-          gin.add((const uint16_t*)gb.frames[gfirst + mc * f + m].out[0] + (size_t)(2 * gsps.conf_win[2]) * gc.w + 2 * gsps.conf_win[0], gc.w, W, H, geo + ys * (size_t)(mc * f + m));
+          gin.add_decoded(gb, gds, mc * f + m, W, H, geo + ys * (size_t)(mc * f + m));
           gather_420(gin, db.frames[first + mc * f + m].out, c.w, 2 * isps.conf_win[0], 2 * isps.conf_win[2], W, H, attr.p + fs * (size_t)(mc * f + m));
         }
       }
-      if (!rc && (rc = gin.launch()) != 0) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+      if (!rc) rc = gin.launch(j.err);
       if (!rc) colorframe_upconvert(attr.p, W, H, c.bit_depth, (int)n_pic, E.t.upsample_filter, up.p);      // (pictures of frames with a handle: never gathered, never read)
       rbt_atlas_params ain = a; ain.occupancy_precision = W / E.in_ow;
       for (int f = 0; f < nf && !rc; f++) if (!E.ref[f]) {
@@ -1211,7 +1181,7 @@ static int color_setup(GofJob& j, int gi) {
       if (pcloud_merged(A) > (1 << 21) || pcloud_merged(colorframe_cloud(E.frames[f])) > (1 << 21)) { j.err = merged_limit; rc = RBT_ERR_PARAM; }
       else rc = colorframe_pair(j.err, E.frames[f], A);
     }
-    if (int bad = color_timed(j, E, rc)) return bad;
+    if (int bad = cloud_timed(j, E, rc)) return bad;
   }
   return 0;
 }
@@ -1237,14 +1207,13 @@ static int color_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e
   out.assign(nf, rbt_color_result());
   rbtk::timer_begin(T_CENSUS);
   for (int k = 0; k < d.n_frames; k++) { const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k]; gather_420(gs, f.out, f.cfg.w, 0, 0, W, H, attr.p + fs * (size_t)k); }
-  int rc = gs.launch();
-  if (rc) j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed";
+  int rc = gs.launch(j.err);
   if (!rc) colorframe_upconvert(attr.p, W, H, d.bd, d.n_frames, E.t.upsample_filter, up.p);
   for (int f = 0; f < nf && !rc; f++) {
     rc = colorframe_color(j.err, E.frames[f], up.p + 3 * ys * (size_t)(mc * f), mc > 1 ? up.p + 3 * ys * (size_t)(mc * f + 1) : nullptr, d.bd);
     if (!rc) rc = colorframe_score(j.err, E.frames[f], &out[f]);
   }
-  return color_timed(j, E, rc);
+  return cloud_timed(j, E, rc);
 }
 static int finish_round(GofJob& j, int gi) {
   RoundPipe& r = j.pipes[gi]; std::vector<std::vector<uint8_t>> outs;
@@ -1307,6 +1276,22 @@ static void quality_fill_result(rbt_quality_result& o, int qp, int q0, int qs, i
     o.psnr[c] = quality_psnr(s.sse[c], s.samples[c], bit_depth); o.psnr_occ[c] = quality_psnr(s.sse_occ[c], s.samples_occ[c], bit_depth);
   }
 }
+// Cloud targets: of every entry of the pipeline with a target the frames at the entry's own QP (own[q], the entry's only encode) or, where a walk of `kind` ran for a
+// floor, at its q*
+template <class Entry, class Result> static void fill_cloud_outs(GofJob& j, int gi, const std::vector<Entry>& in, std::vector<FloorOut<Result>>& out, WalkKind kind, const std::vector<std::vector<Result>>& own,
+                                                                  std::vector<Result> TargetTried::*tried) {
+  RoundPipe& r = j.pipes[gi]; const std::vector<int>& gs = j.groups[gi];
+  if (in.empty()) return;
+  out.resize(j.n);
+  for (size_t q = 0; q < gs.size(); q++) if (in[gs[q]].t.n_frames > 0) {
+    FloorOut<Result>& o = out[gs[q]]; const int qp = j.params[gs[q]].qp;
+    o.qp = o.q0 = o.qs = qp; o.met = 1; o.n_enc = 1; o.bytes = r.o1[q].size(); o.frames = own[q]; o.cloud_ms = in[gs[q]].cloud_ms;
+  }
+  for (size_t k = 0; k < r.walks.size(); k++) if (r.walks[k].kind == kind) {
+    const TargetWalk& w = r.walks[k]; const TargetTried& t = w.tried.find(w.qstar)->second; FloorOut<Result>& o = out[w.entry];
+    o.qp = w.qstar; o.q0 = w.floor.q0; o.qs = w.start; o.met = w.met; o.n_enc = r.n_enc[k]; o.bytes = t.stream.size(); o.frames = t.*tried;
+  }
+}
 // the public results of a pipeline whose walks have settled: a budget's (qe = the walk's start), or a floor's and the distortion of the entries without one
 static void fill_results(GofJob& j, int gi) {
   RoundPipe& r = j.pipes[gi]; const std::vector<int>& gs = j.groups[gi];
@@ -1314,31 +1299,11 @@ static void fill_results(GofJob& j, int gi) {
   for (size_t q = 0; q < gs.size() && !j.qtargets.empty(); q++) if (!has_floor(j, gs[q])) { const int qp = j.params[gs[q]].qp; quality_fill_result(j.qresults[gs[q]], qp, qp, qp, 1, 1, r.o1[q].size(), r.sums[q], entry_bit_depth(j, gi, q)); }
   for (size_t k = 0; k < r.walks.size(); k++) {
     const TargetWalk& w = r.walks[k]; const QualityTried& t = w.tried.find(w.qstar)->second;
-    if (w.toward < 0) j.results[w.entry] = rbt_rate_result{w.qstar, w.start, w.met, r.n_enc[k], (uint64_t)t.stream.size(), w.budget.e_qe};
-    else if (!w.is_d1 && !w.is_color) quality_fill_result(j.qresults[w.entry], w.qstar, w.floor.q0, w.start, w.met, r.n_enc[k], t.stream.size(), t.sums, w.floor.bit_depth);
+    if (w.kind == WALK_BUDGET) j.results[w.entry] = rbt_rate_result{w.qstar, w.start, w.met, r.n_enc[k], (uint64_t)t.stream.size(), w.budget.e_qe};
+    else if (w.kind == WALK_PSNR) quality_fill_result(j.qresults[w.entry], w.qstar, w.floor.q0, w.start, w.met, r.n_enc[k], t.stream.size(), t.sums, w.bit_depth);
   }
-  // D1 floors: the frames at q*, or at the entry's own QP
-  if (!j.d1.empty()) j.d1out.resize(j.n);
-  for (size_t q = 0; q < gs.size() && !j.d1.empty(); q++) if (has_d1(j, gs[q]) && !has_d1_floor(j, gs[q])) {
-    D1Out& o = j.d1out[gs[q]]; const int qp = j.params[gs[q]].qp;
-    o.qp = o.q0 = o.qs = qp; o.met = 1; o.n_enc = 1; o.bytes = r.o1[q].size(); o.frames = r.d1[q];
-  }
-  for (size_t k = 0; k < r.walks.size(); k++) if (r.walks[k].is_d1) {
-    const TargetWalk& w = r.walks[k]; const TargetTried& t = w.tried.find(w.qstar)->second; D1Out& o = j.d1out[w.entry];
-    o.qp = w.qstar; o.q0 = w.dist.q0; o.qs = w.start; o.met = w.met; o.n_enc = r.n_enc[k]; o.bytes = t.stream.size(); o.frames = t.d1;
-  }
-  for (size_t q = 0; q < gs.size() && !j.d1.empty(); q++) if (has_d1(j, gs[q])) j.d1out[gs[q]].cloud_ms = j.d1[gs[q]].cloud_ms;
-  // colour floors: the same
-  if (!j.color.empty()) j.colorout.resize(j.n);
-  for (size_t q = 0; q < gs.size() && !j.color.empty(); q++) if (has_color(j, gs[q]) && !has_color_floor(j, gs[q])) {
-    ColorOut& o = j.colorout[gs[q]]; const int qp = j.params[gs[q]].qp;
-    o.qp = o.q0 = o.qs = qp; o.met = 1; o.n_enc = 1; o.bytes = r.o1[q].size(); o.frames = r.color[q];
-  }
-  for (size_t k = 0; k < r.walks.size(); k++) if (r.walks[k].is_color) {
-    const TargetWalk& w = r.walks[k]; const TargetTried& t = w.tried.find(w.qstar)->second; ColorOut& o = j.colorout[w.entry];
-    o.qp = w.qstar; o.q0 = w.col.q0; o.qs = w.start; o.met = w.met; o.n_enc = r.n_enc[k]; o.bytes = t.stream.size(); o.frames = t.color;
-  }
-  for (size_t q = 0; q < gs.size() && !j.color.empty(); q++) if (has_color(j, gs[q])) j.colorout[gs[q]].cloud_ms = j.color[gs[q]].cloud_ms;
+  fill_cloud_outs(j, gi, j.d1, j.d1out, WALK_D1, r.d1, &TargetTried::d1);
+  fill_cloud_outs(j, gi, j.color, j.colorout, WALK_COLOR, r.color, &TargetTried::color);
 }
 // ... and of a pipeline whose entries walked frame by frame: per frame q*, qs, met, its encodes, its bytes and its figure at q*; the stream assembled from the passes
 static void fill_frame_results(GofJob& j, int gi) {
@@ -1351,9 +1316,10 @@ static void fill_frame_results(GofJob& j, int gi) {
     if (has_d1(j, fw.entry)) o.cloud_ms = j.d1[fw.entry].cloud_ms;
     for (size_t f = 0; f < fw.frames.size(); f++) {
       const TargetWalk& w = fw.frames[f]; const TargetTried& at = w.tried.find(w.qstar)->second; const QualitySums& s = at.sums;
-      o.q0 = w.is_d1 ? w.dist.q0 : w.floor.q0; o.bit_depth = w.floor.bit_depth; o.pictures += 2 * (uint64_t)fw.n_enc[f];
-      if (w.is_d1) o.d1.push_back(at.d1[0]);
-      o.frames.push_back(rbt_frame_pick{w.qstar, w.start, w.met, fw.n_enc[f], bytes[f], w.is_d1 ? (double)at.d1[0].psnr : quality_region_psnr(s, w.floor.region, w.floor.bit_depth)});
+      const bool d1 = w.kind == WALK_D1;
+      o.q0 = w.floor.q0; o.bit_depth = w.bit_depth; o.pictures += 2 * (uint64_t)fw.n_enc[f];
+      if (d1) o.d1.push_back(at.d1[0]);
+      o.frames.push_back(rbt_frame_pick{w.qstar, w.start, w.met, fw.n_enc[f], bytes[f], d1 ? (double)at.d1[0].psnr : quality_region_psnr(s, w.region, w.bit_depth)});
       for (int c = 0; c < 3; c++) { o.sums.sse[c] += s.sse[c]; o.sums.samples[c] += s.samples[c]; o.sums.sse_occ[c] += s.sse_occ[c]; o.sums.samples_occ[c] += s.samples_occ[c]; }
     }
   }
@@ -1367,11 +1333,13 @@ static int run_rounds(GofJob& j, int gi) {
   if (int rc = pipeline_decoded(j, gi)) return rc;
   D1Live d1_live{j, gi};                                            // (releases the pipeline's frames and reference clouds on every way out)
   ColorLive color_live{j, gi};                                      // (releases the frames of the pipeline's colour entries on every way out)
-  if (!j.d1.empty()) { if (j.per_frame) seed_frame_floors(j, gi, r); else seed_d1_floors(j, gi, r); if (int rc = d1_setup(j, gi)) return rc; }
-  else if (!j.color.empty()) { seed_color_floors(j, gi, r); if (int rc = color_setup(j, gi)) return rc; }
-  else if (j.per_frame && j.d1.empty()) seed_frame_floors(j, gi, r);
-  else if (!j.qtargets.empty()) seed_floors(j, gi, r);
+  if (j.per_frame) seed_frame_floors(j, gi, r);
+  else if (j.kind == GOF_D1) seed_floors(j, gi, r, WALK_D1);
+  else if (j.kind == GOF_COLOR) seed_floors(j, gi, r, WALK_COLOR);
+  else if (j.kind == GOF_QUALITY) seed_floors(j, gi, r, WALK_PSNR);
   else if (int rc = seed_budgets(j, gi, r, true)) return rc;
+  if (!j.d1.empty()) if (int rc = d1_setup(j, gi)) return rc;
+  if (!j.color.empty()) if (int rc = color_setup(j, gi)) return rc;
   r.o1.assign(n, {}); r.sums.assign(n, QualitySums()); r.d1.assign(n, {}); r.color.assign(n, {}); r.n_enc.assign(r.walks.size(), 0);
   name_round(j, gi, r, true);
   for (;;) {
@@ -1412,14 +1380,13 @@ static int quality_prepare(GofJob& j, SubmitPlan& s, int gi) {
   DecodeBatch& db = j.db[gi]; const std::vector<int>& gs = j.groups[gi];
   if (db.frames.empty()) return 0;
   for (size_t q = 0; q < gs.size(); q++) {
-    const int i = gs[q], io = s.meas_of[i], ds = j.dec_of[gi][q], first = db.stream_first[ds], cnt = db.stream_count[ds];
+    const int i = gs[q], io = s.meas_of[i], ds = j.dec_of[gi][q], cnt = db.stream_count[ds];
     bool has = false;
     if (j.per_frame && cnt % 2) {      // a frame is two pictures: a stream that ends with half a frame has no walk for it
       j.err = "entry " + std::to_string(i) + ": floors held frame by frame need two pictures per point-cloud frame, the stream holds " + std::to_string(cnt);
       j.refused = true; return RBT_ERR_PARAM; }
     if (io >= 0 && s.occ_src[io].n > 0 && cnt > 0) {
-      const OccSource& os = s.occ_src[io]; const RbtStreamCfg& c = db.frames[first].cfg; const Sps& isps = db.stream_sps[ds];
-      const int dw = c.w - 2 * isps.conf_win[0] - 2 * isps.conf_win[1], dh = c.h - 2 * isps.conf_win[2] - 2 * isps.conf_win[3];
+      const OccSource& os = s.occ_src[io]; int dw, dh; displayed(db, ds, &dw, &dh);
       if (dw > 0 && dh > 0 && cnt % os.n == 0 && dw % os.ow == 0 && dh % os.oh == 0 && dw / os.ow == dh / os.oh) {
         has = true; QualityOcc& o = j.qocc[i]; o.occ = os.occ; o.in_step = os.in_step; o.n = os.n; o.ow = os.ow; o.oh = os.oh;
         if (s.occ_of[i] >= 0) {
@@ -1575,38 +1542,33 @@ static int enqueue_pipeline(GofJob& j, SubmitPlan& s, int gi) {
   return 0;
 }
 
+// A job with cloud targets runs as a job with quality floors that are all 0; the targets are kept with their patch lists copied (the caller's arrays may go when submit returns)
+template <class Entry, class Target> static void keep_cloud_targets(GofJob& j, std::vector<Entry>& to, const CloudRequest<Target>& req) {
+  j.qtargets.assign(j.n, rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, RBT_QUALITY_ALL, 0, 0}); j.qocc.assign(j.n, QualityOcc());
+  to.resize(j.n); j.cloud_cache = req.cache;
+  for (int i = 0; i < j.n; i++) {
+    Entry& E = to[i]; E.t = req.targets[i]; E.ref = req.refs[i];
+    for (int f = 0; f < E.t.n_frames; f++) E.patches.emplace_back(E.t.patches[f], E.t.patches[f] + E.t.n_patches[f]);
+    E.t.patches = nullptr; E.t.n_patches = nullptr; E.t.reference = nullptr;
+  }
+}
 // Phase A of a job: plan, build and upload everything, then enqueue. Every upload of the job is issued before its first kernel: a copy from pageable memory blocks the host
 // until the stream has reached it, and pipelines may share a stream. The first failure ends the submission (j.rc, j.err); gof_wait drains what was enqueued.
-GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets, const rbt_quality_target* quality,
-                   const D1Request* d1, const ColorRequest* color, const std::vector<std::vector<int8_t>>* frame_qp, bool per_frame, const std::vector<QpMapIn>* qp_maps) {
+GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   GofJob* J = new GofJob(); GofJob& j = *J;
-  j.per_frame = per_frame && (quality || d1);
+  const int n = r.n; const rbt_stream_params* p = r.params;
+  j.per_frame = r.per_frame && (r.quality || r.d1);
+  j.kind = r.color ? GOF_COLOR : r.d1 ? (j.per_frame ? GOF_D1_FRAMES : GOF_D1) : r.quality ? (j.per_frame ? GOF_QUALITY_FRAMES : GOF_QUALITY) : GOF_PLAIN;
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
-  j.params.assign(p, p + n); j.n_in.assign(n_in, n_in + n);
-  if (targets) j.targets.assign(targets, targets + n);
-  if (frame_qp) j.frame_qp = *frame_qp;
-  if (qp_maps) j.qp_maps = *qp_maps;
-  if (quality) { j.qtargets.assign(quality, quality + n); j.qocc.assign(n, QualityOcc()); }
-  if (d1) {      // a job with quality floors of 0, and the D1 targets with their patch lists copied
-    j.qtargets.assign(n, rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, RBT_QUALITY_ALL, 0, 0}); j.qocc.assign(n, QualityOcc());
-    j.d1.resize(n); j.cloud_cache = d1->cache;
-    for (int i = 0; i < n; i++) {
-      D1Entry& E = j.d1[i]; E.t = d1->targets[i]; E.ref = d1->refs[i];
-      for (int f = 0; f < E.t.n_frames; f++) E.patches.emplace_back(E.t.patches[f], E.t.patches[f] + E.t.n_patches[f]);
-      E.t.patches = nullptr; E.t.n_patches = nullptr; E.t.reference = nullptr;      // (the caller's arrays may go when submit returns)
-    }
-  }
-  if (color) {   // the same kind of job with the colour targets
-    j.qtargets.assign(n, rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, RBT_QUALITY_ALL, 0, 0}); j.qocc.assign(n, QualityOcc());
-    j.color.resize(n); j.cloud_cache = color->cache;
-    for (int i = 0; i < n; i++) {
-      ColorEntry& E = j.color[i]; E.t = color->targets[i]; E.ref = color->refs[i];
-      for (int f = 0; f < E.t.n_frames; f++) E.patches.emplace_back(E.t.patches[f], E.t.patches[f] + E.t.n_patches[f]);
-      E.t.patches = nullptr; E.t.n_patches = nullptr; E.t.reference = nullptr;
-    }
-  }
-  SubmitPlan s; s.in = in; s.p = p; s.gof_rule = gof_rule;
+  j.params.assign(p, p + n); j.n_in.assign(r.n_in, r.n_in + n);
+  if (r.targets) j.targets.assign(r.targets, r.targets + n);
+  if (r.frame_qp) j.frame_qp = *r.frame_qp;
+  if (r.qp_maps) j.qp_maps = *r.qp_maps;
+  if (r.quality) { j.qtargets.assign(r.quality, r.quality + n); j.qocc.assign(n, QualityOcc()); }
+  if (r.d1) keep_cloud_targets(j, j.d1, *r.d1);
+  if (r.color) keep_cloud_targets(j, j.color, *r.color);
+  SubmitPlan s; s.in = r.in; s.p = p; s.gof_rule = r.gof_rule;
   int rc = plan_pipelines(j, s, depth);
   j.t_gpu = now_ms();
   if (!rc) rc = build_decoders(j, s);
@@ -1620,10 +1582,29 @@ GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const s
   return J;
 }
 
+// The public results of a job with cloud targets: per entry its own QP and one encode, or what the rounds left of an entry with a target (FloorOut) with the statistics
+// over its frames; on a failure - rc, or an allocation here - nothing is handed out
+template <class Entry, class Result, class Public, class Stats> static int cloud_results(const GofJob& j, int rc, const std::vector<Entry>& in, const std::vector<FloorOut<Result>>& outs, Public* res,
+                                                                                        uint8_t** out, size_t* n_out, Stats stats) {
+  for (int i = 0; i < j.n && !rc; i++) {
+    Public& o = res[i]; memset(&o, 0, sizeof(o));
+    o.qp = o.qp_probe = o.qp_start = j.params[i].qp; o.met = 1; o.n_encodes = j.is_pass[i] ? 0 : 1; o.bytes = (uint64_t)n_out[i];
+    if (in.empty() || in[i].t.n_frames <= 0 || i >= (int)outs.size()) continue;
+    const FloorOut<Result>& r = outs[i];
+    o.qp = r.qp; o.qp_probe = r.q0; o.qp_start = r.qs; o.met = r.met; o.n_encodes = r.n_enc; o.bytes = r.bytes; o.cloud_ms = r.cloud_ms; o.n_frames = (int)r.frames.size();
+    stats(o, r.frames.data());
+    o.frames = (Result*)malloc(sizeof(Result) * r.frames.size());
+    if (!o.frames) { rc = RBT_ERR_NOMEM; break; }
+    memcpy(o.frames, r.frames.data(), sizeof(Result) * r.frames.size());
+  }
+  if (rc) for (int i = 0; i < j.n; i++) { free(res[i].frames); memset(&res[i], 0, sizeof(res[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; }
+  return rc;
+}
 // phase B, shortest pipeline first: one sync per stream, then slice sizes -> pack -> NAL assembly. Consumes the job.
-int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, size_t* n_out, rbt_rate_result* results, rbt_quality_result* qresults, int* n_flat, rbt_d1_floor_result* d1results,
-             rbt_color_floor_result* cresults, rbt_frame_floor_result* fresults) {
+int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResults& res) {
   std::unique_ptr<GofJob> guard(J); GofJob& j = *J;
+  uint8_t** out = res.out; size_t* n_out = res.n_out; int* n_flat = res.n_flat;
+  rbt_rate_result* results = res.rate; rbt_quality_result* qresults = res.quality; rbt_d1_floor_result* d1results = res.d1; rbt_color_floor_result* cresults = res.color; rbt_frame_floor_result* fresults = res.frames;
   const int n = j.n, ng = j.ng; int rc = j.rc;
   rbt_stats& st = j.st; std::string& err = j.err;
   std::vector<DecodeBatch>& db = j.db; std::vector<EncodeBatch>& eb = j.eb; const rbt_stream_params* p = j.params.data();
@@ -1683,30 +1664,8 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, uint8_t** out, 
     }
   }
   if (fresults && rc) { for (int i = 0; i < n; i++) { free(fresults[i].frames); free(fresults[i].d1); memset(&fresults[i], 0, sizeof(fresults[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; } }
-  if (d1results && !rc) for (int i = 0; i < n; i++) {
-    rbt_d1_floor_result& o = d1results[i]; memset(&o, 0, sizeof(o));
-    o.qp = o.qp_probe = o.qp_start = p[i].qp; o.met = 1; o.n_encodes = j.is_pass[i] ? 0 : 1; o.bytes = (uint64_t)n_out[i];
-    if (!has_d1(j, i) || i >= (int)j.d1out.size()) continue;
-    const D1Out& r = j.d1out[i];
-    o.qp = r.qp; o.qp_probe = r.q0; o.qp_start = r.qs; o.met = r.met; o.n_encodes = r.n_enc; o.bytes = r.bytes; o.cloud_ms = r.cloud_ms; o.n_frames = (int)r.frames.size();
-    d1_stats(r.frames.data(), o.n_frames, &o.mean_d1, &o.min_d1);
-    o.frames = (rbt_d1_result*)malloc(sizeof(rbt_d1_result) * r.frames.size());
-    if (!o.frames) { rc = RBT_ERR_NOMEM; break; }
-    memcpy(o.frames, r.frames.data(), sizeof(rbt_d1_result) * r.frames.size());
-  }
-  if (cresults && !rc) for (int i = 0; i < n; i++) {
-    rbt_color_floor_result& o = cresults[i]; memset(&o, 0, sizeof(o));
-    o.qp = o.qp_probe = o.qp_start = p[i].qp; o.met = 1; o.n_encodes = j.is_pass[i] ? 0 : 1; o.bytes = (uint64_t)n_out[i];
-    if (!has_color(j, i) || i >= (int)j.colorout.size()) continue;
-    const ColorOut& r = j.colorout[i];
-    o.qp = r.qp; o.qp_probe = r.q0; o.qp_start = r.qs; o.met = r.met; o.n_encodes = r.n_enc; o.bytes = r.bytes; o.cloud_ms = r.cloud_ms; o.n_frames = (int)r.frames.size();
-    color_stats(r.frames.data(), o.n_frames, o.mean_psnr, o.min_psnr);
-    o.frames = (rbt_color_result*)malloc(sizeof(rbt_color_result) * r.frames.size());
-    if (!o.frames) { rc = RBT_ERR_NOMEM; break; }
-    memcpy(o.frames, r.frames.data(), sizeof(rbt_color_result) * r.frames.size());
-  }
-  if (cresults && rc) { for (int i = 0; i < n; i++) { free(cresults[i].frames); memset(&cresults[i], 0, sizeof(cresults[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; } }
-  if (d1results && rc) { for (int i = 0; i < n; i++) { free(d1results[i].frames); memset(&d1results[i], 0, sizeof(d1results[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; } }
+  if (d1results) rc = cloud_results(j, rc, j.d1, j.d1out, d1results, out, n_out, [](rbt_d1_floor_result& o, const rbt_d1_result* f) { d1_stats(f, o.n_frames, &o.mean_d1, &o.min_d1); });
+  if (cresults) rc = cloud_results(j, rc, j.color, j.colorout, cresults, out, n_out, [](rbt_color_floor_result& o, const rbt_color_result* f) { color_stats(f, o.n_frames, o.mean_psnr, o.min_psnr); });
   // SURVEY.md 8(d) algorithmic traffic: per coded picture of S samples (2 bytes each): decode writes S, P pictures read
   // their reference once; encode reads the source S, writes the reconstruction S (I) and reads the reference (P)
   uint64_t bytes = 0;
@@ -1725,9 +1684,6 @@ void gof_abandon(GofJob* J) {   // a job nobody will wait for: drain its streams
   for (int g = 0; g < J->ng; g++) { rbtk::set_stream(job_stream(*J, g)); rbtk::dev_sync(); }
   rbtk::set_stream(job_stream(*J, rbtk::RBT_AUX_STREAM)); rbtk::dev_sync(); rbtk::set_stream(0);
   delete J;
-}
-int transcode_gof(rbt_stats& st, std::string& err, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, uint8_t** out, size_t* n_out) {
-  return gof_wait(gof_submit(0, 1, n, in, n_in, p, true, nullptr), st, err, out, n_out, nullptr);
 }
 
 int encode_yuv(rbt_stats& st, std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int qp, int gop, int lossless, int log2_ctb, int rows, int md5,

@@ -4,32 +4,38 @@
 #include <vector>
 #include "../../include/rbt.h"
 namespace rbt {
-int transcode_gof(rbt_stats& st, std::string& err, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, uint8_t** out, size_t* n_out);
 struct GofJob;
-// gof_rule: apply transcodeData's rule (PCCTranscoder.cpp:150): an occupancy stream is only transcoded when occupancyPrecision == 4
-// targets: nullptr, or one per entry (checked by the caller: rbt_submit_gof_rate); results: nullptr, or one per entry
-// quality: nullptr, or one floor per entry (rbt_submit_gof_quality; not together with targets); quality_results: nullptr, or one per entry of such a job
-// d1: nullptr, or the D1 targets of rbt_submit_gof_d1 (checked by the caller; not together with targets or quality): one per entry, the reference handles of each entry
-// resolved to the clouds (n_frames of them, nullptr = the cloud of the decoded input), and the context's cache of cloud volumes
 struct PCloud; struct PCloudCache;
-struct D1Request { const rbt_d1_target* targets; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache; };
-// color: nullptr, or the colour targets of rbt_submit_gof_color (checked by the caller; not together with targets, quality or d1), resolved the same way
-struct ColorRequest { const rbt_color_target* targets; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache; };
-// frame_qp: nullptr, or per entry a QP per point-cloud frame (rbt_submit_gof_frame_qp; values and video types checked by the caller, the count against the stream's pictures
-// here: gof_refused), empty = the entry's own QP; not together with targets, quality, d1 or color
-// qp_maps: nullptr, or per entry a QP per CTB (rbt_submit_gof_qp_map; struct sizes, values and video types checked by the caller, the counts against the stream's pictures here:
-// gof_refused), an empty qp = the entry's own QP; not together with anything but p
+// the cloud targets of rbt_submit_gof_d1 / rbt_submit_gof_color (Target: rbt_d1_target / rbt_color_target), checked by the caller: one per entry, the reference handles of each
+// entry resolved to the clouds (n_frames of them, nullptr = the cloud of the decoded input), and the context's cache of cloud volumes
+template <class Target> struct CloudRequest { const Target* targets = nullptr; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache = nullptr; };
 struct QpMapIn { std::vector<int8_t> qp; int n_frames = 0, w_ctb = 0, h_ctb = 0; };
-GofJob* gof_submit(int slot, int depth, int n, const uint8_t* const* in, const size_t* n_in, const rbt_stream_params* p, bool gof_rule, const rbt_rate_target* targets = nullptr, const rbt_quality_target* quality = nullptr,
-                   const D1Request* d1 = nullptr, const ColorRequest* color = nullptr, const std::vector<std::vector<int8_t>>* frame_qp = nullptr, bool per_frame = false,   // per_frame: with quality, rbt_submit_gof_quality_frames
-                   const std::vector<QpMapIn>* qp_maps = nullptr);
-int gof_wait(GofJob* j, rbt_stats& st, std::string& err, uint8_t** out, size_t* n_out, rbt_rate_result* results = nullptr, rbt_quality_result* quality_results = nullptr, int* n_flat = nullptr,
-             rbt_d1_floor_result* d1_results = nullptr, rbt_color_floor_result* color_results = nullptr, rbt_frame_floor_result* frame_results = nullptr);   // consumes the job
-bool gof_is_quality(const GofJob* j);           // a job of rbt_submit_gof_quality
-bool gof_is_quality_frames(const GofJob* j);    // a job of rbt_submit_gof_quality_frames
-bool gof_is_d1_frames(const GofJob* j);         // a job of rbt_submit_gof_d1_frames
-bool gof_is_d1(const GofJob* j);                // a job of rbt_submit_gof_d1
-bool gof_is_color(const GofJob* j);             // a job of rbt_submit_gof_color
+// What a job is made of: the n inputs with their parameters, and at most one kind of target - each nullptr or one per entry, checked by the caller
+struct GofRequest {
+  int n = 0; const uint8_t* const* in = nullptr; const size_t* n_in = nullptr; const rbt_stream_params* params = nullptr;
+  bool gof_rule = true;                               // transcodeData's rule (PCCTranscoder.cpp:150): an occupancy stream is only transcoded when occupancyPrecision == 4
+  const rbt_rate_target* targets = nullptr;           // byte budgets (rbt_submit_gof_rate)
+  const rbt_quality_target* quality = nullptr;        // PSNR floors (rbt_submit_gof_quality; with per_frame: rbt_submit_gof_quality_frames)
+  const CloudRequest<rbt_d1_target>* d1 = nullptr;    // D1 floors (rbt_submit_gof_d1; with per_frame: rbt_submit_gof_d1_frames)
+  const CloudRequest<rbt_color_target>* color = nullptr;   // colour floors (rbt_submit_gof_color)
+  bool per_frame = false;                             // the floors of quality / d1 are held frame by frame
+  // a QP per point-cloud frame (rbt_submit_gof_frame_qp; values and video types checked by the caller, the count against the stream's pictures here: gof_refused), an empty
+  // list = the entry's own QP; not together with a target
+  const std::vector<std::vector<int8_t>>* frame_qp = nullptr;
+  // a QP per CTB (rbt_submit_gof_qp_map; struct sizes, values and video types checked by the caller, the counts against the stream's pictures here: gof_refused), an empty qp =
+  // the entry's own QP; not together with anything else
+  const std::vector<QpMapIn>* qp_maps = nullptr;
+};
+// Where a job's outcome goes: a stream per entry, and of the result arrays - one per entry each - the one of the job's kind; n_flat: nullptr, or the decoded pictures with flat chroma
+struct GofResults {
+  uint8_t** out = nullptr; size_t* n_out = nullptr; int* n_flat = nullptr;
+  rbt_rate_result* rate = nullptr; rbt_quality_result* quality = nullptr; rbt_d1_floor_result* d1 = nullptr; rbt_color_floor_result* color = nullptr; rbt_frame_floor_result* frames = nullptr;
+};
+GofJob* gof_submit(int slot, int depth, const GofRequest& r);
+int gof_wait(GofJob* j, rbt_stats& st, std::string& err, const GofResults& r);   // consumes the job
+// which submit made the job, in the order the wait half tells a mismatch (rbt_api.cpp wait): the lower of two kinds that differ is the one the message names
+enum GofKind { GOF_PLAIN, GOF_QUALITY, GOF_D1, GOF_COLOR, GOF_D1_FRAMES, GOF_QUALITY_FRAMES };   // GOF_PLAIN: constant QPs, QP lists, QP maps and byte budgets
+GofKind gof_kind(const GofJob* j);
 int gof_refused(const GofJob* j, std::string& err);   // != 0: the job's plan was refused before anything was built or enqueued (the code; the reason in err)
 void gof_abandon(GofJob* j);
 size_t gof_memory(const GofJob* j);             // device memory the job's build took (its arenas)

@@ -1,5 +1,5 @@
 // TEST-ONLY: the bodies of the recolouring route - the recolour of an index and the colour walks on stored distances (csrc/rbt_score.h), the gather on the three planes of
-// 4:2:0 pictures (csrc/rbt_cloudmaps.h) - and the host half of a colour floor (host/rbt_color_walk.h, host/rbt_qp_walk.h) as a stand-alone host program, so that they can be
+// 4:2:0 pictures (csrc/rbt_cloudmaps.h) - and the host half of a colour floor (host/rbt_color_walk.h, host/rbt_floor_walk.h, host/rbt_qp_walk.h) as a stand-alone host program, so that they can be
 // built with -fsanitize=address,undefined and run on the CPU (tests/test_color_floor.py). Points, colours, maps and distances are heap blocks that end with the last point /
 // slot, the coded pictures blocks that end with the last sample a window reads, so a step past an end is caught. A recoloured index is held against the index of the same
 // points built with the new colours, word for word; the colour walks against launch_sc_score's sums. Prints "ok".
@@ -12,11 +12,12 @@
 #include "../rabbit-transcoding_amd/csrc/rbt_score.h"
 #include "../rabbit-transcoding_amd/csrc/rbt_cloudmaps.h"
 #include "../rabbit-transcoding_amd/host/rbt_color_walk.h"
+#include "../rabbit-transcoding_amd/host/rbt_floor_walk.h"
 
 static int fail(const char* what, long a = 0, long b = 0, long c = 0) { printf("FAIL %s %ld %ld %ld\n", what, a, b, c); fflush(stdout); return 1; }
 static uint32_t g_seed = 2468;
 static uint32_t rnd() { g_seed = g_seed * 1664525u + 1013904223u; return g_seed >> 8; }
-template <class T> static T* block(size_t n) { T* p = (T*)malloc(n * sizeof(T) ? n * sizeof(T) : 1); if (!p) { printf("FAIL malloc\n"); exit(1); } return p; }
+template <class T> static T* block(size_t n) { T* p = (T*)malloc(n ? n * sizeof(T) : 1); if (!p) { printf("FAIL malloc\n"); exit(1); } return p; }
 
 // an indexed cloud on heap blocks of exactly its sizes
 struct Cloud {
@@ -109,7 +110,9 @@ static std::vector<rbt_color_result> frames_of(double db, double gap, int channe
 }
 struct Tried { std::vector<rbt_color_result> color; };
 static int walk_case(const std::vector<std::vector<rbt_color_result>>& t, int qp, int32_t floor_mdb, int stat, int ch, int lo, int hi) {
-  rbt::QpWalk<Tried> w; rbt::ColorGoal g; g.floor_mdb = floor_mdb; g.stat = stat; g.channel = ch; w.lo = lo; w.hi = hi; rbt::color_seed(w, g, qp);
+  rbt::QpWalk<Tried> w; rbt::FloorGoal g; g.floor_mdb = floor_mdb; w.lo = lo; w.hi = hi; rbt::floor_seed(w, g, qp);
+  auto figure_of = [&](const Tried& x) { return rbt::color_figure(x.color, stat, ch); };
+  auto trial_meets = [&](const Tried& x) { return rbt::color_meets(x.color, stat, ch, floor_mdb); };
   const int q0 = qp < lo ? lo : qp > hi ? hi : qp;
   if (g.q0 != q0 || w.toward != 1) return fail("seed", qp, g.q0, q0);
   auto D = [&](int q) { const double a = (double)t[q][0].psnr[ch], b = (double)t[q][1].psnr[ch]; return stat == RBT_D1_MEAN ? (a + b) / 2 : (a < b ? a : b); };
@@ -118,8 +121,8 @@ static int walk_case(const std::vector<std::vector<rbt_color_result>>& t, int qp
   int qs = std::isinf(D(q0)) ? q0 : q0 + (int)(D(q0) - floor_mdb / 1000.0); qs = qs < lo ? lo : qs > hi ? hi : qs;
   int n_enc = 0, need = 0, dir = 0, round = 0; std::vector<int> qps, rule;
   for (;; round++) {
-    const bool probe = !rbt::color_probe(w, g);
-    if (probe) { need = g.q0; dir = 0; } else if (rbt::qp_walk_step(w, rbt::color_holds(w, g), need, dir)) break;
+    const bool probe = !rbt::floor_probe(w, g, figure_of);
+    if (probe) { need = g.q0; dir = 0; } else if (rbt::qp_walk_step(w, rbt::floor_holds(w, trial_meets), need, dir)) break;
     rbt::qp_round(w, need, dir, probe, qps);
     rule.clear();
     if (round == 0) { if (!probe || need != q0 || dir != 0) return fail("first round", need, dir, q0); rule = {q0}; }

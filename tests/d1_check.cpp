@@ -1,5 +1,5 @@
-// TEST-ONLY: the body of the luma gather (csrc/rbt_cloudmaps.h) and the host half of a transcode to a D1 floor (host/rbt_d1_walk.h: D(q), the floor's condition, probe;
-// host/rbt_qp_walk.h: walk, rounds) as a stand-alone host program, so that they can be built with -fsanitize=address,undefined and run on the CPU (tests/test_d1_floor.py).
+// TEST-ONLY: the body of the luma gather (csrc/rbt_cloudmaps.h) and the host half of a transcode to a D1 floor (host/rbt_d1_walk.h: D(q), the floor's condition;
+// host/rbt_floor_walk.h: probe; host/rbt_qp_walk.h: walk, rounds) as a stand-alone host program, so that they can be built with -fsanitize=address,undefined and run on the CPU (tests/test_d1_floor.py).
 // The source planes are views into heap blocks that end with the last sample of the window's last row and the packed planes blocks of exactly w x h samples, at every
 // misalignment of the source against a 16-byte boundary, so a read or a write past a row's end or a misaligned 16-byte access is caught; the planes are compared with a
 // per-sample loop. The walk - driven round by round the way run_rounds drives it - is held against the definition's loop on every floor, start and range of three D1 tables,
@@ -11,6 +11,7 @@
 #include <vector>
 #include "../rabbit-transcoding_amd/csrc/rbt_cloudmaps.h"
 #include "../rabbit-transcoding_amd/host/rbt_d1_walk.h"
+#include "../rabbit-transcoding_amd/host/rbt_floor_walk.h"
 
 static int fail(const char* what, long a = 0, long b = 0, long c = 0) { printf("FAIL %s %ld %ld %ld\n", what, a, b, c); fflush(stdout); return 1; }
 static uint32_t g_seed = 9753;
@@ -43,7 +44,9 @@ static std::vector<rbt_d1_result> frames_of(double db, double gap) {
 }
 struct Tried { std::vector<rbt_d1_result> d1; };
 static int walk_case(const std::vector<std::vector<rbt_d1_result>>& t, int qp, int32_t floor_mdb, int stat, int lo, int hi) {
-  rbt::QpWalk<Tried> w; rbt::D1Goal g; g.floor_mdb = floor_mdb; g.stat = stat; w.lo = lo; w.hi = hi; rbt::d1_seed(w, g, qp);
+  rbt::QpWalk<Tried> w; rbt::FloorGoal g; g.floor_mdb = floor_mdb; w.lo = lo; w.hi = hi; rbt::floor_seed(w, g, qp);
+  auto figure_of = [&](const Tried& x) { return rbt::d1_figure(x.d1, stat); };
+  auto trial_meets = [&](const Tried& x) { return rbt::d1_meets(x.d1, stat, floor_mdb); };
   const int q0 = qp < lo ? lo : qp > hi ? hi : qp;
   if (g.q0 != q0 || w.toward != 1) return fail("seed", qp, g.q0, q0);
   auto D = [&](int q) { const double a = (double)t[q][0].psnr, b = (double)t[q][1].psnr; return stat == RBT_D1_MEAN ? (a + b) / 2 : (a < b ? a : b); };
@@ -52,8 +55,8 @@ static int walk_case(const std::vector<std::vector<rbt_d1_result>>& t, int qp, i
   int qs = std::isinf(D(q0)) ? q0 : q0 + (int)(D(q0) - floor_mdb / 1000.0); qs = qs < lo ? lo : qs > hi ? hi : qs;
   int n_enc = 0, need = 0, dir = 0, round = 0; std::vector<int> qps, rule;
   for (;; round++) {
-    const bool probe = !rbt::d1_probe(w, g);
-    if (probe) { need = g.q0; dir = 0; } else if (rbt::qp_walk_step(w, rbt::d1_holds(w, g), need, dir)) break;
+    const bool probe = !rbt::floor_probe(w, g, figure_of);
+    if (probe) { need = g.q0; dir = 0; } else if (rbt::qp_walk_step(w, rbt::floor_holds(w, trial_meets), need, dir)) break;
     rbt::qp_round(w, need, dir, probe, qps);
     // the rule of the PSNR floor's rounds: the probe at q0 alone; then qs - 1, qs, qs + 1; then the QP asked for and the next one the same way
     rule.clear();

@@ -1,5 +1,5 @@
-// TEST-ONLY: the body of the distortion sums (csrc/rbt_quality.h) and the host half of a transcode to a PSNR floor (host/rbt_quality_walk.h: PSNR, the floor's condition,
-// probe; host/rbt_qp_walk.h: walk, rounds) as a stand-alone host program, so that they can be built with -fsanitize=address,undefined and run on the CPU (tests/test_quality.py). The planes are views
+// TEST-ONLY: the body of the distortion sums (csrc/rbt_quality.h) and the host half of a transcode to a PSNR floor (host/rbt_quality_walk.h: PSNR, the floor's condition;
+// host/rbt_floor_walk.h: probe; host/rbt_qp_walk.h: walk, rounds) as a stand-alone host program, so that they can be built with -fsanitize=address,undefined and run on the CPU (tests/test_quality.py). The planes are views
 // into heap blocks that end with the last sample of the last row, at every misalignment of the two pictures against a 16-byte boundary and against each other, so a read
 // past a row's end or a misaligned 16-byte load is caught; the sums are compared with a per-sample loop of the definition, the walk - driven round by round the way
 // run_rounds drives it - with the definition's loop on every floor, start and range of three PSNR tables, one of them not monotone, and every round with the rule of what
@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <vector>
 #include "../rabbit-transcoding_amd/host/rbt_quality_walk.h"
+#include "../rabbit-transcoding_amd/host/rbt_floor_walk.h"
 
 static int fail(const char* what, long a = 0, long b = 0, long c = 0) { printf("FAIL %s %ld %ld %ld\n", what, a, b, c); fflush(stdout); return 1; }
 static uint32_t g_seed = 4321;
@@ -52,7 +53,9 @@ static rbt::QualitySums sums_of(double db) {
   return s;
 }
 static int walk_case(const std::vector<rbt::QualitySums>& t, int qp, int32_t floor_mdb, int region, int lo, int hi) {
-  rbt::QpWalk<rbt::QualityTried> w; rbt::QualityGoal g; g.floor_mdb = floor_mdb; g.region = region; g.bit_depth = 10; w.lo = lo; w.hi = hi; rbt::quality_seed(w, g, qp);
+  rbt::QpWalk<rbt::QualityTried> w; rbt::FloorGoal g; g.floor_mdb = floor_mdb; w.lo = lo; w.hi = hi; rbt::floor_seed(w, g, qp);
+  auto figure_of = [&](const rbt::QualityTried& x) { return rbt::quality_region_psnr(x.sums, region, 10); };
+  auto trial_meets = [&](const rbt::QualityTried& x) { return rbt::quality_meets(x.sums, region, floor_mdb, 10); };
   const int q0 = qp < lo ? lo : qp > hi ? hi : qp;
   if (g.q0 != q0 || w.toward != 1) return fail("seed", qp, g.q0, q0);
   auto meets = [&](int q) { return rbt::quality_meets(t[q], region, floor_mdb, 10); };
@@ -60,8 +63,8 @@ static int walk_case(const std::vector<rbt::QualitySums>& t, int qp, int32_t flo
   int qs = std::isinf(p0) ? q0 : q0 + (int)(p0 - floor_mdb / 1000.0); qs = qs < lo ? lo : qs > hi ? hi : qs;
   int n_enc = 0, need = 0, dir = 0, round = 0; std::vector<int> qps, rule;
   for (;; round++) {
-    const bool probe = !rbt::quality_probe(w, g);
-    if (probe) { need = g.q0; dir = 0; } else if (rbt::qp_walk_step(w, rbt::quality_holds(w, g), need, dir)) break;
+    const bool probe = !rbt::floor_probe(w, g, figure_of);
+    if (probe) { need = g.q0; dir = 0; } else if (rbt::qp_walk_step(w, rbt::floor_holds(w, trial_meets), need, dir)) break;
     rbt::qp_round(w, need, dir, probe, qps);
     // the rule: the first round is the probe at q0 alone; the second qs - 1, qs, qs + 1; every later one the QP asked for and the next one the same way - up while the
     // floor was met at qs, down while it was not -; a QP out of the range or already encoded is left out
@@ -80,6 +83,33 @@ static int walk_case(const std::vector<rbt::QualitySums>& t, int qp, int32_t flo
   if (meets(q)) { while (q < hi && meets(q + 1)) q++; met = 1; } else { while (q > lo && !meets(q)) q--; met = meets(q); }
   if (w.start != qs || w.qstar != q || w.met != met) return fail("walk", floor_mdb, w.qstar, q);
   if (n_enc > abs(q - qs) + 5) return fail("encodes", n_enc, q, qs);
+  return 0;
+}
+
+// A walk on the occupied region of trials without an occupied sample. The definitions give the expectation, not the functions under test: the figure of a region without
+// samples is 0.0, so the probe at q0 puts the start at q0 + (int)(0.0 - floor) clamped to the range; a region without samples meets every floor, so the walk climbs from
+// there to hi: q* = hi, met = 1. (A condition derived from the figure - 0.0 >= floor - would stay at lo with met = 0.)
+static int empty_region_case(int qp, int32_t floor_mdb, int lo, int hi) {
+  rbt::QpWalk<rbt::QualityTried> w; rbt::FloorGoal g; g.floor_mdb = floor_mdb; w.lo = lo; w.hi = hi; rbt::floor_seed(w, g, qp);
+  auto figure_of = [](const rbt::QualityTried& x) { return rbt::quality_region_psnr(x.sums, 1, 10); };
+  auto trial_meets = [&](const rbt::QualityTried& x) { return rbt::quality_meets(x.sums, 1, floor_mdb, 10); };
+  const int q0 = qp < lo ? lo : qp > hi ? hi : qp;
+  int qs = q0 + (int)(0.0 - floor_mdb / 1000.0); qs = qs < lo ? lo : qs > hi ? hi : qs;
+  int n_enc = 0, need = 0, dir = 0; std::vector<int> qps;
+  for (int round = 0;; round++) {
+    const bool probe = !rbt::floor_probe(w, g, figure_of);
+    if (probe) { need = g.q0; dir = 0; } else if (rbt::qp_walk_step(w, rbt::floor_holds(w, trial_meets), need, dir)) break;
+    if (probe != (round == 0) || (probe && need != q0)) return fail("empty region: the probe is the first round, at q0", round, need, q0);
+    if (!probe && w.start != qs) return fail("empty region: start", w.start, qs);
+    rbt::qp_round(w, need, dir, probe, qps);
+    if (qps.empty() || round > 60) return fail("empty region: rounds", round, lo, hi);
+    for (int q : qps) {      // every trial: distortion on all samples, not one occupied sample
+      if (q < lo || q > hi || w.tried.count(q)) return fail("empty region: round", q, lo, hi);
+      rbt::QualitySums s; s.samples[0] = 1000000; s.sse[0] = 5000000 + 100000 * (uint64_t)q; w.tried[q].sums = s; n_enc++;
+    }
+  }
+  if (w.start != qs || w.qstar != hi || w.met != 1) return fail("empty region: walk", w.start, w.qstar, w.met);
+  if (n_enc > hi - qs + 5) return fail("empty region: encodes", n_enc, hi, qs);
   return 0;
 }
 
@@ -110,6 +140,8 @@ int main() {
   // a picture that comes back exactly: psnr +inf, the walk starts at q0 and climbs while the sums stay zero
   { std::vector<rbt::QualitySums> t(52); for (int q = 0; q < 52; q++) { t[q] = sums_of(50.0 - q); if (q < 12) t[q].sse[0] = 0; }
     if (walk_case(t, 5, 45000, 0, 0, 51) || walk_case(t, 11, 30000, 0, 0, 51) || walk_case(t, 0, 99000, 0, 0, 11)) return 1; }
+  // no occupied sample in any trial: figure 0.0, floor met (the expected starts, by hand: 26 - 40 and 0 - 40, clamped: 20 and 0)
+  if (empty_region_case(26, 40000, 20, 30) || empty_region_case(0, 40000, 0, 51)) return 1;
   printf("ok\n");
   return 0;
 }
