@@ -816,7 +816,7 @@ int rbt_transcode_v3c_quality_frames(rbt_ctx* ctx, const uint8_t* in, size_t n, 
 /* ---- a QP per CTB (csrc/rbt_qpmap.h, host/rbt_transcode.cpp encode_plan) ----
  * Every call above spends one QP on a whole picture. An atlas picture is a few dozen patches and the padding between them, and what a V-PCC user steers is the patch. Here a
  * geometry / attribute entry may carry a map with one QP per CTB and point-cloud frame: M[f][r][c], n_frames * h_ctb * w_ctb values, row-major. It is the building block,
- * as the QP list was for the floors held frame by frame; floors and byte caps per patch are not built on it yet.
+ * as the QP list was for the floors held frame by frame: the PSNR floors held patch by patch (below) are built on it; byte caps per patch are not built yet.
  *
  * Let T be the target QP of a CTB: max(0, M[f][r][c] - 3) in picture 2f and M[f][r][c] in picture 2f + 1, the constant-QP path's own I / P rule.
  * 1. Decisions. Everything the encoder derives from the QP takes T of the CTB it works in instead of the slice's QP: the quantiser and the dequantiser, the chroma QPs, the
@@ -844,7 +844,7 @@ int rbt_transcode_v3c_quality_frames(rbt_ctx* ctx, const uint8_t* in, size_t n, 
  *    at the entry's log2_ctb; a value outside 0..51; a map without its counts, or counts without a map.
  * The maps are copied at submit. The job is a job of rbt_submit_gof in every other respect: depth, rbt_job_memory, rbt_wait_gof, shared pipelines. Maps together with a rate,
  * quality, D1 or colour target are not offered.
- * Not built: floors and byte caps per patch, a map in the container-level calls (rbt_transcode_v3c), quantisation groups smaller than the CTB. */
+ * Not built: byte caps per patch (PSNR floors per patch: below), a map in the container-level calls (rbt_transcode_v3c), quantisation groups smaller than the CTB. */
 typedef struct {
   uint32_t struct_size;   /* sizeof(rbt_qp_map): checked */
   int n_frames;           /* pictures / 2; 0 with qp NULL = no map */
@@ -860,6 +860,75 @@ int rbt_transcode_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_i
  * that are not ceil(width / ctb), ceil(height / ctb), a QP outside 0..51, occupancy_resolution < 1. A patch that reaches beyond the atlas is clipped to it. */
 int rbt_qp_map_from_patches(const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const int8_t* patch_qp, int background_qp,
                             int log2_ctb, int8_t* out, int w_ctb, int h_ctb);
+
+/* ---- PSNR floors held patch by patch (csrc/rbt_ctbsse.h, host/rbt_patch_walk.h) ----
+ * "Every patch of every frame keeps X dB, bits spent only on the patches that need them": the closed loop on the QP per CTB, for the luma PSNR - the figure that needs nothing
+ * but the pictures already in device memory. Per entry with a target the caller gives, per point-cloud frame f, the patch list (the fields rbt_qp_map_from_patches reads).
+ *
+ * 1. Region. R_k, the region of patch k, is the set of CTBs its rectangle meets - rbt_qp_map_from_patches' rule, clipping included. A CTB two patches meet counts for both.
+ * 2. Sums. Behind a trial's last filter k_ctb_sse leaves, per picture and CTB of the output grid, {sse, sse_occ, n_occ} of the luma samples of the CTB that lie in the
+ *    displayed area - A, B and "occupied" are those of the PSNR floor's rule 1 -, and k_patch_fold adds them over R_k in pictures 2f and 2f + 1. Only the folded words come
+ *    back, with the slice sizes.
+ * 3. Figure of patch k in a trial: rule 2 of the PSNR floor on the folded sums of R_k, in the chosen region (RBT_QUALITY_ALL: sse over the displayed samples of R_k in both
+ *    pictures; RBT_QUALITY_OCCUPIED: sse_occ over n_occ). meets is rule 4 of the PSNR floor with the patch's floor F_k: a patch without a CTB or without a sample meets.
+ * 4. Trial map. A frame's trial with the vector q[] is coded with rbt_qp_map_from_patches(atlas, patches, q, background, log2_ctb): a shared CTB takes the lower QP, the
+ *    background takes background_qp, q0 where that is -1.
+ * 5. Walk (host/rbt_patch_walk.h). Frames are closed pairs of pictures, so each frame walks alone. lo, hi and q0 = clamp(params[i].qp, lo, hi) are the PSNR floor's.
+ *    Trial 0 has q[k] = q0 for all k. After a trial every patch updates: if it does not meet, failed[k] = 1 and, if q[k] > lo, q[k] -= max(1, (int)(F_k - figure_k)),
+ *    clamped at lo; if it meets, has never failed, q[k] < hi, its figure is finite and (int)(figure_k - F_k) >= 1, q[k] += (int)(figure_k - F_k), clamped at hi; otherwise
+ *    it stays. The casts truncate toward zero. If no q[k] changed the frame has settled on this trial, else the next trial takes the new vector. A patch moves up until its
+ *    first failure and only down after it, so a frame's vector never repeats and the walk ends. max_trials (0 = no cap): a frame that reaches it settles on its last trial,
+ *    met as measured. The distortion of a patch depends on its neighbours' QPs and is not monotone in its own, so the walk is the definition: the result is a map under
+ *    which every patch meets or sits at lo, reached by this walk - it is NOT a proof of the cheapest such map.
+ * 6. Rounds. A round is one pass per entry over the frames that have not settled, each with its trial map; settled frames are in no later pass. pictures_encoded = 2 * the
+ *    sum of the frames' n_trials, n_passes = the largest n_trials.
+ * 7. Stream. Byte for byte rbt_transcode_gof_qp_map's for the final map (results[i].map), assembled on the host from the frames' NAL units of their settling trials; every
+ *    pass writes the parameter sets of params[i].qp with cu_qp_delta_enabled_flag = 1. No further encode runs.
+ * 8. Floor 0. With min_psnr_mdb 0 and patch_min_psnr_mdb NULL there is one trial at clamp(params[i].qp, 0, 51): the figures per patch are reported, met = 1.
+ * 9. Everything is copied at submit. The pairing rule (rbt_wait_gof_quality_patches and no other wait; a wrong pairing is RBT_ERR_PARAM and leaves the job collectable),
+ *    rbt_job_memory (the first round at params[i].qp; the map and the words per CTB, 26 bytes a CTB and picture, are not in it), the occupancy source, occupancy_rd, the
+ *    lifetime of the pooled planes and the errors are the PSNR floor's. Further refusals, all RBT_ERR_PARAM with a reason, nothing submitted, the context usable: a wrong
+ *    struct_size; an odd picture count; n_frames that is not pictures / 2; an atlas size that is not the output pictures'; occupancy_resolution < 1; a background_qp
+ *    outside -1..51; a negative max_trials; a negative floor; a QP range or a region the PSNR floor refuses; a frame with patches but no list; a target on an occupancy
+ *    entry. An entry without a target (n_frames 0, everything else 0) is coded at params[i].qp: n_frames 0, map and frames NULL, sums filled.
+ * There is no container-level call and no rbt_pipeline option: the library does not parse the atlas sub-bitstream.
+ * Not built: D1 and colour floors per patch, byte caps per patch, a caller's map together with a target, quantisation groups below the CTB. */
+typedef struct {
+  uint32_t struct_size;                                        /* sizeof(rbt_patch_floor_target): checked */
+  int32_t  min_psnr_mdb;  int region;  int qp_min, qp_max;     /* as rbt_quality_target */
+  int      background_qp;                                      /* 0..51, -1 = q0 */
+  int      max_trials;                                         /* 0 = no cap */
+  rbt_atlas_params atlas;                                      /* width, height, occupancy_resolution are read */
+  int n_frames;  const rbt_patch* const* patches;  const int* n_patches;
+  const int32_t* const* patch_min_psnr_mdb;                    /* NULL, or per frame NULL / one floor per patch: F_k; else F_k = min_psnr_mdb */
+} rbt_patch_floor_target;
+typedef struct { int qp, met, failed; uint64_t sse, samples; double figure; } rbt_patch_pick;   /* of the settling trial: q[k], met, failed[k], the sums of R_k in the chosen region, the figure */
+typedef struct {
+  int n_trials, met, n_patches;                                /* met = AND of patches[k].met */
+  uint64_t bytes;                                              /* the frame's NAL units in the returned stream, start codes included */
+  uint64_t background[3];                                      /* sse, sse_occ, n_occ of the CTBs no patch meets */
+  rbt_patch_pick* patches;                                     /* n_patches picks: they point into rbt_patch_floor_result.picks */
+} rbt_patch_frame;
+typedef struct {
+  int n_frames, qp_probe, met_all, n_passes;                   /* q0; met_all = AND of frames[f].met */
+  uint64_t bytes, pictures_encoded;                            /* size of the returned stream; 2 * sum of frames[f].n_trials */
+  int w_ctb, h_ctb;
+  int8_t* map;                                                 /* the final map, n_frames * h_ctb * w_ctb (malloc'd, rbt_free): rbt_transcode_gof_qp_map returns the same stream for it */
+  rbt_patch_frame* frames;                                     /* n_frames (malloc'd, rbt_free) */
+  rbt_patch_pick* picks;                                       /* every frame's picks back to back (malloc'd, rbt_free) */
+  rbt_quality_result sums;                                     /* over the returned stream, as rbt_wait_gof_quality reports them; its qp fields are -1 */
+} rbt_patch_floor_result;
+int rbt_submit_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_floor_target* targets, rbt_job** job);
+int rbt_wait_gof_quality_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_patch_floor_result* results);   /* results: n entries */
+int rbt_transcode_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_floor_target* targets,
+                                      uint8_t** annexb_out, size_t* n_out, rbt_patch_floor_result* results);   /* submit + wait */
+/* The two kernels on host arrays (tests, and users who only want the measurement): pictures laid out as for rbt_picture_sse. out_ctb: n_frames x h_ctb x w_ctb x {sse,
+ * sse_occ, n_occ} of the luma plane, the grid being ceil(width / ctb) x ceil(height / ctb). rects (may be NULL with n_rects 0): n_rects x {c0, r0, c1, r1} in CTB units,
+ * half-open, the same list for every pair of pictures; out_rect (may be NULL; needs an even n_frames): (n_frames / 2) x (n_rects + 2) x 3 - the rectangles, then the
+ * background (the CTBs no rectangle meets), then the whole frame. RBT_ERR_PARAM: rbt_picture_sse's refusals, log2_ctb outside 4..6, a rectangle outside the grid.
+ * rbt_get_stats afterwards: gpu_ms = the device time between events around the two launches. */
+int rbt_ctb_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int width, int height, int n_frames, int log2_ctb, const uint16_t* occ, int ow, int oh,
+                const int32_t* rects, int n_rects, uint64_t* out_ctb, uint64_t* out_rect);
 
 /* ---- normal estimation (csrc/rbt_normals.h) ----
  * D2 needs normals on the source. Where a sequence comes without them, the reference's PccAppNormalGenerator makes them (PCCNormalsGenerator.cpp: a kd-tree query of the

@@ -182,6 +182,48 @@ class FrameFloorResult(C.Structure):
                 ("frames", C.POINTER(FramePick)), ("sums", QualityResult), ("d1", C.POINTER(D1Result)), ("cloud_ms", C.c_double)]
 
 
+class PatchFloorTarget(C.Structure):
+    """rbt_patch_floor_target; struct_size is filled in. PatchFloorTarget() is the empty target of an entry without one. patches: one list of Patch per point-cloud frame;
+    patch_floors: None, or per frame None / one floor in 1/1000 dB per patch (F_k; else min_psnr_mdb). The object keeps the arrays it points to alive."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_psnr_mdb", C.c_int32), ("region", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("background_qp", C.c_int), ("max_trials", C.c_int),
+                ("atlas", AtlasParams), ("n_frames", C.c_int), ("patches", C.POINTER(C.POINTER(Patch))), ("n_patches", C.POINTER(C.c_int)), ("patch_min_psnr_mdb", C.POINTER(C.POINTER(C.c_int32)))]
+
+    def __init__(self, atlas=None, patches=None, min_psnr_mdb=0, region=RBT_QUALITY_ALL, qp_min=0, qp_max=0, background_qp=-1, max_trials=0, patch_floors=None):
+        super().__init__(C.sizeof(PatchFloorTarget))
+        self._keep = []
+        if atlas is None:
+            return
+        self.min_psnr_mdb, self.region, self.qp_min, self.qp_max, self.background_qp, self.max_trials = min_psnr_mdb, region, qp_min, qp_max, background_qp, max_trials
+        self.atlas = AtlasParams(*[getattr(atlas, n) for n, _ in AtlasParams._fields_])
+        self.n_frames = len(patches)
+        lists = [(Patch * max(1, len(p)))(*p) for p in patches]
+        ptrs = (C.POINTER(Patch) * max(1, len(lists)))(*[C.cast(a, C.POINTER(Patch)) for a in lists])
+        counts = (C.c_int * max(1, len(lists)))(*[len(p) for p in patches])
+        self.patches, self.n_patches = ptrs, counts
+        self._keep += [lists, ptrs, counts]
+        if patch_floors is not None:
+            fl = [None if f is None else (C.c_int32 * max(1, len(f)))(*f) for f in patch_floors]
+            fp = (C.POINTER(C.c_int32) * max(1, len(fl)))(*[None if a is None else C.cast(a, C.POINTER(C.c_int32)) for a in fl])
+            self.patch_min_psnr_mdb = fp
+            self._keep += [fl, fp]
+
+
+class PatchPick(C.Structure):
+    """rbt_patch_pick: of a frame's settling trial, per patch: its QP, met, failed, the sums of its region in the chosen region of samples, its figure"""
+    _fields_ = [("qp", C.c_int), ("met", C.c_int), ("failed", C.c_int), ("sse", C.c_uint64), ("samples", C.c_uint64), ("figure", C.c_double)]
+
+
+class PatchFrame(C.Structure):
+    """rbt_patch_frame: trials, met, the patch count, the frame's bytes, the background's {sse, sse_occ, n_occ}, the picks"""
+    _fields_ = [("n_trials", C.c_int), ("met", C.c_int), ("n_patches", C.c_int), ("bytes", C.c_uint64), ("background", C.c_uint64 * 3), ("patches", C.POINTER(PatchPick))]
+
+
+class PatchFloorResult(C.Structure):
+    """rbt_patch_floor_result: frames, the probe q0, met_all, the passes, the stream's size, the pictures encoded, the grid, the final map, the frames, the stream's sums"""
+    _fields_ = [("n_frames", C.c_int), ("qp_probe", C.c_int), ("met_all", C.c_int), ("n_passes", C.c_int), ("bytes", C.c_uint64), ("pictures_encoded", C.c_uint64), ("w_ctb", C.c_int), ("h_ctb", C.c_int),
+                ("map", C.POINTER(C.c_int8)), ("frames", C.POINTER(PatchFrame)), ("picks", C.POINTER(PatchPick)), ("sums", QualityResult)]
+
+
 RBT_D1_MIN, RBT_D1_MEAN = 0, 1
 
 
@@ -327,6 +369,11 @@ def load(path=None):
     L.rbt_transcode_gof_frame_qp.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(FrameQp), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.rbt_submit_gof_qp_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QpMap), C.POINTER(C.c_void_p)]
     L.rbt_transcode_gof_qp_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(QpMap), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    gof_patch = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(PatchFloorTarget)]
+    L.rbt_submit_gof_quality_patches.argtypes = gof_patch + [C.POINTER(C.c_void_p)]
+    L.rbt_wait_gof_quality_patches.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PatchFloorResult)]
+    L.rbt_transcode_gof_quality_patches.argtypes = gof_patch + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PatchFloorResult)]
+    L.rbt_ctb_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.rbt_qp_map_from_patches.argtypes = [C.POINTER(AtlasParams), C.POINTER(Patch), C.c_int, C.POINTER(C.c_int8), C.c_int, C.c_int, C.POINTER(C.c_int8), C.c_int, C.c_int]
     L.rbt_submit_gof_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(RateTarget), C.POINTER(C.c_void_p)]
     L.rbt_wait_gof_rate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(RateResult)]
@@ -774,6 +821,57 @@ class Context:
         """rbt_transcode_gof_quality_frames: submit + wait"""
         args = self._gof_args(streams, params, targets, QualityTarget)
         return self._frame_results(self._collect(self.L.rbt_transcode_gof_quality_frames, args[0], args, FrameFloorResult))
+
+    def _patch_results(self, res):
+        """([stream bytes, ...], [PatchFloorResult, ...] as dicts): map becomes an int8 array [n_frames, h_ctb, w_ctb] (None without a target), frames a list of dicts whose
+        patches are pick dicts, sums a dict, and the library's arrays are released"""
+        outs, rs = res
+        for r in rs:
+            fr, mp = r["frames"], r["map"]
+            r["frames"] = [dict(_result_dict(fr[f]), patches=[_result_dict(fr[f].patches[k]) for k in range(fr[f].n_patches)]) for f in range(r["n_frames"])] if fr else []
+            r["map"] = np.ctypeslib.as_array(mp, (r["n_frames"], r["h_ctb"], r["w_ctb"])).copy() if mp else None
+            for ptr in (fr, mp, r.pop("picks")):
+                self.L.rbt_free(ptr)
+            r["sums"] = _result_dict(r["sums"])
+        return outs, rs
+
+    def submit_gof_quality_patches(self, streams, params, targets):
+        """rbt_submit_gof_quality_patches: submit_gof with one PatchFloorTarget per entry (PatchFloorTarget() = none): every patch of every frame holds its floor; returns a
+        job for wait_gof_quality_patches"""
+        return self._submit(self.L.rbt_submit_gof_quality_patches, streams, params, targets, PatchFloorTarget)
+
+    def wait_gof_quality_patches(self, job):
+        """rbt_wait_gof_quality_patches -> ([stream bytes, ...], [result dict, ...])"""
+        return self._patch_results(self._collect(self.L.rbt_wait_gof_quality_patches, job[1], [job[0]], PatchFloorResult))
+
+    def transcode_gof_quality_patches(self, streams, params, targets):
+        """rbt_transcode_gof_quality_patches: submit + wait"""
+        args = self._gof_args(streams, params, targets, PatchFloorTarget)
+        return self._patch_results(self._collect(self.L.rbt_transcode_gof_quality_patches, args[0], args, PatchFloorResult))
+
+    def ctb_sse(self, a, b, w, h, log2_ctb=5, occ=None, rects=None):
+        """rbt_ctb_sse: planar 4:2:0 pictures a, b ([n, w*h*3/2] uint16), or None one occupancy plane per picture ([n, oh, ow] uint16), or None rectangles [[c0, r0, c1, r1],
+        ...] in CTB units -> uint64 [n, h_ctb, w_ctb, 3]: per picture and CTB the luma sums sse, sse_occ, n_occ; with rects (a list, may be empty) also uint64
+        [n / 2, n_rects + 2, 3]: per pair of pictures the sums over each rectangle, the background and the whole frame. stats()["gpu_ms"]: the device time of the launches"""
+        a = np.ascontiguousarray(a, dtype=np.uint16).reshape(-1, w * h * 3 // 2)
+        b = np.ascontiguousarray(b, dtype=np.uint16).reshape(-1, w * h * 3 // 2)
+        if a.shape != b.shape:
+            raise ValueError("a and b must hold the same number of pictures")
+        ow = oh = 0
+        if occ is not None:
+            occ = np.ascontiguousarray(occ, dtype=np.uint16)
+            if occ.ndim != 3 or occ.shape[0] != a.shape[0]:
+                raise ValueError("occ must be [n, oh, ow]")
+            oh, ow = occ.shape[1:]
+        ctb = 1 << max(0, min(log2_ctb, 12))
+        out = np.zeros((a.shape[0], (h + ctb - 1) // ctb, (w + ctb - 1) // ctb, 3), np.uint64)
+        rc = out_r = None
+        if rects is not None:
+            rc = np.ascontiguousarray(np.asarray(rects, dtype=np.int32).reshape(-1, 4))
+            out_r = np.zeros((a.shape[0] // 2, rc.shape[0] + 2, 3), np.uint64)
+        self._chk(self.L.rbt_ctb_sse(self.h, a.ctypes.data, b.ctypes.data, w, h, a.shape[0], log2_ctb, occ.ctypes.data if occ is not None else None, ow, oh,
+                                     rc.ctypes.data if rc is not None and rc.size else None, rc.shape[0] if rc is not None else 0, out.ctypes.data, out_r.ctypes.data if out_r is not None else None))
+        return out if rects is None else (out, out_r)
 
     def _d1_results(self, res):
         """([stream bytes, ...], [D1FloorResult, ...] as dicts): frames becomes a list of D1 dicts and the library's array is released"""

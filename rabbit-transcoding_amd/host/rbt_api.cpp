@@ -171,6 +171,7 @@ int rbt_sample_to_byte_stream(const uint8_t* in, size_t n, uint8_t** out, size_t
 struct SubmitExtras {
   bool gof_rule = true; const rbt_rate_target* targets = nullptr; const rbt_quality_target* quality = nullptr; const rbt_d1_target* d1 = nullptr; const rbt_color_target* color = nullptr;
   bool per_frame = false; const rbt_frame_qp* lists = nullptr; const rbt_qp_map* maps = nullptr;
+  const rbt_patch_floor_target* patches = nullptr;
 };
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x = SubmitExtras());
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
@@ -289,6 +290,40 @@ static int check_qp_maps(std::string& err, int n, const rbt_stream_params* p, co
   }
   return RBT_OK;
 }
+// the refusals of rbt_submit_gof_quality_patches that the parameters alone decide (the counts and the atlas against the stream's pictures: gof_refused); out: the targets
+// with their patch lists and floors copied
+static int check_patch_floors(std::string& err, int n, const rbt_stream_params* p, const rbt_patch_floor_target* t, std::vector<rbt::PatchFloorIn>& out) {
+  out.assign((size_t)n, rbt::PatchFloorIn());
+  for (int i = 0; i < n; i++) {
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    rbt::PatchFloorIn& o = out[(size_t)i]; memset(&o.t, 0, sizeof(o.t));
+    if (t[i].struct_size != sizeof(rbt_patch_floor_target)) { err = who + "rbt_patch_floor_target.struct_size is not sizeof(rbt_patch_floor_target)"; return RBT_ERR_PARAM; }
+    rbt_patch_floor_target zero; memset(&zero, 0, sizeof(zero));
+    const bool empty = !t[i].min_psnr_mdb && !t[i].region && !t[i].qp_min && !t[i].qp_max && !t[i].background_qp && !t[i].max_trials && !t[i].n_frames && !t[i].patches && !t[i].n_patches &&
+                       !t[i].patch_min_psnr_mdb && !memcmp(&t[i].atlas, &zero.atlas, sizeof(zero.atlas));
+    if (empty) continue;
+    if (p[i].video_type == RBT_VIDEO_OCCUPANCY) { err = who + "an occupancy stream is coded losslessly and takes no PSNR floor (its target must be empty)"; return RBT_ERR_PARAM; }
+    if (t[i].min_psnr_mdb < 0) { err = who + "min_psnr_mdb must not be negative"; return RBT_ERR_PARAM; }
+    if (t[i].region != RBT_QUALITY_ALL && t[i].region != RBT_QUALITY_OCCUPIED) { err = who + "region must be RBT_QUALITY_ALL or RBT_QUALITY_OCCUPIED"; return RBT_ERR_PARAM; }
+    const int lo = t[i].qp_min, hi = t[i].qp_max ? t[i].qp_max : 51;
+    if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
+    if (t[i].background_qp < -1 || t[i].background_qp > 51) { err = who + "background_qp is outside -1..51 (-1 = the probe's QP)"; return RBT_ERR_PARAM; }
+    if (t[i].max_trials < 0) { err = who + "max_trials must not be negative (0 = no cap)"; return RBT_ERR_PARAM; }
+    if (t[i].n_frames < 1 || !t[i].patches || !t[i].n_patches) { err = who + "a patch target needs n_frames = pictures / 2 with a patch list and a count per frame"; return RBT_ERR_PARAM; }
+    if (t[i].atlas.width < 1 || t[i].atlas.height < 1 || t[i].atlas.occupancy_resolution < 1) { err = who + "the atlas needs a size and an occupancy_resolution"; return RBT_ERR_PARAM; }
+    if (p[i].log2_ctb && (p[i].log2_ctb < 4 || p[i].log2_ctb > 6)) { err = who + "log2_ctb must be 4..6"; return RBT_ERR_PARAM; }
+    for (int f = 0; f < t[i].n_frames; f++) {
+      const int np = t[i].n_patches[f];
+      if (np < 0 || (np > 0 && !t[i].patches[f])) { err = who + "frame " + std::to_string(f) + " has a patch count without a list"; return RBT_ERR_PARAM; }
+      o.patches.emplace_back(np ? t[i].patches[f] : nullptr, np ? t[i].patches[f] + np : nullptr);
+      const int32_t* fl = t[i].patch_min_psnr_mdb ? t[i].patch_min_psnr_mdb[f] : nullptr;
+      o.floors.emplace_back((size_t)np, t[i].min_psnr_mdb);
+      for (int k = 0; k < np && fl; k++) { if (fl[k] < 0) { err = who + "the floor of patch " + std::to_string(k) + " of frame " + std::to_string(f) + " is negative"; return RBT_ERR_PARAM; } o.floors.back()[(size_t)k] = fl[k]; }
+    }
+    o.t = t[i]; o.t.patches = nullptr; o.t.n_patches = nullptr; o.t.patch_min_psnr_mdb = nullptr;
+  }
+  return RBT_OK;
+}
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
@@ -305,12 +340,14 @@ static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const si
   if (x.lists) { if (int rc = check_frame_qp(ctx->last_err, n, p, x.lists, frame_qp)) return rc; r.frame_qp = &frame_qp; }
   std::vector<rbt::QpMapIn> qp_maps;
   if (x.maps) { if (int rc = check_qp_maps(ctx->last_err, n, p, x.maps, qp_maps)) return rc; r.qp_maps = &qp_maps; }
+  std::vector<rbt::PatchFloorIn> patch_floors;
+  if (x.patches) { if (int rc = check_patch_floors(ctx->last_err, n, p, x.patches, patch_floors)) return rc; r.patch_floors = &patch_floors; }
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
   rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, r), ctx};
-  if (x.quality || x.d1 || x.color || x.lists || x.maps) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
+  if (x.quality || x.d1 || x.color || x.lists || x.maps || x.patches) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -385,7 +422,8 @@ static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out,
     {"rbt_wait_gof_d1 collects jobs of rbt_submit_gof_d1 only", "a job of rbt_submit_gof_d1 is collected by rbt_wait_gof_d1"},
     {"rbt_wait_gof_color collects jobs of rbt_submit_gof_color only", "a job of rbt_submit_gof_color is collected by rbt_wait_gof_color"},
     {"rbt_wait_gof_d1_frames collects jobs of rbt_submit_gof_d1_frames only", "a job of rbt_submit_gof_d1_frames is collected by rbt_wait_gof_d1_frames"},
-    {"rbt_wait_gof_quality_frames collects jobs of rbt_submit_gof_quality_frames only", "a job of rbt_submit_gof_quality_frames is collected by rbt_wait_gof_quality_frames"}};
+    {"rbt_wait_gof_quality_frames collects jobs of rbt_submit_gof_quality_frames only", "a job of rbt_submit_gof_quality_frames is collected by rbt_wait_gof_quality_frames"},
+    {"rbt_wait_gof_quality_patches collects jobs of rbt_submit_gof_quality_patches only", "a job of rbt_submit_gof_quality_patches is collected by rbt_wait_gof_quality_patches"}};
   const rbt::GofKind is = rbt::gof_kind(job->j);
   if (is != kind) { const bool called = is == rbt::GOF_PLAIN || (kind != rbt::GOF_PLAIN && kind < is); ctx->last_err = mismatch[called ? kind : is][called ? 0 : 1]; return RBT_ERR_PARAM; }
   int n_flat = 0; r.out = annexb_out; r.n_out = n_out; r.n_flat = &n_flat;
@@ -457,6 +495,23 @@ int rbt_transcode_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_i
 int rbt_qp_map_from_patches(const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const int8_t* patch_qp, int background_qp, int log2_ctb, int8_t* out, int w_ctb, int h_ctb) try {
   std::string err;      // (no context to leave the reason with: the header names every refusal)
   return rbt::qp_map_from_patches(err, atlas, patches, n_patches, patch_qp, background_qp, log2_ctb, out, w_ctb, h_ctb);
+} RBT_CATCH
+// ---- PSNR floors held patch by patch ----
+int rbt_submit_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_floor_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  SubmitExtras x; x.patches = targets; return submit(ctx, n, annexb_in, n_in, p, job, x);
+} RBT_CATCH
+int rbt_wait_gof_quality_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_patch_floor_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  rbt::GofResults r; r.patches = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_QUALITY_PATCHES, r);
+} RBT_CATCH
+int rbt_transcode_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_floor_target* targets,
+                                      uint8_t** annexb_out, size_t* n_out, rbt_patch_floor_result* results) try {
+  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_quality_patches(ctx, n, annexb_in, n_in, p, targets, &job);
+  if (rc) return rc;
+  return rbt_wait_gof_quality_patches(ctx, job, annexb_out, n_out, results);
 } RBT_CATCH
 // ---- floors held frame by frame ----
 int rbt_submit_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job) try {
@@ -539,6 +594,12 @@ int rbt_picture_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int widt
   if (!ctx || !a || !b || !out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);
   return rbt::picture_sse_host(ctx->last_err, a, b, width, height, n_frames, occ, ow, oh, out, ctx->stats);
+} RBT_CATCH
+int rbt_ctb_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int width, int height, int n_frames, int log2_ctb, const uint16_t* occ, int ow, int oh,
+                const int32_t* rects, int n_rects, uint64_t* out_ctb, uint64_t* out_rect) try {
+  if (!ctx || !a || !b || !out_ctb) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  return rbt::ctb_sse_host(ctx->last_err, a, b, width, height, n_frames, log2_ctb, occ, ow, oh, rects, n_rects, out_ctb, out_rect, ctx->stats);
 } RBT_CATCH
 int rbt_level_census(rbt_ctx* ctx, const int16_t* y, const int16_t* cb, const int16_t* cr, int w, int h, const int8_t* qp4, const uint8_t* pm4, uint32_t* hist) try {
   if (!ctx || !y || !cb || !cr || !qp4 || !pm4 || !hist) return RBT_ERR_PARAM;

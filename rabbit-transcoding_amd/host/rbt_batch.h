@@ -10,6 +10,7 @@
 #include "../csrc/rbt_hash.h"
 #include "../csrc/rbt_rate.h"
 #include "../csrc/rbt_quality.h"
+#include "../csrc/rbt_ctbsse.h"
 #include "rbt_hls.h"
 
 namespace rbt {

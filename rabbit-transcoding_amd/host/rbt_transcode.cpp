@@ -15,6 +15,8 @@
 #include "rbt_d1_walk.h"
 #include "rbt_color_walk.h"
 #include "rbt_frame_walk.h"
+#include "rbt_patch_walk.h"
+#include "rbt_qp_map.h"
 #include "rbt_pcc.h"
 #include "../csrc/rbt_cloudmaps.h"
 #ifdef RBT_HOSTEMU
@@ -66,6 +68,7 @@ struct EncodeBatch {
   int main_stream = 0, aux_stream = -1;          // aux_stream >= 0: the intra part was enqueued there (its timers live there)
   HashSet hash; std::vector<int> hash_idx;      // md5_sei: the reconstructions to hash (after SAO), index of each picture in `hash` (-1: none)
   size_t n_sums = 0; uint64_t* d_sums = nullptr; std::vector<uint64_t> sums;   // quality floors: RBT_SSE_WORDS distortion words per picture behind the slice table (set n_sums before encode_build); after encode_finish: their values
+  size_t n_ctb_words = 0; uint64_t* d_ctb_words = nullptr;   // floors per patch: the words per CTB of k_ctb_sse (set before encode_build); they stay here, their folds are the tail of d_sums
   std::vector<int32_t> lists_keep; size_t off_i = 0, off_ideb = 0, off_p = 0, off_sl = 0, off_sl_p = 0, off_isao = 0, off_psao = 0, off_pdeb = 0; int n_pdeb = 0, n_i = 0, n_ideb = 0, n_p = 0, n_sl_i = 0, n_sl_p = 0, n_isao = 0, n_psao = 0;   // index lists (encode_upload_lists)
   std::string err;
   ~EncodeBatch() { rbtk::dev_free(arena); }
@@ -139,6 +142,7 @@ static void encode_lay_out(EncodeBatch& b, Arena& a) {
   b.d_frames = a.take<RbtFrame>(nf); b.d_slices = a.take<RbtSlice>(ns);
   if (a.base) for (size_t i = 0; i < nf; i++) if (b.desc[b.frame_stream[i]].src_flat_always) { b.frames[i].src_flat_one = 1; b.frames[i].src_flat = &b.d_frames[i].src_flat_one; }
   if (b.n_sums) b.d_sums = a.take<uint64_t>(b.n_sums);      // right behind the slices: one copy brings both back
+  if (b.n_ctb_words) b.d_ctb_words = a.take<uint64_t>(b.n_ctb_words);
   b.d_lists = a.take<int32_t>((nf + ns) * 3); b.d_dst = a.take<uint32_t>(ns);
   // the packed output holds every slice back to back: as large as the slice buffers together, so that slices which fit their buffers always fit it (half of that, which
   // it had before, is less than noise needs in every QP band: DESIGN.md 9.5)
@@ -486,7 +490,7 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
 // a caller can keep two GOFs in flight (job slots use disjoint HIP streams): the next GOF's entropy decoding then runs
 // underneath the previous GOF's reconstruction and re-encode.
 // Targets - a byte budget or a PSNR floor per entry -: what a pipeline with such an entry keeps between the rounds of its trial encodes (run_rounds, launch_round, finish_round)
-struct RoundCand { int q, qp, walk; int fw = -1; FramePass pass; };   // entry q of the group at qp; walk: index of its walk, -1 for a constant-QP entry of the pipeline; fw >= 0: a pass of the entry's frame walks (qp: the entry's own, for the parameter sets)
+struct RoundCand { int q, qp, walk; int fw = -1; FramePass pass; int pw = -1; std::vector<int8_t> qmap; };   // entry q of the group at qp; walk: index of its walk, -1 for a constant-QP entry of the pipeline; fw >= 0: a pass of the entry's frame walks (qp: the entry's own, for the parameter sets)
 struct TargetTried : QualityTried { std::vector<rbt_d1_result> d1; std::vector<rbt_color_result> color; };      // d1 / color: a job with D1 / colour floors, the frames of the trial
 // A budget (toward < 0) or a floor (toward > 0, rbt_floor_walk.h) - on the PSNR of `region` at bit_depth, on D1 or on the colour PSNR of `channel` of the clouds, stat over the frames
 enum WalkKind { WALK_BUDGET, WALK_PSNR, WALK_D1, WALK_COLOR };
@@ -494,7 +498,30 @@ struct TargetWalk : QpWalk<TargetTried> { WalkKind kind = WALK_BUDGET; RateGoal 
 // Quality floors: the occupancy source of an entry (include/rbt.h, "transcoding to a PSNR floor", rule 3), kept in the job because the pipelines that use it are encoded in
 // the wait half: the pooled luma planes of the occupancy stream, and for occupancy_rd the per-4x4-unit maps made of them (both live in GofJob::pooled until the job goes)
 struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
+// Floors held patch by patch: the walk of one point-cloud frame (rbt_patch_walk.h) with what its last trial brought - the frame's NAL units, the sums of its two pictures,
+// the folded sums per patch and of the background, the map it was coded with - and the walks of one entry: per frame R_k in CTB units (the rectangles k_patch_fold reads, on
+// the device from the first round to the last) and the displayed samples of R_k in both pictures
+struct PatchFrame { PatchWalk w; std::vector<uint8_t> stream; QualitySums sums; std::vector<PatchSums> ps; uint64_t bg[3] = {0, 0, 0}; std::vector<int8_t> map; std::vector<int32_t> rects; std::vector<uint64_t> samples; size_t rect_off = 0; };
+struct PatchWalks {
+  int q = 0, entry = 0, n_passes = 0, l2 = 5, wc = 0, hc = 0, W = 0, H = 0, bit_depth = 8; std::vector<PatchFrame> frames; int32_t* d_rects = nullptr;
+  bool settled() const { for (const PatchFrame& f : frames) if (!f.w.settled) return false; return true; }
+};
+// the tables of k_ctb_sse and k_patch_fold for the round in flight, used like SseSet: one upload before the round's first kernel, the launches behind its last filter
+struct CtbSseSet {
+  std::vector<RbtCtbSsePic> pics; std::vector<RbtFoldJob> jobs; int max_ctbs = 0, max_rects = 0; std::vector<uint8_t> staging; uint8_t* d = nullptr; size_t o_jobs = 0;
+  int upload() {
+    o_jobs = (pics.size() * sizeof(RbtCtbSsePic) + 255) & ~(size_t)255;
+    staging.assign(o_jobs + jobs.size() * sizeof(RbtFoldJob), 0);
+    memcpy(staging.data(), pics.data(), pics.size() * sizeof(RbtCtbSsePic)); memcpy(staging.data() + o_jobs, jobs.data(), jobs.size() * sizeof(RbtFoldJob));
+    d = (uint8_t*)rbtk::dev_alloc(staging.size());
+    if (!d) return RBT_ERR_NOMEM;
+    return rbtk::h2d(d, staging.data(), staging.size()) ? RBT_ERR_NO_DEVICE : 0;
+  }
+  void launch() const { rbtk::launch_ctb_sse((const RbtCtbSsePic*)d, (int)pics.size(), max_ctbs); rbtk::launch_patch_fold((const RbtFoldJob*)(d + o_jobs), (int)jobs.size(), max_rects); }
+  ~CtbSseSet() { rbtk::dev_free(d); }
+};
 struct RoundPipe {
+  std::vector<PatchWalks> pwalks; std::unique_ptr<CtbSseSet> ctbsse;   // a job with floors held patch by patch: per entry with a target its frames' walks; the round's tables
   std::vector<TargetWalk> walks; std::vector<int> n_enc;
   std::vector<FrameWalks<TargetWalk>> fwalks;  // a job with floors held frame by frame: per entry of the group one walk per point-cloud frame
   std::vector<RoundCand> cands;                // the round to run (eb == nullptr) or running
@@ -517,6 +544,7 @@ struct D1Entry : CloudEntry { rbt_d1_target t; std::vector<MapFrame*> frames; st
 struct ColorEntry : CloudEntry { rbt_color_target t; int geo = -1; uint16_t* geo_planes = nullptr; uint16_t* in_planes = nullptr; std::vector<ColorFrame*> frames, own_ref; };
 // what a pipeline's rounds leave of an entry with a cloud target: the walk's result - or the entry's own QP - and the frames' figures there
 template <class Result> struct FloorOut { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<Result> frames; double cloud_ms = 0; };
+struct PatchFloorOut { int q0 = 0, n_passes = 0, wc = 0, hc = 0, bit_depth = 8; uint64_t bytes = 0, pictures = 0; std::vector<int8_t> map; std::vector<rbt_patch_frame> frames; std::vector<rbt_patch_pick> picks; QualitySums sums; };
 struct FrameFloorOut { int q0 = 0, n_passes = 0, bit_depth = 8; std::vector<rbt_frame_pick> frames; std::vector<rbt_d1_result> d1; double cloud_ms = 0; uint64_t bytes = 0, pictures = 0; QualitySums sums; };
 struct GofJob {
   int n = 0, slot = 0, ng = 0, rc = 0; GofKind kind = GOF_PLAIN;      // kind: which submit made the job, fixed there
@@ -550,6 +578,9 @@ struct GofJob {
   std::vector<QpMapIn> qp_maps;      // a QP per CTB (rbt_submit_gof_qp_map): per entry the maps, an empty qp = none; the job is a constant-QP job otherwise, as with frame_qp
   // floors held frame by frame (rbt_submit_gof_quality_frames): a job with quality floors whose pipelines walk every frame on its own (RoundPipe::fwalks)
   bool per_frame = false; std::vector<FrameFloorOut> fout;
+  // floors held patch by patch (rbt_submit_gof_quality_patches): a job with quality floors that are all 0, like a job with cloud targets; the entries with a target walk
+  // every frame's patches (RoundPipe::pwalks), the others are coded once at their own QP
+  std::vector<PatchFloorIn> patch; std::vector<PatchFloorOut> pout;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   void color_release(int entry) {        // the frames' volumes go back to the context's cache; their streams have been waited for
     ColorEntry& E = color[entry];
@@ -721,6 +752,24 @@ static int check_qp_maps(GofJob& j) {
   }
   return 0;
 }
+// Floors held patch by patch (include/rbt.h, rule 9): the target's counts and atlas against the pictures the decoders found. A refusal of the plan, like check_frame_qp's
+static int check_patch_floors(GofJob& j) {
+  if (j.patch.empty()) return 0;
+  for (int g = 0; g < j.ng; g++) for (size_t q = 0; q < j.groups[g].size(); q++) {
+    const int i = j.groups[g][q]; const DecodeBatch& db = j.db[g]; const rbt_patch_floor_target& t = j.patch[i].t;
+    if (t.n_frames <= 0) continue;
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    const int ds = j.dec_of[g][q], cnt = db.stream_count[ds];
+    if (cnt % 2 || t.n_frames != cnt / 2) {
+      j.err = who + "rbt_patch_floor_target.n_frames is " + std::to_string(t.n_frames) + ", the stream holds " + std::to_string(cnt) + " pictures (n_frames must be pictures / 2)";
+      j.refused = true; return RBT_ERR_PARAM; }
+    int dw, dh; displayed(db, ds, &dw, &dh);
+    if (t.atlas.width != dw || t.atlas.height != dh) {
+      j.err = who + "the atlas is " + std::to_string(t.atlas.width) + " x " + std::to_string(t.atlas.height) + ", the output pictures are " + std::to_string(dw) + " x " + std::to_string(dh);
+      j.refused = true; return RBT_ERR_PARAM; }
+  }
+  return 0;
+}
 static int rate_prepare(GofJob& j, int gi);
 static int quality_prepare(GofJob& j, SubmitPlan& s, int gi);
 static int d1_prepare(GofJob& j, SubmitPlan& s, int gi);
@@ -770,6 +819,11 @@ static void desc_subset(EncStreamDesc& d, const FramePass& p) {
   pick(d.hint_pm); pick(d.hint_dm); pick(d.occ4); pick(d.src_flat); pick(d.alias_pix); pick(d.alias_coef);
   d.n_total = d.n_frames; d.n_frames = (int)pic.size(); d.pic.swap(pic);
   d.frame_qp.assign(p.qps.begin(), p.qps.end());
+  if (!d.qp_map.empty()) {      // a map per frame of the stream: the maps of the frames the pass carries
+    const size_t per = (size_t)d.qm_w * d.qm_h; std::vector<int8_t> m;
+    for (int f : p.frames) m.insert(m.end(), d.qp_map.begin() + (ptrdiff_t)(per * (size_t)f), d.qp_map.begin() + (ptrdiff_t)(per * (size_t)(f + 1)));
+    d.qp_map.swap(m);
+  }
 }
 static int round_fill_batch(GofJob& j, int gi, const std::vector<RoundCand>& cands, EncodeBatch& eb) {
   for (size_t e = 0; e < cands.size(); e++) {
@@ -782,7 +836,11 @@ static int round_fill_batch(GofJob& j, int gi, const std::vector<RoundCand>& can
     d.occ4.resize(d.n_frames); d.occ4_w = o.w4; d.occ4_h = o.h4;
     for (int k = 0; k < d.n_frames; k++) d.occ4[k] = o.maps + (size_t)((size_t)k * o.n / d.n_frames) * o.w4 * o.h4;
   }
-  for (size_t e = 0; e < cands.size(); e++) if (cands[e].fw >= 0) desc_subset(eb.desc[e], cands[e].pass);      // last: every table above is per picture of the stream
+  for (size_t e = 0; e < cands.size(); e++) if (cands[e].pw >= 0) {      // a pass of an entry's patch walks: the trial maps of all its frames (desc_subset picks the pass's)
+    const PatchWalks& pw = j.pipes[gi].pwalks[(size_t)cands[e].pw];
+    eb.desc[e].qp_map = cands[e].qmap; eb.desc[e].qm_w = pw.wc; eb.desc[e].qm_h = pw.hc;
+  }
+  for (size_t e = 0; e < cands.size(); e++) if (cands[e].fw >= 0 || cands[e].pw >= 0) desc_subset(eb.desc[e], cands[e].pass);      // last: every table above is per picture of the stream
   return 0;
 }
 template <class Target> static TargetWalk new_walk(size_t q, int entry, const Target& t) { TargetWalk w; w.q = (int)q; w.entry = entry; w.lo = t.qp_min; w.hi = t.qp_max ? t.qp_max : 51; return w; }
@@ -851,10 +909,66 @@ static bool walk_step(TargetWalk& w, int& need, int& dir, bool& alone) {
   if (alone) { need = w.floor.q0; dir = 0; return false; }
   return qp_walk_step(w, floor_holds(w, meets), need, dir);
 }
+// ------------------------------------------------------------------------------------------------ floors held patch by patch (include/rbt.h, "PSNR floors held patch by patch")
+static bool has_patch_floor(const GofJob& j, int i) { return !j.patch.empty() && j.patch[i].t.n_frames > 0; }
+// In the wait half, once the pipeline's decoder has been collected: per entry with a target the walks of its frames - lo, hi and q0 as the PSNR floor has them, a range of
+// q0 alone where there is no floor at all (rule 8) -, R_k of every patch in CTB units and its displayed samples, and the rectangles on the device for all rounds
+static int seed_patch_walks(GofJob& j, int gi, RoundPipe& r) {
+  const std::vector<int>& gs = j.groups[gi]; DecodeBatch& db = j.db[gi];
+  for (size_t q = 0; q < gs.size(); q++) if (has_patch_floor(j, gs[q])) {
+    const int i = gs[q]; const PatchFloorIn& in = j.patch[i]; const rbt_patch_floor_target& t = in.t;
+    PatchWalks pw; pw.q = (int)q; pw.entry = i; pw.l2 = j.params[i].log2_ctb ? j.params[i].log2_ctb : 5; pw.bit_depth = entry_bit_depth(j, gi, q);
+    displayed(db, j.dec_of[gi][q], &pw.W, &pw.H);
+    pw.wc = (pw.W + (1 << pw.l2) - 1) >> pw.l2; pw.hc = (pw.H + (1 << pw.l2) - 1) >> pw.l2;
+    bool any_floor = t.min_psnr_mdb != 0; for (const std::vector<int32_t>& fl : in.floors) for (int32_t v : fl) any_floor |= v != 0;
+    const int qp = std::min(51, std::max(0, j.params[i].qp)), lo = any_floor ? t.qp_min : qp, hi = any_floor ? (t.qp_max ? t.qp_max : 51) : qp;
+    pw.frames.resize((size_t)t.n_frames); size_t n_rects = 0;
+    for (int f = 0; f < t.n_frames; f++) {
+      PatchFrame& F = pw.frames[(size_t)f]; const std::vector<rbt_patch>& ps = in.patches[(size_t)f];
+      patch_walk_seed(F.w, qp, lo, hi, t.max_trials, in.floors[(size_t)f]);
+      F.rects.resize(4 * ps.size()); F.samples.resize(ps.size()); F.rect_off = n_rects; n_rects += ps.size();
+      for (size_t k = 0; k < ps.size(); k++) {
+        patch_region(pw.W, pw.H, t.atlas.occupancy_resolution, ps[k].u0, ps[k].v0, ps[k].size_u0, ps[k].size_v0, pw.l2, &F.rects[4 * k]);
+        F.samples[k] = patch_region_samples(&F.rects[4 * k], pw.W, pw.H, pw.l2);
+      }
+    }
+    pw.d_rects = (int32_t*)rbtk::dev_alloc(std::max<size_t>(1, n_rects) * 16);
+    if (!pw.d_rects) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    j.pooled.push_back(pw.d_rects);
+    for (const PatchFrame& F : pw.frames) if (!F.rects.empty() && rbtk::h2d(pw.d_rects + 4 * F.rect_off, F.rects.data(), F.rects.size() * 4)) { j.err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+    r.pwalks.push_back(std::move(pw));
+  }
+  return 0;
+}
+// the trial maps of an entry's frames: rule 4 for every frame that has not settled (a settled frame is in no pass: its part stays at q0)
+static int patch_trial_maps(GofJob& j, const PatchWalks& pw, std::vector<int8_t>& out) {
+  const PatchFloorIn& in = j.patch[pw.entry]; const size_t per = (size_t)pw.wc * pw.hc;
+  rbt_atlas_params a = in.t.atlas; a.width = pw.W; a.height = pw.H;
+  out.assign(per * pw.frames.size(), 0);
+  for (size_t f = 0; f < pw.frames.size(); f++) {
+    const PatchWalk& w = pw.frames[f].w;
+    if (w.settled) { std::fill(out.begin() + (ptrdiff_t)(per * f), out.begin() + (ptrdiff_t)(per * (f + 1)), (int8_t)w.q0); continue; }
+    std::vector<int8_t> q(w.q.begin(), w.q.end());
+    if (int rc = qp_map_from_patches(j.err, &a, in.patches[f].data(), (int)in.patches[f].size(), q.data(), in.t.background_qp < 0 ? w.q0 : in.t.background_qp, pw.l2, out.data() + per * f, pw.wc, pw.hc)) return rc;
+  }
+  return 0;
+}
 // The round to run next, in group order: what every unsettled walk asks for (qp_round) and, in the first round, the pipeline's entries without a target at their own QP
-static void name_round(const GofJob& j, int gi, RoundPipe& r, bool first) {
+static void name_round(GofJob& j, int gi, RoundPipe& r, bool first) {
   const std::vector<int>& gs = j.groups[gi]; std::vector<int> qps; size_t k = 0;
   r.cands.clear();
+  if (!j.patch.empty()) {      // floors held patch by patch: one pass per entry with a target over its unsettled frames, each with its trial map (rule 6)
+    size_t p = 0;
+    for (size_t q = 0; q < gs.size(); q++) {
+      if (p == r.pwalks.size() || r.pwalks[p].q != (int)q) { if (first) r.cands.push_back(RoundCand{(int)q, j.params[gs[q]].qp, -1}); continue; }
+      PatchWalks& pw = r.pwalks[p];
+      RoundCand c{pw.q, j.params[pw.entry].qp, -1}; c.pw = (int)p;
+      for (size_t f = 0; f < pw.frames.size(); f++) if (!pw.frames[f].w.settled) c.pass.frames.push_back((int)f);
+      if (!c.pass.frames.empty() && !patch_trial_maps(j, pw, c.qmap)) r.cands.push_back(std::move(c));
+      p++;
+    }
+    return;
+  }
   if (j.per_frame) {      // every entry of the pipeline walks frame by frame: its passes (rbt_frame_walk.h), in group order
     std::vector<FramePass> passes;
     for (size_t e = 0; e < r.fwalks.size(); e++) {
@@ -907,6 +1021,33 @@ static int round_sums_setup(GofJob& j, int gi) {
     }
   }
   if (int rc = r.sse->upload()) { j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
+  // floors held patch by patch: the luma of the same pairs CTB by CTB into the batch's arena, and per frame of a pass the folds of its rectangles behind the words above
+  if (j.patch.empty()) return 0;
+  r.ctbsse.reset(new CtbSseSet()); CtbSseSet& cs = *r.ctbsse;
+  size_t pic = 0, ctb_at = 0, fold_at = r.sse->pics.size() * RBT_SSE_WORDS;
+  for (size_t e = 0; e < r.cands.size(); e++) {
+    const EncStreamDesc& d = eb.desc[e]; const RoundCand& c = r.cands[e];
+    if (c.pw < 0) { pic += (size_t)d.n_frames; continue; }
+    const PatchWalks& pw = r.pwalks[(size_t)c.pw]; const size_t per = (size_t)pw.wc * pw.hc * RBT_CTBSSE_WORDS;
+    if (d.gop != 2 || d.w != pw.W || d.h != pw.H) { j.err = "internal: a patch target does not fit its stream"; return RBT_ERR_PARAM; }
+    for (size_t i = 0; i < c.pass.frames.size(); i++) {
+      const PatchFrame& F = pw.frames[(size_t)c.pass.frames[i]];
+      RbtFoldJob J; memset(&J, 0, sizeof(J));
+      for (int k = 0; k < d.gop; k++, pic++, ctb_at += per) {
+        const RbtSsePic& S = r.sse->pics[pic]; RbtCtbSsePic P; memset(&P, 0, sizeof(P));
+        P.a = S.a[0]; P.b = S.b[0]; P.occ = S.occ; P.w = S.w; P.h = S.h; P.a_stride = S.a_stride; P.b_stride = S.b_stride; P.ow = S.ow; P.scale = S.scale;
+        P.log2_ctb = pw.l2; P.w_ctb = pw.wc; P.h_ctb = pw.hc; P.out = eb.d_ctb_words + ctb_at;
+        if (k < 2) J.ctb[k] = P.out;
+        cs.pics.push_back(P);
+      }
+      J.rects = pw.d_rects + 4 * F.rect_off; J.n_rects = (int)F.samples.size(); J.w_ctb = pw.wc; J.h_ctb = pw.hc; J.out = eb.d_sums + fold_at;
+      fold_at += ((size_t)J.n_rects + 2) * RBT_CTBSSE_WORDS;
+      cs.jobs.push_back(J); cs.max_rects = std::max(cs.max_rects, J.n_rects); cs.max_ctbs = std::max(cs.max_ctbs, pw.wc * pw.hc);
+    }
+  }
+  if (cs.pics.empty()) { r.ctbsse.reset(); return 0; }
+  if (fold_at > eb.n_sums || ctb_at > eb.n_ctb_words) { j.err = "internal: the sums per patch do not fit the round's arena"; return RBT_ERR_PARAM; }
+  if (int rc = cs.upload()) { j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
   return 0;
 }
 static int launch_round(GofJob& j, int gi) {
@@ -916,6 +1057,11 @@ static int launch_round(GofJob& j, int gi) {
   r.eb.reset(new EncodeBatch()); EncodeBatch& eb = *r.eb;
   int rc = round_fill_batch(j, gi, r.cands, eb);
   if (sums) for (const EncStreamDesc& d : eb.desc) eb.n_sums += (size_t)d.n_frames * RBT_SSE_WORDS;
+  for (size_t e = 0; e < r.cands.size() && !rc; e++) if (r.cands[e].pw >= 0) {      // floors held patch by patch: the folds behind the words per picture, the words per CTB
+    const PatchWalks& pw = r.pwalks[(size_t)r.cands[e].pw];
+    for (int f : r.cands[e].pass.frames) eb.n_sums += (pw.frames[(size_t)f].samples.size() + 2) * RBT_CTBSSE_WORDS;
+    eb.n_ctb_words += (size_t)eb.desc[e].n_frames * pw.wc * pw.hc * RBT_CTBSSE_WORDS;
+  }
   if (!rc && (rc = encode_build(eb)) != 0) j.err = eb.err;
   if (!rc && sums) rc = round_sums_setup(j, gi);
   if (!rc && (rc = encode_upload_lists(eb)) != 0) j.err = eb.err;
@@ -923,6 +1069,7 @@ static int launch_round(GofJob& j, int gi) {
   encode_launch_intra(eb); encode_launch_entropy_intra(eb); encode_launch_inter(eb);
   if (!eb.hash.empty()) eb.hash.launch();
   if (sums) r.sse->launch();
+  if (r.ctbsse) r.ctbsse->launch();
   encode_launch_entropy_rest(eb);
   return 0;
 }
@@ -1219,9 +1366,30 @@ static int finish_round(GofJob& j, int gi) {
   RoundPipe& r = j.pipes[gi]; std::vector<std::vector<uint8_t>> outs;
   rbtk::set_stream(job_stream(j, gi));
   if (int rc = encode_finish(*r.eb, outs, j.st)) { j.err = r.eb->err; return rc; }
-  size_t at = 0;                                                    // (the words came back with the slice sizes)
+  size_t at = 0, fold_at = 0;                                       // (the words came back with the slice sizes)
+  for (const EncStreamDesc& d : r.eb->desc) fold_at += (size_t)d.n_frames * RBT_SSE_WORDS;      // the folds per patch lie behind the words per picture
   for (size_t e = 0; e < r.cands.size(); e++) {
     const EncStreamDesc& d = r.eb->desc[e]; const RoundCand& c = r.cands[e]; QualitySums sums;
+    if (c.pw >= 0) {      // a pass of patch walks: every frame it carried keeps this trial - NAL units, sums, folds, map - and takes the walk's step on it
+      PatchWalks& pw = r.pwalks[(size_t)c.pw]; const int region = j.patch[pw.entry].t.region; const size_t per = (size_t)pw.wc * pw.hc;
+      for (size_t i = 0; i < c.pass.frames.size(); i++) {
+        const size_t f = (size_t)c.pass.frames[i]; PatchFrame& F = pw.frames[f]; const size_t np = F.samples.size();
+        frame_cut(outs[e], r.eb->pic_at[e], i, (size_t)d.gop, F.stream);
+        F.sums = QualitySums();
+        for (int k = 0; k < d.gop; k++, at++) quality_add_picture(F.sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
+        const uint64_t* w = &r.eb->sums[fold_at]; fold_at += (np + 2) * RBT_CTBSSE_WORDS;
+        F.ps.assign(np, PatchSums()); std::vector<double> fig(np); std::vector<char> meets(np);
+        for (size_t k = 0; k < np; k++) {
+          PatchSums& s = F.ps[k]; s.sse = w[3 * k]; s.sse_occ = w[3 * k + 1]; s.samples_occ = w[3 * k + 2]; s.samples = F.samples[k];
+          fig[k] = patch_figure(s, region, pw.bit_depth); meets[k] = patch_meets(s, region, F.w.floor_mdb[k], pw.bit_depth);
+        }
+        for (int k = 0; k < 3; k++) F.bg[k] = w[3 * np + k];
+        F.map.assign(c.qmap.begin() + (ptrdiff_t)(per * f), c.qmap.begin() + (ptrdiff_t)(per * (f + 1)));
+        patch_walk_step(F.w, fig.data(), meets.data());
+      }
+      pw.n_passes++;
+      continue;
+    }
     if (c.fw >= 0) {      // a pass: every frame it carried goes to its own walk - its NAL units and the sums of its pictures
       FrameWalks<TargetWalk>& fw = r.fwalks[c.fw];
       std::vector<rbt_d1_result> clouds;                               // a D1 target: the clouds of the frames the pass carried, in pass order
@@ -1247,7 +1415,7 @@ static int finish_round(GofJob& j, int gi) {
     if (c.walk < 0) { r.o1[c.q].swap(outs[e]); r.sums[c.q] = sums; r.d1[c.q].swap(frames); r.color[c.q].swap(cframes); }
     else { TargetTried& t = r.walks[c.walk].tried[c.qp]; t.stream.swap(outs[e]); t.sums = sums; t.d1.swap(frames); t.color.swap(cframes); r.n_enc[c.walk]++; }
   }
-  r.eb.reset(); r.sse.reset();
+  r.eb.reset(); r.sse.reset(); r.ctbsse.reset();
   name_round(j, gi, r, false);
   return 0;
 }
@@ -1324,6 +1492,31 @@ static void fill_frame_results(GofJob& j, int gi) {
     }
   }
 }
+// ... and of a pipeline whose entries walked patch by patch: per frame its trials, bytes, background and the picks of its settling trial; the final map; the stream assembled
+// from the frames' NAL units (rule 7). The entries without a target keep their only encode (r.o1) and its sums
+static void fill_patch_results(GofJob& j, int gi) {
+  RoundPipe& r = j.pipes[gi]; const std::vector<int>& gs = j.groups[gi];
+  j.pout.resize(j.n);
+  for (size_t q = 0; q < gs.size(); q++) if (!has_patch_floor(j, gs[q])) { PatchFloorOut& o = j.pout[gs[q]]; o.q0 = j.params[gs[q]].qp; o.bytes = r.o1[q].size(); o.sums = r.sums[q]; o.bit_depth = entry_bit_depth(j, gi, q); }
+  for (const PatchWalks& pw : r.pwalks) {
+    PatchFloorOut& o = j.pout[pw.entry]; std::vector<uint8_t>& out = r.o1[pw.q]; const int region = j.patch[pw.entry].t.region;
+    out.clear(); o.n_passes = pw.n_passes; o.wc = pw.wc; o.hc = pw.hc; o.bit_depth = pw.bit_depth;
+    for (const PatchFrame& F : pw.frames) {
+      out.insert(out.end(), F.stream.begin(), F.stream.end()); o.map.insert(o.map.end(), F.map.begin(), F.map.end());
+      o.q0 = F.w.q0; o.pictures += 2 * (uint64_t)F.w.n_trials;
+      rbt_patch_frame pf; memset(&pf, 0, sizeof(pf));
+      pf.n_trials = F.w.n_trials; pf.met = 1; pf.n_patches = (int)F.ps.size(); pf.bytes = F.stream.size();
+      for (int k = 0; k < 3; k++) pf.background[k] = F.bg[k];
+      for (size_t k = 0; k < F.ps.size(); k++) {
+        const PatchSums& s = F.ps[k]; pf.met &= F.w.met[k];
+        o.picks.push_back(rbt_patch_pick{F.w.q[k], F.w.met[k], F.w.failed[k], region ? s.sse_occ : s.sse, region ? s.samples_occ : s.samples, F.w.figure[k]});
+      }
+      o.frames.push_back(pf);
+      for (int c = 0; c < 3; c++) { o.sums.sse[c] += F.sums.sse[c]; o.sums.samples[c] += F.sums.samples[c]; o.sums.sse_occ[c] += F.sums.sse_occ[c]; o.sums.samples_occ[c] += F.sums.samples_occ[c]; }
+    }
+    o.bytes = out.size();
+  }
+}
 // A pipeline with targets, in the wait half: its decoder is collected, the walks are seeded and the rounds run, one after the other, until every walk has settled. In a
 // job with floors the occupancy pipelines have been collected by then (gof_wait), so the pooled planes and the maps the rounds read are complete. (Measured and not
 // adopted, DESIGN.md 12: the rounds of a job's pipelines side by side, and the first rounds of the other jobs in flight enqueued ahead of their turn - both were slower
@@ -1333,7 +1526,8 @@ static int run_rounds(GofJob& j, int gi) {
   if (int rc = pipeline_decoded(j, gi)) return rc;
   D1Live d1_live{j, gi};                                            // (releases the pipeline's frames and reference clouds on every way out)
   ColorLive color_live{j, gi};                                      // (releases the frames of the pipeline's colour entries on every way out)
-  if (j.per_frame) seed_frame_floors(j, gi, r);
+  if (!j.patch.empty()) { if (int rc = seed_patch_walks(j, gi, r)) return rc; }
+  else if (j.per_frame) seed_frame_floors(j, gi, r);
   else if (j.kind == GOF_D1) seed_floors(j, gi, r, WALK_D1);
   else if (j.kind == GOF_COLOR) seed_floors(j, gi, r, WALK_COLOR);
   else if (j.kind == GOF_QUALITY) seed_floors(j, gi, r, WALK_PSNR);
@@ -1349,6 +1543,8 @@ static int run_rounds(GofJob& j, int gi) {
   }
   for (const TargetWalk& w : r.walks) if (!w.settled) { j.err = "internal: QP walk did not settle"; return RBT_ERR_PARAM; }
   for (const FrameWalks<TargetWalk>& fw : r.fwalks) if (!fw.settled()) { j.err = "internal: QP walk did not settle"; return RBT_ERR_PARAM; }
+  for (const PatchWalks& pw : r.pwalks) if (!pw.settled()) { j.err = "internal: patch walk did not settle"; return RBT_ERR_PARAM; }
+  if (!j.patch.empty()) { fill_patch_results(j, gi); return 0; }
   if (j.per_frame) { fill_frame_results(j, gi); return 0; }
   fill_results(j, gi);
   for (TargetWalk& w : r.walks) r.o1[w.q].swap(w.tried[w.qstar].stream);
@@ -1558,7 +1754,7 @@ GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   GofJob* J = new GofJob(); GofJob& j = *J;
   const int n = r.n; const rbt_stream_params* p = r.params;
   j.per_frame = r.per_frame && (r.quality || r.d1);
-  j.kind = r.color ? GOF_COLOR : r.d1 ? (j.per_frame ? GOF_D1_FRAMES : GOF_D1) : r.quality ? (j.per_frame ? GOF_QUALITY_FRAMES : GOF_QUALITY) : GOF_PLAIN;
+  j.kind = r.patch_floors ? GOF_QUALITY_PATCHES : r.color ? GOF_COLOR : r.d1 ? (j.per_frame ? GOF_D1_FRAMES : GOF_D1) : r.quality ? (j.per_frame ? GOF_QUALITY_FRAMES : GOF_QUALITY) : GOF_PLAIN;
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
   j.params.assign(p, p + n); j.n_in.assign(r.n_in, r.n_in + n);
@@ -1568,12 +1764,17 @@ GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   if (r.quality) { j.qtargets.assign(r.quality, r.quality + n); j.qocc.assign(n, QualityOcc()); }
   if (r.d1) keep_cloud_targets(j, j.d1, *r.d1);
   if (r.color) keep_cloud_targets(j, j.color, *r.color);
+  if (r.patch_floors) {      // runs as a job with quality floors that are all 0, in each entry's region
+    j.patch = *r.patch_floors; j.qocc.assign(n, QualityOcc());
+    for (int i = 0; i < n; i++) j.qtargets.push_back(rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, j.patch[i].t.region, 0, 0});
+  }
   SubmitPlan s; s.in = r.in; s.p = p; s.gof_rule = r.gof_rule;
   int rc = plan_pipelines(j, s, depth);
   j.t_gpu = now_ms();
   if (!rc) rc = build_decoders(j, s);
   if (!rc) rc = check_frame_qp(j);
   if (!rc) rc = check_qp_maps(j);
+  if (!rc) rc = check_patch_floors(j);
   if (!rc) rc = build_encoders(j, s);
   if (!rc) rc = launch_merged(j);
   // enqueue order: longest pipeline first - except that a pipeline whose occupancy maps others wait for goes in front of them (an event has to be recorded before it is waited for)
@@ -1608,7 +1809,7 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResult
   const int n = j.n, ng = j.ng; int rc = j.rc;
   rbt_stats& st = j.st; std::string& err = j.err;
   std::vector<DecodeBatch>& db = j.db; std::vector<EncodeBatch>& eb = j.eb; const rbt_stream_params* p = j.params.data();
-  for (int i = 0; i < n; i++) { out[i] = nullptr; n_out[i] = 0; if (d1results) memset(&d1results[i], 0, sizeof(d1results[i])); if (cresults) memset(&cresults[i], 0, sizeof(cresults[i])); }
+  for (int i = 0; i < n; i++) { out[i] = nullptr; n_out[i] = 0; if (d1results) memset(&d1results[i], 0, sizeof(d1results[i])); if (cresults) memset(&cresults[i], 0, sizeof(cresults[i])); if (res.patches) memset(&res.patches[i], 0, sizeof(res.patches[i])); }
   std::vector<std::vector<uint8_t>> outs(n);
   // a job with quality floors: the pipelines that were encoded at submit first - its occupancy pipelines, whose pooled planes and maps the others' rounds read -, then those
   // that are encoded here; every other job has one pass
@@ -1664,6 +1865,26 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResult
     }
   }
   if (fresults && rc) { for (int i = 0; i < n; i++) { free(fresults[i].frames); free(fresults[i].d1); memset(&fresults[i], 0, sizeof(fresults[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; } }
+  if (rbt_patch_floor_result* pres = res.patches) {
+    for (int i = 0; i < n; i++) memset(&pres[i], 0, sizeof(pres[i]));
+    for (int i = 0; i < n && !rc; i++) {
+      rbt_patch_floor_result& o = pres[i];
+      o.qp_probe = p[i].qp; o.met_all = 1; o.bytes = (uint64_t)n_out[i];
+      quality_fill_result(o.sums, -1, -1, -1, 1, j.is_pass[i] ? 0 : 1, o.bytes, QualitySums(), 8);
+      if (i >= (int)j.pout.size() || j.is_pass[i] || p[i].video_type == RBT_VIDEO_OCCUPANCY) continue;
+      const PatchFloorOut& r = j.pout[i];
+      if (r.frames.empty()) { quality_fill_result(o.sums, -1, -1, -1, 1, 1, o.bytes, r.sums, r.bit_depth); continue; }
+      o.n_frames = (int)r.frames.size(); o.qp_probe = r.q0; o.n_passes = r.n_passes; o.pictures_encoded = r.pictures; o.w_ctb = r.wc; o.h_ctb = r.hc;
+      for (const rbt_patch_frame& f : r.frames) o.met_all &= f.met;
+      quality_fill_result(o.sums, -1, -1, -1, o.met_all, (int)(r.pictures / 2), o.bytes, r.sums, r.bit_depth);
+      o.map = (int8_t*)malloc(std::max<size_t>(1, r.map.size())); o.frames = (rbt_patch_frame*)malloc(sizeof(rbt_patch_frame) * r.frames.size());
+      o.picks = (rbt_patch_pick*)malloc(sizeof(rbt_patch_pick) * std::max<size_t>(1, r.picks.size()));
+      if (!o.map || !o.frames || !o.picks) { rc = RBT_ERR_NOMEM; break; }
+      memcpy(o.map, r.map.data(), r.map.size()); memcpy(o.frames, r.frames.data(), sizeof(rbt_patch_frame) * r.frames.size()); memcpy(o.picks, r.picks.data(), sizeof(rbt_patch_pick) * r.picks.size());
+      size_t at = 0; for (int f = 0; f < o.n_frames; f++) { o.frames[f].patches = o.picks + at; at += (size_t)o.frames[f].n_patches; }
+    }
+    if (rc) for (int i = 0; i < n; i++) { free(pres[i].map); free(pres[i].frames); free(pres[i].picks); memset(&pres[i], 0, sizeof(pres[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; }
+  }
   if (d1results) rc = cloud_results(j, rc, j.d1, j.d1out, d1results, out, n_out, [](rbt_d1_floor_result& o, const rbt_d1_result* f) { d1_stats(f, o.n_frames, &o.mean_d1, &o.min_d1); });
   if (cresults) rc = cloud_results(j, rc, j.color, j.colorout, cresults, out, n_out, [](rbt_color_floor_result& o, const rbt_color_result* f) { color_stats(f, o.n_frames, o.mean_psnr, o.min_psnr); });
   // SURVEY.md 8(d) algorithmic traffic: per coded picture of S samples (2 bytes each): decode writes S, P pictures read
@@ -1789,6 +2010,56 @@ int picture_sse_host(std::string& err, const uint16_t* a, const uint16_t* b, int
   if (rc) { err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
   st.gpu_ms = rbtk::timer_ms(T_CENSUS);
   memcpy(out, set.words.data(), set.words.size() * 8);
+  return 0;
+}
+
+// rbt_ctb_sse: the pictures laid out as picture_sse_host lays them out, the rectangles and the two tables behind them; the words per CTB and, with out_rect, the folded
+// triples of every pair of pictures come back
+int ctb_sse_host(std::string& err, const uint16_t* a, const uint16_t* b, int w, int h, int n_frames, int log2_ctb, const uint16_t* occ, int ow, int oh, const int32_t* rects, int n_rects,
+                 uint64_t* out_ctb, uint64_t* out_rect, rbt_stats& st) {
+  memset(&st, 0, sizeof(st));
+  if (w <= 0 || h <= 0 || w % 2 || h % 2 || w > 8192 || h > 8192 || n_frames < 1) { err = "picture size must be even and at most 8192"; return RBT_ERR_PARAM; }
+  if (occ && (ow <= 0 || oh <= 0 || w % ow || h % oh || w / ow != h / oh)) { err = "the occupancy map's scale must be whole and the same in both directions"; return RBT_ERR_PARAM; }
+  if (log2_ctb < 4 || log2_ctb > 6) { err = "log2_ctb must be 4..6"; return RBT_ERR_PARAM; }
+  if (n_rects < 0 || (n_rects > 0 && !rects)) { err = "n_rects rectangles need a list"; return RBT_ERR_PARAM; }
+  if (out_rect && n_frames % 2) { err = "sums per rectangle are taken over pairs of pictures: n_frames must be even"; return RBT_ERR_PARAM; }
+  const int wc = (w + (1 << log2_ctb) - 1) >> log2_ctb, hc = (h + (1 << log2_ctb) - 1) >> log2_ctb;
+  for (int k = 0; k < n_rects; k++) {
+    const int32_t* r = rects + 4 * k;
+    if (r[0] < 0 || r[1] < 0 || r[2] > wc || r[3] > hc || r[0] > r[2] || r[1] > r[3]) { err = "rectangle " + std::to_string(k) + " is outside the grid of " + std::to_string(wc) + " x " + std::to_string(hc) + " CTBs"; return RBT_ERR_PARAM; }
+  }
+  const size_t ys = (size_t)w * h, cs = (size_t)(w / 2) * (h / 2), fs = ys + 2 * cs, os = occ ? (size_t)ow * oh : 0, nf = (size_t)n_frames, nc = (size_t)wc * hc;
+  const size_t n_jobs = out_rect ? nf / 2 : 0, trip = (size_t)n_rects + 2;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t blk = up(fs * 2 * nf), o_occ = 2 * blk, o_rects = up(o_occ + os * 2 * nf), o_pics = up(o_rects + (size_t)n_rects * 16), o_jobs = up(o_pics + nf * sizeof(RbtCtbSsePic));
+  const size_t o_ctb = up(o_jobs + n_jobs * sizeof(RbtFoldJob)), o_fold = up(o_ctb + nf * nc * 24), end = o_fold + n_jobs * trip * 24;
+  uint8_t* buf = (uint8_t*)rbtk::dev_alloc(end);
+  if (!buf) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  struct G { void* p; ~G() { rbtk::dev_free(p); } } g{buf};
+  std::vector<uint8_t> staging(o_ctb, 0);
+  memcpy(staging.data(), a, fs * 2 * nf); memcpy(staging.data() + blk, b, fs * 2 * nf);
+  if (occ) memcpy(staging.data() + o_occ, occ, os * 2 * nf);
+  if (n_rects) memcpy(staging.data() + o_rects, rects, (size_t)n_rects * 16);
+  for (size_t k = 0; k < nf; k++) {
+    RbtCtbSsePic P; memset(&P, 0, sizeof(P));
+    P.a = (const uint16_t*)buf + fs * k; P.b = (const uint16_t*)(buf + blk) + fs * k; P.w = w; P.h = h; P.a_stride = P.b_stride = w;
+    if (occ) { P.occ = (const uint16_t*)(buf + o_occ) + os * k; P.ow = ow; P.scale = w / ow; }
+    P.log2_ctb = log2_ctb; P.w_ctb = wc; P.h_ctb = hc; P.out = (uint64_t*)(buf + o_ctb) + k * nc * 3;
+    memcpy(staging.data() + o_pics + k * sizeof(P), &P, sizeof(P));
+  }
+  for (size_t f = 0; f < n_jobs; f++) {
+    RbtFoldJob J; memset(&J, 0, sizeof(J));
+    for (int p = 0; p < 2; p++) J.ctb[p] = (const uint64_t*)(buf + o_ctb) + (2 * f + p) * nc * 3;
+    J.rects = (const int32_t*)(buf + o_rects); J.n_rects = n_rects; J.w_ctb = wc; J.h_ctb = hc; J.out = (uint64_t*)(buf + o_fold) + f * trip * 3;
+    memcpy(staging.data() + o_jobs + f * sizeof(J), &J, sizeof(J));
+  }
+  if (rbtk::h2d(buf, staging.data(), staging.size())) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  rbtk::timer_begin(T_CENSUS);      // (the census timer's events: no census runs inside this call)
+  rbtk::launch_ctb_sse((const RbtCtbSsePic*)(buf + o_pics), n_frames, (int)nc);
+  if (n_jobs) rbtk::launch_patch_fold((const RbtFoldJob*)(buf + o_jobs), (int)n_jobs, n_rects);
+  rbtk::timer_end(T_CENSUS);
+  if (rbtk::d2h(out_ctb, buf + o_ctb, nf * nc * 24) || (n_jobs && rbtk::d2h(out_rect, buf + o_fold, n_jobs * trip * 24))) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  st.gpu_ms = rbtk::timer_ms(T_CENSUS);
   return 0;
 }
 

@@ -10,6 +10,9 @@ struct PCloud; struct PCloudCache;
 // entry resolved to the clouds (n_frames of them, nullptr = the cloud of the decoded input), and the context's cache of cloud volumes
 template <class Target> struct CloudRequest { const Target* targets = nullptr; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache = nullptr; };
 struct QpMapIn { std::vector<int8_t> qp; int n_frames = 0, w_ctb = 0, h_ctb = 0; };
+// PSNR floors held patch by patch (rbt_submit_gof_quality_patches), one per entry, checked and copied by the caller: the target without its pointers (n_frames 0: no target),
+// per frame the patches and their floors F_k
+struct PatchFloorIn { rbt_patch_floor_target t; std::vector<std::vector<rbt_patch>> patches; std::vector<std::vector<int32_t>> floors; };
 // What a job is made of: the n inputs with their parameters, and at most one kind of target - each nullptr or one per entry, checked by the caller
 struct GofRequest {
   int n = 0; const uint8_t* const* in = nullptr; const size_t* n_in = nullptr; const rbt_stream_params* params = nullptr;
@@ -25,16 +28,17 @@ struct GofRequest {
   // a QP per CTB (rbt_submit_gof_qp_map; struct sizes, values and video types checked by the caller, the counts against the stream's pictures here: gof_refused), an empty qp =
   // the entry's own QP; not together with anything else
   const std::vector<QpMapIn>* qp_maps = nullptr;
+  const std::vector<PatchFloorIn>* patch_floors = nullptr;   // PSNR floors held patch by patch (rbt_submit_gof_quality_patches); not together with anything else
 };
 // Where a job's outcome goes: a stream per entry, and of the result arrays - one per entry each - the one of the job's kind; n_flat: nullptr, or the decoded pictures with flat chroma
 struct GofResults {
   uint8_t** out = nullptr; size_t* n_out = nullptr; int* n_flat = nullptr;
-  rbt_rate_result* rate = nullptr; rbt_quality_result* quality = nullptr; rbt_d1_floor_result* d1 = nullptr; rbt_color_floor_result* color = nullptr; rbt_frame_floor_result* frames = nullptr;
+  rbt_rate_result* rate = nullptr; rbt_quality_result* quality = nullptr; rbt_d1_floor_result* d1 = nullptr; rbt_color_floor_result* color = nullptr; rbt_frame_floor_result* frames = nullptr; rbt_patch_floor_result* patches = nullptr;
 };
 GofJob* gof_submit(int slot, int depth, const GofRequest& r);
 int gof_wait(GofJob* j, rbt_stats& st, std::string& err, const GofResults& r);   // consumes the job
 // which submit made the job, in the order the wait half tells a mismatch (rbt_api.cpp wait): the lower of two kinds that differ is the one the message names
-enum GofKind { GOF_PLAIN, GOF_QUALITY, GOF_D1, GOF_COLOR, GOF_D1_FRAMES, GOF_QUALITY_FRAMES };   // GOF_PLAIN: constant QPs, QP lists, QP maps and byte budgets
+enum GofKind { GOF_PLAIN, GOF_QUALITY, GOF_D1, GOF_COLOR, GOF_D1_FRAMES, GOF_QUALITY_FRAMES, GOF_QUALITY_PATCHES };   // GOF_PLAIN: constant QPs, QP lists, QP maps and byte budgets
 GofKind gof_kind(const GofJob* j);
 int gof_refused(const GofJob* j, std::string& err);   // != 0: the job's plan was refused before anything was built or enqueued (the code; the reason in err)
 void gof_abandon(GofJob* j);
@@ -43,6 +47,8 @@ int encode_yuv(rbt_stats& st, std::string& err, const uint16_t* yuv, int w, int 
 int or_pool_host(const uint16_t* plane, int w, int h, int factor, uint16_t* out);
 int level_census_host(std::string& err, const int16_t* y, const int16_t* cb, const int16_t* cr, int w, int h, const int8_t* qp4, const uint8_t* pm4, uint32_t* hist);   // rbt_level_census
 int picture_sse_host(std::string& err, const uint16_t* a, const uint16_t* b, int w, int h, int n_frames, const uint16_t* occ, int ow, int oh, uint64_t* out, rbt_stats& st);   // rbt_picture_sse; st.gpu_ms: device time between events around the launches
+int ctb_sse_host(std::string& err, const uint16_t* a, const uint16_t* b, int w, int h, int n_frames, int log2_ctb, const uint16_t* occ, int ow, int oh, const int32_t* rects, int n_rects,
+                 uint64_t* out_ctb, uint64_t* out_rect, rbt_stats& st);   // rbt_ctb_sse; st.gpu_ms as picture_sse_host's
 int rate_estimate(std::string& err, const uint8_t* annexb, size_t n, rbt_rate_table* out);   // rbt_rate_estimate
 int picture_hash_host(std::string& err, const uint16_t* yuv, int w, int h, int bd, int n_frames, int kind, uint8_t* out);   // rbt_picture_hash
 }

@@ -1,0 +1,159 @@
+// TEST-ONLY: the walk of the PSNR floors held patch by patch (host/rbt_patch_walk.h) and the bodies of the sums per CTB and per patch (csrc/rbt_ctbsse.h) as a stand-alone
+// host program, so that they can be built with -fsanitize=address,undefined and run on the CPU (tests/test_patch_floor.py).
+//   walk    driven trial by trial the way finish_round drives it, over synthetic figure functions of the QP vector - monotone, not monotone, and coupled (a patch's figure
+//           depends on its neighbours' QPs through the minimum a shared CTB takes) -, 1 to 40 patches, random floors, ranges and starts. Checked: it ends within the sum over
+//           the patches of (hi - q0) + (hi - lo) + 1 trials; no patch rises after it failed; the result is the last trial's vector; met is what the last figures say; without
+//           a cap every patch meets or sits at lo; a cap is honoured
+//   bodies  ctbsse_ctb and ctbsse_fold against a per-sample serial restatement: the shapes of the tests, CTBs of 16, 32 and 64, every pair of misalignments of the two
+//           pictures for the 130-wide one, strides that are not the width, maps of scale 1, 2 and 4, the extremes at 10 and 16 bits. The planes are views into heap blocks
+//           that end with the last sample of the last row, and the outputs are exact-size blocks: a read past a row's end, a misaligned 16-byte load or a store past the
+//           words is caught
+// Prints "ok".
+#define RBT_HOSTEMU 1
+#include <stdio.h>
+#include <stdlib.h>
+#include <vector>
+#include "../rabbit-transcoding_amd/csrc/rbt_ctbsse.h"
+#include "../rabbit-transcoding_amd/host/rbt_patch_walk.h"
+
+static int fail(const char* what, long a = 0, long b = 0, long c = 0) { printf("FAIL %s %ld %ld %ld\n", what, a, b, c); fflush(stdout); return 1; }
+static uint32_t g_seed = 97531;
+static uint32_t rnd() { g_seed = g_seed * 1664525u + 1013904223u; return g_seed >> 8; }
+
+// ------------------------------------------------------------------------------------------------ walk
+enum { MONOTONE, BUMPY, COUPLED };
+// the figure of patch k under the vector q: about a dB per QP step below base[k]
+static double figure_of(int kind, const std::vector<int>& q, const std::vector<double>& base, size_t k) {
+  const size_t n = q.size();
+  if (kind == MONOTONE) return base[k] - 0.9 * q[k];
+  if (kind == BUMPY) return base[k] - 0.9 * q[k] + 1.7 * ((q[k] * 7 + (int)k) % 5 == 0) - 1.3 * ((q[k] + 2 * (int)k) % 7 == 0);      // inversions of more than a step
+  const int l = k > 0 ? std::min(q[k], q[k - 1]) : q[k], r = k + 1 < n ? std::min(q[k], q[k + 1]) : q[k];                               // shared CTBs take the lower QP
+  return base[k] - 0.9 * (2 * q[k] + l + r) / 4.0 - 0.4 * (k > 0 && q[k - 1] > q[k] + 6);                                              // ... and a coarse neighbour bleeds in
+}
+static int walk_case(int kind, int n, int qp, int lo, int hi, int cap) {
+  std::vector<double> base(n); std::vector<int32_t> floors(n);
+  for (int k = 0; k < n; k++) { base[k] = 60.0 + (rnd() % 16000) / 1000.0; floors[k] = (int32_t)(25000 + rnd() % 30000); }
+  if (n > 2) floors[1] = 0;                 // a patch without a floor climbs to hi
+  if (n > 3) floors[2] = 120000;            // one nothing reaches ends at lo
+  rbt::PatchWalk w; rbt::patch_walk_seed(w, qp, lo, hi, cap, floors);
+  const int q0 = qp < lo ? lo : qp > hi ? hi : qp;
+  if (w.q0 != q0 || (int)w.q.size() != n) return fail("seed", qp, w.q0, q0);
+  for (int k = 0; k < n; k++) if (w.q[k] != q0) return fail("trial 0 is not q0", k, w.q[k], q0);
+  const long bound = (long)n * ((hi - q0) + (hi - lo) + 1) + 1;      // (+ 1: a frame without patches takes its one trial)
+  std::vector<char> failed(n, 0), meets(n); std::vector<double> fig(n); std::vector<int> last;
+  for (long trial = 1;; trial++) {
+    if (trial > bound) return fail("walk does not end", kind, n, trial);
+    last = w.q;
+    for (int k = 0; k < n; k++) {
+      if (w.q[k] < lo || w.q[k] > hi) return fail("QP out of range", k, w.q[k]);
+      fig[k] = figure_of(kind, w.q, base, (size_t)k); meets[k] = fig[k] >= floors[k] / 1000.0;
+    }
+    const bool done = rbt::patch_walk_step(w, fig.data(), meets.data());
+    if (w.n_trials != trial || done != w.settled) return fail("trial count", w.n_trials, trial);
+    for (int k = 0; k < n; k++) {
+      if (failed[k] && w.q[k] > last[k]) return fail("a patch rises after it failed", k, last[k], w.q[k]);
+      failed[k] |= !meets[k];
+      if ((w.failed[k] != 0) != (failed[k] != 0)) return fail("failed flag", k, w.failed[k], failed[k]);
+    }
+    if (done) break;
+    if (w.q == last) return fail("a trial repeats", kind, n, trial);
+  }
+  if (w.q != last) return fail("the result is not the last trial", kind, n);
+  for (int k = 0; k < n; k++) {
+    if ((w.met[k] != 0) != (meets[k] != 0) || w.figure[k] != fig[k]) return fail("met is not the last figures'", k, w.met[k], meets[k]);
+    if (!cap && !w.met[k] && w.q[k] != lo) return fail("a patch neither meets nor sits at lo", k, w.q[k], lo);
+  }
+  if (cap && w.n_trials > cap) return fail("cap", w.n_trials, cap);
+  if (cap) {      // the same walk without the cap takes at least as long, and agrees with this one up to the cap
+    rbt::PatchWalk u; rbt::patch_walk_seed(u, qp, lo, hi, 0, floors); int t = 0;
+    for (;;) { for (int k = 0; k < n; k++) { fig[k] = figure_of(kind, u.q, base, (size_t)k); meets[k] = fig[k] >= floors[k] / 1000.0; }
+      last = u.q; t++; if (rbt::patch_walk_step(u, fig.data(), meets.data()) || t == cap) break; }
+    if (last != w.q || t != w.n_trials) return fail("capped walk is not the uncapped walk's prefix", t, w.n_trials);
+  }
+  return 0;
+}
+static int region_cases() {
+  int32_t r[4];
+  rbt::patch_region(96, 80, 16, 0, 0, 2, 2, 5, r); if (r[0] != 0 || r[1] != 0 || r[2] != 1 || r[3] != 1 || rbt::patch_region_samples(r, 96, 80, 5) != 2 * 32 * 32) return fail("region: ends on a CTB edge");
+  rbt::patch_region(96, 80, 16, 0, 0, 3, 2, 5, r); if (r[2] != 2 || r[3] != 1) return fail("region: one block more");
+  rbt::patch_region(96, 80, 16, 5, 4, 9, 9, 6, r); if (r[0] != 1 || r[1] != 1 || r[2] != 2 || r[3] != 2 || rbt::patch_region_samples(r, 96, 80, 6) != 2 * 32 * 16) return fail("region: clipped");
+  rbt::patch_region(96, 80, 16, 7, 7, 1, 1, 5, r); if (r[0] | r[1] | r[2] | r[3] || rbt::patch_region_samples(r, 96, 80, 5)) return fail("region: outside");
+  rbt::patch_region(96, 80, 16, -3, -2, 2, 1, 5, r); if (r[0] | r[1] | r[2] | r[3]) return fail("region: negative");
+  rbt::PatchSums s; if (!rbt::patch_meets(s, 0, 99000, 10) || rbt::patch_figure(s, 1, 10) != 0.0) return fail("no sample meets");
+  s.samples = 100; s.sse = 100; if (rbt::patch_meets(s, 0, 61000, 10) || !rbt::patch_meets(s, 1, 61000, 10) || !rbt::patch_meets(s, 0, 60000, 10)) return fail("meets");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ bodies
+struct Plane { uint16_t* mem = nullptr; uint16_t* p = nullptr; ~Plane() { free(mem); } };
+static void make_plane(Plane& P, int pw, int ph, int stride, int mis, int peak, int fill) {
+  const size_t n = (size_t)(ph - 1) * stride + pw;
+  P.mem = (uint16_t*)malloc((n + mis) * 2);                      // malloc's blocks start on a multiple of 16
+  if (!P.mem || ((uintptr_t)P.mem & 15)) { printf("FAIL malloc\n"); exit(1); }
+  P.p = P.mem + mis;
+  for (size_t i = 0; i < n; i++) P.p[i] = (uint16_t)(fill >= 0 ? fill : (int)(rnd() % (peak + 1)));
+}
+static int body_case(int w, int h, int l2, int a_stride, int b_stride, int mis_a, int mis_b, int scale, int peak, int extremes) {
+  const int ctb = 1 << l2, wc = (w + ctb - 1) / ctb, hc = (h + ctb - 1) / ctb; const size_t nc = (size_t)wc * hc;
+  Plane A[2], B[2]; RbtCtbSsePic P[2]; std::vector<uint16_t> occ[2];
+  std::vector<uint64_t*> words(2);
+  for (int p = 0; p < 2; p++) {
+    make_plane(A[p], w, h, a_stride, mis_a, peak, extremes ? 0 : -1); make_plane(B[p], w, h, b_stride, mis_b, peak, extremes ? peak : -1);
+    memset(&P[p], 0, sizeof(P[p]));
+    P[p].a = A[p].p; P[p].b = B[p].p; P[p].w = w; P[p].h = h; P[p].a_stride = a_stride; P[p].b_stride = b_stride; P[p].log2_ctb = l2; P[p].w_ctb = wc; P[p].h_ctb = hc;
+    if (scale) { occ[p].resize((size_t)(w / scale) * (h / scale)); for (auto& v : occ[p]) v = (uint16_t)(rnd() % 3 == 0 ? 0 : rnd() % 300 + 1); occ[p].back() = 1; P[p].occ = occ[p].data(); P[p].ow = w / scale; P[p].scale = scale; }
+    words[p] = (uint64_t*)malloc(nc * 24); memset(words[p], 0xA5, nc * 24); P[p].out = words[p];
+  }
+  rbtk::launch_ctb_sse(P, 2, (int)nc);
+  int bad = 0;
+  std::vector<uint64_t> want(2 * nc * 3, 0);
+  for (int p = 0; p < 2 && !bad; p++) {
+    for (int y = 0; y < h; y++) for (int x = 0; x < w; x++) {
+      const long long d = (long long)P[p].a[(size_t)y * a_stride + x] - (long long)P[p].b[(size_t)y * b_stride + x]; uint64_t* o = &want[(p * nc + (size_t)(y / ctb) * wc + x / ctb) * 3];
+      o[0] += (uint64_t)(d * d);
+      if (scale && occ[p][(size_t)(y / scale) * (w / scale) + x / scale] > 0) { o[1] += (uint64_t)(d * d); o[2]++; }
+    }
+    for (size_t i = 0; i < nc * 3; i++) if (words[p][i] != want[p * nc * 3 + i]) { bad = fail("ctb words", w, l2, (long)i); break; }
+  }
+  if (!bad && extremes && words[0][0] != (uint64_t)std::min(ctb, w) * std::min(ctb, h) * peak * peak) bad = fail("extremes", w, h, l2);
+  // folds: random rectangles, some overlapping, one empty, one single CTB; then the background and the whole frame
+  std::vector<int32_t> rects;
+  const int nr = 1 + (int)(rnd() % 5);
+  for (int k = 0; k < nr; k++) { const int c0 = (int)(rnd() % wc), r0 = (int)(rnd() % hc), c1 = c0 + (k == 1 ? 0 : 1 + (int)(rnd() % (wc - c0))), r1 = r0 + 1 + (int)(rnd() % (hc - r0)); rects.insert(rects.end(), {c0, r0, c1, r1}); }
+  int32_t* dr = (int32_t*)malloc(rects.size() * 4); memcpy(dr, rects.data(), rects.size() * 4);      // an exact-size block
+  uint64_t* folds = (uint64_t*)malloc((size_t)(nr + 2) * 24); memset(folds, 0xA5, (size_t)(nr + 2) * 24);
+  RbtFoldJob J; memset(&J, 0, sizeof(J)); J.ctb[0] = words[0]; J.ctb[1] = words[1]; J.rects = dr; J.n_rects = nr; J.w_ctb = wc; J.h_ctb = hc; J.out = folds;
+  rbtk::launch_patch_fold(&J, 1, nr);
+  for (int r = 0; r < nr + 2 && !bad; r++) {
+    uint64_t s[3] = {0, 0, 0};
+    for (int cy = 0; cy < hc; cy++) for (int cx = 0; cx < wc; cx++) {
+      bool in_any = false, in_r = false;
+      for (int k = 0; k < nr; k++) { const bool in = cx >= rects[4 * k] && cx < rects[4 * k + 2] && cy >= rects[4 * k + 1] && cy < rects[4 * k + 3]; in_any |= in; if (k == r) in_r = in; }
+      if (r < nr ? in_r : r == nr ? !in_any : true) for (int p = 0; p < 2; p++) for (int i = 0; i < 3; i++) s[i] += want[(p * nc + (size_t)cy * wc + cx) * 3 + i];
+    }
+    for (int i = 0; i < 3; i++) if (folds[3 * r + i] != s[i]) { bad = fail("fold", w, l2, r); break; }
+  }
+  free(dr); free(folds); for (int p = 0; p < 2; p++) free(words[p]);
+  return bad;
+}
+
+int main() {
+  if (region_cases()) return 1;
+  for (int kind = MONOTONE; kind <= COUPLED; kind++) for (int n = 0; n <= 40; n += (n < 6 ? 1 : 7)) for (int rep = 0; rep < 12; rep++) {
+    const int lo = (int)(rnd() % 30), hi = lo + (int)(rnd() % (52 - lo)), qp = (int)(rnd() % 52);
+    if (walk_case(kind, n, qp, lo, hi, 0)) return 1;
+    if (walk_case(kind, n, qp, lo, hi, 1 + (int)(rnd() % 4))) return 1;
+  }
+  for (int kind = MONOTONE; kind <= COUPLED; kind++) if (walk_case(kind, 40, 30, 0, 51, 0) || walk_case(kind, 1, 30, 30, 30, 0) || walk_case(kind, 5, 0, 0, 51, 0) || walk_case(kind, 5, 51, 0, 51, 0)) return 1;
+  // the shapes of the tests at every CTB size; strides that are not the width; every pair of misalignments for the 130-wide picture
+  const int sizes[][2] = {{96, 80}, {130, 66}, {264, 136}, {16, 16}, {18, 34}};
+  for (auto& sz : sizes) for (int l2 = 4; l2 <= 6; l2++) for (int scale : {0, 1, 2}) {
+    if (body_case(sz[0], sz[1], l2, sz[0], sz[0], 0, 0, scale, 1023, 0)) return 1;
+    if (body_case(sz[0], sz[1], l2, sz[0] + 6, sz[0] + 22, 2, 2, scale, 1023, 0)) return 1;
+    if (body_case(sz[0], sz[1], l2, sz[0] + 16, sz[0], 4, 0, scale, 255, 0)) return 1;
+  }
+  for (int ma = 0; ma < 8; ma++) for (int mb = 0; mb < 8; mb++) for (int l2 = 4; l2 <= 6; l2++) if (body_case(130, 66, l2, 130, 144, ma, mb, 2, 1023, 0)) return 1;
+  for (int l2 = 4; l2 <= 6; l2++) if (body_case(264, 136, l2, 264, 272, 0, 0, 4, 1023, 1) || body_case(264, 136, l2, 264, 264, 3, 3, 4, 65535, 1) || body_case(96, 80, l2, 96, 104, 0, 6, 4, 1023, 1)) return 1;
+  printf("ok\n");
+  return 0;
+}
