@@ -702,6 +702,30 @@ typedef struct rbt_score_pair rbt_score_pair;
 int rbt_score_pair_create(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, rbt_score_pair** out);
 int rbt_score_pair_color(rbt_ctx* ctx, const rbt_score_pair* pair, rbt_color_result* out);
 void rbt_score_pair_release(rbt_ctx* ctx, rbt_score_pair* pair);
+/* ---- D1 per patch of the decoded cloud (csrc/rbt_score.h) ----
+ * A is the reference cloud and B the decoded cloud. B carries a label L[j] in 0..P-1 per point: its patch index. Merging and representatives are rbt_score's, with the
+ * lowest point index of a voxel as representative. Per patch k, with exact integers:
+ *   B -> A   over the representatives j of B with L[j] = k: n_ba[k] counts them, sse_ba[k] is the sum of their nearest squared distances to A, max_ba[k] the maximum.
+ *   A -> B   every representative i of A has a nearest squared distance d_i to B. Its owner is the representative of B with the lowest point index among all merged
+ *            points of B at exactly distance d_i - rbt_score's tie set. n_ab[k], sse_ab[k] and max_ab[k] are taken over the i whose owner has label k. This holds for
+ *            any reference, uploaded or decoded input; A needs no labels.
+ *   figure   mse_*[k] = sse / n and psnr[k] = 10 log10(3 peak^2 / max(mse_ab, mse_ba)), from the one float routine rbt_d1 and rbt_score share. A direction without a
+ *            point has mse 0; a patch without a point in either direction has psnr +inf.
+ * The sums over k of sse_ab, sse_ba, n_ab and n_ba are rbt_score(a, b).d1's sse_ab, sse_ba, n_a and n_b; the maxima over k are its maxima.
+ * Labels: a cloud of rbt_pcloud_from_maps carries the patch index of every point (the index into `patches` of the patch that emitted it), with geometry smoothing on or
+ * off - smoothing moves points, it changes neither their order nor their patch. An uploaded cloud gets labels through rbt_pcloud_set_labels (one per point, in point
+ * order, each below 65536; the cloud keeps the labels it had when the call fails). rbt_pcloud_labels copies them out (n_points words); RBT_ERR_PARAM for a cloud without
+ * labels.
+ * rbt_score_patches: out receives n_patches entries. whole and device_ms may be NULL; whole is bit for bit rbt_score(a, b, peak, RBT_SCORE_D1).d1, device_ms the time
+ * between events around the two searches, the two D1 walks and the two per-patch kernels (k_pd_sums: integer atomics only, one per wave and word where a wave's labels are
+ * all the same, so the words do not depend on the order of arrival and two calls return the same bits). RBT_ERR_PARAM, with the reason in rbt_last_error and the context
+ * still usable: a handle of another context, b without labels, a label >= n_patches (a kernel checks the labels and reports through an error word before any sum is
+ * written), n_patches outside 1..65536, peak < 1.
+ * The closed loop on these figures: "D1 floors held patch by patch" below. Not built: colour figures per patch. */
+typedef struct { uint32_t n_ab, n_ba; uint64_t sse_ab, sse_ba, max_ab, max_ba; float mse_ab, mse_ba, psnr; } rbt_patch_d1;
+int rbt_pcloud_set_labels(rbt_ctx* ctx, rbt_pcloud* cloud, const uint32_t* labels);        /* one per point, < 65536 */
+int rbt_pcloud_labels(rbt_ctx* ctx, const rbt_pcloud* cloud, uint32_t* labels);            /* of rbt_pcloud_from_maps: the patch index; RBT_ERR_PARAM for a cloud without labels */
+int rbt_score_patches(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int n_patches, rbt_patch_d1* out, rbt_d1_result* whole, double* device_ms);
 /* Summary over the frames of a sequence, per figure (the symmetric PSNR of D1, D2, Y, U, V): arithmetic mean and minimum, in double, over the frames that carry that part
  * (n_d1 / n_d2 / n_color of them; 0 where there is none); a frame whose PSNR is +inf makes the mean +inf. The reference itself writes one line per frame and averages
  * nothing (PCCMetrics::write); the mean over the frames is what the CTC reporting forms from those lines. points_* / merged_*: sums over all frames. Host only. */
@@ -892,7 +916,7 @@ int rbt_qp_map_from_patches(const rbt_atlas_params* atlas, const rbt_patch* patc
  *    outside -1..51; a negative max_trials; a negative floor; a QP range or a region the PSNR floor refuses; a frame with patches but no list; a target on an occupancy
  *    entry. An entry without a target (n_frames 0, everything else 0) is coded at params[i].qp: n_frames 0, map and frames NULL, sums filled.
  * There is no container-level call and no rbt_pipeline option: the library does not parse the atlas sub-bitstream.
- * Not built: D1 and colour floors per patch, byte caps per patch, a caller's map together with a target, quantisation groups below the CTB. */
+ * Not built: colour floors per patch (D1 floors per patch: below), byte caps per patch, a caller's map together with a target, quantisation groups below the CTB. */
 typedef struct {
   uint32_t struct_size;                                        /* sizeof(rbt_patch_floor_target): checked */
   int32_t  min_psnr_mdb;  int region;  int qp_min, qp_max;     /* as rbt_quality_target */
@@ -929,6 +953,61 @@ int rbt_transcode_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const*
  * rbt_get_stats afterwards: gpu_ms = the device time between events around the two launches. */
 int rbt_ctb_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int width, int height, int n_frames, int log2_ctb, const uint16_t* occ, int ow, int oh,
                 const int32_t* rects, int n_rects, uint64_t* out_ctb, uint64_t* out_rect);
+
+/* ---- D1 floors held patch by patch (csrc/rbt_score.h, host/rbt_patch_walk.h) ----
+ * The PSNR floor per patch counts every sample of a CTB, although the occupancy map of the output decides which samples become points; the D1 floor per frame measures the
+ * right figure but moves one QP per frame, so a frame's worst patch dictates the QP of every other patch in it. Here every patch of every frame of a geometry entry walks
+ * to its own QP on its own D1 ("D1 per patch of the decoded cloud" above), and the result names the patch that sets a frame's D1.
+ *
+ * 1. Cloud and reference of a trial. Rules 1 - 4 of "transcoding geometry to a D1 floor", unchanged: the occupancy source, the shapes, B_f (the cloud of the trial's
+ *    reconstruction of frame f through the output atlas) and A_f (reference[f], or the cloud of the decoded input where that is NULL). atlas.map_count must be 2: a
+ *    point-cloud frame is the two pictures that are coded as a pair. B_f carries the labels of rbt_pcloud_from_maps: the index of the point's patch in the frame's list.
+ * 2. Figure. The figure of patch k of frame f in a trial is (double)psnr[k] of rbt_score_patches on (A_f, B_f(trial map)) with peak (0 = 1023). meets is
+ *    figure >= F_k / 1000.0; +inf meets (a patch that contributes no point and owns no reference point).
+ * 3. Trial map, walk, rounds, stream: rules 4 - 7 of "PSNR floors held patch by patch", word for word, with this figure (patch_walk_seed / patch_walk_step unchanged). A
+ *    round is one pass per entry over the unsettled frames with their trial maps; behind the pass the clouds of the frames it carried are built and scored one after the
+ *    other. The returned stream is byte for byte rbt_transcode_gof_qp_map's for the final map, assembled from the settling trials; no further encode runs. The walk moves a
+ *    patch by (int)(F_k - figure) QP steps, a model of 1 dB per step: that is poor for D1, which saturates where the quantisation error stays below half a depth level and
+ *    depends on the neighbours' points. This costs trials, not correctness: the walk is the definition, and the result is a map under which every patch meets or sits at lo.
+ * 4. Floor 0. With min_d1_mdb 0 and patch_min_d1_mdb NULL there is one trial at clamp(params[i].qp, 0, 51): every patch's rbt_patch_d1 is reported and met = 1.
+ * 5. Everything is copied at submit. A job is collected by rbt_wait_gof_d1_patches only; a wrong pairing is RBT_ERR_PARAM and leaves the job collectable. rbt_job_memory is
+ *    as in the D1 section. Refusals, all RBT_ERR_PARAM with a reason, nothing submitted, the context usable: those of the D1 section (no occupancy source, shapes that do
+ *    not fit, a foreign reference handle, a negative floor or peak, a bad QP range, a malformed patch list) and those of the patch-floor section (a wrong struct_size, an
+ *    odd picture count, n_frames that is not pictures / 2, an atlas size that is not the output pictures', a background_qp outside -1..51, a negative max_trials, a
+ *    negative patch floor, log2_ctb outside 4..6); a target on an attribute or occupancy entry; map_count other than 2; occupancy_rd together with verify_md5 as the PSNR
+ *    floor refuses it. An entry without a target (n_frames 0, everything else 0) is coded at params[i].qp: n_frames 0, map, frames and picks NULL.
+ * Not built: colour floors per patch, byte caps per patch, a caller's map together with a target, and a container-level call or rbt_pipeline option - the library does not
+ * parse the atlas sub-bitstream. */
+typedef struct {
+  uint32_t struct_size;                                        /* sizeof(rbt_patch_d1_target): checked */
+  int32_t  min_d1_mdb;  int peak;  int qp_min, qp_max;         /* as rbt_d1_target: floor in 1/1000 dB (0 = none), peak 0 = 1023, qp_max 0 = 51 */
+  int      background_qp;                                      /* 0..51, -1 = q0 */
+  int      max_trials;                                         /* 0 = no cap */
+  rbt_atlas_params atlas;                                      /* the OUTPUT atlas, as in rbt_d1_target */
+  int n_frames;  const rbt_patch* const* patches;  const int* n_patches;
+  const int32_t* const* patch_min_d1_mdb;                      /* NULL, or per frame NULL / one floor per patch: F_k; else F_k = min_d1_mdb */
+  const rbt_pcloud* const* reference;                          /* NULL, or n_frames handles: A_f; a NULL handle = the cloud of the decoded input */
+} rbt_patch_d1_target;
+typedef struct { int qp, met, failed; rbt_patch_d1 d1; double figure; } rbt_patch_d1_pick;   /* of the settling trial: q[k], met, failed[k], the patch's sums and figures, (double)d1.psnr */
+typedef struct {
+  int n_trials, met, n_patches;                                /* met = AND of patches[k].met */
+  uint64_t bytes;                                              /* the frame's NAL units in the returned stream, start codes included */
+  rbt_d1_result d1;                                            /* the whole frame's D1 in the settling trial: what rbt_score returns for (A_f, B_f) */
+  rbt_patch_d1_pick* patches;                                  /* n_patches picks: they point into rbt_patch_d1_result.picks */
+} rbt_patch_d1_frame;
+typedef struct {
+  int n_frames, qp_probe, met_all, n_passes;                   /* q0; met_all = AND of frames[f].met */
+  uint64_t bytes, pictures_encoded;                            /* size of the returned stream; 2 * sum of frames[f].n_trials */
+  int w_ctb, h_ctb;
+  int8_t* map;                                                 /* the final map, n_frames * h_ctb * w_ctb (malloc'd, rbt_free): rbt_transcode_gof_qp_map returns the same stream for it */
+  rbt_patch_d1_frame* frames;                                  /* n_frames (malloc'd, rbt_free) */
+  rbt_patch_d1_pick* picks;                                    /* every frame's picks back to back (malloc'd, rbt_free) */
+  double cloud_ms;                                             /* as rbt_d1_floor_result.cloud_ms, the per-patch kernels included */
+} rbt_patch_d1_result;
+int rbt_submit_gof_d1_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d1_target* targets, rbt_job** job);
+int rbt_wait_gof_d1_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_patch_d1_result* results);   /* results: n entries */
+int rbt_transcode_gof_d1_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d1_target* targets,
+                                 uint8_t** annexb_out, size_t* n_out, rbt_patch_d1_result* results);   /* submit + wait */
 
 /* ---- normal estimation (csrc/rbt_normals.h) ----
  * D2 needs normals on the source. Where a sequence comes without them, the reference's PccAppNormalGenerator makes them (PCCNormalsGenerator.cpp: a kd-tree query of the

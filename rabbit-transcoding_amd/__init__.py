@@ -82,6 +82,16 @@ class ColorResult(C.Structure):
 RBT_SCORE_D1, RBT_SCORE_D2, RBT_SCORE_COLOR = 1, 2, 4
 
 
+class PatchD1(C.Structure):
+    """rbt_patch_d1: the D1 sums and figures of one patch of the decoded cloud (rbt_score_patches)"""
+    _fields_ = [("n_ab", C.c_uint32), ("n_ba", C.c_uint32), ("sse_ab", C.c_uint64), ("sse_ba", C.c_uint64), ("max_ab", C.c_uint64), ("max_ba", C.c_uint64),
+                ("mse_ab", C.c_float), ("mse_ba", C.c_float), ("psnr", C.c_float)]
+
+
+def patch_d1_dict(p):
+    return {k: getattr(p, k) for k, _ in PatchD1._fields_}
+
+
 class FrameScore(C.Structure):
     """rbt_frame_score: what rbt_score returns for one pair of clouds"""
     _fields_ = [("parts", C.c_int), ("d1", D1Result), ("d2", D2Result), ("color", ColorResult), ("device_ms", C.c_double)] + \
@@ -251,6 +261,55 @@ class D1Target(C.Structure):
             self._keep += [refs, list(reference)]
 
 
+class PatchD1Target(C.Structure):
+    """rbt_patch_d1_target; struct_size is filled in. PatchD1Target() is the empty target of an entry without one. patches: one list of Patch per point-cloud frame;
+    patch_floors: None, or per frame None / one floor in 1/1000 dB per patch (F_k; else min_d1_mdb); reference: None, or one PCloud (or None = the cloud of the decoded
+    input) per frame. The object keeps the arrays it points to alive."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_d1_mdb", C.c_int32), ("peak", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("background_qp", C.c_int), ("max_trials", C.c_int),
+                ("atlas", AtlasParams), ("n_frames", C.c_int), ("patches", C.POINTER(C.POINTER(Patch))), ("n_patches", C.POINTER(C.c_int)), ("patch_min_d1_mdb", C.POINTER(C.POINTER(C.c_int32))),
+                ("reference", C.POINTER(C.c_void_p))]
+
+    def __init__(self, atlas=None, patches=None, min_d1_mdb=0, peak=0, qp_min=0, qp_max=0, background_qp=-1, max_trials=0, patch_floors=None, reference=None):
+        super().__init__(C.sizeof(PatchD1Target))
+        self._keep = []
+        if atlas is None:
+            return
+        self.min_d1_mdb, self.peak, self.qp_min, self.qp_max, self.background_qp, self.max_trials = min_d1_mdb, peak, qp_min, qp_max, background_qp, max_trials
+        self.atlas = AtlasParams(*[getattr(atlas, n) for n, _ in AtlasParams._fields_])
+        self.n_frames = len(patches)
+        lists = [(Patch * max(1, len(p)))(*p) for p in patches]
+        ptrs = (C.POINTER(Patch) * max(1, len(lists)))(*[C.cast(a, C.POINTER(Patch)) for a in lists])
+        counts = (C.c_int * max(1, len(lists)))(*[len(p) for p in patches])
+        self.patches, self.n_patches = ptrs, counts
+        self._keep += [lists, ptrs, counts]
+        if patch_floors is not None:
+            fl = [None if f is None else (C.c_int32 * max(1, len(f)))(*f) for f in patch_floors]
+            fp = (C.POINTER(C.c_int32) * max(1, len(fl)))(*[None if a is None else C.cast(a, C.POINTER(C.c_int32)) for a in fl])
+            self.patch_min_d1_mdb = fp
+            self._keep += [fl, fp]
+        if reference is not None:
+            refs = (C.c_void_p * max(1, len(reference)))(*[None if r is None else (r.h.value if isinstance(r, PCloud) else r) for r in reference])
+            self.reference = refs
+            self._keep += [refs, list(reference)]
+
+
+class PatchD1Pick(C.Structure):
+    """rbt_patch_d1_pick: of a frame's settling trial, per patch: its QP, met, failed, its PatchD1, its figure"""
+    _fields_ = [("qp", C.c_int), ("met", C.c_int), ("failed", C.c_int), ("d1", PatchD1), ("figure", C.c_double)]
+
+
+class PatchD1Frame(C.Structure):
+    """rbt_patch_d1_frame: trials, met, the patch count, the frame's bytes, the whole frame's D1Result in the settling trial, the picks"""
+    _fields_ = [("n_trials", C.c_int), ("met", C.c_int), ("n_patches", C.c_int), ("bytes", C.c_uint64), ("d1", D1Result), ("patches", C.POINTER(PatchD1Pick))]
+
+
+class PatchD1Result(C.Structure):
+    """rbt_patch_d1_result: frames, the probe q0, met_all, the passes, the stream's size, the pictures encoded, the grid, the final map, the frames, the picks, device
+    milliseconds of the clouds"""
+    _fields_ = [("n_frames", C.c_int), ("qp_probe", C.c_int), ("met_all", C.c_int), ("n_passes", C.c_int), ("bytes", C.c_uint64), ("pictures_encoded", C.c_uint64), ("w_ctb", C.c_int), ("h_ctb", C.c_int),
+                ("map", C.POINTER(C.c_int8)), ("frames", C.POINTER(PatchD1Frame)), ("picks", C.POINTER(PatchD1Pick)), ("cloud_ms", C.c_double)]
+
+
 class D1FloorResult(C.Structure):
     """rbt_d1_floor_result: q*, the probe q0, the walk's start qs, met, distinct QPs encoded, the stream's size, mean and minimum D1 over the frames, the frames' D1Result
     (freed by the binding), device milliseconds of the clouds"""
@@ -373,6 +432,10 @@ def load(path=None):
     L.rbt_submit_gof_quality_patches.argtypes = gof_patch + [C.POINTER(C.c_void_p)]
     L.rbt_wait_gof_quality_patches.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PatchFloorResult)]
     L.rbt_transcode_gof_quality_patches.argtypes = gof_patch + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PatchFloorResult)]
+    gof_pd1 = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(PatchD1Target)]
+    L.rbt_submit_gof_d1_patches.argtypes = gof_pd1 + [C.POINTER(C.c_void_p)]
+    L.rbt_wait_gof_d1_patches.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PatchD1Result)]
+    L.rbt_transcode_gof_d1_patches.argtypes = gof_pd1 + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PatchD1Result)]
     L.rbt_ctb_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.rbt_qp_map_from_patches.argtypes = [C.POINTER(AtlasParams), C.POINTER(Patch), C.c_int, C.POINTER(C.c_int8), C.c_int, C.c_int, C.POINTER(C.c_int8), C.c_int, C.c_int]
     L.rbt_submit_gof_rate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(RateTarget), C.POINTER(C.c_void_p)]
@@ -402,6 +465,9 @@ def load(path=None):
                                           C.POINTER(ColorFloorResult)]
     L.rbt_gather_420.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]
     L.rbt_pcloud_set_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rbt_pcloud_set_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rbt_pcloud_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rbt_score_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(PatchD1), C.POINTER(D1Result), C.POINTER(C.c_double)]
     L.rbt_score_pair_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     L.rbt_score_pair_color.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ColorResult)]
     L.rbt_score_pair_release.argtypes = [C.c_void_p, C.c_void_p]
@@ -571,6 +637,19 @@ class PCloud:
         if c.shape != (self.points()[0], 3):
             raise ValueError("one colour per point")
         self.ctx._chk(self.ctx.L.rbt_pcloud_set_colors(self.ctx.h, self.h, c.ctypes.data))
+
+    def set_labels(self, labels):
+        """rbt_pcloud_set_labels: a label per point (uint32 [n], each below 65536), in point order - the patch of the point for rbt_score_patches"""
+        a = np.ascontiguousarray(labels, dtype=np.uint32)
+        if a.shape != (self.points()[0],):
+            raise ValueError("one label per point")
+        self.ctx._chk(self.ctx.L.rbt_pcloud_set_labels(self.ctx.h, self.h, a.ctypes.data))
+
+    def labels(self):
+        """rbt_pcloud_labels: the label of every point (uint32 [n]); of a cloud made from maps, the index of the patch that emitted the point"""
+        out = np.empty(self.points()[0], np.uint32)
+        self.ctx._chk(self.ctx.L.rbt_pcloud_labels(self.ctx.h, self.h, out.ctypes.data))
+        return out
 
     def release(self):
         if self.h:
@@ -848,6 +927,33 @@ class Context:
         """rbt_transcode_gof_quality_patches: submit + wait"""
         args = self._gof_args(streams, params, targets, PatchFloorTarget)
         return self._patch_results(self._collect(self.L.rbt_transcode_gof_quality_patches, args[0], args, PatchFloorResult))
+
+    def _patch_d1_results(self, res):
+        """([stream bytes, ...], [PatchD1Result, ...] as dicts): map becomes an int8 array [n_frames, h_ctb, w_ctb] (None without a target), frames a list of dicts with the
+        whole frame's d1 as a dict and patches as pick dicts (d1: a patch_d1_dict), and the library's arrays are released"""
+        outs, rs = res
+        for r in rs:
+            fr, mp = r["frames"], r["map"]
+            r["frames"] = [dict(_result_dict(fr[f]), d1=_result_dict(fr[f].d1), patches=[dict(_result_dict(fr[f].patches[k]), d1=patch_d1_dict(fr[f].patches[k].d1)) for k in range(fr[f].n_patches)])
+                           for f in range(r["n_frames"])] if fr else []
+            r["map"] = np.ctypeslib.as_array(mp, (r["n_frames"], r["h_ctb"], r["w_ctb"])).copy() if mp else None
+            for ptr in (fr, mp, r.pop("picks")):
+                self.L.rbt_free(ptr)
+        return outs, rs
+
+    def submit_gof_d1_patches(self, streams, params, targets):
+        """rbt_submit_gof_d1_patches: submit_gof with one PatchD1Target per entry (PatchD1Target() = none): every patch of every frame of a geometry entry holds its D1
+        floor; returns a job for wait_gof_d1_patches"""
+        return self._submit(self.L.rbt_submit_gof_d1_patches, streams, params, targets, PatchD1Target)
+
+    def wait_gof_d1_patches(self, job):
+        """rbt_wait_gof_d1_patches -> ([stream bytes, ...], [result dict, ...])"""
+        return self._patch_d1_results(self._collect(self.L.rbt_wait_gof_d1_patches, job[1], [job[0]], PatchD1Result))
+
+    def transcode_gof_d1_patches(self, streams, params, targets):
+        """rbt_transcode_gof_d1_patches: submit + wait"""
+        args = self._gof_args(streams, params, targets, PatchD1Target)
+        return self._patch_d1_results(self._collect(self.L.rbt_transcode_gof_d1_patches, args[0], args, PatchD1Result))
 
     def ctb_sse(self, a, b, w, h, log2_ctb=5, occ=None, rects=None):
         """rbt_ctb_sse: planar 4:2:0 pictures a, b ([n, w*h*3/2] uint16), or None one occupancy plane per picture ([n, oh, ow] uint16), or None rectangles [[c0, r0, c1, r1],
@@ -1167,6 +1273,13 @@ class Context:
         s = FrameScore()
         self._chk(self.L.rbt_score(self.h, a.h if a is not None else None, b.h if b is not None else None, peak, parts, C.byref(s)))
         return s if raw else frame_score_dict(s)
+
+    def score_patches(self, a, b, n_patches, peak=1023, raw=False):
+        """rbt_score_patches: a = the reference PCloud, b = the decoded one with its labels -> (one dict per patch - or the PatchD1 array itself (raw) -, the whole
+        frame's D1 as rbt_score returns it, device_ms)"""
+        out = (PatchD1 * max(1, n_patches))(); whole = D1Result(); ms = C.c_double()
+        self._chk(self.L.rbt_score_patches(self.h, a.h if a is not None else None, b.h if b is not None else None, peak, n_patches, out, C.byref(whole), C.byref(ms)))
+        return (out if raw else [patch_d1_dict(out[k]) for k in range(n_patches)]), (whole if raw else _result_dict(whole)), ms.value
 
     def score_pair(self, a, b):
         """rbt_score_pair_create: a = the source PCloud, b = the decoded one -> ScorePair"""

@@ -135,6 +135,28 @@ __global__ void __launch_bounds__(RBT_SC_SUM) k_sc_sum_final(const double* part,
   __shared__ RbtScoreSumLds lds;
   sc_sum_final(part, n_blocks, out, RBT_LDS_CAST(RbtScoreSumLds, &lds));
 }
+// ---- D1 per patch (rbt_score.h) ----
+// one wave per work item: its points are a contiguous run of the cloud
+__global__ void __launch_bounds__(64) k_pd_labels(const uint32_t* items, const uint32_t* offsets, uint32_t* labels) { pd_label_item(items, offsets, (int)blockIdx.x, (int)threadIdx.x, 64, labels); }
+__global__ void __launch_bounds__(256) k_pd_check(const uint32_t* labels, int n, uint32_t n_patches, uint32_t* err) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (__ballot(i < n && labels[i] >= n_patches) && (threadIdx.x & 63) == 0) atomicOr(err, 1u);
+}
+// dir 0: one lane per point of A, 1: per point of B. No LDS: every wave adds on its own. A wave whose terms all carry one label - the rule, since points come in patch
+// order - folds them with shuffles and lane 0 issues one atomic per word; a mixed wave issues them per lane. Integer atomics: the words do not depend on the order.
+__global__ void __launch_bounds__(256) k_pd_sums(RbtScoreCloud A, RbtScoreCloud B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out, int dir) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  uint32_t label = 0, d = 0; int valid = 0;
+  if (i < (dir ? B.n : A.n)) valid = dir ? pd_term_ba(labels_b, dist_b, i, &label, &d) : pd_term_ab(&A, &B, labels_b, dist_a, i, &label, &d);
+  const unsigned long long act = __ballot(valid);
+  if (!act) return;                                                     // uniform over the wave
+  const uint32_t first = (uint32_t)__shfl((int)label, __ffsll((long long)act) - 1);
+  if (__ballot(valid && label != first) == 0) {
+    unsigned long long s = valid ? d : 0; uint32_t m = valid ? d : 0;
+    for (int o = 32; o > 0; o >>= 1) { s += (unsigned long long)__shfl_xor((long long)s, o); const uint32_t w = (uint32_t)__shfl_xor((int)m, o); m = w > m ? w : m; }
+    if ((threadIdx.x & 63) == 0) pd_add(out, first, dir, s, (unsigned long long)__popcll(act), m);
+  } else if (valid) pd_add(out, label, dir, d, 1, d);
+}
 
 void launch_up444(const uint16_t* yuv420, int w, int h, int bit_depth, int n_frames, int filter, uint16_t* yuv444) {
   if (n_frames <= 0) return;
@@ -205,5 +227,16 @@ void launch_sc_color_walks(const RbtScoreCloud* A, const RbtScoreCloud* B, const
   if (A->n <= 0 || B->n <= 0) return;
   hipLaunchKernelGGL(k_sc_color_walk, dim3((unsigned)((A->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, dist_a, dist_b, res, 0);
   hipLaunchKernelGGL(k_sc_color_walk, dim3((unsigned)((B->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, dist_a, dist_b, res, 1);
+}
+void launch_pd_labels(const uint32_t* items, const uint32_t* offsets, int n_items, uint32_t* labels) {
+  if (n_items > 0) hipLaunchKernelGGL(k_pd_labels, dim3((unsigned)n_items), dim3(64), 0, g_stream, items, offsets, labels);
+}
+void launch_pd_check(const uint32_t* labels, int n, uint32_t n_patches, uint32_t* err) {
+  if (n > 0) hipLaunchKernelGGL(k_pd_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, labels, n, n_patches, err);
+}
+void launch_pd_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out) {
+  if (A->n <= 0 || B->n <= 0) return;
+  hipLaunchKernelGGL(k_pd_sums, dim3((unsigned)((A->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, labels_b, dist_a, dist_b, out, 0);
+  hipLaunchKernelGGL(k_pd_sums, dim3((unsigned)((B->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, labels_b, dist_a, dist_b, out, 1);
 }
 }  // namespace rbtk

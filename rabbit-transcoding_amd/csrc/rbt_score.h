@@ -18,6 +18,12 @@
 //            a fresh index of the same points with the new colours.
 //   pairs    the nearest squared distances of both directions depend on positions only. A score pair (rbt_score_pair_*) keeps them; launch_sc_color_walks runs the walks
 //            with the colour part alone on the stored distances - three sums per direction, reduced in the workgroup, one 64-bit atomic per workgroup and sum.
+//   patches  D1 per patch of the decoded cloud (rbt_score_patches; the definition is in include/rbt.h): B carries a label per point. Behind the two searches one lane per
+//            point reads its stored distance; B -> A adds (label of j, d_j), A -> B walks pc_for_ties on B's volume at d_i, takes the lowest pc_hash_find over the tie
+//            voxels - the owner - and adds (label of the owner, d_i). RBT_PD_WORDS 64-bit words per patch, integer atomics only: a wave whose labels are all the same
+//            (points arrive in patch order) folds sum, count and maximum in registers and issues one atomic per word, a mixed wave one per lane and word. The labels
+//            are checked against the patch count by a kernel of their own first (error word), so a refused call has written no sum. The labels of a cloud made from maps
+//            come from a kernel of their own over the work items' offsets (pd_label_item): the reconstruction kernels are the ones they were.
 // No kernel waits for another; every loop is bounded by the size of the volume.
 #pragma once
 #include "rbt_color.h"
@@ -47,8 +53,15 @@ void launch_sc_recolor(const RbtScoreCloud* S);                         // S->rg
 void launch_sc_search(const RbtScoreCloud* A, const RbtScoreCloud* B, uint32_t* dist_a, uint32_t* dist_b);   // the two searches of launch_sc_score on their own
 // the colour sums of launch_sc_score from stored distances: res[0..2] A -> B, res[3..5] B -> A (RBT_SC_COLOR_RESULTS words, zeroed beforehand)
 void launch_sc_color_walks(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* res);
+// the label of every point of a cloud made from maps: the points of work item t (items[t] = patch << 16 | block) are offsets[t] .. offsets[t + 1] - 1
+void launch_pd_labels(const uint32_t* items, const uint32_t* offsets, int n_items, uint32_t* labels);
+void launch_pd_check(const uint32_t* labels, int n, uint32_t n_patches, uint32_t* err);       // *err = 1 when a label is >= n_patches
+// behind launch_sc_score / launch_sc_search on the same clouds: out holds RBT_PD_WORDS words per patch (zeroed beforehand); every label of B is below the patch count
+void launch_pd_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out);
 }  // namespace rbtk
 enum { RBT_SC_COLOR_RESULTS = 8 };
+// words of one patch in the result of launch_pd_sums, 64-bit each; + 1 for the direction B -> A
+enum { RBT_PD_SSE_AB = 0, RBT_PD_SSE_BA, RBT_PD_N_AB, RBT_PD_N_BA, RBT_PD_MAX_AB, RBT_PD_MAX_BA, RBT_PD_WORDS };
 
 // ------------------------------------------------------------------------------------------------ bodies (device and host emulation)
 RBT_DEV size_t sc_coarse_word(int cx, int cy, int cz) { return (((size_t)cz * RBT_SC_CDIM + cy) * RBT_SC_CROW) + (cx >> 5); }
@@ -284,9 +297,49 @@ RBT_DEV void sc_sum_final(const double* part, int n_blocks, double* out, RBT_LDS
   sc_fold(L, &out[0], &out[1]);
 }
 
+// ---- D1 per patch ----
+RBT_DEV void pd_label_item(const uint32_t* items, const uint32_t* offsets, int t, int lane, int lanes, uint32_t* labels) {
+  const uint32_t l = items[t] >> 16, end = offsets[t + 1];
+  for (uint32_t i = offsets[t] + (uint32_t)lane; i < end; i += (uint32_t)lanes) labels[i] = l;
+}
+// the term of point j of B: its own label and its stored distance. Returns 0 for a point that is no representative.
+RBT_DEV int pd_term_ba(const uint32_t* labels_b, const uint32_t* dist_b, int j, uint32_t* label, uint32_t* d) {
+  const uint32_t d2 = dist_b[j]; if (d2 == RBT_SC_NONE) return 0;
+  *label = labels_b[j]; *d = d2;
+  return 1;
+}
+// the term of point i of A: the label of its owner - the lowest representative of B among the voxels at exactly the stored distance - and that distance
+RBT_DEV int pd_term_ab(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, int i, uint32_t* label, uint32_t* d) {
+  const uint32_t d2 = dist_a[i]; if (d2 == RBT_SC_NONE) return 0;
+  const int16_t* p = A->xyz + 3 * (size_t)i;
+  uint32_t owner = 0xFFFFFFFFu;
+  pc_for_ties(B->vol, p[0], p[1], p[2], d2, [&](uint32_t id) { const uint32_t j = pc_hash_find(B->keys, B->vals, B->lg, id); if (j < owner) owner = j; });
+  if (owner >= (uint32_t)B->n) return 0;            // (the distance is that of a voxel of B: there is an owner)
+  *label = labels_b[owner]; *d = d2;
+  return 1;
+}
+// sum, count and maximum of one or more terms into the words of patch `label`, direction dir
+RBT_DEV void pd_add(unsigned long long* out, uint32_t label, int dir, unsigned long long sum, unsigned long long cnt, unsigned long long mx) {
+  unsigned long long* w = out + (size_t)RBT_PD_WORDS * label + dir;
+#ifdef RBT_HOSTEMU
+  w[RBT_PD_SSE_AB] += sum; w[RBT_PD_N_AB] += cnt; if (mx > w[RBT_PD_MAX_AB]) w[RBT_PD_MAX_AB] = mx;
+#else
+  if (sum) atomicAdd(&w[RBT_PD_SSE_AB], sum);
+  atomicAdd(&w[RBT_PD_N_AB], cnt);
+  if (mx) atomicMax(&w[RBT_PD_MAX_AB], mx);
+#endif
+}
+
 #ifdef RBT_HOSTEMU
 // serial stand-ins of the launchers (the product's are in rbt_color.hip)
 namespace rbtk {
+inline void launch_pd_labels(const uint32_t* items, const uint32_t* offsets, int n_items, uint32_t* labels) { for (int t = 0; t < n_items; t++) pd_label_item(items, offsets, t, 0, 1, labels); }
+inline void launch_pd_check(const uint32_t* labels, int n, uint32_t n_patches, uint32_t* err) { for (int i = 0; i < n; i++) if (labels[i] >= n_patches) *err = 1; }
+inline void launch_pd_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out) {
+  uint32_t label = 0, d = 0;
+  for (int i = 0; i < A->n; i++) if (pd_term_ab(A, B, labels_b, dist_a, i, &label, &d)) pd_add(out, label, 0, d, 1, d);
+  for (int j = 0; j < B->n; j++) if (pd_term_ba(labels_b, dist_b, j, &label, &d)) pd_add(out, label, 1, d, 1, d);
+}
 inline void launch_sc_check(const int16_t* xyz, int n, uint32_t* scal) { for (int i = 0; i < n; i++) if (!tc_in_range(xyz + 3 * (size_t)i)) scal[RBT_SC_ERR] = 1; }
 inline void launch_sc_index(const RbtScoreCloud* S, uint32_t* scal) {
   for (int i = 0; i < S->n; i++) scal[RBT_SC_N_MERGED] += (uint32_t)sc_insert(S, i);

@@ -172,6 +172,7 @@ struct SubmitExtras {
   bool gof_rule = true; const rbt_rate_target* targets = nullptr; const rbt_quality_target* quality = nullptr; const rbt_d1_target* d1 = nullptr; const rbt_color_target* color = nullptr;
   bool per_frame = false; const rbt_frame_qp* lists = nullptr; const rbt_qp_map* maps = nullptr;
   const rbt_patch_floor_target* patches = nullptr;
+  const rbt_patch_d1_target* d1_patches = nullptr;
 };
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x = SubmitExtras());
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
@@ -324,6 +325,33 @@ static int check_patch_floors(std::string& err, int n, const rbt_stream_params* 
   }
   return RBT_OK;
 }
+// The refusals of rbt_submit_gof_d1_patches that the parameters alone decide. A target is split in two: its walks' side becomes a patch-floor target (floors, range,
+// background, cap; min_psnr_mdb holds min_d1_mdb) and goes through check_patch_floors, its clouds' side a D1 target without a floor of its own (atlas, patch lists,
+// references, peak) and goes through check_d1. as_patch / as_d1 / floors: the two arrays and the floor pointers they refer to, alive until submit returns.
+static int check_d1_patches(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_patch_d1_target* t, std::vector<rbt_patch_floor_target>& as_patch, std::vector<rbt_d1_target>& as_d1,
+                            std::vector<rbt::PatchFloorIn>& out, rbt::CloudRequest<rbt_d1_target>& req) {
+  std::string& err = ctx->last_err;
+  as_patch.assign((size_t)n, rbt_patch_floor_target()); as_d1.assign((size_t)n, rbt_d1_target());
+  for (int i = 0; i < n; i++) {
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    rbt_patch_floor_target& a = as_patch[(size_t)i]; rbt_d1_target& d = as_d1[(size_t)i];
+    memset(&a, 0, sizeof(a)); memset(&d, 0, sizeof(d)); a.struct_size = sizeof(a); d.struct_size = sizeof(d);
+    if (t[i].struct_size != sizeof(rbt_patch_d1_target)) { err = who + "rbt_patch_d1_target.struct_size is not sizeof(rbt_patch_d1_target)"; return RBT_ERR_PARAM; }
+    rbt_patch_d1_target zero; memset(&zero, 0, sizeof(zero));
+    const bool empty = !t[i].min_d1_mdb && !t[i].peak && !t[i].qp_min && !t[i].qp_max && !t[i].background_qp && !t[i].max_trials && !t[i].n_frames && !t[i].patches && !t[i].n_patches &&
+                       !t[i].patch_min_d1_mdb && !t[i].reference && !memcmp(&t[i].atlas, &zero.atlas, sizeof(zero.atlas));
+    if (empty) continue;
+    if (p[i].video_type != RBT_VIDEO_GEOMETRY) { err = who + "a D1 target on a non-geometry entry (the target of an attribute or occupancy entry must be empty)"; return RBT_ERR_PARAM; }
+    if (t[i].min_d1_mdb < 0) { err = who + "min_d1_mdb must not be negative"; return RBT_ERR_PARAM; }
+    if (t[i].peak < 0) { err = who + "peak must not be negative (0 = 1023)"; return RBT_ERR_PARAM; }
+    if (t[i].atlas.map_count != 2) { err = who + "floors held patch by patch need atlas.map_count 2: a point-cloud frame is the two pictures that are coded as a pair"; return RBT_ERR_PARAM; }
+    a.min_psnr_mdb = t[i].min_d1_mdb; a.region = RBT_QUALITY_ALL; a.qp_min = t[i].qp_min; a.qp_max = t[i].qp_max; a.background_qp = t[i].background_qp; a.max_trials = t[i].max_trials;
+    a.atlas = t[i].atlas; a.n_frames = t[i].n_frames; a.patches = t[i].patches; a.n_patches = t[i].n_patches; a.patch_min_psnr_mdb = t[i].patch_min_d1_mdb;
+    d.peak = t[i].peak; d.qp_min = t[i].qp_min; d.qp_max = t[i].qp_max; d.n_frames = t[i].n_frames; d.atlas = t[i].atlas; d.patches = t[i].patches; d.n_patches = t[i].n_patches; d.reference = t[i].reference;
+  }
+  if (int rc = check_patch_floors(err, n, p, as_patch.data(), out)) return rc;
+  return check_d1(ctx, n, p, as_d1.data(), req);
+}
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
@@ -342,12 +370,14 @@ static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const si
   if (x.maps) { if (int rc = check_qp_maps(ctx->last_err, n, p, x.maps, qp_maps)) return rc; r.qp_maps = &qp_maps; }
   std::vector<rbt::PatchFloorIn> patch_floors;
   if (x.patches) { if (int rc = check_patch_floors(ctx->last_err, n, p, x.patches, patch_floors)) return rc; r.patch_floors = &patch_floors; }
+  std::vector<rbt_patch_floor_target> as_patch; std::vector<rbt_d1_target> as_d1;
+  if (x.d1_patches) { if (int rc = check_d1_patches(ctx, n, p, x.d1_patches, as_patch, as_d1, patch_floors, d1)) return rc; r.patch_floors = &patch_floors; r.d1 = &d1; r.patch_d1 = true; }
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
   rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, r), ctx};
-  if (x.quality || x.d1 || x.color || x.lists || x.maps || x.patches) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
+  if (x.quality || x.d1 || x.color || x.lists || x.maps || x.patches || x.d1_patches) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -423,7 +453,8 @@ static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out,
     {"rbt_wait_gof_color collects jobs of rbt_submit_gof_color only", "a job of rbt_submit_gof_color is collected by rbt_wait_gof_color"},
     {"rbt_wait_gof_d1_frames collects jobs of rbt_submit_gof_d1_frames only", "a job of rbt_submit_gof_d1_frames is collected by rbt_wait_gof_d1_frames"},
     {"rbt_wait_gof_quality_frames collects jobs of rbt_submit_gof_quality_frames only", "a job of rbt_submit_gof_quality_frames is collected by rbt_wait_gof_quality_frames"},
-    {"rbt_wait_gof_quality_patches collects jobs of rbt_submit_gof_quality_patches only", "a job of rbt_submit_gof_quality_patches is collected by rbt_wait_gof_quality_patches"}};
+    {"rbt_wait_gof_quality_patches collects jobs of rbt_submit_gof_quality_patches only", "a job of rbt_submit_gof_quality_patches is collected by rbt_wait_gof_quality_patches"},
+    {"rbt_wait_gof_d1_patches collects jobs of rbt_submit_gof_d1_patches only", "a job of rbt_submit_gof_d1_patches is collected by rbt_wait_gof_d1_patches"}};
   const rbt::GofKind is = rbt::gof_kind(job->j);
   if (is != kind) { const bool called = is == rbt::GOF_PLAIN || (kind != rbt::GOF_PLAIN && kind < is); ctx->last_err = mismatch[called ? kind : is][called ? 0 : 1]; return RBT_ERR_PARAM; }
   int n_flat = 0; r.out = annexb_out; r.n_out = n_out; r.n_flat = &n_flat;
@@ -495,6 +526,23 @@ int rbt_transcode_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_i
 int rbt_qp_map_from_patches(const rbt_atlas_params* atlas, const rbt_patch* patches, int n_patches, const int8_t* patch_qp, int background_qp, int log2_ctb, int8_t* out, int w_ctb, int h_ctb) try {
   std::string err;      // (no context to leave the reason with: the header names every refusal)
   return rbt::qp_map_from_patches(err, atlas, patches, n_patches, patch_qp, background_qp, log2_ctb, out, w_ctb, h_ctb);
+} RBT_CATCH
+// ---- D1 floors held patch by patch ----
+int rbt_submit_gof_d1_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d1_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  SubmitExtras x; x.d1_patches = targets; return submit(ctx, n, annexb_in, n_in, p, job, x);
+} RBT_CATCH
+int rbt_wait_gof_d1_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_patch_d1_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  rbt::GofResults r; r.d1_patches = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_D1_PATCHES, r);
+} RBT_CATCH
+int rbt_transcode_gof_d1_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d1_target* targets,
+                                 uint8_t** annexb_out, size_t* n_out, rbt_patch_d1_result* results) try {
+  if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !targets || !annexb_out || !n_out || !results) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  int rc = rbt_submit_gof_d1_patches(ctx, n, annexb_in, n_in, p, targets, &job);
+  if (rc) return rc;
+  return rbt_wait_gof_d1_patches(ctx, job, annexb_out, n_out, results);
 } RBT_CATCH
 // ---- PSNR floors held patch by patch ----
 int rbt_submit_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_floor_target* targets, rbt_job** job) try {
@@ -841,6 +889,24 @@ int rbt_pcloud_set_colors(rbt_ctx* ctx, rbt_pcloud* cloud, const uint8_t* rgb) t
   RBT_ENTER(ctx);
   if (!cloud_of(ctx, cloud)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
   return rbt::pcloud_set_colors(ctx->last_err, cloud->cloud, rgb);
+} RBT_CATCH
+int rbt_pcloud_set_labels(rbt_ctx* ctx, rbt_pcloud* cloud, const uint32_t* labels) try {
+  if (!ctx || !labels) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  if (!cloud_of(ctx, cloud)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
+  return rbt::pcloud_set_labels(ctx->last_err, cloud->cloud, labels);
+} RBT_CATCH
+int rbt_pcloud_labels(rbt_ctx* ctx, const rbt_pcloud* cloud, uint32_t* labels) try {
+  if (!ctx || !labels) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  if (!cloud_of(ctx, cloud)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
+  return rbt::pcloud_labels(ctx->last_err, cloud->cloud, labels);
+} RBT_CATCH
+int rbt_score_patches(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int n_patches, rbt_patch_d1* out, rbt_d1_result* whole, double* device_ms) try {
+  if (!ctx || !out) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  if (!cloud_of(ctx, a) || !cloud_of(ctx, b)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
+  return rbt::pcloud_score_patches(ctx->last_err, a->cloud, b->cloud, peak, n_patches, out, whole, device_ms);
 } RBT_CATCH
 static bool pair_of(const rbt_ctx* ctx, const rbt_score_pair* h) { return h && h->owner == ctx; }
 int rbt_score_pair_create(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, rbt_score_pair** out) try {

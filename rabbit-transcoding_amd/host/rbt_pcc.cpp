@@ -7,6 +7,7 @@
 #include <vector>
 #include "rbt_batch.h"
 #include "rbt_pcc.h"
+#include "rbt_d1_figures.h"
 #include "../csrc/rbt_pcc.h"
 #include "../csrc/rbt_cloudmaps.h"
 #include "../csrc/rbt_color.h"
@@ -18,7 +19,8 @@ namespace {
 struct DevBuf { void* p = nullptr; ~DevBuf() { rbtk::dev_free(p); } bool alloc(size_t n) { p = rbtk::dev_alloc(n); return p != nullptr; } template <class T> T* as() const { return (T*)p; }
                 void take(DevBuf& o) { rbtk::dev_free(p); p = o.p; o.p = nullptr; } };
 // what reconstruct_impl leaves on the device for rbt_pcloud_from_maps: positions, 4:4:4 triples and RGB8 triples of the finished cloud
-struct DevCloud { DevBuf xyz, yuv, rgb; };
+// and the patch index of every point (csrc/rbt_score.h, launch_pd_labels)
+struct DevCloud { DevBuf xyz, yuv, rgb, labels; };
 int block_xy(const rbt_patch& p, int ub, int vb, int* x, int* y) {       // PCCPatch::patchBlock2CanvasBlock
   switch (p.orientation) {
     case RBT_OR_DEFAULT: *x = ub + p.u0; *y = vb + p.v0; return 1;
@@ -38,10 +40,11 @@ static_assert(T_COL_TRANSFER_COPY < 16, "timer slots");
 int lg_of(int n) { int lg = 4; while (((size_t)1 << lg) < 2 * (size_t)n) lg++; return lg; }
 // the derived fields of the three results from the sums and counts (shared by the host-array calls and rbt_score)
 // QualityMetrics::compute :204-206: float mse, getPSNR with factor 3; symmetric = the worse direction (:299-309)
+// (geometry_mse / geometry_psnr: rbt_d1_figures.h, where the figures per patch use them too)
 template <class R> void finish_geometry(R* out, int peak) {
-  out->mse_ab = (float)((double)out->sse_ab / out->n_a); out->mse_ba = (float)((double)out->sse_ba / out->n_b);
-  const float p = (float)peak, m = out->mse_ab > out->mse_ba ? out->mse_ab : out->mse_ba;
-  out->psnr_ab = 10 * log10f(3 * p * p / out->mse_ab); out->psnr_ba = 10 * log10f(3 * p * p / out->mse_ba); out->psnr = 10 * log10f(3 * p * p / m);
+  out->mse_ab = geometry_mse((double)out->sse_ab, out->n_a); out->mse_ba = geometry_mse((double)out->sse_ba, out->n_b);
+  const float m = out->mse_ab > out->mse_ba ? out->mse_ab : out->mse_ba;
+  out->psnr_ab = geometry_psnr(peak, out->mse_ab); out->psnr_ba = geometry_psnr(peak, out->mse_ba); out->psnr = geometry_psnr(peak, m);
 }
 void finish_color(rbt_color_result* out) {
   const double unit = 2550000.0 * 2550000.0;
@@ -128,7 +131,7 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
   }
   const int n_items = (int)items.size();
   const size_t ys = (size_t)W * H, os = (size_t)(W / prec) * (H / prec), fs = ys * 3 / 2;
-  DevBuf b_occ, b_d0, b_d1, b_t0, b_t1, b_patches, b_items, b_b2p, b_counts, b_off, b_om, b_xyz, b_yuv, b_meta, b_cells, b_scal, b_420, b_rgb, b_xyz0, b_yuv0, b_moved;
+  DevBuf b_occ, b_d0, b_d1, b_t0, b_t1, b_patches, b_items, b_b2p, b_counts, b_off, b_om, b_xyz, b_yuv, b_meta, b_cells, b_scal, b_420, b_rgb, b_xyz0, b_yuv0, b_moved, b_labels;
   if (!b_occ.alloc(os * 2) || !b_d0.alloc(ys * 2) || !b_d1.alloc(ys * 2) || !b_patches.alloc(sizeof(rbt_patch) * (size_t)(n_patches ? n_patches : 1)) || !b_items.alloc(4 * (size_t)(n_items ? n_items : 1)) ||
       !b_b2p.alloc(4 * (size_t)P.bw * P.bh) || !b_counts.alloc(4 * (size_t)(n_items + 1)) || !b_off.alloc(4 * (size_t)(n_items + 1)) || !b_om.alloc(ys) ||
       (t0 && !want_rgb && (!b_t0.alloc(fs * 2) || !b_t1.alloc(fs * 2))) || (want_rgb && (!b_420.alloc(fs * 4) || !b_t0.alloc(ys * 12)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
@@ -154,6 +157,10 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
   rbtk::launch_pcc_emit(&P, b_patches.as<rbt_patch>(), b_items.as<uint32_t>(), n_items, b_occ.as<uint16_t>(), b_d0.as<uint16_t>(), b_d1.as<uint16_t>(), p_t0, p_t1,
                         b_b2p.as<uint32_t>(), b_off.as<uint32_t>(), b_xyz.as<int16_t>(), b_yuv.as<uint16_t>(), smooth ? b_om.as<uint8_t>() : nullptr, smooth ? b_meta.as<uint32_t>() : nullptr);
   out->n_points = (int)total;
+  if (keep_dev) {                   // the patch of every point, by a kernel of its own over the items' offsets: the emit above is the kernel it was
+    if (!b_labels.alloc(4 * (size_t)(total ? total : 1))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    rbtk::launch_pd_labels(b_items.as<uint32_t>(), b_off.as<uint32_t>(), n_items, b_labels.as<uint32_t>());
+  }
   if (keep && total) {              // rbt_reconstruct_decoded: the cloud before smoothing stays on the device as the source of the attribute transfer
     if (!b_xyz0.alloc(6 * (size_t)total) || !b_yuv0.alloc(6 * (size_t)total) || !b_moved.alloc(total)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
     rbtk::timer_begin(T_COL_TRANSFER_COPY);
@@ -215,7 +222,7 @@ static int reconstruct_impl(std::string& err, const rbt_atlas_params* a, const r
   }
   if (bad || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
   if (want_rgb && stage_ms) { stage_ms[0] = rbtk::timer_ms(T_COL_UP); stage_ms[1] = rbtk::timer_ms(T_COL_RGB); }
-  if (keep_dev) { keep_dev->xyz.take(b_xyz); keep_dev->yuv.take(b_yuv); keep_dev->rgb.take(b_rgb); }
+  if (keep_dev) { keep_dev->xyz.take(b_xyz); keep_dev->yuv.take(b_yuv); keep_dev->rgb.take(b_rgb); keep_dev->labels.take(b_labels); }
   return RBT_OK;
 }
 int pcc_reconstruct(std::string& err, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* occ, const uint16_t* d0, const uint16_t* d1, int geo_bd,
@@ -376,7 +383,8 @@ int pcc_d2(std::string& err, const int16_t* a, const int16_t* normals_a, int na,
 // ---- clouds that stay on the device, and their scoring (csrc/rbt_score.h) ----
 struct PCloud {
   int n = 0, n_merged = 0, lg = 0; bool indexed = false;
-  DevBuf xyz, rgb, yuv, nrm, maps, scal; void* vol = nullptr;             // vol: the bit volume with the coarse level behind it; taken from / returned to the context's cache
+  DevBuf xyz, rgb, yuv, nrm, labels, maps, scal; void* vol = nullptr;
+  int label_bound = 0;                                                     // > 0: every label is below it by construction (a cloud made from maps: its patch count); 0: not known             // vol: the bit volume with the coarse level behind it; taken from / returned to the context's cache
   RbtScoreCloud view() const {
     uint32_t* m = maps.as<uint32_t>(); const size_t slots = (size_t)1 << lg;
     return RbtScoreCloud{xyz.as<int16_t>(), rgb.as<uint8_t>(), nrm.as<int16_t>(), n, lg, (uint32_t*)vol, (uint32_t*)vol + (PCLOUD_VOL_BYTES - 4 * (size_t)RBT_SC_COARSE_WORDS) / 4, m, m + slots, m + 2 * slots, m + 6 * slots};
@@ -444,7 +452,7 @@ int pcloud_from_maps(std::string& err, PCloudCache& cache, const rbt_atlas_param
   const int n = (host_copy ? host_copy : &counts)->n_points;
   if (n <= 0) { err = "empty point cloud"; return RBT_ERR_PARAM; }
   PCloud* c = new PCloud(); c->n = n;
-  c->xyz.take(dev.xyz); c->yuv.take(dev.yuv); c->rgb.take(dev.rgb);
+  c->xyz.take(dev.xyz); c->yuv.take(dev.yuv); c->rgb.take(dev.rgb); c->labels.take(dev.labels); c->label_bound = n_patches;
   rc = pcloud_index(err, cache, c);
   if (rc) { pcloud_release(cache, c); return rc; }
   *out = c;
@@ -505,7 +513,7 @@ int mapframe_new(std::string& err, const rbt_atlas_params* a, const rbt_patch* p
 // smoothing and, where points moved and `flags` is set, the per-point moved flags (k_tc_flag, while the grid's cells are alive). One routine for mapframe_cloud and
 // colorframe_new: the grid's sizing lives here and in reconstruct_impl.
 static int mapframe_points(std::string& err, const MapFrame* F, const RbtPccParams& P, const uint16_t* d0, const uint16_t* d1, DevBuf& xyz, DevBuf& yuv, DevBuf* keep_xyz0, DevBuf* keep_moved, bool flags,
-                           int* n_points, int* n_moved) {
+                           int* n_points, int* n_moved, DevBuf* labels = nullptr) {
   *n_points = 0; *n_moved = 0;
   const rbt_atlas_params* a = &F->a; const int n_items = F->n_items; const bool smooth = a->geometry_smoothing != 0;
   const rbt_patch* patches = F->b_patches.as<rbt_patch>(); const uint32_t *items = F->b_items.as<uint32_t>(), *b2p = F->b_b2p.as<uint32_t>();
@@ -519,6 +527,10 @@ static int mapframe_points(std::string& err, const MapFrame* F, const RbtPccPara
       (smooth && keep_xyz0 && (!keep_xyz0->alloc(6 * (size_t)total) || !keep_moved->alloc(total)))) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
   rbtk::launch_pcc_emit(&P, patches, items, n_items, F->d_occ, d0, d1, nullptr, nullptr, b2p, F->b_off.as<uint32_t>(), xyz.as<int16_t>(), yuv.as<uint16_t>(),
                         smooth ? F->b_om.as<uint8_t>() : nullptr, smooth ? b_meta.as<uint32_t>() : nullptr);
+  if (labels) {                     // the patch of every point (smoothing moves points, it changes neither their order nor their patch)
+    if (!labels->alloc(4 * (size_t)total)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+    rbtk::launch_pd_labels(items, F->b_off.as<uint32_t>(), n_items, labels->as<uint32_t>());
+  }
   *n_points = (int)total;
   if (!smooth) return RBT_OK;
   if (keep_xyz0) {
@@ -553,11 +565,11 @@ int mapframe_cloud(std::string& err, PCloudCache& cache, const MapFrame* F, cons
   *out = nullptr; if (n_smoothed) *n_smoothed = 0;
   if (geo_bd < 8 || geo_bd > 16) { err = "bad atlas parameters"; return RBT_ERR_PARAM; }
   RbtPccParams P = F->P; P.geo_bd = geo_bd; P.attr_bd = geo_bd;
-  DevBuf b_xyz, b_yuv; int total = 0, moved = 0;
-  if (int rc = mapframe_points(err, F, P, d0, d1 ? d1 : d0, b_xyz, b_yuv, nullptr, nullptr, false, &total, &moved)) return rc;
+  DevBuf b_xyz, b_yuv, b_labels; int total = 0, moved = 0;
+  if (int rc = mapframe_points(err, F, P, d0, d1 ? d1 : d0, b_xyz, b_yuv, nullptr, nullptr, false, &total, &moved, &b_labels)) return rc;
   if (n_smoothed) *n_smoothed = moved;
   PCloud* c = new PCloud(); c->n = total;
-  c->xyz.take(b_xyz);
+  c->xyz.take(b_xyz); c->labels.take(b_labels); c->label_bound = P.n_patches;
   if (int rc = pcloud_index(err, cache, c)) { pcloud_release(cache, c); return rc; }      // (waits for the stream: the buffers that go out of scope here are idle)
   *out = c;
   return RBT_OK;
@@ -679,6 +691,64 @@ int pcloud_set_colors(std::string& err, PCloud* c, const uint8_t* rgb) {
   const RbtScoreCloud S = c->view();
   rbtk::launch_sc_recolor(&S);
   if (rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  return RBT_OK;
+}
+
+// A label per point for a cloud that is indexed already; as with the colours, the cloud keeps what it had until the upload has succeeded.
+int pcloud_set_labels(std::string& err, PCloud* c, const uint32_t* labels) {
+  for (int i = 0; i < c->n; i++) if (labels[i] >= 65536u) { err = "label " + std::to_string(i) + " is not below 65536"; return RBT_ERR_PARAM; }
+  DevBuf fresh;
+  if (!fresh.alloc(4 * (size_t)c->n)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::h2d(fresh.p, labels, 4 * (size_t)c->n) || rbtk::dev_sync()) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  c->labels.take(fresh); c->label_bound = 0;
+  return RBT_OK;
+}
+int pcloud_labels(std::string& err, const PCloud* c, uint32_t* labels) {
+  if (!c->labels.p) { err = "the cloud carries no labels"; return RBT_ERR_PARAM; }
+  if (rbtk::d2h(labels, c->labels.p, 4 * (size_t)c->n) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  return RBT_OK;
+}
+bool pcloud_has_labels(const PCloud* c) { return c->labels.p != nullptr; }
+// rbt_score_patches: the D1 part of pcloud_score - the same launches, so `whole` is its d1 bit for bit - and the per-patch sums on the distances it leaves
+int pcloud_score_patches(std::string& err, const PCloud* a, const PCloud* b, int peak, int n_patches, rbt_patch_d1* out, rbt_d1_result* whole, double* device_ms) {
+  if (whole) memset(whole, 0, sizeof(*whole));
+  if (device_ms) *device_ms = 0;
+  if (peak <= 0) { err = "bad peak"; return RBT_ERR_PARAM; }
+  if (n_patches < 1 || n_patches > 65536) { err = "n_patches is 1..65536"; return RBT_ERR_PARAM; }
+  if (!b->labels.p) { err = "the decoded cloud carries no labels"; return RBT_ERR_PARAM; }
+  memset(out, 0, sizeof(*out) * (size_t)n_patches);
+  const size_t na = (size_t)a->n, nb = (size_t)b->n, words = (size_t)RBT_PD_WORDS * (size_t)n_patches;
+  DevBuf dist, res, sums, bad;
+  if (!dist.alloc(4 * (na + nb)) || !res.alloc(8 * RBT_SC_RESULTS) || !sums.alloc(8 * words) || !bad.alloc(4)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::dev_memset(res.p, 0, 8 * RBT_SC_RESULTS) | rbtk::dev_memset(sums.p, 0, 8 * words) | rbtk::dev_memset(bad.p, 0, 4)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  // the labels of a cloud made from maps are its items' patch indices, below its patch count: no kernel and no read-back is needed to know them good (the trial clouds
+  // of rbt_submit_gof_d1_patches, one per frame and trial). Labels a caller gave are checked on the device.
+  uint32_t is_bad = 0;
+  if (b->label_bound <= 0 || b->label_bound > n_patches) {
+    rbtk::launch_pd_check(b->labels.as<uint32_t>(), b->n, (uint32_t)n_patches, bad.as<uint32_t>());
+    if (rbtk::d2h(&is_bad, bad.p, 4) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  }
+  if (is_bad) { err = "a label of the decoded cloud is not below n_patches"; return RBT_ERR_PARAM; }      // no sum has been written
+  RbtScoreWork W; memset(&W, 0, sizeof(W));
+  W.dist_a = dist.as<uint32_t>(); W.dist_b = W.dist_a + na; W.res = res.as<unsigned long long>();
+  const RbtScoreCloud A = a->view(), B = b->view();
+  rbtk::timer_begin(T_COL_DIST);             // as pcloud_score: every call reads its timers before it returns
+  rbtk::launch_sc_score(&A, &B, RBT_SCORE_D1, &W);
+  rbtk::launch_pd_sums(&A, &B, b->labels.as<uint32_t>(), W.dist_a, W.dist_b, sums.as<unsigned long long>());
+  rbtk::timer_end(T_COL_DIST);
+  uint64_t h[RBT_SC_RESULTS]; std::vector<uint64_t> hw(words);
+  if (rbtk::d2h(h, res.p, sizeof(h)) || rbtk::d2h(hw.data(), sums.p, 8 * words) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (device_ms) *device_ms = rbtk::timer_ms(T_COL_DIST);
+  for (int k = 0; k < n_patches; k++) {
+    const uint64_t* w = &hw[(size_t)RBT_PD_WORDS * (size_t)k]; rbt_patch_d1* o = &out[k];
+    o->n_ab = (uint32_t)w[RBT_PD_N_AB]; o->n_ba = (uint32_t)w[RBT_PD_N_BA]; o->sse_ab = w[RBT_PD_SSE_AB]; o->sse_ba = w[RBT_PD_SSE_BA]; o->max_ab = w[RBT_PD_MAX_AB]; o->max_ba = w[RBT_PD_MAX_BA];
+    patch_d1_finish(o, peak);
+  }
+  if (whole) {
+    const uint32_t* mx = (const uint32_t*)&h[RBT_SC_D1_MAX];
+    whole->n_a = a->n_merged; whole->n_b = b->n_merged; whole->sse_ab = h[RBT_SC_D1_AB]; whole->sse_ba = h[RBT_SC_D1_BA]; whole->max_ab = mx[0]; whole->max_ba = mx[1];
+    finish_geometry(whole, peak);
+  }
   return RBT_OK;
 }
 

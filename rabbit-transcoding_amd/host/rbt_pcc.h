@@ -49,6 +49,13 @@ int gather_luma_host(std::string& err, const uint16_t* src, int n_pics, int stri
 int gather_420_host(std::string& err, const uint16_t* src, int n_pics, int stride, int rows, int cstride, int crows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out);
 // rbt_pcloud_set_colors: new RGB triples (3 per point, host) for an indexed cloud; only the colour sums and merged colours of its index are remade (csrc/rbt_score.h)
 int pcloud_set_colors(std::string& err, PCloud* c, const uint8_t* rgb);
+// D1 per patch of the decoded cloud (csrc/rbt_score.h, "patches"). A cloud of pcloud_from_maps / mapframe_cloud carries the patch index of every point; an uploaded
+// cloud gets labels (one per point, < 65536, host) through pcloud_set_labels. pcloud_score_patches: out holds n_patches entries; whole (what pcloud_d1 returns for
+// the two clouds) and device_ms may be null.
+int pcloud_set_labels(std::string& err, PCloud* c, const uint32_t* labels);
+int pcloud_labels(std::string& err, const PCloud* c, uint32_t* labels);
+bool pcloud_has_labels(const PCloud* c);
+int pcloud_score_patches(std::string& err, const PCloud* a, const PCloud* b, int peak, int n_patches, rbt_patch_d1* out, rbt_d1_result* whole, double* device_ms);
 // rbt_score_pair_*: the nearest squared distances of both directions between two indexed clouds, kept; pair_color runs the colour walks on them (out: what the colour
 // part of pcloud_score returns for the clouds' colours of the moment). The clouds must outlive the pair.
 struct ScorePair;

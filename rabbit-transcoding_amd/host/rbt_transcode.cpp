@@ -16,6 +16,7 @@
 #include "rbt_color_walk.h"
 #include "rbt_frame_walk.h"
 #include "rbt_patch_walk.h"
+#include "rbt_d1_figures.h"
 #include "rbt_qp_map.h"
 #include "rbt_pcc.h"
 #include "../csrc/rbt_cloudmaps.h"
@@ -501,7 +502,7 @@ struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0
 // Floors held patch by patch: the walk of one point-cloud frame (rbt_patch_walk.h) with what its last trial brought - the frame's NAL units, the sums of its two pictures,
 // the folded sums per patch and of the background, the map it was coded with - and the walks of one entry: per frame R_k in CTB units (the rectangles k_patch_fold reads, on
 // the device from the first round to the last) and the displayed samples of R_k in both pictures
-struct PatchFrame { PatchWalk w; std::vector<uint8_t> stream; QualitySums sums; std::vector<PatchSums> ps; uint64_t bg[3] = {0, 0, 0}; std::vector<int8_t> map; std::vector<int32_t> rects; std::vector<uint64_t> samples; size_t rect_off = 0; };
+struct PatchFrame { PatchWalk w; std::vector<uint8_t> stream; QualitySums sums; std::vector<rbt_patch_d1> pd; rbt_d1_result whole = rbt_d1_result(); std::vector<PatchSums> ps; uint64_t bg[3] = {0, 0, 0}; std::vector<int8_t> map; std::vector<int32_t> rects; std::vector<uint64_t> samples; size_t rect_off = 0; };
 struct PatchWalks {
   int q = 0, entry = 0, n_passes = 0, l2 = 5, wc = 0, hc = 0, W = 0, H = 0, bit_depth = 8; std::vector<PatchFrame> frames; int32_t* d_rects = nullptr;
   bool settled() const { for (const PatchFrame& f : frames) if (!f.w.settled) return false; return true; }
@@ -545,6 +546,7 @@ struct ColorEntry : CloudEntry { rbt_color_target t; int geo = -1; uint16_t* geo
 // what a pipeline's rounds leave of an entry with a cloud target: the walk's result - or the entry's own QP - and the frames' figures there
 template <class Result> struct FloorOut { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<Result> frames; double cloud_ms = 0; };
 struct PatchFloorOut { int q0 = 0, n_passes = 0, wc = 0, hc = 0, bit_depth = 8; uint64_t bytes = 0, pictures = 0; std::vector<int8_t> map; std::vector<rbt_patch_frame> frames; std::vector<rbt_patch_pick> picks; QualitySums sums; };
+struct PatchD1Out { int q0 = 0, n_passes = 0, wc = 0, hc = 0; uint64_t bytes = 0, pictures = 0; std::vector<int8_t> map; std::vector<rbt_patch_d1_frame> frames; std::vector<rbt_patch_d1_pick> picks; double cloud_ms = 0; };
 struct FrameFloorOut { int q0 = 0, n_passes = 0, bit_depth = 8; std::vector<rbt_frame_pick> frames; std::vector<rbt_d1_result> d1; double cloud_ms = 0; uint64_t bytes = 0, pictures = 0; QualitySums sums; };
 struct GofJob {
   int n = 0, slot = 0, ng = 0, rc = 0; GofKind kind = GOF_PLAIN;      // kind: which submit made the job, fixed there
@@ -581,6 +583,9 @@ struct GofJob {
   // floors held patch by patch (rbt_submit_gof_quality_patches): a job with quality floors that are all 0, like a job with cloud targets; the entries with a target walk
   // every frame's patches (RoundPipe::pwalks), the others are coded once at their own QP
   std::vector<PatchFloorIn> patch; std::vector<PatchFloorOut> pout;
+  // D1 floors held patch by patch (rbt_submit_gof_d1_patches): such a job with the figures taken from the trial's cloud - d1 holds the targets' clouds' side as in a job
+  // with D1 floors (no walk of its own: min_d1_mdb 0), every pass is scored by d1_score patch by patch (PatchFrame::pd, ::whole), no sums per CTB run
+  bool patch_d1 = false; std::vector<PatchD1Out> pdout;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   void color_release(int entry) {        // the frames' volumes go back to the context's cache; their streams have been waited for
     ColorEntry& E = color[entry];
@@ -1022,7 +1027,7 @@ static int round_sums_setup(GofJob& j, int gi) {
   }
   if (int rc = r.sse->upload()) { j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
   // floors held patch by patch: the luma of the same pairs CTB by CTB into the batch's arena, and per frame of a pass the folds of its rectangles behind the words above
-  if (j.patch.empty()) return 0;
+  if (j.patch.empty() || j.patch_d1) return 0;
   r.ctbsse.reset(new CtbSseSet()); CtbSseSet& cs = *r.ctbsse;
   size_t pic = 0, ctb_at = 0, fold_at = r.sse->pics.size() * RBT_SSE_WORDS;
   for (size_t e = 0; e < r.cands.size(); e++) {
@@ -1057,7 +1062,7 @@ static int launch_round(GofJob& j, int gi) {
   r.eb.reset(new EncodeBatch()); EncodeBatch& eb = *r.eb;
   int rc = round_fill_batch(j, gi, r.cands, eb);
   if (sums) for (const EncStreamDesc& d : eb.desc) eb.n_sums += (size_t)d.n_frames * RBT_SSE_WORDS;
-  for (size_t e = 0; e < r.cands.size() && !rc; e++) if (r.cands[e].pw >= 0) {      // floors held patch by patch: the folds behind the words per picture, the words per CTB
+  for (size_t e = 0; e < r.cands.size() && !rc && !j.patch_d1; e++) if (r.cands[e].pw >= 0) {      // floors held patch by patch: the folds behind the words per picture, the words per CTB
     const PatchWalks& pw = r.pwalks[(size_t)r.cands[e].pw];
     for (int f : r.cands[e].pass.frames) eb.n_sums += (pw.frames[(size_t)f].samples.size() + 2) * RBT_CTBSSE_WORDS;
     eb.n_ctb_words += (size_t)eb.desc[e].n_frames * pw.wc * pw.hc * RBT_CTBSSE_WORDS;
@@ -1115,6 +1120,7 @@ static int d1_prepare(GofJob& j, SubmitPlan& s, int gi) {
     int dw, dh; const int cnt = displayed(db, j.dec_of[gi][q], &dw, &dh);
     if (const char* why = cloud_fits_stream(E.t, dw, dh, cnt)) return refuse(i, why);
     if (j.per_frame && a.map_count != 2) return refuse(i, "floors held frame by frame need atlas.map_count 2: a point-cloud frame is the two pictures that are coded as a pair");
+    if (j.patch_d1 && a.map_count != 2) return refuse(i, "floors held patch by patch need atlas.map_count 2: a point-cloud frame is the two pictures that are coded as a pair");
     if (const char* why = cloud_fits_occupancy(j, s.occ_src[io], io, E.t, dw, dh, E)) return refuse(i, why);
     // memory: per frame the frame's maps (twice while a reference cloud is made), per frame without a handle a volume, one more for the trial being scored; the packed
     // planes of one trial and of the decoded input
@@ -1198,7 +1204,8 @@ struct D1Live {
 // The clouds of candidate e of the round in flight - stream `q` of the pipeline's group at one QP - against the entry's references: the luma of the encoder's
 // reconstructions (the displayed window starts at the picture's origin: make_param_sets pads at the right and at the bottom) is gathered into packed planes by one launch,
 // then frame after frame: cloud, index, search, release (one recycled volume). The round's encode has been waited for (encode_finish).
-static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, std::vector<rbt_d1_result>& out) {
+// per_patch (D1 floors held patch by patch): per frame of the pass the figures of its patches too - rbt_score_patches in place of the D1 part of rbt_score, out unchanged
+static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, std::vector<rbt_d1_result>& out, std::vector<std::vector<rbt_patch_d1>>* per_patch = nullptr) {
   const int i = j.groups[gi][q]; D1Entry& E = j.d1[i]; const rbt_atlas_params& a = E.t.atlas; PCloudCache& cache = *j.cloud_cache;
   const EncStreamDesc& d = eb.desc[e]; const int W = a.width, H = a.height, mc = a.map_count, nf = E.t.n_frames, peak = E.t.peak ? E.t.peak : 1023;
   const size_t ys = (size_t)W * H;
@@ -1209,13 +1216,17 @@ static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, s
   DevPlanes geo; GatherSet gs;
   if (!geo.alloc(ys * (size_t)d.n_frames)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
   out.assign(np, rbt_d1_result());
+  if (per_patch) per_patch->assign((size_t)np, {});
   rbtk::timer_begin(T_CENSUS);
   gs.add_coded(eb, e, W, H, geo.p);
   int rc = gs.launch(j.err);
   for (int i = 0; i < np && !rc; i++) {
     const int f = d.pic.empty() ? i : d.pic[(size_t)(mc * i)] / mc; PCloud* c = nullptr;
     rc = mapframe_cloud(j.err, cache, E.frames[f], geo.p + ys * (size_t)(mc * i), mc > 1 ? geo.p + ys * (size_t)(mc * i + 1) : nullptr, d.bd, &c, nullptr);
-    if (!rc) rc = pcloud_d1(j.err, E.ref[f] ? E.ref[f] : E.own_ref[f], c, peak, &out[i]);
+    if (!rc && per_patch) {
+      std::vector<rbt_patch_d1>& pp = (*per_patch)[(size_t)i]; pp.resize(E.patches[f].size());
+      rc = pcloud_score_patches(j.err, E.ref[f] ? E.ref[f] : E.own_ref[f], c, peak, (int)pp.size(), pp.data(), &out[i], nullptr);
+    } else if (!rc) rc = pcloud_d1(j.err, E.ref[f] ? E.ref[f] : E.own_ref[f], c, peak, &out[i]);
     pcloud_release(cache, c);
   }
   return cloud_timed(j, E, rc);
@@ -1372,13 +1383,23 @@ static int finish_round(GofJob& j, int gi) {
     const EncStreamDesc& d = r.eb->desc[e]; const RoundCand& c = r.cands[e]; QualitySums sums;
     if (c.pw >= 0) {      // a pass of patch walks: every frame it carried keeps this trial - NAL units, sums, folds, map - and takes the walk's step on it
       PatchWalks& pw = r.pwalks[(size_t)c.pw]; const int region = j.patch[pw.entry].t.region; const size_t per = (size_t)pw.wc * pw.hc;
+      std::vector<rbt_d1_result> whole; std::vector<std::vector<rbt_patch_d1>> clouds;      // D1 floors: the clouds of the frames the pass carried, in pass order, patch by patch
+      if (j.patch_d1) if (int rc = d1_score(j, gi, c.q, *r.eb, e, whole, &clouds)) return rc;
       for (size_t i = 0; i < c.pass.frames.size(); i++) {
         const size_t f = (size_t)c.pass.frames[i]; PatchFrame& F = pw.frames[f]; const size_t np = F.samples.size();
         frame_cut(outs[e], r.eb->pic_at[e], i, (size_t)d.gop, F.stream);
         F.sums = QualitySums();
         for (int k = 0; k < d.gop; k++, at++) quality_add_picture(F.sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
+        std::vector<double> fig(np); std::vector<char> meets(np);
+        if (j.patch_d1) {
+          F.pd.swap(clouds[i]); F.whole = whole[i];
+          for (size_t k = 0; k < np; k++) { fig[k] = patch_d1_figure(F.pd[k]); meets[k] = patch_d1_meets(F.pd[k], F.w.floor_mdb[k]); }
+          F.map.assign(c.qmap.begin() + (ptrdiff_t)(per * f), c.qmap.begin() + (ptrdiff_t)(per * (f + 1)));
+          patch_walk_step(F.w, fig.data(), meets.data());
+          continue;
+        }
         const uint64_t* w = &r.eb->sums[fold_at]; fold_at += (np + 2) * RBT_CTBSSE_WORDS;
-        F.ps.assign(np, PatchSums()); std::vector<double> fig(np); std::vector<char> meets(np);
+        F.ps.assign(np, PatchSums());
         for (size_t k = 0; k < np; k++) {
           PatchSums& s = F.ps[k]; s.sse = w[3 * k]; s.sse_occ = w[3 * k + 1]; s.samples_occ = w[3 * k + 2]; s.samples = F.samples[k];
           fig[k] = patch_figure(s, region, pw.bit_depth); meets[k] = patch_meets(s, region, F.w.floor_mdb[k], pw.bit_depth);
@@ -1494,6 +1515,23 @@ static void fill_frame_results(GofJob& j, int gi) {
 }
 // ... and of a pipeline whose entries walked patch by patch: per frame its trials, bytes, background and the picks of its settling trial; the final map; the stream assembled
 // from the frames' NAL units (rule 7). The entries without a target keep their only encode (r.o1) and its sums
+static void fill_patch_d1_results(GofJob& j, int gi) {
+  RoundPipe& r = j.pipes[gi];
+  j.pdout.resize(j.n);
+  for (const PatchWalks& pw : r.pwalks) {
+    PatchD1Out& o = j.pdout[pw.entry]; std::vector<uint8_t>& out = r.o1[pw.q];
+    out.clear(); o.n_passes = pw.n_passes; o.wc = pw.wc; o.hc = pw.hc; o.cloud_ms = j.d1[pw.entry].cloud_ms;
+    for (const PatchFrame& F : pw.frames) {
+      out.insert(out.end(), F.stream.begin(), F.stream.end()); o.map.insert(o.map.end(), F.map.begin(), F.map.end());
+      o.q0 = F.w.q0; o.pictures += 2 * (uint64_t)F.w.n_trials;
+      rbt_patch_d1_frame pf; memset(&pf, 0, sizeof(pf));
+      pf.n_trials = F.w.n_trials; pf.met = 1; pf.n_patches = (int)F.pd.size(); pf.bytes = F.stream.size(); pf.d1 = F.whole;
+      for (size_t k = 0; k < F.pd.size(); k++) { pf.met &= F.w.met[k]; o.picks.push_back(rbt_patch_d1_pick{F.w.q[k], F.w.met[k], F.w.failed[k], F.pd[k], F.w.figure[k]}); }
+      o.frames.push_back(pf);
+    }
+    o.bytes = out.size();
+  }
+}
 static void fill_patch_results(GofJob& j, int gi) {
   RoundPipe& r = j.pipes[gi]; const std::vector<int>& gs = j.groups[gi];
   j.pout.resize(j.n);
@@ -1544,6 +1582,7 @@ static int run_rounds(GofJob& j, int gi) {
   for (const TargetWalk& w : r.walks) if (!w.settled) { j.err = "internal: QP walk did not settle"; return RBT_ERR_PARAM; }
   for (const FrameWalks<TargetWalk>& fw : r.fwalks) if (!fw.settled()) { j.err = "internal: QP walk did not settle"; return RBT_ERR_PARAM; }
   for (const PatchWalks& pw : r.pwalks) if (!pw.settled()) { j.err = "internal: patch walk did not settle"; return RBT_ERR_PARAM; }
+  if (j.patch_d1) { fill_patch_d1_results(j, gi); return 0; }
   if (!j.patch.empty()) { fill_patch_results(j, gi); return 0; }
   if (j.per_frame) { fill_frame_results(j, gi); return 0; }
   fill_results(j, gi);
@@ -1754,7 +1793,8 @@ GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   GofJob* J = new GofJob(); GofJob& j = *J;
   const int n = r.n; const rbt_stream_params* p = r.params;
   j.per_frame = r.per_frame && (r.quality || r.d1);
-  j.kind = r.patch_floors ? GOF_QUALITY_PATCHES : r.color ? GOF_COLOR : r.d1 ? (j.per_frame ? GOF_D1_FRAMES : GOF_D1) : r.quality ? (j.per_frame ? GOF_QUALITY_FRAMES : GOF_QUALITY) : GOF_PLAIN;
+  j.patch_d1 = r.patch_d1 && r.patch_floors && r.d1;
+  j.kind = j.patch_d1 ? GOF_D1_PATCHES : r.patch_floors ? GOF_QUALITY_PATCHES : r.color ? GOF_COLOR : r.d1 ? (j.per_frame ? GOF_D1_FRAMES : GOF_D1) : r.quality ? (j.per_frame ? GOF_QUALITY_FRAMES : GOF_QUALITY) : GOF_PLAIN;
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
   j.params.assign(p, p + n); j.n_in.assign(r.n_in, r.n_in + n);
@@ -1766,6 +1806,7 @@ GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   if (r.color) keep_cloud_targets(j, j.color, *r.color);
   if (r.patch_floors) {      // runs as a job with quality floors that are all 0, in each entry's region
     j.patch = *r.patch_floors; j.qocc.assign(n, QualityOcc());
+    j.qtargets.clear();      // (a job with D1 floors held patch by patch has passed keep_cloud_targets above, which filled them; a job with PSNR floors per patch comes here with none)
     for (int i = 0; i < n; i++) j.qtargets.push_back(rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, j.patch[i].t.region, 0, 0});
   }
   SubmitPlan s; s.in = r.in; s.p = p; s.gof_rule = r.gof_rule;
@@ -1881,6 +1922,23 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResult
       o.picks = (rbt_patch_pick*)malloc(sizeof(rbt_patch_pick) * std::max<size_t>(1, r.picks.size()));
       if (!o.map || !o.frames || !o.picks) { rc = RBT_ERR_NOMEM; break; }
       memcpy(o.map, r.map.data(), r.map.size()); memcpy(o.frames, r.frames.data(), sizeof(rbt_patch_frame) * r.frames.size()); memcpy(o.picks, r.picks.data(), sizeof(rbt_patch_pick) * r.picks.size());
+      size_t at = 0; for (int f = 0; f < o.n_frames; f++) { o.frames[f].patches = o.picks + at; at += (size_t)o.frames[f].n_patches; }
+    }
+    if (rc) for (int i = 0; i < n; i++) { free(pres[i].map); free(pres[i].frames); free(pres[i].picks); memset(&pres[i], 0, sizeof(pres[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; }
+  }
+  if (rbt_patch_d1_result* pres = res.d1_patches) {
+    for (int i = 0; i < n; i++) memset(&pres[i], 0, sizeof(pres[i]));
+    for (int i = 0; i < n && !rc; i++) {
+      rbt_patch_d1_result& o = pres[i];
+      o.qp_probe = p[i].qp; o.met_all = 1; o.bytes = (uint64_t)n_out[i];
+      if (i >= (int)j.pdout.size() || j.pdout[i].frames.empty()) continue;
+      const PatchD1Out& r = j.pdout[i];
+      o.n_frames = (int)r.frames.size(); o.qp_probe = r.q0; o.n_passes = r.n_passes; o.pictures_encoded = r.pictures; o.w_ctb = r.wc; o.h_ctb = r.hc; o.cloud_ms = r.cloud_ms;
+      for (const rbt_patch_d1_frame& f : r.frames) o.met_all &= f.met;
+      o.map = (int8_t*)malloc(std::max<size_t>(1, r.map.size())); o.frames = (rbt_patch_d1_frame*)malloc(sizeof(rbt_patch_d1_frame) * r.frames.size());
+      o.picks = (rbt_patch_d1_pick*)malloc(sizeof(rbt_patch_d1_pick) * std::max<size_t>(1, r.picks.size()));
+      if (!o.map || !o.frames || !o.picks) { rc = RBT_ERR_NOMEM; break; }
+      memcpy(o.map, r.map.data(), r.map.size()); memcpy(o.frames, r.frames.data(), sizeof(rbt_patch_d1_frame) * r.frames.size()); memcpy(o.picks, r.picks.data(), sizeof(rbt_patch_d1_pick) * r.picks.size());
       size_t at = 0; for (int f = 0; f < o.n_frames; f++) { o.frames[f].patches = o.picks + at; at += (size_t)o.frames[f].n_patches; }
     }
     if (rc) for (int i = 0; i < n; i++) { free(pres[i].map); free(pres[i].frames); free(pres[i].picks); memset(&pres[i], 0, sizeof(pres[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; }

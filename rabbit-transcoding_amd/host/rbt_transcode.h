@@ -29,16 +29,19 @@ struct GofRequest {
   // the entry's own QP; not together with anything else
   const std::vector<QpMapIn>* qp_maps = nullptr;
   const std::vector<PatchFloorIn>* patch_floors = nullptr;   // PSNR floors held patch by patch (rbt_submit_gof_quality_patches); not together with anything else
+  // D1 floors held patch by patch (rbt_submit_gof_d1_patches): patch_floors carries the walks' side of the targets (floors, range, background, cap; min_psnr_mdb holds
+  // min_d1_mdb) and d1 their clouds' side (atlas, patch lists, references, peak; min_d1_mdb 0: no walk of its own)
+  bool patch_d1 = false;
 };
 // Where a job's outcome goes: a stream per entry, and of the result arrays - one per entry each - the one of the job's kind; n_flat: nullptr, or the decoded pictures with flat chroma
 struct GofResults {
   uint8_t** out = nullptr; size_t* n_out = nullptr; int* n_flat = nullptr;
-  rbt_rate_result* rate = nullptr; rbt_quality_result* quality = nullptr; rbt_d1_floor_result* d1 = nullptr; rbt_color_floor_result* color = nullptr; rbt_frame_floor_result* frames = nullptr; rbt_patch_floor_result* patches = nullptr;
+  rbt_rate_result* rate = nullptr; rbt_quality_result* quality = nullptr; rbt_d1_floor_result* d1 = nullptr; rbt_color_floor_result* color = nullptr; rbt_frame_floor_result* frames = nullptr; rbt_patch_floor_result* patches = nullptr; rbt_patch_d1_result* d1_patches = nullptr;
 };
 GofJob* gof_submit(int slot, int depth, const GofRequest& r);
 int gof_wait(GofJob* j, rbt_stats& st, std::string& err, const GofResults& r);   // consumes the job
 // which submit made the job, in the order the wait half tells a mismatch (rbt_api.cpp wait): the lower of two kinds that differ is the one the message names
-enum GofKind { GOF_PLAIN, GOF_QUALITY, GOF_D1, GOF_COLOR, GOF_D1_FRAMES, GOF_QUALITY_FRAMES, GOF_QUALITY_PATCHES };   // GOF_PLAIN: constant QPs, QP lists, QP maps and byte budgets
+enum GofKind { GOF_PLAIN, GOF_QUALITY, GOF_D1, GOF_COLOR, GOF_D1_FRAMES, GOF_QUALITY_FRAMES, GOF_QUALITY_PATCHES, GOF_D1_PATCHES };   // GOF_PLAIN: constant QPs, QP lists, QP maps and byte budgets
 GofKind gof_kind(const GofJob* j);
 int gof_refused(const GofJob* j, std::string& err);   // != 0: the job's plan was refused before anything was built or enqueued (the code; the reason in err)
 void gof_abandon(GofJob* j);
