@@ -838,30 +838,6 @@ class Context:
         """rbt_transcode_gof_qp_map: submit + wait"""
         return self.wait_gof(self.submit_gof_qp_map(streams, params, maps))
 
-    def submit_gof_rate(self, streams, params, targets):
-        """rbt_submit_gof_rate: submit_gof with one RateTarget per entry (target_bytes 0 = constant QP); returns a job for wait_gof_rate"""
-        return self._submit(self.L.rbt_submit_gof_rate, streams, params, targets, RateTarget)
-
-    def wait_gof_rate(self, job):
-        """rbt_wait_gof_rate -> ([stream bytes, ...], [result dict, ...])"""
-        return self._collect(self.L.rbt_wait_gof_rate, job[1], [job[0]], RateResult)
-
-    def transcode_gof_rate(self, streams, params, targets):
-        """rbt_transcode_gof_rate: submit + wait"""
-        return self._transcode(self.L.rbt_transcode_gof_rate, streams, params, targets, RateTarget, RateResult)
-
-    def submit_gof_quality(self, streams, params, targets):
-        """rbt_submit_gof_quality: submit_gof with one QualityTarget per entry (min_psnr_mdb 0 = constant QP, distortion reported); returns a job for wait_gof_quality"""
-        return self._submit(self.L.rbt_submit_gof_quality, streams, params, targets, QualityTarget)
-
-    def wait_gof_quality(self, job):
-        """rbt_wait_gof_quality -> ([stream bytes, ...], [result dict, ...])"""
-        return self._collect(self.L.rbt_wait_gof_quality, job[1], [job[0]], QualityResult)
-
-    def transcode_gof_quality(self, streams, params, targets):
-        """rbt_transcode_gof_quality: submit + wait"""
-        return self._transcode(self.L.rbt_transcode_gof_quality, streams, params, targets, QualityTarget, QualityResult)
-
     def _frame_results(self, res):
         """([stream bytes, ...], [FrameFloorResult, ...] as dicts): frames becomes a list of pick dicts, sums a dict, and the library's array is released"""
         outs, rs = res
@@ -875,85 +851,19 @@ class Context:
             self.L.rbt_free(d1)
         return outs, rs
 
-    def submit_gof_d1_frames(self, streams, params, targets):
-        """rbt_submit_gof_d1_frames: submit_gof_d1 with the floor held by every point-cloud frame on its own (stat must be RBT_D1_MIN); returns a job for wait_gof_d1_frames"""
-        return self._submit(self.L.rbt_submit_gof_d1_frames, streams, params, targets, D1Target)
-
-    def wait_gof_d1_frames(self, job):
-        """rbt_wait_gof_d1_frames -> ([stream bytes, ...], [result dict, ...]); d1: the D1 dict of every frame at its pick"""
-        return self._frame_results(self._collect(self.L.rbt_wait_gof_d1_frames, job[1], [job[0]], FrameFloorResult))
-
-    def transcode_gof_d1_frames(self, streams, params, targets):
-        """rbt_transcode_gof_d1_frames: submit + wait"""
-        args = self._gof_args(streams, params, targets, D1Target)
-        return self._frame_results(self._collect(self.L.rbt_transcode_gof_d1_frames, args[0], args, FrameFloorResult))
-
-    def submit_gof_quality_frames(self, streams, params, targets):
-        """rbt_submit_gof_quality_frames: submit_gof_quality with the floor held by every point-cloud frame on its own; returns a job for wait_gof_quality_frames"""
-        return self._submit(self.L.rbt_submit_gof_quality_frames, streams, params, targets, QualityTarget)
-
-    def wait_gof_quality_frames(self, job):
-        """rbt_wait_gof_quality_frames -> ([stream bytes, ...], [result dict, ...])"""
-        return self._frame_results(self._collect(self.L.rbt_wait_gof_quality_frames, job[1], [job[0]], FrameFloorResult))
-
-    def transcode_gof_quality_frames(self, streams, params, targets):
-        """rbt_transcode_gof_quality_frames: submit + wait"""
-        args = self._gof_args(streams, params, targets, QualityTarget)
-        return self._frame_results(self._collect(self.L.rbt_transcode_gof_quality_frames, args[0], args, FrameFloorResult))
-
-    def _patch_results(self, res):
-        """([stream bytes, ...], [PatchFloorResult, ...] as dicts): map becomes an int8 array [n_frames, h_ctb, w_ctb] (None without a target), frames a list of dicts whose
-        patches are pick dicts, sums a dict, and the library's arrays are released"""
+    def _patch_results(self, res, frame_dict=_result_dict, pick_dict=_result_dict):
+        """([stream bytes, ...], [PatchFloorResult or PatchD1Result, ...] as dicts): map becomes an int8 array [n_frames, h_ctb, w_ctb] (None without a target), frames a list
+        of dicts (frame_dict of the frame) whose patches are pick dicts (pick_dict of the pick), sums (the PSNR kind's) a dict, and the library's arrays are released"""
         outs, rs = res
         for r in rs:
             fr, mp = r["frames"], r["map"]
-            r["frames"] = [dict(_result_dict(fr[f]), patches=[_result_dict(fr[f].patches[k]) for k in range(fr[f].n_patches)]) for f in range(r["n_frames"])] if fr else []
+            r["frames"] = [dict(frame_dict(fr[f]), patches=[pick_dict(fr[f].patches[k]) for k in range(fr[f].n_patches)]) for f in range(r["n_frames"])] if fr else []
             r["map"] = np.ctypeslib.as_array(mp, (r["n_frames"], r["h_ctb"], r["w_ctb"])).copy() if mp else None
             for ptr in (fr, mp, r.pop("picks")):
                 self.L.rbt_free(ptr)
-            r["sums"] = _result_dict(r["sums"])
+            if "sums" in r:
+                r["sums"] = _result_dict(r["sums"])
         return outs, rs
-
-    def submit_gof_quality_patches(self, streams, params, targets):
-        """rbt_submit_gof_quality_patches: submit_gof with one PatchFloorTarget per entry (PatchFloorTarget() = none): every patch of every frame holds its floor; returns a
-        job for wait_gof_quality_patches"""
-        return self._submit(self.L.rbt_submit_gof_quality_patches, streams, params, targets, PatchFloorTarget)
-
-    def wait_gof_quality_patches(self, job):
-        """rbt_wait_gof_quality_patches -> ([stream bytes, ...], [result dict, ...])"""
-        return self._patch_results(self._collect(self.L.rbt_wait_gof_quality_patches, job[1], [job[0]], PatchFloorResult))
-
-    def transcode_gof_quality_patches(self, streams, params, targets):
-        """rbt_transcode_gof_quality_patches: submit + wait"""
-        args = self._gof_args(streams, params, targets, PatchFloorTarget)
-        return self._patch_results(self._collect(self.L.rbt_transcode_gof_quality_patches, args[0], args, PatchFloorResult))
-
-    def _patch_d1_results(self, res):
-        """([stream bytes, ...], [PatchD1Result, ...] as dicts): map becomes an int8 array [n_frames, h_ctb, w_ctb] (None without a target), frames a list of dicts with the
-        whole frame's d1 as a dict and patches as pick dicts (d1: a patch_d1_dict), and the library's arrays are released"""
-        outs, rs = res
-        for r in rs:
-            fr, mp = r["frames"], r["map"]
-            r["frames"] = [dict(_result_dict(fr[f]), d1=_result_dict(fr[f].d1), patches=[dict(_result_dict(fr[f].patches[k]), d1=patch_d1_dict(fr[f].patches[k].d1)) for k in range(fr[f].n_patches)])
-                           for f in range(r["n_frames"])] if fr else []
-            r["map"] = np.ctypeslib.as_array(mp, (r["n_frames"], r["h_ctb"], r["w_ctb"])).copy() if mp else None
-            for ptr in (fr, mp, r.pop("picks")):
-                self.L.rbt_free(ptr)
-        return outs, rs
-
-    def submit_gof_d1_patches(self, streams, params, targets):
-        """rbt_submit_gof_d1_patches: submit_gof with one PatchD1Target per entry (PatchD1Target() = none): every patch of every frame of a geometry entry holds its D1
-        floor; returns a job for wait_gof_d1_patches"""
-        return self._submit(self.L.rbt_submit_gof_d1_patches, streams, params, targets, PatchD1Target)
-
-    def wait_gof_d1_patches(self, job):
-        """rbt_wait_gof_d1_patches -> ([stream bytes, ...], [result dict, ...])"""
-        return self._patch_d1_results(self._collect(self.L.rbt_wait_gof_d1_patches, job[1], [job[0]], PatchD1Result))
-
-    def transcode_gof_d1_patches(self, streams, params, targets):
-        """rbt_transcode_gof_d1_patches: submit + wait"""
-        args = self._gof_args(streams, params, targets, PatchD1Target)
-        return self._patch_d1_results(self._collect(self.L.rbt_transcode_gof_d1_patches, args[0], args, PatchD1Result))
 
     def ctb_sse(self, a, b, w, h, log2_ctb=5, occ=None, rects=None):
         """rbt_ctb_sse: planar 4:2:0 pictures a, b ([n, w*h*3/2] uint16), or None one occupancy plane per picture ([n, oh, ow] uint16), or None rectangles [[c0, r0, c1, r1],
@@ -988,19 +898,6 @@ class Context:
             self.L.rbt_free(ptr)
         return outs, rs
 
-    def submit_gof_d1(self, streams, params, targets):
-        """rbt_submit_gof_d1: submit_gof with one D1Target per entry (D1Target() = none; min_d1_mdb 0 = constant QP, D1 reported); returns a job for wait_gof_d1"""
-        return self._submit(self.L.rbt_submit_gof_d1, streams, params, targets, D1Target)
-
-    def wait_gof_d1(self, job):
-        """rbt_wait_gof_d1 -> ([stream bytes, ...], [result dict, ...])"""
-        return self._d1_results(self._collect(self.L.rbt_wait_gof_d1, job[1], [job[0]], D1FloorResult))
-
-    def transcode_gof_d1(self, streams, params, targets):
-        """rbt_transcode_gof_d1: submit + wait"""
-        args = self._gof_args(streams, params, targets, D1Target)
-        return self._d1_results(self._collect(self.L.rbt_transcode_gof_d1, args[0], args, D1FloorResult))
-
     def _color_results(self, res):
         """([stream bytes, ...], [ColorFloorResult, ...] as dicts): frames becomes a list of colour dicts (Context.color_metric's) and the library's array is released"""
         outs, rs = res
@@ -1010,20 +907,6 @@ class Context:
             r["mean_psnr"], r["min_psnr"] = list(r["mean_psnr"]), list(r["min_psnr"])
             self.L.rbt_free(ptr)
         return outs, rs
-
-    def submit_gof_color(self, streams, params, targets):
-        """rbt_submit_gof_color: submit_gof with one ColorTarget per entry (ColorTarget() = none; min_psnr_mdb 0 = constant QP, colour results reported); returns a job for
-        wait_gof_color"""
-        return self._submit(self.L.rbt_submit_gof_color, streams, params, targets, ColorTarget)
-
-    def wait_gof_color(self, job):
-        """rbt_wait_gof_color -> ([stream bytes, ...], [result dict, ...])"""
-        return self._color_results(self._collect(self.L.rbt_wait_gof_color, job[1], [job[0]], ColorFloorResult))
-
-    def transcode_gof_color(self, streams, params, targets):
-        """rbt_transcode_gof_color: submit + wait"""
-        args = self._gof_args(streams, params, targets, ColorTarget)
-        return self._color_results(self._collect(self.L.rbt_transcode_gof_color, args[0], args, ColorFloorResult))
 
     def gather_luma(self, src, x0, y0, w, h, src_misalign=0):
         """rbt_gather_luma: planes src ([n, rows, stride] uint16) -> the w x h window at (x0, y0) of each, packed ([n, h, w]); the planes lie src_misalign samples behind
@@ -1323,3 +1206,50 @@ class Context:
         s = Stats()
         self._chk(self.L.rbt_get_stats(self.h, C.byref(s)))
         return {n: getattr(s, n) for n, _ in Stats._fields_}
+
+
+# The jobs with targets and results: Context.submit_gof_<name>, .wait_gof_<name> and .transcode_gof_<name> over rbt_submit_gof_<name>, rbt_wait_gof_<name> and
+# rbt_transcode_gof_<name>. Per name: the target type, the result type, how ([stream bytes, ...], [result dict, ...]) is finished (None: as it is), what the targets are
+# (submit's docstring) and what wait's docstring adds
+_GOF_KINDS = {
+    "rate": (RateTarget, RateResult, None, "submit_gof with one RateTarget per entry (target_bytes 0 = constant QP)", ""),
+    "quality": (QualityTarget, QualityResult, None, "submit_gof with one QualityTarget per entry (min_psnr_mdb 0 = constant QP, distortion reported)", ""),
+    "d1_frames": (D1Target, FrameFloorResult, Context._frame_results, "submit_gof_d1 with the floor held by every point-cloud frame on its own (stat must be RBT_D1_MIN)",
+                  "; d1: the D1 dict of every frame at its pick"),
+    "quality_frames": (QualityTarget, FrameFloorResult, Context._frame_results, "submit_gof_quality with the floor held by every point-cloud frame on its own", ""),
+    "quality_patches": (PatchFloorTarget, PatchFloorResult, Context._patch_results,
+                        "submit_gof with one PatchFloorTarget per entry (PatchFloorTarget() = none): every patch of every frame holds its floor", ""),
+    # a frame with the whole frame's d1 as a dict, a pick with its d1 as a patch_d1_dict
+    "d1_patches": (PatchD1Target, PatchD1Result,
+                   lambda self, res: self._patch_results(res, lambda f: dict(_result_dict(f), d1=_result_dict(f.d1)), lambda p: dict(_result_dict(p), d1=patch_d1_dict(p.d1))),
+                   "submit_gof with one PatchD1Target per entry (PatchD1Target() = none): every patch of every frame of a geometry entry holds its D1 floor", ""),
+    "d1": (D1Target, D1FloorResult, Context._d1_results, "submit_gof with one D1Target per entry (D1Target() = none; min_d1_mdb 0 = constant QP, D1 reported)", ""),
+    "color": (ColorTarget, ColorFloorResult, Context._color_results,
+              "submit_gof with one ColorTarget per entry (ColorTarget() = none; min_psnr_mdb 0 = constant QP, colour results reported)", ""),
+}
+
+
+def _gof_kind(name, target_type, result_type, finish, what, wait_adds):
+    finish = finish or (lambda self, res: res)
+
+    def submit(self, streams, params, targets):
+        return self._submit(getattr(self.L, "rbt_submit_gof_" + name), streams, params, targets, target_type)
+
+    def wait(self, job):
+        return finish(self, self._collect(getattr(self.L, "rbt_wait_gof_" + name), job[1], [job[0]], result_type))
+
+    def transcode(self, streams, params, targets):
+        args = self._gof_args(streams, params, targets, target_type)
+        return finish(self, self._collect(getattr(self.L, "rbt_transcode_gof_" + name), args[0], args, result_type))
+
+    submit.__doc__ = "rbt_submit_gof_%s: %s; returns a job for wait_gof_%s" % (name, what, name)
+    wait.__doc__ = "rbt_wait_gof_%s -> ([stream bytes, ...], [result dict, ...])%s" % (name, wait_adds)
+    transcode.__doc__ = "rbt_transcode_gof_%s: submit + wait" % name
+    for f, part in ((submit, "submit"), (wait, "wait"), (transcode, "transcode")):
+        f.__name__ = "%s_gof_%s" % (part, name)
+        f.__qualname__ = "Context." + f.__name__
+        setattr(Context, f.__name__, f)
+
+
+for _name, _kind in _GOF_KINDS.items():
+    _gof_kind(_name, *_kind)

@@ -51,6 +51,39 @@ template <class Target> static int check_cloud_target(rbt_ctx* ctx, const std::s
   return RBT_OK;
 }
 
+// Floors held patch by patch: the refusals the two kinds of target share (Target: rbt_patch_floor_target / rbt_patch_d1_target, floors: its floors per patch), behind those of
+// the kind's own fields; o: the request the walks read, with the patch lists and the floors F_k copied - floor_mdb where a patch has none of its own
+template <class Target> static int fill_patch_request(std::string& err, const std::string& who, const rbt_stream_params& p, const Target& t, int32_t floor_mdb, int region, const int32_t* const* floors,
+                                                      rbt::PatchFloorIn& o) {
+  const int lo = t.qp_min, hi = t.qp_max ? t.qp_max : 51;
+  if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
+  if (t.background_qp < -1 || t.background_qp > 51) { err = who + "background_qp is outside -1..51 (-1 = the probe's QP)"; return RBT_ERR_PARAM; }
+  if (t.max_trials < 0) { err = who + "max_trials must not be negative (0 = no cap)"; return RBT_ERR_PARAM; }
+  if (t.n_frames < 1 || !t.patches || !t.n_patches) { err = who + "a patch target needs n_frames = pictures / 2 with a patch list and a count per frame"; return RBT_ERR_PARAM; }
+  if (t.atlas.width < 1 || t.atlas.height < 1 || t.atlas.occupancy_resolution < 1) { err = who + "the atlas needs a size and an occupancy_resolution"; return RBT_ERR_PARAM; }
+  if (p.log2_ctb && (p.log2_ctb < 4 || p.log2_ctb > 6)) { err = who + "log2_ctb must be 4..6"; return RBT_ERR_PARAM; }
+  for (int f = 0; f < t.n_frames; f++) {
+    const int np = t.n_patches[f];
+    if (np < 0 || (np > 0 && !t.patches[f])) { err = who + "frame " + std::to_string(f) + " has a patch count without a list"; return RBT_ERR_PARAM; }
+    o.patches.emplace_back(np ? t.patches[f] : nullptr, np ? t.patches[f] + np : nullptr);
+    const int32_t* fl = floors ? floors[f] : nullptr;
+    o.floors.emplace_back((size_t)np, floor_mdb);
+    for (int k = 0; k < np && fl; k++) { if (fl[k] < 0) { err = who + "the floor of patch " + std::to_string(k) + " of frame " + std::to_string(f) + " is negative"; return RBT_ERR_PARAM; } o.floors.back()[(size_t)k] = fl[k]; }
+  }
+  o.floor_mdb = floor_mdb; o.region = region; o.qp_min = t.qp_min; o.qp_max = t.qp_max; o.background_qp = t.background_qp; o.max_trials = t.max_trials;
+  o.atlas_width = t.atlas.width; o.atlas_height = t.atlas.height; o.occupancy_resolution = t.atlas.occupancy_resolution; o.n_frames = t.n_frames;
+  return RBT_OK;
+}
+// submit + wait, what every rbt_transcode_gof_* with targets and results is: the two named halves of its kind, one behind the other
+template <class Target, class Result>
+static int transcode(int (*submit_kind)(rbt_ctx*, int, const uint8_t* const*, const size_t*, const rbt_stream_params*, const Target*, rbt_job**), int (*wait_kind)(rbt_ctx*, rbt_job*, uint8_t**, size_t*, Result*),
+                     rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const Target* targets, uint8_t** annexb_out, size_t* n_out, Result* results) {
+  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
+  rbt_job* job = nullptr;
+  if (int rc = submit_kind(ctx, n, annexb_in, n_in, p, targets, &job)) return rc;
+  return wait_kind(ctx, job, annexb_out, n_out, results);
+}
+
 extern "C" {
 
 const char* rbt_version(void) { return "rabbit-transcoding_amd 0.1 (RBT-E1 encoder, gfx950)"; }
@@ -291,13 +324,11 @@ static int check_qp_maps(std::string& err, int n, const rbt_stream_params* p, co
   }
   return RBT_OK;
 }
-// the refusals of rbt_submit_gof_quality_patches that the parameters alone decide (the counts and the atlas against the stream's pictures: gof_refused); out: the targets
-// with their patch lists and floors copied
+// the refusals of rbt_submit_gof_quality_patches that the parameters alone decide (the counts and the atlas against the stream's pictures: gof_refused); out: the requests
 static int check_patch_floors(std::string& err, int n, const rbt_stream_params* p, const rbt_patch_floor_target* t, std::vector<rbt::PatchFloorIn>& out) {
   out.assign((size_t)n, rbt::PatchFloorIn());
   for (int i = 0; i < n; i++) {
     const std::string who = "entry " + std::to_string(i) + ": ";
-    rbt::PatchFloorIn& o = out[(size_t)i]; memset(&o.t, 0, sizeof(o.t));
     if (t[i].struct_size != sizeof(rbt_patch_floor_target)) { err = who + "rbt_patch_floor_target.struct_size is not sizeof(rbt_patch_floor_target)"; return RBT_ERR_PARAM; }
     rbt_patch_floor_target zero; memset(&zero, 0, sizeof(zero));
     const bool empty = !t[i].min_psnr_mdb && !t[i].region && !t[i].qp_min && !t[i].qp_max && !t[i].background_qp && !t[i].max_trials && !t[i].n_frames && !t[i].patches && !t[i].n_patches &&
@@ -306,36 +337,21 @@ static int check_patch_floors(std::string& err, int n, const rbt_stream_params* 
     if (p[i].video_type == RBT_VIDEO_OCCUPANCY) { err = who + "an occupancy stream is coded losslessly and takes no PSNR floor (its target must be empty)"; return RBT_ERR_PARAM; }
     if (t[i].min_psnr_mdb < 0) { err = who + "min_psnr_mdb must not be negative"; return RBT_ERR_PARAM; }
     if (t[i].region != RBT_QUALITY_ALL && t[i].region != RBT_QUALITY_OCCUPIED) { err = who + "region must be RBT_QUALITY_ALL or RBT_QUALITY_OCCUPIED"; return RBT_ERR_PARAM; }
-    const int lo = t[i].qp_min, hi = t[i].qp_max ? t[i].qp_max : 51;
-    if (lo < 0 || hi > 51 || lo > hi) { err = who + "the QP range must satisfy 0 <= qp_min <= qp_max <= 51 (qp_max 0 = 51)"; return RBT_ERR_PARAM; }
-    if (t[i].background_qp < -1 || t[i].background_qp > 51) { err = who + "background_qp is outside -1..51 (-1 = the probe's QP)"; return RBT_ERR_PARAM; }
-    if (t[i].max_trials < 0) { err = who + "max_trials must not be negative (0 = no cap)"; return RBT_ERR_PARAM; }
-    if (t[i].n_frames < 1 || !t[i].patches || !t[i].n_patches) { err = who + "a patch target needs n_frames = pictures / 2 with a patch list and a count per frame"; return RBT_ERR_PARAM; }
-    if (t[i].atlas.width < 1 || t[i].atlas.height < 1 || t[i].atlas.occupancy_resolution < 1) { err = who + "the atlas needs a size and an occupancy_resolution"; return RBT_ERR_PARAM; }
-    if (p[i].log2_ctb && (p[i].log2_ctb < 4 || p[i].log2_ctb > 6)) { err = who + "log2_ctb must be 4..6"; return RBT_ERR_PARAM; }
-    for (int f = 0; f < t[i].n_frames; f++) {
-      const int np = t[i].n_patches[f];
-      if (np < 0 || (np > 0 && !t[i].patches[f])) { err = who + "frame " + std::to_string(f) + " has a patch count without a list"; return RBT_ERR_PARAM; }
-      o.patches.emplace_back(np ? t[i].patches[f] : nullptr, np ? t[i].patches[f] + np : nullptr);
-      const int32_t* fl = t[i].patch_min_psnr_mdb ? t[i].patch_min_psnr_mdb[f] : nullptr;
-      o.floors.emplace_back((size_t)np, t[i].min_psnr_mdb);
-      for (int k = 0; k < np && fl; k++) { if (fl[k] < 0) { err = who + "the floor of patch " + std::to_string(k) + " of frame " + std::to_string(f) + " is negative"; return RBT_ERR_PARAM; } o.floors.back()[(size_t)k] = fl[k]; }
-    }
-    o.t = t[i]; o.t.patches = nullptr; o.t.n_patches = nullptr; o.t.patch_min_psnr_mdb = nullptr;
+    if (int rc = fill_patch_request(err, who, p[i], t[i], t[i].min_psnr_mdb, t[i].region, t[i].patch_min_psnr_mdb, out[(size_t)i])) return rc;
   }
   return RBT_OK;
 }
-// The refusals of rbt_submit_gof_d1_patches that the parameters alone decide. A target is split in two: its walks' side becomes a patch-floor target (floors, range,
-// background, cap; min_psnr_mdb holds min_d1_mdb) and goes through check_patch_floors, its clouds' side a D1 target without a floor of its own (atlas, patch lists,
-// references, peak) and goes through check_d1. as_patch / as_d1 / floors: the two arrays and the floor pointers they refer to, alive until submit returns.
-static int check_d1_patches(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_patch_d1_target* t, std::vector<rbt_patch_floor_target>& as_patch, std::vector<rbt_d1_target>& as_d1,
-                            std::vector<rbt::PatchFloorIn>& out, rbt::CloudRequest<rbt_d1_target>& req) {
+// The refusals of rbt_submit_gof_d1_patches that the parameters alone decide, in three rounds over the entries as their order of precedence has it: the target's own fields,
+// the walks' side (out, fill_patch_request) and the clouds' side (req, check_d1). as_d1: the clouds' side as D1 targets without a floor of their own (atlas, patch lists,
+// references, peak), alive until submit returns - check_d1 and the CloudRequest take an array of rbt_d1_target, the type the job keeps its clouds' side in
+static int check_d1_patches(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_patch_d1_target* t, std::vector<rbt_d1_target>& as_d1, std::vector<rbt::PatchFloorIn>& out,
+                            rbt::CloudRequest<rbt_d1_target>& req) {
   std::string& err = ctx->last_err;
-  as_patch.assign((size_t)n, rbt_patch_floor_target()); as_d1.assign((size_t)n, rbt_d1_target());
+  out.assign((size_t)n, rbt::PatchFloorIn()); as_d1.assign((size_t)n, rbt_d1_target());
+  std::vector<char> has((size_t)n, 0);
   for (int i = 0; i < n; i++) {
     const std::string who = "entry " + std::to_string(i) + ": ";
-    rbt_patch_floor_target& a = as_patch[(size_t)i]; rbt_d1_target& d = as_d1[(size_t)i];
-    memset(&a, 0, sizeof(a)); memset(&d, 0, sizeof(d)); a.struct_size = sizeof(a); d.struct_size = sizeof(d);
+    rbt_d1_target& d = as_d1[(size_t)i]; memset(&d, 0, sizeof(d)); d.struct_size = sizeof(d);
     if (t[i].struct_size != sizeof(rbt_patch_d1_target)) { err = who + "rbt_patch_d1_target.struct_size is not sizeof(rbt_patch_d1_target)"; return RBT_ERR_PARAM; }
     rbt_patch_d1_target zero; memset(&zero, 0, sizeof(zero));
     const bool empty = !t[i].min_d1_mdb && !t[i].peak && !t[i].qp_min && !t[i].qp_max && !t[i].background_qp && !t[i].max_trials && !t[i].n_frames && !t[i].patches && !t[i].n_patches &&
@@ -345,11 +361,11 @@ static int check_d1_patches(rbt_ctx* ctx, int n, const rbt_stream_params* p, con
     if (t[i].min_d1_mdb < 0) { err = who + "min_d1_mdb must not be negative"; return RBT_ERR_PARAM; }
     if (t[i].peak < 0) { err = who + "peak must not be negative (0 = 1023)"; return RBT_ERR_PARAM; }
     if (t[i].atlas.map_count != 2) { err = who + "floors held patch by patch need atlas.map_count 2: a point-cloud frame is the two pictures that are coded as a pair"; return RBT_ERR_PARAM; }
-    a.min_psnr_mdb = t[i].min_d1_mdb; a.region = RBT_QUALITY_ALL; a.qp_min = t[i].qp_min; a.qp_max = t[i].qp_max; a.background_qp = t[i].background_qp; a.max_trials = t[i].max_trials;
-    a.atlas = t[i].atlas; a.n_frames = t[i].n_frames; a.patches = t[i].patches; a.n_patches = t[i].n_patches; a.patch_min_psnr_mdb = t[i].patch_min_d1_mdb;
+    has[(size_t)i] = 1;
     d.peak = t[i].peak; d.qp_min = t[i].qp_min; d.qp_max = t[i].qp_max; d.n_frames = t[i].n_frames; d.atlas = t[i].atlas; d.patches = t[i].patches; d.n_patches = t[i].n_patches; d.reference = t[i].reference;
   }
-  if (int rc = check_patch_floors(err, n, p, as_patch.data(), out)) return rc;
+  for (int i = 0; i < n; i++) if (has[(size_t)i])
+    if (int rc = fill_patch_request(err, "entry " + std::to_string(i) + ": ", p[i], t[i], t[i].min_d1_mdb, RBT_QUALITY_ALL, t[i].patch_min_d1_mdb, out[(size_t)i])) return rc;
   return check_d1(ctx, n, p, as_d1.data(), req);
 }
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x) {
@@ -370,8 +386,8 @@ static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const si
   if (x.maps) { if (int rc = check_qp_maps(ctx->last_err, n, p, x.maps, qp_maps)) return rc; r.qp_maps = &qp_maps; }
   std::vector<rbt::PatchFloorIn> patch_floors;
   if (x.patches) { if (int rc = check_patch_floors(ctx->last_err, n, p, x.patches, patch_floors)) return rc; r.patch_floors = &patch_floors; }
-  std::vector<rbt_patch_floor_target> as_patch; std::vector<rbt_d1_target> as_d1;
-  if (x.d1_patches) { if (int rc = check_d1_patches(ctx, n, p, x.d1_patches, as_patch, as_d1, patch_floors, d1)) return rc; r.patch_floors = &patch_floors; r.d1 = &d1; r.patch_d1 = true; }
+  std::vector<rbt_d1_target> as_d1;
+  if (x.d1_patches) { if (int rc = check_d1_patches(ctx, n, p, x.d1_patches, as_d1, patch_floors, d1)) return rc; r.patch_floors = &patch_floors; r.d1 = &d1; r.patch_d1 = true; }
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
@@ -446,17 +462,14 @@ static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out,
   int slot = -1;
   for (int s = 0; s < RBT_MAX_JOBS; s++) if (D.jobs[s] == job) slot = s;
   if (slot < 0 || job->owner != ctx) return RBT_ERR_PARAM;
-  static const char* const mismatch[][2] = {      // per GofKind: the wait was called for a job of another kind / the job was handed to another wait
-    {nullptr, nullptr},
-    {"rbt_wait_gof_quality collects jobs of rbt_submit_gof_quality only", "a job of rbt_submit_gof_quality is collected by rbt_wait_gof_quality"},
-    {"rbt_wait_gof_d1 collects jobs of rbt_submit_gof_d1 only", "a job of rbt_submit_gof_d1 is collected by rbt_wait_gof_d1"},
-    {"rbt_wait_gof_color collects jobs of rbt_submit_gof_color only", "a job of rbt_submit_gof_color is collected by rbt_wait_gof_color"},
-    {"rbt_wait_gof_d1_frames collects jobs of rbt_submit_gof_d1_frames only", "a job of rbt_submit_gof_d1_frames is collected by rbt_wait_gof_d1_frames"},
-    {"rbt_wait_gof_quality_frames collects jobs of rbt_submit_gof_quality_frames only", "a job of rbt_submit_gof_quality_frames is collected by rbt_wait_gof_quality_frames"},
-    {"rbt_wait_gof_quality_patches collects jobs of rbt_submit_gof_quality_patches only", "a job of rbt_submit_gof_quality_patches is collected by rbt_wait_gof_quality_patches"},
-    {"rbt_wait_gof_d1_patches collects jobs of rbt_submit_gof_d1_patches only", "a job of rbt_submit_gof_d1_patches is collected by rbt_wait_gof_d1_patches"}};
+  static const char* const names[] = {nullptr, "quality", "d1", "color", "d1_frames", "quality_frames", "quality_patches", "d1_patches"};      // per GofKind: rbt_submit_gof_<name>, rbt_wait_gof_<name>
   const rbt::GofKind is = rbt::gof_kind(job->j);
-  if (is != kind) { const bool called = is == rbt::GOF_PLAIN || (kind != rbt::GOF_PLAIN && kind < is); ctx->last_err = mismatch[called ? kind : is][called ? 0 : 1]; return RBT_ERR_PARAM; }
+  if (is != kind) {      // the wait was called for a job of another kind / the job was handed to another wait
+    const bool called = is == rbt::GOF_PLAIN || (kind != rbt::GOF_PLAIN && kind < is);
+    const std::string name = names[called ? kind : is], sub = "rbt_submit_gof_" + name, wt = "rbt_wait_gof_" + name;
+    ctx->last_err = called ? wt + " collects jobs of " + sub + " only" : "a job of " + sub + " is collected by " + wt;
+    return RBT_ERR_PARAM;
+  }
   int n_flat = 0; r.out = annexb_out; r.n_out = n_out; r.n_flat = &n_flat;
   int rc = rbt::gof_wait(job->j, ctx->stats, ctx->last_err, r);
   if (!rc) ctx->n_flat = n_flat;
@@ -487,13 +500,9 @@ int rbt_wait_gof_rate(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* 
   rbt::GofResults r; r.rate = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_PLAIN, r);
 } RBT_CATCH
 int rbt_transcode_gof_rate(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_rate_target* targets,
-                           uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results) try {
-  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
-  rbt_job* job = nullptr;
-  int rc = rbt_submit_gof_rate(ctx, n, annexb_in, n_in, p, targets, &job);
-  if (rc) return rc;
-  return rbt_wait_gof_rate(ctx, job, annexb_out, n_out, results);
-} RBT_CATCH
+                           uint8_t** annexb_out, size_t* n_out, rbt_rate_result* results) {
+  return transcode(rbt_submit_gof_rate, rbt_wait_gof_rate, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
 // ---- transcoding to a PSNR floor ----
 int rbt_submit_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
@@ -504,13 +513,9 @@ int rbt_wait_gof_quality(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_
   rbt::GofResults r; r.quality = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_QUALITY, r);
 } RBT_CATCH
 int rbt_transcode_gof_quality(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets,
-                              uint8_t** annexb_out, size_t* n_out, rbt_quality_result* results) try {
-  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
-  rbt_job* job = nullptr;
-  int rc = rbt_submit_gof_quality(ctx, n, annexb_in, n_in, p, targets, &job);
-  if (rc) return rc;
-  return rbt_wait_gof_quality(ctx, job, annexb_out, n_out, results);
-} RBT_CATCH
+                              uint8_t** annexb_out, size_t* n_out, rbt_quality_result* results) {
+  return transcode(rbt_submit_gof_quality, rbt_wait_gof_quality, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
 // ---- a QP per CTB ----
 int rbt_submit_gof_qp_map(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_qp_map* maps, rbt_job** job) try {
   SubmitExtras x; x.maps = maps; return submit(ctx, n, annexb_in, n_in, p, job, x);      // maps == NULL: rbt_submit_gof
@@ -537,13 +542,10 @@ int rbt_wait_gof_d1_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, si
   rbt::GofResults r; r.d1_patches = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_D1_PATCHES, r);
 } RBT_CATCH
 int rbt_transcode_gof_d1_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d1_target* targets,
-                                 uint8_t** annexb_out, size_t* n_out, rbt_patch_d1_result* results) try {
-  if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !targets || !annexb_out || !n_out || !results) return RBT_ERR_PARAM;
-  rbt_job* job = nullptr;
-  int rc = rbt_submit_gof_d1_patches(ctx, n, annexb_in, n_in, p, targets, &job);
-  if (rc) return rc;
-  return rbt_wait_gof_d1_patches(ctx, job, annexb_out, n_out, results);
-} RBT_CATCH
+                                 uint8_t** annexb_out, size_t* n_out, rbt_patch_d1_result* results) {
+  if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !targets) return RBT_ERR_PARAM;      // (refused here, before submit would)
+  return transcode(rbt_submit_gof_d1_patches, rbt_wait_gof_d1_patches, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
 // ---- PSNR floors held patch by patch ----
 int rbt_submit_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_floor_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
@@ -554,13 +556,9 @@ int rbt_wait_gof_quality_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_ou
   rbt::GofResults r; r.patches = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_QUALITY_PATCHES, r);
 } RBT_CATCH
 int rbt_transcode_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_floor_target* targets,
-                                      uint8_t** annexb_out, size_t* n_out, rbt_patch_floor_result* results) try {
-  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
-  rbt_job* job = nullptr;
-  int rc = rbt_submit_gof_quality_patches(ctx, n, annexb_in, n_in, p, targets, &job);
-  if (rc) return rc;
-  return rbt_wait_gof_quality_patches(ctx, job, annexb_out, n_out, results);
-} RBT_CATCH
+                                      uint8_t** annexb_out, size_t* n_out, rbt_patch_floor_result* results) {
+  return transcode(rbt_submit_gof_quality_patches, rbt_wait_gof_quality_patches, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
 // ---- floors held frame by frame ----
 int rbt_submit_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
@@ -571,13 +569,9 @@ int rbt_wait_gof_quality_frames(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out
   rbt::GofResults r; r.frames = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_QUALITY_FRAMES, r);
 } RBT_CATCH
 int rbt_transcode_gof_quality_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_quality_target* targets,
-                                     uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
-  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
-  rbt_job* job = nullptr;
-  int rc = rbt_submit_gof_quality_frames(ctx, n, annexb_in, n_in, p, targets, &job);
-  if (rc) return rc;
-  return rbt_wait_gof_quality_frames(ctx, job, annexb_out, n_out, results);
-} RBT_CATCH
+                                     uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) {
+  return transcode(rbt_submit_gof_quality_frames, rbt_wait_gof_quality_frames, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
 int rbt_submit_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
   SubmitExtras x; x.d1 = targets; x.per_frame = true; return submit(ctx, n, annexb_in, n_in, p, job, x);
@@ -587,13 +581,9 @@ int rbt_wait_gof_d1_frames(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, siz
   rbt::GofResults r; r.frames = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_D1_FRAMES, r);
 } RBT_CATCH
 int rbt_transcode_gof_d1_frames(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets,
-                                uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) try {
-  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
-  rbt_job* job = nullptr;
-  int rc = rbt_submit_gof_d1_frames(ctx, n, annexb_in, n_in, p, targets, &job);
-  if (rc) return rc;
-  return rbt_wait_gof_d1_frames(ctx, job, annexb_out, n_out, results);
-} RBT_CATCH
+                                uint8_t** annexb_out, size_t* n_out, rbt_frame_floor_result* results) {
+  return transcode(rbt_submit_gof_d1_frames, rbt_wait_gof_d1_frames, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
 // ---- transcoding geometry to a D1 floor ----
 int rbt_submit_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
@@ -604,13 +594,9 @@ int rbt_wait_gof_d1(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_
   rbt::GofResults r; r.d1 = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_D1, r);
 } RBT_CATCH
 int rbt_transcode_gof_d1(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d1_target* targets,
-                         uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results) try {
-  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
-  rbt_job* job = nullptr;
-  int rc = rbt_submit_gof_d1(ctx, n, annexb_in, n_in, p, targets, &job);
-  if (rc) return rc;
-  return rbt_wait_gof_d1(ctx, job, annexb_out, n_out, results);
-} RBT_CATCH
+                         uint8_t** annexb_out, size_t* n_out, rbt_d1_floor_result* results) {
+  return transcode(rbt_submit_gof_d1, rbt_wait_gof_d1, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
 // ---- transcoding attributes to a colour PSNR floor ----
 int rbt_submit_gof_color(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_color_target* targets, rbt_job** job) try {
   if (!targets) return RBT_ERR_PARAM;
@@ -621,13 +607,9 @@ int rbt_wait_gof_color(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t*
   rbt::GofResults r; r.color = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_COLOR, r);
 } RBT_CATCH
 int rbt_transcode_gof_color(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_color_target* targets,
-                            uint8_t** annexb_out, size_t* n_out, rbt_color_floor_result* results) try {
-  if (!annexb_out || !n_out || !results) return RBT_ERR_PARAM;
-  rbt_job* job = nullptr;
-  int rc = rbt_submit_gof_color(ctx, n, annexb_in, n_in, p, targets, &job);
-  if (rc) return rc;
-  return rbt_wait_gof_color(ctx, job, annexb_out, n_out, results);
-} RBT_CATCH
+                            uint8_t** annexb_out, size_t* n_out, rbt_color_floor_result* results) {
+  return transcode(rbt_submit_gof_color, rbt_wait_gof_color, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
 int rbt_gather_luma(rbt_ctx* ctx, const uint16_t* src, int n_pics, int stride, int rows, int x0, int y0, int w, int h, int src_misalign, uint16_t* out) try {
   if (!ctx || !src || !out) return RBT_ERR_PARAM;
   RBT_ENTER(ctx);

@@ -1,6 +1,6 @@
 // The float routine of the D1 results (rbt_d1, rbt_score, rbt_score_patches) and what the walk of the D1 floors held patch by patch is told about a patch
 // (include/rbt.h, "D1 per patch of the decoded cloud", "D1 floors held patch by patch"). Plain host code without a device call, so that tests/patch_d1_check.cpp can run
-// it under the sanitizers; host/rbt_patch_walk.h itself still takes figures and `meets` and nothing else.
+// it under the sanitizers; host/rbt_patch_walk.h includes this and makes a trial's figures of it (patch_trial_d1), its walk still takes figures and `meets` and nothing else.
 #pragma once
 #include <cmath>
 #include <cstdint>

@@ -11,13 +11,16 @@
 //             The casts truncate toward zero: one QP step is about 1 dB, the PSNR floor's own argument; no tuned constant.
 //   end       no q[k] changed: the frame has settled on this trial. A patch moves up until its first failure and only down after it, so the vector never repeats: at most
 //             the sum over the patches of (hi - q0) + (hi - lo) + 1 trials. max_trials (0 = no cap): a frame that reaches it settles on its last trial, met as measured.
-// Plain host code without a device call, so that tests/patch_floor_check.cpp can run it under the sanitizers.
+// The walk takes figures and `meets` and nothing else. What they are made of is a kind of figure: a source that turns what a trial brought into a PatchTrial and keeps the
+// kind's payload for the report (below: luma PSNR from the fold words, D1 from the trial's cloud). A further kind is one more payload and one more source.
+// Plain host code without a device call, so that tests/patch_floor_check.cpp and tests/patch_d1_check.cpp can run it under the sanitizers.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
 #include "rbt_quality_walk.h"
+#include "rbt_d1_figures.h"
 
 namespace rbt {
 // the folded sums of one region in the two pictures of a frame: the words of k_patch_fold and the displayed luma samples the region holds
@@ -70,5 +73,28 @@ inline bool patch_walk_step(PatchWalk& w, const double* figure, const char* meet
     changed |= w.q[k] != was;
   }
   return w.settled = !changed;
+}
+
+// What a trial said about the patches of one frame - per patch the figure and its condition against F_k, as patch_walk_step takes them - and per kind of figure what the
+// report needs of the trial beside that: the folded sums of every region and of the background; every patch's D1 and the whole frame's
+struct PatchTrial { std::vector<double> figure; std::vector<char> meets; };
+struct PatchPsnr { std::vector<PatchSums> patches; uint64_t background[3] = {0, 0, 0}; };
+struct PatchD1 { std::vector<rbt_patch_d1> patches; rbt_d1_result whole = rbt_d1_result(); };
+// the PSNR source: the words k_patch_fold left of the frame - sse, sse_occ, n_occ per patch, then the background's - with the displayed samples of every R_k
+inline void patch_trial_psnr(const uint64_t* words, const std::vector<uint64_t>& samples, int region, int bit_depth, const std::vector<int32_t>& floor_mdb, PatchTrial& t, PatchPsnr& p) {
+  const size_t np = samples.size();
+  t.figure.resize(np); t.meets.resize(np); p.patches.assign(np, PatchSums());
+  for (size_t k = 0; k < np; k++) {
+    PatchSums& s = p.patches[k]; s.sse = words[3 * k]; s.sse_occ = words[3 * k + 1]; s.samples_occ = words[3 * k + 2]; s.samples = samples[k];
+    t.figure[k] = patch_figure(s, region, bit_depth); t.meets[k] = patch_meets(s, region, floor_mdb[k], bit_depth);
+  }
+  for (int c = 0; c < 3; c++) p.background[c] = words[3 * np + c];
+}
+// the D1 source: the patches of the trial's cloud as rbt_score_patches left them (taken over, not copied) and the whole frame's result
+inline void patch_trial_d1(std::vector<rbt_patch_d1>& patches, const rbt_d1_result& whole, const std::vector<int32_t>& floor_mdb, PatchTrial& t, PatchD1& p) {
+  p.patches.swap(patches); p.whole = whole;
+  const size_t np = p.patches.size();
+  t.figure.resize(np); t.meets.resize(np);
+  for (size_t k = 0; k < np; k++) { t.figure[k] = patch_d1_figure(p.patches[k]); t.meets[k] = patch_d1_meets(p.patches[k], floor_mdb[k]); }
 }
 }  // namespace rbt

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include "rbt_batch.h"
 #include "rbt_transcode.h"
 #include "rbt_rate_walk.h"
@@ -16,7 +17,6 @@
 #include "rbt_color_walk.h"
 #include "rbt_frame_walk.h"
 #include "rbt_patch_walk.h"
-#include "rbt_d1_figures.h"
 #include "rbt_qp_map.h"
 #include "rbt_pcc.h"
 #include "../csrc/rbt_cloudmaps.h"
@@ -500,9 +500,9 @@ struct TargetWalk : QpWalk<TargetTried> { WalkKind kind = WALK_BUDGET; RateGoal 
 // the wait half: the pooled luma planes of the occupancy stream, and for occupancy_rd the per-4x4-unit maps made of them (both live in GofJob::pooled until the job goes)
 struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
 // Floors held patch by patch: the walk of one point-cloud frame (rbt_patch_walk.h) with what its last trial brought - the frame's NAL units, the sums of its two pictures,
-// the folded sums per patch and of the background, the map it was coded with - and the walks of one entry: per frame R_k in CTB units (the rectangles k_patch_fold reads, on
-// the device from the first round to the last) and the displayed samples of R_k in both pictures
-struct PatchFrame { PatchWalk w; std::vector<uint8_t> stream; QualitySums sums; std::vector<rbt_patch_d1> pd; rbt_d1_result whole = rbt_d1_result(); std::vector<PatchSums> ps; uint64_t bg[3] = {0, 0, 0}; std::vector<int8_t> map; std::vector<int32_t> rects; std::vector<uint64_t> samples; size_t rect_off = 0; };
+// the payload of the job's kind of figure (PatchPsnr or PatchD1, the other stays empty), the map it was coded with - and the walks of one entry: per frame R_k in CTB units
+// (the rectangles k_patch_fold reads, on the device from the first round to the last) and the displayed samples of R_k in both pictures
+struct PatchFrame { PatchWalk w; std::vector<uint8_t> stream; QualitySums sums; PatchPsnr psnr; PatchD1 d1; std::vector<int8_t> map; std::vector<int32_t> rects; std::vector<uint64_t> samples; size_t rect_off = 0; };
 struct PatchWalks {
   int q = 0, entry = 0, n_passes = 0, l2 = 5, wc = 0, hc = 0, W = 0, H = 0, bit_depth = 8; std::vector<PatchFrame> frames; int32_t* d_rects = nullptr;
   bool settled() const { for (const PatchFrame& f : frames) if (!f.w.settled) return false; return true; }
@@ -545,8 +545,13 @@ struct D1Entry : CloudEntry { rbt_d1_target t; std::vector<MapFrame*> frames; st
 struct ColorEntry : CloudEntry { rbt_color_target t; int geo = -1; uint16_t* geo_planes = nullptr; uint16_t* in_planes = nullptr; std::vector<ColorFrame*> frames, own_ref; };
 // what a pipeline's rounds leave of an entry with a cloud target: the walk's result - or the entry's own QP - and the frames' figures there
 template <class Result> struct FloorOut { int qp = 0, q0 = 0, qs = 0, met = 0, n_enc = 0; uint64_t bytes = 0; std::vector<Result> frames; double cloud_ms = 0; };
-struct PatchFloorOut { int q0 = 0, n_passes = 0, wc = 0, hc = 0, bit_depth = 8; uint64_t bytes = 0, pictures = 0; std::vector<int8_t> map; std::vector<rbt_patch_frame> frames; std::vector<rbt_patch_pick> picks; QualitySums sums; };
-struct PatchD1Out { int q0 = 0, n_passes = 0, wc = 0, hc = 0; uint64_t bytes = 0, pictures = 0; std::vector<int8_t> map; std::vector<rbt_patch_d1_frame> frames; std::vector<rbt_patch_d1_pick> picks; double cloud_ms = 0; };
+// what a pipeline's rounds leave of an entry of a job with floors held patch by patch, either kind: the header, per frame its trials and bytes with the payload of its
+// settling trial, and every frame's picks back to back. An entry without a target has no frames: q0, bytes, bit_depth and sums are those of its only encode
+struct PatchOut {
+  int q0 = 0, n_passes = 0, wc = 0, hc = 0, bit_depth = 8, region = 0; uint64_t bytes = 0, pictures = 0; std::vector<int8_t> map; QualitySums sums; double cloud_ms = 0;
+  struct Frame { int n_trials = 0, met = 1, n_patches = 0; uint64_t bytes = 0; PatchPsnr psnr; PatchD1 d1; }; std::vector<Frame> frames;
+  struct Pick { int qp, met, failed; double figure; }; std::vector<Pick> picks;
+};
 struct FrameFloorOut { int q0 = 0, n_passes = 0, bit_depth = 8; std::vector<rbt_frame_pick> frames; std::vector<rbt_d1_result> d1; double cloud_ms = 0; uint64_t bytes = 0, pictures = 0; QualitySums sums; };
 struct GofJob {
   int n = 0, slot = 0, ng = 0, rc = 0; GofKind kind = GOF_PLAIN;      // kind: which submit made the job, fixed there
@@ -582,10 +587,10 @@ struct GofJob {
   bool per_frame = false; std::vector<FrameFloorOut> fout;
   // floors held patch by patch (rbt_submit_gof_quality_patches): a job with quality floors that are all 0, like a job with cloud targets; the entries with a target walk
   // every frame's patches (RoundPipe::pwalks), the others are coded once at their own QP
-  std::vector<PatchFloorIn> patch; std::vector<PatchFloorOut> pout;
+  std::vector<PatchFloorIn> patch; std::vector<PatchOut> pout;
   // D1 floors held patch by patch (rbt_submit_gof_d1_patches): such a job with the figures taken from the trial's cloud - d1 holds the targets' clouds' side as in a job
-  // with D1 floors (no walk of its own: min_d1_mdb 0), every pass is scored by d1_score patch by patch (PatchFrame::pd, ::whole), no sums per CTB run
-  bool patch_d1 = false; std::vector<PatchD1Out> pdout;
+  // with D1 floors (no walk of its own: min_d1_mdb 0), every pass is scored by d1_score patch by patch (PatchFrame::d1), no sums per CTB run
+  bool patch_d1 = false;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   void color_release(int entry) {        // the frames' volumes go back to the context's cache; their streams have been waited for
     ColorEntry& E = color[entry];
@@ -761,7 +766,7 @@ static int check_qp_maps(GofJob& j) {
 static int check_patch_floors(GofJob& j) {
   if (j.patch.empty()) return 0;
   for (int g = 0; g < j.ng; g++) for (size_t q = 0; q < j.groups[g].size(); q++) {
-    const int i = j.groups[g][q]; const DecodeBatch& db = j.db[g]; const rbt_patch_floor_target& t = j.patch[i].t;
+    const int i = j.groups[g][q]; const DecodeBatch& db = j.db[g]; const PatchFloorIn& t = j.patch[i];
     if (t.n_frames <= 0) continue;
     const std::string who = "entry " + std::to_string(i) + ": ";
     const int ds = j.dec_of[g][q], cnt = db.stream_count[ds];
@@ -769,8 +774,8 @@ static int check_patch_floors(GofJob& j) {
       j.err = who + "rbt_patch_floor_target.n_frames is " + std::to_string(t.n_frames) + ", the stream holds " + std::to_string(cnt) + " pictures (n_frames must be pictures / 2)";
       j.refused = true; return RBT_ERR_PARAM; }
     int dw, dh; displayed(db, ds, &dw, &dh);
-    if (t.atlas.width != dw || t.atlas.height != dh) {
-      j.err = who + "the atlas is " + std::to_string(t.atlas.width) + " x " + std::to_string(t.atlas.height) + ", the output pictures are " + std::to_string(dw) + " x " + std::to_string(dh);
+    if (t.atlas_width != dw || t.atlas_height != dh) {
+      j.err = who + "the atlas is " + std::to_string(t.atlas_width) + " x " + std::to_string(t.atlas_height) + ", the output pictures are " + std::to_string(dw) + " x " + std::to_string(dh);
       j.refused = true; return RBT_ERR_PARAM; }
   }
   return 0;
@@ -915,25 +920,25 @@ static bool walk_step(TargetWalk& w, int& need, int& dir, bool& alone) {
   return qp_walk_step(w, floor_holds(w, meets), need, dir);
 }
 // ------------------------------------------------------------------------------------------------ floors held patch by patch (include/rbt.h, "PSNR floors held patch by patch")
-static bool has_patch_floor(const GofJob& j, int i) { return !j.patch.empty() && j.patch[i].t.n_frames > 0; }
+static bool has_patch_floor(const GofJob& j, int i) { return !j.patch.empty() && j.patch[i].n_frames > 0; }
 // In the wait half, once the pipeline's decoder has been collected: per entry with a target the walks of its frames - lo, hi and q0 as the PSNR floor has them, a range of
 // q0 alone where there is no floor at all (rule 8) -, R_k of every patch in CTB units and its displayed samples, and the rectangles on the device for all rounds
 static int seed_patch_walks(GofJob& j, int gi, RoundPipe& r) {
   const std::vector<int>& gs = j.groups[gi]; DecodeBatch& db = j.db[gi];
   for (size_t q = 0; q < gs.size(); q++) if (has_patch_floor(j, gs[q])) {
-    const int i = gs[q]; const PatchFloorIn& in = j.patch[i]; const rbt_patch_floor_target& t = in.t;
+    const int i = gs[q]; const PatchFloorIn& in = j.patch[i];
     PatchWalks pw; pw.q = (int)q; pw.entry = i; pw.l2 = j.params[i].log2_ctb ? j.params[i].log2_ctb : 5; pw.bit_depth = entry_bit_depth(j, gi, q);
     displayed(db, j.dec_of[gi][q], &pw.W, &pw.H);
     pw.wc = (pw.W + (1 << pw.l2) - 1) >> pw.l2; pw.hc = (pw.H + (1 << pw.l2) - 1) >> pw.l2;
-    bool any_floor = t.min_psnr_mdb != 0; for (const std::vector<int32_t>& fl : in.floors) for (int32_t v : fl) any_floor |= v != 0;
-    const int qp = std::min(51, std::max(0, j.params[i].qp)), lo = any_floor ? t.qp_min : qp, hi = any_floor ? (t.qp_max ? t.qp_max : 51) : qp;
-    pw.frames.resize((size_t)t.n_frames); size_t n_rects = 0;
-    for (int f = 0; f < t.n_frames; f++) {
+    bool any_floor = in.floor_mdb != 0; for (const std::vector<int32_t>& fl : in.floors) for (int32_t v : fl) any_floor |= v != 0;
+    const int qp = std::min(51, std::max(0, j.params[i].qp)), lo = any_floor ? in.qp_min : qp, hi = any_floor ? (in.qp_max ? in.qp_max : 51) : qp;
+    pw.frames.resize((size_t)in.n_frames); size_t n_rects = 0;
+    for (int f = 0; f < in.n_frames; f++) {
       PatchFrame& F = pw.frames[(size_t)f]; const std::vector<rbt_patch>& ps = in.patches[(size_t)f];
-      patch_walk_seed(F.w, qp, lo, hi, t.max_trials, in.floors[(size_t)f]);
+      patch_walk_seed(F.w, qp, lo, hi, in.max_trials, in.floors[(size_t)f]);
       F.rects.resize(4 * ps.size()); F.samples.resize(ps.size()); F.rect_off = n_rects; n_rects += ps.size();
       for (size_t k = 0; k < ps.size(); k++) {
-        patch_region(pw.W, pw.H, t.atlas.occupancy_resolution, ps[k].u0, ps[k].v0, ps[k].size_u0, ps[k].size_v0, pw.l2, &F.rects[4 * k]);
+        patch_region(pw.W, pw.H, in.occupancy_resolution, ps[k].u0, ps[k].v0, ps[k].size_u0, ps[k].size_v0, pw.l2, &F.rects[4 * k]);
         F.samples[k] = patch_region_samples(&F.rects[4 * k], pw.W, pw.H, pw.l2);
       }
     }
@@ -948,13 +953,13 @@ static int seed_patch_walks(GofJob& j, int gi, RoundPipe& r) {
 // the trial maps of an entry's frames: rule 4 for every frame that has not settled (a settled frame is in no pass: its part stays at q0)
 static int patch_trial_maps(GofJob& j, const PatchWalks& pw, std::vector<int8_t>& out) {
   const PatchFloorIn& in = j.patch[pw.entry]; const size_t per = (size_t)pw.wc * pw.hc;
-  rbt_atlas_params a = in.t.atlas; a.width = pw.W; a.height = pw.H;
+  rbt_atlas_params a; memset(&a, 0, sizeof(a)); a.width = pw.W; a.height = pw.H; a.occupancy_resolution = in.occupancy_resolution;      // (what qp_map_from_patches reads)
   out.assign(per * pw.frames.size(), 0);
   for (size_t f = 0; f < pw.frames.size(); f++) {
     const PatchWalk& w = pw.frames[f].w;
     if (w.settled) { std::fill(out.begin() + (ptrdiff_t)(per * f), out.begin() + (ptrdiff_t)(per * (f + 1)), (int8_t)w.q0); continue; }
     std::vector<int8_t> q(w.q.begin(), w.q.end());
-    if (int rc = qp_map_from_patches(j.err, &a, in.patches[f].data(), (int)in.patches[f].size(), q.data(), in.t.background_qp < 0 ? w.q0 : in.t.background_qp, pw.l2, out.data() + per * f, pw.wc, pw.hc)) return rc;
+    if (int rc = qp_map_from_patches(j.err, &a, in.patches[f].data(), (int)in.patches[f].size(), q.data(), in.background_qp < 0 ? w.q0 : in.background_qp, pw.l2, out.data() + per * f, pw.wc, pw.hc)) return rc;
   }
   return 0;
 }
@@ -1381,32 +1386,25 @@ static int finish_round(GofJob& j, int gi) {
   for (const EncStreamDesc& d : r.eb->desc) fold_at += (size_t)d.n_frames * RBT_SSE_WORDS;      // the folds per patch lie behind the words per picture
   for (size_t e = 0; e < r.cands.size(); e++) {
     const EncStreamDesc& d = r.eb->desc[e]; const RoundCand& c = r.cands[e]; QualitySums sums;
-    if (c.pw >= 0) {      // a pass of patch walks: every frame it carried keeps this trial - NAL units, sums, folds, map - and takes the walk's step on it
-      PatchWalks& pw = r.pwalks[(size_t)c.pw]; const int region = j.patch[pw.entry].t.region; const size_t per = (size_t)pw.wc * pw.hc;
+    if (c.pw >= 0) {      // a pass of patch walks: every frame it carried keeps this trial - NAL units, sums, payload, map - and takes the walk's step on what the trial said
+      PatchWalks& pw = r.pwalks[(size_t)c.pw]; const int region = j.patch[pw.entry].region; const size_t per = (size_t)pw.wc * pw.hc;
       std::vector<rbt_d1_result> whole; std::vector<std::vector<rbt_patch_d1>> clouds;      // D1 floors: the clouds of the frames the pass carried, in pass order, patch by patch
       if (j.patch_d1) if (int rc = d1_score(j, gi, c.q, *r.eb, e, whole, &clouds)) return rc;
+      // the pass's figure source (rbt_patch_walk.h): frame i of the pass from its cloud, or from its fold words, which lie in pass order behind the words per picture
+      PatchTrial said;
+      auto figures = [&](size_t i, PatchFrame& F) {
+        if (j.patch_d1) { patch_trial_d1(clouds[i], whole[i], F.w.floor_mdb, said, F.d1); return; }
+        patch_trial_psnr(&r.eb->sums[fold_at], F.samples, region, pw.bit_depth, F.w.floor_mdb, said, F.psnr);
+        fold_at += (F.samples.size() + 2) * RBT_CTBSSE_WORDS;
+      };
       for (size_t i = 0; i < c.pass.frames.size(); i++) {
-        const size_t f = (size_t)c.pass.frames[i]; PatchFrame& F = pw.frames[f]; const size_t np = F.samples.size();
+        const size_t f = (size_t)c.pass.frames[i]; PatchFrame& F = pw.frames[f];
         frame_cut(outs[e], r.eb->pic_at[e], i, (size_t)d.gop, F.stream);
         F.sums = QualitySums();
         for (int k = 0; k < d.gop; k++, at++) quality_add_picture(F.sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
-        std::vector<double> fig(np); std::vector<char> meets(np);
-        if (j.patch_d1) {
-          F.pd.swap(clouds[i]); F.whole = whole[i];
-          for (size_t k = 0; k < np; k++) { fig[k] = patch_d1_figure(F.pd[k]); meets[k] = patch_d1_meets(F.pd[k], F.w.floor_mdb[k]); }
-          F.map.assign(c.qmap.begin() + (ptrdiff_t)(per * f), c.qmap.begin() + (ptrdiff_t)(per * (f + 1)));
-          patch_walk_step(F.w, fig.data(), meets.data());
-          continue;
-        }
-        const uint64_t* w = &r.eb->sums[fold_at]; fold_at += (np + 2) * RBT_CTBSSE_WORDS;
-        F.ps.assign(np, PatchSums());
-        for (size_t k = 0; k < np; k++) {
-          PatchSums& s = F.ps[k]; s.sse = w[3 * k]; s.sse_occ = w[3 * k + 1]; s.samples_occ = w[3 * k + 2]; s.samples = F.samples[k];
-          fig[k] = patch_figure(s, region, pw.bit_depth); meets[k] = patch_meets(s, region, F.w.floor_mdb[k], pw.bit_depth);
-        }
-        for (int k = 0; k < 3; k++) F.bg[k] = w[3 * np + k];
+        figures(i, F);
         F.map.assign(c.qmap.begin() + (ptrdiff_t)(per * f), c.qmap.begin() + (ptrdiff_t)(per * (f + 1)));
-        patch_walk_step(F.w, fig.data(), meets.data());
+        patch_walk_step(F.w, said.figure.data(), said.meets.data());
       }
       pw.n_passes++;
       continue;
@@ -1515,41 +1513,20 @@ static void fill_frame_results(GofJob& j, int gi) {
 }
 // ... and of a pipeline whose entries walked patch by patch: per frame its trials, bytes, background and the picks of its settling trial; the final map; the stream assembled
 // from the frames' NAL units (rule 7). The entries without a target keep their only encode (r.o1) and its sums
-static void fill_patch_d1_results(GofJob& j, int gi) {
-  RoundPipe& r = j.pipes[gi];
-  j.pdout.resize(j.n);
-  for (const PatchWalks& pw : r.pwalks) {
-    PatchD1Out& o = j.pdout[pw.entry]; std::vector<uint8_t>& out = r.o1[pw.q];
-    out.clear(); o.n_passes = pw.n_passes; o.wc = pw.wc; o.hc = pw.hc; o.cloud_ms = j.d1[pw.entry].cloud_ms;
-    for (const PatchFrame& F : pw.frames) {
-      out.insert(out.end(), F.stream.begin(), F.stream.end()); o.map.insert(o.map.end(), F.map.begin(), F.map.end());
-      o.q0 = F.w.q0; o.pictures += 2 * (uint64_t)F.w.n_trials;
-      rbt_patch_d1_frame pf; memset(&pf, 0, sizeof(pf));
-      pf.n_trials = F.w.n_trials; pf.met = 1; pf.n_patches = (int)F.pd.size(); pf.bytes = F.stream.size(); pf.d1 = F.whole;
-      for (size_t k = 0; k < F.pd.size(); k++) { pf.met &= F.w.met[k]; o.picks.push_back(rbt_patch_d1_pick{F.w.q[k], F.w.met[k], F.w.failed[k], F.pd[k], F.w.figure[k]}); }
-      o.frames.push_back(pf);
-    }
-    o.bytes = out.size();
-  }
-}
 static void fill_patch_results(GofJob& j, int gi) {
   RoundPipe& r = j.pipes[gi]; const std::vector<int>& gs = j.groups[gi];
   j.pout.resize(j.n);
-  for (size_t q = 0; q < gs.size(); q++) if (!has_patch_floor(j, gs[q])) { PatchFloorOut& o = j.pout[gs[q]]; o.q0 = j.params[gs[q]].qp; o.bytes = r.o1[q].size(); o.sums = r.sums[q]; o.bit_depth = entry_bit_depth(j, gi, q); }
+  for (size_t q = 0; q < gs.size(); q++) if (!has_patch_floor(j, gs[q])) { PatchOut& o = j.pout[gs[q]]; o.q0 = j.params[gs[q]].qp; o.bytes = r.o1[q].size(); o.sums = r.sums[q]; o.bit_depth = entry_bit_depth(j, gi, q); }
   for (const PatchWalks& pw : r.pwalks) {
-    PatchFloorOut& o = j.pout[pw.entry]; std::vector<uint8_t>& out = r.o1[pw.q]; const int region = j.patch[pw.entry].t.region;
-    out.clear(); o.n_passes = pw.n_passes; o.wc = pw.wc; o.hc = pw.hc; o.bit_depth = pw.bit_depth;
+    PatchOut& o = j.pout[pw.entry]; std::vector<uint8_t>& out = r.o1[pw.q];
+    out.clear(); o.n_passes = pw.n_passes; o.wc = pw.wc; o.hc = pw.hc; o.bit_depth = pw.bit_depth; o.region = j.patch[pw.entry].region;
+    if (has_d1(j, pw.entry)) o.cloud_ms = j.d1[pw.entry].cloud_ms;
     for (const PatchFrame& F : pw.frames) {
       out.insert(out.end(), F.stream.begin(), F.stream.end()); o.map.insert(o.map.end(), F.map.begin(), F.map.end());
       o.q0 = F.w.q0; o.pictures += 2 * (uint64_t)F.w.n_trials;
-      rbt_patch_frame pf; memset(&pf, 0, sizeof(pf));
-      pf.n_trials = F.w.n_trials; pf.met = 1; pf.n_patches = (int)F.ps.size(); pf.bytes = F.stream.size();
-      for (int k = 0; k < 3; k++) pf.background[k] = F.bg[k];
-      for (size_t k = 0; k < F.ps.size(); k++) {
-        const PatchSums& s = F.ps[k]; pf.met &= F.w.met[k];
-        o.picks.push_back(rbt_patch_pick{F.w.q[k], F.w.met[k], F.w.failed[k], region ? s.sse_occ : s.sse, region ? s.samples_occ : s.samples, F.w.figure[k]});
-      }
-      o.frames.push_back(pf);
+      PatchOut::Frame pf; pf.n_trials = F.w.n_trials; pf.n_patches = (int)F.w.q.size(); pf.bytes = F.stream.size(); pf.psnr = F.psnr; pf.d1 = F.d1;
+      for (size_t k = 0; k < F.w.q.size(); k++) { pf.met &= F.w.met[k]; o.picks.push_back(PatchOut::Pick{F.w.q[k], F.w.met[k], F.w.failed[k], F.w.figure[k]}); }
+      o.frames.push_back(std::move(pf));
       for (int c = 0; c < 3; c++) { o.sums.sse[c] += F.sums.sse[c]; o.sums.samples[c] += F.sums.samples[c]; o.sums.sse_occ[c] += F.sums.sse_occ[c]; o.sums.samples_occ[c] += F.sums.samples_occ[c]; }
     }
     o.bytes = out.size();
@@ -1582,7 +1559,6 @@ static int run_rounds(GofJob& j, int gi) {
   for (const TargetWalk& w : r.walks) if (!w.settled) { j.err = "internal: QP walk did not settle"; return RBT_ERR_PARAM; }
   for (const FrameWalks<TargetWalk>& fw : r.fwalks) if (!fw.settled()) { j.err = "internal: QP walk did not settle"; return RBT_ERR_PARAM; }
   for (const PatchWalks& pw : r.pwalks) if (!pw.settled()) { j.err = "internal: patch walk did not settle"; return RBT_ERR_PARAM; }
-  if (j.patch_d1) { fill_patch_d1_results(j, gi); return 0; }
   if (!j.patch.empty()) { fill_patch_results(j, gi); return 0; }
   if (j.per_frame) { fill_frame_results(j, gi); return 0; }
   fill_results(j, gi);
@@ -1807,7 +1783,7 @@ GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   if (r.patch_floors) {      // runs as a job with quality floors that are all 0, in each entry's region
     j.patch = *r.patch_floors; j.qocc.assign(n, QualityOcc());
     j.qtargets.clear();      // (a job with D1 floors held patch by patch has passed keep_cloud_targets above, which filled them; a job with PSNR floors per patch comes here with none)
-    for (int i = 0; i < n; i++) j.qtargets.push_back(rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, j.patch[i].t.region, 0, 0});
+    for (int i = 0; i < n; i++) j.qtargets.push_back(rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, j.patch[i].region, 0, 0});
   }
   SubmitPlan s; s.in = r.in; s.p = p; s.gof_rule = r.gof_rule;
   int rc = plan_pipelines(j, s, depth);
@@ -1824,23 +1800,72 @@ GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   return J;
 }
 
+// What gof_wait hands to the caller beside the streams. Every array is a copy made here (malloc'd, rbt_free; never NULL, an empty vector's neither); the first allocation that
+// fails ends the copying - copy returns nullptr from then on -, and gof_wait takes back every array given so far together with the streams: all or nothing
+struct HandOver {
+  std::vector<void*> given; int rc = 0;
+  template <class T> T* copy(const std::vector<T>& v) {
+    if (rc) return nullptr;
+    T* p = (T*)malloc(std::max<size_t>(1, v.size() * sizeof(T)));
+    if (!p) { rc = RBT_ERR_NOMEM; return nullptr; }
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
+    given.push_back(p);
+    return p;
+  }
+  void take_back() { for (void* p : given) free(p); given.clear(); }
+};
+// the result arrays whose entries carry arrays of their own, zeroed: before anything is filled in, and again when everything is taken back
+static void zero_results(const GofResults& r, int n) {
+  auto zero = [n](auto* a) { if (a) memset(a, 0, sizeof(*a) * (size_t)n); };
+  zero(r.d1); zero(r.color); zero(r.frames); zero(r.patches); zero(r.d1_patches);
+}
 // The public results of a job with cloud targets: per entry its own QP and one encode, or what the rounds left of an entry with a target (FloorOut) with the statistics
-// over its frames; on a failure - rc, or an allocation here - nothing is handed out
-template <class Entry, class Result, class Public, class Stats> static int cloud_results(const GofJob& j, int rc, const std::vector<Entry>& in, const std::vector<FloorOut<Result>>& outs, Public* res,
-                                                                                        uint8_t** out, size_t* n_out, Stats stats) {
-  for (int i = 0; i < j.n && !rc; i++) {
-    Public& o = res[i]; memset(&o, 0, sizeof(o));
+// over its frames
+template <class Entry, class Result, class Public, class Stats> static void cloud_results(const GofJob& j, HandOver& h, const std::vector<Entry>& in, const std::vector<FloorOut<Result>>& outs, Public* res,
+                                                                                         const size_t* n_out, Stats stats) {
+  for (int i = 0; i < j.n && !h.rc; i++) {
+    Public& o = res[i];
     o.qp = o.qp_probe = o.qp_start = j.params[i].qp; o.met = 1; o.n_encodes = j.is_pass[i] ? 0 : 1; o.bytes = (uint64_t)n_out[i];
     if (in.empty() || in[i].t.n_frames <= 0 || i >= (int)outs.size()) continue;
     const FloorOut<Result>& r = outs[i];
     o.qp = r.qp; o.qp_probe = r.q0; o.qp_start = r.qs; o.met = r.met; o.n_encodes = r.n_enc; o.bytes = r.bytes; o.cloud_ms = r.cloud_ms; o.n_frames = (int)r.frames.size();
     stats(o, r.frames.data());
-    o.frames = (Result*)malloc(sizeof(Result) * r.frames.size());
-    if (!o.frames) { rc = RBT_ERR_NOMEM; break; }
-    memcpy(o.frames, r.frames.data(), sizeof(Result) * r.frames.size());
+    o.frames = h.copy(r.frames);
   }
-  if (rc) for (int i = 0; i < j.n; i++) { free(res[i].frames); memset(&res[i], 0, sizeof(res[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; }
-  return rc;
+}
+// The public results of a job with floors held patch by patch, either kind: per entry its own QP and its stream, or what the rounds left of an entry with a target
+// (PatchOut) - the header, the final map, the frames and their picks, every frame pointing at its own. What a kind adds to the result, to a frame and to its picks:
+static void patch_payload(rbt_patch_floor_result& o, const PatchOut& r, int met, int n_enc) { quality_fill_result(o.sums, -1, -1, -1, met, n_enc, o.bytes, r.sums, r.bit_depth); }
+static void patch_payload(rbt_patch_d1_result& o, const PatchOut& r, int, int) { o.cloud_ms = r.cloud_ms; }
+static void patch_payload(rbt_patch_frame& o, rbt_patch_pick* picks, const PatchOut& r, const PatchOut::Frame& f) {
+  for (int c = 0; c < 3; c++) o.background[c] = f.psnr.background[c];
+  for (size_t k = 0; k < f.psnr.patches.size(); k++) { const PatchSums& s = f.psnr.patches[k]; picks[k].sse = r.region ? s.sse_occ : s.sse; picks[k].samples = r.region ? s.samples_occ : s.samples; }
+}
+static void patch_payload(rbt_patch_d1_frame& o, rbt_patch_d1_pick* picks, const PatchOut&, const PatchOut::Frame& f) {
+  o.d1 = f.d1.whole;
+  for (size_t k = 0; k < f.d1.patches.size(); k++) picks[k].d1 = f.d1.patches[k];
+}
+template <class Public> static void patch_results(const GofJob& j, HandOver& h, Public* res, const size_t* n_out) {
+  typedef typename std::remove_pointer<decltype(res->frames)>::type Frame; typedef typename std::remove_pointer<decltype(res->picks)>::type Pick;
+  const PatchOut none;      // an entry no round coded - a pass-through or occupancy entry -: no frames, no sums
+  for (int i = 0; i < j.n && !h.rc; i++) {
+    Public& o = res[i];
+    const PatchOut& r = i < (int)j.pout.size() && !j.is_pass[i] && j.params[i].video_type != RBT_VIDEO_OCCUPANCY ? j.pout[i] : none;
+    o.qp_probe = j.params[i].qp; o.met_all = 1; o.bytes = (uint64_t)n_out[i];
+    if (r.frames.empty()) { patch_payload(o, r, 1, j.is_pass[i] ? 0 : 1); continue; }      // no target: the sums of its only encode
+    o.n_frames = (int)r.frames.size(); o.qp_probe = r.q0; o.n_passes = r.n_passes; o.pictures_encoded = r.pictures; o.w_ctb = r.wc; o.h_ctb = r.hc;
+    std::vector<Frame> frames(r.frames.size()); std::vector<Pick> picks(r.picks.size()); size_t at = 0;
+    for (size_t f = 0; f < frames.size(); f++) {
+      const PatchOut::Frame& rf = r.frames[f]; Frame& pf = frames[f];
+      pf.n_trials = rf.n_trials; pf.met = rf.met; pf.n_patches = rf.n_patches; pf.bytes = rf.bytes; o.met_all &= rf.met;
+      for (int k = 0; k < rf.n_patches; k++) { const PatchOut::Pick& rp = r.picks[at + k]; Pick& pk = picks[at + k]; pk.qp = rp.qp; pk.met = rp.met; pk.failed = rp.failed; pk.figure = rp.figure; }
+      patch_payload(pf, picks.data() + at, r, rf);
+      at += (size_t)rf.n_patches;
+    }
+    patch_payload(o, r, o.met_all, (int)(r.pictures / 2));
+    o.map = h.copy(r.map); o.frames = h.copy(frames); o.picks = h.copy(picks);
+    at = 0; for (int f = 0; f < o.n_frames && !h.rc; f++) { o.frames[f].patches = o.picks + at; at += (size_t)o.frames[f].n_patches; }
+  }
 }
 // phase B, shortest pipeline first: one sync per stream, then slice sizes -> pack -> NAL assembly. Consumes the job.
 int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResults& res) {
@@ -1850,7 +1875,8 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResult
   const int n = j.n, ng = j.ng; int rc = j.rc;
   rbt_stats& st = j.st; std::string& err = j.err;
   std::vector<DecodeBatch>& db = j.db; std::vector<EncodeBatch>& eb = j.eb; const rbt_stream_params* p = j.params.data();
-  for (int i = 0; i < n; i++) { out[i] = nullptr; n_out[i] = 0; if (d1results) memset(&d1results[i], 0, sizeof(d1results[i])); if (cresults) memset(&cresults[i], 0, sizeof(cresults[i])); if (res.patches) memset(&res.patches[i], 0, sizeof(res.patches[i])); }
+  for (int i = 0; i < n; i++) { out[i] = nullptr; n_out[i] = 0; }
+  zero_results(res, n);
   std::vector<std::vector<uint8_t>> outs(n);
   // a job with quality floors: the pipelines that were encoded at submit first - its occupancy pipelines, whose pooled planes and maps the others' rounds read -, then those
   // that are encoded here; every other job has one pass
@@ -1876,7 +1902,7 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResult
   if (n_flat) { *n_flat = 0; for (int g = 0; g < ng; g++) *n_flat += db[g].n_flat; }      // decoded pictures reconstructed with flat chroma (came back with the error words: decode_finish)
   for (int i = 0; i < n; i++) if (j.is_pass[i]) outs[i].swap(j.passthrough[i]);
   st.gpu_ms = now_ms() - j.t_gpu;
-  rc = hand_out(outs, out, n_out);
+  HandOver h; h.rc = hand_out(outs, out, n_out);
   if (results) for (int i = 0; i < n; i++) {
     if (has_target(j, i)) { results[i] = j.results[i]; continue; }
     results[i] = rbt_rate_result{p[i].qp, p[i].qp, 1, j.is_pass[i] ? 0 : 1, (uint64_t)n_out[i], 0};
@@ -1885,66 +1911,24 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResult
     if (quality && !j.is_pass[i] && p[i].video_type != RBT_VIDEO_OCCUPANCY && i < (int)j.qresults.size()) { qresults[i] = j.qresults[i]; continue; }
     quality_fill_result(qresults[i], p[i].qp, p[i].qp, p[i].qp, 1, j.is_pass[i] ? 0 : 1, (uint64_t)n_out[i], QualitySums(), 8);
   }
-  if (fresults) for (int i = 0; i < n; i++) memset(&fresults[i], 0, sizeof(fresults[i]));
-  if (fresults && !rc) for (int i = 0; i < n; i++) {
+  if (fresults) for (int i = 0; i < n && !h.rc; i++) {
     rbt_frame_floor_result& o = fresults[i];
     o.qp_probe = p[i].qp; o.met_all = 1; o.bytes = (uint64_t)n_out[i];
     quality_fill_result(o.sums, -1, -1, -1, 1, 0, o.bytes, QualitySums(), 8);
     if (i >= (int)j.fout.size() || j.fout[i].frames.empty()) continue;
     const FrameFloorOut& r = j.fout[i];
-    o.n_frames = (int)r.frames.size(); o.qp_probe = r.q0; o.n_passes = r.n_passes; o.pictures_encoded = r.pictures;
+    o.n_frames = (int)r.frames.size(); o.qp_probe = r.q0; o.n_passes = r.n_passes; o.pictures_encoded = r.pictures; o.cloud_ms = r.cloud_ms;
     for (const rbt_frame_pick& f : r.frames) o.met_all &= f.met;
     quality_fill_result(o.sums, -1, -1, -1, o.met_all, (int)(r.pictures / 2), o.bytes, r.sums, r.bit_depth);
-    o.frames = (rbt_frame_pick*)malloc(sizeof(rbt_frame_pick) * r.frames.size());
-    if (!o.frames) { rc = RBT_ERR_NOMEM; break; }
-    memcpy(o.frames, r.frames.data(), sizeof(rbt_frame_pick) * r.frames.size());
-    o.cloud_ms = r.cloud_ms;
-    if (!r.d1.empty()) {
-      o.d1 = (rbt_d1_result*)malloc(sizeof(rbt_d1_result) * r.d1.size());
-      if (!o.d1) { rc = RBT_ERR_NOMEM; break; }
-      memcpy(o.d1, r.d1.data(), sizeof(rbt_d1_result) * r.d1.size());
-    }
+    o.frames = h.copy(r.frames);
+    if (!r.d1.empty()) o.d1 = h.copy(r.d1);
   }
-  if (fresults && rc) { for (int i = 0; i < n; i++) { free(fresults[i].frames); free(fresults[i].d1); memset(&fresults[i], 0, sizeof(fresults[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; } }
-  if (rbt_patch_floor_result* pres = res.patches) {
-    for (int i = 0; i < n; i++) memset(&pres[i], 0, sizeof(pres[i]));
-    for (int i = 0; i < n && !rc; i++) {
-      rbt_patch_floor_result& o = pres[i];
-      o.qp_probe = p[i].qp; o.met_all = 1; o.bytes = (uint64_t)n_out[i];
-      quality_fill_result(o.sums, -1, -1, -1, 1, j.is_pass[i] ? 0 : 1, o.bytes, QualitySums(), 8);
-      if (i >= (int)j.pout.size() || j.is_pass[i] || p[i].video_type == RBT_VIDEO_OCCUPANCY) continue;
-      const PatchFloorOut& r = j.pout[i];
-      if (r.frames.empty()) { quality_fill_result(o.sums, -1, -1, -1, 1, 1, o.bytes, r.sums, r.bit_depth); continue; }
-      o.n_frames = (int)r.frames.size(); o.qp_probe = r.q0; o.n_passes = r.n_passes; o.pictures_encoded = r.pictures; o.w_ctb = r.wc; o.h_ctb = r.hc;
-      for (const rbt_patch_frame& f : r.frames) o.met_all &= f.met;
-      quality_fill_result(o.sums, -1, -1, -1, o.met_all, (int)(r.pictures / 2), o.bytes, r.sums, r.bit_depth);
-      o.map = (int8_t*)malloc(std::max<size_t>(1, r.map.size())); o.frames = (rbt_patch_frame*)malloc(sizeof(rbt_patch_frame) * r.frames.size());
-      o.picks = (rbt_patch_pick*)malloc(sizeof(rbt_patch_pick) * std::max<size_t>(1, r.picks.size()));
-      if (!o.map || !o.frames || !o.picks) { rc = RBT_ERR_NOMEM; break; }
-      memcpy(o.map, r.map.data(), r.map.size()); memcpy(o.frames, r.frames.data(), sizeof(rbt_patch_frame) * r.frames.size()); memcpy(o.picks, r.picks.data(), sizeof(rbt_patch_pick) * r.picks.size());
-      size_t at = 0; for (int f = 0; f < o.n_frames; f++) { o.frames[f].patches = o.picks + at; at += (size_t)o.frames[f].n_patches; }
-    }
-    if (rc) for (int i = 0; i < n; i++) { free(pres[i].map); free(pres[i].frames); free(pres[i].picks); memset(&pres[i], 0, sizeof(pres[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; }
-  }
-  if (rbt_patch_d1_result* pres = res.d1_patches) {
-    for (int i = 0; i < n; i++) memset(&pres[i], 0, sizeof(pres[i]));
-    for (int i = 0; i < n && !rc; i++) {
-      rbt_patch_d1_result& o = pres[i];
-      o.qp_probe = p[i].qp; o.met_all = 1; o.bytes = (uint64_t)n_out[i];
-      if (i >= (int)j.pdout.size() || j.pdout[i].frames.empty()) continue;
-      const PatchD1Out& r = j.pdout[i];
-      o.n_frames = (int)r.frames.size(); o.qp_probe = r.q0; o.n_passes = r.n_passes; o.pictures_encoded = r.pictures; o.w_ctb = r.wc; o.h_ctb = r.hc; o.cloud_ms = r.cloud_ms;
-      for (const rbt_patch_d1_frame& f : r.frames) o.met_all &= f.met;
-      o.map = (int8_t*)malloc(std::max<size_t>(1, r.map.size())); o.frames = (rbt_patch_d1_frame*)malloc(sizeof(rbt_patch_d1_frame) * r.frames.size());
-      o.picks = (rbt_patch_d1_pick*)malloc(sizeof(rbt_patch_d1_pick) * std::max<size_t>(1, r.picks.size()));
-      if (!o.map || !o.frames || !o.picks) { rc = RBT_ERR_NOMEM; break; }
-      memcpy(o.map, r.map.data(), r.map.size()); memcpy(o.frames, r.frames.data(), sizeof(rbt_patch_d1_frame) * r.frames.size()); memcpy(o.picks, r.picks.data(), sizeof(rbt_patch_d1_pick) * r.picks.size());
-      size_t at = 0; for (int f = 0; f < o.n_frames; f++) { o.frames[f].patches = o.picks + at; at += (size_t)o.frames[f].n_patches; }
-    }
-    if (rc) for (int i = 0; i < n; i++) { free(pres[i].map); free(pres[i].frames); free(pres[i].picks); memset(&pres[i], 0, sizeof(pres[i])); free(out[i]); out[i] = nullptr; n_out[i] = 0; }
-  }
-  if (d1results) rc = cloud_results(j, rc, j.d1, j.d1out, d1results, out, n_out, [](rbt_d1_floor_result& o, const rbt_d1_result* f) { d1_stats(f, o.n_frames, &o.mean_d1, &o.min_d1); });
-  if (cresults) rc = cloud_results(j, rc, j.color, j.colorout, cresults, out, n_out, [](rbt_color_floor_result& o, const rbt_color_result* f) { color_stats(f, o.n_frames, o.mean_psnr, o.min_psnr); });
+  if (res.patches) patch_results(j, h, res.patches, n_out);
+  if (res.d1_patches) patch_results(j, h, res.d1_patches, n_out);
+  if (d1results) cloud_results(j, h, j.d1, j.d1out, d1results, n_out, [](rbt_d1_floor_result& o, const rbt_d1_result* f) { d1_stats(f, o.n_frames, &o.mean_d1, &o.min_d1); });
+  if (cresults) cloud_results(j, h, j.color, j.colorout, cresults, n_out, [](rbt_color_floor_result& o, const rbt_color_result* f) { color_stats(f, o.n_frames, o.mean_psnr, o.min_psnr); });
+  rc = h.rc;
+  if (rc) { h.take_back(); zero_results(res, n); for (int i = 0; i < n; i++) { free(out[i]); out[i] = nullptr; n_out[i] = 0; } }      // all or nothing
   // SURVEY.md 8(d) algorithmic traffic: per coded picture of S samples (2 bytes each): decode writes S, P pictures read
   // their reference once; encode reads the source S, writes the reconstruction S (I) and reads the reference (P)
   uint64_t bytes = 0;

@@ -10,9 +10,13 @@ struct PCloud; struct PCloudCache;
 // entry resolved to the clouds (n_frames of them, nullptr = the cloud of the decoded input), and the context's cache of cloud volumes
 template <class Target> struct CloudRequest { const Target* targets = nullptr; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache = nullptr; };
 struct QpMapIn { std::vector<int8_t> qp; int n_frames = 0, w_ctb = 0, h_ctb = 0; };
-// PSNR floors held patch by patch (rbt_submit_gof_quality_patches), one per entry, checked and copied by the caller: the target without its pointers (n_frames 0: no target),
-// per frame the patches and their floors F_k
-struct PatchFloorIn { rbt_patch_floor_target t; std::vector<std::vector<rbt_patch>> patches; std::vector<std::vector<int32_t>> floors; };
+// Floors held patch by patch (rbt_submit_gof_quality_patches, rbt_submit_gof_d1_patches), one request per entry, checked and copied by the caller from its own target type: what
+// the walks read - the floor where a patch has none of its own, the region of the PSNR figure (RBT_QUALITY_ALL for D1), the QP range, the background's QP (-1 = q0), the cap on
+// the trials, of the atlas its size and occupancy_resolution - and per frame (n_frames 0: no target) the patches and their floors F_k
+struct PatchFloorIn {
+  int32_t floor_mdb = 0; int region = 0, qp_min = 0, qp_max = 0, background_qp = 0, max_trials = 0, atlas_width = 0, atlas_height = 0, occupancy_resolution = 0, n_frames = 0;
+  std::vector<std::vector<rbt_patch>> patches; std::vector<std::vector<int32_t>> floors;
+};
 // What a job is made of: the n inputs with their parameters, and at most one kind of target - each nullptr or one per entry, checked by the caller
 struct GofRequest {
   int n = 0; const uint8_t* const* in = nullptr; const size_t* n_in = nullptr; const rbt_stream_params* params = nullptr;
@@ -29,8 +33,8 @@ struct GofRequest {
   // the entry's own QP; not together with anything else
   const std::vector<QpMapIn>* qp_maps = nullptr;
   const std::vector<PatchFloorIn>* patch_floors = nullptr;   // PSNR floors held patch by patch (rbt_submit_gof_quality_patches); not together with anything else
-  // D1 floors held patch by patch (rbt_submit_gof_d1_patches): patch_floors carries the walks' side of the targets (floors, range, background, cap; min_psnr_mdb holds
-  // min_d1_mdb) and d1 their clouds' side (atlas, patch lists, references, peak; min_d1_mdb 0: no walk of its own)
+  // D1 floors held patch by patch (rbt_submit_gof_d1_patches): patch_floors carries the walks' side of the targets (floors, range, background, cap) and d1 their clouds'
+  // side (atlas, patch lists, references, peak; min_d1_mdb 0: no walk of its own)
   bool patch_d1 = false;
 };
 // Where a job's outcome goes: a stream per entry, and of the result arrays - one per entry each - the one of the job's kind; n_flat: nullptr, or the decoded pictures with flat chroma

@@ -6,7 +6,10 @@
 //           distances and the words per patch are exact-size heap blocks: a label read past the cloud or a word written past the last patch is caught
 //   labels  work items with their offsets, among them items without a point and the last one: every point gets its item's patch, nothing is written past the cloud
 //   adapter the figures of a patch from its words (patch_d1_finish) and what the walk is told (patch_d1_figure, patch_d1_meets): a direction without a point has mse 0,
-//           a patch without a point has psnr +inf and meets any floor, a floor is met at equality; then a walk driven by such figures ends
+//           a patch without a point has psnr +inf and meets any floor, a floor is met at equality; then a walk driven by such figures through the D1 source of a
+//           trial (patch_trial_d1) ends
+//   seam    two walks with one seed, one fed by the PSNR source (patch_trial_psnr, from fold words) and one by the D1 source (patch_trial_d1), trial by trial beside walks
+//           fed by patch_figure / patch_meets and patch_d1_figure / patch_d1_meets on the same inputs: the same figures, conditions and vectors, and the payloads kept
 //   check   the error word is set by a label that equals the patch count and by nothing less
 // Prints "ok".
 #define RBT_HOSTEMU 1
@@ -15,8 +18,7 @@
 #include <string.h>
 #include <vector>
 #include "../rabbit-transcoding_amd/csrc/rbt_score.h"
-#include "../rabbit-transcoding_amd/host/rbt_patch_walk.h"
-#include "../rabbit-transcoding_amd/host/rbt_d1_figures.h"
+#include "../rabbit-transcoding_amd/host/rbt_patch_walk.h"      // (with rbt_d1_figures.h)
 
 static int fail(const char* what, long a = 0, long b = 0, long c = 0) { printf("FAIL %s %ld %ld %ld\n", what, a, b, c); fflush(stdout); return 1; }
 static uint32_t g_seed = 24680;
@@ -117,20 +119,85 @@ static int adapter_case() {
   rbt::PatchWalk w; rbt::patch_walk_seed(w, 30, 20, 40, 0, floors);
   for (int trial = 0;; trial++) {
     if (trial > 200) return fail("walk does not end");
-    std::vector<double> f(3); std::vector<char> m(3);
+    std::vector<rbt_patch_d1> pd(3); rbt_d1_result whole; memset(&whole, 0, sizeof(whole));
     for (int k = 0; k < 3; k++) {
-      rbt_patch_d1 p; memset(&p, 0, sizeof(p));
+      rbt_patch_d1& p = pd[(size_t)k]; memset(&p, 0, sizeof(p));
       if (k < 2) { p.n_ab = p.n_ba = 1000; p.sse_ab = p.sse_ba = (uint64_t)(1000 * 3.0 * 1023 * 1023 / pow(10.0, (62.0 + k - 0.04 * w.q[k]) / 10.0)); }
-      rbt::patch_d1_finish(&p, 1023); f[k] = rbt::patch_d1_figure(p); m[k] = rbt::patch_d1_meets(p, floors[(size_t)k]);
+      rbt::patch_d1_finish(&p, 1023);
     }
-    if (rbt::patch_walk_step(w, f.data(), m.data())) break;
+    rbt::PatchTrial said; rbt::PatchD1 kept;
+    rbt::patch_trial_d1(pd, whole, floors, said, kept);
+    if (said.figure.size() != 3 || said.meets.size() != 3 || kept.patches.size() != 3) return fail("trial size");
+    if (rbt::patch_walk_step(w, said.figure.data(), said.meets.data())) break;
   }
   if (!w.met[2] || w.q[2] != 30 || !w.met[0]) return fail("walk result", w.q[0], w.q[1], w.q[2]);
   return 0;
 }
 
+// one seed, two kinds of figure: each source against the plain functions on the same inputs, and the walks they drive against each other
+static int seam_case() {
+  const int np = 5, bit_depth = 10, peak = 1023;
+  for (int region = 0; region < 2; region++) {
+    const std::vector<int32_t> floors = {38000, 0, 45500, 90000, 41000};
+    const std::vector<uint64_t> samples = {2048, 512, 0, 8192, 1024};      // patch 2 has no sample: figure 0, meets
+    rbt::PatchWalk ws[4];      // PSNR through the source / by the functions, D1 through the source / by the functions
+    for (rbt::PatchWalk& w : ws) rbt::patch_walk_seed(w, 30, 18, 44, 0, floors);
+    for (int trial = 0; !ws[0].settled || !ws[2].settled; trial++) {
+      if (trial > 400) return fail("seam walks do not end", region);
+      if (!ws[0].settled) {
+        // fold words as k_patch_fold leaves them: sse, sse_occ, n_occ per patch, then the background's - about a dB per QP step, the occupied half a little better
+        uint64_t* words = (uint64_t*)malloc((size_t)(np + 1) * 24);      // an exact-size block: a read past the background's words is caught
+        for (int k = 0; k < np; k++) {
+          const double mse = 1023.0 * 1023.0 / pow(10.0, (70.0 + 2 * k - 0.9 * ws[0].q[(size_t)k]) / 10.0);
+          words[3 * k] = (uint64_t)(mse * (double)samples[(size_t)k]); words[3 * k + 2] = samples[(size_t)k] / 2; words[3 * k + 1] = (uint64_t)(0.8 * mse * (double)words[3 * k + 2]);
+        }
+        if (trial == 1) words[3] = words[4] = 0;                           // no error at all: the figure is infinite and meets
+        for (int c = 0; c < 3; c++) words[3 * np + c] = 1000 + (uint64_t)(7 * trial + c);
+        rbt::PatchTrial said; rbt::PatchPsnr kept; std::vector<double> f((size_t)np); std::vector<char> m((size_t)np);
+        rbt::patch_trial_psnr(words, samples, region, bit_depth, floors, said, kept);
+        if ((int)said.figure.size() != np || (int)said.meets.size() != np || (int)kept.patches.size() != np) return fail("psnr trial size", region, trial);
+        for (int k = 0; k < np; k++) {
+          rbt::PatchSums s; s.sse = words[3 * k]; s.sse_occ = words[3 * k + 1]; s.samples_occ = words[3 * k + 2]; s.samples = samples[(size_t)k];
+          f[(size_t)k] = rbt::patch_figure(s, region, bit_depth); m[(size_t)k] = rbt::patch_meets(s, region, floors[(size_t)k], bit_depth);
+          const rbt::PatchSums& g = kept.patches[(size_t)k];
+          if (g.sse != s.sse || g.sse_occ != s.sse_occ || g.samples_occ != s.samples_occ || g.samples != s.samples) return fail("psnr payload", region, trial, k);
+          if (memcmp(&said.figure[(size_t)k], &f[(size_t)k], sizeof(double)) || (said.meets[(size_t)k] != 0) != (m[(size_t)k] != 0)) return fail("psnr source is not patch_figure / patch_meets", region, trial, k);
+        }
+        for (int c = 0; c < 3; c++) if (kept.background[c] != words[3 * np + c]) return fail("background", region, trial, c);
+        free(words);
+        const bool a = rbt::patch_walk_step(ws[0], said.figure.data(), said.meets.data()), b = rbt::patch_walk_step(ws[1], f.data(), m.data());
+        if (a != b || ws[0].q != ws[1].q || ws[0].met != ws[1].met || ws[0].failed != ws[1].failed) return fail("psnr walks part", region, trial);
+      }
+      if (!ws[2].settled) {
+        std::vector<rbt_patch_d1> pd((size_t)np), copy; rbt_d1_result whole; memset(&whole, 0, sizeof(whole)); whole.psnr = 60.0f + (float)trial; whole.n_a = 77;
+        for (int k = 0; k < np; k++) {
+          rbt_patch_d1& p = pd[(size_t)k]; memset(&p, 0, sizeof(p));
+          if (k != 2) { p.n_ab = 900 + (uint64_t)k; p.n_ba = 1000; p.sse_ba = (uint64_t)(1000 * 3.0 * peak * peak / pow(10.0, (70.0 + 2 * k - 0.9 * ws[2].q[(size_t)k]) / 10.0)); p.sse_ab = p.sse_ba / 2; }      // patch 2 has no point
+          rbt::patch_d1_finish(&p, peak);
+        }
+        copy = pd;
+        rbt::PatchTrial said; rbt::PatchD1 kept; std::vector<double> f((size_t)np); std::vector<char> m((size_t)np);
+        rbt::patch_trial_d1(pd, whole, floors, said, kept);
+        if ((int)said.figure.size() != np || (int)said.meets.size() != np || (int)kept.patches.size() != np) return fail("d1 trial size", region, trial);
+        if (memcmp(&kept.whole, &whole, sizeof(whole))) return fail("whole frame", region, trial);
+        for (int k = 0; k < np; k++) {
+          f[(size_t)k] = rbt::patch_d1_figure(copy[(size_t)k]); m[(size_t)k] = rbt::patch_d1_meets(copy[(size_t)k], floors[(size_t)k]);
+          if (memcmp(&kept.patches[(size_t)k], &copy[(size_t)k], sizeof(rbt_patch_d1))) return fail("d1 payload", region, trial, k);
+          if (memcmp(&said.figure[(size_t)k], &f[(size_t)k], sizeof(double)) || (said.meets[(size_t)k] != 0) != (m[(size_t)k] != 0)) return fail("d1 source is not patch_d1_figure / patch_d1_meets", region, trial, k);
+        }
+        if (!std::isinf(said.figure[2]) || !said.meets[2]) return fail("a patch without a point through the source", region, trial);
+        const bool a = rbt::patch_walk_step(ws[2], said.figure.data(), said.meets.data()), b = rbt::patch_walk_step(ws[3], f.data(), m.data());
+        if (a != b || ws[2].q != ws[3].q || ws[2].met != ws[3].met || ws[2].failed != ws[3].failed) return fail("d1 walks part", region, trial);
+      }
+    }
+    // what the floors say of either walk's end: the floor nothing reaches sits at lo, the patch without a floor never failed
+    for (int w = 0; w < 4; w += 2) if (ws[w].q[3] != 18 || ws[w].met[3] || ws[w].failed[1] || !ws[w].met[2]) return fail("seam walk result", region, w, ws[w].q[3]);
+  }
+  return 0;
+}
+
 int main() {
-  if (adapter_case()) return 1;
+  if (adapter_case() || seam_case()) return 1;
   Cloud CA, CB;
   CA.vol = (uint32_t*)calloc(VOL_WORDS + RBT_SC_COARSE_WORDS, 4); CB.vol = (uint32_t*)calloc(VOL_WORDS + RBT_SC_COARSE_WORDS, 4);
   if (!CA.vol || !CB.vol) return fail("calloc");

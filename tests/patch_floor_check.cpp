@@ -1,6 +1,6 @@
 // TEST-ONLY: the walk of the PSNR floors held patch by patch (host/rbt_patch_walk.h) and the bodies of the sums per CTB and per patch (csrc/rbt_ctbsse.h) as a stand-alone
 // host program, so that they can be built with -fsanitize=address,undefined and run on the CPU (tests/test_patch_floor.py).
-//   walk    driven trial by trial the way finish_round drives it, over synthetic figure functions of the QP vector - monotone, not monotone, and coupled (a patch's figure
+//   walk    driven trial by trial the way finish_round drives it - a PatchTrial per frame and trial -, over synthetic figure functions of the QP vector - monotone, not monotone, and coupled (a patch's figure
 //           depends on its neighbours' QPs through the minimum a shared CTB takes) -, 1 to 40 patches, random floors, ranges and starts. Checked: it ends within the sum over
 //           the patches of (hi - q0) + (hi - lo) + 1 trials; no patch rises after it failed; the result is the last trial's vector; met is what the last figures say; without
 //           a cap every patch meets or sits at lo; a cap is honoured
@@ -40,7 +40,9 @@ static int walk_case(int kind, int n, int qp, int lo, int hi, int cap) {
   if (w.q0 != q0 || (int)w.q.size() != n) return fail("seed", qp, w.q0, q0);
   for (int k = 0; k < n; k++) if (w.q[k] != q0) return fail("trial 0 is not q0", k, w.q[k], q0);
   const long bound = (long)n * ((hi - q0) + (hi - lo) + 1) + 1;      // (+ 1: a frame without patches takes its one trial)
-  std::vector<char> failed(n, 0), meets(n); std::vector<double> fig(n); std::vector<int> last;
+  std::vector<char> failed(n, 0); std::vector<int> last;
+  rbt::PatchTrial said; said.figure.resize((size_t)n); said.meets.resize((size_t)n);      // what a trial said, as the walk's caller hands it over
+  std::vector<double>& fig = said.figure; std::vector<char>& meets = said.meets;
   for (long trial = 1;; trial++) {
     if (trial > bound) return fail("walk does not end", kind, n, trial);
     last = w.q;
@@ -81,6 +83,14 @@ static int region_cases() {
   rbt::patch_region(96, 80, 16, -3, -2, 2, 1, 5, r); if (r[0] | r[1] | r[2] | r[3]) return fail("region: negative");
   rbt::PatchSums s; if (!rbt::patch_meets(s, 0, 99000, 10) || rbt::patch_figure(s, 1, 10) != 0.0) return fail("no sample meets");
   s.samples = 100; s.sse = 100; if (rbt::patch_meets(s, 0, 61000, 10) || !rbt::patch_meets(s, 1, 61000, 10) || !rbt::patch_meets(s, 0, 60000, 10)) return fail("meets");
+  // the same through the PSNR source of a trial: patch 0 without a sample, patch 1 with mse 1 (60.2 dB at 10 bits) and nothing occupied; the background's words behind them
+  const uint64_t words[9] = {0, 0, 0, 100, 0, 0, 7, 8, 9}; const std::vector<uint64_t> samples = {0, 100};
+  rbt::PatchTrial t; rbt::PatchPsnr p;
+  rbt::patch_trial_psnr(words, samples, 0, 10, {99000, 61000}, t, p);
+  if (t.figure.size() != 2 || !t.meets[0] || t.figure[0] != 0.0 || t.meets[1] || t.figure[1] != rbt::patch_figure(s, 0, 10)) return fail("source: all samples");
+  rbt::patch_trial_psnr(words, samples, 0, 10, {99000, 60000}, t, p); if (!t.meets[1]) return fail("source: a lower floor");
+  rbt::patch_trial_psnr(words, samples, 1, 10, {99000, 61000}, t, p); if (!t.meets[0] || !t.meets[1] || t.figure[1] != 0.0) return fail("source: occupied");
+  if (p.patches.size() != 2 || p.patches[1].sse != 100 || p.patches[1].samples != 100 || p.background[0] != 7 || p.background[1] != 8 || p.background[2] != 9) return fail("source: payload");
   return 0;
 }
 
