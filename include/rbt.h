@@ -484,7 +484,14 @@ typedef struct {
   uint64_t sse_ab, sse_ba, max_ab, max_ba;   /* sum / maximum of squared nearest-neighbour distances, A -> B and B -> A (exact integers) */
   float mse_ab, mse_ba, psnr_ab, psnr_ba, psnr;   /* psnr = 10 log10(3 peak^2 / max(mse_ab, mse_ba)) (PCCMetrics.cpp:44-48, :299-309) */
 } rbt_d1_result;
-/* point-to-point (D1) metric between two clouds; coordinates 0..1023 (peak = 1023 in the CTC). */
+/* point-to-point (D1) metric between two clouds; coordinates 0..1023 (peak = 1023 in the CTC).
+ * rbt_d1, rbt_d2 and rbt_color_metric are each the upload, one score and the release of two temporary clouds ("frame scoring on clouds that stay on the device" below:
+ * the same index, search and walks, so out is that part of rbt_score's result, field for field and bit for bit, and two calls return the same bits). RBT_ERR_PARAM with
+ * the reason in rbt_last_error: an empty cloud (for D1 and D2 also peak <= 0) and, checked on the device, cloud A before cloud B, a coordinate outside 0..1023 or more
+ * than 2^26 points in a cloud. Device memory while a call runs, all of it back in the pool when it returns (the context's cloud cache, rbt_device_memory's cached
+ * figure and rbt_trim see nothing of it): per cloud a 128 MB bit volume with its 256 KB coarse level, the points, and 28 bytes per slot of the voxel map, whose slot
+ * count is the power of two that is at least 2 n (16 at the least); the score's scratch of 4 bytes per point (for D2 also 8 per point, 28 per point of B and 16 per 256 points of the larger cloud). For
+ * rbt_d1 that is more than the byte per point it took next to the volumes before it shared the index. */
 int rbt_d1(rbt_ctx* ctx, const int16_t* xyz_a, int n_a, const int16_t* xyz_b, int n_b, int peak, rbt_d1_result* out);
 /* point-to-plane (D2) metric, the other half of BASELINE's "D1/D2 geom PSNR": QualityMetrics::compute with computeC2p_ (PCCMetrics.cpp:100-124, :213-215), symmetric (:299-309),
  * between a source cloud A that comes with normals (three per point, fixed point Q14: 16384 = 1.0) and a decoded cloud B that gets its normals from A the way
@@ -492,7 +499,8 @@ int rbt_d1(rbt_ctx* ctx, const int16_t* xyz_a, int n_a, const int16_t* xyz_b, in
  * the points of B nearest to it, a point of B that got none takes the mean of the source points nearest to it). Per point of one cloud: the mean, over the other cloud's points
  * at the nearest distance, of the squared projection of the difference on that point's normal. Where the reference depends on the order its kd-tree returns equidistant points
  * in, this is defined instead: duplicates are merged first and a merged point keeps the normal of its lowest-index duplicate; ALL points at exactly the nearest squared
- * distance count (the reference looks at up to 30 results). */
+ * distance count (the reference looks at up to 30 results). The two sums are added in the fixed order given at rbt_score. Upload + score + release, refusals and
+ * memory as at rbt_d1; normals_a is required. */
 typedef struct {
   int n_a, n_b;
   double sse_ab, sse_ba, max_ab, max_ba;              /* sum / maximum of the per-point values, A -> B and B -> A */
@@ -594,7 +602,8 @@ int rbt_reconstruct_rgb(rbt_ctx* ctx, const rbt_atlas_params* atlas, const rbt_p
  *  - per channel the error term is the BT.709 row of convertRGBtoYUVBT709 (:50-55) times 10000 applied to the RGB difference, an integer of magnitude <= 2.55e6; sse is the
  *    sum of its squares, exact in 64 bits for up to 2^21 merged points per cloud (more are refused, RBT_ERR_PARAM);
  *  - mse = (float)(sse / (2550000^2 n)), psnr = 10 log10f(1 / mse) (getPSNR(mse, 1.0)): identical clouds give mse 0 and psnr +inf.
- * Coordinates 0..1023. Index 0, 1, 2 = Y, U, V. */
+ * Coordinates 0..1023. Index 0, 1, 2 = Y, U, V. Upload + score + release, refusals and memory as at rbt_d1 (3 more bytes per point for the colours); both clouds need
+ * colours, and the merged points are counted, and more than 2^21 refused, after the two uploads and before the score. */
 typedef struct {
   int n_a, n_b;                            /* points after merging duplicates */
   uint64_t sse_ab[3], sse_ba[3];           /* exact integers */
@@ -602,7 +611,7 @@ typedef struct {
 } rbt_color_result;
 int rbt_color_metric(rbt_ctx* ctx, const int16_t* xyz_a, const uint8_t* rgb_a, int n_a, const int16_t* xyz_b, const uint8_t* rgb_b, int n_b, rbt_color_result* out);
 /* Device time in milliseconds (events around the launches) the three stages took in this context's last call of each: [0] up-conversion, [1] RGB conversion,
- * [2] colour metric (its kernels: insert + merge and distance, without the read-back of the merged counts between them); 0 for a stage that has not run. The stages are
+ * [2] colour metric (the device_ms of its score: the search, the walks and the sums; the building of the two indices is outside); 0 for a stage that has not run and after a call that was refused. The stages are
  * separate launches inside calls that also copy and allocate: this is the only way to time them without a profiling build (tools/color_quality.py). */
 int rbt_color_stage_ms(rbt_ctx* ctx, double ms[3]);
 
@@ -645,16 +654,18 @@ int rbt_reconstruct_decoded(rbt_ctx* ctx, const rbt_atlas_params* atlas, const r
 int rbt_transfer_stage(rbt_ctx* ctx, double* ms, int* n_changed);
 
 /* ---- frame scoring on clouds that stay on the device (csrc/rbt_score.h) ----
- * rbt_d1, rbt_d2 and rbt_color_metric each upload both clouds, build their own index and search on their own. Here a cloud is uploaded (or reconstructed) once and
- * indexed once - bit volume, a coarse level over it, one map voxel -> lowest point index + merged colour - and rbt_score runs one nearest-distance search per direction
- * that feeds all three metrics. The definitions do not change: out->d1 is what rbt_d1(a, b, peak) returns, out->color what rbt_color_metric(a, b) returns and out->d2
- * what rbt_d2(a, normals_a, b, peak) returns (same merged points and representatives, same tie sets - all points at exactly the nearest squared distance -, same give /
- * take rule for the decoded cloud's normals), with one exception, the order of the two D2 sums:
- *   rbt_d2 adds its per-point values with floating-point atomics, in order of arrival. rbt_score stores the value v[i] of every point i (0 for a point that is not the
- *   lowest-index point of its voxel) and adds them in an order that depends on the input alone. Block b holds s[t] = v[256 b + t], t = 0..255 (0 past the last point) and
+ * This is the one implementation of the three metrics. A cloud is uploaded (or reconstructed) once and indexed once - bit volume, a coarse level over it, one map
+ * voxel -> lowest point index + merged colour - and rbt_score runs one nearest-distance search per direction that feeds all three metrics. rbt_d1, rbt_d2 and
+ * rbt_color_metric take host arrays and are this path on two clouds that live for the call: each uploads both clouds, scores its one part and releases them, so a caller
+ * with more than one metric to take, or a cloud to score more than once, is better served here. out->d1 is what rbt_d1(a, b, peak) returns, out->color what
+ * rbt_color_metric(a, b) returns and out->d2 what rbt_d2(a, normals_a, b, peak) returns, field for field and bit for bit (merged points and representatives, tie sets -
+ * all points at exactly the nearest squared distance -, the give / take rule for the decoded cloud's normals). The order of the two D2 sums, of rbt_score and rbt_d2 alike:
+ *   no floating-point atomics. The value v[i] of every point i is stored (0 for a point that is not the lowest-index point of its voxel) and the values are added in
+ *   an order that depends on the input alone. Block b holds s[t] = v[256 b + t], t = 0..255 (0 past the last point) and
  *   is folded by s[t] = s[t] + s[t + h] for all t < h, h = 128, 64, .. 1; its sum is s[0]. Then S[t] = the sums of blocks t, t + 256, t + 512, .. added in ascending
  *   order starting from 0, t = 0..255, and S is folded the same way; sse = S[0]. Every operation is a double addition rounded on its own. Two calls therefore return the
- *   same bits, and so does the serial host emulation of the kernels. sse_* may differ from rbt_d2's in the last bits (relative 1e-9 at most for these sizes); max_* and the
+ *   same bits, of rbt_score and of rbt_d2 alike, and so does the serial host emulation of the kernels. A sum taken in another order - the oracle's, or rbt_d2's before
+ *   it became this path, which added with floating-point atomics in order of arrival - differs in the last bits (relative 1e-9 at most for these sizes); max_* and the
  *   counts are exact.
  * A handle belongs to the context that made it: used with another context it is refused (RBT_ERR_PARAM); rbt_destroy releases the handles still outstanding.
  * Limits: 1 .. 2^26 points a cloud, coordinates 0..1023 (a coordinate outside is RBT_ERR_PARAM: a kernel checks them and reports through an error word before any

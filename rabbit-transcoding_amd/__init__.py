@@ -1076,7 +1076,8 @@ class Context:
         return {n: (getattr(r, n) if n in ("n_a", "n_b") else list(getattr(r, n))) for n, _ in ColorResult._fields_}
 
     def color_stage_ms(self):
-        """rbt_color_stage_ms + rbt_transfer_stage: device milliseconds of the last up-conversion, RGB conversion, colour metric and attribute transfer of this context"""
+        """rbt_color_stage_ms + rbt_transfer_stage: device milliseconds of the last up-conversion, RGB conversion, colour metric (the device_ms of its
+        score: search, walks and sums, the index building outside) and attribute transfer of this context"""
         ms = (C.c_double * 3)(); t = C.c_double()
         self._chk(self.L.rbt_color_stage_ms(self.h, ms))
         self._chk(self.L.rbt_transfer_stage(self.h, C.byref(t), None))

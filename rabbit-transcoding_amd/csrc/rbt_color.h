@@ -12,6 +12,7 @@
 // The metric is integer throughout (the reference's float form and how far the two can differ: DESIGN.md 8): a cloud becomes a bit volume plus a hash map voxel ->
 // slot (csrc/rbt_pcc.h), the slot holds the colour sums and the count of the voxel's points, and the set of nearest merged points is walked in the other cloud's
 // volume as for D2. The error terms are BT.709 differences times 10000 * 255; their squares are summed in unsigned 64-bit, so the order of arrival does not matter.
+// Index, search and walks are those of frame scoring (csrc/rbt_score.h); the slot look-ups they share with the transfer are below.
 //   attribute transfer  the re-colouring of the points geometry smoothing moved (PCCDecoder.cpp:434-494 -> PCCPointSet3::transferColors16bitBP, PCCPointSet.cpp:1126-1485, with
 //                  the CTC's arguments): the last section of this file
 //
@@ -30,9 +31,6 @@
 enum { RBT_UP_TW = 64, RBT_UP_TH = 32, RBT_UP_SW = RBT_UP_TW / 2 + 3, RBT_UP_SH = RBT_UP_TH / 2 + 4, RBT_UP_STRIDE = RBT_UP_SW + 2, RBT_UP_THREADS = 256 };
 struct RbtUpLds { float src[RBT_UP_SH * RBT_UP_STRIDE]; float tmp[RBT_UP_TH * RBT_UP_STRIDE]; };   // the staged samples as float; the vertical pass's output
 struct alignas(16) RbtU16x8 { uint32_t w[4]; };                                                    // eight samples, two per word (the lower-addressed one in the low half): one 16-byte access, built in registers
-
-// one cloud of the colour metric: acc holds 4 words per hash slot (sums of R, G, B and the number of points of the voxel), col the merged colour (R | G << 8 | B << 16)
-struct RbtColSet { const int16_t* xyz; const uint8_t* rgb; int32_t n, lg; uint32_t* vol; uint32_t* keys; uint32_t* acc; uint32_t* col; };
 
 // ---- attribute transfer after geometry smoothing (rbt_transfer_colors; the definition is in include/rbt.h) ----
 // Source S = the cloud before smoothing, target T = the cloud after it; both have a 1024^3-bit volume (csrc/rbt_pcc.h). S also has a hash map voxel -> (first, count)
@@ -70,11 +68,6 @@ void launch_transfer(const RbtTransfer* T);
 // yuv420: n_frames planar 4:2:0 pictures; yuv444: n_frames x 3 planes of w * h. filter: RBT_UPSAMPLE_F0 or RBT_UPSAMPLE_REPLICATE
 void launch_up444(const uint16_t* yuv420, int w, int h, int bit_depth, int n_frames, int filter, uint16_t* yuv444);
 void launch_yuv16_rgb8(const uint16_t* yuv, int n, uint8_t* rgb);
-// vol, keys, acc zeroed beforehand; *n_unique (zeroed) counts the voxels, i.e. the merged points
-void launch_col_insert(const RbtColSet* S, uint32_t* n_unique);
-void launch_col_merge(const RbtColSet* S);
-// sse[3] (zeroed): sums of the squared error terms of P's merged points against Q
-void launch_col_dist(const RbtColSet* P, const RbtColSet* Q, unsigned long long* sse);
 }  // namespace rbtk
 
 // ------------------------------------------------------------------------------------------------ bodies (device and host emulation)
@@ -222,44 +215,6 @@ RBT_DEV uint32_t cl_slot_claim(uint32_t* keys, int lg, uint32_t id, int* fresh) 
 RBT_DEV uint32_t cl_slot_find(const uint32_t* keys, int lg, uint32_t id) {     // the voxel is known to be in the map (its bit is set in the volume)
   const uint32_t mask = (1u << lg) - 1;
   for (uint32_t s = pc_hash_slot(id, lg);; s = (s + 1) & mask) if (keys[s] == id + 1 || keys[s] == 0) return s;
-}
-// point i: its voxel's bit, slot, colour sums and count; returns 1 for the first point of a voxel
-RBT_DEV int cl_insert(const RbtColSet* S, int i) {
-  const int x = S->xyz[3 * i], y = S->xyz[3 * i + 1], z = S->xyz[3 * i + 2];
-  int fresh; const uint32_t s = cl_slot_claim(S->keys, S->lg, pc_voxel_id(x, y, z), &fresh);
-#ifdef RBT_HOSTEMU
-  S->vol[pc_voxel_word(x, y, z)] |= 1u << (x & 31);
-  for (int c = 0; c < 3; c++) S->acc[4 * s + c] += S->rgb[3 * i + c];
-  S->acc[4 * s + 3]++;
-#else
-  atomicOr(&S->vol[pc_voxel_word(x, y, z)], 1u << (x & 31));
-  for (int c = 0; c < 3; c++) atomicAdd(&S->acc[4 * s + c], (uint32_t)S->rgb[3 * i + c]);
-  atomicAdd(&S->acc[4 * s + 3], 1u);
-#endif
-  return fresh;
-}
-// removeDuplicate (PCCPointSet.cpp:190-203): the colour of a voxel is sum / count per channel, in integer division
-RBT_DEV void cl_merge(const RbtColSet* S, uint32_t s) {
-  if (!S->keys[s]) return;
-  const uint32_t n = S->acc[4 * s + 3];
-  S->col[s] = (S->acc[4 * s] / n) | (S->acc[4 * s + 1] / n) << 8 | (S->acc[4 * s + 2] / n) << 16;
-}
-// the merged point in slot s of P against Q: e[0..2] = error terms of Y, U, V; returns 0 for an empty slot.
-// Q's colour is the mean over ALL its merged points at exactly the nearest squared distance, rounded half up ((2 sum + n) / (2 n), PCCMetrics.cpp:140-154);
-// the terms are the BT.709 rows of convertRGBtoYUVBT709 (:50-55) times 10000 applied to the RGB difference (the + 0.5 offsets cancel)
-RBT_DEV int cl_error(const RbtColSet* P, const RbtColSet* Q, uint32_t s, long long e[3]) {
-  if (!P->keys[s]) return 0;
-  const uint32_t id = P->keys[s] - 1;
-  const int x = (int)(id & (RBT_PCC_DIM - 1)), y = (int)((id >> RBT_PCC_BITS) & (RBT_PCC_DIM - 1)), z = (int)(id >> (2 * RBT_PCC_BITS));
-  const uint32_t d2 = pc_nearest_d2(Q->vol, x, y, z);
-  uint32_t sr = 0, sg = 0, sb = 0, n = 0;
-  pc_for_ties(Q->vol, x, y, z, d2, [&](uint32_t qid) { const uint32_t c = Q->col[cl_slot_find(Q->keys, Q->lg, qid)]; sr += c & 255u; sg += (c >> 8) & 255u; sb += c >> 16; n++; });
-  const uint32_t pc = P->col[s];
-  const int dr = (int)(pc & 255u) - (int)((2 * sr + n) / (2 * n)), dg = (int)((pc >> 8) & 255u) - (int)((2 * sg + n) / (2 * n)), db = (int)(pc >> 16) - (int)((2 * sb + n) / (2 * n));
-  e[0] = 2126 * dr + 7152 * dg + 722 * db;
-  e[1] = -1146 * dr - 3854 * dg + 5000 * db;
-  e[2] = 5000 * dr - 4542 * dg - 458 * db;
-  return 1;
 }
 
 // ---- attribute transfer ----
@@ -468,11 +423,6 @@ inline void launch_up444(const uint16_t* yuv420, int w, int h, int bit_depth, in
   }
 }
 inline void launch_yuv16_rgb8(const uint16_t* yuv, int n, uint8_t* rgb) { for (int i = 0; i < n; i++) cl_yuv16_to_rgb8(yuv + 3 * (size_t)i, rgb + 3 * (size_t)i); }
-inline void launch_col_insert(const RbtColSet* S, uint32_t* n_unique) { for (int i = 0; i < S->n; i++) *n_unique += (uint32_t)cl_insert(S, i); }
-inline void launch_col_merge(const RbtColSet* S) { for (uint32_t s = 0; s < (1u << S->lg); s++) cl_merge(S, s); }
-inline void launch_col_dist(const RbtColSet* P, const RbtColSet* Q, unsigned long long* sse) {
-  for (uint32_t s = 0; s < (1u << P->lg); s++) { long long e[3]; if (cl_error(P, Q, s, e)) for (int c = 0; c < 3; c++) sse[c] += (unsigned long long)(e[c] * e[c]); }
-}
 inline void launch_tc_copy(uint16_t* dst, const uint16_t* src, size_t n) { memcpy(dst, src, 2 * n); }
 inline void launch_tc_flag(const RbtSmooth* G, const int16_t* xyz_before, const uint32_t* meta, uint8_t* moved) { for (int i = 0; i < G->n_points; i++) moved[i] = (uint8_t)tc_flag(G, xyz_before, meta, i); }
 inline void launch_transfer(const RbtTransfer* T) {

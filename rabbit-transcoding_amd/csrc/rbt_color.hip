@@ -31,28 +31,6 @@ __device__ __forceinline__ unsigned long long col_block_sum(unsigned long long v
   __syncthreads();
   return part[0] + part[1] + part[2] + part[3];
 }
-__global__ void __launch_bounds__(256) k_col_insert(RbtColSet S, uint32_t* n_unique) {
-  __shared__ unsigned long long part[4];
-  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-  const unsigned long long fresh = i < S.n ? (unsigned long long)cl_insert(&S, i) : 0;
-  const unsigned long long n = col_block_sum(fresh, part);
-  if (threadIdx.x == 0 && n) atomicAdd(n_unique, (uint32_t)n);
-}
-__global__ void __launch_bounds__(256) k_col_merge(RbtColSet S) {
-  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-  if (s < (1u << S.lg)) cl_merge(&S, s);
-}
-// one lane per slot of P's map; per workgroup the three sums are reduced on chip, then one 64-bit integer atomic per workgroup and channel
-__global__ void __launch_bounds__(256) k_col_dist(RbtColSet P, RbtColSet Q, unsigned long long* sse) {
-  __shared__ unsigned long long part[3][4];
-  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-  long long e[3] = {0, 0, 0};
-  if (s < (1u << P.lg)) cl_error(&P, &Q, s, e);
-  for (int c = 0; c < 3; c++) {
-    const unsigned long long t = col_block_sum((unsigned long long)(e[c] * e[c]), part[c]);
-    if (threadIdx.x == 0 && t) atomicAdd(&sse[c], t);
-  }
-}
 
 // ---- attribute transfer (rbt_color.h): one lane per source point / hash slot / target point / moved point / entry; no LDS ----
 __global__ void __launch_bounds__(256) k_tc_copy(uint16_t* dst, const uint16_t* src, size_t n) { const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i < n) dst[i] = src[i]; }
@@ -165,11 +143,6 @@ void launch_up444(const uint16_t* yuv420, int w, int h, int bit_depth, int n_fra
                           yuv420, yuv444, w, h, bit_depth);
 }
 void launch_yuv16_rgb8(const uint16_t* yuv, int n, uint8_t* rgb) { if (n > 0) hipLaunchKernelGGL(k_yuv16_rgb8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, yuv, n, rgb); }
-void launch_col_insert(const RbtColSet* S, uint32_t* n_unique) { if (S->n > 0) hipLaunchKernelGGL(k_col_insert, dim3((unsigned)((S->n + 255) / 256)), dim3(256), 0, g_stream, *S, n_unique); }
-void launch_col_merge(const RbtColSet* S) { hipLaunchKernelGGL(k_col_merge, dim3((unsigned)(((1u << S->lg) + 255) / 256)), dim3(256), 0, g_stream, *S); }
-void launch_col_dist(const RbtColSet* P, const RbtColSet* Q, unsigned long long* sse) {
-  hipLaunchKernelGGL(k_col_dist, dim3((unsigned)(((1u << P->lg) + 255) / 256)), dim3(256), 0, g_stream, *P, *Q, sse);
-}
 void launch_tc_copy(uint16_t* dst, const uint16_t* src, size_t n) { if (n) hipLaunchKernelGGL(k_tc_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, dst, src, n); }
 void launch_tc_flag(const RbtSmooth* G, const int16_t* xyz_before, const uint32_t* meta, uint8_t* moved) {
   if (G->n_points > 0) hipLaunchKernelGGL(k_tc_flag, dim3((unsigned)((G->n_points + 255) / 256)), dim3(256), 0, g_stream, *G, xyz_before, meta, moved);

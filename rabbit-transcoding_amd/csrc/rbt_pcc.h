@@ -121,6 +121,7 @@ RBT_DEV uint32_t pc_nearest_d2(const uint32_t* vol, int x, int y, int z) {
 // Duplicates are merged as for D1; a merged point is stood for by its lowest original index (hash map voxel -> index), its normal is that point's. "The points at the same
 // distance" are all points at exactly the nearest squared distance: the shell of voxels at that distance is walked in the other cloud's bit volume. Normals are Q14 integers;
 // the reconstruction's normals are kept as integer sum and count (scaleNormals' mean is formed where it is used), so the only floating point is the final per-point value.
+// Here: the voxel ids, the map and the tie walk; the walks that use them are in csrc/rbt_score.h (sc_walk_ab, sc_walk_ba, sc_d2_ab).
 RBT_DEV uint32_t pc_voxel_id(int x, int y, int z) { return ((uint32_t)z << (2 * RBT_PCC_BITS)) | ((uint32_t)y << RBT_PCC_BITS) | (uint32_t)x; }
 RBT_DEV uint32_t pc_hash_slot(uint32_t id, int lg) { return (id * 2654435761u) >> (32 - lg); }
 // voxel -> lowest point index; keys: voxel id + 1 (0 = empty), vals start at 0xFFFFFFFF
@@ -155,6 +156,11 @@ template <class F> RBT_DEV void pc_for_ties(const uint32_t* vol, int x, int y, i
     }
   }
 }
+#ifdef RBT_HOSTEMU
+// Serial reference of D2, in the host emulation only (the GPU build does not see it): per point, with a search of its own (pc_nearest_d2) and one walk per step, where
+// the score (csrc/rbt_score.h) searches once and shares its walks. tests/metric_fold_check.cpp holds rbt_d2 against it.
+// one cloud: points, bit volume of its voxels, hash map voxel -> lowest point index (keys: voxel id + 1, 0 = empty)
+struct RbtD2Set { const int16_t* xyz; int n; const uint32_t* vol; const uint32_t* keys; const uint32_t* vals; int lg; };
 RBT_DEV int pc_d2_is_rep(const RbtD2Set* s, int i) { return pc_hash_find(s->keys, s->vals, s->lg, pc_voxel_id(s->xyz[3 * i], s->xyz[3 * i + 1], s->xyz[3 * i + 2])) == (uint32_t)i; }
 // scaleNormals, first half: source point i (a representative) gives its normal to the points of B nearest to it
 RBT_DEV void pc_d2_give(const RbtD2Set* A, const int16_t* normals_a, const RbtD2Set* B, long long* acc_b, int32_t* cnt_b, int i) {
@@ -163,13 +169,8 @@ RBT_DEV void pc_d2_give(const RbtD2Set* A, const int16_t* normals_a, const RbtD2
   const uint32_t d2 = pc_nearest_d2(B->vol, x, y, z);
   pc_for_ties(B->vol, x, y, z, d2, [&](uint32_t id) {
     const uint32_t j = pc_hash_find(B->keys, B->vals, B->lg, id);
-#ifdef RBT_HOSTEMU
     for (int c = 0; c < 3; c++) acc_b[3 * j + c] += normals_a[3 * i + c];
     cnt_b[j]++;
-#else
-    for (int c = 0; c < 3; c++) atomicAdd((unsigned long long*)&acc_b[3 * j + c], (unsigned long long)(long long)normals_a[3 * i + c]);
-    atomicAdd(&cnt_b[j], 1);
-#endif
   });
 }
 // second half: a point of B that got no normal takes the mean of the source points nearest to it (sum and count)
@@ -199,6 +200,7 @@ RBT_DEV double pc_d2_value(const RbtD2Set* P, const RbtD2Set* Q, const long long
   });
   return sum / n / (16384.0 * 16384.0);
 }
+#endif
 
 // ---- geometry smoothing (rbt_atlas_params.geometry_smoothing): PCCCodec::identifyBoundaryPoints (PCCCodec.cpp:266-325) and smoothPointCloudPostprocess with gridSmoothing
 // (:52-145, addGridCentroid :980-998, gridFiltering :1000-1063, smoothPointCloudGrid :1065-1104) ----

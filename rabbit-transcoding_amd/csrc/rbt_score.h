@@ -1,5 +1,5 @@
 // Frame scoring on clouds that stay on the device (rbt_pcloud_*, rbt_score; the definitions are in include/rbt.h): D1, D2 and the colour PSNR from ONE index per cloud
-// and ONE nearest-distance search per direction, where rbt_d1 + rbt_d2 + rbt_color_metric build six indices and search seven to eight times.
+// and ONE nearest-distance search per direction. The host-array calls rbt_d1, rbt_d2 and rbt_color_metric are this path on two temporary clouds (host/rbt_pcc.cpp).
 //   index    built once per cloud: the 1024^3-bit volume (csrc/rbt_pcc.h), a coarse level over it (one bit per 8 x 8 x 8 block, 256 KB), one hash map voxel -> slot whose
 //            slot holds the lowest point index of the voxel (the representative of the merged point, as in D2) and the colour sums and count (as in the colour metric).
 //            Only the first point of a voxel touches the volume and the coarse level. Coordinates are checked by a kernel of their own first (error word), so a
@@ -84,7 +84,7 @@ RBT_DEV int sc_insert(const RbtScoreCloud* S, int i) {
 #endif
   return fresh;
 }
-RBT_DEV void sc_merge(const RbtScoreCloud* S, uint32_t s) {             // removeDuplicate (PCCPointSet.cpp:190-203), as cl_merge
+RBT_DEV void sc_merge(const RbtScoreCloud* S, uint32_t s) {             // removeDuplicate (PCCPointSet.cpp:190-203): the colour of a voxel is sum / count per channel, in integer division
   if (!S->keys[s]) return;
   const uint32_t n = S->acc[4 * s + 3];
   S->col[s] = (S->acc[4 * s] / n) | (S->acc[4 * s + 1] / n) << 8 | (S->acc[4 * s + 2] / n) << 16;
@@ -182,14 +182,16 @@ RBT_DEV void sc_search(const RbtScoreCloud* P, const RbtScoreCloud* Q, uint32_t*
   const uint32_t s = cl_slot_find(P->keys, P->lg, pc_voxel_id(p[0], p[1], p[2]));
   dist[i] = P->vals[s] == (uint32_t)i ? sc_nearest(Q, p[0], p[1], p[2]) : RBT_SC_NONE;
 }
-// the colour error terms of a merged point of colour pc against the tie sums (cl_error)
+// the colour error terms e[0..2] (Y, U, V) of a merged point of colour pc against the tie sums: the other cloud's colour is the mean over ALL its merged points at exactly
+// the nearest squared distance, rounded half up ((2 sum + n) / (2 n), PCCMetrics.cpp:140-154); the terms are the BT.709 rows of convertRGBtoYUVBT709 (:50-55) times 10000
+// applied to the RGB difference (the + 0.5 offsets cancel)
 RBT_DEV void sc_color_error(uint32_t pc, uint32_t sr, uint32_t sg, uint32_t sb, uint32_t n, long long e[3]) {
   const int dr = (int)(pc & 255u) - (int)((2 * sr + n) / (2 * n)), dg = (int)((pc >> 8) & 255u) - (int)((2 * sg + n) / (2 * n)), db = (int)(pc >> 16) - (int)((2 * sb + n) / (2 * n));
   e[0] = 2126 * dr + 7152 * dg + 722 * db;
   e[1] = -1146 * dr - 3854 * dg + 5000 * db;
   e[2] = 5000 * dr - 4542 * dg - 458 * db;
 }
-// walk A -> B for point i of A: normals to B's tie points (pc_d2_give), the D1 term *d, the colour error e. Returns 0 for a point that is no representative.
+// walk A -> B for point i of A: its normal to B's tie points (scaleNormals, first half: PCCPointSet.cpp:2322-2380), the D1 term *d, the colour error e. Returns 0 for a point that is no representative.
 RBT_DEV int sc_walk_ab(const RbtScoreCloud* A, const RbtScoreCloud* B, const RbtScoreWork* W, int parts, int i, uint32_t* d, long long e[3]) {
   const uint32_t d2 = W->dist_a[i]; if (d2 == RBT_SC_NONE) return 0;
   const int16_t* p = A->xyz + 3 * (size_t)i; const int x = p[0], y = p[1], z = p[2];
@@ -213,8 +215,9 @@ RBT_DEV int sc_walk_ab(const RbtScoreCloud* A, const RbtScoreCloud* B, const Rbt
   if (parts & RBT_SCORE_COLOR) sc_color_error(A->col[cl_slot_find(A->keys, A->lg, pc_voxel_id(x, y, z))], sr, sg, sb, n, e);
   return 1;
 }
-// walk B -> A for point j of B: the D1 term, the colour error, the D2 value against A's own normals (pc_d2_value with a count of 1), and the "take" step of
-// scaleNormals for a point that got no normal from the walk A -> B (pc_d2_take)
+// walk B -> A for point j of B: the D1 term, the colour error, the D2 value against A's own normals (computeC2p_, PCCMetrics.cpp:100-124: the mean over A's points at the
+// nearest distance of ((p - q) . normal(q))^2, Q14 normals), and the "take" step of scaleNormals for a point that got no normal from the walk A -> B: the sum and
+// count of the normals of the source points nearest to it
 RBT_DEV int sc_walk_ba(const RbtScoreCloud* B, const RbtScoreCloud* A, const RbtScoreWork* W, int parts, int j, uint32_t* d, long long e[3]) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -249,7 +252,7 @@ RBT_DEV int sc_color_walk(const RbtScoreCloud* A, const RbtScoreCloud* B, const 
   uint32_t d = 0;
   return dir ? sc_walk_ba(B, A, &W, RBT_SCORE_COLOR, i, &d, e) : sc_walk_ab(A, B, &W, RBT_SCORE_COLOR, i, &d, e);
 }
-// third walk, point i of A: the D2 value against B's normals acc_b / cnt_b, complete now (pc_d2_value)
+// third walk, point i of A: the D2 value against B's normals acc_b / cnt_b, complete now (the same mean, each normal sum / count)
 RBT_DEV void sc_d2_ab(const RbtScoreCloud* A, const RbtScoreCloud* B, const RbtScoreWork* W, int i) {
 #if defined(__clang__)
 #pragma clang fp contract(off)

@@ -35,7 +35,7 @@ int block_xy(const rbt_patch& p, int ub, int vb, int* x, int* y) {       // PCCP
   return 0;
 }
 // device timers of the colour stages (rbt_color_stage_ms), behind the transcoder's (rbt_batch.h)
-enum { T_COL_UP = T_COUNT, T_COL_RGB, T_COL_METRIC, T_COL_DIST, T_COL_TRANSFER, T_COL_TRANSFER_COPY };    // the metric in two parts: insert + merge, distance (a read-back of the merged counts lies between them)
+enum { T_COL_UP = T_COUNT, T_COL_RGB, T_COL_DIST, T_COL_TRANSFER, T_COL_TRANSFER_COPY };    // T_COL_DIST: search, walks and sums of a score (rbt_frame_score.device_ms)
 static_assert(T_COL_TRANSFER_COPY < 16, "timer slots");
 int lg_of(int n) { int lg = 4; while (((size_t)1 << lg) < 2 * (size_t)n) lg++; return lg; }
 // the derived fields of the three results from the sums and counts (shared by the host-array calls and rbt_score)
@@ -279,104 +279,6 @@ int pcc_yuv16_to_rgb8(std::string& err, const uint16_t* yuv, int n, uint8_t* rgb
   rbtk::timer_begin(T_COL_RGB); rbtk::launch_yuv16_rgb8(b_in.as<uint16_t>(), n, b_out.as<uint8_t>()); rbtk::timer_end(T_COL_RGB);
   if (rbtk::d2h(rgb, b_out.p, 3 * (size_t)n) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
   if (ms) *ms = rbtk::timer_ms(T_COL_RGB);
-  return RBT_OK;
-}
-
-// QualityMetrics::compute with computeColor_ (PCCMetrics.cpp:127-179, :221-225) both ways (:321-325) on merged clouds: csrc/rbt_color.h
-int pcc_color_metric(std::string& err, const int16_t* a, const uint8_t* rgb_a, int na, const int16_t* b, const uint8_t* rgb_b, int nb, rbt_color_result* out, double* ms) {
-  memset(out, 0, sizeof(*out));
-  if (na <= 0 || nb <= 0 || !rgb_a || !rgb_b) { err = "empty point cloud or no colours"; return RBT_ERR_PARAM; }
-  for (int i = 0; i < 3 * na; i++) if (a[i] < 0 || a[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
-  for (int i = 0; i < 3 * nb; i++) if (b[i] < 0 || b[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
-  const size_t vol_bytes = (size_t)1 << (3 * RBT_PCC_BITS - 3);
-  auto lg_of = [](int n) { int lg = 4; while (((size_t)1 << lg) < 2 * (size_t)n) lg++; return lg; };
-  const int lga = lg_of(na), lgb = lg_of(nb);
-  DevBuf va, vb, pa, pb, ca, cb, ka, kb, aa, ab, ma, mb, res;
-  if (!va.alloc(vol_bytes) || !vb.alloc(vol_bytes) || !pa.alloc(6 * (size_t)na) || !pb.alloc(6 * (size_t)nb) || !ca.alloc(3 * (size_t)na) || !cb.alloc(3 * (size_t)nb) ||
-      !ka.alloc((size_t)4 << lga) || !kb.alloc((size_t)4 << lgb) || !aa.alloc((size_t)16 << lga) || !ab.alloc((size_t)16 << lgb) || !ma.alloc((size_t)4 << lga) || !mb.alloc((size_t)4 << lgb) ||
-      !res.alloc(64)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
-  int bad = rbtk::dev_memset(va.p, 0, vol_bytes) | rbtk::dev_memset(vb.p, 0, vol_bytes) | rbtk::dev_memset(ka.p, 0, (size_t)4 << lga) | rbtk::dev_memset(kb.p, 0, (size_t)4 << lgb) |
-            rbtk::dev_memset(aa.p, 0, (size_t)16 << lga) | rbtk::dev_memset(ab.p, 0, (size_t)16 << lgb) | rbtk::dev_memset(ma.p, 0, (size_t)4 << lga) | rbtk::dev_memset(mb.p, 0, (size_t)4 << lgb) |
-            rbtk::dev_memset(res.p, 0, 64) | rbtk::h2d(pa.p, a, 6 * (size_t)na) | rbtk::h2d(pb.p, b, 6 * (size_t)nb) | rbtk::h2d(ca.p, rgb_a, 3 * (size_t)na) | rbtk::h2d(cb.p, rgb_b, 3 * (size_t)nb);
-  if (bad) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
-  RbtColSet A{pa.as<int16_t>(), ca.as<uint8_t>(), na, lga, va.as<uint32_t>(), ka.as<uint32_t>(), aa.as<uint32_t>(), ma.as<uint32_t>()};
-  RbtColSet B{pb.as<int16_t>(), cb.as<uint8_t>(), nb, lgb, vb.as<uint32_t>(), kb.as<uint32_t>(), ab.as<uint32_t>(), mb.as<uint32_t>()};
-  // res: u64 [0..2] sse_ab, [3..5] sse_ba; u32 [12] merged points of a, [13] of b
-  unsigned long long* r64 = res.as<unsigned long long>(); uint32_t* r32 = res.as<uint32_t>();
-  rbtk::timer_begin(T_COL_METRIC);
-  rbtk::launch_col_insert(&A, r32 + 12); rbtk::launch_col_insert(&B, r32 + 13);
-  rbtk::launch_col_merge(&A); rbtk::launch_col_merge(&B);
-  rbtk::timer_end(T_COL_METRIC);
-  if (ms) *ms = 0;
-  uint32_t cnt[2];
-  if (rbtk::d2h(cnt, r32 + 12, 8)) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-  // |error term| <= 2.55e6: the sum of 2^21 squares still fits 64 bits
-  if (cnt[0] > (1u << 21) || cnt[1] > (1u << 21)) { rbtk::dev_sync(); err = "more than 2^21 merged points"; return RBT_ERR_PARAM; }
-  rbtk::timer_begin(T_COL_DIST);
-  rbtk::launch_col_dist(&A, &B, r64); rbtk::launch_col_dist(&B, &A, r64 + 3);
-  rbtk::timer_end(T_COL_DIST);
-  uint64_t h[8];
-  if (rbtk::d2h(h, res.p, 64) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-  if (ms) *ms = rbtk::timer_ms(T_COL_METRIC) + rbtk::timer_ms(T_COL_DIST);      // kernels only: the read-back between the two parts is not in it
-  out->n_a = (int)cnt[0]; out->n_b = (int)cnt[1];
-  for (int c = 0; c < 3; c++) { out->sse_ab[c] = h[c]; out->sse_ba[c] = h[3 + c]; }
-  finish_color(out);
-  return RBT_OK;
-}
-
-int pcc_d1(std::string& err, const int16_t* a, int na, const int16_t* b, int nb, int peak, rbt_d1_result* out) {
-  memset(out, 0, sizeof(*out));
-  if (na <= 0 || nb <= 0 || peak <= 0) { err = "empty point cloud"; return RBT_ERR_PARAM; }
-  for (int i = 0; i < 3 * na; i++) if (a[i] < 0 || a[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
-  for (int i = 0; i < 3 * nb; i++) if (b[i] < 0 || b[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
-  const size_t vol_bytes = (size_t)1 << (3 * RBT_PCC_BITS - 3);
-  DevBuf va, vb, pa, pb, fa, fb, acc;
-  if (!va.alloc(vol_bytes) || !vb.alloc(vol_bytes) || !pa.alloc(6 * (size_t)na) || !pb.alloc(6 * (size_t)nb) || !fa.alloc((size_t)na) || !fb.alloc((size_t)nb) || !acc.alloc(64)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
-  int bad = rbtk::dev_memset(va.p, 0, vol_bytes) | rbtk::dev_memset(vb.p, 0, vol_bytes) | rbtk::dev_memset(acc.p, 0, 64) | rbtk::h2d(pa.p, a, 6 * (size_t)na) | rbtk::h2d(pb.p, b, 6 * (size_t)nb);
-  if (bad) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
-  // acc: [0] sse_ab (u64), [1] sse_ba (u64), then u32: [4] unique a, [5] unique b, [6] max ab, [7] max ba
-  unsigned long long* a64 = acc.as<unsigned long long>(); uint32_t* a32 = acc.as<uint32_t>();
-  rbtk::launch_vol_set(pa.as<int16_t>(), na, va.as<uint32_t>(), fa.as<uint8_t>(), a32 + 4);
-  rbtk::launch_vol_set(pb.as<int16_t>(), nb, vb.as<uint32_t>(), fb.as<uint8_t>(), a32 + 5);
-  rbtk::launch_vol_nn(pa.as<int16_t>(), fa.as<uint8_t>(), na, vb.as<uint32_t>(), a64, a32 + 6);
-  rbtk::launch_vol_nn(pb.as<int16_t>(), fb.as<uint8_t>(), nb, va.as<uint32_t>(), a64 + 1, a32 + 7);
-  uint64_t h[8];
-  if (rbtk::d2h(h, acc.p, 64) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-  const uint32_t* h32 = (const uint32_t*)h;
-  out->sse_ab = h[0]; out->sse_ba = h[1]; out->n_a = (int)h32[4]; out->n_b = (int)h32[5]; out->max_ab = h32[6]; out->max_ba = h32[7];
-  finish_geometry(out, peak);
-  return RBT_OK;
-}
-
-// QualityMetrics::compute with computeC2p_ (PCCMetrics.cpp:100-124, :213-215) both ways (:299-309), normals as PCCMetrics::compute arranges them (:371-376): csrc/rbt_pcc.h
-int pcc_d2(std::string& err, const int16_t* a, const int16_t* normals_a, int na, const int16_t* b, int nb, int peak, rbt_d2_result* out) {
-  memset(out, 0, sizeof(*out));
-  if (na <= 0 || nb <= 0 || peak <= 0 || !normals_a) { err = "empty point cloud or no normals"; return RBT_ERR_PARAM; }
-  for (int i = 0; i < 3 * na; i++) if (a[i] < 0 || a[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
-  for (int i = 0; i < 3 * nb; i++) if (b[i] < 0 || b[i] >= RBT_PCC_DIM) { err = "coordinate outside 0..1023"; return RBT_ERR_PARAM; }
-  const size_t vol_bytes = (size_t)1 << (3 * RBT_PCC_BITS - 3);
-  auto lg_of = [](int n) { int lg = 4; while (((size_t)1 << lg) < 2 * (size_t)n) lg++; return lg; };
-  const int lga = lg_of(na), lgb = lg_of(nb);
-  DevBuf va, vb, pa, pb, na_, ka, kb, wa, wb, accb, cntb, res;
-  if (!va.alloc(vol_bytes) || !vb.alloc(vol_bytes) || !pa.alloc(6 * (size_t)na) || !pb.alloc(6 * (size_t)nb) || !na_.alloc(6 * (size_t)na) || !ka.alloc((size_t)4 << lga) || !wa.alloc((size_t)4 << lga) ||
-      !kb.alloc((size_t)4 << lgb) || !wb.alloc((size_t)4 << lgb) || !accb.alloc(24 * (size_t)nb) || !cntb.alloc(4 * (size_t)nb) || !res.alloc(64)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
-  int bad = rbtk::dev_memset(va.p, 0, vol_bytes) | rbtk::dev_memset(vb.p, 0, vol_bytes) | rbtk::dev_memset(ka.p, 0, (size_t)4 << lga) | rbtk::dev_memset(kb.p, 0, (size_t)4 << lgb) |
-            rbtk::dev_memset(wa.p, 0xFF, (size_t)4 << lga) | rbtk::dev_memset(wb.p, 0xFF, (size_t)4 << lgb) | rbtk::dev_memset(accb.p, 0, 24 * (size_t)nb) | rbtk::dev_memset(cntb.p, 0, 4 * (size_t)nb) |
-            rbtk::dev_memset(res.p, 0, 64) | rbtk::h2d(pa.p, a, 6 * (size_t)na) | rbtk::h2d(pb.p, b, 6 * (size_t)nb) | rbtk::h2d(na_.p, normals_a, 6 * (size_t)na);
-  if (bad) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
-  rbtk::launch_d2_insert(pa.as<int16_t>(), na, va.as<uint32_t>(), ka.as<uint32_t>(), wa.as<uint32_t>(), lga);
-  rbtk::launch_d2_insert(pb.as<int16_t>(), nb, vb.as<uint32_t>(), kb.as<uint32_t>(), wb.as<uint32_t>(), lgb);
-  RbtD2Set A{pa.as<int16_t>(), na, va.as<uint32_t>(), ka.as<uint32_t>(), wa.as<uint32_t>(), lga}, B{pb.as<int16_t>(), nb, vb.as<uint32_t>(), kb.as<uint32_t>(), wb.as<uint32_t>(), lgb};
-  rbtk::launch_d2_give(&A, na_.as<int16_t>(), &B, accb.as<long long>(), cntb.as<int32_t>());
-  rbtk::launch_d2_take(&B, &A, na_.as<int16_t>(), accb.as<long long>(), cntb.as<int32_t>());
-  double* r = res.as<double>();
-  rbtk::launch_d2_dist(&A, &B, accb.as<long long>(), cntb.as<int32_t>(), nullptr, r);
-  rbtk::launch_d2_dist(&B, &A, nullptr, nullptr, na_.as<int16_t>(), r + 4);
-  double h[8];
-  if (rbtk::d2h(h, res.p, 64) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
-  uint64_t cnt_a, cnt_b; memcpy(&cnt_a, &h[2], 8); memcpy(&cnt_b, &h[6], 8);
-  out->n_a = (int)cnt_a; out->n_b = (int)cnt_b; out->sse_ab = h[0]; out->max_ab = h[1]; out->sse_ba = h[4]; out->max_ba = h[5];
-  finish_geometry(out, peak);
   return RBT_OK;
 }
 
@@ -818,7 +720,7 @@ int pcloud_score(std::string& err, const PCloud* a, const PCloud* b, int peak, i
   W.dist_a = dist.as<uint32_t>(); W.dist_b = W.dist_a + na; W.res = res.as<unsigned long long>();
   if (d2) { W.acc_b = nrm_b.as<long long>(); W.cnt_b = (int32_t*)(W.acc_b + 3 * nb); W.val_ab = val.as<double>(); W.val_ba = W.val_ab + na; W.part = part.as<double>(); }
   const RbtScoreCloud A = a->view(), B = b->view();
-  rbtk::timer_begin(T_COL_DIST);             // the colour metric's distance timer: every call reads its timers before it returns
+  rbtk::timer_begin(T_COL_DIST);             // one timer for every score: each call reads its timers before it returns
   rbtk::launch_sc_score(&A, &B, parts, &W);
   rbtk::timer_end(T_COL_DIST);
   uint64_t h[RBT_SC_RESULTS];
@@ -839,5 +741,46 @@ int pcloud_score(std::string& err, const PCloud* a, const PCloud* b, int peak, i
     finish_color(&out->color);
   }
   return RBT_OK;
+}
+
+// ---- the host-array metrics (rbt_d1, rbt_d2, rbt_color_metric): upload + score + release of two temporary clouds ----
+// The callers have refused empty input, a bad peak and missing colours or normals in their own words; what can still be refused here is a coordinate outside the volume
+// or more than 2^26 points (pcloud_index; A before B) and, for the colour part, more than 2^21 merged points. The cache is the call's own and is trimmed when the call
+// ends: the volumes go back to the device pool, and the context's cloud cache never sees them.
+static int score_host_clouds(std::string& err, const int16_t* a, const uint8_t* rgb_a, const int16_t* normals_a, int na, const int16_t* b, const uint8_t* rgb_b, int nb, int peak, int parts, rbt_frame_score* out) {
+  struct Guard { PCloudCache cache; PCloud* a = nullptr; PCloud* b = nullptr; ~Guard() { pcloud_release(cache, a); pcloud_release(cache, b); pcloud_cache_trim(cache); } } g;
+  if (int rc = pcloud_upload(err, g.cache, a, rgb_a, normals_a, na, &g.a)) return rc;
+  if (int rc = pcloud_upload(err, g.cache, b, rgb_b, nullptr, nb, &g.b)) return rc;
+  // |colour error term| <= 2.55e6: the sum of 2^21 squares still fits 64 bits
+  if ((parts & RBT_SCORE_COLOR) && (pcloud_merged(g.a) > (1 << 21) || pcloud_merged(g.b) > (1 << 21))) { err = "more than 2^21 merged points"; return RBT_ERR_PARAM; }
+  return pcloud_score(err, g.a, g.b, peak, parts, out);
+}
+// QualityMetrics::compute with the point-to-point error (PCCMetrics.cpp:75-231) both ways (:299-309)
+int pcc_d1(std::string& err, const int16_t* a, int na, const int16_t* b, int nb, int peak, rbt_d1_result* out) {
+  memset(out, 0, sizeof(*out));
+  if (na <= 0 || nb <= 0 || peak <= 0) { err = "empty point cloud"; return RBT_ERR_PARAM; }
+  rbt_frame_score s;
+  const int rc = score_host_clouds(err, a, nullptr, nullptr, na, b, nullptr, nb, peak, RBT_SCORE_D1, &s);
+  if (!rc) *out = s.d1;
+  return rc;
+}
+// QualityMetrics::compute with computeC2p_ (PCCMetrics.cpp:100-124, :213-215) both ways (:299-309), normals as PCCMetrics::compute arranges them (:371-376)
+int pcc_d2(std::string& err, const int16_t* a, const int16_t* normals_a, int na, const int16_t* b, int nb, int peak, rbt_d2_result* out) {
+  memset(out, 0, sizeof(*out));
+  if (na <= 0 || nb <= 0 || peak <= 0 || !normals_a) { err = "empty point cloud or no normals"; return RBT_ERR_PARAM; }
+  rbt_frame_score s;
+  const int rc = score_host_clouds(err, a, nullptr, normals_a, na, b, nullptr, nb, peak, RBT_SCORE_D2, &s);
+  if (!rc) *out = s.d2;
+  return rc;
+}
+// QualityMetrics::compute with computeColor_ (PCCMetrics.cpp:127-179, :221-225) both ways (:321-325) on merged clouds. ms: device time of the score (search, walks, sums)
+int pcc_color_metric(std::string& err, const int16_t* a, const uint8_t* rgb_a, int na, const int16_t* b, const uint8_t* rgb_b, int nb, rbt_color_result* out, double* ms) {
+  memset(out, 0, sizeof(*out));
+  if (ms) *ms = 0;                           // a refused call has run no stage
+  if (na <= 0 || nb <= 0 || !rgb_a || !rgb_b) { err = "empty point cloud or no colours"; return RBT_ERR_PARAM; }
+  rbt_frame_score s;
+  const int rc = score_host_clouds(err, a, rgb_a, nullptr, na, b, rgb_b, nb, RBT_PCC_DIM - 1, RBT_SCORE_COLOR, &s);      // the peak enters the geometry figures only
+  if (!rc) { *out = s.color; if (ms) *ms = s.device_ms; }
+  return rc;
 }
 }  // namespace rbt

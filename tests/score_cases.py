@@ -148,14 +148,14 @@ def check_against_definition(got, ref, peak=1023):
 
 
 def check_against_host_array_calls(ctx, got, case, peak=1023, colour=True):
-    """out->d1 == rbt_d1 and out->color == rbt_color_metric field for field; out->d2: counts and maxima equal rbt_d2's, sums within rel 1e-9"""
+    """out->d1 == rbt_d1, out->color == rbt_color_metric and out->d2 == rbt_d2 field for field: the D2 sums are the same additions in the same order"""
     a, ca, na, b, cb = case
     assert got["d1"] == ctx.d1(a, b, peak)
     if colour: assert got["color"] == ctx.color_metric(a, ca, b, cb)
     old = ctx.d2(a, na, b, peak)
     print("d2 max", got["d2"]["max_ab"], got["d2"]["max_ba"], "rbt_d2", old["max_ab"], old["max_ba"], "sse", got["d2"]["sse_ab"], old["sse_ab"], got["d2"]["sse_ba"], old["sse_ba"])
     for k in ("n_a", "n_b", "max_ab", "max_ba"): assert got["d2"][k] == old[k], (k, got["d2"][k], old[k])
-    for k in ("sse_ab", "sse_ba"): assert got["d2"][k] == pytest.approx(old[k], rel=1e-9), k
+    for k in ("sse_ab", "sse_ba"): assert got["d2"][k] == old[k], (k, got["d2"][k], old[k])
 
 
 def check_swap(ctx, case, got):

@@ -1,4 +1,4 @@
-"""GPU build of the colour stages (csrc/rbt_color.hip: k_up444, k_yuv16_rgb8, k_col_insert / k_col_merge / k_col_dist) through the C ABI: every case of
+"""GPU build of the colour stages (csrc/rbt_color.hip: k_up444, k_yuv16_rgb8, and the k_sc_* kernels behind rbt_color_metric) through the C ABI: every case of
 tests/test_color.py on the device, full-size inputs against the serial host emulation of the same bodies (arrays and integers equal), and point-cloud frame 0 of the
 benchmark fixture after a real R5 -> R3 transcode."""
 import json

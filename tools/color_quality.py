@@ -7,7 +7,7 @@ transcode against the R5 input. Decoded clouds go through the decoder's geometry
 R3 transcode are scored a second time with the attribute transfer the reference decoder runs after its smoothing (rbt_reconstruct_decoded, attr_transfer 1): rows
 "..._transfer_vs_source", with the number of moved and of re-coloured points per frame. Stage times: events around the launches (rbt_color_stage_ms, rbt_transfer_stage),
 median of 5 calls after a warm-up, per point-cloud frame (up-conversion: its two attribute pictures; RGB: its points; metric: source against the R3 cloud, both directions,
-kernels only; transfer: frame 0 of the R3 transcode inside rbt_reconstruct_decoded, kernels only). Prints one JSON line; --out also writes it to a file.
+the score's kernels without the index building; transfer: frame 0 of the R3 transcode inside rbt_reconstruct_decoded, kernels only). Prints one JSON line; --out also writes it to a file.
 
     python tools/color_quality.py --out profiles/color_quality.json
 """
@@ -94,7 +94,7 @@ def main():
             "bytes_occupancy_geometry_attribute": sizes, "colour_psnr": psnr, "attr_transfer_points": counts,
             "stage_ms_per_frame": {k: round(statistics.median(v), 4) for k, v in t.items()}, "stage_ms_samples": {k: [round(x, 4) for x in v] for k, v in t.items()},
             "stage_note": "device time between events around the launches, median of 5 after a warm-up; upconvert: the frame's two 1280x1280 10-bit attribute pictures; rgb: the source "
-                          "cloud's points; metric: source cloud against the R3 cloud, both directions: the insert + merge kernels and the distance kernels, each between its own pair of events (the read-back of the merged counts between the two parts and the volume clears are outside); "
+                          "cloud's points; metric: source cloud against the R3 cloud, both directions: the device_ms of the call's score - the search, the walks and the sums between one pair of events (the uploads, the building of the two indices and the volume clears are outside); "
                           "transfer: the attribute transfer inside rbt_reconstruct_decoded of frame 0 of the R3 transcode: the two copies that keep the unsmoothed cloud (one pair of events) plus the "
                           "per-point flag pass, index building, forward, backward, lists and sums (a second pair); the clears of the two 128 MB volumes and of the maps, the allocations and the "
                           "read-back of the counters are outside"}

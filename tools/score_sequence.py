@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Scores the benchmark GOF's point-cloud frames on the GPU with rbt_pcloud_from_maps + rbt_score (D1, D2, colour PSNR per frame, and the sequence summary of
-rbt_score_summary), and times that route against the host-array route it replaces.
+rbt_score_summary), and times that route against the host-array calls, which are three separate upload-and-score calls on the same index and search.
 
 Frames: 0..3, the GOF's four base atlases (tests/synth.py make_maps(w, h, 1051 + k)). The later frames of the fixture are these atlases rolled by a few pixels, so their
 patches do not lie on the 16-pixel block grid and tests/synth.py has no patch list for them - tools/color_quality.py stops at frame 3 for the same reason. Pairs: the
@@ -8,7 +8,8 @@ decoded R5 input and the R5 -> R3 transcode, each against the source cloud (rbt_
 patch). Decoded clouds go through the decoder's geometry smoothing and attribute transfer (CTC: grid 8, threshold 64, attr_transfer 1).
 
 Timing, per frame of the R3 pair, both routes in this one process, alternating, a warm-up of each and then 5 samples, host clock around calls that end in a synchronise:
-  (a) host arrays: reconstruct_decoded to the host, then d1 + d2 + color_metric (each uploads both clouds, builds its own index, searches on its own)
+  (a) host arrays: reconstruct_decoded to the host, then d1 + d2 + color_metric: three separate upload-and-score calls, each uploading and indexing both clouds,
+      scoring its one part and releasing them (profiles/score_sequence.json was recorded when these calls still had kernels of their own)
   (b) device clouds: pcloud_from_maps + score against the source handle uploaded beforehand + release of the decoded handle
 Also recorded: rbt_frame_score.device_ms of (b) and the colour stage's rbt_color_stage_ms figure of (a) for the same pair. All samples are kept. "faster" holds for a
 frame when median(a) - median(b) exceeds the spread (max - min) of (a)'s samples. Prints the per-frame lines and the summaries, then one JSON line; --out also writes it.
@@ -100,7 +101,7 @@ def main():
             t2 = time.perf_counter()
             hb = ctx.pcloud_from_maps(*a_args, attr_transfer=1); new = ctx.score(handles[k], hb); hb.release()
             t3 = time.perf_counter()
-            assert new["d1"] == old[0] and new["color"] == old[2] and new["d2"]["n_b"] == old[1]["n_b"] and abs(new["d2"]["sse_ab"] - old[1]["sse_ab"]) <= 1e-9 * old[1]["sse_ab"]
+            assert new["d1"] == old[0] and new["color"] == old[2] and new["d2"] == old[1]
             if i:
                 t["host_arrays_ms"].append(1e3 * (t1 - t0)); t["device_clouds_ms"].append(1e3 * (t3 - t2)); t["score_device_ms"].append(new["device_ms"]); t["color_metric_stage_ms"].append(stage)
         med = {n: statistics.median(v) for n, v in t.items()}
