@@ -336,7 +336,7 @@ int rbt_picture_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int widt
  * rbt_wait_gof_d1 collects no other job: any other pairing is RBT_ERR_PARAM and the job stays collectable.
  * Memory: the clouds of a round are scored one after the other. A job holds one 128 MB volume per frame without a reference handle (for the whole job), one more for the
  * trial being scored, and three packed planes per frame; rbt_job_memory counts them with the arenas of the first round.
- * Not built: a container-level call (the library does not parse the atlas sub-bitstream, so rbt_transcode_v3c cannot know the patches), a D2 floor (a colour floor: rbt_submit_gof_color below), a D1 floor
+ * Not built: a container-level call (the library does not parse the atlas sub-bitstream, so rbt_transcode_v3c cannot know the patches), a D1 floor (a D2 floor: "D2 floors" at the end of this header; a colour floor: rbt_submit_gof_color below)
  * together with a byte budget or a PSNR floor, a floor per frame other than through RBT_D1_MIN. */
 enum { RBT_D1_MIN = 0, RBT_D1_MEAN = 1 };
 typedef struct rbt_d1_target rbt_d1_target;                  /* both defined behind rbt_score_summary, where the types of their fields are known */
@@ -737,6 +737,29 @@ typedef struct { uint32_t n_ab, n_ba; uint64_t sse_ab, sse_ba, max_ab, max_ba; f
 int rbt_pcloud_set_labels(rbt_ctx* ctx, rbt_pcloud* cloud, const uint32_t* labels);        /* one per point, < 65536 */
 int rbt_pcloud_labels(rbt_ctx* ctx, const rbt_pcloud* cloud, uint32_t* labels);            /* of rbt_pcloud_from_maps: the patch index; RBT_ERR_PARAM for a cloud without labels */
 int rbt_score_patches(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int n_patches, rbt_patch_d1* out, rbt_d1_result* whole, double* device_ms);
+/* ---- D2 per patch of the decoded cloud (csrc/rbt_score.h) ----
+ * A is the source with normals, B the decoded cloud with one label per point, as for rbt_score_patches. Merging, representatives, tie sets, the give / take rule for B's
+ * normals and the per-point values v_ab[i] (point i of A against B's completed normals) and v_ba[j] (point j of B against A's normals) are rbt_score's with RBT_SCORE_D2,
+ * unchanged; a point that is no representative has the value 0. New are the attribution of the values to patches and the order of the sums.
+ *   attribution  that of D1 per patch: v_ba[j] belongs to patch L[j]; v_ab[i] belongs to the label of i's owner, the lowest point index among B's merged points at
+ *                exactly the nearest distance. n_ab[k] and n_ba[k] are therefore rbt_score_patches' counts.
+ *   sums         no floating-point atomics. For patch k and one direction let w[i] = v[i] where the term of point i belongs to k, and 0 elsewhere (also where point i has no
+ *                term). sse[k] is the fixed-order sum given at rbt_score - blocks of 256 entries folded by s[t] += s[t + h], h = 128 .. 1; the block sums added by column t,
+ *                t + 256, .. in ascending order; the 256 columns folded the same way - applied to w, and max[k] is the maximum of w. The values are >= 0, so adding a 0
+ *                changes no bit: the library skips blocks and columns in which a patch has no term and keeps the tree. With n_patches = 1, patch 0's sums and maxima are
+ *                rbt_score(a, b, peak, RBT_SCORE_D2).d2's bit for bit; two calls return the same bits, and so does the serial host emulation.
+ *   figure       mse_*[k] = sse / n and psnr[k] = 10 log10(3 peak^2 / max(mse_ab, mse_ba)) from the one float routine rbt_d2 and rbt_score use. A direction without a point
+ *                has mse 0; a patch without a point in either direction has psnr +inf.
+ * The sums over k of n_ab and n_ba are the whole's n_a and n_b; the maxima over k of max_ab and max_ba are its maxima bit for bit; the sums over k of sse_* are its sums
+ * up to the rounding of a reordered double sum.
+ * rbt_score_patches_d2: out receives n_patches entries. whole and device_ms may be NULL; whole is bit for bit rbt_score(a, b, peak, RBT_SCORE_D2).d2 (the same launches),
+ * device_ms the time between events around those launches and the per-patch kernels (k_p2_block, k_p2_cols, k_p2_fold per direction). Scratch next to rbt_score's for D2:
+ * 12 bytes per point of the larger cloud rounded up to a multiple of 256, 4 bytes per 256 points of it, and 2 KB + 48 bytes per patch - it grows with points + patches,
+ * never with patches x blocks. RBT_ERR_PARAM, with the reason in rbt_last_error and the context still usable: those of rbt_score_patches (a handle of another context, b
+ * without labels, a label >= n_patches - checked by a kernel before any sum is written -, n_patches outside 1..65536, peak < 1) and a without normals.
+ * The closed loops on these figures: "D2 floors" below. Not built: colour figures per patch. */
+typedef struct { uint32_t n_ab, n_ba; double sse_ab, sse_ba, max_ab, max_ba; float mse_ab, mse_ba, psnr; } rbt_patch_d2;
+int rbt_score_patches_d2(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int n_patches, rbt_patch_d2* out, rbt_d2_result* whole, double* device_ms);
 /* Summary over the frames of a sequence, per figure (the symmetric PSNR of D1, D2, Y, U, V): arithmetic mean and minimum, in double, over the frames that carry that part
  * (n_d1 / n_d2 / n_color of them; 0 where there is none); a frame whose PSNR is +inf makes the mean +inf. The reference itself writes one line per frame and averages
  * nothing (PCCMetrics::write); the mean over the frames is what the CTC reporting forms from those lines. points_* / merged_*: sums over all frames. Host only. */
@@ -1059,6 +1082,82 @@ typedef struct {
 int rbt_pcloud_estimate_normals(rbt_ctx* ctx, rbt_pcloud* cloud, const rbt_normals_params* p, int16_t* normals_q14, double* device_ms);
 /* The same stage for host arrays: upload, index, estimate, release. Limits and error codes of rbt_pcloud_upload, and the above. */
 int rbt_estimate_normals(rbt_ctx* ctx, const int16_t* xyz, int n, const rbt_normals_params* p, int16_t* normals_q14);
+
+/* ---- D2 floors: on the stream and held patch by patch (csrc/rbt_score.h, host/rbt_patch_walk.h) ----
+ * The common test conditions report D1 and D2. These two job kinds are the D1 kinds ("transcoding geometry to a D1 floor", "D1 floors held patch by patch") with the D2
+ * figure: one more figure on the same cloud path, the same walks, the same rounds.
+ *
+ * On the stream (rbt_submit_gof_d2 / rbt_wait_gof_d2 / rbt_transcode_gof_d2). Rules 1 - 7 of "transcoding geometry to a D1 floor" hold word for word with
+ * D_f(q) = (double)rbt_score(A_f, B_f(q), peak, RBT_SCORE_D2).d2.psnr. Reference: a given handle must carry normals (uploaded with them, or given them through
+ * rbt_pcloud_estimate_normals), else RBT_ERR_PARAM at submit; a NULL handle is the cloud of the decoded input, which receives normals once per job through the estimation
+ * of rbt_pcloud_estimate_normals with target.normals (struct_size 0 = all defaults; else checked as that call checks it) and keeps them for the job. The returned stream is
+ * byte for byte rbt_transcode_gof's at q*. min_d2_mdb 0: coded at params[i].qp, D2 reported. stat takes RBT_D2_MIN / RBT_D2_MEAN. Refusals are the D1 kind's, with its
+ * words, plus a reference without normals and a bad normals record. cloud_ms includes the estimation.
+ *
+ * Patch by patch (rbt_submit_gof_d2_patches / rbt_wait_gof_d2_patches / rbt_transcode_gof_d2_patches). Rules 1 - 5 of "D1 floors held patch by patch" hold with the figure
+ * (double)psnr[k] of rbt_score_patches_d2 on (A_f, B_f(trial map)); patch_walk_seed and patch_walk_step are unchanged. The stream is byte for byte
+ * rbt_transcode_gof_qp_map's for the final map, no further encode runs, and the result names the patch that sets a frame's D2 as the D1 kind does. The reference rule is
+ * the one above.
+ * A job is collected only by the wait call of its kind; a wrong pairing is RBT_ERR_PARAM and leaves the job collectable.
+ * Not built: D2 floors per frame through the QP list (rbt_submit_gof_d1_frames has no D2 sibling), colour figures and colour floors per patch, a D2 floor together with
+ * another kind of target in one job, and container-level calls - the library does not parse the atlas sub-bitstream. */
+enum { RBT_D2_MIN = RBT_D1_MIN, RBT_D2_MEAN = RBT_D1_MEAN };
+typedef struct {
+  uint32_t struct_size;                  /* sizeof(rbt_d2_target): checked */
+  int32_t  min_d2_mdb;                   /* floor on D, 1/1000 dB; 0 = none: coded at params[i].qp, D2 reported */
+  int      stat;                         /* RBT_D2_MIN (the default) or RBT_D2_MEAN */
+  int      peak;                         /* 0 = 1023 */
+  int      qp_min, qp_max;               /* the walk's range; qp_max 0 = 51 */
+  int      n_frames;                     /* point-cloud frames of the entry; 0 in an empty target */
+  rbt_atlas_params atlas;                /* the OUTPUT atlas, as in rbt_d1_target */
+  const rbt_patch* const* patches;       /* n_frames lists ... */
+  const int* n_patches;                  /* ... and their lengths; copied at submit */
+  const rbt_pcloud* const* reference;    /* NULL, or n_frames handles: A_f with normals; a NULL handle = the cloud of the decoded input with estimated normals */
+  rbt_normals_params normals;            /* for the clouds of the decoded input; struct_size 0 = all defaults */
+} rbt_d2_target;
+typedef struct {
+  int qp, qp_probe, qp_start, met, n_encodes;   /* q*, q0, qs, met, distinct QPs encoded */
+  uint64_t bytes;                               /* size of the returned stream */
+  double mean_d2, min_d2;                       /* over the frames at q*: the sum of (double)psnr in frame order / n_frames, and the minimum */
+  int n_frames;                                 /* 0 for an entry without a target */
+  rbt_d2_result* frames;                        /* n_frames results at q* (malloc'd, rbt_free; NULL for an entry without a target) */
+  double cloud_ms;                              /* as rbt_d1_floor_result.cloud_ms, the normal estimation of the reference clouds included */
+} rbt_d2_floor_result;
+int rbt_submit_gof_d2(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d2_target* targets, rbt_job** job);
+int rbt_wait_gof_d2(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_d2_floor_result* results);   /* results: n entries */
+int rbt_transcode_gof_d2(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d2_target* targets,
+                         uint8_t** annexb_out, size_t* n_out, rbt_d2_floor_result* results);   /* submit + wait */
+typedef struct {
+  uint32_t struct_size;                                        /* sizeof(rbt_patch_d2_target): checked */
+  int32_t  min_d2_mdb;  int peak;  int qp_min, qp_max;         /* as rbt_patch_d1_target */
+  int      background_qp;                                      /* 0..51, -1 = q0 */
+  int      max_trials;                                         /* 0 = no cap */
+  rbt_atlas_params atlas;                                      /* the OUTPUT atlas */
+  int n_frames;  const rbt_patch* const* patches;  const int* n_patches;
+  const int32_t* const* patch_min_d2_mdb;                      /* NULL, or per frame NULL / one floor per patch: F_k; else F_k = min_d2_mdb */
+  const rbt_pcloud* const* reference;                          /* as in rbt_d2_target */
+  rbt_normals_params normals;                                  /* as in rbt_d2_target */
+} rbt_patch_d2_target;
+typedef struct { int qp, met, failed; rbt_patch_d2 d2; double figure; } rbt_patch_d2_pick;   /* of the settling trial: q[k], met, failed[k], the patch's sums and figures, (double)d2.psnr */
+typedef struct {
+  int n_trials, met, n_patches;                                /* met = AND of patches[k].met */
+  uint64_t bytes;                                              /* the frame's NAL units in the returned stream, start codes included */
+  rbt_d2_result d2;                                            /* the whole frame's D2 in the settling trial: rbt_score(A_f, B_f, peak, RBT_SCORE_D2).d2 */
+  rbt_patch_d2_pick* patches;                                  /* n_patches picks: they point into rbt_patch_d2_result.picks */
+} rbt_patch_d2_frame;
+typedef struct {
+  int n_frames, qp_probe, met_all, n_passes;                   /* q0; met_all = AND of frames[f].met */
+  uint64_t bytes, pictures_encoded;                            /* size of the returned stream; 2 * sum of frames[f].n_trials */
+  int w_ctb, h_ctb;
+  int8_t* map;                                                 /* the final map, n_frames * h_ctb * w_ctb (malloc'd, rbt_free) */
+  rbt_patch_d2_frame* frames;                                  /* n_frames (malloc'd, rbt_free) */
+  rbt_patch_d2_pick* picks;                                    /* every frame's picks back to back (malloc'd, rbt_free) */
+  double cloud_ms;                                             /* as rbt_d2_floor_result.cloud_ms, the per-patch kernels included */
+} rbt_patch_d2_result;
+int rbt_submit_gof_d2_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d2_target* targets, rbt_job** job);
+int rbt_wait_gof_d2_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_patch_d2_result* results);   /* results: n entries */
+int rbt_transcode_gof_d2_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d2_target* targets,
+                                 uint8_t** annexb_out, size_t* n_out, rbt_patch_d2_result* results);   /* submit + wait */
 
 #ifdef __cplusplus
 }

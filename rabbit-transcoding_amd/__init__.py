@@ -92,6 +92,16 @@ def patch_d1_dict(p):
     return {k: getattr(p, k) for k, _ in PatchD1._fields_}
 
 
+class PatchD2(C.Structure):
+    """rbt_patch_d2: the D2 sums and figures of one patch of the decoded cloud (rbt_score_patches_d2)"""
+    _fields_ = [("n_ab", C.c_uint32), ("n_ba", C.c_uint32), ("sse_ab", C.c_double), ("sse_ba", C.c_double), ("max_ab", C.c_double), ("max_ba", C.c_double),
+                ("mse_ab", C.c_float), ("mse_ba", C.c_float), ("psnr", C.c_float)]
+
+
+def patch_d2_dict(p):
+    return {k: getattr(p, k) for k, _ in PatchD2._fields_}
+
+
 class FrameScore(C.Structure):
     """rbt_frame_score: what rbt_score returns for one pair of clouds"""
     _fields_ = [("parts", C.c_int), ("d1", D1Result), ("d2", D2Result), ("color", ColorResult), ("device_ms", C.c_double)] + \
@@ -454,6 +464,11 @@ def load(path=None):
     L.rbt_wait_gof_d1_frames.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(FrameFloorResult)]
     L.rbt_transcode_gof_d1_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                               C.POINTER(FrameFloorResult)]
+    for name, tt, rt in (("d2", D2Target, D2FloorResult), ("d2_patches", PatchD2Target, PatchD2Result)):
+        args = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(tt)]
+        getattr(L, "rbt_submit_gof_" + name).argtypes = args + [C.POINTER(C.c_void_p)]
+        getattr(L, "rbt_wait_gof_" + name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(rt)]
+        getattr(L, "rbt_transcode_gof_" + name).argtypes = args + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(rt)]
     L.rbt_submit_gof_d1.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p)]
     L.rbt_wait_gof_d1.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(D1FloorResult)]
     L.rbt_transcode_gof_d1.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
@@ -468,6 +483,7 @@ def load(path=None):
     L.rbt_pcloud_set_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.rbt_pcloud_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.rbt_score_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(PatchD1), C.POINTER(D1Result), C.POINTER(C.c_double)]
+    L.rbt_score_patches_d2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(PatchD2), C.POINTER(D2Result), C.POINTER(C.c_double)]
     L.rbt_score_pair_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     L.rbt_score_pair_color.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ColorResult)]
     L.rbt_score_pair_release.argtypes = [C.c_void_p, C.c_void_p]
@@ -609,6 +625,76 @@ class NormalsParams(C.Structure):
 
     def __init__(self, k=0, orientation=RBT_NORMALS_ORIENT_VIEW_POINT, view_point=(0, 0, 0)):
         super().__init__(C.sizeof(NormalsParams), k, orientation, (C.c_int32 * 3)(*view_point))
+
+
+RBT_D2_MIN, RBT_D2_MEAN = RBT_D1_MIN, RBT_D1_MEAN
+
+
+def _set_normals(target, normals):
+    """the normals field of a D2 target: None leaves struct_size 0 (all defaults)"""
+    if normals is not None:
+        target.normals = NormalsParams(normals.k, normals.orientation, tuple(normals.view_point))
+
+
+class D2Target(C.Structure):
+    """rbt_d2_target: D1Target with min_d2_mdb, references that carry normals (None = the cloud of the decoded input with estimated normals) and normals, the
+    NormalsParams of that estimation (None = all defaults)"""
+    _fields_ = [("struct_size", C.c_uint32), ("min_d2_mdb", C.c_int32), ("stat", C.c_int), ("peak", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("n_frames", C.c_int),
+                ("atlas", AtlasParams), ("patches", C.POINTER(C.POINTER(Patch))), ("n_patches", C.POINTER(C.c_int)), ("reference", C.POINTER(C.c_void_p)), ("normals", NormalsParams)]
+
+    def __init__(self, atlas=None, patches=None, min_d2_mdb=0, stat=RBT_D2_MIN, qp_min=0, qp_max=0, peak=0, reference=None, normals=None):
+        C.Structure.__init__(self)
+        self.struct_size = C.sizeof(D2Target)
+        self._keep = []
+        if atlas is None:
+            return
+        d = D1Target(atlas, patches, min_d2_mdb, stat, qp_min, qp_max, peak, reference)      # the arrays are D1Target's, kept alive with it
+        for name, _ in D1Target._fields_[2:]:
+            setattr(self, name, getattr(d, name))
+        self.min_d2_mdb = min_d2_mdb
+        self._keep.append(d)
+        _set_normals(self, normals)
+
+
+class D2FloorResult(C.Structure):
+    """rbt_d2_floor_result: D1FloorResult with mean_d2, min_d2 and the frames' D2Result"""
+    _fields_ = [("qp", C.c_int), ("qp_probe", C.c_int), ("qp_start", C.c_int), ("met", C.c_int), ("n_encodes", C.c_int), ("bytes", C.c_uint64), ("mean_d2", C.c_double), ("min_d2", C.c_double),
+                ("n_frames", C.c_int), ("frames", C.POINTER(D2Result)), ("cloud_ms", C.c_double)]
+
+
+class PatchD2Target(C.Structure):
+    """rbt_patch_d2_target: PatchD1Target with min_d2_mdb, patch_floors as patch_min_d2_mdb, references that carry normals and normals (None = all defaults)"""
+    _fields_ = [("struct_size", C.c_uint32), ("min_d2_mdb", C.c_int32), ("peak", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("background_qp", C.c_int), ("max_trials", C.c_int),
+                ("atlas", AtlasParams), ("n_frames", C.c_int), ("patches", C.POINTER(C.POINTER(Patch))), ("n_patches", C.POINTER(C.c_int)), ("patch_min_d2_mdb", C.POINTER(C.POINTER(C.c_int32))),
+                ("reference", C.POINTER(C.c_void_p)), ("normals", NormalsParams)]
+
+    def __init__(self, atlas=None, patches=None, min_d2_mdb=0, peak=0, qp_min=0, qp_max=0, background_qp=-1, max_trials=0, patch_floors=None, reference=None, normals=None):
+        C.Structure.__init__(self)
+        self.struct_size = C.sizeof(PatchD2Target)
+        self._keep = []
+        if atlas is None:
+            return
+        d = PatchD1Target(atlas, patches, min_d2_mdb, peak, qp_min, qp_max, background_qp, max_trials, patch_floors, reference)      # the arrays are PatchD1Target's
+        for (name, _), (src, _) in zip(PatchD2Target._fields_[1:13], PatchD1Target._fields_[1:13]):
+            setattr(self, name, getattr(d, src))
+        self._keep.append(d)
+        _set_normals(self, normals)
+
+
+class PatchD2Pick(C.Structure):
+    """rbt_patch_d2_pick: of a frame's settling trial, per patch: its QP, met, failed, its PatchD2, its figure"""
+    _fields_ = [("qp", C.c_int), ("met", C.c_int), ("failed", C.c_int), ("d2", PatchD2), ("figure", C.c_double)]
+
+
+class PatchD2Frame(C.Structure):
+    """rbt_patch_d2_frame: trials, met, the patch count, the frame's bytes, the whole frame's D2Result in the settling trial, the picks"""
+    _fields_ = [("n_trials", C.c_int), ("met", C.c_int), ("n_patches", C.c_int), ("bytes", C.c_uint64), ("d2", D2Result), ("patches", C.POINTER(PatchD2Pick))]
+
+
+class PatchD2Result(C.Structure):
+    """rbt_patch_d2_result: as PatchD1Result"""
+    _fields_ = [("n_frames", C.c_int), ("qp_probe", C.c_int), ("met_all", C.c_int), ("n_passes", C.c_int), ("bytes", C.c_uint64), ("pictures_encoded", C.c_uint64), ("w_ctb", C.c_int), ("h_ctb", C.c_int),
+                ("map", C.POINTER(C.c_int8)), ("frames", C.POINTER(PatchD2Frame)), ("picks", C.POINTER(PatchD2Pick)), ("cloud_ms", C.c_double)]
 
 
 class PCloud:
@@ -898,6 +984,15 @@ class Context:
             self.L.rbt_free(ptr)
         return outs, rs
 
+    def _d2_results(self, res):
+        """as _d1_results, with D2 dicts"""
+        outs, rs = res
+        for r in rs:
+            ptr = r["frames"]
+            r["frames"] = [{n: getattr(ptr[f], n) for n, _ in D2Result._fields_} for f in range(r["n_frames"])]
+            self.L.rbt_free(ptr)
+        return outs, rs
+
     def _color_results(self, res):
         """([stream bytes, ...], [ColorFloorResult, ...] as dicts): frames becomes a list of colour dicts (Context.color_metric's) and the library's array is released"""
         outs, rs = res
@@ -1165,6 +1260,13 @@ class Context:
         self._chk(self.L.rbt_score_patches(self.h, a.h if a is not None else None, b.h if b is not None else None, peak, n_patches, out, C.byref(whole), C.byref(ms)))
         return (out if raw else [patch_d1_dict(out[k]) for k in range(n_patches)]), (whole if raw else _result_dict(whole)), ms.value
 
+    def score_patches_d2(self, a, b, n_patches, peak=1023, raw=False):
+        """rbt_score_patches_d2: a = the source PCloud with normals, b = the decoded one with its labels -> (one dict per patch - or the PatchD2 array itself (raw) -, the
+        whole frame's D2 as rbt_score returns it, device_ms)"""
+        out = (PatchD2 * max(1, n_patches))(); whole = D2Result(); ms = C.c_double()
+        self._chk(self.L.rbt_score_patches_d2(self.h, a.h if a is not None else None, b.h if b is not None else None, peak, n_patches, out, C.byref(whole), C.byref(ms)))
+        return (out if raw else [patch_d2_dict(out[k]) for k in range(n_patches)]), (whole if raw else _result_dict(whole)), ms.value
+
     def score_pair(self, a, b):
         """rbt_score_pair_create: a = the source PCloud, b = the decoded one -> ScorePair"""
         return ScorePair(self, a, b)
@@ -1225,6 +1327,10 @@ _GOF_KINDS = {
                    lambda self, res: self._patch_results(res, lambda f: dict(_result_dict(f), d1=_result_dict(f.d1)), lambda p: dict(_result_dict(p), d1=patch_d1_dict(p.d1))),
                    "submit_gof with one PatchD1Target per entry (PatchD1Target() = none): every patch of every frame of a geometry entry holds its D1 floor", ""),
     "d1": (D1Target, D1FloorResult, Context._d1_results, "submit_gof with one D1Target per entry (D1Target() = none; min_d1_mdb 0 = constant QP, D1 reported)", ""),
+    "d2": (D2Target, D2FloorResult, Context._d2_results, "submit_gof with one D2Target per entry (D2Target() = none; min_d2_mdb 0 = constant QP, D2 reported)", ""),
+    "d2_patches": (PatchD2Target, PatchD2Result,
+                   lambda self, res: self._patch_results(res, lambda f: dict(_result_dict(f), d2=_result_dict(f.d2)), lambda p: dict(_result_dict(p), d2=patch_d2_dict(p.d2))),
+                   "submit_gof with one PatchD2Target per entry (PatchD2Target() = none): every patch of every frame of a geometry entry holds its D2 floor", ""),
     "color": (ColorTarget, ColorFloorResult, Context._color_results,
               "submit_gof with one ColorTarget per entry (ColorTarget() = none; min_psnr_mdb 0 = constant QP, colour results reported)", ""),
 }

@@ -135,6 +135,19 @@ __global__ void __launch_bounds__(256) k_pd_sums(RbtScoreCloud A, RbtScoreCloud 
     if ((threadIdx.x & 63) == 0) pd_add(out, first, dir, s, (unsigned long long)__popcll(act), m);
   } else if (valid) pd_add(out, label, dir, d, 1, d);
 }
+// ---- D2 per patch (rbt_score.h) ----
+// one workgroup per 256 entries of the walking cloud. LDS per workgroup: sizeof(RbtPatchD2Lds), 8 KB
+__global__ void __launch_bounds__(RBT_SC_SUM) k_p2_block(RbtScoreCloud A, RbtScoreCloud B, const uint32_t* labels_b, RbtScoreWork W, RbtPatchD2Work P, unsigned long long* out, int dir) {
+  __shared__ RbtPatchD2Lds lds;
+  p2_block(&A, &B, labels_b, &W, &P, out, dir, (int)blockIdx.x, RBT_LDS_CAST(RbtPatchD2Lds, &lds));
+}
+// one workgroup: lane t owns column t of S
+__global__ void __launch_bounds__(RBT_SC_SUM) k_p2_cols(RbtPatchD2Work P, int n_blocks) { p2_cols(&P, n_blocks, (int)threadIdx.x); }
+// one workgroup per patch
+__global__ void __launch_bounds__(RBT_SC_SUM) k_p2_fold(RbtPatchD2Work P, unsigned long long* out, int dir) {
+  __shared__ RbtScoreSumLds lds;
+  p2_fold(&P, out, dir, (int)blockIdx.x, RBT_LDS_CAST(RbtScoreSumLds, &lds));
+}
 
 void launch_up444(const uint16_t* yuv420, int w, int h, int bit_depth, int n_frames, int filter, uint16_t* yuv444) {
   if (n_frames <= 0) return;
@@ -211,5 +224,14 @@ void launch_pd_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32
   if (A->n <= 0 || B->n <= 0) return;
   hipLaunchKernelGGL(k_pd_sums, dim3((unsigned)((A->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, labels_b, dist_a, dist_b, out, 0);
   hipLaunchKernelGGL(k_pd_sums, dim3((unsigned)((B->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, labels_b, dist_a, dist_b, out, 1);
+}
+void launch_p2_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const RbtScoreWork* W, const RbtPatchD2Work* P, int n_patches, unsigned long long* out) {
+  if (A->n <= 0 || B->n <= 0 || n_patches <= 0) return;
+  for (int dir = 0; dir < 2; dir++) {
+    const int n = dir ? B->n : A->n, nb = (n + RBT_SC_SUM - 1) / RBT_SC_SUM;
+    hipLaunchKernelGGL(k_p2_block, dim3((unsigned)nb), dim3(RBT_SC_SUM), 0, g_stream, *A, *B, labels_b, *W, *P, out, dir);
+    hipLaunchKernelGGL(k_p2_cols, dim3(1), dim3(RBT_SC_SUM), 0, g_stream, *P, nb);
+    hipLaunchKernelGGL(k_p2_fold, dim3((unsigned)n_patches), dim3(RBT_SC_SUM), 0, g_stream, *P, out, dir);
+  }
 }
 }  // namespace rbtk

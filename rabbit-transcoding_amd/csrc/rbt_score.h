@@ -24,6 +24,13 @@
 //            (points arrive in patch order) folds sum, count and maximum in registers and issues one atomic per word, a mixed wave one per lane and word. The labels
 //            are checked against the patch count by a kernel of their own first (error word), so a refused call has written no sum. The labels of a cloud made from maps
 //            come from a kernel of their own over the work items' offsets (pd_label_item): the reconstruction kernels are the ones they were.
+//   D2/patch D2 per patch of the decoded cloud (rbt_score_patches_d2; the definition is in include/rbt.h): behind launch_sc_score with the D2 part, on the values val_ab / val_ba
+//            it leaves. The attribution is that of D1 per patch (pd_term_ab / pd_term_ba); the sums keep rbt_score's fixed order with the values of other patches read as 0.
+//            p2_block: a workgroup takes 256 entries, and for every distinct label among them - in the order of the lowest lane that carries it - folds the masked tree
+//            in LDS and appends (label, sum) to the block's own range of 256 entries; the patch's count and maximum go out as integer atomics (a value >= 0 orders as
+//            its bit pattern does). p2_cols: 256 lanes, lane t walks blocks t, t + 256, .. in ascending order and adds every entry into S[label][t] - it owns its
+//            column, no atomics. p2_fold: one workgroup per patch folds S[k][0..255] and leaves the row zero for the other direction. No floating-point atomics.
+//            Scratch: 12 bytes per entry of the larger cloud rounded up to 256, 4 per 256 entries, 2 KB (S) + 8 RBT_P2_WORDS bytes per patch: O(points + patches).
 // No kernel waits for another; every loop is bounded by the size of the volume.
 #pragma once
 #include "rbt_color.h"
@@ -42,6 +49,9 @@ struct RbtScoreCloud { const int16_t* xyz; const uint8_t* rgb; const int16_t* nr
 // scored against another source next); val_*: D2 value per point; part: 2 * ceil(max(n) / 256) doubles; res: RBT_SC_RESULTS words (zeroed beforehand)
 struct RbtScoreWork { uint32_t* dist_a; uint32_t* dist_b; long long* acc_b; int32_t* cnt_b; double* val_ab; double* val_ba; double* part; unsigned long long* res; };
 struct RbtScoreSumLds { double s[RBT_SC_SUM]; double m[RBT_SC_SUM]; };
+// scratch of one rbt_score_patches_d2 call beside RbtScoreWork. ent_label / ent_sum: 256 entries per block of 256 points of the larger cloud, ent_n: the entries a block
+// wrote; S: n_patches rows of RBT_SC_SUM doubles (zeroed beforehand; zero again when the call has run)
+struct RbtPatchD2Work { uint32_t* ent_label; double* ent_sum; uint32_t* ent_n; double* S; };
 
 namespace rbtk {
 void launch_sc_check(const int16_t* xyz, int n, uint32_t* scal);        // scal[RBT_SC_ERR] = 1 when a coordinate lies outside 0..1023
@@ -58,10 +68,17 @@ void launch_pd_labels(const uint32_t* items, const uint32_t* offsets, int n_item
 void launch_pd_check(const uint32_t* labels, int n, uint32_t n_patches, uint32_t* err);       // *err = 1 when a label is >= n_patches
 // behind launch_sc_score / launch_sc_search on the same clouds: out holds RBT_PD_WORDS words per patch (zeroed beforehand); every label of B is below the patch count
 void launch_pd_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out);
+// behind launch_sc_score with RBT_SCORE_D2 on the same clouds and the same W (dist_*, val_*): out holds RBT_P2_WORDS words per patch (zeroed beforehand); every label of B
+// is below n_patches
+void launch_p2_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const RbtScoreWork* W, const RbtPatchD2Work* P, int n_patches, unsigned long long* out);
 }  // namespace rbtk
 enum { RBT_SC_COLOR_RESULTS = 8 };
 // words of one patch in the result of launch_pd_sums, 64-bit each; + 1 for the direction B -> A
 enum { RBT_PD_SSE_AB = 0, RBT_PD_SSE_BA, RBT_PD_N_AB, RBT_PD_N_BA, RBT_PD_MAX_AB, RBT_PD_MAX_BA, RBT_PD_WORDS };
+// words of one patch in the result of launch_p2_sums, 64-bit each; + 1 for the direction B -> A. SSE and MAX hold doubles, N counts
+enum { RBT_P2_SSE_AB = 0, RBT_P2_SSE_BA, RBT_P2_N_AB, RBT_P2_N_BA, RBT_P2_MAX_AB, RBT_P2_MAX_BA, RBT_P2_WORDS };
+// LDS of p2_block: the fold's arrays, then per lane its label (RBT_SC_NONE: no term), its value, and - for the lowest lane of a label - the label's count of lanes (else 0)
+struct RbtPatchD2Lds { RbtScoreSumLds f; double v[RBT_SC_SUM]; uint32_t lab[RBT_SC_SUM]; uint32_t lead[RBT_SC_SUM]; };
 
 // ------------------------------------------------------------------------------------------------ bodies (device and host emulation)
 RBT_DEV size_t sc_coarse_word(int cx, int cy, int cz) { return (((size_t)cz * RBT_SC_CDIM + cy) * RBT_SC_CROW) + (cx >> 5); }
@@ -333,6 +350,78 @@ RBT_DEV void pd_add(unsigned long long* out, uint32_t label, int dir, unsigned l
 #endif
 }
 
+// ---- D2 per patch ----
+// sc_fold's tree on the arrays alone: s[0] and m[0] hold sum and maximum when it returns
+RBT_DEV void p2_tree(RBT_LDS_AS RbtScoreSumLds* L) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  RBT_SYNC();
+  for (int h = RBT_SC_SUM / 2; h > 0; h >>= 1) {
+    RBT_BLK_FOR(t, h) { L->s[t] = L->s[t] + L->s[t + h]; if (L->m[t + h] > L->m[t]) L->m[t] = L->m[t + h]; }
+    RBT_SYNC();
+  }
+}
+// Block b of direction dir (0: the points of A, 1: of B): entries b * 256 + t. For every distinct label of the block, in the order of its lowest lane, the masked tree of
+// sc_sum_block - the values of the label's lanes, 0 elsewhere - is folded, and (label, sum) becomes entry ent_n[b] of the block's range; count and maximum go to `out`.
+RBT_DEV void p2_block(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const RbtScoreWork* W, const RbtPatchD2Work* P, unsigned long long* out, int dir, int b,
+                      RBT_LDS_AS RbtPatchD2Lds* L) {
+  const int n = dir ? B->n : A->n;
+  RBT_BLK_FOR(t, RBT_SC_SUM) {
+    const int i = b * RBT_SC_SUM + t;
+    uint32_t label = 0, d = 0; int valid = 0;
+    if (i < n) valid = dir ? pd_term_ba(labels_b, W->dist_b, i, &label, &d) : pd_term_ab(A, B, labels_b, W->dist_a, i, &label, &d);
+    L->lab[t] = valid ? label : RBT_SC_NONE; L->v[t] = valid ? (dir ? W->val_ba[i] : W->val_ab[i]) : 0.0;
+  }
+  RBT_SYNC();
+  RBT_BLK_FOR(t, RBT_SC_SUM) {
+    const uint32_t mine = L->lab[t]; uint32_t cnt = 0; int lower = 0;
+    if (mine != RBT_SC_NONE) for (int u = 0; u < RBT_SC_SUM; u++) if (L->lab[u] == mine) { cnt++; if (u < t) lower = 1; }
+    L->lead[t] = lower ? 0u : cnt;
+  }
+  RBT_SYNC();
+  int e = 0;
+  for (int k = 0; k < RBT_SC_SUM; k++) {
+    const uint32_t cnt = L->lead[k];                                    // the same word for every lane: the branch is uniform over the workgroup
+    if (!cnt) continue;
+    const uint32_t label = L->lab[k];
+    RBT_BLK_FOR(t, RBT_SC_SUM) { const double v = L->lab[t] == label ? L->v[t] : 0.0; L->f.s[t] = v; L->f.m[t] = v; }
+    p2_tree(&L->f);
+    RBT_BLK_FOR(t, 1) {
+      const size_t slot = (size_t)b * RBT_SC_SUM + (size_t)e;
+      P->ent_label[slot] = label; P->ent_sum[slot] = L->f.s[0];
+      unsigned long long* w = out + (size_t)RBT_P2_WORDS * label + dir; const double mx = L->f.m[0];
+      unsigned long long bits; __builtin_memcpy(&bits, &mx, 8);          // a double >= 0 orders as its bit pattern does
+#ifdef RBT_HOSTEMU
+      w[RBT_P2_N_AB] += cnt; if (bits > w[RBT_P2_MAX_AB]) w[RBT_P2_MAX_AB] = bits;
+#else
+      atomicAdd(&w[RBT_P2_N_AB], (unsigned long long)cnt);
+      if (bits) atomicMax(&w[RBT_P2_MAX_AB], bits);
+#endif
+    }
+    RBT_SYNC();
+    e++;
+  }
+  RBT_BLK_FOR(t, 1) P->ent_n[b] = (uint32_t)e;
+}
+// the block sums by column: lane t adds the entries of blocks t, t + 256, .. in ascending order into S[label][t] (sc_sum_final's first step, a patch absent from a block adding 0)
+RBT_DEV void p2_cols(const RbtPatchD2Work* P, int n_blocks, int t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  for (int b = t; b < n_blocks; b += RBT_SC_SUM) {
+    const uint32_t ne = P->ent_n[b];
+    for (uint32_t e = 0; e < ne; e++) { const size_t slot = (size_t)b * RBT_SC_SUM + e; double* s = &P->S[(size_t)P->ent_label[slot] * RBT_SC_SUM + (size_t)t]; *s = *s + P->ent_sum[slot]; }
+  }
+}
+// patch k: the fold of sc_sum_final over S[k][0..255] into the patch's sum of direction dir; the row goes back to zero
+RBT_DEV void p2_fold(const RbtPatchD2Work* P, unsigned long long* out, int dir, int k, RBT_LDS_AS RbtScoreSumLds* L) {
+  double* row = P->S + (size_t)k * RBT_SC_SUM;
+  RBT_BLK_FOR(t, RBT_SC_SUM) { L->s[t] = row[t]; L->m[t] = 0.0; row[t] = 0.0; }
+  p2_tree(L);
+  RBT_BLK_FOR(t, 1) { double* w = (double*)(out + (size_t)RBT_P2_WORDS * (size_t)k + dir); w[RBT_P2_SSE_AB] = L->s[0]; }
+}
+
 #ifdef RBT_HOSTEMU
 // serial stand-ins of the launchers (the product's are in rbt_color.hip)
 namespace rbtk {
@@ -342,6 +431,15 @@ inline void launch_pd_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const
   uint32_t label = 0, d = 0;
   for (int i = 0; i < A->n; i++) if (pd_term_ab(A, B, labels_b, dist_a, i, &label, &d)) pd_add(out, label, 0, d, 1, d);
   for (int j = 0; j < B->n; j++) if (pd_term_ba(labels_b, dist_b, j, &label, &d)) pd_add(out, label, 1, d, 1, d);
+}
+inline void launch_p2_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const RbtScoreWork* W, const RbtPatchD2Work* P, int n_patches, unsigned long long* out) {
+  static RbtPatchD2Lds lds;
+  for (int dir = 0; dir < 2; dir++) {
+    const int n = dir ? B->n : A->n, nb = (n + RBT_SC_SUM - 1) / RBT_SC_SUM;
+    for (int b = 0; b < nb; b++) p2_block(A, B, labels_b, W, P, out, dir, b, &lds);
+    for (int t = 0; t < RBT_SC_SUM; t++) p2_cols(P, nb, t);
+    for (int k = 0; k < n_patches; k++) p2_fold(P, out, dir, k, &lds.f);
+  }
 }
 inline void launch_sc_check(const int16_t* xyz, int n, uint32_t* scal) { for (int i = 0; i < n; i++) if (!tc_in_range(xyz + 3 * (size_t)i)) scal[RBT_SC_ERR] = 1; }
 inline void launch_sc_index(const RbtScoreCloud* S, uint32_t* scal) {

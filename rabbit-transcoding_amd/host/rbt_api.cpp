@@ -206,6 +206,7 @@ struct SubmitExtras {
   bool per_frame = false; const rbt_frame_qp* lists = nullptr; const rbt_qp_map* maps = nullptr;
   const rbt_patch_floor_target* patches = nullptr;
   const rbt_patch_d1_target* d1_patches = nullptr;
+  const rbt_d2_target* d2 = nullptr; const rbt_patch_d2_target* d2_patches = nullptr;      // the D1 kinds with the D2 figure (check_d2, check_d2_patches)
 };
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x = SubmitExtras());
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
@@ -251,6 +252,7 @@ static int check_quality(std::string& err, int n, const rbt_stream_params* p, co
   }
   return RBT_OK;
 }
+static int normals_params(std::string& err, const rbt_normals_params* p, int* k, int* orient, int32_t vp[3]);
 // the refusals of rbt_submit_gof_d1 that the parameters alone decide (those that need the streams' sizes: gof_refused); req: the reference handles as clouds
 static int check_d1(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_d1_target* t, rbt::CloudRequest<rbt_d1_target>& req) {
   std::string& err = ctx->last_err;
@@ -368,6 +370,44 @@ static int check_d1_patches(rbt_ctx* ctx, int n, const rbt_stream_params* p, con
     if (int rc = fill_patch_request(err, "entry " + std::to_string(i) + ": ", p[i], t[i], t[i].min_d1_mdb, RBT_QUALITY_ALL, t[i].patch_min_d1_mdb, out[(size_t)i])) return rc;
   return check_d1(ctx, n, p, as_d1.data(), req);
 }
+// D2 floors: what a D2 target adds to the D1 target it is turned into - every given reference carries normals, and the record for the normals of the clouds of the
+// decoded input is a good one (struct_size 0 = all defaults)
+static int check_d2_side(rbt_ctx* ctx, const std::string& who, const rbt_pcloud* const* reference, int n_frames, const rbt_normals_params& np, rbt::NormalsIn& out) {
+  if (int rc = normals_params(ctx->last_err, np.struct_size ? &np : nullptr, &out.k, &out.orient, out.vp)) { ctx->last_err = who + ctx->last_err; return rc; }
+  for (int f = 0; reference && f < n_frames; f++) if (reference[f] && !rbt::pcloud_has_normals(reference[f]->cloud)) {
+    ctx->last_err = who + "reference " + std::to_string(f) + " carries no normals (D2 needs normals on the source)"; return RBT_ERR_PARAM; }
+  return RBT_OK;
+}
+// The refusals of rbt_submit_gof_d2: the target becomes the D1 target of the same fields (as_d1, min_d1_mdb holding the D2 floor) and takes check_d1's refusals with its
+// words; then the D2 side
+static int check_d2(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_d2_target* t, std::vector<rbt_d1_target>& as_d1, rbt::CloudRequest<rbt_d1_target>& req, std::vector<rbt::NormalsIn>& normals) {
+  as_d1.assign((size_t)n, rbt_d1_target()); normals.assign((size_t)n, rbt::NormalsIn());
+  for (int i = 0; i < n; i++) {
+    rbt_d1_target& d = as_d1[(size_t)i]; memset(&d, 0, sizeof(d)); d.struct_size = sizeof(d);
+    if (t[i].struct_size != sizeof(rbt_d2_target)) { ctx->last_err = "entry " + std::to_string(i) + ": rbt_d2_target.struct_size is not sizeof(rbt_d2_target)"; return RBT_ERR_PARAM; }
+    d.min_d1_mdb = t[i].min_d2_mdb; d.stat = t[i].stat; d.peak = t[i].peak; d.qp_min = t[i].qp_min; d.qp_max = t[i].qp_max; d.n_frames = t[i].n_frames; d.atlas = t[i].atlas;
+    d.patches = t[i].patches; d.n_patches = t[i].n_patches; d.reference = t[i].reference;
+  }
+  if (int rc = check_d1(ctx, n, p, as_d1.data(), req)) return rc;
+  for (int i = 0; i < n; i++) if (as_d1[(size_t)i].n_frames > 0)
+    if (int rc = check_d2_side(ctx, "entry " + std::to_string(i) + ": ", t[i].reference, t[i].n_frames, t[i].normals, normals[(size_t)i])) return rc;
+  return RBT_OK;
+}
+// ... and of rbt_submit_gof_d2_patches: the target becomes the rbt_patch_d1_target of the same fields and takes check_d1_patches' refusals; then the D2 side
+static int check_d2_patches(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_patch_d2_target* t, std::vector<rbt_patch_d1_target>& as_pd1, std::vector<rbt_d1_target>& as_d1,
+                            std::vector<rbt::PatchFloorIn>& out, rbt::CloudRequest<rbt_d1_target>& req, std::vector<rbt::NormalsIn>& normals) {
+  as_pd1.assign((size_t)n, rbt_patch_d1_target()); normals.assign((size_t)n, rbt::NormalsIn());
+  for (int i = 0; i < n; i++) {
+    rbt_patch_d1_target& d = as_pd1[(size_t)i]; memset(&d, 0, sizeof(d)); d.struct_size = sizeof(d);
+    if (t[i].struct_size != sizeof(rbt_patch_d2_target)) { ctx->last_err = "entry " + std::to_string(i) + ": rbt_patch_d2_target.struct_size is not sizeof(rbt_patch_d2_target)"; return RBT_ERR_PARAM; }
+    d.min_d1_mdb = t[i].min_d2_mdb; d.peak = t[i].peak; d.qp_min = t[i].qp_min; d.qp_max = t[i].qp_max; d.background_qp = t[i].background_qp; d.max_trials = t[i].max_trials; d.atlas = t[i].atlas;
+    d.n_frames = t[i].n_frames; d.patches = t[i].patches; d.n_patches = t[i].n_patches; d.patch_min_d1_mdb = t[i].patch_min_d2_mdb; d.reference = t[i].reference;
+  }
+  if (int rc = check_d1_patches(ctx, n, p, as_pd1.data(), as_d1, out, req)) return rc;
+  for (int i = 0; i < n; i++) if (as_d1[(size_t)i].n_frames > 0)
+    if (int rc = check_d2_side(ctx, "entry " + std::to_string(i) + ": ", t[i].reference, t[i].n_frames, t[i].normals, normals[(size_t)i])) return rc;
+  return RBT_OK;
+}
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
@@ -388,12 +428,15 @@ static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const si
   if (x.patches) { if (int rc = check_patch_floors(ctx->last_err, n, p, x.patches, patch_floors)) return rc; r.patch_floors = &patch_floors; }
   std::vector<rbt_d1_target> as_d1;
   if (x.d1_patches) { if (int rc = check_d1_patches(ctx, n, p, x.d1_patches, as_d1, patch_floors, d1)) return rc; r.patch_floors = &patch_floors; r.d1 = &d1; r.patch_d1 = true; }
+  std::vector<rbt_patch_d1_target> as_pd1; std::vector<rbt::NormalsIn> normals;
+  if (x.d2) { if (int rc = check_d2(ctx, n, p, x.d2, as_d1, d1, normals)) return rc; r.d1 = &d1; r.d2_normals = &normals; }
+  if (x.d2_patches) { if (int rc = check_d2_patches(ctx, n, p, x.d2_patches, as_pd1, as_d1, patch_floors, d1, normals)) return rc; r.patch_floors = &patch_floors; r.d1 = &d1; r.patch_d1 = true; r.d2_normals = &normals; }
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
   rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, r), ctx};
-  if (x.quality || x.d1 || x.color || x.lists || x.maps || x.patches || x.d1_patches) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
+  if (x.quality || x.d1 || x.color || x.lists || x.maps || x.patches || x.d1_patches || x.d2 || x.d2_patches) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -462,7 +505,7 @@ static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out,
   int slot = -1;
   for (int s = 0; s < RBT_MAX_JOBS; s++) if (D.jobs[s] == job) slot = s;
   if (slot < 0 || job->owner != ctx) return RBT_ERR_PARAM;
-  static const char* const names[] = {nullptr, "quality", "d1", "color", "d1_frames", "quality_frames", "quality_patches", "d1_patches"};      // per GofKind: rbt_submit_gof_<name>, rbt_wait_gof_<name>
+  static const char* const names[] = {nullptr, "quality", "d1", "color", "d1_frames", "quality_frames", "quality_patches", "d1_patches", "d2", "d2_patches"};      // per GofKind: rbt_submit_gof_<name>, rbt_wait_gof_<name>
   const rbt::GofKind is = rbt::gof_kind(job->j);
   if (is != kind) {      // the wait was called for a job of another kind / the job was handed to another wait
     const bool called = is == rbt::GOF_PLAIN || (kind != rbt::GOF_PLAIN && kind < is);
@@ -545,6 +588,32 @@ int rbt_transcode_gof_d1_patches(rbt_ctx* ctx, int n, const uint8_t* const* anne
                                  uint8_t** annexb_out, size_t* n_out, rbt_patch_d1_result* results) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !targets) return RBT_ERR_PARAM;      // (refused here, before submit would)
   return transcode(rbt_submit_gof_d1_patches, rbt_wait_gof_d1_patches, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
+// ---- D2 floors: on the stream and held patch by patch ----
+int rbt_submit_gof_d2(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d2_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  SubmitExtras x; x.d2 = targets; return submit(ctx, n, annexb_in, n_in, p, job, x);
+} RBT_CATCH
+int rbt_wait_gof_d2(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_d2_floor_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  rbt::GofResults r; r.d2 = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_D2, r);
+} RBT_CATCH
+int rbt_transcode_gof_d2(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_d2_target* targets,
+                         uint8_t** annexb_out, size_t* n_out, rbt_d2_floor_result* results) {
+  return transcode(rbt_submit_gof_d2, rbt_wait_gof_d2, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
+int rbt_submit_gof_d2_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d2_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  SubmitExtras x; x.d2_patches = targets; return submit(ctx, n, annexb_in, n_in, p, job, x);
+} RBT_CATCH
+int rbt_wait_gof_d2_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_patch_d2_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  rbt::GofResults r; r.d2_patches = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_D2_PATCHES, r);
+} RBT_CATCH
+int rbt_transcode_gof_d2_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d2_target* targets,
+                                 uint8_t** annexb_out, size_t* n_out, rbt_patch_d2_result* results) {
+  if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !targets) return RBT_ERR_PARAM;      // (refused here, before submit would)
+  return transcode(rbt_submit_gof_d2_patches, rbt_wait_gof_d2_patches, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
 }
 // ---- PSNR floors held patch by patch ----
 int rbt_submit_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_floor_target* targets, rbt_job** job) try {
@@ -889,6 +958,12 @@ int rbt_score_patches(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, in
   RBT_ENTER(ctx);
   if (!cloud_of(ctx, a) || !cloud_of(ctx, b)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
   return rbt::pcloud_score_patches(ctx->last_err, a->cloud, b->cloud, peak, n_patches, out, whole, device_ms);
+} RBT_CATCH
+int rbt_score_patches_d2(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int n_patches, rbt_patch_d2* out, rbt_d2_result* whole, double* device_ms) try {
+  if (!ctx || !out) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  if (!cloud_of(ctx, a) || !cloud_of(ctx, b)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
+  return rbt::pcloud_score_patches_d2(ctx->last_err, a->cloud, b->cloud, peak, n_patches, out, whole, device_ms);
 } RBT_CATCH
 static bool pair_of(const rbt_ctx* ctx, const rbt_score_pair* h) { return h && h->owner == ctx; }
 int rbt_score_pair_create(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, rbt_score_pair** out) try {

@@ -654,6 +654,55 @@ int pcloud_score_patches(std::string& err, const PCloud* a, const PCloud* b, int
   return RBT_OK;
 }
 
+bool pcloud_has_normals(const PCloud* c) { return c->nrm.p != nullptr; }
+// rbt_score_patches_d2: pcloud_score with RBT_SCORE_D2 - the same launches, so `whole` is its d2 bit for bit - and the per-patch sums on the distances and values it leaves
+int pcloud_score_patches_d2(std::string& err, const PCloud* a, const PCloud* b, int peak, int n_patches, rbt_patch_d2* out, rbt_d2_result* whole, double* device_ms) {
+  if (whole) memset(whole, 0, sizeof(*whole));
+  if (device_ms) *device_ms = 0;
+  if (peak <= 0) { err = "bad peak"; return RBT_ERR_PARAM; }
+  if (n_patches < 1 || n_patches > 65536) { err = "n_patches is 1..65536"; return RBT_ERR_PARAM; }
+  if (!b->labels.p) { err = "the decoded cloud carries no labels"; return RBT_ERR_PARAM; }
+  if (!a->nrm.p) { err = "D2 needs normals on the source"; return RBT_ERR_PARAM; }
+  memset(out, 0, sizeof(*out) * (size_t)n_patches);
+  const size_t na = (size_t)a->n, nb = (size_t)b->n, blocks = (std::max(na, nb) + RBT_SC_SUM - 1) / RBT_SC_SUM, words = (size_t)RBT_P2_WORDS * (size_t)n_patches;
+  const size_t ents = blocks * RBT_SC_SUM, cols = (size_t)n_patches * RBT_SC_SUM;
+  DevBuf dist, nrm_b, val, part, res, sums, bad, ent, S;
+  if (!dist.alloc(4 * (na + nb)) || !res.alloc(8 * RBT_SC_RESULTS) || !nrm_b.alloc(28 * nb) || !val.alloc(8 * (na + nb)) || !part.alloc(16 * blocks) || !sums.alloc(8 * words) || !bad.alloc(4) ||
+      !ent.alloc(12 * ents + 4 * blocks) || !S.alloc(8 * cols)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::dev_memset(res.p, 0, 8 * RBT_SC_RESULTS) | rbtk::dev_memset(nrm_b.p, 0, 28 * nb) | rbtk::dev_memset(sums.p, 0, 8 * words) | rbtk::dev_memset(bad.p, 0, 4) | rbtk::dev_memset(S.p, 0, 8 * cols)) {
+    err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  uint32_t is_bad = 0;                       // as pcloud_score_patches: labels a caller gave are checked on the device before any sum is written
+  if (b->label_bound <= 0 || b->label_bound > n_patches) {
+    rbtk::launch_pd_check(b->labels.as<uint32_t>(), b->n, (uint32_t)n_patches, bad.as<uint32_t>());
+    if (rbtk::d2h(&is_bad, bad.p, 4) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  }
+  if (is_bad) { err = "a label of the decoded cloud is not below n_patches"; return RBT_ERR_PARAM; }
+  RbtScoreWork W; memset(&W, 0, sizeof(W));
+  W.dist_a = dist.as<uint32_t>(); W.dist_b = W.dist_a + na; W.res = res.as<unsigned long long>();
+  W.acc_b = nrm_b.as<long long>(); W.cnt_b = (int32_t*)(W.acc_b + 3 * nb); W.val_ab = val.as<double>(); W.val_ba = W.val_ab + na; W.part = part.as<double>();
+  RbtPatchD2Work P; P.ent_sum = ent.as<double>(); P.ent_label = (uint32_t*)(P.ent_sum + ents); P.ent_n = P.ent_label + ents; P.S = S.as<double>();
+  const RbtScoreCloud A = a->view(), B = b->view();
+  rbtk::timer_begin(T_COL_DIST);             // as pcloud_score: every call reads its timers before it returns
+  rbtk::launch_sc_score(&A, &B, RBT_SCORE_D2, &W);
+  rbtk::launch_p2_sums(&A, &B, b->labels.as<uint32_t>(), &W, &P, n_patches, sums.as<unsigned long long>());
+  rbtk::timer_end(T_COL_DIST);
+  uint64_t h[RBT_SC_RESULTS]; std::vector<uint64_t> hw(words);
+  if (rbtk::d2h(h, res.p, sizeof(h)) || rbtk::d2h(hw.data(), sums.p, 8 * words) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (device_ms) *device_ms = rbtk::timer_ms(T_COL_DIST);
+  for (int k = 0; k < n_patches; k++) {
+    const uint64_t* w = &hw[(size_t)RBT_P2_WORDS * (size_t)k]; rbt_patch_d2* o = &out[k];
+    double v[4]; memcpy(&v[0], &w[RBT_P2_SSE_AB], 16); memcpy(&v[2], &w[RBT_P2_MAX_AB], 16);
+    o->n_ab = (uint32_t)w[RBT_P2_N_AB]; o->n_ba = (uint32_t)w[RBT_P2_N_BA]; o->sse_ab = v[0]; o->sse_ba = v[1]; o->max_ab = v[2]; o->max_ba = v[3];
+    patch_d2_finish(o, peak);
+  }
+  if (whole) {
+    double v[4]; memcpy(v, &h[RBT_SC_D2_AB], sizeof(v));
+    whole->n_a = a->n_merged; whole->n_b = b->n_merged; whole->sse_ab = v[0]; whole->max_ab = v[1]; whole->sse_ba = v[2]; whole->max_ba = v[3];
+    finish_geometry(whole, peak);
+  }
+  return RBT_OK;
+}
+
 struct ScorePair { const PCloud* a; const PCloud* b; int na, nb; DevBuf dist; };
 bool score_pair_uses(const ScorePair* p, const PCloud* c) { return p->a == c || p->b == c; }
 void score_pair_release(ScorePair* p) { delete p; }

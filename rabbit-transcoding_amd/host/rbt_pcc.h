@@ -56,6 +56,10 @@ int pcloud_set_labels(std::string& err, PCloud* c, const uint32_t* labels);
 int pcloud_labels(std::string& err, const PCloud* c, uint32_t* labels);
 bool pcloud_has_labels(const PCloud* c);
 int pcloud_score_patches(std::string& err, const PCloud* a, const PCloud* b, int peak, int n_patches, rbt_patch_d1* out, rbt_d1_result* whole, double* device_ms);
+// D2 per patch of the decoded cloud (csrc/rbt_score.h, "D2/patch"): a carries normals, b labels; out holds n_patches entries; whole (the d2 of pcloud_score with
+// RBT_SCORE_D2 for the two clouds) and device_ms may be null
+bool pcloud_has_normals(const PCloud* c);
+int pcloud_score_patches_d2(std::string& err, const PCloud* a, const PCloud* b, int peak, int n_patches, rbt_patch_d2* out, rbt_d2_result* whole, double* device_ms);
 // rbt_score_pair_*: the nearest squared distances of both directions between two indexed clouds, kept; pair_color runs the colour walks on them (out: what the colour
 // part of pcloud_score returns for the clouds' colours of the moment). The clouds must outlive the pair.
 struct ScorePair;

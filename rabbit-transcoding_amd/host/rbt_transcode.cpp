@@ -492,17 +492,17 @@ static int setup_encode(DecodeBatch& db, int si, int ei, const rbt_stream_params
 // underneath the previous GOF's reconstruction and re-encode.
 // Targets - a byte budget or a PSNR floor per entry -: what a pipeline with such an entry keeps between the rounds of its trial encodes (run_rounds, launch_round, finish_round)
 struct RoundCand { int q, qp, walk; int fw = -1; FramePass pass; int pw = -1; std::vector<int8_t> qmap; };   // entry q of the group at qp; walk: index of its walk, -1 for a constant-QP entry of the pipeline; fw >= 0: a pass of the entry's frame walks (qp: the entry's own, for the parameter sets)
-struct TargetTried : QualityTried { std::vector<rbt_d1_result> d1; std::vector<rbt_color_result> color; };      // d1 / color: a job with D1 / colour floors, the frames of the trial
+struct TargetTried : QualityTried { std::vector<rbt_d1_result> d1; std::vector<rbt_d2_result> d2; std::vector<rbt_color_result> color; };      // d1 / d2 / color: a job with D1 / D2 / colour floors, the frames of the trial
 // A budget (toward < 0) or a floor (toward > 0, rbt_floor_walk.h) - on the PSNR of `region` at bit_depth, on D1 or on the colour PSNR of `channel` of the clouds, stat over the frames
 enum WalkKind { WALK_BUDGET, WALK_PSNR, WALK_D1, WALK_COLOR };
-struct TargetWalk : QpWalk<TargetTried> { WalkKind kind = WALK_BUDGET; RateGoal budget; FloorGoal floor; int region = 0, bit_depth = 8, stat = RBT_D1_MIN, channel = 0; };
+struct TargetWalk : QpWalk<TargetTried> { WalkKind kind = WALK_BUDGET; RateGoal budget; FloorGoal floor; int region = 0, bit_depth = 8, stat = RBT_D1_MIN, channel = 0; bool d2 = false; };      // d2: a WALK_D1 on the D2 figure
 // Quality floors: the occupancy source of an entry (include/rbt.h, "transcoding to a PSNR floor", rule 3), kept in the job because the pipelines that use it are encoded in
 // the wait half: the pooled luma planes of the occupancy stream, and for occupancy_rd the per-4x4-unit maps made of them (both live in GofJob::pooled until the job goes)
 struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
 // Floors held patch by patch: the walk of one point-cloud frame (rbt_patch_walk.h) with what its last trial brought - the frame's NAL units, the sums of its two pictures,
-// the payload of the job's kind of figure (PatchPsnr or PatchD1, the other stays empty), the map it was coded with - and the walks of one entry: per frame R_k in CTB units
+// the payload of the job's kind of figure (PatchPsnr, PatchD1 or PatchD2, the others stay empty), the map it was coded with - and the walks of one entry: per frame R_k in CTB units
 // (the rectangles k_patch_fold reads, on the device from the first round to the last) and the displayed samples of R_k in both pictures
-struct PatchFrame { PatchWalk w; std::vector<uint8_t> stream; QualitySums sums; PatchPsnr psnr; PatchD1 d1; std::vector<int8_t> map; std::vector<int32_t> rects; std::vector<uint64_t> samples; size_t rect_off = 0; };
+struct PatchFrame { PatchWalk w; std::vector<uint8_t> stream; QualitySums sums; PatchPsnr psnr; PatchD1 d1; PatchD2 d2; std::vector<int8_t> map; std::vector<int32_t> rects; std::vector<uint64_t> samples; size_t rect_off = 0; };
 struct PatchWalks {
   int q = 0, entry = 0, n_passes = 0, l2 = 5, wc = 0, hc = 0, W = 0, H = 0, bit_depth = 8; std::vector<PatchFrame> frames; int32_t* d_rects = nullptr;
   bool settled() const { for (const PatchFrame& f : frames) if (!f.w.settled) return false; return true; }
@@ -529,6 +529,7 @@ struct RoundPipe {
   std::unique_ptr<EncodeBatch> eb; std::unique_ptr<SseSet> sse;   // the round in flight on the pipeline's stream; sse: a round of a job with floors carries distortion sums
   std::vector<std::vector<uint8_t>> o1; std::vector<QualitySums> sums;   // the pipeline's streams in group order, as they settle, and (floors) their sums
   std::vector<std::vector<rbt_d1_result>> d1;  // (D1 floors) the frames of the constant-QP entries with a target, in group order
+  std::vector<std::vector<rbt_d2_result>> d2;  // (D2 floors) the same
   std::vector<std::vector<rbt_color_result>> color;   // (colour floors) the same
   bool done = false;
 };
@@ -549,7 +550,7 @@ template <class Result> struct FloorOut { int qp = 0, q0 = 0, qs = 0, met = 0, n
 // settling trial, and every frame's picks back to back. An entry without a target has no frames: q0, bytes, bit_depth and sums are those of its only encode
 struct PatchOut {
   int q0 = 0, n_passes = 0, wc = 0, hc = 0, bit_depth = 8, region = 0; uint64_t bytes = 0, pictures = 0; std::vector<int8_t> map; QualitySums sums; double cloud_ms = 0;
-  struct Frame { int n_trials = 0, met = 1, n_patches = 0; uint64_t bytes = 0; PatchPsnr psnr; PatchD1 d1; }; std::vector<Frame> frames;
+  struct Frame { int n_trials = 0, met = 1, n_patches = 0; uint64_t bytes = 0; PatchPsnr psnr; PatchD1 d1; PatchD2 d2; }; std::vector<Frame> frames;
   struct Pick { int qp, met, failed; double figure; }; std::vector<Pick> picks;
 };
 struct FrameFloorOut { int q0 = 0, n_passes = 0, bit_depth = 8; std::vector<rbt_frame_pick> frames; std::vector<rbt_d1_result> d1; double cloud_ms = 0; uint64_t bytes = 0, pictures = 0; QualitySums sums; };
@@ -591,6 +592,9 @@ struct GofJob {
   // D1 floors held patch by patch (rbt_submit_gof_d1_patches): such a job with the figures taken from the trial's cloud - d1 holds the targets' clouds' side as in a job
   // with D1 floors (no walk of its own: min_d1_mdb 0), every pass is scored by d1_score patch by patch (PatchFrame::d1), no sums per CTB run
   bool patch_d1 = false;
+  // D2 floors (rbt_submit_gof_d2, rbt_submit_gof_d2_patches): a job with D1 floors, on the stream or patch by patch, whose figure is D2 - d1 holds the targets (min_d1_mdb:
+  // the D2 floor), d1_score asks for the D2 part too, the reference clouds made of the decoded input get normals in d1_setup (normals: one record per entry)
+  bool d2 = false; std::vector<NormalsIn> normals; std::vector<FloorOut<rbt_d2_result>> d2out;
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   void color_release(int entry) {        // the frames' volumes go back to the context's cache; their streams have been waited for
     ColorEntry& E = color[entry];
@@ -879,7 +883,7 @@ static void walk_goal(TargetWalk& w, const rbt_d1_target& t) { w.kind = WALK_D1;
 static void walk_goal(TargetWalk& w, const rbt_color_target& t) { w.kind = WALK_COLOR; w.floor.floor_mdb = t.min_psnr_mdb; w.stat = t.stat; w.channel = t.channel; }
 template <class Target> static TargetWalk floor_walk(const GofJob& j, int gi, size_t q, const Target& t, bool pinned = false) {
   const int i = j.groups[gi][q], qp = j.params[i].qp;
-  TargetWalk w = new_walk(q, i, t); walk_goal(w, t); w.bit_depth = entry_bit_depth(j, gi, q);
+  TargetWalk w = new_walk(q, i, t); walk_goal(w, t); w.bit_depth = entry_bit_depth(j, gi, q); w.d2 = j.d2 && w.kind == WALK_D1;
   if (pinned) w.lo = w.hi = std::min(51, std::max(0, qp));
   floor_seed(w, w.floor, qp);
   return w;
@@ -911,9 +915,9 @@ static void seed_frame_floors(GofJob& j, int gi, RoundPipe& r) {
 static bool walk_step(TargetWalk& w, int& need, int& dir, bool& alone) {
   alone = false;
   if (w.kind == WALK_BUDGET) return qp_walk_step(w, rate_fits(w, w.budget), need, dir);
-  auto figure = [&w](const TargetTried& t) { return w.kind == WALK_D1 ? d1_figure(t.d1, w.stat) : w.kind == WALK_COLOR ? color_figure(t.color, w.stat, w.channel) : quality_region_psnr(t.sums, w.region, w.bit_depth); };
+  auto figure = [&w](const TargetTried& t) { return w.d2 ? d1_figure(t.d2, w.stat) : w.kind == WALK_D1 ? d1_figure(t.d1, w.stat) : w.kind == WALK_COLOR ? color_figure(t.color, w.stat, w.channel) : quality_region_psnr(t.sums, w.region, w.bit_depth); };
   auto meets = [&w](const TargetTried& t) {
-    return w.kind == WALK_D1 ? d1_meets(t.d1, w.stat, w.floor.floor_mdb) : w.kind == WALK_COLOR ? color_meets(t.color, w.stat, w.channel, w.floor.floor_mdb) : quality_meets(t.sums, w.region, w.floor.floor_mdb, w.bit_depth);
+    return w.d2 ? d1_meets(t.d2, w.stat, w.floor.floor_mdb) : w.kind == WALK_D1 ? d1_meets(t.d1, w.stat, w.floor.floor_mdb) : w.kind == WALK_COLOR ? color_meets(t.color, w.stat, w.channel, w.floor.floor_mdb) : quality_meets(t.sums, w.region, w.floor.floor_mdb, w.bit_depth);
   };
   alone = !floor_probe(w, w.floor, figure);
   if (alone) { need = w.floor.q0; dir = 0; return false; }
@@ -1187,6 +1191,7 @@ static int d1_setup(GofJob& j, int gi) {
       MapFrame* F = nullptr;
       rc = mapframe_new(j.err, &ain, E.patches[f].data(), (int)E.patches[f].size(), occ.p + os * (size_t)f, &F);
       if (!rc) rc = mapframe_cloud(j.err, cache, F, geo.p + ys * (size_t)(mc * f), mc > 1 ? geo.p + ys * (size_t)(mc * f + 1) : nullptr, bd, &E.own_ref[f], nullptr);
+      if (!rc && j.d2) { const NormalsIn& N = j.normals[(size_t)i]; rc = pcloud_estimate_normals(j.err, E.own_ref[f], N.k, N.orient, N.vp, nullptr, nullptr); }      // D2: once per job, kept with the cloud
       if (rbtk::dev_sync() && !rc) { j.err = "kernel execution failed"; rc = RBT_ERR_NO_DEVICE; }      // F's buffers are idle before they go
       mapframe_delete(F);
     }
@@ -1210,7 +1215,10 @@ struct D1Live {
 // reconstructions (the displayed window starts at the picture's origin: make_param_sets pads at the right and at the bottom) is gathered into packed planes by one launch,
 // then frame after frame: cloud, index, search, release (one recycled volume). The round's encode has been waited for (encode_finish).
 // per_patch (D1 floors held patch by patch): per frame of the pass the figures of its patches too - rbt_score_patches in place of the D1 part of rbt_score, out unchanged
-static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, std::vector<rbt_d1_result>& out, std::vector<std::vector<rbt_patch_d1>>* per_patch = nullptr) {
+// A job with D2 floors: g2->whole receives the frames' D2 - rbt_score with RBT_SCORE_D2, whose D1 part still fills out - or, patch by patch, rbt_score_patches_d2's
+// whole with g2->patches its figures per patch (out then stays zero: the kind reports no D1)
+struct CloudScoresD2 { std::vector<rbt_d2_result> whole; std::vector<std::vector<rbt_patch_d2>> patches; };
+static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, std::vector<rbt_d1_result>& out, std::vector<std::vector<rbt_patch_d1>>* per_patch = nullptr, CloudScoresD2* g2 = nullptr) {
   const int i = j.groups[gi][q]; D1Entry& E = j.d1[i]; const rbt_atlas_params& a = E.t.atlas; PCloudCache& cache = *j.cloud_cache;
   const EncStreamDesc& d = eb.desc[e]; const int W = a.width, H = a.height, mc = a.map_count, nf = E.t.n_frames, peak = E.t.peak ? E.t.peak : 1023;
   const size_t ys = (size_t)W * H;
@@ -1222,16 +1230,25 @@ static int d1_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, s
   if (!geo.alloc(ys * (size_t)d.n_frames)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
   out.assign(np, rbt_d1_result());
   if (per_patch) per_patch->assign((size_t)np, {});
+  if (j.d2 && !g2) { j.err = "internal: a D2 job scored without its figure"; return RBT_ERR_PARAM; }
+  if (g2) { g2->whole.assign((size_t)np, rbt_d2_result()); g2->patches.assign((size_t)np, {}); }
   rbtk::timer_begin(T_CENSUS);
   gs.add_coded(eb, e, W, H, geo.p);
   int rc = gs.launch(j.err);
   for (int i = 0; i < np && !rc; i++) {
     const int f = d.pic.empty() ? i : d.pic[(size_t)(mc * i)] / mc; PCloud* c = nullptr;
     rc = mapframe_cloud(j.err, cache, E.frames[f], geo.p + ys * (size_t)(mc * i), mc > 1 ? geo.p + ys * (size_t)(mc * i + 1) : nullptr, d.bd, &c, nullptr);
-    if (!rc && per_patch) {
+    const PCloud* A = E.ref[f] ? E.ref[f] : E.own_ref[f];
+    if (!rc && g2 && per_patch) {
+      std::vector<rbt_patch_d2>& pp = g2->patches[(size_t)i]; pp.resize(E.patches[f].size());
+      rc = pcloud_score_patches_d2(j.err, A, c, peak, (int)pp.size(), pp.data(), &g2->whole[(size_t)i], nullptr);
+    } else if (!rc && g2) {
+      rbt_frame_score s; rc = pcloud_score(j.err, A, c, peak, RBT_SCORE_D2, &s);
+      out[i] = s.d1; g2->whole[(size_t)i] = s.d2;
+    } else if (!rc && per_patch) {
       std::vector<rbt_patch_d1>& pp = (*per_patch)[(size_t)i]; pp.resize(E.patches[f].size());
-      rc = pcloud_score_patches(j.err, E.ref[f] ? E.ref[f] : E.own_ref[f], c, peak, (int)pp.size(), pp.data(), &out[i], nullptr);
-    } else if (!rc) rc = pcloud_d1(j.err, E.ref[f] ? E.ref[f] : E.own_ref[f], c, peak, &out[i]);
+      rc = pcloud_score_patches(j.err, A, c, peak, (int)pp.size(), pp.data(), &out[i], nullptr);
+    } else if (!rc) rc = pcloud_d1(j.err, A, c, peak, &out[i]);
     pcloud_release(cache, c);
   }
   return cloud_timed(j, E, rc);
@@ -1389,10 +1406,12 @@ static int finish_round(GofJob& j, int gi) {
     if (c.pw >= 0) {      // a pass of patch walks: every frame it carried keeps this trial - NAL units, sums, payload, map - and takes the walk's step on what the trial said
       PatchWalks& pw = r.pwalks[(size_t)c.pw]; const int region = j.patch[pw.entry].region; const size_t per = (size_t)pw.wc * pw.hc;
       std::vector<rbt_d1_result> whole; std::vector<std::vector<rbt_patch_d1>> clouds;      // D1 floors: the clouds of the frames the pass carried, in pass order, patch by patch
-      if (j.patch_d1) if (int rc = d1_score(j, gi, c.q, *r.eb, e, whole, &clouds)) return rc;
+      CloudScoresD2 g2;                                                // D2 floors: the same of the D2 figure
+      if (j.patch_d1) if (int rc = d1_score(j, gi, c.q, *r.eb, e, whole, &clouds, j.d2 ? &g2 : nullptr)) return rc;
       // the pass's figure source (rbt_patch_walk.h): frame i of the pass from its cloud, or from its fold words, which lie in pass order behind the words per picture
       PatchTrial said;
       auto figures = [&](size_t i, PatchFrame& F) {
+        if (j.patch_d1 && j.d2) { patch_trial_d2(g2.patches[i], g2.whole[i], F.w.floor_mdb, said, F.d2); return; }
         if (j.patch_d1) { patch_trial_d1(clouds[i], whole[i], F.w.floor_mdb, said, F.d1); return; }
         patch_trial_psnr(&r.eb->sums[fold_at], F.samples, region, pw.bit_depth, F.w.floor_mdb, said, F.psnr);
         fold_at += (F.samples.size() + 2) * RBT_CTBSSE_WORDS;
@@ -1425,14 +1444,15 @@ static int finish_round(GofJob& j, int gi) {
     }
     for (int k = 0; r.sse && k < d.n_frames; k++, at++) quality_add_picture(sums, &r.eb->sums[at * RBT_SSE_WORDS], d.w, d.h);
     std::vector<rbt_d1_result> frames;                                // a D1 target: the candidate's clouds, from its reconstruction while the round's arena is alive
-    if (has_d1(j, j.groups[gi][c.q])) if (int rc = d1_score(j, gi, c.q, *r.eb, e, frames)) return rc;
+    CloudScoresD2 g2;                                                 // a D2 target: the same clouds' D2
+    if (has_d1(j, j.groups[gi][c.q])) if (int rc = d1_score(j, gi, c.q, *r.eb, e, frames, nullptr, j.d2 ? &g2 : nullptr)) return rc;
     std::vector<rbt_color_result> cframes;                            // a colour target: the candidate's clouds, recoloured from its reconstruction
     if (!j.color.empty()) {
       if (has_color(j, j.groups[gi][c.q])) { if (int rc = color_score(j, gi, c.q, *r.eb, e, cframes)) return rc; }
       else if (c.walk < 0) if (int rc = color_geometry(j, gi, c.q, *r.eb, e)) return rc;      // a geometry source: the geometry half of its clouds, behind its only encode
     }
-    if (c.walk < 0) { r.o1[c.q].swap(outs[e]); r.sums[c.q] = sums; r.d1[c.q].swap(frames); r.color[c.q].swap(cframes); }
-    else { TargetTried& t = r.walks[c.walk].tried[c.qp]; t.stream.swap(outs[e]); t.sums = sums; t.d1.swap(frames); t.color.swap(cframes); r.n_enc[c.walk]++; }
+    if (c.walk < 0) { r.o1[c.q].swap(outs[e]); r.sums[c.q] = sums; r.d1[c.q].swap(frames); r.d2[c.q].swap(g2.whole); r.color[c.q].swap(cframes); }
+    else { TargetTried& t = r.walks[c.walk].tried[c.qp]; t.stream.swap(outs[e]); t.sums = sums; t.d1.swap(frames); t.d2.swap(g2.whole); t.color.swap(cframes); r.n_enc[c.walk]++; }
   }
   r.eb.reset(); r.sse.reset(); r.ctbsse.reset();
   name_round(j, gi, r, false);
@@ -1490,6 +1510,7 @@ static void fill_results(GofJob& j, int gi) {
     else if (w.kind == WALK_PSNR) quality_fill_result(j.qresults[w.entry], w.qstar, w.floor.q0, w.start, w.met, r.n_enc[k], t.stream.size(), t.sums, w.bit_depth);
   }
   fill_cloud_outs(j, gi, j.d1, j.d1out, WALK_D1, r.d1, &TargetTried::d1);
+  if (j.d2) fill_cloud_outs(j, gi, j.d1, j.d2out, WALK_D1, r.d2, &TargetTried::d2);
   fill_cloud_outs(j, gi, j.color, j.colorout, WALK_COLOR, r.color, &TargetTried::color);
 }
 // ... and of a pipeline whose entries walked frame by frame: per frame q*, qs, met, its encodes, its bytes and its figure at q*; the stream assembled from the passes
@@ -1524,7 +1545,7 @@ static void fill_patch_results(GofJob& j, int gi) {
     for (const PatchFrame& F : pw.frames) {
       out.insert(out.end(), F.stream.begin(), F.stream.end()); o.map.insert(o.map.end(), F.map.begin(), F.map.end());
       o.q0 = F.w.q0; o.pictures += 2 * (uint64_t)F.w.n_trials;
-      PatchOut::Frame pf; pf.n_trials = F.w.n_trials; pf.n_patches = (int)F.w.q.size(); pf.bytes = F.stream.size(); pf.psnr = F.psnr; pf.d1 = F.d1;
+      PatchOut::Frame pf; pf.n_trials = F.w.n_trials; pf.n_patches = (int)F.w.q.size(); pf.bytes = F.stream.size(); pf.psnr = F.psnr; pf.d1 = F.d1; pf.d2 = F.d2;
       for (size_t k = 0; k < F.w.q.size(); k++) { pf.met &= F.w.met[k]; o.picks.push_back(PatchOut::Pick{F.w.q[k], F.w.met[k], F.w.failed[k], F.w.figure[k]}); }
       o.frames.push_back(std::move(pf));
       for (int c = 0; c < 3; c++) { o.sums.sse[c] += F.sums.sse[c]; o.sums.samples[c] += F.sums.samples[c]; o.sums.sse_occ[c] += F.sums.sse_occ[c]; o.sums.samples_occ[c] += F.sums.samples_occ[c]; }
@@ -1543,13 +1564,13 @@ static int run_rounds(GofJob& j, int gi) {
   ColorLive color_live{j, gi};                                      // (releases the frames of the pipeline's colour entries on every way out)
   if (!j.patch.empty()) { if (int rc = seed_patch_walks(j, gi, r)) return rc; }
   else if (j.per_frame) seed_frame_floors(j, gi, r);
-  else if (j.kind == GOF_D1) seed_floors(j, gi, r, WALK_D1);
+  else if (j.kind == GOF_D1 || j.kind == GOF_D2) seed_floors(j, gi, r, WALK_D1);
   else if (j.kind == GOF_COLOR) seed_floors(j, gi, r, WALK_COLOR);
   else if (j.kind == GOF_QUALITY) seed_floors(j, gi, r, WALK_PSNR);
   else if (int rc = seed_budgets(j, gi, r, true)) return rc;
   if (!j.d1.empty()) if (int rc = d1_setup(j, gi)) return rc;
   if (!j.color.empty()) if (int rc = color_setup(j, gi)) return rc;
-  r.o1.assign(n, {}); r.sums.assign(n, QualitySums()); r.d1.assign(n, {}); r.color.assign(n, {}); r.n_enc.assign(r.walks.size(), 0);
+  r.o1.assign(n, {}); r.sums.assign(n, QualitySums()); r.d1.assign(n, {}); r.d2.assign(n, {}); r.color.assign(n, {}); r.n_enc.assign(r.walks.size(), 0);
   name_round(j, gi, r, true);
   for (;;) {
     if (int rc = launch_round(j, gi)) return rc;
@@ -1770,7 +1791,9 @@ GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   const int n = r.n; const rbt_stream_params* p = r.params;
   j.per_frame = r.per_frame && (r.quality || r.d1);
   j.patch_d1 = r.patch_d1 && r.patch_floors && r.d1;
-  j.kind = j.patch_d1 ? GOF_D1_PATCHES : r.patch_floors ? GOF_QUALITY_PATCHES : r.color ? GOF_COLOR : r.d1 ? (j.per_frame ? GOF_D1_FRAMES : GOF_D1) : r.quality ? (j.per_frame ? GOF_QUALITY_FRAMES : GOF_QUALITY) : GOF_PLAIN;
+  j.d2 = r.d2_normals && r.d1 && !j.per_frame;
+  if (j.d2) j.normals = *r.d2_normals;
+  j.kind = j.d2 ? (j.patch_d1 ? GOF_D2_PATCHES : GOF_D2) : j.patch_d1 ? GOF_D1_PATCHES : r.patch_floors ? GOF_QUALITY_PATCHES : r.color ? GOF_COLOR : r.d1 ? (j.per_frame ? GOF_D1_FRAMES : GOF_D1) : r.quality ? (j.per_frame ? GOF_QUALITY_FRAMES : GOF_QUALITY) : GOF_PLAIN;
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
   j.params.assign(p, p + n); j.n_in.assign(r.n_in, r.n_in + n);
@@ -1817,7 +1840,7 @@ struct HandOver {
 // the result arrays whose entries carry arrays of their own, zeroed: before anything is filled in, and again when everything is taken back
 static void zero_results(const GofResults& r, int n) {
   auto zero = [n](auto* a) { if (a) memset(a, 0, sizeof(*a) * (size_t)n); };
-  zero(r.d1); zero(r.color); zero(r.frames); zero(r.patches); zero(r.d1_patches);
+  zero(r.d1); zero(r.color); zero(r.frames); zero(r.patches); zero(r.d1_patches); zero(r.d2); zero(r.d2_patches);
 }
 // The public results of a job with cloud targets: per entry its own QP and one encode, or what the rounds left of an entry with a target (FloorOut) with the statistics
 // over its frames
@@ -1837,6 +1860,7 @@ template <class Entry, class Result, class Public, class Stats> static void clou
 // (PatchOut) - the header, the final map, the frames and their picks, every frame pointing at its own. What a kind adds to the result, to a frame and to its picks:
 static void patch_payload(rbt_patch_floor_result& o, const PatchOut& r, int met, int n_enc) { quality_fill_result(o.sums, -1, -1, -1, met, n_enc, o.bytes, r.sums, r.bit_depth); }
 static void patch_payload(rbt_patch_d1_result& o, const PatchOut& r, int, int) { o.cloud_ms = r.cloud_ms; }
+static void patch_payload(rbt_patch_d2_result& o, const PatchOut& r, int, int) { o.cloud_ms = r.cloud_ms; }
 static void patch_payload(rbt_patch_frame& o, rbt_patch_pick* picks, const PatchOut& r, const PatchOut::Frame& f) {
   for (int c = 0; c < 3; c++) o.background[c] = f.psnr.background[c];
   for (size_t k = 0; k < f.psnr.patches.size(); k++) { const PatchSums& s = f.psnr.patches[k]; picks[k].sse = r.region ? s.sse_occ : s.sse; picks[k].samples = r.region ? s.samples_occ : s.samples; }
@@ -1844,6 +1868,10 @@ static void patch_payload(rbt_patch_frame& o, rbt_patch_pick* picks, const Patch
 static void patch_payload(rbt_patch_d1_frame& o, rbt_patch_d1_pick* picks, const PatchOut&, const PatchOut::Frame& f) {
   o.d1 = f.d1.whole;
   for (size_t k = 0; k < f.d1.patches.size(); k++) picks[k].d1 = f.d1.patches[k];
+}
+static void patch_payload(rbt_patch_d2_frame& o, rbt_patch_d2_pick* picks, const PatchOut&, const PatchOut::Frame& f) {
+  o.d2 = f.d2.whole;
+  for (size_t k = 0; k < f.d2.patches.size(); k++) picks[k].d2 = f.d2.patches[k];
 }
 template <class Public> static void patch_results(const GofJob& j, HandOver& h, Public* res, const size_t* n_out) {
   typedef typename std::remove_pointer<decltype(res->frames)>::type Frame; typedef typename std::remove_pointer<decltype(res->picks)>::type Pick;
@@ -1925,6 +1953,8 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResult
   }
   if (res.patches) patch_results(j, h, res.patches, n_out);
   if (res.d1_patches) patch_results(j, h, res.d1_patches, n_out);
+  if (res.d2_patches) patch_results(j, h, res.d2_patches, n_out);
+  if (res.d2) cloud_results(j, h, j.d1, j.d2out, res.d2, n_out, [](rbt_d2_floor_result& o, const rbt_d2_result* f) { d1_stats(f, o.n_frames, &o.mean_d2, &o.min_d2); });
   if (d1results) cloud_results(j, h, j.d1, j.d1out, d1results, n_out, [](rbt_d1_floor_result& o, const rbt_d1_result* f) { d1_stats(f, o.n_frames, &o.mean_d1, &o.min_d1); });
   if (cresults) cloud_results(j, h, j.color, j.colorout, cresults, n_out, [](rbt_color_floor_result& o, const rbt_color_result* f) { color_stats(f, o.n_frames, o.mean_psnr, o.min_psnr); });
   rc = h.rc;

@@ -9,6 +9,8 @@ struct PCloud; struct PCloudCache;
 // the cloud targets of rbt_submit_gof_d1 / rbt_submit_gof_color (Target: rbt_d1_target / rbt_color_target), checked by the caller: one per entry, the reference handles of each
 // entry resolved to the clouds (n_frames of them, nullptr = the cloud of the decoded input), and the context's cache of cloud volumes
 template <class Target> struct CloudRequest { const Target* targets = nullptr; std::vector<std::vector<const PCloud*>> refs; PCloudCache* cache = nullptr; };
+// D2 floors: the checked form of an entry's rbt_normals_params, for the clouds of the decoded input (rbt_pcloud_estimate_normals' arguments)
+struct NormalsIn { int k = 16, orient = RBT_NORMALS_ORIENT_VIEW_POINT; int32_t vp[3] = {0, 0, 0}; };
 struct QpMapIn { std::vector<int8_t> qp; int n_frames = 0, w_ctb = 0, h_ctb = 0; };
 // Floors held patch by patch (rbt_submit_gof_quality_patches, rbt_submit_gof_d1_patches), one request per entry, checked and copied by the caller from its own target type: what
 // the walks read - the floor where a patch has none of its own, the region of the PSNR figure (RBT_QUALITY_ALL for D1), the QP range, the background's QP (-1 = q0), the cap on
@@ -36,16 +38,20 @@ struct GofRequest {
   // D1 floors held patch by patch (rbt_submit_gof_d1_patches): patch_floors carries the walks' side of the targets (floors, range, background, cap) and d1 their clouds'
   // side (atlas, patch lists, references, peak; min_d1_mdb 0: no walk of its own)
   bool patch_d1 = false;
+  // D2 floors (rbt_submit_gof_d2; with patch_d1: rbt_submit_gof_d2_patches): the request is that of the D1 kind - d1 carries the targets as D1 targets, min_d1_mdb holding
+  // the D2 floor - and the figure is D2; one record per entry for the normals of the reference clouds made of the decoded input
+  const std::vector<NormalsIn>* d2_normals = nullptr;
 };
 // Where a job's outcome goes: a stream per entry, and of the result arrays - one per entry each - the one of the job's kind; n_flat: nullptr, or the decoded pictures with flat chroma
 struct GofResults {
   uint8_t** out = nullptr; size_t* n_out = nullptr; int* n_flat = nullptr;
   rbt_rate_result* rate = nullptr; rbt_quality_result* quality = nullptr; rbt_d1_floor_result* d1 = nullptr; rbt_color_floor_result* color = nullptr; rbt_frame_floor_result* frames = nullptr; rbt_patch_floor_result* patches = nullptr; rbt_patch_d1_result* d1_patches = nullptr;
+  rbt_d2_floor_result* d2 = nullptr; rbt_patch_d2_result* d2_patches = nullptr;
 };
 GofJob* gof_submit(int slot, int depth, const GofRequest& r);
 int gof_wait(GofJob* j, rbt_stats& st, std::string& err, const GofResults& r);   // consumes the job
 // which submit made the job, in the order the wait half tells a mismatch (rbt_api.cpp wait): the lower of two kinds that differ is the one the message names
-enum GofKind { GOF_PLAIN, GOF_QUALITY, GOF_D1, GOF_COLOR, GOF_D1_FRAMES, GOF_QUALITY_FRAMES, GOF_QUALITY_PATCHES, GOF_D1_PATCHES };   // GOF_PLAIN: constant QPs, QP lists, QP maps and byte budgets
+enum GofKind { GOF_PLAIN, GOF_QUALITY, GOF_D1, GOF_COLOR, GOF_D1_FRAMES, GOF_QUALITY_FRAMES, GOF_QUALITY_PATCHES, GOF_D1_PATCHES, GOF_D2, GOF_D2_PATCHES };   // GOF_PLAIN: constant QPs, QP lists, QP maps and byte budgets
 GofKind gof_kind(const GofJob* j);
 int gof_refused(const GofJob* j, std::string& err);   // != 0: the job's plan was refused before anything was built or enqueued (the code; the reason in err)
 void gof_abandon(GofJob* j);
