@@ -732,7 +732,7 @@ void rbt_score_pair_release(rbt_ctx* ctx, rbt_score_pair* pair);
  * all the same, so the words do not depend on the order of arrival and two calls return the same bits). RBT_ERR_PARAM, with the reason in rbt_last_error and the context
  * still usable: a handle of another context, b without labels, a label >= n_patches (a kernel checks the labels and reports through an error word before any sum is
  * written), n_patches outside 1..65536, peak < 1.
- * The closed loop on these figures: "D1 floors held patch by patch" below. Not built: colour figures per patch. */
+ * The closed loop on these figures: "D1 floors held patch by patch" below. (Colour figures per patch: "colour PSNR per patch of the decoded cloud" below.) */
 typedef struct { uint32_t n_ab, n_ba; uint64_t sse_ab, sse_ba, max_ab, max_ba; float mse_ab, mse_ba, psnr; } rbt_patch_d1;
 int rbt_pcloud_set_labels(rbt_ctx* ctx, rbt_pcloud* cloud, const uint32_t* labels);        /* one per point, < 65536 */
 int rbt_pcloud_labels(rbt_ctx* ctx, const rbt_pcloud* cloud, uint32_t* labels);            /* of rbt_pcloud_from_maps: the patch index; RBT_ERR_PARAM for a cloud without labels */
@@ -757,9 +757,34 @@ int rbt_score_patches(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, in
  * 12 bytes per point of the larger cloud rounded up to a multiple of 256, 4 bytes per 256 points of it, and 2 KB + 48 bytes per patch - it grows with points + patches,
  * never with patches x blocks. RBT_ERR_PARAM, with the reason in rbt_last_error and the context still usable: those of rbt_score_patches (a handle of another context, b
  * without labels, a label >= n_patches - checked by a kernel before any sum is written -, n_patches outside 1..65536, peak < 1) and a without normals.
- * The closed loops on these figures: "D2 floors" below. Not built: colour figures per patch. */
+ * The closed loops on these figures: "D2 floors" below. (Colour figures per patch: the next section.) */
 typedef struct { uint32_t n_ab, n_ba; double sse_ab, sse_ba, max_ab, max_ba; float mse_ab, mse_ba, psnr; } rbt_patch_d2;
 int rbt_score_patches_d2(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int peak, int n_patches, rbt_patch_d2* out, rbt_d2_result* whole, double* device_ms);
+/* ---- colour PSNR per patch of the decoded cloud (csrc/rbt_score.h) ----
+ * A is the reference and B the decoded cloud with one label L[j] per point, as for rbt_score_patches; both carry colours. Merging, representatives, tie sets, the rounded
+ * mean tie colour and the three error terms e[0..2] (Y, U, V) of a representative are rbt_score's with RBT_SCORE_COLOR, unchanged (rbt_color_metric above). Only the
+ * attribution is new, and it is that of D1 per patch. Per patch k, with exact integers:
+ *   B -> A   a representative j of B belongs to patch L[j]: n_ba[k] counts the representatives of patch k, sse_ba[c][k] is the sum of e[c]^2 over them.
+ *   A -> B   a representative i of A belongs to the label of its owner, the lowest point index among B's merged points at exactly i's nearest distance. n_ab[k] and
+ *            sse_ab[c][k] are taken over the i whose owner has label k: the counts are rbt_score_patches' counts for the same pair.
+ *   figure   mse_*[c][k] = (float)(sse / (2550000^2 n)) and psnr = 10 log10f(1 / mse), from the one float routine rbt_color_metric and rbt_score use. A direction without
+ *            a point has mse 0. mse[c] is the larger and psnr[c] the smaller of the two directions; a patch without a point in either direction has psnr +inf.
+ * All relations are exact - the sums are integers: over k, sse_ab[c], sse_ba[c], n_ab and n_ba add up to the whole's sse_ab[c], sse_ba[c], n_a and n_b; with n_patches = 1
+ * patch 0 is the whole, float fields included; two calls return the same bits, and so does the serial host emulation.
+ * rbt_score_patches_color: the two searches of rbt_score, then k_pc_sums once per direction in place of the colour walks - one lane per point, one walk over the tie set
+ * that yields the tie colour sums and the owner, eight 64-bit words per patch (three sums and a count per direction), integer atomics only, one per wave and non-zero word
+ * where a wave's labels are all the same. whole (may be NULL) is made on the host from the per-patch words through the same float routine: bit for bit
+ * rbt_score(a, b, peak, RBT_SCORE_COLOR).color for any peak. device_ms (may be NULL): the time between events around the searches and the two launches.
+ * rbt_score_pair_patches_color: the same on the distances a score pair keeps, with the colours and labels the clouds have at that moment: no search runs; whole is bit for
+ * bit rbt_score_pair_color(pair), out is rbt_score_patches_color's, before and after rbt_pcloud_set_colors on either cloud. Scratch: 64 bytes per patch beside what the
+ * score or the pair holds.
+ * RBT_ERR_PARAM, with the reason in rbt_last_error and the context still usable: a handle or pair of another context, a pair one of whose clouds has been released, a cloud
+ * without colours, b without labels, a label >= n_patches (k_pd_check reports through an error word before any sum is written), n_patches outside 1..65536, more than
+ * 2^21 merged points in a cloud.
+ * The closed loop on these figures: "colour floors held patch by patch" at the end of this header. */
+typedef struct { uint32_t n_ab, n_ba; uint64_t sse_ab[3], sse_ba[3]; float mse_ab[3], mse_ba[3], mse[3], psnr[3]; } rbt_patch_color;
+int rbt_score_patches_color(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int n_patches, rbt_patch_color* out, rbt_color_result* whole, double* device_ms);
+int rbt_score_pair_patches_color(rbt_ctx* ctx, const rbt_score_pair* pair, int n_patches, rbt_patch_color* out, rbt_color_result* whole);
 /* Summary over the frames of a sequence, per figure (the symmetric PSNR of D1, D2, Y, U, V): arithmetic mean and minimum, in double, over the frames that carry that part
  * (n_d1 / n_d2 / n_color of them; 0 where there is none); a frame whose PSNR is +inf makes the mean +inf. The reference itself writes one line per frame and averages
  * nothing (PCCMetrics::write); the mean over the frames is what the CTC reporting forms from those lines. points_* / merged_*: sums over all frames. Host only. */
@@ -950,7 +975,7 @@ int rbt_qp_map_from_patches(const rbt_atlas_params* atlas, const rbt_patch* patc
  *    outside -1..51; a negative max_trials; a negative floor; a QP range or a region the PSNR floor refuses; a frame with patches but no list; a target on an occupancy
  *    entry. An entry without a target (n_frames 0, everything else 0) is coded at params[i].qp: n_frames 0, map and frames NULL, sums filled.
  * There is no container-level call and no rbt_pipeline option: the library does not parse the atlas sub-bitstream.
- * Not built: colour floors per patch (D1 floors per patch: below), byte caps per patch, a caller's map together with a target, quantisation groups below the CTB. */
+ * Not built: byte caps per patch (D1, D2 and colour floors per patch: below), a caller's map together with a target, quantisation groups below the CTB. */
 typedef struct {
   uint32_t struct_size;                                        /* sizeof(rbt_patch_floor_target): checked */
   int32_t  min_psnr_mdb;  int region;  int qp_min, qp_max;     /* as rbt_quality_target */
@@ -1010,7 +1035,7 @@ int rbt_ctb_sse(rbt_ctx* ctx, const uint16_t* a, const uint16_t* b, int width, i
  *    odd picture count, n_frames that is not pictures / 2, an atlas size that is not the output pictures', a background_qp outside -1..51, a negative max_trials, a
  *    negative patch floor, log2_ctb outside 4..6); a target on an attribute or occupancy entry; map_count other than 2; occupancy_rd together with verify_md5 as the PSNR
  *    floor refuses it. An entry without a target (n_frames 0, everything else 0) is coded at params[i].qp: n_frames 0, map, frames and picks NULL.
- * Not built: colour floors per patch, byte caps per patch, a caller's map together with a target, and a container-level call or rbt_pipeline option - the library does not
+ * Not built: byte caps per patch, a caller's map together with a target, and a container-level call or rbt_pipeline option - the library does not
  * parse the atlas sub-bitstream. */
 typedef struct {
   uint32_t struct_size;                                        /* sizeof(rbt_patch_d1_target): checked */
@@ -1099,7 +1124,7 @@ int rbt_estimate_normals(rbt_ctx* ctx, const int16_t* xyz, int n, const rbt_norm
  * rbt_transcode_gof_qp_map's for the final map, no further encode runs, and the result names the patch that sets a frame's D2 as the D1 kind does. The reference rule is
  * the one above.
  * A job is collected only by the wait call of its kind; a wrong pairing is RBT_ERR_PARAM and leaves the job collectable.
- * Not built: D2 floors per frame through the QP list (rbt_submit_gof_d1_frames has no D2 sibling), colour figures and colour floors per patch, a D2 floor together with
+ * Not built: D2 floors per frame through the QP list (rbt_submit_gof_d1_frames has no D2 sibling), a D2 floor together with
  * another kind of target in one job, and container-level calls - the library does not parse the atlas sub-bitstream. */
 enum { RBT_D2_MIN = RBT_D1_MIN, RBT_D2_MEAN = RBT_D1_MEAN };
 typedef struct {
@@ -1158,6 +1183,63 @@ int rbt_submit_gof_d2_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_
 int rbt_wait_gof_d2_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_patch_d2_result* results);   /* results: n entries */
 int rbt_transcode_gof_d2_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_d2_target* targets,
                                  uint8_t** annexb_out, size_t* n_out, rbt_patch_d2_result* results);   /* submit + wait */
+
+/* ---- colour floors held patch by patch (csrc/rbt_score.h, host/rbt_patch_walk.h) ----
+ * The attribute sub-bitstream is where the bytes are, and the QP map codes attribute entries; the PSNR floor per patch on such an entry steers by the luma PSNR of the
+ * map, a proxy for what the common test conditions report. Here every patch of every frame of an attribute entry walks to its own QP on the colour PSNR of its points in
+ * the decoded cloud ("colour PSNR per patch of the decoded cloud" above): one more figure on the patch walk, over the colour job's "cloud once, recolour per trial" route.
+ *
+ * 1. Sources, shapes, cloud, reference. Rules 1 - 4 of "transcoding attributes to a colour PSNR floor" hold: the target sits on an attribute entry; its geometry source is
+ *    coded once at its own params[i].qp, byte for byte as rbt_transcode_gof codes it, occupancy_rd included. atlas.map_count must be 2: a point-cloud frame is the two
+ *    pictures that are coded as a pair. B_f(trial map) is rule 3's cloud with the attribute pictures coded under the trial's QP map; it carries the labels of
+ *    rbt_pcloud_from_maps. Everything of B_f that does not depend on the attribute QP - positions, smoothing, index, labels, the score pair against A_f - is made once per
+ *    job and frame behind the geometry encode.
+ * 2. Figure. The figure of patch k of frame f in a trial is (double)psnr[channel] of patch k from rbt_score_pair_patches_color on the frame's pair. meets is
+ *    figure >= F_k / 1000.0; +inf meets.
+ * 3. Trial map, walk, rounds, stream: rules 4 - 7 of "PSNR floors held patch by patch", word for word, with this figure (patch_walk_seed / patch_walk_step unchanged). A
+ *    round is one pass over the unsettled frames with their trial maps; behind it exactly those frames are gathered, up-converted, recoloured and scored per patch. The
+ *    attribute entry's stream is byte for byte rbt_transcode_gof_qp_map's for the final map, assembled from the settling trials; no further encode runs.
+ * 4. Floor 0. With min_psnr_mdb 0 and patch_min_psnr_mdb NULL there is one trial at clamp(params[i].qp, 0, 51): every patch's rbt_patch_color is reported and met = 1.
+ * 5. Everything is copied at submit. A job is collected by rbt_wait_gof_color_patches only; a wrong pairing is RBT_ERR_PARAM and leaves the job collectable. Refusals, all
+ *    RBT_ERR_PARAM with a reason, nothing submitted, the context usable: those of the colour section (rule 7 there, with its words) and those of the patch-floor section
+ *    (rule 9 there: a wrong struct_size, an odd picture count, n_frames that is not pictures / 2, an atlas size that is not the output pictures', a background_qp outside
+ *    -1..51, a negative max_trials, a negative patch floor, log2_ctb outside 4..6); a target on a non-attribute entry; map_count other than 2. An empty cloud, a coordinate
+ *    outside 0..1023 or more than 2^21 merged points fail the job in its wait call, as in the colour section. An entry without a target (every field but struct_size
+ *    zero) is coded at params[i].qp: n_frames 0, map, frames and picks NULL.
+ * Memory is the colour section's plus 4 bytes per point of labels and 64 bytes per patch of sums.
+ * Not built: colour floors per frame through the QP list, byte caps per patch, two kinds of floor in one job, a caller's map together with a target, and a
+ * container-level call - the library does not parse the atlas sub-bitstream. */
+typedef struct {
+  uint32_t struct_size;                                        /* sizeof(rbt_patch_color_target): checked */
+  int32_t  min_psnr_mdb;  int channel;  int qp_min, qp_max;    /* floor in 1/1000 dB (0 = none) on the symmetric colour PSNR of channel 0 Y, 1 U, 2 V; qp_max 0 = 51 */
+  int      background_qp;                                      /* 0..51, -1 = q0 */
+  int      max_trials;                                         /* 0 = no cap */
+  rbt_atlas_params atlas;                                      /* the OUTPUT atlas, as in rbt_color_target */
+  int n_frames;  const rbt_patch* const* patches;  const int* n_patches;
+  const int32_t* const* patch_min_psnr_mdb;                    /* NULL, or per frame NULL / one floor per patch: F_k; else F_k = min_psnr_mdb */
+  int      upsample_filter, attr_transfer;                     /* as in rbt_color_target */
+  const rbt_pcloud* const* reference;                          /* NULL, or n_frames handles with colours: A_f; a NULL handle = the cloud of the decoded input */
+} rbt_patch_color_target;
+typedef struct { int qp, met, failed; rbt_patch_color color; double figure; } rbt_patch_color_pick;   /* of the settling trial: q[k], met, failed[k], the patch's sums and figures, (double)color.psnr[channel] */
+typedef struct {
+  int n_trials, met, n_patches;                                /* met = AND of patches[k].met */
+  uint64_t bytes;                                              /* the frame's NAL units in the returned stream, start codes included */
+  rbt_color_result color;                                      /* the whole frame's colour result in the settling trial: rbt_score(A_f, B_f, peak, RBT_SCORE_COLOR).color */
+  rbt_patch_color_pick* patches;                               /* n_patches picks: they point into rbt_patch_color_result.picks */
+} rbt_patch_color_frame;
+typedef struct {
+  int n_frames, qp_probe, met_all, n_passes;                   /* q0; met_all = AND of frames[f].met */
+  uint64_t bytes, pictures_encoded;                            /* size of the returned stream; 2 * sum of frames[f].n_trials */
+  int w_ctb, h_ctb;
+  int8_t* map;                                                 /* the final map, n_frames * h_ctb * w_ctb (malloc'd, rbt_free) */
+  rbt_patch_color_frame* frames;                               /* n_frames (malloc'd, rbt_free) */
+  rbt_patch_color_pick* picks;                                 /* every frame's picks back to back (malloc'd, rbt_free) */
+  double cloud_ms;                                             /* as rbt_color_floor_result.cloud_ms, the per-patch kernel included */
+} rbt_patch_color_result;
+int rbt_submit_gof_color_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_color_target* targets, rbt_job** job);
+int rbt_wait_gof_color_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_patch_color_result* results);   /* results: n entries */
+int rbt_transcode_gof_color_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_color_target* targets,
+                                    uint8_t** annexb_out, size_t* n_out, rbt_patch_color_result* results);   /* submit + wait */
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,15 @@ def patch_d2_dict(p):
     return {k: getattr(p, k) for k, _ in PatchD2._fields_}
 
 
+class PatchColor(C.Structure):
+    """rbt_patch_color: the colour sums and figures of one patch of the decoded cloud (rbt_score_patches_color), [Y, U, V] per array field"""
+    _fields_ = [("n_ab", C.c_uint32), ("n_ba", C.c_uint32), ("sse_ab", C.c_uint64 * 3), ("sse_ba", C.c_uint64 * 3)] + [(n, C.c_float * 3) for n in ("mse_ab", "mse_ba", "mse", "psnr")]
+
+
+def patch_color_dict(p):
+    return {k: (list(getattr(p, k)) if isinstance(getattr(p, k), C.Array) else getattr(p, k)) for k, _ in PatchColor._fields_}
+
+
 class FrameScore(C.Structure):
     """rbt_frame_score: what rbt_score returns for one pair of clouds"""
     _fields_ = [("parts", C.c_int), ("d1", D1Result), ("d2", D2Result), ("color", ColorResult), ("device_ms", C.c_double)] + \
@@ -464,7 +473,7 @@ def load(path=None):
     L.rbt_wait_gof_d1_frames.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(FrameFloorResult)]
     L.rbt_transcode_gof_d1_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(D1Target), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                               C.POINTER(FrameFloorResult)]
-    for name, tt, rt in (("d2", D2Target, D2FloorResult), ("d2_patches", PatchD2Target, PatchD2Result)):
+    for name, tt, rt in (("d2", D2Target, D2FloorResult), ("d2_patches", PatchD2Target, PatchD2Result), ("color_patches", PatchColorTarget, PatchColorResult)):
         args = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(StreamParams), C.POINTER(tt)]
         getattr(L, "rbt_submit_gof_" + name).argtypes = args + [C.POINTER(C.c_void_p)]
         getattr(L, "rbt_wait_gof_" + name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(rt)]
@@ -486,6 +495,8 @@ def load(path=None):
     L.rbt_score_patches_d2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(PatchD2), C.POINTER(D2Result), C.POINTER(C.c_double)]
     L.rbt_score_pair_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     L.rbt_score_pair_color.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ColorResult)]
+    L.rbt_score_patches_color.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PatchColor), C.POINTER(ColorResult), C.POINTER(C.c_double)]
+    L.rbt_score_pair_patches_color.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PatchColor), C.POINTER(ColorResult)]
     L.rbt_score_pair_release.argtypes = [C.c_void_p, C.c_void_p]
     L.rbt_score_pair_release.restype = None
     L.rbt_picture_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -697,6 +708,42 @@ class PatchD2Result(C.Structure):
                 ("map", C.POINTER(C.c_int8)), ("frames", C.POINTER(PatchD2Frame)), ("picks", C.POINTER(PatchD2Pick)), ("cloud_ms", C.c_double)]
 
 
+class PatchColorTarget(C.Structure):
+    """rbt_patch_color_target: PatchD1Target's walk side (min_psnr_mdb, qp_min, qp_max, background_qp, max_trials, patch_floors as patch_min_psnr_mdb) with ColorTarget's
+    cloud side (channel, upsample_filter, attr_transfer, references with colours)"""
+    _fields_ = [("struct_size", C.c_uint32), ("min_psnr_mdb", C.c_int32), ("channel", C.c_int), ("qp_min", C.c_int), ("qp_max", C.c_int), ("background_qp", C.c_int), ("max_trials", C.c_int),
+                ("atlas", AtlasParams), ("n_frames", C.c_int), ("patches", C.POINTER(C.POINTER(Patch))), ("n_patches", C.POINTER(C.c_int)), ("patch_min_psnr_mdb", C.POINTER(C.POINTER(C.c_int32))),
+                ("upsample_filter", C.c_int), ("attr_transfer", C.c_int), ("reference", C.POINTER(C.c_void_p))]
+
+    def __init__(self, atlas=None, patches=None, min_psnr_mdb=0, channel=0, qp_min=0, qp_max=0, background_qp=-1, max_trials=0, patch_floors=None, upsample_filter=0, attr_transfer=1, reference=None):
+        C.Structure.__init__(self)
+        self.struct_size = C.sizeof(PatchColorTarget)
+        self._keep = []
+        if atlas is None:
+            return
+        d = PatchD1Target(atlas, patches, min_psnr_mdb, 0, qp_min, qp_max, background_qp, max_trials, patch_floors, reference)      # the arrays are PatchD1Target's, kept alive with it
+        for name, src in (("min_psnr_mdb", "min_d1_mdb"), ("patch_min_psnr_mdb", "patch_min_d1_mdb")) + tuple((n, n) for n in ("qp_min", "qp_max", "background_qp", "max_trials", "atlas", "n_frames", "patches", "n_patches", "reference")):
+            setattr(self, name, getattr(d, src))
+        self.channel, self.upsample_filter, self.attr_transfer = channel, upsample_filter, attr_transfer
+        self._keep.append(d)
+
+
+class PatchColorPick(C.Structure):
+    """rbt_patch_color_pick: of a frame's settling trial, per patch: its QP, met, failed, its PatchColor, its figure"""
+    _fields_ = [("qp", C.c_int), ("met", C.c_int), ("failed", C.c_int), ("color", PatchColor), ("figure", C.c_double)]
+
+
+class PatchColorFrame(C.Structure):
+    """rbt_patch_color_frame: trials, met, the patch count, the frame's bytes, the whole frame's ColorResult in the settling trial, the picks"""
+    _fields_ = [("n_trials", C.c_int), ("met", C.c_int), ("n_patches", C.c_int), ("bytes", C.c_uint64), ("color", ColorResult), ("patches", C.POINTER(PatchColorPick))]
+
+
+class PatchColorResult(C.Structure):
+    """rbt_patch_color_result: as PatchD1Result"""
+    _fields_ = [("n_frames", C.c_int), ("qp_probe", C.c_int), ("met_all", C.c_int), ("n_passes", C.c_int), ("bytes", C.c_uint64), ("pictures_encoded", C.c_uint64), ("w_ctb", C.c_int), ("h_ctb", C.c_int),
+                ("map", C.POINTER(C.c_int8)), ("frames", C.POINTER(PatchColorFrame)), ("picks", C.POINTER(PatchColorPick)), ("cloud_ms", C.c_double)]
+
+
 class PCloud:
     """rbt_pcloud: a point cloud on the device with its index; belongs to the context that made it. release() hands it back (its clean volume stays cached in the context)."""
 
@@ -756,6 +803,12 @@ class ScorePair:
         r = ColorResult()
         self.ctx._chk(self.ctx.L.rbt_score_pair_color(self.ctx.h, self.h, C.byref(r)))
         return {n: (getattr(r, n) if n in ("n_a", "n_b") else list(getattr(r, n))) for n, _ in ColorResult._fields_}
+
+    def patches_color(self, n_patches, raw=False):
+        """rbt_score_pair_patches_color -> (one dict per patch - or the PatchColor array itself (raw) -, the whole frame's colour result as color() returns it)"""
+        out = (PatchColor * max(1, n_patches))(); whole = ColorResult()
+        self.ctx._chk(self.ctx.L.rbt_score_pair_patches_color(self.ctx.h, self.h, n_patches, out, C.byref(whole)))
+        return (out if raw else [patch_color_dict(out[k]) for k in range(n_patches)]), (whole if raw else _result_dict(whole))
 
     def release(self):
         if self.h:
@@ -1267,6 +1320,13 @@ class Context:
         self._chk(self.L.rbt_score_patches_d2(self.h, a.h if a is not None else None, b.h if b is not None else None, peak, n_patches, out, C.byref(whole), C.byref(ms)))
         return (out if raw else [patch_d2_dict(out[k]) for k in range(n_patches)]), (whole if raw else _result_dict(whole)), ms.value
 
+    def score_patches_color(self, a, b, n_patches, raw=False):
+        """rbt_score_patches_color: a = the source PCloud, b = the decoded one with its labels, both with colours -> (one dict per patch - or the PatchColor array itself
+        (raw) -, the whole frame's colour result as rbt_score returns it, device_ms)"""
+        out = (PatchColor * max(1, n_patches))(); whole = ColorResult(); ms = C.c_double()
+        self._chk(self.L.rbt_score_patches_color(self.h, a.h if a is not None else None, b.h if b is not None else None, n_patches, out, C.byref(whole), C.byref(ms)))
+        return (out if raw else [patch_color_dict(out[k]) for k in range(n_patches)]), (whole if raw else _result_dict(whole)), ms.value
+
     def score_pair(self, a, b):
         """rbt_score_pair_create: a = the source PCloud, b = the decoded one -> ScorePair"""
         return ScorePair(self, a, b)
@@ -1331,6 +1391,9 @@ _GOF_KINDS = {
     "d2_patches": (PatchD2Target, PatchD2Result,
                    lambda self, res: self._patch_results(res, lambda f: dict(_result_dict(f), d2=_result_dict(f.d2)), lambda p: dict(_result_dict(p), d2=patch_d2_dict(p.d2))),
                    "submit_gof with one PatchD2Target per entry (PatchD2Target() = none): every patch of every frame of a geometry entry holds its D2 floor", ""),
+    "color_patches": (PatchColorTarget, PatchColorResult,
+                      lambda self, res: self._patch_results(res, lambda f: dict(_result_dict(f), color=_result_dict(f.color)), lambda p: dict(_result_dict(p), color=patch_color_dict(p.color))),
+                      "submit_gof with one PatchColorTarget per entry (PatchColorTarget() = none): every patch of every frame of an attribute entry holds its colour PSNR floor", ""),
     "color": (ColorTarget, ColorFloorResult, Context._color_results,
               "submit_gof with one ColorTarget per entry (ColorTarget() = none; min_psnr_mdb 0 = constant QP, colour results reported)", ""),
 }

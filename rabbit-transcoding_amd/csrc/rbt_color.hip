@@ -148,6 +148,23 @@ __global__ void __launch_bounds__(RBT_SC_SUM) k_p2_fold(RbtPatchD2Work P, unsign
   __shared__ RbtScoreSumLds lds;
   p2_fold(&P, out, dir, (int)blockIdx.x, RBT_LDS_CAST(RbtScoreSumLds, &lds));
 }
+// ---- colour per patch (rbt_score.h) ----
+// dir 0: one lane per point of A, 1: per point of B; in place of k_sc_color_walk. No LDS: every wave adds on its own, as in k_pd_sums. A wave whose terms all carry one
+// label folds the three squares with shuffles and lane 0 issues one atomic per non-zero word; a mixed wave issues them per lane. Integer atomics only.
+__global__ void __launch_bounds__(256) k_pc_sums(RbtScoreCloud A, RbtScoreCloud B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out, int dir) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  uint32_t label = 0; long long e[3] = {0, 0, 0}; int valid = 0;
+  if (i < (dir ? B.n : A.n)) valid = pc_term(&A, &B, labels_b, dist_a, dist_b, dir, i, &label, e);
+  const unsigned long long act = __ballot(valid);
+  if (!act) return;                                                     // uniform over the wave
+  unsigned long long sq[3];
+  for (int c = 0; c < 3; c++) sq[c] = valid ? (unsigned long long)(e[c] * e[c]) : 0;
+  const uint32_t first = (uint32_t)__shfl((int)label, __ffsll((long long)act) - 1);
+  if (__ballot(valid && label != first) == 0) {
+    for (int o = 32; o > 0; o >>= 1) for (int c = 0; c < 3; c++) sq[c] += (unsigned long long)__shfl_xor((long long)sq[c], o);
+    if ((threadIdx.x & 63) == 0) pc_add(out, first, dir, sq, (unsigned long long)__popcll(act));
+  } else if (valid) pc_add(out, label, dir, sq, 1);
+}
 
 void launch_up444(const uint16_t* yuv420, int w, int h, int bit_depth, int n_frames, int filter, uint16_t* yuv444) {
   if (n_frames <= 0) return;
@@ -233,5 +250,10 @@ void launch_p2_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32
     hipLaunchKernelGGL(k_p2_cols, dim3(1), dim3(RBT_SC_SUM), 0, g_stream, *P, nb);
     hipLaunchKernelGGL(k_p2_fold, dim3((unsigned)n_patches), dim3(RBT_SC_SUM), 0, g_stream, *P, out, dir);
   }
+}
+void launch_pc_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out) {
+  if (A->n <= 0 || B->n <= 0) return;
+  hipLaunchKernelGGL(k_pc_sums, dim3((unsigned)((A->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, labels_b, dist_a, dist_b, out, 0);
+  hipLaunchKernelGGL(k_pc_sums, dim3((unsigned)((B->n + 255) / 256)), dim3(256), 0, g_stream, *A, *B, labels_b, dist_a, dist_b, out, 1);
 }
 }  // namespace rbtk

@@ -31,6 +31,12 @@
 //            its bit pattern does). p2_cols: 256 lanes, lane t walks blocks t, t + 256, .. in ascending order and adds every entry into S[label][t] - it owns its
 //            column, no atomics. p2_fold: one workgroup per patch folds S[k][0..255] and leaves the row zero for the other direction. No floating-point atomics.
 //            Scratch: 12 bytes per entry of the larger cloud rounded up to 256, 4 per 256 entries, 2 KB (S) + 8 RBT_P2_WORDS bytes per patch: O(points + patches).
+//   col/patch the colour sums per patch of the decoded cloud (rbt_score_patches_color, rbt_score_pair_patches_color; the definition is in include/rbt.h): behind the two searches,
+//            or on the distances a score pair keeps, in place of the colour walks. One lane per point of the walking cloud. pc_term walks the tie set once: A -> B the walk
+//            that sums the tie colours also takes the lowest point index among the tie voxels - the owner, pd_term_ab's rule - so the label costs one comparison per tie
+//            voxel; B -> A the label is the point's own. RBT_PC_WORDS 64-bit words per patch - three sums of squared error terms and a count per direction -, integer
+//            atomics only, added as k_pd_sums adds: a wave whose terms all carry one label folds them with shuffles and lane 0 issues one atomic per non-zero word, a
+//            mixed wave one per lane and non-zero word. The whole frame's sums are the sums over the patches, exact: the host adds them, no second kernel runs.
 // No kernel waits for another; every loop is bounded by the size of the volume.
 #pragma once
 #include "rbt_color.h"
@@ -71,10 +77,15 @@ void launch_pd_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32
 // behind launch_sc_score with RBT_SCORE_D2 on the same clouds and the same W (dist_*, val_*): out holds RBT_P2_WORDS words per patch (zeroed beforehand); every label of B
 // is below n_patches
 void launch_p2_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const RbtScoreWork* W, const RbtPatchD2Work* P, int n_patches, unsigned long long* out);
+// behind launch_sc_search on the same clouds, or on the distances of a score pair, in place of launch_sc_color_walks: out holds RBT_PC_WORDS words per patch (zeroed
+// beforehand); both clouds carry colours, every label of B is below the patch count
+void launch_pc_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out);
 }  // namespace rbtk
 enum { RBT_SC_COLOR_RESULTS = 8 };
 // words of one patch in the result of launch_pd_sums, 64-bit each; + 1 for the direction B -> A
 enum { RBT_PD_SSE_AB = 0, RBT_PD_SSE_BA, RBT_PD_N_AB, RBT_PD_N_BA, RBT_PD_MAX_AB, RBT_PD_MAX_BA, RBT_PD_WORDS };
+// words of one patch in the result of launch_pc_sums, 64-bit each: the sums of e[c]^2 at RBT_PC_SSE_AB + c / RBT_PC_SSE_BA + c (c = 0, 1, 2: Y, U, V), then the counts
+enum { RBT_PC_SSE_AB = 0, RBT_PC_SSE_BA = 3, RBT_PC_N_AB = 6, RBT_PC_N_BA = 7, RBT_PC_WORDS = 8 };
 // words of one patch in the result of launch_p2_sums, 64-bit each; + 1 for the direction B -> A. SSE and MAX hold doubles, N counts
 enum { RBT_P2_SSE_AB = 0, RBT_P2_SSE_BA, RBT_P2_N_AB, RBT_P2_N_BA, RBT_P2_MAX_AB, RBT_P2_MAX_BA, RBT_P2_WORDS };
 // LDS of p2_block: the fold's arrays, then per lane its label (RBT_SC_NONE: no term), its value, and - for the lowest lane of a label - the label's count of lanes (else 0)
@@ -422,9 +433,49 @@ RBT_DEV void p2_fold(const RbtPatchD2Work* P, unsigned long long* out, int dir, 
   RBT_BLK_FOR(t, 1) { double* w = (double*)(out + (size_t)RBT_P2_WORDS * (size_t)k + dir); w[RBT_P2_SSE_AB] = L->s[0]; }
 }
 
+// ---- colour per patch ----
+// the term of point i of the walking cloud (dir 0: A, 1: B): the colour error e of sc_walk_ab / sc_walk_ba and the label it belongs to. ONE walk over the tie set gives the
+// tie colour sums and, A -> B, the owner: the lowest point index among the tie voxels (pd_term_ab's rule). Returns 0 for a point that is no representative.
+RBT_DEV int pc_term(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, int dir, int i, uint32_t* label, long long e[3]) {
+  const uint32_t d2 = dir ? dist_b[i] : dist_a[i]; if (d2 == RBT_SC_NONE) return 0;
+  const RbtScoreCloud* P = dir ? B : A; const RbtScoreCloud* Q = dir ? A : B;
+  const int16_t* p = P->xyz + 3 * (size_t)i; const int x = p[0], y = p[1], z = p[2];
+  uint32_t sr = 0, sg = 0, sb = 0, n = 0, owner = 0xFFFFFFFFu;
+  pc_for_ties(Q->vol, x, y, z, d2, [&](uint32_t id) {
+    const uint32_t s = cl_slot_find(Q->keys, Q->lg, id), c = Q->col[s];
+    sr += c & 255u; sg += (c >> 8) & 255u; sb += c >> 16; n++;
+    if (!dir) { const uint32_t j = Q->vals[s]; if (j < owner) owner = j; }
+  });
+  if (!n) return 0;                                 // (the distance is that of a voxel of Q: there is a tie)
+  if (dir) *label = labels_b[i];
+  else { if (owner >= (uint32_t)B->n) return 0; *label = labels_b[owner]; }
+  sc_color_error(P->col[cl_slot_find(P->keys, P->lg, pc_voxel_id(x, y, z))], sr, sg, sb, n, e);
+  return 1;
+}
+// the sums of e[c]^2 and the count of one or more terms into the words of patch `label`, direction dir
+RBT_DEV void pc_add(unsigned long long* out, uint32_t label, int dir, const unsigned long long sq[3], unsigned long long cnt) {
+  unsigned long long* w = out + (size_t)RBT_PC_WORDS * label;
+  unsigned long long* s = w + (dir ? RBT_PC_SSE_BA : RBT_PC_SSE_AB); unsigned long long* n = w + (dir ? RBT_PC_N_BA : RBT_PC_N_AB);
+#ifdef RBT_HOSTEMU
+  for (int c = 0; c < 3; c++) s[c] += sq[c];
+  *n += cnt;
+#else
+  for (int c = 0; c < 3; c++) if (sq[c]) atomicAdd(&s[c], sq[c]);
+  atomicAdd(n, cnt);
+#endif
+}
+
 #ifdef RBT_HOSTEMU
 // serial stand-ins of the launchers (the product's are in rbt_color.hip)
 namespace rbtk {
+inline void launch_pc_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out) {
+  for (int dir = 0; dir < 2; dir++) for (int i = 0; i < (dir ? B->n : A->n); i++) {
+    uint32_t label = 0; long long e[3] = {0, 0, 0};
+    if (!pc_term(A, B, labels_b, dist_a, dist_b, dir, i, &label, e)) continue;
+    const unsigned long long sq[3] = {(unsigned long long)(e[0] * e[0]), (unsigned long long)(e[1] * e[1]), (unsigned long long)(e[2] * e[2])};
+    pc_add(out, label, dir, sq, 1);
+  }
+}
 inline void launch_pd_labels(const uint32_t* items, const uint32_t* offsets, int n_items, uint32_t* labels) { for (int t = 0; t < n_items; t++) pd_label_item(items, offsets, t, 0, 1, labels); }
 inline void launch_pd_check(const uint32_t* labels, int n, uint32_t n_patches, uint32_t* err) { for (int i = 0; i < n; i++) if (labels[i] >= n_patches) *err = 1; }
 inline void launch_pd_sums(const RbtScoreCloud* A, const RbtScoreCloud* B, const uint32_t* labels_b, const uint32_t* dist_a, const uint32_t* dist_b, unsigned long long* out) {

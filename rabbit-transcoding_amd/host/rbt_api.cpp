@@ -207,6 +207,7 @@ struct SubmitExtras {
   const rbt_patch_floor_target* patches = nullptr;
   const rbt_patch_d1_target* d1_patches = nullptr;
   const rbt_d2_target* d2 = nullptr; const rbt_patch_d2_target* d2_patches = nullptr;      // the D1 kinds with the D2 figure (check_d2, check_d2_patches)
+  const rbt_patch_color_target* color_patches = nullptr;
 };
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x = SubmitExtras());
 // transcodeVideo re-encodes whatever it is handed (an occupancy stream with occupancyPrecision != 4 is re-encoded without pooling)
@@ -408,6 +409,33 @@ static int check_d2_patches(rbt_ctx* ctx, int n, const rbt_stream_params* p, con
     if (int rc = check_d2_side(ctx, "entry " + std::to_string(i) + ": ", t[i].reference, t[i].n_frames, t[i].normals, normals[(size_t)i])) return rc;
   return RBT_OK;
 }
+// The refusals of rbt_submit_gof_color_patches that the parameters alone decide, as check_d1_patches has them: the target's own fields, the walks' side (out,
+// fill_patch_request) and the clouds' side (req, check_color, with its words). as_color: the clouds' side as colour targets without a floor of their own, alive until
+// submit returns
+static int check_color_patches(rbt_ctx* ctx, int n, const rbt_stream_params* p, const rbt_patch_color_target* t, std::vector<rbt_color_target>& as_color, std::vector<rbt::PatchFloorIn>& out,
+                               rbt::CloudRequest<rbt_color_target>& req) {
+  std::string& err = ctx->last_err;
+  out.assign((size_t)n, rbt::PatchFloorIn()); as_color.assign((size_t)n, rbt_color_target());
+  std::vector<char> has((size_t)n, 0);
+  for (int i = 0; i < n; i++) {
+    const std::string who = "entry " + std::to_string(i) + ": ";
+    rbt_color_target& d = as_color[(size_t)i]; memset(&d, 0, sizeof(d)); d.struct_size = sizeof(d);
+    if (t[i].struct_size != sizeof(rbt_patch_color_target)) { err = who + "rbt_patch_color_target.struct_size is not sizeof(rbt_patch_color_target)"; return RBT_ERR_PARAM; }
+    rbt_patch_color_target zero; memset(&zero, 0, sizeof(zero));
+    const bool empty = !t[i].min_psnr_mdb && !t[i].channel && !t[i].qp_min && !t[i].qp_max && !t[i].background_qp && !t[i].max_trials && !t[i].n_frames && !t[i].patches && !t[i].n_patches &&
+                       !t[i].patch_min_psnr_mdb && !t[i].upsample_filter && !t[i].attr_transfer && !t[i].reference && !memcmp(&t[i].atlas, &zero.atlas, sizeof(zero.atlas));
+    if (empty) continue;
+    if (p[i].video_type != RBT_VIDEO_ATTRIBUTE) { err = who + "a colour target on a non-attribute entry (the target of a geometry or occupancy entry must be empty)"; return RBT_ERR_PARAM; }
+    if (t[i].min_psnr_mdb < 0) { err = who + "min_psnr_mdb must not be negative"; return RBT_ERR_PARAM; }
+    if (t[i].atlas.map_count != 2) { err = who + "floors held patch by patch need atlas.map_count 2: a point-cloud frame is the two pictures that are coded as a pair"; return RBT_ERR_PARAM; }
+    has[(size_t)i] = 1;
+    d.channel = t[i].channel; d.stat = RBT_D1_MIN; d.qp_min = t[i].qp_min; d.qp_max = t[i].qp_max; d.n_frames = t[i].n_frames; d.atlas = t[i].atlas; d.patches = t[i].patches; d.n_patches = t[i].n_patches;
+    d.upsample_filter = t[i].upsample_filter; d.attr_transfer = t[i].attr_transfer; d.reference = t[i].reference;
+  }
+  for (int i = 0; i < n; i++) if (has[(size_t)i])
+    if (int rc = fill_patch_request(err, "entry " + std::to_string(i) + ": ", p[i], t[i], t[i].min_psnr_mdb, RBT_QUALITY_ALL, t[i].patch_min_psnr_mdb, out[(size_t)i])) return rc;
+  return check_color(ctx, n, p, as_color.data(), req);
+}
 static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, rbt_job** job, const SubmitExtras& x) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !job) return RBT_ERR_PARAM;
   *job = nullptr;
@@ -431,12 +459,14 @@ static int submit(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const si
   std::vector<rbt_patch_d1_target> as_pd1; std::vector<rbt::NormalsIn> normals;
   if (x.d2) { if (int rc = check_d2(ctx, n, p, x.d2, as_d1, d1, normals)) return rc; r.d1 = &d1; r.d2_normals = &normals; }
   if (x.d2_patches) { if (int rc = check_d2_patches(ctx, n, p, x.d2_patches, as_pd1, as_d1, patch_floors, d1, normals)) return rc; r.patch_floors = &patch_floors; r.d1 = &d1; r.patch_d1 = true; r.d2_normals = &normals; }
+  std::vector<rbt_color_target> as_color;
+  if (x.color_patches) { if (int rc = check_color_patches(ctx, n, p, x.color_patches, as_color, patch_floors, color)) return rc; r.patch_floors = &patch_floors; r.color = &color; r.patch_color = true; }
   int slot = -1;
   for (int s = 0; s < D.depth && slot < 0; s++) if (!D.jobs[s]) slot = s;
   if (slot < 0) return RBT_ERR_BUSY;
   for (int i = 0; i < n; i++) if (p[i].md5_sei < RBT_HASH_NONE || p[i].md5_sei > RBT_HASH_CHECKSUM) { ctx->last_err = "md5_sei of stream " + std::to_string(i) + " is not an RBT_HASH_* kind"; return RBT_ERR_PARAM; }
   rbt_job* j = new rbt_job{rbt::gof_submit(slot, D.depth, r), ctx};
-  if (x.quality || x.d1 || x.color || x.lists || x.maps || x.patches || x.d1_patches || x.d2 || x.d2_patches) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
+  if (x.quality || x.d1 || x.color || x.lists || x.maps || x.patches || x.d1_patches || x.d2 || x.d2_patches || x.color_patches) if (int rc = rbt::gof_refused(j->j, ctx->last_err)) { rbt::gof_abandon(j->j); delete j; return rc; }      // refused by the plan: nothing was enqueued, the slot stays free
   D.jobs[slot] = j; *job = j;
   return RBT_OK;                       // errors of the build surface in rbt_wait_gof, which also releases the job
 }
@@ -505,7 +535,7 @@ static int wait(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out,
   int slot = -1;
   for (int s = 0; s < RBT_MAX_JOBS; s++) if (D.jobs[s] == job) slot = s;
   if (slot < 0 || job->owner != ctx) return RBT_ERR_PARAM;
-  static const char* const names[] = {nullptr, "quality", "d1", "color", "d1_frames", "quality_frames", "quality_patches", "d1_patches", "d2", "d2_patches"};      // per GofKind: rbt_submit_gof_<name>, rbt_wait_gof_<name>
+  static const char* const names[] = {nullptr, "quality", "d1", "color", "d1_frames", "quality_frames", "quality_patches", "d1_patches", "d2", "d2_patches", "color_patches"};      // per GofKind: rbt_submit_gof_<name>, rbt_wait_gof_<name>
   const rbt::GofKind is = rbt::gof_kind(job->j);
   if (is != kind) {      // the wait was called for a job of another kind / the job was handed to another wait
     const bool called = is == rbt::GOF_PLAIN || (kind != rbt::GOF_PLAIN && kind < is);
@@ -614,6 +644,20 @@ int rbt_transcode_gof_d2_patches(rbt_ctx* ctx, int n, const uint8_t* const* anne
                                  uint8_t** annexb_out, size_t* n_out, rbt_patch_d2_result* results) {
   if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !targets) return RBT_ERR_PARAM;      // (refused here, before submit would)
   return transcode(rbt_submit_gof_d2_patches, rbt_wait_gof_d2_patches, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
+}
+// ---- colour floors held patch by patch ----
+int rbt_submit_gof_color_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_color_target* targets, rbt_job** job) try {
+  if (!targets) return RBT_ERR_PARAM;
+  SubmitExtras x; x.color_patches = targets; return submit(ctx, n, annexb_in, n_in, p, job, x);
+} RBT_CATCH
+int rbt_wait_gof_color_patches(rbt_ctx* ctx, rbt_job* job, uint8_t** annexb_out, size_t* n_out, rbt_patch_color_result* results) try {
+  if (!results) return RBT_ERR_PARAM;
+  rbt::GofResults r; r.color_patches = results; return wait(ctx, job, annexb_out, n_out, rbt::GOF_COLOR_PATCHES, r);
+} RBT_CATCH
+int rbt_transcode_gof_color_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_color_target* targets,
+                                    uint8_t** annexb_out, size_t* n_out, rbt_patch_color_result* results) {
+  if (!ctx || n < 1 || n > RBT_MAX_STREAMS || !annexb_in || !n_in || !p || !targets) return RBT_ERR_PARAM;      // (refused here, before submit would)
+  return transcode(rbt_submit_gof_color_patches, rbt_wait_gof_color_patches, ctx, n, annexb_in, n_in, p, targets, annexb_out, n_out, results);
 }
 // ---- PSNR floors held patch by patch ----
 int rbt_submit_gof_quality_patches(rbt_ctx* ctx, int n, const uint8_t* const* annexb_in, const size_t* n_in, const rbt_stream_params* p, const rbt_patch_floor_target* targets, rbt_job** job) try {
@@ -985,6 +1029,20 @@ int rbt_score_pair_color(rbt_ctx* ctx, const rbt_score_pair* pair, rbt_color_res
   if (!pair_of(ctx, pair)) { ctx->last_err = "not a score pair of this context"; return RBT_ERR_PARAM; }
   if (pair->stale) { ctx->last_err = "a cloud of the pair has been released"; return RBT_ERR_PARAM; }
   return rbt::score_pair_color(ctx->last_err, pair->pair, out);
+} RBT_CATCH
+int rbt_score_patches_color(rbt_ctx* ctx, const rbt_pcloud* a, const rbt_pcloud* b, int n_patches, rbt_patch_color* out, rbt_color_result* whole, double* device_ms) try {
+  if (!ctx || !out) return RBT_ERR_PARAM;
+  RBT_ENTER(ctx);
+  if (!cloud_of(ctx, a) || !cloud_of(ctx, b)) { ctx->last_err = "not a cloud of this context"; return RBT_ERR_PARAM; }
+  return rbt::pcloud_score_patches_color(ctx->last_err, a->cloud, b->cloud, n_patches, out, whole, device_ms);
+} RBT_CATCH
+int rbt_score_pair_patches_color(rbt_ctx* ctx, const rbt_score_pair* pair, int n_patches, rbt_patch_color* out, rbt_color_result* whole) try {
+  if (!ctx || !out) return RBT_ERR_PARAM;
+  if (whole) memset(whole, 0, sizeof(*whole));
+  RBT_ENTER(ctx);
+  if (!pair_of(ctx, pair)) { ctx->last_err = "not a score pair of this context"; return RBT_ERR_PARAM; }
+  if (pair->stale) { ctx->last_err = "a cloud of the pair has been released"; return RBT_ERR_PARAM; }
+  return rbt::score_pair_patches_color(ctx->last_err, pair->pair, n_patches, out, whole);
 } RBT_CATCH
 void rbt_score_pair_release(rbt_ctx* ctx, rbt_score_pair* pair) {
   if (!ctx || !pair_of(ctx, pair)) return;

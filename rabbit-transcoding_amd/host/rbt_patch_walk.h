@@ -12,7 +12,7 @@
 //   end       no q[k] changed: the frame has settled on this trial. A patch moves up until its first failure and only down after it, so the vector never repeats: at most
 //             the sum over the patches of (hi - q0) + (hi - lo) + 1 trials. max_trials (0 = no cap): a frame that reaches it settles on its last trial, met as measured.
 // The walk takes figures and `meets` and nothing else. What they are made of is a kind of figure: a source that turns what a trial brought into a PatchTrial and keeps the
-// kind's payload for the report (below: luma PSNR from the fold words, D1 and D2 from the trial's cloud). A further kind is one more payload and one more source.
+// kind's payload for the report (below: luma PSNR from the fold words, D1, D2 and the colour PSNR from the trial's cloud). A further kind is one more payload and one more source.
 // Plain host code without a device call, so that tests/patch_floor_check.cpp and tests/patch_d1_check.cpp can run it under the sanitizers.
 #pragma once
 #include <algorithm>
@@ -21,6 +21,7 @@
 #include <vector>
 #include "rbt_quality_walk.h"
 #include "rbt_d1_figures.h"
+#include "rbt_color_walk.h"
 
 namespace rbt {
 // the folded sums of one region in the two pictures of a frame: the words of k_patch_fold and the displayed luma samples the region holds
@@ -81,6 +82,7 @@ struct PatchTrial { std::vector<double> figure; std::vector<char> meets; };
 struct PatchPsnr { std::vector<PatchSums> patches; uint64_t background[3] = {0, 0, 0}; };
 struct PatchD1 { std::vector<rbt_patch_d1> patches; rbt_d1_result whole = rbt_d1_result(); };
 struct PatchD2 { std::vector<rbt_patch_d2> patches; rbt_d2_result whole = rbt_d2_result(); };
+struct PatchColor { std::vector<rbt_patch_color> patches; rbt_color_result whole = rbt_color_result(); };
 // the PSNR source: the words k_patch_fold left of the frame - sse, sse_occ, n_occ per patch, then the background's - with the displayed samples of every R_k
 inline void patch_trial_psnr(const uint64_t* words, const std::vector<uint64_t>& samples, int region, int bit_depth, const std::vector<int32_t>& floor_mdb, PatchTrial& t, PatchPsnr& p) {
   const size_t np = samples.size();
@@ -104,5 +106,12 @@ inline void patch_trial_d2(std::vector<rbt_patch_d2>& patches, const rbt_d2_resu
   const size_t np = p.patches.size();
   t.figure.resize(np); t.meets.resize(np);
   for (size_t k = 0; k < np; k++) { t.figure[k] = patch_d2_figure(p.patches[k]); t.meets[k] = patch_d2_meets(p.patches[k], floor_mdb[k]); }
+}
+// the colour source: the same of rbt_score_pair_patches_color, the figure on `channel` (0 Y, 1 U, 2 V)
+inline void patch_trial_color(std::vector<rbt_patch_color>& patches, const rbt_color_result& whole, int channel, const std::vector<int32_t>& floor_mdb, PatchTrial& t, PatchColor& p) {
+  p.patches.swap(patches); p.whole = whole;
+  const size_t np = p.patches.size();
+  t.figure.resize(np); t.meets.resize(np);
+  for (size_t k = 0; k < np; k++) { t.figure[k] = patch_color_figure(p.patches[k], channel); t.meets[k] = patch_color_meets(p.patches[k], channel, floor_mdb[k]); }
 }
 }  // namespace rbt

@@ -8,6 +8,7 @@
 #include "rbt_batch.h"
 #include "rbt_pcc.h"
 #include "rbt_d1_figures.h"
+#include "rbt_color_walk.h"
 #include "../csrc/rbt_pcc.h"
 #include "../csrc/rbt_cloudmaps.h"
 #include "../csrc/rbt_color.h"
@@ -46,11 +47,10 @@ template <class R> void finish_geometry(R* out, int peak) {
   const float m = out->mse_ab > out->mse_ba ? out->mse_ab : out->mse_ba;
   out->psnr_ab = geometry_psnr(peak, out->mse_ab); out->psnr_ba = geometry_psnr(peak, out->mse_ba); out->psnr = geometry_psnr(peak, m);
 }
-void finish_color(rbt_color_result* out) {
-  const double unit = 2550000.0 * 2550000.0;
+void finish_color(rbt_color_result* out) {      // (color_mse / color_psnr: rbt_color_walk.h, where the figures per patch use them too)
   for (int c = 0; c < 3; c++) {
-    out->mse_ab[c] = (float)((double)out->sse_ab[c] / (unit * (double)out->n_a)); out->mse_ba[c] = (float)((double)out->sse_ba[c] / (unit * (double)out->n_b));
-    out->psnr_ab[c] = 10 * log10f(1.0f / out->mse_ab[c]); out->psnr_ba[c] = 10 * log10f(1.0f / out->mse_ba[c]);
+    out->mse_ab[c] = color_mse(out->sse_ab[c], (double)out->n_a); out->mse_ba[c] = color_mse(out->sse_ba[c], (double)out->n_b);
+    out->psnr_ab[c] = color_psnr(out->mse_ab[c]); out->psnr_ba[c] = color_psnr(out->mse_ba[c]);
     out->mse[c] = out->mse_ab[c] > out->mse_ba[c] ? out->mse_ab[c] : out->mse_ba[c];
     out->psnr[c] = out->psnr_ab[c] < out->psnr_ba[c] ? out->psnr_ab[c] : out->psnr_ba[c];
   }
@@ -495,7 +495,7 @@ const PCloud* colorframe_cloud(const ColorFrame* f) { return f->cloud; }
 int colorframe_changed(const ColorFrame* f) { return f->n_changed; }
 size_t colorframe_bytes(const rbt_atlas_params* a, int n_patches) {      // but for its volume: maps, and per possible point positions twice, flags, triples twice, the index's maps
   const size_t pts = (size_t)a->width * (size_t)a->height * (size_t)a->map_count;
-  return mapframe_bytes(a, n_patches) + pts * (6 + 6 + 1 + 6 + 6 + 6 + 3 + 2 * 28);
+  return mapframe_bytes(a, n_patches) + pts * (6 + 6 + 1 + 6 + 6 + 6 + 3 + 4 + 2 * 28);
 }
 int colorframe_new(std::string& err, PCloudCache& cache, const rbt_atlas_params* a, const rbt_patch* patches, int n_patches, const uint16_t* d_occ, const uint16_t* d_d0, const uint16_t* d_d1,
                    int geo_bd, int attr_transfer, ColorFrame** out) {
@@ -505,11 +505,11 @@ int colorframe_new(std::string& err, PCloudCache& cache, const rbt_atlas_params*
   ColorFrame* F = g.f;
   if (int rc = mapframe_new(err, a, patches, n_patches, d_occ, &F->maps)) return rc;
   F->P = F->maps->P; F->P.geo_bd = geo_bd; F->P.attr_bd = geo_bd; F->d0 = d_d0; F->d1 = d_d1 ? d_d1 : d_d0;
-  DevBuf b_xyz;
-  if (int rc = mapframe_points(err, F->maps, F->P, F->d0, F->d1, b_xyz, F->yuv0, &F->xyz0, &F->moved, attr_transfer != 0, &F->total, &F->n_moved)) return rc;
+  DevBuf b_xyz, b_labels;      // (the labels: the colour figures per patch read them, as the D1 route's clouds carry them)
+  if (int rc = mapframe_points(err, F->maps, F->P, F->d0, F->d1, b_xyz, F->yuv0, &F->xyz0, &F->moved, attr_transfer != 0, &F->total, &F->n_moved, &b_labels)) return rc;
   F->transfer = a->geometry_smoothing != 0 && attr_transfer != 0 && F->n_moved != 0;
   const size_t total = (size_t)F->total;
-  PCloud* c = new PCloud(); c->n = F->total; c->xyz.take(b_xyz);
+  PCloud* c = new PCloud(); c->n = F->total; c->xyz.take(b_xyz); c->labels.take(b_labels); c->label_bound = F->P.n_patches;
   F->cloud = c;
   if (!F->yuv.alloc(6 * total) || !F->scratch_xyz.alloc(6 * total) || !c->rgb.alloc(3 * total)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
   if (rbtk::dev_memset(c->rgb.p, 0, 3 * total)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
@@ -536,6 +536,7 @@ int colorframe_color(std::string& err, ColorFrame* F, const uint16_t* t0, const 
 }
 int colorframe_pair(std::string& err, ColorFrame* F, const PCloud* ref) { score_pair_release(F->pair); F->pair = nullptr; return score_pair_create(err, ref, F->cloud, &F->pair); }
 int colorframe_score(std::string& err, const ColorFrame* F, rbt_color_result* out) { return score_pair_color(err, F->pair, out); }
+int colorframe_score_patches(std::string& err, const ColorFrame* F, int n_patches, rbt_patch_color* out, rbt_color_result* whole) { return score_pair_patches_color(err, F->pair, n_patches, out, whole); }
 
 int pcloud_d1(std::string& err, const PCloud* a, const PCloud* b, int peak, rbt_d1_result* out) {
   rbt_frame_score s;
@@ -703,6 +704,53 @@ int pcloud_score_patches_d2(std::string& err, const PCloud* a, const PCloud* b, 
   return RBT_OK;
 }
 
+// The colour sums per patch on stored distances (csrc/rbt_score.h, "col/patch"): the refusals the two calls share, the label check, k_pc_sums per direction, and the
+// figures - the whole frame's from the sums over the patches, which are exact. timed: events around search (when dist is still to be made) and sums
+static int patch_color_sums(std::string& err, const PCloud* a, const PCloud* b, uint32_t* dist_a, uint32_t* dist_b, bool search, int n_patches, rbt_patch_color* out, rbt_color_result* whole, double* device_ms) {
+  if (whole) memset(whole, 0, sizeof(*whole));
+  if (device_ms) *device_ms = 0;
+  if (n_patches < 1 || n_patches > 65536) { err = "n_patches is 1..65536"; return RBT_ERR_PARAM; }
+  if (!a->rgb.p || !b->rgb.p || a->n_merged > (1 << 21) || b->n_merged > (1 << 21)) { err = "the colour part needs colours on both clouds and at most 2^21 merged points in each"; return RBT_ERR_PARAM; }
+  if (!b->labels.p) { err = "the decoded cloud carries no labels"; return RBT_ERR_PARAM; }
+  memset(out, 0, sizeof(*out) * (size_t)n_patches);
+  const size_t words = (size_t)RBT_PC_WORDS * (size_t)n_patches;
+  DevBuf sums, bad;
+  if (!sums.alloc(8 * words) || !bad.alloc(4)) { err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  if (rbtk::dev_memset(sums.p, 0, 8 * words) | rbtk::dev_memset(bad.p, 0, 4)) { err = "device transfer failed"; return RBT_ERR_NO_DEVICE; }
+  uint32_t is_bad = 0;                       // as pcloud_score_patches: labels a caller gave are checked on the device before any sum is written
+  if (b->label_bound <= 0 || b->label_bound > n_patches) {
+    rbtk::launch_pd_check(b->labels.as<uint32_t>(), b->n, (uint32_t)n_patches, bad.as<uint32_t>());
+    if (rbtk::d2h(&is_bad, bad.p, 4) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  }
+  if (is_bad) { err = "a label of the decoded cloud is not below n_patches"; return RBT_ERR_PARAM; }
+  const RbtScoreCloud A = a->view(), B = b->view();
+  if (device_ms) rbtk::timer_begin(T_COL_DIST);             // as pcloud_score: every call reads its timers before it returns
+  if (search) rbtk::launch_sc_search(&A, &B, dist_a, dist_b);
+  rbtk::launch_pc_sums(&A, &B, b->labels.as<uint32_t>(), dist_a, dist_b, sums.as<unsigned long long>());
+  if (device_ms) rbtk::timer_end(T_COL_DIST);
+  std::vector<uint64_t> hw(words);
+  if (rbtk::d2h(hw.data(), sums.p, 8 * words) || rbtk::dev_sync()) { err = "kernel execution failed"; return RBT_ERR_NO_DEVICE; }
+  if (device_ms) *device_ms = rbtk::timer_ms(T_COL_DIST);
+  rbt_color_result all; memset(&all, 0, sizeof(all));
+  for (int k = 0; k < n_patches; k++) {
+    const uint64_t* w = &hw[(size_t)RBT_PC_WORDS * (size_t)k]; rbt_patch_color* o = &out[k];
+    o->n_ab = (uint32_t)w[RBT_PC_N_AB]; o->n_ba = (uint32_t)w[RBT_PC_N_BA];
+    for (int c = 0; c < 3; c++) { o->sse_ab[c] = w[RBT_PC_SSE_AB + c]; o->sse_ba[c] = w[RBT_PC_SSE_BA + c]; all.sse_ab[c] += o->sse_ab[c]; all.sse_ba[c] += o->sse_ba[c]; }
+    patch_color_finish(o);
+  }
+  if (whole) { all.n_a = a->n_merged; all.n_b = b->n_merged; finish_color(&all); *whole = all; }
+  return RBT_OK;
+}
+// rbt_score_patches_color: the two searches of pcloud_score, then the sums per patch in place of the colour walks
+int pcloud_score_patches_color(std::string& err, const PCloud* a, const PCloud* b, int n_patches, rbt_patch_color* out, rbt_color_result* whole, double* device_ms) {
+  DevBuf dist;
+  if (!dist.alloc(4 * ((size_t)a->n + (size_t)b->n))) { if (whole) memset(whole, 0, sizeof(*whole)); if (device_ms) *device_ms = 0; err = "device allocation failed"; return RBT_ERR_NOMEM; }
+  double ms = 0;
+  const int rc = patch_color_sums(err, a, b, dist.as<uint32_t>(), dist.as<uint32_t>() + a->n, true, n_patches, out, whole, &ms);
+  if (device_ms) *device_ms = ms;
+  return rc;
+}
+
 struct ScorePair { const PCloud* a; const PCloud* b; int na, nb; DevBuf dist; };
 bool score_pair_uses(const ScorePair* p, const PCloud* c) { return p->a == c || p->b == c; }
 void score_pair_release(ScorePair* p) { delete p; }
@@ -731,6 +779,10 @@ int score_pair_color(std::string& err, const ScorePair* p, rbt_color_result* out
   for (int c = 0; c < 3; c++) { out->sse_ab[c] = h[c]; out->sse_ba[c] = h[3 + c]; }
   finish_color(out);
   return RBT_OK;
+}
+// rbt_score_pair_patches_color: the sums per patch on the pair's distances, with the colours and labels of the moment
+int score_pair_patches_color(std::string& err, const ScorePair* p, int n_patches, rbt_patch_color* out, rbt_color_result* whole) {
+  return patch_color_sums(err, p->a, p->b, p->dist.as<uint32_t>(), p->dist.as<uint32_t>() + p->na, false, n_patches, out, whole, nullptr);
 }
 
 // The cloud keeps the normals it had until the new ones are complete: they are written to a buffer of their own, which replaces the old one after the kernels have run.

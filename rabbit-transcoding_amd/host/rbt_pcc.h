@@ -65,6 +65,10 @@ int pcloud_score_patches_d2(std::string& err, const PCloud* a, const PCloud* b, 
 struct ScorePair;
 int score_pair_create(std::string& err, const PCloud* a, const PCloud* b, ScorePair** out);
 int score_pair_color(std::string& err, const ScorePair* p, rbt_color_result* out);
+// Colour per patch of the decoded cloud (csrc/rbt_score.h, "col/patch"): both clouds carry colours, b labels; out holds n_patches entries; whole (the colour part of
+// pcloud_score / score_pair_color for the same clouds) and device_ms may be null. The pair form runs no search.
+int pcloud_score_patches_color(std::string& err, const PCloud* a, const PCloud* b, int n_patches, rbt_patch_color* out, rbt_color_result* whole, double* device_ms);
+int score_pair_patches_color(std::string& err, const ScorePair* p, int n_patches, rbt_patch_color* out, rbt_color_result* whole);
 bool score_pair_uses(const ScorePair* p, const PCloud* c);
 void score_pair_release(ScorePair* p);
 // A frame whose cloud is recoloured per trial (rbt_submit_gof_color): the geometry of a trial does not change with the attribute QP. colorframe_new is the geometry half,
@@ -78,6 +82,8 @@ int colorframe_new(std::string& err, PCloudCache& cache, const rbt_atlas_params*
 int colorframe_color(std::string& err, ColorFrame* f, const uint16_t* d_t0, const uint16_t* d_t1, int attr_bd);
 int colorframe_pair(std::string& err, ColorFrame* f, const PCloud* reference);
 int colorframe_score(std::string& err, const ColorFrame* f, rbt_color_result* out);
+// ... or, in their place, the sums per patch on the same distances (the frame's cloud carries its labels): out holds n_patches entries, whole what colorframe_score returns
+int colorframe_score_patches(std::string& err, const ColorFrame* f, int n_patches, rbt_patch_color* out, rbt_color_result* whole);
 // packed planar 4:2:0 pictures on the device -> their 4:4:4 planes (3 x w x h each): launch_up444 on the current stream
 void colorframe_upconvert(const uint16_t* d_420, int w, int h, int bit_depth, int n_pictures, int filter, uint16_t* d_444);
 const PCloud* colorframe_cloud(const ColorFrame* f);

@@ -500,9 +500,9 @@ struct TargetWalk : QpWalk<TargetTried> { WalkKind kind = WALK_BUDGET; RateGoal 
 // the wait half: the pooled luma planes of the occupancy stream, and for occupancy_rd the per-4x4-unit maps made of them (both live in GofJob::pooled until the job goes)
 struct QualityOcc { const uint16_t* occ = nullptr; size_t in_step = 0; int n = 0, ow = 0, oh = 0; const uint8_t* maps = nullptr; int w4 = 0, h4 = 0; };
 // Floors held patch by patch: the walk of one point-cloud frame (rbt_patch_walk.h) with what its last trial brought - the frame's NAL units, the sums of its two pictures,
-// the payload of the job's kind of figure (PatchPsnr, PatchD1 or PatchD2, the others stay empty), the map it was coded with - and the walks of one entry: per frame R_k in CTB units
+// the payload of the job's kind of figure (PatchPsnr, PatchD1, PatchD2 or PatchColor, the others stay empty), the map it was coded with - and the walks of one entry: per frame R_k in CTB units
 // (the rectangles k_patch_fold reads, on the device from the first round to the last) and the displayed samples of R_k in both pictures
-struct PatchFrame { PatchWalk w; std::vector<uint8_t> stream; QualitySums sums; PatchPsnr psnr; PatchD1 d1; PatchD2 d2; std::vector<int8_t> map; std::vector<int32_t> rects; std::vector<uint64_t> samples; size_t rect_off = 0; };
+struct PatchFrame { PatchWalk w; std::vector<uint8_t> stream; QualitySums sums; PatchPsnr psnr; PatchD1 d1; PatchD2 d2; PatchColor color; std::vector<int8_t> map; std::vector<int32_t> rects; std::vector<uint64_t> samples; size_t rect_off = 0; };
 struct PatchWalks {
   int q = 0, entry = 0, n_passes = 0, l2 = 5, wc = 0, hc = 0, W = 0, H = 0, bit_depth = 8; std::vector<PatchFrame> frames; int32_t* d_rects = nullptr;
   bool settled() const { for (const PatchFrame& f : frames) if (!f.w.settled) return false; return true; }
@@ -550,7 +550,7 @@ template <class Result> struct FloorOut { int qp = 0, q0 = 0, qs = 0, met = 0, n
 // settling trial, and every frame's picks back to back. An entry without a target has no frames: q0, bytes, bit_depth and sums are those of its only encode
 struct PatchOut {
   int q0 = 0, n_passes = 0, wc = 0, hc = 0, bit_depth = 8, region = 0; uint64_t bytes = 0, pictures = 0; std::vector<int8_t> map; QualitySums sums; double cloud_ms = 0;
-  struct Frame { int n_trials = 0, met = 1, n_patches = 0; uint64_t bytes = 0; PatchPsnr psnr; PatchD1 d1; PatchD2 d2; }; std::vector<Frame> frames;
+  struct Frame { int n_trials = 0, met = 1, n_patches = 0; uint64_t bytes = 0; PatchPsnr psnr; PatchD1 d1; PatchD2 d2; PatchColor color; }; std::vector<Frame> frames;
   struct Pick { int qp, met, failed; double figure; }; std::vector<Pick> picks;
 };
 struct FrameFloorOut { int q0 = 0, n_passes = 0, bit_depth = 8; std::vector<rbt_frame_pick> frames; std::vector<rbt_d1_result> d1; double cloud_ms = 0; uint64_t bytes = 0, pictures = 0; QualitySums sums; };
@@ -595,6 +595,11 @@ struct GofJob {
   // D2 floors (rbt_submit_gof_d2, rbt_submit_gof_d2_patches): a job with D1 floors, on the stream or patch by patch, whose figure is D2 - d1 holds the targets (min_d1_mdb:
   // the D2 floor), d1_score asks for the D2 part too, the reference clouds made of the decoded input get normals in d1_setup (normals: one record per entry)
   bool d2 = false; std::vector<NormalsIn> normals; std::vector<FloorOut<rbt_d2_result>> d2out;
+  // colour floors held patch by patch (rbt_submit_gof_color_patches): a job with floors held patch by patch whose figures come from the trial's cloud, as patch_d1 - color
+  // holds the targets' clouds' side as in a job with colour floors (no walk of its own: min_psnr_mdb 0), so the geometry pipelines run first and leave the clouds'
+  // geometry half; every pass is scored by color_score patch by patch (PatchFrame::color), no sums per CTB run
+  bool patch_color = false;
+  bool patch_clouds() const { return patch_d1 || patch_color; }      // the figures per patch come from the trial's cloud
   rbt_stats st; std::string err; double t_all = 0, t_gpu = 0; size_t dev_bytes = 0;
   void color_release(int entry) {        // the frames' volumes go back to the context's cache; their streams have been waited for
     ColorEntry& E = color[entry];
@@ -1036,7 +1041,7 @@ static int round_sums_setup(GofJob& j, int gi) {
   }
   if (int rc = r.sse->upload()) { j.err = rc == RBT_ERR_NOMEM ? "device allocation failed" : "device transfer failed"; return rc; }
   // floors held patch by patch: the luma of the same pairs CTB by CTB into the batch's arena, and per frame of a pass the folds of its rectangles behind the words above
-  if (j.patch.empty() || j.patch_d1) return 0;
+  if (j.patch.empty() || j.patch_clouds()) return 0;
   r.ctbsse.reset(new CtbSseSet()); CtbSseSet& cs = *r.ctbsse;
   size_t pic = 0, ctb_at = 0, fold_at = r.sse->pics.size() * RBT_SSE_WORDS;
   for (size_t e = 0; e < r.cands.size(); e++) {
@@ -1071,7 +1076,7 @@ static int launch_round(GofJob& j, int gi) {
   r.eb.reset(new EncodeBatch()); EncodeBatch& eb = *r.eb;
   int rc = round_fill_batch(j, gi, r.cands, eb);
   if (sums) for (const EncStreamDesc& d : eb.desc) eb.n_sums += (size_t)d.n_frames * RBT_SSE_WORDS;
-  for (size_t e = 0; e < r.cands.size() && !rc && !j.patch_d1; e++) if (r.cands[e].pw >= 0) {      // floors held patch by patch: the folds behind the words per picture, the words per CTB
+  for (size_t e = 0; e < r.cands.size() && !rc && !j.patch_clouds(); e++) if (r.cands[e].pw >= 0) {      // floors held patch by patch: the folds behind the words per picture, the words per CTB
     const PatchWalks& pw = r.pwalks[(size_t)r.cands[e].pw];
     for (int f : r.cands[e].pass.frames) eb.n_sums += (pw.frames[(size_t)f].samples.size() + 2) * RBT_CTBSSE_WORDS;
     eb.n_ctb_words += (size_t)eb.desc[e].n_frames * pw.wc * pw.hc * RBT_CTBSSE_WORDS;
@@ -1377,21 +1382,29 @@ struct ColorLive {
 // The clouds of candidate e of the round in flight - stream `q` of the pipeline's group at one QP - against the entry's references, while the round's arena is alive: the
 // three planes of every reconstructed attribute picture gathered into packed 4:2:0 (the displayed window starts at the picture's origin), one up-conversion for all of
 // them, then frame after frame the colour half (colorframe_color) and the colour walks on the pair's distances. Only the colour sums come back.
-static int color_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, std::vector<rbt_color_result>& out) {
+// A pass over a subset of the frames (desc_subset) codes np of the nf frames, as in d1_score: the gathered pictures go by the coded picture, the ColorFrames by the frame
+// d.pic names; out is in pass order. per_patch (colour floors held patch by patch): per frame of the pass the figures of its patches - the sums per patch in place of
+// the colour walks, out[i] made of them
+static int color_score(GofJob& j, int gi, int q, const EncodeBatch& eb, size_t e, std::vector<rbt_color_result>& out, std::vector<std::vector<rbt_patch_color>>* per_patch = nullptr) {
   const int i = j.groups[gi][q]; ColorEntry& E = j.color[i]; const rbt_atlas_params& a = E.t.atlas;
-  const EncStreamDesc& d = eb.desc[e]; const int W = a.width, H = a.height, mc = a.map_count, nf = E.t.n_frames;
+  const EncStreamDesc& d = eb.desc[e]; const int W = a.width, H = a.height, mc = a.map_count, nf = E.t.n_frames, np = d.n_frames / mc;
   const size_t ys = (size_t)W * H, fs = ys * 3 / 2;
-  if (d.w != W || d.h != H || d.n_frames != mc * nf || (int)E.frames.size() != nf) { j.err = "internal: a colour target does not fit its stream"; return RBT_ERR_PARAM; }
+  if (d.w != W || d.h != H || d.n_frames != mc * np || (d.pic.empty() ? np != nf : d.n_total != mc * nf) || (int)E.frames.size() != nf) { j.err = "internal: a colour target does not fit its stream"; return RBT_ERR_PARAM; }
   DevPlanes attr, up; GatherSet gs;
   if (!attr.alloc(fs * (size_t)d.n_frames) || !up.alloc(3 * ys * (size_t)d.n_frames)) { j.err = "device allocation failed"; return RBT_ERR_NOMEM; }
-  out.assign(nf, rbt_color_result());
+  out.assign(np, rbt_color_result());
+  if (per_patch) per_patch->assign((size_t)np, {});
   rbtk::timer_begin(T_CENSUS);
   for (int k = 0; k < d.n_frames; k++) { const RbtFrame& f = eb.frames[(size_t)eb.stream_first[e] + k]; gather_420(gs, f.out, f.cfg.w, 0, 0, W, H, attr.p + fs * (size_t)k); }
   int rc = gs.launch(j.err);
   if (!rc) colorframe_upconvert(attr.p, W, H, d.bd, d.n_frames, E.t.upsample_filter, up.p);
-  for (int f = 0; f < nf && !rc; f++) {
-    rc = colorframe_color(j.err, E.frames[f], up.p + 3 * ys * (size_t)(mc * f), mc > 1 ? up.p + 3 * ys * (size_t)(mc * f + 1) : nullptr, d.bd);
-    if (!rc) rc = colorframe_score(j.err, E.frames[f], &out[f]);
+  for (int i = 0; i < np && !rc; i++) {
+    const int f = d.pic.empty() ? i : d.pic[(size_t)(mc * i)] / mc;
+    rc = colorframe_color(j.err, E.frames[f], up.p + 3 * ys * (size_t)(mc * i), mc > 1 ? up.p + 3 * ys * (size_t)(mc * i + 1) : nullptr, d.bd);
+    if (!rc && per_patch) {
+      std::vector<rbt_patch_color>& pp = (*per_patch)[(size_t)i]; pp.resize(E.patches[f].size());
+      rc = pp.empty() ? colorframe_score(j.err, E.frames[f], &out[i]) : colorframe_score_patches(j.err, E.frames[f], (int)pp.size(), pp.data(), &out[i]);
+    } else if (!rc) rc = colorframe_score(j.err, E.frames[f], &out[i]);
   }
   return cloud_timed(j, E, rc);
 }
@@ -1408,9 +1421,12 @@ static int finish_round(GofJob& j, int gi) {
       std::vector<rbt_d1_result> whole; std::vector<std::vector<rbt_patch_d1>> clouds;      // D1 floors: the clouds of the frames the pass carried, in pass order, patch by patch
       CloudScoresD2 g2;                                                // D2 floors: the same of the D2 figure
       if (j.patch_d1) if (int rc = d1_score(j, gi, c.q, *r.eb, e, whole, &clouds, j.d2 ? &g2 : nullptr)) return rc;
+      std::vector<rbt_color_result> cwhole; std::vector<std::vector<rbt_patch_color>> cclouds;      // colour floors: the same frames recoloured, patch by patch
+      if (j.patch_color) if (int rc = color_score(j, gi, c.q, *r.eb, e, cwhole, &cclouds)) return rc;
       // the pass's figure source (rbt_patch_walk.h): frame i of the pass from its cloud, or from its fold words, which lie in pass order behind the words per picture
       PatchTrial said;
       auto figures = [&](size_t i, PatchFrame& F) {
+        if (j.patch_color) { patch_trial_color(cclouds[i], cwhole[i], j.color[pw.entry].t.channel, F.w.floor_mdb, said, F.color); return; }
         if (j.patch_d1 && j.d2) { patch_trial_d2(g2.patches[i], g2.whole[i], F.w.floor_mdb, said, F.d2); return; }
         if (j.patch_d1) { patch_trial_d1(clouds[i], whole[i], F.w.floor_mdb, said, F.d1); return; }
         patch_trial_psnr(&r.eb->sums[fold_at], F.samples, region, pw.bit_depth, F.w.floor_mdb, said, F.psnr);
@@ -1542,10 +1558,11 @@ static void fill_patch_results(GofJob& j, int gi) {
     PatchOut& o = j.pout[pw.entry]; std::vector<uint8_t>& out = r.o1[pw.q];
     out.clear(); o.n_passes = pw.n_passes; o.wc = pw.wc; o.hc = pw.hc; o.bit_depth = pw.bit_depth; o.region = j.patch[pw.entry].region;
     if (has_d1(j, pw.entry)) o.cloud_ms = j.d1[pw.entry].cloud_ms;
+    if (has_color(j, pw.entry)) o.cloud_ms = j.color[pw.entry].cloud_ms;
     for (const PatchFrame& F : pw.frames) {
       out.insert(out.end(), F.stream.begin(), F.stream.end()); o.map.insert(o.map.end(), F.map.begin(), F.map.end());
       o.q0 = F.w.q0; o.pictures += 2 * (uint64_t)F.w.n_trials;
-      PatchOut::Frame pf; pf.n_trials = F.w.n_trials; pf.n_patches = (int)F.w.q.size(); pf.bytes = F.stream.size(); pf.psnr = F.psnr; pf.d1 = F.d1; pf.d2 = F.d2;
+      PatchOut::Frame pf; pf.n_trials = F.w.n_trials; pf.n_patches = (int)F.w.q.size(); pf.bytes = F.stream.size(); pf.psnr = F.psnr; pf.d1 = F.d1; pf.d2 = F.d2; pf.color = F.color;
       for (size_t k = 0; k < F.w.q.size(); k++) { pf.met &= F.w.met[k]; o.picks.push_back(PatchOut::Pick{F.w.q[k], F.w.met[k], F.w.failed[k], F.w.figure[k]}); }
       o.frames.push_back(std::move(pf));
       for (int c = 0; c < 3; c++) { o.sums.sse[c] += F.sums.sse[c]; o.sums.samples[c] += F.sums.samples[c]; o.sums.sse_occ[c] += F.sums.sse_occ[c]; o.sums.samples_occ[c] += F.sums.samples_occ[c]; }
@@ -1792,8 +1809,9 @@ GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   j.per_frame = r.per_frame && (r.quality || r.d1);
   j.patch_d1 = r.patch_d1 && r.patch_floors && r.d1;
   j.d2 = r.d2_normals && r.d1 && !j.per_frame;
+  j.patch_color = r.patch_color && r.patch_floors && r.color;
   if (j.d2) j.normals = *r.d2_normals;
-  j.kind = j.d2 ? (j.patch_d1 ? GOF_D2_PATCHES : GOF_D2) : j.patch_d1 ? GOF_D1_PATCHES : r.patch_floors ? GOF_QUALITY_PATCHES : r.color ? GOF_COLOR : r.d1 ? (j.per_frame ? GOF_D1_FRAMES : GOF_D1) : r.quality ? (j.per_frame ? GOF_QUALITY_FRAMES : GOF_QUALITY) : GOF_PLAIN;
+  j.kind = j.patch_color ? GOF_COLOR_PATCHES : j.d2 ? (j.patch_d1 ? GOF_D2_PATCHES : GOF_D2) : j.patch_d1 ? GOF_D1_PATCHES : r.patch_floors ? GOF_QUALITY_PATCHES : r.color ? GOF_COLOR : r.d1 ? (j.per_frame ? GOF_D1_FRAMES : GOF_D1) : r.quality ? (j.per_frame ? GOF_QUALITY_FRAMES : GOF_QUALITY) : GOF_PLAIN;
   struct Footprint { GofJob& j; size_t a0; ~Footprint() { j.dev_bytes = rbtk::dev_alloc_total() - a0; } } footprint{j, rbtk::dev_alloc_total()};
   j.t_all = now_ms(); j.n = n; j.slot = slot; memset(&j.st, 0, sizeof(j.st));
   j.params.assign(p, p + n); j.n_in.assign(r.n_in, r.n_in + n);
@@ -1805,7 +1823,7 @@ GofJob* gof_submit(int slot, int depth, const GofRequest& r) {
   if (r.color) keep_cloud_targets(j, j.color, *r.color);
   if (r.patch_floors) {      // runs as a job with quality floors that are all 0, in each entry's region
     j.patch = *r.patch_floors; j.qocc.assign(n, QualityOcc());
-    j.qtargets.clear();      // (a job with D1 floors held patch by patch has passed keep_cloud_targets above, which filled them; a job with PSNR floors per patch comes here with none)
+    j.qtargets.clear();      // (a job with D1 or colour floors held patch by patch has passed keep_cloud_targets above, which filled them; a job with PSNR floors per patch comes here with none)
     for (int i = 0; i < n; i++) j.qtargets.push_back(rbt_quality_target{(uint32_t)sizeof(rbt_quality_target), 0, j.patch[i].region, 0, 0});
   }
   SubmitPlan s; s.in = r.in; s.p = p; s.gof_rule = r.gof_rule;
@@ -1840,7 +1858,7 @@ struct HandOver {
 // the result arrays whose entries carry arrays of their own, zeroed: before anything is filled in, and again when everything is taken back
 static void zero_results(const GofResults& r, int n) {
   auto zero = [n](auto* a) { if (a) memset(a, 0, sizeof(*a) * (size_t)n); };
-  zero(r.d1); zero(r.color); zero(r.frames); zero(r.patches); zero(r.d1_patches); zero(r.d2); zero(r.d2_patches);
+  zero(r.d1); zero(r.color); zero(r.frames); zero(r.patches); zero(r.d1_patches); zero(r.d2); zero(r.d2_patches); zero(r.color_patches);
 }
 // The public results of a job with cloud targets: per entry its own QP and one encode, or what the rounds left of an entry with a target (FloorOut) with the statistics
 // over its frames
@@ -1861,6 +1879,7 @@ template <class Entry, class Result, class Public, class Stats> static void clou
 static void patch_payload(rbt_patch_floor_result& o, const PatchOut& r, int met, int n_enc) { quality_fill_result(o.sums, -1, -1, -1, met, n_enc, o.bytes, r.sums, r.bit_depth); }
 static void patch_payload(rbt_patch_d1_result& o, const PatchOut& r, int, int) { o.cloud_ms = r.cloud_ms; }
 static void patch_payload(rbt_patch_d2_result& o, const PatchOut& r, int, int) { o.cloud_ms = r.cloud_ms; }
+static void patch_payload(rbt_patch_color_result& o, const PatchOut& r, int, int) { o.cloud_ms = r.cloud_ms; }
 static void patch_payload(rbt_patch_frame& o, rbt_patch_pick* picks, const PatchOut& r, const PatchOut::Frame& f) {
   for (int c = 0; c < 3; c++) o.background[c] = f.psnr.background[c];
   for (size_t k = 0; k < f.psnr.patches.size(); k++) { const PatchSums& s = f.psnr.patches[k]; picks[k].sse = r.region ? s.sse_occ : s.sse; picks[k].samples = r.region ? s.samples_occ : s.samples; }
@@ -1872,6 +1891,10 @@ static void patch_payload(rbt_patch_d1_frame& o, rbt_patch_d1_pick* picks, const
 static void patch_payload(rbt_patch_d2_frame& o, rbt_patch_d2_pick* picks, const PatchOut&, const PatchOut::Frame& f) {
   o.d2 = f.d2.whole;
   for (size_t k = 0; k < f.d2.patches.size(); k++) picks[k].d2 = f.d2.patches[k];
+}
+static void patch_payload(rbt_patch_color_frame& o, rbt_patch_color_pick* picks, const PatchOut&, const PatchOut::Frame& f) {
+  o.color = f.color.whole;
+  for (size_t k = 0; k < f.color.patches.size(); k++) picks[k].color = f.color.patches[k];
 }
 template <class Public> static void patch_results(const GofJob& j, HandOver& h, Public* res, const size_t* n_out) {
   typedef typename std::remove_pointer<decltype(res->frames)>::type Frame; typedef typename std::remove_pointer<decltype(res->picks)>::type Pick;
@@ -1954,6 +1977,7 @@ int gof_wait(GofJob* J, rbt_stats& st_out, std::string& err_out, const GofResult
   if (res.patches) patch_results(j, h, res.patches, n_out);
   if (res.d1_patches) patch_results(j, h, res.d1_patches, n_out);
   if (res.d2_patches) patch_results(j, h, res.d2_patches, n_out);
+  if (res.color_patches) patch_results(j, h, res.color_patches, n_out);
   if (res.d2) cloud_results(j, h, j.d1, j.d2out, res.d2, n_out, [](rbt_d2_floor_result& o, const rbt_d2_result* f) { d1_stats(f, o.n_frames, &o.mean_d2, &o.min_d2); });
   if (d1results) cloud_results(j, h, j.d1, j.d1out, d1results, n_out, [](rbt_d1_floor_result& o, const rbt_d1_result* f) { d1_stats(f, o.n_frames, &o.mean_d1, &o.min_d1); });
   if (cresults) cloud_results(j, h, j.color, j.colorout, cresults, n_out, [](rbt_color_floor_result& o, const rbt_color_result* f) { color_stats(f, o.n_frames, o.mean_psnr, o.min_psnr); });

@@ -41,17 +41,20 @@ struct GofRequest {
   // D2 floors (rbt_submit_gof_d2; with patch_d1: rbt_submit_gof_d2_patches): the request is that of the D1 kind - d1 carries the targets as D1 targets, min_d1_mdb holding
   // the D2 floor - and the figure is D2; one record per entry for the normals of the reference clouds made of the decoded input
   const std::vector<NormalsIn>* d2_normals = nullptr;
+  // colour floors held patch by patch (rbt_submit_gof_color_patches): patch_floors carries the walks' side of the targets and color their clouds' side (atlas, patch lists,
+  // references, channel, filter, transfer; min_psnr_mdb 0: no walk of its own)
+  bool patch_color = false;
 };
 // Where a job's outcome goes: a stream per entry, and of the result arrays - one per entry each - the one of the job's kind; n_flat: nullptr, or the decoded pictures with flat chroma
 struct GofResults {
   uint8_t** out = nullptr; size_t* n_out = nullptr; int* n_flat = nullptr;
   rbt_rate_result* rate = nullptr; rbt_quality_result* quality = nullptr; rbt_d1_floor_result* d1 = nullptr; rbt_color_floor_result* color = nullptr; rbt_frame_floor_result* frames = nullptr; rbt_patch_floor_result* patches = nullptr; rbt_patch_d1_result* d1_patches = nullptr;
-  rbt_d2_floor_result* d2 = nullptr; rbt_patch_d2_result* d2_patches = nullptr;
+  rbt_d2_floor_result* d2 = nullptr; rbt_patch_d2_result* d2_patches = nullptr; rbt_patch_color_result* color_patches = nullptr;
 };
 GofJob* gof_submit(int slot, int depth, const GofRequest& r);
 int gof_wait(GofJob* j, rbt_stats& st, std::string& err, const GofResults& r);   // consumes the job
 // which submit made the job, in the order the wait half tells a mismatch (rbt_api.cpp wait): the lower of two kinds that differ is the one the message names
-enum GofKind { GOF_PLAIN, GOF_QUALITY, GOF_D1, GOF_COLOR, GOF_D1_FRAMES, GOF_QUALITY_FRAMES, GOF_QUALITY_PATCHES, GOF_D1_PATCHES, GOF_D2, GOF_D2_PATCHES };   // GOF_PLAIN: constant QPs, QP lists, QP maps and byte budgets
+enum GofKind { GOF_PLAIN, GOF_QUALITY, GOF_D1, GOF_COLOR, GOF_D1_FRAMES, GOF_QUALITY_FRAMES, GOF_QUALITY_PATCHES, GOF_D1_PATCHES, GOF_D2, GOF_D2_PATCHES, GOF_COLOR_PATCHES };   // GOF_PLAIN: constant QPs, QP lists, QP maps and byte budgets
 GofKind gof_kind(const GofJob* j);
 int gof_refused(const GofJob* j, std::string& err);   // != 0: the job's plan was refused before anything was built or enqueued (the code; the reason in err)
 void gof_abandon(GofJob* j);
